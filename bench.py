@@ -14,6 +14,10 @@ a second timed region of the same run; aggregated over ranks.
 
   python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run, one rank per GPU)
 
+A plain run times the headline region alone: set-up, W warm-up steps, K timed steps, the result line.  --full adds everything else
+(the batched region, phase and kernel rooflines, config.c4 / c2 / c5 / c3_solve / small_newton, CPU baselines).  --dump-outputs DIR
+writes what the last timed step computed (rank 0) as DIR/<name>.npy.
+
 Multi-GPU: problems are independent => ranks share nothing on the data path (a single system is "replicas only", the batched path
 is sharded block-contiguously: weak scaling); torch.distributed (RCCL) is used for the barrier, the max-over-ranks time and the
 post-round gather of status rows / counters.  Prints ONE JSON line on rank 0.
@@ -438,6 +442,20 @@ def cpu_baseline(shape, name="C3", staged=None, samples=3, full=False):
                 B0_ii_reference_refactorisation=b0ii, B1_lapack_all_cores=b1, B2_julia_reference=b2)
 
 
+def step_outputs(h, info):
+    """what a caller of the timed path receives from its last step: the handle's step, residual and line-search candidate, and the step's
+    record of calipso_hip_newton_steps [status, step_size, step_size_cone_slack_dual, refinement_rounds, factorizations, merit_candidate,
+    violation_candidate]"""
+    rec = [info[k] for k in ("status", "step_size", "step_size_cone_slack_dual", "refinement_rounds", "factorizations", "merit_candidate", "violation_candidate")]
+    return {"step": h.data("step").all, "residual": h.data("residual").all, "candidate": h.get("candidate", h.N), "step_record": np.array(rec, dtype=np.float64)}
+
+
+def write_outputs(d, outputs):
+    os.makedirs(d, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def free_port():
     import socket
     with socket.socket() as sk:
@@ -464,7 +482,8 @@ def spawn_ranks(args):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     cmd = spawn_command(args.gpus, sys.argv[1:])
     sys.stdout.flush(); sys.stderr.flush()
-    os.execve(sys.executable, cmd, env)
+    import subprocess
+    sys.exit(subprocess.call(cmd, env=env))
 
 
 class Exchange:
@@ -522,14 +541,16 @@ class Workload:
     """B independent instances of one configuration on this rank's GPU.  Instance 0 is the rank's single system (headline region); the B
     instances form B / G groups of G (the members of a group are stepped in lockstep through the same launches), `lanes` groups in flight."""
 
-    def __init__(self, pkg, pr, name, rank, world, device, B, G, lanes, dense_structure=False, no_stage_parallel=False, no_stage_blocks=False, dense_buffers=False):
+    def __init__(self, pkg, pr, name, rank, world, device, B, G, lanes, dense_structure=False, no_stage_parallel=False, no_stage_blocks=False, dense_buffers=False,
+                 shard=None):
         from calipso_jl_amd.batch import BatchSolver, shard_range
         self.pkg, self.name, self.B, self.G, self.world = pkg, name, max(0, B), max(1, G), world
         self.staged = STAGED.get(name)
         self.shape = staged_shape(self.staged) if self.staged else CONFIGS[name]
         assert self.B % self.G == 0, "--batch must be a multiple of --group"
         nb = max(self.B, 1)
-        self.ids = list(shard_range(world * nb, rank, world))      # block-contiguous problem ids of this rank
+        # block-contiguous problem ids of this rank; `shard`: the instances per rank the ids are dealt out for (a plain run creates only instance 0 of the default batch)
+        self.ids = list(shard_range(world * max(nb if shard is None else shard, 1), rank, world))
         # creation order: the first member of every unit first, so that the streams that carry the launches get distinct priority
         # classes (handles take class = creation index mod 3, calipso_hip_create)
         G_ = self.G
@@ -640,6 +661,10 @@ def main():
     ap.add_argument("--c4-all", type=int, default=256, help="config.c4: also time ALL the problems of BASELINE config 4 (256) on this one GPU for the stage-structured variant\n"
                     "(groups of up to 128 members, two in flight); 0 skips it")
     ap.add_argument("--c4-configs", default=None, help="the configurations of the config.c4 block (default: C4,C4T with --config C3, none otherwise)")
+    ap.add_argument("--full", action="store_true", help="also measure everything beyond the headline: the batched region, phase and kernel rooflines, config.c4 / c2 / c5 /\n"
+                    "c3_solve / small_newton and the CPU baselines (a plain run times the headline region alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step computed (rank 0; the step, the residual,\n"
+                    "the line-search candidate and the step's record) as DIR/<name>.npy, float64")
     ap.add_argument("--dist-backend", default="nccl", help="testing only: gloo lets two ranks share one GPU")
     ap.add_argument("--force-device", type=int, default=-1, help="testing only: every rank uses this device ordinal")
     ap.add_argument("--spawn-check", action="store_true", help="testing only (runs without a GPU): start the ranks, all-gather their ids and print\n"
@@ -705,7 +730,8 @@ def main():
     from __graft_entry__ import load_package
     pkg = load_package()
     import problems as pr
-    exchange = Exchange(pkg, dist, args.dist_backend, rank, world, local_rank)
+    batched_region = args.full or args.no_single           # the batched region is the headline under --no-single and a --full figure otherwise
+    exchange = Exchange(pkg, dist, args.dist_backend, rank, world, local_rank) if batched_region else None
 
     def barrier(wl):
         if dist is not None:
@@ -777,7 +803,8 @@ def main():
         return dict(schur=sch, ldl=ldl, chain=chain, sd=sd, total=tot, cone=cw, matvec=mv, kt=[float(v) for v in kt_])
 
     # =================================================================== headline workload ======================================
-    wl = Workload(pkg, pr, args.config, rank, world, local_rank, args.batch, args.group, args.lanes, args.dense_structure, args.no_stage_parallel, args.no_stage_blocks, args.dense_buffers)
+    wl = Workload(pkg, pr, args.config, rank, world, local_rank, args.batch if batched_region else 0, args.group, args.lanes, args.dense_structure, args.no_stage_parallel,
+                  args.no_stage_blocks, args.dense_buffers, shard=args.batch)
     B, G = wl.B, wl.G
     shape, staged = wl.shape, wl.staged
     # "opt.solve_block" (a tuning knob of the device factorisation, not an option of the reference): the widest diagonal block of L whose inverse
@@ -797,14 +824,17 @@ def main():
     for _ in range(args.warmup):
         if not args.no_single:
             wl.single.newton_step(advance=False)
-    peak_measured = pkg.mfma_f64_peak(local_rank) if rank == 0 else None
+    peak_measured = pkg.mfma_f64_peak(local_rank) if rank == 0 and args.full else None
 
     # ---- timed region 1 (headline): K sequential Newton steps of ONE system per GPU ------------------------------------------------
     K = args.steps
     single_elapsed, single_infos, ph = None, [], None
     if not args.no_single:
         single_elapsed, single_infos = run_single(wl, K)
-        ph = single_phases(wl, max(3, min(K, 10)))
+        if args.dump_outputs and rank == 0:
+            write_outputs(args.dump_outputs, step_outputs(wl.single, single_infos[-1]))
+        if args.full:
+            ph = single_phases(wl, max(3, min(K, 10)))
 
     # ---- warm-up of the batched pass; unit 0 alone (one group of G instances): its launches have the device to themselves => clean per-launch figures --
     alone, alone_chain, unit_rate = [], [], None
@@ -812,21 +842,24 @@ def main():
         solve_block(wl.solvers if G > 1 else [], int(os.environ.get("CALIPSO_BENCH_GROUP_SOLVE_BLOCK", "512")), int(os.environ.get("CALIPSO_BENCH_GROUP_SOLVE_WFORM", "0")))
         for _ in range(args.warmup):
             wl.batched_pass()
-        barrier(wl)
-        n_alone = max(3, min(10, K))
-        ts = time.perf_counter()
-        for _ in range(n_alone):
-            wl.units[0].newton_step(advance=False)
-            alone.append(wl.units[0].phase_times())
-            alone_chain.append(wl.solvers[0].kernel_times()[0])
-        wl.units[0].synchronize()
-        unit_rate = G * n_alone / (time.perf_counter() - ts)
+        if args.full:
+            barrier(wl)
+            n_alone = max(3, min(10, K))
+            ts = time.perf_counter()
+            for _ in range(n_alone):
+                wl.units[0].newton_step(advance=False)
+                alone.append(wl.units[0].phase_times())
+                alone_chain.append(wl.solvers[0].kernel_times()[0])
+            wl.units[0].synchronize()
+            unit_rate = G * n_alone / (time.perf_counter() - ts)
 
     # ---- timed region 2 (batched): P passes over all B instances of the rank ------------------------------------------------------
     P = max(1, args.batched_passes)
     batched_elapsed, infos, sch_conc = None, None, []
     if wl.batch is not None:
         batched_elapsed, infos, sch_conc = run_batched(wl, P, args.lockstep_passes)
+        if args.no_single and args.dump_outputs and rank == 0:      # (the batched rate is the headline: instance 0's last pass)
+            write_outputs(args.dump_outputs, step_outputs(wl.solvers[0], infos[0]))
 
     info = single_infos[-1] if single_infos else infos[0]
     nx, ne, n_nn, n_soc, dim = shape
@@ -838,125 +871,127 @@ def main():
     else:                                                     # --no-single (profiling): the batched rate stands in
         value, elapsed, steps_timed = world * B * P / batched_elapsed, batched_elapsed, P
 
-    # ---- roofline of the DOMINANT kernel = the kernel with the largest share of the headline step -----------------------------------
-    # Two candidates carry matrix-core work (everything else is a few microseconds per launch): the panel-step kernel of the LDL^T of S
-    # (k_ldl_step: one launch per 64 pivots; its first workgroup carries the sequential pivot chain) and the Schur-complement kernel k_schur.
-    # Both are timed live with HIP events on the handle's stream (calipso_hip_kernel_times / phase_times) over the launches of the TIMED
-    # region; whichever takes the larger share of the step is `roofline`, the other goes to roofline.secondary.  Algorithmic flops:
-    #   k_ldl_step  nx^3 / 3 per factorisation (a dense LDL^T of the nx x nx Schur complement), spread over its NP / 64 - 1 launches
-    #   k_schur     multiply-adds of the lower triangle of S incl. diagonal: per constraint row with w non-zero columns w (w + 1); dense: nx (nx + 1)
-    prob0 = wl.prob0
-    wrow = np.concatenate([np.count_nonzero(prob0.A, axis=1), np.count_nonzero(prob0.G, axis=1)]).astype(np.float64)
-    flops_schur = float(np.sum(wrow * (wrow + 1.0)))
-    flops_ldl = nx ** 3 / 3.0
-    n_ldl_launch = max(1, NP // 64 - 1)
-    pmc = {}
-    for name in ("r06_pmc_summary.json", "r05_pmc_summary.json", "r04_pmc_summary.json", "r03_pmc_summary.json", "r02_pmc_summary.json"):
-        try:
-            pmc = json.load(open(os.path.join(ROOT, "profiles", name)))
-            pmc["_file"] = "profiles/" + name
-            break
-        except Exception:
-            pmc = {}
+    roof, cfg_phases = None, {}
+    if args.full:
+        # ---- roofline of the DOMINANT kernel = the kernel with the largest share of the headline step -----------------------------------
+        # Two candidates carry matrix-core work (everything else is a few microseconds per launch): the panel-step kernel of the LDL^T of S
+        # (k_ldl_step: one launch per 64 pivots; its first workgroup carries the sequential pivot chain) and the Schur-complement kernel k_schur.
+        # Both are timed live with HIP events on the handle's stream (calipso_hip_kernel_times / phase_times) over the launches of the TIMED
+        # region; whichever takes the larger share of the step is `roofline`, the other goes to roofline.secondary.  Algorithmic flops:
+        #   k_ldl_step  nx^3 / 3 per factorisation (a dense LDL^T of the nx x nx Schur complement), spread over its NP / 64 - 1 launches
+        #   k_schur     multiply-adds of the lower triangle of S incl. diagonal: per constraint row with w non-zero columns w (w + 1); dense: nx (nx + 1)
+        prob0 = wl.prob0
+        wrow = np.concatenate([np.count_nonzero(prob0.A, axis=1), np.count_nonzero(prob0.G, axis=1)]).astype(np.float64)
+        flops_schur = float(np.sum(wrow * (wrow + 1.0)))
+        flops_ldl = nx ** 3 / 3.0
+        n_ldl_launch = max(1, NP // 64 - 1)
+        pmc = {}
+        for name in ("r06_pmc_summary.json", "r05_pmc_summary.json", "r04_pmc_summary.json", "r03_pmc_summary.json", "r02_pmc_summary.json"):
+            try:
+                pmc = json.load(open(os.path.join(ROOT, "profiles", name)))
+                pmc["_file"] = "profiles/" + name
+                break
+            except Exception:
+                pmc = {}
 
-    def pmc_traffic(section, kernel_prefix, scale=1.0):
-        """HBM bytes per launch (PMC passes, profiles/) of the kernel VARIANT that carries the section's work: among the counter rows whose name starts with
-        the prefix, the one with the most bytes over its sampled launches (a group's factorisation runs k_ldl_step<2> with a few <1> launches beside it, one system <0>)"""
-        if args.config != "C3":
-            return None
-        best, best_total = None, -1.0
-        for kname, e in pmc.get(section, {}).items():
-            if kname.startswith(kernel_prefix) and "hbm_bytes_per_launch" in e:
-                total = e["hbm_bytes_per_launch"] * max(1, e.get("launches_sampled", 1))
-                if total > best_total:
-                    best, best_total = e, total
-        return best["hbm_bytes_per_launch"] * scale if best else None
+        def pmc_traffic(section, kernel_prefix, scale=1.0):
+            """HBM bytes per launch (PMC passes, profiles/) of the kernel VARIANT that carries the section's work: among the counter rows whose name starts with
+            the prefix, the one with the most bytes over its sampled launches (a group's factorisation runs k_ldl_step<2> with a few <1> launches beside it, one system <0>)"""
+            if args.config != "C3":
+                return None
+            best, best_total = None, -1.0
+            for kname, e in pmc.get(section, {}).items():
+                if kname.startswith(kernel_prefix) and "hbm_bytes_per_launch" in e:
+                    total = e["hbm_bytes_per_launch"] * max(1, e.get("launches_sampled", 1))
+                    if total > best_total:
+                        best, best_total = e, total
+            return best["hbm_bytes_per_launch"] * scale if best else None
 
-    def entry(kernel, flops_per_factor, launches, ms_total, inst, section, prefix, step_ms):
-        ms_launch = ms_total / launches
-        e = {"kernel": kernel, "bound": "mfma", "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-             "achieved": inst * flops_per_factor / (ms_total * 1e-3) * 1e-12, "flops_per_launch": inst * flops_per_factor / launches,
-             "launches_per_step": launches, "instances_per_launch": inst, "avg_launch_ms": ms_launch, "ms_per_step": ms_total,
-             "share_of_step": ms_total / step_ms if step_ms else None, "traffic": pmc_traffic(section, prefix)}
-        e["frac"] = e["achieved"] / FP64_MFMA_PEAK_TFLOPS
-        return e
-    K_LDL = "k_ldl_step (LDL^T of the nx x nx Schur complement S, one launch per 64 pivots: trailing update on v_mfma_f64_16x16x4_f64, its first workgroup factors the next diagonal block)"
-    K_LFAC = ("k_lfac (one dense system alone: the left-looking schedule of csrc/lfac.hip — every launch = the pivot chain's workgroup for one 64-pivot panel + 255 workers on "
-              "slices of S = Lxx + eps*I + omega*gx'gx + hx'(Omega hx) and on the deferred trailing updates, v_mfma_f64_16x16x4_f64; flops = Schur complement + nx^3/3)")
-    K_SCH = "k_schur (S = Lxx + eps*I + omega*gx'gx + hx'(Omega hx), v_mfma_f64_16x16x4_f64)"
-    cands = []
-    if ph is not None:
-        step_ms = float(np.mean(ph["total"]))
-        kt_single = ph["kt"]
-        if kt_single[6] > 0:      # the Schur complement's products are slices of the panel launches: ONE kernel carries both (calipso_hip_kernel_times [6])
-            cands = [entry(K_LFAC, flops_schur + flops_ldl, max(1, int(kt_single[1])), float(np.mean(ph["chain"])), 1, "single", "calipso::k_lfac", step_ms)]
-            cands[0]["flops_schur"] = flops_schur; cands[0]["flops_ldl"] = flops_ldl
-            cands[0]["schedule_buffers_bytes"] = kt_single[7]
-        else:
-            cands = [entry(K_LDL, flops_ldl, n_ldl_launch, float(np.mean(ph["chain"])), 1, "single", "calipso::k_ldl_step", step_ms),
-                     entry(K_SCH, flops_schur, 1, float(np.mean(ph["schur"])), 1, "single", "calipso::k_schur", step_ms)]
-    grp = None
-    if alone:
-        al = np.mean(np.asarray(alone), axis=0)
-        grp = [entry(K_LDL, flops_ldl, n_ldl_launch, float(np.mean(alone_chain)), G, "group", "calipso::k_ldl_step", float(al[6])),
-               entry(K_SCH, flops_schur, 1, float(al[7]), G, "group", "calipso::k_schur", float(al[6]))]
-        grp[1]["avg_launch_ms_with_all_units_in_flight"] = float(np.mean(sch_conc)) if sch_conc else None
-        if not cands:
-            cands = grp
-    if staged is not None:                                    # stage-structured: the LDL^T is the multifrontal path, k_ldl_step does not run
-        cands = [c for c in cands if c["ms_per_step"] > 0] or cands
-        for c in cands + (grp or []):
-            if c["kernel"] == K_LDL:                          # (the dense nx^3 / 3 does not price a factorisation over the stage tree: time only)
-                c.update(kernel="multifrontal LDL^T of S over the nested-dissection tree of the stages (sparse.hip), timed as a whole", achieved=None, frac=None,
-                         flops_per_launch=None, launches_per_step=None, avg_launch_ms=None)
-    cands.sort(key=lambda c: -c["ms_per_step"])
-    roof = dict(cands[0])
-    roof["secondary"] = cands[1:]
-    if ph is not None and np.mean(ph["matvec"]) > 0:
-        # the HBM-bound side of the step: the mat-vec kernel of a refinement residual ([gx; hx]' times two vectors + Lxx times one, one pass over both), ONE
-        # launch timed live per step with HIP events on the handle's stream (calipso_hip_kernel_times [4]); algorithmic bytes = the two blocks read once
-        mv_ms = float(np.mean(ph["matvec"]))
-        mv_bytes = 8.0 * (m * nx + nx * nx)
-        roof["secondary"].append({"kernel": "k_gemv_t2_and_n (refinement residual: [gx; hx]'(v_yz, Omega b_m) and Lxx v_x in one pass)", "bound": "hbm", "peak": 8000.0, "unit": "GB/s",
-                                  "achieved": mv_bytes / (mv_ms * 1e-3) * 1e-9, "frac": mv_bytes / (mv_ms * 1e-3) * 1e-9 / 8000.0, "bytes_per_launch": mv_bytes, "avg_launch_ms": mv_ms,
-                                  "launches_per_step": 1 + int(single_infos[-1]["refinement_rounds"]), "traffic": pmc_traffic("single", "calipso::k_gemv_t2_and_n")})
-    roof["dominance"] = ("the kernel with the largest share of the headline step among all kernels (profiles/r05_kernel_stats_single.csv lists every kernel); "
-                         "HIP-event durations of this run")
-    roof["peak_measured"] = peak_measured
-    roof["peak_note"] = ("peak = datasheet fp64 matrix rate (not tabulated in MI355X_MICROARCH.md); peak_measured = calipso_hip_mfma_f64_peak in this run; "
-                         "traffic = (2 FETCH_SIZE + WRITE_SIZE) KiB of %s (separate rocprofv3 --pmc passes of the same command), null when no counter file covers the kernel" % pmc.get("_file", "profiles/"))
-    if grp:
-        roof["group_launch"] = {g["kernel"].split(" ")[0]: g for g in grp}
+        def entry(kernel, flops_per_factor, launches, ms_total, inst, section, prefix, step_ms):
+            ms_launch = ms_total / launches
+            e = {"kernel": kernel, "bound": "mfma", "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                 "achieved": inst * flops_per_factor / (ms_total * 1e-3) * 1e-12, "flops_per_launch": inst * flops_per_factor / launches,
+                 "launches_per_step": launches, "instances_per_launch": inst, "avg_launch_ms": ms_launch, "ms_per_step": ms_total,
+                 "share_of_step": ms_total / step_ms if step_ms else None, "traffic": pmc_traffic(section, prefix)}
+            e["frac"] = e["achieved"] / FP64_MFMA_PEAK_TFLOPS
+            return e
+        K_LDL = "k_ldl_step (LDL^T of the nx x nx Schur complement S, one launch per 64 pivots: trailing update on v_mfma_f64_16x16x4_f64, its first workgroup factors the next diagonal block)"
+        K_LFAC = ("k_lfac (one dense system alone: the left-looking schedule of csrc/lfac.hip — every launch = the pivot chain's workgroup for one 64-pivot panel + 255 workers on "
+                  "slices of S = Lxx + eps*I + omega*gx'gx + hx'(Omega hx) and on the deferred trailing updates, v_mfma_f64_16x16x4_f64; flops = Schur complement + nx^3/3)")
+        K_SCH = "k_schur (S = Lxx + eps*I + omega*gx'gx + hx'(Omega hx), v_mfma_f64_16x16x4_f64)"
+        cands = []
+        if ph is not None:
+            step_ms = float(np.mean(ph["total"]))
+            kt_single = ph["kt"]
+            if kt_single[6] > 0:      # the Schur complement's products are slices of the panel launches: ONE kernel carries both (calipso_hip_kernel_times [6])
+                cands = [entry(K_LFAC, flops_schur + flops_ldl, max(1, int(kt_single[1])), float(np.mean(ph["chain"])), 1, "single", "calipso::k_lfac", step_ms)]
+                cands[0]["flops_schur"] = flops_schur; cands[0]["flops_ldl"] = flops_ldl
+                cands[0]["schedule_buffers_bytes"] = kt_single[7]
+            else:
+                cands = [entry(K_LDL, flops_ldl, n_ldl_launch, float(np.mean(ph["chain"])), 1, "single", "calipso::k_ldl_step", step_ms),
+                         entry(K_SCH, flops_schur, 1, float(np.mean(ph["schur"])), 1, "single", "calipso::k_schur", step_ms)]
+        grp = None
+        if alone:
+            al = np.mean(np.asarray(alone), axis=0)
+            grp = [entry(K_LDL, flops_ldl, n_ldl_launch, float(np.mean(alone_chain)), G, "group", "calipso::k_ldl_step", float(al[6])),
+                   entry(K_SCH, flops_schur, 1, float(al[7]), G, "group", "calipso::k_schur", float(al[6]))]
+            grp[1]["avg_launch_ms_with_all_units_in_flight"] = float(np.mean(sch_conc)) if sch_conc else None
+            if not cands:
+                cands = grp
+        if staged is not None:                                    # stage-structured: the LDL^T is the multifrontal path, k_ldl_step does not run
+            cands = [c for c in cands if c["ms_per_step"] > 0] or cands
+            for c in cands + (grp or []):
+                if c["kernel"] == K_LDL:                          # (the dense nx^3 / 3 does not price a factorisation over the stage tree: time only)
+                    c.update(kernel="multifrontal LDL^T of S over the nested-dissection tree of the stages (sparse.hip), timed as a whole", achieved=None, frac=None,
+                             flops_per_launch=None, launches_per_step=None, avg_launch_ms=None)
+        cands.sort(key=lambda c: -c["ms_per_step"])
+        roof = dict(cands[0])
+        roof["secondary"] = cands[1:]
+        if ph is not None and np.mean(ph["matvec"]) > 0:
+            # the HBM-bound side of the step: the mat-vec kernel of a refinement residual ([gx; hx]' times two vectors + Lxx times one, one pass over both), ONE
+            # launch timed live per step with HIP events on the handle's stream (calipso_hip_kernel_times [4]); algorithmic bytes = the two blocks read once
+            mv_ms = float(np.mean(ph["matvec"]))
+            mv_bytes = 8.0 * (m * nx + nx * nx)
+            roof["secondary"].append({"kernel": "k_gemv_t2_and_n (refinement residual: [gx; hx]'(v_yz, Omega b_m) and Lxx v_x in one pass)", "bound": "hbm", "peak": 8000.0, "unit": "GB/s",
+                                      "achieved": mv_bytes / (mv_ms * 1e-3) * 1e-9, "frac": mv_bytes / (mv_ms * 1e-3) * 1e-9 / 8000.0, "bytes_per_launch": mv_bytes, "avg_launch_ms": mv_ms,
+                                      "launches_per_step": 1 + int(single_infos[-1]["refinement_rounds"]), "traffic": pmc_traffic("single", "calipso::k_gemv_t2_and_n")})
+        roof["dominance"] = ("the kernel with the largest share of the headline step among all kernels (profiles/r05_kernel_stats_single.csv lists every kernel); "
+                             "HIP-event durations of this run")
+        roof["peak_measured"] = peak_measured
+        roof["peak_note"] = ("peak = datasheet fp64 matrix rate; peak_measured = calipso_hip_mfma_f64_peak in this run; "
+                             "traffic = (2 FETCH_SIZE + WRITE_SIZE) KiB of %s (separate rocprofv3 --pmc passes of the same command), null when no counter file covers the kernel" % pmc.get("_file", "profiles/"))
+        if grp:
+            roof["group_launch"] = {g["kernel"].split(" ")[0]: g for g in grp}
 
-    # per-phase rooflines: SURVEY.md 8(d)'s algorithmic figures AND the bytes / flops the constraint-first path really executes
-    n_cond = nx + m
-    n_r = int(info["refinement_rounds"])
+        # per-phase rooflines: SURVEY.md 8(d)'s algorithmic figures AND the bytes / flops the constraint-first path really executes
+        n_cond = nx + m
+        n_r = int(info["refinement_rounds"])
 
-    def phases(al, inst):
-        t_factor = float(al[1] + al[7] + al[3])                       # cone pivots + Schur complement + LDL^T of S
-        t_solve = float(al[2]) - t_factor                              # condensed solves + recovery + refinement residuals
-        f_survey = inst * n_cond ** 3 / 3.0                            # dense n^3/3 of 8(d)
-        f_exec = inst * (flops_schur + flops_ldl)                      # what the constraint-first order executes
-        b_survey = inst * (1 + n_r) * (2 * 8 * n_cond * (n_cond + 1) / 2 + 8.0 * (nx * nx + ne * nx + nc * nx))
-        # executed: every solve reads the factor of S twice (L forward, L' backward: NP^2 / 2 doubles each); [gx; hx] is passed over
-        # 2 (first solve) + n_r (correction solves) + n_r + 1 (refinement residuals) times, Lxx n_r + 1 times
-        b_exec = inst * 8.0 * ((1 + n_r) * NP * NP + (2 * n_r + 3) * m * nx + (n_r + 1) * nx * nx)
-        return {"instances": inst, "whole_step_ms": float(al[6]),
-                "factor": {"ms": t_factor, "schur_ms": float(al[7]), "ldl_ms": float(al[3]), "bound": "mfma", "flops_survey_n3_over_3": f_survey,
-                           "flops_executed": f_exec, "achieved_TFLOPs_survey": f_survey / t_factor * 1e-9,
-                           "achieved_TFLOPs_executed": f_exec / t_factor * 1e-9, "frac_executed": f_exec / t_factor * 1e-9 / FP64_MFMA_PEAK_TFLOPS},
-                "solve_and_refine": {"ms": t_solve, "bound": "hbm", "solves": 1 + n_r, "bytes_executed": b_exec, "achieved_GBs_executed": b_exec / t_solve * 1e-6,
-                                     "frac_executed": b_exec / t_solve * 1e-6 / 8000.0, "bytes_survey": b_survey,
-                                     "note": "priced with the bytes the executed path moves (factor of the NP x NP Schur complement, [gx; hx], Lxx); bytes_survey = the "
-                                             "n = nx + ne + nc triangular-solve figure of SURVEY 8(d), kept for reference only"}}
-    cfg_phases = {}
-    if ph is not None:
-        al1 = np.zeros(9); al1[7] = np.mean(ph["schur"]); al1[3] = np.mean(ph["ldl"]); al1[2] = np.mean(ph["sd"]); al1[6] = np.mean(ph["total"])
-        al1[1] = np.mean(ph["cone"])      # (read per step inside the timed region: afterwards the handle has been the base of a group and holds the group's figure)
-        cfg_phases["single_system"] = phases(al1, 1)
-        cfg_phases["single_system"]["launches_per_step"] = wl.single.kernel_times()[1]
-    if alone:
-        cfg_phases["one_group_alone"] = phases(np.mean(np.asarray(alone), axis=0), G)
+        def phases(al, inst):
+            t_factor = float(al[1] + al[7] + al[3])                       # cone pivots + Schur complement + LDL^T of S
+            t_solve = float(al[2]) - t_factor                              # condensed solves + recovery + refinement residuals
+            f_survey = inst * n_cond ** 3 / 3.0                            # dense n^3/3 of 8(d)
+            f_exec = inst * (flops_schur + flops_ldl)                      # what the constraint-first order executes
+            b_survey = inst * (1 + n_r) * (2 * 8 * n_cond * (n_cond + 1) / 2 + 8.0 * (nx * nx + ne * nx + nc * nx))
+            # executed: every solve reads the factor of S twice (L forward, L' backward: NP^2 / 2 doubles each); [gx; hx] is passed over
+            # 2 (first solve) + n_r (correction solves) + n_r + 1 (refinement residuals) times, Lxx n_r + 1 times
+            b_exec = inst * 8.0 * ((1 + n_r) * NP * NP + (2 * n_r + 3) * m * nx + (n_r + 1) * nx * nx)
+            return {"instances": inst, "whole_step_ms": float(al[6]),
+                    "factor": {"ms": t_factor, "schur_ms": float(al[7]), "ldl_ms": float(al[3]), "bound": "mfma", "flops_survey_n3_over_3": f_survey,
+                               "flops_executed": f_exec, "achieved_TFLOPs_survey": f_survey / t_factor * 1e-9,
+                               "achieved_TFLOPs_executed": f_exec / t_factor * 1e-9, "frac_executed": f_exec / t_factor * 1e-9 / FP64_MFMA_PEAK_TFLOPS},
+                    "solve_and_refine": {"ms": t_solve, "bound": "hbm", "solves": 1 + n_r, "bytes_executed": b_exec, "achieved_GBs_executed": b_exec / t_solve * 1e-6,
+                                         "frac_executed": b_exec / t_solve * 1e-6 / 8000.0, "bytes_survey": b_survey,
+                                         "note": "priced with the bytes the executed path moves (factor of the NP x NP Schur complement, [gx; hx], Lxx); bytes_survey = the "
+                                                 "n = nx + ne + nc triangular-solve figure of SURVEY 8(d), kept for reference only"}}
+        cfg_phases = {}
+        if ph is not None:
+            al1 = np.zeros(9); al1[7] = np.mean(ph["schur"]); al1[3] = np.mean(ph["ldl"]); al1[2] = np.mean(ph["sd"]); al1[6] = np.mean(ph["total"])
+            al1[1] = np.mean(ph["cone"])      # (read per step inside the timed region: afterwards the handle has been the base of a group and holds the group's figure)
+            cfg_phases["single_system"] = phases(al1, 1)
+            cfg_phases["single_system"]["launches_per_step"] = wl.single.kernel_times()[1]
+        if alone:
+            cfg_phases["one_group_alone"] = phases(np.mean(np.asarray(alone), axis=0), G)
 
     batched = None
     if batched_elapsed is not None:
@@ -1002,7 +1037,7 @@ def main():
     # stage-parallel multifrontal LDL^T).  Same timed-region rules as above; no CPU baseline.
     c4 = None
     c4_configs = args.c4_configs if args.c4_configs is not None else ("C4,C4T" if args.config == "C3" else "")
-    if c4_configs and not args.no_c4 and args.c4_batch > 0:
+    if args.full and c4_configs and not args.no_c4 and args.c4_batch > 0:
         c4 = {"instances_per_gpu": args.c4_batch, "instances_per_group": args.c4_group, "problems_total": world * args.c4_batch,
               "problem": "10 Newton steps of one instance (SURVEY 8(d))"}
         # (CALIPSO_BENCH_C4_SHIFT=k: k small handles created first — shifts which hardware queues the lanes' streams get: the experiment behind BatchSolver.spread_streams,
@@ -1080,7 +1115,7 @@ def main():
                             "speedup": {str(n): n * per_gpu[256 // n] / per_gpu[256] for n in (1, 2, 4, 8)}}
 
     c2 = c5 = None
-    if rank == 0 and world == 1 and not args.no_c2_c5 and args.config == "C3":
+    if args.full and rank == 0 and world == 1 and not args.no_c2_c5 and args.config == "C3":
         try:
             c2 = config_c2(pkg, pr, local_rank if args.force_device < 0 else args.force_device, cpu=not args.no_cpu_baseline)
             c5 = config_c5(pkg, pr, local_rank if args.force_device < 0 else args.force_device, cpu=not args.no_cpu_baseline)
@@ -1088,7 +1123,7 @@ def main():
             c2 = c2 or {"error": repr(e)}
             c5 = c5 or {"error": repr(e)}
     c3_solve = small_newton = None
-    if rank == 0 and world == 1 and not args.no_c2_c5 and args.config == "C3":
+    if args.full and rank == 0 and world == 1 and not args.no_c2_c5 and args.config == "C3":
         try:
             c3_solve = config_c3_solve(pkg, pr, local_rank if args.force_device < 0 else args.force_device, shape)
         except Exception as e:
@@ -1100,7 +1135,7 @@ def main():
     out = {
         "metric": "Newton steps/sec (n~5k KKT)", "value": value, "unit": "Newton steps/s", "n_gpus": world, "steps": steps_timed,
         "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / steps_timed, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "vs_baseline": None, "dtype": "f64", "data": "synthetic", "full": bool(args.full),
         "config": {"workload": workload,
                    "parallelism": "one system per GPU: replicas only; batched: independent problems per GPU (no data-path collective)",
                    "refinement_rounds": refinement_rounds, "factorizations_per_step": factorizations,
@@ -1109,11 +1144,12 @@ def main():
                                         + ("MEASURED in this run (--cpu-baseline-full)" if args.cpu_baseline_full else "NOT in this line (value: null; --cpu-baseline-full measures it, ~100 s more)")
                                         + "; B1 = LAPACK on all cores, not the reference",
                    "batched": batched, "c4": c4, "c2": c2, "c5": c5, "c3_solve": c3_solve, "small_newton": small_newton, "roofline_phases": cfg_phases,
-                   "rccl_ranks": exchange.ranks_reported, "exchange_path": exchange.path},
+                   "rccl_ranks": exchange.ranks_reported if exchange else None, "exchange_path": exchange.path if exchange else None},
         "roofline": roof,
     }
-    exchange.close()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if exchange is not None:
+        exchange.close()
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(shape, args.config, staged, samples=args.cpu_samples, full=args.cpu_baseline_full)
     else:
         out["cpu_baseline"] = None

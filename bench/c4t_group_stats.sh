@@ -1,7 +1,7 @@
 #!/bin/bash
 # kernel stats of ONE C4T group of 16 in flight (rocprofv3 --kernel-trace --stats): bash bench/c4t_group_stats.sh -> gpurun_out/c4t_stats.csv
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/c4t; mkdir -p $O
-(cd /tmp && export TMPDIR=/tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/st -- python $R/bench.py --config C4T --batch 16 --group 16 --lanes 1 --steps 10 --warmup 2 --batched-passes 10 --no-cpu-baseline --no-single > $O/bench.json 2> /dev/null < /dev/null)
+(cd /tmp && export TMPDIR=/tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/st -- python $R/bench.py --full --config C4T --batch 16 --group 16 --lanes 1 --steps 10 --warmup 2 --batched-passes 10 --no-cpu-baseline --no-single > $O/bench.json 2> /dev/null < /dev/null)
 f=$(find $O/st -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" $R/gpurun_out/c4t_stats.csv; rm -rf $O/st
 python - "$R/gpurun_out/c4t_stats.csv" <<'PY'
 import csv, sys

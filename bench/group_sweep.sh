@@ -3,7 +3,7 @@
 for cfg in "$@"; do
   IFS=: read B G L <<< "$cfg"
   echo "== batch=$B group=$G lanes=$L"
-  timeout 600 python bench.py --batch $B --group $G --lanes $L --steps ${STEPS:-8} --warmup 2 --no-cpu-baseline --no-single --config ${CONFIG:-C3} 2>&1 | python -c "
+  timeout 600 python bench.py --full --batch $B --group $G --lanes $L --steps ${STEPS:-8} --warmup 2 --no-cpu-baseline --no-single --config ${CONFIG:-C3} 2>&1 | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -1,6 +1,6 @@
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pc4t -- python $R/bench.py --config C4T --batch 12 --group 12 --lanes 1 --steps 10 --warmup 2 --no-cpu-baseline --no-single > /tmp/pc4t.log 2>&1 < /dev/null
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pc4t -- python $R/bench.py --full --config C4T --batch 12 --group 12 --lanes 1 --steps 10 --warmup 2 --no-cpu-baseline --no-single > /tmp/pc4t.log 2>&1 < /dev/null
 f=$(find /tmp/pc4t -name "*kernel_stats.csv" | head -1)
 if [ -n "$f" ]; then python3 - "$f" <<'PY'
 import csv,sys

@@ -11,8 +11,8 @@ O=$R/gpurun_out/round
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 SINGLE="python $R/bench.py --batch 0 --steps 10 --warmup 2 --no-cpu-baseline --no-c4 --no-c2-c5"
-GROUP="python $R/bench.py --batch $G --group $G --lanes 1 --steps 10 --warmup 2 --batched-passes 10 --no-cpu-baseline --no-single --no-c4 --no-c2-c5"
-timeout 900 python $R/bench.py > $O/bench_default.json 2> $O/bench_default.err < /dev/null
+GROUP="python $R/bench.py --full --batch $G --group $G --lanes 1 --steps 10 --warmup 2 --batched-passes 10 --no-cpu-baseline --no-single --no-c4 --no-c2-c5"
+timeout 900 python $R/bench.py --full > $O/bench_default.json 2> $O/bench_default.err < /dev/null
 for mode in single group; do
   if [ $mode = single ]; then CMD=$SINGLE; Z=1; else CMD=$GROUP; Z=$G; fi
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$mode -- $CMD > $O/bench_${mode}_under_rocprof.json 2> $O/stats_$mode.err < /dev/null

@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out; mkdir -p $O
 cd $R
 for i in 1 2; do
-  python bench.py --batch 0 --no-c4 --no-c2-c5 --no-cpu-baseline --steps 30 > $O/quick_${TAG}_$i.json 2> $O/quick_${TAG}_$i.err
+  python bench.py --full --batch 0 --no-c4 --no-c2-c5 --no-cpu-baseline --steps 30 > $O/quick_${TAG}_$i.json 2> $O/quick_${TAG}_$i.err
   python - <<PY
 import json
 d=json.loads([l for l in open("$O/quick_${TAG}_$i.json") if l.startswith("{")][-1])

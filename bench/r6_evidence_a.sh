@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/r6d; mkdir -p $O
 cd $R
 hipcc --offload-arch=gfx950 -O3 bench/overlap_probe.hip -o /tmp/overlap_probe 2>/dev/null && timeout 120 /tmp/overlap_probe > $O/overlap_probe.txt 2>&1
 for w in 0 1 0 1; do
-  CALIPSO_BENCH_GROUP_SOLVE_WFORM=$w timeout 300 python bench.py --no-single --no-c4 --no-c2-c5 --no-cpu-baseline --batched-passes 10 > $O/group_wform_$w.json 2> /dev/null
+  CALIPSO_BENCH_GROUP_SOLVE_WFORM=$w timeout 300 python bench.py --full --no-single --no-c4 --no-c2-c5 --no-cpu-baseline --batched-passes 10 > $O/group_wform_$w.json 2> /dev/null
   python - <<PY
 import json
 d=json.loads([l for l in open("$O/group_wform_$w.json") if l.startswith("{")][-1])

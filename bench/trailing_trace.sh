@@ -1,7 +1,7 @@
 # per-launch durations of k_ldl_trailing within one group step (grid size tells the panel)
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
-timeout 600 rocprofv3 --kernel-trace --output-format csv -d /tmp/tt -- python $R/bench.py --batch ${1:-12} --group ${1:-12} --lanes 1 --steps 3 --warmup 1 --no-cpu-baseline --no-single > /tmp/tt.log 2>&1 < /dev/null
+timeout 600 rocprofv3 --kernel-trace --output-format csv -d /tmp/tt -- python $R/bench.py --full --batch ${1:-12} --group ${1:-12} --lanes 1 --steps 3 --warmup 1 --no-cpu-baseline --no-single > /tmp/tt.log 2>&1 < /dev/null
 f=$(find /tmp/tt -name "*kernel_trace.csv" | head -1)
 if [ -n "$f" ]; then python3 - "$f" ${1:-12} <<'PY'
 import csv,sys

@@ -1,13 +1,15 @@
-"""GPU: the one-line JSON contract of bench.py (metric / value / ms_per_step / roofline / cpu_baseline ...) on a small configuration,
+"""GPU: the one-line JSON contract of bench.py (metric / value / ms_per_step / roofline / cpu_baseline ...) on a small configuration, with --full,
 single rank and two ranks (both ranks on device 0 with the gloo backend: the multi-rank path of bench.py on one GPU), started both ways:
 under torch.distributed.run and by `python bench.py --gpus 2` alone (bench.py then spawns the ranks itself).  Structural asserts only: rates
-are reported, never compared (a wall-clock ratio does not belong in a correctness suite)."""
+are reported, never compared (a wall-clock ratio does not belong in a correctness suite).  A plain run (no --full): the headline alone, and
+--dump-outputs writes what its last timed step computed."""
 import json
 import os
 import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -52,7 +54,7 @@ def check_roofline_entry(e, inst):
 
 
 def test_bench_line_contract():
-    d = run_bench("--batch", "4", "--group", "2", "--lanes", "2", "--batched-passes", "3", "--cpu-samples", "2",
+    d = run_bench("--full", "--batch", "4", "--group", "2", "--lanes", "2", "--batched-passes", "3", "--cpu-samples", "2",
                   "--c4-configs", "smallT", "--c4-batch", "4", "--c4-group", "2")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
               "config", "roofline", "cpu_baseline"):
@@ -106,7 +108,7 @@ def test_bench_line_contract():
 
 
 def test_bench_single_units_and_no_baseline():
-    d = run_bench("--batch", "2", "--group", "1", "--lanes", "2", "--no-cpu-baseline", "--batched-passes", "2")
+    d = run_bench("--full", "--batch", "2", "--group", "1", "--lanes", "2", "--no-cpu-baseline", "--batched-passes", "2")
     assert d["cpu_baseline"] is None and d["config"]["batched"]["instances_per_group"] == 1 and d["value"] > 0 and d["config"]["c4"] is None
 
 
@@ -116,10 +118,32 @@ def test_bench_two_ranks_on_one_gpu(torchrun):
     ranks with the gloo backend, both on device 0 — once launched by torch.distributed.run, once by `python bench.py --gpus 2` alone.
     value = sum over ranks of the steps over the max time (bench.py itself asserts that the gathered status table has 2 x B rows, all ok,
     and that the counters sum to 2 B P)."""
-    two = run_bench_2ranks("--batch", "4", "--group", "2", "--lanes", "2", "--batched-passes", "3", torchrun=torchrun)
+    two = run_bench_2ranks("--full", "--batch", "4", "--group", "2", "--lanes", "2", "--batched-passes", "3", torchrun=torchrun)
     assert two["n_gpus"] == 2 and two["cpu_baseline"] is None and two["steps"] == 3
     assert abs(two["value"] - 2 * 3 / (two["ms_per_step"] * 3e-3)) <= 1e-6 * two["value"]         # both ranks' steps over the max time
     b2 = two["config"]["batched"]
     assert b2["instances_per_gpu"] == 4 and abs(b2["newton_steps_per_s"] - 2 * 4 * 3 / (b2["ms_per_pass"] * 3e-3)) <= 1e-6 * b2["newton_steps_per_s"]
     assert "torch.distributed (gloo)" in b2["post_round_exchange"] and two["config"]["rccl_ranks"] is None      # (no RCCL communicator between two ranks on one device)
     print("two ranks on one GPU (%s): %.1f steps/s single, %.1f batched" % ("torchrun" if torchrun else "self-spawned", two["value"], b2["newton_steps_per_s"]))
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """a plain run: the headline region alone (no batched region, rooflines, side configurations or CPU baselines), --steps timed steps; --dump-outputs
+    writes the last timed step's results, the same whether or not --full runs the rest beside it"""
+    d = run_bench("--dump-outputs", str(tmp_path / "plain"))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["full"] is False and d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "Newton steps/s" and d["dtype"] == "f64"
+    assert abs(d["value"] - 3 / (d["ms_per_step"] * 3e-3)) <= 1e-6 * d["value"]
+    assert d["roofline"] is None and d["cpu_baseline"] is None and d["config"]["batched"] is None and d["config"]["c4"] is None
+    full = run_bench("--full", "--batch", "2", "--group", "2", "--lanes", "1", "--batched-passes", "2", "--no-cpu-baseline", "--no-c4", "--dump-outputs", str(tmp_path / "full"))
+    assert full["full"] is True and full["steps"] == 3 and full["config"]["batched"]["instances_per_gpu"] == 2
+    names = sorted(os.listdir(tmp_path / "plain"))
+    assert names == ["candidate.npy", "residual.npy", "step.npy", "step_record.npy"] and sorted(os.listdir(tmp_path / "full")) == names
+    for name in names:
+        a, b = np.load(tmp_path / "plain" / name), np.load(tmp_path / "full" / name)
+        assert a.dtype == np.float64 and a.shape == b.shape and np.isfinite(a).all()
+        assert np.abs(a - b).max() <= 1e-10 * max(1.0, np.abs(b).max()), name
+    rec = np.load(tmp_path / "plain" / "step_record.npy")
+    assert rec[0] == 0 and rec[4] == d["config"]["factorizations_per_step"] and rec[3] == d["config"]["refinement_rounds"]
+    assert np.abs(np.load(tmp_path / "plain" / "step.npy")).max() > 0

@@ -158,11 +158,11 @@ def test_nested_dissection_eliminates_the_stages_in_parallel(oracle_mod):
     nat.close(); nd.close(); mf.close()
 
 
-def test_rate_report_on_trajectory_kkt_systems(oracle_mod):
+def test_rate_report_on_trajectory_kkt_systems(oracle_mod, tmp_path):
     """Timings (device events) of the level-scheduled factorisation / solve on stage-structured KKT systems, natural order vs nested dissection,
-    next to the oracle's QDLDL on one host core for the same permutation; written to gpurun_out/sparse_ldl_rate.json (copied to profiles/).
+    next to the oracle's QDLDL on one host core for the same permutation; printed as one JSON list (the rows profiles/ keeps).
     Asserts only correctness and that nested dissection shortens the device factorisation."""
-    import json, os, time
+    import json, time
     pkg = load_pkg()
     rng = np.random.default_rng(2)
     rows = []
@@ -210,8 +210,7 @@ def test_rate_report_on_trajectory_kkt_systems(oracle_mod):
         rows.append(dict(T=T, state=ns, control=nu, n=n, batch=Bn, numeric=S.info["numeric"], levels=S.info["levels"], factor_ms_whole_batch=min(f),
                          solve_ms_whole_batch=min(sv), factorisations_per_s=Bn / (1e-3 * min(f)), solves_per_s=Bn / (1e-3 * min(sv))))
         S.close()
-    os.makedirs("gpurun_out", exist_ok=True)
-    with open("gpurun_out/sparse_ldl_rate.json", "w") as fh:
+    with open(tmp_path / "sparse_ldl_rate.json", "w") as fh:
         json.dump(rows, fh, indent=1)
     print(json.dumps(rows))
 

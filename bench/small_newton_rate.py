@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """Rate of the batched small-problem path (csrc/smallnewton.hip): python bench/small_newton_rate.py [nx ne nc [batch [steps]]] — whole solve!s of `batch` C5-shaped random
 QPs (nx = 49, ne = 40: the shape of the reference's cart-pole MPC problem, examples/autotuning/cartpole.jl:85-146) in one launch, and `steps` non-advancing Newton
-steps per instance in one launch; the same problems through the oracle on one host core for comparison (a sample of them)."""
+steps per instance in one launch; the same problems through the oracle on one host core for comparison (a sample of them).
+  --soc q:d1,d2,...   cone layout: q nonnegative entries, then second-order cones of dimensions d1, d2, ... (nc = q + sum; replaces the positional nc)
+  --lu-fallback       set_option("lu_fallback", 1): the reference's H \\ residual inside the kernel where refinement fails (else such instances stop with -102)
+  --general K         also time K of the problems through the general path (calipso_hip_solve with the attached QP evaluator, one handle at a time)
+e.g. the cold-started SOC batch of DESIGN 5.00: python bench/small_newton_rate.py 48 12 0 4096 --soc 4:4,4,4,4 --lu-fallback --general 8"""
 import json, os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -11,23 +15,39 @@ import problems as pr
 
 def main():
     a = sys.argv[1:]
+    flag = lambda name: name in a and (a.remove(name) or True)
+    def opt(name):
+        if name not in a: return None
+        i = a.index(name); v = a[i + 1]; del a[i:i + 2]; return v
+    lu = flag("--lu-fallback")
+    soc_arg, general = opt("--soc"), int(opt("--general") or 0)
     nx, ne, nc = (int(a[0]), int(a[1]), int(a[2])) if len(a) >= 3 else (49, 40, 0)
+    q, dims = nc, []
+    if soc_arg:
+        q_s, d_s = soc_arg.split(":")
+        q, dims = int(q_s), [int(x) for x in d_s.split(",") if x]
+        nc = q + sum(dims)
+    soc_idx, at = [], q + 1
+    for dm in dims:
+        soc_idx.append(list(range(at, at + dm))); at += dm
     B = int(a[3]) if len(a) > 3 else 4096
     K = int(a[4]) if len(a) > 4 else 20
     pkg = load_package()
     nprob = min(B, 64)                                 # distinct problems (the batch cycles through them with perturbed starting points)
-    probs = [pr.random_qp(nx, ne, nc, seed=1000 + k, nonnegative_indices=list(range(1, nc + 1))) for k in range(nprob)]
+    probs = [pr.random_qp(nx, ne, nc, seed=1000 + k, nonnegative_indices=list(range(1, q + 1)), second_order_indices=soc_idx or None) for k in range(nprob)]
     idx = np.arange(B) % nprob
     st = lambda name: np.stack([np.asarray(getattr(probs[i], name), dtype=np.float64) for i in idx])
     sn = pkg.SmallNewtonBatch(nx, ne, nc, B)
     if os.environ.get("SN_THREADS"): sn.set_option("threads", int(os.environ["SN_THREADS"]))      # threads per instance (0 / unset: chosen by the LDS footprint)
+    if dims: sn.set_cones(q, dims)
+    if lu: sn.set_option("lu_fallback", 1)
     sn.set_qp(st("P"), st("q"), st("A"), st("b"), st("G"), st("h"), objective_scale=probs[0].c, shared=False)
     rng = np.random.default_rng(0)
     x0 = np.stack([probs[i].x0 for i in idx]) + 0.01 * rng.standard_normal((B, nx))
     import ctypes as C
     from calipso_jl_amd._lib import lib
     dsc = np.zeros(4); f = lib().calipso_hip_debug_smallnewton_describe; f.argtypes = [C.c_void_p, C.POINTER(C.c_double)]; f(sn._h, dsc.ctypes.data_as(C.POINTER(C.c_double)))
-    out = {"shape": [nx, ne, nc], "n": nx + ne + nc, "batch": B, "threads": os.environ.get("SN_THREADS", "auto"),
+    out = {"shape": [nx, ne, nc], "cones": {"nonnegative": q, "second_order": dims}, "lu_fallback": int(lu), "n": nx + ne + nc, "batch": B, "threads": os.environ.get("SN_THREADS", "auto"),
            "kernel": {"threads_per_instance": int(dsc[0]), "lds_bytes_per_instance": int(dsc[1]), "instances_per_compute_unit": int(dsc[2]), "compute_units": int(dsc[3])}}
     ms_all = []
     for rep in range(3):
@@ -39,7 +59,18 @@ def main():
     ms = min(ms_all)
     out["solve"] = {"launch_ms": ms, "launch_ms_all": ms_all, "converged": int((res == 1).sum()), "solves_per_s": B / (ms * 1e-3), "newton_steps_total": int(steps.sum()),
                     "newton_steps_per_s": float(steps.sum()) / (ms * 1e-3), "mean_iterations": float(its.mean()), "max_iterations": int(its.max()),
-                    "mean_factorizations": float(stt["counters"]["factorizations"].mean()), "max_refinement_rounds": int(stt["counters"]["max_refinement_rounds"].max())}
+                    "mean_factorizations": float(stt["counters"]["factorizations"].mean()), "max_refinement_rounds": int(stt["counters"]["max_refinement_rounds"].max()),
+                    "status_counts": {str(int(v)): int((res == v).sum()) for v in np.unique(res)}, "fallbacks_per_solve": float(stt["counters"]["refinement_failures"].mean())}
+    if general:      # the general path on the first `general` problems, one handle at a time (its fallback: fallback.hip)
+        tg, itg = [], []
+        for k in range(min(general, nprob)):
+            p = probs[k]
+            s = pkg.Solver(p, p.nx, 0, p.ne, p.nc, nonnegative_indices=p.nonnegative_indices, second_order_indices=p.second_order_indices)
+            s.qp_attach(p.P, p.q, p.A, p.b, p.G, p.h, p.c)
+            pkg.initialize_b(s, p.x0)
+            t0 = time.perf_counter(); pkg.solve_b(s); tg.append(time.perf_counter() - t0); itg.append(int(s.stats()["total_iterations"]))
+            del s
+        out["general_path"] = {"solves": len(tg), "solve_ms_median": 1e3 * float(np.median(tg)), "solves_per_s": 1.0 / float(np.median(tg)), "iterations": itg}
     # non-advancing steps from an interior state (the benchmark step of the headline, for the batch)
     w = stt["solution"].copy()
     if nc:

@@ -828,7 +828,9 @@ class SmallBatch:
 class SmallNewtonBatch:
     """Solver / initialize! / solve! (src/solver/solver.jl:46-150, initialize.jl:9-48, solve.jl:8-377) for `batch` independent small conic QPs of one shape in ONE
     kernel launch: a workgroup per instance, everything in LDS, every decision of solve! on the device (include/calipso_hip.h, "solve! for a batch of SMALL conic QPs";
-    csrc/smallnewton.hip).  QP data as qp_attach: min c x'Px + q'x s.t. Ax = b, h - Gx >= 0 (nonnegative cones)."""
+    csrc/smallnewton.hip).  QP data as qp_attach: min c x'Px + q'x s.t. Ax = b, h - Gx >= 0 (nonnegative cones).  options={...} go to set_option: the reference's
+    options by name, "threads" (0, 64, 128, 256) and "lu_fallback" (0 or 1: where iterative refinement fails, take the reference's H \\ residual inside the kernel
+    instead of stopping the instance with -102; costs batch x N^2 doubles of device memory)."""
 
     def __init__(self, nx, ne, nc, batch, device=0, options=None):
         self._L = lib()

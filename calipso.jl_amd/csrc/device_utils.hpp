@@ -128,4 +128,15 @@ __device__ __forceinline__ void arrow_inverse_small(int n, const double (&u)[MAX
     for (int i = 1; i < MAXD; ++i) if (i < n) out[i] = 1.0 / u[0] * out[i];
 }
 
+// value of arrow(u)[k][c] (cone-local indices): diagonal for nonnegative entries, arrow for second-order cones.  jk, jc: the second-order cone entries k and c
+// belong to (-1: a nonnegative entry); st: the first entry of cone jk (read only when jk == jc >= 0).  The dense H of the pivoted fallback (fallback.hip,
+// smallnewton_device.hpp) is assembled from it.
+__device__ __forceinline__ double arrow_entry(int jk, int jc, int st, const double* __restrict__ u, int k, int c) {
+    if (jk < 0 || jc < 0) return (k == c) ? u[k] : 0.0;
+    if (jk != jc) return 0.0;
+    if (k == st) return u[c];
+    if (c == st) return u[k];
+    return (c == k) ? u[st] : 0.0;
+}
+
 }  // namespace calipso

@@ -9,15 +9,10 @@
 
 namespace calipso {
 
-// value of arrow(u)[k][c] (cone-local indices) for the cone layout: diagonal for nonnegative entries, arrow for second-order cones
+// arrow(u)[k][c] for the handle's cone layout (device_utils.hpp: arrow_entry)
 __device__ __forceinline__ double arrow_entry(const ConeDev& cd, const double* __restrict__ u, int k, int c) {
     const int jk = cd.entry_soc[k], jc = cd.entry_soc[c];
-    if (jk < 0 || jc < 0) return (k == c) ? u[k] : 0.0;
-    if (jk != jc) return 0.0;
-    const int st = cd.soc_start[jk];
-    if (k == st) return u[c];
-    if (c == st) return u[k];
-    return (c == k) ? u[st] : 0.0;
+    return arrow_entry(jk, jc, jk >= 0 && jk == jc ? cd.soc_start[jk] : 0, u, k, c);
 }
 
 // H (N x N, column-major) as residual_jacobian_variables! writes it, regularisation included

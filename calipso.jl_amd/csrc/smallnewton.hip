@@ -10,7 +10,8 @@
 //
 // Scope: the device-resident QP evaluator of qp.hip (f = c x'Px + q'x, g = Ax - b, cone constraint h - Gx) with nonnegative cones (second-order cones and other
 // evaluators: the general path); residual_norm = constraint_norm = 1 (the defaults of options.jl).  When iterative refinement fails, the reference falls back to
-// `H \ residual` (search_direction.jl:22): such an instance stops with status CALIPSO_WARN_REFINEMENT and is left to the general path.
+// `H \ residual` (search_direction.jl:22): by default such an instance stops with status CALIPSO_WARN_REFINEMENT and is left to the general path; with the option
+// lu_fallback = 1 the kernel's LU builds take the fallback themselves (a pivoted LU of the unreduced H in per-instance global scratch) and the iteration goes on.
 //
 // Arithmetic: the condensed system in the constraint-first order [z | y | x] of DESIGN.md 4 — closed-form pivots for the y and z blocks, S = Lsym + ep I +
 // [A; -G]' Omega [A; -G] factored without pivoting in LDS, inertia = signs of the closed-form pivots + signs of D(S) (negative = #(d <= 0) as compute_inertia!).
@@ -40,6 +41,7 @@ struct calipso_hip_smallnewton {
     int trace_rows = 0;
     size_t lds_bytes = 0;
     int threads = 0;                 // options.threads: 0 = by the LDS footprint (sn_threads), 64 / 128 / 256 forced
+    bool lu = false; double* Hs = nullptr;      // options.lu_fallback: H \ residual in the kernel, batch x N x N doubles of scratch for H and its factors
     double last_ms = 0.0;
     std::string err;
 };
@@ -91,6 +93,7 @@ struct Args {
     int batch, mode, count, advance, trace_rows;
     double* stf;                                    // batch x 2 nc: s and t at the last search direction (smallnewton_device.hpp: quirk B-12)
     const double* rtheta; double* sens; long long srtheta;             // differentiate!: dR/dtheta and the sensitivities, per instance N x count, column-major
+    double* Hs;                                     // lu_fallback: per instance N x N (the unreduced H, then its LU factors)
 };
 
 // the device code, once per workgroup size (launch() picks: sn_threads())
@@ -131,11 +134,20 @@ int sn_threads(const SN* s) {
     const size_t per = s->lds_bytes + 1280, lds = 160 * 1024;
     return 6 * per <= lds ? 64 : 3 * per <= lds ? 128 : 256;
 }
+// the build of k_smallnewton for a workgroup size, cone layout and lu_fallback
+const void* sn_kernel(int nt, bool soc, bool lu) {
+    if (lu) {
+        if (nt == 64) return soc ? (const void*)t64::k_smallnewton<true, true> : (const void*)t64::k_smallnewton<false, true>;
+        if (nt == 128) return soc ? (const void*)t128::k_smallnewton<true, true> : (const void*)t128::k_smallnewton<false, true>;
+        return soc ? (const void*)t256::k_smallnewton<true, true> : (const void*)t256::k_smallnewton<false, true>;
+    }
+    if (nt == 64) return soc ? (const void*)t64::k_smallnewton<true, false> : (const void*)t64::k_smallnewton<false, false>;
+    if (nt == 128) return soc ? (const void*)t128::k_smallnewton<true, false> : (const void*)t128::k_smallnewton<false, false>;
+    return soc ? (const void*)t256::k_smallnewton<true, false> : (const void*)t256::k_smallnewton<false, false>;
+}
 int grant_lds(SN* s) {
     if (s->lds_bytes <= 64 * 1024) return CALIPSO_OK;
-    (void)calipso::lds_attribute((const void*)t64::k_smallnewton<false>, 160 * 1024); (void)calipso::lds_attribute((const void*)t64::k_smallnewton<true>, 160 * 1024);
-    (void)calipso::lds_attribute((const void*)t128::k_smallnewton<false>, 160 * 1024); (void)calipso::lds_attribute((const void*)t128::k_smallnewton<true>, 160 * 1024);
-    (void)calipso::lds_attribute((const void*)t256::k_smallnewton<false>, 160 * 1024); (void)calipso::lds_attribute((const void*)t256::k_smallnewton<true>, 160 * 1024);
+    for (const bool soc : {false, true}) for (const bool lu : {false, true}) for (const int nt : {64, 128, 256}) (void)calipso::lds_attribute(sn_kernel(nt, soc, lu), 160 * 1024);
     (void)calipso::lds_attribute((const void*)t64::k_smallnewton_diff<false>, 160 * 1024); (void)calipso::lds_attribute((const void*)t64::k_smallnewton_diff<true>, 160 * 1024);
     (void)calipso::lds_attribute((const void*)t128::k_smallnewton_diff<false>, 160 * 1024); (void)calipso::lds_attribute((const void*)t128::k_smallnewton_diff<true>, 160 * 1024);
     (void)calipso::lds_attribute((const void*)t256::k_smallnewton_diff<false>, 160 * 1024); (void)calipso::lds_attribute((const void*)t256::k_smallnewton_diff<true>, 160 * 1024);
@@ -155,6 +167,7 @@ int launch(SN* s, int mode, int count, int advance) {
     { const int ns = (int)s->soc_dim.size(); a.soc_start = s->d_soc; a.soc_dim = s->d_soc ? s->d_soc + ns : nullptr; a.soc_woff = s->d_soc ? s->d_soc + 2 * ns : nullptr; }
     a.batch = s->batch; a.mode = mode; a.count = count; a.advance = advance; a.trace_rows = s->trace_rows;
     a.rtheta = s->rtheta; a.sens = s->sens; a.stf = s->stf; a.srtheta = s->diff_shared ? 0 : (long long)a.d.N * (long long)count;
+    a.Hs = s->Hs;
     static_assert(sizeof(Args) <= 3800, "kernel arguments");
     SK(hipEventRecord(s->ev0, s->stream));
     const bool soc = !s->soc_dim.empty();
@@ -169,15 +182,10 @@ int launch(SN* s, int mode, int count, int advance) {
             if (soc) hipLaunchKernelGGL(t256::k_smallnewton_diff<true>, dim3((unsigned)s->batch), dim3(256), s->lds_bytes, s->stream, a);
             else hipLaunchKernelGGL(t256::k_smallnewton_diff<false>, dim3((unsigned)s->batch), dim3(256), s->lds_bytes, s->stream, a);
         }
-    } else if (sn_threads(s) == 64) {
-        if (soc) hipLaunchKernelGGL(t64::k_smallnewton<true>, dim3((unsigned)s->batch), dim3(64), s->lds_bytes, s->stream, a);
-        else hipLaunchKernelGGL(t64::k_smallnewton<false>, dim3((unsigned)s->batch), dim3(64), s->lds_bytes, s->stream, a);
-    } else if (sn_threads(s) == 128) {
-        if (soc) hipLaunchKernelGGL(t128::k_smallnewton<true>, dim3((unsigned)s->batch), dim3(128), s->lds_bytes, s->stream, a);
-        else hipLaunchKernelGGL(t128::k_smallnewton<false>, dim3((unsigned)s->batch), dim3(128), s->lds_bytes, s->stream, a);
     } else {
-        if (soc) hipLaunchKernelGGL(t256::k_smallnewton<true>, dim3((unsigned)s->batch), dim3(256), s->lds_bytes, s->stream, a);
-        else hipLaunchKernelGGL(t256::k_smallnewton<false>, dim3((unsigned)s->batch), dim3(256), s->lds_bytes, s->stream, a);
+        const int nt = sn_threads(s);
+        void* args[] = {&a};
+        SK(hipLaunchKernel(sn_kernel(nt, soc, s->lu), dim3((unsigned)s->batch), dim3((unsigned)nt), args, s->lds_bytes, s->stream));
     }
     SK(hipGetLastError());
     SK(hipEventRecord(s->ev1, s->stream));
@@ -230,7 +238,7 @@ int32_t calipso_hip_smallnewton_destroy(calipso_hip_smallnewton* s) {
     if (!s) return CALIPSO_OK;
     (void)hipSetDevice(s->device);
     if (s->stream) (void)hipStreamSynchronize(s->stream);
-    for (double* p : {s->P, s->q, s->Z, s->bh, s->w, s->lam, s->sc, s->filt, s->info, s->trace, s->prof, s->rtheta, s->sens, s->stf}) if (p) (void)hipFree(p);
+    for (double* p : {s->P, s->q, s->Z, s->bh, s->w, s->lam, s->sc, s->filt, s->info, s->trace, s->prof, s->rtheta, s->sens, s->stf, s->Hs}) if (p) (void)hipFree(p);
     if (s->cnt) (void)hipFree(s->cnt);
     if (s->d_soc) (void)hipFree(s->d_soc);
     if (s->status) (void)hipFree(s->status);
@@ -287,6 +295,23 @@ int32_t calipso_hip_smallnewton_set_option(calipso_hip_smallnewton* s, const cha
     if (n == "threads") {         // (not an option of the reference) threads per instance: 0 = chosen by the LDS footprint, 64, 128 or 256
         if (value != 0.0 && value != 64.0 && value != 128.0 && value != 256.0) return fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_smallnewton: threads is 0 (automatic), 64, 128 or 256");
         s->threads = (int)value; return CALIPSO_OK;
+    }
+    if (n == "lu_fallback") {     // (not an option of the reference) 1: H \ residual in the kernel where iterative refinement fails (search_direction.jl:22), 0: stop there
+        if (value != 0.0 && value != 1.0) return fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_smallnewton: lu_fallback is 0 or 1");
+        SK(hipSetDevice(s->device));
+        if (value == 1.0 && !s->Hs) {
+            const size_t N = (size_t)dims_of(s).N;
+            SK(hipStreamSynchronize(s->stream));
+            if (hipMalloc((void**)&s->Hs, sizeof(double) * (size_t)s->batch * N * N) != hipSuccess) {
+                s->Hs = nullptr;
+                return fail(s, CALIPSO_ERR_HIP, "calipso_hip_smallnewton: lu_fallback needs batch x N x N doubles of device memory (" + std::to_string(sizeof(double) * (size_t)s->batch * N * N) + " bytes)");
+            }
+        } else if (value == 0.0 && s->Hs) {
+            SK(hipStreamSynchronize(s->stream));
+            (void)hipFree(s->Hs); s->Hs = nullptr;
+        }
+        s->lu = value == 1.0;
+        return CALIPSO_OK;
     }
     if (n == "max_filter") {      // filter.jl:7-13: the instances' filter pairs live in global memory (6 x max_filter doubles each): re-sized here, emptied
         if (value < 1.0 || value > 1.0e6) return fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_smallnewton: 1 <= max_filter <= 1e6");
@@ -398,7 +423,8 @@ int32_t calipso_hip_smallnewton_trace(calipso_hip_smallnewton* s, int32_t rows, 
 }
 
 // solve!(solver) for every instance in ONE launch (cold start unless opt.warmstart: x from the resident points).  result[k] = 1 converged, 0 iteration caps reached,
-// CALIPSO_ERR_INERTIA / CALIPSO_ERR_CONE_SEARCH as the reference's error()s, -100 - CALIPSO_WARN_REFINEMENT where the reference would fall back to H \ residual.
+// CALIPSO_ERR_INERTIA / CALIPSO_ERR_CONE_SEARCH as the reference's error()s, -100 - CALIPSO_WARN_REFINEMENT where the reference would fall back to H \ residual
+// (lu_fallback = 0), -100 - CALIPSO_WARN_ZERO_PIVOT where that fallback met an exactly singular H (lu_fallback = 1).
 int32_t calipso_hip_smallnewton_solve(calipso_hip_smallnewton* s, int32_t* result, double* ms) {
     if (!s) return CALIPSO_ERR_ARGUMENT;
     const int rc = launch(s, MODE_SOLVE, 0, 1);
@@ -454,10 +480,8 @@ int32_t calipso_hip_smallnewton_differentiate(calipso_hip_smallnewton* s, int64_
 int32_t calipso_hip_debug_smallnewton_describe(calipso_hip_smallnewton* s, double out[4]) {
     if (!s || !out) return CALIPSO_ERR_ARGUMENT;
     SK(hipSetDevice(s->device));
-    const int nt = sn_threads(s); const bool soc = !s->soc_dim.empty();
-    const void* f = nt == 64 ? (soc ? (const void*)t64::k_smallnewton<true> : (const void*)t64::k_smallnewton<false>)
-                  : nt == 128 ? (soc ? (const void*)t128::k_smallnewton<true> : (const void*)t128::k_smallnewton<false>)
-                              : (soc ? (const void*)t256::k_smallnewton<true> : (const void*)t256::k_smallnewton<false>);
+    const int nt = sn_threads(s);
+    const void* f = sn_kernel(nt, !s->soc_dim.empty(), s->lu);
     int per = 0, cus = 0;
     SK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, f, nt, s->lds_bytes));
     SK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device));

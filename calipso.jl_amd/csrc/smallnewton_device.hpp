@@ -566,6 +566,106 @@ template <bool SOC> struct CtxT {
         return v[0];
     }
 
+    // the second-order cone cone-local entry k belongs to (-1: a nonnegative entry)
+    __device__ __forceinline__ int soc_of(int k) const {
+        if (!SOC || k < d.q) return -1;
+        int j = 0;
+        while (j + 1 < d.nsoc && k >= soc_start[j + 1]) ++j;
+        return j;
+    }
+
+    // ---- search_direction_nonsymmetric! (search_direction.jl:106-119): step = H \ res on the UNREDUCED N x N matrix — the reference's fallback when iterative
+    // refinement fails (search_direction.jl:22).  Only the lu_fallback builds of the kernel (LU = true) call it.  H of the resident point with the current ep / ed, by
+    // the closed forms of fallback.hip (k_assemble_H: Lxx from the Hessian block in L2, [A; -G] from the LDS copy, arrow(s) / arrow(t) for the cone rows), goes to the
+    // instance's global scratch Hg (N x N, column-major: it does not fit the LDS beside the instance), then a right-looking LU with partial pivoting whose pivot choice
+    // and arithmetic are the oracle's dense_lu_solve: the largest |a_ik|, the first row on a tie; multipliers times the reciprocal pivot; the right-hand side eliminated
+    // with the columns, then backward substitution.  Returns false (every thread) on an exactly singular H.
+    __device__ __forceinline__ bool nonsymmetric_solve(double* Hg) {      // (no __restrict__: every thread of the workgroup writes Hg)
+        const int N = d.N, nx = d.nx, ne = d.ne;
+        const int orr = d.orr(), os = d.os(), oy = d.oy(), oz = d.oz(), ot = d.ot();
+        for (int e = tid; e < N * N; e += NT) {
+            const int j = e / N, i = e - j * N;                   // row i (fast), column j
+            double v = 0.0;
+            if (i < orr) {                                        // x rows
+                if (j < orr) { v = Lg[i + (size_t)j * nx]; if (i == j) v += ep; }
+                else if (j >= oy && j < oz) v = Z[(j - oy) + i * d.ldz];             // gx'
+                else if (j >= oz && j < ot) v = Z[ne + (j - oz) + i * d.ldz];        // hx'
+            } else if (i < os) {                                  // r rows
+                const int k = i - orr;
+                if (j == i) v = rho + ep;
+                else if (j == oy + k) v = -1.0;
+            } else if (i < oy) {                                  // s rows
+                const int k = i - os;
+                if (j == i) v = 0.0 + ep;
+                else if (j == oz + k) v = -1.0;
+                else if (j == ot + k) v = -1.0;
+            } else if (i < oz) {                                  // y rows
+                const int k = i - oy;
+                if (j < orr) v = Z[k + j * d.ldz];
+                else if (j == orr + k) v = -1.0;
+                else if (j == i) v = 0.0 - ed;
+            } else if (i < ot) {                                  // z rows
+                const int k = i - oz;
+                if (j < orr) v = Z[ne + k + j * d.ldz];
+                else if (j == os + k) v = -1.0;
+                else if (j == i) v = 0.0 - ed;
+            } else if (j >= os && (j < oy || j >= ot)) {          // t rows: d(s o t)/ds = arrow(t), d(s o t)/dt = arrow(s) - ed I
+                const int k = i - ot, cj = j < oy ? j - os : j - ot;
+                const int jk = soc_of(k), jc = soc_of(cj);
+                const int st = jk >= 0 && jk == jc ? soc_start[jk] : 0;
+                v = calipso::arrow_entry(jk, jc, st, j < oy ? sol + ot : sol + os, k, cj);
+                if (j == i) v -= ed;
+            }
+            Hg[e] = v;
+        }
+        for (int i = tid; i < N; i += NT) step[i] = res[i];
+        __syncthreads();
+        const int lane = tid & 63, wave = tid >> 6;
+        for (int k = 0; k < N; ++k) {
+            double* colk = Hg + (size_t)k * N;
+            // pivot: the largest |a_ik|, i >= k, the first on a tie (a total order: every lane of the butterfly ends with the same pair)
+            double best = -1.0; int bi = N;
+            for (int i = k + tid; i < N; i += NT) { const double a = fabs(colk[i]); if (a > best) { best = a; bi = i; } }
+            for (int off = 32; off > 0; off >>= 1) {
+                const double ob = __shfl_xor(best, off, 64); const int oi = __shfl_xor(bi, off, 64);
+                if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+            }
+            if constexpr (NW > 1) {
+                if (lane == 0) { red[wave] = best; red[4 + wave] = (double)bi; }
+                __syncthreads();
+                for (int w = 0; w < NW; ++w) { const double ob = red[w]; const int oi = (int)red[4 + w]; if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; } }
+            }
+            if (best == 0.0) return false;                        // (uniform) exactly singular, as dense_lu_solve
+            const int p = bi < N ? bi : k;                        // (a column of NaNs: the pivot stays in place and the NaN travels on, as in dense_lu_solve)
+            if (p != k) {                                         // (uniform) the whole rows, multipliers included, and the right-hand side
+                for (int j = tid; j < N; j += NT) { double* cj = Hg + (size_t)j * N; const double t = cj[k]; cj[k] = cj[p]; cj[p] = t; }
+                if (tid == 0) { const double t = step[k]; step[k] = step[p]; step[p] = t; }
+                __syncthreads();
+            }
+            const double inv = 1.0 / colk[k], bk = step[k];
+            for (int i = k + 1 + tid; i < N; i += NT) { const double l = colk[i] * inv; colk[i] = l; step[i] -= l * bk; }
+            __syncthreads();
+            // trailing update a_ij -= l_i a_kj (columns with a_kj = 0 skipped, as dense_lu_solve): lane -> row (coalesced), wavefront w -> every NW-th column
+            // (one column at a time: unrolling four raised the build's scratch by another 48 - 64 bytes per lane)
+            for (int i = k + 1 + lane; i < N; i += 64) {
+                const double l = colk[i];
+                for (int j = k + 1 + wave; j < N; j += NW) { double* cj = Hg + (size_t)j * N; const double akj = cj[k]; if (akj != 0.0) cj[i] -= l * akj; }
+            }
+            __syncthreads();
+        }
+        // U x = y, from the last row: x_k goes to corr (step[k] is still read by every thread in the pass that forms it)
+        for (int k = N - 1; k >= 0; --k) {
+            const double* colk = Hg + (size_t)k * N;
+            const double xk = step[k] / colk[k];
+            for (int i = tid; i < k; i += NT) step[i] -= colk[i] * xk;
+            if (tid == 0) corr[k] = xk;
+            __syncthreads();
+        }
+        for (int i = tid; i < N; i += NT) step[i] = corr[i];
+        __syncthreads();
+        return true;
+    }
+
     // ---- filter (filter.jl), thread 0 on the instance's global arrays, result through LDS -------------------------------------------------------
     __device__ __forceinline__ bool check_filter(double theta, double merit) {
         __syncthreads();
@@ -615,8 +715,9 @@ __device__ __forceinline__ bool armijo(double m, double mc, double dd, double st
 
 struct StepOut { int exit_kind = 0; int rc = 0; double step_size = 1.0, step_size_t = 1.0, Mh = 0.0, thetah = 0.0, optimality = 0.0; int rounds = 0; int nfact = 0; };
 
-// one pass of the inner loop body of solve! (solve.jl:98-353); equality_violation / cone_product_violation as the caller holds them (:85-86, :332-333)
-template <bool SOC> __device__ __forceinline__ StepOut inner_iteration(CtxT<SOC>& c, bool may_converge) {
+// one pass of the inner loop body of solve! (solve.jl:98-353); equality_violation / cone_product_violation as the caller holds them (:85-86, :332-333).
+// LU: the reference's H \ residual where iterative refinement fails, in the instance's N x N scratch Hg (else the instance stops there: CALIPSO_WARN_REFINEMENT)
+template <bool SOC, bool LU> __device__ __forceinline__ StepOut inner_iteration(CtxT<SOC>& c, bool may_converge, double* Hg) {
     const Dm& d = c.d; const Options& o = *c.o; const int tid = c.tid;
     StepOut out;
     double* sol = c.sol; double* cand = c.cand; double* step = c.step; double* res = c.res;
@@ -723,7 +824,11 @@ template <bool SOC> __device__ __forceinline__ StepOut inner_iteration(CtxT<SOC>
         }
         out.rounds = it;
         if (o.iterative_refinement) { c.rlast = it; if (it > c.rmax) c.rmax = it; }
-        if (!good && !(norm <= norm0)) { c.rfail += 1; out.rc = CALIPSO_WARN_REFINEMENT; return out; }      // (the reference would take H \ residual: left to the general path)
+        if (!good && !(norm <= norm0)) {
+            c.rfail += 1;
+            if constexpr (LU) { if (!c.nonsymmetric_solve(Hg)) { out.rc = CALIPSO_WARN_ZERO_PIVOT; return out; } }      // search_direction.jl:22, then on to the cone search
+            else { out.rc = CALIPSO_WARN_REFINEMENT; return out; }      // (the reference takes H \ residual: the lu_fallback build does)
+        }
     }
     c.stamp(5);
     // ---- :190-221 cone search: separate step sizes for s and t -----------------------------------------------------------------------------------------
@@ -898,7 +1003,7 @@ template <bool SOC> __global__ __launch_bounds__(NT, 2) void k_smallnewton_diff(
     if (tid == 0) a.status[inst] = inertia_ok ? 0 : 1;      // (1: the factorisation's inertia is not (nx, ne + nc, 0); the reference does not look, the sensitivities are what they are)
 }
 
-template <bool SOC> __global__ __launch_bounds__(NT, 2) void k_smallnewton(Args a) {
+template <bool SOC, bool LU> __global__ __launch_bounds__(NT, 2) void k_smallnewton(Args a) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int inst = blockIdx.x, tid = threadIdx.x;
     if (inst >= a.batch) return;
@@ -965,8 +1070,8 @@ template <bool SOC> __global__ __launch_bounds__(NT, 2) void k_smallnewton(Args 
         const long long fidx = c.filter_index;
         const bool restore = !solving && !a.advance;
         if (restore && tid == 0) for (long long i = 0; i < fidx; ++i) { c.filt[4 * mf_ + i] = c.filt[i]; c.filt[5 * mf_ + i] = c.filt[mf_ + i]; }
-        last = inner_iteration(c, solving);
-        if (last.rc < 0 || last.rc == CALIPSO_WARN_REFINEMENT) { status = last.rc < 0 ? last.rc : -100 - last.rc; break; }
+        last = inner_iteration<SOC, LU>(c, solving, LU ? a.Hs + (size_t)inst * d.N * d.N : nullptr);
+        if (last.rc < 0 || last.rc == CALIPSO_WARN_REFINEMENT || (LU && last.rc == CALIPSO_WARN_ZERO_PIVOT)) { status = last.rc < 0 ? last.rc : -100 - last.rc; break; }
         if (solving) {
             if (last.exit_kind == 1) { status = 1; break; }                                                  // :138-160
             bool inner_done = last.exit_kind == 2;                                                           // :165

@@ -531,6 +531,11 @@ function HIPSmallNewton(nx::Integer, ne::Integer, nc::Integer, batch::Integer; d
     return s
 end
 sn_check(s::HIPSmallNewton, rc, what) = rc < 0 ? error("$what failed ($rc): " * unsafe_string(ccall((:calipso_hip_smallnewton_last_error, lib), Cstring, (Ptr{Cvoid},), s.handle))) : rc
+"options.jl:6-59 by name (Symbol or String), plus `threads` (0, 64, 128, 256) and `lu_fallback` (0 or 1: `H \\ residual` in the kernel where iterative refinement fails, batch x N^2 doubles of device memory)"
+function set_option!(s::HIPSmallNewton, name, value::Real)
+    sn_check(s, ccall((:calipso_hip_smallnewton_set_option, lib), Int32, (Ptr{Cvoid}, Cstring, Float64), s.handle, String(name), Float64(value)), "calipso_hip_smallnewton_set_option($name)")
+    return s
+end
 "cone layout: the first `n_nonnegative` cone entries nonnegative, then second-order cones of the given dimensions (contiguous; 2 .. 16 entries each)"
 function set_cones!(s::HIPSmallNewton, n_nonnegative::Integer, dims::Vector{Int64}=Int64[])
     sn_check(s, ccall((:calipso_hip_smallnewton_set_cones, lib), Int32, (Ptr{Cvoid}, Int64, Int64, Ptr{Int64}), s.handle, n_nonnegative, length(dims), isempty(dims) ? C_NULL : dims), "calipso_hip_smallnewton_set_cones")
@@ -612,7 +617,7 @@ function allreduce_sum!(c::HIPComm, v::Vector{Float64})
     return v
 end
 
-export HIPSolver, streams_concurrent, rebind_stream!, spread_streams!, HIPLDLSolver, HIPSparseLDLSolver, hip_sparse_ldl_solver, HIPKKTSolver, hip_ldl_solver, HIPGroup, HIPSmallNewton, set_cones!, set_qp!, solution, HIPComm, comm_unique_id, comm_size, gather_status, allreduce_sum!, newton_step!,
+export HIPSolver, streams_concurrent, rebind_stream!, spread_streams!, HIPLDLSolver, HIPSparseLDLSolver, hip_sparse_ldl_solver, HIPKKTSolver, hip_ldl_solver, HIPGroup, HIPSmallNewton, set_option!, set_cones!, set_qp!, solution, HIPComm, comm_unique_id, comm_size, gather_status, allreduce_sum!, newton_step!,
        search_direction_nonsymmetric!, analyze_structure!, clear_structure!, set_stage_parallel!, set_stage_blocks!, declared_structure, kernel_times, sync_scalars!, copy_back!
 
 end # module

@@ -435,11 +435,14 @@ int32_t calipso_hip_small_get(calipso_hip_small*, double* X, int64_t* inertia);
  * nonnegative and second-order cones (dimension <= 16; wider: the general path); residual_norm = constraint_norm = 1.  Points have the layout of point.jl:13-22 (N = nx + 2 ne + 3 nc).  Limits: nx <= 128 and the
  * instance must fit 160 KB of LDS (n up to ~200), else CALIPSO_ERR_ARGUMENT at create: the general path (calipso_hip_create + groups) takes those.
  *   create(nx, ne, nc, batch, device)        set_option(name, value): options.jl:6-59 by name; plus "threads" = threads per instance (0: chosen by the LDS footprint so that
- *                                            a compute unit holds as many instances as fit; 64, 128 or 256 force a build of the kernel)
+ *                                            a compute unit holds as many instances as fit; 64, 128 or 256 force a build of the kernel); "lu_fallback" = 0 (default) or 1:
+ *                                            where iterative refinement fails, take the reference's `H \ residual` (search_direction.jl:22) inside the kernel — a partially
+ *                                            pivoted LU of the unreduced N x N matrix — and go on; costs batch x N^2 doubles of device memory, held while the option is 1
  *   set_qp(P, q, A, b, G, h, c, shared)      column-major host arrays, batch-major (instance k at k * size) or ONE problem for all (shared != 0)
  *   set_state(w, lambda, scalars)            points (batch x N; initialize!: x in the first nx entries), lambda (batch x ne), [central_path, fraction_to_boundary, penalty] (batch x 3)
  *   solve(result, ms)                        solve! of every instance: 1 converged, 0 iteration caps, CALIPSO_ERR_INERTIA / CALIPSO_ERR_CONE_SEARCH (the reference's error()s),
- *                                            -100 - CALIPSO_WARN_REFINEMENT where the reference would fall back to `H \ residual` (search_direction.jl:22: left to the general path)
+ *                                            -100 - CALIPSO_WARN_REFINEMENT where the reference would fall back to `H \ residual` (search_direction.jl:22: left to the general path;
+ *                                            lu_fallback = 0 only), -100 - CALIPSO_WARN_ZERO_PIVOT where that fallback met an exactly singular H (lu_fallback = 1)
  *   steps(count, advance, info, status, ms)  `count` passes of the inner loop body (solve.jl:98-353) from the resident state = calipso_hip_newton_steps for the batch
  *   get_state(w, lambda, scalars, counters)  scalars batch x 6 [central_path, fraction_to_boundary, penalty, primal_regularization, primal_regularization_last, dual_regularization],
  *                                            counters batch x 8 [total_iterations, outer, factorizations, refinement failures, max / last refinement rounds, Newton steps, accepted iterates]

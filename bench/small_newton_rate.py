@@ -5,6 +5,9 @@ steps per instance in one launch; the same problems through the oracle on one ho
   --soc q:d1,d2,...   cone layout: q nonnegative entries, then second-order cones of dimensions d1, d2, ... (nc = q + sum; replaces the positional nc)
   --lu-fallback       set_option("lu_fallback", 1): the reference's H \\ residual inside the kernel where refinement fails (else such instances stop with -102)
   --general K         also time K of the problems through the general path (calipso_hip_solve with the attached QP evaluator, one handle at a time)
+  --evaluator cartpole   instead of random QPs: the cart-pole MPC problem itself (nx 49, ne 40, np 102) through the device evaluator of
+                      tests/device_eval_small/cartpole_mpc.hip, per-instance parameters (x_init and weights moved by a few per cent): solve!s, Newton steps and
+                      differentiate!s (dR/dtheta from the evaluator) per second for the batch (default 4096), beside the oracle's solve! + differentiate! on one core
 e.g. the cold-started SOC batch of DESIGN 5.00: python bench/small_newton_rate.py 48 12 0 4096 --soc 4:4,4,4,4 --lu-fallback --general 8"""
 import json, os, sys, time
 import numpy as np
@@ -13,12 +16,62 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle")]
 from __graft_entry__ import load_package
 import problems as pr
 
+def evaluator_rate(name, B):
+    import ctypes
+    if name != "cartpole":
+        raise SystemExit("--evaluator: cartpole")
+    pkg = load_package()
+    prob = pr.cartpole_mpc()
+    rng = np.random.default_rng(0)
+    th = np.repeat(prob.parameters[None], B, axis=0)
+    th[:, 10:14] += 0.05 * rng.uniform(-1, 1, (B, 4))
+    for t in range(9):
+        o = 0 if t == 0 else 14 + 10 * (t - 1)
+        th[:, o + 5:o + 10] *= 1.0 + 0.1 * rng.uniform(-1, 1, (B, 5))
+    th[:, 98:102] *= 1.0 + 0.1 * rng.uniform(-1, 1, (B, 4))
+    opts = dict(residual_tolerance=1e-3, optimality_tolerance=1e-3, equality_tolerance=1e-3, complementarity_tolerance=1e-3, slack_tolerance=1e-3)
+    sn = pkg.SmallNewtonBatch(prob.nx, prob.ne, prob.nc, B, options=opts)
+    sn.set_evaluator(ctypes.CDLL(os.path.join(ROOT, "tests", "device_eval_small", "libsmall_evaluators.so")), "cartpole_mpc_kernels", prob.np)
+    sn.set_parameters(th)
+    x0 = np.repeat(prob.x0[None], B, axis=0)
+    ms_all = []
+    for rep in range(3):
+        sn.initialize(x0)
+        res, ms = sn.solve()
+        ms_all.append(ms)
+    st = sn.get_state()
+    ms = min(ms_all)
+    steps = int(st["counters"]["newton_steps"].sum())
+    dms = min(sn.differentiate()[2] for _ in range(3))
+    out = {"evaluator": "cartpole_mpc", "shape": [prob.nx, prob.ne, prob.nc], "n_parameters": prob.np, "batch": B,
+           "solve": {"launch_ms": ms, "launch_ms_all": ms_all, "converged": int((res == 1).sum()), "solves_per_s": B / (ms * 1e-3), "newton_steps_total": steps,
+                     "newton_steps_per_s": steps / (ms * 1e-3), "mean_iterations": float(st["counters"]["total_iterations"].mean())},
+           "differentiate": {"launch_ms": dms, "differentiates_per_s": B / (dms * 1e-3)}}
+    try:
+        import oracle
+        from test_oracle_solve import run as run_oracle
+        ts = []
+        for k in range(8):
+            prob.parameters = th[k].copy()
+            t0 = time.perf_counter(); run_oracle(oracle, prob, differentiate=1, **opts); ts.append(time.perf_counter() - t0)
+        out["cpu_baseline"] = {"kind": "port", "cores": 1, "solve_and_differentiate_ms_median": 1e3 * float(np.median(ts)), "per_s": 1.0 / float(np.median(ts)),
+                               "sample": "%d solve! + differentiate! by the oracle (evaluation through Python callbacks)" % len(ts)}
+    except Exception as e:
+        out["cpu_baseline"] = {"error": repr(e)}
+    sn.close()
+    print(json.dumps(out))
+
+
 def main():
     a = sys.argv[1:]
     flag = lambda name: name in a and (a.remove(name) or True)
     def opt(name):
         if name not in a: return None
         i = a.index(name); v = a[i + 1]; del a[i:i + 2]; return v
+    ev = None
+    if "--evaluator" in a:
+        i = a.index("--evaluator"); ev = a[i + 1]; del a[i:i + 2]
+        return evaluator_rate(ev, int(a[0]) if a else 4096)
     lu = flag("--lu-fallback")
     soc_arg, general = opt("--soc"), int(opt("--general") or 0)
     nx, ne, nc = (int(a[0]), int(a[1]), int(a[2])) if len(a) >= 3 else (49, 40, 0)

@@ -830,7 +830,8 @@ class SmallNewtonBatch:
     kernel launch: a workgroup per instance, everything in LDS, every decision of solve! on the device (include/calipso_hip.h, "solve! for a batch of SMALL conic QPs";
     csrc/smallnewton.hip).  QP data as qp_attach: min c x'Px + q'x s.t. Ax = b, h - Gx >= 0 (nonnegative cones).  options={...} go to set_option: the reference's
     options by name, "threads" (0, 64, 128, 256) and "lu_fallback" (0 or 1: where iterative refinement fails, take the reference's H \\ residual inside the kernel
-    instead of stopping the instance with -102; costs batch x N^2 doubles of device memory)."""
+    instead of stopping the instance with -102; costs batch x N^2 doubles of device memory).  Nonlinear problems: set_evaluator with a device evaluator compiled
+    into a HIP library of the caller's (include/calipso_smallnewton.hpp), set_parameters, differentiate() with dR/dtheta from the evaluator."""
 
     def __init__(self, nx, ne, nc, batch, device=0, options=None):
         self._L = lib()
@@ -871,6 +872,25 @@ class SmallNewtonBatch:
         Pc, Ac, Gc = cm(P, self.nx, self.nx), cm(A, self.ne, self.nx), cm(G, self.nc, self.nx)
         qv, bv, hv = vv(q, self.nx), vv(b, self.ne), vv(h, self.nc)
         self._check(self._L.calipso_hip_smallnewton_set_qp(self._h, _pd(Pc), _pd(qv), _pd(Ac), _pd(bv), _pd(Gc), _pd(hv), float(objective_scale), int(bool(shared))), "smallnewton_set_qp")
+
+    def set_evaluator(self, cdll, symbol, n_parameters=0):
+        """a device evaluator instead of the QP: `symbol` is the entry that CALIPSO_SMALLNEWTON_EVALUATOR (include/calipso_smallnewton.hpp) emitted into the HIP shared
+        library `cdll` (a ctypes.CDLL, or its path); n_parameters = the length of theta per instance (set_parameters)"""
+        if not isinstance(cdll, C.CDLL):
+            cdll = C.CDLL(str(cdll))
+        self._evlib = cdll                                                      # (the entry's code must outlive the handle's use of it)
+        fn = C.cast(getattr(cdll, symbol), C.c_void_p)
+        self.n_parameters = int(n_parameters)
+        self._check(self._L.calipso_hip_smallnewton_set_evaluator(self._h, fn, self.n_parameters), "smallnewton_set_evaluator(%s)" % symbol)
+
+    def set_parameters(self, theta):
+        """theta (batch, n_parameters) per instance, or (n_parameters,) shared by all"""
+        th = np.asarray(theta, dtype=np.float64)
+        shared = th.ndim == 1
+        if th.shape[-1] != getattr(self, "n_parameters", -1) or (not shared and th.shape != (self.batch, self.n_parameters)):
+            raise ValueError("theta must be (batch, n_parameters) or (n_parameters,)")
+        th = np.ascontiguousarray(th).reshape(-1)
+        self._check(self._L.calipso_hip_smallnewton_set_parameters(self._h, _pd(th), int(shared)), "smallnewton_set_parameters")
 
     def set_state(self, w=None, dual=None, scalars=None):
         """w: (batch, N) points; dual: (batch, ne) multiplier estimates; scalars: (batch, 3) [central_path, fraction_to_boundary, penalty]"""
@@ -914,12 +934,17 @@ class SmallNewtonBatch:
         self._check(self._L.calipso_hip_smallnewton_steps(self._h, int(count), int(bool(advance)), _pd(info), st.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(ms)), "smallnewton_steps")
         return info.reshape(self.batch, 8), st, float(ms.value)
 
-    def differentiate(self, jacobian_parameters):
+    def differentiate(self, jacobian_parameters=None):
         """differentiate! of every instance at its resident point, one launch (differentiate.jl:1-61): jacobian_parameters (batch, N, p) = dR/dtheta per instance, or
-        (N, p) = one matrix for all instances; returns (sensitivity (batch, N, p) = dw/dtheta, status (batch,) — 1: the factorisation's inertia is not
-        (nx, ne + nc, 0) —, launch milliseconds)"""
-        J = np.asarray(jacobian_parameters, dtype=np.float64)
+        (N, p) = one matrix for all instances, or None = the evaluator's dR/dtheta at the resident points (p = n_parameters); returns (sensitivity (batch, N, p) =
+        dw/dtheta, status (batch,) — 1: the factorisation's inertia is not (nx, ne + nc, 0) —, launch milliseconds)"""
         N = self.nx + 2 * self.ne + 3 * self.nc
+        if jacobian_parameters is None:
+            p = getattr(self, "n_parameters", 0)
+            out = np.zeros(self.batch * N * max(p, 1)); st = np.zeros(self.batch, dtype=np.int32); ms = C.c_double(0.0)
+            self._check(self._L.calipso_hip_smallnewton_differentiate_parameters(self._h, _pd(out), st.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(ms)), "smallnewton_differentiate_parameters")
+            return np.transpose(out.reshape(self.batch, p, N), (0, 2, 1)).copy(), st, float(ms.value)
+        J = np.asarray(jacobian_parameters, dtype=np.float64)
         shared = J.ndim == 2
         if shared:
             J = J[None]

@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "../../include/calipso_wave.hpp"      // wave_sum_l63, wave_max_l63, arrow_entry
+
 namespace calipso {
 
 // ---- instance addressing (internal.hpp: Batch): shift every per-instance pointer of a kernel to the slab of its instance -----
@@ -14,36 +16,7 @@ template <typename... P> __device__ __forceinline__ void inst_shift_i(const Batc
     ((p += o), ...);
 }
 
-// ---- wave64 reductions (a CDNA wavefront is 64 lanes) ------------------------------------------------
-// The same reductions with the result in LANE 63 only, by data-parallel moves on the vector unit: four shifts inside the rows of 16 lanes, then two row broadcasts.
-// __shfl_down above is two ds_bpermute through the LDS pipeline per step and each step waits for the one before (~0.4 us per sum): where a kernel is a chain of short
-// dependent phases (the multifrontal sweeps, the small-problem solve! kernel) these are what to call.  (Another summation order: other bits than wave_sum.)
-template <int CTRL, int ROW_MASK> __device__ __forceinline__ double dpp_moved(double v) {     // the value from the lane the control names; 0 where there is none or the row is masked
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, ROW_MASK, 0xf, true), hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, ROW_MASK, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double wave_sum_l63(double v) {
-    v += dpp_moved<0x111, 0xf>(v);                                            // row_shr:1
-    v += dpp_moved<0x112, 0xf>(v);                                            // row_shr:2
-    v += dpp_moved<0x114, 0xf>(v);                                            // row_shr:4
-    v += dpp_moved<0x118, 0xf>(v);                                            // row_shr:8   -> lane 15 of every row holds the row's sum
-    v += dpp_moved<0x142, 0xa>(v);                                            // row_bcast:15 into rows 1 and 3
-    v += dpp_moved<0x143, 0xc>(v);                                            // row_bcast:31 into rows 2 and 3 -> lane 63 holds the total
-    return v;
-}
-template <int CTRL, int ROW_MASK> __device__ __forceinline__ double dpp_moved_or_own(double v) {     // ... the lane's own value where there is none
-    const int lo = __builtin_amdgcn_update_dpp(__double2loint(v), __double2loint(v), CTRL, ROW_MASK, 0xf, false), hi = __builtin_amdgcn_update_dpp(__double2hiint(v), __double2hiint(v), CTRL, ROW_MASK, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double wave_max_l63(double v) {
-    v = fmax(v, dpp_moved_or_own<0x111, 0xf>(v));
-    v = fmax(v, dpp_moved_or_own<0x112, 0xf>(v));
-    v = fmax(v, dpp_moved_or_own<0x114, 0xf>(v));
-    v = fmax(v, dpp_moved_or_own<0x118, 0xf>(v));
-    v = fmax(v, dpp_moved_or_own<0x142, 0xa>(v));
-    v = fmax(v, dpp_moved_or_own<0x143, 0xc>(v));
-    return v;
-}
+// ---- wave64 reductions (a CDNA wavefront is 64 lanes): the lane-63 forms wave_sum_l63 / wave_max_l63 are in include/calipso_wave.hpp
 // ... and in EVERY lane (what the callers that read lane 0, or broadcast it, expect): the total travels from lane 63 through a scalar register
 __device__ __forceinline__ double from_lane63(double v) {
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63), __builtin_amdgcn_readlane(__double2loint(v), 63));
@@ -126,17 +99,6 @@ __device__ __forceinline__ void arrow_inverse_small(int n, const double (&u)[MAX
     out[0] = 1.0 / u[0] * x2_1;
 #pragma unroll
     for (int i = 1; i < MAXD; ++i) if (i < n) out[i] = 1.0 / u[0] * out[i];
-}
-
-// value of arrow(u)[k][c] (cone-local indices): diagonal for nonnegative entries, arrow for second-order cones.  jk, jc: the second-order cone entries k and c
-// belong to (-1: a nonnegative entry); st: the first entry of cone jk (read only when jk == jc >= 0).  The dense H of the pivoted fallback (fallback.hip,
-// smallnewton_device.hpp) is assembled from it.
-__device__ __forceinline__ double arrow_entry(int jk, int jc, int st, const double* __restrict__ u, int k, int c) {
-    if (jk < 0 || jc < 0) return (k == c) ? u[k] : 0.0;
-    if (jk != jc) return 0.0;
-    if (k == st) return u[c];
-    if (c == st) return u[k];
-    return (c == k) ? u[st] : 0.0;
 }
 
 }  // namespace calipso

@@ -8,8 +8,9 @@
 // reference's host code takes (exit tests, regularisation loop, refinement loop, step-size searches, filter) is taken on the device; ONE launch carries whole solve!s
 // (or `count` Newton steps) of all instances.
 //
-// Scope: the device-resident QP evaluator of qp.hip (f = c x'Px + q'x, g = Ax - b, cone constraint h - Gx) with nonnegative cones (second-order cones and other
-// evaluators: the general path); residual_norm = constraint_norm = 1 (the defaults of options.jl).  When iterative refinement fails, the reference falls back to
+// Scope: the device-resident QP evaluator of qp.hip (f = c x'Px + q'x, g = Ax - b, cone constraint h - Gx), or a device evaluator compiled into the caller's own
+// library against include/calipso_smallnewton.hpp (set_evaluator: its entry launches its own builds of the same kernels), with nonnegative and second-order cones;
+// residual_norm = constraint_norm = 1 (the defaults of options.jl).  When iterative refinement fails, the reference falls back to
 // `H \ residual` (search_direction.jl:22): by default such an instance stops with status CALIPSO_WARN_REFINEMENT and is left to the general path; with the option
 // lu_fallback = 1 the kernel's LU builds take the fallback themselves (a pivoted LU of the unreduced H in per-instance global scratch) and the iteration goes on.
 //
@@ -24,6 +25,7 @@
 
 #include "internal.hpp"
 #include "device_utils.hpp"
+#include "../../include/calipso_smallnewton.hpp"      // Dm, Lay, Args, the device code, QpEval
 
 struct calipso_hip_smallnewton {
     int nx = 0, ne = 0, nc = 0, batch = 0, device = 0;
@@ -32,6 +34,8 @@ struct calipso_hip_smallnewton {
     calipso::Options opt;
     double objective_scale = 0.5;
     bool shared_qp = false, have_qp = false;
+    calipso_smallnewton_kernels_fn ev = nullptr; int np = 0; bool ev_rtheta = false;      // set_evaluator: the user library's entry, parameters per instance, dR/dtheta provided
+    double *theta = nullptr, *hess = nullptr, *dpt = nullptr; bool theta_shared = false, have_theta = false;      // parameters (batch x np or one row), Lagrangian Hessians (batch x nx^2), the points they were evaluated at (batch x (nx + m))
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     double *P = nullptr, *q = nullptr, *Z = nullptr, *bh = nullptr;      // Lxx = 2 c P (nx x nx), q, Z = [A; -G] (m x nx, ld m), bh = [-b; h]: per instance or shared
@@ -50,68 +54,7 @@ namespace {
 using calipso::Options;
 typedef calipso_hip_smallnewton SN;
 
-#ifndef SN_JB
-#define SN_JB 8          // columns per panel of the LDL^T (bench/small_newton_phases.sh builds other values)
-#endif
-enum { SC_KAPPA = 0, SC_TAU, SC_RHO, SC_EP, SC_EPLAST, SC_ED, SC_EQV, SC_CPV, SC_F, SC_COUNT = 16 };
-enum { CN_TOTAL = 0, CN_OUTER, CN_INNER, CN_FACT, CN_RFAIL, CN_RMAX, CN_RLAST, CN_STEPS, CN_FILTER, CN_TRACE, CN_COUNT = 16 };
-enum { IN_STEP = 0, IN_STEP_T, IN_ROUNDS, IN_NFACT, IN_MH, IN_THETAH, IN_EXIT, IN_OPT, IN_COUNT = 8 };
-enum { MODE_SOLVE = 0, MODE_STEPS = 1, MODE_DIFF = 2 };
-
-struct Dm {
-    int nx, ne, nc, m, n, N, ldz, q, nsoc, wsz, maxd;      // q nonnegative entries first, then nsoc second-order cones (contiguous ranges); wsz = sum of dim^2; ldz: leading dimension of Z in LDS (odd: conflict-free column walks)
-    __host__ __device__ int orr() const { return nx; }
-    __host__ __device__ int os() const { return nx + ne; }
-    __host__ __device__ int oy() const { return nx + ne + nc; }
-    __host__ __device__ int oz() const { return nx + ne + nc + ne; }
-    __host__ __device__ int ot() const { return nx + ne + nc + ne + nc; }
-};
-
-// LDS carve-up (offsets in doubles): the same function sizes the launch on the host and places the pointers on the device
-struct Lay { int Z, S, q, bh, lam, sol, cand, step, res, rerr, corr, rsym, fx, gzx, gh, ghc, cprod, bgrad, wz, wsoc, bsoc, vsoc, D, Dinv, xb, t1, t2, ycol, red, total; };
-__host__ __device__ inline Lay layout(const Dm& d) {
-    Lay L; int o = 0;
-    auto take = [&](int n) { const int at = o; o += (n + 1) & ~1; return at; };
-    L.Z = take(d.ldz * d.nx); L.S = take(d.nx * (d.nx + 1) / 2);
-    L.q = take(d.nx); L.bh = take(d.m); L.lam = take(d.ne);
-    L.sol = take(d.N); L.cand = take(d.N); L.step = take(d.N); L.res = take(d.N); L.rerr = take(d.N); L.corr = take(d.N);
-    L.rsym = take(d.n);
-    L.fx = take(d.nx); L.gzx = take(d.nx); L.gh = take(d.m); L.ghc = take(d.m);
-    L.cprod = take(d.nc); L.bgrad = take(d.nc); L.wz = take(d.nc); L.wsoc = take(d.wsz); L.bsoc = take(d.wsz); L.vsoc = take(4 * d.maxd * d.nsoc);
-    L.D = take(d.nx); L.Dinv = take(d.nx); L.xb = take(d.nx); L.t1 = take(d.m); L.t2 = take(d.m);
-    L.ycol = take(SN_JB * d.nx);
-    L.red = take(64);
-    L.total = o;
-    return L;
-}
-
-struct Args {
-    Dm d; Options o;
-    const double *P, *q, *Z, *bh; long long sP, sq, sZ, sbh;      // element strides per instance (0: one problem shared by all)
-    double *w, *lam, *sc, *filt, *info, *trace, *prof; long long* cnt; int* status;
-    const int *soc_start, *soc_dim, *soc_woff;      // per second-order cone: first cone-local index, dimension, offset of its dim x dim blocks
-    int batch, mode, count, advance, trace_rows;
-    double* stf;                                    // batch x 2 nc: s and t at the last search direction (smallnewton_device.hpp: quirk B-12)
-    const double* rtheta; double* sens; long long srtheta;             // differentiate!: dR/dtheta and the sensitivities, per instance N x count, column-major
-    double* Hs;                                     // lu_fallback: per instance N x N (the unreduced H, then its LU factors)
-};
-
-// the device code, once per workgroup size (launch() picks: sn_threads())
-#define SN_THREADS 64
-namespace t64 {
-#include "smallnewton_device.hpp"
-}
-#undef SN_THREADS
-#define SN_THREADS 128
-namespace t128 {
-#include "smallnewton_device.hpp"
-}
-#undef SN_THREADS
-#define SN_THREADS 256
-namespace t256 {
-#include "smallnewton_device.hpp"
-}
-#undef SN_THREADS
+using namespace calipso::sn;
 
 int fail(SN* s, int code, const std::string& msg) { s->err = msg; return code; }
 thread_local std::string g_sn_err;
@@ -134,28 +77,27 @@ int sn_threads(const SN* s) {
     const size_t per = s->lds_bytes + 1280, lds = 160 * 1024;
     return 6 * per <= lds ? 64 : 3 * per <= lds ? 128 : 256;
 }
-// the build of k_smallnewton for a workgroup size, cone layout and lu_fallback
-const void* sn_kernel(int nt, bool soc, bool lu) {
-    if (lu) {
-        if (nt == 64) return soc ? (const void*)t64::k_smallnewton<true, true> : (const void*)t64::k_smallnewton<false, true>;
-        if (nt == 128) return soc ? (const void*)t128::k_smallnewton<true, true> : (const void*)t128::k_smallnewton<false, true>;
-        return soc ? (const void*)t256::k_smallnewton<true, true> : (const void*)t256::k_smallnewton<false, true>;
-    }
-    if (nt == 64) return soc ? (const void*)t64::k_smallnewton<true, false> : (const void*)t64::k_smallnewton<false, false>;
-    if (nt == 128) return soc ? (const void*)t128::k_smallnewton<true, false> : (const void*)t128::k_smallnewton<false, false>;
-    return soc ? (const void*)t256::k_smallnewton<true, false> : (const void*)t256::k_smallnewton<false, false>;
+// a request to the entry of the handle's evaluator (include/calipso_hip.h: calipso_smallnewton_launch)
+calipso_smallnewton_launch ev_request(const SN* s, int op, int64_t* out) {
+    calipso_smallnewton_launch L;
+    std::memset(&L, 0, sizeof(L));
+    L.op = op; L.abi = CALIPSO_SMALLNEWTON_ABI; L.out = out; L.args_bytes = (int64_t)sizeof(Args);
+    L.threads = sn_threads(s); L.soc = !s->soc_dim.empty(); L.lu = s->lu; L.grid = s->batch; L.lds_bytes = (int64_t)s->lds_bytes; L.stream = (void*)s->stream;
+    return L;
 }
 int grant_lds(SN* s) {
     if (s->lds_bytes <= 64 * 1024) return CALIPSO_OK;
-    for (const bool soc : {false, true}) for (const bool lu : {false, true}) for (const int nt : {64, 128, 256}) (void)calipso::lds_attribute(sn_kernel(nt, soc, lu), 160 * 1024);
-    (void)calipso::lds_attribute((const void*)t64::k_smallnewton_diff<false>, 160 * 1024); (void)calipso::lds_attribute((const void*)t64::k_smallnewton_diff<true>, 160 * 1024);
-    (void)calipso::lds_attribute((const void*)t128::k_smallnewton_diff<false>, 160 * 1024); (void)calipso::lds_attribute((const void*)t128::k_smallnewton_diff<true>, 160 * 1024);
-    (void)calipso::lds_attribute((const void*)t256::k_smallnewton_diff<false>, 160 * 1024); (void)calipso::lds_attribute((const void*)t256::k_smallnewton_diff<true>, 160 * 1024);
+    for (const bool soc : {false, true}) for (const int nt : {64, 128, 256}) {
+        for (const bool lu : {false, true}) (void)calipso::lds_attribute(kernel_of<QpEval>(nt, soc, lu), 160 * 1024);
+        (void)calipso::lds_attribute(diff_kernel_of<QpEval>(nt, soc), 160 * 1024);
+    }
+    if (s->ev) { int64_t out[4] = {0, 0, 0, 0}; calipso_smallnewton_launch L = ev_request(s, CALIPSO_SMALLNEWTON_GRANT_LDS, out); L.lds_bytes = 160 * 1024; (void)s->ev(&L); }
     return CALIPSO_OK;
 }
 
-int launch(SN* s, int mode, int count, int advance) {
-    if (!s->have_qp) return fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_smallnewton: no problem data (calipso_hip_smallnewton_set_qp)");
+int launch(SN* s, int mode, int count, int advance, bool eval_rtheta = false) {
+    if (!s->have_qp && !s->ev) return fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_smallnewton: no problem data (calipso_hip_smallnewton_set_qp or calipso_hip_smallnewton_set_evaluator)");
+    if (s->ev && s->np > 0 && !s->have_theta) return fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_smallnewton: the evaluator takes " + std::to_string(s->np) + " parameters and none were set (calipso_hip_smallnewton_set_parameters)");
     SK(hipSetDevice(s->device));
     Args a;
     a.d = dims_of(s); a.o = s->opt;
@@ -168,24 +110,24 @@ int launch(SN* s, int mode, int count, int advance) {
     a.batch = s->batch; a.mode = mode; a.count = count; a.advance = advance; a.trace_rows = s->trace_rows;
     a.rtheta = s->rtheta; a.sens = s->sens; a.stf = s->stf; a.srtheta = s->diff_shared ? 0 : (long long)a.d.N * (long long)count;
     a.Hs = s->Hs;
+    a.theta = s->theta; a.stheta = s->theta_shared ? 0 : (long long)s->np; a.hess = s->hess; a.dpt = s->dpt; a.eval_rtheta = eval_rtheta ? 1 : 0;
     static_assert(sizeof(Args) <= 3800, "kernel arguments");
     SK(hipEventRecord(s->ev0, s->stream));
     const bool soc = !s->soc_dim.empty();
-    if (mode == MODE_DIFF) {
-        if (sn_threads(s) == 64) {
-            if (soc) hipLaunchKernelGGL(t64::k_smallnewton_diff<true>, dim3((unsigned)s->batch), dim3(64), s->lds_bytes, s->stream, a);
-            else hipLaunchKernelGGL(t64::k_smallnewton_diff<false>, dim3((unsigned)s->batch), dim3(64), s->lds_bytes, s->stream, a);
-        } else if (sn_threads(s) == 128) {
-            if (soc) hipLaunchKernelGGL(t128::k_smallnewton_diff<true>, dim3((unsigned)s->batch), dim3(128), s->lds_bytes, s->stream, a);
-            else hipLaunchKernelGGL(t128::k_smallnewton_diff<false>, dim3((unsigned)s->batch), dim3(128), s->lds_bytes, s->stream, a);
-        } else {
-            if (soc) hipLaunchKernelGGL(t256::k_smallnewton_diff<true>, dim3((unsigned)s->batch), dim3(256), s->lds_bytes, s->stream, a);
-            else hipLaunchKernelGGL(t256::k_smallnewton_diff<false>, dim3((unsigned)s->batch), dim3(256), s->lds_bytes, s->stream, a);
-        }
+    if (s->ev) {      // the evaluator's own builds of the kernels, launched by its entry on the handle's stream
+        int64_t out[4] = {0, 0, 0, 0};
+        calipso_smallnewton_launch L = ev_request(s, CALIPSO_SMALLNEWTON_LAUNCH, out);
+        L.args = &a; L.mode = mode; L.eval_rtheta = eval_rtheta ? 1 : 0;
+        const int rc = s->ev(&L);
+        if (rc != CALIPSO_OK) return fail(s, rc, "calipso_hip_smallnewton: the evaluator's entry refused or failed the launch (" + std::to_string(rc) + ")");
+    } else if (mode == MODE_DIFF) {
+        const int nt = sn_threads(s);
+        void* args[] = {&a};
+        SK(hipLaunchKernel(diff_kernel_of<QpEval>(nt, soc), dim3((unsigned)s->batch), dim3((unsigned)nt), args, s->lds_bytes, s->stream));
     } else {
         const int nt = sn_threads(s);
         void* args[] = {&a};
-        SK(hipLaunchKernel(sn_kernel(nt, soc, s->lu), dim3((unsigned)s->batch), dim3((unsigned)nt), args, s->lds_bytes, s->stream));
+        SK(hipLaunchKernel(kernel_of<QpEval>(nt, soc, s->lu), dim3((unsigned)s->batch), dim3((unsigned)nt), args, s->lds_bytes, s->stream));
     }
     SK(hipGetLastError());
     SK(hipEventRecord(s->ev1, s->stream));
@@ -238,7 +180,7 @@ int32_t calipso_hip_smallnewton_destroy(calipso_hip_smallnewton* s) {
     if (!s) return CALIPSO_OK;
     (void)hipSetDevice(s->device);
     if (s->stream) (void)hipStreamSynchronize(s->stream);
-    for (double* p : {s->P, s->q, s->Z, s->bh, s->w, s->lam, s->sc, s->filt, s->info, s->trace, s->prof, s->rtheta, s->sens, s->stf, s->Hs}) if (p) (void)hipFree(p);
+    for (double* p : {s->P, s->q, s->Z, s->bh, s->theta, s->hess, s->dpt, s->w, s->lam, s->sc, s->filt, s->info, s->trace, s->prof, s->rtheta, s->sens, s->stf, s->Hs}) if (p) (void)hipFree(p);
     if (s->cnt) (void)hipFree(s->cnt);
     if (s->d_soc) (void)hipFree(s->d_soc);
     if (s->status) (void)hipFree(s->status);
@@ -361,6 +303,51 @@ int32_t calipso_hip_smallnewton_set_qp(calipso_hip_smallnewton* s, const double*
     SK(hipMemcpyAsync(s->bh, bh.data(), sizeof(double) * bh.size(), hipMemcpyHostToDevice, s->stream));
     SK(hipStreamSynchronize(s->stream));
     s->shared_qp = shared != 0; s->have_qp = true; s->objective_scale = objective_scale;
+    s->ev = nullptr; s->np = 0; s->ev_rtheta = false; s->have_theta = false;      // (replaces an evaluator)
+    for (double** p : {&s->theta, &s->hess, &s->dpt}) if (*p) { (void)hipFree(*p); *p = nullptr; }
+    return CALIPSO_OK;
+}
+
+// a device evaluator (include/calipso_smallnewton.hpp): its entry's handshake, then the per-instance Lagrangian Hessians; replaces the QP
+int32_t calipso_hip_smallnewton_set_evaluator(calipso_hip_smallnewton* s, calipso_smallnewton_kernels_fn fn, int64_t n_parameters) {
+    if (!s || !fn || n_parameters < 0 || n_parameters > (1 << 20)) return CALIPSO_ERR_ARGUMENT;
+    int64_t out[4] = {0, 0, 0, 0};
+    calipso_smallnewton_launch L = ev_request(s, CALIPSO_SMALLNEWTON_QUERY, out);
+    const int rc = fn(&L);
+    if (rc != CALIPSO_OK) return fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_smallnewton_set_evaluator: the entry refused the query (" + std::to_string(rc) + ")");
+    if (out[0] != CALIPSO_SMALLNEWTON_ABI || out[1] != (int64_t)sizeof(Args) || out[2] != SN_JB)
+        return fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_smallnewton_set_evaluator: the entry was built against another calipso_smallnewton.hpp (ABI " + std::to_string(out[0]) + ", sizeof(Args) " +
+                    std::to_string(out[1]) + ", SN_JB " + std::to_string(out[2]) + "; this library: ABI " + std::to_string(CALIPSO_SMALLNEWTON_ABI) + ", " + std::to_string(sizeof(Args)) + ", " +
+                    std::to_string(SN_JB) + ")");
+    SK(hipSetDevice(s->device));
+    SK(hipStreamSynchronize(s->stream));
+    for (double** p : {&s->P, &s->q, &s->Z, &s->bh, &s->theta, &s->hess, &s->dpt}) if (*p) { (void)hipFree(*p); *p = nullptr; }
+    s->have_qp = false; s->ev = nullptr; s->have_theta = false;
+    const size_t bytes = sizeof(double) * (size_t)s->batch * (size_t)s->nx * (size_t)s->nx;
+    if (hipMalloc((void**)&s->hess, bytes) != hipSuccess) {
+        (void)hipGetLastError(); s->hess = nullptr;
+        return fail(s, CALIPSO_ERR_HIP, "calipso_hip_smallnewton_set_evaluator: the Lagrangian Hessians need batch x nx^2 doubles of device memory (" + std::to_string(bytes) + " bytes)");
+    }
+    SK(hipMemset(s->hess, 0, bytes));
+    const size_t pbytes = sizeof(double) * (size_t)s->batch * (size_t)(s->nx + s->ne + s->nc);
+    SK(hipMalloc((void**)&s->dpt, pbytes)); SK(hipMemset(s->dpt, 0, pbytes));
+    s->ev = fn; s->np = (int)n_parameters; s->ev_rtheta = out[3] != 0;
+    grant_lds(s);
+    return CALIPSO_OK;
+}
+
+// the parameters theta of the evaluator: batch x np (row k for instance k) or one row for all (shared != 0)
+int32_t calipso_hip_smallnewton_set_parameters(calipso_hip_smallnewton* s, const double* theta, int32_t shared) {
+    if (!s || !theta) return CALIPSO_ERR_ARGUMENT;
+    if (!s->ev) return fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_smallnewton_set_parameters: no evaluator (calipso_hip_smallnewton_set_evaluator)");
+    if (s->np == 0) return CALIPSO_OK;
+    SK(hipSetDevice(s->device));
+    SK(hipStreamSynchronize(s->stream));
+    const size_t n = (size_t)s->np * (shared ? 1 : (size_t)s->batch);
+    if (s->theta) { (void)hipFree(s->theta); s->theta = nullptr; }
+    SK(hipMalloc((void**)&s->theta, sizeof(double) * n));
+    SK(hipMemcpy(s->theta, theta, sizeof(double) * n, hipMemcpyHostToDevice));
+    s->theta_shared = shared != 0; s->have_theta = true;
     return CALIPSO_OK;
 }
 
@@ -451,11 +438,9 @@ int32_t calipso_hip_smallnewton_steps(calipso_hip_smallnewton* s, int32_t count,
 // the condensed matrix with the regularisation solve! left, then search_direction_symmetric! per column of dR/dtheta and sensitivity = -1.0 * the result.
 // jacobian_parameters: batch x (N x p), column-major per instance (host), or ONE N x p matrix for all instances (shared != 0: the model of an MPC loop is the same
 // for every problem); sensitivity: batch x (N x p).  status[k]: 0, or 1 when the factorisation's inertia is not (nx, ne + nc, 0).
-int32_t calipso_hip_smallnewton_differentiate(calipso_hip_smallnewton* s, int64_t p, int32_t shared, const double* jacobian_parameters, double* sensitivity, int32_t* status, double* ms) {
-    if (!s || p < 1 || p > (1 << 20) || !jacobian_parameters || !sensitivity) return CALIPSO_ERR_ARGUMENT;
-    SK(hipSetDevice(s->device));
-    const Dm d = dims_of(s);
-    const size_t need = (size_t)s->batch * (size_t)d.N * (size_t)p;
+namespace {
+// the dR/dtheta buffer and the sensitivities (batch x N x p each), grown on demand
+int diff_buffers(SN* s, size_t need) {
     if (need > s->cap_diff) {
         if (s->rtheta) (void)hipFree(s->rtheta);
         if (s->sens) (void)hipFree(s->sens);
@@ -464,9 +449,37 @@ int32_t calipso_hip_smallnewton_differentiate(calipso_hip_smallnewton* s, int64_
         SK(hipMalloc((void**)&s->sens, sizeof(double) * need));
         s->cap_diff = need;
     }
+    return CALIPSO_OK;
+}
+}  // namespace
+
+int32_t calipso_hip_smallnewton_differentiate(calipso_hip_smallnewton* s, int64_t p, int32_t shared, const double* jacobian_parameters, double* sensitivity, int32_t* status, double* ms) {
+    if (!s || p < 1 || p > (1 << 20) || !jacobian_parameters || !sensitivity) return CALIPSO_ERR_ARGUMENT;
+    SK(hipSetDevice(s->device));
+    const Dm d = dims_of(s);
+    const size_t need = (size_t)s->batch * (size_t)d.N * (size_t)p;
+    { const int rc = diff_buffers(s, need); if (rc < 0) return rc; }
     SK(hipMemcpyAsync(s->rtheta, jacobian_parameters, sizeof(double) * (shared ? (size_t)d.N * (size_t)p : need), hipMemcpyHostToDevice, s->stream));
     s->diff_shared = shared != 0;
     const int rc = launch(s, MODE_DIFF, (int)p, 0);
+    if (rc < 0) return rc;
+    SK(hipMemcpy(sensitivity, s->sens, sizeof(double) * need, hipMemcpyDeviceToHost));
+    if (status) SK(hipMemcpy(status, s->status, sizeof(int) * (size_t)s->batch, hipMemcpyDeviceToHost));
+    if (ms) *ms = s->last_ms;
+    return CALIPSO_OK;
+}
+
+// differentiate! with dR/dtheta from the evaluator (residual_jacobian_parameters.jl:1-40 at the resident points, p = n_parameters columns): as above otherwise
+int32_t calipso_hip_smallnewton_differentiate_parameters(calipso_hip_smallnewton* s, double* sensitivity, int32_t* status, double* ms) {
+    if (!s || !sensitivity) return CALIPSO_ERR_ARGUMENT;
+    if (!s->ev || !s->ev_rtheta || s->np < 1)
+        return fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_smallnewton_differentiate_parameters: needs an evaluator that provides dR/dtheta and has parameters");
+    SK(hipSetDevice(s->device));
+    const Dm d = dims_of(s);
+    const size_t need = (size_t)s->batch * (size_t)d.N * (size_t)s->np;
+    { const int rc = diff_buffers(s, need); if (rc < 0) return rc; }
+    s->diff_shared = false;
+    const int rc = launch(s, MODE_DIFF, s->np, 0, true);
     if (rc < 0) return rc;
     SK(hipMemcpy(sensitivity, s->sens, sizeof(double) * need, hipMemcpyDeviceToHost));
     if (status) SK(hipMemcpy(status, s->status, sizeof(int) * (size_t)s->batch, hipMemcpyDeviceToHost));
@@ -481,9 +494,14 @@ int32_t calipso_hip_debug_smallnewton_describe(calipso_hip_smallnewton* s, doubl
     if (!s || !out) return CALIPSO_ERR_ARGUMENT;
     SK(hipSetDevice(s->device));
     const int nt = sn_threads(s);
-    const void* f = sn_kernel(nt, !s->soc_dim.empty(), s->lu);
     int per = 0, cus = 0;
-    SK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, f, nt, s->lds_bytes));
+    if (s->ev) {      // the evaluator's build: its entry answers
+        int64_t o1[4] = {0, 0, 0, 0};
+        const calipso_smallnewton_launch L = ev_request(s, CALIPSO_SMALLNEWTON_OCCUPANCY, o1);
+        const int rc = s->ev(&L);
+        if (rc != CALIPSO_OK) return fail(s, rc, "calipso_hip_debug_smallnewton_describe: the evaluator's entry failed the occupancy query");
+        per = (int)o1[0];
+    } else SK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kernel_of<QpEval>(nt, !s->soc_dim.empty(), s->lu), nt, s->lds_bytes));
     SK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device));
     out[0] = nt; out[1] = (double)s->lds_bytes; out[2] = per; out[3] = cus;
     return CALIPSO_OK;

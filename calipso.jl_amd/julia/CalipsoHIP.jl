@@ -15,6 +15,7 @@
 module CalipsoHIP
 
 using CALIPSO
+import Libdl
 using LinearAlgebra
 using SparseArrays
 
@@ -517,16 +518,17 @@ function CALIPSO.solve!(g::HIPGroup)
 end
 
 # ---- solve! for a batch of small QPs in one kernel launch (include/calipso_hip.h: calipso_hip_smallnewton_*; csrc/smallnewton.hip) ----------------
-"`batch` independent QPs (min c x'Px + q'x s.t. Ax = b, h - Gx >= 0) of one shape: `HIPSmallNewton(nx, ne, nc, batch)`, `set_qp!`, `initialize!`, `solve!` — every instance's whole solve! in ONE launch."
+"`batch` independent QPs (min c x'Px + q'x s.t. Ax = b, h - Gx >= 0) of one shape: `HIPSmallNewton(nx, ne, nc, batch)`, `set_qp!` (or `set_evaluator!` + `set_parameters!` for a nonlinear problem with a device evaluator), `initialize!`, `solve!`, `differentiate!` — every instance's whole solve! in ONE launch."
 mutable struct HIPSmallNewton
     handle::Ptr{Cvoid}
     nx::Int; ne::Int; nc::Int; batch::Int
+    np::Int                     # parameters of the device evaluator (set_evaluator!), 0 for a QP
 end
 function HIPSmallNewton(nx::Integer, ne::Integer, nc::Integer, batch::Integer; device::Integer=0)
     h = Ref{Ptr{Cvoid}}(C_NULL)
     rc = ccall((:calipso_hip_smallnewton_create, lib), Int32, (Int64, Int64, Int64, Int64, Int32, Ptr{Ptr{Cvoid}}), nx, ne, nc, batch, device, h)
     rc == 0 || error("calipso_hip_smallnewton_create failed ($rc): " * unsafe_string(ccall((:calipso_hip_smallnewton_last_error, lib), Cstring, (Ptr{Cvoid},), h[])))
-    s = HIPSmallNewton(h[], nx, ne, nc, batch)
+    s = HIPSmallNewton(h[], nx, ne, nc, batch, 0)
     finalizer(x -> ccall((:calipso_hip_smallnewton_destroy, lib), Int32, (Ptr{Cvoid},), x.handle), s)
     return s
 end
@@ -545,21 +547,22 @@ function set_qp!(s::HIPSmallNewton, P, q, A, b, G, h; objective_scale::Float64=0
     f(a) = isempty(a) ? zeros(1) : collect(Float64, vec(a))
     sn_check(s, ccall((:calipso_hip_smallnewton_set_qp, lib), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Float64, Int32),
                       s.handle, f(P), f(q), f(A), f(b), f(G), f(h), objective_scale, shared ? 1 : 0), "calipso_hip_smallnewton_set_qp")
+    s.np = 0
 end
 "initialize!(solver, guess) for every instance: x0 is nx x batch"
-function initialize!(s::HIPSmallNewton, x0::AbstractMatrix)
+function CALIPSO.initialize!(s::HIPSmallNewton, x0::AbstractMatrix)
     N = s.nx + 2 * s.ne + 3 * s.nc
     w = zeros(N, s.batch); w[1:s.nx, :] .= x0
     sn_check(s, ccall((:calipso_hip_smallnewton_set_state, lib), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), s.handle, w, C_NULL, C_NULL), "calipso_hip_smallnewton_set_state")
 end
 "solve!(solver) for every instance in one launch: (result per instance, launch milliseconds)"
-function solve!(s::HIPSmallNewton)
+function CALIPSO.solve!(s::HIPSmallNewton)
     res = zeros(Int32, s.batch); ms = Ref{Float64}(0.0)
     sn_check(s, ccall((:calipso_hip_smallnewton_solve, lib), Int32, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Float64}), s.handle, res, ms), "calipso_hip_smallnewton_solve")
     return res, ms[]
 end
 "differentiate!(solver) for every instance in one launch (differentiate.jl:1-61): jacobian_parameters is N x p x batch (dR/dtheta per instance) or N x p (one matrix for all); returns (sensitivity N x p x batch, status, ms)"
-function differentiate!(s::HIPSmallNewton, jacobian_parameters::AbstractArray{Float64})
+function CALIPSO.differentiate!(s::HIPSmallNewton, jacobian_parameters::AbstractArray{Float64})
     N = s.nx + 2 * s.ne + 3 * s.nc
     shared = ndims(jacobian_parameters) == 2
     size(jacobian_parameters, 1) == N && (shared || size(jacobian_parameters, 3) == s.batch) || error("jacobian_parameters must be N x p x batch or N x p")
@@ -567,6 +570,26 @@ function differentiate!(s::HIPSmallNewton, jacobian_parameters::AbstractArray{Fl
     J = Array{Float64}(jacobian_parameters); sens = zeros(N, p, s.batch); st = zeros(Int32, s.batch); ms = Ref{Float64}(0.0)
     sn_check(s, ccall((:calipso_hip_smallnewton_differentiate, lib), Int32, (Ptr{Cvoid}, Int64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}), s.handle, p, shared ? 1 : 0, J, sens, st, ms), "calipso_hip_smallnewton_differentiate")
     return sens, st, ms[]
+end
+"differentiate!(solver) with dR/dtheta from the device evaluator at the resident points (p = n_parameters): (sensitivity N x p x batch, status, ms)"
+function CALIPSO.differentiate!(s::HIPSmallNewton)
+    N = s.nx + 2 * s.ne + 3 * s.nc
+    sens = zeros(N, max(s.np, 1), s.batch); st = zeros(Int32, s.batch); ms = Ref{Float64}(0.0)
+    sn_check(s, ccall((:calipso_hip_smallnewton_differentiate_parameters, lib), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}), s.handle, sens, st, ms), "calipso_hip_smallnewton_differentiate_parameters")
+    return sens, st, ms[]
+end
+"""a device evaluator instead of the QP: `symbol` is the entry CALIPSO_SMALLNEWTON_EVALUATOR (include/calipso_smallnewton.hpp) emitted into the HIP shared library at
+`library` (INTEGRATION.md, "Writing an evaluator for the batched kernel"); n_parameters = length of theta per instance"""
+function set_evaluator!(s::HIPSmallNewton, library::AbstractString, symbol::Symbol, n_parameters::Integer)
+    fn = Libdl.dlsym(Libdl.dlopen(library), symbol)
+    sn_check(s, ccall((:calipso_hip_smallnewton_set_evaluator, lib), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int64), s.handle, fn, n_parameters), "calipso_hip_smallnewton_set_evaluator($symbol)")
+    s.np = Int(n_parameters)
+end
+"theta: n_parameters x batch (column k for instance k) or one n_parameters vector for all"
+function set_parameters!(s::HIPSmallNewton, theta::AbstractVecOrMat)
+    shared = ndims(theta) == 1
+    size(theta, 1) == s.np && (shared || size(theta, 2) == s.batch) || error("theta must be n_parameters x batch or n_parameters")
+    sn_check(s, ccall((:calipso_hip_smallnewton_set_parameters, lib), Int32, (Ptr{Cvoid}, Ptr{Float64}, Int32), s.handle, Array{Float64}(theta), shared ? 1 : 0), "calipso_hip_smallnewton_set_parameters")
 end
 "solution.all of every instance (N x batch)"
 function solution(s::HIPSmallNewton)
@@ -617,7 +640,7 @@ function allreduce_sum!(c::HIPComm, v::Vector{Float64})
     return v
 end
 
-export HIPSolver, streams_concurrent, rebind_stream!, spread_streams!, HIPLDLSolver, HIPSparseLDLSolver, hip_sparse_ldl_solver, HIPKKTSolver, hip_ldl_solver, HIPGroup, HIPSmallNewton, set_option!, set_cones!, set_qp!, solution, HIPComm, comm_unique_id, comm_size, gather_status, allreduce_sum!, newton_step!,
+export HIPSolver, streams_concurrent, rebind_stream!, spread_streams!, HIPLDLSolver, HIPSparseLDLSolver, hip_sparse_ldl_solver, HIPKKTSolver, hip_ldl_solver, HIPGroup, HIPSmallNewton, set_option!, set_cones!, set_qp!, set_evaluator!, set_parameters!, solution, HIPComm, comm_unique_id, comm_size, gather_status, allreduce_sum!, newton_step!,
        search_direction_nonsymmetric!, analyze_structure!, clear_structure!, set_stage_parallel!, set_stage_blocks!, declared_structure, kernel_times, sync_scalars!, copy_back!
 
 end # module

@@ -427,12 +427,12 @@ int32_t calipso_hip_small_set(calipso_hip_small*, const double* K, const double*
 int32_t calipso_hip_small_solve(calipso_hip_small*, double* ms);
 int32_t calipso_hip_small_get(calipso_hip_small*, double* X, int64_t* inertia);
 
-/* ---- solve! for a batch of SMALL conic QPs, the whole Newton iteration in one kernel (csrc/smallnewton.hip) ----------------------------------
+/* ---- solve! for a batch of SMALL conic problems, the whole Newton iteration in one kernel (csrc/smallnewton.hip) ------------------------------
  * Solver / initialize! / solve! (src/solver/solver.jl:46-150, initialize.jl:9-48, solve.jl:8-377) for `batch` independent problems of ONE shape that are too small
  * for the general path to be anything but launch latency (the MPC problems of examples/autotuning/cartpole.jl:179-227: n = 89): one workgroup per instance, problem
  * data ([A; -G], q, [-b; h]; the Hessian block stays in L2), iterates and the factor in the compute unit's LDS, every decision of solve.jl:98-368 (exit tests, inertia_correction!, iterative_refinement!, cone search,
- * filter line search, outer updates) on the device, ONE launch per call.  Evaluator: the QP of calipso_hip_qp_attach (min c x'Px + q'x s.t. Ax = b, h - Gx >= 0) with
- * nonnegative and second-order cones (dimension <= 16; wider: the general path); residual_norm = constraint_norm = 1.  Points have the layout of point.jl:13-22 (N = nx + 2 ne + 3 nc).  Limits: nx <= 128 and the
+ * filter line search, outer updates) on the device, ONE launch per call.  Evaluator: the QP of calipso_hip_qp_attach (min c x'Px + q'x s.t. Ax = b, h - Gx >= 0), or a
+ * device evaluator of the caller's (set_evaluator below: nonlinear f, g, h with parameters theta), with nonnegative and second-order cones (dimension <= 16; wider: the general path); residual_norm = constraint_norm = 1.  Points have the layout of point.jl:13-22 (N = nx + 2 ne + 3 nc).  Limits: nx <= 128 and the
  * instance must fit 160 KB of LDS (n up to ~200), else CALIPSO_ERR_ARGUMENT at create: the general path (calipso_hip_create + groups) takes those.
  *   create(nx, ne, nc, batch, device)        set_option(name, value): options.jl:6-59 by name; plus "threads" = threads per instance (0: chosen by the LDS footprint so that
  *                                            a compute unit holds as many instances as fit; 64, 128 or 256 force a build of the kernel); "lu_fallback" = 0 (default) or 1:
@@ -469,6 +469,42 @@ int32_t calipso_hip_smallnewton_steps(calipso_hip_smallnewton*, int32_t count, i
  * the condensed solve is five digits short of the reference's QDLDL at a solution); with second-order cones the unrefined solve IS the reference's result (quirk B-3).
  * The cone Jacobians are those of the last search direction, as the reference's fields are (quirk B-12).  status[k] = 0, or 1 when the inertia of the factorisation is not (nx, ne + nc, 0) (the reference does not look). */
 int32_t calipso_hip_smallnewton_differentiate(calipso_hip_smallnewton*, int64_t p, int32_t shared, const double* jacobian_parameters, double* sensitivity, int32_t* status, double* ms);
+/* Nonlinear problems: a DEVICE EVALUATOR compiled into the caller's own HIP library against include/calipso_smallnewton.hpp (HIP C++; INTEGRATION.md "Writing an
+ * evaluator for the batched kernel").  The evaluator is a C++ type whose workgroup-cooperative hooks give f and [g; h] at a point (evaluate!, solve.jl:78,231,278), fx,
+ * [gx; hx] and the Lagrangian Hessian fxx + (y'g)xx + (z'h)xx at the solution (solve.jl:100,175; differentiate.jl:3) and, optionally, dR/dtheta
+ * (residual_jacobian_parameters.jl:1-40).  CALIPSO_SMALLNEWTON_EVALUATOR(Type, symbol) instantiates every build of the kernels for that type in the caller's code
+ * object and emits  extern "C" int32_t symbol(const calipso_smallnewton_launch*): the library asks it for its ABI version, sizeof(Args), SN_JB and whether it
+ * provides dR/dtheta, has it grant the LDS, and has it launch the right build on the handle's stream (as a calipso_device_eval_fn enqueues on the stream it is given).
+ *   set_evaluator(fn, n_parameters)          checks the handshake (a mismatch: CALIPSO_ERR_ARGUMENT and a message), allocates the per-instance Hessians (batch x nx^2
+ *                                            doubles: the message states the bytes when that fails); replaces set_qp, as set_qp replaces it; solve / steps /
+ *                                            differentiate need one of the two.  The cone layout, options and state calls are the same for both.
+ *   set_parameters(theta, shared)            theta: batch x n_parameters (row k for instance k) or ONE n_parameters vector for all (shared != 0); required before a
+ *                                            launch when n_parameters > 0
+ *   differentiate_parameters(sens, status, ms)  differentiate! with dR/dtheta from the evaluator at the resident points (p = n_parameters): sensitivity batch x (N x p)
+ *                                            as calipso_hip_smallnewton_differentiate, which keeps taking a caller-given dR/dtheta under an evaluator too
+ *   differentiate! takes [gx; hx] and the Hessian where the last search direction evaluated them (the iterate before the final one, as the cone Jacobians:
+ *   quirk B-12) and dR/dtheta at the solution, as the reference does.  calipso_hip_debug_smallnewton_describe answers for the evaluator's build of the kernel (its entry's occupancy query). */
+#define CALIPSO_SMALLNEWTON_ABI 1
+enum { CALIPSO_SMALLNEWTON_QUERY = 0, CALIPSO_SMALLNEWTON_GRANT_LDS = 1, CALIPSO_SMALLNEWTON_OCCUPANCY = 2, CALIPSO_SMALLNEWTON_LAUNCH = 3 };
+typedef struct calipso_smallnewton_launch {
+    int32_t op;                 /* CALIPSO_SMALLNEWTON_QUERY / _GRANT_LDS / _OCCUPANCY / _LAUNCH */
+    int32_t abi;                /* CALIPSO_SMALLNEWTON_ABI of the library that asks */
+    int64_t* out;               /* QUERY: out[4] = {ABI, sizeof(Args), SN_JB, 1 if dR/dtheta is provided}; OCCUPANCY: out[0] = instances a compute unit holds */
+    const void* args;           /* LAUNCH: the kernels' argument block (calipso::sn::Args) */
+    int64_t args_bytes;         /* its size, sizeof(Args) of the library */
+    int32_t mode;               /* 0 solve!, 1 Newton steps, 2 differentiate! */
+    int32_t threads;            /* threads per instance: 64, 128 or 256 */
+    int32_t soc, lu;            /* second-order cones in the layout; the lu_fallback build */
+    int32_t eval_rtheta;        /* differentiate!: dR/dtheta from the evaluator */
+    int32_t reserved;
+    int64_t grid;               /* instances = workgroups */
+    int64_t lds_bytes;          /* dynamic LDS per workgroup (GRANT_LDS: the size to grant) */
+    void* stream;               /* hipStream_t to launch on */
+} calipso_smallnewton_launch;
+typedef int32_t (*calipso_smallnewton_kernels_fn)(const calipso_smallnewton_launch*);
+int32_t calipso_hip_smallnewton_set_evaluator(calipso_hip_smallnewton*, calipso_smallnewton_kernels_fn fn, int64_t n_parameters);
+int32_t calipso_hip_smallnewton_set_parameters(calipso_hip_smallnewton*, const double* theta, int32_t shared);
+int32_t calipso_hip_smallnewton_differentiate_parameters(calipso_hip_smallnewton*, double* sensitivity, int32_t* status, double* ms);
 
 /* ---- multi-GPU exchange of the batched path: RCCL over xGMI, one process per GPU ---------------------------------
  * Problem instances are sharded block-contiguously over ranks and never interact (the reference's `Solver`s are independent); the

@@ -1,6 +1,7 @@
-// smallnewton_device.hpp — the device side of csrc/smallnewton.hip, included once per workgroup size inside a namespace of its own (SN_THREADS = threads per
-// instance = per workgroup): two wavefronts per instance let a compute unit hold four C5-sized instances, four wavefronts are faster per instance when the LDS
-// footprint allows two instances anyway.  Everything here is __device__ code over the common types (Dm, Lay, Args, the enums) of smallnewton.hip.
+// calipso_smallnewton_device.hpp — the device side of the batched small-problem solve! (csrc/smallnewton.hip), included by calipso_smallnewton.hpp once per
+// workgroup size inside a namespace of its own (SN_THREADS = threads per instance = per workgroup): two wavefronts per instance let a compute unit hold four
+// C5-sized instances, four wavefronts are faster per instance when the LDS footprint allows two instances anyway.  Everything here is __device__ code over the
+// common types (Dm, Lay, Args, the enums) of calipso_smallnewton.hpp, templated over the evaluator Ev (QpEval, or a user's: calipso_smallnewton.hpp).
 constexpr int NT = SN_THREADS, NW = NT / 64;
 static_assert(NT == 64 || NT == 128 || NT == 256, "one, two or four wavefronts per instance");
 
@@ -145,13 +146,16 @@ __device__ __forceinline__ double recip(double d) {
     return d == 0.0 ? r0 : r;
 }
 
-template <bool SOC> struct CtxT {
+template <class Ev, bool SOC> struct CtxT {
     Dm d; const Options* o;
-    const double* Lg;                               // the QP's Hessian block P of this instance, column-major nx x nx, in global memory
+    const double* Lg;                               // the Hessian block of this instance, column-major nx x nx, in global memory: the QP's P, or what the evaluator wrote to Hw
+    double* Hw;                                     // (evaluators other than the QP) the instance's nx x nx of Args::hess
+    const double* theta;                            // (evaluators other than the QP) the instance's parameters, global
     double *Z, *S, *q, *bh, *lam, *sol, *cand, *step, *res, *rerr, *corr, *rsym, *fx, *gzx, *gh, *ghc, *cprod, *bgrad, *wz, *wsoc, *bsoc, *vsoc, *D, *Dinv, *xb, *t1, *t2, *ycol, *red;
     const int *soc_start, *soc_dim, *soc_woff;
     double* filt;                                   // global: [pairs theta | pairs merit | cache theta | cache merit | saved theta | saved merit], max_filter each
     double* stf;                                    // global: the slacks s and t (nc each) the cone Jacobians of the LAST search direction were formed at (differentiate!'s quirk B-12)
+    double* dpt;                                    // (evaluators other than the QP) global: x and [y; z] the derivatives of the LAST search direction were evaluated at
     // uniform scalars (every thread holds the same values)
     double kappa, tau, rho, ep, ep_last, ed, fcur, fcand, eqv, cpv, omega_y, kyy;
     long long filter_index, nfact_total, rfail, rmax, rlast, nsteps;
@@ -166,25 +170,29 @@ template <bool SOC> struct CtxT {
     __device__ __forceinline__ void stamp(int) {}
 #endif
 
-    // ---- evaluate! of the QP (qp.hip): which = the point (sol / cand) ------------------------------------------------------------------------
-    __device__ __forceinline__ double eval_objective(const double* p) {        // f = 1/2 x'Lxx x + q'x   (uses xb as scratch)
-        mvg_partial(Lg, d.nx, p, ycol);
+    // ---- what an evaluator may call (calipso_smallnewton.hpp) ------------------------------------------------------------------------------------
+    static constexpr int threads = NT;
+    template <int K> __device__ __forceinline__ void sum(double (&v)[K]) { block_sum(v, red); }        // workgroup sums, the result in every thread
+    __device__ __forceinline__ static void matvec(const double* M, int ld, int rows, int cols, const double* x, double* y, const double* add) { mv_n(M, ld, rows, cols, x, y, add); }
+    __device__ __forceinline__ static void matvec_t(const double* M, int ld, int rows, int cols, const double* x, double* y, const double* add) { mv_t(M, ld, rows, cols, x, y, add); }
+    __device__ __forceinline__ static void hess_partial(const double* __restrict__ M, int n, const double* x, double* part) { mvg_partial(M, n, x, part); }
+    __device__ __forceinline__ static double hess_sum(const double* part, int n, int r) { return mvg_sum(part, n, r); }
+
+    // ---- evaluate! through the evaluator at a point p (sol / cand) ----------------------------------------------------------------------------
+    __device__ __forceinline__ double eval_objective(const double* p) { return Ev::objective(*this, p); }
+    __device__ __forceinline__ void eval_constraints(const double* p, double* out) {      // [g; h]
+        Ev::constraints(*this, p, out);
         __syncthreads();
-        double v[2] = {0.0, 0.0};
-        for (int i = tid; i < d.nx; i += NT) { v[0] += p[i] * mvg_sum(ycol, d.nx, i); v[1] += q[i] * p[i]; }
-        block_sum(v, red);
-        return 0.5 * v[0] + v[1];
     }
-    __device__ __forceinline__ void eval_constraints(const double* p, double* out) {      // [g; h] = [A; -G] x + [-b; hvec]
-        mv_n(Z, d.ldz, d.m, d.nx, p, out, bh);
-        __syncthreads();
-    }
-    __device__ __forceinline__ void eval_gradients(const double* p) {                     // fx = Lxx x + q ; gzx = A'y + (-G)'z
-        mvg_partial(Lg, d.nx, p, ycol);
-        mv_t(Z, d.ldz, d.m, d.nx, p + d.oy(), gzx, nullptr);
-        __syncthreads();
-        for (int i = tid; i < d.nx; i += NT) fx[i] = mvg_sum(ycol, d.nx, i) + q[i];
-        __syncthreads();
+    // fx, gzx = gx'y + hx'z, and (evaluators other than the QP) [gx; hx] into Z and the Lagrangian Hessian into Hw (= Lg) at the point p: solve.jl:100-104, 175-181
+    __device__ __forceinline__ void eval_gradients(const double* p) {
+        if constexpr (Ev::constant_derivatives) Ev::gradients(*this, p);
+        else {
+            Ev::derivatives(*this, p);
+            __syncthreads();
+            mv_t(Z, d.ldz, d.m, d.nx, p + d.oy(), gzx, nullptr);
+            __syncthreads();
+        }
     }
 
     // cone_target (cone.jl:55-59): 1 for nonnegative entries and for the first entry of a second-order cone, 0 for its other entries
@@ -717,7 +725,7 @@ struct StepOut { int exit_kind = 0; int rc = 0; double step_size = 1.0, step_siz
 
 // one pass of the inner loop body of solve! (solve.jl:98-353); equality_violation / cone_product_violation as the caller holds them (:85-86, :332-333).
 // LU: the reference's H \ residual where iterative refinement fails, in the instance's N x N scratch Hg (else the instance stops there: CALIPSO_WARN_REFINEMENT)
-template <bool SOC, bool LU> __device__ __forceinline__ StepOut inner_iteration(CtxT<SOC>& c, bool may_converge, double* Hg) {
+template <class Ev, bool SOC, bool LU> __device__ __forceinline__ StepOut inner_iteration(CtxT<Ev, SOC>& c, bool may_converge, double* Hg) {
     const Dm& d = c.d; const Options& o = *c.o; const int tid = c.tid;
     StepOut out;
     double* sol = c.sol; double* cand = c.cand; double* step = c.step; double* res = c.res;
@@ -784,11 +792,15 @@ template <bool SOC, bool LU> __device__ __forceinline__ StepOut inner_iteration(
         c.cpv <= o.complementarity_tolerance) { out.exit_kind = 1; return out; }                           // :138-143
     if (optimality <= fmax(o.central_path_update_tolerance * c.kappa, o.optimality_tolerance)) { out.exit_kind = 2; return out; }      // :165
     c.stamp(0);
-    // :175-185: the Hessian and the Jacobians of a QP are constant; the cone Jacobians are functions of (s, t) formed where they are used
+    // :175-185: the Hessian and the Jacobians came with the gradients above (a QP's are constant); the cone Jacobians are functions of (s, t) formed where they are used
     // ---- :187 search_direction!: inertia_correction! (inertia.jl:30-80, quirk B-1: IC-3 always takes max(min_regularization, scaling_regularization_last * eps_last))
     // :183-185 cone!(jacobian = true): the cone Jacobians of this search direction are functions of THIS point's s and t.  The reference keeps them as fields, and
     // differentiate! (differentiate.jl:13-16) reads them where the last search direction left them — at the iterate BEFORE the final one (quirk B-12): remember which
     for (int i = tid; i < d.nc; i += NT) { c.stf[i] = sol[d.os() + i]; c.stf[d.nc + i] = sol[d.ot() + i]; }
+    if constexpr (!Ev::constant_derivatives) {      // ... and so are [gx; hx] and the Hessian (:175-181 evaluates them here, differentiate! does not evaluate them again)
+        for (int i = tid; i < d.nx; i += NT) c.dpt[i] = sol[i];
+        for (int i = tid; i < d.m; i += NT) c.dpt[d.nx + i] = sol[d.oy() + i];
+    }
     {   // (one loop, ONE instance of the factorisation's code: IC-1, then IC-4 as often as the inertia test fails)
         int zero = 0, count = 0;
         c.ep = o.primal_regularization_initial; c.ed = o.dual_regularization_initial;
@@ -871,11 +883,12 @@ template <bool SOC, bool LU> __device__ __forceinline__ StepOut inner_iteration(
     for (int i = tid; i < d.nc; i += NT) cand[d.ot() + i] = sol[d.ot() + i] - a_t * step[d.ot() + i];
     __syncthreads();
     auto candidate_merit = [&](double& Mh, double& thetah) {                                                // :231-250 / :278-297: evaluate!(objective, equality, cone), cone!(barrier), merit, violation
-        mvg_partial(c.Lg, d.nx, cand, c.ycol);
-        mv_n(c.Z, d.ldz, d.m, d.nx, cand, c.ghc, c.bh);
+        double fgen = 0.0;
+        if constexpr (Ev::constant_derivatives) Ev::candidate_begin(c, cand, c.ghc);      // (the QP: f's two sums join the merit's reduction below)
+        else { fgen = Ev::objective(c, cand); Ev::constraints(c, cand, c.ghc); }
         __syncthreads();
-        double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};      // Phi, lambda'r, r'r, theta numerator, x'Lxx x, q'x
-        for (int i = tid; i < d.nx; i += NT) { v[4] += cand[i] * mvg_sum(c.ycol, d.nx, i); v[5] += c.q[i] * cand[i]; }
+        double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};      // Phi, lambda'r, r'r, theta numerator, the QP's x'Lxx x and q'x
+        if constexpr (Ev::constant_derivatives) for (int i = tid; i < d.nx; i += NT) Ev::candidate_terms(c, cand, i, v[4], v[5]);
         for (int i = tid; i < d.nc; i += NT) { const double sl = cand[d.os() + i]; if (i < d.q) v[0] += log(sl); v[3] += fabs(c.ghc[d.ne + i] - sl); }
         for (int j = tid; SOC && j < d.nsoc; j += NT) {
             const int st = c.soc_start[j], dm = c.soc_dim[j];
@@ -886,7 +899,8 @@ template <bool SOC, bool LU> __device__ __forceinline__ StepOut inner_iteration(
         }
         for (int i = tid; i < d.ne; i += NT) { const double r = cand[d.orr() + i]; v[1] += lam[i] * r; v[2] += r * r; v[3] += fabs(c.ghc[i] - r); }
         block_sum(v, c.red);
-        c.fcand = 0.5 * v[4] + v[5];
+        if constexpr (Ev::constant_derivatives) c.fcand = Ev::candidate_objective(v[4], v[5]);
+        else c.fcand = fgen;
         Mh = c.fcand + (v[1] + 0.5 * c.rho * v[2]) - c.kappa * v[0];
         thetah = (d.ne + d.nc > 0) ? v[3] / (double)(d.ne + d.nc) : 0.0;
     };
@@ -930,11 +944,11 @@ template <bool SOC, bool LU> __device__ __forceinline__ StepOut inner_iteration(
 }
 
 // the instance's context: the LDS carve, the problem data and the point into LDS (every thread of the workgroup; ends with the data written, not yet synchronised)
-template <bool SOC> __device__ __forceinline__ void bind_instance(CtxT<SOC>& c, const Args& a, double* sm, int inst, int tid) {
+template <class Ev, bool SOC> __device__ __forceinline__ void bind_instance(CtxT<Ev, SOC>& c, const Args& a, double* sm, int inst, int tid) {
     const Dm d = a.d;
     const Lay L = layout(d);
     c.d = d; c.o = &a.o; c.tid = tid;
-    c.Lg = a.P + (size_t)inst * a.sP; c.Z = sm + L.Z; c.S = sm + L.S; c.q = sm + L.q; c.bh = sm + L.bh; c.lam = sm + L.lam; c.sol = sm + L.sol; c.cand = sm + L.cand; c.step = sm + L.step;
+    c.Z = sm + L.Z; c.S = sm + L.S; c.q = sm + L.q; c.bh = sm + L.bh; c.lam = sm + L.lam; c.sol = sm + L.sol; c.cand = sm + L.cand; c.step = sm + L.step;
     c.res = sm + L.res; c.rerr = sm + L.rerr; c.corr = sm + L.corr; c.rsym = sm + L.rsym;
     c.fx = sm + L.fx; c.gzx = sm + L.gzx; c.gh = sm + L.gh; c.ghc = sm + L.ghc; c.cprod = sm + L.cprod; c.bgrad = sm + L.bgrad; c.wz = sm + L.wz; c.wsoc = sm + L.wsoc; c.bsoc = sm + L.bsoc; c.vsoc = sm + L.vsoc;
     c.soc_start = a.soc_start; c.soc_dim = a.soc_dim; c.soc_woff = a.soc_woff;
@@ -942,11 +956,8 @@ template <bool SOC> __device__ __forceinline__ void bind_instance(CtxT<SOC>& c, 
     c.mf = (int)a.o.max_filter;
     c.filt = a.filt + (size_t)inst * 6 * (size_t)c.mf;
     c.stf = a.stf + (size_t)inst * 2 * (size_t)(d.nc > 0 ? d.nc : 1);
-    const double* q = a.q + (size_t)inst * a.sq;
-    const double* Zg = a.Z + (size_t)inst * a.sZ; const double* bh = a.bh + (size_t)inst * a.sbh;
-    for (int e = tid; e < d.m * d.nx; e += NT) c.Z[(e % d.m) + (e / d.m) * d.ldz] = Zg[e];
-    for (int i = tid; i < d.nx; i += NT) c.q[i] = q[i];
-    for (int i = tid; i < d.m; i += NT) c.bh[i] = bh[i];
+    if constexpr (Ev::constant_derivatives) Ev::bind(c, a, inst);            // (the QP: its data into LDS)
+    else { c.theta = a.theta + (size_t)inst * a.stheta; c.Hw = a.hess + (size_t)inst * d.nx * d.nx; c.Lg = c.Hw; c.dpt = a.dpt + (size_t)inst * (d.nx + d.m); }
     const double* w = a.w + (size_t)inst * d.N;
     for (int i = tid; i < d.N; i += NT) c.sol[i] = w[i];
 }
@@ -954,12 +965,12 @@ template <bool SOC> __device__ __forceinline__ void bind_instance(CtxT<SOC>& c, 
 // differentiate!(solver) for every instance of the batch (differentiate.jl:1-61) at the resident point: the condensed matrix for the regularisation the last
 // factorisation of solve! left (:13-20: residual_jacobian_variables!, the symmetric form, factorize!), then per parameter column search_direction_symmetric! on
 // the column of dR/dtheta (:29-52) and sensitivity = -1.0 * the result (:55-57).  dR/dtheta comes from the caller (residual_jacobian_parameters.jl:1-40 is the
-// caller's model: for the parametric QPs of the MPC loops it is constant); `count` = its columns.
-template <bool SOC> __global__ __launch_bounds__(NT, 2) void k_smallnewton_diff(Args a) {
+// caller's model: for the parametric QPs of the MPC loops it is constant) or, with a.eval_rtheta, from the evaluator at the resident point; `count` = its columns.
+template <class Ev, bool SOC> __global__ __launch_bounds__(NT, 2) void k_smallnewton_diff(Args a) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int inst = blockIdx.x, tid = threadIdx.x;
     if (inst >= a.batch) return;
-    CtxT<SOC> c;
+    CtxT<Ev, SOC> c;
     bind_instance(c, a, sm, inst, tid);
     const Dm& d = c.d;
     const double* gsc = a.sc + (size_t)inst * SC_COUNT;
@@ -971,12 +982,29 @@ template <bool SOC> __global__ __launch_bounds__(NT, 2) void k_smallnewton_diff(
     c.tlast = wall_clock64();
 #endif
     __syncthreads();
+    double* Jw = a.rtheta + (size_t)inst * (size_t)a.srtheta;
+    if constexpr (!Ev::constant_derivatives) {
+        // [gx; hx] and the Hessian where the reference's fields hold them: evaluated by the last search direction (solve.jl:175-181) at the iterate BEFORE the
+        // final one, as the cone Jacobians (quirk B-12); differentiate.jl:3 evaluates only the parameter Jacobians, at the solution
+        for (int i = tid; i < d.N; i += NT) c.cand[i] = c.sol[i];
+        __syncthreads();
+        for (int i = tid; i < d.nx; i += NT) c.cand[i] = c.dpt[i];
+        for (int i = tid; i < d.m; i += NT) c.cand[d.oy() + i] = c.dpt[d.nx + i];
+        __syncthreads();
+        c.eval_gradients(c.cand);
+        if constexpr (Ev::provides_jacobian_parameters) if (a.eval_rtheta) {
+            for (size_t e = tid; e < (size_t)d.N * a.count; e += NT) Jw[e] = 0.0;
+            __syncthreads();
+            Ev::jacobian_parameters(c, c.sol, Jw);
+            __syncthreads();
+        }
+    }
     // the cone Jacobians as the reference's differentiate! finds them: formed at the s, t of the last search direction (quirk B-12), not at the solution
     for (int i = tid; i < d.nc; i += NT) { c.sol[d.os() + i] = c.stf[i]; c.sol[d.ot() + i] = c.stf[d.nc + i]; }
     __syncthreads();
     int zero = 0;
     const bool inertia_ok = c.factorize(zero);
-    const double* J = a.rtheta + (size_t)inst * (size_t)a.srtheta;
+    const double* J = Jw;
     double* Sn = a.sens + (size_t)inst * (size_t)d.N * (size_t)a.count;
     for (int j = 0; j < a.count; ++j) {
         for (int i = tid; i < d.N; i += NT) c.res[i] = J[(size_t)j * d.N + i];
@@ -1003,11 +1031,11 @@ template <bool SOC> __global__ __launch_bounds__(NT, 2) void k_smallnewton_diff(
     if (tid == 0) a.status[inst] = inertia_ok ? 0 : 1;      // (1: the factorisation's inertia is not (nx, ne + nc, 0); the reference does not look, the sensitivities are what they are)
 }
 
-template <bool SOC, bool LU> __global__ __launch_bounds__(NT, 2) void k_smallnewton(Args a) {
+template <class Ev, bool SOC, bool LU> __global__ __launch_bounds__(NT, 2) void k_smallnewton(Args a) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int inst = blockIdx.x, tid = threadIdx.x;
     if (inst >= a.batch) return;
-    CtxT<SOC> c;
+    CtxT<Ev, SOC> c;
     bind_instance(c, a, sm, inst, tid);
     const Dm d = a.d;
     const long long mf_ = c.mf;
@@ -1070,7 +1098,7 @@ template <bool SOC, bool LU> __global__ __launch_bounds__(NT, 2) void k_smallnew
         const long long fidx = c.filter_index;
         const bool restore = !solving && !a.advance;
         if (restore && tid == 0) for (long long i = 0; i < fidx; ++i) { c.filt[4 * mf_ + i] = c.filt[i]; c.filt[5 * mf_ + i] = c.filt[mf_ + i]; }
-        last = inner_iteration<SOC, LU>(c, solving, LU ? a.Hs + (size_t)inst * d.N * d.N : nullptr);
+        last = inner_iteration<Ev, SOC, LU>(c, solving, LU ? a.Hs + (size_t)inst * d.N * d.N : nullptr);
         if (last.rc < 0 || last.rc == CALIPSO_WARN_REFINEMENT || (LU && last.rc == CALIPSO_WARN_ZERO_PIVOT)) { status = last.rc < 0 ? last.rc : -100 - last.rc; break; }
         if (solving) {
             if (last.exit_kind == 1) { status = 1; break; }                                                  // :138-160

@@ -8,6 +8,9 @@ steps per instance in one launch; the same problems through the oracle on one ho
   --evaluator cartpole   instead of random QPs: the cart-pole MPC problem itself (nx 49, ne 40, np 102) through the device evaluator of
                       tests/device_eval_small/cartpole_mpc.hip, per-instance parameters (x_init and weights moved by a few per cent): solve!s, Newton steps and
                       differentiate!s (dR/dtheta from the evaluator) per second for the batch (default 4096), beside the oracle's solve! + differentiate! on one core
+  --vjp               also differentiate! in reverse mode (SmallNewtonBatch.vjp): VJPs per second for k = 1 cotangent per instance — with --evaluator cartpole the
+                      autotuning row (e_{u_1}, the first action) contracted with the evaluator's dR/dtheta, beside the forward differentiates (102 columns); for
+                      QPs a random cotangent on x with the gradients of all QP data (grad_qp)
 e.g. the cold-started SOC batch of DESIGN 5.00: python bench/small_newton_rate.py 48 12 0 4096 --soc 4:4,4,4,4 --lu-fallback --general 8"""
 import json, os, sys, time
 import numpy as np
@@ -16,7 +19,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle")]
 from __graft_entry__ import load_package
 import problems as pr
 
-def evaluator_rate(name, B):
+def evaluator_rate(name, B, vjp=False):
     import ctypes
     if name != "cartpole":
         raise SystemExit("--evaluator: cartpole")
@@ -47,6 +50,11 @@ def evaluator_rate(name, B):
            "solve": {"launch_ms": ms, "launch_ms_all": ms_all, "converged": int((res == 1).sum()), "solves_per_s": B / (ms * 1e-3), "newton_steps_total": steps,
                      "newton_steps_per_s": steps / (ms * 1e-3), "mean_iterations": float(st["counters"]["total_iterations"].mean())},
            "differentiate": {"launch_ms": dms, "differentiates_per_s": B / (dms * 1e-3)}}
+    if vjp:      # reverse mode: one cotangent per instance, the autotuning row e_{u_1} (u_1 after the 4 states of stage 1), gradient over theta
+        e = np.zeros((B, sn.N)); e[:, 4] = 1.0
+        vms = [sn.vjp(e, adjoint=False)["ms"] for _ in range(3)]
+        out["vjp"] = {"k": 1, "cotangent": "e_u1", "grad": "theta", "launch_ms": min(vms), "launch_ms_all": vms, "vjps_per_s": B / (min(vms) * 1e-3),
+                      "forward_over_reverse_ms": dms / min(vms)}
     try:
         import oracle
         from test_oracle_solve import run as run_oracle
@@ -69,9 +77,10 @@ def main():
         if name not in a: return None
         i = a.index(name); v = a[i + 1]; del a[i:i + 2]; return v
     ev = None
+    vjp = flag("--vjp")
     if "--evaluator" in a:
         i = a.index("--evaluator"); ev = a[i + 1]; del a[i:i + 2]
-        return evaluator_rate(ev, int(a[0]) if a else 4096)
+        return evaluator_rate(ev, int(a[0]) if a else 4096, vjp)
     lu = flag("--lu-fallback")
     soc_arg, general = opt("--soc"), int(opt("--general") or 0)
     nx, ne, nc = (int(a[0]), int(a[1]), int(a[2])) if len(a) >= 3 else (49, 40, 0)
@@ -114,6 +123,10 @@ def main():
                     "newton_steps_per_s": float(steps.sum()) / (ms * 1e-3), "mean_iterations": float(its.mean()), "max_iterations": int(its.max()),
                     "mean_factorizations": float(stt["counters"]["factorizations"].mean()), "max_refinement_rounds": int(stt["counters"]["max_refinement_rounds"].max()),
                     "status_counts": {str(int(v)): int((res == v).sum()) for v in np.unique(res)}, "fallbacks_per_solve": float(stt["counters"]["refinement_failures"].mean())}
+    if vjp:          # reverse mode at the solutions: one random cotangent on x per instance, the gradients of all QP data
+        v = rng.standard_normal((B, nx))
+        vms = [sn.vjp(v, adjoint=False, qp=True)["ms"] for _ in range(3)]
+        out["vjp"] = {"k": 1, "cotangent": "x", "grad": "qp", "launch_ms": min(vms), "launch_ms_all": vms, "vjps_per_s": B / (min(vms) * 1e-3)}
     if general:      # the general path on the first `general` problems, one handle at a time (its fallback: fallback.hip)
         tg, itg = [], []
         for k in range(min(general, nprob)):

@@ -831,7 +831,8 @@ class SmallNewtonBatch:
     csrc/smallnewton.hip).  QP data as qp_attach: min c x'Px + q'x s.t. Ax = b, h - Gx >= 0 (nonnegative cones).  options={...} go to set_option: the reference's
     options by name, "threads" (0, 64, 128, 256) and "lu_fallback" (0 or 1: where iterative refinement fails, take the reference's H \\ residual inside the kernel
     instead of stopping the instance with -102; costs batch x N^2 doubles of device memory).  Nonlinear problems: set_evaluator with a device evaluator compiled
-    into a HIP library of the caller's (include/calipso_smallnewton.hpp), set_parameters, differentiate() with dR/dtheta from the evaluator."""
+    into a HIP library of the caller's (include/calipso_smallnewton.hpp), set_parameters, differentiate() with dR/dtheta from the evaluator.  vjp(): the
+    reverse mode — gradients of a loss with respect to theta or the QP's data with one solve per cotangent (torch_layer.QPLayer builds on it)."""
 
     def __init__(self, nx, ne, nc, batch, device=0, options=None):
         self._L = lib()
@@ -872,6 +873,7 @@ class SmallNewtonBatch:
         Pc, Ac, Gc = cm(P, self.nx, self.nx), cm(A, self.ne, self.nx), cm(G, self.nc, self.nx)
         qv, bv, hv = vv(q, self.nx), vv(b, self.ne), vv(h, self.nc)
         self._check(self._L.calipso_hip_smallnewton_set_qp(self._h, _pd(Pc), _pd(qv), _pd(Ac), _pd(bv), _pd(Gc), _pd(hv), float(objective_scale), int(bool(shared))), "smallnewton_set_qp")
+        self._evaluator = False
 
     def set_evaluator(self, cdll, symbol, n_parameters=0):
         """a device evaluator instead of the QP: `symbol` is the entry that CALIPSO_SMALLNEWTON_EVALUATOR (include/calipso_smallnewton.hpp) emitted into the HIP shared
@@ -882,6 +884,7 @@ class SmallNewtonBatch:
         fn = C.cast(getattr(cdll, symbol), C.c_void_p)
         self.n_parameters = int(n_parameters)
         self._check(self._L.calipso_hip_smallnewton_set_evaluator(self._h, fn, self.n_parameters), "smallnewton_set_evaluator(%s)" % symbol)
+        self._evaluator = True
 
     def set_parameters(self, theta):
         """theta (batch, n_parameters) per instance, or (n_parameters,) shared by all"""
@@ -955,6 +958,59 @@ class SmallNewtonBatch:
         out = np.zeros(self.batch * N * p); st = np.zeros(self.batch, dtype=np.int32); ms = C.c_double(0.0)
         self._check(self._L.calipso_hip_smallnewton_differentiate(self._h, int(p), int(shared), _pd(Jc), _pd(out), st.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(ms)), "smallnewton_differentiate")
         return np.transpose(out.reshape(self.batch, p, N), (0, 2, 1)).copy(), st, float(ms.value)
+
+    def vjp(self, cotangent, adjoint=True, theta=None, qp=None):
+        """differentiate! in reverse mode, one launch (calipso_hip_smallnewton_differentiate_adjoint): for cotangents v = dLoss/dw at the resident points,
+        lambda = M' v and the gradients v'S for the S = dw/dtheta that differentiate() would return.  cotangent: (batch, N) or (batch, N, k), or (batch, nx) /
+        (batch, nx, k) for x alone (the other rows zero).  theta: -R_theta' lambda with the evaluator's dR/dtheta (default: when an evaluator with parameters is
+        set); qp: the built-in QP's data gradients (default: when the QP is set).  Returns a dict: "adjoint" (batch, N[, k]), "theta" (batch, n_parameters[, k]),
+        "P", "q", "A", "b", "G", "h" in set_qp's shapes (per instance, [, k]), "status" (batch,) as differentiate() and "ms"; the trailing k axis only when the
+        cotangent had one"""
+        v = np.asarray(cotangent, dtype=np.float64)
+        squeeze = v.ndim == 2
+        if squeeze:
+            v = v[:, :, None]
+        if v.ndim != 3 or v.shape[0] != self.batch or v.shape[1] not in (self.N, self.nx) or v.shape[2] < 1:
+            raise ValueError("cotangent must be (batch, N), (batch, N, k), (batch, nx) or (batch, nx, k)")
+        if v.shape[1] != self.N:
+            w = np.zeros((self.batch, self.N, v.shape[2]))
+            w[:, :self.nx] = v
+            v = w
+        k = v.shape[2]
+        evaluator = getattr(self, "_evaluator", False)
+        p = getattr(self, "n_parameters", 0) if evaluator else 0
+        if theta is None:
+            theta = evaluator and p > 0
+        if qp is None:
+            qp = not evaluator
+        nx, ne, nc = self.nx, self.ne, self.nc
+        nqp = nx * nx + nx + ne * nx + ne + nc * nx + nc
+        vc = np.ascontiguousarray(np.transpose(v, (0, 2, 1))).ravel()         # per instance column-major N x k
+        adj = np.zeros(self.batch * self.N * k) if adjoint else None
+        gth = np.zeros(self.batch * k * max(p, 1)) if theta else None
+        gqp = np.zeros(self.batch * k * nqp) if qp else None
+        st = np.zeros(self.batch, dtype=np.int32); ms = C.c_double(0.0)
+        opt = lambda a: _pd(a) if a is not None else None
+        self._check(self._L.calipso_hip_smallnewton_differentiate_adjoint(self._h, int(k), _pd(vc), opt(adj), opt(gth), opt(gqp), st.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                                           C.byref(ms)), "smallnewton_differentiate_adjoint")
+        fin = lambda a: a[..., 0] if squeeze else a                           # (..., k) -> (...) for a cotangent without a k axis
+        out = dict(status=st, ms=float(ms.value))
+        if adjoint:
+            out["adjoint"] = fin(np.transpose(adj.reshape(self.batch, k, self.N), (0, 2, 1)).copy())
+        if theta:
+            out["theta"] = fin(np.transpose(gth.reshape(self.batch, k, p), (0, 2, 1)).copy())
+        if qp:
+            g = gqp.reshape(self.batch, k, nqp)
+            at = 0
+            for name, r, c in (("P", nx, nx), ("q", nx, 0), ("A", ne, nx), ("b", ne, 0), ("G", nc, nx), ("h", nc, 0)):
+                n = r * c if c else r
+                blk = g[:, :, at:at + n]
+                at += n
+                if c:      # column-major r x c -> (batch, r, c, k)
+                    out[name] = fin(np.transpose(blk.reshape(self.batch, k, c, r), (0, 3, 2, 1)).copy())
+                else:
+                    out[name] = fin(np.transpose(blk, (0, 2, 1)).copy())
+        return out
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:

@@ -115,6 +115,7 @@ SYMBOLS = {
     "calipso_hip_smallnewton_set_evaluator": (_i32, [_vp, _vp, _i64]),
     "calipso_hip_smallnewton_set_parameters": (_i32, [_vp, _pd, _i32]),
     "calipso_hip_smallnewton_differentiate_parameters": (_i32, [_vp, _pd, _pi32, _pd]),
+    "calipso_hip_smallnewton_differentiate_adjoint": (_i32, [_vp, _i64, _pd, _pd, _pd, _pd, _pi32, _pd]),
     "calipso_hip_comm_unique_id": (_i32, [C.POINTER(C.c_uint8)]),
     "calipso_hip_comm_init": (_i32, [_i32, _i32, C.POINTER(C.c_uint8), _i32, C.POINTER(_vp)]),
     "calipso_hip_comm_destroy": (_i32, [_vp]),

@@ -34,13 +34,15 @@ struct calipso_hip_smallnewton {
     calipso::Options opt;
     double objective_scale = 0.5;
     bool shared_qp = false, have_qp = false;
-    calipso_smallnewton_kernels_fn ev = nullptr; int np = 0; bool ev_rtheta = false;      // set_evaluator: the user library's entry, parameters per instance, dR/dtheta provided
+    calipso_smallnewton_kernels_fn ev = nullptr; int np = 0; bool ev_rtheta = false, ev_adj = false;      // set_evaluator: the user library's entry, parameters per instance, dR/dtheta provided, reverse mode built
     double *theta = nullptr, *hess = nullptr, *dpt = nullptr; bool theta_shared = false, have_theta = false;      // parameters (batch x np or one row), Lagrangian Hessians (batch x nx^2), the points they were evaluated at (batch x (nx + m))
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     double *P = nullptr, *q = nullptr, *Z = nullptr, *bh = nullptr;      // Lxx = 2 c P (nx x nx), q, Z = [A; -G] (m x nx, ld m), bh = [-b; h]: per instance or shared
     double *w = nullptr, *lam = nullptr, *sc = nullptr, *filt = nullptr, *info = nullptr, *trace = nullptr, *prof = nullptr;
     double *rtheta = nullptr, *sens = nullptr, *stf = nullptr; size_t cap_diff = 0; bool diff_shared = false;      // differentiate!: batch x N x p each
+    double *adj_rt = nullptr, *adj_in = nullptr, *adj_out = nullptr, *adj_gth = nullptr, *adj_gqp = nullptr;      // reverse mode: dR/dtheta, cotangents, lambda, gradients
+    size_t cap_adj_rt = 0, cap_adj_in = 0, cap_adj_out = 0, cap_adj_gth = 0, cap_adj_gqp = 0;                      // (their capacities in doubles, grown on demand)
     long long* cnt = nullptr; int* status = nullptr;
     int trace_rows = 0;
     size_t lds_bytes = 0;
@@ -90,12 +92,14 @@ int grant_lds(SN* s) {
     for (const bool soc : {false, true}) for (const int nt : {64, 128, 256}) {
         for (const bool lu : {false, true}) (void)calipso::lds_attribute(kernel_of<QpEval>(nt, soc, lu), 160 * 1024);
         (void)calipso::lds_attribute(diff_kernel_of<QpEval>(nt, soc), 160 * 1024);
+        (void)calipso::lds_attribute(adj_kernel_of<QpEval>(nt, soc), 160 * 1024);
     }
-    if (s->ev) { int64_t out[4] = {0, 0, 0, 0}; calipso_smallnewton_launch L = ev_request(s, CALIPSO_SMALLNEWTON_GRANT_LDS, out); L.lds_bytes = 160 * 1024; (void)s->ev(&L); }
+    if (s->ev) { int64_t out[5] = {0, 0, 0, 0, 0}; calipso_smallnewton_launch L = ev_request(s, CALIPSO_SMALLNEWTON_GRANT_LDS, out); L.lds_bytes = 160 * 1024; (void)s->ev(&L); }
     return CALIPSO_OK;
 }
 
-int launch(SN* s, int mode, int count, int advance, bool eval_rtheta = false) {
+// adj: MODE_ADJ's extra arguments (its `base` is filled here)
+int launch(SN* s, int mode, int count, int advance, bool eval_rtheta = false, const AdjArgs* adj = nullptr) {
     if (!s->have_qp && !s->ev) return fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_smallnewton: no problem data (calipso_hip_smallnewton_set_qp or calipso_hip_smallnewton_set_evaluator)");
     if (s->ev && s->np > 0 && !s->have_theta) return fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_smallnewton: the evaluator takes " + std::to_string(s->np) + " parameters and none were set (calipso_hip_smallnewton_set_parameters)");
     SK(hipSetDevice(s->device));
@@ -111,15 +115,24 @@ int launch(SN* s, int mode, int count, int advance, bool eval_rtheta = false) {
     a.rtheta = s->rtheta; a.sens = s->sens; a.stf = s->stf; a.srtheta = s->diff_shared ? 0 : (long long)a.d.N * (long long)count;
     a.Hs = s->Hs;
     a.theta = s->theta; a.stheta = s->theta_shared ? 0 : (long long)s->np; a.hess = s->hess; a.dpt = s->dpt; a.eval_rtheta = eval_rtheta ? 1 : 0;
-    static_assert(sizeof(Args) <= 3800, "kernel arguments");
+    static_assert(sizeof(Args) <= 3800 && sizeof(AdjArgs) <= 3800, "kernel arguments");
+    AdjArgs aa;
+    if (mode == MODE_ADJ) {      // (dR/dtheta of the reverse mode in a buffer of its own, count = n_parameters columns per instance)
+        aa = *adj; aa.base = a;
+        aa.base.rtheta = s->adj_rt; aa.base.srtheta = (long long)a.d.N * (long long)count;
+    }
     SK(hipEventRecord(s->ev0, s->stream));
     const bool soc = !s->soc_dim.empty();
     if (s->ev) {      // the evaluator's own builds of the kernels, launched by its entry on the handle's stream
-        int64_t out[4] = {0, 0, 0, 0};
+        int64_t out[5] = {0, 0, 0, 0, 0};
         calipso_smallnewton_launch L = ev_request(s, CALIPSO_SMALLNEWTON_LAUNCH, out);
-        L.args = &a; L.mode = mode; L.eval_rtheta = eval_rtheta ? 1 : 0;
+        L.args = mode == MODE_ADJ ? (const void*)&aa : (const void*)&a; L.mode = mode; L.eval_rtheta = eval_rtheta ? 1 : 0;
         const int rc = s->ev(&L);
         if (rc != CALIPSO_OK) return fail(s, rc, "calipso_hip_smallnewton: the evaluator's entry refused or failed the launch (" + std::to_string(rc) + ")");
+    } else if (mode == MODE_ADJ) {
+        const int nt = sn_threads(s);
+        void* args[] = {&aa};
+        SK(hipLaunchKernel(adj_kernel_of<QpEval>(nt, soc), dim3((unsigned)s->batch), dim3((unsigned)nt), args, s->lds_bytes, s->stream));
     } else if (mode == MODE_DIFF) {
         const int nt = sn_threads(s);
         void* args[] = {&a};
@@ -180,7 +193,8 @@ int32_t calipso_hip_smallnewton_destroy(calipso_hip_smallnewton* s) {
     if (!s) return CALIPSO_OK;
     (void)hipSetDevice(s->device);
     if (s->stream) (void)hipStreamSynchronize(s->stream);
-    for (double* p : {s->P, s->q, s->Z, s->bh, s->theta, s->hess, s->dpt, s->w, s->lam, s->sc, s->filt, s->info, s->trace, s->prof, s->rtheta, s->sens, s->stf, s->Hs}) if (p) (void)hipFree(p);
+    for (double* p : {s->P, s->q, s->Z, s->bh, s->theta, s->hess, s->dpt, s->w, s->lam, s->sc, s->filt, s->info, s->trace, s->prof, s->rtheta, s->sens, s->stf, s->Hs,
+                      s->adj_rt, s->adj_in, s->adj_out, s->adj_gth, s->adj_gqp}) if (p) (void)hipFree(p);
     if (s->cnt) (void)hipFree(s->cnt);
     if (s->d_soc) (void)hipFree(s->d_soc);
     if (s->status) (void)hipFree(s->status);
@@ -303,7 +317,7 @@ int32_t calipso_hip_smallnewton_set_qp(calipso_hip_smallnewton* s, const double*
     SK(hipMemcpyAsync(s->bh, bh.data(), sizeof(double) * bh.size(), hipMemcpyHostToDevice, s->stream));
     SK(hipStreamSynchronize(s->stream));
     s->shared_qp = shared != 0; s->have_qp = true; s->objective_scale = objective_scale;
-    s->ev = nullptr; s->np = 0; s->ev_rtheta = false; s->have_theta = false;      // (replaces an evaluator)
+    s->ev = nullptr; s->np = 0; s->ev_rtheta = false; s->ev_adj = false; s->have_theta = false;      // (replaces an evaluator)
     for (double** p : {&s->theta, &s->hess, &s->dpt}) if (*p) { (void)hipFree(*p); *p = nullptr; }
     return CALIPSO_OK;
 }
@@ -311,7 +325,7 @@ int32_t calipso_hip_smallnewton_set_qp(calipso_hip_smallnewton* s, const double*
 // a device evaluator (include/calipso_smallnewton.hpp): its entry's handshake, then the per-instance Lagrangian Hessians; replaces the QP
 int32_t calipso_hip_smallnewton_set_evaluator(calipso_hip_smallnewton* s, calipso_smallnewton_kernels_fn fn, int64_t n_parameters) {
     if (!s || !fn || n_parameters < 0 || n_parameters > (1 << 20)) return CALIPSO_ERR_ARGUMENT;
-    int64_t out[4] = {0, 0, 0, 0};
+    int64_t out[5] = {0, 0, 0, 0, 0};      // (out[4]: reverse mode built; an entry compiled before it answers the first four)
     calipso_smallnewton_launch L = ev_request(s, CALIPSO_SMALLNEWTON_QUERY, out);
     const int rc = fn(&L);
     if (rc != CALIPSO_OK) return fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_smallnewton_set_evaluator: the entry refused the query (" + std::to_string(rc) + ")");
@@ -331,7 +345,7 @@ int32_t calipso_hip_smallnewton_set_evaluator(calipso_hip_smallnewton* s, calips
     SK(hipMemset(s->hess, 0, bytes));
     const size_t pbytes = sizeof(double) * (size_t)s->batch * (size_t)(s->nx + s->ne + s->nc);
     SK(hipMalloc((void**)&s->dpt, pbytes)); SK(hipMemset(s->dpt, 0, pbytes));
-    s->ev = fn; s->np = (int)n_parameters; s->ev_rtheta = out[3] != 0;
+    s->ev = fn; s->np = (int)n_parameters; s->ev_rtheta = out[3] != 0; s->ev_adj = out[4] == 1;
     grant_lds(s);
     return CALIPSO_OK;
 }
@@ -487,6 +501,62 @@ int32_t calipso_hip_smallnewton_differentiate_parameters(calipso_hip_smallnewton
     return CALIPSO_OK;
 }
 
+// differentiate! in reverse mode (differentiate.jl:1-61 transposed): for k cotangents v per instance, lambda = M' v for the map M that
+// calipso_hip_smallnewton_differentiate applies to a column of dR/dtheta (the same factorisation; refinement against H' for batches without second-order
+// cones, none with them: quirk B-3), then grad = -R_theta' lambda = S' v for the S that differentiate would return.  R_theta: the evaluator's dR/dtheta at the
+// resident points (grad_theta), or the built-in QP's data (grad_qp: P, q, A, b, G, h in set_qp's column-major block order, P's gradient symmetric).
+namespace {
+// a device buffer of at least `need` doubles (grown, never shrunk)
+int grow(SN* s, double** p, size_t* cap, size_t need) {
+    if (need <= *cap) return CALIPSO_OK;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr; *cap = 0;
+    if (hipMalloc((void**)p, sizeof(double) * need) != hipSuccess) {
+        (void)hipGetLastError(); *p = nullptr;
+        return fail(s, CALIPSO_ERR_HIP, "calipso_hip_smallnewton_differentiate_adjoint: device allocation of " + std::to_string(sizeof(double) * need) + " bytes failed");
+    }
+    *cap = need;
+    return CALIPSO_OK;
+}
+}  // namespace
+
+int32_t calipso_hip_smallnewton_differentiate_adjoint(calipso_hip_smallnewton* s, int64_t k, const double* cotangent, double* adjoint, double* grad_theta, double* grad_qp,
+                                                      int32_t* status, double* ms) {
+    if (!s) return CALIPSO_ERR_ARGUMENT;
+    const char* me = "calipso_hip_smallnewton_differentiate_adjoint: ";
+    if (k < 1 || k > (1 << 20)) return fail(s, CALIPSO_ERR_ARGUMENT, std::string(me) + "k >= 1 cotangent columns");
+    if (!cotangent) return fail(s, CALIPSO_ERR_ARGUMENT, std::string(me) + "no cotangent");
+    if (!s->have_qp && !s->ev) return fail(s, CALIPSO_ERR_ARGUMENT, std::string(me) + "no problem data (calipso_hip_smallnewton_set_qp or calipso_hip_smallnewton_set_evaluator)");
+    if (s->ev && !s->ev_adj)
+        return fail(s, CALIPSO_ERR_ARGUMENT, std::string(me) + "the evaluator's entry was built without the reverse mode: rebuild it against the current include/calipso_smallnewton.hpp");
+    if (grad_theta && (!s->ev || !s->ev_rtheta || s->np < 1))
+        return fail(s, CALIPSO_ERR_ARGUMENT, std::string(me) + "grad_theta needs an evaluator that provides dR/dtheta and has parameters");
+    if (grad_qp && s->ev) return fail(s, CALIPSO_ERR_ARGUMENT, std::string(me) + "grad_qp is for the built-in QP (set_qp), not an evaluator");
+    SK(hipSetDevice(s->device));
+    const Dm d = dims_of(s);
+    const size_t B = (size_t)s->batch, N = (size_t)d.N, K = (size_t)k;
+    const size_t nqp = (size_t)d.nx * d.nx + d.nx + (size_t)d.ne * d.nx + d.ne + (size_t)d.nc * d.nx + d.nc;
+    int rc = grow(s, &s->adj_in, &s->cap_adj_in, B * N * K);
+    if (rc == CALIPSO_OK && adjoint) rc = grow(s, &s->adj_out, &s->cap_adj_out, B * N * K);
+    if (rc == CALIPSO_OK && grad_theta) rc = grow(s, &s->adj_rt, &s->cap_adj_rt, B * N * (size_t)s->np);
+    if (rc == CALIPSO_OK && grad_theta) rc = grow(s, &s->adj_gth, &s->cap_adj_gth, B * K * (size_t)s->np);
+    if (rc == CALIPSO_OK && grad_qp) rc = grow(s, &s->adj_gqp, &s->cap_adj_gqp, B * K * nqp);
+    if (rc < 0) return rc;
+    SK(hipMemcpyAsync(s->adj_in, cotangent, sizeof(double) * B * N * K, hipMemcpyHostToDevice, s->stream));
+    AdjArgs aa;
+    std::memset(&aa, 0, sizeof(aa));
+    aa.cot = s->adj_in; aa.adjoint = adjoint ? s->adj_out : nullptr; aa.grad_theta = grad_theta ? s->adj_gth : nullptr; aa.grad_qp = grad_qp ? s->adj_gqp : nullptr;
+    aa.objective_scale = s->objective_scale; aa.k = (int)k;
+    rc = launch(s, MODE_ADJ, grad_theta ? s->np : 0, 0, grad_theta != nullptr, &aa);
+    if (rc < 0) return rc;
+    if (adjoint) SK(hipMemcpy(adjoint, s->adj_out, sizeof(double) * B * N * K, hipMemcpyDeviceToHost));
+    if (grad_theta) SK(hipMemcpy(grad_theta, s->adj_gth, sizeof(double) * B * K * (size_t)s->np, hipMemcpyDeviceToHost));
+    if (grad_qp) SK(hipMemcpy(grad_qp, s->adj_gqp, sizeof(double) * B * K * nqp, hipMemcpyDeviceToHost));
+    if (status) SK(hipMemcpy(status, s->status, sizeof(int) * B, hipMemcpyDeviceToHost));
+    if (ms) *ms = s->last_ms;
+    return CALIPSO_OK;
+}
+
 // phase clocks of instance 0 in the last launch, microseconds (a build with -DSN_TRACE; zeros otherwise): [0] evaluation + residual + norms, [1] inertia logic, [2] cone
 // weights + assembly of S, [3] LDL^T, [4] first condensed solve, [5] refinement, [6] cone search + candidate, [7] candidate merit + line search, [8] accept, [9] of the LDL^T: the panels (one wavefront), [3] then holds its trailing updates, [11] between steps
 // out = {threads per instance, LDS bytes per instance, instances a compute unit holds (the runtime's occupancy query for the kernel launch() would pick), compute units}
@@ -496,7 +566,7 @@ int32_t calipso_hip_debug_smallnewton_describe(calipso_hip_smallnewton* s, doubl
     const int nt = sn_threads(s);
     int per = 0, cus = 0;
     if (s->ev) {      // the evaluator's build: its entry answers
-        int64_t o1[4] = {0, 0, 0, 0};
+        int64_t o1[5] = {0, 0, 0, 0, 0};
         const calipso_smallnewton_launch L = ev_request(s, CALIPSO_SMALLNEWTON_OCCUPANCY, o1);
         const int rc = s->ev(&L);
         if (rc != CALIPSO_OK) return fail(s, rc, "calipso_hip_debug_smallnewton_describe: the evaluator's entry failed the occupancy query");

@@ -578,6 +578,25 @@ function CALIPSO.differentiate!(s::HIPSmallNewton)
     sn_check(s, ccall((:calipso_hip_smallnewton_differentiate_parameters, lib), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}), s.handle, sens, st, ms), "calipso_hip_smallnewton_differentiate_parameters")
     return sens, st, ms[]
 end
+"""differentiate! in reverse mode for every instance in one launch (calipso_hip_smallnewton_differentiate_adjoint): cotangent N x k x batch (dLoss/dw per
+instance; an N x batch matrix is k = 1); returns (adjoint N x k x batch = M'v or nothing, grad_theta n_parameters x k x batch = -R_theta' lambda with the
+evaluator's dR/dtheta or nothing, grad_qp nqp x k x batch — P, q, A, b, G, h in set_qp!'s column-major block order — or nothing, status, ms)"""
+function differentiate_adjoint!(s::HIPSmallNewton, cotangent::AbstractArray{Float64}; adjoint::Bool=true, theta::Bool=s.np > 0, qp::Bool=s.np == 0)
+    N = s.nx + 2 * s.ne + 3 * s.nc
+    V = ndims(cotangent) == 2 ? reshape(Array{Float64}(cotangent), N, 1, s.batch) : Array{Float64}(cotangent)
+    size(V, 1) == N && size(V, 3) == s.batch || error("cotangent must be N x k x batch or N x batch")
+    k = size(V, 2)
+    nqp = s.nx * s.nx + s.nx + s.ne * s.nx + s.ne + s.nc * s.nx + s.nc
+    adj = adjoint ? zeros(N, k, s.batch) : nothing
+    gth = theta ? zeros(max(s.np, 1), k, s.batch) : nothing
+    gqp = qp ? zeros(nqp, k, s.batch) : nothing
+    st = zeros(Int32, s.batch); ms = Ref{Float64}(0.0)
+    ptr(a) = a === nothing ? Ptr{Float64}(C_NULL) : pointer(a)
+    GC.@preserve V adj gth gqp sn_check(s, ccall((:calipso_hip_smallnewton_differentiate_adjoint, lib), Int32,
+        (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}), s.handle, k, V, ptr(adj), ptr(gth), ptr(gqp), st, ms),
+        "calipso_hip_smallnewton_differentiate_adjoint")
+    return adj, gth, gqp, st, ms[]
+end
 """a device evaluator instead of the QP: `symbol` is the entry CALIPSO_SMALLNEWTON_EVALUATOR (include/calipso_smallnewton.hpp) emitted into the HIP shared library at
 `library` (INTEGRATION.md, "Writing an evaluator for the batched kernel"); n_parameters = length of theta per instance"""
 function set_evaluator!(s::HIPSmallNewton, library::AbstractString, symbol::Symbol, n_parameters::Integer)
@@ -640,7 +659,7 @@ function allreduce_sum!(c::HIPComm, v::Vector{Float64})
     return v
 end
 
-export HIPSolver, streams_concurrent, rebind_stream!, spread_streams!, HIPLDLSolver, HIPSparseLDLSolver, hip_sparse_ldl_solver, HIPKKTSolver, hip_ldl_solver, HIPGroup, HIPSmallNewton, set_option!, set_cones!, set_qp!, set_evaluator!, set_parameters!, solution, HIPComm, comm_unique_id, comm_size, gather_status, allreduce_sum!, newton_step!,
+export HIPSolver, streams_concurrent, rebind_stream!, spread_streams!, HIPLDLSolver, HIPSparseLDLSolver, hip_sparse_ldl_solver, HIPKKTSolver, hip_ldl_solver, HIPGroup, HIPSmallNewton, set_option!, set_cones!, set_qp!, set_evaluator!, set_parameters!, differentiate_adjoint!, solution, HIPComm, comm_unique_id, comm_size, gather_status, allreduce_sum!, newton_step!,
        search_direction_nonsymmetric!, analyze_structure!, clear_structure!, set_stage_parallel!, set_stage_blocks!, declared_structure, kernel_times, sync_scalars!, copy_back!
 
 end # module

@@ -489,10 +489,11 @@ enum { CALIPSO_SMALLNEWTON_QUERY = 0, CALIPSO_SMALLNEWTON_GRANT_LDS = 1, CALIPSO
 typedef struct calipso_smallnewton_launch {
     int32_t op;                 /* CALIPSO_SMALLNEWTON_QUERY / _GRANT_LDS / _OCCUPANCY / _LAUNCH */
     int32_t abi;                /* CALIPSO_SMALLNEWTON_ABI of the library that asks */
-    int64_t* out;               /* QUERY: out[4] = {ABI, sizeof(Args), SN_JB, 1 if dR/dtheta is provided}; OCCUPANCY: out[0] = instances a compute unit holds */
+    int64_t* out;               /* QUERY: out[5] = {ABI, sizeof(Args), SN_JB, 1 if dR/dtheta is provided, 1 if the reverse mode is built} (the library pre-zeroes five
+                                   entries: an entry built before the reverse mode leaves out[4] = 0); OCCUPANCY: out[0] = instances a compute unit holds */
     const void* args;           /* LAUNCH: the kernels' argument block (calipso::sn::Args) */
     int64_t args_bytes;         /* its size, sizeof(Args) of the library */
-    int32_t mode;               /* 0 solve!, 1 Newton steps, 2 differentiate! */
+    int32_t mode;               /* 0 solve!, 1 Newton steps, 2 differentiate!, 3 its reverse mode (args: calipso::sn::AdjArgs, which begins with Args) */
     int32_t threads;            /* threads per instance: 64, 128 or 256 */
     int32_t soc, lu;            /* second-order cones in the layout; the lu_fallback build */
     int32_t eval_rtheta;        /* differentiate!: dR/dtheta from the evaluator */
@@ -505,6 +506,21 @@ typedef int32_t (*calipso_smallnewton_kernels_fn)(const calipso_smallnewton_laun
 int32_t calipso_hip_smallnewton_set_evaluator(calipso_hip_smallnewton*, calipso_smallnewton_kernels_fn fn, int64_t n_parameters);
 int32_t calipso_hip_smallnewton_set_parameters(calipso_hip_smallnewton*, const double* theta, int32_t shared);
 int32_t calipso_hip_smallnewton_differentiate_parameters(calipso_hip_smallnewton*, double* sensitivity, int32_t* status, double* ms);
+/* differentiate! in REVERSE mode (differentiate.jl:1-61 and residual_jacobian_parameters.jl:1-40, transposed) for every instance in ONE launch, at the resident
+ * points: the factorisation of differentiate above, then for each of k cotangent columns v = dLoss/dw the transposed map lambda = M' v of the map M that
+ * differentiate applies to a column (search_direction_symmetric! stage by stage in reverse order; batches without second-order cones refine against H' as the
+ * forward columns refine against H, with the same options; with second-order cones neither refines, quirk B-3), then the contractions with dR/dtheta in the same
+ * launch: grad = -R_theta' lambda = S' v for the S = dw/dtheta that differentiate would return — one solve per cotangent instead of one per parameter.  The cone
+ * Jacobians, [gx; hx] and the Hessian are those of the last search direction (quirk B-12), as for differentiate.
+ *   cotangent   batch x (N x k), column-major per instance (required)
+ *   adjoint     batch x (N x k) = lambda (NULL: not returned)
+ *   grad_theta  batch x (n_parameters x k): -R_theta' lambda with the evaluator's dR/dtheta at the resident points (NULL: skipped; needs an evaluator that provides it)
+ *   grad_qp     batch x (nqp x k), nqp = nx^2 + nx + ne nx + ne + nc nx + nc: the built-in QP's data gradients in set_qp's column-major block order P, q, A, b, G, h
+ *               (P's gradient symmetric, P taken symmetric) per instance even for shared data — summing is the caller's (NULL: skipped; the QP only)
+ *   status[k] as differentiate.  CALIPSO_ERR_ARGUMENT with last_error for k < 1, no cotangent, no problem data, grad_theta without an evaluator providing dR/dtheta
+ *   (or with no parameters), grad_qp under an evaluator, and an evaluator entry that does not report the reverse mode (QUERY's out[4] stays 0: built before it) */
+int32_t calipso_hip_smallnewton_differentiate_adjoint(calipso_hip_smallnewton*, int64_t k, const double* cotangent, double* adjoint, double* grad_theta, double* grad_qp,
+                                                      int32_t* status, double* ms);
 
 /* ---- multi-GPU exchange of the batched path: RCCL over xGMI, one process per GPU ---------------------------------
  * Problem instances are sharded block-contiguously over ranks and never interact (the reference's `Solver`s are independent); the

@@ -6,7 +6,7 @@
 //     CALIPSO_SMALLNEWTON_EVALUATOR(MyEvaluator, my_problem_kernels)
 //
 // which emits  extern "C" int32_t my_problem_kernels(const calipso_smallnewton_launch*)  and instantiates every build of the kernels (64 / 128 / 256 threads
-// per instance x second-order cones x lu_fallback, and differentiate!) for MyEvaluator in the user's own code object: the evaluator is inlined into the Newton
+// per instance x second-order cones x lu_fallback, differentiate! and its reverse mode) for MyEvaluator in the user's own code object: the evaluator is inlined into the Newton
 // loop, no device function pointer crosses the two libraries.  calipso_hip_smallnewton_set_evaluator(handle, my_problem_kernels, n_parameters) registers it.
 //
 // An evaluator (the hooks are workgroup-cooperative: EVERY thread of the instance calls each one, with the inputs written and synchronised; the kernel puts a
@@ -46,7 +46,7 @@ namespace sn {
 enum { SC_KAPPA = 0, SC_TAU, SC_RHO, SC_EP, SC_EPLAST, SC_ED, SC_EQV, SC_CPV, SC_F, SC_COUNT = 16 };
 enum { CN_TOTAL = 0, CN_OUTER, CN_INNER, CN_FACT, CN_RFAIL, CN_RMAX, CN_RLAST, CN_STEPS, CN_FILTER, CN_TRACE, CN_COUNT = 16 };
 enum { IN_STEP = 0, IN_STEP_T, IN_ROUNDS, IN_NFACT, IN_MH, IN_THETAH, IN_EXIT, IN_OPT, IN_COUNT = 8 };
-enum { MODE_SOLVE = 0, MODE_STEPS = 1, MODE_DIFF = 2 };
+enum { MODE_SOLVE = 0, MODE_STEPS = 1, MODE_DIFF = 2, MODE_ADJ = 3 };
 
 struct Dm {
     int nx, ne, nc, m, n, N, ldz, q, nsoc, wsz, maxd;      // q nonnegative entries first, then nsoc second-order cones (contiguous ranges); wsz = sum of dim^2; ldz: leading dimension of Z in LDS (odd: conflict-free column walks)
@@ -89,6 +89,16 @@ struct Args {
     double* hess;                                   // the Lagrangian Hessian, batch x nx x nx
     double* dpt;                                    // batch x (nx + m): x and [y; z] where the last search direction evaluated the derivatives (differentiate! reads them there)
     int eval_rtheta;                                // differentiate!: 1 = dR/dtheta from the evaluator into rtheta (count = n_parameters), 0 = the caller's
+};
+
+// the argument block of differentiate! in reverse mode (k_smallnewton_adj only: Args itself, which every build shares with entries compiled before it, keeps its
+// size).  Per instance, column-major: cotangents N x k in; lambda = M' v (N x k), -R_theta' lambda (n_parameters x k, base.count = n_parameters) and the QP data's
+// gradients ((nx^2 + nx + ne nx + ne + nc nx + nc) x k) out, each skipped when NULL
+struct AdjArgs {
+    Args base;
+    const double* cot; double* adjoint; double* grad_theta; double* grad_qp;
+    double objective_scale;                         // c of the QP's f = c x'Px + q'x
+    int k, reserved;
 };
 
 // the built-in evaluator: the QP of qp.hip (f = 1/2 x'Lxx x + q'x with Lxx = 2cP, [g; h] = [A; -G] x + [-b; h]).  Its derivatives are constant: Z = [A; -G]
@@ -161,6 +171,11 @@ template <class Ev> inline const void* kernel_of(int nt, bool soc, bool lu) {
     if (nt == 128) return soc ? (const void*)t128::k_smallnewton<Ev, true, false> : (const void*)t128::k_smallnewton<Ev, false, false>;
     return soc ? (const void*)t256::k_smallnewton<Ev, true, false> : (const void*)t256::k_smallnewton<Ev, false, false>;
 }
+template <class Ev> inline const void* adj_kernel_of(int nt, bool soc) {
+    if (nt == 64) return soc ? (const void*)t64::k_smallnewton_adj<Ev, true> : (const void*)t64::k_smallnewton_adj<Ev, false>;
+    if (nt == 128) return soc ? (const void*)t128::k_smallnewton_adj<Ev, true> : (const void*)t128::k_smallnewton_adj<Ev, false>;
+    return soc ? (const void*)t256::k_smallnewton_adj<Ev, true> : (const void*)t256::k_smallnewton_adj<Ev, false>;
+}
 template <class Ev> inline const void* diff_kernel_of(int nt, bool soc) {
     if (nt == 64) return soc ? (const void*)t64::k_smallnewton_diff<Ev, true> : (const void*)t64::k_smallnewton_diff<Ev, false>;
     if (nt == 128) return soc ? (const void*)t128::k_smallnewton_diff<Ev, true> : (const void*)t128::k_smallnewton_diff<Ev, false>;
@@ -172,20 +187,22 @@ template <class Ev> inline int32_t entry(const calipso_smallnewton_launch* L) {
     if (!L || !L->out) return CALIPSO_ERR_ARGUMENT;
     if (L->op == CALIPSO_SMALLNEWTON_QUERY) {
         L->out[0] = CALIPSO_SMALLNEWTON_ABI; L->out[1] = (int64_t)sizeof(Args); L->out[2] = SN_JB; L->out[3] = Ev::provides_jacobian_parameters ? 1 : 0;
+        L->out[4] = 1;                                  // (the caller's buffer has five entries, pre-zeroed: an entry built before the reverse mode leaves a 0 here)
         return CALIPSO_OK;
     }
     if (L->abi != CALIPSO_SMALLNEWTON_ABI || L->args_bytes != (int64_t)sizeof(Args)) return CALIPSO_ERR_ARGUMENT;
-    const bool diff = L->mode == MODE_DIFF;
+    const bool diff = L->mode == MODE_DIFF, adj = L->mode == MODE_ADJ;      // (MODE_ADJ: L->args is an AdjArgs)
     if (L->op == CALIPSO_SMALLNEWTON_GRANT_LDS) {       // every build may take the LDS the handle asks for
         for (const bool soc : {false, true}) for (const int nt : {64, 128, 256}) {
             for (const bool lu : {false, true}) if (hipFuncSetAttribute(kernel_of<Ev>(nt, soc, lu), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L->lds_bytes) != hipSuccess) (void)hipGetLastError();
             if (hipFuncSetAttribute(diff_kernel_of<Ev>(nt, soc), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L->lds_bytes) != hipSuccess) (void)hipGetLastError();
+            if (hipFuncSetAttribute(adj_kernel_of<Ev>(nt, soc), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L->lds_bytes) != hipSuccess) (void)hipGetLastError();
         }
         return CALIPSO_OK;
     }
     if (L->threads != 64 && L->threads != 128 && L->threads != 256) return CALIPSO_ERR_ARGUMENT;
-    if (diff && L->eval_rtheta && !Ev::provides_jacobian_parameters) return CALIPSO_ERR_ARGUMENT;
-    const void* k = diff ? diff_kernel_of<Ev>(L->threads, L->soc != 0) : kernel_of<Ev>(L->threads, L->soc != 0, L->lu != 0);
+    if ((diff || adj) && L->eval_rtheta && !Ev::provides_jacobian_parameters) return CALIPSO_ERR_ARGUMENT;
+    const void* k = adj ? adj_kernel_of<Ev>(L->threads, L->soc != 0) : diff ? diff_kernel_of<Ev>(L->threads, L->soc != 0) : kernel_of<Ev>(L->threads, L->soc != 0, L->lu != 0);
     if (L->op == CALIPSO_SMALLNEWTON_OCCUPANCY) {
         int per = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k, L->threads, (size_t)L->lds_bytes) != hipSuccess) return CALIPSO_ERR_HIP;

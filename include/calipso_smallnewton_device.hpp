@@ -99,6 +99,21 @@ __device__ __forceinline__ void arrow_inverse(int n, const double* u, const doub
     for (int i = 1; i < n; ++i) out[i] = 1.0 / u[0] * out[i];
 }
 
+// the exact transpose of arrow_inverse's operation sequence for the same u (first-row quirk included): out = T' y, where arrow_inverse(u, x) = T x — its stages in
+// reverse order, each transposed (out and y distinct)
+__device__ __forceinline__ void arrow_inverse_t(int n, const double* u, const double* y, double* out) {
+    double uu = 0.0;
+    for (int i = 1; i < n; ++i) uu += u[i] * u[i];
+    const double alpha = -1.0 / (u[0] * u[0]) * uu;
+    const double beta = 1.0 / (1.0 + alpha);
+    const double x2_1 = 1.0 / u[0] * y[0];                              // out[0] = x2_1 / u0, out[i] = o_i / u0
+    double s = 0.0;
+    for (int i = 1; i < n; ++i) { const double o = 1.0 / u[0] * y[i] - (u[i] / u[0]) * x2_1; out[i] = o; s += (u[i] / u[0]) * o; }      // x2_1 = x0 - sum g_i o_i
+    const double x0_1 = -beta * s;                                      // o_i = x_i - beta g_i x0_1
+    out[0] = x2_1 + x0_1;                                               // x0_1 = x0 - sum g_i x_i
+    for (int i = 1; i < n; ++i) out[i] = out[i] - (u[i] / u[0]) * x0_1;
+}
+
 // v_readlane of a double: the value lane `src` (wave-uniform) holds
 __device__ __forceinline__ double rl(double v, int src) {
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), src), __builtin_amdgcn_readlane(__double2loint(v), src));
@@ -565,6 +580,147 @@ template <class Ev, bool SOC> struct CtxT {
         __syncthreads();
     }
 
+    // ---- the transpose of search_direction_symmetric!'s linear map for the same factorisation: out = M' v (differentiate! in reverse mode).  The stages of the
+    // forward map in reverse order, each transposed: the recoveries of dy, dz, ds, dt (diagonal, or per second-order cone through arrow_inverse_t), [A; -G] and
+    // its transpose swapped, S^-1 as it is (symmetric), Omega as stored, then the condensed right-hand side's assembly
+    __device__ __forceinline__ void search_direction_symmetric_t(const double* v, double* out) {
+        const double hrr = rho + ep;
+        for (int i = tid; i < d.ne; i += NT) {
+            const double vr = v[d.orr() + i] / hrr;
+            const double dyb = v[d.oy() + i] + vr;                      // dr = (r_r + dy) / hrr, out_y = dy
+            out[d.orr() + i] = vr;
+            rsym[d.nx + i] = -omega_y * dyb;                            // dy = -omega_y (b_y - [A dx]_y)
+            t2[i] = omega_y * dyb;
+        }
+        for (int i = tid; i < d.q; i += NT) {
+            const double Sb = sol[d.os() + i] - ed, T = sol[d.ot() + i], den = T + Sb * ep;
+            const double vt = v[d.ot() + i] / Sb;                       // dt = (r_t - T ds) / Sb
+            const double g = (v[d.os() + i] - T * vt) / den;            // ds = (r_t + Sb (r_s + dz)) / den
+            out[d.ot() + i] = vt + g;
+            out[d.os() + i] = Sb * g;
+            const double dzb = v[d.oz() + i] + Sb * g;
+            rsym[d.nx + d.ne + i] = -wz[i] * dzb;                       // dz = -wz (b_z - [-G dx]_z)
+            t2[d.ne + i] = wz[i] * dzb;
+        }
+        for (int j = tid; SOC && j < d.nsoc; j += NT) {                 // search_direction.jl:80-101 transposed
+            const int st = soc_start[j], dm = soc_dim[j];
+            double* u = vsoc + 4 * d.maxd * j; double* a = u + d.maxd; double* b = a + d.maxd; double* ct = b + d.maxd;
+            const double* sl = sol + d.os() + st; const double* t = sol + d.ot() + st;
+            const double* vs = v + d.os() + st; const double* vt = v + d.ot() + st; const double* vz = v + d.oz() + st;
+            double* os_ = out + d.os() + st; double* ot_ = out + d.ot() + st;
+            const double* W = wsoc + soc_woff[j];
+            for (int e = 0; e < dm; ++e) { u[e] = t[e] + (sl[e] - (e == 0 ? ed : 0.0)) * ep; ct[e] = sl[e] - (e == 0 ? ed : 0.0); }
+            arrow_inverse_t(dm, ct, vt, a);                             // dt = arrow_inverse(first row of Cbar_t, r_t - arrow(t) ds)
+            double a0 = t[0] * a[0];
+            for (int e = 1; e < dm; ++e) a0 += t[e] * a[e];
+            b[0] = vs[0] - a0;
+            for (int e = 1; e < dm; ++e) b[e] = vs[e] - (t[e] * a[0] + t[0] * a[e]);
+            for (int e = 0; e < dm; ++e) ot_[e] = a[e];
+            arrow_inverse_t(dm, u, b, a);                               // ds = arrow_inverse(u, r_t + Cbar_t (r_s + dz))
+            double g0 = (sl[0] - ed) * a[0];
+            for (int e = 1; e < dm; ++e) g0 += sl[e] * a[e];
+            b[0] = g0;
+            for (int e = 1; e < dm; ++e) b[e] = sl[e] * a[0] + (sl[0] - ed) * a[e];
+            for (int e = 0; e < dm; ++e) { ot_[e] += a[e]; os_[e] = b[e]; b[e] = vz[e] + b[e]; }
+            for (int c0 = 0; c0 < dm; ++c0) {                           // dz = -W (b_z - [-G dx]_z): W' as stored
+                double wv = 0.0;
+                for (int r0 = 0; r0 < dm; ++r0) wv += W[r0 + c0 * dm] * b[r0];
+                rsym[d.nx + d.ne + st + c0] = -wv; t2[d.ne + st + c0] = wv;
+            }
+        }
+        __syncthreads();
+        mv_t(Z, d.ldz, d.m, d.nx, t2, xb, v);                          // out_x = dx, t2 = [A; -G] dx
+        __syncthreads();
+        solve_S();
+        mv_n(Z, d.ldz, d.m, d.nx, xb, t1, nullptr);                    // xb = b_x + [A; -G]' t1
+        __syncthreads();
+        for (int i = tid; i < d.nx; i += NT) out[i] = xb[i];
+        for (int i = tid; i < d.ne; i += NT) {                          // b_y = r_y + r_r / hrr, t1_y = omega_y b_y
+            const double tot = rsym[d.nx + i] + omega_y * t1[i];
+            out[d.oy() + i] = tot;
+            out[d.orr() + i] += tot / hrr;
+        }
+        for (int i = tid; i < d.q; i += NT) {                           // b_z = r_z + (r_t + Sb r_s) / den, t1_z = wz b_z
+            const double Sb = sol[d.os() + i] - ed, T = sol[d.ot() + i], den = T + Sb * ep;
+            const double tot = rsym[d.nx + d.ne + i] + wz[i] * t1[d.ne + i];
+            out[d.oz() + i] = tot;
+            out[d.ot() + i] += tot / den;
+            out[d.os() + i] += Sb * tot / den;
+        }
+        for (int j = tid; SOC && j < d.nsoc; j += NT) {                 // b_z = r_z + arrow_inverse(u, Cbar_t r_s + r_t), t1_z = W b_z
+            const int st = soc_start[j], dm = soc_dim[j];
+            double* u = vsoc + 4 * d.maxd * j; double* a = u + d.maxd; double* b = a + d.maxd;
+            const double* sl = sol + d.os() + st;
+            double* os_ = out + d.os() + st; double* ot_ = out + d.ot() + st; double* oz_ = out + d.oz() + st;
+            const double* W = wsoc + soc_woff[j];
+            for (int c0 = 0; c0 < dm; ++c0) {
+                double wv = 0.0;
+                for (int r0 = 0; r0 < dm; ++r0) wv += W[r0 + c0 * dm] * t1[d.ne + st + r0];
+                b[c0] = rsym[d.nx + d.ne + st + c0] + wv;
+                oz_[c0] = b[c0];
+            }
+            arrow_inverse_t(dm, u, b, a);
+            double g0 = (sl[0] - ed) * a[0];
+            for (int e = 1; e < dm; ++e) g0 += sl[e] * a[e];
+            os_[0] += g0;
+            for (int e = 1; e < dm; ++e) os_[e] += sl[e] * a[0] + (sl[0] - ed) * a[e];
+            for (int e = 0; e < dm; ++e) ot_[e] += a[e];
+        }
+        __syncthreads();
+    }
+
+    // ---- H' v (Hmul transposed: Lxx' for the Hessian block; the s / t coupling and the cone rows swap, every other block of H is symmetric) -> out ----------
+    __device__ __forceinline__ void HTmul(const double* v, double* out) {
+        mv_n(Z, d.ldz, d.m, d.nx, v, t2, nullptr);                      // [A; -G] vx
+        __syncthreads();
+        for (int c = tid; c < d.nx; c += NT) {
+            const double* lc = Lg + (size_t)c * d.nx;                   // column c of Lxx = row c of Lxx'
+            const double* col = Z + c * d.ldz; const double* vy = v + d.oy();
+            double a0 = 0.0, a1 = 0.0, l0 = 0.0, l1 = 0.0;
+            int r = 0;
+            for (; r + 2 <= d.nx; r += 2) { l0 += lc[r] * v[r]; l1 += lc[r + 1] * v[r + 1]; }
+            for (; r < d.nx; ++r) l0 += lc[r] * v[r];
+            for (r = 0; r + 2 <= d.m; r += 2) { a0 += col[r] * vy[r]; a1 += col[r + 1] * vy[r + 1]; }
+            for (; r < d.m; ++r) a0 += col[r] * vy[r];
+            out[c] = ((l0 + l1) + ep * v[c]) + (a0 + a1);
+        }
+        for (int i = tid; i < d.ne; i += NT) {
+            out[d.orr() + i] = (rho + ep) * v[d.orr() + i] - v[d.oy() + i];
+            out[d.oy() + i] = t2[i] - v[d.orr() + i] + (0.0 - ed) * v[d.oy() + i];
+        }
+        for (int i = tid; i < d.nc; i += NT) {
+            out[d.oz() + i] = t2[d.ne + i] - v[d.os() + i] + (0.0 - ed) * v[d.oz() + i];
+            if (i < d.q) {
+                const double sl = sol[d.os() + i], t = sol[d.ot() + i];
+                out[d.os() + i] = ((0.0 + ep) * v[d.os() + i] - v[d.oz() + i]) + t * v[d.ot() + i];
+                out[d.ot() + i] = -v[d.os() + i] + (sl - ed) * v[d.ot() + i];
+            }
+        }
+        for (int j = tid; SOC && j < d.nsoc; j += NT) {                 // s columns: ep v_s - v_z + arrow(t)' v_t; t columns: -v_s + (arrow(s) - ed I)' v_t
+            const int st = soc_start[j], dm = soc_dim[j];
+            const double* sl = sol + d.os() + st; const double* t = sol + d.ot() + st;
+            const double* vs = v + d.os() + st; const double* vt = v + d.ot() + st; const double* vz = v + d.oz() + st;
+            double as = t[0] * vt[0], at = (sl[0] - ed) * vt[0];
+            for (int e = 1; e < dm; ++e) { as += t[e] * vt[e]; at += sl[e] * vt[e]; }
+            out[d.os() + st] = ((0.0 + ep) * vs[0] - vz[0]) + as;
+            out[d.ot() + st] = -vs[0] + at;
+            for (int e = 1; e < dm; ++e) {
+                out[d.os() + st + e] = ((0.0 + ep) * vs[e] - vz[e]) + (t[e] * vt[0] + t[0] * vt[e]);
+                out[d.ot() + st + e] = -vs[e] + (sl[e] * vt[0] + (sl[0] - ed) * vt[e]);
+            }
+        }
+        __syncthreads();
+    }
+
+    // residual_error of the transposed system: rerr = res - H' step; returns its inf-norm
+    __device__ __forceinline__ double residual_error_t() {
+        HTmul(step, rerr);
+        double v[1] = {0.0};
+        for (int i = tid; i < d.N; i += NT) { const double e = res[i] - rerr[i]; rerr[i] = e; v[0] = fmax(v[0], nabs(e)); }
+        block_max(v, red);
+        return v[0];
+    }
+
     // residual_error = residual - H step; returns its inf-norm
     __device__ __forceinline__ double residual_error() {
         Hmul(step, rerr);                          // (H step lands in residual_error itself and is turned into residual - H step in place: no N-vector of scratch)
@@ -966,11 +1122,10 @@ template <class Ev, bool SOC> __device__ __forceinline__ void bind_instance(CtxT
 // factorisation of solve! left (:13-20: residual_jacobian_variables!, the symmetric form, factorize!), then per parameter column search_direction_symmetric! on
 // the column of dR/dtheta (:29-52) and sensitivity = -1.0 * the result (:55-57).  dR/dtheta comes from the caller (residual_jacobian_parameters.jl:1-40 is the
 // caller's model: for the parametric QPs of the MPC loops it is constant) or, with a.eval_rtheta, from the evaluator at the resident point; `count` = its columns.
-template <class Ev, bool SOC> __global__ __launch_bounds__(NT, 2) void k_smallnewton_diff(Args a) {
-    extern __shared__ __attribute__((aligned(16))) double sm[];
-    const int inst = blockIdx.x, tid = threadIdx.x;
-    if (inst >= a.batch) return;
-    CtxT<Ev, SOC> c;
+// what differentiate! and its transpose share: the instance bound, the scalars the last solve! left, [gx; hx] and the Hessian (evaluators) where the last search
+// direction evaluated them, dR/dtheta from the evaluator into a.rtheta when a.eval_rtheta, the cone Jacobians at the s, t of the last search direction (quirk B-12) and ONE
+// factorisation of the condensed matrix with the regularisation solve! left.  Returns whether its inertia is (nx, ne + nc, 0)
+template <class Ev, bool SOC> __device__ __forceinline__ bool diff_prologue(CtxT<Ev, SOC>& c, const Args& a, double* sm, int inst, int tid) {
     bind_instance(c, a, sm, inst, tid);
     const Dm& d = c.d;
     const double* gsc = a.sc + (size_t)inst * SC_COUNT;
@@ -1003,8 +1158,21 @@ template <class Ev, bool SOC> __global__ __launch_bounds__(NT, 2) void k_smallne
     for (int i = tid; i < d.nc; i += NT) { c.sol[d.os() + i] = c.stf[i]; c.sol[d.ot() + i] = c.stf[d.nc + i]; }
     __syncthreads();
     int zero = 0;
-    const bool inertia_ok = c.factorize(zero);
-    const double* J = Jw;
+    return c.factorize(zero);
+}
+
+// differentiate!(solver) for every instance of the batch (differentiate.jl:1-61) at the resident point: the condensed matrix for the regularisation the last
+// factorisation of solve! left (:13-20: residual_jacobian_variables!, the symmetric form, factorize!), then per parameter column search_direction_symmetric! on
+// the column of dR/dtheta (:29-52) and sensitivity = -1.0 * the result (:55-57).  dR/dtheta comes from the caller (residual_jacobian_parameters.jl:1-40 is the
+// caller's model: for the parametric QPs of the MPC loops it is constant) or, with a.eval_rtheta, from the evaluator at the resident point; `count` = its columns.
+template <class Ev, bool SOC> __global__ __launch_bounds__(NT, 2) void k_smallnewton_diff(Args a) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    const int inst = blockIdx.x, tid = threadIdx.x;
+    if (inst >= a.batch) return;
+    CtxT<Ev, SOC> c;
+    const bool inertia_ok = diff_prologue(c, a, sm, inst, tid);
+    const Dm& d = c.d;
+    const double* J = a.rtheta + (size_t)inst * (size_t)a.srtheta;
     double* Sn = a.sens + (size_t)inst * (size_t)d.N * (size_t)a.count;
     for (int j = 0; j < a.count; ++j) {
         for (int i = tid; i < d.N; i += NT) c.res[i] = J[(size_t)j * d.N + i];
@@ -1029,6 +1197,73 @@ template <class Ev, bool SOC> __global__ __launch_bounds__(NT, 2) void k_smallne
         __syncthreads();
     }
     if (tid == 0) a.status[inst] = inertia_ok ? 0 : 1;      // (1: the factorisation's inertia is not (nx, ne + nc, 0); the reference does not look, the sensitivities are what they are)
+}
+
+// differentiate! in reverse mode for every instance of the batch: the factorisation of k_smallnewton_diff (diff_prologue), then per cotangent column v the
+// transposed map lambda = M' v — search_direction_symmetric_t, and for batches WITHOUT second-order cones correction rounds against H' with the options of the
+// forward rounds (with second-order cones the forward column is the unrefined solve, quirk B-3, and so is its transpose).  Since the forward sensitivity is
+// S = -M R_theta, v'S = -(M' v)' R_theta: the contractions with R_theta are done here — the evaluator's dR/dtheta at the resident point (grad_theta = -R_theta' lambda)
+// or, for the built-in QP, the closed forms of its data's gradients (the resident x, y, z; set_qp's block order P, q, A, b, G, h, column-major)
+template <class Ev, bool SOC> __global__ __launch_bounds__(NT, 2) void k_smallnewton_adj(AdjArgs aa) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    const Args& a = aa.base;
+    const int inst = blockIdx.x, tid = threadIdx.x;
+    if (inst >= a.batch) return;
+    CtxT<Ev, SOC> c;
+    const bool inertia_ok = diff_prologue(c, a, sm, inst, tid);      // (base.eval_rtheta: dR/dtheta into base.rtheta, count = n_parameters)
+    const double* Jw = aa.grad_theta ? a.rtheta + (size_t)inst * (size_t)a.srtheta : nullptr;
+    const Dm& d = c.d;
+    const int K = aa.k;
+    const double* V = aa.cot + (size_t)inst * (size_t)d.N * K;
+    const size_t nqp = (size_t)d.nx * d.nx + d.nx + (size_t)d.ne * d.nx + d.ne + (size_t)d.nc * d.nx + d.nc;
+    for (int j = 0; j < K; ++j) {
+        for (int i = tid; i < d.N; i += NT) c.res[i] = V[(size_t)j * d.N + i];
+        __syncthreads();
+        int it = 0;
+        bool first = true;
+        for (;;) {                                                      // the forward column's loop, against H'
+            c.search_direction_symmetric_t(first ? c.res : c.rerr, first ? c.step : c.corr);
+            if (SOC || !a.o.iterative_refinement) break;
+            if (!first) { for (int i = tid; i < d.N; i += NT) c.step[i] += c.corr[i]; __syncthreads(); it += 1; }
+            const double norm = c.residual_error_t();
+            first = false;
+            if (it > a.o.max_iterative_refinement) break;
+            if (norm <= a.o.iterative_refinement_tolerance && it >= a.o.min_iterative_refinement) break;
+        }
+        const double* lam = c.step;
+        if (aa.adjoint) { double* o = aa.adjoint + ((size_t)inst * K + j) * d.N; for (int i = tid; i < d.N; i += NT) o[i] = lam[i]; }
+        if (Jw) {                                                       // -R_theta' lambda
+            double* o = aa.grad_theta + ((size_t)inst * K + j) * (size_t)a.count;
+            for (int p = tid; p < a.count; p += NT) {
+                const double* col = Jw + (size_t)p * d.N;
+                double s0 = 0.0, s1 = 0.0;
+                int i = 0;
+                for (; i + 2 <= d.N; i += 2) { s0 += col[i] * lam[i]; s1 += col[i + 1] * lam[i + 1]; }
+                for (; i < d.N; ++i) s0 += col[i] * lam[i];
+                o[p] = -(s0 + s1);
+            }
+        }
+        if (aa.grad_qp) {                                               // R_x = 2cP x + q + A'y - G'z, R_y = Ax - b - r, R_z = h - Gx - s
+            double* g = aa.grad_qp + ((size_t)inst * K + j) * nqp;
+            const double* x = c.sol; const double* y = c.sol + d.oy(); const double* z = c.sol + d.oz();
+            const double* lx = lam; const double* ly = lam + d.oy(); const double* lz = lam + d.oz();
+            const double cs = aa.objective_scale;
+            const int nx = d.nx, ne = d.ne, nc = d.nc;
+            for (int e = tid; e < nx * nx; e += NT) { const int r = e % nx, cc = e / nx; g[e] = -cs * (lx[r] * x[cc] + x[r] * lx[cc]); }      // P (symmetric gradient)
+            g += (size_t)nx * nx;
+            for (int i = tid; i < nx; i += NT) g[i] = -lx[i];                                                                                 // q
+            g += nx;
+            for (int e = tid; e < ne * nx; e += NT) { const int r = e % ne, cc = e / ne; g[e] = -(ly[r] * x[cc] + y[r] * lx[cc]); }           // A
+            g += (size_t)ne * nx;
+            for (int i = tid; i < ne; i += NT) g[i] = ly[i];                                                                                  // b
+            g += ne;
+            for (int e = tid; e < nc * nx; e += NT) { const int r = e % nc, cc = e / nc; g[e] = lz[r] * x[cc] + z[r] * lx[cc]; }              // G
+            g += (size_t)nc * nx;
+            for (int i = tid; i < nc; i += NT) g[i] = -lz[i];                                                                                 // h
+        }
+        __syncthreads();
+    }
+    if (tid == 0) a.status[inst] = inertia_ok ? 0 : 1;
 }
 
 template <class Ev, bool SOC, bool LU> __global__ __launch_bounds__(NT, 2) void k_smallnewton(Args a) {

@@ -434,6 +434,14 @@ int32_t calipso_hip_small_get(calipso_hip_small*, double* X, int64_t* inertia);
  * filter line search, outer updates) on the device, ONE launch per call.  Evaluator: the QP of calipso_hip_qp_attach (min c x'Px + q'x s.t. Ax = b, h - Gx >= 0), or a
  * device evaluator of the caller's (set_evaluator below: nonlinear f, g, h with parameters theta), with nonnegative and second-order cones (dimension <= 16; wider: the general path); residual_norm = constraint_norm = 1.  Points have the layout of point.jl:13-22 (N = nx + 2 ne + 3 nc).  Limits: nx <= 128 and the
  * instance must fit 160 KB of LDS (n up to ~200), else CALIPSO_ERR_ARGUMENT at create: the general path (calipso_hip_create + groups) takes those.
+ * Admitted: 1 <= nx <= 128, ne, nc >= 0, cones of dimension 2 .. 16, any footprint up to 160 KB (e.g. (nx, ne, nc) = (128, 63, 0); tests/test_gpu_smallnewton_edges.py
+ * finds the last admitted shape from the refusal itself and holds the kernel to the oracle there).
+ * Quirk B-13, a DELIBERATE DEPARTURE of this kernel: with ne = nc = 0 the reference's constraint_violation! returns norm(c) / length(c) = 0.0 / 0 = NaN
+ * (constraint_violation.jl:13); no comparison of the residual line search holds with it (solve.jl:257-259, line_search.jl:11-12), every iteration halves its step
+ * max_residual_line_search = 25 times, moves by 2^-25 of the Newton step, and solve! returns false after max_outer_iterations x max_residual_iterations iterations far
+ * from the minimiser.  The oracle and the general path (calipso_hip_solve) keep that behaviour.  This kernel takes the violation of an empty constraint set as 0, so an
+ * unconstrained problem takes full Newton steps and converges (status 1; a convex QP: to -(2cP)^-1 q within the tolerances).  Both behaviours are pinned:
+ * tests/test_oracle_solve.py (the crawl) and tests/test_gpu_smallnewton_edges.py (the kernel against the closed form, the general path against the oracle).
  *   create(nx, ne, nc, batch, device)        set_option(name, value): options.jl:6-59 by name; plus "threads" = threads per instance (0: chosen by the LDS footprint so that
  *                                            a compute unit holds as many instances as fit; 64, 128 or 256 force a build of the kernel); "lu_fallback" = 0 (default) or 1:
  *                                            where iterative refinement fails, take the reference's `H \ residual` (search_direction.jl:22) inside the kernel — a partially

@@ -265,6 +265,8 @@ struct oracle_solver {
     std::vector<vec> trace;   // solution.all after every accepted inner iteration (test fixture support)
     i64 stat_total_iterations = 0, stat_outer = 0, stat_factorizations = 0, stat_refine_fail = 0,
         stat_refine_max = 0, stat_lu_fallback = 0, stat_last_refine_rounds = 0;
+    i64 stat_accepted_rows = 0;               // accepted iterates of solve! so far (the trace keeps the first 512 of them)
+    i64 stat_first_lu_fallback_row = -1;      // accepted iterates of solve! before its first `H \ residual` (-1: none)
 
     vec& B(const char* k) { return buf[k]; }
     double* P(const char* k) { return buf[k].data(); }
@@ -785,6 +787,7 @@ bool search_direction_nonsymmetric(S* s, double* step, const double* res) {
     vec H((size_t)(N * N));
     oracle_H_dense(s, H.data());
     for (i64 i = 0; i < N; ++i) step[i] = res[i];
+    if (s->stat_lu_fallback == 0) s->stat_first_lu_fallback_row = s->stat_accepted_rows;
     s->stat_lu_fallback += 1;
     return dense_lu_solve(N, H, step);
 }
@@ -974,7 +977,7 @@ int64_t oracle_trace(oracle_solver* s, double* out, int64_t cap_rows) {
 
 void oracle_stats(oracle_solver* s, int64_t out[8]) {
     out[0] = s->stat_total_iterations; out[1] = s->stat_outer; out[2] = s->stat_factorizations; out[3] = s->stat_refine_fail;
-    out[4] = s->stat_refine_max; out[5] = s->stat_lu_fallback; out[6] = s->stat_last_refine_rounds; out[7] = 0;
+    out[4] = s->stat_refine_max; out[5] = s->stat_lu_fallback; out[6] = s->stat_last_refine_rounds; out[7] = s->stat_first_lu_fallback_row;
 }
 
 namespace {
@@ -997,6 +1000,7 @@ int oracle_solve(oracle_solver* s, oracle_eval_fn eval, void* user) {
     double& rho = s->P("penalty")[0]; double* lam = s->P("dual");
     s->trace.clear();
     s->stat_total_iterations = 0; s->stat_outer = 0; s->stat_factorizations = 0; s->stat_refine_fail = 0; s->stat_refine_max = 0; s->stat_lu_fallback = 0;
+    s->stat_first_lu_fallback_row = -1; s->stat_accepted_rows = 0;
 
     if (!o.warmstart) {
         // initialize_slacks! initialize.jl:15-29
@@ -1105,6 +1109,7 @@ int oracle_solve(oracle_solver* s, oracle_eval_fn eval, void* user) {
             total_iterations += 1;
             s->stat_total_iterations = total_iterations;
             if (s->trace.size() < 512) s->trace.push_back(vec(w, w + N));
+            s->stat_accepted_rows += 1;
         }
         kappa = std::max(o.residual_tolerance / 10.0, std::min(o.central_path_scaling * kappa, std::pow(kappa, o.central_path_exponent)));   // :356
         tau = std::max(0.99, 1.0 - kappa);                                    // :359

@@ -112,7 +112,8 @@ int oracle_differentiate(oracle_solver*, oracle_eval_fn eval, void* user);
 /* iterate trace of the last oracle_solve: row k = solution.all after the k-th accepted inner iteration (solve.jl:309-326).
  * Returns the number of rows available; copies min(rows, cap_rows) rows of length N. */
 int64_t oracle_trace(oracle_solver*, double* out, int64_t cap_rows);
-/* per-solve statistics: [total_iterations, outer, factorizations, refinement_failures, max_refinement_rounds] */
+/* per-solve statistics: [total_iterations, outer, factorizations, refinement_failures, max_refinement_rounds, lu_fallbacks (`H \ residual`,
+ * search_direction.jl:22), last_refinement_rounds, accepted iterates of the last oracle_solve before its first lu fallback (-1: it took none)] */
 void oracle_stats(oracle_solver*, int64_t out[8]);
 /* elimination order used by factorize! (1-based perm of 1:n).  Default: [z | y | x]. */
 void oracle_set_perm(oracle_solver*, const int64_t* perm);

@@ -279,7 +279,8 @@ class OracleSolver:
         out = np.zeros(8, dtype=np.int64)
         self._L.oracle_stats(self._h, _pi(out))
         return dict(total_iterations=int(out[0]), outer=int(out[1]), factorizations=int(out[2]), refinement_failures=int(out[3]),
-                    max_refinement_rounds=int(out[4]), lu_fallbacks=int(out[5]), last_refinement_rounds=int(out[6]))
+                    max_refinement_rounds=int(out[4]), lu_fallbacks=int(out[5]), last_refinement_rounds=int(out[6]),
+                    first_lu_fallback_row=int(out[7]))      # accepted iterates of solve! before its first fallback, -1 when it took none
 
     # ---- evaluation callback plumbing --------------------------------------------------------
     def make_eval(self, problem):

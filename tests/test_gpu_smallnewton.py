@@ -81,12 +81,17 @@ def test_batched_solve_with_second_order_cones_matches_the_oracle(oracle_mod, la
     res, _ = sn.solve()
     st = sn.get_state()
     tr = sn.trace()
-    rounds_seen, compared = 0, 0
+    rounds_seen, compared, stopped = 0, 0, 0
     for k, prob in enumerate(probs):
         o, status = run_oracle(oracle_mod, prob)
         os_ = o.stats()
-        if os_["lu_fallbacks"] > 0:                       # the reference fell back to H \ residual: this path stops there and says so
+        if os_["lu_fallbacks"] > 0:                       # the reference fell back to H \ residual: this path stops there and says so, having accepted the same iterates
             assert res[k] == -102, (k, res[k])
+            rows, ot = int(st["counters"]["accepted_iterates"][k]), o.trace()
+            assert rows == os_["first_lu_fallback_row"], (k, rows, os_["first_lu_fallback_row"])
+            for r in range(min(rows, 96)):
+                assert rel(tr[k, r], ot[r]) <= 1e-8, (k, r, rel(tr[k, r], ot[r]))
+            stopped += 1
             continue
         assert status == int(res[k]) == 1, (k, status, res[k])
         compared += 1
@@ -99,6 +104,7 @@ def test_batched_solve_with_second_order_cones_matches_the_oracle(oracle_mod, la
         for r in range(min(rows, 96)):
             assert rel(tr[k, r], ot[r]) <= 1e-8, (k, r, rel(tr[k, r], ot[r]))
         assert rel(st["solution"][k], o.point()["all"]) <= 1e-8
+    assert compared + stopped == len(probs)               # every instance: whole, or up to the oracle's first fallback (whole with lu_fallback = 1: test_gpu_smallnewton_fallback.py)
     assert compared == 0 or rounds_seen >= 2              # the triu-symmetrised cone blocks do make refinement work (cold-started cone problems often end in the reference's fallback: compared == 0)
     sn.close()
 

@@ -202,3 +202,25 @@ def test_double_integrator_sensitivities(oracle_mod):
     Jp = o.mat("jacobian_parameters", o.N, prob.np)
     bufs_gp = o.mat("equality_jacobian_parameters", prob.ne, prob.np)
     assert np.abs(Jp[o.index("equality_dual") - 1] - bufs_gp).max() < 1e-12
+
+
+@pytest.mark.parametrize("nx,seed", [(15, 9), (1, 900), (128, 900)])
+def test_unconstrained_problems_crawl_as_in_the_reference(oracle_mod, nx, seed):
+    """ne = nc = 0 (quirk B-13): constraint_violation! returns norm(c, 1) / length(c) = 0.0 / 0 = NaN for the empty vector (constraint_violation.jl:13).  No comparison
+    with NaN holds: `theta <= slack_tolerance` (solve.jl:257) and both clauses of sufficient_progress (line_search.jl:11-12, whose merit clause subtracts
+    merit_tolerance * NaN) are false, so the residual line search never breaks, halves the step max_residual_line_search = 25 times and the iterate moves by 2^-25 of
+    the Newton step.  solve! therefore returns false after its 10 x 100 iterations, far from the minimiser -(2cP)^-1 q of the convex objective.  The oracle restates
+    this; pinned: the status, and that each of the first 20 accepted iterates is the one before minus 2^-25 of the regularised Newton step (2cP + 1e-7 I)^-1 (2cP x + q)."""
+    prob = pr.random_qp(nx, 0, 0, seed=seed, nonnegative_indices=[])
+    o, status = run(oracle_mod, prob)
+    st = o.stats()
+    assert status == 0 and st["outer"] == 10 and st["lu_fallbacks"] == 0 and st["total_iterations"] >= 801
+    H = 2.0 * prob.c * prob.P
+    newton = lambda x: np.linalg.solve(H + 1.0e-7 * np.eye(nx), H @ x + prob.q)
+    tr = o.trace()
+    assert np.abs(tr[0] - (prob.x0 - 2.0 ** -25 * newton(prob.x0))).max() <= 1e-12 * max(1.0, np.abs(prob.x0).max())
+    for k in range(20):
+        d = newton(tr[k])
+        assert np.abs((tr[k] - tr[k + 1]) * 2.0 ** 25 - d).max() <= 1e-6 * np.abs(d).max(), (k, np.abs((tr[k] - tr[k + 1]) * 2.0 ** 25 - d).max())
+    xs = np.linalg.solve(H, -prob.q)
+    assert np.abs(o.point()["x"] - xs).max() > 1.0

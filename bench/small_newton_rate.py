@@ -11,6 +11,9 @@ steps per instance in one launch; the same problems through the oracle on one ho
   --vjp               also differentiate! in reverse mode (SmallNewtonBatch.vjp): VJPs per second for k = 1 cotangent per instance — with --evaluator cartpole the
                       autotuning row (e_{u_1}, the first action) contracted with the evaluator's dR/dtheta, beside the forward differentiates (102 columns); for
                       QPs a random cotangent on x with the gradients of all QP data (grad_qp)
+  --layer [--repeats R]  instead of the launches: wall-clock milliseconds of torch_layer.QPLayer forward + backward (loss = sum(w * x), every input requires a gradient)
+                      with torch.cuda.synchronize() around the timed region, the first call discarded, R >= 5 repeats (default 7) reported as min and all values —
+                      (a) CPU tensors, (b) CUDA tensors, each with per-instance data and with ONE P shared by the batch
 e.g. the cold-started SOC batch of DESIGN 5.00: python bench/small_newton_rate.py 48 12 0 4096 --soc 4:4,4,4,4 --lu-fallback --general 8"""
 import json, os, sys, time
 import numpy as np
@@ -70,6 +73,37 @@ def evaluator_rate(name, B, vjp=False):
     print(json.dumps(out))
 
 
+def layer_rate(nx, ne, nc, q, dims, soc_idx, B, repeats):
+    import torch                                       # (one HIP runtime per process: torch first)
+    pkg = load_package()
+    from calipso_jl_amd.torch_layer import QPLayer
+    nprob = min(B, 64)
+    probs = [pr.random_qp(nx, ne, nc, seed=1000 + k, nonnegative_indices=list(range(1, q + 1)), second_order_indices=soc_idx or None) for k in range(nprob)]
+    idx = np.arange(B) % nprob
+    shape = {"P": (nx, nx), "q": (nx,), "A": (ne, nx), "b": (ne,), "G": (nc, nx), "h": (nc,)}
+    st = lambda name: np.stack([np.asarray(getattr(probs[i], name), dtype=np.float64).reshape(shape[name]) for i in idx])
+    data = {name: st(name) for name in "PqAbGh"}
+    wx = np.random.default_rng(0).standard_normal((B, nx))
+    out = {"layer": "QPLayer forward + backward, wall clock", "shape": [nx, ne, nc], "batch": B, "repeats": repeats, "torch": torch.__version__}
+    for device in ("cpu", "cuda"):
+        for variant in ("per_instance", "shared_P"):
+            sn = pkg.SmallNewtonBatch(nx, ne, nc, B)
+            if dims: sn.set_cones(q, dims)
+            ts = [torch.tensor(data[name][0] if (variant == "shared_P" and name == "P") else data[name], device=device, requires_grad=True) for name in "PqAbGh"]
+            w = torch.tensor(wx, device=device)
+            ms = []
+            for r in range(repeats + 1):
+                for t_ in ts: t_.grad = None
+                torch.cuda.synchronize(); t0 = time.perf_counter()
+                x = QPLayer.apply(sn, *ts, False, probs[0].c)
+                (x * w).sum().backward()
+                torch.cuda.synchronize(); ms.append(1e3 * (time.perf_counter() - t0))
+            ms = ms[1:]                                # (the first call sizes buffers and pools)
+            out["%s_%s" % (device, variant)] = {"ms_min": min(ms), "ms_median": float(np.median(ms)), "ms_all": ms, "finite_gradients": bool(all(torch.isfinite(t_.grad).all() for t_ in ts))}
+            sn.close()
+    print(json.dumps(out))
+
+
 def main():
     a = sys.argv[1:]
     flag = lambda name: name in a and (a.remove(name) or True)
@@ -82,6 +116,7 @@ def main():
         i = a.index("--evaluator"); ev = a[i + 1]; del a[i:i + 2]
         return evaluator_rate(ev, int(a[0]) if a else 4096, vjp)
     lu = flag("--lu-fallback")
+    layer = max(5, int(opt("--repeats") or 7)) if flag("--layer") else None
     soc_arg, general = opt("--soc"), int(opt("--general") or 0)
     nx, ne, nc = (int(a[0]), int(a[1]), int(a[2])) if len(a) >= 3 else (49, 40, 0)
     q, dims = nc, []
@@ -94,6 +129,7 @@ def main():
         soc_idx.append(list(range(at, at + dm))); at += dm
     B = int(a[3]) if len(a) > 3 else 4096
     K = int(a[4]) if len(a) > 4 else 20
+    if layer: return layer_rate(nx, ne, nc, q, dims, soc_idx, B, layer)
     pkg = load_package()
     nprob = min(B, 64)                                 # distinct problems (the batch cycles through them with perturbed starting points)
     probs = [pr.random_qp(nx, ne, nc, seed=1000 + k, nonnegative_indices=list(range(1, q + 1)), second_order_indices=soc_idx or None) for k in range(nprob)]

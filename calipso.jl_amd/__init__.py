@@ -846,6 +846,7 @@ class SmallNewtonBatch:
                 self._L.calipso_hip_smallnewton_destroy(h)
             raise CalipsoHipError("calipso_hip_smallnewton_create failed (%d): %s" % (rc, msg))
         self._h = h
+        self.device = int(device)
         for k, v in (options or {}).items():
             self.set_option(k, v)
 
@@ -1011,6 +1012,187 @@ class SmallNewtonBatch:
                 else:
                     out[name] = fin(np.transpose(blk, (0, 2, 1)).copy())
         return out
+
+    # ---- the device-resident, stream-ordered entries (include/calipso_hip.h; csrc/smallnewton_io.hip): torch CUDA tensors in and out, nothing waits for the device ----
+    _QP_NAMES = "PqAbGh"
+
+    def _qp_dims(self):
+        return ((self.nx, self.nx), (self.nx,), (self.ne, self.nx), (self.ne,), (self.nc, self.nx), (self.nc,))
+
+    def _form(self, t, name, shapes, dtype="float64"):
+        """a torch tensor of the dtype and one of the shapes, contiguous"""
+        import torch
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("%s must be a torch tensor" % name)
+        if t.dtype != getattr(torch, dtype):
+            raise ValueError("%s must be %s, not %s" % (name, dtype, t.dtype))
+        if tuple(t.shape) not in [tuple(s) for s in shapes]:
+            raise ValueError("%s must have shape %s, not %s" % (name, " or ".join(str(tuple(s)) for s in shapes), tuple(t.shape)))
+        if not t.is_contiguous():
+            raise ValueError("%s must be contiguous" % name)
+
+    def _ptr(self, t, name):
+        """a tensor on the handle's device: its device pointer (None for an empty tensor)"""
+        if not t.is_cuda:
+            raise ValueError("%s must be a CUDA tensor: the device entries take device memory only" % name)
+        if t.device.index != getattr(self, "device", 0):
+            raise ValueError("%s is on %s, the handle on device %d" % (name, t.device, getattr(self, "device", 0)))
+        return C.c_void_p(t.data_ptr()) if t.numel() else None
+
+    def _dev(self, t, name, shapes, dtype="float64"):
+        """the checks every tensor passes before any C call: its form, then where it lives; returns its device pointer"""
+        self._form(t, name, shapes, dtype)
+        return self._ptr(t, name)
+
+    def _empty(self, shape, dtype="float64"):
+        import torch
+        return torch.empty(shape, dtype=getattr(torch, dtype), device=torch.device("cuda", getattr(self, "device", 0)))
+
+    def set_stream(self, stream=None):
+        """all later work of the handle goes to `stream` — a torch.cuda.Stream (e.g. torch.cuda.current_stream()) or a raw hipStream_t as an int (0: the legacy
+        default stream) —, or back to the handle's own stream (None).  The new stream waits on the device for what the old one holds; the handle does not own it."""
+        if stream is None:
+            self._check(self._L.calipso_hip_smallnewton_set_stream(self._h, None, 0), "smallnewton_set_stream")
+        else:
+            raw = int(getattr(stream, "cuda_stream", stream))
+            self._check(self._L.calipso_hip_smallnewton_set_stream(self._h, C.c_void_p(raw), 1), "smallnewton_set_stream")
+
+    def set_qp_device(self, P, q, A, b, G, h, objective_scale=0.5, row_major=True):
+        """set_qp from float64 CUDA tensors, packed on the device.  Each array is ONE for all instances (P (nx, nx), q (nx,), A (ne, nx), ...) or stacked along a
+        leading batch axis, independently of the others: a shared P is stored once.  row_major=False: the matrices are column-major, i.e. tensors of the transposed
+        shape ([batch,] nx, rows).  Returns the mask of shared arrays (bit i: array i of P, q, A, b, G, h)."""
+        data, mask = (P, q, A, b, G, h), 0
+        for i, (name, t, dm) in enumerate(zip(self._QP_NAMES, data, self._qp_dims())):
+            if len(dm) == 2 and not row_major:
+                dm = (dm[1], dm[0])
+            self._form(t, name, (dm, (self.batch,) + dm))
+            if t.dim() == len(dm):
+                mask |= 1 << i
+        ptrs = [self._ptr(t, name) for name, t in zip(self._QP_NAMES, data)]
+        self._check(self._L.calipso_hip_smallnewton_set_qp_device(self._h, *ptrs, float(objective_scale), mask, int(bool(row_major))), "smallnewton_set_qp_device")
+        self._evaluator = False
+        return mask
+
+    def initialize_device(self, x0=None):
+        """initialize!(solver, guess) for every instance: x0 (batch, nx) on the device, or None for zeros"""
+        ptr = self._dev(x0, "x0", ((self.batch, self.nx),)) if x0 is not None else None
+        self._check(self._L.calipso_hip_smallnewton_initialize_device(self._h, ptr), "smallnewton_initialize_device")
+
+    def set_state_device(self, w=None, dual=None, scalars=None):
+        """set_state from CUDA tensors: w (batch, N), dual (batch, ne), scalars (batch, 3) [central_path, fraction_to_boundary, penalty]"""
+        pw = self._dev(w, "w", ((self.batch, self.N),)) if w is not None else None
+        pl = self._dev(dual, "dual", ((self.batch, self.ne),)) if dual is not None else None
+        ps = self._dev(scalars, "scalars", ((self.batch, 3),)) if scalars is not None else None
+        self._check(self._L.calipso_hip_smallnewton_set_state_device(self._h, pw, pl, ps), "smallnewton_set_state_device")
+
+    def set_parameters_device(self, theta):
+        """theta (batch, n_parameters) per instance, or (n_parameters,) shared by all, on the device"""
+        p = getattr(self, "n_parameters", -1)
+        ptr = self._dev(theta, "theta", ((self.batch, p), (p,)))
+        if ptr is not None:
+            self._check(self._L.calipso_hip_smallnewton_set_parameters_device(self._h, ptr, int(theta.dim() == 1)), "smallnewton_set_parameters_device")
+
+    def solve_device(self):
+        """solve! of every instance, enqueued on the handle's stream: nothing comes back (solution_device, status_device)"""
+        self._check(self._L.calipso_hip_smallnewton_solve_device(self._h), "smallnewton_solve_device")
+
+    def solution_device(self, out=None, parts="xyz"):
+        """x (batch, nx), y (batch, ne), z (batch, nc), w (batch, N) and status (batch,) int32 — the status of the last solve — gathered on the device: a dict
+        with the keys named in `parts` (letters of "xyzw" and "s" for status) and those of `out`, a dict of tensors to write into (allocated with torch otherwise)"""
+        shapes = dict(x=(self.batch, self.nx), y=(self.batch, self.ne), z=(self.batch, self.nc), w=(self.batch, self.N), status=(self.batch,))
+        res = dict(out or {})
+        for key in res:
+            if key not in shapes:
+                raise ValueError("solution_device: unknown output %r" % key)
+        for letter in parts:
+            key = "status" if letter == "s" else letter
+            if key not in shapes:
+                raise ValueError("solution_device: parts are letters of 'xyzws'")
+        ptrs = {key: self._dev(t, key, (shapes[key],), "int32" if key == "status" else "float64") for key, t in res.items()}
+        for letter in parts:
+            key = "status" if letter == "s" else letter
+            if key not in res:
+                res[key] = self._empty(shapes[key], "int32" if key == "status" else "float64")
+                ptrs[key] = C.c_void_p(res[key].data_ptr()) if res[key].numel() else None
+        self._check(self._L.calipso_hip_smallnewton_get_solution_device(self._h, *[ptrs.get(key) for key in ("x", "y", "z", "w", "status")]), "smallnewton_get_solution_device")
+        return res
+
+    def status_device(self):
+        """the solve status of every instance (1 converged, 0 caps reached, < 0: include/calipso_hip.h) of the last solve, as an int32 CUDA tensor: no read-back"""
+        return self.solution_device(parts="s")["status"]
+
+    def vjp_device(self, cotangent=None, x=None, y=None, z=None, adjoint=False, theta=None, qp=None, reduce="", out=None):
+        """vjp() on the device (calipso_hip_smallnewton_differentiate_adjoint_device), CUDA tensors in and out.  The cotangent: `cotangent` (batch, N[, k]), or its
+        parts x (batch, nx[, k]), y (batch, ne[, k]), z (batch, nc[, k]) — the rest zero.  theta / qp as vjp(); qp may also name the arrays wanted ("Pq").  reduce:
+        names of the QP arrays whose gradient is summed over the batch on the device (deterministic: fixed chunks of 64 instances in order).  Gradients of an
+        instance whose last SOLVE status is not 1 are NaN, before any sum.  Returns a dict as vjp() — "adjoint", "theta", "P" .. "h" in vjp()'s shapes (views of the
+        buffers the kernels wrote; summed arrays without the batch axis) — and "status" (batch,) int32 as differentiate(), all on the device.  out: buffers to
+        write into, in the kernels' layout: "adjoint" (batch, k, N), "theta" (batch, k, n_parameters), a QP array ([batch,] k) + its shape, "status" (batch,)."""
+        B, N = self.batch, self.N
+        mask = 0
+        for n in (reduce or ""):
+            if n not in self._QP_NAMES:
+                raise ValueError("vjp_device: reduce names arrays of " + self._QP_NAMES)
+            mask |= 1 << self._QP_NAMES.index(n)
+        given = [(n, t) for n, t in (("cotangent", cotangent), ("x", x), ("y", y), ("z", z)) if t is not None]
+        if not given or (cotangent is not None and len(given) > 1):
+            raise ValueError("vjp_device: the cotangent as `cotangent` (batch, N[, k]) or as parts x, y, z")
+        nd = given[0][1].dim() if hasattr(given[0][1], "dim") else -1
+        k = given[0][1].shape[2] if nd == 3 else 1
+        squeeze = nd != 3
+        if k < 1:
+            raise ValueError("vjp_device: k >= 1 cotangent columns")
+        widths = dict(cotangent=N, x=self.nx, y=self.ne, z=self.nc)
+        for n, t in given:
+            self._form(t, n, [(B, widths[n]) + ((k,) if nd == 3 else ())])
+        ptrs, keep = {}, []      # (keep: the permuted copies, alive until the call is enqueued)
+        for n, t in given:
+            ptrs[n] = self._ptr(t, n)
+            if nd == 3 and k > 1 and t.numel():      # (batch, n, k) -> the kernel's column-major n x k per instance
+                t = t.permute(0, 2, 1).contiguous()
+                ptrs[n] = C.c_void_p(t.data_ptr())
+            keep.append(t)
+        evaluator = getattr(self, "_evaluator", False)
+        p = getattr(self, "n_parameters", 0) if evaluator else 0
+        if theta is None:
+            theta = evaluator and p > 0
+        if qp is None:
+            qp = not evaluator
+        names = self._QP_NAMES if qp is True else ("" if not qp else "".join(qp))
+        out = dict(out or {})
+        bufs = {}
+
+        def buffer(key, shape, dtype="float64"):
+            if key in out:
+                self._dev(out[key], key, (shape,), dtype)
+                bufs[key] = out[key]
+            else:
+                bufs[key] = self._empty(shape, dtype)
+            return C.c_void_p(bufs[key].data_ptr()) if bufs[key].numel() else None
+
+        p_adj = buffer("adjoint", (B, k, N)) if adjoint else None
+        p_th = buffer("theta", (B, k, max(p, 1))) if theta else None
+        p_st = buffer("status", (B,), "int32")
+        gq = (C.c_void_p * 6)()
+        for i, (n, dm) in enumerate(zip(self._QP_NAMES, self._qp_dims())):
+            if n in names:
+                ptr = buffer(n, ((k,) if (mask >> i) & 1 else (B, k)) + dm)
+                gq[i] = ptr.value if ptr is not None else None
+        self._check(self._L.calipso_hip_smallnewton_differentiate_adjoint_device(
+            self._h, int(k), ptrs.get("cotangent"), ptrs.get("x"), ptrs.get("y"), ptrs.get("z"), p_adj, p_th, gq if names else None, mask, 1, p_st), "smallnewton_differentiate_adjoint_device")
+        res = dict(status=bufs["status"])
+        if adjoint:
+            res["adjoint"] = bufs["adjoint"][:, 0] if squeeze else bufs["adjoint"].permute(0, 2, 1)
+        if theta:
+            res["theta"] = bufs["theta"][:, 0] if squeeze else bufs["theta"].permute(0, 2, 1)
+        for i, (n, dm) in enumerate(zip(self._QP_NAMES, self._qp_dims())):
+            if n in names:
+                g = bufs[n]
+                if (mask >> i) & 1:
+                    res[n] = g[0] if squeeze else g.permute(*range(1, g.dim()), 0)
+                else:
+                    res[n] = g[:, 0] if squeeze else g.permute(0, *range(2, g.dim()), 1)
+        return res
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:

@@ -116,6 +116,14 @@ SYMBOLS = {
     "calipso_hip_smallnewton_set_parameters": (_i32, [_vp, _pd, _i32]),
     "calipso_hip_smallnewton_differentiate_parameters": (_i32, [_vp, _pd, _pi32, _pd]),
     "calipso_hip_smallnewton_differentiate_adjoint": (_i32, [_vp, _i64, _pd, _pd, _pd, _pd, _pi32, _pd]),
+    "calipso_hip_smallnewton_set_stream": (_i32, [_vp, _vp, _i32]),
+    "calipso_hip_smallnewton_set_qp_device": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _dbl, _i32, _i32]),
+    "calipso_hip_smallnewton_initialize_device": (_i32, [_vp, _vp]),
+    "calipso_hip_smallnewton_set_state_device": (_i32, [_vp, _vp, _vp, _vp]),
+    "calipso_hip_smallnewton_set_parameters_device": (_i32, [_vp, _vp, _i32]),
+    "calipso_hip_smallnewton_solve_device": (_i32, [_vp]),
+    "calipso_hip_smallnewton_get_solution_device": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "calipso_hip_smallnewton_differentiate_adjoint_device": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_vp), _i32, _i32, _vp]),
     "calipso_hip_comm_unique_id": (_i32, [C.POINTER(C.c_uint8)]),
     "calipso_hip_comm_init": (_i32, [_i32, _i32, C.POINTER(C.c_uint8), _i32, C.POINTER(_vp)]),
     "calipso_hip_comm_destroy": (_i32, [_vp]),

@@ -25,43 +25,27 @@
 
 #include "internal.hpp"
 #include "device_utils.hpp"
-#include "../../include/calipso_smallnewton.hpp"      // Dm, Lay, Args, the device code, QpEval
-
-struct calipso_hip_smallnewton {
-    int nx = 0, ne = 0, nc = 0, batch = 0, device = 0;
-    int nq = 0; std::vector<int> soc_start, soc_dim, soc_woff; int wsz = 0, maxd = 0;      // cone layout: nq nonnegative entries, then the second-order cones (contiguous)
-    int *d_soc = nullptr;                                                                   // device: [start | dim | woff], nsoc each
-    calipso::Options opt;
-    double objective_scale = 0.5;
-    bool shared_qp = false, have_qp = false;
-    calipso_smallnewton_kernels_fn ev = nullptr; int np = 0; bool ev_rtheta = false, ev_adj = false;      // set_evaluator: the user library's entry, parameters per instance, dR/dtheta provided, reverse mode built
-    double *theta = nullptr, *hess = nullptr, *dpt = nullptr; bool theta_shared = false, have_theta = false;      // parameters (batch x np or one row), Lagrangian Hessians (batch x nx^2), the points they were evaluated at (batch x (nx + m))
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    double *P = nullptr, *q = nullptr, *Z = nullptr, *bh = nullptr;      // Lxx = 2 c P (nx x nx), q, Z = [A; -G] (m x nx, ld m), bh = [-b; h]: per instance or shared
-    double *w = nullptr, *lam = nullptr, *sc = nullptr, *filt = nullptr, *info = nullptr, *trace = nullptr, *prof = nullptr;
-    double *rtheta = nullptr, *sens = nullptr, *stf = nullptr; size_t cap_diff = 0; bool diff_shared = false;      // differentiate!: batch x N x p each
-    double *adj_rt = nullptr, *adj_in = nullptr, *adj_out = nullptr, *adj_gth = nullptr, *adj_gqp = nullptr;      // reverse mode: dR/dtheta, cotangents, lambda, gradients
-    size_t cap_adj_rt = 0, cap_adj_in = 0, cap_adj_out = 0, cap_adj_gth = 0, cap_adj_gqp = 0;                      // (their capacities in doubles, grown on demand)
-    long long* cnt = nullptr; int* status = nullptr;
-    int trace_rows = 0;
-    size_t lds_bytes = 0;
-    int threads = 0;                 // options.threads: 0 = by the LDS footprint (sn_threads), 64 / 128 / 256 forced
-    bool lu = false; double* Hs = nullptr;      // options.lu_fallback: H \ residual in the kernel, batch x N x N doubles of scratch for H and its factors
-    double last_ms = 0.0;
-    std::string err;
-};
+#include "smallnewton_handle.hpp"                      // the handle; include/calipso_smallnewton.hpp: Dm, Lay, Args, the device code, QpEval
 
 namespace {
 using calipso::Options;
 typedef calipso_hip_smallnewton SN;
 
 using namespace calipso::sn;
+using calipso::snh::fail;
+using calipso::snh::dims_of;
+using calipso::snh::launch;
+using calipso::snh::grow;
 
-int fail(SN* s, int code, const std::string& msg) { s->err = msg; return code; }
 thread_local std::string g_sn_err;
 
 #define SK(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return fail(s, CALIPSO_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); } while (0)
+
+}  // namespace
+
+namespace calipso {
+namespace snh {
+int fail(SN* s, int code, const std::string& msg) { s->err = msg; return code; }
 
 Dm dims_of(const SN* s) {
     Dm d; d.nx = s->nx; d.ne = s->ne; d.nc = s->nc; d.m = s->ne + s->nc; d.n = s->nx + d.m; d.N = s->nx + 2 * s->ne + 3 * s->nc;
@@ -70,6 +54,22 @@ Dm dims_of(const SN* s) {
     return d;
 }
 
+// a device buffer of at least `need` doubles (grown, never shrunk)
+int grow(SN* s, double** p, size_t* cap, size_t need, const char* who) {
+    if (need <= *cap) return CALIPSO_OK;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr; *cap = 0;
+    if (hipMalloc((void**)p, sizeof(double) * need) != hipSuccess) {
+        (void)hipGetLastError(); *p = nullptr;
+        return fail(s, CALIPSO_ERR_HIP, std::string(who) + ": device allocation of " + std::to_string(sizeof(double) * need) + " bytes failed");
+    }
+    *cap = need;
+    return CALIPSO_OK;
+}
+}  // namespace snh
+}  // namespace calipso
+
+namespace {
 // threads per instance.  The kernel is a chain of dependent phases: a compute unit's throughput is (resident instances) / (latency of one), the latency grows slowly as
 // wavefronts are taken away (C5 shape at equal residency: 92.7 / 99.7 / 121.4 us a step with 4 / 2 / 1 wavefronts), and with 256 registers per thread a compute unit
 // holds 8 wavefronts.  So: as many instances as the LDS footprint allows, and the most wavefronts each that still fit — one wavefront from 6 instances per compute unit,
@@ -98,17 +98,20 @@ int grant_lds(SN* s) {
     return CALIPSO_OK;
 }
 
-// adj: MODE_ADJ's extra arguments (its `base` is filled here)
-int launch(SN* s, int mode, int count, int advance, bool eval_rtheta = false, const AdjArgs* adj = nullptr) {
+}  // namespace
+
+namespace calipso {
+namespace snh {
+using sn::QpEval;      // (calipso::QpEval is the general path's)
+
+int launch(SN* s, int mode, int count, int advance, bool eval_rtheta, const AdjArgs* adj, bool enqueue_only) {
     if (!s->have_qp && !s->ev) return fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_smallnewton: no problem data (calipso_hip_smallnewton_set_qp or calipso_hip_smallnewton_set_evaluator)");
     if (s->ev && s->np > 0 && !s->have_theta) return fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_smallnewton: the evaluator takes " + std::to_string(s->np) + " parameters and none were set (calipso_hip_smallnewton_set_parameters)");
     SK(hipSetDevice(s->device));
     Args a;
     a.d = dims_of(s); a.o = s->opt;
-    const size_t nx = s->nx, m = a.d.m;
     a.P = s->P; a.q = s->q; a.Z = s->Z; a.bh = s->bh;
-    a.sP = s->shared_qp ? 0 : (long long)(nx * nx); a.sq = s->shared_qp ? 0 : (long long)nx; a.sZ = s->shared_qp ? 0 : (long long)(std::max<size_t>(m, 1) * nx);
-    a.sbh = s->shared_qp ? 0 : (long long)std::max<size_t>(m, 1);
+    a.sP = s->sP; a.sq = s->sq; a.sZ = s->sZ; a.sbh = s->sbh;
     a.w = s->w; a.lam = s->lam; a.sc = s->sc; a.filt = s->filt; a.info = s->info; a.trace = s->trace; a.prof = s->prof; a.cnt = s->cnt; a.status = s->status;
     { const int ns = (int)s->soc_dim.size(); a.soc_start = s->d_soc; a.soc_dim = s->d_soc ? s->d_soc + ns : nullptr; a.soc_woff = s->d_soc ? s->d_soc + 2 * ns : nullptr; }
     a.batch = s->batch; a.mode = mode; a.count = count; a.advance = advance; a.trace_rows = s->trace_rows;
@@ -121,7 +124,7 @@ int launch(SN* s, int mode, int count, int advance, bool eval_rtheta = false, co
         aa = *adj; aa.base = a;
         aa.base.rtheta = s->adj_rt; aa.base.srtheta = (long long)a.d.N * (long long)count;
     }
-    SK(hipEventRecord(s->ev0, s->stream));
+    if (!enqueue_only) SK(hipEventRecord(s->ev0, s->stream));
     const bool soc = !s->soc_dim.empty();
     if (s->ev) {      // the evaluator's own builds of the kernels, launched by its entry on the handle's stream
         int64_t out[5] = {0, 0, 0, 0, 0};
@@ -143,7 +146,12 @@ int launch(SN* s, int mode, int count, int advance, bool eval_rtheta = false, co
         SK(hipLaunchKernel(kernel_of<QpEval>(nt, soc, s->lu), dim3((unsigned)s->batch), dim3((unsigned)nt), args, s->lds_bytes, s->stream));
     }
     SK(hipGetLastError());
+    if (enqueue_only) {
+        if (mode == MODE_SOLVE) SK(hipMemcpyAsync(s->solve_status, s->status, sizeof(int) * (size_t)s->batch, hipMemcpyDeviceToDevice, s->stream));
+        return CALIPSO_OK;
+    }
     SK(hipEventRecord(s->ev1, s->stream));
+    if (mode == MODE_SOLVE) SK(hipMemcpyAsync(s->solve_status, s->status, sizeof(int) * (size_t)s->batch, hipMemcpyDeviceToDevice, s->stream));
     SK(hipStreamSynchronize(s->stream));
     float ms = 0.f;
     SK(hipEventElapsedTime(&ms, s->ev0, s->ev1));
@@ -151,7 +159,8 @@ int launch(SN* s, int mode, int count, int advance, bool eval_rtheta = false, co
     return CALIPSO_OK;
 }
 
-}  // namespace
+}  // namespace snh
+}  // namespace calipso
 
 extern "C" {
 
@@ -172,14 +181,16 @@ int32_t calipso_hip_smallnewton_create(int64_t nx, int64_t ne, int64_t nc, int64
     if (s->lds_bytes > 160 * 1024) return fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_smallnewton_create: the problem does not fit the 160 KB of LDS of a compute unit (" + std::to_string(s->lds_bytes) + " bytes): the general path takes it");
     SK(hipSetDevice(device));
     grant_lds(s);
-    SK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-    SK(hipEventCreate(&s->ev0)); SK(hipEventCreate(&s->ev1));
+    SK(hipStreamCreateWithFlags(&s->own_stream, hipStreamNonBlocking));
+    s->stream = s->own_stream;
+    SK(hipEventCreate(&s->ev0)); SK(hipEventCreate(&s->ev1)); SK(hipEventCreateWithFlags(&s->ev_order, hipEventDisableTiming));
     const size_t B = (size_t)batch, N = (size_t)d.N;
     auto alloc = [&](double** p, size_t n) { if (hipMalloc((void**)p, sizeof(double) * std::max<size_t>(n, 1)) != hipSuccess) return false; return hipMemsetAsync(*p, 0, sizeof(double) * std::max<size_t>(n, 1), s->stream) == hipSuccess; };
     if (!alloc(&s->w, B * N) || !alloc(&s->lam, B * std::max(1, d.ne)) || !alloc(&s->sc, B * SC_COUNT) || !alloc(&s->filt, B * 6 * (size_t)s->opt.max_filter) || !alloc(&s->info, B * IN_COUNT) || !alloc(&s->prof, 16) || !alloc(&s->stf, B * 2 * (size_t)std::max(1, d.nc)))
         return fail(s, CALIPSO_ERR_HIP, "calipso_hip_smallnewton_create: device allocation failed");
     SK(hipMalloc((void**)&s->cnt, sizeof(long long) * B * CN_COUNT)); SK(hipMemsetAsync(s->cnt, 0, sizeof(long long) * B * CN_COUNT, s->stream));
     SK(hipMalloc((void**)&s->status, sizeof(int) * B)); SK(hipMemsetAsync(s->status, 0, sizeof(int) * B, s->stream));
+    SK(hipMalloc((void**)&s->solve_status, sizeof(int) * B)); SK(hipMemsetAsync(s->solve_status, 0, sizeof(int) * B, s->stream));
     {   // solver.jl:81-85 defaults of the scalars
         std::vector<double> sc(B * SC_COUNT, 0.0);
         for (size_t k = 0; k < B; ++k) { sc[k * SC_COUNT + SC_KAPPA] = 0.1; sc[k * SC_COUNT + SC_TAU] = 0.99; sc[k * SC_COUNT + SC_RHO] = 10.0; }
@@ -193,14 +204,17 @@ int32_t calipso_hip_smallnewton_destroy(calipso_hip_smallnewton* s) {
     if (!s) return CALIPSO_OK;
     (void)hipSetDevice(s->device);
     if (s->stream) (void)hipStreamSynchronize(s->stream);
+    if (s->own_stream && s->own_stream != s->stream) (void)hipStreamSynchronize(s->own_stream);
     for (double* p : {s->P, s->q, s->Z, s->bh, s->theta, s->hess, s->dpt, s->w, s->lam, s->sc, s->filt, s->info, s->trace, s->prof, s->rtheta, s->sens, s->stf, s->Hs,
-                      s->adj_rt, s->adj_in, s->adj_out, s->adj_gth, s->adj_gqp}) if (p) (void)hipFree(p);
+                      s->adj_rt, s->adj_in, s->adj_out, s->adj_gth, s->adj_gqp, s->red}) if (p) (void)hipFree(p);
     if (s->cnt) (void)hipFree(s->cnt);
     if (s->d_soc) (void)hipFree(s->d_soc);
     if (s->status) (void)hipFree(s->status);
+    if (s->solve_status) (void)hipFree(s->solve_status);
     if (s->ev0) (void)hipEventDestroy(s->ev0);
     if (s->ev1) (void)hipEventDestroy(s->ev1);
-    if (s->stream) (void)hipStreamDestroy(s->stream);
+    if (s->ev_order) (void)hipEventDestroy(s->ev_order);
+    if (s->own_stream) (void)hipStreamDestroy(s->own_stream);
     delete s;
     return CALIPSO_OK;
 }
@@ -298,6 +312,7 @@ int32_t calipso_hip_smallnewton_set_qp(calipso_hip_smallnewton* s, const double*
     SK(hipSetDevice(s->device));
     const size_t nx = s->nx, ne = s->ne, nc = s->nc, m = ne + nc, K = shared ? 1 : (size_t)s->batch;
     for (double** p : {&s->P, &s->q, &s->Z, &s->bh}) if (*p) { (void)hipFree(*p); *p = nullptr; }
+    s->cap_P = s->cap_q = s->cap_Z = s->cap_bh = 0;
     std::vector<double> Lxx(K * nx * nx), Z(K * std::max<size_t>(m, 1) * nx, 0.0), bh(K * std::max<size_t>(m, 1), 0.0);
     for (size_t k = 0; k < K; ++k) {
         for (size_t e = 0; e < nx * nx; ++e) Lxx[k * nx * nx + e] = 2.0 * objective_scale * P[k * nx * nx + e];
@@ -316,9 +331,12 @@ int32_t calipso_hip_smallnewton_set_qp(calipso_hip_smallnewton* s, const double*
     SK(hipMemcpyAsync(s->Z, Z.data(), sizeof(double) * Z.size(), hipMemcpyHostToDevice, s->stream));
     SK(hipMemcpyAsync(s->bh, bh.data(), sizeof(double) * bh.size(), hipMemcpyHostToDevice, s->stream));
     SK(hipStreamSynchronize(s->stream));
-    s->shared_qp = shared != 0; s->have_qp = true; s->objective_scale = objective_scale;
+    s->sP = shared ? 0 : (long long)(nx * nx); s->sq = shared ? 0 : (long long)nx; s->sZ = shared ? 0 : (long long)(std::max<size_t>(m, 1) * nx); s->sbh = shared ? 0 : (long long)std::max<size_t>(m, 1);
+    s->cap_P = Lxx.size(); s->cap_q = K * nx; s->cap_Z = Z.size(); s->cap_bh = bh.size();
+    s->have_qp = true; s->objective_scale = objective_scale;
     s->ev = nullptr; s->np = 0; s->ev_rtheta = false; s->ev_adj = false; s->have_theta = false;      // (replaces an evaluator)
     for (double** p : {&s->theta, &s->hess, &s->dpt}) if (*p) { (void)hipFree(*p); *p = nullptr; }
+    s->cap_theta = 0;
     return CALIPSO_OK;
 }
 
@@ -336,6 +354,7 @@ int32_t calipso_hip_smallnewton_set_evaluator(calipso_hip_smallnewton* s, calips
     SK(hipSetDevice(s->device));
     SK(hipStreamSynchronize(s->stream));
     for (double** p : {&s->P, &s->q, &s->Z, &s->bh, &s->theta, &s->hess, &s->dpt}) if (*p) { (void)hipFree(*p); *p = nullptr; }
+    s->cap_P = s->cap_q = s->cap_Z = s->cap_bh = s->cap_theta = 0;
     s->have_qp = false; s->ev = nullptr; s->have_theta = false;
     const size_t bytes = sizeof(double) * (size_t)s->batch * (size_t)s->nx * (size_t)s->nx;
     if (hipMalloc((void**)&s->hess, bytes) != hipSuccess) {
@@ -358,8 +377,9 @@ int32_t calipso_hip_smallnewton_set_parameters(calipso_hip_smallnewton* s, const
     SK(hipSetDevice(s->device));
     SK(hipStreamSynchronize(s->stream));
     const size_t n = (size_t)s->np * (shared ? 1 : (size_t)s->batch);
-    if (s->theta) { (void)hipFree(s->theta); s->theta = nullptr; }
+    if (s->theta) { (void)hipFree(s->theta); s->theta = nullptr; s->cap_theta = 0; }
     SK(hipMalloc((void**)&s->theta, sizeof(double) * n));
+    s->cap_theta = n;
     SK(hipMemcpy(s->theta, theta, sizeof(double) * n, hipMemcpyHostToDevice));
     s->theta_shared = shared != 0; s->have_theta = true;
     return CALIPSO_OK;
@@ -428,7 +448,7 @@ int32_t calipso_hip_smallnewton_trace(calipso_hip_smallnewton* s, int32_t rows, 
 // (lu_fallback = 0), -100 - CALIPSO_WARN_ZERO_PIVOT where that fallback met an exactly singular H (lu_fallback = 1).
 int32_t calipso_hip_smallnewton_solve(calipso_hip_smallnewton* s, int32_t* result, double* ms) {
     if (!s) return CALIPSO_ERR_ARGUMENT;
-    const int rc = launch(s, MODE_SOLVE, 0, 1);
+    const int rc = launch(s, MODE_SOLVE, 0, 1, false, nullptr, false);
     if (rc < 0) return rc;
     if (result) SK(hipMemcpy(result, s->status, sizeof(int) * (size_t)s->batch, hipMemcpyDeviceToHost));
     if (ms) *ms = s->last_ms;
@@ -440,7 +460,7 @@ int32_t calipso_hip_smallnewton_solve(calipso_hip_smallnewton* s, int32_t* resul
 // candidate, exit kind (2: inner-loop exit of solve.jl:165, no step), optimality error] of the LAST step; status as calipso_hip_smallnewton_solve (0: stepped).
 int32_t calipso_hip_smallnewton_steps(calipso_hip_smallnewton* s, int32_t count, int32_t advance, double* info, int32_t* status, double* ms) {
     if (!s || count < 0) return CALIPSO_ERR_ARGUMENT;
-    const int rc = launch(s, MODE_STEPS, count, advance);
+    const int rc = launch(s, MODE_STEPS, count, advance, false, nullptr, false);
     if (rc < 0) return rc;
     if (info) SK(hipMemcpy(info, s->info, sizeof(double) * (size_t)s->batch * IN_COUNT, hipMemcpyDeviceToHost));
     if (status) SK(hipMemcpy(status, s->status, sizeof(int) * (size_t)s->batch, hipMemcpyDeviceToHost));
@@ -475,7 +495,7 @@ int32_t calipso_hip_smallnewton_differentiate(calipso_hip_smallnewton* s, int64_
     { const int rc = diff_buffers(s, need); if (rc < 0) return rc; }
     SK(hipMemcpyAsync(s->rtheta, jacobian_parameters, sizeof(double) * (shared ? (size_t)d.N * (size_t)p : need), hipMemcpyHostToDevice, s->stream));
     s->diff_shared = shared != 0;
-    const int rc = launch(s, MODE_DIFF, (int)p, 0);
+    const int rc = launch(s, MODE_DIFF, (int)p, 0, false, nullptr, false);
     if (rc < 0) return rc;
     SK(hipMemcpy(sensitivity, s->sens, sizeof(double) * need, hipMemcpyDeviceToHost));
     if (status) SK(hipMemcpy(status, s->status, sizeof(int) * (size_t)s->batch, hipMemcpyDeviceToHost));
@@ -493,7 +513,7 @@ int32_t calipso_hip_smallnewton_differentiate_parameters(calipso_hip_smallnewton
     const size_t need = (size_t)s->batch * (size_t)d.N * (size_t)s->np;
     { const int rc = diff_buffers(s, need); if (rc < 0) return rc; }
     s->diff_shared = false;
-    const int rc = launch(s, MODE_DIFF, s->np, 0, true);
+    const int rc = launch(s, MODE_DIFF, s->np, 0, true, nullptr, false);
     if (rc < 0) return rc;
     SK(hipMemcpy(sensitivity, s->sens, sizeof(double) * need, hipMemcpyDeviceToHost));
     if (status) SK(hipMemcpy(status, s->status, sizeof(int) * (size_t)s->batch, hipMemcpyDeviceToHost));
@@ -505,21 +525,6 @@ int32_t calipso_hip_smallnewton_differentiate_parameters(calipso_hip_smallnewton
 // calipso_hip_smallnewton_differentiate applies to a column of dR/dtheta (the same factorisation; refinement against H' for batches without second-order
 // cones, none with them: quirk B-3), then grad = -R_theta' lambda = S' v for the S that differentiate would return.  R_theta: the evaluator's dR/dtheta at the
 // resident points (grad_theta), or the built-in QP's data (grad_qp: P, q, A, b, G, h in set_qp's column-major block order, P's gradient symmetric).
-namespace {
-// a device buffer of at least `need` doubles (grown, never shrunk)
-int grow(SN* s, double** p, size_t* cap, size_t need) {
-    if (need <= *cap) return CALIPSO_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr; *cap = 0;
-    if (hipMalloc((void**)p, sizeof(double) * need) != hipSuccess) {
-        (void)hipGetLastError(); *p = nullptr;
-        return fail(s, CALIPSO_ERR_HIP, "calipso_hip_smallnewton_differentiate_adjoint: device allocation of " + std::to_string(sizeof(double) * need) + " bytes failed");
-    }
-    *cap = need;
-    return CALIPSO_OK;
-}
-}  // namespace
-
 int32_t calipso_hip_smallnewton_differentiate_adjoint(calipso_hip_smallnewton* s, int64_t k, const double* cotangent, double* adjoint, double* grad_theta, double* grad_qp,
                                                       int32_t* status, double* ms) {
     if (!s) return CALIPSO_ERR_ARGUMENT;
@@ -536,18 +541,18 @@ int32_t calipso_hip_smallnewton_differentiate_adjoint(calipso_hip_smallnewton* s
     const Dm d = dims_of(s);
     const size_t B = (size_t)s->batch, N = (size_t)d.N, K = (size_t)k;
     const size_t nqp = (size_t)d.nx * d.nx + d.nx + (size_t)d.ne * d.nx + d.ne + (size_t)d.nc * d.nx + d.nc;
-    int rc = grow(s, &s->adj_in, &s->cap_adj_in, B * N * K);
-    if (rc == CALIPSO_OK && adjoint) rc = grow(s, &s->adj_out, &s->cap_adj_out, B * N * K);
-    if (rc == CALIPSO_OK && grad_theta) rc = grow(s, &s->adj_rt, &s->cap_adj_rt, B * N * (size_t)s->np);
-    if (rc == CALIPSO_OK && grad_theta) rc = grow(s, &s->adj_gth, &s->cap_adj_gth, B * K * (size_t)s->np);
-    if (rc == CALIPSO_OK && grad_qp) rc = grow(s, &s->adj_gqp, &s->cap_adj_gqp, B * K * nqp);
+    int rc = grow(s, &s->adj_in, &s->cap_adj_in, B * N * K, "calipso_hip_smallnewton_differentiate_adjoint");
+    if (rc == CALIPSO_OK && adjoint) rc = grow(s, &s->adj_out, &s->cap_adj_out, B * N * K, "calipso_hip_smallnewton_differentiate_adjoint");
+    if (rc == CALIPSO_OK && grad_theta) rc = grow(s, &s->adj_rt, &s->cap_adj_rt, B * N * (size_t)s->np, "calipso_hip_smallnewton_differentiate_adjoint");
+    if (rc == CALIPSO_OK && grad_theta) rc = grow(s, &s->adj_gth, &s->cap_adj_gth, B * K * (size_t)s->np, "calipso_hip_smallnewton_differentiate_adjoint");
+    if (rc == CALIPSO_OK && grad_qp) rc = grow(s, &s->adj_gqp, &s->cap_adj_gqp, B * K * nqp, "calipso_hip_smallnewton_differentiate_adjoint");
     if (rc < 0) return rc;
     SK(hipMemcpyAsync(s->adj_in, cotangent, sizeof(double) * B * N * K, hipMemcpyHostToDevice, s->stream));
     AdjArgs aa;
     std::memset(&aa, 0, sizeof(aa));
     aa.cot = s->adj_in; aa.adjoint = adjoint ? s->adj_out : nullptr; aa.grad_theta = grad_theta ? s->adj_gth : nullptr; aa.grad_qp = grad_qp ? s->adj_gqp : nullptr;
     aa.objective_scale = s->objective_scale; aa.k = (int)k;
-    rc = launch(s, MODE_ADJ, grad_theta ? s->np : 0, 0, grad_theta != nullptr, &aa);
+    rc = launch(s, MODE_ADJ, grad_theta ? s->np : 0, 0, grad_theta != nullptr, &aa, false);
     if (rc < 0) return rc;
     if (adjoint) SK(hipMemcpy(adjoint, s->adj_out, sizeof(double) * B * N * K, hipMemcpyDeviceToHost));
     if (grad_theta) SK(hipMemcpy(grad_theta, s->adj_gth, sizeof(double) * B * K * (size_t)s->np, hipMemcpyDeviceToHost));

@@ -618,6 +618,48 @@ function solution(s::HIPSmallNewton)
     return w
 end
 
+# ---- the device-resident, stream-ordered entries of the batch kernel (include/calipso_hip.h: calipso_hip_smallnewton_*_device; csrc/smallnewton_io.hip) ----
+# Every array argument is a DEVICE pointer on the handle's device (e.g. `Ptr{Float64}(UInt(pointer(a)))` of an AMDGPU.jl ROCArray; column-major Julia arrays:
+# row_major = false); the work is enqueued on the handle's stream and nothing waits for it.  C_NULL skips an optional argument.
+const DevPtr = Ptr{Float64}
+"all later work of the handle on the caller's hipStream_t (`stream`: a pointer; C_NULL = the legacy default stream), or `nothing`: back to the handle's own stream"
+function set_stream!(s::HIPSmallNewton, stream::Union{Nothing,Ptr{Cvoid}})
+    sn_check(s, ccall((:calipso_hip_smallnewton_set_stream, lib), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int32), s.handle, stream === nothing ? C_NULL : stream, stream === nothing ? 0 : 1), "calipso_hip_smallnewton_set_stream")
+end
+"set_qp! from device arrays; bit i of shared_mask: array i of P, q, A, b, G, h is one array for all instances"
+function set_qp_device!(s::HIPSmallNewton, P::DevPtr, q::DevPtr, A::DevPtr, b::DevPtr, G::DevPtr, h::DevPtr; objective_scale::Float64=0.5, shared_mask::Integer=0, row_major::Bool=false)
+    sn_check(s, ccall((:calipso_hip_smallnewton_set_qp_device, lib), Int32, (Ptr{Cvoid}, DevPtr, DevPtr, DevPtr, DevPtr, DevPtr, DevPtr, Float64, Int32, Int32),
+                      s.handle, P, q, A, b, G, h, objective_scale, shared_mask, row_major ? 1 : 0), "calipso_hip_smallnewton_set_qp_device")
+    s.np = 0
+    return s
+end
+"initialize! with the guesses on the device (nx x batch), or zeros (C_NULL)"
+initialize_device!(s::HIPSmallNewton, x0::DevPtr=DevPtr(C_NULL)) =
+    sn_check(s, ccall((:calipso_hip_smallnewton_initialize_device, lib), Int32, (Ptr{Cvoid}, DevPtr), s.handle, x0), "calipso_hip_smallnewton_initialize_device")
+"points (N x batch), lambda (ne x batch), [central_path, fraction_to_boundary, penalty] (3 x batch) from the device; C_NULL leaves what is resident"
+set_state_device!(s::HIPSmallNewton, w::DevPtr, lambda::DevPtr=DevPtr(C_NULL), scalars::DevPtr=DevPtr(C_NULL)) =
+    sn_check(s, ccall((:calipso_hip_smallnewton_set_state_device, lib), Int32, (Ptr{Cvoid}, DevPtr, DevPtr, DevPtr), s.handle, w, lambda, scalars), "calipso_hip_smallnewton_set_state_device")
+"theta on the device: n_parameters x batch, or one n_parameters vector for all (shared)"
+set_parameters_device!(s::HIPSmallNewton, theta::DevPtr; shared::Bool=false) =
+    sn_check(s, ccall((:calipso_hip_smallnewton_set_parameters_device, lib), Int32, (Ptr{Cvoid}, DevPtr, Int32), s.handle, theta, shared ? 1 : 0), "calipso_hip_smallnewton_set_parameters_device")
+"solve! of every instance, enqueued: nothing is read back (solution_device!)"
+solve_device!(s::HIPSmallNewton) = sn_check(s, ccall((:calipso_hip_smallnewton_solve_device, lib), Int32, (Ptr{Cvoid},), s.handle), "calipso_hip_smallnewton_solve_device")
+"x (nx x batch), y (ne x batch), z (nc x batch), w (N x batch) and the Int32 status of the last solve (batch) into device arrays; C_NULL skips one"
+solution_device!(s::HIPSmallNewton; x::DevPtr=DevPtr(C_NULL), y::DevPtr=DevPtr(C_NULL), z::DevPtr=DevPtr(C_NULL), w::DevPtr=DevPtr(C_NULL), status::Ptr{Int32}=Ptr{Int32}(C_NULL)) =
+    sn_check(s, ccall((:calipso_hip_smallnewton_get_solution_device, lib), Int32, (Ptr{Cvoid}, DevPtr, DevPtr, DevPtr, DevPtr, Ptr{Int32}), s.handle, x, y, z, w, status), "calipso_hip_smallnewton_get_solution_device")
+"""differentiate_adjoint! on the device: k cotangent columns as `cot_w` (N x k x batch) or as the parts `cot_x`, `cot_y`, `cot_z`; `adjoint` (N x k x batch) and
+`grad_theta` (n_parameters x k x batch) are written by the launch; `grad_qp`: six device pointers (P, q, A, b, G, h; C_NULL skips one), per instance (size x k x batch)
+or, with bit i of `reduce_mask`, summed over the batch on the device (size x k).  Gradients of instances whose solve status is not 1 are NaN."""
+function differentiate_adjoint_device!(s::HIPSmallNewton, k::Integer; cot_w::DevPtr=DevPtr(C_NULL), cot_x::DevPtr=DevPtr(C_NULL), cot_y::DevPtr=DevPtr(C_NULL), cot_z::DevPtr=DevPtr(C_NULL),
+                                       adjoint::DevPtr=DevPtr(C_NULL), grad_theta::DevPtr=DevPtr(C_NULL), grad_qp::Union{Nothing,Vector{DevPtr}}=nothing, reduce_mask::Integer=0,
+                                       row_major::Bool=false, status::Ptr{Int32}=Ptr{Int32}(C_NULL))
+    grad_qp === nothing || length(grad_qp) == 6 || error("grad_qp: six device pointers (P, q, A, b, G, h)")
+    gq = grad_qp === nothing ? Ptr{DevPtr}(C_NULL) : pointer(grad_qp)
+    GC.@preserve grad_qp sn_check(s, ccall((:calipso_hip_smallnewton_differentiate_adjoint_device, lib), Int32,
+        (Ptr{Cvoid}, Int64, DevPtr, DevPtr, DevPtr, DevPtr, DevPtr, DevPtr, Ptr{DevPtr}, Int32, Int32, Ptr{Int32}),
+        s.handle, k, cot_w, cot_x, cot_y, cot_z, adjoint, grad_theta, gq, reduce_mask, row_major ? 1 : 0, status), "calipso_hip_smallnewton_differentiate_adjoint_device")
+end
+
 # ---- multi-GPU exchange (include/calipso_hip.h: calipso_hip_comm_*): RCCL over xGMI, one process per GPU -------------------------
 "RCCL communicator: `id = comm_unique_id()` on one rank, distributed by the launcher (file / MPI / Distributed.jl), then `HIPComm(rank, nranks, id; device)` on every rank."
 mutable struct HIPComm
@@ -659,7 +701,7 @@ function allreduce_sum!(c::HIPComm, v::Vector{Float64})
     return v
 end
 
-export HIPSolver, streams_concurrent, rebind_stream!, spread_streams!, HIPLDLSolver, HIPSparseLDLSolver, hip_sparse_ldl_solver, HIPKKTSolver, hip_ldl_solver, HIPGroup, HIPSmallNewton, set_option!, set_cones!, set_qp!, set_evaluator!, set_parameters!, differentiate_adjoint!, solution, HIPComm, comm_unique_id, comm_size, gather_status, allreduce_sum!, newton_step!,
+export HIPSolver, streams_concurrent, rebind_stream!, spread_streams!, HIPLDLSolver, HIPSparseLDLSolver, hip_sparse_ldl_solver, HIPKKTSolver, hip_ldl_solver, HIPGroup, HIPSmallNewton, set_option!, set_cones!, set_qp!, set_evaluator!, set_parameters!, differentiate_adjoint!, solution, set_stream!, set_qp_device!, initialize_device!, set_state_device!, set_parameters_device!, solve_device!, solution_device!, differentiate_adjoint_device!, HIPComm, comm_unique_id, comm_size, gather_status, allreduce_sum!, newton_step!,
        search_direction_nonsymmetric!, analyze_structure!, clear_structure!, set_stage_parallel!, set_stage_blocks!, declared_structure, kernel_times, sync_scalars!, copy_back!
 
 end # module

@@ -6,14 +6,26 @@
     x, y, z = QPLayer.apply(sn, P, q, A, b, G, h, True)  # with the duals
 
 Every input is a float64 tensor, batched (leading axis = batch) or unbatched and shared by the batch.  The forward pass is one solve! launch of the batch kernel,
-the backward pass one reverse-mode differentiate! launch (SmallNewtonBatch.vjp): gradients of shared inputs are summed over the batch.  Tensors travel through
-host numpy arrays and come back on the inputs' device.  An instance whose solve did not converge (status != 1) gets NaN gradients, with a warning.  torch is
-imported on first use of QPLayer: the package itself loads without it."""
+the backward pass one reverse-mode differentiate! launch (SmallNewtonBatch.vjp): gradients of shared inputs are summed over the batch.  An instance whose solve
+did not converge (status != 1) gets NaN gradients.
+
+With CPU tensors the data travel through host numpy arrays, and non-converged instances are reported with a warning.  When EVERY input is a CUDA tensor on the
+handle's device the layer takes the device path and never leaves the GPU: the handle is put on torch's current stream (set_stream), the data are packed by a
+kernel with each array shared or per instance by its own shape (a shared P is stored once, never broadcast), the solution is gathered on the device
+(set_qp_device, initialize_device(None), solve_device, solution_device), and backward is vjp_device with the cotangent parts and the gradients of shared inputs
+summed on the device — no host copy and no synchronisation in forward or backward.  The host cannot know the statuses there without waiting, so there is no
+warning on that path: sn.status_device() gives the solve statuses as an int32 CUDA tensor (1 = converged) for the caller to look at when it suits.
+
+    w = ParametricLayer.apply(sn, theta)                 # the points (batch, N) of a handle with a device evaluator that provides dR/dtheta; CUDA tensors only
+
+ParametricLayer is the auto-tuning loop of examples/autotuning/cartpole.jl as a layer: forward = set_parameters_device + initialize_device + solve_device,
+backward = vjp_device with grad_theta (theta (batch, n_parameters), or (n_parameters,) shared: summed).  torch is imported on first use of a layer: the package
+itself loads without it."""
 import warnings
 
 import numpy as np
 
-__all__ = ["QPLayer"]
+__all__ = ["QPLayer", "ParametricLayer"]
 
 _cls = {}
 
@@ -42,6 +54,15 @@ def _build():
                     shared.append(False)
                 else:
                     raise ValueError("QPLayer: %s must be %s or %s" % (name, dm, (sn.batch,) + dm))
+            if all(t.is_cuda and t.device.index == sn.device for t in data):      # the device path: nothing leaves the GPU, nothing waits for it
+                tensors = [t.detach().contiguous() for t in data]
+                key = object()
+                _solve_device(torch, sn, tensors, objective_scale, key)
+                sol = sn.solution_device(parts="xyz" if return_duals else "x")
+                ctx.sn, ctx.key, ctx.tensors, ctx.c, ctx.shared, ctx.on_device = sn, key, tensors, objective_scale, shared, True
+                ctx.inputs, ctx.versions = data, [t._version for t in data]      # (ctx.tensors may alias the inputs' storage: the re-solve in backward checks them)
+                return (sol["x"], sol["y"], sol["z"]) if return_duals else sol["x"]
+            ctx.on_device = False
             arrays = [_np(t) for t in data]
             all_shared = all(shared)
             if not all_shared:      # (set_qp takes one problem for all or one per instance: the shared inputs are repeated)
@@ -64,6 +85,17 @@ def _build():
         @staticmethod
         def backward(ctx, gx, gy=None, gz=None):
             sn = ctx.sn
+            if ctx.on_device:
+                if getattr(sn, "_qp_layer_key", None) is not ctx.key:      # the handle solved another batch since: the same data solve again (deterministic)
+                    if any(t._version != v for t, v in zip(ctx.inputs, ctx.versions)):      # (the host path keeps copies; this one keeps the tensors themselves)
+                        raise RuntimeError("QPLayer: an input was modified in place after forward and the handle has solved another batch since: backward cannot solve the same data again")
+                    _solve_device(torch, sn, ctx.tensors, ctx.c, ctx.key)
+                else:
+                    sn.set_stream(torch.cuda.current_stream(ctx.tensors[0].device))
+                part = lambda g, n: g.contiguous() if (g is not None and n) else None
+                want = "".join(name for name, need in zip("PqAbGh", ctx.needs_input_grad[1:7]) if need)
+                out = sn.vjp_device(x=part(gx, sn.nx), y=part(gy, sn.ne), z=part(gz, sn.nc), qp=want, reduce="".join(name for name, s in zip("PqAbGh", ctx.shared) if s))
+                return (None, *[out.get(name) for name in "PqAbGh"], None, None)
             if getattr(sn, "_qp_layer_key", None) is not ctx.key:      # the handle solved another batch since: the same data solve again (deterministic)
                 _solve(sn, ctx.arrays, ctx.all_shared, ctx.c, ctx.key)
             nx, ne, nc = sn.nx, sn.ne, sn.nc
@@ -91,7 +123,51 @@ def _build():
                 grads.append(torch.from_numpy(g).to(ctx.device))
             return (None, *grads, None, None)
 
-    return QPLayer
+    class ParametricLayer(torch.autograd.Function):
+        """apply(sn, theta, x0=None): the points w (batch, N) of solve! with the handle's device evaluator at the parameters theta (CUDA, float64; (batch,
+        n_parameters) or (n_parameters,) shared by the batch); x0 (batch, nx): the guess of initialize!, zeros by default"""
+
+        @staticmethod
+        def forward(ctx, sn, theta, x0=None):
+            if not theta.is_cuda:
+                raise ValueError("ParametricLayer: theta must be a CUDA tensor (the layer has no host path)")
+            th = theta.detach().contiguous()
+            x0 = x0.detach().contiguous() if x0 is not None else None
+            key = object()
+            _solve_parameters(torch, sn, th, x0, key)
+            ctx.sn, ctx.key, ctx.theta, ctx.x0 = sn, key, th, x0
+            ctx.inputs, ctx.versions = (theta,), [theta._version]
+            return sn.solution_device(parts="w")["w"]
+
+        @staticmethod
+        def backward(ctx, gw):
+            sn = ctx.sn
+            if getattr(sn, "_qp_layer_key", None) is not ctx.key:
+                if any(t._version != v for t, v in zip(ctx.inputs, ctx.versions)):
+                    raise RuntimeError("ParametricLayer: theta was modified in place after forward and the handle has solved another batch since: backward cannot solve the same data again")
+                _solve_parameters(torch, sn, ctx.theta, ctx.x0, ctx.key)
+            else:
+                sn.set_stream(torch.cuda.current_stream(ctx.theta.device))
+            g = sn.vjp_device(cotangent=gw.contiguous(), theta=True, qp=False)["theta"]
+            return None, (g.sum(dim=0) if ctx.theta.dim() == 1 else g), None
+
+    return {"QPLayer": QPLayer, "ParametricLayer": ParametricLayer}
+
+
+def _solve_device(torch, sn, tensors, objective_scale, key):
+    sn.set_stream(torch.cuda.current_stream(tensors[0].device))
+    sn.set_qp_device(*tensors, objective_scale=objective_scale)
+    sn.initialize_device(None)
+    sn.solve_device()
+    sn._qp_layer_key, sn._qp_layer_status = key, None
+
+
+def _solve_parameters(torch, sn, theta, x0, key):
+    sn.set_stream(torch.cuda.current_stream(theta.device))
+    sn.set_parameters_device(theta)
+    sn.initialize_device(x0)
+    sn.solve_device()
+    sn._qp_layer_key, sn._qp_layer_status = key, None
 
 
 def _solve(sn, arrays, shared, objective_scale, key):
@@ -102,8 +178,8 @@ def _solve(sn, arrays, shared, objective_scale, key):
 
 
 def __getattr__(name):
-    if name == "QPLayer":
+    if name in __all__:
         if name not in _cls:
-            _cls[name] = _build()
+            _cls.update(_build())
         return _cls[name]
     raise AttributeError(name)

@@ -529,6 +529,55 @@ int32_t calipso_hip_smallnewton_differentiate_parameters(calipso_hip_smallnewton
  *   (or with no parameters), grad_qp under an evaluator, and an evaluator entry that does not report the reverse mode (QUERY's out[4] stays 0: built before it) */
 int32_t calipso_hip_smallnewton_differentiate_adjoint(calipso_hip_smallnewton*, int64_t k, const double* cotangent, double* adjoint, double* grad_theta, double* grad_qp,
                                                       int32_t* status, double* ms);
+/* DEVICE-RESIDENT, STREAM-ORDERED twins of the data entries above (csrc/smallnewton_io.hip; INTEGRATION.md "The batch kernel on device tensors").  Every pointer
+ * is DEVICE memory on the handle's device; the work is enqueued on the handle's stream; NO entry waits for the device, none reports `ms`, and nothing is read back:
+ * the results are valid in stream order.  Each entry checks, before it enqueues anything, that every non-NULL pointer is device memory of the handle's device
+ * (hipPointerGetAttributes): a host or foreign pointer is CALIPSO_ERR_ARGUMENT with a message naming the argument.  The host entries above keep working on the
+ * same handle, on whatever stream it has, and still wait for their own work.  The launches are those of solve / differentiate_adjoint: k_smallnewton and
+ * k_smallnewton_adj, unchanged; small kernels pack and unpack around them.  Buffers grow on demand and are kept: a call that repeats its shapes allocates nothing
+ * (hipFree waits for the whole device).  One HIP runtime per process: with PyTorch, `import torch` first.
+ *   set_stream(hip_stream, borrow)           borrow != 0: all later work of the handle goes to the caller's hipStream_t (torch.cuda.current_stream().cuda_stream;
+ *                                            NULL = the legacy default stream, which is torch's default stream); borrow == 0: back to the handle's own stream.  The
+ *                                            new stream first waits ON THE DEVICE for what the old one holds (an event recorded on the old stream).  A borrowed
+ *                                            stream is not owned and is never destroyed by the handle: the caller must take the handle off it — set_stream(NULL, 0)
+ *                                            or set_stream(another, 1) — BEFORE destroying it; the handle touches the old stream once more in that call (and
+ *                                            destroy waits for the stream it holds).  The evaluator's entry already launches on the stream it is handed.
+ *   set_qp_device(P, q, A, b, G, h, c, shared_mask, row_major)
+ *                                            bit i of shared_mask: array i of P, q, A, b, G, h is ONE array for all instances, else batch-major; row_major != 0:
+ *                                            matrices (rows, cols) row-major, as torch lays them out, else column-major as set_qp.  A pack kernel writes what
+ *                                            set_qp builds on the host — Lxx = (2c) P, Z = [A; -G] (ld m, column-major), bh = [-b; h] — with the same operations:
+ *                                            the same bits.  P and q are stored once when shared; Z once only when A and G are both shared or absent, bh likewise
+ *                                            for b and h — otherwise the shared half is repeated into per-instance storage.  Replaces an evaluator as set_qp does
+ *                                            (that one case frees the evaluator's buffers and waits).
+ *   initialize_device(x0)                    initialize!: x0 (batch x nx; NULL: zeros) into the first nx entries of every point, zeros behind
+ *   set_state_device(w, lambda, scalars)     the layouts of set_state; one kernel copies w and lambda and scatters the three scalars into their slots
+ *   set_parameters_device(theta, shared)     theta copied device to device into the handle's buffer (kept while the size repeats)
+ *   solve_device()                           the launch of solve: no events, no wait; the statuses stay on the device
+ *   get_solution_device(x, y, z, w, status)  one kernel gathers x (batch x nx), y (batch x ne), z (batch x nc) out of the points, optionally the points (batch x N)
+ *                                            and the int32 status of the handle's last SOLVE (host or device; kept apart from the status a differentiate leaves); NULLs skipped
+ *   differentiate_adjoint_device(k, cot_w, cot_x, cot_y, cot_z, adjoint, grad_theta, grad_qp, reduce_mask, row_major, status)
+ *                                            the launch of differentiate_adjoint.  The cotangent is cot_w, batch x (N x k), which the kernel reads where it lies — or,
+ *                                            with cot_w NULL, the parts cot_x / cot_y / cot_z (batch x (nx | ne | nc) x k, column-major per instance, each may be
+ *                                            NULL), scattered into the N-layout with zeros elsewhere.  adjoint (batch x (N x k)) and grad_theta (batch x
+ *                                            (n_parameters x k)) are written by the launch straight into the caller's buffers.  grad_qp: NULL or SIX pointers in the
+ *                                            order P, q, A, b, G, h (NULLs skipped).  Without bit i of reduce_mask array i's gradient comes per instance, batch x k x
+ *                                            size_i (a matrix row-major when row_major != 0, else column-major); with bit i it is SUMMED OVER THE BATCH on the
+ *                                            device, k x size_i.  The sum is deterministic and free of atomics: the batch is cut into chunks of 64 instances
+ *                                            (whatever the grid or the device), a chunk is added in instance order, the chunks in chunk order.  Every gradient
+ *                                            (grad_qp and grad_theta) of an instance whose last solve status is not 1 is NaN, before any sum.  status (batch, int32)
+ *                                            as differentiate_adjoint.  The refusals of differentiate_adjoint apply, with its messages.
+ *   For tests (exported, not declared, like calipso_hip_debug_smallnewton_describe): calipso_hip_debug_smallnewton_buffers(s, int64_t out[8]) = the device
+ *   addresses of Lxx, q, Z, bh and their element strides per instance (0: stored once) — a repeated set_qp_device must leave all eight as they were. */
+int32_t calipso_hip_smallnewton_set_stream(calipso_hip_smallnewton*, void* hip_stream, int32_t borrow);
+int32_t calipso_hip_smallnewton_set_qp_device(calipso_hip_smallnewton*, const double* P, const double* q, const double* A, const double* b, const double* G, const double* h,
+                                              double objective_scale, int32_t shared_mask, int32_t row_major);
+int32_t calipso_hip_smallnewton_initialize_device(calipso_hip_smallnewton*, const double* x0);
+int32_t calipso_hip_smallnewton_set_state_device(calipso_hip_smallnewton*, const double* w, const double* lambda, const double* scalars);
+int32_t calipso_hip_smallnewton_set_parameters_device(calipso_hip_smallnewton*, const double* theta, int32_t shared);
+int32_t calipso_hip_smallnewton_solve_device(calipso_hip_smallnewton*);
+int32_t calipso_hip_smallnewton_get_solution_device(calipso_hip_smallnewton*, double* x, double* y, double* z, double* w, int32_t* status);
+int32_t calipso_hip_smallnewton_differentiate_adjoint_device(calipso_hip_smallnewton*, int64_t k, const double* cot_w, const double* cot_x, const double* cot_y, const double* cot_z,
+                                                             double* adjoint, double* grad_theta, double* const* grad_qp, int32_t reduce_mask, int32_t row_major, int32_t* status);
 
 /* ---- multi-GPU exchange of the batched path: RCCL over xGMI, one process per GPU ---------------------------------
  * Problem instances are sharded block-contiguously over ranks and never interact (the reference's `Solver`s are independent); the

@@ -29,17 +29,10 @@
 
 namespace {
 using calipso::Options;
-typedef calipso_hip_smallnewton SN;
-
 using namespace calipso::sn;
-using calipso::snh::fail;
-using calipso::snh::dims_of;
-using calipso::snh::launch;
-using calipso::snh::grow;
+using namespace calipso::snh;
 
 thread_local std::string g_sn_err;
-
-#define SK(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return fail(s, CALIPSO_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); } while (0)
 
 }  // namespace
 
@@ -104,7 +97,7 @@ namespace calipso {
 namespace snh {
 using sn::QpEval;      // (calipso::QpEval is the general path's)
 
-int launch(SN* s, int mode, int count, int advance, bool eval_rtheta, const AdjArgs* adj, bool enqueue_only) {
+int launch(SN* s, int mode, int count, int advance, bool eval_rtheta, const AdjArgs* adj, bool timed) {
     if (!s->have_qp && !s->ev) return fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_smallnewton: no problem data (calipso_hip_smallnewton_set_qp or calipso_hip_smallnewton_set_evaluator)");
     if (s->ev && s->np > 0 && !s->have_theta) return fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_smallnewton: the evaluator takes " + std::to_string(s->np) + " parameters and none were set (calipso_hip_smallnewton_set_parameters)");
     SK(hipSetDevice(s->device));
@@ -124,34 +117,25 @@ int launch(SN* s, int mode, int count, int advance, bool eval_rtheta, const AdjA
         aa = *adj; aa.base = a;
         aa.base.rtheta = s->adj_rt; aa.base.srtheta = (long long)a.d.N * (long long)count;
     }
-    if (!enqueue_only) SK(hipEventRecord(s->ev0, s->stream));
-    const bool soc = !s->soc_dim.empty();
+    void* block = mode == MODE_ADJ ? (void*)&aa : (void*)&a;      // the kernel's one argument
+    if (timed) SK(hipEventRecord(s->ev0, s->stream));
     if (s->ev) {      // the evaluator's own builds of the kernels, launched by its entry on the handle's stream
         int64_t out[5] = {0, 0, 0, 0, 0};
         calipso_smallnewton_launch L = ev_request(s, CALIPSO_SMALLNEWTON_LAUNCH, out);
-        L.args = mode == MODE_ADJ ? (const void*)&aa : (const void*)&a; L.mode = mode; L.eval_rtheta = eval_rtheta ? 1 : 0;
+        L.args = block; L.mode = mode; L.eval_rtheta = eval_rtheta ? 1 : 0;
         const int rc = s->ev(&L);
         if (rc != CALIPSO_OK) return fail(s, rc, "calipso_hip_smallnewton: the evaluator's entry refused or failed the launch (" + std::to_string(rc) + ")");
-    } else if (mode == MODE_ADJ) {
-        const int nt = sn_threads(s);
-        void* args[] = {&aa};
-        SK(hipLaunchKernel(adj_kernel_of<QpEval>(nt, soc), dim3((unsigned)s->batch), dim3((unsigned)nt), args, s->lds_bytes, s->stream));
-    } else if (mode == MODE_DIFF) {
-        const int nt = sn_threads(s);
-        void* args[] = {&a};
-        SK(hipLaunchKernel(diff_kernel_of<QpEval>(nt, soc), dim3((unsigned)s->batch), dim3((unsigned)nt), args, s->lds_bytes, s->stream));
     } else {
         const int nt = sn_threads(s);
-        void* args[] = {&a};
-        SK(hipLaunchKernel(kernel_of<QpEval>(nt, soc, s->lu), dim3((unsigned)s->batch), dim3((unsigned)nt), args, s->lds_bytes, s->stream));
+        const bool soc = !s->soc_dim.empty();
+        const void* kernel = mode == MODE_ADJ ? adj_kernel_of<QpEval>(nt, soc) : mode == MODE_DIFF ? diff_kernel_of<QpEval>(nt, soc) : kernel_of<QpEval>(nt, soc, s->lu);
+        void* args[] = {block};
+        SK(hipLaunchKernel(kernel, dim3((unsigned)s->batch), dim3((unsigned)nt), args, s->lds_bytes, s->stream));
     }
     SK(hipGetLastError());
-    if (enqueue_only) {
-        if (mode == MODE_SOLVE) SK(hipMemcpyAsync(s->solve_status, s->status, sizeof(int) * (size_t)s->batch, hipMemcpyDeviceToDevice, s->stream));
-        return CALIPSO_OK;
-    }
-    SK(hipEventRecord(s->ev1, s->stream));
+    if (timed) SK(hipEventRecord(s->ev1, s->stream));
     if (mode == MODE_SOLVE) SK(hipMemcpyAsync(s->solve_status, s->status, sizeof(int) * (size_t)s->batch, hipMemcpyDeviceToDevice, s->stream));
+    if (!timed) return CALIPSO_OK;
     SK(hipStreamSynchronize(s->stream));
     float ms = 0.f;
     SK(hipEventElapsedTime(&ms, s->ev0, s->ev1));
@@ -206,7 +190,7 @@ int32_t calipso_hip_smallnewton_destroy(calipso_hip_smallnewton* s) {
     if (s->stream) (void)hipStreamSynchronize(s->stream);
     if (s->own_stream && s->own_stream != s->stream) (void)hipStreamSynchronize(s->own_stream);
     for (double* p : {s->P, s->q, s->Z, s->bh, s->theta, s->hess, s->dpt, s->w, s->lam, s->sc, s->filt, s->info, s->trace, s->prof, s->rtheta, s->sens, s->stf, s->Hs,
-                      s->adj_rt, s->adj_in, s->adj_out, s->adj_gth, s->adj_gqp, s->red}) if (p) (void)hipFree(p);
+                      s->adj_rt, s->adj_in, s->adj_out, s->adj_gth, s->adj_gqp, s->red, s->stage}) if (p) (void)hipFree(p);
     if (s->cnt) (void)hipFree(s->cnt);
     if (s->d_soc) (void)hipFree(s->d_soc);
     if (s->status) (void)hipFree(s->status);
@@ -305,39 +289,30 @@ int32_t calipso_hip_smallnewton_set_option(calipso_hip_smallnewton* s, const cha
 }
 
 // min c x'Px + q'x  s.t.  Ax = b, h - Gx >= 0  (qp.hip's conventions; column-major host arrays).  shared != 0: ONE problem for all instances (the arrays hold one
-// problem), else batch-major arrays (instance k at offset k * size).
+// problem), else batch-major arrays (instance k at offset k * size).  The arrays go to the device as they are, into a block that lives for this call; pack_qp
+// builds Lxx, Z and bh from them there.
 int32_t calipso_hip_smallnewton_set_qp(calipso_hip_smallnewton* s, const double* P, const double* q, const double* A, const double* b, const double* G, const double* h,
                                        double objective_scale, int32_t shared) {
     if (!s || !P || !q || (s->ne && (!A || !b)) || (s->nc && (!G || !h))) return CALIPSO_ERR_ARGUMENT;
     SK(hipSetDevice(s->device));
-    const size_t nx = s->nx, ne = s->ne, nc = s->nc, m = ne + nc, K = shared ? 1 : (size_t)s->batch;
-    for (double** p : {&s->P, &s->q, &s->Z, &s->bh}) if (*p) { (void)hipFree(*p); *p = nullptr; }
-    s->cap_P = s->cap_q = s->cap_Z = s->cap_bh = 0;
-    std::vector<double> Lxx(K * nx * nx), Z(K * std::max<size_t>(m, 1) * nx, 0.0), bh(K * std::max<size_t>(m, 1), 0.0);
-    for (size_t k = 0; k < K; ++k) {
-        for (size_t e = 0; e < nx * nx; ++e) Lxx[k * nx * nx + e] = 2.0 * objective_scale * P[k * nx * nx + e];
-        double* Zk = Z.data() + k * std::max<size_t>(m, 1) * nx;
-        for (size_t c = 0; c < nx; ++c) {
-            for (size_t r = 0; r < ne; ++r) Zk[r + c * m] = A[k * ne * nx + r + c * ne];
-            for (size_t r = 0; r < nc; ++r) Zk[ne + r + c * m] = -G[k * nc * nx + r + c * nc];
-        }
-        for (size_t r = 0; r < ne; ++r) bh[k * std::max<size_t>(m, 1) + r] = -b[k * ne + r];
-        for (size_t r = 0; r < nc; ++r) bh[k * std::max<size_t>(m, 1) + ne + r] = h[k * nc + r];
+    const size_t nx = s->nx, ne = s->ne, nc = s->nc, K = shared ? 1 : (size_t)s->batch;
+    const double* host[6] = {P, q, A, b, G, h};
+    const size_t len[6] = {K * nx * nx, K * nx, K * ne * nx, K * ne, K * nc * nx, K * nc};
+    struct Block { double* p = nullptr; ~Block() { if (p) (void)hipFree(p); } } block;
+    if (hipMalloc((void**)&block.p, sizeof(double) * K * qp_entries(dims_of(s))) != hipSuccess) {
+        (void)hipGetLastError(); block.p = nullptr;
+        return fail(s, CALIPSO_ERR_HIP, "calipso_hip_smallnewton_set_qp: device allocation of " + std::to_string(sizeof(double) * K * qp_entries(dims_of(s))) + " bytes failed");
     }
-    SK(hipMalloc((void**)&s->P, sizeof(double) * Lxx.size())); SK(hipMalloc((void**)&s->q, sizeof(double) * K * nx));
-    SK(hipMalloc((void**)&s->Z, sizeof(double) * Z.size())); SK(hipMalloc((void**)&s->bh, sizeof(double) * bh.size()));
-    SK(hipMemcpyAsync(s->P, Lxx.data(), sizeof(double) * Lxx.size(), hipMemcpyHostToDevice, s->stream));
-    SK(hipMemcpyAsync(s->q, q, sizeof(double) * K * nx, hipMemcpyHostToDevice, s->stream));
-    SK(hipMemcpyAsync(s->Z, Z.data(), sizeof(double) * Z.size(), hipMemcpyHostToDevice, s->stream));
-    SK(hipMemcpyAsync(s->bh, bh.data(), sizeof(double) * bh.size(), hipMemcpyHostToDevice, s->stream));
-    SK(hipStreamSynchronize(s->stream));
-    s->sP = shared ? 0 : (long long)(nx * nx); s->sq = shared ? 0 : (long long)nx; s->sZ = shared ? 0 : (long long)(std::max<size_t>(m, 1) * nx); s->sbh = shared ? 0 : (long long)std::max<size_t>(m, 1);
-    s->cap_P = Lxx.size(); s->cap_q = K * nx; s->cap_Z = Z.size(); s->cap_bh = bh.size();
-    s->have_qp = true; s->objective_scale = objective_scale;
-    s->ev = nullptr; s->np = 0; s->ev_rtheta = false; s->ev_adj = false; s->have_theta = false;      // (replaces an evaluator)
-    for (double** p : {&s->theta, &s->hess, &s->dpt}) if (*p) { (void)hipFree(*p); *p = nullptr; }
-    s->cap_theta = 0;
-    return CALIPSO_OK;
+    const double* src[6];
+    size_t at = 0;
+    for (int i = 0; i < 6; ++i) {
+        src[i] = len[i] ? block.p + at : nullptr;
+        if (len[i]) SK(hipMemcpyAsync(block.p + at, host[i], sizeof(double) * len[i], hipMemcpyHostToDevice, s->stream));
+        at += len[i];
+    }
+    const int rc = pack_qp(s, src, objective_scale, shared ? 63 : 0, 0, "calipso_hip_smallnewton_set_qp");
+    SK(hipStreamSynchronize(s->stream));      // (also after a refusal: the copies read the caller's arrays and the block goes)
+    return rc;
 }
 
 // a device evaluator (include/calipso_smallnewton.hpp): its entry's handshake, then the per-instance Lagrangian Hessians; replaces the QP
@@ -372,17 +347,10 @@ int32_t calipso_hip_smallnewton_set_evaluator(calipso_hip_smallnewton* s, calips
 // the parameters theta of the evaluator: batch x np (row k for instance k) or one row for all (shared != 0)
 int32_t calipso_hip_smallnewton_set_parameters(calipso_hip_smallnewton* s, const double* theta, int32_t shared) {
     if (!s || !theta) return CALIPSO_ERR_ARGUMENT;
-    if (!s->ev) return fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_smallnewton_set_parameters: no evaluator (calipso_hip_smallnewton_set_evaluator)");
-    if (s->np == 0) return CALIPSO_OK;
     SK(hipSetDevice(s->device));
+    const int rc = put_parameters(s, theta, shared, hipMemcpyHostToDevice, "calipso_hip_smallnewton_set_parameters");
     SK(hipStreamSynchronize(s->stream));
-    const size_t n = (size_t)s->np * (shared ? 1 : (size_t)s->batch);
-    if (s->theta) { (void)hipFree(s->theta); s->theta = nullptr; s->cap_theta = 0; }
-    SK(hipMalloc((void**)&s->theta, sizeof(double) * n));
-    s->cap_theta = n;
-    SK(hipMemcpy(s->theta, theta, sizeof(double) * n, hipMemcpyHostToDevice));
-    s->theta_shared = shared != 0; s->have_theta = true;
-    return CALIPSO_OK;
+    return rc;
 }
 
 // the points (batch x N, the layout of point.jl:13-22), the multiplier estimates lambda (batch x ne) and per instance [central_path, fraction_to_boundary, penalty]
@@ -392,17 +360,19 @@ int32_t calipso_hip_smallnewton_set_state(calipso_hip_smallnewton* s, const doub
     SK(hipSetDevice(s->device));
     const Dm d = dims_of(s);
     const size_t B = s->batch;
-    if (w) SK(hipMemcpyAsync(s->w, w, sizeof(double) * B * d.N, hipMemcpyHostToDevice, s->stream));
-    if (lambda && d.ne) SK(hipMemcpyAsync(s->lam, lambda, sizeof(double) * B * d.ne, hipMemcpyHostToDevice, s->stream));
-    if (scalars) {
-        std::vector<double> sc(B * SC_COUNT);
-        SK(hipMemcpyAsync(sc.data(), s->sc, sizeof(double) * sc.size(), hipMemcpyDeviceToHost, s->stream));
-        SK(hipStreamSynchronize(s->stream));
-        for (size_t k = 0; k < B; ++k) { sc[k * SC_COUNT + SC_KAPPA] = scalars[3 * k]; sc[k * SC_COUNT + SC_TAU] = scalars[3 * k + 1]; sc[k * SC_COUNT + SC_RHO] = scalars[3 * k + 2]; }
-        SK(hipMemcpyAsync(s->sc, sc.data(), sizeof(double) * sc.size(), hipMemcpyHostToDevice, s->stream));
+    const double* host[3] = {w, d.ne ? lambda : nullptr, scalars};
+    const size_t len[3] = {B * d.N, B * d.ne, B * 3};
+    { const int rc = grow(s, &s->stage, &s->cap_stage, len[0] + len[1] + len[2], "calipso_hip_smallnewton_set_state"); if (rc < 0) return rc; }
+    const double* dev[3];
+    size_t at = 0;
+    for (int i = 0; i < 3; ++i) {
+        dev[i] = host[i] ? s->stage + at : nullptr;
+        if (host[i]) SK(hipMemcpyAsync(s->stage + at, host[i], sizeof(double) * len[i], hipMemcpyHostToDevice, s->stream));
+        at += len[i];
     }
+    const int rc = put_state(s, dev[0], nullptr, w ? 1 : 0, dev[1], dev[2]);
     SK(hipStreamSynchronize(s->stream));
-    return CALIPSO_OK;
+    return rc;
 }
 
 // points, lambda, scalars [central_path, fraction_to_boundary, penalty, primal_regularization, primal_regularization_last, dual_regularization] (batch x 6),
@@ -448,7 +418,7 @@ int32_t calipso_hip_smallnewton_trace(calipso_hip_smallnewton* s, int32_t rows, 
 // (lu_fallback = 0), -100 - CALIPSO_WARN_ZERO_PIVOT where that fallback met an exactly singular H (lu_fallback = 1).
 int32_t calipso_hip_smallnewton_solve(calipso_hip_smallnewton* s, int32_t* result, double* ms) {
     if (!s) return CALIPSO_ERR_ARGUMENT;
-    const int rc = launch(s, MODE_SOLVE, 0, 1, false, nullptr, false);
+    const int rc = launch(s, MODE_SOLVE, 0, 1, false, nullptr, true);
     if (rc < 0) return rc;
     if (result) SK(hipMemcpy(result, s->status, sizeof(int) * (size_t)s->batch, hipMemcpyDeviceToHost));
     if (ms) *ms = s->last_ms;
@@ -460,7 +430,7 @@ int32_t calipso_hip_smallnewton_solve(calipso_hip_smallnewton* s, int32_t* resul
 // candidate, exit kind (2: inner-loop exit of solve.jl:165, no step), optimality error] of the LAST step; status as calipso_hip_smallnewton_solve (0: stepped).
 int32_t calipso_hip_smallnewton_steps(calipso_hip_smallnewton* s, int32_t count, int32_t advance, double* info, int32_t* status, double* ms) {
     if (!s || count < 0) return CALIPSO_ERR_ARGUMENT;
-    const int rc = launch(s, MODE_STEPS, count, advance, false, nullptr, false);
+    const int rc = launch(s, MODE_STEPS, count, advance, false, nullptr, true);
     if (rc < 0) return rc;
     if (info) SK(hipMemcpy(info, s->info, sizeof(double) * (size_t)s->batch * IN_COUNT, hipMemcpyDeviceToHost));
     if (status) SK(hipMemcpy(status, s->status, sizeof(int) * (size_t)s->batch, hipMemcpyDeviceToHost));
@@ -473,17 +443,10 @@ int32_t calipso_hip_smallnewton_steps(calipso_hip_smallnewton* s, int32_t count,
 // jacobian_parameters: batch x (N x p), column-major per instance (host), or ONE N x p matrix for all instances (shared != 0: the model of an MPC loop is the same
 // for every problem); sensitivity: batch x (N x p).  status[k]: 0, or 1 when the factorisation's inertia is not (nx, ne + nc, 0).
 namespace {
-// the dR/dtheta buffer and the sensitivities (batch x N x p each), grown on demand
+// the dR/dtheta buffer and the sensitivities (batch x N x p each)
 int diff_buffers(SN* s, size_t need) {
-    if (need > s->cap_diff) {
-        if (s->rtheta) (void)hipFree(s->rtheta);
-        if (s->sens) (void)hipFree(s->sens);
-        s->rtheta = s->sens = nullptr; s->cap_diff = 0;
-        SK(hipMalloc((void**)&s->rtheta, sizeof(double) * need));
-        SK(hipMalloc((void**)&s->sens, sizeof(double) * need));
-        s->cap_diff = need;
-    }
-    return CALIPSO_OK;
+    const int rc = grow(s, &s->rtheta, &s->cap_rtheta, need, "calipso_hip_smallnewton_differentiate");
+    return rc < 0 ? rc : grow(s, &s->sens, &s->cap_sens, need, "calipso_hip_smallnewton_differentiate");
 }
 }  // namespace
 
@@ -495,7 +458,7 @@ int32_t calipso_hip_smallnewton_differentiate(calipso_hip_smallnewton* s, int64_
     { const int rc = diff_buffers(s, need); if (rc < 0) return rc; }
     SK(hipMemcpyAsync(s->rtheta, jacobian_parameters, sizeof(double) * (shared ? (size_t)d.N * (size_t)p : need), hipMemcpyHostToDevice, s->stream));
     s->diff_shared = shared != 0;
-    const int rc = launch(s, MODE_DIFF, (int)p, 0, false, nullptr, false);
+    const int rc = launch(s, MODE_DIFF, (int)p, 0, false, nullptr, true);
     if (rc < 0) return rc;
     SK(hipMemcpy(sensitivity, s->sens, sizeof(double) * need, hipMemcpyDeviceToHost));
     if (status) SK(hipMemcpy(status, s->status, sizeof(int) * (size_t)s->batch, hipMemcpyDeviceToHost));
@@ -513,7 +476,7 @@ int32_t calipso_hip_smallnewton_differentiate_parameters(calipso_hip_smallnewton
     const size_t need = (size_t)s->batch * (size_t)d.N * (size_t)s->np;
     { const int rc = diff_buffers(s, need); if (rc < 0) return rc; }
     s->diff_shared = false;
-    const int rc = launch(s, MODE_DIFF, s->np, 0, true, nullptr, false);
+    const int rc = launch(s, MODE_DIFF, s->np, 0, true, nullptr, true);
     if (rc < 0) return rc;
     SK(hipMemcpy(sensitivity, s->sens, sizeof(double) * need, hipMemcpyDeviceToHost));
     if (status) SK(hipMemcpy(status, s->status, sizeof(int) * (size_t)s->batch, hipMemcpyDeviceToHost));
@@ -528,35 +491,22 @@ int32_t calipso_hip_smallnewton_differentiate_parameters(calipso_hip_smallnewton
 int32_t calipso_hip_smallnewton_differentiate_adjoint(calipso_hip_smallnewton* s, int64_t k, const double* cotangent, double* adjoint, double* grad_theta, double* grad_qp,
                                                       int32_t* status, double* ms) {
     if (!s) return CALIPSO_ERR_ARGUMENT;
-    const char* me = "calipso_hip_smallnewton_differentiate_adjoint: ";
-    if (k < 1 || k > (1 << 20)) return fail(s, CALIPSO_ERR_ARGUMENT, std::string(me) + "k >= 1 cotangent columns");
-    if (!cotangent) return fail(s, CALIPSO_ERR_ARGUMENT, std::string(me) + "no cotangent");
-    if (!s->have_qp && !s->ev) return fail(s, CALIPSO_ERR_ARGUMENT, std::string(me) + "no problem data (calipso_hip_smallnewton_set_qp or calipso_hip_smallnewton_set_evaluator)");
-    if (s->ev && !s->ev_adj)
-        return fail(s, CALIPSO_ERR_ARGUMENT, std::string(me) + "the evaluator's entry was built without the reverse mode: rebuild it against the current include/calipso_smallnewton.hpp");
-    if (grad_theta && (!s->ev || !s->ev_rtheta || s->np < 1))
-        return fail(s, CALIPSO_ERR_ARGUMENT, std::string(me) + "grad_theta needs an evaluator that provides dR/dtheta and has parameters");
-    if (grad_qp && s->ev) return fail(s, CALIPSO_ERR_ARGUMENT, std::string(me) + "grad_qp is for the built-in QP (set_qp), not an evaluator");
+    const char* me = "calipso_hip_smallnewton_differentiate_adjoint";
+    int rc = adjoint_refusals(s, k, cotangent != nullptr, grad_theta != nullptr, grad_qp != nullptr);
+    if (rc < 0) return rc;
     SK(hipSetDevice(s->device));
     const Dm d = dims_of(s);
     const size_t B = (size_t)s->batch, N = (size_t)d.N, K = (size_t)k;
-    const size_t nqp = (size_t)d.nx * d.nx + d.nx + (size_t)d.ne * d.nx + d.ne + (size_t)d.nc * d.nx + d.nc;
-    int rc = grow(s, &s->adj_in, &s->cap_adj_in, B * N * K, "calipso_hip_smallnewton_differentiate_adjoint");
-    if (rc == CALIPSO_OK && adjoint) rc = grow(s, &s->adj_out, &s->cap_adj_out, B * N * K, "calipso_hip_smallnewton_differentiate_adjoint");
-    if (rc == CALIPSO_OK && grad_theta) rc = grow(s, &s->adj_rt, &s->cap_adj_rt, B * N * (size_t)s->np, "calipso_hip_smallnewton_differentiate_adjoint");
-    if (rc == CALIPSO_OK && grad_theta) rc = grow(s, &s->adj_gth, &s->cap_adj_gth, B * K * (size_t)s->np, "calipso_hip_smallnewton_differentiate_adjoint");
-    if (rc == CALIPSO_OK && grad_qp) rc = grow(s, &s->adj_gqp, &s->cap_adj_gqp, B * K * nqp, "calipso_hip_smallnewton_differentiate_adjoint");
+    rc = grow(s, &s->adj_in, &s->cap_adj_in, B * N * K, me);
+    if (rc == CALIPSO_OK && adjoint) rc = grow(s, &s->adj_out, &s->cap_adj_out, B * N * K, me);
+    if (rc == CALIPSO_OK && grad_theta) rc = grow(s, &s->adj_gth, &s->cap_adj_gth, B * K * (size_t)s->np, me);
     if (rc < 0) return rc;
     SK(hipMemcpyAsync(s->adj_in, cotangent, sizeof(double) * B * N * K, hipMemcpyHostToDevice, s->stream));
-    AdjArgs aa;
-    std::memset(&aa, 0, sizeof(aa));
-    aa.cot = s->adj_in; aa.adjoint = adjoint ? s->adj_out : nullptr; aa.grad_theta = grad_theta ? s->adj_gth : nullptr; aa.grad_qp = grad_qp ? s->adj_gqp : nullptr;
-    aa.objective_scale = s->objective_scale; aa.k = (int)k;
-    rc = launch(s, MODE_ADJ, grad_theta ? s->np : 0, 0, grad_theta != nullptr, &aa, false);
+    rc = calipso::snh::adjoint(s, k, s->adj_in, adjoint ? s->adj_out : nullptr, grad_theta ? s->adj_gth : nullptr, grad_qp != nullptr, true);
     if (rc < 0) return rc;
     if (adjoint) SK(hipMemcpy(adjoint, s->adj_out, sizeof(double) * B * N * K, hipMemcpyDeviceToHost));
     if (grad_theta) SK(hipMemcpy(grad_theta, s->adj_gth, sizeof(double) * B * K * (size_t)s->np, hipMemcpyDeviceToHost));
-    if (grad_qp) SK(hipMemcpy(grad_qp, s->adj_gqp, sizeof(double) * B * K * nqp, hipMemcpyDeviceToHost));
+    if (grad_qp) SK(hipMemcpy(grad_qp, s->adj_gqp, sizeof(double) * B * K * qp_entries(d), hipMemcpyDeviceToHost));
     if (status) SK(hipMemcpy(status, s->status, sizeof(int) * B, hipMemcpyDeviceToHost));
     if (ms) *ms = s->last_ms;
     return CALIPSO_OK;

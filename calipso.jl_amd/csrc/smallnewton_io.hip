@@ -1,9 +1,9 @@
-// smallnewton_io.hip — the device-resident, stream-ordered twins of the batch kernel's data entries (smallnewton.hip): every pointer is device memory on the handle's
-// device, everything is enqueued on the handle's stream (its own, or the caller's after calipso_hip_smallnewton_set_stream) and NO entry waits for the device.
-//
-// The kernels here only move data around the launches of k_smallnewton / k_smallnewton_adj, which are unchanged:
-//   k_sn_pack          what set_qp builds on the host — Lxx = (2c) P, Z = [A; -G] (ld m, column-major), bh = [-b; h] — with the same operations (one multiply, two
-//                      negations), so the packed bits are those of the host path; per array shared or per instance, row- or column-major sources
+// smallnewton_io.hip — the ONE data path around the launches of the batch kernel (k_smallnewton / k_smallnewton_adj), and its device-resident, stream-ordered
+// entries.  The cores (calipso::snh: pack_qp, put_state, put_parameters, adjoint) take device pointers, enqueue on the handle's stream (its own, or the caller's
+// after calipso_hip_smallnewton_set_stream) and do not wait.  A *_device entry checks that its pointers are device memory of the handle's device and calls the
+// core: NO device entry waits.  A host entry (smallnewton.hip) copies its arrays to the device, calls the same core, waits and reads back.  The kernels here:
+//   k_sn_pack          the kernel's form of the QP — Lxx = (2c) P, Z = [A; -G] (ld m, column-major), bh = [-b; h]: one multiply (by 2c, rounded once on the host),
+//                      two negations; per array shared or per instance, row- or column-major sources
 //   k_sn_state         set_state / initialize!: the points, lambda, and the three scalars scattered into their SC_* slots
 //   k_sn_gather        x, y, z out of the point.jl layout, the whole w, the status of the last solve
 //   k_sn_cot           cotangent parts (x, y, z) into the N-layout the adjoint kernel reads, zeros elsewhere
@@ -24,13 +24,7 @@
 
 namespace {
 using namespace calipso::sn;
-using calipso::snh::SN;
-using calipso::snh::fail;
-using calipso::snh::dims_of;
-using calipso::snh::launch;
-using calipso::snh::grow;
-
-#define SK(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return fail(s, CALIPSO_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); } while (0)
+using namespace calipso::snh;
 
 constexpr int IO_NT = 256;
 constexpr int SN_RED_CHUNK = 64;      // instances per partial sum of the batch reduction: fixed, so the summation order is a function of the batch size alone
@@ -207,6 +201,93 @@ int device_pointer(SN* s, const void* p, const char* entry, const char* arg) {
 
 }  // namespace
 
+namespace calipso {
+namespace snh {
+
+int pack_qp(SN* s, const double* const src[6], double objective_scale, int shared_mask, int row_major, const char* who) {
+    const size_t nx = s->nx, ne = s->ne, nc = s->nc, m = ne + nc, m1 = std::max<size_t>(m, 1), B = (size_t)s->batch;
+    const auto sh = [&](int i) { return ((shared_mask >> i) & 1) != 0; };
+    const bool zP = sh(0), zq = sh(1), zZ = (ne == 0 || sh(2)) && (nc == 0 || sh(4)), zbh = (ne == 0 || sh(3)) && (nc == 0 || sh(5));
+    if (s->ev) {      // (replaces an evaluator: its buffers go — the one case that waits for the device)
+        SK(hipStreamSynchronize(s->stream));
+        for (double** p : {&s->theta, &s->hess, &s->dpt}) if (*p) { (void)hipFree(*p); *p = nullptr; }
+        s->cap_theta = 0;
+        s->ev = nullptr; s->np = 0; s->ev_rtheta = false; s->ev_adj = false; s->have_theta = false;
+    }
+    s->have_qp = false;
+    int rc = grow(s, &s->P, &s->cap_P, (zP ? 1 : B) * nx * nx, who);
+    if (rc == CALIPSO_OK) rc = grow(s, &s->q, &s->cap_q, (zq ? 1 : B) * nx, who);
+    if (rc == CALIPSO_OK) rc = grow(s, &s->Z, &s->cap_Z, (zZ ? 1 : B) * m1 * nx, who);
+    if (rc == CALIPSO_OK) rc = grow(s, &s->bh, &s->cap_bh, (zbh ? 1 : B) * m1, who);
+    if (rc < 0) return rc;
+    PackArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.P = src[0]; a.q = src[1]; a.A = src[2]; a.b = src[3]; a.G = src[4]; a.h = src[5];
+    a.iP = sh(0) ? 0 : (long long)(nx * nx); a.iq = sh(1) ? 0 : (long long)nx; a.iA = sh(2) ? 0 : (long long)(ne * nx); a.ib = sh(3) ? 0 : (long long)ne;
+    a.iG = sh(4) ? 0 : (long long)(nc * nx); a.ih = sh(5) ? 0 : (long long)nc;
+    a.oP = s->P; a.oq = s->q; a.oZ = s->Z; a.obh = s->bh;
+    a.sP = zP ? 0 : (long long)(nx * nx); a.sq = zq ? 0 : (long long)nx; a.sZ = zZ ? 0 : (long long)(m1 * nx); a.sbh = zbh ? 0 : (long long)m1;
+    a.nx = s->nx; a.ne = s->ne; a.nc = s->nc; a.row_major = row_major != 0; a.two_c = 2.0 * objective_scale;
+    const bool any = a.sP || a.sq || (m > 0 && (a.sZ || a.sbh));
+    hipLaunchKernelGGL(k_sn_pack, dim3(any ? (unsigned)B : 1u), dim3(IO_NT), 0, s->stream, a);
+    SK(hipGetLastError());
+    s->sP = a.sP; s->sq = a.sq; s->sZ = a.sZ; s->sbh = a.sbh;
+    s->have_qp = true; s->objective_scale = objective_scale;
+    return CALIPSO_OK;
+}
+
+int put_state(SN* s, const double* w, const double* x0, int w_mode, const double* lambda, const double* scalars) {
+    const Dm d = dims_of(s);
+    StateArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.w_src = w; a.x0 = x0; a.lam_src = d.ne ? lambda : nullptr; a.sc_src = scalars; a.w = s->w; a.lam = s->lam; a.sc = s->sc;
+    a.N = d.N; a.nx = d.nx; a.ne = d.ne; a.batch = s->batch; a.w_mode = w_mode;
+    if (!w_mode && !a.lam_src && !a.sc_src) return CALIPSO_OK;
+    hipLaunchKernelGGL(k_sn_state, dim3(blocks_for((size_t)s->batch * d.N)), dim3(IO_NT), 0, s->stream, a);
+    SK(hipGetLastError());
+    return CALIPSO_OK;
+}
+
+int put_parameters(SN* s, const double* theta, int shared, hipMemcpyKind kind, const char* who) {
+    if (!s->ev) return fail(s, CALIPSO_ERR_ARGUMENT, std::string(who) + ": no evaluator (calipso_hip_smallnewton_set_evaluator)");
+    if (s->np == 0) return CALIPSO_OK;
+    const size_t n = (size_t)s->np * (shared ? 1 : (size_t)s->batch);
+    { const int rc = grow(s, &s->theta, &s->cap_theta, n, who); if (rc < 0) return rc; }
+    SK(hipMemcpyAsync(s->theta, theta, sizeof(double) * n, kind, s->stream));
+    s->theta_shared = shared != 0; s->have_theta = true;
+    return CALIPSO_OK;
+}
+
+// (the messages name the host entry, whichever entry asked)
+int adjoint_refusals(SN* s, int64_t k, bool have_cotangent, bool grad_theta, bool grad_qp) {
+    const std::string me = "calipso_hip_smallnewton_differentiate_adjoint: ";
+    if (k < 1 || k > (1 << 20)) return fail(s, CALIPSO_ERR_ARGUMENT, me + "k >= 1 cotangent columns");
+    if (!have_cotangent) return fail(s, CALIPSO_ERR_ARGUMENT, me + "no cotangent");
+    if (!s->have_qp && !s->ev) return fail(s, CALIPSO_ERR_ARGUMENT, me + "no problem data (calipso_hip_smallnewton_set_qp or calipso_hip_smallnewton_set_evaluator)");
+    if (s->ev && !s->ev_adj) return fail(s, CALIPSO_ERR_ARGUMENT, me + "the evaluator's entry was built without the reverse mode: rebuild it against the current include/calipso_smallnewton.hpp");
+    if (grad_theta && (!s->ev || !s->ev_rtheta || s->np < 1)) return fail(s, CALIPSO_ERR_ARGUMENT, me + "grad_theta needs an evaluator that provides dR/dtheta and has parameters");
+    if (grad_qp && s->ev) return fail(s, CALIPSO_ERR_ARGUMENT, me + "grad_qp is for the built-in QP (set_qp), not an evaluator");
+    return CALIPSO_OK;
+}
+
+int adjoint(SN* s, int64_t k, const double* cot, double* adjoint, double* grad_theta, bool want_grad_qp, bool timed) {
+    const char* me = "calipso_hip_smallnewton_differentiate_adjoint";
+    const Dm d = dims_of(s);
+    const size_t B = (size_t)s->batch;
+    int rc = CALIPSO_OK;
+    if (grad_theta) rc = grow(s, &s->adj_rt, &s->cap_adj_rt, B * (size_t)d.N * (size_t)s->np, me);
+    if (rc == CALIPSO_OK && want_grad_qp) rc = grow(s, &s->adj_gqp, &s->cap_adj_gqp, B * (size_t)k * qp_entries(d), me);
+    if (rc < 0) return rc;
+    AdjArgs aa;
+    std::memset(&aa, 0, sizeof(aa));
+    aa.cot = cot; aa.adjoint = adjoint; aa.grad_theta = grad_theta; aa.grad_qp = want_grad_qp ? s->adj_gqp : nullptr;
+    aa.objective_scale = s->objective_scale; aa.k = (int)k;
+    return launch(s, MODE_ADJ, grad_theta ? s->np : 0, 0, grad_theta != nullptr, &aa, timed);
+}
+
+}  // namespace snh
+}  // namespace calipso
+
 extern "C" {
 
 // All later work of the handle goes to the caller's stream (borrow != 0; hip_stream may be NULL: the legacy default stream, which is torch's default stream) or back
@@ -234,84 +315,39 @@ int32_t calipso_hip_smallnewton_set_qp_device(calipso_hip_smallnewton* s, const 
     if (shared_mask < 0 || shared_mask > 63) return fail(s, CALIPSO_ERR_ARGUMENT, std::string(me) + ": shared_mask has one bit per array of P, q, A, b, G, h (0 .. 63)");
     SK(hipSetDevice(s->device));
     DEVPTR(me, P); DEVPTR(me, q); DEVPTR(me, A); DEVPTR(me, b); DEVPTR(me, G); DEVPTR(me, h);
-    const size_t nx = s->nx, ne = s->ne, nc = s->nc, m = ne + nc, m1 = std::max<size_t>(m, 1), B = (size_t)s->batch;
-    const auto sh = [&](int i) { return ((shared_mask >> i) & 1) != 0; };
-    const bool zP = sh(0), zq = sh(1), zZ = (ne == 0 || sh(2)) && (nc == 0 || sh(4)), zbh = (ne == 0 || sh(3)) && (nc == 0 || sh(5));
-    if (s->ev) {      // (replaces an evaluator, as set_qp does: its buffers go — the one case that waits for the device)
-        SK(hipStreamSynchronize(s->stream));
-        for (double** p : {&s->theta, &s->hess, &s->dpt}) if (*p) { (void)hipFree(*p); *p = nullptr; }
-        s->cap_theta = 0;
-        s->ev = nullptr; s->np = 0; s->ev_rtheta = false; s->ev_adj = false; s->have_theta = false;
-    }
-    s->have_qp = false;
-    int rc = grow(s, &s->P, &s->cap_P, (zP ? 1 : B) * nx * nx, me);
-    if (rc == CALIPSO_OK) rc = grow(s, &s->q, &s->cap_q, (zq ? 1 : B) * nx, me);
-    if (rc == CALIPSO_OK) rc = grow(s, &s->Z, &s->cap_Z, (zZ ? 1 : B) * m1 * nx, me);
-    if (rc == CALIPSO_OK) rc = grow(s, &s->bh, &s->cap_bh, (zbh ? 1 : B) * m1, me);
-    if (rc < 0) return rc;
-    PackArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.P = P; a.q = q; a.A = A; a.b = b; a.G = G; a.h = h;
-    a.iP = sh(0) ? 0 : (long long)(nx * nx); a.iq = sh(1) ? 0 : (long long)nx; a.iA = sh(2) ? 0 : (long long)(ne * nx); a.ib = sh(3) ? 0 : (long long)ne;
-    a.iG = sh(4) ? 0 : (long long)(nc * nx); a.ih = sh(5) ? 0 : (long long)nc;
-    a.oP = s->P; a.oq = s->q; a.oZ = s->Z; a.obh = s->bh;
-    a.sP = zP ? 0 : (long long)(nx * nx); a.sq = zq ? 0 : (long long)nx; a.sZ = zZ ? 0 : (long long)(m1 * nx); a.sbh = zbh ? 0 : (long long)m1;
-    a.nx = s->nx; a.ne = s->ne; a.nc = s->nc; a.row_major = row_major != 0; a.two_c = 2.0 * objective_scale;
-    const bool any = a.sP || a.sq || (m > 0 && (a.sZ || a.sbh));
-    hipLaunchKernelGGL(k_sn_pack, dim3(any ? (unsigned)B : 1u), dim3(IO_NT), 0, s->stream, a);
-    SK(hipGetLastError());
-    s->sP = a.sP; s->sq = a.sq; s->sZ = a.sZ; s->sbh = a.sbh;
-    s->have_qp = true; s->objective_scale = objective_scale;
-    return CALIPSO_OK;
+    const double* src[6] = {P, q, A, b, G, h};
+    return pack_qp(s, src, objective_scale, shared_mask, row_major, me);
 }
-
-namespace {
-int state_device(SN* s, const char* me, const double* w, const double* x0, int w_mode, const double* lambda, const double* scalars) {
-    SK(hipSetDevice(s->device));
-    DEVPTR(me, w); DEVPTR(me, x0); DEVPTR(me, lambda); DEVPTR(me, scalars);
-    const Dm d = dims_of(s);
-    StateArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.w_src = w; a.x0 = x0; a.lam_src = d.ne ? lambda : nullptr; a.sc_src = scalars; a.w = s->w; a.lam = s->lam; a.sc = s->sc;
-    a.N = d.N; a.nx = d.nx; a.ne = d.ne; a.batch = s->batch; a.w_mode = w_mode;
-    if (!w_mode && !a.lam_src && !a.sc_src) return CALIPSO_OK;
-    hipLaunchKernelGGL(k_sn_state, dim3(blocks_for((size_t)s->batch * d.N)), dim3(IO_NT), 0, s->stream, a);
-    SK(hipGetLastError());
-    return CALIPSO_OK;
-}
-}  // namespace
 
 // initialize!(solver, guess) for every instance: x0 (batch x nx) in the first nx entries of the points, zeros behind; x0 = NULL: zeros (what set_state does with such points)
 int32_t calipso_hip_smallnewton_initialize_device(calipso_hip_smallnewton* s, const double* x0) {
     if (!s) return CALIPSO_ERR_ARGUMENT;
-    return state_device(s, "calipso_hip_smallnewton_initialize_device", nullptr, x0, 2, nullptr, nullptr);
+    SK(hipSetDevice(s->device));
+    DEVPTR("calipso_hip_smallnewton_initialize_device", x0);
+    return put_state(s, nullptr, x0, 2, nullptr, nullptr);
 }
 
 // set_state with the arrays on the device, the same layouts: w batch x N, lambda batch x ne, scalars batch x 3; NULL leaves what is resident
 int32_t calipso_hip_smallnewton_set_state_device(calipso_hip_smallnewton* s, const double* w, const double* lambda, const double* scalars) {
     if (!s) return CALIPSO_ERR_ARGUMENT;
-    return state_device(s, "calipso_hip_smallnewton_set_state_device", w, nullptr, w ? 1 : 0, lambda, scalars);
+    const char* me = "calipso_hip_smallnewton_set_state_device";
+    SK(hipSetDevice(s->device));
+    DEVPTR(me, w); DEVPTR(me, lambda); DEVPTR(me, scalars);
+    return put_state(s, w, nullptr, w ? 1 : 0, lambda, scalars);
 }
 
 // set_parameters with theta on the device: copied (device to device, on the stream) into the handle's buffer, which is kept while the size repeats
 int32_t calipso_hip_smallnewton_set_parameters_device(calipso_hip_smallnewton* s, const double* theta, int32_t shared) {
     if (!s || !theta) return CALIPSO_ERR_ARGUMENT;
-    const char* me = "calipso_hip_smallnewton_set_parameters_device";
-    if (!s->ev) return fail(s, CALIPSO_ERR_ARGUMENT, std::string(me) + ": no evaluator (calipso_hip_smallnewton_set_evaluator)");
-    if (s->np == 0) return CALIPSO_OK;
     SK(hipSetDevice(s->device));
-    DEVPTR(me, theta);
-    const size_t n = (size_t)s->np * (shared ? 1 : (size_t)s->batch);
-    { const int rc = grow(s, &s->theta, &s->cap_theta, n, me); if (rc < 0) return rc; }
-    SK(hipMemcpyAsync(s->theta, theta, sizeof(double) * n, hipMemcpyDeviceToDevice, s->stream));
-    s->theta_shared = shared != 0; s->have_theta = true;
-    return CALIPSO_OK;
+    if (s->ev && s->np > 0) DEVPTR("calipso_hip_smallnewton_set_parameters_device", theta);
+    return put_parameters(s, theta, shared, hipMemcpyDeviceToDevice, "calipso_hip_smallnewton_set_parameters_device");
 }
 
 // the launch of calipso_hip_smallnewton_solve, enqueued: no events, no wait, no status read back (get_solution_device hands it out on the device)
 int32_t calipso_hip_smallnewton_solve_device(calipso_hip_smallnewton* s) {
     if (!s) return CALIPSO_ERR_ARGUMENT;
-    return launch(s, MODE_SOLVE, 0, 1, false, nullptr, true);
+    return launch(s, MODE_SOLVE, 0, 1, false, nullptr, false);
 }
 
 // x (batch x nx), y (batch x ne), z (batch x nc) out of the resident points, the points themselves (batch x N), the status of the last solve (batch, int32): NULLs skipped
@@ -339,22 +375,14 @@ int32_t calipso_hip_smallnewton_get_solution_device(calipso_hip_smallnewton* s, 
 int32_t calipso_hip_smallnewton_differentiate_adjoint_device(calipso_hip_smallnewton* s, int64_t k, const double* cot_w, const double* cot_x, const double* cot_y, const double* cot_z,
                                                              double* adjoint, double* grad_theta, double* const* grad_qp, int32_t reduce_mask, int32_t row_major, int32_t* status) {
     if (!s) return CALIPSO_ERR_ARGUMENT;
-    const char* me = "calipso_hip_smallnewton_differentiate_adjoint: ";      // (the host entry's refusals, with its messages)
     const char* dev = "calipso_hip_smallnewton_differentiate_adjoint_device";
-    if (k < 1 || k > (1 << 20)) return fail(s, CALIPSO_ERR_ARGUMENT, std::string(me) + "k >= 1 cotangent columns");
-    if (!cot_w && !cot_x && !cot_y && !cot_z) return fail(s, CALIPSO_ERR_ARGUMENT, std::string(me) + "no cotangent");
-    if (!s->have_qp && !s->ev) return fail(s, CALIPSO_ERR_ARGUMENT, std::string(me) + "no problem data (calipso_hip_smallnewton_set_qp or calipso_hip_smallnewton_set_evaluator)");
-    if (s->ev && !s->ev_adj)
-        return fail(s, CALIPSO_ERR_ARGUMENT, std::string(me) + "the evaluator's entry was built without the reverse mode: rebuild it against the current include/calipso_smallnewton.hpp");
-    if (grad_theta && (!s->ev || !s->ev_rtheta || s->np < 1))
-        return fail(s, CALIPSO_ERR_ARGUMENT, std::string(me) + "grad_theta needs an evaluator that provides dR/dtheta and has parameters");
-    if (grad_qp && s->ev) return fail(s, CALIPSO_ERR_ARGUMENT, std::string(me) + "grad_qp is for the built-in QP (set_qp), not an evaluator");
+    { const int rc = adjoint_refusals(s, k, cot_w || cot_x || cot_y || cot_z, grad_theta != nullptr, grad_qp != nullptr); if (rc < 0) return rc; }
     if (reduce_mask < 0 || reduce_mask > 63) return fail(s, CALIPSO_ERR_ARGUMENT, std::string(dev) + ": reduce_mask has one bit per array of P, q, A, b, G, h (0 .. 63)");
     SK(hipSetDevice(s->device));
     DEVPTR(dev, cot_w); DEVPTR(dev, cot_x); DEVPTR(dev, cot_y); DEVPTR(dev, cot_z); DEVPTR(dev, adjoint); DEVPTR(dev, grad_theta); DEVPTR(dev, status);
     const Dm d = dims_of(s);
     const size_t B = (size_t)s->batch, N = (size_t)d.N, K = (size_t)k;
-    const size_t nqp = (size_t)d.nx * d.nx + d.nx + (size_t)d.ne * d.nx + d.ne + (size_t)d.nc * d.nx + d.nc;
+    const size_t nqp = qp_entries(d);
     GqpArgs ga;
     std::memset(&ga, 0, sizeof(ga));
     bool any_qp = false, any_red = false, any_per = false;
@@ -374,8 +402,6 @@ int32_t calipso_hip_smallnewton_differentiate_adjoint_device(calipso_hip_smallne
     if (any_red && nchunks * tblocks > 0x7fffffffull) return fail(s, CALIPSO_ERR_ARGUMENT, std::string(dev) + ": the batch reduction exceeds a launch grid");
     int rc = CALIPSO_OK;
     if (!cot_w) rc = grow(s, &s->adj_in, &s->cap_adj_in, B * N * K, dev);
-    if (rc == CALIPSO_OK && grad_theta) rc = grow(s, &s->adj_rt, &s->cap_adj_rt, B * N * (size_t)s->np, dev);
-    if (rc == CALIPSO_OK && any_qp) rc = grow(s, &s->adj_gqp, &s->cap_adj_gqp, B * K * nqp, dev);
     if (rc == CALIPSO_OK && any_red) rc = grow(s, &s->red, &s->cap_red, nchunks * K * nqp, dev);
     if (rc < 0) return rc;
     if (!cot_w) {
@@ -385,11 +411,7 @@ int32_t calipso_hip_smallnewton_differentiate_adjoint_device(calipso_hip_smallne
         hipLaunchKernelGGL(k_sn_cot, dim3(blocks_for(B * K * N)), dim3(IO_NT), 0, s->stream, ca);
         SK(hipGetLastError());
     }
-    AdjArgs aa;
-    std::memset(&aa, 0, sizeof(aa));
-    aa.cot = cot_w ? cot_w : s->adj_in; aa.adjoint = adjoint; aa.grad_theta = grad_theta; aa.grad_qp = any_qp ? s->adj_gqp : nullptr;
-    aa.objective_scale = s->objective_scale; aa.k = (int)k;
-    rc = launch(s, MODE_ADJ, grad_theta ? s->np : 0, 0, grad_theta != nullptr, &aa, true);
+    rc = calipso::snh::adjoint(s, k, cot_w ? cot_w : s->adj_in, adjoint, grad_theta, any_qp, false);
     if (rc < 0) return rc;
     if (grad_theta) {
         hipLaunchKernelGGL(k_sn_nan_rows, dim3((unsigned)B), dim3(IO_NT), 0, s->stream, grad_theta, (const int*)s->solve_status, (long long)(K * (size_t)s->np), s->batch);
@@ -408,7 +430,7 @@ int32_t calipso_hip_smallnewton_differentiate_adjoint_device(calipso_hip_smallne
     return CALIPSO_OK;
 }
 
-// out = {addresses of Lxx, q, Z, bh; their element strides per instance}: what tests read to see that a repeated set_qp_device keeps its buffers and which arrays are stored once
+// out = {addresses of Lxx, q, Z, bh; their element strides per instance}: what tests read to see that a repeated set_qp / set_qp_device keeps its buffers and which arrays are stored once
 int32_t calipso_hip_debug_smallnewton_buffers(calipso_hip_smallnewton* s, int64_t out[8]) {
     if (!s || !out) return CALIPSO_ERR_ARGUMENT;
     out[0] = (int64_t)(uintptr_t)s->P; out[1] = (int64_t)(uintptr_t)s->q; out[2] = (int64_t)(uintptr_t)s->Z; out[3] = (int64_t)(uintptr_t)s->bh;

@@ -544,9 +544,9 @@ int32_t calipso_hip_smallnewton_differentiate_adjoint(calipso_hip_smallnewton*, 
  *                                            destroy waits for the stream it holds).  The evaluator's entry already launches on the stream it is handed.
  *   set_qp_device(P, q, A, b, G, h, c, shared_mask, row_major)
  *                                            bit i of shared_mask: array i of P, q, A, b, G, h is ONE array for all instances, else batch-major; row_major != 0:
- *                                            matrices (rows, cols) row-major, as torch lays them out, else column-major as set_qp.  A pack kernel writes what
- *                                            set_qp builds on the host — Lxx = (2c) P, Z = [A; -G] (ld m, column-major), bh = [-b; h] — with the same operations:
- *                                            the same bits.  P and q are stored once when shared; Z once only when A and G are both shared or absent, bh likewise
+ *                                            matrices (rows, cols) row-major, as torch lays them out, else column-major as set_qp.  The pack kernel that set_qp
+ *                                            goes through as well writes Lxx = (2c) P, Z = [A; -G] (ld m, column-major), bh = [-b; h]: the same bits from both
+ *                                            entries.  P and q are stored once when shared; Z once only when A and G are both shared or absent, bh likewise
  *                                            for b and h — otherwise the shared half is repeated into per-instance storage.  Replaces an evaluator as set_qp does
  *                                            (that one case frees the evaluator's buffers and waits).
  *   initialize_device(x0)                    initialize!: x0 (batch x nx; NULL: zeros) into the first nx entries of every point, zeros behind

@@ -521,3 +521,132 @@ def test_host_entries_keep_their_bits_on_a_borrowed_stream():
     assert np.array_equal(host_solve(S, d, c), res)
     assert_same_state(S, H)
     S.close(); H.close()
+
+
+# ---- 9. one data path behind the host and the device entries -----------------------------------------------------------------------------------------
+# Both kinds of entry pack through k_sn_pack, so "device equals host" no longer anchors the pack by itself: the scale is pinned here, transposes and signs by the
+# oracle comparisons of test_gpu_smallnewton.py and test_gpu_smallnewton_edges.py.
+def set_and_solve(sn, kind, data, c):
+    """the QP through the host ("host") or the device ("device") entry — arrays without a batch axis are shared —, a cold start, the solve: its statuses"""
+    if kind == "host":
+        sn.set_qp(*[data[n] for n in NAMES], objective_scale=c, shared=data["P"].ndim == 2)
+        sn.initialize(np.zeros((sn.batch, sn.nx)))
+        return sn.solve()[0]
+    sn.set_qp_device(*[cuda(data[n]) for n in NAMES], objective_scale=c)
+    sn.initialize_device(None)
+    sn.solve_device()
+    return sn.status_device().cpu().numpy()
+
+
+def on_torch_stream(sn):
+    sn.set_stream(torch.cuda.current_stream())
+    return sn
+
+
+@pytest.mark.parametrize("shared", [False, True])
+@pytest.mark.parametrize("kind", ["host", "device"])
+def test_objective_scale_is_one_multiply_of_P(kind, shared):
+    """Lxx = (2c) P is all the solve reads of P and c.  With P' = (2.0 * c) * P from numpy, 2 * 0.5 * P' = P' exactly: set_qp(P', objective_scale=0.5) must give
+    the bits of set_qp(P, objective_scale=c) — the pack multiplies once, by the rounded 2c"""
+    pkg = load_pkg()
+    c = 0.7
+    for layout in [(12, 5, 6, 0, 0), (1, 0, 0, 0, 0)]:
+        B = 5
+        d = gen(layout, B, 610)
+        data = {n: (d[n][0] if shared else d[n]) for n in NAMES}
+        scaled = dict(data, P=(2.0 * c) * data["P"])
+        X, Y = on_torch_stream(handle(pkg, layout, B, **TIGHT)), on_torch_stream(handle(pkg, layout, B, **TIGHT))
+        rx, ry = set_and_solve(X, kind, data, c), set_and_solve(Y, kind, scaled, 0.5)
+        assert np.array_equal(rx, ry) and (rx == 1).any(), (rx, ry)
+        assert_same_state(X, Y)
+        X.close(); Y.close()
+
+
+def test_one_handle_alternating_host_and_device_entries():
+    """buffers grow and never shrink, strides change with every call: after each step the handle solves as a fresh handle given only that step's data"""
+    pkg = load_pkg()
+    layout, B, c = (12, 5, 6, 0, 0), 6, 0.5
+    nx, m = 12, 11
+    full, zero = [nx * nx, nx, m * nx, m], [0, 0, 0, 0]
+    steps = [("host", "", full), ("device", "PAG", [0, nx, 0, m]), ("host", NAMES, zero), ("device", "", full), ("host", "", full)]
+    sn = on_torch_stream(handle(pkg, layout, B, **TIGHT))
+    for i, (kind, shared, strides) in enumerate(steps):
+        d = gen(layout, B, 620 + i)
+        data = {n: (d[n][0] if n in shared else d[n]) for n in NAMES}
+        fresh = on_torch_stream(handle(pkg, layout, B, **TIGHT))
+        res, ref = set_and_solve(sn, kind, data, c), set_and_solve(fresh, kind, data, c)
+        assert np.array_equal(res, ref) and (ref == 1).any(), (i, res, ref)
+        assert_same_state(sn, fresh)
+        assert buffers(sn)[4:] == strides and buffers(fresh)[4:] == strides, (i, buffers(sn))
+        fresh.close()
+    sn.close()
+
+
+def test_repeated_host_set_qp_keeps_its_buffers():
+    pkg = load_pkg()
+    layout, B = (12, 5, 6, 0, 0), 5
+    sn = handle(pkg, layout, B, **TIGHT)
+    host_solve(sn, gen(layout, B, 630), 0.5)
+    first = buffers(sn)
+    assert all(first[:4]) and first[4:] == [144, 12, 132, 11]
+    res = host_solve(sn, gen(layout, B, 631), 0.5)
+    assert buffers(sn) == first
+    fresh = handle(pkg, layout, B, **TIGHT)
+    assert np.array_equal(host_solve(fresh, gen(layout, B, 631), 0.5), res)
+    assert_same_state(sn, fresh)
+    sn.close(); fresh.close()
+
+
+def test_host_set_state_with_one_argument_leaves_the_other_two():
+    pkg = load_pkg()
+    layout, B = (12, 5, 6, 0, 0), 5
+    sn = handle(pkg, layout, B, **TIGHT)
+    host_solve(sn, gen(layout, B, 640), 0.5)
+    rng = np.random.default_rng(7)
+    before = sn.get_state()
+    assert (before["scalars"][:, 3:] != 0).any()                                      # (the regularisations the solve left: slots 3..5 hold something to lose)
+    sc = np.tile([0.05, 0.995, 30.0], (B, 1)) * (1.0 + 0.1 * rng.random((B, 3)))
+    sn.set_state(scalars=sc)
+    after = sn.get_state()
+    assert np.array_equal(after["scalars"][:, :3], sc) and np.array_equal(after["scalars"][:, 3:], before["scalars"][:, 3:])
+    assert np.array_equal(after["solution"], before["solution"]) and np.array_equal(after["dual"], before["dual"])
+    lam = before["dual"] + rng.standard_normal(before["dual"].shape)
+    sn.set_state(dual=lam)
+    third = sn.get_state()
+    assert np.array_equal(third["dual"], lam) and np.array_equal(third["solution"], before["solution"]) and np.array_equal(third["scalars"], after["scalars"])
+    w = before["solution"] + rng.standard_normal(before["solution"].shape)
+    sn.set_state(w=w)
+    last = sn.get_state()
+    assert np.array_equal(last["solution"], w) and np.array_equal(last["dual"], lam) and np.array_equal(last["scalars"], after["scalars"])
+    for key in before["counters"]:
+        assert np.array_equal(last["counters"][key], before["counters"][key]), key
+    sn.close()
+
+
+def test_host_set_qp_replaces_an_evaluator_and_an_evaluator_comes_back():
+    import test_gpu_smallnewton_evaluator as te
+    pkg = load_pkg()
+    prob = te.nonlinear_cone()
+    B = 5
+    th = te.nonlinear_thetas(B)
+    E, ref = te.make(pkg, prob, "nonlinear_cone_kernels", th), te.make(pkg, prob, "nonlinear_cone_kernels", th)
+    res_ev = ref.solve()[0]
+    assert (res_ev == 1).all() and np.array_equal(E.solve()[0], res_ev)
+    layout = (prob.nx, prob.ne, prob.nc, 0, 0)
+    d = gen(layout, B, 650)
+    Q = handle(pkg, layout, B)
+    res = host_solve(Q, d, 0.5)
+    assert np.array_equal(host_solve(E, d, 0.5), res) and (res == 1).any()           # the QP on the handle that held the evaluator
+    assert_same_state(E, Q)
+    assert "P" in E.vjp(np.ones((B, E.N)))
+    with pytest.raises(pkg.CalipsoHipError, match="calipso_hip_smallnewton_set_parameters: no evaluator"):
+        E.set_parameters(th)
+    E.set_evaluator(evlib(), "nonlinear_cone_kernels", prob.np)
+    E.initialize(np.repeat(prob.x0[None], B, axis=0))
+    with pytest.raises(pkg.CalipsoHipError, match="parameters and none were set"):
+        E.solve()                                                                     # (the parameters went with the first evaluator)
+    E.set_parameters(th)
+    assert np.array_equal(E.solve()[0], res_ev)
+    assert_same_state(E, ref)
+    for sn in (E, ref, Q):
+        sn.close()

@@ -726,35 +726,27 @@ static int do_factorize(H* s, int64_t inertia[3], bool rhs_ahead_ok = false) {
     return CALIPSO_OK;
 }
 
-// inertia.jl:30-80.  Quirk kept: the `primal_regularization_last == 0.0` test of :48 compares a Vector with a Float64 and is
-// always false, so IC-3 always takes max(min_regularization, scaling_regularization_last * eps_last).
+// inertia.jl:30-80: the walk itself is step_decisions.hpp (ic_begin / ic_after), the factorisations are queued here.
 // first_in / first_rc: IC-1 (the factorisation with the initial regularisation) was queued — and its inertia read — by the caller already (inner_iteration: ahead of the
 // host's exit tests); the loop goes on from its result
 static int do_inertia_correction(H* s, int64_t* nfact, bool rhs_ahead_ok = false, const int64_t* first_in = nullptr, int first_rc = 0) {
-    Options& o = s->opt; Scalars& sc = s->sc;
+    const Options& o = s->opt; const Dims& d = s->d;
     int64_t in[3];
-    int64_t count = 0;
-    sc.ep = o.primal_regularization_initial;
-    sc.ed = o.dual_regularization_initial;
+    ic_begin(o, s->sc);
     int rc;
     if (first_in) { in[0] = first_in[0]; in[1] = first_in[1]; in[2] = first_in[2]; rc = first_rc; }
-    else rc = do_factorize(s, in, rhs_ahead_ok);
-    count++;                                                     // IC-1
-    if (rc < 0) return rc;
-    if (inertia_ok(s, in)) { if (nfact) *nfact = count; return CALIPSO_OK; }
-    if (in[2] != 0) sc.ed = o.dual_regularization * std::pow(sc.kappa, o.dual_regularization_exponent);   // IC-2
-    sc.ep = std::max(o.min_regularization, o.scaling_regularization_last * sc.ep_last);                   // IC-3
-    while (!inertia_ok(s, in)) {
-        rc = do_factorize(s, in, rhs_ahead_ok); count++;         // IC-4 (the operands are formed again with the new regularisation)
+    else rc = do_factorize(s, in, rhs_ahead_ok);                 // IC-1
+    for (int64_t count = 1;; ++count) {
         if (rc < 0) return rc;
-        if (inertia_ok(s, in)) break;
-        if (sc.ep_last == 0.0) sc.ep = o.scaling_regularization_initial * sc.ep;   // IC-5
-        else sc.ep = o.scaling_regularization * sc.ep;
-        if (sc.ep > o.max_regularization) { if (nfact) *nfact = count; s->err = "inertia correction failure"; return CALIPSO_ERR_INERTIA; }   // IC-6
+        const IcVerdict v = ic_after(o, s->sc, in, d.nx, d.ne + d.nc, count == 1);
+        if (v != IC_AGAIN) {
+            if (nfact) *nfact = count;
+            if (v == IC_DONE) return CALIPSO_OK;
+            s->err = "inertia correction failure";
+            return CALIPSO_ERR_INERTIA;
+        }
+        rc = do_factorize(s, in, rhs_ahead_ok);                  // IC-4 (the operands are formed again with the new regularisation)
     }
-    sc.ep_last = sc.ep;
-    if (nfact) *nfact = count;
-    return CALIPSO_OK;
 }
 
 // refine_follows: the caller goes straight on to a refinement residual of s->step (which = 0 only: the local rows of that residual then come out of the same launch)
@@ -815,7 +807,6 @@ static int do_refinement(H* s, int* rounds, double* final_norm, bool zsx_valid =
     if (!zsx_valid && d.m) gemv_n(s, d.m, d.nx, s->Z, d.m, s->step, s->zsx, 1.0, 0.0, SP_Z);
     double norm, norm0;
     int it = 0;
-    bool met = false;
     if (spec_refinement_ok(s)) {
         const int spec = (int)std::min<calipso::i64>(o.max_iterative_refinement, std::max<calipso::i64>(1, s->stats.last_refine > 0 ? s->stats.last_refine : o.min_iterative_refinement));
         if (++s->gate_counter == 0) s->gate_counter = 1;
@@ -834,14 +825,13 @@ static int do_refinement(H* s, int* rounds, double* final_norm, bool zsx_valid =
         // (do_refinement_resume) — no host wait here
         if (s->refine_defer) { s->refine_pending = true; if (rounds) *rounds = -1; return CALIPSO_OK; }
         if (wait_published(s, s->pub_seq)) return CALIPSO_ERR_HIP;
-        norm = s->hscal[7]; norm0 = s->hscal[20]; it = (int)s->hscal[21]; met = s->hscal[22] != 0.0;
+        norm = s->hscal[7]; norm0 = s->hscal[20]; it = (int)s->hscal[21];
     } else {
         refine_residual(s, true);                  // (k_refine_x itself publishes the norm: no separate read-back launch)
         if (wait_published(s, s->pub_seq)) return CALIPSO_ERR_HIP;
         norm = s->hscal[7];
         norm0 = norm;
     }
-    (void)met;
     return refinement_loop(s, norm, norm0, it, rounds, final_norm, nullptr);
 }
 // the report of the speculative rounds has arrived with a later read-back of the caller: go on from it
@@ -850,21 +840,9 @@ static int do_refinement_resume(H* s, int* rounds, bool* ran_more) {
     return refinement_loop(s, s->hscal[7], s->hscal[20], (int)s->hscal[21], rounds, nullptr, ran_more);
 }
 static int refinement_loop(H* s, double norm, double norm0, int it, int* rounds, double* final_norm, bool* ran_more) {
-    const Options& o = s->opt;
     if (ran_more) *ran_more = false;
-    while (it <= o.max_iterative_refinement) {
-        if (norm <= o.iterative_refinement_tolerance && it >= o.min_iterative_refinement) {
-            if (it == 0) fill_d(s, s->step_correction, s->d.N, 0.0);
-            if (rounds) *rounds = it;
-            if (final_norm) *final_norm = norm;
-            s->stats.last_refine = it; s->stats.refine_max = std::max<calipso::i64>(s->stats.refine_max, it);
-            return CALIPSO_OK;
-        }
-        // a residual with a NaN in it reports +inf (vectors.hip: rabs).  The reference's norm is NaN there: `norm <= tol` is never true, so its loop (`while iteration <=
-        // max_iterative_refinement`, iterative_refinement.jl:14-44) runs ALL its rounds on NaNs before it fails (:45-51).  DEVIATION, same outcome: the rounds that cannot
-        // change the verdict are not run — the loop leaves as soon as the minimum number of rounds is done, fails (WARN_REFINEMENT -> the H \ residual fallback) and
-        // reports the reference's round count (max_iterative_refinement + 1) in rounds / stats so that the statistics agree with the reference's
-        if (!std::isfinite(norm) && it >= o.min_iterative_refinement) { it = (int)std::max<calipso::i64>(it, o.max_iterative_refinement + 1); break; }
+    RefineVerdict v;
+    while ((v = refine_next(s->opt, norm, norm0, &it)) == REFINE_ROUND) {
         if (ran_more) *ran_more = true;
         refine_solve(s);                   // step += step_correction fused into the recovery kernel
         refine_residual(s, true);
@@ -872,15 +850,20 @@ static int refinement_loop(H* s, double norm, double norm0, int it, int* rounds,
         norm = s->hscal[7];
         it += 1;
     }
-    if (it == 0) fill_d(s, s->step_correction, s->d.N, 0.0);      // (max_iterative_refinement < 0)
+    if (it == 0) fill_d(s, s->step_correction, s->d.N, 0.0);      // (no round ran: nothing has written step_correction)
     if (rounds) *rounds = it;
     if (final_norm) *final_norm = norm;
     s->stats.last_refine = it; s->stats.refine_max = std::max<calipso::i64>(s->stats.refine_max, it);
-    if (std::isfinite(norm) && norm <= norm0) return CALIPSO_OK;
-    s->stats.refine_fail += 1;
+    if (v == REFINE_DONE) return CALIPSO_OK;
+    s->stats.refine_fail += 1;             // -> WARN_REFINEMENT -> the H \ residual fallback
     return CALIPSO_WARN_REFINEMENT;
 }
-
+// a failed refinement (rc = WARN_REFINEMENT): the reference falls back to `H \ residual` on the unreduced system (search_direction.jl:22,113): fallback.hip
+static int refinement_fallback(H* s, int rc) {
+    if (rc != CALIPSO_WARN_REFINEMENT) return rc;
+    const int fr = nonsymmetric_solve(s, s->residual, s->step);
+    return fr < 0 ? fr : CALIPSO_WARN_REFINEMENT;
+}
 // defer: the refinement's speculative rounds are queued and NOT waited for (s->refine_pending; the caller reads their report later and calls search_direction_finish)
 static int do_search_direction(H* s, int64_t* nfact, int* rounds, const int64_t* first_in = nullptr, int first_rc = 0, bool defer = false) {
     int rc = do_inertia_correction(s, nfact, true, first_in, first_rc);
@@ -895,30 +878,16 @@ static int do_search_direction(H* s, int64_t* nfact, int* rounds, const int64_t*
         s->refine_defer = defer; s->refine_pending = false;
         rc = do_refinement(s, rounds, nullptr, true);
         s->refine_defer = false;
-        if (rc < 0) return rc;
-        if (rc == CALIPSO_WARN_REFINEMENT) {
-            // the reference falls back to `H \ residual` on the unreduced system (search_direction.jl:22,113): fallback.hip
-            const int fr = nonsymmetric_solve(s, s->residual, s->step);
-            if (fr < 0) return fr;
-            return CALIPSO_WARN_REFINEMENT;
-        }
+        return refinement_fallback(s, rc);
     }
     return CALIPSO_OK;
 }
 // the rest of do_search_direction once the deferred refinement report has arrived; step_changed: the step is not the one the caller queued work on (further rounds ran,
 // or the fallback replaced it)
 static int search_direction_finish(H* s, int* rounds, bool* step_changed) {
-    bool more = false;
-    const int rc = do_refinement_resume(s, rounds, &more);
-    *step_changed = more;
-    if (rc < 0) return rc;
-    if (rc == CALIPSO_WARN_REFINEMENT) {
-        const int fr = nonsymmetric_solve(s, s->residual, s->step);
-        if (fr < 0) return fr;
-        *step_changed = true;
-        return CALIPSO_WARN_REFINEMENT;
-    }
-    return CALIPSO_OK;
+    const int rc = refinement_fallback(s, do_refinement_resume(s, rounds, step_changed));
+    if (rc == CALIPSO_WARN_REFINEMENT) *step_changed = true;      // (the fallback replaced the step)
+    return rc;
 }
 // Queueing ahead of the host's knowledge inside a Newton step (a single handle with a device-side evaluator; CALIPSO_HIP_SPEC_STEP=0: every decision waited for in
 // place, as up to round 5): IC-1 of the search direction is queued before the host has seen the norms of the exit tests, and the cone search, the first candidate and its
@@ -929,22 +898,21 @@ static bool spec_step_ok(const H* s) {
     return env && !s->cur && (s->qp.attached || s->dev_eval || s->dev_block_eval);
 }
 
+// the step sizes of the cone search from the masks the handle has read back
+static int step_sizes_from_masks(H* s, double* a_s, double* a_t) {
+    if (cone_step_sizes(s->hicount + 6, s->hicount + 32, s->opt, a_s, a_t)) return CALIPSO_OK;
+    s->err = "cone search failure";                                                     // solve.jl:210,220
+    return CALIPSO_ERR_CONE_SEARCH;
+}
 static int do_cone_search(H* s, double* a_s, double* a_t, bool emit_candidate = true) {
-    const Options& o = s->opt;
     if (s->d.nc == 0) { *a_s = 1.0; *a_t = 1.0; return CALIPSO_OK; }
     {   // the kernel publishes its masks itself (no k_publish_words launch behind it)
         const unsigned long long seq = ++s->pub_seq;
         launch_cone_search(s, seq);
         if (wait_published(s, seq)) return CALIPSO_ERR_HIP;
     }
-    const int ks = first_feasible_trial(s->hicount + 6, o.max_cone_line_search), kt = first_feasible_trial(s->hicount + 32, o.max_cone_line_search);
-    if (ks < 0 || kt < 0) { s->err = "cone search failure"; return CALIPSO_ERR_CONE_SEARCH; }   // solve.jl:210,220
-    // step sizes as the reference forms them: repeated multiplication by scaling_line_search (the kernel tested exactly these)
-    double as = 1.0, at = 1.0;
-    for (int k = 0; k < ks; ++k) as = o.scaling_line_search * as;
-    for (int k = 0; k < kt; ++k) at = o.scaling_line_search * at;
-    *a_s = as; *a_t = at;
-    if (emit_candidate) launch_cone_candidate(s, as, at);
+    if (int rc = step_sizes_from_masks(s, a_s, a_t)) return rc;
+    if (emit_candidate) launch_cone_candidate(s, *a_s, *a_t);
     return CALIPSO_OK;
 }
 
@@ -1066,7 +1034,7 @@ static int inner_iteration(H* s, calipso_eval_fn eval, void* user, double equali
         rc = evaluate(s, eval, user, 0, fl);                                            // :175-181
         if (rc < 0) return rc;
         EV(2);
-        sc.ep = o.primal_regularization_initial; sc.ed = o.dual_regularization_initial;
+        ic_begin(o, sc);
         rc0 = do_factorize(s, in0, true);                                               // IC-1 of inertia_correction! (its read-back is behind the norms' in the stream)
         if (rc0 < 0) return rc0;
     } else if (wait_published(s, s->pub_seq)) return CALIPSO_ERR_HIP;
@@ -1078,29 +1046,16 @@ static int inner_iteration(H* s, calipso_eval_fn eval, void* user, double equali
         s->stats.factorizations -= 1; s->phase_ms[8] -= 1.0;
         s->spec_ahead_ok = false;
     };
-    const double* hs = s->hscal;
-    info.M = hs[4]; info.theta = hs[5];
-    info.residual_violation = hs[8] / (double)d.N;
-    const double sd = (d.ne + d.nc > 0) ? std::max(100.0, (hs[13] + hs[14]) / (double)(d.ne + d.nc)) / 100.0 : 1.0;   // optimality_error.jl:8
-    const double scn = (d.nc > 0) ? std::max(100.0, hs[15] / (double)d.nc) / 100.0 : 1.0;                             // :9
-    info.optimality = std::max(std::max(hs[9] / sd, hs[10]), std::max(hs[11], hs[12] / scn));
-    info.slack_violation = std::max(hs[10], hs[11]);
+    info.M = s->hscal[4]; info.theta = s->hscal[5];
+    const StepNorms norms = step_norms(s->hscal, d.N, d.ne, d.nc);
     if (!ahead) EV(1);
-    if (info.residual_violation < o.residual_tolerance && info.slack_violation < o.slack_tolerance &&
-        equality_violation <= o.equality_tolerance && cone_product_violation <= o.complementarity_tolerance) {   // :138-143
+    info.exit_kind = exit_kind(o, sc_before.kappa, norms, equality_violation, cone_product_violation, true);      // :138-143, :165
+    if (info.exit_kind != 0) {
         undo_ahead();
         s->spec_ahead_ok = false;
-        info.exit_kind = 1;
         return CALIPSO_OK;
     }
-    const double exit2 = std::max(o.central_path_update_tolerance * sc_before.kappa, o.optimality_tolerance);
-    if (info.optimality <= exit2) {                                                                               // :165
-        undo_ahead();
-        s->spec_ahead_ok = false;
-        info.exit_kind = 2;
-        return CALIPSO_OK;
-    }
-    s->spec_ahead_ok = info.optimality > 4.0 * exit2 && info.residual_violation >= o.residual_tolerance;          // (the next step's prediction)
+    s->spec_ahead_ok = norms.optimality > 4.0 * inner_exit_threshold(o, sc_before.kappa) && norms.residual_violation >= o.residual_tolerance;   // (the next step's prediction)
     if (!ahead) {
         rc = evaluate(s, eval, user, 0, fl);                                            // :175-181
         if (rc < 0) return rc;
@@ -1126,12 +1081,9 @@ static int inner_iteration(H* s, calipso_eval_fn eval, void* user, double equali
         if (w2 < 0) return w2;
         warn = std::max(warn, w2);
         if (!step_changed) {
-            const int ks = first_feasible_trial(s->hicount + 6, o.max_cone_line_search), kt = first_feasible_trial(s->hicount + 32, o.max_cone_line_search);
-            if (ks < 0 || kt < 0) { s->err = "cone search failure"; return CALIPSO_ERR_CONE_SEARCH; }   // solve.jl:210,220
-            double as = 1.0, at = 1.0;                                                   // (what k_first_candidate_masks formed from the same masks)
-            for (int k = 0; k < ks; ++k) as = o.scaling_line_search * as;
-            for (int k = 0; k < kt; ++k) at = o.scaling_line_search * at;
-            info.step_size = as; info.step_size_t = at; step_size = as;
+            rc = step_sizes_from_masks(s, &info.step_size, &info.step_size_t);            // (what k_first_candidate_masks formed from the same masks)
+            if (rc < 0) return rc;
+            step_size = info.step_size;
             Mh = s->hscal[4]; thetah = s->hscal[5];
             tail_done = true;
         }
@@ -1151,14 +1103,7 @@ static int inner_iteration(H* s, calipso_eval_fn eval, void* user, double equali
     const double M = info.M, theta = info.theta;
     calipso::i64 residual_iteration = 0;
     while (residual_iteration < o.max_residual_line_search) {                           // :254-302
-        if (check_filter(s, thetah, Mh)) {
-            if (theta <= o.slack_tolerance && switching_condition(step_size, dd, o.merit_exponent, theta, o.violation_exponent, 1.0) &&
-                armijo(M, Mh, dd, step_size, o.armijo_tolerance, o.machine_tolerance)) {
-                break;
-            } else if (sufficient_progress(theta, thetah, M, Mh, o.violation_tolerance, o.merit_tolerance, o.machine_tolerance)) {
-                break;
-            }
-        }
+        if (line_search_accepts(o, check_filter(s, thetah, Mh), theta, M, thetah, Mh, dd, step_size)) break;
         step_size = o.scaling_line_search * step_size;
         launch_axpy_points(s, step_size, 1);                                            // :268-276
         rc = candidate_merit(s, eval, user, &Mh, &thetah);                              // :278-297
@@ -1166,10 +1111,7 @@ static int inner_iteration(H* s, calipso_eval_fn eval, void* user, double equali
         residual_iteration += 1;
     }
     if (residual_iteration >= o.max_residual_line_search) warn = std::max(warn, (int)CALIPSO_WARN_LINE_SEARCH);
-    // augment_filter!(solver, ...)  filter.jl:81-89
-    if (!switching_condition(step_size, dd, o.merit_exponent, theta, o.violation_exponent, 1.0) ||
-        !armijo(M, Mh, dd, step_size, o.armijo_tolerance, o.machine_tolerance))
-        augment_filter(s, (1.0 - o.violation_tolerance) * theta, M - o.merit_tolerance * theta);
+    augment_filter_after_step(s, theta, M, Mh, dd, step_size);
     launch_accept(s, step_size);                                                        // :309-326
     launch_cone(s, s->solution, CALIPSO_CONE_PRODUCT);                                  // :328-330
     launch_violations(s, 16, 2);                                                        // ||g||inf, ||s o t||inf  :332-333
@@ -1195,14 +1137,10 @@ int32_t calipso_hip_violations(H* s, double out[5]) {
     const Dims& d = s->d;
     launch_violations(s);
     if (read_scalars(s, 8, 10)) return CALIPSO_ERR_HIP;
-    const double* hs = s->hscal;
-    const double sd = (d.ne + d.nc > 0) ? std::max(100.0, (hs[13] + hs[14]) / (double)(d.ne + d.nc)) / 100.0 : 1.0;
-    const double scn = (d.nc > 0) ? std::max(100.0, hs[15] / (double)d.nc) / 100.0 : 1.0;
-    out[0] = hs[8] / (double)d.N;
-    out[1] = std::max(std::max(hs[9] / sd, hs[10]), std::max(hs[11], hs[12] / scn));
-    out[2] = std::max(hs[10], hs[11]);
-    out[3] = hs[16];
-    out[4] = hs[17];
+    const StepNorms n = step_norms(s->hscal, d.N, d.ne, d.nc);
+    out[0] = n.residual_violation; out[1] = n.optimality; out[2] = n.slack_violation;
+    out[3] = s->hscal[16];
+    out[4] = s->hscal[17];
     return CALIPSO_OK;
 }
 
@@ -1371,8 +1309,7 @@ int32_t calipso_hip_solve(H* s, calipso_eval_fn eval, void* user) {
         if (rc < 0) return rc;
         launch_init_point(s);                                                           // + initialize_duals! :31-36
     }
-    sc.kappa = o.central_path_initial; sc.tau = std::max(0.99, 1.0 - sc.kappa);          // initialize.jl:38-42
-    sc.rho = o.penalty_initial;                                                         // :44-48
+    initial_scalars(o, sc);                                                             // initialize.jl:38-48
     {
         std::vector<double> l0((size_t)std::max(1, d.ne), o.dual_initial);
         if (d.ne) CK(hipMemcpyAsync(s->lambda, l0.data(), sizeof(double) * d.ne, hipMemcpyHostToDevice, s->stream));
@@ -1406,10 +1343,9 @@ int32_t calipso_hip_solve(H* s, calipso_eval_fn eval, void* user) {
             total_iterations += 1;
             s->stats.total_iterations = total_iterations;
         }
-        sc.kappa = std::max(o.residual_tolerance / 10.0, std::min(o.central_path_scaling * sc.kappa, std::pow(sc.kappa, o.central_path_exponent)));   // :356
-        sc.tau = std::max(0.99, 1.0 - sc.kappa);                                         // :359
+        central_path_update(o, sc);                                                     // :356-359
         launch_lambda_update(s);                                                        // :362-364
-        sc.rho = std::min(std::max(o.penalty_scaling * sc.rho, 1.0 / sc.kappa), o.max_penalty);   // :365
+        penalty_update(o, sc);                                                          // :365
         filter_reset(s);                                                                // :368
         if (s->cb_outer) { SYNC(); s->cb_outer(s->cb_user, s); }         // callback_outer(custom, solver)  solve.jl:371
     }
@@ -1499,16 +1435,10 @@ static int32_t newton_step_impl(H* s, int32_t advance, double info_out[6], bool 
     if (!s) return CALIPSO_ERR_ARGUMENT;
     (void)hipGetLastError();      // (launch_errors reports what THIS call's launches leave behind, not an earlier call's)
     if (!s->qp.attached && !s->dev_eval && !s->dev_block_eval) { s->err = "calipso_hip_newton_step needs a device evaluator (calipso_hip_qp_attach or calipso_hip_set_device_evaluator)"; return CALIPSO_ERR_ARGUMENT; }
-    const Dims& d = s->d;
     const Scalars saved_sc = s->sc;
     std::vector<double> ft, fm; calipso::i64 fi = 0;
     if (!advance) {
-        {
-            double* const dst[4] = {s->saved_point, s->saved_g, s->saved_h, s->dscal + 32};
-            const double* const src[4] = {s->solution, s->g, s->hc, s->dscal};
-            const size_t n[4] = {(size_t)d.N, (size_t)d.ne, (size_t)d.nc, 2};
-            copy4_d(s, dst, src, n);
-        }
+        copy_step_state(s, true);
         ft = s->filter_theta; fm = s->filter_merit; fi = s->filter_index;
     }
     IterInfo info;
@@ -1518,16 +1448,10 @@ static int32_t newton_step_impl(H* s, int32_t advance, double info_out[6], bool 
     EV(9);
     if (rc < 0) return rc;
     if (!advance) {
-        {
-            double* const dst[4] = {s->solution, s->g, s->hc, s->dscal};
-            const double* const src[4] = {s->saved_point, s->saved_g, s->saved_h, s->dscal + 32};
-            const size_t n[4] = {(size_t)d.N, (size_t)d.ne, (size_t)d.nc, 2};
-            copy4_d(s, dst, src, n);
-        }
+        copy_step_state(s, false);
         launch_cone(s, s->solution, CALIPSO_CONE_PRODUCT);
         s->filter_theta = ft; s->filter_merit = fm; s->filter_index = fi;
-        const double keep_ep = s->sc.ep, keep_ed = s->sc.ed;
-        s->sc = saved_sc; s->sc.ep = keep_ep; s->sc.ed = keep_ed;   // eps_last restored: every benchmark step repeats IC-1
+        restore_scalars_keeping_regularization(s->sc, saved_sc);
     }
     if (info_out) {
         info_out[0] = info.step_size; info_out[1] = info.step_size_t; info_out[2] = info.rounds; info_out[3] = (double)info.nfact;

@@ -240,31 +240,19 @@ static int gb_factorize(G* g, const Set& a, std::vector<std::array<int64_t, 3>>&
 
 // inertia_correction! (inertia.jl:30-80) for every member of `a`; rc[i] < 0 marks a member that failed
 static int gb_inertia_correction(G* g, const Set& a, std::vector<int>& rc, std::vector<int64_t>& nfact) {
+    const Dims& d = g->base->d;
     std::vector<std::array<int64_t, 3>> in(g->hs.size());
-    for (int i : a) { H* h = g->hs[i]; h->sc.ep = h->opt.primal_regularization_initial; h->sc.ed = h->opt.dual_regularization_initial; nfact[i] = 0; }
-    int e = gb_factorize(g, a, in);                              // IC-1
-    if (e < 0) return e;
-    Set pending;
-    for (int i : a) {
-        H* h = g->hs[i]; nfact[i] += 1;
-        if (inertia_ok(h, in[i].data())) continue;
-        Options& o = h->opt; Scalars& sc = h->sc;
-        if (in[i][2] != 0) sc.ed = o.dual_regularization * std::pow(sc.kappa, o.dual_regularization_exponent);   // IC-2
-        sc.ep = std::max(o.min_regularization, o.scaling_regularization_last * sc.ep_last);                     // IC-3
-        pending.push_back(i);
-    }
-    while (!pending.empty()) {
-        e = gb_factorize(g, pending, in);                        // IC-4
+    for (int i : a) { H* h = g->hs[i]; ic_begin(h->opt, h->sc); nfact[i] = 0; }
+    Set pending = a;
+    for (bool first = true; !pending.empty(); first = false) {
+        const int e = gb_factorize(g, pending, in);              // IC-1, then IC-4 for the members that need another one
         if (e < 0) return e;
         Set next;
         for (int i : pending) {
             H* h = g->hs[i]; nfact[i] += 1;
-            Options& o = h->opt; Scalars& sc = h->sc;
-            if (inertia_ok(h, in[i].data())) { sc.ep_last = sc.ep; continue; }
-            if (sc.ep_last == 0.0) sc.ep = o.scaling_regularization_initial * sc.ep;   // IC-5
-            else sc.ep = o.scaling_regularization * sc.ep;
-            if (sc.ep > o.max_regularization) { h->err = "inertia correction failure"; rc[i] = CALIPSO_ERR_INERTIA; continue; }   // IC-6
-            next.push_back(i);
+            const IcVerdict v = ic_after(h->opt, h->sc, in[i].data(), d.nx, d.ne + d.nc, first);
+            if (v == IC_AGAIN) next.push_back(i);
+            else if (v == IC_FAILED) { h->err = "inertia correction failure"; rc[i] = CALIPSO_ERR_INERTIA; }
         }
         pending.swap(next);
     }
@@ -312,21 +300,17 @@ static int gb_refinement(G* g, const Set& a, std::vector<int>& rc, std::vector<i
     while (!run.empty()) {
         Set sub, none;
         for (int i : run) {
-            H* h = g->hs[i]; const Options& o = h->opt;
-            bool finished = false;
-            if (it[i] > o.max_iterative_refinement) {        // loop exhausted: fail <=> the final error exceeds the initial one
-                finished = true;
-                if (!(norm[i] <= norm0[i])) {           // search_direction.jl:22 -> H \ residual on the member's own stream
-                    h->stats.refine_fail += 1;
-                    const int fr = nonsymmetric_solve(h, h->residual, h->step);
-                    rc[i] = fr < 0 ? fr : std::max(rc[i], (int)CALIPSO_WARN_REFINEMENT);
-                }
-            } else if (norm[i] <= o.iterative_refinement_tolerance && it[i] >= o.min_iterative_refinement) finished = true;
-            if (finished) {
-                rounds[i] = it[i];
-                h->stats.last_refine = it[i]; h->stats.refine_max = std::max<calipso::i64>(h->stats.refine_max, it[i]);
-                if (it[i] == 0) none.push_back(i);
-            } else sub.push_back(i);
+            H* h = g->hs[i];
+            const RefineVerdict v = refine_next(h->opt, norm[i], norm0[i], &it[i]);
+            if (v == REFINE_ROUND) { sub.push_back(i); continue; }
+            if (v == REFINE_FAILED) {                   // search_direction.jl:22 -> H \ residual on the member's own stream
+                h->stats.refine_fail += 1;
+                const int fr = nonsymmetric_solve(h, h->residual, h->step);
+                rc[i] = fr < 0 ? fr : std::max(rc[i], (int)CALIPSO_WARN_REFINEMENT);
+            }
+            rounds[i] = it[i];
+            h->stats.last_refine = it[i]; h->stats.refine_max = std::max<calipso::i64>(h->stats.refine_max, it[i]);
+            if (it[i] == 0) none.push_back(i);
         }
         // fill!(step_correction, 0) (iterative_refinement.jl:5) only for the members that take no round: the first round's k_recover writes every entry
         if (first_pass && !none.empty()) { g_activate(g, none); fill_d(s, s->step_correction, s->d.N, 0.0); }
@@ -376,18 +360,12 @@ static int gb_inner_iteration(G* g, const Set& a0, std::vector<IterInfo>& info, 
     if (g_read_d(g, a0, 4, 14)) return CALIPSO_ERR_HIP;
     Set a;
     for (int i : a0) {
-        H* h = g->hs[i]; const Options& o = h->opt; const double* hs = h->hscal; IterInfo& f = info[i];
-        f.M = hs[4]; f.theta = hs[5];
-        f.residual_violation = hs[8] / (double)d.N;
-        const double sd = (d.ne + d.nc > 0) ? std::max(100.0, (hs[13] + hs[14]) / (double)(d.ne + d.nc)) / 100.0 : 1.0;
-        const double scn = (d.nc > 0) ? std::max(100.0, hs[15] / (double)d.nc) / 100.0 : 1.0;
-        f.optimality = std::max(std::max(hs[9] / sd, hs[10]), std::max(hs[11], hs[12] / scn));
-        f.slack_violation = std::max(hs[10], hs[11]);
-        if (eq_violation && f.residual_violation < o.residual_tolerance && f.slack_violation < o.slack_tolerance &&
-            (*eq_violation)[i] <= o.equality_tolerance && (*cp_violation)[i] <= o.complementarity_tolerance) { f.exit_kind = 1; continue; }   // :138-143
-        // (the benchmark step passes no violations: the outer-convergence exit cannot trigger there)
-        if (f.optimality <= std::max(o.central_path_update_tolerance * h->sc.kappa, o.optimality_tolerance)) { f.exit_kind = 2; continue; }   // :165
-        a.push_back(i);
+        H* h = g->hs[i]; IterInfo& f = info[i];
+        f.M = h->hscal[4]; f.theta = h->hscal[5];
+        // :138-143, :165 (the benchmark step passes no violations: the outer-convergence exit cannot trigger there)
+        f.exit_kind = exit_kind(h->opt, h->sc.kappa, step_norms(h->hscal, d.N, d.ne, d.nc), eq_violation ? (*eq_violation)[i] : 0.0, cp_violation ? (*cp_violation)[i] : 0.0,
+                                eq_violation != nullptr);
+        if (f.exit_kind == 0) a.push_back(i);
     }
     EV(1);
     if (a.empty()) { EV(2); EV(3); EV(4); return CALIPSO_OK; }
@@ -429,11 +407,8 @@ static int gb_inner_iteration(G* g, const Set& a0, std::vector<IterInfo>& info, 
     for (int i : a) all_device = all_device && (g->hs[i]->qp.attached || g->hs[i]->dev_eval || g->hs[i]->dev_block_eval);
     auto step_sizes_from_masks = [&](const Set& set) {
         for (int i : set) {
-            H* h = g->hs[i]; const Options& o = h->opt;
-            const int ks = first_feasible_trial(h->hicount + 6, o.max_cone_line_search), kt = first_feasible_trial(h->hicount + 32, o.max_cone_line_search);
-            if (ks < 0 || kt < 0) { h->err = "cone search failure"; rc[i] = CALIPSO_ERR_CONE_SEARCH; continue; }
-            for (int k = 0; k < ks; ++k) as[i] = o.scaling_line_search * as[i];
-            for (int k = 0; k < kt; ++k) at[i] = o.scaling_line_search * at[i];
+            H* h = g->hs[i];
+            if (!cone_step_sizes(h->hicount + 6, h->hicount + 32, h->opt, &as[i], &at[i])) { h->err = "cone search failure"; rc[i] = CALIPSO_ERR_CONE_SEARCH; }
         }
     };
     if (all_device) {
@@ -476,11 +451,7 @@ static int gb_inner_iteration(G* g, const Set& a0, std::vector<IterInfo>& info, 
             H* h = g->hs[i]; const Options& o = h->opt;
             const double M = info[i].M, theta = info[i].theta;
             if (!(ls_it[i] < o.max_residual_line_search)) continue;
-            if (check_filter(h, thetah[i], Mh[i])) {
-                if (theta <= o.slack_tolerance && switching_condition(step_size[i], dd[i], o.merit_exponent, theta, o.violation_exponent, 1.0) &&
-                    armijo(M, Mh[i], dd[i], step_size[i], o.armijo_tolerance, o.machine_tolerance)) continue;
-                else if (sufficient_progress(theta, thetah[i], M, Mh[i], o.violation_tolerance, o.merit_tolerance, o.machine_tolerance)) continue;
-            }
+            if (line_search_accepts(o, check_filter(h, thetah[i], Mh[i]), theta, M, thetah[i], Mh[i], dd[i], step_size[i])) continue;
             step_size[i] = o.scaling_line_search * step_size[i];
             sub.push_back(i);
         }
@@ -496,11 +467,8 @@ static int gb_inner_iteration(G* g, const Set& a0, std::vector<IterInfo>& info, 
     }
     for (int i : a) {
         H* h = g->hs[i]; const Options& o = h->opt;
-        const double M = info[i].M, theta = info[i].theta;
         if (ls_it[i] >= o.max_residual_line_search) rc[i] = std::max(rc[i], (int)CALIPSO_WARN_LINE_SEARCH);
-        if (!switching_condition(step_size[i], dd[i], o.merit_exponent, theta, o.violation_exponent, 1.0) ||
-            !armijo(M, Mh[i], dd[i], step_size[i], o.armijo_tolerance, o.machine_tolerance))
-            augment_filter(h, (1.0 - o.violation_tolerance) * theta, M - o.merit_tolerance * theta);   // filter.jl:81-89
+        augment_filter_after_step(h, info[i].theta, info[i].M, Mh[i], dd[i], step_size[i]);
         info[i].step_size = step_size[i]; info[i].Mh = Mh[i]; info[i].thetah = thetah[i];
         h->stats.newton_steps += 1;
     }
@@ -543,6 +511,36 @@ static int g_check_options(G* g) {
             g->base->err = "group members must share opt.scaling_line_search and opt.max_cone_line_search";
             return CALIPSO_ERR_ARGUMENT;
         }
+    return CALIPSO_OK;
+}
+
+// What a group call overrides on the base handle, put back however the call leaves.
+struct GroupCall {
+    G* g;
+    bool entered = false;
+    ~GroupCall() { if (entered) { g->base->cur = nullptr; g_restore_band(g); } }
+};
+// The entry of a group call: the members' options agree, every member has an evaluator (callbacks_count: a host callback of calipso_hip_group_set_evaluators is one;
+// `missing`: the error text otherwise), the members' own streams have drained, the band and blocks of the group's launches are in force and no Hessian is dirty.
+// all = every member's index.
+static int g_enter(G* g, GroupCall& call, bool callbacks_count, const char* missing, Set& all) {
+    H* s = g->base;
+    CK(hipSetDevice(s->device));
+    (void)hipGetLastError();      // (launch_errors: this call's launches only)
+    { const int oc = g_check_options(g); if (oc < 0) return oc; }
+    for (size_t i = 0; i < g->hs.size(); ++i) {
+        H* h = g->hs[i];
+        const bool callback = callbacks_count && i < g->evals.size() && g->evals[i];
+        if (!h->qp.attached && !h->dev_eval && !h->dev_block_eval && !callback) { s->err = missing; return CALIPSO_ERR_ARGUMENT; }
+        if (h != s) CK(hipStreamSynchronize(h->stream));   // uploads made through the member's own stream are complete
+        all.push_back((int)i);
+    }
+    g_effective_band(g);
+    { const int brc = g_effective_blocks(g); if (brc < 0) { g_restore_band(g); return brc; } }
+    call.entered = true;
+    Set dirty;                    // Lsym of the members whose Hessian changed
+    for (int i : all) if (g->hs[i]->hessian_dirty) dirty.push_back(i);
+    if (!dirty.empty()) { g_activate(g, dirty); launch_symmetrize(s); for (int i : dirty) g->hs[i]->hessian_dirty = false; }
     return CALIPSO_OK;
 }
 
@@ -614,37 +612,16 @@ int32_t calipso_hip_group_destroy(calipso_hip_group* g) {
 int32_t calipso_hip_group_newton_step(calipso_hip_group* g, int32_t advance, double* info_out, int32_t* status) {
     if (!g || !g->base || g->dead) return CALIPSO_ERR_ARGUMENT;
     H* s = g->base;
-    const Dims& d = s->d;
     const size_t B = g->hs.size();
-    CK(hipSetDevice(s->device));
-    (void)hipGetLastError();      // (launch_errors: this call's launches only)
-    { const int oc = g_check_options(g); if (oc < 0) return oc; }
     Set all;
-    for (size_t i = 0; i < B; ++i) {
-        H* h = g->hs[i];
-        if (!h->qp.attached && !h->dev_eval && !h->dev_block_eval) { s->err = "calipso_hip_group_newton_step needs a device evaluator on every member (calipso_hip_qp_attach or calipso_hip_set_device_evaluator)"; return CALIPSO_ERR_ARGUMENT; }
-        if (h != s) CK(hipStreamSynchronize(h->stream));   // uploads made through the member's own stream are complete
-        all.push_back((int)i);
-    }
-    g_effective_band(g);
-    { const int brc = g_effective_blocks(g); if (brc < 0) { g_restore_band(g); return brc; } }
-    struct Finally { G* g; ~Finally() { g->base->cur = nullptr; g_restore_band(g); } } fin{g};
-    {   // Lsym of the members whose Hessian changed
-        Set dirty;
-        for (int i : all) if (g->hs[i]->hessian_dirty) dirty.push_back(i);
-        if (!dirty.empty()) { g_activate(g, dirty); launch_symmetrize(s); for (int i : dirty) g->hs[i]->hessian_dirty = false; }
-    }
+    GroupCall call{g};
+    if (const int rc0 = g_enter(g, call, false, "calipso_hip_group_newton_step needs a device evaluator on every member (calipso_hip_qp_attach or calipso_hip_set_device_evaluator)", all)) return rc0;
     std::vector<Scalars> saved_sc(B);
     std::vector<std::vector<double>> ft(B), fm(B);
     std::vector<calipso::i64> fi(B, 0);
     g_activate(g, all);
     if (!advance) {
-        {   // (one launch, as for a single handle: api.hip)
-            double* const dst[4] = {s->saved_point, s->saved_g, s->saved_h, s->dscal + 32};
-            const double* const src[4] = {s->solution, s->g, s->hc, s->dscal};
-            const size_t n[4] = {(size_t)d.N, (size_t)d.ne, (size_t)d.nc, 2};
-            copy4_d(s, dst, src, n);
-        }
+        copy_step_state(s, true);
         for (int i : all) { H* h = g->hs[i]; saved_sc[i] = h->sc; ft[i] = h->filter_theta; fm[i] = h->filter_merit; fi[i] = h->filter_index; }
     }
     std::vector<IterInfo> info(B);
@@ -655,18 +632,12 @@ int32_t calipso_hip_group_newton_step(calipso_hip_group* g, int32_t advance, dou
     if (e < 0) return e;
     if (!advance) {
         g_activate(g, all);
-        {
-            double* const dst[4] = {s->solution, s->g, s->hc, s->dscal};
-            const double* const src[4] = {s->saved_point, s->saved_g, s->saved_h, s->dscal + 32};
-            const size_t n[4] = {(size_t)d.N, (size_t)d.ne, (size_t)d.nc, 2};
-            copy4_d(s, dst, src, n);
-        }
+        copy_step_state(s, false);
         launch_cone(s, s->solution, CALIPSO_CONE_PRODUCT);
         for (int i : all) {
             H* h = g->hs[i];
             h->filter_theta = ft[i]; h->filter_merit = fm[i]; h->filter_index = fi[i];
-            const double keep_ep = h->sc.ep, keep_ed = h->sc.ed;
-            h->sc = saved_sc[i]; h->sc.ep = keep_ep; h->sc.ed = keep_ed;
+            restore_scalars_keeping_regularization(h->sc, saved_sc[i]);
         }
     }
     SYNC();
@@ -693,27 +664,9 @@ int32_t calipso_hip_group_solve(calipso_hip_group* g, int32_t* result) {
     H* s = g->base;
     const Dims& d = s->d;
     const size_t B = g->hs.size();
-    CK(hipSetDevice(s->device));
-    (void)hipGetLastError();      // (launch_errors: this call's launches only)
-    { const int oc = g_check_options(g); if (oc < 0) return oc; }
     Set all;
-    for (size_t i = 0; i < B; ++i) {
-        H* h = g->hs[i];
-        if (!h->qp.attached && !h->dev_eval && !h->dev_block_eval && (i >= g->evals.size() || !g->evals[i])) {
-            s->err = "calipso_hip_group_solve: member without a device evaluator and without a callback (calipso_hip_group_set_evaluators)";
-            return CALIPSO_ERR_ARGUMENT;
-        }
-        if (h != s) CK(hipStreamSynchronize(h->stream));
-        all.push_back((int)i);
-    }
-    g_effective_band(g);
-    { const int brc = g_effective_blocks(g); if (brc < 0) { g_restore_band(g); return brc; } }
-    struct Finally { G* g; ~Finally() { g->base->cur = nullptr; g_restore_band(g); } } fin{g};
-    {
-        Set dirty;
-        for (int i : all) if (g->hs[i]->hessian_dirty) dirty.push_back(i);
-        if (!dirty.empty()) { g_activate(g, dirty); launch_symmetrize(s); for (int i : dirty) g->hs[i]->hessian_dirty = false; }
-    }
+    GroupCall call{g};
+    if (const int rc0 = g_enter(g, call, true, "calipso_hip_group_solve: member without a device evaluator and without a callback (calipso_hip_group_set_evaluators)", all)) return rc0;
     const uint32_t eval0 = CALIPSO_EVAL_EQUALITY | CALIPSO_EVAL_CONE;
     Set cold;
     for (int i : all) { g->hs[i]->stats = Stats(); if (g->hs[i]->opt.warmstart == 0.0) cold.push_back(i); }
@@ -723,11 +676,10 @@ int32_t calipso_hip_group_solve(calipso_hip_group* g, int32_t* result) {
         launch_init_point(s);
     }
     for (int i : all) {
-        H* h = g->hs[i]; Options& o = h->opt; Scalars& sc = h->sc;
-        sc.kappa = o.central_path_initial; sc.tau = std::max(0.99, 1.0 - sc.kappa);       // initialize.jl:38-42
-        sc.rho = o.penalty_initial;                                                       // :44-48
+        H* h = g->hs[i];
+        initial_scalars(h->opt, h->sc);                                                   // initialize.jl:38-48
         g_activate(g, Set{i});
-        fill_d(s, s->lambda, d.ne, o.dual_initial);
+        fill_d(s, s->lambda, d.ne, h->opt.dual_initial);
         filter_reset(h);                                                                  // solve.jl:95
     }
     {
@@ -774,16 +726,12 @@ int32_t calipso_hip_group_solve(calipso_hip_group* g, int32_t* result) {
             if (inner_done) upd.push_back(i); else next.push_back(i);
         }
         if (!upd.empty()) {                                                                // outer updates  :356-371
-            for (int i : upd) {
-                H* h = g->hs[i]; const Options& o = h->opt; Scalars& sc = h->sc;
-                sc.kappa = std::max(o.residual_tolerance / 10.0, std::min(o.central_path_scaling * sc.kappa, std::pow(sc.kappa, o.central_path_exponent)));
-                sc.tau = std::max(0.99, 1.0 - sc.kappa);
-            }
+            for (int i : upd) central_path_update(g->hs[i]->opt, g->hs[i]->sc);
             g_activate(g, upd);                                                            // lambda += rho r with the OLD rho (:362-365)
             launch_lambda_update(s);
             for (int i : upd) {
-                H* h = g->hs[i]; const Options& o = h->opt; Scalars& sc = h->sc;
-                sc.rho = std::min(std::max(o.penalty_scaling * sc.rho, 1.0 / sc.kappa), o.max_penalty);
+                H* h = g->hs[i]; const Options& o = h->opt;
+                penalty_update(o, h->sc);
                 filter_reset(h);
                 if (h->cb_outer) { SYNC(); h->cb_outer(h->cb_user, h); }
                 outer[i] += 1; inner[i] = 1;

@@ -1,9 +1,7 @@
 // host_logic.hpp — host-side pieces of the inner iteration shared by the single-handle driver (api.hip) and the group driver
-// (group.hip): inertia test, filter, line-search predicates.  Pure C++ on the handle's host state; nothing here touches the device.
+// (group.hip) that need the handle: the waits, the filter and its storage, IterInfo.  The decisions themselves are step_decisions.hpp (through internal.hpp).
 #pragma once
-#include <algorithm>
 #include <chrono>
-#include <cmath>
 #include <cstdint>
 #include <thread>
 
@@ -35,17 +33,6 @@ template <typename Ready, typename Alive> static inline bool host_wait(Ready rea
     }
 }
 
-static inline bool inertia_ok(const H* s, const int64_t in[3]) { return in[0] == s->d.nx && in[1] == s->d.ne + s->d.nc && in[2] == 0; }   // inertia.jl:7-11
-
-
-// first trial index k in 0..max_cone_line_search whose violation bit is clear (cones.hip: violation_masks), -1 if none: the
-// reference raises "cone search failure" once cone_iteration exceeds max_cone_line_search (solve.jl:204-221)
-static inline int first_feasible_trial(const int* mask, calipso::i64 max_cone_line_search) {
-    const int nk = (int)std::min<calipso::i64>(max_cone_line_search + 1, calipso::CONE_MASK_TRIALS);
-    for (int k = 0; k < nk; ++k) if (!(mask[k >> 5] & (1 << (k & 31)))) return k;
-    return -1;
-}
-
 // ---- filter (filter.jl:1-89), host side ------------------------------------------------------------------------------------
 static inline void filter_reset(H* s) {
     for (calipso::i64 i = 0; i < s->filter_index; ++i) { s->cache_theta[i] = 1.0e8; s->cache_merit[i] = 1.0e8; }
@@ -53,9 +40,7 @@ static inline void filter_reset(H* s) {
     s->filter_index = 0;
 }
 static inline bool check_filter(const H* s, double theta, double merit) {
-    for (size_t i = 0; i < s->filter_theta.size(); ++i)
-        if (!(theta < s->filter_theta[i] || merit < s->filter_merit[i])) return false;
-    return true;
+    return calipso::filter_accepts(s->filter_theta.data(), s->filter_merit.data(), (calipso::i64)s->filter_theta.size(), theta, merit);
 }
 static inline void filter_resize(H* s, calipso::i64 n) {
     if (n < 1) n = 1;
@@ -85,24 +70,17 @@ static inline bool augment_filter(H* s, double theta, double merit) {
     }
     return true;
 }
-// line_search.jl:2-18 with d = dot(merit_gradient, step.primals) precomputed on the device
-static inline bool switching_condition(double step_size, double dd, double merit_exponent, double violation, double violation_exponent, double reg) {
-    return dd < 0.0 && step_size * std::pow(-dd, merit_exponent) > reg * std::pow(violation, violation_exponent);
+// behind a step's line search: augment_filter!(solver, ...)  filter.jl:81-89
+static inline void augment_filter_after_step(H* s, double theta, double M, double Mh, double dd, double step_size) {
+    const calipso::Options& o = s->opt;
+    if (calipso::filter_needs_augment(o, theta, M, Mh, dd, step_size)) augment_filter(s, (1.0 - o.violation_tolerance) * theta, M - o.merit_tolerance * theta);
 }
-static inline bool sufficient_progress(double v, double vc, double m, double mc, double vt, double mt, double mach) {
-    return vc - 10.0 * mach * std::fabs(v) <= (1.0 - vt) * v || mc - 10.0 * mach * std::fabs(m) <= m - mt * v;
-}
-static inline bool armijo(double m, double mc, double dd, double step_size, double at, double mach) {
-    return mc - m - 10.0 * mach * std::fabs(m) <= at * step_size * dd;
-}
-
 
 struct IterInfo {
     double step_size = 1.0, step_size_t = 1.0, M = 0.0, Mh = 0.0, theta = 0.0, thetah = 0.0;
     int rounds = 0;
     int64_t nfact = 0;
     int exit_kind = 0;   // 0 stepped, 1 outer convergence, 2 inner convergence
-    double residual_violation = 0, optimality = 0, slack_violation = 0;
 };
 
 #define EV(i) (void)hipEventRecord(s->ev[i], s->stream)

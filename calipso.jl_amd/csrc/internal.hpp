@@ -10,6 +10,7 @@
 
 #include "../../include/calipso_hip.h"
 #include "../../include/calipso_options.hpp"     // calipso::i64, calipso::Options
+#include "step_decisions.hpp"                    // calipso::Scalars, CONE_MASK_TRIALS (and the host's decisions on them: plain C++)
 
 namespace calipso {
 
@@ -41,14 +42,6 @@ inline size_t wform_offset(int NP, int tb, int kb) {
     for (int b = 0; b < kb; ++b) { const int k0 = b * tb, w = tb < NP - k0 ? tb : NP - k0; off += (size_t)(NP - k0 - w) * (size_t)w; }
     return off;
 }
-constexpr int CONE_MASK_WORDS = 26;                     // icount[6..31] (slack) and icount[32..57] (slack dual): one bit per trial step size
-constexpr int CONE_MASK_TRIALS = 32 * CONE_MASK_WORDS;  // => max_cone_line_search <= 831
-
-// scalars the host owns and passes to kernels by value (solver.jl:81-127)
-struct Scalars {
-    double kappa = 0.1, tau = 0.99, rho = 10.0, ep = 0.0, ep_last = 0.0, ed = 0.0;
-};
-
 // Which problem instances a launch covers.  Every handle carves all its device buffers out of ONE slab with the same layout, so
 // "buffer X of instance k" = "buffer X of the base handle" + delta[k] doubles, for every X.  Kernels take this by value, use
 // blockIdx.z as the instance slot and shift their pointers (device_utils.hpp: inst_shift).  A single handle is a batch of one
@@ -445,6 +438,7 @@ void fill_d(calipso_hip_solver* s, double* p, size_t n, double v);
 void fill_i(calipso_hip_solver* s, int* p, size_t n, int v);
 void copy_d(calipso_hip_solver* s, double* dst, const double* src, size_t n);
 void copy4_d(calipso_hip_solver* s, double* const dst[4], const double* const src[4], const size_t n[4]);   // four copies, one launch
+void copy_step_state(calipso_hip_solver* s, bool save);   // the save / restore of a step that does not advance (copy4_d)
 }  // namespace calipso
 
 #define CK(call)                                                        \

@@ -604,7 +604,7 @@ void launch_first_candidate_batch(calipso_hip_solver* s, const double* a_s, cons
 void launch_first_candidate(calipso_hip_solver* s, double a_s, double a_t) { launch_first_candidate_batch(s, &a_s, &a_t); }
 
 // The same launch with the step sizes taken from the cone-search masks ON THE DEVICE (a single handle: api.hip queues the first candidate behind the cone search without
-// a host round trip in between).  Every workgroup repeats what the host does with the published masks (host_logic.hpp: first_feasible_trial, then api.hip's repeated
+// a host round trip in between).  Every workgroup repeats what the host does with the published masks (step_decisions.hpp: cone_step_sizes — first_feasible_trial, then the repeated
 // multiplication by scaling_line_search — the same IEEE operations, so the host's step sizes are these to the bit); no feasible trial: NaN (the host sees the same masks
 // and raises "cone search failure").
 __global__ __launch_bounds__(RT) void k_first_candidate_masks(Batch bt, Dims d, const double* __restrict__ sol, const double* __restrict__ step, double* __restrict__ cand,
@@ -1471,6 +1471,14 @@ void copy4_d(calipso_hip_solver* s, double* const dst[4], const double* const sr
     if (!nmax) return;
     const BatchSc B = batch_of(s);
     hipLaunchKernelGGL(k_copy4_d, dim3((unsigned)((nmax + 255) / 256), 4, B.b.n), dim3(256), 0, s->stream, B.b, c);
+}
+// a step that does not advance: point, g, h and dscal[0..1] to the handle's saved copies before it (save) and back behind it (on a group's base handle: for every
+// active member)
+void copy_step_state(calipso_hip_solver* s, bool save) {
+    double* const now[4] = {s->solution, s->g, s->hc, s->dscal};
+    double* const kept[4] = {s->saved_point, s->saved_g, s->saved_h, s->dscal + 32};
+    const size_t n[4] = {(size_t)s->d.N, (size_t)s->d.ne, (size_t)s->d.nc, 2};
+    copy4_d(s, save ? kept : now, save ? now : kept, n);
 }
 void copy_d(calipso_hip_solver* s, double* dst, const double* src, size_t n) {
     if (!n) return;

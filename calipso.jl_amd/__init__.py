@@ -358,6 +358,13 @@ class Solver:
     def differentiate(self):
         self._check(self._L.calipso_hip_differentiate(self._h, self._cb, None), "differentiate")
 
+    def differentiate_info(self):
+        """report of the last differentiate() (calipso_hip_differentiate_info; set_option("differentiate_refinement", 1) turns the correction rounds on):
+        dict(columns, rounds (largest over the columns), failed_columns (did not meet the stopping test), final_norm (largest over the columns)); zeros when no round ran"""
+        out = np.zeros(4)
+        self._check(self._L.calipso_hip_differentiate_info(self._h, _pd(out)), "differentiate_info")
+        return dict(columns=int(out[0]), rounds=int(out[1]), failed_columns=int(out[2]), final_norm=float(out[3]))
+
     def set_device_evaluator(self, fn_ptr, user=None):
         """install a device-side evaluator (calipso_device_eval_fn, include/calipso_hip.h): `fn_ptr` is the C function's address (e.g.
         ctypes.cast(lib.sym, c_void_p)), `user` its opaque pointer; solve_b / differentiate then never call back into Python"""

@@ -316,9 +316,9 @@ int32_t calipso_hip_destroy(H* s) {
     if (s->spS_inv) { (void)hipFree(s->spS_inv); s->spS_inv = nullptr; }
     if (s->d_reach) { (void)hipFree(s->d_reach); s->d_reach = nullptr; }
     calipso::blocks_release(s);
-    double* dp[] = {s->slab, s->Kdense, s->multi_rhs, s->dsym_multi, s->evalL, s->evalZ};
+    double* dp[] = {s->slab, s->Kdense, s->multi_rhs, s->dsym_multi, s->evalL, s->evalZ, s->diff_refine};
     for (double* p : dp) if (p) (void)hipFree(p);
-    int* ip[] = {s->cone.soc_start, s->cone.soc_dim, s->cone.soc_woff, s->cone.entry_soc, s->cone.wide, s->zgrp, s->gate};
+    int* ip[] = {s->cone.soc_start, s->cone.soc_dim, s->cone.soc_woff, s->cone.entry_soc, s->cone.wide, s->zgrp, s->gate, s->diff_active};
     for (int* p : ip) if (p) (void)hipFree(p);
     if (s->hscal) (void)hipHostFree(s->hscal);
     if (s->hicount) (void)hipHostFree(s->hicount);
@@ -389,7 +389,8 @@ static bool find_field(H* s, const std::string& name, Field& f) {
     IO ios[] = {{"opt.max_outer_iterations", &o.max_outer_iterations}, {"opt.max_residual_iterations", &o.max_residual_iterations},
                 {"opt.max_residual_line_search", &o.max_residual_line_search}, {"opt.max_cone_line_search", &o.max_cone_line_search},
                 {"opt.iterative_refinement", &o.iterative_refinement}, {"opt.max_iterative_refinement", &o.max_iterative_refinement},
-                {"opt.min_iterative_refinement", &o.min_iterative_refinement}, {"opt.solve_block", &s->solve_block}, {"opt.solve_wform", &s->solve_wform}};
+                {"opt.min_iterative_refinement", &o.min_iterative_refinement}, {"opt.solve_block", &s->solve_block}, {"opt.solve_wform", &s->solve_wform},
+                {"opt.differentiate_refinement", &s->differentiate_refinement}};
     for (auto& io : ios)
         if (name == io.n) { f.host = (double*)io.p; f.len = -1; return true; }   // len -1 marks an int64 slot
     return false;
@@ -418,6 +419,8 @@ int32_t calipso_hip_set_field(H* s, const char* name, const double* data, int64_
             if (v != 0 && v != 1) return fail_arg(s, "opt.solve_wform must be 0 or 1");
             if (v != s->solve_wform) { CK(hipSetDevice(s->device)); CK(hipStreamSynchronize(s->stream)); calipso::ldl_drop_graphs(s); }
         }
+        // not an option of the reference either: correction rounds on the columns of differentiate! (calipso_hip_differentiate)
+        if (nm == "opt.differentiate_refinement" && ((v != 0 && v != 1) || data[0] != (double)v)) return fail_arg(s, "opt.differentiate_refinement must be 0 or 1");
         *(calipso::i64*)f.host = v;
         return CALIPSO_OK;
     }
@@ -1252,22 +1255,11 @@ int32_t calipso_hip_stats(H* s, int64_t out[8]) {
     return CALIPSO_OK;
 }
 
-// differentiate!  differentiate.jl:1-61
-int32_t calipso_hip_differentiate(H* s, calipso_eval_fn eval, void* user) {
-    if (!s) return CALIPSO_ERR_ARGUMENT;
+// the condensed solve of differentiate.jl:29-58 for p right-hand-side columns `rhs` (N apart) through the current factors: out = scale * H^-1 rhs (as far as the
+// condensed, constraint-first solve gets).  The reference solves one condensed system per parameter column; here all columns go through the same factors together:
+// condensation per column, mat-vecs as GEMMs, block triangular solves as TRSMs
+static int solve_columns(H* s, const double* rhs, int p, double* out, double scale) {
     const Dims& d = s->d;
-    if (d.np == 0) return CALIPSO_OK;
-    int rc = evaluate(s, eval, user, 0, CALIPSO_EVAL_OBJECTIVE_JACOBIAN_PARAMETERS | CALIPSO_EVAL_EQUALITY_JACOBIAN_PARAMETERS |
-                                           CALIPSO_EVAL_EQUALITY_DUAL_JACOBIAN_PARAMETERS | CALIPSO_EVAL_CONE_JACOBIAN_PARAMETERS |
-                                           CALIPSO_EVAL_CONE_DUAL_JACOBIAN_PARAMETERS);
-    if (rc < 0) return rc;
-    int64_t in[3];
-    rc = do_factorize(s, in);                      // :13-20 (same regularisation as the last search direction)
-    if (rc < 0) return rc;
-    launch_jacobian_parameters(s);                 // :23
-    // :29-58 — the reference solves one condensed system per parameter column (no refinement); here all np columns go through
-    // the same factors together: condensation per column, mat-vecs as GEMMs, block triangular solves as TRSMs
-    const int p = d.np;
     const size_t NPd = d.NP, M = d.m, n = d.n;
     if (!s->multi_rhs) {
         if (dalloc(s, &s->multi_rhs, (n + 3 * NPd + 2 * M) * (size_t)p) || dalloc(s, &s->dsym_multi, n * (size_t)p)) return CALIPSO_ERR_HIP;
@@ -1278,7 +1270,7 @@ int32_t calipso_hip_differentiate(H* s, calipso_eval_fn eval, void* user) {
     double* zM = uM + NPd * p;                     // NP x p
     double* t1M = zM + NPd * p;                    // m  x p   Omega b_m
     double* t2M = t1M + M * p;                     // m  x p   [gx; hx] dx
-    launch_residual_symmetric_multi(s, s->jacobian_parameters, p, rsymM, xbufM, t1M);
+    launch_residual_symmetric_multi(s, rhs, p, rsymM, xbufM, t1M);
     // (a handle that works on stage blocks — every structured handle — takes the products block by block, all columns in one launch each; its factor lives in the
     // fronts of the multifrontal LDL^T, which take all columns through the tree together: trsm_multi)
     if (d.m && !blocks_gemm_t(s, t1M, d.m, xbufM, d.NP, p, 1.0)) {
@@ -1290,8 +1282,117 @@ int32_t calipso_hip_differentiate(H* s, calipso_eval_fn eval, void* user) {
         if (s->compact) { s->err = "calipso_hip_differentiate: the block products are not available on this structured handle"; return CALIPSO_ERR_HIP; }
         gemm(s, d.m, p, d.nx, 1.0, s->Z, d.m, false, xbufM, d.NP, 0.0, t2M, d.m);          // [gx; hx] dx
     }
-    launch_recover_multi(s, s->jacobian_parameters, p, rsymM, xbufM, t2M, s->solution_sensitivity, -1.0);   // :54-56 sensitivity = -step
+    launch_recover_multi(s, rhs, p, rsymM, xbufM, t2M, out, scale);
+    return CALIPSO_OK;
+}
+
+// E = R_theta - H X for all p columns with the unreduced, matrix-free H (what k_refine_local / k_refine_x form for one vector), and their infinity norms.  The products
+// land in workspace of solve_columns that is free between two solves: [gx; hx] X_x in its t2 (m x p), Lxx X_x + [gx; hx]' X_yz in its forward-substitution scratch
+static int residual_columns(H* s, const double* X, int p, double* E, double* part, double* norms) {
+    const Dims& d = s->d;
+    const size_t NPd = d.NP, M = d.m, n = d.n;
+    double* hxM = s->multi_rhs + (n + NPd) * (size_t)p;                 // NP x p (rows < nx are used)
+    double* zxM = s->multi_rhs + (n + 3 * NPd + M) * (size_t)p;         // m x p
+    if (!blocks_gemm_l(s, X, d.N, hxM, d.NP, p)) {
+        if (s->compact) { s->err = "calipso_hip_differentiate: the Hessian block product is not available on this structured handle"; return CALIPSO_ERR_HIP; }
+        gemm(s, d.nx, p, d.nx, 1.0, s->Lxx, d.nx, false, X, d.N, 0.0, hxM, d.NP);           // Lxx X_x
+    }
+    if (d.m) {
+        if (!blocks_gemm_t(s, X + d.oy(), d.N, hxM, d.NP, p, 1.0)) {                        // + [gx; hx]' X_yz (y and z are adjacent in a Point)
+            if (s->compact) { s->err = "calipso_hip_differentiate: the block products are not available on this structured handle"; return CALIPSO_ERR_HIP; }
+            gemm(s, d.nx, p, d.m, 1.0, s->Z, d.m, true, X + d.oy(), d.N, 1.0, hxM, d.NP);
+        }
+        if (!blocks_gemm_n(s, X, d.N, zxM, d.m, p)) {                                       // [gx; hx] X_x
+            if (s->compact) { s->err = "calipso_hip_differentiate: the block products are not available on this structured handle"; return CALIPSO_ERR_HIP; }
+            gemm(s, d.m, p, d.nx, 1.0, s->Z, d.m, false, X, d.N, 0.0, zxM, d.m);
+        }
+    }
+    launch_refine_rows_multi(s, X, s->jacobian_parameters, zxM, p, E, part);
+    launch_refine_x_multi(s, X, s->jacobian_parameters, hxM, d.NP, p, E, part, norms);
+    return CALIPSO_OK;
+}
+
+// differentiate! with "opt.differentiate_refinement" = 1 on a handle without second-order cones: the unrefined pass kept as the step matrix X (sensitivity = -X), then
+// the loop of iterative_refinement.jl:14-44 over all columns at once — residual against the unreduced H, column norms (one read-back of p doubles per round), the
+// correction through the same factors and the same multi-column pipeline, X(:, j) += correction(:, j) for the columns still active.  The per-column decisions are
+// sensitivity_columns.hpp's (refine_next with the handle's options).  A column that fails its test keeps its last iterate and is counted (differentiate! has no fallback);
+// a column already within the tolerance takes the round min_iterative_refinement asks for only if that does not raise its norm (its iterate is saved and put back).
+static int differentiate_refined(H* s) {
+    const Dims& d = s->d;
+    const int p = d.np;
+    const size_t Np = (size_t)d.N * p, nparts = (size_t)refine_multi_parts(s);
+    if (!s->diff_refine) {
+        const size_t bytes = (4 * Np + (nparts + 1) * (size_t)p) * sizeof(double), ibytes = 2 * (size_t)p * sizeof(int);
+        if (hipMalloc((void**)&s->diff_refine, bytes) != hipSuccess || hipMalloc((void**)&s->diff_active, ibytes) != hipSuccess) {
+            (void)hipGetLastError();
+            if (s->diff_refine) { (void)hipFree(s->diff_refine); s->diff_refine = nullptr; }
+            s->diff_active = nullptr;
+            char buf[192];
+            snprintf(buf, sizeof buf, "calipso_hip_differentiate: the workspace of the correction rounds (%zu + %zu bytes for %d columns) could not be allocated", bytes, ibytes, p);
+            s->err = buf;
+            return CALIPSO_ERR_HIP;
+        }
+        s->scratch_bytes += bytes + ibytes;
+        s->diff_norms.assign((size_t)p, 0.0);
+    }
+    double* X = s->diff_refine; double* E = X + Np; double* C = E + Np; double* Xsave = C + Np; double* part = Xsave + Np; double* norms = part + nparts * (size_t)p;
+    int rc = solve_columns(s, s->jacobian_parameters, p, X, 1.0);
+    if (rc < 0) return rc;
+    SensitivityColumns& cols = s->diff_cols;
+    cols.begin(p);
+    for (;;) {
+        rc = residual_columns(s, X, p, E, part, norms);
+        if (rc < 0) return rc;
+        CK(hipMemcpyAsync(s->diff_norms.data(), norms, sizeof(double) * (size_t)p, hipMemcpyDeviceToHost, s->stream));
+        if (launch_errors(s, "a kernel launch of differentiate!'s correction rounds was refused")) return CALIPSO_ERR_HIP;
+        SYNC();
+        cols.judge(s->opt, s->diff_norms.data());
+        if (cols.n_restore) {      // a round that only min_iterative_refinement asked for raised these columns' norms: they go back to the iterate they had
+            CK(hipMemcpyAsync(s->diff_active + p, cols.restore.data(), sizeof(int) * (size_t)p, hipMemcpyHostToDevice, s->stream));
+            launch_restore_masked(s, s->diff_active + p, Xsave, p, X);
+            SYNC();                // (cols.restore is rewritten by the next judge)
+        }
+        if (cols.finished()) break;
+        CK(hipMemcpyAsync(s->diff_active, cols.active.data(), sizeof(int) * (size_t)p, hipMemcpyHostToDevice, s->stream));
+        rc = solve_columns(s, E, p, C, 1.0);
+        if (rc < 0) return rc;
+        launch_accumulate_masked(s, s->diff_active, C, p, X, Xsave);
+    }
+    launch_scale_into(s, X, s->solution_sensitivity, Np, -1.0);      // :54-56 sensitivity = -step
+    cols.report(s->diff_info);
+    return CALIPSO_OK;
+}
+
+// differentiate!  differentiate.jl:1-61
+int32_t calipso_hip_differentiate(H* s, calipso_eval_fn eval, void* user) {
+    if (!s) return CALIPSO_ERR_ARGUMENT;
+    const Dims& d = s->d;
+    (void)hipGetLastError();      // (launch_errors: this call's launches only, as calipso_hip_solve)
+    s->diff_info[0] = (double)d.np; s->diff_info[1] = s->diff_info[2] = s->diff_info[3] = 0.0;
+    if (d.np == 0) return CALIPSO_OK;
+    int rc = evaluate(s, eval, user, 0, CALIPSO_EVAL_OBJECTIVE_JACOBIAN_PARAMETERS | CALIPSO_EVAL_EQUALITY_JACOBIAN_PARAMETERS |
+                                           CALIPSO_EVAL_EQUALITY_DUAL_JACOBIAN_PARAMETERS | CALIPSO_EVAL_CONE_JACOBIAN_PARAMETERS |
+                                           CALIPSO_EVAL_CONE_DUAL_JACOBIAN_PARAMETERS);
+    if (rc < 0) return rc;
+    int64_t in[3];
+    rc = do_factorize(s, in);                      // :13-20 (same regularisation as the last search direction)
+    if (rc < 0) return rc;
+    launch_jacobian_parameters(s);                 // :23
+    // :29-58 — one condensed solve for all np columns, unrefined as the reference's (its QDLDL works on the (nx + ne + nc) symmetric matrix and does not need more).
+    // "opt.differentiate_refinement": correction rounds on all columns (differentiate_refined) — not with second-order cones, where the reference's answer IS the
+    // unrefined solve with its triu-symmetrised cone blocks (quirk B-3: refining would move away from it, towards H^-1; the batch kernel does the same), and not
+    // with iterative_refinement = 0
+    if (s->differentiate_refinement && s->opt.iterative_refinement && d.n_soc == 0) rc = differentiate_refined(s);
+    else rc = solve_columns(s, s->jacobian_parameters, d.np, s->solution_sensitivity, -1.0);   // :54-56 sensitivity = -step
+    if (rc < 0) return rc;
     SYNC();
+    return CALIPSO_OK;
+}
+
+// [columns, correction rounds run (largest over the columns), columns that did not meet the stopping test, largest final column norm] of the last differentiate!
+int32_t calipso_hip_differentiate_info(H* s, double out[4]) {
+    if (!s || !out) return CALIPSO_ERR_ARGUMENT;
+    for (int i = 0; i < 4; ++i) out[i] = s->diff_info[i];
     return CALIPSO_OK;
 }
 

@@ -11,6 +11,7 @@
 #include "../../include/calipso_hip.h"
 #include "../../include/calipso_options.hpp"     // calipso::i64, calipso::Options
 #include "step_decisions.hpp"                    // calipso::Scalars, CONE_MASK_TRIALS (and the host's decisions on them: plain C++)
+#include "sensitivity_columns.hpp"               // calipso::SensitivityColumns (the column bookkeeping of differentiate!'s correction rounds: plain C++)
 
 namespace calipso {
 
@@ -151,7 +152,7 @@ struct calipso_hip_solver {
     void* dev_eval_user = nullptr;
     calipso_device_block_eval_fn dev_block_eval = nullptr;   // structured handles: the evaluator writes the packed blocks (no dense scratch)
     void* dev_block_eval_user = nullptr;
-    size_t scratch_bytes = 0;                    // dense scratch of a structured handle with a dense-layout device evaluator (evalL / evalZ)
+    size_t scratch_bytes = 0;                    // dense scratch of a structured handle with a dense-layout device evaluator (evalL / evalZ) + the workspace of differentiate!'s correction rounds (diff_refine)
     bool rhs_ahead = false, rhs_joined = false;   // the operands of the first condensed solve were queued on the second stream during this factorisation (ldl.hip: ldl_rhs_stream) / the main stream has joined it
     double *evalL = nullptr, *evalZ = nullptr;   // structured handle with a device evaluator: dense scratch (nx^2, m nx) the evaluator writes; packed into the blocks behind it
     std::map<std::string, double*> optd;
@@ -239,6 +240,14 @@ struct calipso_hip_solver {
     std::vector<double> hparams;
     double* multi_rhs = nullptr;  // workspace of the multi-right-hand-side solve of differentiate! (allocated on demand)
     double* dsym_multi = nullptr; // n * np
+    // "opt.differentiate_refinement" (not an option of the reference: differentiate! there does not refine; a handle-level value like solve_block): 1 = the correction
+    // rounds of iterative_refinement.jl:14-44 on every column of differentiate! (api.hip: calipso_hip_differentiate); inert on a handle with second-order cones
+    calipso::i64 differentiate_refinement = 0;
+    double* diff_refine = nullptr;     // its workspace, allocated on the first refined call and kept: X, E, C, Xsave (N x np each), the partial norms, the column norms
+    int* diff_active = nullptr;        // 2 np: the device's copies of SensitivityColumns::active and ::restore
+    calipso::SensitivityColumns diff_cols;
+    std::vector<double> diff_norms;    // host side of the per-round read-back (np)
+    double diff_info[4] = {0, 0, 0, 0};   // calipso_hip_differentiate_info of the last differentiate!
     void* scatter_aux = nullptr;  // scatter.hip: registered sparsity patterns of the evaluate! scatter
     void* ldl_aux = nullptr;      // ldlsolver.hip: staging of the caller's CSC matrix (handles made by calipso_hip_ldl_create)
     void* lfac_aux = nullptr;     // lfac.hip: plan and buffers of the left-looking schedule (one dense system alone)
@@ -355,6 +364,7 @@ void blocks_mirror(calipso_hip_solver* s, bool l, bool zg, bool zh);            
 bool blocks_gemv_n(calipso_hip_solver* s, int kind, const double* x, double* y, double alpha, double beta);
 bool blocks_gemv_t(calipso_hip_solver* s, int kind, const double* u1, const double* u2, double* y1, double* y2, double alpha, double beta);
 bool blocks_schur(calipso_hip_solver* s);
+bool blocks_gemm_l(calipso_hip_solver* s, const double* X, long long ldx, double* Y, long long ldy, int p);                  // Y(:, c) = Lxx X(:, c) over the Hessian blocks, p columns
 bool blocks_gemm_n(calipso_hip_solver* s, const double* X, long long ldx, double* Y, long long ldy, int p);                  // Y(:, c) = [gx; hx] X(:, c), p columns
 bool blocks_gemm_t(calipso_hip_solver* s, const double* U, long long ldu, double* Y, long long ldy, int p, double beta);     // Y(:, c) = [gx; hx]' U(:, c) + beta Y(:, c)
 bool blocks_plan(const Dims& d, const std::vector<int>& zrow, const std::vector<int>& lreach, BlockPlan& P, std::string& err);
@@ -390,6 +400,14 @@ void gemm(calipso_hip_solver* s, int M, int N, int K, double alpha, const double
 void trsm_multi(calipso_hip_solver* s, double* X, int p, double* U, double* Zm);
 void launch_residual_symmetric_multi(calipso_hip_solver* s, const double* res, int p, double* rsym, double* xbuf, double* t1);
 void launch_recover_multi(calipso_hip_solver* s, const double* res, int p, const double* rsym, const double* xbuf, const double* t2, double* step, double scale);
+// vectors.hip: the correction rounds of differentiate! on p columns together (handles without second-order cones).  E = R - H X: the rows r, s, y, z, t from zx = [gx; hx] X_x
+// (m apart) with refine_multi_parts(s) partial norms per column, then the rows x from hx = Lxx X_x + [gx; hx]' X_yz (ldh apart) and norms[c] = ||E(:, c)||_inf (NaN: +inf)
+int refine_multi_parts(const calipso_hip_solver* s);
+void launch_refine_rows_multi(calipso_hip_solver* s, const double* X, const double* R, const double* zx, int p, double* E, double* part);
+void launch_refine_x_multi(calipso_hip_solver* s, const double* X, const double* R, const double* hx, long long ldh, int p, double* E, const double* part, double* norms);
+void launch_accumulate_masked(calipso_hip_solver* s, const int* active, const double* C, int p, double* X, double* Xsave);      // X(:, c) += C(:, c) where active[c] (2: Xsave(:, c) = X(:, c) first)
+void launch_restore_masked(calipso_hip_solver* s, const int* restore, const double* Xsave, int p, double* X);                   // X(:, c) = Xsave(:, c) where restore[c]
+void launch_scale_into(calipso_hip_solver* s, const double* x, double* y, size_t n, double a);                 // y = a x
 // fallback.hip
 int nonsymmetric_solve(calipso_hip_solver* s, const double* res, double* step);   // step = H \\ res (pivoted LU of the unreduced matrix)
 void nonsymmetric_release(calipso_hip_solver* s);

@@ -382,6 +382,98 @@ void launch_recover_multi(calipso_hip_solver* s, const double* res, int p, const
     }
 }
 
+// ---- correction rounds of differentiate! on all parameter columns together ("opt.differentiate_refinement", api.hip: calipso_hip_differentiate) ---------------
+// E = R_theta - H X with the unreduced H (iterative_refinement.jl:8-12,38-41 per column), handles WITHOUT second-order cones.  Columns in grid.y as in k_residual_symmetric:
+// X, R, E are N apart, zx = [gx; hx] X_x is m apart, hx_ = Lxx X_x + [gx; hx]' X_yz is ldh apart.  Single instance (the multi-column path has no group form).
+// rows r, s, y, z, t: one work item per constraint, the expressions of k_refine_local; part[blockIdx.x + gridDim.x * column] = the workgroup's part of the column's norm
+constexpr int RM_THREADS = 256;
+__global__ __launch_bounds__(RM_THREADS) void k_refine_rows_multi(Scalars sc, Dims d, const double* __restrict__ w, const double* __restrict__ X_, const double* __restrict__ R_,
+                                                                   const double* __restrict__ zx_, double* __restrict__ E_, double* __restrict__ part) {
+    __shared__ double sm[RM_THREADS / 64];
+    const double* v = X_ + (size_t)blockIdx.y * d.N;
+    const double* res = R_ + (size_t)blockIdx.y * d.N;
+    const double* zx = zx_ + (size_t)blockIdx.y * d.m;
+    double* e = E_ + (size_t)blockIdx.y * d.N;
+    double m = 0.0;
+    const int ee = blockIdx.x * RM_THREADS + threadIdx.x;
+    if (ee < d.ne) {
+        const int ir = d.orr() + ee, iy = d.oy() + ee;
+        const double hr = (sc.rho + sc.ep) * v[ir] - v[iy];
+        const double er = res[ir] - hr;
+        const double hy = zx[ee] + (-v[ir] + (0.0 - sc.ed) * v[iy]);
+        const double ey = res[iy] - hy;
+        e[ir] = er; e[iy] = ey;
+        m = fmax(rabs(er), rabs(ey));
+    } else if (ee < d.ne + d.q) {
+        const int k = ee - d.ne;
+        const int is = d.os() + k, iz = d.oz() + k, it = d.ot() + k;
+        const double hs = (0.0 + sc.ep) * v[is] - v[iz] - v[it];
+        const double es = res[is] - hs;
+        const double hz = zx[d.ne + k] + (-v[is] + (0.0 - sc.ed) * v[iz]);
+        const double ez = res[iz] - hz;
+        const double ht = w[it] * v[is] + (w[is] - sc.ed) * v[it];
+        const double et = res[it] - ht;
+        e[is] = es; e[iz] = ez; e[it] = et;
+        m = fmax(fmax(rabs(es), rabs(ez)), rabs(et));
+    }
+    const double mr = block_max(m, sm);
+    if (threadIdx.x == 0) part[blockIdx.x + (size_t)gridDim.x * blockIdx.y] = mr;
+}
+// rows x: E_x = R_x - (hx + ep X_x), and norms[column] = ||E(:, column)||_inf with the nparts partial norms of the other rows: one workgroup per column
+__global__ __launch_bounds__(RT) void k_refine_x_multi(Scalars sc, Dims d, const double* __restrict__ X_, const double* __restrict__ R_, const double* __restrict__ hx_, long long ldh,
+                                                        double* __restrict__ E_, const double* __restrict__ part, int nparts, double* __restrict__ norms) {
+    __shared__ double sm[RT / 64];
+    const double* v = X_ + (size_t)blockIdx.y * d.N;
+    const double* res = R_ + (size_t)blockIdx.y * d.N;
+    const double* hx = hx_ + (size_t)blockIdx.y * ldh;
+    double* e = E_ + (size_t)blockIdx.y * d.N;
+    double m = 0.0;
+    for (int i = threadIdx.x; i < nparts; i += RT) m = fmax(m, part[i + (size_t)nparts * blockIdx.y]);
+    for (int i = threadIdx.x; i < d.nx; i += RT) {
+        const double hv = hx[i] + sc.ep * v[i];
+        const double r = res[i] - hv;
+        e[i] = r;
+        m = fmax(m, rabs(r));
+    }
+    const double mr = block_max(m, sm);
+    if (threadIdx.x == 0) norms[blockIdx.y] = mr;
+}
+// X(:, j) += C(:, j) for the columns that are still active (iterative_refinement.jl:34 per column); a column that has stopped is not touched.  active = 2 (a round
+// that only min_iterative_refinement asks for, sensitivity_columns.hpp): the column's iterate is saved in Xsave first
+__global__ void k_accumulate_masked(int N, const int* __restrict__ active, const double* __restrict__ C, double* __restrict__ X, double* __restrict__ Xsave) {
+    const int a = active[blockIdx.y];
+    if (!a) return;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < N) { const size_t e = (size_t)blockIdx.y * N + i; const double x = X[e]; if (a == 2) Xsave[e] = x; X[e] = x + C[e]; }
+}
+// X(:, j) = Xsave(:, j) for the columns whose forced round raised their norm
+__global__ void k_restore_masked(int N, const int* __restrict__ restore, const double* __restrict__ Xsave, double* __restrict__ X) {
+    if (!restore[blockIdx.y]) return;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < N) { const size_t e = (size_t)blockIdx.y * N + i; X[e] = Xsave[e]; }
+}
+__global__ void k_scale_into(size_t n, const double* __restrict__ x, double* __restrict__ y, double a) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) y[i] = a * x[i];
+}
+int refine_multi_parts(const calipso_hip_solver* s) { return (s->d.ne + s->d.q + RM_THREADS - 1) / RM_THREADS; }
+void launch_refine_rows_multi(calipso_hip_solver* s, const double* X, const double* R, const double* zx, int p, double* E, double* part) {
+    const int nparts = refine_multi_parts(s);
+    if (nparts > 0) hipLaunchKernelGGL(k_refine_rows_multi, dim3(nparts, p, 1), dim3(RM_THREADS), 0, s->stream, s->sc, s->d, s->solution, X, R, zx, E, part);
+}
+void launch_refine_x_multi(calipso_hip_solver* s, const double* X, const double* R, const double* hx, long long ldh, int p, double* E, const double* part, double* norms) {
+    hipLaunchKernelGGL(k_refine_x_multi, dim3(1, p, 1), dim3(RT), 0, s->stream, s->sc, s->d, X, R, hx, ldh, E, part, refine_multi_parts(s), norms);
+}
+void launch_accumulate_masked(calipso_hip_solver* s, const int* active, const double* C, int p, double* X, double* Xsave) {
+    hipLaunchKernelGGL(k_accumulate_masked, dim3((s->d.N + 255) / 256, p, 1), dim3(256), 0, s->stream, s->d.N, active, C, X, Xsave);
+}
+void launch_restore_masked(calipso_hip_solver* s, const int* restore, const double* Xsave, int p, double* X) {
+    hipLaunchKernelGGL(k_restore_masked, dim3((s->d.N + 255) / 256, p, 1), dim3(256), 0, s->stream, s->d.N, restore, Xsave, X);
+}
+void launch_scale_into(calipso_hip_solver* s, const double* x, double* y, size_t n, double a) {
+    hipLaunchKernelGGL(k_scale_into, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, n, x, y, a);
+}
+
 // candidate x, r (, s) = solution - step_size * step    solve.jl:224-229, 268-276
 struct PerInst { double v[MAX_BATCH]; };
 __global__ void k_axpy_points(Batch bt, Dims d, const double* __restrict__ sol, const double* __restrict__ step, double* __restrict__ cand,

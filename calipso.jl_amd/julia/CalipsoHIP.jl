@@ -223,6 +223,17 @@ function set_device_evaluator!(hs::HIPSolver, fn::Ptr{Cvoid}, user::Ptr{Cvoid} =
     return
 end
 
+"""correction rounds on every column of `differentiate!` (iterative_refinement.jl:14-44 per column; `"opt.differentiate_refinement"`, not an option of the reference —
+the default is the unrefined condensed solve; inert on a layout with second-order cones, where the unrefined solve is the reference's answer)"""
+set_differentiate_refinement!(hs::HIPSolver, on::Bool = true) = set_field!(hs.handle, "opt.differentiate_refinement", on ? 1.0 : 0.0)
+
+"report of the last `differentiate!` of the handle: (columns, rounds = largest over the columns, failed_columns, final_norm); zeros when no correction round ran"
+function differentiate_info(hs::HIPSolver)
+    out = zeros(Float64, 4)
+    check(hs.handle, ccall((:calipso_hip_differentiate_info, lib), Int32, (Ptr{Cvoid}, Ptr{Float64}), hs.handle, out), "differentiate_info")
+    return (columns = Int(out[1]), rounds = Int(out[2]), failed_columns = Int(out[3]), final_norm = out[4])
+end
+
 "solve!(solver)::Bool  src/solver/solve.jl:8-377 — results are copied back into the wrapped Solver's fields"
 function CALIPSO.solve!(hs::HIPSolver)
     rc = GC.@preserve hs ccall((:calipso_hip_solve, lib), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), hs.handle, hs.eval_cfunction, pointer_from_objref(hs))

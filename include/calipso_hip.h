@@ -268,8 +268,24 @@ int32_t calipso_hip_initialize(calipso_hip_solver*, const double* guess);
  * evaluator is attached (calipso_hip_qp_attach). */
 int32_t calipso_hip_solve(calipso_hip_solver*, calipso_eval_fn eval, void* user);
 /* differentiate!(solver)  differentiate.jl:1-61: dR/dtheta assembled on the device, one factorisation, then one condensed
- * solve + recovery per parameter column (as differentiate.jl:29-58, without its per-column re-factorisation) */
+ * solve + recovery per parameter column (as differentiate.jl:29-58, without its per-column re-factorisation).
+ * Default: the columns are the UNREFINED condensed solve.  The reference's QDLDL works on the (nx + ne + nc) symmetric matrix; the constraint-first condensation onto
+ * nx loses digits at a solution (penalty 1e7, central path 1e-7), so the columns agree with the reference only as far as the record in INTEGRATION.md (next to quirk
+ * B-12) shows: 5e-10 .. 2e-9 relative to max(1, |S|) at the solutions measured there, already below 1e-8 — the option below is insurance, it brings
+ * |H S + dR/dtheta| from 1e-10 .. 1e-9 down to 1e-16.
+ * Option "opt.differentiate_refinement" = 1 (calipso_hip_set_field; a handle-level value like "opt.solve_block", not an option of the reference; default 0, other values
+ * CALIPSO_ERR_ARGUMENT): the correction rounds of iterative_refinement.jl:14-44 on all columns together — E = dR/dtheta - H X with the unreduced, matrix-free H
+ * (residual_jacobian_variables.jl:1-108), per-column infinity norms, the correction through the same factors, X(:, j) += correction(:, j) for the columns that have not
+ * met the stopping test of iterative_refinement.jl:14-16 (the handle's iterative_refinement_tolerance, min_ / max_iterative_refinement; iterative_refinement = 0: no
+ * rounds; a column already within the tolerance keeps the round min_iterative_refinement asks for only if it does not raise the column's norm, so the option never
+ * leaves such a column with a larger residual than the unrefined solve had).  A column that exhausts its rounds with a larger error than it started with keeps its last iterate (differentiate! has no H \ residual fallback) and is counted.
+ * Exception: on a handle whose layout has any second-order cone the option is inert, the columns are the unrefined solve bit for bit — that IS the reference's answer
+ * there (its triu-symmetrised cone blocks, quirk B-3; refining would move away from it), and calipso_hip_differentiate_info reports 0 rounds. */
 int32_t calipso_hip_differentiate(calipso_hip_solver*, calipso_eval_fn eval, void* user);
+/* report of the last calipso_hip_differentiate (also the one at the end of calipso_hip_solve, solve.jl:144-146 with options.differentiate): [columns, correction rounds
+ * run (largest over the columns; iterative_refinement.jl:14-44), columns that did not meet the stopping test (:45-51), largest final column norm
+ * ||dR/dtheta(:, j) - H X(:, j)||_inf].  Zeros when no refinement ran; out[0] = columns is still filled in. */
+int32_t calipso_hip_differentiate_info(calipso_hip_solver*, double out[4]);
 /* install a device-side evaluator (NULL removes it): calipso_hip_solve / calipso_hip_differentiate / the group drivers then call it instead
  * of the host callback (their `eval` argument may be NULL), and calipso_hip_device_evaluate runs it on point `which` (0 solution, 1 candidate) */
 int32_t calipso_hip_set_device_evaluator(calipso_hip_solver*, calipso_device_eval_fn fn, void* user);

@@ -365,6 +365,67 @@ class Solver:
         self._check(self._L.calipso_hip_differentiate_info(self._h, _pd(out)), "differentiate_info")
         return dict(columns=int(out[0]), rounds=int(out[1]), failed_columns=int(out[2]), final_norm=float(out[3]))
 
+    def vjp(self, cotangent, adjoint=True, theta=None, qp=None):
+        """differentiate! in reverse mode on this handle (calipso_hip_differentiate_adjoint): for cotangents v = dLoss/dw at the resident point, lambda = M' v for the map
+        M that differentiate() applies to a column, and the gradients S' v for the S = dw/dtheta that differentiate() would return — one condensed solve per cotangent
+        instead of one per parameter.  cotangent: (N,) or (N, k).  theta: -R_theta' lambda (default: when the handle has parameters); qp: True, or a string of names out
+        of "PqAbGh": the data gradients of the QP given to qp_attach.  Returns a dict: "adjoint" (N[, k]), "theta" (np[, k]) and one entry per requested QP array in
+        qp_attach's shape ([, k]); the trailing k axis only when the cotangent had one.  set_option("differentiate_refinement", 1) turns the correction rounds on
+        (vjp_info)."""
+        N = self.N
+        squeeze = True
+        if cotangent is None:
+            vc, k = None, 1
+        else:
+            v = np.asarray(cotangent, dtype=np.float64)
+            squeeze = v.ndim == 1
+            if squeeze:
+                v = v[:, None]
+            if v.ndim != 2 or v.shape[0] != N:
+                raise ValueError("cotangent must be (N,) or (N, k)")
+            k = v.shape[1]
+            vc = np.ascontiguousarray(v.T).ravel()                              # column-major N x k
+        if theta is None:
+            theta = self.np > 0
+        names = "PqAbGh" if qp is True else (qp or "")
+        if any(c not in "PqAbGh" for c in names):
+            raise ValueError("qp must be True or a string of names out of 'PqAbGh'")
+        nx, ne, nc = self.nx, self.ne, self.nc
+        shape = dict(P=(nx, nx), q=(nx,), A=(ne, nx), b=(ne,), G=(nc, nx), h=(nc,))
+        kk = max(k, 1)
+        adj = np.zeros(kk * N) if adjoint else None
+        gth = np.zeros(max(kk * self.np, 1)) if theta else None
+        arrays = {c: np.zeros(max(kk * int(np.prod(shape[c])), 1)) for c in names}
+        ptrs = None
+        if names:
+            ptrs = (C.POINTER(C.c_double) * 6)(*[_pd(arrays[c]) if c in arrays else None for c in "PqAbGh"])
+        opt = lambda a: _pd(a) if a is not None else None
+        self._check(self._L.calipso_hip_differentiate_adjoint(self._h, self._cb, None, int(k), opt(vc), opt(adj), opt(gth), ptrs), "differentiate_adjoint")
+        fin = lambda a: a[..., 0] if squeeze else a
+        out = {}
+        if adjoint:
+            out["adjoint"] = fin(adj.reshape(k, N).T.copy())
+        if theta:
+            out["theta"] = fin(gth[:k * self.np].reshape(k, self.np).T.copy())
+        for c in names:
+            sh = shape[c]
+            a = arrays[c][:k * int(np.prod(sh))]
+            out[c] = fin(np.transpose(a.reshape(k, nx, sh[0]), (2, 1, 0)).copy() if len(sh) == 2 else a.reshape(k, sh[0]).T.copy())
+        return out
+
+    def vjp_info(self):
+        """report of the last vjp() (calipso_hip_differentiate_adjoint_info), as differentiate_info(): dict(columns, rounds, failed_columns, final_norm)"""
+        out = np.zeros(4)
+        self._check(self._L.calipso_hip_differentiate_adjoint_info(self._h, _pd(out)), "differentiate_adjoint_info")
+        return dict(columns=int(out[0]), rounds=int(out[1]), failed_columns=int(out[2]), final_norm=float(out[3]))
+
+    def vjp_times(self):
+        """HIP-event times of the last vjp() in ms: dict(device = entry to last kernel, copy = the results to the host, gradients = of device, the QP data-gradient
+        kernels alone)"""
+        out = np.zeros(3)
+        self._check(self._L.calipso_hip_differentiate_adjoint_times(self._h, _pd(out)), "differentiate_adjoint_times")
+        return dict(device=float(out[0]), copy=float(out[1]), gradients=float(out[2]))
+
     def set_device_evaluator(self, fn_ptr, user=None):
         """install a device-side evaluator (calipso_device_eval_fn, include/calipso_hip.h): `fn_ptr` is the C function's address (e.g.
         ctypes.cast(lib.sym, c_void_p)), `user` its opaque pointer; solve_b / differentiate then never call back into Python"""

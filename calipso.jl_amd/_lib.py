@@ -55,6 +55,9 @@ SYMBOLS = {
     "calipso_hip_solve": (_i32, [_vp, EVAL_FN, _vp]),
     "calipso_hip_differentiate": (_i32, [_vp, EVAL_FN, _vp]),
     "calipso_hip_differentiate_info": (_i32, [_vp, _pd]),
+    "calipso_hip_differentiate_adjoint": (_i32, [_vp, EVAL_FN, _vp, _i64, _pd, _pd, _pd, C.POINTER(_pd)]),
+    "calipso_hip_differentiate_adjoint_info": (_i32, [_vp, _pd]),
+    "calipso_hip_differentiate_adjoint_times": (_i32, [_vp, _pd]),
     "calipso_hip_set_device_evaluator": (_i32, [_vp, C.c_void_p, _vp]),
     "calipso_hip_set_device_block_evaluator": (_i32, [_vp, C.c_void_p, _vp]),
     "calipso_hip_device_evaluate": (_i32, [_vp, _i32, _u32]),

@@ -442,6 +442,7 @@ bool blocks_gemm_t(calipso_hip_solver* s, const double* U, long long ldu, double
 }
 // Y(:, c) = Lxx X(:, c) over the diagonal Hessian blocks for p columns in one launch (k_bgemv_l's sum per column; the columns ride in gridDim.z, which the
 // single-column launches use for the instances of a group: the multi-column path is single-instance)
+template <bool TR>      // TR: Lxx' X from the row-major copies of the blocks (the same lanes, the same order of the sum)
 __global__ __launch_bounds__(256) void k_bgemm_l(Batch bt, const LBlock* __restrict__ blk, const double* __restrict__ pk, const double* __restrict__ x, long long ldx,
                                                   double* __restrict__ y, long long ldy) {
     __shared__ double part[4][64];
@@ -453,7 +454,7 @@ __global__ __launch_bounds__(256) void k_bgemm_l(Batch bt, const LBlock* __restr
     if ((int)blockIdx.y * 64 >= b.n) return;
     double acc = 0.0;
     if (i < b.n) {
-        const double* a = pk + b.off_c + i;
+        const double* a = pk + (TR ? b.off_r : b.off_c) + i;
         for (int j0 = p; j0 < b.n; j0 += 32) {                  // eight columns in flight together, same order of the sum as k_bgemv_l
             double av[8], xv[8];
 #pragma unroll
@@ -466,12 +467,13 @@ __global__ __launch_bounds__(256) void k_bgemm_l(Batch bt, const LBlock* __restr
     __syncthreads();
     if (p == 0 && i < b.n) y[b.c0 + i] = (part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane]);
 }
-bool blocks_gemm_l(calipso_hip_solver* s, const double* X, long long ldx, double* Y, long long ldy, int p) {
+bool blocks_gemm_l(calipso_hip_solver* s, const double* X, long long ldx, double* Y, long long ldy, int p, bool transposed) {
     if (!blocks_usable(s) || p < 1 || p > 65535) return false;
     const StageBlocks& B = s->blocks;
     const BatchSc bs = batch_of(s);
     // (rows of Lxx that no Hessian block covers do not exist: the blocks partition the columns, blocks_plan)
-    hipLaunchKernelGGL(k_bgemm_l, dim3(B.nlb, (B.max_lb + 63) / 64, p), dim3(256), 0, s->stream, bs.b, B.d_lblk, s->Lsym, X, ldx, Y, ldy);
+    if (transposed) hipLaunchKernelGGL(k_bgemm_l<true>, dim3(B.nlb, (B.max_lb + 63) / 64, p), dim3(256), 0, s->stream, bs.b, B.d_lblk, s->Lsym, X, ldx, Y, ldy);
+    else hipLaunchKernelGGL(k_bgemm_l<false>, dim3(B.nlb, (B.max_lb + 63) / 64, p), dim3(256), 0, s->stream, bs.b, B.d_lblk, s->Lsym, X, ldx, Y, ldy);
     return true;
 }
 bool blocks_schur(calipso_hip_solver* s) {

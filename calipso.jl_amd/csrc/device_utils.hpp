@@ -101,4 +101,27 @@ __device__ __forceinline__ void arrow_inverse_small(int n, const double (&u)[MAX
     for (int i = 1; i < MAXD; ++i) if (i < n) out[i] = 1.0 / u[0] * out[i];
 }
 
+// the transpose of arrow_inverse_small's operation sequence for the same u (out = T' y where arrow_inverse_small(u, x) = T x; the first-row quirk of
+// second_order.jl:63-65 lives in the caller's u): its stages in reverse order, each transposed, loops unrolled to constant indices
+template <int MAXD>
+__device__ __forceinline__ void arrow_inverse_t_small(int n, const double (&u)[MAXD], const double (&y)[MAXD], double (&out)[MAXD]) {
+    double uu = 0.0;
+#pragma unroll
+    for (int i = 1; i < MAXD; ++i) if (i < n) uu += u[i] * u[i];
+    const double alpha = -1.0 / (u[0] * u[0]) * uu;
+    const double beta = 1.0 / (1.0 + alpha);
+    const double x2_1 = 1.0 / u[0] * y[0];
+    double s = 0.0;
+#pragma unroll
+    for (int i = 1; i < MAXD; ++i) if (i < n) {
+        const double o = 1.0 / u[0] * y[i] - (u[i] / u[0]) * x2_1;
+        out[i] = o;
+        s += (u[i] / u[0]) * o;
+    }
+    const double x0_1 = -beta * s;
+    out[0] = x2_1 + x0_1;
+#pragma unroll
+    for (int i = 1; i < MAXD; ++i) if (i < n) out[i] = out[i] - (u[i] / u[0]) * x0_1;
+}
+
 }  // namespace calipso

@@ -248,6 +248,16 @@ struct calipso_hip_solver {
     calipso::SensitivityColumns diff_cols;
     std::vector<double> diff_norms;    // host side of the per-round read-back (np)
     double diff_info[4] = {0, 0, 0, 0};   // calipso_hip_differentiate_info of the last differentiate!
+    // differentiate! in reverse mode (api.hip: calipso_hip_differentiate_adjoint): its own workspace, grown on demand and kept (k cotangent columns, not np: the
+    // forward's multi_rhs stays as it is), counted in scratch_bytes
+    double* adj_work = nullptr; size_t adj_work_doubles = 0;      // the condensed pipeline, V, lambda, grad_theta (+ E, C, Xsave, partial and column norms when the rounds run)
+    double* adj_qp = nullptr; size_t adj_qp_doubles = 0;          // the QP data gradients asked for, k x size each
+    int* adj_active = nullptr; size_t adj_active_ints = 0;        // 2 k: SensitivityColumns::active and ::restore
+    calipso::SensitivityColumns adj_cols;
+    std::vector<double> adj_norms;
+    double adj_info[4] = {0, 0, 0, 0};    // calipso_hip_differentiate_adjoint_info of the last reverse call
+    hipEvent_t adj_ev[4] = {};            // entry, behind the last kernel, behind the copies to the host, before the QP gradient kernels (created on the first reverse call)
+    double adj_ms[3] = {0, 0, 0};          // calipso_hip_differentiate_adjoint_times of the last reverse call
     void* scatter_aux = nullptr;  // scatter.hip: registered sparsity patterns of the evaluate! scatter
     void* ldl_aux = nullptr;      // ldlsolver.hip: staging of the caller's CSC matrix (handles made by calipso_hip_ldl_create)
     void* lfac_aux = nullptr;     // lfac.hip: plan and buffers of the left-looking schedule (one dense system alone)
@@ -364,7 +374,7 @@ void blocks_mirror(calipso_hip_solver* s, bool l, bool zg, bool zh);            
 bool blocks_gemv_n(calipso_hip_solver* s, int kind, const double* x, double* y, double alpha, double beta);
 bool blocks_gemv_t(calipso_hip_solver* s, int kind, const double* u1, const double* u2, double* y1, double* y2, double alpha, double beta);
 bool blocks_schur(calipso_hip_solver* s);
-bool blocks_gemm_l(calipso_hip_solver* s, const double* X, long long ldx, double* Y, long long ldy, int p);                  // Y(:, c) = Lxx X(:, c) over the Hessian blocks, p columns
+bool blocks_gemm_l(calipso_hip_solver* s, const double* X, long long ldx, double* Y, long long ldy, int p, bool transposed = false);   // Y(:, c) = Lxx X(:, c) (transposed: Lxx' X(:, c)) over the Hessian blocks, p columns
 bool blocks_gemm_n(calipso_hip_solver* s, const double* X, long long ldx, double* Y, long long ldy, int p);                  // Y(:, c) = [gx; hx] X(:, c), p columns
 bool blocks_gemm_t(calipso_hip_solver* s, const double* U, long long ldu, double* Y, long long ldy, int p, double beta);     // Y(:, c) = [gx; hx]' U(:, c) + beta Y(:, c)
 bool blocks_plan(const Dims& d, const std::vector<int>& zrow, const std::vector<int>& lreach, BlockPlan& P, std::string& err);
@@ -403,11 +413,19 @@ void launch_recover_multi(calipso_hip_solver* s, const double* res, int p, const
 // vectors.hip: the correction rounds of differentiate! on p columns together (handles without second-order cones).  E = R - H X: the rows r, s, y, z, t from zx = [gx; hx] X_x
 // (m apart) with refine_multi_parts(s) partial norms per column, then the rows x from hx = Lxx X_x + [gx; hx]' X_yz (ldh apart) and norms[c] = ||E(:, c)||_inf (NaN: +inf)
 int refine_multi_parts(const calipso_hip_solver* s);
-void launch_refine_rows_multi(calipso_hip_solver* s, const double* X, const double* R, const double* zx, int p, double* E, double* part);
+void launch_refine_rows_multi(calipso_hip_solver* s, const double* X, const double* R, const double* zx, int p, double* E, double* part, bool transposed = false);   // transposed: E = R - H' X
 void launch_refine_x_multi(calipso_hip_solver* s, const double* X, const double* R, const double* hx, long long ldh, int p, double* E, const double* part, double* norms);
 void launch_accumulate_masked(calipso_hip_solver* s, const int* active, const double* C, int p, double* X, double* Xsave);      // X(:, c) += C(:, c) where active[c] (2: Xsave(:, c) = X(:, c) first)
 void launch_restore_masked(calipso_hip_solver* s, const int* restore, const double* Xsave, int p, double* X);                   // X(:, c) = Xsave(:, c) where restore[c]
 void launch_scale_into(calipso_hip_solver* s, const double* x, double* y, size_t n, double a);                 // y = a x
+// adjoint.hip: the first and the last stage of the condensed solve transposed (differentiate! in reverse mode), p cotangent columns in grid.y; the cones of
+// dimension > 4 in soc_wide.hip (launch_*_t_wide, called by these launchers)
+void launch_recover_t_multi(calipso_hip_solver* s, const double* V, int p, double* lam, double* g, double* xbuf);           // first contributions to lam_r, lam_s, lam_t; g (m x p); xbuf = [V_x; 0]
+void launch_residual_symmetric_t_multi(calipso_hip_solver* s, int p, const double* g, const double* xbuf, const double* t1, double* lam);   // lam_x, lam_y, lam_z and the second contributions
+void launch_recover_t_wide(calipso_hip_solver* s, const double* V, int p, double* lam, double* g);
+void launch_residual_symmetric_t_wide(calipso_hip_solver* s, int p, const double* g, const double* t1, double* lam);
+// gradients of a loss with respect to the data of an attached QP from lam (N x p) and the resident point w: out[a] (p x size of array a, NULL: skipped) in the order P, q, A, b, G, h
+void launch_qp_data_gradients(calipso_hip_solver* s, const double* lam, int p, double* const out[6]);
 // fallback.hip
 int nonsymmetric_solve(calipso_hip_solver* s, const double* res, double* step);   // step = H \\ res (pivoted LU of the unreduced matrix)
 void nonsymmetric_release(calipso_hip_solver* s);

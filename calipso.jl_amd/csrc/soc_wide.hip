@@ -332,6 +332,126 @@ __global__ __launch_bounds__(64) void k_refine_local_wide(BatchSc bt, Dims d, Co
     if (lane == 0) part[part0 + blockIdx.x] = m;
 }
 
+// ---- the two cone stages of the condensed solve TRANSPOSED (differentiate! in reverse mode, adjoint.hip: k_recover_t / k_residual_symmetric_t are the register path) ----
+// out = T' y for the T of arrow_inverse_wave with the same u: its stages in reverse order, each transposed (device_utils.hpp: arrow_inverse_t_small, same operations)
+template <int E>
+__device__ __forceinline__ void arrow_inverse_t_wave(int n, int lane, const double (&u)[E], const double (&y)[E], double (&out)[E]) {
+    const double u0 = bc(u[0], 0), y0 = bc(y[0], 0);
+    double uu = 0.0;
+    for_elems<E>(1, n, [&](int e, int l) { const double ui = bc(u[e], l); uu += ui * ui; });
+    const double alpha = -1.0 / (u0 * u0) * uu;
+    const double beta = 1.0 / (1.0 + alpha);
+    const double x2_1 = 1.0 / u0 * y0;
+    double o[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) o[e] = 1.0 / u0 * y[e] - (u[e] / u0) * x2_1;
+    double s = 0.0;
+    for_elems<E>(1, n, [&](int e, int l) { s += (bc(u[e], l) / u0) * bc(o[e], l); });
+    const double x0_1 = -beta * s;
+#pragma unroll
+    for (int e = 0; e < E; ++e) out[e] = (lane + 64 * e == 0) ? x2_1 + x0_1 : o[e] - (u[e] / u0) * x0_1;
+}
+// s_a = sum_b W[b + a dim] o_b in index order: W' by swapped indices (W is not assumed symmetric)
+template <int E>
+__device__ __forceinline__ void w_t_times(int dim, int lane, const bool (&in)[E], const double* __restrict__ W, const double (&o)[E], double (&s)[E]) {
+#pragma unroll
+    for (int e = 0; e < E; ++e) s[e] = 0.0;
+    for_elems<E>(0, dim, [&](int eb, int lb) {
+        const int b = 64 * eb + lb;
+        const double ob = bc(o[eb], lb);
+#pragma unroll
+        for (int e = 0; e < E; ++e) { const int a = lane + 64 * e; if (in[e]) s[e] += W[b + (size_t)a * dim] * ob; }
+    });
+}
+// out = arrow(c0; c)' a with the diagonal c0 (arrow matrices are symmetric): out_0 = c0 a_0 + sum_{i >= 1} c_i a_i, out_i = c_i a_0 + c0 a_i
+template <int E>
+__device__ __forceinline__ void arrow_times(int dim, int lane, double c0, const double (&c)[E], const double (&a)[E], double (&out)[E]) {
+    const double a0 = bc(a[0], 0);
+    double acc = c0 * a0;
+    for_elems<E>(1, dim, [&](int e, int l) { acc += bc(c[e], l) * bc(a[e], l); });
+#pragma unroll
+    for (int e = 0; e < E; ++e) out[e] = (lane + 64 * e == 0) ? acc : c[e] * a0 + c0 * a[e];
+}
+
+// first contributions to the s, t rows of lam and the cone's rows of g (k_recover_wide transposed; the dt recovery with the first row of Cbar_t only)
+template <int E>
+__global__ __launch_bounds__(64) void k_recover_t_wide(Scalars sc, Dims d, ConeDev cd, const double* __restrict__ w, const double* __restrict__ V_, const double* __restrict__ Wsoc,
+                                                        double* __restrict__ lam_, double* __restrict__ g_) {
+    const double* v = V_ + (size_t)blockIdx.y * d.N;
+    double* lam = lam_ + (size_t)blockIdx.y * d.N;
+    double* g = g_ + (size_t)blockIdx.y * d.m;
+    const int j = cd.wide[blockIdx.x];
+    const int st = cd.soc_start[j], dim = cd.soc_dim[j];
+    const int lane = threadIdx.x;
+    const double Hss = 0.0 + sc.ep;
+    double sl[E], t[E], vs[E], vt[E], vz[E], u[E], ct[E], a[E], b[E], a2[E], gb[E], s[E];
+    bool in[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const int k = lane + 64 * e; in[e] = k < dim;
+        sl[e] = in[e] ? w[d.os() + st + k] : 0.0; t[e] = in[e] ? w[d.ot() + st + k] : 0.0;
+        vs[e] = in[e] ? v[d.os() + st + k] : 0.0; vt[e] = in[e] ? v[d.ot() + st + k] : 0.0; vz[e] = in[e] ? v[d.oz() + st + k] : 0.0;
+    }
+    const double sb1 = bc(sl[0], 0) - sc.ed, t0 = bc(t[0], 0);
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const int k = lane + 64 * e;
+        ct[e] = k == 0 ? sb1 : sl[e];
+        u[e] = k == 0 ? t[e] + sb1 * Hss : t[e] + sl[e] * Hss;
+    }
+    arrow_inverse_t_wave<E>(dim, lane, ct, vt, a);
+    arrow_times<E>(dim, lane, t0, t, a, b);                        // arrow(t)' a
+#pragma unroll
+    for (int e = 0; e < E; ++e) b[e] = vs[e] - b[e];
+    arrow_inverse_t_wave<E>(dim, lane, u, b, a2);
+    arrow_times<E>(dim, lane, sb1, sl, a2, gb);                    // Cbar_t' a2
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const int k = lane + 64 * e;
+        if (in[e]) { lam[d.ot() + st + k] = a[e] + a2[e]; lam[d.os() + st + k] = gb[e]; }
+        gb[e] = in[e] ? vz[e] + gb[e] : 0.0;
+    }
+    w_t_times<E>(dim, lane, in, Wsoc + cd.soc_woff[j], gb, s);
+#pragma unroll
+    for (int e = 0; e < E; ++e) if (in[e]) g[d.ne + st + lane + 64 * e] = s[e];
+}
+
+// lam_z of the cone and the second contributions to its s, t rows (k_residual_symmetric_wide transposed)
+template <int E>
+__global__ __launch_bounds__(64) void k_residual_symmetric_t_wide(Scalars sc, Dims d, ConeDev cd, const double* __restrict__ w, const double* __restrict__ g_,
+                                                                   const double* __restrict__ t1_, const double* __restrict__ Wsoc, double* __restrict__ lam_) {
+    const double* g = g_ + (size_t)blockIdx.y * d.m;
+    const double* t1 = t1_ + (size_t)blockIdx.y * d.m;
+    double* lam = lam_ + (size_t)blockIdx.y * d.N;
+    const int j = cd.wide[blockIdx.x];
+    const int st = cd.soc_start[j], dim = cd.soc_dim[j];
+    const int lane = threadIdx.x;
+    const double Hss = 0.0 + sc.ep;
+    double sl[E], t[E], tt[E], u[E], bz[E], a[E], gb[E], s[E];
+    bool in[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const int k = lane + 64 * e; in[e] = k < dim;
+        sl[e] = in[e] ? w[d.os() + st + k] : 0.0; t[e] = in[e] ? w[d.ot() + st + k] : 0.0;
+        tt[e] = in[e] ? t1[d.ne + st + k] : 0.0;
+    }
+    const double sb1 = bc(sl[0], 0) - sc.ed;
+#pragma unroll
+    for (int e = 0; e < E; ++e) u[e] = (lane + 64 * e == 0) ? t[e] + sb1 * Hss : t[e] + sl[e] * Hss;
+    w_t_times<E>(dim, lane, in, Wsoc + cd.soc_woff[j], tt, s);
+#pragma unroll
+    for (int e = 0; e < E; ++e) bz[e] = in[e] ? -g[d.ne + st + lane + 64 * e] + s[e] : 0.0;
+    arrow_inverse_t_wave<E>(dim, lane, u, bz, a);
+    arrow_times<E>(dim, lane, sb1, sl, a, gb);
+#pragma unroll
+    for (int e = 0; e < E; ++e) if (in[e]) {
+        const int k = lane + 64 * e;
+        lam[d.oz() + st + k] = bz[e];
+        lam[d.os() + st + k] += gb[e];
+        lam[d.ot() + st + k] += a[e];
+    }
+}
+
 // ---- launchers (called by the launchers of schur.hip / vectors.hip right after their own kernel, only when the handle has wide cones) ----------
 // E = elements per lane for the widest cone of the handle
 static int wide_E(const calipso_hip_solver* s) { const int m = s->d.max_dim; return m <= 64 ? 1 : (m <= 128 ? 2 : (m <= 256 ? 4 : (m <= 512 ? 8 : 16))); }
@@ -366,6 +486,14 @@ void launch_refine_local_wide(calipso_hip_solver* s, int part0) {
     const BatchSc B = batch_of(s);
     WIDE_DISPATCH(wide_E(s), hipLaunchKernelGGL(k_refine_local_wide<E>, dim3(s->d.n_wide, 1, B.b.n), dim3(64), 0, s->stream, B, s->d, s->cone, s->solution, s->step, s->residual, s->zsx, s->Wsoc,
                                                s->residual_error, s->residual_symmetric, s->t1, s->refpart, part0));
+}
+void launch_recover_t_wide(calipso_hip_solver* s, const double* V, int p, double* lam, double* g) {
+    if (!s->d.n_wide) return;
+    WIDE_DISPATCH(wide_E(s), hipLaunchKernelGGL(k_recover_t_wide<E>, dim3(s->d.n_wide, p, 1), dim3(64), 0, s->stream, s->sc, s->d, s->cone, s->solution, V, s->Wsoc, lam, g));
+}
+void launch_residual_symmetric_t_wide(calipso_hip_solver* s, int p, const double* g, const double* t1, double* lam) {
+    if (!s->d.n_wide) return;
+    WIDE_DISPATCH(wide_E(s), hipLaunchKernelGGL(k_residual_symmetric_t_wide<E>, dim3(s->d.n_wide, p, 1), dim3(64), 0, s->stream, s->sc, s->d, s->cone, s->solution, g, t1, s->Wsoc, lam));
 }
 
 }  // namespace calipso

@@ -386,7 +386,10 @@ void launch_recover_multi(calipso_hip_solver* s, const double* res, int p, const
 // E = R_theta - H X with the unreduced H (iterative_refinement.jl:8-12,38-41 per column), handles WITHOUT second-order cones.  Columns in grid.y as in k_residual_symmetric:
 // X, R, E are N apart, zx = [gx; hx] X_x is m apart, hx_ = Lxx X_x + [gx; hx]' X_yz is ldh apart.  Single instance (the multi-column path has no group form).
 // rows r, s, y, z, t: one work item per constraint, the expressions of k_refine_local; part[blockIdx.x + gridDim.x * column] = the workgroup's part of the column's norm
+// TR: E = R - H' X (the reverse mode's rounds, api.hip: calipso_hip_differentiate_adjoint).  Without second-order cones H and H' differ in the (s, t) rows only:
+// (H' v)_s = ep v_s - v_z + T v_t, (H' v)_t = -v_s + (S - ed) v_t
 constexpr int RM_THREADS = 256;
+template <bool TR>
 __global__ __launch_bounds__(RM_THREADS) void k_refine_rows_multi(Scalars sc, Dims d, const double* __restrict__ w, const double* __restrict__ X_, const double* __restrict__ R_,
                                                                    const double* __restrict__ zx_, double* __restrict__ E_, double* __restrict__ part) {
     __shared__ double sm[RM_THREADS / 64];
@@ -407,11 +410,11 @@ __global__ __launch_bounds__(RM_THREADS) void k_refine_rows_multi(Scalars sc, Di
     } else if (ee < d.ne + d.q) {
         const int k = ee - d.ne;
         const int is = d.os() + k, iz = d.oz() + k, it = d.ot() + k;
-        const double hs = (0.0 + sc.ep) * v[is] - v[iz] - v[it];
+        const double hs = TR ? ((0.0 + sc.ep) * v[is] - v[iz]) + w[it] * v[it] : (0.0 + sc.ep) * v[is] - v[iz] - v[it];
         const double es = res[is] - hs;
         const double hz = zx[d.ne + k] + (-v[is] + (0.0 - sc.ed) * v[iz]);
         const double ez = res[iz] - hz;
-        const double ht = w[it] * v[is] + (w[is] - sc.ed) * v[it];
+        const double ht = TR ? -v[is] + (w[is] - sc.ed) * v[it] : w[it] * v[is] + (w[is] - sc.ed) * v[it];
         const double et = res[it] - ht;
         e[is] = es; e[iz] = ez; e[it] = et;
         m = fmax(fmax(rabs(es), rabs(ez)), rabs(et));
@@ -457,9 +460,11 @@ __global__ void k_scale_into(size_t n, const double* __restrict__ x, double* __r
     if (i < n) y[i] = a * x[i];
 }
 int refine_multi_parts(const calipso_hip_solver* s) { return (s->d.ne + s->d.q + RM_THREADS - 1) / RM_THREADS; }
-void launch_refine_rows_multi(calipso_hip_solver* s, const double* X, const double* R, const double* zx, int p, double* E, double* part) {
+void launch_refine_rows_multi(calipso_hip_solver* s, const double* X, const double* R, const double* zx, int p, double* E, double* part, bool transposed) {
     const int nparts = refine_multi_parts(s);
-    if (nparts > 0) hipLaunchKernelGGL(k_refine_rows_multi, dim3(nparts, p, 1), dim3(RM_THREADS), 0, s->stream, s->sc, s->d, s->solution, X, R, zx, E, part);
+    if (nparts <= 0) return;
+    if (transposed) hipLaunchKernelGGL(k_refine_rows_multi<true>, dim3(nparts, p, 1), dim3(RM_THREADS), 0, s->stream, s->sc, s->d, s->solution, X, R, zx, E, part);
+    else hipLaunchKernelGGL(k_refine_rows_multi<false>, dim3(nparts, p, 1), dim3(RM_THREADS), 0, s->stream, s->sc, s->d, s->solution, X, R, zx, E, part);
 }
 void launch_refine_x_multi(calipso_hip_solver* s, const double* X, const double* R, const double* hx, long long ldh, int p, double* E, const double* part, double* norms) {
     hipLaunchKernelGGL(k_refine_x_multi, dim3(1, p, 1), dim3(RT), 0, s->stream, s->sc, s->d, X, R, hx, ldh, E, part, refine_multi_parts(s), norms);

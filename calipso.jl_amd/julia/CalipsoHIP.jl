@@ -234,6 +234,45 @@ function differentiate_info(hs::HIPSolver)
     return (columns = Int(out[1]), rounds = Int(out[2]), failed_columns = Int(out[3]), final_norm = out[4])
 end
 
+"""differentiate! in reverse mode on the handle (calipso_hip_differentiate_adjoint; differentiate.jl:1-61 and residual_jacobian_parameters.jl:1-40, transposed): for the
+cotangent columns `cotangent` (N or N x k, dLoss/dw at the resident point) the adjoint `lambda = M' v` of the map `differentiate!` applies to a column and
+`grad_theta = S' v` for the `S = dw/dtheta` that `differentiate!` would return — one condensed solve per cotangent instead of one per parameter.  `qp`: names out of
+"PqAbGh" on a handle with an attached QP: the gradients with respect to those arrays (matrices rows x nx x k).  Returns a NamedTuple (adjoint, theta, qp::Dict).
+`set_differentiate_refinement!` turns the correction rounds (against H') on; `differentiate_adjoint_info` reports them."""
+function differentiate_adjoint!(hs::HIPSolver, cotangent::AbstractVecOrMat{Float64}; adjoint::Bool = true, theta::Bool = hs.solver.dimensions.parameters > 0, qp::AbstractString = "")
+    d = hs.solver.dimensions
+    V = Matrix{Float64}(reshape(cotangent, size(cotangent, 1), :))
+    size(V, 1) == d.total || throw(ArgumentError("cotangent must be N or N x k"))
+    k = size(V, 2)
+    nx, ne, nc = d.variables, d.equality_dual, d.cone_dual
+    sizes = Dict('P' => (nx, nx), 'q' => (nx,), 'A' => (ne, nx), 'b' => (ne,), 'G' => (nc, nx), 'h' => (nc,))
+    all(c -> haskey(sizes, c), qp) || throw(ArgumentError("qp must be made of names out of PqAbGh"))
+    adj = adjoint ? zeros(Float64, d.total, k) : nothing
+    gth = theta ? zeros(Float64, max(d.parameters, 1), k) : nothing
+    gq = Dict{Char,Array{Float64}}(c => zeros(Float64, sizes[c]..., k) for c in qp)
+    ptrs = Ptr{Float64}[haskey(gq, c) ? pointer(gq[c]) : Ptr{Float64}(C_NULL) for c in "PqAbGh"]
+    opt(a) = a === nothing ? Ptr{Float64}(C_NULL) : pointer(a)
+    rc = GC.@preserve hs V adj gth gq ptrs ccall((:calipso_hip_differentiate_adjoint, lib), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Ptr{Float64}}),
+        hs.handle, hs.eval_cfunction, pointer_from_objref(hs), k, V, opt(adj), opt(gth), isempty(qp) ? Ptr{Ptr{Float64}}(C_NULL) : pointer(ptrs))
+    check(hs.handle, rc, "differentiate_adjoint!")
+    return (adjoint = adj, theta = theta ? gth[1:d.parameters, :] : nothing, qp = gq)
+end
+
+"report of the last `differentiate_adjoint!` of the handle, as `differentiate_info`: (columns, rounds, failed_columns, final_norm)"
+function differentiate_adjoint_info(hs::HIPSolver)
+    out = zeros(Float64, 4)
+    check(hs.handle, ccall((:calipso_hip_differentiate_adjoint_info, lib), Int32, (Ptr{Cvoid}, Ptr{Float64}), hs.handle, out), "differentiate_adjoint_info")
+    return (columns = Int(out[1]), rounds = Int(out[2]), failed_columns = Int(out[3]), final_norm = out[4])
+end
+
+"HIP-event times of the last `differentiate_adjoint!` in ms: (device = entry to last kernel, copy = results to the host, gradients = of device, the QP data-gradient kernels alone)"
+function differentiate_adjoint_times(hs::HIPSolver)
+    out = zeros(Float64, 3)
+    check(hs.handle, ccall((:calipso_hip_differentiate_adjoint_times, lib), Int32, (Ptr{Cvoid}, Ptr{Float64}), hs.handle, out), "differentiate_adjoint_times")
+    return (device = out[1], copy = out[2], gradients = out[3])
+end
+
 "solve!(solver)::Bool  src/solver/solve.jl:8-377 — results are copied back into the wrapped Solver's fields"
 function CALIPSO.solve!(hs::HIPSolver)
     rc = GC.@preserve hs ccall((:calipso_hip_solve, lib), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), hs.handle, hs.eval_cfunction, pointer_from_objref(hs))

@@ -20,12 +20,18 @@ warning on that path: sn.status_device() gives the solve statuses as an int32 CU
 
 ParametricLayer is the auto-tuning loop of examples/autotuning/cartpole.jl as a layer: forward = set_parameters_device + initialize_device + solve_device,
 backward = vjp_device with grad_theta (theta (batch, n_parameters), or (n_parameters,) shared: summed).  torch is imported on first use of a layer: the package
-itself loads without it."""
+itself loads without it.
+
+    x = SolverQPLayer.apply(solver, P, q, A, b, G, h)    # ONE unbatched QP on a Solver handle (dense, stage-structured or stage-parallel: any size the handle admits)
+
+SolverQPLayer is the same layer over the general path: forward = qp_attach + initialize! with zeros + solve!, backward = Solver.vjp(qp=...) — one transposed
+condensed solve for the cotangent and the closed-form data gradients of the inputs that need them.  The data travel through host arrays; a solve that did not
+converge gives NaN gradients and a warning, as on the host path of QPLayer."""
 import warnings
 
 import numpy as np
 
-__all__ = ["QPLayer", "ParametricLayer"]
+__all__ = ["QPLayer", "ParametricLayer", "SolverQPLayer"]
 
 _cls = {}
 
@@ -151,7 +157,59 @@ def _build():
             g = sn.vjp_device(cotangent=gw.contiguous(), theta=True, qp=False)["theta"]
             return None, (g.sum(dim=0) if ctx.theta.dim() == 1 else g), None
 
-    return {"QPLayer": QPLayer, "ParametricLayer": ParametricLayer}
+    class SolverQPLayer(torch.autograd.Function):
+        """apply(solver, P, q, A, b, G, h, return_duals=False, objective_scale=0.5): the solution x (nx,) of one QP on a Solver handle, or (x, y, z) with return_duals"""
+
+        @staticmethod
+        def forward(ctx, solver, P, q, A, b, G, h, return_duals=False, objective_scale=0.5):
+            data = (P, q, A, b, G, h)
+            dims = ((solver.nx, solver.nx), (solver.nx,), (solver.ne, solver.nx), (solver.ne,), (solver.nc, solver.nx), (solver.nc,))
+            for name, t, dm in zip("PqAbGh", data, dims):
+                if t.dtype != torch.float64:
+                    raise TypeError("SolverQPLayer: %s must be float64" % name)
+                if tuple(t.shape) != dm:
+                    raise ValueError("SolverQPLayer: %s must be %s" % (name, dm))
+            arrays = [_np(t) for t in data]
+            key = object()
+            _solve_handle(solver, arrays, objective_scale, key)
+            w = solver.solution
+            ctx.solver, ctx.key, ctx.arrays, ctx.c, ctx.converged, ctx.device = solver, key, arrays, objective_scale, solver._qp_layer_converged, P.device
+            dev = P.device
+            x = torch.from_numpy(w.variables.copy()).to(dev)
+            if not return_duals:
+                return x
+            return x, torch.from_numpy(w.equality_dual.copy()).to(dev), torch.from_numpy(w.cone_dual.copy()).to(dev)
+
+        @staticmethod
+        def backward(ctx, gx, gy=None, gz=None):
+            solver = ctx.solver
+            if getattr(solver, "_qp_layer_key", None) is not ctx.key:      # the handle solved another QP since: the same data solve again (deterministic)
+                _solve_handle(solver, ctx.arrays, ctx.c, ctx.key)
+            nx, ne, nc = solver.nx, solver.ne, solver.nc
+            oy, oz = nx + ne + nc, nx + 2 * ne + nc
+            v = np.zeros(solver.N)
+            if gx is not None:
+                v[:nx] = _np(gx)
+            if gy is not None and ne:
+                v[oy:oy + ne] = _np(gy)
+            if gz is not None and nc:
+                v[oz:oz + nc] = _np(gz)
+            want = "".join(name for name, need in zip("PqAbGh", ctx.needs_input_grad[1:7]) if need)
+            out = solver.vjp(v, adjoint=False, theta=False, qp=want) if want else {}
+            if not ctx.converged:
+                warnings.warn("SolverQPLayer: the solve did not converge: the gradients are NaN")
+            grads = []
+            for name in "PqAbGh":
+                if name not in out:
+                    grads.append(None)
+                    continue
+                g = out[name]
+                if not ctx.converged:
+                    g = np.full_like(g, np.nan)
+                grads.append(torch.from_numpy(np.ascontiguousarray(g)).to(ctx.device))
+            return (None, *grads, None, None)
+
+    return {"QPLayer": QPLayer, "ParametricLayer": ParametricLayer, "SolverQPLayer": SolverQPLayer}
 
 
 def _solve_device(torch, sn, tensors, objective_scale, key):
@@ -168,6 +226,14 @@ def _solve_parameters(torch, sn, theta, x0, key):
     sn.initialize_device(x0)
     sn.solve_device()
     sn._qp_layer_key, sn._qp_layer_status = key, None
+
+
+def _solve_handle(solver, arrays, objective_scale, key):
+    from . import initialize_b, solve_b
+    solver.qp_attach(*arrays, objective_scale=objective_scale)
+    initialize_b(solver, np.zeros(solver.nx))
+    converged = solve_b(solver)
+    solver._qp_layer_key, solver._qp_layer_converged = key, bool(converged)
 
 
 def _solve(sn, arrays, shared, objective_scale, key):

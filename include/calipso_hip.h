@@ -286,6 +286,39 @@ int32_t calipso_hip_differentiate(calipso_hip_solver*, calipso_eval_fn eval, voi
  * run (largest over the columns; iterative_refinement.jl:14-44), columns that did not meet the stopping test (:45-51), largest final column norm
  * ||dR/dtheta(:, j) - H X(:, j)||_inf].  Zeros when no refinement ran; out[0] = columns is still filled in. */
 int32_t calipso_hip_differentiate_info(calipso_hip_solver*, double out[4]);
+/* differentiate! in REVERSE mode on a Solver handle (dense, stage-structured or stage-parallel): differentiate.jl:1-61 and residual_jacobian_parameters.jl:1-40,
+ * transposed.  One factorisation with the regularisation the handle holds, as calipso_hip_differentiate; then for k cotangent columns v = dLoss/dw at once the
+ * transposed map lambda = M' v of the map M that calipso_hip_differentiate applies to a column: the condensed solve of differentiate.jl:29-58 stage by stage in reverse
+ * order (search_direction.jl:38-101 and residual.jl:53-101 transposed; the products with [gx; hx] and the solve with the factor of S are their own transposes, S being
+ * factored from one triangle).  One condensed solve per cotangent instead of one per parameter column.  The fields are those of the last search direction (quirk
+ * B-12), as for calipso_hip_differentiate: grad_theta = S' v for the S = dw/dtheta that calipso_hip_differentiate would return on the same handle state.
+ * Host arrays:
+ *   cotangent   N x k, column-major, required
+ *   adjoint     N x k = lambda = M' v, or NULL
+ *   grad_theta  np x k = -R_theta' lambda = S' v, or NULL (the parameter Jacobians are evaluated as by calipso_hip_differentiate: `eval`, or the device evaluator)
+ *   grad_qp     NULL, or six pointers in the order P, q, A, b, G, h (NULLs skipped) on a handle with calipso_hip_qp_attach: per cotangent column the gradient with
+ *               respect to that array of the QP, each k x size with the matrices column-major as calipso_hip_qp_attach takes them:
+ *               P: -c (lambda_x x' + x lambda_x'); q: -lambda_x; A: -(lambda_y x' + y lambda_x'); b: lambda_y; G: lambda_z x' + z lambda_x'; h: -lambda_z
+ *               with x, y, z of the resident point and c the objective scale
+ * "opt.differentiate_refinement" = 1 with iterative_refinement = 1: the correction rounds of calipso_hip_differentiate on all cotangent columns, against H' (E = v - H'
+ * lambda; the same per-column stopping and restoring decisions).  Inert on a handle with any second-order cone, as for calipso_hip_differentiate (quirk B-3): the result is the
+ * unrefined transposed map bit for bit.
+ * The call keeps its own workspace (grown on demand, kept, counted in the device bytes of calipso_hip_kernel_times); it leaves solution_sensitivity and the workspace
+ * of calipso_hip_differentiate alone.  CALIPSO_ERR_ARGUMENT with calipso_hip_last_error naming the argument: a NULL handle, k < 1 (or above 65535), a NULL cotangent,
+ * grad_theta with np = 0, grad_qp on a handle without an attached QP.  A compact structured handle whose block products are not available is refused with the message of
+ * calipso_hip_differentiate. */
+int32_t calipso_hip_differentiate_adjoint(calipso_hip_solver*, calipso_eval_fn eval, void* user, int64_t k,
+                                          const double* cotangent,   /* N x k, column-major, required */
+                                          double* adjoint,           /* N x k = lambda = M' v, or NULL */
+                                          double* grad_theta,        /* np x k = -R_theta' lambda = S' v, or NULL */
+                                          double* const* grad_qp);   /* NULL, or six pointers P, q, A, b, G, h (NULLs skipped), each k x size, column-major matrices */
+/* as calipso_hip_differentiate_info, for the last reverse call: [cotangent columns, correction rounds run (largest over the columns), columns that did not meet the
+ * stopping test, largest final column norm ||v - H' lambda||_inf]; zeros when no round ran, out[0] is still filled in */
+int32_t calipso_hip_differentiate_adjoint_info(calipso_hip_solver*, double out[4]);
+/* HIP-event times of the last reverse call in ms (a deliberate addition for callers that budget the call, and for bench/differentiate_adjoint.py): [0] from its entry to
+ * its last kernel (evaluation of the parameter Jacobians — a host callback included, when grad_theta is asked for —, factorisation, transposed solve, rounds, gradient
+ * kernels), [1] the copies of the results to the host arrays, [2] of [0] the QP data-gradient kernels alone, between events of their own (0 without grad_qp) */
+int32_t calipso_hip_differentiate_adjoint_times(calipso_hip_solver*, double out[3]);
 /* install a device-side evaluator (NULL removes it): calipso_hip_solve / calipso_hip_differentiate / the group drivers then call it instead
  * of the host callback (their `eval` argument may be NULL), and calipso_hip_device_evaluate runs it on point `which` (0 solution, 1 candidate) */
 int32_t calipso_hip_set_device_evaluator(calipso_hip_solver*, calipso_device_eval_fn fn, void* user);

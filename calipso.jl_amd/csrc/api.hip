@@ -316,9 +316,9 @@ int32_t calipso_hip_destroy(H* s) {
     if (s->spS_inv) { (void)hipFree(s->spS_inv); s->spS_inv = nullptr; }
     if (s->d_reach) { (void)hipFree(s->d_reach); s->d_reach = nullptr; }
     calipso::blocks_release(s);
-    double* dp[] = {s->slab, s->Kdense, s->multi_rhs, s->dsym_multi, s->evalL, s->evalZ, s->diff_refine, s->adj_work, s->adj_qp};
+    double* dp[] = {s->slab, s->Kdense, s->evalL, s->evalZ, s->fwd.d, s->rev.d, s->adj_qp};
     for (double* p : dp) if (p) (void)hipFree(p);
-    int* ip[] = {s->cone.soc_start, s->cone.soc_dim, s->cone.soc_woff, s->cone.entry_soc, s->cone.wide, s->zgrp, s->gate, s->diff_active, s->adj_active};
+    int* ip[] = {s->cone.soc_start, s->cone.soc_dim, s->cone.soc_woff, s->cone.entry_soc, s->cone.wide, s->zgrp, s->gate, s->fwd.active, s->rev.active};
     for (int* p : ip) if (p) (void)hipFree(p);
     if (s->hscal) (void)hipHostFree(s->hscal);
     if (s->hicount) (void)hipHostFree(s->hicount);
@@ -1131,25 +1131,6 @@ static int inner_iteration(H* s, calipso_eval_fn eval, void* user, double equali
     return warn;
 }
 
-// the workspaces of the reverse mode (calipso_hip_differentiate_adjoint): grown on demand (never shrunk), kept, counted in scratch_bytes — a call that repeats its
-// shapes allocates nothing
-template <class T>
-static int adjoint_reserve(H* s, T** buf, size_t* have, size_t want, const char* what) {
-    if (want <= *have) return CALIPSO_OK;
-    CK(hipStreamSynchronize(s->stream));           // (nothing queued may still use the buffer that goes)
-    if (*buf) { (void)hipFree(*buf); *buf = nullptr; s->scratch_bytes -= *have * sizeof(T); *have = 0; }
-    if (hipMalloc((void**)buf, want * sizeof(T)) != hipSuccess) {
-        (void)hipGetLastError();
-        *buf = nullptr;
-        char msg[192];
-        snprintf(msg, sizeof msg, "calipso_hip_differentiate_adjoint: %s (%zu bytes) could not be allocated", what, want * sizeof(T));
-        s->err = msg;
-        return CALIPSO_ERR_HIP;
-    }
-    *have = want; s->scratch_bytes += want * sizeof(T);
-    return CALIPSO_OK;
-}
-
 extern "C" {
 
 int32_t calipso_hip_cone(H* s, int32_t which, int32_t flags) { if (!s) return CALIPSO_ERR_ARGUMENT; launch_cone(s, point_of(s, which), flags); return CALIPSO_OK; }
@@ -1275,198 +1256,29 @@ int32_t calipso_hip_stats(H* s, int64_t out[8]) {
     return CALIPSO_OK;
 }
 
-// the condensed solve of differentiate.jl:29-58 for p right-hand-side columns `rhs` (N apart) through the current factors: out = scale * H^-1 rhs (as far as the
-// condensed, constraint-first solve gets).  The reference solves one condensed system per parameter column; here all columns go through the same factors together:
-// condensation per column, mat-vecs as GEMMs, block triangular solves as TRSMs
-static int solve_columns(H* s, const double* rhs, int p, double* out, double scale) {
-    const Dims& d = s->d;
-    const size_t NPd = d.NP, M = d.m, n = d.n;
-    if (!s->multi_rhs) {
-        if (dalloc(s, &s->multi_rhs, (n + 3 * NPd + 2 * M) * (size_t)p) || dalloc(s, &s->dsym_multi, n * (size_t)p)) return CALIPSO_ERR_HIP;
-    }
-    double* rsymM = s->multi_rhs;                  // n  x p   condensed right-hand sides
-    double* xbufM = rsymM + n * p;                 // NP x p   b_x (zero padded) -> dx
-    double* uM = xbufM + NPd * p;                  // NP x p   forward-substitution scratch
-    double* zM = uM + NPd * p;                     // NP x p
-    double* t1M = zM + NPd * p;                    // m  x p   Omega b_m
-    double* t2M = t1M + M * p;                     // m  x p   [gx; hx] dx
-    launch_residual_symmetric_multi(s, rhs, p, rsymM, xbufM, t1M);
-    // (a handle that works on stage blocks — every structured handle — takes the products block by block, all columns in one launch each; its factor lives in the
-    // fronts of the multifrontal LDL^T, which take all columns through the tree together: trsm_multi)
-    if (d.m && !blocks_gemm_t(s, t1M, d.m, xbufM, d.NP, p, 1.0)) {
-        if (s->compact) { s->err = "calipso_hip_differentiate: the block products are not available on this structured handle"; return CALIPSO_ERR_HIP; }
-        gemm(s, d.nx, p, d.m, 1.0, s->Z, d.m, true, t1M, d.m, 1.0, xbufM, d.NP);           // b_x + [gx; hx]' Omega b_m
-    }
-    trsm_multi(s, xbufM, p, uM, zM);                                                        // dx = S^-1 (...)
-    if (d.m && !blocks_gemm_n(s, xbufM, d.NP, t2M, d.m, p)) {
-        if (s->compact) { s->err = "calipso_hip_differentiate: the block products are not available on this structured handle"; return CALIPSO_ERR_HIP; }
-        gemm(s, d.m, p, d.nx, 1.0, s->Z, d.m, false, xbufM, d.NP, 0.0, t2M, d.m);          // [gx; hx] dx
-    }
-    launch_recover_multi(s, rhs, p, rsymM, xbufM, t2M, out, scale);
-    return CALIPSO_OK;
-}
-
-// E = R - H X for all p columns with the unreduced, matrix-free H (what k_refine_local / k_refine_x form for one vector), and their infinity norms.  The products
-// land in the caller's hxM (NP x p: Lxx X_x + [gx; hx]' X_yz) and zxM (m x p: [gx; hx] X_x)
-// (transposed: E = R - H' X for the reverse mode's rounds — Lxx' X_x in the x rows, the (s, t) rows swapped (k_refine_rows_multi); every other block of H is symmetric)
-static int residual_columns(H* s, const double* R, bool transposed, const double* X, int p, double* hxM, double* zxM, double* E, double* part, double* norms) {
-    const Dims& d = s->d;
-    if (!blocks_gemm_l(s, X, d.N, hxM, d.NP, p, transposed)) {
-        if (s->compact) { s->err = "calipso_hip_differentiate: the Hessian block product is not available on this structured handle"; return CALIPSO_ERR_HIP; }
-        gemm(s, d.nx, p, d.nx, 1.0, s->Lxx, d.nx, transposed, X, d.N, 0.0, hxM, d.NP);      // Lxx X_x (Lxx' X_x)
-    }
-    if (d.m) {
-        if (!blocks_gemm_t(s, X + d.oy(), d.N, hxM, d.NP, p, 1.0)) {                        // + [gx; hx]' X_yz (y and z are adjacent in a Point)
-            if (s->compact) { s->err = "calipso_hip_differentiate: the block products are not available on this structured handle"; return CALIPSO_ERR_HIP; }
-            gemm(s, d.nx, p, d.m, 1.0, s->Z, d.m, true, X + d.oy(), d.N, 1.0, hxM, d.NP);
-        }
-        if (!blocks_gemm_n(s, X, d.N, zxM, d.m, p)) {                                       // [gx; hx] X_x
-            if (s->compact) { s->err = "calipso_hip_differentiate: the block products are not available on this structured handle"; return CALIPSO_ERR_HIP; }
-            gemm(s, d.m, p, d.nx, 1.0, s->Z, d.m, false, X, d.N, 0.0, zxM, d.m);
-        }
-    }
-    launch_refine_rows_multi(s, X, R, zxM, p, E, part, transposed);
-    launch_refine_x_multi(s, X, R, hxM, d.NP, p, E, part, norms);
-    return CALIPSO_OK;
-}
-
-// The transposed pipeline of solve_columns for p cotangent columns V (N apart) through the current factors: lam = M' V for the map M solve_columns applies to a column
-// (scale 1).  Its stages in reverse order: k_recover_t, Z'., S^-1 (symmetric: factored from one triangle), Z., k_residual_symmetric_t.  work: 3 NP p + 2 m p doubles.
-// One column takes the triangular solve and the mat-vecs of a Newton step's condensed solve (linear_solve_device) instead of the GEMM forms.
-static size_t adjoint_pipeline_doubles(const Dims& d, int p) { return (3 * (size_t)d.NP + 2 * (size_t)d.m) * (size_t)p; }
-static int solve_columns_t(H* s, double* work, const double* V, int p, double* lam) {
-    const Dims& d = s->d;
-    const size_t NPd = d.NP, M = d.m;
-    double* xbufM = work;                          // NP x p   [V_x; 0] -> xb
-    double* uM = xbufM + NPd * p;                  // NP x p   forward-substitution scratch
-    double* zM = uM + NPd * p;                     // NP x p
-    double* gM = zM + NPd * p;                     // m  x p   the seed of the x-system
-    double* t1M = gM + M * p;                      // m  x p   [gx; hx] xb
-    launch_recover_t_multi(s, V, p, lam, gM, xbufM);
-    if (p == 1 && !s->compact) {
-        if (d.m) gemv_t(s, d.m, d.nx, s->Z, d.m, gM, xbufM, 1.0, 1.0, SP_Z);
-        launch_trsv(s, xbufM);
-        if (d.m) gemv_n(s, d.m, d.nx, s->Z, d.m, xbufM, t1M, 1.0, 0.0, SP_Z);
-    } else {
-        if (d.m && !blocks_gemm_t(s, gM, d.m, xbufM, d.NP, p, 1.0)) {
-            if (s->compact) { s->err = "calipso_hip_differentiate: the block products are not available on this structured handle"; return CALIPSO_ERR_HIP; }
-            gemm(s, d.nx, p, d.m, 1.0, s->Z, d.m, true, gM, d.m, 1.0, xbufM, d.NP);            // v_x + [gx; hx]' g
-        }
-        trsm_multi(s, xbufM, p, uM, zM);                                                        // xb = S^-1 (...)
-        if (d.m && !blocks_gemm_n(s, xbufM, d.NP, t1M, d.m, p)) {
-            if (s->compact) { s->err = "calipso_hip_differentiate: the block products are not available on this structured handle"; return CALIPSO_ERR_HIP; }
-            gemm(s, d.m, p, d.nx, 1.0, s->Z, d.m, false, xbufM, d.NP, 0.0, t1M, d.m);          // [gx; hx] xb
-        }
-    }
-    launch_residual_symmetric_t_multi(s, p, gM, xbufM, t1M, lam);
-    return CALIPSO_OK;
-}
-
-// The loop of iterative_refinement.jl:14-44 over p columns at once, for differentiate! (E = R - H X, corrections through solve_columns) and for its reverse mode
-// (E = R - H' X, corrections through solve_columns_t): residual against the unreduced matrix, column norms (one read-back of p doubles per round), the correction
-// through the same factors, X(:, j) += correction(:, j) for the columns still active.  The per-column decisions are sensitivity_columns.hpp's.
-struct ColumnRounds {
-    const double* R; bool transposed; int p;
-    double *X, *E, *C, *Xsave, *part, *norms;      // N x p each; nparts x p; p
-    double *hxM, *zxM;                             // NP x p, m x p: the products of residual_columns
-    double* pipeline;                              // transposed: the workspace of solve_columns_t
-    int* active;                                   // 2 p
-    SensitivityColumns* cols; double* hnorms; const char* refused;
-};
-static int refine_columns(H* s, const ColumnRounds& r) {
-    const int p = r.p;
-    SensitivityColumns& cols = *r.cols;
-    cols.begin(p);
-    for (;;) {
-        int rc = residual_columns(s, r.R, r.transposed, r.X, p, r.hxM, r.zxM, r.E, r.part, r.norms);
-        if (rc < 0) return rc;
-        CK(hipMemcpyAsync(r.hnorms, r.norms, sizeof(double) * (size_t)p, hipMemcpyDeviceToHost, s->stream));
-        if (launch_errors(s, r.refused)) return CALIPSO_ERR_HIP;
-        SYNC();
-        cols.judge(s->opt, r.hnorms);
-        if (cols.n_restore) {      // a round that only min_iterative_refinement asked for raised these columns' norms: they go back to the iterate they had
-            CK(hipMemcpyAsync(r.active + p, cols.restore.data(), sizeof(int) * (size_t)p, hipMemcpyHostToDevice, s->stream));
-            launch_restore_masked(s, r.active + p, r.Xsave, p, r.X);
-            SYNC();                // (cols.restore is rewritten by the next judge)
-        }
-        if (cols.finished()) break;
-        CK(hipMemcpyAsync(r.active, cols.active.data(), sizeof(int) * (size_t)p, hipMemcpyHostToDevice, s->stream));
-        rc = r.transposed ? solve_columns_t(s, r.pipeline, r.E, p, r.C) : solve_columns(s, r.E, p, r.C, 1.0);
-        if (rc < 0) return rc;
-        launch_accumulate_masked(s, r.active, r.C, p, r.X, r.Xsave);
-    }
-    return CALIPSO_OK;
-}
-
-// differentiate! with "opt.differentiate_refinement" = 1 on a handle without second-order cones: the unrefined pass kept as the step matrix X (sensitivity = -X), then
-// the loop of iterative_refinement.jl:14-44 over all columns at once — residual against the unreduced H, column norms (one read-back of p doubles per round), the
-// correction through the same factors and the same multi-column pipeline, X(:, j) += correction(:, j) for the columns still active.  The per-column decisions are
-// sensitivity_columns.hpp's (refine_next with the handle's options).  A column that fails its test keeps its last iterate and is counted (differentiate! has no fallback);
-// a column already within the tolerance takes the round min_iterative_refinement asks for only if that does not raise its norm (its iterate is saved and put back).
-static int differentiate_refined(H* s) {
-    const Dims& d = s->d;
-    const int p = d.np;
-    const size_t Np = (size_t)d.N * p, nparts = (size_t)refine_multi_parts(s);
-    if (!s->diff_refine) {
-        const size_t bytes = (4 * Np + (nparts + 1) * (size_t)p) * sizeof(double), ibytes = 2 * (size_t)p * sizeof(int);
-        if (hipMalloc((void**)&s->diff_refine, bytes) != hipSuccess || hipMalloc((void**)&s->diff_active, ibytes) != hipSuccess) {
-            (void)hipGetLastError();
-            if (s->diff_refine) { (void)hipFree(s->diff_refine); s->diff_refine = nullptr; }
-            s->diff_active = nullptr;
-            char buf[192];
-            snprintf(buf, sizeof buf, "calipso_hip_differentiate: the workspace of the correction rounds (%zu + %zu bytes for %d columns) could not be allocated", bytes, ibytes, p);
-            s->err = buf;
-            return CALIPSO_ERR_HIP;
-        }
-        s->scratch_bytes += bytes + ibytes;
-        s->diff_norms.assign((size_t)p, 0.0);
-    }
-    double* X = s->diff_refine; double* E = X + Np; double* C = E + Np; double* Xsave = C + Np; double* part = Xsave + Np; double* norms = part + nparts * (size_t)p;
-    int rc = solve_columns(s, s->jacobian_parameters, p, X, 1.0);
-    if (rc < 0) return rc;
-    // (the products of residual_columns land in workspace of solve_columns that is free between two solves: its forward-substitution scratch and its t2)
-    const size_t NPd = d.NP, M = d.m, n = d.n;
-    ColumnRounds r{s->jacobian_parameters, false, p, X, E, C, Xsave, part, norms, s->multi_rhs + (n + NPd) * (size_t)p, s->multi_rhs + (n + 3 * NPd + M) * (size_t)p, nullptr,
-                   s->diff_active, &s->diff_cols, s->diff_norms.data(), "a kernel launch of differentiate!'s correction rounds was refused"};
-    rc = refine_columns(s, r);
-    if (rc < 0) return rc;
-    launch_scale_into(s, X, s->solution_sensitivity, Np, -1.0);      // :54-56 sensitivity = -step
-    s->diff_cols.report(s->diff_info);
-    return CALIPSO_OK;
-}
-
+static const uint32_t PARAMETER_JACOBIANS = CALIPSO_EVAL_OBJECTIVE_JACOBIAN_PARAMETERS | CALIPSO_EVAL_EQUALITY_JACOBIAN_PARAMETERS | CALIPSO_EVAL_EQUALITY_DUAL_JACOBIAN_PARAMETERS |
+                                            CALIPSO_EVAL_CONE_JACOBIAN_PARAMETERS | CALIPSO_EVAL_CONE_DUAL_JACOBIAN_PARAMETERS;      // what differentiate! re-evaluates (differentiate.jl:3)
 // differentiate!  differentiate.jl:1-61
 int32_t calipso_hip_differentiate(H* s, calipso_eval_fn eval, void* user) {
     if (!s) return CALIPSO_ERR_ARGUMENT;
     const Dims& d = s->d;
     (void)hipGetLastError();      // (launch_errors: this call's launches only, as calipso_hip_solve)
-    s->diff_info[0] = (double)d.np; s->diff_info[1] = s->diff_info[2] = s->diff_info[3] = 0.0;
+    double* info = s->fwd.info; info[0] = (double)d.np; info[1] = info[2] = info[3] = 0.0;
     if (d.np == 0) return CALIPSO_OK;
-    int rc = evaluate(s, eval, user, 0, CALIPSO_EVAL_OBJECTIVE_JACOBIAN_PARAMETERS | CALIPSO_EVAL_EQUALITY_JACOBIAN_PARAMETERS |
-                                           CALIPSO_EVAL_EQUALITY_DUAL_JACOBIAN_PARAMETERS | CALIPSO_EVAL_CONE_JACOBIAN_PARAMETERS |
-                                           CALIPSO_EVAL_CONE_DUAL_JACOBIAN_PARAMETERS);
+    int rc = evaluate(s, eval, user, 0, PARAMETER_JACOBIANS);
     if (rc < 0) return rc;
     int64_t in[3];
     rc = do_factorize(s, in);                      // :13-20 (same regularisation as the last search direction)
     if (rc < 0) return rc;
     launch_jacobian_parameters(s);                 // :23
-    // :29-58 — one condensed solve for all np columns, unrefined as the reference's (its QDLDL works on the (nx + ne + nc) symmetric matrix and does not need more).
-    // "opt.differentiate_refinement": correction rounds on all columns (differentiate_refined) — not with second-order cones, where the reference's answer IS the
-    // unrefined solve with its triu-symmetrised cone blocks (quirk B-3: refining would move away from it, towards H^-1; the batch kernel does the same), and not
-    // with iterative_refinement = 0
-    if (s->differentiate_refinement && s->opt.iterative_refinement && d.n_soc == 0) rc = differentiate_refined(s);
-    else rc = solve_columns(s, s->jacobian_parameters, d.np, s->solution_sensitivity, -1.0);   // :54-56 sensitivity = -step
+    rc = differentiate_columns(s);                 // :29-58, all np columns together (columns.hip)
     if (rc < 0) return rc;
     SYNC();
     return CALIPSO_OK;
 }
 
 // [columns, correction rounds run (largest over the columns), columns that did not meet the stopping test, largest final column norm] of the last differentiate!
-int32_t calipso_hip_differentiate_info(H* s, double out[4]) {
-    if (!s || !out) return CALIPSO_ERR_ARGUMENT;
-    for (int i = 0; i < 4; ++i) out[i] = s->diff_info[i];
-    return CALIPSO_OK;
-}
+int32_t calipso_hip_differentiate_info(H* s, double out[4]) { if (!s || !out) return CALIPSO_ERR_ARGUMENT; for (int i = 0; i < 4; ++i) out[i] = s->fwd.info[i]; return CALIPSO_OK; }
 
 // differentiate! in reverse mode  differentiate.jl:1-61 and residual_jacobian_parameters.jl:1-40, transposed (include/calipso_hip.h)
 int32_t calipso_hip_differentiate_adjoint(H* s, calipso_eval_fn eval, void* user, int64_t k, const double* cotangent, double* adjoint, double* grad_theta,
@@ -1481,48 +1293,22 @@ int32_t calipso_hip_differentiate_adjoint(H* s, calipso_eval_fn eval, void* user
     CK(hipSetDevice(s->device));
     const int p = (int)k;
     const size_t Np = (size_t)d.N * p, nx = d.nx;
-    const bool rounds = s->differentiate_refinement && s->opt.iterative_refinement && d.n_soc == 0;      // as calipso_hip_differentiate: inert with second-order cones (quirk B-3)
-    const size_t nparts = (size_t)refine_multi_parts(s);
-    s->adj_info[0] = (double)p; s->adj_info[1] = s->adj_info[2] = s->adj_info[3] = 0.0;
+    double* info = s->rev.info; info[0] = (double)p; info[1] = info[2] = info[3] = 0.0;
     for (auto& e : s->adj_ev) if (!e) CK(hipEventCreate(&e));
-    // workspace: [pipeline | V | lam | grad_theta | (E, C, Xsave, partial norms, column norms)]
-    const size_t pipe = adjoint_pipeline_doubles(d, p), gth = grad_theta ? (size_t)d.np * p : 0;
-    int rc = adjoint_reserve(s, &s->adj_work, &s->adj_work_doubles, pipe + 2 * Np + gth + (rounds ? 3 * Np + (nparts + 1) * (size_t)p : 0), "the workspace of the transposed solve");
-    if (rc < 0) return rc;
-    if (rounds) {
-        rc = adjoint_reserve(s, &s->adj_active, &s->adj_active_ints, 2 * (size_t)p, "the column masks of the correction rounds");
-        if (rc < 0) return rc;
-        if (s->adj_norms.size() < (size_t)p) s->adj_norms.assign((size_t)p, 0.0);
-    }
     const size_t qsize[6] = {nx * nx, nx, (size_t)d.ne * nx, (size_t)d.ne, (size_t)d.nc * nx, (size_t)d.nc};
     size_t qtotal = 0;
     if (grad_qp) for (int a = 0; a < 6; ++a) if (grad_qp[a]) qtotal += qsize[a] * p;
-    if (qtotal) { rc = adjoint_reserve(s, &s->adj_qp, &s->adj_qp_doubles, qtotal, "the QP data gradients"); if (rc < 0) return rc; }
-    double* pipeline = s->adj_work; double* V = pipeline + pipe; double* lam = V + Np; double* gthM = lam + Np; double* E = gthM + gth;
-    double* C = E + Np; double* Xsave = C + Np; double* part = Xsave + Np; double* norms = part + nparts * (size_t)p;
+    int rc = reserve_device(s, (void**)&s->adj_qp, &s->adj_qp_doubles, qtotal, sizeof(double), 0, "calipso_hip_differentiate_adjoint", "the QP data gradients");
+    if (rc < 0) return rc;
     (void)hipEventRecord(s->adj_ev[0], s->stream);
-    if (grad_theta) {
-        rc = evaluate(s, eval, user, 0, CALIPSO_EVAL_OBJECTIVE_JACOBIAN_PARAMETERS | CALIPSO_EVAL_EQUALITY_JACOBIAN_PARAMETERS |
-                                           CALIPSO_EVAL_EQUALITY_DUAL_JACOBIAN_PARAMETERS | CALIPSO_EVAL_CONE_JACOBIAN_PARAMETERS |
-                                           CALIPSO_EVAL_CONE_DUAL_JACOBIAN_PARAMETERS);
-        if (rc < 0) return rc;
-    }
+    if (grad_theta && (rc = evaluate(s, eval, user, 0, PARAMETER_JACOBIANS)) < 0) return rc;
     int64_t in[3];
     rc = do_factorize(s, in);                      // differentiate.jl:13-20 (same regularisation as the last search direction)
     if (rc < 0) return rc;
     if (grad_theta) launch_jacobian_parameters(s);  // :23
-    CK(hipMemcpyAsync(V, cotangent, sizeof(double) * Np, hipMemcpyHostToDevice, s->stream));
-    rc = solve_columns_t(s, pipeline, V, p, lam);  // :29-58 transposed, all k columns at once
+    const double *lam = nullptr, *gthM = nullptr;
+    rc = differentiate_columns_t(s, p, cotangent, grad_theta != nullptr, &lam, &gthM);      // :29-58 transposed, all k columns together (columns.hip)
     if (rc < 0) return rc;
-    if (rounds) {
-        // the correction rounds of differentiate_refined against H': the products of residual_columns land in the pipeline's forward-substitution scratch and its t1
-        ColumnRounds r{V, true, p, lam, E, C, Xsave, part, norms, pipeline + (size_t)d.NP * p, pipeline + (3 * (size_t)d.NP + (size_t)d.m) * p, pipeline,
-                       s->adj_active, &s->adj_cols, s->adj_norms.data(), "a kernel launch of the reverse mode's correction rounds was refused"};
-        rc = refine_columns(s, r);
-        if (rc < 0) return rc;
-        s->adj_cols.report(s->adj_info);
-    }
-    if (grad_theta) gemm(s, d.np, p, d.N, -1.0, s->jacobian_parameters, d.N, true, lam, d.N, 0.0, gthM, d.np);      // -R_theta' lam = S' v
     double* qdev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     if (qtotal) {
         size_t off = 0;
@@ -1532,7 +1318,7 @@ int32_t calipso_hip_differentiate_adjoint(H* s, calipso_eval_fn eval, void* user
     }
     (void)hipEventRecord(s->adj_ev[1], s->stream);
     if (adjoint) CK(hipMemcpyAsync(adjoint, lam, sizeof(double) * Np, hipMemcpyDeviceToHost, s->stream));
-    if (grad_theta) CK(hipMemcpyAsync(grad_theta, gthM, sizeof(double) * gth, hipMemcpyDeviceToHost, s->stream));
+    if (grad_theta) CK(hipMemcpyAsync(grad_theta, gthM, sizeof(double) * (size_t)d.np * p, hipMemcpyDeviceToHost, s->stream));
     for (int a = 0; a < 6; ++a) if (qdev[a]) CK(hipMemcpyAsync(grad_qp[a], qdev[a], sizeof(double) * qsize[a] * p, hipMemcpyDeviceToHost, s->stream));
     (void)hipEventRecord(s->adj_ev[2], s->stream);
     if (launch_errors(s, "a kernel launch of calipso_hip_differentiate_adjoint was refused")) return CALIPSO_ERR_HIP;
@@ -1544,17 +1330,8 @@ int32_t calipso_hip_differentiate_adjoint(H* s, calipso_eval_fn eval, void* user
     return CALIPSO_OK;
 }
 
-int32_t calipso_hip_differentiate_adjoint_info(H* s, double out[4]) {
-    if (!s || !out) return CALIPSO_ERR_ARGUMENT;
-    for (int i = 0; i < 4; ++i) out[i] = s->adj_info[i];
-    return CALIPSO_OK;
-}
-
-int32_t calipso_hip_differentiate_adjoint_times(H* s, double out[3]) {
-    if (!s || !out) return CALIPSO_ERR_ARGUMENT;
-    out[0] = s->adj_ms[0]; out[1] = s->adj_ms[1]; out[2] = s->adj_ms[2];
-    return CALIPSO_OK;
-}
+int32_t calipso_hip_differentiate_adjoint_info(H* s, double out[4]) { if (!s || !out) return CALIPSO_ERR_ARGUMENT; for (int i = 0; i < 4; ++i) out[i] = s->rev.info[i]; return CALIPSO_OK; }
+int32_t calipso_hip_differentiate_adjoint_times(H* s, double out[3]) { if (!s || !out) return CALIPSO_ERR_ARGUMENT; for (int i = 0; i < 3; ++i) out[i] = s->adj_ms[i]; return CALIPSO_OK; }
 
 // solve!(solver)  solve.jl:8-377
 int32_t calipso_hip_solve(H* s, calipso_eval_fn eval, void* user) {

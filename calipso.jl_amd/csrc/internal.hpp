@@ -127,6 +127,14 @@ struct QpEval {
     double *q = nullptr, *bh = nullptr;   // device: q[nx], bh = [-b; h] (m)
 };
 
+struct ColumnWorkspace {                          // of a p-column pass (columns.hip; where everything lives in `d`: column_layout.hpp)
+    double* d = nullptr; size_t doubles = 0;      // the condensed pipeline and the columns (+ E, C, Xsave, partial and column norms when the rounds run)
+    int* active = nullptr; size_t ints = 0;       // 2 p: the device's copies of SensitivityColumns::active and ::restore
+    std::vector<double> norms;                    // host side of the per-round read-back (p)
+    SensitivityColumns cols;
+    double info[4] = {0, 0, 0, 0};                // calipso_hip_differentiate_info / _adjoint_info of the last call: [columns, rounds, failed columns, largest final norm]
+};
+
 struct Stats {
     i64 total_iterations = 0, outer = 0, factorizations = 0, refine_fail = 0, refine_max = 0, fallbacks = 0, last_refine = 0, newton_steps = 0;
 };
@@ -152,7 +160,7 @@ struct calipso_hip_solver {
     void* dev_eval_user = nullptr;
     calipso_device_block_eval_fn dev_block_eval = nullptr;   // structured handles: the evaluator writes the packed blocks (no dense scratch)
     void* dev_block_eval_user = nullptr;
-    size_t scratch_bytes = 0;                    // dense scratch of a structured handle with a dense-layout device evaluator (evalL / evalZ) + the workspace of differentiate!'s correction rounds (diff_refine)
+    size_t scratch_bytes = 0;                    // dense scratch of a structured handle with a dense-layout device evaluator (evalL / evalZ) + the workspaces of differentiate! (columns.hip: all but the forward's unrefined pipeline)
     bool rhs_ahead = false, rhs_joined = false;   // the operands of the first condensed solve were queued on the second stream during this factorisation (ldl.hip: ldl_rhs_stream) / the main stream has joined it
     double *evalL = nullptr, *evalZ = nullptr;   // structured handle with a device evaluator: dense scratch (nx^2, m nx) the evaluator writes; packed into the blocks behind it
     std::map<std::string, double*> optd;
@@ -238,24 +246,13 @@ struct calipso_hip_solver {
     double *saved_g = nullptr, *saved_h = nullptr;                          // ne, nc (benchmark-mode restore)
     double *lgp = nullptr, *gp = nullptr, *hp = nullptr;                    // nx*np, ne*np, nc*np parameter Jacobians
     std::vector<double> hparams;
-    double* multi_rhs = nullptr;  // workspace of the multi-right-hand-side solve of differentiate! (allocated on demand)
-    double* dsym_multi = nullptr; // n * np
+    // differentiate! (columns.hip): ONE pipeline takes p columns through the current factors in two directions, forward (calipso_hip_differentiate: the np parameter
+    // columns) and transposed (calipso_hip_differentiate_adjoint: k cotangent columns), each with a workspace of its own: neither call disturbs what the other left
+    calipso::ColumnWorkspace fwd, rev;
+    double* adj_qp = nullptr; size_t adj_qp_doubles = 0;          // the QP data gradients the last reverse calls asked for, k x size each (grown on demand, counted in scratch_bytes)
     // "opt.differentiate_refinement" (not an option of the reference: differentiate! there does not refine; a handle-level value like solve_block): 1 = the correction
-    // rounds of iterative_refinement.jl:14-44 on every column of differentiate! (api.hip: calipso_hip_differentiate); inert on a handle with second-order cones
+    // rounds of iterative_refinement.jl:14-44 on every column, in both directions; inert on a handle with second-order cones
     calipso::i64 differentiate_refinement = 0;
-    double* diff_refine = nullptr;     // its workspace, allocated on the first refined call and kept: X, E, C, Xsave (N x np each), the partial norms, the column norms
-    int* diff_active = nullptr;        // 2 np: the device's copies of SensitivityColumns::active and ::restore
-    calipso::SensitivityColumns diff_cols;
-    std::vector<double> diff_norms;    // host side of the per-round read-back (np)
-    double diff_info[4] = {0, 0, 0, 0};   // calipso_hip_differentiate_info of the last differentiate!
-    // differentiate! in reverse mode (api.hip: calipso_hip_differentiate_adjoint): its own workspace, grown on demand and kept (k cotangent columns, not np: the
-    // forward's multi_rhs stays as it is), counted in scratch_bytes
-    double* adj_work = nullptr; size_t adj_work_doubles = 0;      // the condensed pipeline, V, lambda, grad_theta (+ E, C, Xsave, partial and column norms when the rounds run)
-    double* adj_qp = nullptr; size_t adj_qp_doubles = 0;          // the QP data gradients asked for, k x size each
-    int* adj_active = nullptr; size_t adj_active_ints = 0;        // 2 k: SensitivityColumns::active and ::restore
-    calipso::SensitivityColumns adj_cols;
-    std::vector<double> adj_norms;
-    double adj_info[4] = {0, 0, 0, 0};    // calipso_hip_differentiate_adjoint_info of the last reverse call
     hipEvent_t adj_ev[4] = {};            // entry, behind the last kernel, behind the copies to the host, before the QP gradient kernels (created on the first reverse call)
     double adj_ms[3] = {0, 0, 0};          // calipso_hip_differentiate_adjoint_times of the last reverse call
     void* scatter_aux = nullptr;  // scatter.hip: registered sparsity patterns of the evaluate! scatter
@@ -409,7 +406,7 @@ void gemm(calipso_hip_solver* s, int M, int N, int K, double alpha, const double
           double* C, int ldc);
 void trsm_multi(calipso_hip_solver* s, double* X, int p, double* U, double* Zm);
 void launch_residual_symmetric_multi(calipso_hip_solver* s, const double* res, int p, double* rsym, double* xbuf, double* t1);
-void launch_recover_multi(calipso_hip_solver* s, const double* res, int p, const double* rsym, const double* xbuf, const double* t2, double* step, double scale);
+void launch_recover_multi(calipso_hip_solver* s, const double* res, int p, const double* rsym, const double* xbuf, const double* t2, double* dsym, double* step, double scale);
 // vectors.hip: the correction rounds of differentiate! on p columns together (handles without second-order cones).  E = R - H X: the rows r, s, y, z, t from zx = [gx; hx] X_x
 // (m apart) with refine_multi_parts(s) partial norms per column, then the rows x from hx = Lxx X_x + [gx; hx]' X_yz (ldh apart) and norms[c] = ||E(:, c)||_inf (NaN: +inf)
 int refine_multi_parts(const calipso_hip_solver* s);
@@ -418,6 +415,12 @@ void launch_refine_x_multi(calipso_hip_solver* s, const double* X, const double*
 void launch_accumulate_masked(calipso_hip_solver* s, const int* active, const double* C, int p, double* X, double* Xsave);      // X(:, c) += C(:, c) where active[c] (2: Xsave(:, c) = X(:, c) first)
 void launch_restore_masked(calipso_hip_solver* s, const int* restore, const double* Xsave, int p, double* X);                   // X(:, c) = Xsave(:, c) where restore[c]
 void launch_scale_into(calipso_hip_solver* s, const double* x, double* y, size_t n, double a);                 // y = a x
+// columns.hip: p columns through the current factors (the caller has evaluated the parameter Jacobians it needs, factored, and formed jacobian_parameters): solution_sensitivity =
+// -H^-1 jacobian_parameters (+ the correction rounds where the option asks); p cotangent columns from the host -> *lam (N x p), *grad_theta (np x p): device, the reverse workspace
+int differentiate_columns(calipso_hip_solver* s);
+int differentiate_columns_t(calipso_hip_solver* s, int p, const double* cotangent, bool with_theta, const double** lam, const double** grad_theta);
+// *buf holds >= want elements of `elem` bytes afterwards: grown on demand, never shrunk, zero-filled when fresh, counted in scratch_bytes but for its first `uncounted` elements
+int reserve_device(calipso_hip_solver* s, void** buf, size_t* have, size_t want, size_t elem, size_t uncounted, const char* caller, const char* what);
 // adjoint.hip: the first and the last stage of the condensed solve transposed (differentiate! in reverse mode), p cotangent columns in grid.y; the cones of
 // dimension > 4 in soc_wide.hip (launch_*_t_wide, called by these launchers)
 void launch_recover_t_multi(calipso_hip_solver* s, const double* V, int p, double* lam, double* g, double* xbuf);           // first contributions to lam_r, lam_s, lam_t; g (m x p); xbuf = [V_x; 0]

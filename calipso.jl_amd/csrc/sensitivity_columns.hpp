@@ -1,5 +1,5 @@
 // sensitivity_columns.hpp — the bookkeeping of differentiate! with "opt.differentiate_refinement": which parameter columns still take correction rounds, how many
-// each has taken, and when the whole loop ends.  The ONE copy of it (api.hip: calipso_hip_differentiate calls it); plain C++ like step_decisions.hpp (no HIP, no
+// each has taken, and when the whole loop ends.  The ONE copy of it (columns.hip: refine_columns calls it, for differentiate! and for its reverse mode); plain C++ like step_decisions.hpp (no HIP, no
 // handle, no device): tests/sensitivity_columns runs it on the CPU.  Every column is the loop of iterative_refinement.jl:14-44 on its own: its own round count and
 // first norm, the verdict of step_decisions.hpp: refine_next on the norms the device reports.
 #pragma once

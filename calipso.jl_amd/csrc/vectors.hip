@@ -369,24 +369,24 @@ __global__ void k_scale_inplace(size_t n, double* __restrict__ x, double a) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) x[i] = a * x[i];
 }
-// all p columns at once; rsym is reused as the dsym scratch (each lane reads b before the same lane writes dsym)
-void launch_recover_multi(calipso_hip_solver* s, const double* res, int p, const double* rsym, const double* xbuf, const double* t2, double* step, double scale) {
+// all p columns at once; dsym (n x p): the scratch the condensed steps go to, as step_symmetric for one vector (the caller's: nothing reads it afterwards)
+void launch_recover_multi(calipso_hip_solver* s, const double* res, int p, const double* rsym, const double* xbuf, const double* t2, double* dsym, double* step, double scale) {
     const int work = s->d.nx + s->d.ne + s->d.q + s->d.n_soc;
     const BatchSc B = batch_of(s);
     hipLaunchKernelGGL(k_recover, dim3((work + 127) / 128, p, 1), dim3(128), 0, s->stream, B, s->d, s->cone, s->solution, res,
-                       rsym, xbuf, t2, s->wz, s->Wsoc, s->dsym_multi, step, (double*)nullptr, (double*)nullptr, 0);
-    launch_recover_wide(s, res, p, rsym, t2, s->dsym_multi, step, nullptr, 0);
+                       rsym, xbuf, t2, s->wz, s->Wsoc, dsym, step, (double*)nullptr, (double*)nullptr, 0);
+    launch_recover_wide(s, res, p, rsym, t2, dsym, step, nullptr, 0);
     if (scale != 1.0) {
         const size_t n = (size_t)s->d.N * p;
         hipLaunchKernelGGL(k_scale_inplace, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, n, step, scale);
     }
 }
 
-// ---- correction rounds of differentiate! on all parameter columns together ("opt.differentiate_refinement", api.hip: calipso_hip_differentiate) ---------------
+// ---- correction rounds of differentiate! on all parameter columns together ("opt.differentiate_refinement", columns.hip: refine_columns) ---------------
 // E = R_theta - H X with the unreduced H (iterative_refinement.jl:8-12,38-41 per column), handles WITHOUT second-order cones.  Columns in grid.y as in k_residual_symmetric:
 // X, R, E are N apart, zx = [gx; hx] X_x is m apart, hx_ = Lxx X_x + [gx; hx]' X_yz is ldh apart.  Single instance (the multi-column path has no group form).
 // rows r, s, y, z, t: one work item per constraint, the expressions of k_refine_local; part[blockIdx.x + gridDim.x * column] = the workgroup's part of the column's norm
-// TR: E = R - H' X (the reverse mode's rounds, api.hip: calipso_hip_differentiate_adjoint).  Without second-order cones H and H' differ in the (s, t) rows only:
+// TR: E = R - H' X (the reverse mode's rounds, columns.hip: differentiate_columns_t).  Without second-order cones H and H' differ in the (s, t) rows only:
 // (H' v)_s = ep v_s - v_z + T v_t, (H' v)_t = -v_s + (S - ed) v_t
 constexpr int RM_THREADS = 256;
 template <bool TR>

@@ -1,6 +1,6 @@
 // The column bookkeeping of differentiate!'s correction rounds (calipso.jl_amd/csrc/sensitivity_columns.hpp) against cases worked out by hand from the loop of
 // iterative_refinement.jl:14-51, which every column runs on its own (step_decisions.hpp: refine_next).  Stand-alone: only the two pure headers are included;
-// tests/test_sensitivity_columns_cpu.py builds this with the host compiler and runs it.  The driver below is the loop of api.hip: differentiate_refined without the
+// tests/test_sensitivity_columns_cpu.py builds this with the host compiler and runs it.  The driver below is the loop of columns.hip: refine_columns without the
 // device: judge the norms of the unrefined columns, then one judge() behind every round, until no column is active.
 #include <cstdio>
 #include <limits>

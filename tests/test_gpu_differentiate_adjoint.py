@@ -1,4 +1,4 @@
-"""differentiate! in reverse mode on a Solver handle (calipso_hip_differentiate_adjoint, csrc/api.hip + csrc/adjoint.hip + the wide-cone kernels of csrc/soc_wide.hip):
+"""differentiate! in reverse mode on a Solver handle (calipso_hip_differentiate_adjoint, csrc/api.hip + csrc/columns.hip + csrc/adjoint.hip + the wide-cone kernels of csrc/soc_wide.hip):
 Solver.vjp against the ORACLE's forward maps — search_direction_symmetric! column by column at interior points (the transposed map itself, every cone branch), the
 sensitivities of differentiate! at solutions (grad_theta = S' v, with and without the correction rounds against H'), the multifrontal factor, the QP data gradients
 (closed forms, signs against a parametric handle, P / A / G against a problem whose parameters move them) and torch_layer.SolverQPLayer.

@@ -1,5 +1,5 @@
 """differentiate! on a Solver handle with set_option("differentiate_refinement", 1): the correction rounds of iterative_refinement.jl:14-44 on all parameter columns
-together (calipso_hip_differentiate, csrc/api.hip: differentiate_refined), against the oracle's differentiate! (QDLDL on the (nx + ne + nc) symmetric matrix, unrefined)
+together (calipso_hip_differentiate, csrc/columns.hip: differentiate_columns), against the oracle's differentiate! (QDLDL on the (nx + ne + nc) symmetric matrix, unrefined)
 at solution-like points — penalty 1e7, central path 1e-7 — where the constraint-first condensed solve of the default path loses digits.
 
 The 1e-8 bound: at these points the oracle's sensitivities are within 7e-10 (relative to max(1, |S|)) of an extended-precision solve of the dense H

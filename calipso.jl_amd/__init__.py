@@ -588,6 +588,67 @@ class Group:
             raise CalipsoHipError("group_solve: %s (%d): %s" % (STATUS_TEXT.get(rc, "error"), rc, self._L.calipso_hip_last_error(self.solvers[0]._h).decode()))
         return [int(v) for v in res]
 
+    def vjp(self, cotangent, adjoint=True, theta=None, qp=None):
+        """differentiate! in reverse mode for every member through the same launches (calipso_hip_group_differentiate_adjoint): per member what Solver.vjp gives on the
+        handle alone with differentiate_refinement off.  cotangent: (count, N) or (count, N, k), member i's cotangents at its resident point.  theta, qp: as for Solver.vjp
+        (the parameter Jacobians of members without a device evaluator come through their host callbacks, as in solve()).  Returns a dict of arrays with a leading member
+        axis: "adjoint" (count, N[, k]), "theta" (count, np[, k]), one entry per requested QP array in qp_attach's shape (count, ...[, k]), and "status" (count,); the
+        trailing k axis only when the cotangent had one."""
+        import ctypes as C
+        s0 = self.solvers[0]
+        B, N, npar = len(self.solvers), s0.N, s0.np
+        squeeze = True
+        if cotangent is None:
+            vc, k = None, 1
+        else:
+            v = np.asarray(cotangent, dtype=np.float64)
+            squeeze = v.ndim == 2
+            if squeeze:
+                v = v[:, :, None]
+            if v.ndim != 3 or v.shape[0] != B or v.shape[1] != N:
+                raise ValueError("cotangent must be (count, N) or (count, N, k)")
+            k = v.shape[2]
+            vc = np.ascontiguousarray(np.transpose(v, (0, 2, 1))).ravel()       # member-major, column-major N x k per member
+        if theta is None:
+            theta = npar > 0
+        names = "PqAbGh" if qp is True else (qp or "")
+        if any(c not in "PqAbGh" for c in names):
+            raise ValueError("qp must be True or a string of names out of 'PqAbGh'")
+        nx, ne, nc = s0.nx, s0.ne, s0.nc
+        shape = dict(P=(nx, nx), q=(nx,), A=(ne, nx), b=(ne,), G=(nc, nx), h=(nc,))
+        kk = max(k, 1)
+        adj = np.zeros(B * kk * N) if adjoint else None
+        gth = np.zeros(max(B * kk * npar, 1)) if theta else None
+        arrays = {c: np.zeros(max(B * kk * int(np.prod(shape[c])), 1)) for c in names}
+        ptrs = None
+        if names:
+            ptrs = (C.POINTER(C.c_double) * 6)(*[_pd(arrays[c]) if c in arrays else None for c in "PqAbGh"])
+        opt = lambda a: _pd(a) if a is not None else None
+        status = np.zeros(B, dtype=np.int32)
+        ms = C.c_double(0.0)
+        self._evals = (EVAL_FN * B)(*[s._cb for s in self.solvers])       # host callbacks (used by members without a device evaluator)
+        self._L.calipso_hip_group_set_evaluators(self._g, self._evals, None)
+        rc = self._L.calipso_hip_group_differentiate_adjoint(self._g, int(k), opt(vc), opt(adj), opt(gth), ptrs, status.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(ms))
+        if rc < 0:
+            raise CalipsoHipError("group_differentiate_adjoint: %s (%d): %s" % (STATUS_TEXT.get(rc, "error"), rc, self._L.calipso_hip_last_error(s0._h).decode()))
+        self._vjp_ms = float(ms.value)
+        fin = lambda a: a[..., 0] if squeeze else a
+        out = {}
+        if adjoint:
+            out["adjoint"] = fin(np.transpose(adj.reshape(B, k, N), (0, 2, 1)).copy())
+        if theta:
+            out["theta"] = fin(np.transpose(gth[:B * k * npar].reshape(B, k, npar), (0, 2, 1)).copy())
+        for c in names:
+            sh = shape[c]
+            a = arrays[c][:B * k * int(np.prod(sh))]
+            out[c] = fin(np.transpose(a.reshape(B, k, nx, sh[0]), (0, 3, 2, 1)).copy() if len(sh) == 2 else np.transpose(a.reshape(B, k, sh[0]), (0, 2, 1)).copy())
+        out["status"] = status
+        return out
+
+    def vjp_ms(self):
+        """HIP-event time in ms of the last vjp(), from its first enqueue to its last kernel"""
+        return getattr(self, "_vjp_ms", 0.0)
+
     def phase_times(self):
         return self.solvers[0].phase_times()
 

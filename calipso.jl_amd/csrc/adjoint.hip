@@ -10,7 +10,8 @@
 // unrolled to constant indices (as the forward kernels of vectors.hip); wider cones: one wavefront per cone (soc_wide.hip).  W (the cone's block of Omega) is applied
 // transposed by swapping its indices: nothing here assumes that it is symmetric.  The dt recovery keeps the reference's quirk (second_order.jl:63-65: the arrow inverse
 // sees the first row of Cbar_t only), so this is the transpose of the map the forward kernels compute, not of H^-1.
-// Single instance (the multi-column path has no group form): the handle's scalars by value, no instance shift.
+// Every kernel takes the instance from blockIdx.z (a handle alone is a batch of one): the point, the cone weights and the scalars are the member's (Batch::delta,
+// BatchSc::scal), the column regions hold the members' columns slot after slot (device_utils.hpp: column_shift) — calipso_hip_group_differentiate_adjoint (group.hip).
 #include "internal.hpp"
 #include "device_utils.hpp"
 
@@ -19,13 +20,16 @@ namespace calipso {
 constexpr int ADJ_THREADS = 128;
 
 // work items: [0, NP) xbuf = [v_x; 0]; then one per equality row, per nonnegative entry, per second-order cone
-__global__ __launch_bounds__(ADJ_THREADS) void k_recover_t(Scalars sc, Dims d, ConeDev cd, const double* __restrict__ w, const double* __restrict__ V_,
+__global__ __launch_bounds__(ADJ_THREADS) void k_recover_t(BatchSc bt, Dims d, ConeDev cd, const double* __restrict__ w, const double* __restrict__ V_,
                                                             const double* __restrict__ wz, const double* __restrict__ Wsoc, double* __restrict__ lam_,
                                                             double* __restrict__ g_, double* __restrict__ xbuf_) {
-    const double* v = V_ + (size_t)blockIdx.y * d.N;
-    double* lam = lam_ + (size_t)blockIdx.y * d.N;
-    double* g = g_ + (size_t)blockIdx.y * d.m;
-    double* xbuf = xbuf_ + (size_t)blockIdx.y * d.NP;
+    inst_shift(bt.b, w, wz, Wsoc);
+    const Scalars sc = bt.scal(blockIdx.z);
+    const size_t col = column_shift(bt.b, gridDim.y) + blockIdx.y;      // the column among the columns of all members
+    const double* v = V_ + col * d.N;
+    double* lam = lam_ + col * d.N;
+    double* g = g_ + col * d.m;
+    double* xbuf = xbuf_ + col * d.NP;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const double Hrr = sc.rho + sc.ep, Hss = 0.0 + sc.ep;
     if (i < d.NP) { xbuf[i] = i < d.nx ? v[i] : 0.0; return; }
@@ -100,13 +104,16 @@ __global__ __launch_bounds__(ADJ_THREADS) void k_recover_t(Scalars sc, Dims d, C
 }
 
 // work items: [0, nx) lam_x = xb; then one per equality row, per nonnegative entry, per second-order cone (the item that wrote the row's first contributions)
-__global__ __launch_bounds__(ADJ_THREADS) void k_residual_symmetric_t(Scalars sc, Dims d, ConeDev cd, const double* __restrict__ w, const double* __restrict__ g_,
+__global__ __launch_bounds__(ADJ_THREADS) void k_residual_symmetric_t(BatchSc bt, Dims d, ConeDev cd, const double* __restrict__ w, const double* __restrict__ g_,
                                                                        const double* __restrict__ xb_, const double* __restrict__ t1_, const double* __restrict__ wz,
                                                                        const double* __restrict__ Wsoc, double* __restrict__ lam_) {
-    const double* g = g_ + (size_t)blockIdx.y * d.m;
-    const double* xb = xb_ + (size_t)blockIdx.y * d.NP;
-    const double* t1 = t1_ + (size_t)blockIdx.y * d.m;
-    double* lam = lam_ + (size_t)blockIdx.y * d.N;
+    inst_shift(bt.b, w, wz, Wsoc);
+    const Scalars sc = bt.scal(blockIdx.z);
+    const size_t col = column_shift(bt.b, gridDim.y) + blockIdx.y;
+    const double* g = g_ + col * d.m;
+    const double* xb = xb_ + col * d.NP;
+    const double* t1 = t1_ + col * d.m;
+    double* lam = lam_ + col * d.N;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const double Hrr = sc.rho + sc.ep, Hss = 0.0 + sc.ep;
     if (i < d.nx) { lam[i] = xb[i]; return; }
@@ -177,14 +184,16 @@ __global__ __launch_bounds__(ADJ_THREADS) void k_residual_symmetric_t(Scalars sc
 void launch_recover_t_multi(calipso_hip_solver* s, const double* V, int p, double* lam, double* g, double* xbuf) {
     const Dims& d = s->d;
     const int work = d.NP + d.ne + d.q + d.n_soc;
-    hipLaunchKernelGGL(k_recover_t, dim3((work + ADJ_THREADS - 1) / ADJ_THREADS, p, 1), dim3(ADJ_THREADS), 0, s->stream, s->sc, d, s->cone, s->solution, V, s->wz, s->Wsoc,
+    const BatchSc B = batch_of(s);
+    hipLaunchKernelGGL(k_recover_t, dim3((work + ADJ_THREADS - 1) / ADJ_THREADS, p, B.b.n), dim3(ADJ_THREADS), 0, s->stream, B, d, s->cone, s->solution, V, s->wz, s->Wsoc,
                        lam, g, xbuf);
     launch_recover_t_wide(s, V, p, lam, g);
 }
 void launch_residual_symmetric_t_multi(calipso_hip_solver* s, int p, const double* g, const double* xbuf, const double* t1, double* lam) {
     const Dims& d = s->d;
     const int work = d.nx + d.ne + d.q + d.n_soc;
-    hipLaunchKernelGGL(k_residual_symmetric_t, dim3((work + ADJ_THREADS - 1) / ADJ_THREADS, p, 1), dim3(ADJ_THREADS), 0, s->stream, s->sc, d, s->cone, s->solution, g, xbuf,
+    const BatchSc B = batch_of(s);
+    hipLaunchKernelGGL(k_residual_symmetric_t, dim3((work + ADJ_THREADS - 1) / ADJ_THREADS, p, B.b.n), dim3(ADJ_THREADS), 0, s->stream, B, d, s->cone, s->solution, g, xbuf,
                        t1, s->wz, s->Wsoc, lam);
     launch_residual_symmetric_t_wide(s, p, g, t1, lam);
 }
@@ -200,32 +209,39 @@ __device__ __forceinline__ double two_products(double a, double b, double c, dou
     const double p = a * b, q = c * d;
     return p + q;
 }
-__global__ __launch_bounds__(256) void k_qp_grad_matrix(int rows, int cols, int N, const double* __restrict__ lam_, int lrow_off, const double* __restrict__ w, int prow_off, double alpha,
-                                                         double* __restrict__ out_, size_t size) {
-    const double* lam = lam_ + (size_t)blockIdx.z * N;
-    double* out = out_ + (size_t)blockIdx.z * size;
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+// grid: x = row blocks x column lanes (a lane of the matrix's columns strides over them), y = the cotangent column, z = the instance
+__global__ __launch_bounds__(256) void k_qp_grad_matrix(Batch bt, int rows, int cols, int N, int row_blocks, const double* __restrict__ lam_, int lrow_off, const double* __restrict__ w,
+                                                         int prow_off, double alpha, double* __restrict__ out_, size_t size) {
+    inst_shift(bt, w);
+    const size_t col = column_shift(bt, gridDim.y) + blockIdx.y;
+    const double* lam = lam_ + col * N;
+    double* out = out_ + col * size;
+    const int rb = blockIdx.x % row_blocks, c0 = blockIdx.x / row_blocks, cstep = gridDim.x / row_blocks;
+    const int r = rb * blockDim.x + threadIdx.x;
     if (r >= rows) return;
     const double lr = lam[lrow_off + r], pr = w[prow_off + r];
     // (the two products rounded on their own, two_products: entry (r, c) of the gradient of P is then entry (c, r) to the bit)
-    for (int c = blockIdx.y; c < cols; c += gridDim.y) out[(size_t)r + (size_t)c * rows] = alpha * two_products(lr, w[c], pr, lam[c]);
+    for (int c = c0; c < cols; c += cstep) out[(size_t)r + (size_t)c * rows] = alpha * two_products(lr, w[c], pr, lam[c]);
 }
 // q: -lam_x; b: lam_y; h: -lam_z
-__global__ __launch_bounds__(256) void k_qp_grad_vector(int rows, int N, const double* __restrict__ lam_, int off, double alpha, double* __restrict__ out_) {
+__global__ __launch_bounds__(256) void k_qp_grad_vector(Batch bt, int rows, int N, const double* __restrict__ lam_, int off, double alpha, double* __restrict__ out_) {
+    const size_t col = column_shift(bt, gridDim.y) + blockIdx.y;
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r < rows) out_[(size_t)blockIdx.y * rows + r] = alpha * lam_[(size_t)blockIdx.y * N + off + r];
+    if (r < rows) out_[col * rows + r] = alpha * lam_[col * N + off + r];
 }
 
-void launch_qp_data_gradients(calipso_hip_solver* s, const double* lam, int p, double* const out[6]) {
+void launch_qp_data_gradients(calipso_hip_solver* s, const double* lam, int p, double* const out[6], double scale) {
     const Dims& d = s->d;
     const double* w = s->solution;
+    const Batch B = batch_of(s).b;
     auto mat = [&](double* o, int rows, int loff, int poff, double alpha) {
-        if (o && rows > 0) hipLaunchKernelGGL(k_qp_grad_matrix, dim3((rows + 255) / 256, d.nx < 65535 ? d.nx : 65535, p), dim3(256), 0, s->stream, rows, d.nx, d.N, lam, loff, w, poff, alpha, o, (size_t)rows * d.nx);
+        const int rb = (rows + 255) / 256, lanes = d.nx < 65535 ? d.nx : 65535;
+        if (o && rows > 0) hipLaunchKernelGGL(k_qp_grad_matrix, dim3(rb * lanes, p, B.n), dim3(256), 0, s->stream, B, rows, d.nx, d.N, rb, lam, loff, w, poff, alpha, o, (size_t)rows * d.nx);
     };
     auto vec = [&](double* o, int rows, int off, double alpha) {
-        if (o && rows > 0) hipLaunchKernelGGL(k_qp_grad_vector, dim3((rows + 255) / 256, p, 1), dim3(256), 0, s->stream, rows, d.N, lam, off, alpha, o);
+        if (o && rows > 0) hipLaunchKernelGGL(k_qp_grad_vector, dim3((rows + 255) / 256, p, B.n), dim3(256), 0, s->stream, B, rows, d.N, lam, off, alpha, o);
     };
-    mat(out[0], d.nx, 0, 0, -s->qp.scale);
+    mat(out[0], d.nx, 0, 0, -scale);
     vec(out[1], d.nx, 0, -1.0);
     mat(out[2], d.ne, d.oy(), d.oy(), -1.0);
     vec(out[3], d.ne, d.oy(), 1.0);

@@ -1256,8 +1256,6 @@ int32_t calipso_hip_stats(H* s, int64_t out[8]) {
     return CALIPSO_OK;
 }
 
-static const uint32_t PARAMETER_JACOBIANS = CALIPSO_EVAL_OBJECTIVE_JACOBIAN_PARAMETERS | CALIPSO_EVAL_EQUALITY_JACOBIAN_PARAMETERS | CALIPSO_EVAL_EQUALITY_DUAL_JACOBIAN_PARAMETERS |
-                                            CALIPSO_EVAL_CONE_JACOBIAN_PARAMETERS | CALIPSO_EVAL_CONE_DUAL_JACOBIAN_PARAMETERS;      // what differentiate! re-evaluates (differentiate.jl:3)
 // differentiate!  differentiate.jl:1-61
 int32_t calipso_hip_differentiate(H* s, calipso_eval_fn eval, void* user) {
     if (!s) return CALIPSO_ERR_ARGUMENT;
@@ -1314,7 +1312,7 @@ int32_t calipso_hip_differentiate_adjoint(H* s, calipso_eval_fn eval, void* user
         size_t off = 0;
         for (int a = 0; a < 6; ++a) if (grad_qp[a] && qsize[a]) { qdev[a] = s->adj_qp + off; off += qsize[a] * p; }
         (void)hipEventRecord(s->adj_ev[3], s->stream);
-        launch_qp_data_gradients(s, lam, p, qdev);
+        launch_qp_data_gradients(s, lam, p, qdev, s->qp.scale);
     }
     (void)hipEventRecord(s->adj_ev[1], s->stream);
     if (adjoint) CK(hipMemcpyAsync(adjoint, lam, sizeof(double) * Np, hipMemcpyDeviceToHost, s->stream));

@@ -1,6 +1,8 @@
 // columns.hip — p columns through the current factors together: the condensed solve of differentiate.jl:29-58 for differentiate! (parameter columns), for its reverse
 // mode (the same pipeline stage by stage in reverse order, on cotangent columns) and the correction rounds of iterative_refinement.jl:14-44 on either.  ONE pipeline
-// with two directions: a direction only chooses the kernels before and after the middle.  Host code; the kernels are vectors / adjoint / soc_wide / gemm / blocks.hip's.
+// with two directions: a direction only chooses the kernels before and after the middle.  The transposed direction has a third caller, a group in lockstep
+// (differentiate_columns_t_group: the members' columns side by side in the group's workspace, every launch covering all members).  Host code; the kernels are vectors /
+// adjoint / soc_wide / gemm / blocks.hip's.
 #include <cstdio>
 #include "internal.hpp"
 #include "host_logic.hpp"
@@ -35,37 +37,37 @@ static int reserve_pass(H* s, ColumnWorkspace& ws, const ColumnLayout& L, int p,
 }
 
 // The products with p columns, each choice made once: the stage blocks where the handle works on them (every structured handle: all columns in one launch), else a
-// structured handle has no dense arrays to fall back to, else the dense GEMM
+// structured handle has no dense arrays to fall back to, else the dense GEMM (gemm_columns: a group's pass takes its batched form, all members in one launch)
 static int refuse(H* s, const char* msg) { s->err = msg; return CALIPSO_ERR_HIP; }
 static const char* const NO_BLOCK_PRODUCTS = "calipso_hip_differentiate: the block products are not available on this structured handle";
 static int constraints_t_columns(H* s, const double* U, long long ldu, double* Y, long long ldy, int p, double beta) {      // Y = [gx; hx]' U + beta Y
     const Dims& d = s->d;
     if (!d.m || blocks_gemm_t(s, U, ldu, Y, ldy, p, beta)) return CALIPSO_OK;
     if (s->compact) return refuse(s, NO_BLOCK_PRODUCTS);
-    gemm(s, d.nx, p, d.m, 1.0, s->Z, d.m, true, U, (int)ldu, beta, Y, (int)ldy);
+    gemm_columns(s, d.nx, p, d.m, 1.0, s->Z, d.m, true, U, (int)ldu, beta, Y, (int)ldy);
     return CALIPSO_OK;
 }
 static int constraints_columns(H* s, const double* X, long long ldx, double* Y, int p) {                                    // Y (m apart) = [gx; hx] X
     const Dims& d = s->d;
     if (!d.m || blocks_gemm_n(s, X, ldx, Y, d.m, p)) return CALIPSO_OK;
     if (s->compact) return refuse(s, NO_BLOCK_PRODUCTS);
-    gemm(s, d.m, p, d.nx, 1.0, s->Z, d.m, false, X, (int)ldx, 0.0, Y, d.m);
+    gemm_columns(s, d.m, p, d.nx, 1.0, s->Z, d.m, false, X, (int)ldx, 0.0, Y, d.m);
     return CALIPSO_OK;
 }
 static int hessian_columns(H* s, const double* X, long long ldx, double* Y, long long ldy, int p, bool transposed) {       // Y = Lxx X (transposed: Lxx' X)
     if (blocks_gemm_l(s, X, ldx, Y, ldy, p, transposed)) return CALIPSO_OK;
     if (s->compact) return refuse(s, "calipso_hip_differentiate: the Hessian block product is not available on this structured handle");
-    gemm(s, s->d.nx, p, s->d.nx, 1.0, s->Lxx, s->d.nx, transposed, X, (int)ldx, 0.0, Y, (int)ldy);
+    gemm_columns(s, s->d.nx, p, s->d.nx, 1.0, s->Lxx, s->d.nx, transposed, X, (int)ldx, 0.0, Y, (int)ldy);
     return CALIPSO_OK;
 }
 
 // The middle of the condensed pipeline, the same in both directions (S is symmetric): xbuf += [gx; hx]' seed, xbuf = S^-1 xbuf, out = [gx; hx] xbuf (a structured handle's
 // factor lives in the fronts of the multifrontal LDL^T, which take all columns through the tree together: trsm_multi).  matvec_for_one: a single column takes the
 // triangular solve and the mat-vecs of a Newton step's condensed solve (linear_solve_device) instead — the transposed direction asks for it, the forward one keeps the
-// GEMM forms' bits
+// GEMM forms' bits, and so does a group's pass (the mat-vecs work on the handles' own vectors: they cannot address the group's workspace)
 static int condensed_middle(H* s, const double* seed, double* xbuf, double* u, double* z, double* out, int p, bool matvec_for_one) {
     const Dims& d = s->d;
-    if (matvec_for_one && p == 1 && !s->compact) {
+    if (matvec_for_one && p == 1 && !s->compact && !s->group_columns) {
         if (d.m) gemv_t(s, d.m, d.nx, s->Z, d.m, seed, xbuf, 1.0, 1.0, SP_Z);
         launch_trsv(s, xbuf);
         if (d.m) gemv_n(s, d.m, d.nx, s->Z, d.m, xbuf, out, 1.0, 0.0, SP_Z);
@@ -157,20 +159,32 @@ int differentiate_columns(H* s) {
     if (rc >= 0) launch_scale_into(s, w + L.X.off, s->solution_sensitivity, L.X.len, -1.0);
     return rc < 0 ? rc : CALIPSO_OK;
 }
-int differentiate_columns_t(H* s, int p, const double* cotangent, bool with_theta, const double** lam, const double** grad_theta) {
+// The reverse pass for `members` x p cotangent columns in the workspace ws: a handle alone (members = 1, its own workspace, the rounds where it asks for them) or the members
+// of a group (the group's workspace: the layout of members x p columns IS the group's — every region holds the members' columns slot after slot —, no rounds)
+static int columns_t_pass(H* s, ColumnWorkspace& ws, int members, int p, const double* cotangent, bool with_theta, bool rounds, const char* caller, const double** lam,
+                          const double** grad_theta) {
     const Dims& d = s->d;
-    const bool rounds = rounds_wanted(s);
-    const ColumnLayout L = layout_of(s, p, true, rounds, with_theta ? (size_t)d.np * (size_t)p : 0);
-    int rc = reserve_pass(s, s->rev, L, p, rounds, 0, "calipso_hip_differentiate_adjoint");
+    const int cols = members * p;
+    const ColumnLayout L = layout_of(s, cols, true, rounds, with_theta ? (size_t)d.np * (size_t)cols : 0);
+    int rc = reserve_pass(s, ws, L, cols, rounds, 0, caller);
     if (rc < 0) return rc;
-    double *w = s->rev.d, *V = w + L.V.off, *X = w + L.X.off, *gth = w + L.grad_theta.off;
+    double *w = ws.d, *V = w + L.V.off, *X = w + L.X.off, *gth = w + L.grad_theta.off;
     CK(hipMemcpyAsync(V, cotangent, sizeof(double) * L.V.len, hipMemcpyHostToDevice, s->stream));
-    rc = solve_columns_t(s, w, L, V, p, X);        // :29-58 transposed, all p columns at once
-    if (rc >= 0 && rounds) rc = refine_columns(s, s->rev, L, V, true, p, "a kernel launch of the reverse mode's correction rounds was refused");
+    rc = solve_columns_t(s, w, L, V, p, X);        // :29-58 transposed, all p columns (of every member) at once
+    if (rc >= 0 && rounds) rc = refine_columns(s, ws, L, V, true, p, "a kernel launch of the reverse mode's correction rounds was refused");
     if (rc < 0) return rc;
-    if (with_theta) gemm(s, d.np, p, d.N, -1.0, s->jacobian_parameters, d.N, true, X, d.N, 0.0, gth, d.np);      // -R_theta' lam = S' v
+    if (with_theta) gemm_columns(s, d.np, p, d.N, -1.0, s->jacobian_parameters, d.N, true, X, d.N, 0.0, gth, d.np);      // -R_theta' lam = S' v
     *lam = X; *grad_theta = gth;
     return CALIPSO_OK;
+}
+int differentiate_columns_t(H* s, int p, const double* cotangent, bool with_theta, const double** lam, const double** grad_theta) {
+    return columns_t_pass(s, s->rev, 1, p, cotangent, with_theta, rounds_wanted(s), "calipso_hip_differentiate_adjoint", lam, grad_theta);
+}
+int differentiate_columns_t_group(H* s, ColumnWorkspace& ws, int count, int p, const double* cotangent, bool with_theta, const double** lam, const double** grad_theta) {
+    s->group_columns = true;
+    const int rc = columns_t_pass(s, ws, count, p, cotangent, with_theta, false, "calipso_hip_group_differentiate_adjoint", lam, grad_theta);
+    s->group_columns = false;
+    return rc;
 }
 
 }  // namespace calipso

@@ -16,6 +16,10 @@ template <typename... P> __device__ __forceinline__ void inst_shift_i(const Batc
     ((p += o), ...);
 }
 
+// The column regions of a p-column pass (columns.hip) are no part of a slab: a region holds the columns of every member of a group, slot after slot, so "the columns of
+// instance z" start slot[z] * per_member doubles into it (a handle alone: slot 0, no shift)
+__device__ __forceinline__ size_t column_shift(const Batch& b, size_t per_member) { return (size_t)b.slot[blockIdx.z] * per_member; }
+
 // ---- wave64 reductions (a CDNA wavefront is 64 lanes): the lane-63 forms wave_sum_l63 / wave_max_l63 are in include/calipso_wave.hpp
 // ... and in EVERY lane (what the callers that read lane 0, or broadcast it, expect): the total travels from lane 63 through a scalar register
 __device__ __forceinline__ double from_lane63(double v) {

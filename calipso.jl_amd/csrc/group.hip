@@ -37,6 +37,11 @@ struct calipso_hip_group {
     std::vector<calipso_eval_fn> evals;              // host evaluation callbacks of the members without a device evaluator
     std::vector<void*> users;
     int saved_band = 0, saved_hb = 0;                // the base handle's own structure while a group call overrides it
+    // differentiate! in reverse mode for all members (calipso_hip_group_differentiate_adjoint): the column workspace (columns.hip: count x k columns per region) and the
+    // staging of the QP data gradients, grown on demand and kept (a call that repeats its shapes allocates nothing), counted in the base handle's scratch_bytes
+    calipso::ColumnWorkspace rev;
+    double* adj_qp = nullptr; size_t adj_qp_doubles = 0;
+    hipEvent_t adj_ev[2] = {};                       // the entry, behind the last kernel
     bool dead = false;                               // a member was destroyed: every further call fails (no dangling handle is touched)
     std::string err;
 };
@@ -521,7 +526,7 @@ struct GroupCall {
     ~GroupCall() { if (entered) { g->base->cur = nullptr; g_restore_band(g); } }
 };
 // The entry of a group call: the members' options agree, every member has an evaluator (callbacks_count: a host callback of calipso_hip_group_set_evaluators is one;
-// `missing`: the error text otherwise), the members' own streams have drained, the band and blocks of the group's launches are in force and no Hessian is dirty.
+// `missing`: the error text otherwise; NULL: the call evaluates nothing), the members' own streams have drained, the band and blocks of the group's launches are in force and no Hessian is dirty.
 // all = every member's index.
 static int g_enter(G* g, GroupCall& call, bool callbacks_count, const char* missing, Set& all) {
     H* s = g->base;
@@ -531,7 +536,7 @@ static int g_enter(G* g, GroupCall& call, bool callbacks_count, const char* miss
     for (size_t i = 0; i < g->hs.size(); ++i) {
         H* h = g->hs[i];
         const bool callback = callbacks_count && i < g->evals.size() && g->evals[i];
-        if (!h->qp.attached && !h->dev_eval && !h->dev_block_eval && !callback) { s->err = missing; return CALIPSO_ERR_ARGUMENT; }
+        if (missing && !h->qp.attached && !h->dev_eval && !h->dev_block_eval && !callback) { s->err = missing; return CALIPSO_ERR_ARGUMENT; }
         if (h != s) CK(hipStreamSynchronize(h->stream));   // uploads made through the member's own stream are complete
         all.push_back((int)i);
     }
@@ -604,6 +609,10 @@ int32_t calipso_hip_group_destroy(calipso_hip_group* g) {
     if (g->ticket) (void)hipFree(g->ticket);
     if (g->sc_dev) (void)hipFree(g->sc_dev);
     if (g->sc_pin) (void)hipHostFree(g->sc_pin);
+    if (g->base) g->base->scratch_bytes -= sizeof(double) * (g->rev.doubles + g->adj_qp_doubles);
+    if (g->rev.d) (void)hipFree(g->rev.d);
+    if (g->adj_qp) (void)hipFree(g->adj_qp);
+    for (auto& e : g->adj_ev) if (e) (void)hipEventDestroy(e);
     delete g;
     return CALIPSO_OK;
 }
@@ -653,6 +662,81 @@ int32_t calipso_hip_group_newton_step(calipso_hip_group* g, int32_t advance, dou
     (void)hipEventElapsedTime(&ms, s->ev[2], s->ev[3]); s->phase_ms[2] = ms;
     (void)hipEventElapsedTime(&ms, s->ev[3], s->ev[4]); s->phase_ms[5] = ms;
     (void)hipEventElapsedTime(&ms, s->ev[8], s->ev[9]); s->phase_ms[6] = ms;
+    return CALIPSO_OK;
+}
+
+// differentiate! in reverse mode (differentiate.jl:1-61 and residual_jacobian_parameters.jl:1-40, transposed) for every member through the same launches: what
+// calipso_hip_differentiate_adjoint does for one handle with "opt.differentiate_refinement" = 0 (include/calipso_hip.h)
+int32_t calipso_hip_group_differentiate_adjoint(calipso_hip_group* g, int64_t k, const double* cotangent, double* adjoint, double* grad_theta, double* const* grad_qp,
+                                                int32_t* status, double* ms) {
+    if (!g || !g->base || g->dead) return CALIPSO_ERR_ARGUMENT;
+    H* s = g->base;
+    const Dims& d = s->d;
+    const size_t B = g->hs.size();
+    auto refuse = [&](const std::string& msg) { s->err = msg; return (int32_t)CALIPSO_ERR_ARGUMENT; };
+    const std::string name = "calipso_hip_group_differentiate_adjoint: ";
+    if (k < 1 || k > 65535) return refuse(name + "k must be in 1..65535 (the cotangent columns ride in a grid dimension)");
+    if (!cotangent) return refuse(name + "cotangent is NULL");
+    if (!status) return refuse(name + "status is NULL");
+    if (grad_theta && d.np == 0) return refuse(name + "grad_theta on handles without parameters (np = 0)");
+    for (size_t i = 0; i < B; ++i) {
+        const H* h = g->hs[i];
+        const std::string who = name + "member " + std::to_string(i);
+        if (grad_qp && !h->qp.attached) return refuse(who + ": grad_qp on a handle without an attached QP (calipso_hip_qp_attach)");
+        if (h->differentiate_refinement) return refuse(who + " has opt.differentiate_refinement = 1: the correction rounds have no group form");
+        if (h->compact || structure_active(h) || !h->h_reach.empty())
+            return refuse(who + " has an analysed structure (calipso_hip_analyze_structure, stage blocks, the stage-parallel factorisation): the group's reverse mode takes dense members only");
+    }
+    CK(hipSetDevice(s->device));
+    const int p = (int)k;
+    const size_t nx = d.nx, share = (size_t)d.N * p;
+    for (auto& e : g->adj_ev) if (!e) CK(hipEventCreate(&e));
+    const size_t qsize[6] = {nx * nx, nx, (size_t)d.ne * nx, (size_t)d.ne, (size_t)d.nc * nx, (size_t)d.nc};
+    size_t qtotal = 0;
+    if (grad_qp) for (int a = 0; a < 6; ++a) if (grad_qp[a]) qtotal += qsize[a] * p * B;
+    int rc = reserve_device(s, (void**)&g->adj_qp, &g->adj_qp_doubles, qtotal, sizeof(double), 0, "calipso_hip_group_differentiate_adjoint", "the QP data gradients");
+    if (rc < 0) return rc;
+    Set all;
+    GroupCall call{g};
+    (void)hipEventRecord(g->adj_ev[0], s->stream);
+    if (const int rc0 = g_enter(g, call, true, grad_theta ? "calipso_hip_group_differentiate_adjoint: grad_theta needs an evaluator on every member (a device evaluator, or a callback of calipso_hip_group_set_evaluators)" : nullptr, all)) return rc0;
+    for (H* h : g->hs) { double* info = h->rev.info; info[0] = (double)p; info[1] = info[2] = info[3] = 0.0; }
+    if (grad_theta && (rc = gb_evaluate(g, all, 0, PARAMETER_JACOBIANS)) < 0) return rc;
+    std::vector<std::array<int64_t, 3>> in(B);
+    rc = gb_factorize(g, all, in);                  // differentiate.jl:13-20: every member with the regularisation it holds (that of its last search direction)
+    if (rc < 0) return rc;
+    if (grad_theta) launch_jacobian_parameters(s);  // :23
+    const double *lam = nullptr, *gthM = nullptr;
+    rc = differentiate_columns_t_group(s, g->rev, (int)B, p, cotangent, grad_theta != nullptr, &lam, &gthM);      // :29-58 transposed, every member's k columns together
+    if (rc < 0) return rc;
+    double* qdev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (qtotal) {
+        size_t off = 0;
+        for (int a = 0; a < 6; ++a) if (grad_qp[a] && qsize[a]) { qdev[a] = g->adj_qp + off; off += qsize[a] * p * B; }
+        double* const rest[6] = {nullptr, qdev[1], qdev[2], qdev[3], qdev[4], qdev[5]};
+        launch_qp_data_gradients(s, lam, p, rest, 0.0);
+        // the gradient of P carries the member's objective scale: one launch per scale among the members (one, as a rule)
+        std::vector<char> done(B, 0);
+        for (size_t i = 0; qdev[0] && i < B; ++i) {
+            if (done[i]) continue;
+            Set same;
+            for (size_t j = i; j < B; ++j) if (!done[j] && g->hs[j]->qp.scale == g->hs[i]->qp.scale) { same.push_back((int)j); done[j] = 1; }
+            g_activate(g, same);
+            double* const onlyP[6] = {qdev[0], nullptr, nullptr, nullptr, nullptr, nullptr};
+            launch_qp_data_gradients(s, lam, p, onlyP, g->hs[i]->qp.scale);
+        }
+        g_activate(g, all);
+    }
+    (void)hipEventRecord(g->adj_ev[1], s->stream);
+    if (adjoint) CK(hipMemcpyAsync(adjoint, lam, sizeof(double) * share * B, hipMemcpyDeviceToHost, s->stream));
+    if (grad_theta) CK(hipMemcpyAsync(grad_theta, gthM, sizeof(double) * (size_t)d.np * p * B, hipMemcpyDeviceToHost, s->stream));
+    for (int a = 0; a < 6; ++a) if (qdev[a]) CK(hipMemcpyAsync(grad_qp[a], qdev[a], sizeof(double) * qsize[a] * p * B, hipMemcpyDeviceToHost, s->stream));
+    if (launch_errors(s, "a kernel launch of calipso_hip_group_differentiate_adjoint was refused")) return CALIPSO_ERR_HIP;
+    SYNC();
+    g->sc_pending = 0;
+    for (size_t i = 0; i < B; ++i) status[i] = CALIPSO_OK;
+    float t = 0.f;
+    if (ms) *ms = hipEventElapsedTime(&t, g->adj_ev[0], g->adj_ev[1]) == hipSuccess ? t : 0.0;
     return CALIPSO_OK;
 }
 

@@ -249,6 +249,8 @@ struct calipso_hip_solver {
     // differentiate! (columns.hip): ONE pipeline takes p columns through the current factors in two directions, forward (calipso_hip_differentiate: the np parameter
     // columns) and transposed (calipso_hip_differentiate_adjoint: k cotangent columns), each with a workspace of its own: neither call disturbs what the other left
     calipso::ColumnWorkspace fwd, rev;
+    bool group_columns = false;           // columns.hip: the pass in progress is a group's (set on its base handle for the pass): every column region holds the members' columns slot
+                                          // after slot (device_utils.hpp: column_shift) and the products go through the batched GEMM (gemm.hip: gemm_columns)
     double* adj_qp = nullptr; size_t adj_qp_doubles = 0;          // the QP data gradients the last reverse calls asked for, k x size each (grown on demand, counted in scratch_bytes)
     // "opt.differentiate_refinement" (not an option of the reference: differentiate! there does not refine; a handle-level value like solve_block): 1 = the correction
     // rounds of iterative_refinement.jl:14-44 on every column, in both directions; inert on a handle with second-order cones
@@ -404,6 +406,10 @@ void launch_solve_from_b(calipso_hip_solver* s);               // step_symmetric
 // gemm.hip
 void gemm(calipso_hip_solver* s, int M, int N, int K, double alpha, const double* A, int lda, bool transA, const double* B, int ldb, double beta,
           double* C, int ldc);
+// the products of the column pipeline: A is a buffer of the handle (of every covered member's slab: Batch::delta), B and C are column regions with p = N columns per member.
+// A handle alone: gemm; a group's pass (group_columns): one batched launch, the instance in blockIdx.z, B and C shifted by the member's slot
+void gemm_columns(calipso_hip_solver* s, int M, int N, int K, double alpha, const double* A, int lda, bool transA, const double* B, int ldb, double beta,
+                  double* C, int ldc);
 void trsm_multi(calipso_hip_solver* s, double* X, int p, double* U, double* Zm);
 void launch_residual_symmetric_multi(calipso_hip_solver* s, const double* res, int p, double* rsym, double* xbuf, double* t1);
 void launch_recover_multi(calipso_hip_solver* s, const double* res, int p, const double* rsym, const double* xbuf, const double* t2, double* dsym, double* step, double scale);
@@ -419,6 +425,9 @@ void launch_scale_into(calipso_hip_solver* s, const double* x, double* y, size_t
 // -H^-1 jacobian_parameters (+ the correction rounds where the option asks); p cotangent columns from the host -> *lam (N x p), *grad_theta (np x p): device, the reverse workspace
 int differentiate_columns(calipso_hip_solver* s);
 int differentiate_columns_t(calipso_hip_solver* s, int p, const double* cotangent, bool with_theta, const double** lam, const double** grad_theta);
+// the same for the members a group launch on `s` (the group's base handle) covers, in the group's workspace `ws`: every region holds count x p columns, member i's (by its index in
+// the group) at columns [i p, (i + 1) p); cotangent: count x (N x p) from the host; no correction rounds (the caller refuses members that ask for them)
+int differentiate_columns_t_group(calipso_hip_solver* s, ColumnWorkspace& ws, int count, int p, const double* cotangent, bool with_theta, const double** lam, const double** grad_theta);
 // *buf holds >= want elements of `elem` bytes afterwards: grown on demand, never shrunk, zero-filled when fresh, counted in scratch_bytes but for its first `uncounted` elements
 int reserve_device(calipso_hip_solver* s, void** buf, size_t* have, size_t want, size_t elem, size_t uncounted, const char* caller, const char* what);
 // adjoint.hip: the first and the last stage of the condensed solve transposed (differentiate! in reverse mode), p cotangent columns in grid.y; the cones of
@@ -428,7 +437,8 @@ void launch_residual_symmetric_t_multi(calipso_hip_solver* s, int p, const doubl
 void launch_recover_t_wide(calipso_hip_solver* s, const double* V, int p, double* lam, double* g);
 void launch_residual_symmetric_t_wide(calipso_hip_solver* s, int p, const double* g, const double* t1, double* lam);
 // gradients of a loss with respect to the data of an attached QP from lam (N x p) and the resident point w: out[a] (p x size of array a, NULL: skipped) in the order P, q, A, b, G, h
-void launch_qp_data_gradients(calipso_hip_solver* s, const double* lam, int p, double* const out[6]);
+// (a group launch: lam and out hold the members' shares slot after slot; scale: the objective scale of the covered members, who share it)
+void launch_qp_data_gradients(calipso_hip_solver* s, const double* lam, int p, double* const out[6], double scale);
 // fallback.hip
 int nonsymmetric_solve(calipso_hip_solver* s, const double* res, double* step);   // step = H \\ res (pivoted LU of the unreduced matrix)
 void nonsymmetric_release(calipso_hip_solver* s);
@@ -442,6 +452,9 @@ void ldlsolver_release(calipso_hip_solver* s);
 int structure_validate(calipso_hip_solver* s, int which);
 bool csc_pattern_ok(i64 n, const i64* colptr, const i64* rowval);   // ordering.hip: colptr[0] == 1, monotone, nnz < 2^31, rows in 1..n
 inline bool structure_active(const calipso_hip_solver* s) { return s->band64 > 0 || s->stage_parallel || s->blocks.on; }   // an analysed pattern that uploads must respect      // which: 0 Lxx, 1 gx, 2 hx; clears the structure when the block breaks it
+// what differentiate! re-evaluates (differentiate.jl:3)
+constexpr uint32_t PARAMETER_JACOBIANS = CALIPSO_EVAL_OBJECTIVE_JACOBIAN_PARAMETERS | CALIPSO_EVAL_EQUALITY_JACOBIAN_PARAMETERS | CALIPSO_EVAL_EQUALITY_DUAL_JACOBIAN_PARAMETERS |
+                                         CALIPSO_EVAL_CONE_JACOBIAN_PARAMETERS | CALIPSO_EVAL_CONE_DUAL_JACOBIAN_PARAMETERS;
 // qp.hip
 void launch_qp_evaluate(calipso_hip_solver* s, const double* point, uint32_t flags);
 

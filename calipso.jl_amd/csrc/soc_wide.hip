@@ -375,11 +375,14 @@ __device__ __forceinline__ void arrow_times(int dim, int lane, double c0, const 
 
 // first contributions to the s, t rows of lam and the cone's rows of g (k_recover_wide transposed; the dt recovery with the first row of Cbar_t only)
 template <int E>
-__global__ __launch_bounds__(64) void k_recover_t_wide(Scalars sc, Dims d, ConeDev cd, const double* __restrict__ w, const double* __restrict__ V_, const double* __restrict__ Wsoc,
+__global__ __launch_bounds__(64) void k_recover_t_wide(BatchSc bt, Dims d, ConeDev cd, const double* __restrict__ w, const double* __restrict__ V_, const double* __restrict__ Wsoc,
                                                         double* __restrict__ lam_, double* __restrict__ g_) {
-    const double* v = V_ + (size_t)blockIdx.y * d.N;
-    double* lam = lam_ + (size_t)blockIdx.y * d.N;
-    double* g = g_ + (size_t)blockIdx.y * d.m;
+    inst_shift(bt.b, w, Wsoc);
+    const Scalars sc = bt.scal(blockIdx.z);
+    const size_t col = column_shift(bt.b, gridDim.y) + blockIdx.y;      // (adjoint.hip: the column regions hold the members' columns slot after slot)
+    const double* v = V_ + col * d.N;
+    double* lam = lam_ + col * d.N;
+    double* g = g_ + col * d.m;
     const int j = cd.wide[blockIdx.x];
     const int st = cd.soc_start[j], dim = cd.soc_dim[j];
     const int lane = threadIdx.x;
@@ -418,11 +421,14 @@ __global__ __launch_bounds__(64) void k_recover_t_wide(Scalars sc, Dims d, ConeD
 
 // lam_z of the cone and the second contributions to its s, t rows (k_residual_symmetric_wide transposed)
 template <int E>
-__global__ __launch_bounds__(64) void k_residual_symmetric_t_wide(Scalars sc, Dims d, ConeDev cd, const double* __restrict__ w, const double* __restrict__ g_,
+__global__ __launch_bounds__(64) void k_residual_symmetric_t_wide(BatchSc bt, Dims d, ConeDev cd, const double* __restrict__ w, const double* __restrict__ g_,
                                                                    const double* __restrict__ t1_, const double* __restrict__ Wsoc, double* __restrict__ lam_) {
-    const double* g = g_ + (size_t)blockIdx.y * d.m;
-    const double* t1 = t1_ + (size_t)blockIdx.y * d.m;
-    double* lam = lam_ + (size_t)blockIdx.y * d.N;
+    inst_shift(bt.b, w, Wsoc);
+    const Scalars sc = bt.scal(blockIdx.z);
+    const size_t col = column_shift(bt.b, gridDim.y) + blockIdx.y;
+    const double* g = g_ + col * d.m;
+    const double* t1 = t1_ + col * d.m;
+    double* lam = lam_ + col * d.N;
     const int j = cd.wide[blockIdx.x];
     const int st = cd.soc_start[j], dim = cd.soc_dim[j];
     const int lane = threadIdx.x;
@@ -489,11 +495,13 @@ void launch_refine_local_wide(calipso_hip_solver* s, int part0) {
 }
 void launch_recover_t_wide(calipso_hip_solver* s, const double* V, int p, double* lam, double* g) {
     if (!s->d.n_wide) return;
-    WIDE_DISPATCH(wide_E(s), hipLaunchKernelGGL(k_recover_t_wide<E>, dim3(s->d.n_wide, p, 1), dim3(64), 0, s->stream, s->sc, s->d, s->cone, s->solution, V, s->Wsoc, lam, g));
+    const BatchSc B = batch_of(s);
+    WIDE_DISPATCH(wide_E(s), hipLaunchKernelGGL(k_recover_t_wide<E>, dim3(s->d.n_wide, p, B.b.n), dim3(64), 0, s->stream, B, s->d, s->cone, s->solution, V, s->Wsoc, lam, g));
 }
 void launch_residual_symmetric_t_wide(calipso_hip_solver* s, int p, const double* g, const double* t1, double* lam) {
     if (!s->d.n_wide) return;
-    WIDE_DISPATCH(wide_E(s), hipLaunchKernelGGL(k_residual_symmetric_t_wide<E>, dim3(s->d.n_wide, p, 1), dim3(64), 0, s->stream, s->sc, s->d, s->cone, s->solution, g, t1, s->Wsoc, lam));
+    const BatchSc B = batch_of(s);
+    WIDE_DISPATCH(wide_E(s), hipLaunchKernelGGL(k_residual_symmetric_t_wide<E>, dim3(s->d.n_wide, p, B.b.n), dim3(64), 0, s->stream, B, s->d, s->cone, s->solution, g, t1, s->Wsoc, lam));
 }
 
 }  // namespace calipso

@@ -123,8 +123,9 @@ void launch_lambda_update(calipso_hip_solver* s) {
 }
 
 // residual_jacobian_parameters!  residual_jacobian_parameters.jl:1-40: rows x <- Lx_theta, y <- g_theta, z <- h_theta, rest 0
-__global__ void k_jacobian_parameters(Dims d, const double* __restrict__ lgp, const double* __restrict__ gp, const double* __restrict__ hp,
+__global__ void k_jacobian_parameters(Batch bt, Dims d, const double* __restrict__ lgp, const double* __restrict__ gp, const double* __restrict__ hp,
                                       double* __restrict__ J) {
+    inst_shift(bt, lgp, gp, hp, J);
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const int j = blockIdx.y;
     if (i >= d.N) return;
@@ -136,7 +137,8 @@ __global__ void k_jacobian_parameters(Dims d, const double* __restrict__ lgp, co
 }
 void launch_jacobian_parameters(calipso_hip_solver* s) {
     if (s->d.np == 0) return;
-    hipLaunchKernelGGL(k_jacobian_parameters, dim3((s->d.N + 255) / 256, s->d.np), dim3(256), 0, s->stream, s->d, s->lgp, s->gp, s->hp,
+    const Batch B = batch_of(s).b;
+    hipLaunchKernelGGL(k_jacobian_parameters, dim3((s->d.N + 255) / 256, s->d.np, B.n), dim3(256), 0, s->stream, B, s->d, s->lgp, s->gp, s->hp,
                        s->jacobian_parameters);
 }
 

@@ -567,6 +567,40 @@ function CALIPSO.solve!(g::HIPGroup)
     return res
 end
 
+"""differentiate! in reverse mode for every member of the group through the same launches (calipso_hip_group_differentiate_adjoint): `cotangent` N x k x B (dLoss/dw of
+every member at its resident point).  Per member what `differentiate_adjoint!` gives on the handle alone without correction rounds: `adjoint` N x k x B, `theta`
+np x k x B (the parameter Jacobians through `evaluate_callback`, as `solve!` of the group evaluates), `qp`: names out of "PqAbGh" on members with an attached QP
+(matrices rows x nx x k x B).  Returns a NamedTuple (adjoint, theta, qp::Dict, status, ms)."""
+function differentiate_adjoint!(g::HIPGroup, cotangent::AbstractArray{Float64,3}; adjoint::Bool = true, theta::Bool = g.members[1].solver.dimensions.parameters > 0, qp::AbstractString = "")
+    members = g.members
+    d = members[1].solver.dimensions
+    B = length(members)
+    (size(cotangent, 1) == d.total && size(cotangent, 3) == B) || throw(ArgumentError("cotangent must be N x k x members"))
+    V = Array{Float64,3}(cotangent)
+    k = size(V, 2)
+    nx, ne, nc = d.variables, d.equality_dual, d.cone_dual
+    sizes = Dict('P' => (nx, nx), 'q' => (nx,), 'A' => (ne, nx), 'b' => (ne,), 'G' => (nc, nx), 'h' => (nc,))
+    all(c -> haskey(sizes, c), qp) || throw(ArgumentError("qp must be made of names out of PqAbGh"))
+    adj = adjoint ? zeros(Float64, d.total, k, B) : nothing
+    gth = theta ? zeros(Float64, max(d.parameters, 1), k, B) : nothing
+    gq = Dict{Char,Array{Float64}}(c => zeros(Float64, sizes[c]..., k, B) for c in qp)
+    ptrs = Ptr{Float64}[haskey(gq, c) ? pointer(gq[c]) : Ptr{Float64}(C_NULL) for c in "PqAbGh"]
+    opt(a) = a === nothing ? Ptr{Float64}(C_NULL) : pointer(a)
+    status = zeros(Int32, B); ms = Ref{Float64}(0.0)
+    cb = @cfunction(evaluate_callback, Int32, (Ptr{Cvoid}, UInt32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}))
+    evals = fill(cb, B)
+    GC.@preserve members V adj gth gq ptrs begin
+        users = Ptr{Cvoid}[pointer_from_objref(m) for m in members]
+        rc = ccall((:calipso_hip_group_set_evaluators, lib), Int32, (Ptr{Cvoid}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}), g.handle, evals, users)
+        rc < 0 && error("calipso_hip_group_set_evaluators failed ($rc)")
+        rc = ccall((:calipso_hip_group_differentiate_adjoint, lib), Int32,
+            (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Ptr{Float64}}, Ptr{Int32}, Ptr{Float64}),
+            g.handle, k, V, opt(adj), opt(gth), isempty(qp) ? Ptr{Ptr{Float64}}(C_NULL) : pointer(ptrs), status, ms)
+        rc < 0 && error("calipso_hip_group_differentiate_adjoint failed ($rc): $(last_error(members[1].handle))")
+    end
+    return (adjoint = adj, theta = theta ? gth[1:d.parameters, :, :] : nothing, qp = gq, status = status, ms = ms[])
+end
+
 # ---- solve! for a batch of small QPs in one kernel launch (include/calipso_hip.h: calipso_hip_smallnewton_*; csrc/smallnewton.hip) ----------------
 "`batch` independent QPs (min c x'Px + q'x s.t. Ax = b, h - Gx >= 0) of one shape: `HIPSmallNewton(nx, ne, nc, batch)`, `set_qp!` (or `set_evaluator!` + `set_parameters!` for a nonlinear problem with a device evaluator), `initialize!`, `solve!`, `differentiate!` — every instance's whole solve! in ONE launch."
 mutable struct HIPSmallNewton

@@ -26,12 +26,19 @@ itself loads without it.
 
 SolverQPLayer is the same layer over the general path: forward = qp_attach + initialize! with zeros + solve!, backward = Solver.vjp(qp=...) — one transposed
 condensed solve for the cotangent and the closed-form data gradients of the inputs that need them.  The data travel through host arrays; a solve that did not
-converge gives NaN gradients and a warning, as on the host path of QPLayer."""
+converge gives NaN gradients and a warning, as on the host path of QPLayer.
+
+    x = GroupQPLayer.apply(group, P, q, A, b, G, h)      # a batch of QPs too large for the batch kernel (nx in the hundreds or thousands) on a Group of Solver handles
+
+GroupQPLayer is the batched layer over the general path: every input (count, ...) or unbatched and shared by the members; forward = qp_attach per member + initialize!
+with zeros + Group.solve (all members in lockstep through the same launches), backward = ONE Group.vjp(qp=...) for the inputs that need gradients — one factorisation
+launch chain and one transposed condensed solve for the whole group instead of one per member.  Gradients of shared inputs are summed over the members on the host, in
+member order.  Host tensors only: the handles take host arrays.  Members that did not converge get NaN gradients and one warning counts them."""
 import warnings
 
 import numpy as np
 
-__all__ = ["QPLayer", "ParametricLayer", "SolverQPLayer"]
+__all__ = ["QPLayer", "ParametricLayer", "SolverQPLayer", "GroupQPLayer"]
 
 _cls = {}
 
@@ -209,7 +216,73 @@ def _build():
                 grads.append(torch.from_numpy(np.ascontiguousarray(g)).to(ctx.device))
             return (None, *grads, None, None)
 
-    return {"QPLayer": QPLayer, "ParametricLayer": ParametricLayer, "SolverQPLayer": SolverQPLayer}
+    class GroupQPLayer(torch.autograd.Function):
+        """apply(group, P, q, A, b, G, h, return_duals=False, objective_scale=0.5): the solutions x (count, nx) of one QP per member of a Group, or (x, y, z) with
+        return_duals.  Inputs: float64 HOST tensors (the handles take host arrays), batched (count, ...) or unbatched and shared by the members"""
+
+        @staticmethod
+        def forward(ctx, group, P, q, A, b, G, h, return_duals=False, objective_scale=0.5):
+            s0, count = group.solvers[0], len(group.solvers)
+            data = (P, q, A, b, G, h)
+            dims = ((s0.nx, s0.nx), (s0.nx,), (s0.ne, s0.nx), (s0.ne,), (s0.nc, s0.nx), (s0.nc,))
+            shared = []
+            for name, t, dm in zip("PqAbGh", data, dims):
+                if t.dtype != torch.float64:
+                    raise TypeError("GroupQPLayer: %s must be float64" % name)
+                if t.is_cuda:
+                    raise ValueError("GroupQPLayer: %s must be a host tensor (the handles take host arrays)" % name)
+                if tuple(t.shape) == dm:
+                    shared.append(True)
+                elif tuple(t.shape) == (count,) + dm:
+                    shared.append(False)
+                else:
+                    raise ValueError("GroupQPLayer: %s must be %s or %s" % (name, dm, (count,) + dm))
+            arrays = [_np(t).copy() for t in data]
+            key = object()
+            _solve_group(group, arrays, shared, objective_scale, key)
+            ctx.group, ctx.key, ctx.arrays, ctx.shared, ctx.c, ctx.converged = group, key, arrays, shared, objective_scale, group._qp_layer_converged.copy()
+            W = [s.solution for s in group.solvers]
+            x = torch.from_numpy(np.stack([w.variables for w in W]))
+            if not return_duals:
+                return x
+            return x, torch.from_numpy(np.stack([w.equality_dual for w in W])), torch.from_numpy(np.stack([w.cone_dual for w in W]))
+
+        @staticmethod
+        def backward(ctx, gx, gy=None, gz=None):
+            group = ctx.group
+            if getattr(group, "_qp_layer_key", None) is not ctx.key:      # the group solved other data since: the same data solve again (deterministic)
+                _solve_group(group, ctx.arrays, ctx.shared, ctx.c, ctx.key)
+            s0, count = group.solvers[0], len(group.solvers)
+            nx, ne, nc = s0.nx, s0.ne, s0.nc
+            oy, oz = nx + ne + nc, nx + 2 * ne + nc
+            v = np.zeros((count, s0.N))
+            if gx is not None:
+                v[:, :nx] = _np(gx)
+            if gy is not None and ne:
+                v[:, oy:oy + ne] = _np(gy)
+            if gz is not None and nc:
+                v[:, oz:oz + nc] = _np(gz)
+            want = "".join(name for name, need in zip("PqAbGh", ctx.needs_input_grad[1:7]) if need)
+            out = group.vjp(v, adjoint=False, theta=False, qp=want) if want else {}
+            bad = ~ctx.converged
+            if bad.any():
+                warnings.warn("GroupQPLayer: %d of %d members did not converge: their gradients are NaN" % (int(bad.sum()), count))
+            grads = []
+            for name, s in zip("PqAbGh", ctx.shared):
+                if name not in out:
+                    grads.append(None)
+                    continue
+                g = out[name].copy()
+                g[bad] = np.nan
+                if s:                                                     # summed over the members in member order
+                    acc = g[0].copy()
+                    for i in range(1, count):
+                        acc += g[i]
+                    g = acc
+                grads.append(torch.from_numpy(np.ascontiguousarray(g)))
+            return (None, *grads, None, None)
+
+    return {"QPLayer": QPLayer, "ParametricLayer": ParametricLayer, "SolverQPLayer": SolverQPLayer, "GroupQPLayer": GroupQPLayer}
 
 
 def _solve_device(torch, sn, tensors, objective_scale, key):
@@ -234,6 +307,15 @@ def _solve_handle(solver, arrays, objective_scale, key):
     initialize_b(solver, np.zeros(solver.nx))
     converged = solve_b(solver)
     solver._qp_layer_key, solver._qp_layer_converged = key, bool(converged)
+
+
+def _solve_group(group, arrays, shared, objective_scale, key):
+    from . import initialize_b
+    for i, solver in enumerate(group.solvers):
+        solver.qp_attach(*[a if s else a[i] for a, s in zip(arrays, shared)], objective_scale=objective_scale)
+        initialize_b(solver, np.zeros(solver.nx))
+    res = group.solve()
+    group._qp_layer_key, group._qp_layer_converged = key, np.array([r == 1 for r in res])
 
 
 def _solve(sn, arrays, shared, objective_scale, key):

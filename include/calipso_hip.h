@@ -364,6 +364,34 @@ int32_t calipso_hip_group_newton_step(calipso_hip_group*, int32_t advance, doubl
  * per member, NULL where a device evaluator is attached), one member after the other. */
 int32_t calipso_hip_group_set_evaluators(calipso_hip_group*, const calipso_eval_fn* evals, void* const* users);
 int32_t calipso_hip_group_solve(calipso_hip_group*, int32_t* result);
+/* differentiate! in REVERSE mode for every member through the same launches (differentiate.jl:1-61 and residual_jacobian_parameters.jl:1-40, transposed): per member exactly
+ * what calipso_hip_differentiate_adjoint gives with "opt.differentiate_refinement" = 0.  ONE factorisation over all members, each with the regularisation it holds
+ * (differentiate.jl:13-20; the fields are those of the last search direction, quirk B-12), then the condensed solve of differentiate.jl:29-58 transposed
+ * (search_direction.jl:38-101 and residual.jl:53-101 in reverse order; the first-row quirk of the second-order dt recovery, second_order.jl:63-65, is kept) for all members
+ * and all k columns in the same launches: the products and the block triangular solves are batched fp64 MFMA GEMMs with the member in a grid dimension — every k, k = 1
+ * included.  Every cone layout the single-handle entry admits.  Host arrays, member-major (member i's share at i x the share's size):
+ *   cotangent   count x (N x k), column-major per member, required
+ *   adjoint     count x (N x k) = lambda_i = M_i' v_i, or NULL
+ *   grad_theta  count x (np x k) = -R_theta' lambda_i = S_i' v_i, or NULL.  The parameter Jacobians (differentiate.jl:3) are evaluated as calipso_hip_group_solve evaluates:
+ *               device evaluators inside the group's launches, host callbacks of calipso_hip_group_set_evaluators one member after the other
+ *   grad_qp     NULL, or six pointers P, q, A, b, G, h (NULLs skipped), every member with calipso_hip_qp_attach: each count x (k x size), the closed forms of
+ *               calipso_hip_differentiate_adjoint with the member's point and objective scale (the gradient of P symmetric to the bit)
+ *   status      count codes, required: what calipso_hip_differentiate_adjoint would return for that member alone.  The group's factorisation has no failure of one member
+ *               that the single-handle entry would report (a zero pivot is none there either: the values are then not finite); a launch the runtime refuses fails the call
+ *   ms          NULL, or the HIP-event time in ms from the entry's first enqueue to its last kernel
+ * Returns as calipso_hip_group_newton_step: CALIPSO_OK, or the error of the call as a whole.  Afterwards calipso_hip_differentiate_adjoint_info of every member reads
+ * [k, 0, 0, 0].  The workspace (count x the columns of one handle's reverse call, and the staging of the gradients) belongs to the group: grown on demand, kept, freed by
+ * calipso_hip_group_destroy.  The members' own workspaces, solution_sensitivity and points are left alone (their factors are overwritten, as by any factorisation).
+ * CALIPSO_ERR_ARGUMENT, calipso_hip_last_error of the first member naming the cause, the group and its members usable afterwards: k < 1 (or above 65535), a NULL cotangent
+ * or status, grad_theta with np = 0, grad_qp with a member that has no attached QP, a member with "opt.differentiate_refinement" = 1 (the correction rounds have no group
+ * form), a member with an analysed structure (calipso_hip_analyze_structure, stage blocks, stage-parallel, structured handles: dense treatment only), a dead group. */
+int32_t calipso_hip_group_differentiate_adjoint(calipso_hip_group*, int64_t k,
+                                                const double* cotangent,   /* count x (N x k), member-major, column-major per member; required */
+                                                double* adjoint,           /* count x (N x k) = lambda_i = M_i' v_i, or NULL */
+                                                double* grad_theta,        /* count x (np x k) = -R_theta' lambda = S_i' v_i, or NULL */
+                                                double* const* grad_qp,    /* NULL, or six pointers P, q, A, b, G, h (NULLs skipped), each count x (k x size), matrices column-major */
+                                                int32_t* status,           /* count: what calipso_hip_differentiate_adjoint would return for that member alone */
+                                                double* ms);               /* NULL, or the HIP-event time from the entry's first enqueue to its last kernel */
 
 /* ---- stage-banded structure -------------------------------------------------------------------------------
  * Trajectory-optimisation problems order their variables stage by stage (src/trajectory_optimization/indices.jl:41-180), which

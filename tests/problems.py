@@ -207,17 +207,62 @@ class ParametricConicQP(ConicQP):
             _put(out, "cone_dual_jacobian_variables_parameters", np.zeros((nx, npar)))
 
 
-def parametric_conic_qp(nx, ne, n_nn, n_soc, soc_dim, seed=0):
+def parametric_conic_qp_dims(nx, ne, n_nn, dims, seed=0):
+    """ParametricConicQP with n_nn nonnegative rows followed by one second-order cone per entry of dims, in order (nc = n_nn + sum(dims))"""
     rng = np.random.default_rng(seed)
-    nc = n_nn + n_soc * soc_dim
+    dims = [int(dm) for dm in dims]
+    nc = n_nn + sum(dims)
     Q = rng.standard_normal((nx, nx)) / np.sqrt(nx)
     P = Q.T @ Q + np.eye(nx)
     A = rng.standard_normal((ne, nx)) / np.sqrt(nx)
     G = rng.standard_normal((nc, nx)) / np.sqrt(nx)
     nn = list(range(1, n_nn + 1))
-    soc = [list(range(n_nn + 1 + j * soc_dim, n_nn + 1 + (j + 1) * soc_dim)) for j in range(n_soc)] or [[]]
+    starts = np.concatenate([[0], np.cumsum(dims)]).astype(int)
+    soc = [list(range(n_nn + 1 + int(starts[j]), n_nn + 1 + int(starts[j + 1]))) for j in range(len(dims))] or [[]]
     return ParametricConicQP(P, rng.standard_normal(nx), A, rng.standard_normal(ne), G, rng.random(nc) + 1.0, nonnegative_indices=nn,
                              second_order_indices=soc, name="parametric_conic_qp")
+
+
+def parametric_conic_qp(nx, ne, n_nn, n_soc, soc_dim, seed=0):
+    return parametric_conic_qp_dims(nx, ne, n_nn, [soc_dim] * n_soc, seed)
+
+
+class OneParameterConicQP(ConicQP):
+    """ConicQP with ONE parameter, which moves h along a fixed direction:  (h + theta direction) - Gx in K.  cone_jacobian_parameters is that direction, every
+    other parameter Jacobian is zero: differentiate! has a single right-hand side."""
+
+    def __init__(self, base, direction):
+        super().__init__(base.P, base.q, base.A, base.b, base.G, base.h, nonnegative_indices=base.nonnegative_indices,
+                         second_order_indices=base.second_order_indices, objective_scale=base.c, name="one_parameter_conic_qp")
+        self.direction = np.asarray(direction, dtype=np.float64)
+        assert self.direction.shape == (self.nc,)
+        self.np = 1
+        self.parameters = np.zeros(1)
+
+    def evaluate(self, flags, x, y, z, theta, out):
+        th = float(np.asarray(theta, dtype=np.float64)[0])
+        h0 = self.h
+        self.h = h0 + th * self.direction
+        try:
+            super().evaluate(flags, x, y, z, theta, out)
+        finally:
+            self.h = h0
+        if flags & OBJECTIVE_JACOBIAN_PARAMETERS:
+            _put(out, "objective_jacobian_variables_parameters", np.zeros((self.nx, 1)))
+        if flags & EQUALITY_JACOBIAN_PARAMETERS and self.ne:
+            _put(out, "equality_jacobian_parameters", np.zeros((self.ne, 1)))
+        if flags & EQUALITY_DUAL_JACOBIAN_PARAMETERS:
+            _put(out, "equality_dual_jacobian_variables_parameters", np.zeros((self.nx, 1)))
+        if flags & CONE_JACOBIAN_PARAMETERS and self.nc:
+            _put(out, "cone_jacobian_parameters", self.direction[:, None])
+        if flags & CONE_DUAL_JACOBIAN_PARAMETERS:
+            _put(out, "cone_dual_jacobian_variables_parameters", np.zeros((self.nx, 1)))
+
+
+def one_parameter_conic_qp_dims(nx, ne, n_nn, dims, seed=0):
+    """the QP of parametric_conic_qp_dims with a single parameter along a random direction of h (drawn from a generator of its own)"""
+    base = parametric_conic_qp_dims(nx, ne, n_nn, dims, seed)
+    return OneParameterConicQP(base, np.random.default_rng(seed + 7919).standard_normal(base.nc))
 
 
 # ---- the reference's test problems ---------------------------------------------------------------

@@ -588,6 +588,29 @@ class Group:
             raise CalipsoHipError("group_solve: %s (%d): %s" % (STATUS_TEXT.get(rc, "error"), rc, self._L.calipso_hip_last_error(self.solvers[0]._h).decode()))
         return [int(v) for v in res]
 
+    def differentiate(self, tile=0):
+        """differentiate! for every member through the same launches (calipso_hip_group_differentiate): per member what Solver.differentiate gives on the handle alone
+        with differentiate_refinement off (the parameter Jacobians of members without a device evaluator come through their host callbacks, as in solve()).  tile: columns
+        per workgroup of the batched products, 0 = the library's choice, 16 or 64 (the same bits either way).  Returns dict(sensitivity (count, N, np) = dw/dtheta per
+        member — what each member's data("solution_sensitivity") reads afterwards —, status (count,))."""
+        import ctypes as C
+        s0 = self.solvers[0]
+        B, N, npar = len(self.solvers), s0.N, s0.np
+        sens = np.zeros(max(B * N * npar, 1))
+        status = np.zeros(B, dtype=np.int32)
+        ms = np.zeros(2)
+        self._evals = (EVAL_FN * B)(*[s._cb for s in self.solvers])       # host callbacks (used by members without a device evaluator)
+        self._L.calipso_hip_group_set_evaluators(self._g, self._evals, None)
+        rc = self._L.calipso_hip_group_differentiate(self._g, _pd(sens), status.ctypes.data_as(C.POINTER(C.c_int32)), int(tile), _pd(ms))
+        if rc < 0:
+            raise CalipsoHipError("group_differentiate: %s (%d): %s" % (STATUS_TEXT.get(rc, "error"), rc, self._L.calipso_hip_last_error(s0._h).decode()))
+        self._differentiate_ms = (float(ms[0]), float(ms[1]))
+        return dict(sensitivity=np.transpose(sens[:B * N * npar].reshape(B, npar, N), (0, 2, 1)).copy(), status=status)
+
+    def differentiate_ms(self):
+        """HIP-event times in ms of the last differentiate(): (from its first enqueue to its last kernel, of that the column pass alone)"""
+        return getattr(self, "_differentiate_ms", (0.0, 0.0))
+
     def vjp(self, cotangent, adjoint=True, theta=None, qp=None):
         """differentiate! in reverse mode for every member through the same launches (calipso_hip_group_differentiate_adjoint): per member what Solver.vjp gives on the
         handle alone with differentiate_refinement off.  cotangent: (count, N) or (count, N, k), member i's cotangents at its resident point.  theta, qp: as for Solver.vjp

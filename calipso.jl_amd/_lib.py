@@ -80,6 +80,7 @@ SYMBOLS = {
     "calipso_hip_group_solve": (_i32, [_vp, C.POINTER(_i32)]),
     "calipso_hip_group_set_evaluators": (_i32, [_vp, C.POINTER(EVAL_FN), C.POINTER(_vp)]),
     "calipso_hip_group_differentiate_adjoint": (_i32, [_vp, _i64, _pd, _pd, _pd, C.POINTER(_pd), _pi32, _pd]),
+    "calipso_hip_group_differentiate": (_i32, [_vp, _pd, _pi32, _i32, _pd]),
     "calipso_hip_ldl_create": (_i32, [_i64, _i32, C.POINTER(_vp)]),
     "calipso_hip_ldl_factorize_csc": (_i32, [_vp, _i64, _pi64, _pi64, _pd, _pi64]),
     "calipso_hip_ldl_inertia": (_i32, [_vp, _pi64]),

@@ -1,8 +1,8 @@
 // columns.hip — p columns through the current factors together: the condensed solve of differentiate.jl:29-58 for differentiate! (parameter columns), for its reverse
 // mode (the same pipeline stage by stage in reverse order, on cotangent columns) and the correction rounds of iterative_refinement.jl:14-44 on either.  ONE pipeline
-// with two directions: a direction only chooses the kernels before and after the middle.  The transposed direction has a third caller, a group in lockstep
-// (differentiate_columns_t_group: the members' columns side by side in the group's workspace, every launch covering all members).  Host code; the kernels are vectors /
-// adjoint / soc_wide / gemm / blocks.hip's.
+// with two directions: a direction only chooses the kernels before and after the middle.  Either direction has a second caller, a group in lockstep
+// (differentiate_columns_group, differentiate_columns_t_group: the members' columns side by side in the group's workspace, every launch covering all members).  Host code;
+// the kernels are vectors / adjoint / soc_wide / gemm / blocks.hip's.
 #include <cstdio>
 #include "internal.hpp"
 #include "host_logic.hpp"
@@ -79,7 +79,8 @@ static int condensed_middle(H* s, const double* seed, double* xbuf, double* u, d
     return constraints_columns(s, xbuf, d.NP, out, p);
 }
 // out = scale * H^-1 rhs for p right-hand-side columns (N apart), as far as the condensed, constraint-first solve gets.  The reference solves one condensed system per
-// parameter column; here condensation per column, mat-vecs as GEMMs, block triangular solves as TRSMs
+// parameter column; here condensation per column, mat-vecs as GEMMs, block triangular solves as TRSMs.  A group's pass: p columns of every member the launches cover — rhs and
+// out in the members' slabs, L the layout of all members' columns (every region is reached by the member's slot)
 static int solve_columns(H* s, double* w, const ColumnLayout& L, const double* rhs, int p, double* out, double scale) {
     double *rsym = w + L.rsym.off, *xbuf = w + L.xbuf.off, *t1 = w + L.t1.off, *t2 = w + L.t2.off;
     launch_residual_symmetric_multi(s, rhs, p, rsym, xbuf, t1);                             // rsym, xbuf = [b_x; 0], t1 = Omega b_m
@@ -144,20 +145,32 @@ static int refine_columns(H* s, ColumnWorkspace& ws, const ColumnLayout& L, cons
 // triu-symmetrised cone blocks (quirk B-3: refining would move away from it, towards H^-1; the batch kernel does the same), and not with iterative_refinement = 0
 static bool rounds_wanted(const H* s) { return s->differentiate_refinement && s->opt.iterative_refinement && s->d.n_soc == 0; }
 
-int differentiate_columns(H* s) {
-    const int p = s->d.np;
-    const bool rounds = rounds_wanted(s);
-    const ColumnLayout L = layout_of(s, p, false, rounds, 0);
-    // (the unrefined pipeline's share of the buffer is left out of scratch_bytes, as it always was: counting it is a correction for a change of its own)
-    int rc = reserve_pass(s, s->fwd, L, p, rounds, layout_of(s, p, false, false, 0).total, "calipso_hip_differentiate");
+// The forward pass for `members` x np parameter columns in the workspace ws: a handle alone (members = 1, its own workspace, the rounds where it asks for them) or the members
+// of a group (the group's workspace, laid out for members x np columns; no rounds).  R and solution_sensitivity are the members' own (Batch::delta)
+static int columns_pass(H* s, ColumnWorkspace& ws, int members, bool rounds, const char* caller) {
+    const int p = s->d.np, cols = members * p;
+    const ColumnLayout L = layout_of(s, cols, false, rounds, 0);
+    // (a handle's unrefined pipeline's share of the buffer is left out of scratch_bytes, as it always was: counting it is a correction for a change of its own)
+    int rc = reserve_pass(s, ws, L, cols, rounds, members == 1 ? layout_of(s, p, false, false, 0).total : 0, caller);
     if (rc < 0) return rc;
-    double *w = s->fwd.d, *R = s->jacobian_parameters;
+    double *w = ws.d, *R = s->jacobian_parameters;
     // one condensed solve for all np columns, unrefined as the reference's (its QDLDL works on the (nx + ne + nc) symmetric matrix and does not need more)
     if (!rounds) return solve_columns(s, w, L, R, p, s->solution_sensitivity, -1.0);       // :54-56 sensitivity = -step
     rc = solve_columns(s, w, L, R, p, w + L.X.off, 1.0);                                    // the unrefined pass kept as the step matrix X
-    if (rc >= 0) rc = refine_columns(s, s->fwd, L, R, false, p, "a kernel launch of differentiate!'s correction rounds was refused");
+    if (rc >= 0) rc = refine_columns(s, ws, L, R, false, p, "a kernel launch of differentiate!'s correction rounds was refused");
     if (rc >= 0) launch_scale_into(s, w + L.X.off, s->solution_sensitivity, L.X.len, -1.0);
     return rc < 0 ? rc : CALIPSO_OK;
+}
+int differentiate_columns(H* s) { return columns_pass(s, s->fwd, 1, rounds_wanted(s), "calipso_hip_differentiate"); }
+// (tile = 0: the 64-column form of the batched products from GROUP_WIDE_TILE_COLUMNS parameter columns per member on.  Measured: the 16-column form is faster at 24, 48
+// and 102 columns, the two tie at 540, the 64-column form is faster at 770 and 1200 — DESIGN.md, "Forward mode for a group")
+constexpr int GROUP_WIDE_TILE_COLUMNS = 512;
+int differentiate_columns_group(H* s, ColumnWorkspace& ws, int count, int tile) {
+    s->group_columns = true;
+    s->group_tile = tile ? tile : (s->d.np >= GROUP_WIDE_TILE_COLUMNS ? 64 : 16);
+    const int rc = columns_pass(s, ws, count, false, "calipso_hip_group_differentiate");
+    s->group_columns = false; s->group_tile = 0;
+    return rc;
 }
 // The reverse pass for `members` x p cotangent columns in the workspace ws: a handle alone (members = 1, its own workspace, the rounds where it asks for them) or the members
 // of a group (the group's workspace: the layout of members x p columns IS the group's — every region holds the members' columns slot after slot —, no rounds)

@@ -3,7 +3,8 @@
 // through the same factors together, so the mat-vecs and the block triangular solves become GEMMs / TRSMs.
 //     C(M x N) = alpha * op(A)(M x K) * B(K x N) + beta * C          op(A) = A or A', everything column-major
 // 64 x 64 tile per workgroup of 1024 threads (16 wavefronts, one 16 x 16 MFMA tile each), K staged through LDS in chunks of 32.
-// k_gemm_batch: the same product for the members of a group in one launch, with a narrow tile for the few columns of the reverse mode.
+// k_gemm_batch: the same product for the members of a group in one launch, with a narrow tile for the few columns of the reverse mode and a wide one for the
+// parameter columns of the forward mode.
 #include "internal.hpp"
 
 #include <algorithm>
@@ -69,18 +70,25 @@ void gemm(calipso_hip_solver* s, int M, int N, int K, double alpha, const double
 // one 16 x 16 MFMA tile each, stacked along the rows) — at k = 1 a sixteenth of the matrix core works on padding instead of 63/64 under k_gemm's 64 x 64 tile, and with 22 KB
 // of LDS and 256 threads several members' tiles share a compute unit.  More than 16 columns: grid.y tiles them in 16s (the panel of A is read again per tile).  Every
 // element is the same chain of MFMAs over K in chunks of 4 as in k_gemm — one accumulator, the chunks in order — so a member's result has the bits k_gemm gives it alone.
+// The forward group pass (calipso_hip_group_differentiate) has np columns per member, not a handful: at 16 columns per workgroup every panel of [gx; hx], L and Tinv would be
+// read np / 16 times.  NT = 4 is the wide form of the same kernel: 64 x 64 of C per workgroup, still 256 threads (wider workgroups do not share a compute unit with
+// another stream's kernels), each wavefront owning 16 rows x 64 columns as four accumulators fed from one load of its A fragment; 35 KB of LDS, so several members'
+// tiles are still resident together.  An element's chain of MFMAs does not depend on NT: the two forms give the same bits (tests/test_gpu_group_differentiate.py).
 constexpr int GBN = 16;
+template <int NT>      // NT x 16 columns per workgroup
 __global__ __launch_bounds__(256) void k_gemm_batch(Batch bt, int M, int N, int K, double alpha, const double* __restrict__ A, int lda, int transA,
                                                      const double* __restrict__ B, int ldb, long long share_b, double beta, double* __restrict__ C, int ldc, long long share_c) {
-    __shared__ double As[64 * GLD];    // As[i][k]
-    __shared__ double Bs[GBN * GLD];   // Bs[j][k]
+    __shared__ double As[64 * GLD];         // As[i][k]
+    __shared__ double Bs[NT * GBN * GLD];   // Bs[j][k]
     inst_shift(bt, A);
     B += column_shift(bt, (size_t)share_b);
     C += column_shift(bt, (size_t)share_c);
-    const int i0 = blockIdx.x * 64, j0 = blockIdx.y * GBN;
+    const int i0 = blockIdx.x * 64, j0 = blockIdx.y * (NT * GBN);
     const int tid = threadIdx.x, lane = tid & 63, wi = tid >> 6;
     const int fr = lane & 15, fk = lane >> 4;
-    v4d acc = (v4d){0.0, 0.0, 0.0, 0.0};
+    v4d acc[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) acc[t] = (v4d){0.0, 0.0, 0.0, 0.0};
     for (int k0 = 0; k0 < K; k0 += GK) {
         __syncthreads();
 #pragma unroll
@@ -95,8 +103,8 @@ __global__ __launch_bounds__(256) void k_gemm_batch(Batch bt, int M, int N, int 
             }
         }
 #pragma unroll
-        for (int it = 0; it < 2; ++it) {
-            const int idx = tid + it * 256;                  // 16 x 32 elements of B[k + j*ldb]: lanes along k
+        for (int it = 0; it < 2 * NT; ++it) {
+            const int idx = tid + it * 256;                  // NT*16 x 32 elements of B[k + j*ldb]: lanes along k
             const int kb = idx & 31, j = idx >> 5;
             Bs[j * GLD + kb] = (j0 + j < N && k0 + kb < K) ? B[(k0 + kb) + (size_t)(j0 + j) * ldb] : 0.0;
         }
@@ -104,28 +112,41 @@ __global__ __launch_bounds__(256) void k_gemm_batch(Batch bt, int M, int N, int 
 #pragma unroll
         for (int kk = 0; kk < GK / 4; ++kk) {
             const double a = As[(wi * 16 + fr) * GLD + kk * 4 + fk];
-            const double b = Bs[fr * GLD + kk * 4 + fk];
-            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(b, a, acc, 0, 0, 0);   // transposed: MFMA row <-> j, column <-> i
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                const double b = Bs[(t * GBN + fr) * GLD + kk * 4 + fk];
+                acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(b, a, acc[t], 0, 0, 0);   // transposed: MFMA row <-> j, column <-> i
+            }
         }
     }
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int j = j0 + fk + 4 * r, i = i0 + wi * 16 + fr;
-        if (i < M && j < N) {
-            double* c = C + i + (size_t)j * ldc;
-            *c = (beta == 0.0) ? alpha * acc[r] : alpha * acc[r] + beta * *c;
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int j = j0 + t * GBN + fk + 4 * r, i = i0 + wi * 16 + fr;
+            if (i < M && j < N) {
+                double* c = C + i + (size_t)j * ldc;
+                *c = (beta == 0.0) ? alpha * acc[t][r] : alpha * acc[t][r] + beta * *c;
+            }
         }
-    }
 }
 
+// (group_tile: the forward group pass asks for the 64-column form where its column count pays for it — columns.hip: differentiate_columns_group; the reverse pass
+// never sets it and keeps the 16-column form)
+template <int NT>
+static void launch_gemm_batch(calipso_hip_solver* s, const Batch& bt, int M, int N, int K, double alpha, const double* A, int lda, bool transA, const double* B, int ldb,
+                              double beta, double* C, int ldc) {
+    // (a member's share of a column region: its N columns, ld apart — every region of the workspace is dense)
+    hipLaunchKernelGGL(k_gemm_batch<NT>, dim3((M + 63) / 64, (N + NT * GBN - 1) / (NT * GBN), bt.n), dim3(256), 0, s->stream, bt, M, N, K, alpha, A, lda, transA ? 1 : 0, B, ldb,
+                       (long long)ldb * N, beta, C, ldc, (long long)ldc * N);
+}
 void gemm_columns(calipso_hip_solver* s, int M, int N, int K, double alpha, const double* A, int lda, bool transA, const double* B, int ldb, double beta,
                   double* C, int ldc) {
     if (!s->group_columns) { gemm(s, M, N, K, alpha, A, lda, transA, B, ldb, beta, C, ldc); return; }
     if (M <= 0 || N <= 0) return;
     const Batch bt = batch_of(s).b;
-    // (a member's share of a column region: its N columns, ld apart — every region of the workspace is dense)
-    hipLaunchKernelGGL(k_gemm_batch, dim3((M + 63) / 64, (N + GBN - 1) / GBN, bt.n), dim3(256), 0, s->stream, bt, M, N, K, alpha, A, lda, transA ? 1 : 0, B, ldb,
-                       (long long)ldb * N, beta, C, ldc, (long long)ldc * N);
+    if (s->group_tile == 64) launch_gemm_batch<4>(s, bt, M, N, K, alpha, A, lda, transA, B, ldb, beta, C, ldc);
+    else launch_gemm_batch<1>(s, bt, M, N, K, alpha, A, lda, transA, B, ldb, beta, C, ldc);
 }
 
 // rows of X (NP x p) scaled by 1/D: Z = D^-1 U (the pivots from the instance's slab, the columns from its share of the regions)

@@ -42,6 +42,9 @@ struct calipso_hip_group {
     calipso::ColumnWorkspace rev;
     double* adj_qp = nullptr; size_t adj_qp_doubles = 0;
     hipEvent_t adj_ev[2] = {};                       // the entry, behind the last kernel
+    // ... and in forward mode (calipso_hip_group_differentiate): the forward layout of count x np columns, kept and counted the same way
+    calipso::ColumnWorkspace fwd;
+    hipEvent_t fwd_ev[3] = {};                       // the entry, dR/dtheta formed, behind the last kernel
     bool dead = false;                               // a member was destroyed: every further call fails (no dangling handle is touched)
     std::string err;
 };
@@ -609,10 +612,12 @@ int32_t calipso_hip_group_destroy(calipso_hip_group* g) {
     if (g->ticket) (void)hipFree(g->ticket);
     if (g->sc_dev) (void)hipFree(g->sc_dev);
     if (g->sc_pin) (void)hipHostFree(g->sc_pin);
-    if (g->base) g->base->scratch_bytes -= sizeof(double) * (g->rev.doubles + g->adj_qp_doubles);
+    if (g->base) g->base->scratch_bytes -= sizeof(double) * (g->rev.doubles + g->fwd.doubles + g->adj_qp_doubles);
     if (g->rev.d) (void)hipFree(g->rev.d);
+    if (g->fwd.d) (void)hipFree(g->fwd.d);
     if (g->adj_qp) (void)hipFree(g->adj_qp);
     for (auto& e : g->adj_ev) if (e) (void)hipEventDestroy(e);
+    for (auto& e : g->fwd_ev) if (e) (void)hipEventDestroy(e);
     delete g;
     return CALIPSO_OK;
 }
@@ -737,6 +742,59 @@ int32_t calipso_hip_group_differentiate_adjoint(calipso_hip_group* g, int64_t k,
     for (size_t i = 0; i < B; ++i) status[i] = CALIPSO_OK;
     float t = 0.f;
     if (ms) *ms = hipEventElapsedTime(&t, g->adj_ev[0], g->adj_ev[1]) == hipSuccess ? t : 0.0;
+    return CALIPSO_OK;
+}
+
+// differentiate! (differentiate.jl:1-61) for every member through the same launches: what calipso_hip_differentiate does for one handle with
+// "opt.differentiate_refinement" = 0 (include/calipso_hip.h)
+int32_t calipso_hip_group_differentiate(calipso_hip_group* g, double* sensitivity, int32_t* status, int32_t tile, double* ms) {
+    if (!g || !g->base || g->dead) return CALIPSO_ERR_ARGUMENT;
+    H* s = g->base;
+    const Dims& d = s->d;
+    const size_t B = g->hs.size();
+    auto refuse = [&](const std::string& msg) { s->err = msg; return (int32_t)CALIPSO_ERR_ARGUMENT; };
+    const std::string name = "calipso_hip_group_differentiate: ";
+    if (!status) return refuse(name + "status is NULL");
+    if (tile != 0 && tile != 16 && tile != 64) return refuse(name + "tile must be 0 (the library's choice), 16 or 64");
+    if (d.np == 0) return refuse(name + "handles without parameters (np = 0)");
+    for (size_t i = 0; i < B; ++i) {
+        const H* h = g->hs[i];
+        const std::string who = name + "member " + std::to_string(i);
+        if (h->differentiate_refinement) return refuse(who + " has opt.differentiate_refinement = 1: the correction rounds have no group form");
+        if (h->compact || structure_active(h) || !h->h_reach.empty())
+            return refuse(who + " has an analysed structure (calipso_hip_analyze_structure, stage blocks, the stage-parallel factorisation): the group's forward mode takes dense members only");
+        if (!h->qp.attached && !h->dev_eval && !h->dev_block_eval && !(i < g->evals.size() && g->evals[i]))
+            return refuse(who + " has no evaluator (a device evaluator, or a callback of calipso_hip_group_set_evaluators)");
+    }
+    CK(hipSetDevice(s->device));
+    const size_t share = (size_t)d.N * d.np;
+    for (auto& e : g->fwd_ev) if (!e) CK(hipEventCreate(&e));
+    Set all;
+    GroupCall call{g};
+    (void)hipEventRecord(g->fwd_ev[0], s->stream);
+    if (const int rc0 = g_enter(g, call, true, "calipso_hip_group_differentiate: member without a device evaluator and without a callback (calipso_hip_group_set_evaluators)", all)) return rc0;
+    for (H* h : g->hs) { double* info = h->fwd.info; info[0] = (double)d.np; info[1] = info[2] = info[3] = 0.0; }
+    int rc = gb_evaluate(g, all, 0, PARAMETER_JACOBIANS);
+    if (rc < 0) return rc;
+    std::vector<std::array<int64_t, 3>> in(B);
+    rc = gb_factorize(g, all, in);                  // differentiate.jl:13-20: every member with the regularisation it holds (that of its last search direction)
+    if (rc < 0) return rc;
+    launch_jacobian_parameters(s);                  // :23
+    (void)hipEventRecord(g->fwd_ev[1], s->stream);
+    rc = differentiate_columns_group(s, g->fwd, (int)B, tile);      // :29-58, every member's np columns together; :54-56 into each member's solution_sensitivity
+    if (rc < 0) return rc;
+    (void)hipEventRecord(g->fwd_ev[2], s->stream);
+    if (sensitivity)
+        for (size_t i = 0; i < B; ++i) CK(hipMemcpyAsync(sensitivity + i * share, g->hs[i]->solution_sensitivity, sizeof(double) * share, hipMemcpyDeviceToHost, s->stream));
+    if (launch_errors(s, "a kernel launch of calipso_hip_group_differentiate was refused")) return CALIPSO_ERR_HIP;
+    SYNC();
+    g->sc_pending = 0;
+    for (size_t i = 0; i < B; ++i) status[i] = CALIPSO_OK;
+    if (ms) {
+        float t = 0.f;
+        ms[0] = hipEventElapsedTime(&t, g->fwd_ev[0], g->fwd_ev[2]) == hipSuccess ? t : 0.0;
+        ms[1] = hipEventElapsedTime(&t, g->fwd_ev[1], g->fwd_ev[2]) == hipSuccess ? t : 0.0;
+    }
     return CALIPSO_OK;
 }
 

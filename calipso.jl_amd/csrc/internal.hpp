@@ -251,6 +251,7 @@ struct calipso_hip_solver {
     calipso::ColumnWorkspace fwd, rev;
     bool group_columns = false;           // columns.hip: the pass in progress is a group's (set on its base handle for the pass): every column region holds the members' columns slot
                                           // after slot (device_utils.hpp: column_shift) and the products go through the batched GEMM (gemm.hip: gemm_columns)
+    int group_tile = 0;                   // ... and its form: 64 = 64 columns of C per workgroup (set by the forward group pass for its duration), else 16
     double* adj_qp = nullptr; size_t adj_qp_doubles = 0;          // the QP data gradients the last reverse calls asked for, k x size each (grown on demand, counted in scratch_bytes)
     // "opt.differentiate_refinement" (not an option of the reference: differentiate! there does not refine; a handle-level value like solve_block): 1 = the correction
     // rounds of iterative_refinement.jl:14-44 on every column, in both directions; inert on a handle with second-order cones
@@ -354,8 +355,9 @@ void gemv_both(calipso_hip_solver* s, int rows, int cols, const double* A, int l
 void launch_cone_weights(calipso_hip_solver* s);
 // soc_wide.hip: cones of dimension > 4, one wavefront per cone (no-ops on handles without such cones)
 void launch_cone_weights_wide(calipso_hip_solver* s);
-void launch_residual_symmetric_wide(calipso_hip_solver* s, const double* res, int p, double* rsym, double* t1);
-void launch_recover_wide(calipso_hip_solver* s, const double* res, int p, const double* rsym, const double* t2, double* dsym, double* step, double* accumulate, int zsx_mode);
+// (regions: the multi-column use — rsym, t1, t2, dsym are column regions; else they live in the instance's slab)
+void launch_residual_symmetric_wide(calipso_hip_solver* s, const double* res, int p, double* rsym, double* t1, bool regions);
+void launch_recover_wide(calipso_hip_solver* s, const double* res, int p, const double* rsym, const double* t2, double* dsym, double* step, double* accumulate, int zsx_mode, bool regions);
 void launch_refine_local_wide(calipso_hip_solver* s, int part0);
 void launch_scale_rows(calipso_hip_solver* s);
 void launch_schur(calipso_hip_solver* s);
@@ -411,6 +413,8 @@ void gemm(calipso_hip_solver* s, int M, int N, int K, double alpha, const double
 void gemm_columns(calipso_hip_solver* s, int M, int N, int K, double alpha, const double* A, int lda, bool transA, const double* B, int ldb, double beta,
                   double* C, int ldc);
 void trsm_multi(calipso_hip_solver* s, double* X, int p, double* U, double* Zm);
+// the first and the last stage for p columns (grid.y) of every instance the launch covers (grid.z): res and step in the instance's slab or, for a handle alone, anywhere
+// (Batch::delta), the other operands in column regions (device_utils.hpp: column_shift)
 void launch_residual_symmetric_multi(calipso_hip_solver* s, const double* res, int p, double* rsym, double* xbuf, double* t1);
 void launch_recover_multi(calipso_hip_solver* s, const double* res, int p, const double* rsym, const double* xbuf, const double* t2, double* dsym, double* step, double scale);
 // vectors.hip: the correction rounds of differentiate! on p columns together (handles without second-order cones).  E = R - H X: the rows r, s, y, z, t from zx = [gx; hx] X_x
@@ -424,6 +428,10 @@ void launch_scale_into(calipso_hip_solver* s, const double* x, double* y, size_t
 // columns.hip: p columns through the current factors (the caller has evaluated the parameter Jacobians it needs, factored, and formed jacobian_parameters): solution_sensitivity =
 // -H^-1 jacobian_parameters (+ the correction rounds where the option asks); p cotangent columns from the host -> *lam (N x p), *grad_theta (np x p): device, the reverse workspace
 int differentiate_columns(calipso_hip_solver* s);
+// the forward pass for the members a group launch on `s` (the group's base handle) covers, in the group's workspace `ws`: the right-hand sides are the members' own
+// jacobian_parameters, the results land in their solution_sensitivity (both in the slabs), every scratch region holds count x np columns; no correction rounds.
+// tile: the batched GEMM's form (0: chosen by the column count, 16, 64)
+int differentiate_columns_group(calipso_hip_solver* s, ColumnWorkspace& ws, int count, int tile);
 int differentiate_columns_t(calipso_hip_solver* s, int p, const double* cotangent, bool with_theta, const double** lam, const double** grad_theta);
 // the same for the members a group launch on `s` (the group's base handle) covers, in the group's workspace `ws`: every region holds count x p columns, member i's (by its index in
 // the group) at columns [i p, (i + 1) p); cotangent: count x (N x p) from the host; no correction rounds (the caller refuses members that ask for them)

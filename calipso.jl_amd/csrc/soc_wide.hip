@@ -176,12 +176,14 @@ __device__ __forceinline__ void w_times(int dim, int lane, const bool (&in)[E], 
 // ---- condensed right-hand side of the rows of one cone: b_z = r_z + U^-1 (Cbar_t r_s + r_t), t1 = W b_z -------------------------------------
 template <int E>
 __global__ __launch_bounds__(64) void k_residual_symmetric_wide(BatchSc bt, Dims d, ConeDev cd, const double* __restrict__ w, const double* __restrict__ res_,
-                                                                 const double* __restrict__ Wsoc, double* __restrict__ rsym_, double* __restrict__ t1_) {
-    inst_shift(bt.b, w, res_, Wsoc, rsym_, t1_);
+                                                                 const double* __restrict__ Wsoc, double* __restrict__ rsym_, double* __restrict__ t1_, int regions) {
+    inst_shift(bt.b, w, res_, Wsoc);
+    if (!regions) inst_shift(bt.b, rsym_, t1_);
     const Scalars sc = bt.scal(blockIdx.z);
+    const size_t col = (regions ? column_shift(bt.b, gridDim.y) : 0) + blockIdx.y;      // (vectors.hip: k_residual_symmetric)
     const double* res = res_ + (size_t)blockIdx.y * d.N;
-    double* rsym = rsym_ + (size_t)blockIdx.y * d.n;
-    double* t1 = t1_ + (size_t)blockIdx.y * d.m;
+    double* rsym = rsym_ + col * d.n;
+    double* t1 = t1_ + col * d.m;
     const int j = cd.wide[blockIdx.x];
     const int st = cd.soc_start[j], dim = cd.soc_dim[j];
     const int lane = threadIdx.x;
@@ -215,15 +217,18 @@ __global__ __launch_bounds__(64) void k_residual_symmetric_wide(BatchSc bt, Dims
 template <int E>
 __global__ __launch_bounds__(64) void k_recover_wide(BatchSc bt, Dims d, ConeDev cd, const double* __restrict__ w, const double* __restrict__ res_,
                                                       const double* __restrict__ b_, const double* __restrict__ t2_, const double* __restrict__ Wsoc,
-                                                      double* __restrict__ dsym_, double* __restrict__ step_, double* __restrict__ accum, double* __restrict__ zsx, int zsx_mode) {
-    inst_shift(bt.b, w, res_, b_, t2_, Wsoc, dsym_, step_);
+                                                      double* __restrict__ dsym_, double* __restrict__ step_, double* __restrict__ accum, double* __restrict__ zsx, int zsx_mode,
+                                                      int regions) {
+    inst_shift(bt.b, w, res_, Wsoc, step_);
+    if (!regions) inst_shift(bt.b, b_, t2_, dsym_);
     if (accum) inst_shift(bt.b, accum);
     if (zsx_mode) inst_shift(bt.b, zsx);
     const Scalars sc = bt.scal(blockIdx.z);
+    const size_t col = (regions ? column_shift(bt.b, gridDim.y) : 0) + blockIdx.y;      // (vectors.hip: k_recover)
     const double* res = res_ + (size_t)blockIdx.y * d.N;
-    const double* b = b_ + (size_t)blockIdx.y * d.n;
-    const double* t2 = t2_ + (size_t)blockIdx.y * d.m;
-    double* dsym = dsym_ + (size_t)blockIdx.y * d.n;
+    const double* b = b_ + col * d.n;
+    const double* t2 = t2_ + col * d.m;
+    double* dsym = dsym_ + col * d.n;
     double* step = step_ + (size_t)blockIdx.y * d.N;
     const int j = cd.wide[blockIdx.x];
     const int st = cd.soc_start[j], dim = cd.soc_dim[j];
@@ -476,16 +481,18 @@ void launch_cone_weights_wide(calipso_hip_solver* s) {
                            in_lds ? (double*)nullptr : s->socwork);
     });
 }
-void launch_residual_symmetric_wide(calipso_hip_solver* s, const double* res, int p, double* rsym, double* t1) {
+void launch_residual_symmetric_wide(calipso_hip_solver* s, const double* res, int p, double* rsym, double* t1, bool regions) {
     if (!s->d.n_wide) return;
     const BatchSc B = batch_of(s);
-    WIDE_DISPATCH(wide_E(s), hipLaunchKernelGGL(k_residual_symmetric_wide<E>, dim3(s->d.n_wide, p, p > 1 ? 1 : B.b.n), dim3(64), 0, s->stream, B, s->d, s->cone, s->solution, res, s->Wsoc, rsym, t1));
+    WIDE_DISPATCH(wide_E(s), hipLaunchKernelGGL(k_residual_symmetric_wide<E>, dim3(s->d.n_wide, p, B.b.n), dim3(64), 0, s->stream, B, s->d, s->cone, s->solution, res, s->Wsoc, rsym, t1,
+                                               regions ? 1 : 0));
 }
-void launch_recover_wide(calipso_hip_solver* s, const double* res, int p, const double* rsym, const double* t2, double* dsym, double* step, double* accumulate, int zsx_mode) {
+void launch_recover_wide(calipso_hip_solver* s, const double* res, int p, const double* rsym, const double* t2, double* dsym, double* step, double* accumulate, int zsx_mode,
+                         bool regions) {
     if (!s->d.n_wide) return;
     const BatchSc B = batch_of(s);
-    WIDE_DISPATCH(wide_E(s), hipLaunchKernelGGL(k_recover_wide<E>, dim3(s->d.n_wide, p, p > 1 ? 1 : B.b.n), dim3(64), 0, s->stream, B, s->d, s->cone, s->solution, res, rsym, t2, s->Wsoc, dsym, step,
-                                               accumulate, zsx_mode ? s->zsx : (double*)nullptr, zsx_mode));
+    WIDE_DISPATCH(wide_E(s), hipLaunchKernelGGL(k_recover_wide<E>, dim3(s->d.n_wide, p, B.b.n), dim3(64), 0, s->stream, B, s->d, s->cone, s->solution, res, rsym, t2, s->Wsoc, dsym, step,
+                                               accumulate, zsx_mode ? s->zsx : (double*)nullptr, zsx_mode, regions ? 1 : 0));
 }
 void launch_refine_local_wide(calipso_hip_solver* s, int part0) {
     if (!s->d.n_wide) return;

@@ -151,14 +151,17 @@ void launch_violations(calipso_hip_solver* s, int pub_first, int pub_count) {
 // the condensed solve: xbuf = [b_x; 0 padding] and t1 = Omega b_m (omega_y b_y ; Omega_z b_z), see solvek.hip.
 __global__ void k_residual_symmetric(BatchSc bt, Dims d, ConeDev cd, const double* __restrict__ w, const double* __restrict__ res_,
                                      const double* __restrict__ wz, const double* __restrict__ Wsoc, double* __restrict__ rsym_,
-                                     double* __restrict__ xbuf_, double* __restrict__ t1_) {
-    inst_shift(bt.b, w, res_, wz, Wsoc, rsym_, xbuf_, t1_);
+                                     double* __restrict__ xbuf_, double* __restrict__ t1_, int regions) {
+    inst_shift(bt.b, w, res_, wz, Wsoc);
+    if (!regions) inst_shift(bt.b, rsym_, xbuf_, t1_);
     const Scalars sc = bt.scal(blockIdx.z);
-    // blockIdx.y = right-hand-side column (differentiate!: one column per parameter); columns are N / n / NP / m apart
+    // blockIdx.y = right-hand-side column (differentiate!: one column per parameter); columns are N / n / NP / m apart.  regions: the multi-column use — the outputs are
+    // column regions, which hold the members' columns slot after slot (device_utils.hpp: column_shift), while res stays in the instance's slab (its dR/dtheta)
+    const size_t col = (regions ? column_shift(bt.b, gridDim.y) : 0) + blockIdx.y;
     const double* res = res_ + (size_t)blockIdx.y * d.N;
-    double* rsym = rsym_ + (size_t)blockIdx.y * d.n;
-    double* xbuf = xbuf_ + (size_t)blockIdx.y * d.NP;
-    double* t1 = t1_ + (size_t)blockIdx.y * d.m;
+    double* rsym = rsym_ + col * d.n;
+    double* xbuf = xbuf_ + col * d.NP;
+    double* t1 = t1_ + col * d.m;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const double Hrr = sc.rho + sc.ep;   // H[r,r] = rho then += eps_p  (residual_jacobian_variables.jl:60,87)
     const double Hss = 0.0 + sc.ep;      // H[s,s]
@@ -231,15 +234,15 @@ void launch_residual_symmetric(calipso_hip_solver* s, const double* res) {
     const int work = s->d.NP + s->d.ne + s->d.q + s->d.n_soc;
     const BatchSc B = batch_of(s);
     hipLaunchKernelGGL(k_residual_symmetric, dim3((work + 127) / 128, 1, B.b.n), dim3(128), 0, s->stream, B, s->d, s->cone, s->solution, res,
-                       s->wz, s->Wsoc, s->residual_symmetric, s->xbuf, s->t1);
-    launch_residual_symmetric_wide(s, res, 1, s->residual_symmetric, s->t1);
+                       s->wz, s->Wsoc, s->residual_symmetric, s->xbuf, s->t1, 0);
+    launch_residual_symmetric_wide(s, res, 1, s->residual_symmetric, s->t1, false);
 }
 void launch_residual_symmetric_multi(calipso_hip_solver* s, const double* res, int p, double* rsym, double* xbuf, double* t1) {
     const int work = s->d.NP + s->d.ne + s->d.q + s->d.n_soc;
-    const BatchSc B = batch_of(s);   // (the multi-column path is single-instance)
-    hipLaunchKernelGGL(k_residual_symmetric, dim3((work + 127) / 128, p, 1), dim3(128), 0, s->stream, B, s->d, s->cone, s->solution, res,
-                       s->wz, s->Wsoc, rsym, xbuf, t1);
-    launch_residual_symmetric_wide(s, res, p, rsym, t1);
+    const BatchSc B = batch_of(s);   // (a handle alone, or the members of a group's forward pass)
+    hipLaunchKernelGGL(k_residual_symmetric, dim3((work + 127) / 128, p, B.b.n), dim3(128), 0, s->stream, B, s->d, s->cone, s->solution, res,
+                       s->wz, s->Wsoc, rsym, xbuf, t1, 1);
+    launch_residual_symmetric_wide(s, res, p, rsym, t1, true);
 }
 
 // Tail of the condensed solve + search_direction_symmetric! (search_direction.jl:38-101) in one kernel:
@@ -249,17 +252,19 @@ void launch_residual_symmetric_multi(calipso_hip_solver* s, const double* res, i
 __global__ void k_recover(BatchSc bt, Dims d, ConeDev cd, const double* __restrict__ w, const double* __restrict__ res_,
                           const double* __restrict__ b_, const double* __restrict__ dx_, const double* __restrict__ t2_,
                           const double* __restrict__ wz, const double* __restrict__ Wsoc, double* __restrict__ dsym_,
-                          double* __restrict__ step_, double* __restrict__ accum, double* __restrict__ zsx, int zsx_mode) {
-    inst_shift(bt.b, w, res_, b_, dx_, t2_, wz, Wsoc, dsym_, step_);
+                          double* __restrict__ step_, double* __restrict__ accum, double* __restrict__ zsx, int zsx_mode, int regions) {
+    inst_shift(bt.b, w, res_, wz, Wsoc, step_);
+    if (!regions) inst_shift(bt.b, b_, dx_, t2_, dsym_);
     if (accum) inst_shift(bt.b, accum);
     if (zsx_mode) inst_shift(bt.b, zsx);
     const Scalars sc = bt.scal(blockIdx.z);
-    // blockIdx.y = right-hand-side column (see k_residual_symmetric); dsym_ may be null for the multi-column use
+    // blockIdx.y = right-hand-side column, regions: b, dx, t2 and dsym are column regions; res and step stay with the instance (see k_residual_symmetric)
+    const size_t col = (regions ? column_shift(bt.b, gridDim.y) : 0) + blockIdx.y;
     const double* res = res_ + (size_t)blockIdx.y * d.N;
-    const double* b = b_ + (size_t)blockIdx.y * d.n;
-    const double* dx = dx_ + (size_t)blockIdx.y * d.NP;
-    const double* t2 = t2_ + (size_t)blockIdx.y * d.m;
-    double* dsym = dsym_ + (size_t)blockIdx.y * d.n;
+    const double* b = b_ + col * d.n;
+    const double* dx = dx_ + col * d.NP;
+    const double* t2 = t2_ + col * d.m;
+    double* dsym = dsym_ + col * d.n;
     double* step = step_ + (size_t)blockIdx.y * d.N;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const double Hrr = sc.rho + sc.ep, Hss = 0.0 + sc.ep;
@@ -362,23 +367,25 @@ void launch_recover(calipso_hip_solver* s, double* step, const double* res, doub
     const int work = s->d.nx + s->d.ne + s->d.q + s->d.n_soc;
     const BatchSc B = batch_of(s);
     hipLaunchKernelGGL(k_recover, dim3((work + 127) / 128, 1, B.b.n), dim3(128), 0, s->stream, B, s->d, s->cone, s->solution, res,
-                       s->residual_symmetric, s->xbuf, s->t2, s->wz, s->Wsoc, s->step_symmetric, step, accumulate, s->zsx, zsx_mode);
-    launch_recover_wide(s, res, 1, s->residual_symmetric, s->t2, s->step_symmetric, step, accumulate, zsx_mode);
+                       s->residual_symmetric, s->xbuf, s->t2, s->wz, s->Wsoc, s->step_symmetric, step, accumulate, s->zsx, zsx_mode, 0);
+    launch_recover_wide(s, res, 1, s->residual_symmetric, s->t2, s->step_symmetric, step, accumulate, zsx_mode, false);
 }
-__global__ void k_scale_inplace(size_t n, double* __restrict__ x, double a) {
+__global__ void k_scale_inplace(Batch bt, size_t n, double* __restrict__ x, double a) {
+    inst_shift(bt, x);
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) x[i] = a * x[i];
 }
-// all p columns at once; dsym (n x p): the scratch the condensed steps go to, as step_symmetric for one vector (the caller's: nothing reads it afterwards)
+// all p columns at once (of every instance the launch covers); dsym (n x p): the scratch the condensed steps go to, as step_symmetric for one vector (the caller's:
+// nothing reads it afterwards)
 void launch_recover_multi(calipso_hip_solver* s, const double* res, int p, const double* rsym, const double* xbuf, const double* t2, double* dsym, double* step, double scale) {
     const int work = s->d.nx + s->d.ne + s->d.q + s->d.n_soc;
     const BatchSc B = batch_of(s);
-    hipLaunchKernelGGL(k_recover, dim3((work + 127) / 128, p, 1), dim3(128), 0, s->stream, B, s->d, s->cone, s->solution, res,
-                       rsym, xbuf, t2, s->wz, s->Wsoc, dsym, step, (double*)nullptr, (double*)nullptr, 0);
-    launch_recover_wide(s, res, p, rsym, t2, dsym, step, nullptr, 0);
+    hipLaunchKernelGGL(k_recover, dim3((work + 127) / 128, p, B.b.n), dim3(128), 0, s->stream, B, s->d, s->cone, s->solution, res,
+                       rsym, xbuf, t2, s->wz, s->Wsoc, dsym, step, (double*)nullptr, (double*)nullptr, 0, 1);
+    launch_recover_wide(s, res, p, rsym, t2, dsym, step, nullptr, 0, true);
     if (scale != 1.0) {
         const size_t n = (size_t)s->d.N * p;
-        hipLaunchKernelGGL(k_scale_inplace, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, n, step, scale);
+        hipLaunchKernelGGL(k_scale_inplace, dim3((unsigned)((n + 255) / 256), 1, B.b.n), dim3(256), 0, s->stream, B.b, n, step, scale);
     }
 }
 

@@ -601,6 +601,31 @@ function differentiate_adjoint!(g::HIPGroup, cotangent::AbstractArray{Float64,3}
     return (adjoint = adj, theta = theta ? gth[1:d.parameters, :, :] : nothing, qp = gq, status = status, ms = ms[])
 end
 
+"""differentiate! for every member of the group through the same launches (calipso_hip_group_differentiate; differentiate.jl:1-61): per member what `differentiate!` gives
+on the handle alone without correction rounds (the parameter Jacobians through `evaluate_callback`, as `solve!` of the group evaluates).  `tile`: columns per workgroup
+of the batched products, 0 = the library's choice, 16 or 64 (the same bits either way).  Every member's `solver.data.solution_sensitivity` is filled.  Returns a
+NamedTuple (sensitivity N x np x B, status, ms = (whole call, column pass))."""
+function CALIPSO.differentiate!(g::HIPGroup; tile::Integer = 0)
+    members = g.members
+    d = members[1].solver.dimensions
+    B = length(members)
+    sens = zeros(Float64, d.total, d.parameters, B)
+    status = zeros(Int32, B); ms = zeros(Float64, 2)
+    cb = @cfunction(evaluate_callback, Int32, (Ptr{Cvoid}, UInt32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}))
+    evals = fill(cb, B)
+    GC.@preserve members sens begin
+        users = Ptr{Cvoid}[pointer_from_objref(m) for m in members]
+        rc = ccall((:calipso_hip_group_set_evaluators, lib), Int32, (Ptr{Cvoid}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}), g.handle, evals, users)
+        rc < 0 && error("calipso_hip_group_set_evaluators failed ($rc)")
+        rc = ccall((:calipso_hip_group_differentiate, lib), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Int32}, Int32, Ptr{Float64}), g.handle, sens, status, tile, ms)
+        rc < 0 && error("calipso_hip_group_differentiate failed ($rc): $(last_error(members[1].handle))")
+    end
+    for (i, m) in enumerate(members)
+        m.solver.data.solution_sensitivity .= sens[:, :, i]
+    end
+    return (sensitivity = sens, status = status, ms = (ms[1], ms[2]))
+end
+
 # ---- solve! for a batch of small QPs in one kernel launch (include/calipso_hip.h: calipso_hip_smallnewton_*; csrc/smallnewton.hip) ----------------
 "`batch` independent QPs (min c x'Px + q'x s.t. Ax = b, h - Gx >= 0) of one shape: `HIPSmallNewton(nx, ne, nc, batch)`, `set_qp!` (or `set_evaluator!` + `set_parameters!` for a nonlinear problem with a device evaluator), `initialize!`, `solve!`, `differentiate!` — every instance's whole solve! in ONE launch."
 mutable struct HIPSmallNewton

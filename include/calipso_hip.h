@@ -392,6 +392,28 @@ int32_t calipso_hip_group_differentiate_adjoint(calipso_hip_group*, int64_t k,
                                                 double* const* grad_qp,    /* NULL, or six pointers P, q, A, b, G, h (NULLs skipped), each count x (k x size), matrices column-major */
                                                 int32_t* status,           /* count: what calipso_hip_differentiate_adjoint would return for that member alone */
                                                 double* ms);               /* NULL, or the HIP-event time from the entry's first enqueue to its last kernel */
+/* differentiate! in FORWARD mode for every member through the same launches (differentiate.jl:1-61): per member exactly what calipso_hip_differentiate gives on that
+ * handle alone with "opt.differentiate_refinement" = 0.  The parameter Jacobians (differentiate.jl:3) are evaluated as calipso_hip_group_solve evaluates (device evaluators
+ * inside the group's launches, host callbacks of calipso_hip_group_set_evaluators one member after the other), ONE factorisation over all members, each with the
+ * regularisation it holds (differentiate.jl:13-20, quirk B-12), dR/dtheta of all members in one launch (:23, residual_jacobian_parameters.jl:1-40), then the condensed
+ * solve of :29-58 (residual.jl:53-101, search_direction.jl:38-101) for all members' np columns in the same launches — the products and the block triangular solves as
+ * batched fp64 MFMA GEMMs with the member in a grid dimension — and sensitivity = -step (:54-56).  Every cone layout the single-handle entry admits.
+ *   sensitivity count x (N x np) host doubles, member-major, column-major per member, or NULL.  Either way every member's own solution_sensitivity and
+ *               jacobian_parameters hold its result afterwards (calipso_hip_get "solution_sensitivity" reads what it reads after calipso_hip_differentiate)
+ *   status      count codes, required: what calipso_hip_differentiate would return for that member alone (a launch the runtime refuses fails the call)
+ *   tile        columns of the batched products per workgroup: 0 = the library's choice by np, 16 or 64 force a form.  The two forms give the same bits
+ *   ms          NULL, or two HIP-event times in ms: [0] from the entry's first enqueue to its last kernel, [1] of that the column pass alone, from dR/dtheta formed to
+ *               the last kernel (without the host callbacks and the factorisation)
+ * Afterwards calipso_hip_differentiate_info of every member reads [np, 0, 0, 0].  The workspace (count x the columns of one handle's forward call) belongs to the group:
+ * grown on demand, kept, freed by calipso_hip_group_destroy; the group's reverse workspace and the members' own are left alone.
+ * CALIPSO_ERR_ARGUMENT, calipso_hip_last_error of the first member naming the cause, the group and its members usable afterwards: a dead or NULL group, a NULL status,
+ * a tile other than 0, 16, 64, np = 0, a member with "opt.differentiate_refinement" = 1 (the correction rounds have no group form), a member with an analysed structure
+ * (calipso_hip_analyze_structure, stage blocks, stage-parallel, structured handles: dense treatment only), a member with neither a device evaluator nor a callback. */
+int32_t calipso_hip_group_differentiate(calipso_hip_group*,
+                                        double* sensitivity,   /* count x (N x np), member-major, column-major per member, or NULL */
+                                        int32_t* status,       /* count: what calipso_hip_differentiate would return for that member alone */
+                                        int32_t tile,          /* 0, 16 or 64 columns per workgroup of the batched products */
+                                        double ms[2]);         /* NULL, or [whole call, column pass] in ms */
 
 /* ---- stage-banded structure -------------------------------------------------------------------------------
  * Trajectory-optimisation problems order their variables stage by stage (src/trajectory_optimization/indices.jl:41-180), which

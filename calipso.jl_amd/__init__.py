@@ -497,6 +497,13 @@ class Solver:
         self._check(self._L.calipso_hip_structure_work(self._h, _pd(out)), "structure_work")
         return dict(schur_flops=out[0], packed_doubles=out[1], segment_pairs=int(out[2]), factor_flops=out[3], factor_nnz=out[4], order=int(out[5]), structured=bool(out[6]))
 
+    def schedule_info(self):
+        """dict(prologue_ahead_steps: Newton steps so far whose prologue ran on the second stream beside the factorisation, last_prologue_mode: 0 main stream,
+        1 forked at the start of the step, 2 handed over while the pivot chain runs, ahead_undone: factorisations queued ahead of an exit test that held after all)"""
+        out = np.zeros(4)
+        self._check(self._L.calipso_hip_schedule_info(self._h, _pd(out)), "schedule_info")
+        return dict(prologue_ahead_steps=int(out[0]), last_prologue_mode=int(out[1]), ahead_undone=int(out[2]))
+
     def padded_nx(self):
         return int(self.kernel_times()[2])
 

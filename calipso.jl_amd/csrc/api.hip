@@ -231,7 +231,7 @@ static int32_t create_impl(int64_t nx, int64_t np, int64_t ne, int64_t nc, int64
     CK(hipHostGetDevicePointer((void**)&s->hscal_dev, s->hscal, 0));
     CK(hipHostGetDevicePointer((void**)&s->hicount_dev, s->hicount, 0));
     CK(hipHostGetDevicePointer((void**)&s->hseq_dev, s->hseq, 0));
-    s->hseq[0] = 0;
+    s->hseq[0] = 0; s->hseq[1] = 0;        // [0]: the main stream's publishes, [1]: the second stream's (wait_published_side)
     CK(hipStreamSynchronize(s->stream));   // the zero-fills above are complete before the (null-stream) index uploads below
     {   // dense default of the structure table: every column group visits all constraint rows
         std::vector<int> kr(4 * KG);
@@ -669,6 +669,17 @@ static int wait_published(H* s, unsigned long long seq) {
     s->err = "scalar read-back did not arrive";
     return CALIPSO_ERR_HIP;
 }
+// the same for the word of the handle's SECOND stream (hseq[1]: the norms a step's prologue publishes there, inner_iteration).  By the time the host asks — behind the
+// inertia counts of the factorisation the prologue ran beside — the word has long arrived: this is a look, not a second wait
+static int wait_published_side(H* s, unsigned long long seq) {
+    hipError_t q = hipSuccess;
+    const bool ok = host_wait([&] { return __atomic_load_n(s->hseq + 1, __ATOMIC_ACQUIRE) >= seq; },
+                              [&] { q = hipStreamQuery(s->stream2); return q == hipErrorNotReady; });
+    if (ok) return 0;
+    if (q != hipSuccess && q != hipErrorNotReady) return calipso::check(s, q, "wait_published_side");
+    s->err = "scalar read-back of the second stream did not arrive";
+    return CALIPSO_ERR_HIP;
+}
 static int read_scalars(H* s, int first, int count) { return publish_and_wait(s, s->dscal + first, s->hscal_dev + first, 2 * count); }
 static int read_icount(H* s, int first, int count) { return publish_and_wait(s, s->icount + first, s->hicount_dev + first, count); }
 static double* point_of(H* s, int which) { return which == 0 ? s->solution : s->candidate; }
@@ -693,7 +704,10 @@ static int do_factorize(H* s, int64_t inertia[3], bool rhs_ahead_ok = false) {
     // factor: on the handle's second stream they run beside k_schur (ldl.hip: ldl_rhs_stream; joined with the finish of the factorisation) instead of behind it
     s->rhs_ahead = false; s->rhs_joined = false;
     if (rhs_ahead_ok) {
-        if (hipStream_t st2 = calipso::ldl_rhs_stream(s)) {
+        hipStream_t st2 = calipso::ldl_rhs_stream(s);
+        // (a step whose prologue is handed over as a feed of the factorisation's plan: the operands need its residual and are queued by the same feed, queue_side_work)
+        if (st2 && s->side_work) s->rhs_ahead = true;
+        else if (st2) {
             (void)hipEventRecord(s->ev_side[6], s->stream);
             (void)hipStreamWaitEvent(st2, s->ev_side[6], 0);
             hipStream_t keep = s->stream;
@@ -709,7 +723,9 @@ static int do_factorize(H* s, int64_t inertia[3], bool rhs_ahead_ok = false) {
     (void)hipEventRecord(s->ev[11], s->stream);
     launch_schur(s);
     (void)hipEventRecord(s->ev[12], s->stream);
+    s->side_ran = false;
     launch_ldl(s);
+    if (s->side_work && s->rhs_ahead && !s->side_ran) s->side_work(s);      // (the plan had no place for the feed: its work behind the finish, on the main stream)
     (void)hipEventRecord(s->ev[13], s->stream);
     s->factor_times_pending = true;
     if (s->ldl_failed) { s->ldl_failed = false; SYNC(); return CALIPSO_ERR_HIP; }       // (s->err says why: launch_ldl / a dense mat-vec on a structured handle)
@@ -1011,43 +1027,111 @@ static int candidate_merit(H* s, calipso_eval_fn eval, void* user, double* Mh, d
     return CALIPSO_OK;
 }
 
+// The prologue of a step (solve.jl:100-135, 170-172): gradients, barrier + gradient, merit + gradient, residual, and the norms of the exit tests.  The factorisation reads
+// none of it (do_factorize: the point through the cone weights, [gx; hx], Lxx, the regularisation) and it reads nothing the factorisation writes; its first consumers are
+// the right-hand side of the first condensed solve, the host's exit tests and, behind the refinement, the line search.  On the main stream it stands between the
+// accepted point and the head of the next factorisation; a single handle that queues ahead runs it on its second stream, under the pivot chain, where most of the
+// chip is idle.  Same kernels on the same data: the same bits.  side: the launches go to the second stream (s->stream has been switched to it) and the norms are
+// published under that stream's own sequence word — hseq[0] is stored by the main stream alone (wait_published).
+// Hazards, buffer by buffer: the prologue writes fx, gyx, hzx, barrier_gradient, merit_gradient, residual and dscal[1], [4], [5], [8..17] and reads solution, lambda,
+// parameters, the evaluator's data (Lxx, [gx; hx], q for the QP), g, hc, cone_product, dscal[0]; k_cone_weights, k_scale_rows, k_lfac / k_schur + the panel steps and
+// the finish write kzz, wz, Wsoc, Bsoc, socwork, icount, WH, Lsym, S, Dx, Ypanel, Tinv, Ttmp, Wfac and lfac.hip's buffers and read solution, Lxx, [gx; hx]: disjoint
+// but for buffers both only read.  The mat-vecs of the QP's gradients use no scratch (gemv_t), the operands of the first solve queued behind the prologue are in
+// the same stream, and every consumer on the main stream is behind the join of the factorisation's finish (ldl.hip: enqueue_ldl_finish, ev_side[7]) or do_sds's.
+// CALIPSO_HIP_PROLOGUE_AHEAD=0: the prologue on the main stream, in front of the factorisation (read once per process, like CALIPSO_HIP_RHS_AHEAD beside it); 1: the
+// other placement, below.
+static int step_prologue(H* s, bool side, calipso_eval_fn eval = nullptr, void* user = nullptr) {
+    const int rc = evaluate(s, eval, user, 0, CALIPSO_EVAL_OBJECTIVE_GRADIENT | CALIPSO_EVAL_EQUALITY_DUAL_GRADIENT | CALIPSO_EVAL_CONE_DUAL_GRADIENT);   // :100-104
+    if (rc < 0) return rc;
+    launch_cone(s, s->solution, CALIPSO_CONE_BARRIER | CALIPSO_CONE_BARRIER_GRADIENT);   // :106-109
+    launch_merit_and_gradient(s);                                                       // :112-116, :118-124 (one launch)
+    launch_residual(s);                                                                 // :127
+    launch_violations_and_constraint(s, 4, 14, side);                                   // :130-135 and :170-172 (computed early: one read-back, published by the kernel itself)
+    return rc;
+}
+// Where the prologue of a step that queues ahead goes.  0: the main stream (groups, compact / stage-parallel handles, captured factorisations, handles whose
+// factorisation has no second stream — ldl_rhs_stream — and CALIPSO_HIP_PROLOGUE_AHEAD=0).  2 (the default): handed over by the host as a feed of the
+// factorisation's plan once the panel launch chosen in ldl.hip (ldl_plan_ranges) has started, with the operands of the first solve behind it.  1
+// (CALIPSO_HIP_PROLOGUE_AHEAD=1): forked at the start of the step — beside k_cone_weights, k_scale_rows and the first, work-bound panel launches.  Measured at C3,
+// alternating on one box (profiles/r07_ab_prologue.txt): the feed gains, the fork at the start loses against the one-stream order.
+static int prologue_ahead_mode(H* s) {
+    static const int env = [] { const char* e = getenv("CALIPSO_HIP_PROLOGUE_AHEAD"); return e ? atoi(e) : 2; }();
+    if (env <= 0 || calipso::ldl_rhs_stream(s) == nullptr) return 0;
+    return env == 1 ? 1 : 2;
+}
+// what the feed of kind 2 enqueues (ldl.hip: enqueue_feed, with s->stream switched to the stream it feeds): the prologue, once per step, and the operands of the
+// first condensed solve of every factorisation of the step (as do_factorize queues them)
+static void queue_side_work(H* s) {
+    s->side_ran = true;
+    if (s->prologue_pending) {
+        s->prologue_pending = false;
+        s->prologue_rc = step_prologue(s, true);
+        if (s->prologue_rc < 0) return;
+    }
+    launch_residual_symmetric(s, s->residual);
+    if (s->d.m) calipso::gemv_t(s, s->d.m, s->d.nx, s->Z, s->d.m, s->t1, s->xbuf, 1.0, 1.0, calipso::SP_Z);
+}
+
 // one pass of the inner loop body of solve! (solve.jl:98-353)
 static int inner_iteration(H* s, calipso_eval_fn eval, void* user, double equality_violation, double cone_product_violation, IterInfo& info,
                            double* eq_viol_out, double* cp_viol_out, bool violations_unread = false) {
     const Options& o = s->opt; Scalars& sc = s->sc; const Dims& d = s->d;
     int rc;
     EV(0);
-    rc = evaluate(s, eval, user, 0, CALIPSO_EVAL_OBJECTIVE_GRADIENT | CALIPSO_EVAL_EQUALITY_DUAL_GRADIENT | CALIPSO_EVAL_CONE_DUAL_GRADIENT);   // :100-104
-    if (rc < 0) return rc;
-    launch_cone(s, s->solution, CALIPSO_CONE_BARRIER | CALIPSO_CONE_BARRIER_GRADIENT);   // :106-109
-    launch_merit_and_gradient(s);                                                       // :112-116, :118-124 (one launch)
-    launch_residual(s);                                                                 // :127
-    launch_violations_and_constraint(s, 4, 14);                                         // :130-135 and :170-172 (computed early: one read-back, published by the kernel itself)
-    uint32_t fl = CALIPSO_EVAL_OBJECTIVE_HESSIAN | CALIPSO_EVAL_EQUALITY_JACOBIAN | CALIPSO_EVAL_CONE_JACOBIAN;
-    if (o.constraint_tensor != 0.0) fl |= CALIPSO_EVAL_EQUALITY_DUAL_HESSIAN | CALIPSO_EVAL_CONE_DUAL_HESSIAN;
     // Queue-ahead (spec_step_ok): when the last step of this handle went on to a search direction with its optimality error well above the exit thresholds, this one
-    // very likely does too — :175-181 and IC-1 are queued BEFORE the host has seen the norms (they arrive with the inertia counts, in stream order).  Should an exit test
-    // hold after all, the factorisation was for nothing: its traces (regularisation, counters, operands queued on the second stream) are undone.
+    // very likely does too — :175-181 and IC-1 are queued BEFORE the host has seen the norms (they arrive with the inertia counts).  Should an exit test
+    // hold after all, the factorisation was for nothing: its traces (regularisation, counters, work queued on the second stream) are undone.
     const bool spec = spec_step_ok(s);
     const bool ahead = spec && s->spec_ahead_ok;
+    // ... and the prologue of such a step goes to the second stream (prologue_ahead_mode): the main stream goes straight on to the factorisation
+    const int side = ahead ? prologue_ahead_mode(s) : 0;
+    struct SideWork {                         // (the feed hook of ldl.hip lives as long as this step's factorisations)
+        H* s; ~SideWork() { s->side_work = nullptr; s->prologue_pending = false; }
+    } side_guard{s};
+    s->last_prologue_mode = side;
+    const unsigned long long side_seq = side ? s->pub_seq2 + 1 : 0;      // (what the prologue's last kernel will publish under)
+    if (side == 1) {
+        (void)hipEventRecord(s->ev_side[5], s->stream);                   // behind the last kernel of the previous step
+        (void)hipStreamWaitEvent(s->stream2, s->ev_side[5], 0);
+        hipStream_t keep = s->stream;
+        s->stream = s->stream2;                                          // (a user's device evaluator is handed the stream it is to enqueue on: device_evaluate)
+        rc = step_prologue(s, true);
+        s->stream = keep;
+    } else if (side == 2) {
+        s->side_work = queue_side_work; s->prologue_pending = true; s->prologue_rc = 0;
+        rc = 0;
+    } else rc = step_prologue(s, false, eval, user);
+    if (rc < 0) return rc;
+    if (side) s->prologue_ahead_steps += 1;
+    uint32_t fl = CALIPSO_EVAL_OBJECTIVE_HESSIAN | CALIPSO_EVAL_EQUALITY_JACOBIAN | CALIPSO_EVAL_CONE_JACOBIAN;
+    if (o.constraint_tensor != 0.0) fl |= CALIPSO_EVAL_EQUALITY_DUAL_HESSIAN | CALIPSO_EVAL_CONE_DUAL_HESSIAN;
     const Scalars sc_before = sc;
     int64_t in0[3] = {0, 0, 0};
     int rc0 = 0;
+    // nothing of the second stream stays in flight when the step is left early
+    auto drain_side = [&] {
+        if ((side || s->rhs_ahead) && s->stream2) (void)hipStreamSynchronize(s->stream2);
+        s->rhs_ahead = false; s->rhs_joined = false;
+    };
     if (ahead) {
         EV(1);
         rc = evaluate(s, eval, user, 0, fl);                                            // :175-181
-        if (rc < 0) return rc;
+        if (rc < 0) { drain_side(); return rc; }
         EV(2);
         ic_begin(o, sc);
         rc0 = do_factorize(s, in0, true);                                               // IC-1 of inertia_correction! (its read-back is behind the norms' in the stream)
-        if (rc0 < 0) return rc0;
+        if (rc0 >= 0 && side && s->prologue_rc < 0) rc0 = s->prologue_rc;               // (a device evaluator refused inside the feed)
+        if (rc0 < 0) { drain_side(); return rc0; }
+        // the norms of a prologue on the second stream come under that stream's word: published long before the inertia counts the host has just waited for
+        if (side && wait_published_side(s, side_seq)) { drain_side(); return CALIPSO_ERR_HIP; }
     } else if (wait_published(s, s->pub_seq)) return CALIPSO_ERR_HIP;
     auto undo_ahead = [&] {
         if (!ahead) return;
-        if (s->rhs_ahead && s->stream2) (void)hipStreamSynchronize(s->stream2);
+        if ((side || s->rhs_ahead) && s->stream2) (void)hipStreamSynchronize(s->stream2);
         s->rhs_ahead = false; s->rhs_joined = false;
         sc.ep = sc_before.ep; sc.ed = sc_before.ed;
         s->stats.factorizations -= 1; s->phase_ms[8] -= 1.0;
+        s->ahead_undone += 1;
         s->spec_ahead_ok = false;
     };
     info.M = s->hscal[4]; info.theta = s->hscal[5];
@@ -1529,6 +1613,15 @@ int32_t calipso_hip_kernel_times(H* s, double out[8]) {
         float ms = 0.f;
         if (hipEventElapsedTime(&ms, s->ev[5], s->ev[6]) == hipSuccess) { out[4] = ms; out[5] = 8.0 * ((double)s->d.m * s->d.nx + (double)s->d.nx * s->d.nx); }
     }
+    return CALIPSO_OK;
+}
+
+// Which schedule the handle's Newton steps took (tests/test_gpu_prologue_ahead.py): [0] steps so far whose prologue ran on the second stream (inner_iteration),
+// [1] where the last step's went (0: main stream, 1: forked at its start, 2: a feed of the factorisation's plan), [2] factorisations queued ahead of an exit test
+// that held after all (undone), [3]: 0
+int32_t calipso_hip_schedule_info(H* s, double out[4]) {
+    if (!s || !out) return CALIPSO_ERR_ARGUMENT;
+    out[0] = (double)s->prologue_ahead_steps; out[1] = (double)s->last_prologue_mode; out[2] = (double)s->ahead_undone; out[3] = 0.0;
     return CALIPSO_OK;
 }
 

@@ -161,6 +161,16 @@ struct calipso_hip_solver {
     calipso_device_block_eval_fn dev_block_eval = nullptr;   // structured handles: the evaluator writes the packed blocks (no dense scratch)
     void* dev_block_eval_user = nullptr;
     size_t scratch_bytes = 0;                    // dense scratch of a structured handle with a dense-layout device evaluator (evalL / evalZ) + the workspaces of differentiate! (columns.hip: all but the forward's unrefined pipeline)
+    // api.hip: inner_iteration — the prologue of a step that queues ahead (gradients, barrier, merit + gradient, residual, norms: nothing the factorisation reads) runs
+    // on the second stream.  last_prologue_mode: 0 on the main stream, 1 forked at the start of the step, 2 handed over as a feed of the factorisation's plan (ldl.hip);
+    // side_work: what a feed of kind 2 enqueues (set for the factorisations of such a step); prologue_pending: the prologue itself is still to be queued by it
+    int last_prologue_mode = 0;                           // (calipso_hip_schedule_info)
+    bool prologue_pending = false, side_ran = false;      // side_ran: the feed of the factorisation in progress has been queued
+    int prologue_rc = 0;                                  // what the evaluator returned inside the feed
+    void (*side_work)(calipso_hip_solver*) = nullptr;
+    unsigned long long pub_seq2 = 0;              // sequence numbers of the second stream's own word hseq[1] (the norms the prologue publishes there)
+    long long prologue_ahead_steps = 0;           // steps so far whose prologue ran on the second stream (calipso_hip_schedule_info)
+    long long ahead_undone = 0;                   // factorisations queued ahead of an exit test that held after all (inner_iteration: undo_ahead)
     bool rhs_ahead = false, rhs_joined = false;   // the operands of the first condensed solve were queued on the second stream during this factorisation (ldl.hip: ldl_rhs_stream) / the main stream has joined it
     double *evalL = nullptr, *evalZ = nullptr;   // structured handle with a device evaluator: dense scratch (nx^2, m nx) the evaluator writes; packed into the blocks behind it
     std::map<std::string, double*> optd;
@@ -275,7 +285,7 @@ struct calipso_hip_solver {
     int ldl_step_launches = 0;           // panel-step launches (k_ldl_diag + k_ldl_step) of the last blocked factorisation
     int ldl_forks = 0;                   // feeds the last enqueue_ldl_steps left to the second stream (the first ldl_forks of ldl_feeds); the ranges of columns they refer to: ...
     std::vector<int> ldl_ranges;         // ... (first column, width) pairs, in order; range f may be finished once panel step (c0 + w) / 64 has STARTED
-    std::vector<int> ldl_feeds;          // (panel step that must have started, kind, argument) triples in hand-over order; kind 0: finish of range `argument`, 1: W-form product of solve block `argument`
+    std::vector<int> ldl_feeds;          // (panel step that must have started, kind, argument) triples in hand-over order; kind 0: finish of range `argument`, 1: W-form product of solve block `argument`, 2: the step's own work for the second stream (side_work)
     unsigned long long ldl_epoch = 0;    // factorisations so far (tags the progress word)
     unsigned long long *hprog = nullptr, *hprog_dev = nullptr;   // mapped host word: epoch << 16 | index of the last panel step that started
     hipEvent_t ev_side[8] = {};          // [7]: the join (second stream -> main)
@@ -333,7 +343,7 @@ void launch_first_candidate_batch(calipso_hip_solver* s, const double* a_s, cons
 void launch_first_candidate_from_masks(calipso_hip_solver* s);                                     // the step sizes from the cone-search masks on the device (no host round trip)
 void launch_constraint_violation(calipso_hip_solver* s, const double* point, int pub_first = 0, int pub_count = 0);   // -> dscal[5]
 void launch_merit_and_constraint(calipso_hip_solver* s, const double* point, int pub_first, int pub_count);   // k_merit + k_constraint_violation in one launch
-void launch_violations_and_constraint(calipso_hip_solver* s, int pub_first = 0, int pub_count = 0);   // both at the current point, one launch
+void launch_violations_and_constraint(calipso_hip_solver* s, int pub_first = 0, int pub_count = 0, bool side = false);   // both at the current point, one launch; side: queued on the second stream — published under that stream's own sequence word (hseq[1], pub_seq2)
 void launch_dot_merit(calipso_hip_solver* s);                   // -> dscal[6]
 void launch_Hmul(calipso_hip_solver* s, const double* v, double* out);   // out = H v
 void launch_residual_error(calipso_hip_solver* s, const double* step);   // residual_error = residual - H step ; dscal[7] = inf-norm

@@ -678,6 +678,14 @@ static void ldl_plan_ranges(calipso_hip_solver* s) {
             feeds.push_back({step, 1, b0 / tb});
         }
     }
+    if (s->side_work) {
+        // the step's own work for the second stream (api.hip: queue_side_work — the prologue of the step and the operands of the first solve, ~70 us of mat-vecs and
+        // one-workgroup kernels): handed over when the third panel launch has started.  Measured at C3 (profiles/r07_ab_prologue.txt: launch 2, 6, 10, 14, 18, 24, 30 of
+        // 41 -> 559, 555, 553, 550, 549, 540, 537 steps/s against 538 without): the earlier the better, as long as it stays clear of the head — forked at the very
+        // start of the step, beside k_cone_weights, k_scale_rows and the first, longest, work-bound launch, it costs more than it saves (528)
+        const int step = std::max(0, std::min(nblk - 2, 2));
+        feeds.push_back({step, 2, 0});
+    }
     std::stable_sort(feeds.begin(), feeds.end(), [](const std::array<int, 3>& a, const std::array<int, 3>& b) { return a[0] < b[0]; });
     for (const auto& f : feeds) { s->ldl_feeds.push_back(f[0]); s->ldl_feeds.push_back(f[1]); s->ldl_feeds.push_back(f[2]); }
 }
@@ -685,6 +693,13 @@ static void ldl_plan_ranges(calipso_hip_solver* s) {
 static void enqueue_feed(calipso_hip_solver* s, hipStream_t stream, int i, bool beside) {
     const int kind = s->ldl_feeds[3 * i + 1], arg = s->ldl_feeds[3 * i + 2];
     if (kind == 0) { enqueue_finish_feed(s, stream, arg); return; }
+    if (kind == 2) {                                     // the step's own work: its launchers enqueue on the handle's stream, which is `stream` for their duration
+        hipStream_t keep = s->stream;
+        s->stream = stream;
+        if (s->side_work) s->side_work(s);
+        s->stream = keep;
+        return;
+    }
     if (!beside) { enqueue_wform(s, stream, arg); return; }
     const int NP = s->d.NP, tb = trsv_block(NP, (int)s->solve_block);
     const int k0 = arg * tb, w = std::min(tb, NP - k0), rb = NP - k0 - w;

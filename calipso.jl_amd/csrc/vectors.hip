@@ -654,12 +654,15 @@ void launch_merit_and_constraint(calipso_hip_solver* s, const double* point, int
                        pub_first, pub_count, pub ? s->hscal_dev : (double*)nullptr, pub ? s->hseq_dev : (unsigned long long*)nullptr, pub ? ++s->pub_seq : 0ULL);
 }
 
-void launch_violations_and_constraint(calipso_hip_solver* s, int pub_first, int pub_count) {
+void launch_violations_and_constraint(calipso_hip_solver* s, int pub_first, int pub_count, bool side) {
     const BatchSc B = batch_of(s);
     const bool pub = pub_count > 0 && !s->cur;
+    // side: the launch is on the handle's second stream.  The sequence numbers of hseq[0] are stored by the main stream alone (api.hip: wait_published relies on it), so
+    // the second stream publishes under a word and a counter of its own
+    unsigned long long* const word = !pub ? (unsigned long long*)nullptr : (side ? s->hseq_dev + 1 : s->hseq_dev);
+    const unsigned long long seq = !pub ? 0ULL : (side ? ++s->pub_seq2 : ++s->pub_seq);
     hipLaunchKernelGGL(k_violations_and_constraint, dim3(1, 1, B.b.n), dim3(RT), 0, s->stream, B.b, s->d, norm_type(s->opt.residual_norm), norm_type(s->opt.constraint_norm),
-                       s->residual, s->solution, s->g, s->cone_product, s->hc, s->dscal, pub_first, pub_count, pub ? s->hscal_dev : (double*)nullptr,
-                       pub ? s->hseq_dev : (unsigned long long*)nullptr, pub ? ++s->pub_seq : 0ULL);
+                       s->residual, s->solution, s->g, s->cone_product, s->hc, s->dscal, pub_first, pub_count, pub ? s->hscal_dev : (double*)nullptr, word, seq);
 }
 
 // d = dot(merit_gradient, step.primals)   line_search.jl:3,16 -> dscal[6]   (one workgroup of RT threads per instance)

@@ -490,6 +490,14 @@ function kernel_times(hs::HIPSolver)
     return out
 end
 
+# calipso_hip_schedule_info: [1] Newton steps so far whose prologue ran on the second stream beside the factorisation, [2] where the last step's went (0 main stream,
+# 1 forked at the start of the step, 2 handed over while the pivot chain runs), [3] factorisations queued ahead of an exit test that held after all
+function schedule_info(hs::HIPSolver)
+    out = zeros(Float64, 4)
+    ccall((:calipso_hip_schedule_info, lib), Int32, (Ptr{Cvoid}, Ptr{Float64}), hs.handle, out)
+    return out
+end
+
 "After `analyze_structure!`: factor the Schur complement by the multifrontal sparse LDL' over a nested dissection of its pattern (log2(stages) launches instead of the chain of nx pivots); `batch` >= the largest group this solver leads. Returns (tree levels, largest front, nnz of the pattern, 2)."
 function set_stage_parallel!(hs::HIPSolver, on::Bool=true; batch::Integer=1)
     out = zeros(Int64, 4)

@@ -719,6 +719,11 @@ int32_t calipso_hip_kernel_times(calipso_hip_solver*, double out[8]);
  * comes from): [0] flops of the Schur complement by segment pairs (k_schur_blocks)   [1] doubles of the packed blocks of [gx; hx] and Lxx (both orientations)
  * [2] segment pairs   [3] flops of one multifrontal LDL^T of S   [4] nnz(L) of its fronts   [5] order of S   [6] 1 for a structured handle   [7] reserved */
 int32_t calipso_hip_structure_work(calipso_hip_solver*, double out[8]);
+/* which schedule the handle's Newton steps took: [0] steps so far whose prologue (gradients, barrier, merit + gradient, residual, norms: solve.jl:100-135) ran on
+ * the handle's second stream beside the factorisation instead of in front of it (a single handle that queues the step ahead; CALIPSO_HIP_PROLOGUE_AHEAD=0: never)
+ * [1] where the last step's went: 0 main stream, 1 forked at the start of the step, 2 handed over while the pivot chain runs   [2] factorisations queued ahead of an exit
+ * test that held after all (their traces were undone)   [3] reserved */
+int32_t calipso_hip_schedule_info(calipso_hip_solver*, double out[4]);
 int32_t calipso_hip_synchronize(calipso_hip_solver*);
 /* Independent Solvers stepped from different host threads (solver.jl:46-150: the reference's Solvers are independent objects; batch.py: lanes) overlap on the GPU only
  * if the runtime put their streams behind different hardware dispatchers — which depends on the order in which the process created its streams and cannot be queried.

@@ -11,6 +11,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import CALLBACK_FN, EVAL_FN, CalipsoHipError, lib
+from ._marshal import QP_NAMES, pack_cotangent, qp_names, qp_shapes, unpack_columns
 
 __all__ = ["Solver", "Group", "LDLSolver", "SmallBatch", "Comm", "ordering", "symbolic", "Options", "initialize_b", "solve_b", "CalipsoHipError", "FLAGS", "splitmix_uniform",
            "mfma_f64_peak"]
@@ -36,6 +37,61 @@ def _pd(a):
 
 def _pi(a):
     return a.ctypes.data_as(C.POINTER(C.c_int64))
+
+
+def _opt(a):
+    return _pd(a) if a is not None else None
+
+
+class _Handle:
+    """what the classes around a handle of the library share: the status check and the release.  Class attributes name the attribute that holds the handle, the
+    library's last_error and destroy entries for it and the text of the error; nothing here needs an __init__"""
+    _handle, _last_error, _destroy, _message = "_h", "calipso_hip_last_error", "calipso_hip_destroy", "%(what)s failed (%(rc)d): %(text)s"
+    _STATUS_MESSAGE = "%(what)s: %(status)s (%(rc)d): %(text)s"      # the classes whose statuses are the CALIPSO_ERR_* of STATUS_TEXT
+
+    def _error_text(self):
+        return getattr(self._L, self._last_error)(getattr(self, self._handle)).decode()
+
+    def _check(self, rc, what):
+        if rc < 0:
+            raise CalipsoHipError(self._message % dict(what=what, status=STATUS_TEXT.get(rc, "error"), rc=rc, text=self._error_text()))
+        return rc
+
+    def close(self):
+        h = getattr(self, self._handle, None)
+        if h is not None and h.value:
+            getattr(self._L, self._destroy)(h)
+            setattr(self, self._handle, C.c_void_p())
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _vjp(handle, lead, cotangent, adjoint, theta, qp, message, call):
+    """the body of Solver.vjp (lead = ()) and Group.vjp (lead = (count,)) for a `handle` with nx, ne, nc, np, N: pack the cotangent, size the buffers, call(k,
+    cotangent, adjoint, theta, the six QP pointers) — the C entry —, and unpack what it wrote into lead + shape [+ (k,)]"""
+    vc, k, squeeze = (None, 1, True) if cotangent is None else pack_cotangent(cotangent, lead, handle.N, message)
+    if theta is None:
+        theta = handle.np > 0
+    names = qp_names(qp)
+    shape = qp_shapes(handle.nx, handle.ne, handle.nc)
+    columns = int(np.prod(lead, dtype=np.int64)) * max(k, 1)
+    adj = np.zeros(columns * handle.N) if adjoint else None
+    gth = np.zeros(max(columns * handle.np, 1)) if theta else None
+    arrays = {c: np.zeros(max(columns * int(np.prod(shape[c])), 1)) for c in names}
+    ptrs = (C.POINTER(C.c_double) * 6)(*[_pd(arrays[c]) if c in arrays else None for c in QP_NAMES]) if names else None
+    call(int(k), _opt(vc), _opt(adj), _opt(gth), ptrs)
+    out = {}
+    if adjoint:
+        out["adjoint"] = unpack_columns(adj, lead, k, (handle.N,), squeeze)
+    if theta:
+        out["theta"] = unpack_columns(gth, lead, k, (handle.np,), squeeze)
+    for c in names:
+        out[c] = unpack_columns(arrays[c], lead, k, shape[c], squeeze)
+    return out
 
 
 def splitmix_uniform(problem_id, stream_id, lo, hi, count):
@@ -71,12 +127,13 @@ class _Dims:
     pass
 
 
-class Solver:
+class Solver(_Handle):
     """Solver(methods, num_variables, num_parameters, num_equality, num_cone; parameters, nonnegative_indices,
     second_order_indices, options)  — src/solver/solver.jl:46-150.
 
     `methods` stands in for ProblemMethods (src/solver/methods.jl): an object with
     evaluate(flags, x, y, z, theta, out) writing the requested ProblemData fields through out(name)."""
+    _message = _Handle._STATUS_MESSAGE
 
     def __init__(self, methods, num_variables, num_parameters, num_equality, num_cone, parameters=None,
                  nonnegative_indices=None, second_order_indices=None, options=None, device=0, structure=None):
@@ -142,20 +199,7 @@ class Solver:
             self.set_option(k, v)
         self._cb = EVAL_FN(self._evaluate_callback)
 
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) is not None and self._h.value:
-                self._L.calipso_hip_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
-
     # ---- plumbing ---------------------------------------------------------------------------------------------
-    def _check(self, rc, what):
-        if rc < 0:
-            raise CalipsoHipError("%s: %s (%d): %s" % (what, STATUS_TEXT.get(rc, "error"), rc, self._L.calipso_hip_last_error(self._h).decode()))
-        return rc
-
     def set(self, name, arr):
         a = np.ascontiguousarray(np.asarray(arr, dtype=np.float64).reshape(-1))
         self._check(self._L.calipso_hip_set_field(self._h, name.encode(), _pd(a), a.size), "set_field(%s)" % name)
@@ -361,8 +405,11 @@ class Solver:
     def differentiate_info(self):
         """report of the last differentiate() (calipso_hip_differentiate_info; set_option("differentiate_refinement", 1) turns the correction rounds on):
         dict(columns, rounds (largest over the columns), failed_columns (did not meet the stopping test), final_norm (largest over the columns)); zeros when no round ran"""
+        return self._column_report("differentiate_info")
+
+    def _column_report(self, what):
         out = np.zeros(4)
-        self._check(self._L.calipso_hip_differentiate_info(self._h, _pd(out)), "differentiate_info")
+        self._check(getattr(self._L, "calipso_hip_" + what)(self._h, _pd(out)), what)
         return dict(columns=int(out[0]), rounds=int(out[1]), failed_columns=int(out[2]), final_norm=float(out[3]))
 
     def vjp(self, cotangent, adjoint=True, theta=None, qp=None):
@@ -372,52 +419,12 @@ class Solver:
         of "PqAbGh": the data gradients of the QP given to qp_attach.  Returns a dict: "adjoint" (N[, k]), "theta" (np[, k]) and one entry per requested QP array in
         qp_attach's shape ([, k]); the trailing k axis only when the cotangent had one.  set_option("differentiate_refinement", 1) turns the correction rounds on
         (vjp_info)."""
-        N = self.N
-        squeeze = True
-        if cotangent is None:
-            vc, k = None, 1
-        else:
-            v = np.asarray(cotangent, dtype=np.float64)
-            squeeze = v.ndim == 1
-            if squeeze:
-                v = v[:, None]
-            if v.ndim != 2 or v.shape[0] != N:
-                raise ValueError("cotangent must be (N,) or (N, k)")
-            k = v.shape[1]
-            vc = np.ascontiguousarray(v.T).ravel()                              # column-major N x k
-        if theta is None:
-            theta = self.np > 0
-        names = "PqAbGh" if qp is True else (qp or "")
-        if any(c not in "PqAbGh" for c in names):
-            raise ValueError("qp must be True or a string of names out of 'PqAbGh'")
-        nx, ne, nc = self.nx, self.ne, self.nc
-        shape = dict(P=(nx, nx), q=(nx,), A=(ne, nx), b=(ne,), G=(nc, nx), h=(nc,))
-        kk = max(k, 1)
-        adj = np.zeros(kk * N) if adjoint else None
-        gth = np.zeros(max(kk * self.np, 1)) if theta else None
-        arrays = {c: np.zeros(max(kk * int(np.prod(shape[c])), 1)) for c in names}
-        ptrs = None
-        if names:
-            ptrs = (C.POINTER(C.c_double) * 6)(*[_pd(arrays[c]) if c in arrays else None for c in "PqAbGh"])
-        opt = lambda a: _pd(a) if a is not None else None
-        self._check(self._L.calipso_hip_differentiate_adjoint(self._h, self._cb, None, int(k), opt(vc), opt(adj), opt(gth), ptrs), "differentiate_adjoint")
-        fin = lambda a: a[..., 0] if squeeze else a
-        out = {}
-        if adjoint:
-            out["adjoint"] = fin(adj.reshape(k, N).T.copy())
-        if theta:
-            out["theta"] = fin(gth[:k * self.np].reshape(k, self.np).T.copy())
-        for c in names:
-            sh = shape[c]
-            a = arrays[c][:k * int(np.prod(sh))]
-            out[c] = fin(np.transpose(a.reshape(k, nx, sh[0]), (2, 1, 0)).copy() if len(sh) == 2 else a.reshape(k, sh[0]).T.copy())
-        return out
+        call = lambda *args: self._check(self._L.calipso_hip_differentiate_adjoint(self._h, self._cb, None, *args), "differentiate_adjoint")
+        return _vjp(self, (), cotangent, adjoint, theta, qp, "cotangent must be (N,) or (N, k)", call)
 
     def vjp_info(self):
         """report of the last vjp() (calipso_hip_differentiate_adjoint_info), as differentiate_info(): dict(columns, rounds, failed_columns, final_norm)"""
-        out = np.zeros(4)
-        self._check(self._L.calipso_hip_differentiate_adjoint_info(self._h, _pd(out)), "differentiate_adjoint_info")
-        return dict(columns=int(out[0]), rounds=int(out[1]), failed_columns=int(out[2]), final_norm=float(out[3]))
+        return self._column_report("differentiate_adjoint_info")
 
     def vjp_times(self):
         """HIP-event times of the last vjp() in ms: dict(device = entry to last kernel, copy = the results to the host, gradients = of device, the QP data-gradient
@@ -549,13 +556,13 @@ class Solver:
         self._check(self._L.calipso_hip_rebind_stream(self._h, int(priority_class)), "rebind_stream")
 
 
-class Group:
+class Group(_Handle):
     """Up to 128 Solver handles of one shape (same dimensions and cone layout, same device) stepped in lockstep: every kernel
     launch of a group step covers all members (include/calipso_hip.h, "groups").  The reference has no counterpart — its
     `Solver`s are independent objects; this is how BASELINE config C4 keeps many of them in flight on one GPU."""
+    _handle, _destroy, _message = "_g", "calipso_hip_group_destroy", _Handle._STATUS_MESSAGE
 
     def __init__(self, solvers):
-        import ctypes as C
         self.solvers = list(solvers)
         self._L = self.solvers[0]._L
         arr = (C.c_void_p * len(self.solvers))(*[s._h for s in self.solvers])
@@ -565,16 +572,19 @@ class Group:
             raise CalipsoHipError("group_create failed (%d): %s" % (rc, self._L.calipso_hip_last_error(self.solvers[0]._h).decode()))
         self._g = h
 
+    def _error_text(self):
+        return self._L.calipso_hip_last_error(self.solvers[0]._h).decode()      # (the library keeps a group's errors on its first member)
+
+    def _set_evaluators(self):
+        self._evals = (EVAL_FN * len(self.solvers))(*[s._cb for s in self.solvers])       # host callbacks (used by members without a device evaluator)
+        self._L.calipso_hip_group_set_evaluators(self._g, self._evals, None)
+
     def newton_step(self, advance=False):
         """calipso_hip_newton_step for every member; returns one info dict per member (same keys as Solver.newton_step)"""
-        import ctypes as C
         B = len(self.solvers)
         info = np.zeros(6 * B)
         status = (C.c_int32 * B)()
-        rc = self._L.calipso_hip_group_newton_step(self._g, int(advance), _pd(info), status)
-        if rc < 0:
-            raise CalipsoHipError("group_newton_step: %s (%d): %s" % (STATUS_TEXT.get(rc, "error"), rc,
-                                                                      self._L.calipso_hip_last_error(self.solvers[0]._h).decode()))
+        self._check(self._L.calipso_hip_group_newton_step(self._g, int(advance), _pd(info), status), "group_newton_step")
         out = []
         for k in range(B):
             r = info[6 * k: 6 * k + 6]
@@ -585,14 +595,10 @@ class Group:
     def solve(self):
         """solve!(solver) for every member in lockstep (device evaluators attached); returns the per-member results
         (1 converged, 0 iteration caps reached, negative = error code of that member)"""
-        import ctypes as C
         B = len(self.solvers)
         res = (C.c_int32 * B)()
-        self._evals = (EVAL_FN * B)(*[s._cb for s in self.solvers])       # host callbacks (used by members without a device evaluator)
-        self._L.calipso_hip_group_set_evaluators(self._g, self._evals, None)
-        rc = self._L.calipso_hip_group_solve(self._g, res)
-        if rc < 0:
-            raise CalipsoHipError("group_solve: %s (%d): %s" % (STATUS_TEXT.get(rc, "error"), rc, self._L.calipso_hip_last_error(self.solvers[0]._h).decode()))
+        self._set_evaluators()
+        self._check(self._L.calipso_hip_group_solve(self._g, res), "group_solve")
         return [int(v) for v in res]
 
     def differentiate(self, tile=0):
@@ -600,17 +606,13 @@ class Group:
         with differentiate_refinement off (the parameter Jacobians of members without a device evaluator come through their host callbacks, as in solve()).  tile: columns
         per workgroup of the batched products, 0 = the library's choice, 16 or 64 (the same bits either way).  Returns dict(sensitivity (count, N, np) = dw/dtheta per
         member — what each member's data("solution_sensitivity") reads afterwards —, status (count,))."""
-        import ctypes as C
         s0 = self.solvers[0]
         B, N, npar = len(self.solvers), s0.N, s0.np
         sens = np.zeros(max(B * N * npar, 1))
         status = np.zeros(B, dtype=np.int32)
         ms = np.zeros(2)
-        self._evals = (EVAL_FN * B)(*[s._cb for s in self.solvers])       # host callbacks (used by members without a device evaluator)
-        self._L.calipso_hip_group_set_evaluators(self._g, self._evals, None)
-        rc = self._L.calipso_hip_group_differentiate(self._g, _pd(sens), status.ctypes.data_as(C.POINTER(C.c_int32)), int(tile), _pd(ms))
-        if rc < 0:
-            raise CalipsoHipError("group_differentiate: %s (%d): %s" % (STATUS_TEXT.get(rc, "error"), rc, self._L.calipso_hip_last_error(s0._h).decode()))
+        self._set_evaluators()
+        self._check(self._L.calipso_hip_group_differentiate(self._g, _pd(sens), status.ctypes.data_as(C.POINTER(C.c_int32)), int(tile), _pd(ms)), "group_differentiate")
         self._differentiate_ms = (float(ms[0]), float(ms[1]))
         return dict(sensitivity=np.transpose(sens[:B * N * npar].reshape(B, npar, N), (0, 2, 1)).copy(), status=status)
 
@@ -624,54 +626,15 @@ class Group:
         (the parameter Jacobians of members without a device evaluator come through their host callbacks, as in solve()).  Returns a dict of arrays with a leading member
         axis: "adjoint" (count, N[, k]), "theta" (count, np[, k]), one entry per requested QP array in qp_attach's shape (count, ...[, k]), and "status" (count,); the
         trailing k axis only when the cotangent had one."""
-        import ctypes as C
-        s0 = self.solvers[0]
-        B, N, npar = len(self.solvers), s0.N, s0.np
-        squeeze = True
-        if cotangent is None:
-            vc, k = None, 1
-        else:
-            v = np.asarray(cotangent, dtype=np.float64)
-            squeeze = v.ndim == 2
-            if squeeze:
-                v = v[:, :, None]
-            if v.ndim != 3 or v.shape[0] != B or v.shape[1] != N:
-                raise ValueError("cotangent must be (count, N) or (count, N, k)")
-            k = v.shape[2]
-            vc = np.ascontiguousarray(np.transpose(v, (0, 2, 1))).ravel()       # member-major, column-major N x k per member
-        if theta is None:
-            theta = npar > 0
-        names = "PqAbGh" if qp is True else (qp or "")
-        if any(c not in "PqAbGh" for c in names):
-            raise ValueError("qp must be True or a string of names out of 'PqAbGh'")
-        nx, ne, nc = s0.nx, s0.ne, s0.nc
-        shape = dict(P=(nx, nx), q=(nx,), A=(ne, nx), b=(ne,), G=(nc, nx), h=(nc,))
-        kk = max(k, 1)
-        adj = np.zeros(B * kk * N) if adjoint else None
-        gth = np.zeros(max(B * kk * npar, 1)) if theta else None
-        arrays = {c: np.zeros(max(B * kk * int(np.prod(shape[c])), 1)) for c in names}
-        ptrs = None
-        if names:
-            ptrs = (C.POINTER(C.c_double) * 6)(*[_pd(arrays[c]) if c in arrays else None for c in "PqAbGh"])
-        opt = lambda a: _pd(a) if a is not None else None
-        status = np.zeros(B, dtype=np.int32)
+        status = np.zeros(len(self.solvers), dtype=np.int32)
         ms = C.c_double(0.0)
-        self._evals = (EVAL_FN * B)(*[s._cb for s in self.solvers])       # host callbacks (used by members without a device evaluator)
-        self._L.calipso_hip_group_set_evaluators(self._g, self._evals, None)
-        rc = self._L.calipso_hip_group_differentiate_adjoint(self._g, int(k), opt(vc), opt(adj), opt(gth), ptrs, status.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(ms))
-        if rc < 0:
-            raise CalipsoHipError("group_differentiate_adjoint: %s (%d): %s" % (STATUS_TEXT.get(rc, "error"), rc, self._L.calipso_hip_last_error(s0._h).decode()))
+
+        def call(*args):
+            self._set_evaluators()
+            self._check(self._L.calipso_hip_group_differentiate_adjoint(self._g, *args, status.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(ms)), "group_differentiate_adjoint")
+
+        out = _vjp(self.solvers[0], (len(self.solvers),), cotangent, adjoint, theta, qp, "cotangent must be (count, N) or (count, N, k)", call)
         self._vjp_ms = float(ms.value)
-        fin = lambda a: a[..., 0] if squeeze else a
-        out = {}
-        if adjoint:
-            out["adjoint"] = fin(np.transpose(adj.reshape(B, k, N), (0, 2, 1)).copy())
-        if theta:
-            out["theta"] = fin(np.transpose(gth[:B * k * npar].reshape(B, k, npar), (0, 2, 1)).copy())
-        for c in names:
-            sh = shape[c]
-            a = arrays[c][:B * k * int(np.prod(sh))]
-            out[c] = fin(np.transpose(a.reshape(B, k, nx, sh[0]), (0, 3, 2, 1)).copy() if len(sh) == 2 else np.transpose(a.reshape(B, k, sh[0]), (0, 2, 1)).copy())
         out["status"] = status
         return out
 
@@ -684,17 +647,6 @@ class Group:
 
     def synchronize(self):
         self.solvers[0].synchronize()
-
-    def close(self):
-        if self._g is not None:
-            self._L.calipso_hip_group_destroy(self._g)
-            self._g = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _csc_1based(A):
@@ -734,9 +686,10 @@ def symbolic(A, perm=None):
     return dict(Pp=Pp, Pi=Pi[:int(info[1])], AtoPAPt=mp[:nnz], etree=et, Lnz=lnz, nnzL=int(tot), half_bandwidth=int(info[0]))
 
 
-class LDLSolver:
+class LDLSolver(_Handle):
     """LDLSolver / ldl_solver(A) of src/solver/linear_solver.jl:1-60 on the device: factorize!(s, A), compute_inertia!(s),
     linear_solve!(s, x, A, b).  A is a scipy.sparse CSC matrix (or anything scipy can convert); only triu(A) is read."""
+    _message = _Handle._STATUS_MESSAGE
 
     def __init__(self, n, device=0):
         self._L = lib()
@@ -747,11 +700,6 @@ class LDLSolver:
             raise CalipsoHipError("calipso_hip_ldl_create failed (%d): %s" % (rc, self._L.calipso_hip_last_error(h if h.value else None).decode()))
         self._h = h
         self.inertia = (0, 0, 0)          # Inertia(positive, negative, zero)  inertia.jl:1-5
-
-    def _check(self, rc, what):
-        if rc < 0:
-            raise CalipsoHipError("%s: %s (%d): %s" % (what, STATUS_TEXT.get(rc, "error"), rc, self._L.calipso_hip_last_error(self._h).decode()))
-        return rc
 
     def analyze(self, A, method="rcm", perm=None):
         """install the elimination order of the following factorisations ("natural", "rcm", "minimum_degree", or perm=<1-based order>);
@@ -788,23 +736,13 @@ class LDLSolver:
         self._check(self._L.calipso_hip_ldl_solve(self._h, self.n, nrhs, _pd(bf), _pd(x)), "linear_solve!")
         return x if b.ndim == 1 else x.reshape(nrhs, self.n).T
 
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._L.calipso_hip_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class SparseLDL:
+class SparseLDL(_Handle):
     """Sparse LDL^T on the device (include/calipso_hip.h, "sparse LDL^T on the device"): qdldl(A; perm) / QDLDL_factor! / solve! of
     src/solver/qdldl.jl for a scipy.sparse matrix A (only triu(A) is read), memory O(nnz(L)), level-scheduled over the elimination tree.
     method: "natural", "rcm", "minimum_degree", "nested_dissection" (multifrontal over the dissection tree when every front fits one CU's LDS,
     else as "nested_dissection_columns": the same order with the column-level numeric phase), or perm=<1-based order>."""
+    _last_error, _destroy = "calipso_hip_sparse_last_error", "calipso_hip_sparse_destroy"
 
     def __init__(self, A, method="nested_dissection", perm=None, device=0):
         self._L = lib()
@@ -826,11 +764,6 @@ class SparseLDL:
                          multiply_adds=int(info[6]), lds_accumulator=int(info[7]) == 1,
                          numeric={0: "columns_global_accumulator", 1: "columns_lds_accumulator", 2: "multifrontal"}[int(info[7])])
         self.inertia = (0, 0, 0)
-
-    def _check(self, rc, what):
-        if rc < 0:
-            raise CalipsoHipError("%s failed (%d): %s" % (what, rc, self._L.calipso_hip_sparse_last_error(self._h).decode()))
-        return rc
 
     def set_batch(self, batch):
         """treat `batch` matrices of the analysed pattern per factorize / solve call (values (batch, nnz), right-hand sides (batch, n[, nrhs]))"""
@@ -916,22 +849,12 @@ class SparseLDL:
         self._check(self._L.calipso_hip_sparse_timing(self._h, _pd(ms)), "sparse_timing")
         return float(ms[0]), float(ms[1])
 
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._L.calipso_hip_sparse_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class SmallBatch:
+class SmallBatch(_Handle):
     """`batch` independent small systems (n <= 128) factored and solved for `nrhs` right-hand sides each in ONE launch, every system
     resident in the LDS of one workgroup (include/calipso_hip.h, "batched small systems"): the sensitivity solves of differentiate!
     (src/solver/differentiate.jl:29-58) for many MPC steps at once."""
+    _last_error, _destroy = "calipso_hip_small_last_error", "calipso_hip_small_destroy"
 
     def __init__(self, n, nrhs, batch, device=0):
         self._L = lib()
@@ -944,11 +867,6 @@ class SmallBatch:
                 self._L.calipso_hip_small_destroy(h)
             raise CalipsoHipError("calipso_hip_small_create failed (%d): %s" % (rc, msg))
         self._h = h
-
-    def _check(self, rc, what):
-        if rc < 0:
-            raise CalipsoHipError("%s failed (%d): %s" % (what, rc, self._L.calipso_hip_small_last_error(self._h).decode()))
-        return rc
 
     def set(self, K=None, B=None):
         """K: (batch, n, n) matrices (only the upper triangles are read); B: (batch, n, nrhs) right-hand sides"""
@@ -972,19 +890,8 @@ class SmallBatch:
         bad = self._check(self._L.calipso_hip_small_get(self._h, _pd(x), _pi(inr)), "small_get")
         return np.transpose(x.reshape(self.batch, self.nrhs, self.n), (0, 2, 1)), inr.reshape(self.batch, 3), bad
 
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._L.calipso_hip_small_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class SmallNewtonBatch:
+class SmallNewtonBatch(_Handle):
     """Solver / initialize! / solve! (src/solver/solver.jl:46-150, initialize.jl:9-48, solve.jl:8-377) for `batch` independent small conic QPs of one shape in ONE
     kernel launch: a workgroup per instance, everything in LDS, every decision of solve! on the device (include/calipso_hip.h, "solve! for a batch of SMALL conic QPs";
     csrc/smallnewton.hip).  QP data as qp_attach: min c x'Px + q'x s.t. Ax = b, h - Gx >= 0 (nonnegative cones).  options={...} go to set_option: the reference's
@@ -992,6 +899,7 @@ class SmallNewtonBatch:
     instead of stopping the instance with -102; costs batch x N^2 doubles of device memory).  Nonlinear problems: set_evaluator with a device evaluator compiled
     into a HIP library of the caller's (include/calipso_smallnewton.hpp), set_parameters, differentiate() with dR/dtheta from the evaluator.  vjp(): the
     reverse mode — gradients of a loss with respect to theta or the QP's data with one solve per cotangent (torch_layer.QPLayer builds on it)."""
+    _last_error, _destroy = "calipso_hip_smallnewton_last_error", "calipso_hip_smallnewton_destroy"
 
     def __init__(self, nx, ne, nc, batch, device=0, options=None):
         self._L = lib()
@@ -1008,11 +916,6 @@ class SmallNewtonBatch:
         self.device = int(device)
         for k, v in (options or {}).items():
             self.set_option(k, v)
-
-    def _check(self, rc, what):
-        if rc < 0:
-            raise CalipsoHipError("%s failed (%d): %s" % (what, rc, self._L.calipso_hip_smallnewton_last_error(self._h).decode()))
-        return rc
 
     def set_option(self, name, value):
         self._check(self._L.calipso_hip_smallnewton_set_option(self._h, name.encode(), float(value)), "smallnewton_set_option(%s)" % name)
@@ -1126,57 +1029,43 @@ class SmallNewtonBatch:
         set); qp: the built-in QP's data gradients (default: when the QP is set).  Returns a dict: "adjoint" (batch, N[, k]), "theta" (batch, n_parameters[, k]),
         "P", "q", "A", "b", "G", "h" in set_qp's shapes (per instance, [, k]), "status" (batch,) as differentiate() and "ms"; the trailing k axis only when the
         cotangent had one"""
-        v = np.asarray(cotangent, dtype=np.float64)
-        squeeze = v.ndim == 2
-        if squeeze:
-            v = v[:, :, None]
-        if v.ndim != 3 or v.shape[0] != self.batch or v.shape[1] not in (self.N, self.nx) or v.shape[2] < 1:
-            raise ValueError("cotangent must be (batch, N), (batch, N, k), (batch, nx) or (batch, nx, k)")
-        if v.shape[1] != self.N:
-            w = np.zeros((self.batch, self.N, v.shape[2]))
-            w[:, :self.nx] = v
-            v = w
-        k = v.shape[2]
-        evaluator = getattr(self, "_evaluator", False)
-        p = getattr(self, "n_parameters", 0) if evaluator else 0
-        if theta is None:
-            theta = evaluator and p > 0
-        if qp is None:
-            qp = not evaluator
-        nx, ne, nc = self.nx, self.ne, self.nc
-        nqp = nx * nx + nx + ne * nx + ne + nc * nx + nc
-        vc = np.ascontiguousarray(np.transpose(v, (0, 2, 1))).ravel()         # per instance column-major N x k
+        message = "cotangent must be (batch, N), (batch, N, k), (batch, nx) or (batch, nx, k)"
+        lead = (self.batch,)
+        vc, k, squeeze = pack_cotangent(cotangent, lead, self.N, message, also=self.nx)
+        if k < 1:
+            raise ValueError(message)
+        p, theta, qp = self._vjp_defaults(theta, qp)
+        shape = qp_shapes(self.nx, self.ne, self.nc)
+        nqp = sum(int(np.prod(s)) for s in shape.values())
         adj = np.zeros(self.batch * self.N * k) if adjoint else None
         gth = np.zeros(self.batch * k * max(p, 1)) if theta else None
         gqp = np.zeros(self.batch * k * nqp) if qp else None
         st = np.zeros(self.batch, dtype=np.int32); ms = C.c_double(0.0)
-        opt = lambda a: _pd(a) if a is not None else None
-        self._check(self._L.calipso_hip_smallnewton_differentiate_adjoint(self._h, int(k), _pd(vc), opt(adj), opt(gth), opt(gqp), st.ctypes.data_as(C.POINTER(C.c_int32)),
+        self._check(self._L.calipso_hip_smallnewton_differentiate_adjoint(self._h, int(k), _pd(vc), _opt(adj), _opt(gth), _opt(gqp), st.ctypes.data_as(C.POINTER(C.c_int32)),
                                                                            C.byref(ms)), "smallnewton_differentiate_adjoint")
-        fin = lambda a: a[..., 0] if squeeze else a                           # (..., k) -> (...) for a cotangent without a k axis
         out = dict(status=st, ms=float(ms.value))
         if adjoint:
-            out["adjoint"] = fin(np.transpose(adj.reshape(self.batch, k, self.N), (0, 2, 1)).copy())
+            out["adjoint"] = unpack_columns(adj, lead, k, (self.N,), squeeze)
         if theta:
-            out["theta"] = fin(np.transpose(gth.reshape(self.batch, k, p), (0, 2, 1)).copy())
-        if qp:
+            out["theta"] = unpack_columns(gth, lead, k, (p,), squeeze)
+        if qp:      # ONE buffer: per instance and column the six arrays one after the other
             g = gqp.reshape(self.batch, k, nqp)
             at = 0
-            for name, r, c in (("P", nx, nx), ("q", nx, 0), ("A", ne, nx), ("b", ne, 0), ("G", nc, nx), ("h", nc, 0)):
-                n = r * c if c else r
-                blk = g[:, :, at:at + n]
+            for name, sh in shape.items():
+                n = int(np.prod(sh))
+                out[name] = unpack_columns(g[:, :, at:at + n], lead, k, sh, squeeze)
                 at += n
-                if c:      # column-major r x c -> (batch, r, c, k)
-                    out[name] = fin(np.transpose(blk.reshape(self.batch, k, c, r), (0, 3, 2, 1)).copy())
-                else:
-                    out[name] = fin(np.transpose(blk, (0, 2, 1)).copy())
         return out
 
-    # ---- the device-resident, stream-ordered entries (include/calipso_hip.h; csrc/smallnewton_io.hip): torch CUDA tensors in and out, nothing waits for the device ----
-    _QP_NAMES = "PqAbGh"
+    def _vjp_defaults(self, theta, qp):
+        """(n_parameters in use, theta, qp) of vjp() / vjp_device(): theta by default when an evaluator with parameters is set, qp when the QP is"""
+        evaluator = getattr(self, "_evaluator", False)
+        p = getattr(self, "n_parameters", 0) if evaluator else 0
+        return p, (evaluator and p > 0) if theta is None else theta, (not evaluator) if qp is None else qp
 
+    # ---- the device-resident, stream-ordered entries (include/calipso_hip.h; csrc/smallnewton_io.hip): torch CUDA tensors in and out, nothing waits for the device ----
     def _qp_dims(self):
-        return ((self.nx, self.nx), (self.nx,), (self.ne, self.nx), (self.ne,), (self.nc, self.nx), (self.nc,))
+        return tuple(qp_shapes(self.nx, self.ne, self.nc).values())
 
     def _form(self, t, name, shapes, dtype="float64"):
         """a torch tensor of the dtype and one of the shapes, contiguous"""
@@ -1221,13 +1110,13 @@ class SmallNewtonBatch:
         leading batch axis, independently of the others: a shared P is stored once.  row_major=False: the matrices are column-major, i.e. tensors of the transposed
         shape ([batch,] nx, rows).  Returns the mask of shared arrays (bit i: array i of P, q, A, b, G, h)."""
         data, mask = (P, q, A, b, G, h), 0
-        for i, (name, t, dm) in enumerate(zip(self._QP_NAMES, data, self._qp_dims())):
+        for i, (name, t, dm) in enumerate(zip(QP_NAMES, data, self._qp_dims())):
             if len(dm) == 2 and not row_major:
                 dm = (dm[1], dm[0])
             self._form(t, name, (dm, (self.batch,) + dm))
             if t.dim() == len(dm):
                 mask |= 1 << i
-        ptrs = [self._ptr(t, name) for name, t in zip(self._QP_NAMES, data)]
+        ptrs = [self._ptr(t, name) for name, t in zip(QP_NAMES, data)]
         self._check(self._L.calipso_hip_smallnewton_set_qp_device(self._h, *ptrs, float(objective_scale), mask, int(bool(row_major))), "smallnewton_set_qp_device")
         self._evaluator = False
         return mask
@@ -1290,9 +1179,9 @@ class SmallNewtonBatch:
         B, N = self.batch, self.N
         mask = 0
         for n in (reduce or ""):
-            if n not in self._QP_NAMES:
-                raise ValueError("vjp_device: reduce names arrays of " + self._QP_NAMES)
-            mask |= 1 << self._QP_NAMES.index(n)
+            if n not in QP_NAMES:
+                raise ValueError("vjp_device: reduce names arrays of " + QP_NAMES)
+            mask |= 1 << QP_NAMES.index(n)
         given = [(n, t) for n, t in (("cotangent", cotangent), ("x", x), ("y", y), ("z", z)) if t is not None]
         if not given or (cotangent is not None and len(given) > 1):
             raise ValueError("vjp_device: the cotangent as `cotangent` (batch, N[, k]) or as parts x, y, z")
@@ -1311,13 +1200,8 @@ class SmallNewtonBatch:
                 t = t.permute(0, 2, 1).contiguous()
                 ptrs[n] = C.c_void_p(t.data_ptr())
             keep.append(t)
-        evaluator = getattr(self, "_evaluator", False)
-        p = getattr(self, "n_parameters", 0) if evaluator else 0
-        if theta is None:
-            theta = evaluator and p > 0
-        if qp is None:
-            qp = not evaluator
-        names = self._QP_NAMES if qp is True else ("" if not qp else "".join(qp))
+        p, theta, qp = self._vjp_defaults(theta, qp)
+        names = qp_names(qp)
         out = dict(out or {})
         bufs = {}
 
@@ -1333,7 +1217,7 @@ class SmallNewtonBatch:
         p_th = buffer("theta", (B, k, max(p, 1))) if theta else None
         p_st = buffer("status", (B,), "int32")
         gq = (C.c_void_p * 6)()
-        for i, (n, dm) in enumerate(zip(self._QP_NAMES, self._qp_dims())):
+        for i, (n, dm) in enumerate(zip(QP_NAMES, self._qp_dims())):
             if n in names:
                 ptr = buffer(n, ((k,) if (mask >> i) & 1 else (B, k)) + dm)
                 gq[i] = ptr.value if ptr is not None else None
@@ -1344,7 +1228,7 @@ class SmallNewtonBatch:
             res["adjoint"] = bufs["adjoint"][:, 0] if squeeze else bufs["adjoint"].permute(0, 2, 1)
         if theta:
             res["theta"] = bufs["theta"][:, 0] if squeeze else bufs["theta"].permute(0, 2, 1)
-        for i, (n, dm) in enumerate(zip(self._QP_NAMES, self._qp_dims())):
+        for i, (n, dm) in enumerate(zip(QP_NAMES, self._qp_dims())):
             if n in names:
                 g = bufs[n]
                 if (mask >> i) & 1:
@@ -1353,21 +1237,11 @@ class SmallNewtonBatch:
                     res[n] = g[:, 0] if squeeze else g.permute(0, *range(2, g.dim()), 1)
         return res
 
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._L.calipso_hip_smallnewton_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Comm:
+class Comm(_Handle):
     """RCCL communicator of the batched path (include/calipso_hip.h, "multi-GPU exchange"): one process per GPU; the only
     collectives are the post-round all-gather of per-problem status rows and the all-reduce of counters."""
+    _handle, _last_error, _destroy = "_c", "calipso_hip_comm_last_error", "calipso_hip_comm_destroy"
 
     @staticmethod
     def unique_id():
@@ -1390,9 +1264,7 @@ class Comm:
     def size(self):
         """(ranks, own rank) as the communicator itself reports them (ncclCommCount / ncclCommUserRank)"""
         out = np.zeros(2, dtype=np.int32)
-        rc = self._L.calipso_hip_comm_size(self._c, out.ctypes.data_as(C.POINTER(C.c_int32)))
-        if rc < 0:
-            raise CalipsoHipError("comm_size failed (%d): %s" % (rc, self._L.calipso_hip_comm_last_error(self._c).decode()))
+        self._check(self._L.calipso_hip_comm_size(self._c, out.ctypes.data_as(C.POINTER(C.c_int32))), "comm_size")
         return int(out[0]), int(out[1])
 
     def gather_status(self, rows, capacity):
@@ -1400,29 +1272,13 @@ class Comm:
         out = np.zeros((int(capacity), 4), dtype=np.int32)
         counts = np.zeros(self.nranks, dtype=np.int64)
         p32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
-        n = self._L.calipso_hip_comm_gather_status(self._c, p32(rows), rows.shape[0], p32(out), out.shape[0], _pi(counts))
-        if n < 0:
-            raise CalipsoHipError("comm_gather_status failed (%d): %s" % (n, self._L.calipso_hip_comm_last_error(self._c).decode()))
+        n = self._check(self._L.calipso_hip_comm_gather_status(self._c, p32(rows), rows.shape[0], p32(out), out.shape[0], _pi(counts)), "comm_gather_status")
         return out[:n], counts
 
     def allreduce_sum(self, values):
         v = np.ascontiguousarray(values, dtype=np.float64).copy()
-        rc = self._L.calipso_hip_comm_allreduce_sum(self._c, _pd(v), v.size)
-        if rc < 0:
-            raise CalipsoHipError("comm_allreduce_sum failed (%d): %s" % (rc, self._L.calipso_hip_comm_last_error(self._c).decode()))
+        self._check(self._L.calipso_hip_comm_allreduce_sum(self._c, _pd(v), v.size), "comm_allreduce_sum")
         return v
-
-    def close(self):
-        if getattr(self, "_c", None) is not None and self._c.value:
-            self._L.calipso_hip_comm_destroy(self._c)
-            self._c = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def mfma_f64_peak(device=0):
     """measured fp64 matrix-core ceiling of the device in TFLOP/s (calipso_hip_mfma_f64_peak)"""

@@ -38,6 +38,8 @@ import warnings
 
 import numpy as np
 
+from ._marshal import QP_NAMES, cotangent_from_parts, dual_rows, qp_shapes
+
 __all__ = ["QPLayer", "ParametricLayer", "SolverQPLayer", "GroupQPLayer"]
 
 _cls = {}
@@ -45,6 +47,76 @@ _cls = {}
 
 def _np(t):
     return t.detach().to("cpu", dtype=t.dtype).numpy().astype(np.float64, copy=False) if t is not None else None
+
+
+# ---- what the layers share; `h` is the handle or, for a group, its first member: whatever carries nx, ne, nc --------------------------------------------------------
+def _classify(torch, layer, h, data, count=None, host_only=False):
+    """the inputs' dtypes and shapes: per input True for the unbatched shape (shared by the items), False for a leading axis of `count`; count None: one item, no
+    leading axis admitted"""
+    shared = []
+    for name, t, dm in zip(QP_NAMES, data, qp_shapes(h.nx, h.ne, h.nc).values()):
+        if t.dtype != torch.float64:
+            raise TypeError("%s: %s must be float64" % (layer, name))
+        if host_only and t.is_cuda:
+            raise ValueError("%s: %s must be a host tensor (the handles take host arrays)" % (layer, name))
+        if tuple(t.shape) == dm:
+            shared.append(True)
+        elif count is not None and tuple(t.shape) == (count,) + dm:
+            shared.append(False)
+        else:
+            raise ValueError("%s: %s must be %s" % (layer, name, dm) + (" or %s" % ((count,) + dm,) if count is not None else ""))
+    return shared
+
+
+def _cotangent(h, lead, gx, gy, gz):
+    return cotangent_from_parts(_np(gx), _np(gy), _np(gz), lead, h.nx, h.ne, h.nc)
+
+
+def _outputs(torch, x, y, z, return_duals, device):
+    out = [torch.from_numpy(a.copy()).to(device) for a in ((x, y, z) if return_duals else (x,))]
+    return tuple(out) if return_duals else out[0]
+
+
+def _want(ctx):
+    """the names of the inputs that need a gradient"""
+    return "".join(name for name, need in zip(QP_NAMES, ctx.needs_input_grad[1:7]) if need)
+
+
+def _solved_again(handle, ctx, solve, modified=None):
+    """the handle solved other data since forward: the same data solve again (deterministic), and True.  modified: the layer kept the input tensors themselves, not
+    copies — the text of the error if one of them was written to since"""
+    if getattr(handle, "_qp_layer_key", None) is not ctx.key:
+        if modified and any(t._version != v for t, v in zip(ctx.inputs, ctx.versions)):
+            raise RuntimeError(modified)
+        solve()
+        return True
+    return False
+
+
+def _gradients(torch, out, want, shared, bad, warning, reduce, device):
+    """vjp()'s arrays -> the gradients of the six inputs: None where none is wanted, NaN for the items of the mask `bad` (a 0-d mask: the one item) with ONE warning,
+    then shared inputs summed over the items by `reduce`"""
+    bad = np.asarray(bad)
+    if bad.any():
+        warnings.warn(warning)
+    grads = []
+    for name, s in zip(QP_NAMES, shared):
+        if name not in want:
+            grads.append(None)
+            continue
+        g = out[name].copy()
+        g[bad] = np.nan
+        if s and reduce:
+            g = reduce(g)
+        grads.append(torch.from_numpy(np.ascontiguousarray(g)).to(device))
+    return grads
+
+
+def _sum_in_member_order(g):
+    acc = g[0].copy()
+    for i in range(1, g.shape[0]):
+        acc += g[i]
+    return acc
 
 
 def _build():
@@ -56,17 +128,7 @@ def _build():
         @staticmethod
         def forward(ctx, sn, P, q, A, b, G, h, return_duals=False, objective_scale=0.5):
             data = (P, q, A, b, G, h)
-            dims = ((sn.nx, sn.nx), (sn.nx,), (sn.ne, sn.nx), (sn.ne,), (sn.nc, sn.nx), (sn.nc,))
-            shared = []
-            for name, t, dm in zip("PqAbGh", data, dims):
-                if t.dtype != torch.float64:
-                    raise TypeError("QPLayer: %s must be float64" % name)
-                if tuple(t.shape) == dm:
-                    shared.append(True)
-                elif tuple(t.shape) == (sn.batch,) + dm:
-                    shared.append(False)
-                else:
-                    raise ValueError("QPLayer: %s must be %s or %s" % (name, dm, (sn.batch,) + dm))
+            shared = _classify(torch, "QPLayer", sn, data, sn.batch)
             if all(t.is_cuda and t.device.index == sn.device for t in data):      # the device path: nothing leaves the GPU, nothing waits for it
                 tensors = [t.detach().contiguous() for t in data]
                 key = object()
@@ -82,59 +144,27 @@ def _build():
                 arrays = [np.broadcast_to(a, (sn.batch,) + a.shape) if s else a for a, s in zip(arrays, shared)]
             key = object()
             _solve(sn, arrays, all_shared, objective_scale, key)
-            st = sn.get_state()
-            w = st["solution"]
-            nx, ne, nc = sn.nx, sn.ne, sn.nc
-            oy, oz = nx + ne + nc, nx + 2 * ne + nc
             ctx.sn, ctx.key, ctx.arrays, ctx.all_shared, ctx.c = sn, key, arrays, all_shared, objective_scale
             ctx.shared, ctx.status, ctx.device = shared, sn._qp_layer_status.copy(), P.device
-            ctx.return_duals = bool(return_duals)
-            dev = P.device
-            x = torch.from_numpy(w[:, :nx].copy()).to(dev)
-            if not return_duals:
-                return x
-            return x, torch.from_numpy(w[:, oy:oy + ne].copy()).to(dev), torch.from_numpy(w[:, oz:oz + nc].copy()).to(dev)
+            w = sn.get_state()["solution"]
+            oy, oz = dual_rows(sn.nx, sn.ne, sn.nc)
+            return _outputs(torch, w[:, :sn.nx], w[:, oy:oy + sn.ne], w[:, oz:oz + sn.nc], return_duals, P.device)
 
         @staticmethod
         def backward(ctx, gx, gy=None, gz=None):
             sn = ctx.sn
             if ctx.on_device:
-                if getattr(sn, "_qp_layer_key", None) is not ctx.key:      # the handle solved another batch since: the same data solve again (deterministic)
-                    if any(t._version != v for t, v in zip(ctx.inputs, ctx.versions)):      # (the host path keeps copies; this one keeps the tensors themselves)
-                        raise RuntimeError("QPLayer: an input was modified in place after forward and the handle has solved another batch since: backward cannot solve the same data again")
-                    _solve_device(torch, sn, ctx.tensors, ctx.c, ctx.key)
-                else:
+                if not _solved_again(sn, ctx, lambda: _solve_device(torch, sn, ctx.tensors, ctx.c, ctx.key), "QPLayer: an input was modified in place after forward and the "
+                                     "handle has solved another batch since: backward cannot solve the same data again"):
                     sn.set_stream(torch.cuda.current_stream(ctx.tensors[0].device))
                 part = lambda g, n: g.contiguous() if (g is not None and n) else None
-                want = "".join(name for name, need in zip("PqAbGh", ctx.needs_input_grad[1:7]) if need)
-                out = sn.vjp_device(x=part(gx, sn.nx), y=part(gy, sn.ne), z=part(gz, sn.nc), qp=want, reduce="".join(name for name, s in zip("PqAbGh", ctx.shared) if s))
-                return (None, *[out.get(name) for name in "PqAbGh"], None, None)
-            if getattr(sn, "_qp_layer_key", None) is not ctx.key:      # the handle solved another batch since: the same data solve again (deterministic)
-                _solve(sn, ctx.arrays, ctx.all_shared, ctx.c, ctx.key)
-            nx, ne, nc = sn.nx, sn.ne, sn.nc
-            oy, oz = nx + ne + nc, nx + 2 * ne + nc
-            v = np.zeros((sn.batch, sn.N))
-            if gx is not None:
-                v[:, :nx] = _np(gx)
-            if gy is not None and ne:
-                v[:, oy:oy + ne] = _np(gy)
-            if gz is not None and nc:
-                v[:, oz:oz + nc] = _np(gz)
-            out = sn.vjp(v, adjoint=False, qp=True)
+                out = sn.vjp_device(x=part(gx, sn.nx), y=part(gy, sn.ne), z=part(gz, sn.nc), qp=_want(ctx), reduce="".join(name for name, s in zip(QP_NAMES, ctx.shared) if s))
+                return (None, *[out.get(name) for name in QP_NAMES], None, None)
+            _solved_again(sn, ctx, lambda: _solve(sn, ctx.arrays, ctx.all_shared, ctx.c, ctx.key))
+            out = sn.vjp(_cotangent(sn, (sn.batch,), gx, gy, gz), adjoint=False, qp=True)
             bad = ctx.status != 1
-            if bad.any():
-                warnings.warn("QPLayer: %d of %d instances did not converge (solve status != 1): their gradients are NaN" % (int(bad.sum()), sn.batch))
-            grads = []
-            for name, s, need in zip("PqAbGh", ctx.shared, ctx.needs_input_grad[1:7]):
-                if not need:
-                    grads.append(None)
-                    continue
-                g = out[name].copy()
-                g[bad] = np.nan
-                if s:
-                    g = g.sum(axis=0)
-                grads.append(torch.from_numpy(g).to(ctx.device))
-            return (None, *grads, None, None)
+            warning = "QPLayer: %d of %d instances did not converge (solve status != 1): their gradients are NaN" % (int(bad.sum()), sn.batch)
+            return (None, *_gradients(torch, out, _want(ctx), ctx.shared, bad, warning, lambda g: g.sum(axis=0), ctx.device), None, None)
 
     class ParametricLayer(torch.autograd.Function):
         """apply(sn, theta, x0=None): the points w (batch, N) of solve! with the handle's device evaluator at the parameters theta (CUDA, float64; (batch,
@@ -155,11 +185,8 @@ def _build():
         @staticmethod
         def backward(ctx, gw):
             sn = ctx.sn
-            if getattr(sn, "_qp_layer_key", None) is not ctx.key:
-                if any(t._version != v for t, v in zip(ctx.inputs, ctx.versions)):
-                    raise RuntimeError("ParametricLayer: theta was modified in place after forward and the handle has solved another batch since: backward cannot solve the same data again")
-                _solve_parameters(torch, sn, ctx.theta, ctx.x0, ctx.key)
-            else:
+            if not _solved_again(sn, ctx, lambda: _solve_parameters(torch, sn, ctx.theta, ctx.x0, ctx.key), "ParametricLayer: theta was modified in place after forward and "
+                                 "the handle has solved another batch since: backward cannot solve the same data again"):
                 sn.set_stream(torch.cuda.current_stream(ctx.theta.device))
             g = sn.vjp_device(cotangent=gw.contiguous(), theta=True, qp=False)["theta"]
             return None, (g.sum(dim=0) if ctx.theta.dim() == 1 else g), None
@@ -170,51 +197,22 @@ def _build():
         @staticmethod
         def forward(ctx, solver, P, q, A, b, G, h, return_duals=False, objective_scale=0.5):
             data = (P, q, A, b, G, h)
-            dims = ((solver.nx, solver.nx), (solver.nx,), (solver.ne, solver.nx), (solver.ne,), (solver.nc, solver.nx), (solver.nc,))
-            for name, t, dm in zip("PqAbGh", data, dims):
-                if t.dtype != torch.float64:
-                    raise TypeError("SolverQPLayer: %s must be float64" % name)
-                if tuple(t.shape) != dm:
-                    raise ValueError("SolverQPLayer: %s must be %s" % (name, dm))
+            _classify(torch, "SolverQPLayer", solver, data)
             arrays = [_np(t) for t in data]
             key = object()
             _solve_handle(solver, arrays, objective_scale, key)
-            w = solver.solution
             ctx.solver, ctx.key, ctx.arrays, ctx.c, ctx.converged, ctx.device = solver, key, arrays, objective_scale, solver._qp_layer_converged, P.device
-            dev = P.device
-            x = torch.from_numpy(w.variables.copy()).to(dev)
-            if not return_duals:
-                return x
-            return x, torch.from_numpy(w.equality_dual.copy()).to(dev), torch.from_numpy(w.cone_dual.copy()).to(dev)
+            w = solver.solution
+            return _outputs(torch, w.variables, w.equality_dual, w.cone_dual, return_duals, P.device)
 
         @staticmethod
         def backward(ctx, gx, gy=None, gz=None):
-            solver = ctx.solver
-            if getattr(solver, "_qp_layer_key", None) is not ctx.key:      # the handle solved another QP since: the same data solve again (deterministic)
-                _solve_handle(solver, ctx.arrays, ctx.c, ctx.key)
-            nx, ne, nc = solver.nx, solver.ne, solver.nc
-            oy, oz = nx + ne + nc, nx + 2 * ne + nc
-            v = np.zeros(solver.N)
-            if gx is not None:
-                v[:nx] = _np(gx)
-            if gy is not None and ne:
-                v[oy:oy + ne] = _np(gy)
-            if gz is not None and nc:
-                v[oz:oz + nc] = _np(gz)
-            want = "".join(name for name, need in zip("PqAbGh", ctx.needs_input_grad[1:7]) if need)
+            solver, want = ctx.solver, _want(ctx)
+            _solved_again(solver, ctx, lambda: _solve_handle(solver, ctx.arrays, ctx.c, ctx.key))
+            v = _cotangent(solver, (), gx, gy, gz)
             out = solver.vjp(v, adjoint=False, theta=False, qp=want) if want else {}
-            if not ctx.converged:
-                warnings.warn("SolverQPLayer: the solve did not converge: the gradients are NaN")
-            grads = []
-            for name in "PqAbGh":
-                if name not in out:
-                    grads.append(None)
-                    continue
-                g = out[name]
-                if not ctx.converged:
-                    g = np.full_like(g, np.nan)
-                grads.append(torch.from_numpy(np.ascontiguousarray(g)).to(ctx.device))
-            return (None, *grads, None, None)
+            warning = "SolverQPLayer: the solve did not converge: the gradients are NaN"
+            return (None, *_gradients(torch, out, want, (False,) * 6, not ctx.converged, warning, None, ctx.device), None, None)
 
     class GroupQPLayer(torch.autograd.Function):
         """apply(group, P, q, A, b, G, h, return_duals=False, objective_scale=0.5): the solutions x (count, nx) of one QP per member of a Group, or (x, y, z) with
@@ -224,63 +222,24 @@ def _build():
         def forward(ctx, group, P, q, A, b, G, h, return_duals=False, objective_scale=0.5):
             s0, count = group.solvers[0], len(group.solvers)
             data = (P, q, A, b, G, h)
-            dims = ((s0.nx, s0.nx), (s0.nx,), (s0.ne, s0.nx), (s0.ne,), (s0.nc, s0.nx), (s0.nc,))
-            shared = []
-            for name, t, dm in zip("PqAbGh", data, dims):
-                if t.dtype != torch.float64:
-                    raise TypeError("GroupQPLayer: %s must be float64" % name)
-                if t.is_cuda:
-                    raise ValueError("GroupQPLayer: %s must be a host tensor (the handles take host arrays)" % name)
-                if tuple(t.shape) == dm:
-                    shared.append(True)
-                elif tuple(t.shape) == (count,) + dm:
-                    shared.append(False)
-                else:
-                    raise ValueError("GroupQPLayer: %s must be %s or %s" % (name, dm, (count,) + dm))
+            shared = _classify(torch, "GroupQPLayer", s0, data, count, host_only=True)
             arrays = [_np(t).copy() for t in data]
             key = object()
             _solve_group(group, arrays, shared, objective_scale, key)
             ctx.group, ctx.key, ctx.arrays, ctx.shared, ctx.c, ctx.converged = group, key, arrays, shared, objective_scale, group._qp_layer_converged.copy()
             W = [s.solution for s in group.solvers]
-            x = torch.from_numpy(np.stack([w.variables for w in W]))
-            if not return_duals:
-                return x
-            return x, torch.from_numpy(np.stack([w.equality_dual for w in W])), torch.from_numpy(np.stack([w.cone_dual for w in W]))
+            return _outputs(torch, *[np.stack([getattr(w, part) for w in W]) for part in ("variables", "equality_dual", "cone_dual")], return_duals, "cpu")
 
         @staticmethod
         def backward(ctx, gx, gy=None, gz=None):
-            group = ctx.group
-            if getattr(group, "_qp_layer_key", None) is not ctx.key:      # the group solved other data since: the same data solve again (deterministic)
-                _solve_group(group, ctx.arrays, ctx.shared, ctx.c, ctx.key)
-            s0, count = group.solvers[0], len(group.solvers)
-            nx, ne, nc = s0.nx, s0.ne, s0.nc
-            oy, oz = nx + ne + nc, nx + 2 * ne + nc
-            v = np.zeros((count, s0.N))
-            if gx is not None:
-                v[:, :nx] = _np(gx)
-            if gy is not None and ne:
-                v[:, oy:oy + ne] = _np(gy)
-            if gz is not None and nc:
-                v[:, oz:oz + nc] = _np(gz)
-            want = "".join(name for name, need in zip("PqAbGh", ctx.needs_input_grad[1:7]) if need)
+            group, want = ctx.group, _want(ctx)
+            _solved_again(group, ctx, lambda: _solve_group(group, ctx.arrays, ctx.shared, ctx.c, ctx.key))
+            count = len(group.solvers)
+            v = _cotangent(group.solvers[0], (count,), gx, gy, gz)
             out = group.vjp(v, adjoint=False, theta=False, qp=want) if want else {}
             bad = ~ctx.converged
-            if bad.any():
-                warnings.warn("GroupQPLayer: %d of %d members did not converge: their gradients are NaN" % (int(bad.sum()), count))
-            grads = []
-            for name, s in zip("PqAbGh", ctx.shared):
-                if name not in out:
-                    grads.append(None)
-                    continue
-                g = out[name].copy()
-                g[bad] = np.nan
-                if s:                                                     # summed over the members in member order
-                    acc = g[0].copy()
-                    for i in range(1, count):
-                        acc += g[i]
-                    g = acc
-                grads.append(torch.from_numpy(np.ascontiguousarray(g)))
-            return (None, *grads, None, None)
+            warning = "GroupQPLayer: %d of %d members did not converge: their gradients are NaN" % (int(bad.sum()), count)
+            return (None, *_gradients(torch, out, want, ctx.shared, bad, warning, _sum_in_member_order, "cpu"), None, None)
 
     return {"QPLayer": QPLayer, "ParametricLayer": ParametricLayer, "SolverQPLayer": SolverQPLayer, "GroupQPLayer": GroupQPLayer}
 

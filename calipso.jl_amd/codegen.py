@@ -529,3 +529,11 @@ class Problem:
         sn.set_cones(self.n_nonnegative, self.second_order_dims)
         sn.set_evaluator(built.cdll, built.symbol, self.np)
         return sn
+
+
+def __getattr__(name):
+    """codegen.TrajectoryProblem: the front end for per-stage functions and Solver handles lives in trajectory.py, which imports this module"""
+    if name == "TrajectoryProblem":
+        from .trajectory import TrajectoryProblem
+        return TrajectoryProblem
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

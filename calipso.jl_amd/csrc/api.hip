@@ -1082,7 +1082,10 @@ static int inner_iteration(H* s, calipso_eval_fn eval, void* user, double equali
     // very likely does too — :175-181 and IC-1 are queued BEFORE the host has seen the norms (they arrive with the inertia counts).  Should an exit test
     // hold after all, the factorisation was for nothing: its traces (regularisation, counters, work queued on the second stream) are undone.
     const bool spec = spec_step_ok(s);
-    const bool ahead = spec && s->spec_ahead_ok;
+    // Only the device-resident QP queues ahead: its Lxx and [gx; hx] do not depend on the point.  A user's device evaluator writes them for the NEW point, and an exit
+    // test that then holds cannot take that back: solve! would leave them one iterate ahead of where the reference and the host-callback route leave them (quirk
+    // B-12), and differentiate! works on them.
+    const bool ahead = spec && s->spec_ahead_ok && s->qp.attached;
     // ... and the prologue of such a step goes to the second stream (prologue_ahead_mode): the main stream goes straight on to the factorisation
     const int side = ahead ? prologue_ahead_mode(s) : 0;
     struct SideWork {                         // (the feed hook of ldl.hip lives as long as this step's factorisations)

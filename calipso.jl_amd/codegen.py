@@ -158,6 +158,95 @@ class Compiled:
         return self._cdll
 
 
+def compile_cached(stem, text, extra_flags, headers, key, directory=None, hipcc=None, arch="gfx950", symbol=None):
+    """The one build-and-cache path of both generators.  The file name is `stem` and a hash of the text, of the named files of include/ (name and contents, in
+    sorted order), of the flags, `key` and the arch; directory defaults to cache_directory().  Without `symbol`: (compiler flags, path of the .hip, path of the
+    library), nothing is written.  With it: the text is written and compiled unless the library exists (a library appears under its name only whole), and a
+    Compiled comes back; a failing compile raises RuntimeError with the compiler's stderr."""
+    flags = FLAGS + ["--offload-arch=%s" % arch] + list(extra_flags)
+    h = hashlib.sha256()
+    h.update(text.encode())
+    for name in sorted(headers):
+        with open(os.path.join(INCLUDE, name), "rb") as fh:
+            h.update(name.encode() + b"\0" + fh.read())
+    h.update(("\0".join(flags) + key + "\0" + arch).encode())
+    stem = "%s_%s" % (stem, h.hexdigest()[:16])
+    directory = os.path.abspath(directory or cache_directory())
+    src, lib = os.path.join(directory, stem + ".hip"), os.path.join(directory, "lib" + stem + ".so")
+    if symbol is None:
+        return flags, src, lib
+    if not os.path.exists(lib):
+        hipcc = hipcc or os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+        os.makedirs(directory, exist_ok=True)
+        with open(src, "w") as fh:
+            fh.write(text)
+        tmp = "%s.%d.tmp" % (lib, os.getpid())
+        run = subprocess.run([hipcc] + flags + ["-I" + INCLUDE, "-shared", src, "-o", tmp], capture_output=True, text=True)
+        if run.returncode != 0:
+            if os.path.exists(tmp):
+                os.remove(tmp)
+            raise RuntimeError("%s failed (%d) on %s:\n%s" % (hipcc, run.returncode, src, run.stderr))
+        os.replace(tmp, lib)
+    return Compiled(lib, symbol, src)
+
+
+def sweep(directory, prefixes, keep):
+    """remove the .hip and .so files of `directory` whose names start with one of `prefixes` and are not among the Compiled in `keep`: what an earlier state of a
+    generator or of the headers left behind"""
+    current = {os.path.basename(p) for c in keep for p in (c.path, c.source_path)}
+    for name in sorted(os.listdir(directory)):
+        if name.startswith(tuple(prefixes)) and name.endswith((".hip", ".so")) and name not in current:
+            os.remove(os.path.join(directory, name))
+
+
+def check_name(name):
+    if not re.fullmatch(r"[A-Za-z][A-Za-z0-9_]*", name):
+        raise ValueError("name must be a C identifier, got %r" % (name,))
+
+
+def as_scalar(sp, raw, what, entry=False):
+    """`raw` as one scalar sympy expression: what `what` returned, or (entry) one entry of the sequence it returned"""
+    try:
+        s = sp.sympify(raw)
+    except Exception:
+        s = None
+    if not isinstance(s, sp.Expr) or getattr(s, "is_Matrix", False):
+        raise ValueError(("%s must return a sequence of scalar expressions; one entry is a %s" if entry else "%s must return one scalar expression, got %s")
+                         % (what, type(raw).__name__))
+    return s
+
+
+def as_sequence(sp, v, what):
+    """what `what` returned as a list of scalar sympy expressions"""
+    if getattr(v, "is_Matrix", False) and min(v.shape) > 1:
+        raise ValueError("%s must return a sequence of scalar expressions, got a %d x %d matrix" % (what, v.shape[0], v.shape[1]))
+    try:
+        v = list(v)
+    except TypeError:
+        raise ValueError("%s must return a sequence of scalar expressions, got %s" % (what, type(v).__name__))
+    return [as_scalar(sp, e, what, entry=True) for e in v]
+
+
+def check_symbols(exprs, known, what):
+    """`what`: the sentence the error opens with, who may depend on what alone"""
+    for e in exprs:
+        extra = sorted(s.name for s in e.free_symbols if s not in known)
+        if extra:
+            raise ValueError("%s; found the symbols %s" % (what, ", ".join(extra)))
+
+
+def body(sp, exprs, names, indent, prefix):
+    """(lines declaring the common subexpressions, printed expressions, operation count) after sympy.cse, its symbols named `prefix`0, `prefix`1, ..."""
+    repl, reduced = sp.cse(list(exprs), symbols=sp.numbered_symbols(prefix), order="canonical")
+    names = dict(names)
+    for s, _ in repl:
+        names[s] = s.name
+    pr = _Printer(sp, names)
+    lines = ["%sconst double %s = %s;" % (indent, s.name, pr(e)) for s, e in repl]
+    ops = sum(int(sp.count_ops(e)) for _, e in repl) + sum(int(sp.count_ops(e)) for e in reduced)
+    return lines, [pr(e) for e in reduced], ops
+
+
 class Problem:
     """Problem(num_variables, objective, equality=None, cone=None, num_parameters=0, nonnegative_indices=None, second_order_indices=None, name="problem")
 
@@ -171,8 +260,7 @@ class Problem:
     def __init__(self, num_variables, objective, equality=None, cone=None, num_parameters=0, nonnegative_indices=None, second_order_indices=None, name="problem"):
         import sympy as sp
         self._sp = sp
-        if not re.fullmatch(r"[A-Za-z][A-Za-z0-9_]*", name):
-            raise ValueError("name must be a C identifier, got %r" % (name,))
+        check_name(name)
         self.name = name
         self.type_name = "".join(p[:1].upper() + p[1:] for p in name.split("_") if p) + "Evaluator"
         self.symbol = name + "_kernels"
@@ -185,21 +273,11 @@ class Problem:
         x = [sp.Symbol("x%04d" % i) for i in range(nx)]
         th = [sp.Symbol("p%04d" % i) for i in range(npar)]
         call = (lambda fn: fn(list(x), list(th))) if npar else (lambda fn: fn(list(x)))
-        raw = call(objective)
-        try:
-            f = sp.sympify(raw)
-        except Exception:
-            f = None
-        if not isinstance(f, sp.Expr) or getattr(f, "is_Matrix", False):
-            raise ValueError("the objective must return one scalar expression, got %s" % type(raw).__name__)
-        vec = lambda fn, what: [self._scalar(e, what) for e in self._sequence(call(fn), what)] if fn is not None else []
+        f = as_scalar(sp, call(objective), "the objective")
+        vec = lambda fn, what: as_sequence(sp, call(fn), what) if fn is not None else []
         g, h = vec(equality, "equality"), vec(cone, "cone")
         ne, nc = len(g), len(h)
-        known = set(x) | set(th)
-        for e in [f] + g + h:
-            extra = sorted((s.name for s in e.free_symbols if s not in known))
-            if extra:
-                raise ValueError("the functions may depend on x and theta alone; found the symbols %s" % ", ".join(extra))
+        check_symbols([f] + g + h, set(x) | set(th), "the functions may depend on x and theta alone")
         self.nx, self.ne, self.nc, self.np = nx, ne, nc, npar
         self.N = nx + 2 * ne + 3 * nc
         self.n_nonnegative, self.second_order_dims = self._cone_layout(nc, nonnegative_indices, second_order_indices)
@@ -220,27 +298,6 @@ class Problem:
         self._text = None
 
     # ---- the problem ------------------------------------------------------------------------------------------------------------------------------
-    @staticmethod
-    def _sequence(v, what):
-        if getattr(v, "is_Matrix", False):
-            if min(v.shape) > 1:
-                raise ValueError("%s must return a sequence of scalar expressions, got a %d x %d matrix" % (what, v.shape[0], v.shape[1]))
-            return list(v)
-        try:
-            return list(v)
-        except TypeError:
-            raise ValueError("%s must return a sequence of scalar expressions, got %s" % (what, type(v).__name__))
-
-    def _scalar(self, e, what):
-        sp = self._sp
-        try:
-            s = sp.sympify(e)
-        except Exception:
-            s = None
-        if not isinstance(s, sp.Expr) or getattr(s, "is_Matrix", False):
-            raise ValueError("%s must return a sequence of scalar expressions; one entry is a %s" % (what, type(e).__name__))
-        return s
-
     @staticmethod
     def _cone_layout(nc, nonnegative, second_order):
         nonneg = list(range(1, nc + 1)) if nonnegative is None else [int(i) for i in nonnegative]
@@ -357,18 +414,6 @@ class Problem:
             groups.setdefault(key, []).append(([self._where[s][1] for s in ws], [self._where[s][1] for s in ts], dest))
         return zeros, constants, [(k[0], k[1], k[2], members) for k, members in groups.items()]
 
-    def _body(self, exprs, names, indent, prefix="s"):
-        """(lines declaring the common subexpressions, printed expressions, operation count) after sympy.cse"""
-        sp = self._sp
-        repl, reduced = sp.cse(list(exprs), symbols=sp.numbered_symbols(prefix), order="canonical")
-        names = dict(names)
-        for s, _ in repl:
-            names[s] = s.name
-        pr = _Printer(sp, names)
-        lines = ["%sconst double %s = %s;" % (indent, s.name, pr(e)) for s, e in repl]
-        ops = sum(int(sp.count_ops(e)) for _, e in repl) + sum(int(sp.count_ops(e)) for e in reduced)
-        return lines, [pr(e) for e in reduced], ops
-
     # ---- printing --------------------------------------------------------------------------------------------------------------------------------
     def _generate(self):
         if self._text is not None:
@@ -411,7 +456,7 @@ class Problem:
                         ws, ts, dest = members[0]
                         names = {sp.Symbol("a%04d" % k): "w[%d]" % i for k, i in enumerate(ws)}
                         names.update({sp.Symbol("b%04d" % k): "th[%d]" % i for k, i in enumerate(ts)})
-                        decl, (text,), ops = self._body([canonical], names, "            ")
+                        decl, (text,), ops = body(sp, [canonical], names, "            ", "s")
                         lines.append("        if (wave == %d %% W) {" % singles)
                         lines += decl
                         lines.append("            if (lane == 0) acc += %s;" % text if accumulate else "            if (lane == 0) %s = %s;" % (array.at(*[str(i) for i in dest]), text))
@@ -424,7 +469,7 @@ class Problem:
                         tables.append("static __device__ const int %s[%d][%d] = {%s};" % (tab, len(members), nw + nt + nd, ", ".join("{" + ", ".join(str(i) for i in ws + ts + list(dest)) + "}" for ws, ts, dest in members)))
                         names = {sp.Symbol("a%04d" % k): "a%d" % k for k in range(nw)}
                         names.update({sp.Symbol("b%04d" % k): "b%d" % k for k in range(nt)})
-                        decl, (text,), ops = self._body([canonical], names, "            ")
+                        decl, (text,), ops = body(sp, [canonical], names, "            ", "s")
                         lines.append("        for (int e = c.tid; e < %d; e += C::threads) {" % len(members))
                         lines.append("            const int* t = %s[e];" % tab)
                         loads = ["a%d = w[t[%d]]" % (k, k) for k in range(nw)] + ["b%d = th[t[%d]]" % (k, nw + k) for k in range(nt)]
@@ -482,44 +527,23 @@ class Problem:
         return self._stats
 
     # ---- compiling ---------------------------------------------------------------------------------------------------------------------------------
-    def _plan_build(self, directory, arch, sn_jb):
-        """(compiler flags, path of the .hip, path of the library) of compile()"""
-        flags = FLAGS + ["--offload-arch=%s" % arch] + (["-DSN_JB=%d" % int(sn_jb)] if sn_jb is not None else [])
-        h = hashlib.sha256()
-        h.update(self.source().encode())
-        for name in sorted(os.listdir(INCLUDE)):
-            if re.search(r"\.h[^.]*$", name):
-                with open(os.path.join(INCLUDE, name), "rb") as fh:
-                    h.update(name.encode() + b"\0" + fh.read())
-        h.update(("\0".join(flags) + "\0SN_JB=%s\0%s" % (sn_jb, arch)).encode())
-        stem = "%s_%s" % (self.name, h.hexdigest()[:16])
-        directory = os.path.abspath(directory or cache_directory())
-        return flags, os.path.join(directory, stem + ".hip"), os.path.join(directory, "lib" + stem + ".so")
+    def _build(self, directory, arch, sn_jb, **build):
+        # (the five headers named: the hash — and with it the name of a library already built — does not move when include/ gains a file the evaluator never sees)
+        return compile_cached(self.name, self.source(), ["-DSN_JB=%d" % int(sn_jb)] if sn_jb is not None else [],
+                              ["calipso_hip.h", "calipso_options.hpp", "calipso_smallnewton.hpp", "calipso_smallnewton_device.hpp", "calipso_wave.hpp"],
+                              "\0SN_JB=%s" % sn_jb, directory=directory, arch=arch, **build)
 
     def library_path(self, directory=None, arch="gfx950", sn_jb=None):
         """where compile() with the same arguments puts (or finds) the shared library"""
-        return self._plan_build(directory, arch, sn_jb)[2]
+        return self._build(directory, arch, sn_jb)[2]
 
     def compile(self, directory=None, hipcc=None, arch="gfx950", sn_jb=None):
         """Write source() and build it into a shared library; returns a Compiled (.path, .cdll, .symbol).  The file name carries a hash of the generated text, the
-        contents of include/*.h*, SN_JB (sn_jb: the panel width the library was built with when not the header's default), the arch and the flags: a second call
-        with nothing changed loads the existing library and does not run hipcc.  directory defaults to cache_directory(), per user and outside the package.
-        Takes about a minute: the entry instantiates every build of the kernels (three-variable nonlinear_cone: 59.5 s cross-compiling).  A failing compile raises
-        RuntimeError with the compiler's stderr."""
-        flags, src, lib = self._plan_build(directory, arch, sn_jb)
-        if not os.path.exists(lib):
-            hipcc = hipcc or os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-            os.makedirs(os.path.dirname(lib), exist_ok=True)
-            with open(src, "w") as fh:
-                fh.write(self.source())
-            tmp = "%s.%d.tmp" % (lib, os.getpid())
-            run = subprocess.run([hipcc] + flags + ["-I" + INCLUDE, "-shared", src, "-o", tmp], capture_output=True, text=True)
-            if run.returncode != 0:
-                if os.path.exists(tmp):
-                    os.remove(tmp)
-                raise RuntimeError("%s failed (%d) on %s:\n%s" % (hipcc, run.returncode, src, run.stderr))
-            os.replace(tmp, lib)
-        return Compiled(lib, self.symbol, src)
+        contents of the headers of include/ it is built against, SN_JB (sn_jb: the panel width the library was built with when not the header's default), the arch
+        and the flags: a second call with nothing changed loads the existing library and does not run hipcc.  directory defaults to cache_directory(), per user and
+        outside the package.  Takes about a minute: the entry instantiates every build of the kernels (three-variable nonlinear_cone: 59.5 s cross-compiling).  A
+        failing compile raises RuntimeError with the compiler's stderr."""
+        return self._build(directory, arch, sn_jb, hipcc=hipcc, symbol=self.symbol)
 
     def batch(self, batch, device=0, options=None, **compile_args):
         """a SmallNewtonBatch of `batch` instances with this problem's cone layout and its compiled evaluator set: set_parameters, initialize, solve"""

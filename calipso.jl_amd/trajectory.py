@@ -10,7 +10,9 @@ Every stage function is applied to sympy symbols once per TEMPLATE: stages whose
 does with `unique`, solver.jl:129-176), so a horizon of 2048 stages with one dynamics function costs one derivation.  Per template: the value, the non-zeros of the
 Jacobian with respect to the local [x; u; y], of the Hessian of lambda'c (or of the cost) and of their theta_t-derivatives.
 
-How the generated library is shaped (template_source() = the per-template device functions, source() = the whole .hip):
+How the generated library is shaped (template_source() = the per-template device functions; source() = the whole .hip: these, the problem's shape, then
+include/calipso_trajectory.hpp — the kernels and the host code, the same for every problem — and CALIPSO_TRAJECTORY_EVALUATOR, which emits the entries; the blob's
+checks and every address are plain C++ in include/calipso_trajectory_tables.hpp):
   * one evaluation kernel: a lane per stage instance of a template, 64-thread workgroups, different templates in different workgroup ranges of the same launch (every
     branch on the template is workgroup-uniform).  Index and address tables are stage-minor ([entry][stage]): the lanes of a wavefront read consecutive words;
   * an output with ONE writer (the values, the objective gradient, the Jacobians' non-zeros) is stored where the ADDRESS TABLE says: entry -> offset in the destination,
@@ -23,15 +25,11 @@ How the generated library is shaped (template_source() = the per-template device
 One call enqueues at most four operations (the table upload of the first call, the fill, the evaluation kernel, the finishing pass); <name>_debug_last_enqueued counts.
 The text does not depend on the horizon: the tables come from Python through <name>_user_create.  evaluate() is the numpy twin through the same tables."""
 import ctypes
-import hashlib
 import inspect
-import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
 
+from . import Solver
 from . import codegen as _cg
 
 KINDS = ("cost", "dynamics", "equality", "nonnegative", "second_order")
@@ -82,8 +80,7 @@ class TrajectoryProblem:
             raise ValueError("equality_general is not supported by TrajectoryProblem: write the general equality as stage equalities, or use codegen.Problem")
         if unsupported:
             raise TypeError("TrajectoryProblem: unexpected keyword %s" % ", ".join(sorted(unsupported)))
-        if not re.fullmatch(r"[A-Za-z][A-Za-z0-9_]*", name):
-            raise ValueError("name must be a C identifier, got %r" % (name,))
+        _cg.check_name(name)
         if hessian not in ("reference", "exact"):
             raise ValueError('hessian must be "reference" or "exact", got %r' % (hessian,))
         self.name, self.hessian = name, hessian
@@ -207,29 +204,8 @@ class TrajectoryProblem:
             raise ValueError("%s[%d] takes %d arguments, expected %s" % (kind, t, arity, "(y, x, u[, theta])" if kind == "dynamics" else "(x, u[, theta])"))
         raw = fn(*(base + ([list(th)] if arity > len(base) else [])))
         what = "%s[%d]" % (kind, t)
-        if kind == "cost":
-            try:
-                f = sp.sympify(raw)
-            except Exception:
-                f = None
-            if not isinstance(f, sp.Expr) or getattr(f, "is_Matrix", False):
-                raise ValueError("%s must return one scalar expression, got %s" % (what, type(raw).__name__))
-            exprs = [f]
-        else:
-            exprs = []
-            for e in _cg.Problem._sequence(raw, what):
-                try:
-                    s = sp.sympify(e)
-                except Exception:
-                    s = None
-                if not isinstance(s, sp.Expr) or getattr(s, "is_Matrix", False):
-                    raise ValueError("%s must return a sequence of scalar expressions; one entry is a %s" % (what, type(e).__name__))
-                exprs.append(s)
-        known = set(x) | set(u) | set(y) | set(th)
-        for e in exprs:
-            extra = sorted(s.name for s in e.free_symbols if s not in known)
-            if extra:
-                raise ValueError("%s may depend on its arguments alone; found the symbols %s" % (what, ", ".join(extra)))
+        exprs = [_cg.as_scalar(sp, raw, what)] if kind == "cost" else _cg.as_sequence(sp, raw, what)
+        _cg.check_symbols(exprs, set(x) | set(u) | set(y) | set(th), "%s may depend on its arguments alone" % what)
         return exprs
 
     def _derive(self, tp):
@@ -510,7 +486,6 @@ class TrajectoryProblem:
 
     # ---- printing ----------------------------------------------------------------------------------------------------------------------------------
     def _function(self, k, tp):
-        sp = self._sp
         names = {s: "v%d" % i for i, s in enumerate(self._v[:tp.nv])}
         names.update({s: "l%d" % i for i, s in enumerate(tp.lam)})
         names.update({s: "p%d" % i for i, s in enumerate(self._p[:tp.nth])})
@@ -541,15 +516,10 @@ class TrajectoryProblem:
                 lines.append("    const double p%d = th[pi[%d * n + s]];" % (i, i))
         ops = 0
         for bit, items in sections:
-            repl, reduced = sp.cse([e for _, e in items], symbols=sp.numbered_symbols("c"), order="canonical")
-            nm = dict(names)
-            for s_, _ in repl:
-                nm[s_] = s_.name
-            pr = _cg._Printer(sp, nm)
+            declarations, texts, n = _cg.body(self._sp, [e for _, e in items], names, "        ", "c")
             lines.append("    if (flags & 0x%xu) {" % bit)
-            lines += ["        const double %s = %s;" % (s_.name, pr(e)) for s_, e in repl]
-            for (what, e), r in zip([t for t, _ in items], reduced):
-                text = pr(r)
+            lines += declarations
+            for (what, e), text in zip([t for t, _ in items], texts):
                 if what == "value":
                     lines.append("        base[%d][ri[%d * n + s]] = %s;" % (D_G if cls == 1 else D_H, e, text))
                 elif what == "fx":
@@ -559,7 +529,7 @@ class TrajectoryProblem:
                 else:
                     lines.append("        part[%d * n + s] = %s;" % (e, text))
             lines.append("    }")
-            ops += sum(int(sp.count_ops(e)) for _, e in repl) + sum(int(sp.count_ops(e)) for e in reduced)
+            ops += n
         lines.append("}")
         return lines, ops
 
@@ -589,14 +559,23 @@ class TrajectoryProblem:
         return self._text
 
     def source(self):
-        """the whole translation unit: the template functions, the kernels and the four entries"""
-        shape = "static const int T_KIND[NT] = {%s};\nstatic const int T_NV[NT] = {%s};\nstatic const int T_M[NT] = {%s};\nstatic const int T_NTH[NT] = {%s};\n" \
-                "static const int T_ND[NT] = {%s};\nstatic const int T_NQ[NT] = {%s};\n" % tuple(
-                    ", ".join(str(v) for v in vals) for vals in ([KINDS.index(tp.kind) for tp in self.templates], [tp.nv for tp in self.templates],
-                                                                 [tp.m for tp in self.templates], [tp.nth for tp in self.templates],
-                                                                 [tp.nd for tp in self.templates], [tp.nq for tp in self.templates]))
-        return (_RUNTIME.replace("@TEMPLATES@", self.template_source()).replace("@SHAPE@", shape).replace("@NT@", str(len(self.templates)))
-                .replace("@NAME@", self.name))
+        """the whole translation unit: the template functions, the problem type (the shape of every template and the dispatch), include/calipso_trajectory.hpp — the
+        kernels and the host code, the same for every problem — and the macro that emits the entries"""
+        name, arrays = self.name, (("KIND", [KINDS.index(tp.kind) for tp in self.templates]),) + tuple(
+            (key.upper(), [getattr(tp, key) for tp in self.templates]) for key in ("nv", "m", "nth", "nd", "nq"))
+        lines = ["// %s_device_eval, %s_block_eval, %s_user_create, %s_user_destroy, %s_debug_last_enqueued: device evaluators of a trajectory problem for "
+                 "libcalipso_hip.so — generated by calipso.jl_amd/trajectory.py; do not edit" % ((name,) * 5),
+                 "namespace {", "", self.template_source(),
+                 "struct %s_problem {" % name,
+                 "    static constexpr int NT = %d;" % len(self.templates)]
+        lines += ["    static constexpr int %s[NT] = {%s};" % (key, ", ".join(str(v) for v in vals)) for key, vals in arrays]
+        lines += ["    __device__ static void call(int k, unsigned flags, int s, int n, const double* x, const double* y, const double* z, const double* th, const int* vi,",
+                  "            const int* ri, const int* pi, const int* ad, double* const* base, double* part) {",
+                  "        %s_template(k, flags, s, n, x, y, z, th, vi, ri, pi, ad, base, part);" % name,
+                  "    }", "};", "", "}  // namespace", "",
+                  '#include "calipso_trajectory.hpp"', "",
+                  "CALIPSO_TRAJECTORY_EVALUATOR(%s_problem, %s)" % (name, name), ""]
+        return "\n".join(lines)
 
     def stats(self):
         """dict(stages, templates: per kind the number of templates, instances: per template (kind, stages), applications: how often a stage function was applied to
@@ -607,37 +586,18 @@ class TrajectoryProblem:
                     partials=int(self.n_partials), summed_outputs=int(self.G), sum_width=int(self.W))
 
     # ---- compiling and the handle -----------------------------------------------------------------------------------------------------------------
-    def _plan_build(self, directory, arch):
-        flags = _cg.FLAGS + ["--offload-arch=%s" % arch]
-        h = hashlib.sha256()
-        h.update(self.source().encode())
-        with open(os.path.join(_cg.INCLUDE, "calipso_hip.h"), "rb") as fh:
-            h.update(fh.read())
-        h.update(("\0".join(flags) + "\0" + arch).encode())
-        stem = "%s_%s" % (self.name, h.hexdigest()[:16])
-        directory = os.path.abspath(directory or _cg.cache_directory())
-        return flags, os.path.join(directory, stem + ".hip"), os.path.join(directory, "lib" + stem + ".so")
+    def _build(self, directory, arch, **build):
+        return _cg.compile_cached(self.name, self.source(), [], ["calipso_hip.h", "calipso_trajectory.hpp", "calipso_trajectory_tables.hpp"], "", directory=directory,
+                                  arch=arch, **build)
 
     def library_path(self, directory=None, arch="gfx950"):
-        return self._plan_build(directory, arch)[2]
+        return self._build(directory, arch)[2]
 
     def compile(self, directory=None, hipcc=None, arch="gfx950"):
         """Write source() and build it into a shared library; returns a codegen.Compiled (.path, .cdll; .symbol = <name>_device_eval).  Cached like Problem.compile: the
-        file name carries a hash of the text, of include/calipso_hip.h, the arch and the flags.  Plain kernels: a build takes seconds."""
-        flags, src, lib = self._plan_build(directory, arch)
-        if not os.path.exists(lib):
-            hipcc = hipcc or os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-            os.makedirs(os.path.dirname(lib), exist_ok=True)
-            with open(src, "w") as fh:
-                fh.write(self.source())
-            tmp = "%s.%d.tmp" % (lib, os.getpid())
-            run = subprocess.run([hipcc] + flags + ["-I" + _cg.INCLUDE, "-shared", src, "-o", tmp], capture_output=True, text=True)
-            if run.returncode != 0:
-                if os.path.exists(tmp):
-                    os.remove(tmp)
-                raise RuntimeError("%s failed (%d) on %s:\n%s" % (hipcc, run.returncode, src, run.stderr))
-            os.replace(tmp, lib)
-        return _cg.Compiled(lib, self.name + "_device_eval", src)
+        file name carries a hash of the text, of include/calipso_hip.h and the two calipso_trajectory headers, the arch and the flags.  Plain kernels: a build takes
+        seconds."""
+        return self._build(directory, arch, hipcc=hipcc, symbol=self.name + "_device_eval")
 
     def tables(self):
         """the int32 blob <name>_user_create takes: header, per template its shape, then its index tables and output coordinates, then the finishing pass's lists"""
@@ -655,7 +615,6 @@ class TrajectoryProblem:
         """an ordinary Solver whose evaluations run in the generated library: the block evaluator on a structured handle (structured=True, or None when structure()
         gives one), the dense-layout evaluator on a dense handle.  `methods` replaces the host twin as the handle's host callback (the device route never calls it).
         The Solver keeps the library and the evaluator's user object alive; close() frees them."""
-        from . import Solver
         st = self.structure() if structured in (None, True) else None
         if structured and st is None:
             raise ValueError("structured=True, but the Lagrangian Hessian of %s couples consecutive stages: structure() is None, the problem takes a dense handle" % self.name)
@@ -668,7 +627,7 @@ class TrajectoryProblem:
         if not user:
             raise RuntimeError("%s_user_create refused the tables" % self.name)
         try:
-            s = _TrajectorySolver(self if methods is None else methods, self.nx, self.np, self.ne, self.nc, parameters=parameters, nonnegative_indices=self.nonnegative_indices,
+            s = TrajectorySolver(self if methods is None else methods, self.nx, self.np, self.ne, self.nc, parameters=parameters, nonnegative_indices=self.nonnegative_indices,
                                   second_order_indices=self.second_order_indices, options=options, device=device, structure=st)
         except Exception:
             destroy(user)
@@ -685,418 +644,18 @@ class TrajectoryProblem:
         return int(fn(solver._user))
 
 
-def _make_solver_class():
-    from . import Solver
+class TrajectorySolver(Solver):
+    """a Solver that owns the generated library's user object"""
 
-    class TrajectorySolver(Solver):
-        """a Solver that owns the generated library's user object"""
-
-        def close(self):
-            h = getattr(self, "_h", None)
-            live = h is not None and h.value
-            if live:
-                try:
-                    self.synchronize()          # (the user object's buffers outlive the kernels that read them)
-                except Exception:
-                    pass
-            Solver.close(self)
-            user, self._user = getattr(self, "_user", None), None
-            if user:
-                self._user_destroy(user)
-
-    return TrajectorySolver
-
-
-class _Lazy:
-    """(the package imports codegen lazily; the Solver subclass is made on first use)"""
-    cls = None
-
-    def __call__(self, *a, **k):
-        if _Lazy.cls is None:
-            _Lazy.cls = _make_solver_class()
-        return _Lazy.cls(*a, **k)
-
-
-_TrajectorySolver = _Lazy()
-
-_RUNTIME = r'''// @NAME@: device evaluators of a trajectory problem for libcalipso_hip.so — generated by calipso.jl_amd/trajectory.py; do not edit
-//   @NAME@_device_eval   calipso_device_eval_fn        (dense layout)
-//   @NAME@_block_eval    calipso_device_block_eval_fn  (the packed blocks of a structured handle)
-// Both run the same kernels; they differ in the address table (entry -> offset in the destination), built once per handle on the first call.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
-#include <string.h>
-
-#include <vector>
-
-#include "calipso_hip.h"
-
-namespace {
-
-@TEMPLATES@
-constexpr int NT = @NT@;
-@SHAPE@
-enum { D_FX, D_G, D_H, D_GX, D_HX, D_GP, D_HP, D_F, D_GYX, D_HZX, D_LXX, D_LGP, N_DEST };
-constexpr uint32_t HESS = CALIPSO_EVAL_OBJECTIVE_HESSIAN | CALIPSO_EVAL_EQUALITY_DUAL_HESSIAN | CALIPSO_EVAL_CONE_DUAL_HESSIAN;
-constexpr uint32_t LPAR = CALIPSO_EVAL_OBJECTIVE_JACOBIAN_PARAMETERS | CALIPSO_EVAL_EQUALITY_DUAL_JACOBIAN_PARAMETERS | CALIPSO_EVAL_CONE_DUAL_JACOBIAN_PARAMETERS;
-constexpr int CHUNK = 1024;                    // elements one workgroup of the fill zeroes
-constexpr int N_FILL = 6;                      // equality Jacobian, cone Jacobian, Hessian, dg/dtheta, dh/dtheta, the Lagrangian's theta-gradient
-static const int FILL_DEST[N_FILL] = {D_GX, D_HX, D_LXX, D_GP, D_HP, D_LGP};
-static const uint32_t FILL_FLAGS[N_FILL] = {CALIPSO_EVAL_EQUALITY_JACOBIAN, CALIPSO_EVAL_CONE_JACOBIAN, HESS, CALIPSO_EVAL_EQUALITY_JACOBIAN_PARAMETERS,
-                                            CALIPSO_EVAL_CONE_JACOBIAN_PARAMETERS, LPAR};
-
-struct EvalArgs {                              // (by value: a few hundred bytes)
-    const double *x, *y, *z, *th;
-    double* part;
-    const int* tab;                            // the device tables
-    double* base[N_DEST];
-    uint32_t flags;
-    int n[NT], wg0[NT + 1], part0[NT], vi[NT], ri[NT], pi[NT], ad[NT];      // per template: instances, first workgroup, first partial, offsets of its tables in tab
-};
-struct FinishArgs {
-    const double* part;
-    const int* tab;
-    double* base[N_DEST];
-    uint32_t flags;
-    int G, W, n_obj, g_addr, g_field, g_slots, obj_slots;
-};
-struct FillArgs {
-    const int* tab;
-    double* base[N_FILL];
-    int first[N_FILL], wg0[N_FILL + 1];        // per selected category: its first chunk in the chunk table, its first workgroup
-    int count, c_off, c_len;
-};
-
-__global__ __launch_bounds__(64) void k_evaluate(EvalArgs a) {
-    const int b = blockIdx.x;
-    int k = 0;
-    while (k + 1 < NT && b >= a.wg0[k + 1]) ++k;            // workgroup-uniform
-    const int s = (b - a.wg0[k]) * 64 + threadIdx.x;
-    @NAME@_template(k, a.flags, s, a.n[k], a.x, a.y, a.z, a.th, a.tab + a.vi[k], a.tab + a.ri[k], a.tab + a.pi[k], a.tab + a.ad[k], a.base, a.part + a.part0[k]);
-}
-
-// the sums: a lane per summed output adds its partials in the order of the list; the last workgroup adds the stage costs (lane l the costs l, l + 64, ..., then a
-// fixed tree)
-__global__ __launch_bounds__(64) void k_finish(FinishArgs a) {
-    __shared__ double tree[64];
-    if (blockIdx.x == gridDim.x - 1) {
-        if (!(a.flags & CALIPSO_EVAL_OBJECTIVE)) return;
-        double acc = 0.0;
-        for (int i = threadIdx.x; i < a.n_obj; i += 64) acc += a.part[a.tab[a.obj_slots + i]];
-        tree[threadIdx.x] = acc;
-        __syncthreads();
-        for (int w = 32; w > 0; w >>= 1) {
-            if ((int)threadIdx.x < w) tree[threadIdx.x] += tree[threadIdx.x + w];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) a.base[D_F][0] = tree[0];
-        return;
-    }
-    const int g = blockIdx.x * 64 + threadIdx.x;
-    if (g >= a.G) return;
-    const int f = a.tab[a.g_field + g];
-    const uint32_t need = f == D_GYX ? CALIPSO_EVAL_EQUALITY_DUAL_GRADIENT : f == D_HZX ? CALIPSO_EVAL_CONE_DUAL_GRADIENT : f == D_LXX ? HESS : LPAR;
-    if (!(a.flags & need)) return;
-    double acc = 0.0;
-    for (int w = 0; w < a.W; ++w) {
-        const int word = a.tab[a.g_slots + w * a.G + g];
-        if (word < 0) break;
-        const int cls = word >> 29, slot = word & ((1 << 29) - 1);
-        uint32_t bit = need;
-        if (f == D_LXX) bit = cls == 0 ? CALIPSO_EVAL_OBJECTIVE_HESSIAN : cls == 1 ? CALIPSO_EVAL_EQUALITY_DUAL_HESSIAN : CALIPSO_EVAL_CONE_DUAL_HESSIAN;
-        if (f == D_LGP) bit = cls == 0 ? CALIPSO_EVAL_OBJECTIVE_JACOBIAN_PARAMETERS : cls == 1 ? CALIPSO_EVAL_EQUALITY_DUAL_JACOBIAN_PARAMETERS : CALIPSO_EVAL_CONE_DUAL_JACOBIAN_PARAMETERS;
-        if (a.flags & bit) acc += a.part[slot];
-    }
-    a.base[f][a.tab[a.g_addr + g]] = acc;
-}
-
-__global__ __launch_bounds__(256) void k_fill(FillArgs a) {
-    const int b = blockIdx.x;
-    int c = 0;
-    while (c + 1 < a.count && b >= a.wg0[c + 1]) ++c;
-    const int chunk = a.first[c] + (b - a.wg0[c]);
-    const int off = a.tab[a.c_off + chunk], len = a.tab[a.c_len + chunk];
-    double* dst = a.base[c] + off;
-    for (int i = threadIdx.x; i < len; i += 256) dst[i] = 0.0;
-}
-
-struct Route {                                 // one layout of the destinations: the tables on the device and where they came from
-    bool ready = false;
-    int* pinned = nullptr; int* device = nullptr; size_t words = 0;
-    int vi[NT], ri[NT], pi[NT], ad[NT];
-    int g_addr = 0, g_field = 0, g_slots = 0, obj_slots = 0, c_off = 0, c_len = 0;
-    int fill_first[N_FILL] = {0}, fill_count[N_FILL] = {0};
-    const void* key0 = nullptr; int64_t key1 = 0;      // the layout it was built for: (descriptor array, first block's values) or (nullptr, jacobian_ld)
-    double* block_base = nullptr;
-};
-
-struct User {
-    int G = 0, W = 0, n_obj = 0, nx = 0, ne = 0, nc = 0, np = 0;
-    int64_t n_part = 0;
-    int n[NT];
-    std::vector<int32_t> vi[NT], ri[NT], pi[NT], d_field[NT], d_i[NT], d_j[NT];
-    std::vector<int32_t> g_field, g_i, g_j, g_slots, obj_slots;
-    double* part = nullptr;
-    Route dense, block;
-    int last_enqueued = 0;
-};
-
-struct Segment { int cat; int64_t off, len; };
-
-// where (dest, i, j) lives: an offset from the destination's base, or -1
-struct DenseLayout {
-    int64_t ld, nx, ne, nc;
-    int64_t operator()(int dest, int64_t i, int64_t j) const {
-        switch (dest) {
-        case D_GX: case D_HX: return i + j * ld;
-        case D_LXX: return i + j * nx;
-        case D_GP: return i + j * ne;
-        case D_HP: return i + j * nc;
-        case D_LGP: return i + j * nx;
-        default: return -1;
-        }
-    }
-};
-struct BlockLayout {
-    const calipso_device_block_data* o; double* base;
-    std::vector<int> jrow, hcol;              // the block of every row of [equality; cone] and of every column of the Hessian (-1: none)
-    explicit BlockLayout(const calipso_device_block_data* out) : o(out), base(nullptr) {
-        jrow.assign((size_t)(o->ne + o->nc), -1); hcol.assign((size_t)o->nx, -1);
-        for (int64_t b = 0; b < o->n_jacobian_blocks; ++b) {
-            const calipso_device_block& k = o->jacobian_blocks[b];
-            if (!base || k.values < base) base = k.values;
-            for (int64_t r = k.row0; r < k.row0 + k.nrows; ++r) if (r >= 0 && r < o->ne + o->nc) jrow[(size_t)r] = (int)b;
-        }
-        for (int64_t b = 0; b < o->n_hessian_blocks; ++b) {
-            const calipso_device_block& k = o->hessian_blocks[b];
-            if (!base || k.values < base) base = k.values;
-            for (int64_t c = k.col0; c < k.col0 + k.ncols; ++c) if (c >= 0 && c < o->nx) hcol[(size_t)c] = (int)b;
-        }
-    }
-    int64_t in(const calipso_device_block& k, int64_t r, int64_t c) const {
-        if (r < k.row0 || r >= k.row0 + k.nrows || c < k.col0 || c >= k.col0 + k.ncols) return -1;
-        return (k.values - base) + (r - k.row0) + (c - k.col0) * k.ld;
-    }
-    int64_t operator()(int dest, int64_t i, int64_t j) const {
-        switch (dest) {
-        case D_GX: case D_HX: { const int64_t r = dest == D_GX ? i : i + o->ne; const int b = jrow[(size_t)r]; return b < 0 ? -1 : in(o->jacobian_blocks[b], r, j); }
-        case D_LXX: { const int b = hcol[(size_t)j]; return b < 0 ? -1 : in(o->hessian_blocks[b], i, j); }
-        case D_GP: return i + j * o->ne;
-        case D_HP: return i + j * o->nc;
-        case D_LGP: return i + j * o->nx;
-        default: return -1;
-        }
-    }
-};
-
-void add_segment(std::vector<Segment>& segs, int cat, int64_t off, int64_t len) {
-    if (len <= 0) return;
-    if (!segs.empty() && segs.back().cat == cat && segs.back().off + segs.back().len == off) { segs.back().len += len; return; }
-    segs.push_back({cat, off, len});
-}
-
-// the tables of a route: the index tables as they are, the address table and the finishing pass's addresses through `where`, the fill's chunks from `segs`
-// (sorted by category); one pinned block, one device block, one copy
-template <class Where>
-int build_route(User* u, Route& r, const Where& where, const std::vector<Segment>& segs, hipStream_t stream) {
-    std::vector<int32_t> t;
-    auto put = [&](const std::vector<int32_t>& v) { const int at = (int)t.size(); t.insert(t.end(), v.begin(), v.end()); return at; };
-    for (int k = 0; k < NT; ++k) {
-        r.vi[k] = put(u->vi[k]); r.ri[k] = put(u->ri[k]); r.pi[k] = put(u->pi[k]);
-        std::vector<int32_t> ad((size_t)T_ND[k] * u->n[k]);
-        for (int e = 0; e < T_ND[k]; ++e)
-            for (int s = 0; s < u->n[k]; ++s) {
-                const size_t at = (size_t)e * u->n[k] + s;
-                const int64_t off = where(u->d_field[k][e], u->d_i[k][at], u->d_j[k][at]);
-                if (off < 0 || off > INT32_MAX) return 4;            // a non-zero outside the declared structure, or a destination beyond 2^31 entries
-                ad[at] = (int32_t)off;
-            }
-        r.ad[k] = put(ad);
-    }
-    std::vector<int32_t> ga((size_t)u->G);
-    for (int g = 0; g < u->G; ++g) {
-        const int f = u->g_field[g];
-        const int64_t off = (f == D_GYX || f == D_HZX) ? u->g_i[g] : where(f, u->g_i[g], u->g_j[g]);
-        if (off < 0 || off > INT32_MAX) return 4;
-        ga[g] = (int32_t)off;
-    }
-    r.g_addr = put(ga); r.g_field = put(u->g_field); r.g_slots = put(u->g_slots); r.obj_slots = put(u->obj_slots);
-    std::vector<int32_t> c_off, c_len;
-    int cat = -1;
-    for (const Segment& sg : segs) {
-        if (sg.cat < cat) return 5;
-        while (cat < sg.cat) { ++cat; r.fill_first[cat] = (int)c_off.size(); r.fill_count[cat] = 0; }
-        for (int64_t at = 0; at < sg.len; at += CHUNK) {
-            if (sg.off + at > INT32_MAX) return 4;
-            c_off.push_back((int32_t)(sg.off + at)); c_len.push_back((int32_t)(sg.len - at < CHUNK ? sg.len - at : CHUNK));
-            ++r.fill_count[cat];
-        }
-    }
-    while (cat < N_FILL - 1) { ++cat; r.fill_first[cat] = (int)c_off.size(); r.fill_count[cat] = 0; }
-    r.c_off = put(c_off); r.c_len = put(c_len);
-    r.words = t.size() ? t.size() : 1;
-    if (hipHostMalloc((void**)&r.pinned, r.words * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) return 2;
-    if (hipMalloc((void**)&r.device, r.words * sizeof(int32_t)) != hipSuccess) return 2;
-    if (!t.empty()) memcpy(r.pinned, t.data(), t.size() * sizeof(int32_t));
-    if (hipMemcpyAsync(r.device, r.pinned, r.words * sizeof(int32_t), hipMemcpyHostToDevice, stream) != hipSuccess) return 2;
-    ++u->last_enqueued;
-    r.ready = true;
-    return 0;
-}
-
-// fill, evaluate, finish on the stream: at most three launches
-int run(User* u, const Route& r, uint32_t flags, const double* x, const double* y, const double* z, const double* th, double* const* base, hipStream_t stream) {
-    FillArgs fa;
-    fa.tab = r.device; fa.count = 0; fa.c_off = r.c_off; fa.c_len = r.c_len; fa.wg0[0] = 0;
-    for (int c = 0; c < N_FILL; ++c)
-        if ((flags & FILL_FLAGS[c]) && r.fill_count[c] > 0 && base[FILL_DEST[c]]) {
-            fa.base[fa.count] = base[FILL_DEST[c]]; fa.first[fa.count] = r.fill_first[c]; fa.wg0[fa.count + 1] = fa.wg0[fa.count] + r.fill_count[c]; ++fa.count;
-        }
-    if (fa.count > 0) { hipLaunchKernelGGL(k_fill, dim3(fa.wg0[fa.count]), dim3(256), 0, stream, fa); ++u->last_enqueued; }
-    EvalArgs ea;
-    ea.x = x; ea.y = y; ea.z = z; ea.th = th; ea.part = u->part; ea.tab = r.device; ea.flags = flags;
-    for (int d = 0; d < N_DEST; ++d) ea.base[d] = base[d];
-    int wg = 0; int64_t p0 = 0;
-    for (int k = 0; k < NT; ++k) {
-        ea.n[k] = u->n[k]; ea.wg0[k] = wg; ea.part0[k] = (int)p0; ea.vi[k] = r.vi[k]; ea.ri[k] = r.ri[k]; ea.pi[k] = r.pi[k]; ea.ad[k] = r.ad[k];
-        wg += (u->n[k] + 63) / 64; p0 += (int64_t)T_NQ[k] * u->n[k];
-    }
-    ea.wg0[NT] = wg;
-    if (wg > 0) { hipLaunchKernelGGL(k_evaluate, dim3(wg), dim3(64), 0, stream, ea); ++u->last_enqueued; }
-    if (flags & (CALIPSO_EVAL_OBJECTIVE | CALIPSO_EVAL_EQUALITY_DUAL_GRADIENT | CALIPSO_EVAL_CONE_DUAL_GRADIENT | HESS | LPAR)) {
-        FinishArgs fi;
-        fi.part = u->part; fi.tab = r.device; fi.flags = flags; fi.G = u->G; fi.W = u->W; fi.n_obj = u->n_obj;
-        for (int d = 0; d < N_DEST; ++d) fi.base[d] = base[d];
-        fi.g_addr = r.g_addr; fi.g_field = r.g_field; fi.g_slots = r.g_slots; fi.obj_slots = r.obj_slots;
-        hipLaunchKernelGGL(k_finish, dim3((u->G + 63) / 64 + 1), dim3(64), 0, stream, fi);
-        ++u->last_enqueued;
-    }
-    return hipGetLastError() == hipSuccess ? 0 : 2;
-}
-
-void free_route(Route& r) {
-    if (r.device) (void)hipFree(r.device);
-    if (r.pinned) (void)hipHostFree(r.pinned);
-    r = Route();
-}
-
-}  // namespace
-
-extern "C" {
-
-// tables: the int32 blob of TrajectoryProblem.tables(); returns NULL when it does not fit this library or an index lies outside its range
-void* @NAME@_user_create(const int32_t* blob, int64_t words) {
-    if (!blob || words < 10 + 8 * (int64_t)NT || blob[0] != 0x43545250 || blob[1] != NT) return nullptr;
-    User* u = new User();
-    u->G = blob[2]; u->W = blob[3]; u->n_obj = blob[4]; u->n_part = blob[5]; u->nx = blob[6]; u->ne = blob[7]; u->nc = blob[8]; u->np = blob[9];
-    int64_t at = 10, slots = 0;
-    bool ok = u->G >= 0 && u->W >= 1 && u->n_obj >= 0 && u->n_part >= 0;
-    for (int k = 0; k < NT && ok; ++k, at += 8) {
-        const int32_t* h = blob + at;
-        u->n[k] = h[1];
-        ok = h[0] == T_KIND[k] && h[1] >= 0 && h[2] == T_NV[k] && h[3] == T_M[k] && h[4] == T_NTH[k] && h[5] == T_ND[k] && h[6] == T_NQ[k];
-        slots += (int64_t)T_NQ[k] * h[1];
-    }
-    ok = ok && slots == u->n_part && slots < (1 << 29);
-    auto take = [&](std::vector<int32_t>& v, int64_t count, int64_t lo, int64_t hi) {       // every entry in [lo, hi)
-        if (!ok || count < 0 || at + count > words) { ok = false; return; }
-        v.assign(blob + at, blob + at + count); at += count;
-        for (int32_t e : v) if (e < lo || e >= hi) { ok = false; return; }
-    };
-    for (int k = 0; k < NT && ok; ++k) {
-        const int64_t n = u->n[k], rows = (T_KIND[k] == 1 || T_KIND[k] == 2) ? u->ne : u->nc;
-        take(u->vi[k], T_NV[k] * n, 0, u->nx); take(u->ri[k], T_M[k] * n, 0, rows); take(u->pi[k], T_NTH[k] * n, 0, u->np);
-        take(u->d_field[k], T_ND[k], D_GX, D_HP + 1); take(u->d_i[k], T_ND[k] * n, 0, rows);
-        take(u->d_j[k], T_ND[k] * n, 0, u->nx > u->np ? u->nx : u->np);
-        for (int e = 0; e < T_ND[k] && ok; ++e) {
-            const int f = u->d_field[k][e];
-            const int64_t cols = (f == D_GX || f == D_HX) ? u->nx : u->np;
-            for (int64_t s = 0; s < n; ++s) if (u->d_j[k][(size_t)(e * n + s)] >= cols) ok = false;
-        }
-    }
-    take(u->g_field, u->G, D_GYX, D_LGP + 1); take(u->g_i, u->G, 0, u->nx); take(u->g_j, u->G, 0, u->nx > u->np ? u->nx : u->np);
-    if (ok && at + (int64_t)u->W * u->G <= words) {
-        u->g_slots.assign(blob + at, blob + at + (int64_t)u->W * u->G); at += (int64_t)u->W * u->G;
-        for (int32_t w : u->g_slots) if (w != -1 && (w < 0 || (w & ((1 << 29) - 1)) >= slots || (w >> 29) > 2)) ok = false;
-    } else ok = false;
-    take(u->obj_slots, u->n_obj, 0, slots);
-    for (int g = 0; g < u->G && ok; ++g) if (u->g_j[g] >= (u->g_field[g] == D_LGP ? u->np : u->nx)) ok = false;
-    if (ok && at != words) ok = false;
-    if (ok && hipMalloc((void**)&u->part, sizeof(double) * (size_t)(slots ? slots : 1)) != hipSuccess) ok = false;
-    if (!ok) { delete u; return nullptr; }
-    return u;
-}
-
-void @NAME@_user_destroy(void* p) {
-    User* u = (User*)p;
-    if (!u) return;
-    free_route(u->dense); free_route(u->block);
-    if (u->part) (void)hipFree(u->part);
-    delete u;
-}
-
-int32_t @NAME@_debug_last_enqueued(void* p) { return p ? ((User*)p)->last_enqueued : -1; }
-
-int32_t @NAME@_device_eval(void* user, uint32_t flags, const double* x, const double* y, const double* z, const double* theta,
-                           const calipso_device_problem_data* out, void* hip_stream) {
-    User* u = (User*)user;
-    if (!u || !out || out->nx != u->nx || out->ne != u->ne || out->nc != u->nc || out->np != u->np) return 1;
-    hipStream_t stream = (hipStream_t)hip_stream;
-    u->last_enqueued = 0;
-    Route& r = u->dense;
-    if (r.ready && (r.key1 != out->jacobian_ld)) return 3;               // the layout changed under the handle
-    if (!r.ready) {
-        const DenseLayout where{out->jacobian_ld, u->nx, u->ne, u->nc};
-        if (out->jacobian_ld < u->ne + u->nc) return 1;
-        std::vector<Segment> segs;
-        for (int64_t j = 0; j < u->nx; ++j) add_segment(segs, 0, j * out->jacobian_ld, u->ne);
-        for (int64_t j = 0; j < u->nx; ++j) add_segment(segs, 1, j * out->jacobian_ld, u->nc);
-        add_segment(segs, 2, 0, (int64_t)u->nx * u->nx);
-        add_segment(segs, 3, 0, (int64_t)u->ne * u->np); add_segment(segs, 4, 0, (int64_t)u->nc * u->np); add_segment(segs, 5, 0, (int64_t)u->nx * u->np);
-        r.key1 = out->jacobian_ld;
-        if (int rc = build_route(u, r, where, segs, stream)) { free_route(r); return rc; }
-    }
-    double* base[N_DEST] = {out->objective_gradient_variables, out->equality_constraint, out->cone_constraint, out->equality_jacobian_variables,
-                            out->cone_jacobian_variables, out->equality_jacobian_parameters, out->cone_jacobian_parameters, out->objective,
-                            out->equality_dual_jacobian_variables, out->cone_dual_jacobian_variables, out->lagrangian_hessian, out->lagrangian_gradient_parameters};
-    return run(u, r, flags, x, y, z, theta, base, stream);
-}
-
-int32_t @NAME@_block_eval(void* user, uint32_t flags, const double* x, const double* y, const double* z, const double* theta,
-                          const calipso_device_block_data* out, void* hip_stream) {
-    User* u = (User*)user;
-    if (!u || !out || out->nx != u->nx || out->ne != u->ne || out->nc != u->nc || out->np != u->np) return 1;
-    if (out->n_jacobian_blocks + out->n_hessian_blocks < 1 || (out->n_jacobian_blocks && !out->jacobian_blocks) || (out->n_hessian_blocks && !out->hessian_blocks)) return 1;
-    hipStream_t stream = (hipStream_t)hip_stream;
-    u->last_enqueued = 0;
-    Route& r = u->block;
-    const void* key0 = out->n_hessian_blocks ? (const void*)out->hessian_blocks : (const void*)out->jacobian_blocks;
-    const int64_t key1 = (int64_t)(intptr_t)(out->n_hessian_blocks ? out->hessian_blocks[0].values : out->jacobian_blocks[0].values);
-    if (r.ready && (r.key0 != key0 || r.key1 != key1)) return 3;
-    if (!r.ready) {
-        const BlockLayout where(out);
-        std::vector<Segment> segs;
-        for (int cat = 0; cat < 2; ++cat)                     // the equality rows of every Jacobian block, then the cone rows: column by column, merged where contiguous
-            for (int64_t b = 0; b < out->n_jacobian_blocks; ++b) {
-                const calipso_device_block& k = out->jacobian_blocks[b];
-                const int64_t lo = cat == 0 ? k.row0 : (k.row0 > out->ne ? k.row0 : out->ne);
-                const int64_t hi = cat == 0 ? (k.row0 + k.nrows < out->ne ? k.row0 + k.nrows : out->ne) : k.row0 + k.nrows;
-                for (int64_t j = 0; j < k.ncols; ++j) add_segment(segs, cat, (k.values - where.base) + (lo - k.row0) + j * k.ld, hi - lo);
-            }
-        for (int64_t b = 0; b < out->n_hessian_blocks; ++b) {
-            const calipso_device_block& k = out->hessian_blocks[b];
-            for (int64_t j = 0; j < k.ncols; ++j) add_segment(segs, 2, (k.values - where.base) + j * k.ld, k.nrows);
-        }
-        add_segment(segs, 3, 0, (int64_t)u->ne * u->np); add_segment(segs, 4, 0, (int64_t)u->nc * u->np); add_segment(segs, 5, 0, (int64_t)u->nx * u->np);
-        r.key0 = key0; r.key1 = key1; r.block_base = where.base;
-        if (int rc = build_route(u, r, where, segs, stream)) { free_route(r); return rc; }
-    }
-    double* base[N_DEST] = {out->objective_gradient_variables, out->equality_constraint, out->cone_constraint, r.block_base, r.block_base,
-                            out->equality_jacobian_parameters, out->cone_jacobian_parameters, out->objective, out->equality_dual_jacobian_variables,
-                            out->cone_dual_jacobian_variables, r.block_base, out->lagrangian_gradient_parameters};
-    return run(u, r, flags, x, y, z, theta, base, stream);
-}
-
-}  // extern "C"
-'''
+    def close(self):
+        h = getattr(self, "_h", None)
+        live = h is not None and h.value
+        if live:
+            try:
+                self.synchronize()          # (the user object's buffers outlive the kernels that read them)
+            except Exception:
+                pass
+        Solver.close(self)
+        user, self._user = getattr(self, "_user", None), None
+        if user:
+            self._user_destroy(user)

@@ -1,7 +1,8 @@
 """codegen.TrajectoryProblem (calipso.jl_amd/trajectory.py) without a GPU: its bookkeeping and its numpy twin against flat problems built from the same stage functions
 and against the committed pendulum and cart-pole problems, both Hessian modes; one derivation per template whatever the horizon; the generated per-template device
 functions compiled by the host C++ compiler against a mock (tests/trajectory_host/main.cpp, under the address and undefined-behaviour sanitizers, run as a child
-process); its refusals; the oracle solving through TrajectoryProblem.evaluate."""
+process); the host tables of the generated libraries (include/calipso_trajectory_tables.hpp through tests/trajectory_host/tables_main.cpp, the same way): the address
+tables of the dense and of the block layout and the fill chunks against numpy, the checks of the blob; its refusals; the oracle solving through TrajectoryProblem.evaluate."""
 import functools
 import importlib.util
 import inspect
@@ -18,6 +19,7 @@ import problems as pr
 from helpers import ROOT
 
 HOST = os.path.join(ROOT, "tests", "trajectory_host", "main.cpp")
+TABLES_HOST = os.path.join(ROOT, "tests", "trajectory_host", "tables_main.cpp")
 PROBLEMS = os.path.join(ROOT, "tests", "device_eval_trajectory", "problems.py")
 ALL_FLAGS = (1 << 16) - 1
 
@@ -232,6 +234,159 @@ def test_generated_device_functions_on_the_host(tmp_path):
         assert got[("part", k)].shape == (t.nq * t.n,) and close(got[("part", k)], part.reshape(-1)), (k, t.kind)
     want = fields(TP, x, y, z, theta)
     assert close(got[("fx", 0)], want["objective_gradient_variables"]) and close(got[("g", 0)], want["equality_constraint"]) and close(got[("h", 0)], want["cone_constraint"])
+
+
+@pytest.fixture(scope="module")
+def tables_host(tmp_path_factory):
+    """tests/trajectory_host/tables_main.cpp against include/calipso_trajectory_tables.hpp, built once like the program above: the host compiler, both sanitizers"""
+    cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
+    assert cxx, "no host C++ compiler"
+    exe = str(tmp_path_factory.mktemp("tables_host") / "tables")
+    is_clang = "clang" in subprocess.run([cxx, "--version"], capture_output=True, text=True).stdout
+    static_runtimes = [] if is_clang else ["-static-libasan", "-static-libubsan"]
+    build = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-Wall", "-Wextra"] + static_runtimes +
+                           ["-I" + os.path.join(ROOT, "include"), TABLES_HOST, "-o", exe], capture_output=True, text=True)
+    assert build.returncode == 0, build.stdout + build.stderr
+    return exe
+
+
+def route(exe, tmp_path, TP, layout, blob=None):
+    """(return code, {(table, template or category): words}) of the route the program assembles from TP's shape, `blob` (default TP.tables()) and the layout lines;
+    (None, {}) when it refuses the blob"""
+    kinds = sys.modules[type(TP).__module__].KINDS
+    blob = TP.tables() if blob is None else blob
+    shape = [[kinds.index(t.kind) for t in TP.templates]] + [[getattr(t, a) for t in TP.templates] for a in ("nv", "m", "nth", "nd", "nq")]
+    lines = [str(len(TP.templates))] + [" ".join(str(v) for v in vals) for vals in shape] + [str(blob.size), " ".join(str(int(v)) for v in blob)] + list(layout)
+    (tmp_path / "tables.txt").write_text("\n".join(lines) + "\n")
+    run = subprocess.run([exe, str(tmp_path / "tables.txt")], capture_output=True, text=True, timeout=60)
+    assert run.returncode == 0 and run.stdout.endswith("done\n"), run.stdout[-2000:] + run.stderr[-4000:]
+    out = run.stdout.splitlines()[:-1]
+    if out == ["refused"]:
+        return None, {}
+    got = {(f[0], int(f[1])): np.array([int(v) for v in f[2:]], dtype=np.int64) for f in (line.split() for line in out[1:])}
+    return int(out[0].split()[1]), got
+
+
+def covered(chunks):
+    """the elements the fill chunks (offset, length, offset, length, ...) zero; no element twice, no chunk empty or longer than a workgroup's 1024"""
+    off, length = chunks[0::2], chunks[1::2]
+    assert ((length >= 1) & (length <= 1024)).all()
+    cells = np.concatenate([np.arange(o, o + n) for o, n in zip(off, length)]) if len(off) else np.zeros(0, dtype=np.int64)
+    assert len(np.unique(cells)) == len(cells)
+    return np.sort(cells)
+
+
+def test_route_tables_of_the_ragged_problem_in_the_dense_layout(tables_host, tmp_path):
+    """the address table, the finishing pass's addresses and the fill chunks against numpy on the same coordinates, exactly"""
+    TP = tp().trajectory("ragged")
+    tr = sys.modules[type(TP).__module__]
+    nx, ne, nc, npar = TP.nx, TP.ne, TP.nc, TP.np
+    for ld in (ne + nc, ne + nc + 3):
+        rc, got = route(tables_host, tmp_path, TP, ["dense %d" % ld])
+        assert rc == 0
+        for k, t in enumerate(TP.templates):
+            ld_of = {tr.D_GX: ld, tr.D_HX: ld, tr.D_GP: ne, tr.D_HP: nc}
+            want = t.d_i + t.d_j * np.array([ld_of[int(f)] for f in t.d_field], dtype=np.int64)[:, None]
+            assert np.array_equal(got[("ad", k)], want.reshape(-1)), (ld, k, t.kind)
+            for name, table in (("vi", t.vi), ("ri", t.ri), ("pi", t.pi)):
+                assert np.array_equal(got[(name, k)], table.reshape(-1)), (name, k)
+        vector = np.isin(TP.g_field, (tr.D_GYX, tr.D_HZX))
+        assert set(TP.g_field[~vector]) <= {tr.D_LXX, tr.D_LGP}
+        assert np.array_equal(got[("g_addr", 0)], np.where(vector, TP.g_i, TP.g_i + TP.g_j * nx))       # (the Hessian and the theta-gradient: both i + j nx)
+        assert np.array_equal(got[("g_field", 0)], TP.g_field) and np.array_equal(got[("g_slots", 0)], TP.g_slots.reshape(-1))
+        assert np.array_equal(got[("obj_slots", 0)], TP.obj_slots)
+        leading = lambda rows: (np.arange(rows)[:, None] + ld * np.arange(nx)[None, :]).T.reshape(-1)
+        assert np.array_equal(covered(got[("fill", 0)]), leading(ne)) and np.array_equal(covered(got[("fill", 1)]), leading(nc))
+        for c, size in ((2, nx * nx), (3, ne * npar), (4, nc * npar), (5, nx * npar)):
+            assert np.array_equal(covered(got[("fill", c)]), np.arange(size)), c
+    assert route(tables_host, tmp_path, TP, ["dense %d" % (ne + nc - 1)])[0] == 1
+
+
+def test_route_tables_of_a_cone_problem_in_the_block_layout(tables_host, tmp_path):
+    """blocks derived from structure(), laid out back to back: every address inside its block; a block that leaves a non-zero out is code 4"""
+    TP = tp().trajectory("cone_3")
+    tr = sys.modules[type(TP).__module__]
+    st = TP.structure()
+    nx, ne, nc = TP.nx, TP.ne, TP.nc
+    first, last = st["row_first"] - 1, st["row_last"] - 1
+    jac, at = [], 0                                    # [row0, nrows, col0, ncols, offset, ld]: one block per run of rows with one column range
+    for r in range(ne + nc):
+        if r not in (0, ne) and (first[r], last[r]) == (first[r - 1], last[r - 1]):
+            jac[-1][1] += 1
+        else:
+            jac.append([r, 1, int(first[r]), int(last[r] - first[r] + 1), 0, 0])
+    for b in jac:
+        b[4], b[5] = at, b[1]
+        at += b[1] * b[3]
+    starts = [int(s) - 1 for s in st["hessian_block_start"]] + [nx]
+    hes = []
+    for s0, s1 in zip(starts[:-1], starts[1:]):
+        hes.append([s0, s1 - s0, s0, s1 - s0, at, s1 - s0])
+        at += (s1 - s0) ** 2
+    layout = lambda J: ["block %d %d %d" % (len(J), len(hes), at)] + [" ".join(str(v) for v in b) for b in J + hes]
+    rc, got = route(tables_host, tmp_path, TP, layout(jac))
+    assert rc == 0
+
+    def inside(blocks, key, r, c):
+        """the offsets of (r, c) in the block whose rows (key 0) or columns (key 2) hold them; every one must lie in its block"""
+        out = np.full(r.shape, -1, dtype=np.int64)
+        for row0, nrows, col0, ncols, off, ld in blocks:
+            lo, n = (row0, nrows) if key == 0 else (col0, ncols)
+            mine = ((r if key == 0 else c) >= lo) & ((r if key == 0 else c) < lo + n)
+            assert ((r[mine] >= row0) & (r[mine] < row0 + nrows) & (c[mine] >= col0) & (c[mine] < col0 + ncols)).all()
+            out[mine] = off + (r[mine] - row0) + (c[mine] - col0) * ld
+        assert (out >= 0).all()
+        return out
+
+    for k, t in enumerate(TP.templates):
+        want = np.zeros((t.nd, t.n), dtype=np.int64)
+        for e, f in enumerate(t.d_field):
+            if f in (tr.D_GX, tr.D_HX):
+                want[e] = inside(jac, 0, t.d_i[e] + (ne if f == tr.D_HX else 0), t.d_j[e])
+            else:
+                want[e] = t.d_i[e] + t.d_j[e] * (ne if f == tr.D_GP else nc)
+        assert np.array_equal(got[("ad", k)], want.reshape(-1)), (k, t.kind)
+    want = np.where(np.isin(TP.g_field, (tr.D_GYX, tr.D_HZX)), TP.g_i, TP.g_i + TP.g_j * nx)
+    H = TP.g_field == tr.D_LXX
+    assert H.any()
+    want[H] = inside(hes, 2, TP.g_i[H], TP.g_j[H])
+    assert np.array_equal(got[("g_addr", 0)], want)
+    # the fill: the equality rows of the Jacobian blocks, their cone rows, the Hessian blocks — together the packed storage, once
+    cells = lambda blocks, lo, hi: np.sort(np.concatenate([(off + np.arange(max(lo, row0), min(hi, row0 + nrows))[:, None] - row0 + ld * np.arange(ncols)[None, :]).reshape(-1)
+                                                           for row0, nrows, col0, ncols, off, ld in blocks]))
+    parts = [covered(got[("fill", c)]) for c in range(3)]
+    assert np.array_equal(parts[0], cells(jac, 0, ne)) and np.array_equal(parts[1], cells(jac, ne, ne + nc)) and np.array_equal(parts[2], cells(hes, 0, nx))
+    assert np.array_equal(np.sort(np.concatenate(parts)), np.arange(at))
+    # the first block without its last column: the row range's last non-zero lies there
+    narrow = [list(b) for b in jac]
+    narrow[0][3] -= 1
+    assert route(tables_host, tmp_path, TP, layout(narrow))[0] == 4
+
+
+def test_the_tables_blob_is_checked_word_by_word(tables_host, tmp_path):
+    TP = tp().trajectory("ragged")
+    tr = sys.modules[type(TP).__module__]
+    blob, nt = TP.tables(), len(TP.templates)
+    dense = ["dense %d" % (TP.ne + TP.nc)]
+    assert route(tables_host, tmp_path, TP, dense, blob)[0] == 0
+    at, where = 10 + 8 * nt, {}                   # where each template's tables start in the blob
+    for k, t in enumerate(TP.templates):
+        where[k] = dict(vi=at, d_j=at + (t.nv + t.m + t.nth) * t.n + t.nd + t.nd * t.n)
+        at = where[k]["d_j"] + t.nd * t.n
+    k, e = next((k, e) for k, t in enumerate(TP.templates) for e, f in enumerate(t.d_field) if f in (tr.D_GP, tr.D_HP))
+    assert blob[where[0]["vi"]] == TP.templates[0].vi[0, 0] and blob[where[k]["d_j"] + e * TP.templates[k].n] == TP.templates[k].d_j[e, 0] and TP.np < TP.nx
+    assert blob[-1] == TP.obj_slots[-1]
+
+    def changed(index, value):
+        b = blob.copy()
+        b[index] = value
+        return b
+
+    refused = {"magic": changed(0, blob[0] ^ 1), "NT off by one": changed(1, nt + 1), "one word short": blob[:-1], "one word long": np.append(blob, 0),
+               "a variable index nx": changed(where[0]["vi"], TP.nx), "a partial slot past the last": changed(-1, TP.n_partials),
+               "a parameter column np": changed(where[k]["d_j"] + e * TP.templates[k].n, TP.np)}
+    for what, b in refused.items():
+        assert route(tables_host, tmp_path, TP, dense, np.ascontiguousarray(b, dtype=np.int32))[0] is None, what
 
 
 def test_refusals():

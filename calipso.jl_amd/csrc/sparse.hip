@@ -25,14 +25,18 @@
 #include "device_utils.hpp"
 #include "pivot16.hpp"
 #include "ldl_device.hpp"
+#include "sparse_plan.hpp"                 // the analyse phase and the records the kernels read: plain host C++
 
 using calipso::i64;
+using namespace calipso::sparse_plan;
+static_assert(REFUSED_ARGUMENT == CALIPSO_ERR_ARGUMENT, "a refused pattern is an argument error");
 
 namespace {
 
+constexpr Limits LIMITS{};                 // what the kernels are built for; a plan is made under these and the two debug switches
 constexpr int SP_THREADS = 256;
 constexpr int SP_REC = 256;                // update records staged in LDS at a time
-constexpr int SP_LDS_MAX_N = 19400;        // 155 200 B of the CU's 160 KiB LDS for the accumulator (4 KiB of record stage beside it)
+constexpr int SP_LDS_MAX_N = LIMITS.lds_max_n;
 
 struct SpDev {
     int n;
@@ -153,15 +157,7 @@ __global__ void k_sp_permute_out(const double* __restrict__ x, const int* __rest
 // ascending order: fixed summation order), the first c columns are eliminated by a dense LDL^T in LDS (one barrier per pivot column), the
 // m x c panel of L goes to global memory and U_s = F_s[c.., c..] to the node's slot of the update pool.  One launch per LEVEL of the node tree:
 // for a T-stage trajectory problem that is ~log2 T launches for the whole factorisation — the stages are eliminated in parallel, level by level.
-// One record per node in LAUNCH order and one per (node, child): what a workgroup needs to find its front comes with ONE load each instead of a chain of
-// dependent table look-ups (order -> nfirst / ncols / nrows -> childptr -> children -> upd_off / rowptr ...: 0.7 us per hop on a cold launch).
-struct MfNode { int s, f, c, r; int rowptr, chfirst, nch, alp0; int alp1, pad0, pad1, pad2; long long panel_off, upd_off, u_off, foff; int xa0, xa1; };
-// pad0: first row record of a front factored by many workgroups (sparse_wide.hpp; -1: none), pad1: launch position of the parent (-1: a root), pad2: the level's ypan
-struct MfChild { int rc, rowptr; long long upd_off, u_off; int pos, pad; };   // pos: the child's launch position
-// one entry of a child's update matrix on its way into the parent's LDS front (MfNode::xa0 .. xa1, children in ascending order, a child's lower triangle row by row):
-// usrc = its offset in the instance's update pool, tq = its place in the parent's packed front | the child's ordinal << 16
-struct MfXItem { unsigned usrc, tq; };
-struct MfRowItem { long long uoff; int relptr, a, uo, pad; };   // row a of a child's update matrix (offset in the update pool), the child's relative indices, the row's entry of the child's vector (solves)
+// (the records MfNode / MfChild / MfXItem / MfRowItem and the tables below are built on the host by sparse_plan.hpp)
 struct MfDev {
     int nnodes;
     const MfNode* nrec;                       // [launch position]
@@ -193,15 +189,9 @@ struct MfDev {
 struct MfSlots { int use; int slot[calipso::MAX_BATCH]; };
 
 typedef double calipso_v4d __attribute__((ext_vector_type(4)));
-// threads per front: 256 for small fronts (several workgroups share a CU), 512 for fronts of more than MF_BIG rows (one front fills the CU's LDS
-// anyway; more waves shorten the panel, assembly and matrix-core phases)
-constexpr int MF_BIG = 96;
-constexpr int MF_MAX_FRONT = 196;             // (m (m + 1) / 2 + 2 m) doubles <= 160 KiB: the front's lower triangle, packed, + the pivot-column buffers
-constexpr int MF_PY = 18;                     // row stride of the exchange rows of an in-register panel (pivot16.hpp)
-constexpr int MF_MAX_FRONT_WIDE = 8192;       // fronts factored and solved by many workgroups (sparse_wide.hpp); beyond: the column method
-constexpr int MF_MAX_FRONT_GLOBAL = 4095;     // the ONE-workgroup kernels on fronts in global memory (calipso_hip_debug_wide_fronts(0): the A/B reference of
-                                              // sparse_wide.hpp): same algorithm as in LDS, every access a memory access (a 1500-row front is ~2 ms); 4095 is where
-                                              // the 24-bit index arithmetic of the packed triangle ends (tri0)
+// threads per front: 256 for small fronts (several workgroups share a CU), 512 for fronts of more than Limits::big rows (one front fills the CU's LDS
+// anyway; more waves shorten the panel, assembly and matrix-core phases).  The front limits (Limits::max_front, max_front_wide, max_front_global) are the plan's.
+constexpr int MF_PY = LIMITS.py;              // row stride of the exchange rows of an in-register panel (pivot16.hpp)
 
 // The front is symmetric: only its lower triangle is held, packed row by row (row i starts at i (i + 1) / 2), which lets fronts of up to 196 rows
 // fit the 160 KiB of LDS (a full square would stop at 141).
@@ -781,7 +771,6 @@ __global__ __launch_bounds__(MF_THREADS) void k_mf_backward(const MfDev d, const
 
 int g_wide_fronts = 1;         // calipso_hip_debug_wide_fronts: 0 = the one-workgroup kernel for the global-memory fronts too (plans made afterwards)
 static int g_mf_items = 1;      // extend-add items for the LDS fronts (calipso_hip_debug_mf_items)
-struct MfSeg { int first, count; size_t lds_factor, lds_solve; int threads; bool global; int ypan; MfWide wide; };   // ypan: room for the 64 x MF_PY exchange rows of the in-register panels
 // launch helpers: the thread count of a level is fixed by the analyse phase (MfSeg::threads)
 #define MF_LAUNCH(KERNEL, G, GRID, LDS, STREAM, ...)                                                                              \
     do {                                                                                                                          \
@@ -799,30 +788,16 @@ struct MfSeg { int first, count; size_t lds_factor, lds_solve; int threads; bool
         else hipLaunchKernelGGL((KERNEL<256, false>), GRID, dim3(256), LDS, STREAM, __VA_ARGS__);                                \
     } while (0)
 
-struct Segment { int first, count; bool chain; };
-
 }  // namespace
 
 struct calipso_hip_sparse {
+    SparsePlan plan;                             // everything the analyse phase made (sparse_plan.hpp): the host's copy of every table on the device
     int n = 0, device = 0;
-    i64 nnzA = 0, nnzU = 0, nnzL = 0, flops = 0;
-    int levels = 0, widest = 0;
     bool lds_acc = true;
-    std::vector<i64> perm;                       // 1-based, perm[k] = vertex eliminated k-th
-    std::vector<int> hLp, hLi;                   // host copy of the pattern (get_factor)
-    std::vector<Segment> plan;
-    bool mf = false;                             // multifrontal numeric phase (nested-dissection orders whose fronts fit the LDS)
+    bool mf = false;                             // multifrontal numeric phase (plan.mf: nested-dissection orders whose fronts fit)
     MfDev md{};
-    std::vector<MfSeg> mplan;
-    std::vector<int> h_nfirst, h_ncols, h_nrows, h_rowptr, h_rows;
-    std::vector<long long> h_panel_off;
-    long long panel_total = 0, usum = 0;
     size_t cap_uvec = 0;
-    int max_front = 0, nnodes = 0;
     int batch = 1, selected = 0;                 // matrices of this pattern factored together / the one get_factor reads
-    long long upd_total = 0, pool_total = 0;
-    int wide_count = 0;                          // most fronts of one level factored by many workgroups (their scratch: sparse_wide.hpp)
-    int wide_blocks = 1;                         // most row blocks of such a front in the backward sweep
     double* wpart = nullptr;                     // partial products of the backward sweep: (column of the solve, node of the level, row block, 64)
     size_t cap_wpart = 0;
     std::vector<i64> inertia_all;                // batch x 3
@@ -850,21 +825,24 @@ namespace {
 // (re)allocate everything that holds VALUES, for `batch` matrices of the analysed pattern: instance-major
 int alloc_values(calipso_hip_sparse* s, int batch) {
     const size_t B = (size_t)batch;
+    const i64 nnzA = s->plan.nnzA;
     for (double** pp : {&s->d_Aval, &s->d.Lx, &s->d.D, &s->md.panel, &s->md.upd, &s->md.fpool, &s->md.wscr}) if (*pp) { (void)hipFree(*pp); *pp = nullptr; }
-    PK(hipMalloc((void**)&s->d_Aval, sizeof(double) * B * std::max<size_t>((size_t)s->nnzA, 1)));
-    PK(hipMemset(s->d_Aval, 0, sizeof(double) * B * std::max<size_t>((size_t)s->nnzA, 1)));      // (entries a structured handle never writes are structural zeros)
+    PK(hipMalloc((void**)&s->d_Aval, sizeof(double) * B * std::max<size_t>((size_t)nnzA, 1)));
+    PK(hipMemset(s->d_Aval, 0, sizeof(double) * B * std::max<size_t>((size_t)nnzA, 1)));      // (entries a structured handle never writes are structural zeros)
     PK(hipMalloc((void**)&s->d.D, sizeof(double) * B * (size_t)s->n));
     if (s->mf) {
-        PK(hipMalloc((void**)&s->md.panel, sizeof(double) * B * std::max<size_t>((size_t)s->panel_total, 1)));
-        PK(hipMalloc((void**)&s->md.upd, sizeof(double) * B * std::max<size_t>((size_t)s->upd_total, 1)));
-        if (s->pool_total) PK(hipMalloc((void**)&s->md.fpool, sizeof(double) * B * (size_t)s->pool_total));
-        if (s->wide_count) PK(hipMalloc((void**)&s->md.wscr, sizeof(double) * B * (size_t)s->wide_count * WF_SCR));
+        const MfPlan& M = *s->plan.mf;
+        PK(hipMalloc((void**)&s->md.panel, sizeof(double) * B * std::max<size_t>((size_t)M.panel_total, 1)));
+        PK(hipMalloc((void**)&s->md.upd, sizeof(double) * B * std::max<size_t>((size_t)M.upd_total, 1)));
+        if (M.pool_total) PK(hipMalloc((void**)&s->md.fpool, sizeof(double) * B * (size_t)M.pool_total));
+        if (M.wide_count) PK(hipMalloc((void**)&s->md.wscr, sizeof(double) * B * (size_t)M.wide_count * WF_SCR));
+        s->md.sPanel = M.panel_total; s->md.sUpd = M.upd_total; s->md.sPool = M.pool_total;
     } else {
-        PK(hipMalloc((void**)&s->d.Lx, sizeof(double) * B * std::max<size_t>((size_t)s->nnzL, 1)));
+        PK(hipMalloc((void**)&s->d.Lx, sizeof(double) * B * std::max<size_t>((size_t)s->plan.L.nnzL, 1)));
     }
     s->d.Aval = s->d_Aval;
     s->md.Aval = s->d_Aval; s->md.D = s->d.D;
-    s->md.sA = s->nnzA; s->md.sPanel = s->panel_total; s->md.sUpd = s->upd_total; s->md.sD = s->n; s->md.sPool = s->pool_total;
+    s->md.sA = nnzA; s->md.sD = s->n;
     s->batch = batch; s->selected = 0; s->factored = false;
     s->inertia_all.assign(3 * B, 0);
     return CALIPSO_OK;
@@ -882,8 +860,8 @@ int upload(calipso_hip_sparse* s, const std::vector<T>& h, const T** out) {
 
 // room for the partial products of the wide fronts' backward sweep, for `cols` columns per solve
 int mf_reserve_wide_solve(calipso_hip_sparse* s, size_t cols) {
-    if (!s->wide_count) return CALIPSO_OK;
-    const size_t need = cols * (size_t)s->wide_count * (size_t)s->wide_blocks * 64;
+    if (!s->mf || !s->plan.mf->wide_count) return CALIPSO_OK;
+    const size_t need = cols * (size_t)s->plan.mf->wide_count * (size_t)s->plan.mf->wide_blocks * 64;
     if (need > s->cap_wpart) {
         if (s->wpart) (void)hipFree(s->wpart);
         s->wpart = nullptr; s->cap_wpart = 0;
@@ -894,20 +872,21 @@ int mf_reserve_wide_solve(calipso_hip_sparse* s, size_t cols) {
 }
 // the numeric factorisation of nz matrices (storage slots sl) on stream st: a launch per level of the tree (fronts beyond the LDS: three, sparse_wide.hpp)
 void mf_enqueue_factor(calipso_hip_sparse* s, hipStream_t st, const MfSlots& sl, unsigned nz) {
-    for (const MfSeg& g : s->mplan) {
+    for (const MfSeg& g : s->plan.mf->levels) {
         if (g.wide.on) mf_wide_factor(st, s->md, sl, g.wide, g.first, g.count, nz);
         else MF_LAUNCH(k_mf_factor, g, dim3((unsigned)g.count, nz), g.lds_factor, st, s->md, sl, g.first, g.ypan);
     }
 }
 // both sweeps of a solve for ny = instances x nrhs columns of X (already permuted)
 void mf_enqueue_solve(calipso_hip_sparse* s, hipStream_t st, const MfSlots& sl, unsigned ny, int nrhs, double* X) {
-    const bool wide_ok = s->wpart && (size_t)ny * (size_t)s->wide_count * (size_t)s->wide_blocks * 64 <= s->cap_wpart;
-    for (const MfSeg& g : s->mplan) {
-        if (g.wide.solve && wide_ok) mf_wide_forward(st, s->md, sl, g.wide, g.first, g.count, ny, s->n, nrhs, s->usum, X);
-        else MF_LAUNCH_SOLVE(k_mf_forward, g, dim3((unsigned)g.count, ny), g.lds_solve, st, s->md, sl, g.first, s->n, nrhs, s->usum, X);
+    const MfPlan& M = *s->plan.mf;
+    const bool wide_ok = s->wpart && (size_t)ny * (size_t)M.wide_count * (size_t)M.wide_blocks * 64 <= s->cap_wpart;
+    for (const MfSeg& g : M.levels) {
+        if (g.wide.solve && wide_ok) mf_wide_forward(st, s->md, sl, g.wide, g.first, g.count, ny, s->n, nrhs, M.usum, X);
+        else MF_LAUNCH_SOLVE(k_mf_forward, g, dim3((unsigned)g.count, ny), g.lds_solve, st, s->md, sl, g.first, s->n, nrhs, M.usum, X);
     }
-    for (auto g = s->mplan.rbegin(); g != s->mplan.rend(); ++g) {
-        if (g->wide.solve && wide_ok) mf_wide_backward(st, s->md, sl, g->wide, g->first, g->count, ny, s->n, nrhs, X, s->wpart, s->wide_blocks);
+    for (auto g = M.levels.rbegin(); g != M.levels.rend(); ++g) {
+        if (g->wide.solve && wide_ok) mf_wide_backward(st, s->md, sl, g->wide, g->first, g->count, ny, s->n, nrhs, X, s->wpart, M.wide_blocks);
         else MF_LAUNCH_SOLVE(k_mf_backward, (*g), dim3((unsigned)g->count, ny), g->lds_solve, st, s->md, sl, g->first, s->n, nrhs, X);
     }
 }
@@ -917,8 +896,8 @@ void enqueue_factor(calipso_hip_sparse* s) {
     const size_t lds = s->lds_acc ? sizeof(double) * (size_t)s->n : 0;
     for (int z = 0; z < s->batch; ++z) {                    // the column method takes the matrices of a batch one after the other
         SpDev d = s->d;
-        d.Aval += (size_t)z * (size_t)s->nnzA; d.Lx += (size_t)z * (size_t)s->nnzL; d.D += (size_t)z * (size_t)s->n;
-        for (const Segment& g : s->plan) {
+        d.Aval += (size_t)z * (size_t)s->plan.nnzA; d.Lx += (size_t)z * (size_t)s->plan.L.nnzL; d.D += (size_t)z * (size_t)s->n;
+        for (const Segment& g : s->plan.cols.plan) {
             const int grid = g.chain ? 1 : std::min(g.count, s->work_slots);
             if (s->lds_acc) hipLaunchKernelGGL(k_sp_factor<true>, dim3(grid), dim3(SP_THREADS), lds, s->stream, d, g.first, g.count);
             else hipLaunchKernelGGL(k_sp_factor<false>, dim3(grid), dim3(SP_THREADS), 0, s->stream, d, g.first, g.count);
@@ -986,13 +965,13 @@ void sparse_borrow_stream(calipso_hip_sparse* sp, hipStream_t st) {
 }
 int sparse_batch(const calipso_hip_sparse* sp) { return sp ? sp->batch : 0; }
 // gather the pattern's entries from the dense S of every instance of `bt`, factor, add the pivot signs to the instances' counters
-void sparse_values(calipso_hip_sparse* sp, double** values, long long* stride) { *values = sp ? sp->d_Aval : nullptr; *stride = sp ? (long long)sp->nnzA : 0; }
+void sparse_values(calipso_hip_sparse* sp, double** values, long long* stride) { *values = sp ? sp->d_Aval : nullptr; *stride = sp ? (long long)sp->plan.nnzA : 0; }
 // values_in_place: the caller has written the pattern's entries into sparse_values() itself (structured handles: blocks.hip) — no gather
 int sparse_factor_from_dense(calipso_hip_sparse* sp, hipStream_t st, const Batch& bt, const double* S, const long long* src, int* icount, bool values_in_place) {
     if (!sp || !sp->mf || bt.n > sp->batch) return CALIPSO_ERR_ARGUMENT;
     for (int k = 0; k < bt.n; ++k) if (bt.slot[k] >= sp->batch) return CALIPSO_ERR_ARGUMENT;
     const unsigned nz = (unsigned)bt.n;
-    if (!values_in_place) hipLaunchKernelGGL(k_gather_dense, dim3((unsigned)((sp->nnzA + 255) / 256), 1, nz), dim3(256), 0, st, bt, S, src, (long long)sp->nnzA, sp->d_Aval);
+    if (!values_in_place) hipLaunchKernelGGL(k_gather_dense, dim3((unsigned)((sp->plan.nnzA + 255) / 256), 1, nz), dim3(256), 0, st, bt, S, src, (long long)sp->plan.nnzA, sp->d_Aval);
     MfSlots sl{};
     sl.use = 1;
     for (int k = 0; k < bt.n; ++k) sl.slot[k] = bt.slot[k];
@@ -1039,7 +1018,7 @@ int sparse_reserve_solve(calipso_hip_sparse* s, int batch) {
         PK(hipMalloc((void**)&s->d_rhs, sizeof(double) * need)); PK(hipMalloc((void**)&s->d_x, sizeof(double) * need));
         s->cap_rhs = need;
     }
-    const size_t need_u = (size_t)std::max<long long>(s->usum, 1) * (size_t)batch;
+    const size_t need_u = (size_t)std::max<long long>(s->mf ? s->plan.mf->usum : 0, 1) * (size_t)batch;
     if (need_u > s->cap_uvec) {
         if (s->md.uvec) (void)hipFree(s->md.uvec);
         s->md.uvec = nullptr; s->cap_uvec = 0;
@@ -1048,8 +1027,8 @@ int sparse_reserve_solve(calipso_hip_sparse* s, int batch) {
     }
     return mf_reserve_wide_solve(s, (size_t)batch);
 }
-void sparse_work(const calipso_hip_sparse* sp, double out[3]) { out[0] = (double)sp->flops; out[1] = (double)sp->nnzL; out[2] = (double)sp->n; }
-void sparse_describe(const calipso_hip_sparse* sp, int64_t out[4]) { out[0] = sp->levels; out[1] = sp->max_front; out[2] = sp->nnzU; out[3] = sp->mf ? 2 : (sp->lds_acc ? 1 : 0); }
+void sparse_work(const calipso_hip_sparse* sp, double out[3]) { out[0] = (double)sp->plan.R.flops; out[1] = (double)sp->plan.L.nnzL; out[2] = (double)sp->n; }
+void sparse_describe(const calipso_hip_sparse* sp, int64_t out[4]) { out[0] = sp->plan.levels(); out[1] = sp->mf ? sp->plan.mf->max_front : 0; out[2] = sp->plan.A.nnzU; out[3] = sp->mf ? 2 : (sp->lds_acc ? 1 : 0); }
 }  // namespace calipso
 
 // (tests / A-B timing) how plans made AFTERWARDS treat fronts beyond the LDS: 1 = many workgroups per front (default), 0 = one; returns the old value
@@ -1125,10 +1104,9 @@ static int32_t sparse_create_impl(int64_t n, const int64_t* colptr, const int64_
     if (device < 0 || device >= ndev) { g_sparse_err = "device ordinal out of range"; return CALIPSO_ERR_ARGUMENT; }
     // ---- order
     std::vector<i64> p((size_t)n);
-    std::vector<std::pair<int, int>> pieces;        // nested dissection: (first position, count) of every leaf piece / separator
+    Pieces pieces;                                  // nested dissection: (first position, count) of every leaf piece / separator
     if (method == 3) {
-        std::vector<char> seen((size_t)n, 0);
-        for (i64 k = 0; k < n; ++k) { const i64 v = perm[k]; if (v < 1 || v > n || seen[(size_t)v - 1]) { g_sparse_err = "perm is not a permutation of 1:n"; return CALIPSO_ERR_ARGUMENT; } seen[(size_t)v - 1] = 1; p[(size_t)k] = v; }
+        std::copy(perm, perm + n, p.begin());       // (analyse refuses what is not a permutation of 1:n)
     } else if (method >= 4) {
         const int rc = calipso::nested_dissection_pieces(n, colptr, rowval, p.data(), pieces);
         if (rc < 0) { g_sparse_err = "nested dissection failed"; return rc; }
@@ -1136,253 +1114,18 @@ static int32_t sparse_create_impl(int64_t n, const int64_t* colptr, const int64_
         const int rc = calipso_hip_ordering(n, colptr, rowval, method, p.data());
         if (rc < 0) { g_sparse_err = "calipso_hip_ordering failed"; return rc; }
     }
-    std::vector<int> ip((size_t)n);
-    for (i64 k = 0; k < n; ++k) ip[(size_t)p[(size_t)k] - 1] = (int)k;
-    // ---- P A P' as a lower CSC (rows ascending), with the gather map from the caller's nzval
-    const i64 nnzA = colptr[n] - 1;
-    std::vector<std::vector<std::pair<int, int>>> col((size_t)n);       // (row, source index)
-    i64 nnzU = 0;
-    for (i64 c = 0; c < n; ++c)
-        for (i64 q = colptr[c] - 1; q < colptr[c + 1] - 1; ++q) {
-            const i64 r = rowval[q] - 1;
-            if (r < 0 || r >= n) { g_sparse_err = "row index out of range"; return CALIPSO_ERR_ARGUMENT; }
-            if (r > c) continue;
-            const int pr = ip[(size_t)r], pc = ip[(size_t)c];
-            col[(size_t)std::min(pr, pc)].push_back({std::max(pr, pc), (int)q});
-            ++nnzU;
-        }
-    std::vector<int> Alp((size_t)n + 1, 0), Ali, Asrc;
-    Ali.reserve((size_t)nnzU); Asrc.reserve((size_t)nnzU);
-    std::vector<std::vector<int>> lowrow((size_t)n);                    // row view of the strictly lower part: columns i < j of row j
-    for (int j = 0; j < (int)n; ++j) {
-        auto& cj = col[(size_t)j];
-        std::sort(cj.begin(), cj.end());
-        for (size_t a = 1; a < cj.size(); ++a) if (cj[a].first == cj[a - 1].first) { g_sparse_err = "duplicate entry in the CSC pattern"; return CALIPSO_ERR_ARGUMENT; }
-        for (auto& e : cj) { Ali.push_back(e.first); Asrc.push_back(e.second); if (e.first > j) lowrow[(size_t)e.first].push_back(j); }
-        Alp[(size_t)j + 1] = (int)Ali.size();
-    }
-    // QDLDL_etree! refuses a matrix with an empty column of the upper triangle (qdldl.jl:366-371): column j of triu(P A P') = row j of the lower part + diagonal
-    for (int j = 0; j < (int)n; ++j) {
-        const bool diag = Alp[(size_t)j] < Alp[(size_t)j + 1] && Ali[(size_t)Alp[(size_t)j]] == j;
-        if (!diag && lowrow[(size_t)j].empty()) { g_sparse_err = "empty column in triu(A): QDLDL_etree! fails on this matrix (qdldl.jl:366-371)"; return CALIPSO_ERR_ARGUMENT; }
-    }
-    // ---- elimination tree (Liu, path compression)
-    std::vector<int> parent((size_t)n, -1), anc((size_t)n, -1);
-    for (int j = 0; j < (int)n; ++j)
-        for (int i0 : lowrow[(size_t)j]) {
-            int i = i0;
-            while (i != -1 && i < j) { const int nxt = anc[(size_t)i]; anc[(size_t)i] = j; if (nxt == -1) parent[(size_t)i] = j; i = nxt; }
-        }
-    // ---- pattern of L: struct(L_j) = struct(A_j below the diagonal) U (struct(L_c) \ {j}) over the children c of j
-    std::vector<std::vector<int>> children((size_t)n);
-    for (int j = 0; j < (int)n; ++j) if (parent[(size_t)j] >= 0) children[(size_t)parent[(size_t)j]].push_back(j);
-    std::vector<std::vector<int>> Lcol((size_t)n);
-    std::vector<int> mark((size_t)n, -1);
-    i64 nnzL = 0, flops = 0;
-    for (int j = 0; j < (int)n; ++j) {
-        std::vector<int>& lj = Lcol[(size_t)j];
-        mark[(size_t)j] = j;
-        for (int q = Alp[(size_t)j]; q < Alp[(size_t)j + 1]; ++q) { const int r = Ali[(size_t)q]; if (r > j && mark[(size_t)r] != j) { mark[(size_t)r] = j; lj.push_back(r); } }
-        for (int c : children[(size_t)j]) for (int r : Lcol[(size_t)c]) if (r != j && mark[(size_t)r] != j) { mark[(size_t)r] = j; lj.push_back(r); }
-        std::sort(lj.begin(), lj.end());
-        nnzL += (i64)lj.size();
-        if (nnzL > 0x7fffffff) { g_sparse_err = "nnz(L) exceeds 2^31 - 1"; return CALIPSO_ERR_ARGUMENT; }
-    }
-    std::vector<int> Lp((size_t)n + 1, 0), Li; Li.reserve((size_t)nnzL);
-    for (int j = 0; j < (int)n; ++j) { Li.insert(Li.end(), Lcol[(size_t)j].begin(), Lcol[(size_t)j].end()); Lp[(size_t)j + 1] = (int)Li.size(); }
-    // ---- row view
-    std::vector<int> Rp((size_t)n + 1, 0);
-    for (int v : Li) Rp[(size_t)v + 1] += 1;
-    for (int j = 0; j < (int)n; ++j) Rp[(size_t)j + 1] += Rp[(size_t)j];
-    std::vector<int> Rk((size_t)nnzL), Rpos((size_t)nnzL), Rend((size_t)nnzL), nextr(Rp.begin(), Rp.end() - 1);
-    for (int k = 0; k < (int)n; ++k)
-        for (int q = Lp[(size_t)k]; q < Lp[(size_t)k + 1]; ++q) {
-            const int at = nextr[(size_t)Li[(size_t)q]]++;
-            Rk[(size_t)at] = k; Rpos[(size_t)at] = q; Rend[(size_t)at] = Lp[(size_t)k + 1];
-            flops += (i64)(Lp[(size_t)k + 1] - q);
-        }
-    // ---- levels and the launch plan
-    std::vector<int> level((size_t)n, 0);
-    int height = 0;
-    for (int j = 0; j < (int)n; ++j) {          // children have smaller indices: one ascending pass
-        if (parent[(size_t)j] >= 0) level[(size_t)parent[(size_t)j]] = std::max(level[(size_t)parent[(size_t)j]], level[(size_t)j] + 1);
-        height = std::max(height, level[(size_t)j] + 1);
-    }
-    std::vector<int> order((size_t)n);
-    std::iota(order.begin(), order.end(), 0);
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return level[(size_t)a] < level[(size_t)b]; });
-    std::vector<Segment> plan;
-    int widest = 0;
-    for (int a = 0; a < (int)n;) {
-        int b = a;
-        while (b < (int)n && level[(size_t)order[(size_t)b]] == level[(size_t)order[(size_t)a]]) ++b;
-        const int cnt = b - a;
-        widest = std::max(widest, cnt);
-        if (cnt == 1 && !plan.empty() && plan.back().chain) plan.back().count += 1;        // extend the chain of single-column levels
-        else plan.push_back({a, cnt, cnt == 1});
-        a = b;
-    }
-    // ---- multifrontal symbolic phase (method 4): the dissection pieces as supernodes
-    // A piece the level structure could not split (a clique-like stage block) or a wide separator is cut into a chain of chunks of <= w columns;
-    // w is lowered until every front (chunk + its rows below) fits one CU's LDS — e.g. 56 for stages of 56 variables, where chunks that straddle
-    // two stages would carry both stages' neighbours.
-    bool use_mf = false;
-    const std::vector<std::pair<int, int>> base_pieces = pieces;
-    int NN = 0;
-    std::vector<int> m_first, m_cols, m_rows, m_parent, m_rowptr, m_rowsv, m_rel, m_childptr, m_children, m_order, m_Aloc;
-    std::vector<long long> m_panel_off, m_upd_off, m_u_off;
-    std::vector<MfSeg> mplan;
-    long long panel_total = 0, upd_total = 0, usum = 0;
-    int max_front = 0, mf_levels = 0, mf_widest = 0;
-    // last resort: chunks of 64 columns with the oversized fronts in global memory (MF_MAX_FRONT_GLOBAL)
-    std::vector<long long> m_foff;
-    long long pool_total = 0;
-    std::vector<int> m_wbase, w_ptrE, w_ptrC, w_Ecol, w_Esrc;     // fronts factored by many workgroups (sparse_wide.hpp)
-    std::vector<MfRowItem> w_C;
-    int wide_count = 0;
-    for (int attempt = 0; attempt < 8; ++attempt) {
-        const int width = attempt < 7 ? (int[]){64, 56, 48, 40, 32, 24, 16}[attempt] : 64;
-        const int front_limit = attempt < 7 ? MF_MAX_FRONT : (g_wide_fronts ? MF_MAX_FRONT_WIDE : MF_MAX_FRONT_GLOBAL);
-        if (method != 4 || base_pieces.empty() || use_mf) break;
-        pieces.clear();
-        for (const auto& bp : base_pieces) for (int o = 0; o < bp.second; o += width) pieces.push_back({bp.first + o, std::min(width, bp.second - o)});
-        NN = (int)pieces.size();
-        use_mf = true;
-        max_front = 0;
-        m_rowsv.clear(); m_children.clear(); mplan.clear(); panel_total = upd_total = usum = 0; mf_widest = 0;
-        {
-        std::vector<int> node_of((size_t)n, -1);
-        for (int t = 0; t < NN; ++t) for (int q = 0; q < pieces[(size_t)t].second; ++q) node_of[(size_t)(pieces[(size_t)t].first + q)] = t;
-        for (int j = 0; j < (int)n; ++j) if (node_of[(size_t)j] < 0) use_mf = false;
-        std::vector<std::vector<int>> R((size_t)NN);
-        m_parent.assign((size_t)NN, -1);
-        std::vector<int> stamp((size_t)n, -1);
-        for (int t = 0; t < NN && use_mf; ++t) {
-            // rows below the node reached from any of its columns, plus what the children passed up (already in R[t])
-            const int f = pieces[(size_t)t].first, c = pieces[(size_t)t].second, last = f + c - 1;
-            std::vector<int>& rt = R[(size_t)t];
-            for (int v : rt) stamp[(size_t)v] = t;
-            for (int j = f; j <= last; ++j) for (int i : Lcol[(size_t)j]) if (i > last && stamp[(size_t)i] != t) { stamp[(size_t)i] = t; rt.push_back(i); }
-            std::sort(rt.begin(), rt.end());
-            max_front = std::max(max_front, c + (int)rt.size());
-            if (!rt.empty()) {
-                const int par = node_of[(size_t)rt[0]];
-                m_parent[(size_t)t] = par;
-                const int pl = pieces[(size_t)par].first + pieces[(size_t)par].second - 1;
-                std::vector<int>& rp = R[(size_t)par];                  // closure: what the parent does not own it must carry on
-                for (int v : rt) if (v > pl) rp.push_back(v);
-                std::sort(rp.begin(), rp.end()); rp.erase(std::unique(rp.begin(), rp.end()), rp.end());
-            }
-        }
-        if (max_front > front_limit) use_mf = false;                    // a front that does not fit: next chunk width / global fronts / column method
-        if (use_mf) {
-            m_first.resize((size_t)NN); m_cols.resize((size_t)NN); m_rows.resize((size_t)NN); m_rowptr.assign((size_t)NN + 1, 0);
-            m_panel_off.resize((size_t)NN); m_upd_off.resize((size_t)NN); m_u_off.resize((size_t)NN);
-            for (int t = 0; t < NN; ++t) {
-                const int c = pieces[(size_t)t].second, r = (int)R[(size_t)t].size();
-                m_first[(size_t)t] = pieces[(size_t)t].first; m_cols[(size_t)t] = c; m_rows[(size_t)t] = r;
-                m_rowptr[(size_t)t + 1] = m_rowptr[(size_t)t] + r;
-                m_panel_off[(size_t)t] = panel_total; panel_total += (long long)(c + r) * c;
-                m_upd_off[(size_t)t] = upd_total; upd_total += (long long)r * r;
-                m_u_off[(size_t)t] = usum; usum += r;
-                m_rowsv.insert(m_rowsv.end(), R[(size_t)t].begin(), R[(size_t)t].end());
-            }
-            if (upd_total + panel_total > (1ll << 31)) { use_mf = false; continue; }      // (16 GiB of update matrices + panels per matrix: the column method instead)
-            // relative indices into the parent's front, children lists, levels
-            m_rel.assign(m_rowsv.size(), 0);
-            std::vector<std::vector<int>> kids((size_t)NN);
-            std::vector<int> lev((size_t)NN, 0);
-            for (int t = 0; t < NN; ++t) {
-                const int par = m_parent[(size_t)t];
-                if (par < 0) continue;
-                kids[(size_t)par].push_back(t);
-                lev[(size_t)par] = std::max(lev[(size_t)par], lev[(size_t)t] + 1);      // children precede parents in position order
-                const int pf = m_first[(size_t)par], pc = m_cols[(size_t)par];
-                const std::vector<int>& rp = R[(size_t)par];
-                for (int k = 0; k < m_rows[(size_t)t]; ++k) {
-                    const int v = R[(size_t)t][(size_t)k];
-                    m_rel[(size_t)m_rowptr[(size_t)t] + (size_t)k] = v < pf + pc ? v - pf : pc + (int)(std::lower_bound(rp.begin(), rp.end(), v) - rp.begin());
-                }
-            }
-            m_childptr.assign((size_t)NN + 1, 0);
-            for (int t = 0; t < NN; ++t) { m_childptr[(size_t)t + 1] = m_childptr[(size_t)t] + (int)kids[(size_t)t].size(); m_children.insert(m_children.end(), kids[(size_t)t].begin(), kids[(size_t)t].end()); }
-            // where each entry of the permuted lower CSC lands in its node's front
-            m_Aloc.assign(Ali.size(), 0);
-            for (int j = 0; j < (int)n; ++j) {
-                const int t = node_of[(size_t)j], f = m_first[(size_t)t], c = m_cols[(size_t)t];
-                const std::vector<int>& rt = R[(size_t)t];
-                for (int q = Alp[(size_t)j]; q < Alp[(size_t)j + 1]; ++q) {
-                    const int i = Ali[(size_t)q];
-                    const int lr = i < f + c ? i - f : c + (int)(std::lower_bound(rt.begin(), rt.end(), i) - rt.begin());
-                    m_Aloc[(size_t)q] = lr * (lr + 1) / 2 + (j - f);          // packed lower triangle (k_mf_factor: tri)
-                }
-            }
-            m_order.resize((size_t)NN);
-            m_foff.assign((size_t)NN, 0); pool_total = 0;
-            m_wbase.assign((size_t)NN, -1); w_ptrE.clear(); w_ptrC.clear(); w_Ecol.clear(); w_Esrc.clear(); w_C.clear(); wide_count = 0;
-            std::iota(m_order.begin(), m_order.end(), 0);
-            std::stable_sort(m_order.begin(), m_order.end(), [&](int a, int b) { return lev[(size_t)a] < lev[(size_t)b]; });
-            for (int a = 0; a < NN;) {
-                int b = a; size_t lf = 0, ls = 0, mmax = 0;
-                while (b < NN && lev[(size_t)m_order[(size_t)b]] == lev[(size_t)m_order[(size_t)a]]) {
-                    const int t = m_order[(size_t)b]; const size_t m = (size_t)(m_cols[(size_t)t] + m_rows[(size_t)t]);
-                    lf = std::max(lf, sizeof(double) * (m * (m + 1) / 2 + 2 * m)); ls = std::max(ls, sizeof(double) * 5 * m);   // the vector + four slices of partial sums per row
-                    mmax = std::max(mmax, m);
-                    ++b;
-                }
-                const bool glob = mmax > (size_t)MF_MAX_FRONT;
-                if (glob) {                                               // the level's fronts in the (reused) global pool; the solves keep only v in LDS
-                    long long off = 0;
-                    for (int q = a; q < b; ++q) { const int t = m_order[(size_t)q]; const long long mm = m_cols[(size_t)t] + m_rows[(size_t)t]; m_foff[(size_t)t] = off; off += mm * (mm + 1) / 2; }
-                    pool_total = std::max(pool_total, off);
-                    lf = 0;
-                }
-                int ypan = 0;                                             // full 16-column panels of fronts with >= 32 rows go through registers (pivot16.hpp) when the LDS has room for the exchange rows
-                if (!glob && mmax >= 32 && lf + sizeof(double) * 64 * MF_PY <= (size_t)(160 * 1024 - 2048)) { ypan = 1; lf += sizeof(double) * 64 * MF_PY; }
-                MfWide wide;                                              // fronts beyond the LDS: many workgroups per front (sparse_wide.hpp)
-                if (glob && g_wide_fronts) {
-                    wide.on = 1;
-                    wide_count = std::max(wide_count, b - a);
-                    for (int q = a; q < b; ++q) {
-                        const int t = m_order[(size_t)q], f = m_first[(size_t)t], c = m_cols[(size_t)t], r = m_rows[(size_t)t], mm = c + r;
-                        wide.m = std::max(wide.m, mm); wide.r = std::max(wide.r, r); wide.nch = std::max(wide.nch, (int)kids[(size_t)t].size());
-                        // per row of the front: its entries of A (any order: distinct targets) and the child rows that land in it, children ascending
-                        const int base = (int)w_ptrE.size();
-                        m_wbase[(size_t)t] = base;
-                        std::vector<int> cntE((size_t)mm + 1, 0), cntC((size_t)mm + 1, 0);
-                        const std::vector<int>& rt = R[(size_t)t];
-                        auto local = [&](int i) { return i < f + c ? i - f : c + (int)(std::lower_bound(rt.begin(), rt.end(), i) - rt.begin()); };
-                        for (int j = f; j < f + c; ++j) for (int e = Alp[(size_t)j]; e < Alp[(size_t)j + 1]; ++e) ++cntE[(size_t)local(Ali[(size_t)e]) + 1];
-                        for (int ch : kids[(size_t)t]) for (int k = 0; k < m_rows[(size_t)ch]; ++k) ++cntC[(size_t)m_rel[(size_t)m_rowptr[(size_t)ch] + (size_t)k] + 1];
-                        const int e0 = (int)w_Ecol.size(), c0 = (int)w_C.size();
-                        for (int i = 0; i < mm; ++i) { cntE[(size_t)i + 1] += cntE[(size_t)i]; cntC[(size_t)i + 1] += cntC[(size_t)i]; }
-                        for (int i = 0; i <= mm; ++i) { w_ptrE.push_back(e0 + cntE[(size_t)i]); w_ptrC.push_back(c0 + cntC[(size_t)i]); }
-                        w_Ecol.resize((size_t)e0 + (size_t)cntE[(size_t)mm]); w_Esrc.resize(w_Ecol.size()); w_C.resize((size_t)c0 + (size_t)cntC[(size_t)mm]);
-                        std::vector<int> atE(cntE.begin(), cntE.end() - 1), atC(cntC.begin(), cntC.end() - 1);
-                        for (int j = f; j < f + c; ++j) for (int e = Alp[(size_t)j]; e < Alp[(size_t)j + 1]; ++e) {
-                            const int at = e0 + atE[(size_t)local(Ali[(size_t)e])]++;
-                            w_Ecol[(size_t)at] = j - f; w_Esrc[(size_t)at] = Asrc[(size_t)e];
-                        }
-                        for (int ch : kids[(size_t)t]) for (int k = 0; k < m_rows[(size_t)ch]; ++k) {       // kids are ascending: so is every row's item list
-                            const int at = c0 + atC[(size_t)m_rel[(size_t)m_rowptr[(size_t)ch] + (size_t)k]]++;
-                            w_C[(size_t)at] = {m_upd_off[(size_t)ch] + (long long)k * m_rows[(size_t)ch], m_rowptr[(size_t)ch], k, (int)(m_u_off[(size_t)ch] + k), 0};
-                        }
-                    }
-                }
-                wide.solve = wide.on && (wide.m > 2048 || wide.nch > 4);
-                mplan.push_back({a, b - a, lf, ls, mmax > (size_t)MF_BIG ? 512 : 256, glob, ypan, wide});
-                mf_widest = std::max(mf_widest, b - a);
-                a = b;
-            }
-            mf_levels = (int)mplan.size();
-        }
-    }
-    }
+    if (method != 4) pieces.clear();                // the multifrontal numeric phase is method 4's; 5 keeps the dissection's order for the column method
+    // ---- the analysis: every table of both numeric phases, on the host (sparse_plan.hpp)
+    Limits lim = LIMITS;
+    lim.wide_fronts = g_wide_fronts; lim.mf_items = g_mf_items;
+    SparsePlan plan = analyse(n, colptr, rowval, std::move(p), pieces, lim);
+    if (plan.status) { g_sparse_err = plan.message; return plan.status; }
     // ---- the handle and its device side
     s = new calipso_hip_sparse();
     *out = s;
-    s->n = (int)n; s->device = device; s->nnzA = nnzA; s->nnzU = nnzU; s->nnzL = nnzL; s->flops = flops;
-    s->levels = height; s->widest = widest; s->perm = p; s->plan = plan; s->hLp = Lp; s->hLi = Li;
+    s->plan = std::move(plan);
+    const SparsePlan& P = s->plan;
+    s->n = (int)n; s->device = device; s->mf = P.mf.has_value();
     s->lds_acc = n <= SP_LDS_MAX_N;
     PK(hipSetDevice(device));
     PK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
@@ -1390,92 +1133,32 @@ static int32_t sparse_create_impl(int64_t n, const int64_t* colptr, const int64_
     s->d.n = (int)n;
     int rc;
     std::vector<int> hperm((size_t)n);
-    for (i64 k = 0; k < n; ++k) hperm[(size_t)k] = (int)(p[(size_t)k] - 1);
+    for (i64 k = 0; k < n; ++k) hperm[(size_t)k] = (int)(P.perm[(size_t)k] - 1);
     const int* cperm = nullptr;
-    if ((rc = upload(s, order, &s->d.order)) || (rc = upload(s, Alp, &s->d.Alp)) || (rc = upload(s, Ali, &s->d.Ali)) || (rc = upload(s, Asrc, &s->d.Asrc)) ||
-        (rc = upload(s, Lp, &s->d.Lp)) || (rc = upload(s, Li, &s->d.Li)) || (rc = upload(s, Rp, &s->d.Rp)) || (rc = upload(s, Rk, &s->d.Rk)) ||
-        (rc = upload(s, Rpos, &s->d.Rpos)) || (rc = upload(s, Rend, &s->d.Rend)) || (rc = upload(s, hperm, &cperm))) return rc;
+    if ((rc = upload(s, P.cols.order, &s->d.order)) || (rc = upload(s, P.A.Alp, &s->d.Alp)) || (rc = upload(s, P.A.Ali, &s->d.Ali)) || (rc = upload(s, P.A.Asrc, &s->d.Asrc)) ||
+        (rc = upload(s, P.L.Lp, &s->d.Lp)) || (rc = upload(s, P.L.Li, &s->d.Li)) || (rc = upload(s, P.R.Rp, &s->d.Rp)) || (rc = upload(s, P.R.Rk, &s->d.Rk)) ||
+        (rc = upload(s, P.R.Rpos, &s->d.Rpos)) || (rc = upload(s, P.R.Rend, &s->d.Rend)) || (rc = upload(s, hperm, &cperm))) return rc;
     s->d_perm = const_cast<int*>(cperm);
-    s->upd_total = use_mf ? upd_total : 0; s->panel_total = use_mf ? panel_total : 0;
-    s->mf = use_mf;
     if ((rc = alloc_values(s, 1))) return rc;
-    if (use_mf) {
-        s->mplan = mplan; s->nnodes = NN; s->max_front = max_front; s->panel_total = panel_total; s->usum = usum;
-        s->h_nfirst = m_first; s->h_ncols = m_cols; s->h_nrows = m_rows; s->h_rowptr = m_rowptr; s->h_rows = m_rowsv; s->h_panel_off = m_panel_off;
-        s->levels = mf_levels; s->widest = mf_widest;
+    if (s->mf) {
+        const MfPlan& M = *P.mf;
         MfDev& md = s->md;
-        md.nnodes = NN;
-        if ((rc = upload(s, m_order, &md.order)) || (rc = upload(s, m_first, &md.nfirst)) || (rc = upload(s, m_cols, &md.ncols)) || (rc = upload(s, m_rows, &md.nrows)) ||
-            (rc = upload(s, m_rowptr, &md.rowptr)) || (rc = upload(s, m_rowsv, &md.rows)) || (rc = upload(s, m_rel, &md.rel)) || (rc = upload(s, m_childptr, &md.childptr)) ||
-            (rc = upload(s, m_children, &md.children)) || (rc = upload(s, m_panel_off, &md.panel_off)) || (rc = upload(s, m_upd_off, &md.upd_off)) ||
-            (rc = upload(s, m_u_off, &md.u_off)) || (rc = upload(s, m_Aloc, &md.Aloc)) || (rc = upload(s, m_foff, &md.foff))) return rc;
-        {
-            std::vector<MfNode> nrec((size_t)NN);
-            std::vector<MfChild> crec;
-            std::vector<int> pos_of((size_t)NN, 0), ypan_of((size_t)NN, 0);
-            for (int pos = 0; pos < NN; ++pos) pos_of[(size_t)m_order[(size_t)pos]] = pos;
-            for (const MfSeg& g : mplan) for (int q = 0; q < g.count; ++q) ypan_of[(size_t)(g.first + q)] = g.ypan;
-            for (int pos = 0; pos < NN; ++pos) {
-                const int t = m_order[(size_t)pos];
-                MfNode& nd = nrec[(size_t)pos];
-                nd.s = t; nd.f = m_first[(size_t)t]; nd.c = m_cols[(size_t)t]; nd.r = m_rows[(size_t)t];
-                nd.rowptr = m_rowptr[(size_t)t]; nd.chfirst = (int)crec.size(); nd.nch = m_childptr[(size_t)t + 1] - m_childptr[(size_t)t];
-                nd.alp0 = (int)Alp[(size_t)nd.f]; nd.alp1 = (int)Alp[(size_t)(nd.f + nd.c)]; nd.pad0 = m_wbase.empty() ? -1 : m_wbase[(size_t)t];
-                nd.pad1 = m_parent[(size_t)t] >= 0 ? pos_of[(size_t)m_parent[(size_t)t]] : -1; nd.pad2 = ypan_of[(size_t)pos];
-                nd.panel_off = m_panel_off[(size_t)t]; nd.upd_off = m_upd_off[(size_t)t]; nd.u_off = m_u_off[(size_t)t]; nd.foff = m_foff.empty() ? 0 : m_foff[(size_t)t];
-                for (int q = m_childptr[(size_t)t]; q < m_childptr[(size_t)t + 1]; ++q) {
-                    const int ch = m_children[(size_t)q];
-                    crec.push_back({m_rows[(size_t)ch], m_rowptr[(size_t)ch], m_upd_off[(size_t)ch], m_u_off[(size_t)ch], pos_of[(size_t)ch], 0});
-                }
-            }
-            // extend-add items of the fronts that live in LDS (k_mf_factor's assembly): per node the entries of its children's update matrices, children ascending, a
-            // child's lower triangle row by row; not built when a node has more than 65535 children or the table would exceed 512 MiB (the row-wise loop then)
-            std::vector<MfXItem> xit;
-            {
-                std::vector<char> lds_front((size_t)NN, 0);
-                for (const MfSeg& g : mplan) for (int q = 0; q < g.count; ++q) lds_front[(size_t)(g.first + q)] = !g.global;
-                size_t total = 0; bool ok = true;
-                for (int pos = 0; pos < NN && ok; ++pos) {
-                    if (!lds_front[(size_t)pos]) continue;
-                    const int t = m_order[(size_t)pos];
-                    if (m_childptr[(size_t)t + 1] - m_childptr[(size_t)t] > 65535) ok = false;
-                    for (int q = m_childptr[(size_t)t]; q < m_childptr[(size_t)t + 1]; ++q) { const size_t rch = (size_t)m_rows[(size_t)m_children[(size_t)q]]; total += rch * (rch + 1) / 2; }
-                }
-                if (ok && g_mf_items && total <= ((size_t)512 << 20) / sizeof(MfXItem)) {
-                    xit.reserve(total + 1);
-                    for (int pos = 0; pos < NN; ++pos) {
-                        MfNode& nd = nrec[(size_t)pos];
-                        nd.xa0 = nd.xa1 = -1;
-                        if (!lds_front[(size_t)pos]) continue;
-                        const int t = m_order[(size_t)pos];
-                        nd.xa0 = (int)xit.size();
-                        for (int q = m_childptr[(size_t)t]; q < m_childptr[(size_t)t + 1]; ++q) {
-                            const int ch = m_children[(size_t)q], rch = m_rows[(size_t)ch];
-                            const int* rel = m_rel.data() + m_rowptr[(size_t)ch];
-                            const unsigned ord = (unsigned)(q - m_childptr[(size_t)t]);
-                            for (int a = 0; a < rch; ++a) for (int b = 0; b <= a; ++b)
-                                xit.push_back({(unsigned)(m_upd_off[(size_t)ch] + (long long)a * rch + b), (unsigned)(rel[a] * (rel[a] + 1) / 2 + rel[b]) | (ord << 16)});
-                        }
-                        nd.xa1 = (int)xit.size();
-                    }
-                    if (xit.empty()) xit.push_back({0u, 0u});
-                } else for (MfNode& nd : nrec) nd.xa0 = nd.xa1 = -1;
-            }
-            md.xit = nullptr;
-            if ((rc = upload(s, nrec, &md.nrec)) || (rc = upload(s, crec, &md.crec)) || (!xit.empty() && (rc = upload(s, xit, &md.xit)))) return rc;
-        }
-        s->pool_total = pool_total; s->wide_count = wide_count;
-        for (const MfSeg& g : mplan) if (g.wide.solve) s->wide_blocks = std::max(s->wide_blocks, (g.wide.r + WF_SOLVE_ROWS - 1) / WF_SOLVE_ROWS);
-        if (wide_count && ((rc = upload(s, w_ptrE, &md.wptrE)) || (rc = upload(s, w_ptrC, &md.wptrC)) || (rc = upload(s, w_Ecol, &md.wEcol)) ||
-                           (rc = upload(s, w_Esrc, &md.wEsrc)) || (rc = upload(s, w_C, &md.wC)))) return rc;
-        if ((rc = alloc_values(s, 1))) return rc;      // (again: now with the pool of the global-memory fronts)
-        for (const MfSeg& g : s->mplan) if (g.wide.on && !mf_wide_prepare(&s->err)) return CALIPSO_ERR_HIP;
+        md.nnodes = M.nnodes;
+        if ((rc = upload(s, M.order, &md.order)) || (rc = upload(s, M.first, &md.nfirst)) || (rc = upload(s, M.cols, &md.ncols)) || (rc = upload(s, M.rows, &md.nrows)) ||
+            (rc = upload(s, M.rowptr, &md.rowptr)) || (rc = upload(s, M.rowsv, &md.rows)) || (rc = upload(s, M.rel, &md.rel)) || (rc = upload(s, M.childptr, &md.childptr)) ||
+            (rc = upload(s, M.children, &md.children)) || (rc = upload(s, M.panel_off, &md.panel_off)) || (rc = upload(s, M.upd_off, &md.upd_off)) ||
+            (rc = upload(s, M.u_off, &md.u_off)) || (rc = upload(s, M.Aloc, &md.Aloc)) || (rc = upload(s, M.foff, &md.foff))) return rc;
+        md.xit = nullptr;
+        if ((rc = upload(s, M.nrec, &md.nrec)) || (rc = upload(s, M.crec, &md.crec)) || (!M.xit.empty() && (rc = upload(s, M.xit, &md.xit)))) return rc;
+        if (M.wide_count && ((rc = upload(s, M.wptrE, &md.wptrE)) || (rc = upload(s, M.wptrC, &md.wptrC)) || (rc = upload(s, M.wEcol, &md.wEcol)) ||
+                             (rc = upload(s, M.wEsrc, &md.wEsrc)) || (rc = upload(s, M.wC, &md.wC)))) return rc;
+        for (const MfSeg& g : M.levels) if (g.wide.on && !mf_wide_prepare(&s->err)) return CALIPSO_ERR_HIP;
         md.Alp = s->d.Alp; md.Asrc = s->d.Asrc;
         for (const void* fn : {(const void*)k_mf_factor<256, false>, (const void*)k_mf_factor<512, false>, (const void*)k_mf_forward<256, false>,
                                (const void*)k_mf_forward<512, false>, (const void*)k_mf_backward<256, false>, (const void*)k_mf_backward<512, false>})
-            PK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048));     // (k_mf_factor also holds 1 KiB of static LDS)
+            PK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LIMITS.lds_budget));     // (k_mf_factor also holds 1 KiB of static LDS)
     }
-    s->work_slots = std::min(widest, 2048);
+    s->work_slots = std::min(P.cols.widest, 2048);
     if (s->lds_acc) {
         PK(hipFuncSetAttribute((const void*)k_sp_factor<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * SP_LDS_MAX_N)));
     } else {
@@ -1489,7 +1172,8 @@ static int32_t sparse_create_impl(int64_t n, const int64_t* colptr, const int64_
 //         1 if the column accumulator lives in LDS]
 int32_t calipso_hip_sparse_info(calipso_hip_sparse* s, int64_t info[8]) {
     if (!s || !info) return CALIPSO_ERR_ARGUMENT;
-    info[0] = s->n; info[1] = s->nnzU; info[2] = s->nnzL; info[3] = s->levels; info[4] = s->mf ? (i64)s->mplan.size() : (i64)s->plan.size(); info[5] = s->widest; info[6] = s->flops; info[7] = s->mf ? 2 : (s->lds_acc ? 1 : 0);
+    const SparsePlan& P = s->plan;
+    info[0] = s->n; info[1] = P.A.nnzU; info[2] = P.L.nnzL; info[3] = P.levels(); info[4] = s->mf ? (i64)P.mf->levels.size() : (i64)P.cols.plan.size(); info[5] = P.widest(); info[6] = P.R.flops; info[7] = s->mf ? 2 : (s->lds_acc ? 1 : 0);
     return CALIPSO_OK;
 }
 
@@ -1515,10 +1199,10 @@ int32_t calipso_hip_sparse_select(calipso_hip_sparse* s, int64_t instance) {
 // nzval: batch x nnz(A) values in the caller's CSC order (host).  inertia: batch x 3 (may be NULL).  Returns CALIPSO_WARN_ZERO_PIVOT if any
 // matrix met an exact zero pivot (its inertia[0] = -1).
 static int32_t sparse_factorize(calipso_hip_sparse* s, const double* nzval, int64_t* inertia, hipMemcpyKind kind) {
-    if (!s || (!nzval && s->nnzA > 0)) return CALIPSO_ERR_ARGUMENT;
+    if (!s || (!nzval && s->plan.nnzA > 0)) return CALIPSO_ERR_ARGUMENT;
     PK(hipSetDevice(s->device));
     const size_t B = (size_t)s->batch;
-    if (s->nnzA) PK(hipMemcpyAsync(s->d_Aval, nzval, sizeof(double) * B * (size_t)s->nnzA, kind, s->stream));
+    if (s->plan.nnzA) PK(hipMemcpyAsync(s->d_Aval, nzval, sizeof(double) * B * (size_t)s->plan.nnzA, kind, s->stream));
     PK(hipEventRecord(s->e0, s->stream));
     if (!s->graph_tried) {          // the level schedule is a fixed launch sequence with fixed arguments: captured once, replayed afterwards
         s->graph_tried = true;
@@ -1578,7 +1262,7 @@ static int32_t sparse_solve(calipso_hip_sparse* s, int64_t nrhs, const double* b
     const unsigned gx = (unsigned)((s->n + 255) / 256), ny = (unsigned)cols;
     hipLaunchKernelGGL(k_sp_permute_in, dim3(gx, ny), dim3(256), 0, s->stream, s->d_rhs, s->d_perm, s->n, s->d_x);
     if (s->mf) {
-        const size_t need_u = (size_t)std::max<long long>(s->usum, 1) * cols;
+        const size_t need_u = (size_t)std::max<long long>(s->plan.mf->usum, 1) * cols;
         if (need_u > s->cap_uvec) {
             if (s->md.uvec) (void)hipFree(s->md.uvec);
             s->md.uvec = nullptr; s->cap_uvec = 0;
@@ -1590,11 +1274,11 @@ static int32_t sparse_solve(calipso_hip_sparse* s, int64_t nrhs, const double* b
     } else {
         for (int z = 0; z < s->batch; ++z) {
             SpDev d = s->d;
-            d.Lx += (size_t)z * (size_t)s->nnzL; d.D += (size_t)z * (size_t)s->n;
+            d.Lx += (size_t)z * (size_t)s->plan.L.nnzL; d.D += (size_t)z * (size_t)s->n;
             double* xz = s->d_x + (size_t)z * (size_t)nrhs * (size_t)s->n;
-            for (const Segment& g : s->plan)
+            for (const Segment& g : s->plan.cols.plan)
                 hipLaunchKernelGGL(k_sp_forward, dim3(g.chain ? 1 : (unsigned)std::min(g.count, 4096), (unsigned)nrhs), dim3(64), 0, s->stream, d, g.first, g.count, xz);
-            for (auto g = s->plan.rbegin(); g != s->plan.rend(); ++g)
+            for (auto g = s->plan.cols.plan.rbegin(); g != s->plan.cols.plan.rend(); ++g)
                 hipLaunchKernelGGL(k_sp_backward, dim3(g->chain ? 1 : (unsigned)std::min(g->count, 4096), (unsigned)nrhs), dim3(64), 0, s->stream, d, g->first, g->count, xz);
         }
     }
@@ -1616,27 +1300,30 @@ int32_t calipso_hip_sparse_get_factor(calipso_hip_sparse* s, int64_t* perm, int6
     if (!s) return CALIPSO_ERR_ARGUMENT;
     if ((Lx || D) && !s->factored) { s->err = "calipso_hip_sparse_get_factor: factorize first"; return CALIPSO_ERR_ARGUMENT; }
     PK(hipSetDevice(s->device));
-    if (perm) std::copy(s->perm.begin(), s->perm.end(), perm);
-    if (Lp) for (size_t k = 0; k < s->hLp.size(); ++k) Lp[k] = (i64)s->hLp[k] + 1;
-    if (Li) for (size_t k = 0; k < s->hLi.size(); ++k) Li[k] = (i64)s->hLi[k] + 1;
-    if (Lx && s->nnzL && s->mf) {
+    const std::vector<int>&hLp = s->plan.L.Lp, &hLi = s->plan.L.Li;
+    const size_t nnzL = (size_t)s->plan.L.nnzL;
+    if (perm) std::copy(s->plan.perm.begin(), s->plan.perm.end(), perm);
+    if (Lp) for (size_t k = 0; k < hLp.size(); ++k) Lp[k] = (i64)hLp[k] + 1;
+    if (Li) for (size_t k = 0; k < hLi.size(); ++k) Li[k] = (i64)hLi[k] + 1;
+    if (Lx && nnzL && s->mf) {
         // multifrontal storage: dense m x c panels per node; pick the entries of the exact pattern out of them
-        std::vector<double> panel((size_t)s->panel_total);
-        PK(hipMemcpyAsync(panel.data(), s->md.panel + (size_t)s->selected * (size_t)s->panel_total, sizeof(double) * panel.size(), hipMemcpyDeviceToHost, s->stream));
+        const MfPlan& M = *s->plan.mf;
+        std::vector<double> panel((size_t)M.panel_total);
+        PK(hipMemcpyAsync(panel.data(), s->md.panel + (size_t)s->selected * (size_t)M.panel_total, sizeof(double) * panel.size(), hipMemcpyDeviceToHost, s->stream));
         PK(hipStreamSynchronize(s->stream));
-        for (int t = 0; t < s->nnodes; ++t) {
-            const int f = s->h_nfirst[(size_t)t], c = s->h_ncols[(size_t)t], m = c + s->h_nrows[(size_t)t];
-            const int* Rb = s->h_rows.data() + s->h_rowptr[(size_t)t]; const int* Re = Rb + s->h_nrows[(size_t)t];
-            const double* Pn = panel.data() + s->h_panel_off[(size_t)t];
+        for (int t = 0; t < M.nnodes; ++t) {
+            const int f = M.first[(size_t)t], c = M.cols[(size_t)t], m = c + M.rows[(size_t)t];
+            const int* Rb = M.rowsv.data() + M.rowptr[(size_t)t]; const int* Re = Rb + M.rows[(size_t)t];
+            const double* Pn = panel.data() + M.panel_off[(size_t)t];
             for (int j = f; j < f + c; ++j)
-                for (int q = s->hLp[(size_t)j]; q < s->hLp[(size_t)j + 1]; ++q) {
-                    const int i = s->hLi[(size_t)q];
+                for (int q = hLp[(size_t)j]; q < hLp[(size_t)j + 1]; ++q) {
+                    const int i = hLi[(size_t)q];
                     const int lr = i < f + c ? i - f : c + (int)(std::lower_bound(Rb, Re, i) - Rb);
                     Lx[q] = Pn[(size_t)lr + (size_t)(j - f) * m];
                 }
         }
     } else
-    if (Lx && s->nnzL) PK(hipMemcpyAsync(Lx, s->d.Lx + (size_t)s->selected * (size_t)s->nnzL, sizeof(double) * (size_t)s->nnzL, hipMemcpyDeviceToHost, s->stream));
+    if (Lx && nnzL) PK(hipMemcpyAsync(Lx, s->d.Lx + (size_t)s->selected * nnzL, sizeof(double) * nnzL, hipMemcpyDeviceToHost, s->stream));
     if (D) PK(hipMemcpyAsync(D, s->d.D + (size_t)s->selected * (size_t)s->n, sizeof(double) * (size_t)s->n, hipMemcpyDeviceToHost, s->stream));
     PK(hipStreamSynchronize(s->stream));
     return CALIPSO_OK;

@@ -25,11 +25,11 @@ constexpr int WF_UPDATE_LDS = 3 * 64 * WF_LDT * (int)sizeof(double);
 constexpr int WF_DIAG_LDS = calipso::DIAG_LDS_DOUBLES * (int)sizeof(double);
 constexpr int WF_ROWS = 4;                                           // rows of a front per k_wf_assemble workgroup (a wavefront each); fewer where 4 rows exceed the LDS
 constexpr int WF_ASSEMBLE_LDS = 160 * 1024 - 2048;
-constexpr int WF_SOLVE_ROWS = 1024;                                  // rows of L21 per workgroup of the backward sweep's partial products
+constexpr int WF_SOLVE_ROWS = LIMITS.wf_solve_rows;                  // rows of L21 per workgroup of the backward sweep's partial products
 // scratch of one (node of the level, matrix): X | M | L11 (64 x 64 column-major each) | D (64) | counters
 constexpr int WF_SCR_X = 0, WF_SCR_M = 4096, WF_SCR_L = 8192, WF_SCR_D = 12288, WF_SCR_I = 12352, WF_SCR = 12416;
 
-__device__ __forceinline__ int wf_tri(int i) { return (i * (i + 1)) >> 1; }                 // m <= MF_MAX_FRONT_WIDE: fits 31 bits
+__device__ __forceinline__ int wf_tri(int i) { return (i * (i + 1)) >> 1; }                 // m <= Limits::max_front_wide: fits 31 bits
 __device__ __forceinline__ size_t wf_slot(const MfSlots& sl) { return sl.use ? (size_t)sl.slot[blockIdx.z] : (size_t)blockIdx.z; }
 __device__ __forceinline__ double* wf_scratch(const MfDev& d) { return d.wscr + ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * WF_SCR; }
 
@@ -211,9 +211,7 @@ __global__ __launch_bounds__(256) void k_wf_update(const MfDev d, const MfSlots 
     }
 }
 
-// what a level's launches must cover (maxima over its nodes)
-struct MfWide { int on = 0; int m = 0, r = 0, nch = 0; int solve = 0; };   // solve: the sweeps of this level by many workgroups too (measured cross-over: ~2200 rows, or many children per node)
-
+// (what a level's launches must cover, maxima over its nodes: MfWide of sparse_plan.hpp)
 inline bool mf_wide_prepare(std::string* err) {
     if (!calipso::lds_attribute((const void*)k_wf_update, WF_UPDATE_LDS) || !calipso::lds_attribute((const void*)k_wf_diag, WF_DIAG_LDS) ||
         !calipso::lds_attribute((const void*)k_wf_assemble, WF_ASSEMBLE_LDS)) {

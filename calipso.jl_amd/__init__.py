@@ -511,6 +511,13 @@ class Solver(_Handle):
         self._check(self._L.calipso_hip_schedule_info(self._h, _pd(out)), "schedule_info")
         return dict(prologue_ahead_steps=int(out[0]), last_prologue_mode=int(out[1]), ahead_undone=int(out[2]))
 
+    def schur_cache_info(self):
+        """the cache of the Schur complement's equality products on a handle with an attached QP (calipso_hip_schur_cache_info): dict(captures: factorisations that
+        stored the products, hits: that started from the stored ones, bypasses: that could have used the cache and went without, bytes: of the buffer); zeros: no cache"""
+        out = np.zeros(4)
+        self._check(self._L.calipso_hip_schur_cache_info(self._h, _pd(out)), "schur_cache_info")
+        return dict(captures=int(out[0]), hits=int(out[1]), bypasses=int(out[2]), bytes=int(out[3]))
+
     def padded_nx(self):
         return int(self.kernel_times()[2])
 

@@ -391,6 +391,7 @@ static bool find_field(H* s, const std::string& name, Field& f) {
                 {"opt.max_residual_line_search", &o.max_residual_line_search}, {"opt.max_cone_line_search", &o.max_cone_line_search},
                 {"opt.iterative_refinement", &o.iterative_refinement}, {"opt.max_iterative_refinement", &o.max_iterative_refinement},
                 {"opt.min_iterative_refinement", &o.min_iterative_refinement}, {"opt.solve_block", &s->solve_block}, {"opt.solve_wform", &s->solve_wform},
+                {"opt.schur_cache", &s->schur_cache},
                 {"opt.differentiate_refinement", &s->differentiate_refinement}};
     for (auto& io : ios)
         if (name == io.n) { f.host = (double*)io.p; f.len = -1; return true; }   // len -1 marks an int64 slot
@@ -420,6 +421,10 @@ int32_t calipso_hip_set_field(H* s, const char* name, const double* data, int64_
             if (v != 0 && v != 1) return fail_arg(s, "opt.solve_wform must be 0 or 1");
             if (v != s->solve_wform) { CK(hipSetDevice(s->device)); CK(hipStreamSynchronize(s->stream)); calipso::ldl_drop_graphs(s); }
         }
+        if (nm == "opt.schur_cache") {            // not an option of the reference either: the equality products of S kept across an attached QP's factorisations (lfac.hip)
+            if ((v != 0 && v != 1) || data[0] != (double)v) return fail_arg(s, "opt.schur_cache must be 0 or 1");
+            calipso::lfac_cache_drop(s);
+        }
         // not an option of the reference either: correction rounds on the columns of differentiate! (calipso_hip_differentiate)
         if (nm == "opt.differentiate_refinement" && ((v != 0 && v != 1) || data[0] != (double)v)) return fail_arg(s, "opt.differentiate_refinement must be 0 or 1");
         *(calipso::i64*)f.host = v;
@@ -443,6 +448,7 @@ int32_t calipso_hip_set_field(H* s, const char* name, const double* data, int64_
         CK(hipMemcpyAsync(f.dev, data, sizeof(double) * len, hipMemcpyHostToDevice, s->stream));
     if (nm == "parameters") s->hparams.assign(data, data + len);
     if (nm == "lagrangian_hessian") s->hessian_dirty = true;
+    if (nm == "equality_jacobian_variables") s->gx_version += 1;
     // an analysed stage-banded structure (structure.hip) is a promise about where these three blocks are non-zero: re-check it
     // on the device against what was just uploaded; a block that breaks it sends the handle back to the dense treatment
     if (structure_active(s) && (nm == "lagrangian_hessian" || nm == "equality_jacobian_variables" || nm == "cone_jacobian_variables")) {
@@ -738,6 +744,7 @@ static int do_factorize(H* s, int64_t inertia[3], bool rhs_ahead_ok = false) {
         SYNC();
         factor_times(s);
     }
+    if (s->lfac_last) calipso::lfac_cache_commit(s);      // the factorisation completed, whatever its inertia: what a capture run stored is the cached entry from here on
     s->stats.factorizations += 1;
     s->phase_ms[8] += 1.0;
     const int64_t pos = s->hicount[0] + s->hicount[3], nonpos = s->hicount[1] + s->hicount[4], zero = s->hicount[2] + s->hicount[5];
@@ -1309,7 +1316,7 @@ int32_t calipso_hip_set_device_evaluator(H* s, calipso_device_eval_fn fn, void* 
     if (!s) return CALIPSO_ERR_ARGUMENT;
     // (a structured handle holds no dense ProblemData arrays: the evaluator then writes into dense scratch arrays of the handle — allocated on its first evaluation:
     // nx^2 + (ne + nc) nx doubles — whose entries go into the blocks behind it; what lies outside the declared structure must be zero: device_evaluate checks)
-    s->dev_eval = fn; s->dev_eval_user = user;
+    s->dev_eval = fn; s->dev_eval_user = user; s->gx_version += 1;
     if (fn) s->dev_block_eval = nullptr;
     return CALIPSO_OK;
 }
@@ -1317,7 +1324,7 @@ int32_t calipso_hip_set_device_evaluator(H* s, calipso_device_eval_fn fn, void* 
 int32_t calipso_hip_set_device_block_evaluator(H* s, calipso_device_block_eval_fn fn, void* user) {
     if (!s) return CALIPSO_ERR_ARGUMENT;
     if (!s->compact) return fail_arg(s, "calipso_hip_set_device_block_evaluator: only a structured handle (calipso_hip_create_structured) has blocks to write");
-    s->dev_block_eval = fn; s->dev_block_eval_user = user;
+    s->dev_block_eval = fn; s->dev_block_eval_user = user; s->gx_version += 1;
     if (fn) s->dev_eval = nullptr;
     return CALIPSO_OK;
 }
@@ -1497,6 +1504,7 @@ int32_t calipso_hip_qp_attach(H* s, const double* P, const double* q, const doub
     const Dims& d = s->d;
     if ((d.ne && (!A || !b)) || (d.nc && (!G || !h))) return CALIPSO_ERR_ARGUMENT;
     CK(hipSetDevice(s->device));
+    s->gx_version += 1;         // gx is rewritten (also by an attach that fails half way): nothing cached from the old one is used again
     if (s->compact) {
         // structured handle: Lxx = 2c P, gx = A, hx = -G straight into the blocks (packed on the host; entries outside the declared structure are an error)
         int rc = blocks_upload_dense(s, 0, P, 2.0 * objective_scale);
@@ -1625,6 +1633,14 @@ int32_t calipso_hip_kernel_times(H* s, double out[8]) {
 int32_t calipso_hip_schedule_info(H* s, double out[4]) {
     if (!s || !out) return CALIPSO_ERR_ARGUMENT;
     out[0] = (double)s->prologue_ahead_steps; out[1] = (double)s->last_prologue_mode; out[2] = (double)s->ahead_undone; out[3] = 0.0;
+    return CALIPSO_OK;
+}
+
+// The cache of the Schur complement's equality products (lfac.hip: LfacAux): factorisations so far that [0] stored the products, [1] started from the stored ones,
+// [2] could have used the cache and went without (another regularisation than IC-1's), [3] bytes of the buffer.  All zero where the cache is off.
+int32_t calipso_hip_schur_cache_info(H* s, double out[4]) {
+    if (!s || !out) return CALIPSO_ERR_ARGUMENT;
+    calipso::lfac_cache_info(s, out);
     return CALIPSO_OK;
 }
 

@@ -273,6 +273,8 @@ struct calipso_hip_solver {
     void* lfac_aux = nullptr;     // lfac.hip: plan and buffers of the left-looking schedule (one dense system alone)
     bool lfac_last = false;       // the last blocked factorisation took it
     bool lfac_failed = false;     // its buffers could not be had: the handle keeps k_schur + the right-looking panel steps
+    calipso::i64 schur_cache = 1; // "opt.schur_cache": an attached QP's factorisations reuse the equality products of the Schur complement (lfac.hip: LfacAux).  Not an option of the reference.
+    unsigned long long gx_version = 0;   // bumped by everything that can write the equality rows of Z (part of the cache's key)
     double* Lf = nullptr;         // where the factor columns L of the last blocked factorisation live: S (scaled in place) or lfac.hip's buffer
     double* Hdense = nullptr; int* lu_ipiv = nullptr;   // fallback.hip: N x N unreduced matrix and pivots (allocated on first use)
     hipEvent_t ev[16];
@@ -403,6 +405,9 @@ bool wform_on(const calipso_hip_solver* s);                    // the solves of 
 bool lfac_on(const calipso_hip_solver* s);
 bool lfac_ready(calipso_hip_solver* s);          // lfac_on, and the plan / buffers exist
 int lfac_enqueue(calipso_hip_solver* s, unsigned long long* hprog, unsigned long long epoch);   // returns the launches queued (0: not available)
+void lfac_cache_commit(calipso_hip_solver* s);   // the factorisation lfac_enqueue queued last has completed: a capture run's E becomes the cached entry
+void lfac_cache_drop(calipso_hip_solver* s);
+void lfac_cache_info(calipso_hip_solver* s, double out[4]);
 double* lfac_factor_buffer(calipso_hip_solver* s);
 void lfac_release(calipso_hip_solver* s);
 void lfac_describe(calipso_hip_solver* s, double out[8]);

@@ -29,6 +29,7 @@
 #include <atomic>
 #include <chrono>
 #include <cstdio>
+#include <cstring>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -44,13 +45,14 @@ constexpr int LFAC_LDS_DOUBLES = 4 * TT * LDT > DIAG_LDS_DOUBLES ? 4 * TT * LDT 
 static_assert(6 * TT * LLDK <= LFAC_LDS_DOUBLES, "Schur stage buffers (a ring of three)");
 
 enum { LI_SCHUR = 0, LI_FAR = 1, LI_ROW = 2 };
-struct LItem { short kind, i, j, a, b, c, pad0, pad1; };     // SCHUR: tile (i, j), stages [a, b), c bit 0: first slice, bit 1: last (epilogue); FAR: tile (i, j), panels [a, b); ROW: row i, panel j, pending panels of tile (i, j + 2) from a
+struct LItem { short kind, i, j, a, b, c, pad0, pad1; };     // SCHUR: tile (i, j), stages [a, b), c bit 0: first slice, bit 1: last (epilogue), bit 2: the first slice starts from E (the cached plan); FAR: tile (i, j), panels [a, b); ROW: row i, panel j, pending panels of tile (i, j + 2) from a
 
 struct LfacArgs {
     int NP, nx, m, ne, nc, tb;
     int k;                  // launch: -2 head, -1 diagonal block 0, k >= 0 panel k
     int nst0, nst;          // Schur stages: equality rows, all
-    double *S, *Zbuf, *Minv, *Dx, *Tinv;
+    int cut, capture;       // the accumulators after `cut` stages rest in E; capture: a slice that passes stage `cut` stores its accumulator there (the full plan of a capture run)
+    double *S, *Zbuf, *Minv, *Dx, *Tinv, *E;
     const double *Lsym, *Zj, *WH;      // Zj = [gx; hx] (leading dimension m), WH = Omega_z hx (leading dimension nc)
     int* icount;
     const LItem* items; const int* wfirst;
@@ -75,9 +77,10 @@ __device__ __forceinline__ void item_schur(const LfacArgs& a, const LItem it, co
     const int offC = (wr * 16 + L.fr) + (L.wc * 16 + L.fk) * a.NP;
     double* T = a.S + (i0 + (size_t)j0 * a.NP);
     v4d acc = (v4d){0.0, 0.0, 0.0, 0.0};
-    if (mf && !(it.c & 1)) {
+    if (mf && (it.c & 5) != 1) {          // a later slice: what the one before left in S; the first slice of the cached plan: what a capture run left in E after stage cut - 1
+        const double* src = (it.c & 4) ? a.E + (i0 + (size_t)j0 * a.NP) : T;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) acc[r] = T[offC + 4 * r * a.NP];
+        for (int r = 0; r < 4; ++r) acc[r] = src[offC + 4 * r * a.NP];
     }
     // the accumulator has ARRIVED before the stage loop starts: left pending, its first use inside the loop makes the compiler wait for every outstanding load in every
     // stage (s_waitcnt vmcnt(0) in front of the first matrix instruction) — the operands just requested for two stages ahead included, 1.4 us per stage
@@ -116,7 +119,10 @@ __device__ __forceinline__ void item_schur(const LfacArgs& a, const LItem it, co
     // first half of the fragments of stage s + 1 — parked during stage s - 1, visible since the barrier that ended it — is read BEFORE the barrier that ends stage s,
     // under the last matrix instructions of the stage: the next stage's matrix instructions start right behind the barrier instead of behind a round of LDS reads
     // (bench/lfac_item_bench.hip: 1.63 -> 1.43 us per stage).  The arithmetic per entry is untouched.
-    const int s0 = it.a, s1 = it.b;
+    // A capture run cuts a slice that passes stage `cut` in two runs of the pipeline, [a, cut) and [cut, b), and stores the accumulator to E between them: the ring is
+    // primed again, every entry still sees the same matrix instructions on the same operands in the same order
+    const bool cap = a.capture != 0 && it.a < a.cut && a.cut <= it.b;
+    int s0 = it.a, s1 = cap ? a.cut : it.b;
     double fa[8], fb[8];
     auto reads = [&](int buf, int half) {          // fragments 4 half .. 4 half + 3 of the stage in buffer buf
         const unsigned ab = (unsigned)(uintptr_t)(smem + (size_t)buf * 2 * TT * LLDK + (wr * 16 + L.fr) * LLDK + L.fk);
@@ -135,52 +141,63 @@ __device__ __forceinline__ void item_schur(const LfacArgs& a, const LItem it, co
             }
         }
     };
-    if (s1 > s0) {
-        fetch(s0, 0);
-        if (s0 + 1 < s1) fetch(s0 + 1, 1);
-        park(0, 0, s0);
-        if (s0 + 1 < s1) park(1, 1, s0 + 1);
-        if (s0 + 2 < s1) fetch(s0 + 2, 0);
-        if (s0 + 3 < s1) fetch(s0 + 3, 1);
-    }
-    lds_barrier();
-    if (mf && s1 > s0) reads(0, 0);
-    // one stage; u = (stage - s0) mod 6 picks the buffer (u mod 3) and the register set (u mod 2): the loop is unrolled by six so that both are static.  inner: at
-    // least four more stages behind it — no conditions around its requests (the bulk of the loop is straight-line code)
-    auto stage = [&](int st, auto uc, auto inner) {
-        constexpr int u = decltype(uc)::value, buf = u % 3, set = u & 1;
-        if (mf) {
-            reads(buf, 1);
-            asm volatile("s_waitcnt lgkmcnt(8)" : "+v"(fa[0]), "+v"(fb[0]), "+v"(fa[1]), "+v"(fb[1]), "+v"(fa[2]), "+v"(fb[2]), "+v"(fa[3]), "+v"(fb[3]) :: "memory");
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(fb[kk], fa[kk], acc, 0, 0, 0);
-        }
-        if (decltype(inner)::value || st + 2 < s1) park((u + 2) % 3, set, st + 2);      // (its buffer held stage st - 1: every wavefront is past the barrier behind that stage)
-        if (decltype(inner)::value || st + 4 < s1) fetch(st + 4, set);
-        if (mf) {
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fa[4]), "+v"(fb[4]), "+v"(fa[5]), "+v"(fb[5]), "+v"(fa[6]), "+v"(fb[6]), "+v"(fa[7]), "+v"(fb[7]) :: "memory");
-            // (the first half's registers are free: the matrix instructions that read them issued long ago — the pattern of frag_product's ring)
-            if (decltype(inner)::value || st + 1 < s1) reads((u + 1) % 3, 0);
-#pragma unroll
-            for (int kk = 4; kk < 8; ++kk) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(fb[kk], fa[kk], acc, 0, 0, 0);
+#pragma unroll 1
+    for (int run = 0;; ++run) {
+        if (s1 > s0) {
+            fetch(s0, 0);
+            if (s0 + 1 < s1) fetch(s0 + 1, 1);
+            park(0, 0, s0);
+            if (s0 + 1 < s1) park(1, 1, s0 + 1);
+            if (s0 + 2 < s1) fetch(s0 + 2, 0);
+            if (s0 + 3 < s1) fetch(s0 + 3, 1);
         }
         lds_barrier();
-    };
-    int st = s0;
+        if (mf && s1 > s0) reads(0, 0);
+        // one stage; u = (stage - s0) mod 6 picks the buffer (u mod 3) and the register set (u mod 2): the loop is unrolled by six so that both are static.  inner: at
+        // least four more stages behind it — no conditions around its requests (the bulk of the loop is straight-line code)
+        auto stage = [&](int st, auto uc, auto inner) {
+            constexpr int u = decltype(uc)::value, buf = u % 3, set = u & 1;
+            if (mf) {
+                reads(buf, 1);
+                asm volatile("s_waitcnt lgkmcnt(8)" : "+v"(fa[0]), "+v"(fb[0]), "+v"(fa[1]), "+v"(fb[1]), "+v"(fa[2]), "+v"(fb[2]), "+v"(fa[3]), "+v"(fb[3]) :: "memory");
+#pragma unroll
+                for (int kk = 0; kk < 4; ++kk) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(fb[kk], fa[kk], acc, 0, 0, 0);
+            }
+            if (decltype(inner)::value || st + 2 < s1) park((u + 2) % 3, set, st + 2);      // (its buffer held stage st - 1: every wavefront is past the barrier behind that stage)
+            if (decltype(inner)::value || st + 4 < s1) fetch(st + 4, set);
+            if (mf) {
+                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fa[4]), "+v"(fb[4]), "+v"(fa[5]), "+v"(fb[5]), "+v"(fa[6]), "+v"(fb[6]), "+v"(fa[7]), "+v"(fb[7]) :: "memory");
+                // (the first half's registers are free: the matrix instructions that read them issued long ago — the pattern of frag_product's ring)
+                if (decltype(inner)::value || st + 1 < s1) reads((u + 1) % 3, 0);
+#pragma unroll
+                for (int kk = 4; kk < 8; ++kk) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(fb[kk], fa[kk], acc, 0, 0, 0);
+            }
+            lds_barrier();
+        };
+        int st = s0;
 #pragma unroll 1
-    for (; st + 9 < s1; st += 6) {
-        stage(st, std::integral_constant<int, 0>(), std::true_type()); stage(st + 1, std::integral_constant<int, 1>(), std::true_type());
-        stage(st + 2, std::integral_constant<int, 2>(), std::true_type()); stage(st + 3, std::integral_constant<int, 3>(), std::true_type());
-        stage(st + 4, std::integral_constant<int, 4>(), std::true_type()); stage(st + 5, std::integral_constant<int, 5>(), std::true_type());
-    }
+        for (; st + 9 < s1; st += 6) {
+            stage(st, std::integral_constant<int, 0>(), std::true_type()); stage(st + 1, std::integral_constant<int, 1>(), std::true_type());
+            stage(st + 2, std::integral_constant<int, 2>(), std::true_type()); stage(st + 3, std::integral_constant<int, 3>(), std::true_type());
+            stage(st + 4, std::integral_constant<int, 4>(), std::true_type()); stage(st + 5, std::integral_constant<int, 5>(), std::true_type());
+        }
 #pragma unroll 1
-    for (; st < s1; st += 6) {
-        stage(st, std::integral_constant<int, 0>(), std::false_type());
-        if (st + 1 < s1) stage(st + 1, std::integral_constant<int, 1>(), std::false_type());
-        if (st + 2 < s1) stage(st + 2, std::integral_constant<int, 2>(), std::false_type());
-        if (st + 3 < s1) stage(st + 3, std::integral_constant<int, 3>(), std::false_type());
-        if (st + 4 < s1) stage(st + 4, std::integral_constant<int, 4>(), std::false_type());
-        if (st + 5 < s1) stage(st + 5, std::integral_constant<int, 5>(), std::false_type());
+        for (; st < s1; st += 6) {
+            stage(st, std::integral_constant<int, 0>(), std::false_type());
+            if (st + 1 < s1) stage(st + 1, std::integral_constant<int, 1>(), std::false_type());
+            if (st + 2 < s1) stage(st + 2, std::integral_constant<int, 2>(), std::false_type());
+            if (st + 3 < s1) stage(st + 3, std::integral_constant<int, 3>(), std::false_type());
+            if (st + 4 < s1) stage(st + 4, std::integral_constant<int, 4>(), std::false_type());
+            if (st + 5 < s1) stage(st + 5, std::integral_constant<int, 5>(), std::false_type());
+        }
+        if (!cap || run == 1) break;
+        if (mf) {
+            double* Et = a.E + (i0 + (size_t)j0 * a.NP);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) Et[offC + 4 * r * a.NP] = acc[r];
+        }
+        if (a.cut == it.b) break;
+        s0 = a.cut; s1 = it.b;
     }
     if (!mf) return;
     if (it.c & 2) {
@@ -363,6 +380,7 @@ __global__ __launch_bounds__(TR_THREADS) void k_lfac(const LfacArgs a) {
 // ---- the plan (host, once per shape) -------------------------------------------------------------------------------------------------
 struct LfacPlan {
     int nblk = 0, nst0 = 0, nst = 0, W = 0;
+    int first = 0;                          // the stage every real tile starts at (0: the full plan; cut: the cached plan, whose first slices start from E)
     std::vector<int> item0;                 // per launch (index = k + 2): offset of its (W + 1) worker offsets in wfirst
     std::vector<LItem> items;
     std::vector<int> wfirst;
@@ -378,7 +396,22 @@ struct LfacAux {
     double *Zbuf = nullptr, *Lfac = nullptr;
     LItem* d_items = nullptr; int* d_wfirst = nullptr;
     double plan_ms = 0.0;                   // host time of the plan scan this handle paid (0: the shape's plan was in the process-wide cache)
+    // The equality products of the Schur complement, kept across factorisations: the accumulator of every tile after its first `cut` stages is a function
+    // of gx and omega_y = f(rho, ep, ed) alone.  A QP's gx is installed once and every IC-1 starts from the same (ep, ed), so a capture run of the full plan leaves those
+    // accumulators in E and the later factorisations with the same key run planE, whose first slices start from E at stage `cut` — the same matrix instructions on
+    // the same operands in the same order for every entry of S, so not a bit moves.
+    bool cache_tried = false;               // planE / E were asked for (on the first eligible factorisation); E == nullptr afterwards: the cache is off for this handle
+    int cut = 0;
+    LfacPlan planE;
+    double* E = nullptr;                    // NP x NP, S's layout
+    LItem* d_itemsE = nullptr; int* d_wfirstE = nullptr;
+    bool valid = false, pending = false;    // pending: a capture run is queued; lfac_cache_commit makes it the entry once the host knows the factorisation completed
+    std::array<unsigned long long, 4> key{}, pkey{};      // {gx_version, bits of rho, ep, ed}
+    long long captures = 0, hits = 0, bypasses = 0;
 };
+// the stage after which the accumulators are kept: the equality stages, but never the last stage of all (nc = 0) — a tile with no stage left would get no item and
+// so no epilogue (+ Lsym, + ep)
+static int lfac_cut(int nst0, int nst) { return std::min(nst0, nst - 1); }
 
 // cost model (microseconds on one compute unit while the whole chip is busy: the fp64 matrix cores sustain ~41 TFLOP/s on real data, 161 GFLOP/s per unit — a
 // 64 x 64 x 64 product 3.3 us, a Schur stage 1.64 us; bench/lfac_item_bench.hip): what balances the workers of a launch against the chain's workgroup
@@ -391,12 +424,15 @@ static double cost_row_half(int pending, bool second) { return second ? 11.0 + 2
 static int stages_within(double us, int P = 1) { const int n = (int)((us - 3.3) / (P == 1 ? 1.52 : P == 2 ? 1.05 : 0.8)); return n < 1 ? 1 : n; }
 
 // budget: the duration (us) a panel launch should have — the chain's workgroup takes ~19; head: the duration of launch -2 (0: long enough for whole tiles)
-static bool lfac_make_plan(LfacPlan& P, int nblk, int nx, int ne, int nc, int W, double budget, double head, int margin = 1 << 20) {
+// first: the stage the tiles start at (0 < first < nst: the equality stages [0, first) are not planned — their sum is read from E, lfac_cut)
+static bool lfac_make_plan(LfacPlan& P, int nblk, int nx, int ne, int nc, int W, double budget, double head, int margin = 1 << 20, int first = 0) {
     P = LfacPlan();
-    P.nblk = nblk; P.W = W; P.budget = budget;
+    P.nblk = nblk; P.W = W; P.budget = budget; P.first = first;
     P.nst0 = (ne + LKT - 1) / LKT; P.nst = P.nst0 + (nc + LKT - 1) / LKT;
     const int nst = P.nst;
-    if (head <= 0.0) head = std::min(cost_schur(nst), 120.0);
+    if (first < 0 || (first > 0 && first >= nst)) return false;
+    const short c_first = (short)(first > 0 ? 5 : 1);      // LItem::c of a tile's first slice
+    if (head <= 0.0) head = std::min(cost_schur(nst - first), 120.0);
     struct Tile { int st = 0, pn = 0; };
     std::vector<Tile> tiles((size_t)nblk * nblk);
     auto T = [&](int i, int j) -> Tile& { return tiles[(size_t)i * nblk + j]; };
@@ -404,6 +440,7 @@ static bool lfac_make_plan(LfacPlan& P, int nblk, int nx, int ne, int nc, int W,
     std::vector<std::pair<int, int>> order;         // candidates in the order of their deadlines (column-major)
     for (int j = 0; j < nblk; ++j) for (int i = j; i < nblk; ++i) {
         order.push_back({i, j});
+        T(i, j).st = first;
         if (i * TT >= nx) T(i, j).st = nst;         // rows of the padding only: launch_scale_rows / launch_pad_identity wrote the unit pivots, nothing to accumulate
     }
     for (int ell = -2; ell <= nblk - 2; ++ell) {
@@ -486,7 +523,7 @@ static bool lfac_make_plan(LfacPlan& P, int nblk, int nx, int ne, int nc, int W,
                 const int n = std::min(R, stages_within(len, split));
                 for (int part = 0; part < split; ++part) {
                     LItem it{}; it.kind = LI_SCHUR; it.i = (short)c.i; it.j = (short)c.j; it.a = (short)t.st; it.b = (short)(t.st + n);
-                    it.c = (short)((t.st == 0 ? 1 : 0) | (t.st + n == nst ? 2 : 0));
+                    it.c = (short)((t.st == first ? c_first : 0) | (t.st + n == nst ? 2 : 0));
                     it.pad0 = (short)split; it.pad1 = (short)part;
                     its.push_back({cost_schur(n, split), it}); used += cost_schur(n, split);
                 }
@@ -508,7 +545,7 @@ static bool lfac_make_plan(LfacPlan& P, int nblk, int nx, int ne, int nc, int W,
                 Tile& t = T(c.first, c.second);
                 const int n = std::min(nst - t.st, stages_within(room));
                 LItem it{}; it.kind = LI_SCHUR; it.i = (short)c.first; it.j = (short)c.second; it.a = (short)t.st; it.b = (short)(t.st + n);
-                it.c = (short)((t.st == 0 ? 1 : 0) | (t.st + n == nst ? 2 : 0));
+                it.c = (short)((t.st == first ? c_first : 0) | (t.st + n == nst ? 2 : 0));
                 it.pad0 = 1; it.pad1 = 0;
                 t.st += n;
                 its.push_back({cost_schur(n), it}); used += cost_schur(n);
@@ -589,7 +626,7 @@ static double lfac_plan_estimate(const LfacPlan& P) {
 }
 // The launch length (budget) and the head are chosen by the model (it reproduces the measured timeline within a few percent: profiles/r05_lfac_timeline.txt): a scan
 // of both (a fixed pair can be tried through calipso_hip_debug_lfac_plan / bench/lfac_plan.py).  The planner costs a few milliseconds per candidate, once per handle.
-static bool lfac_scan_plans(LfacPlan& best, int nblk, int nx, int ne, int nc, int W) {
+static bool lfac_scan_plans(LfacPlan& best, int nblk, int nx, int ne, int nc, int W, int first = 0) {
     // (a candidate costs ~ nblk^2 microseconds of host time: 630 of them are 0.4 s at C3's 40 panels and 8 s at 128 on ONE core — a coarser grid beyond 48 panels, and
     // the candidates are independent: they are dealt over the host's cores, the winner is the first of the cheapest in candidate order whatever the thread count)
     struct Cand { double b, h; int margin; };
@@ -609,7 +646,7 @@ static bool lfac_scan_plans(LfacPlan& best, int nblk, int nx, int ne, int nc, in
     auto work = [&] {
         for (size_t c; (c = next.fetch_add(1)) < cands.size();) {
             LfacPlan P;
-            if (lfac_make_plan(P, nblk, nx, ne, nc, W, cands[c].b, cands[c].h, cands[c].margin)) est[c] = lfac_plan_estimate(P);
+            if (lfac_make_plan(P, nblk, nx, ne, nc, W, cands[c].b, cands[c].h, cands[c].margin, first)) est[c] = lfac_plan_estimate(P);
         }
     };
     {
@@ -621,7 +658,7 @@ static bool lfac_scan_plans(LfacPlan& best, int nblk, int nx, int ne, int nc, in
     int win = -1;
     for (size_t c = 0; c < cands.size(); ++c) if (est[c] >= 0.0 && (win < 0 || est[c] < est[(size_t)win])) win = (int)c;
     if (win >= 0) {
-        if (!lfac_make_plan(best, nblk, nx, ne, nc, W, cands[(size_t)win].b, cands[(size_t)win].h, cands[(size_t)win].margin)) return false;     // (deterministic: the same plan again)
+        if (!lfac_make_plan(best, nblk, nx, ne, nc, W, cands[(size_t)win].b, cands[(size_t)win].h, cands[(size_t)win].margin, first)) return false;     // (deterministic: the same plan again)
         best.margin = cands[(size_t)win].margin;
         return true;
     }
@@ -630,12 +667,12 @@ static bool lfac_scan_plans(LfacPlan& best, int nblk, int nx, int ne, int nc, in
     // finish a tile (split four ways; from twice that a tile takes ONE worker and the first two columns fit the 255 slots), the cheapest by the model
     {
         const int nst = (ne + LKT - 1) / LKT + (nc + LKT - 1) / LKT;
-        const double h0 = std::max(50.0, cost_schur(nst, 4));
+        const double h0 = std::max(50.0, cost_schur(nst - first, 4));
         double best_e = -1.0;
         for (double b = 40.0; b <= 640.0; b *= 1.25)
             for (double hm : {1.0, 2.0, 3.0}) {
                 LfacPlan P;
-                if (!lfac_make_plan(P, nblk, nx, ne, nc, W, b, hm * h0)) continue;
+                if (!lfac_make_plan(P, nblk, nx, ne, nc, W, b, hm * h0, 1 << 20, first)) continue;
                 const double e = lfac_plan_estimate(P);
                 if (best_e < 0.0 || e < best_e) { best_e = e; best = P; }
             }
@@ -644,10 +681,10 @@ static bool lfac_scan_plans(LfacPlan& best, int nblk, int nx, int ne, int nc, in
 }
 // One plan per SHAPE and process: handles of one shape (the lanes of bench.py, the members of a batch stepped alone, a handle re-created per MPC step) share it — the
 // scan runs once, every later handle of the shape finds its plan here (a shape that cannot be planned is remembered too).
-static std::shared_ptr<const LfacPlan> lfac_cached_plan(int nblk, int nx, int ne, int nc, int W, double* host_ms = nullptr) {
+static std::shared_ptr<const LfacPlan> lfac_cached_plan(int nblk, int nx, int ne, int nc, int W, double* host_ms = nullptr, int first = 0) {
     static std::mutex mu;
-    static std::map<std::array<int, 5>, std::shared_ptr<const LfacPlan>> cache;
-    const std::array<int, 5> key{nblk, nx, ne, nc, W};
+    static std::map<std::array<int, 6>, std::shared_ptr<const LfacPlan>> cache;
+    const std::array<int, 6> key{nblk, nx, ne, nc, W, first};
     std::lock_guard<std::mutex> lock(mu);      // (a second handle of the shape arriving during the scan waits for it instead of scanning again)
     if (host_ms) *host_ms = 0.0;
     const auto it = cache.find(key);
@@ -655,7 +692,7 @@ static std::shared_ptr<const LfacPlan> lfac_cached_plan(int nblk, int nx, int ne
     const auto t0 = std::chrono::steady_clock::now();
     auto P = std::make_shared<LfacPlan>();
     std::shared_ptr<const LfacPlan> out;
-    if (lfac_scan_plans(*P, nblk, nx, ne, nc, W)) out = P;
+    if (lfac_scan_plans(*P, nblk, nx, ne, nc, W, first)) out = P;
     cache[key] = out;
     if (host_ms) *host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return out;
@@ -683,6 +720,9 @@ void lfac_release(calipso_hip_solver* s) {
     if (A->Lfac) (void)hipFree(A->Lfac);
     if (A->d_items) (void)hipFree(A->d_items);
     if (A->d_wfirst) (void)hipFree(A->d_wfirst);
+    if (A->E) (void)hipFree(A->E);
+    if (A->d_itemsE) (void)hipFree(A->d_itemsE);
+    if (A->d_wfirstE) (void)hipFree(A->d_wfirstE);
     delete A;
     s->lfac_aux = nullptr;
 }
@@ -733,28 +773,88 @@ double* lfac_factor_buffer(calipso_hip_solver* s) {
     return static_cast<LfacAux*>(s->lfac_aux)->Lfac;
 }
 
+static unsigned long long bits_of(double v) { unsigned long long u; memcpy(&u, &v, sizeof u); return u; }
+
+// the cached plan and E of a handle that can use them (an attached QP with equality rows), asked for once: a shape without a cached plan or a device without room
+// for E leaves the cache off — not an error, nothing is said
+static void lfac_prepare_cache(calipso_hip_solver* s, LfacAux* A) {
+    A->cache_tried = true;
+    const int cut = lfac_cut(A->plan.nst0, A->plan.nst);
+    if (cut <= 0) return;
+    double ms = 0.0;
+    const auto P = lfac_cached_plan(A->NP / NB, s->d.nx, s->d.ne, s->d.nc, 255, &ms, cut);
+    A->plan_ms += ms;
+    if (!P) return;
+    A->planE = *P; A->cut = cut;
+    const size_t nn = (size_t)A->NP * A->NP;
+    const bool ok = hipMalloc((void**)&A->E, nn * sizeof(double)) == hipSuccess &&
+                    hipMalloc((void**)&A->d_itemsE, std::max<size_t>(1, A->planE.items.size()) * sizeof(LItem)) == hipSuccess &&
+                    hipMalloc((void**)&A->d_wfirstE, A->planE.wfirst.size() * sizeof(int)) == hipSuccess &&
+                    hipMemcpy(A->d_itemsE, A->planE.items.data(), A->planE.items.size() * sizeof(LItem), hipMemcpyHostToDevice) == hipSuccess &&
+                    hipMemcpy(A->d_wfirstE, A->planE.wfirst.data(), A->planE.wfirst.size() * sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
+    if (ok) return;
+    (void)hipGetLastError();
+    if (A->E) (void)hipFree(A->E);
+    if (A->d_itemsE) (void)hipFree(A->d_itemsE);
+    if (A->d_wfirstE) (void)hipFree(A->d_wfirstE);
+    A->E = nullptr; A->d_itemsE = nullptr; A->d_wfirstE = nullptr;
+}
+
 // the launches -2 .. nblk - 2 on the handle's stream; the panel launches carry the progress tags the second stream's feeds wait for (ldl.hip: launch_ldl)
 int lfac_enqueue(calipso_hip_solver* s, unsigned long long* hprog, unsigned long long epoch) {
     LfacAux* A = lfac_prepare(s);
     if (!A) return 0;
     const int NP = s->d.NP, nblk = NP / NB;
+    // hit, capture or bypass (LfacAux): decided from the handle's scalars as they are now — k_lfac takes them by value
+    const bool wanted = s->qp.attached && s->d.ne > 0 && s->schur_cache != 0;
+    if (wanted && !A->cache_tried) lfac_prepare_cache(s, A);
+    const bool eligible = wanted && A->E != nullptr;
+    const std::array<unsigned long long, 4> key{s->gx_version, bits_of(s->sc.rho), bits_of(s->sc.ep), bits_of(s->sc.ed)};
+    const bool hit = eligible && A->valid && key == A->key;
+    const bool capture = eligible && !hit && key[2] == bits_of(s->opt.primal_regularization_initial) && key[3] == bits_of(s->opt.dual_regularization_initial);
+    A->pending = false;
+    if (capture) { A->valid = false; A->pending = true; A->pkey = key; A->captures += 1; }      // (E is being rewritten: no entry until lfac_cache_commit)
+    else if (hit) A->hits += 1;
+    else if (eligible) A->bypasses += 1;
+    const LfacPlan& plan = hit ? A->planE : A->plan;
     LfacArgs a;
     a.NP = NP; a.nx = s->d.nx; a.m = s->d.m; a.ne = s->d.ne; a.nc = s->d.nc; a.tb = trsv_block(NP, (int)s->solve_block);
     a.nst0 = A->plan.nst0; a.nst = A->plan.nst;
-    a.S = s->S; a.Zbuf = A->Zbuf; a.Minv = s->Ypanel; a.Dx = s->Dx; a.Tinv = s->Tinv;
+    a.cut = A->cut; a.capture = capture ? 1 : 0;
+    a.S = s->S; a.Zbuf = A->Zbuf; a.Minv = s->Ypanel; a.Dx = s->Dx; a.Tinv = s->Tinv; a.E = A->E;
     a.Lsym = s->Lsym; a.Zj = s->Z; a.WH = s->WH; a.icount = s->icount;
     a.sc = s->sc;
     int launches = 0;
     for (int ell = -2; ell <= nblk - 2; ++ell) {
         a.k = ell;
-        a.items = A->d_items;
-        a.wfirst = A->d_wfirst + A->plan.item0[ell + 2];
+        a.items = hit ? A->d_itemsE : A->d_items;
+        a.wfirst = (hit ? A->d_wfirstE : A->d_wfirst) + plan.item0[ell + 2];
         a.hprog = ell >= 0 ? hprog : (unsigned long long*)nullptr;
         a.ptag = epoch | (unsigned long long)(ell >= 0 ? ell : 0);
-        hipLaunchKernelGGL(k_lfac, dim3(1 + A->plan.busy[ell + 2]), dim3(TR_THREADS), 0, s->stream, a);
+        hipLaunchKernelGGL(k_lfac, dim3(1 + plan.busy[ell + 2]), dim3(TR_THREADS), 0, s->stream, a);
         ++launches;
     }
     return launches;
+}
+
+// the host knows that the factorisation lfac_enqueue queued last has completed (api.hip: do_factorize): what a capture run left in E becomes the entry
+void lfac_cache_commit(calipso_hip_solver* s) {
+    LfacAux* A = static_cast<LfacAux*>(s->lfac_aux);
+    if (!A || !A->pending) return;
+    A->pending = false; A->valid = true; A->key = A->pkey;
+}
+// "opt.schur_cache" was set: whatever is cached goes
+void lfac_cache_drop(calipso_hip_solver* s) {
+    LfacAux* A = static_cast<LfacAux*>(s->lfac_aux);
+    if (A) { A->valid = false; A->pending = false; }
+}
+// calipso_hip_schur_cache_info: [captures, hits, bypasses, bytes of E]
+void lfac_cache_info(calipso_hip_solver* s, double out[4]) {
+    for (int i = 0; i < 4; ++i) out[i] = 0.0;
+    LfacAux* A = static_cast<LfacAux*>(s->lfac_aux);
+    if (!A) return;
+    out[0] = (double)A->captures; out[1] = (double)A->hits; out[2] = (double)A->bypasses;
+    out[3] = A->E ? (double)A->NP * A->NP * sizeof(double) : 0.0;
 }
 
 // diagnostics for bench.py / tests: [0] launches, [1] items, [2] budget, [3] longest worker of the head, [4] mean longest worker of the panel launches, [5] bytes of the
@@ -768,6 +868,7 @@ void lfac_describe(calipso_hip_solver* s, double out[8]) {
     for (size_t l = 2; l < A->plan.load.size(); ++l) { sum += A->plan.load[l]; ++n; }
     out[4] = n ? sum / n : 0.0;
     out[5] = 2.0 * (double)A->NP * A->NP * sizeof(double) + (double)A->plan.items.size() * sizeof(LItem) + (double)A->plan.wfirst.size() * sizeof(int);      // bytes outside the slab
+    if (A->E) out[5] += (double)A->NP * A->NP * sizeof(double) + (double)A->planE.items.size() * sizeof(LItem) + (double)A->planE.wfirst.size() * sizeof(int);
     out[6] = A->plan_ms; out[7] = lfac_plan_estimate(A->plan);      // [6]: host milliseconds this handle spent scanning plans (0: cache hit)
 }
 
@@ -799,6 +900,26 @@ extern "C" int32_t calipso_hip_debug_lfac_plan(int32_t nblk, int32_t nx, int32_t
         out[6 * l + 0] = P.load[l]; out[6 * l + 1] = i1 - i0; out[6 * l + 2] = kinds[0]; out[6 * l + 3] = kinds[1]; out[6 * l + 4] = kinds[2]; out[6 * l + 5] = P.mean[l]; (void)longrow;
     }
     return nl;
+}
+
+// The items of a shape's scanned plan without a device (tests/test_lfac_cached_plan_cpu.py): first = 0 the full plan, first = the cut stage the cached plan.  Nine shorts
+// per item: launch (-2 ..), kind, i, j, a, b, c, pad0, pad1, in the order the workers walk them; info = [nst0, nst, cut, W].  Returns the number of items (more than
+// max_items: nothing was written), 0 if the shape cannot be planned
+extern "C" int32_t calipso_hip_debug_lfac_plan_items(int32_t nblk, int32_t nx, int32_t ne, int32_t nc, int32_t first, int16_t* out, int32_t max_items, int32_t info[4]) {
+    const auto P = calipso::lfac_cached_plan(nblk, nx, ne, nc, 255, nullptr, first);
+    if (!P) return 0;
+    if (info) { info[0] = P->nst0; info[1] = P->nst; info[2] = calipso::lfac_cut(P->nst0, P->nst); info[3] = P->W; }
+    const int n = (int)P->items.size();
+    if (!out || n > max_items) return n;
+    for (int l = 0; l < (int)P->item0.size(); ++l) {
+        const int w0 = P->item0[(size_t)l];
+        for (int i = P->wfirst[(size_t)w0]; i < P->wfirst[(size_t)(w0 + P->W)]; ++i) {
+            const calipso::LItem& it = P->items[(size_t)i];
+            const int16_t v[9] = {(int16_t)(l - 2), it.kind, it.i, it.j, it.a, it.b, it.c, it.pad0, it.pad1};
+            memcpy(out + 9 * (size_t)i, v, sizeof v);
+        }
+    }
+    return n;
 }
 
 // Timing of synthetic item lists on the real kernel (bench/lfac_items.py; the handle's factor is garbage afterwards): every worker gets `per_worker` items of one kind —
@@ -839,7 +960,7 @@ extern "C" double calipso_hip_debug_lfac_items(calipso_hip_solver* s, int32_t ki
     (void)hipMemcpy(d_wfirst, wfirst.data(), wfirst.size() * sizeof(int), hipMemcpyHostToDevice);
     LfacArgs a;
     a.NP = NP; a.nx = s->d.nx; a.m = s->d.m; a.ne = s->d.ne; a.nc = s->d.nc; a.tb = trsv_block(NP, (int)s->solve_block);
-    a.nst0 = A->plan.nst0; a.nst = nst; a.k = -2;
+    a.nst0 = A->plan.nst0; a.nst = nst; a.k = -2; a.cut = 0; a.capture = 0; a.E = nullptr;
     a.S = s->S; a.Zbuf = A->Zbuf; a.Minv = s->Ypanel; a.Dx = s->Dx; a.Tinv = s->Tinv; a.Lsym = s->Lsym; a.Zj = s->Z; a.WH = s->WH; a.icount = s->icount;
     a.items = d_items; a.wfirst = d_wfirst; a.hprog = nullptr; a.ptag = 0; a.sc = s->sc;
     hipEvent_t e0, e1;

@@ -140,6 +140,7 @@ int32_t calipso_hip_scatter_field(calipso_hip_solver* s, const char* field, cons
         hipLaunchKernelGGL(k_scatter_assign, dim3((unsigned)((pat.winners + 255) / 256)), dim3(256), 0, s->stream, pat.winners, pat.src, pat.dst2, pat.vals, s->Lsym);
     } else
     hipLaunchKernelGGL(k_scatter_assign, dim3((unsigned)((pat.winners + 255) / 256)), dim3(256), 0, s->stream, pat.winners, pat.src, pat.dst, pat.vals, s->Z);
+    if (f == "equality_jacobian_variables") s->gx_version += 1;
     if (structure_active(s)) { const int rc = structure_validate(s, f == "equality_jacobian_variables" ? 1 : 2); if (rc < 0) return rc; }
     blocks_pack(s, true, false);
     SYNC();      // `values` may be reused by the caller

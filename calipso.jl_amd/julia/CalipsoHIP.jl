@@ -498,6 +498,14 @@ function schedule_info(hs::HIPSolver)
     return out
 end
 
+# calipso_hip_schur_cache_info: factorisations of a handle with an attached QP that [1] stored the Schur complement's equality products, [2] started from the stored
+# ones, [3] could have used them and went without; [4] bytes of the buffer (all zero: the handle has no such cache)
+function schur_cache_info(hs::HIPSolver)
+    out = zeros(Float64, 4)
+    ccall((:calipso_hip_schur_cache_info, lib), Int32, (Ptr{Cvoid}, Ptr{Float64}), hs.handle, out)
+    return out
+end
+
 "After `analyze_structure!`: factor the Schur complement by the multifrontal sparse LDL' over a nested dissection of its pattern (log2(stages) launches instead of the chain of nx pivots); `batch` >= the largest group this solver leads. Returns (tree levels, largest front, nnz of the pattern, 2)."
 function set_stage_parallel!(hs::HIPSolver, on::Bool=true; batch::Integer=1)
     out = zeros(Int64, 4)

@@ -334,7 +334,13 @@ int32_t calipso_hip_stats(calipso_hip_solver*, int64_t out[8]);
 
 /* ---- device-resident conic QP evaluator (synthetic benchmark inputs) ------------------------------- */
 /* min c*x'Px + q'x  s.t. Ax - b = 0, h - Gx in K.  Host arrays are copied once; afterwards evaluate! runs as device
- * mat-vecs and no host callback is needed (eval = NULL).  P must be symmetric. */
+ * mat-vecs and no host callback is needed (eval = NULL).  P must be symmetric.
+ * The equality Jacobian gx = A of such a handle stays what this call installed, and every first factorisation of an inertia correction uses the same initial
+ * regularisation: a dense handle stepped alone (padded nx >= 1024, ne > 0) therefore keeps the equality products gx' (omega_y gx) of the Schur complement in a buffer of
+ * its own (padded nx squared doubles) and its later factorisations start from them, until the penalty changes, gx is written (this call, calipso_hip_set_field /
+ * calipso_hip_scatter_field of equality_jacobian_variables, a device evaluator) or the regularisation differs (the retries of an inertia correction go without).
+ * The factor is the same to the bit either way.  "opt.schur_cache" = 0 (calipso_hip_set_field) turns it off; calipso_hip_schur_cache_info counts.  (bench.py's
+ * roofline.achieved counts the algorithmic flops of a step: with hits the device executes fewer than it is credited with.) */
 int32_t calipso_hip_qp_attach(calipso_hip_solver*, const double* P, const double* q, const double* A, const double* b,
                               const double* G, const double* h, double objective_scale);
 /* evaluate!(...; flags) with the attached evaluator on point `which` */
@@ -724,6 +730,10 @@ int32_t calipso_hip_structure_work(calipso_hip_solver*, double out[8]);
  * [1] where the last step's went: 0 main stream, 1 forked at the start of the step, 2 handed over while the pivot chain runs   [2] factorisations queued ahead of an exit
  * test that held after all (their traces were undone)   [3] reserved */
 int32_t calipso_hip_schedule_info(calipso_hip_solver*, double out[4]);
+/* The cache of the Schur complement's equality products (calipso_hip_qp_attach): factorisations so far that [0] stored the products (capture), [1] started from the
+ * stored ones (hit), [2] could have used the cache and went without (bypass: another regularisation than the initial one)   [3] bytes of the buffer.  All zero on a
+ * handle without the cache ("opt.schur_cache" = 0, no attached QP, ne = 0, a member stepped by its group, padded nx < 1024, structured handles). */
+int32_t calipso_hip_schur_cache_info(calipso_hip_solver*, double out[4]);
 int32_t calipso_hip_synchronize(calipso_hip_solver*);
 /* Independent Solvers stepped from different host threads (solver.jl:46-150: the reference's Solvers are independent objects; batch.py: lanes) overlap on the GPU only
  * if the runtime put their streams behind different hardware dispatchers — which depends on the order in which the process created its streams and cannot be queried.

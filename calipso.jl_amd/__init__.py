@@ -13,7 +13,7 @@ import numpy as np
 from ._lib import CALLBACK_FN, EVAL_FN, CalipsoHipError, lib
 from ._marshal import QP_NAMES, pack_cotangent, qp_names, qp_shapes, unpack_columns
 
-__all__ = ["Solver", "Group", "LDLSolver", "SmallBatch", "Comm", "ordering", "symbolic", "Options", "initialize_b", "solve_b", "CalipsoHipError", "FLAGS", "splitmix_uniform",
+__all__ = ["Solver", "Group", "LDLSolver", "SmallBatch", "SparseKKT", "Comm", "ordering", "symbolic", "Options", "initialize_b", "solve_b", "CalipsoHipError", "FLAGS", "splitmix_uniform",
            "mfma_f64_peak"]
 
 # evaluate! flags (include/calipso_hip.h)
@@ -855,6 +855,160 @@ class SparseLDL(_Handle):
         ms = np.zeros(2)
         self._check(self._L.calipso_hip_sparse_timing(self._h, _pd(ms)), "sparse_timing")
         return float(ms[0]), float(ms[1])
+
+
+class SparseKKT(_Handle):
+    """search_direction! (src/solver/search_direction.jl:1-23) on sparse problem data resident on the device (include/calipso_hip.h, "search_direction! on
+    sparse problem data"; csrc/sparse_kkt.hip): assembly of jacobian_variables_symmetric, inertia correction, the symmetric solve and iterative refinement
+    without a dense block anywhere.  Lxx (nx x nx, the full Lagrangian Hessian with both triangles), gx (ne x nx), hx (nc x nx): scipy sparse matrices whose
+    PATTERN is used as it is (stored zeros included; a CSC matrix is taken in its own non-zero order, which later raw value arrays follow).  Cones: the first
+    n_nonnegative rows of hx nonnegative (default: all that the second-order cones leave), then contiguous second-order cones of second_order_dims.
+    method / perm as SparseLDL.  There is no `H \\ residual` fallback: search_direction returns status 2 (CALIPSO_WARN_REFINEMENT) with the last refined step."""
+    _last_error, _destroy = "calipso_hip_sparse_kkt_last_error", "calipso_hip_sparse_kkt_destroy"
+    _message = _Handle._STATUS_MESSAGE
+
+    def __init__(self, Lxx, gx, hx, n_nonnegative=None, second_order_dims=(), method="nested_dissection", perm=None, device=0, options=None):
+        import scipy.sparse as sp
+        self._L = lib()
+        as_csc = lambda A: A if sp.isspmatrix_csc(A) else sp.csc_matrix(A)
+        Lxx, gx, hx = as_csc(Lxx), as_csc(gx), as_csc(hx)
+        self.nx, self.ne, self.nc = int(Lxx.shape[0]), int(gx.shape[0]), int(hx.shape[0])
+        if Lxx.shape != (self.nx, self.nx) or gx.shape[1] != self.nx or hx.shape[1] != self.nx:
+            raise ValueError("SparseKKT: Lxx is nx x nx, gx ne x nx, hx nc x nx")
+        self.n, self.N = self.nx + self.ne + self.nc, self.nx + 2 * self.ne + 3 * self.nc
+        self.nnz = (int(Lxx.indptr[-1]), int(gx.indptr[-1]), int(hx.indptr[-1]))
+        dims = np.ascontiguousarray(list(second_order_dims), dtype=np.int64)
+        if n_nonnegative is None:
+            n_nonnegative = self.nc - int(dims.sum())
+        one_based = lambda A: (np.ascontiguousarray(A.indptr, dtype=np.int64) + 1, np.ascontiguousarray(A.indices, dtype=np.int64) + 1)
+        pats = [one_based(A) for A in (Lxx, gx, hx)]
+        pp = None if perm is None else np.ascontiguousarray(perm, dtype=np.int64)
+        h = C.c_void_p()
+        rc = self._L.calipso_hip_sparse_kkt_create(self.nx, self.ne, self.nc, int(n_nonnegative), int(dims.size), _pi(dims) if dims.size else None,
+                                                   _pi(pats[0][0]), _pi(pats[0][1]), _pi(pats[1][0]), _pi(pats[1][1]), _pi(pats[2][0]), _pi(pats[2][1]),
+                                                   3 if pp is not None else SPARSE_METHODS[method], _pi(pp) if pp is not None else None, device, C.byref(h))
+        if rc != 0:
+            raise CalipsoHipError("calipso_hip_sparse_kkt_create failed (%d): %s" % (rc, self._L.calipso_hip_sparse_kkt_last_error(None).decode()))
+        self._h = h
+        self.device = int(device)
+        info = np.zeros(8, dtype=np.int64)
+        self._check(self._L.calipso_hip_sparse_kkt_info(self._h, _pi(info)), "sparse_kkt_info")
+        self.info = dict(n=int(info[0]), nnz_upper=int(info[1]), nnzL=int(info[2]), levels=int(info[3]),
+                         numeric={0: "columns_global_accumulator", 1: "columns_lds_accumulator", 2: "multifrontal"}[int(info[4])], assemble_launches=int(info[5]),
+                         max_cone_dimension=int(info[6]), N=int(info[7]))
+        self._colptr, self._rowval = np.zeros(self.n + 1, dtype=np.int64), np.zeros(max(self.info["nnz_upper"], 1), dtype=np.int64)
+        self._check(self._L.calipso_hip_sparse_kkt_pattern(self._h, _pi(self._colptr), _pi(self._rowval)), "sparse_kkt_pattern")
+        self.inertia = (0, 0, 0)
+        for k, v in (options or {}).items():
+            self.set_option(k, v)
+
+    def set_option(self, name, value):
+        """the regularisation and refinement options of options.jl:6-59 by name; "central_path": the scalar IC-2 reads"""
+        self._check(self._L.calipso_hip_sparse_kkt_set_option(self._h, name.encode(), float(value)), "sparse_kkt_set_option(%s)" % name)
+
+    def _is_device(self, a):
+        return a is not None and (hasattr(a, "is_cuda") or isinstance(a, C.c_void_p))
+
+    def _device_pointer(self, a, name, count):
+        """a float64 CUDA tensor of `count` entries on the handle's device, or a raw device pointer (ctypes.c_void_p): its pointer"""
+        if a is None:
+            return None
+        if not hasattr(a, "is_cuda"):
+            return a
+        import torch
+        if a.dtype != torch.float64 or a.numel() != count or not a.is_contiguous():
+            raise ValueError("%s must be a contiguous float64 tensor of %d entries" % (name, count))
+        if a.is_cuda and a.device.index != self.device:
+            raise ValueError("%s is on %s, the handle on device %d" % (name, a.device, self.device))
+        if a.is_cuda:
+            torch.cuda.current_stream(a.device).synchronize()      # the handle works on its own stream
+        return C.c_void_p(a.data_ptr())      # (a CPU tensor's pointer goes through: the library refuses it, naming the argument)
+
+    def set_values(self, Lxx=None, gx=None, hx=None, w=None, penalty=None, central_path=None):
+        """non-zeros of Lxx, gx, hx (sparse matrices of the analysed pattern, or the values in its order), the point w (N), the penalty rho; None keeps what
+        is resident.  Host arrays, or — all that are given — float64 CUDA tensors / raw device pointers as ctypes.c_void_p (the device route: the penalty is then
+        one double on the device too)."""
+        given = [a for a in (Lxx, gx, hx, w, penalty) if a is not None]
+        if central_path is not None:
+            self.set_option("central_path", central_path)
+        if given and all(self._is_device(a) for a in given):
+            names, counts = ("Lxx", "gx", "hx", "w", "penalty"), self.nnz + (self.N, 1)
+            ptrs = [self._device_pointer(a, nm, ct) for a, nm, ct in zip((Lxx, gx, hx, w, penalty), names, counts)]
+            self._check(self._L.calipso_hip_sparse_kkt_set_values_device(self._h, *ptrs), "sparse_kkt_set_values_device")
+            return
+        def values(A, count, name):
+            if A is None:
+                return None
+            if hasattr(A, "indptr"):
+                A = A.data
+            v = np.ascontiguousarray(A, dtype=np.float64).reshape(-1)
+            if v.size != count:
+                raise CalipsoHipError("SparseKKT.set_values: %s has %d values, the analysed pattern %d" % (name, v.size, count))
+            return v
+        arrs = [values(Lxx, self.nnz[0], "Lxx"), values(gx, self.nnz[1], "gx"), values(hx, self.nnz[2], "hx"), values(w, self.N, "w"),
+                None if penalty is None else np.array([float(penalty)])]
+        self._check(self._L.calipso_hip_sparse_kkt_set_values(self._h, *[_opt(a) for a in arrs]), "sparse_kkt_set_values")
+
+    def factorize(self, ep, ed):
+        """one assemble + factorisation at (ep, ed); sets .inertia; returns the warning status (1 = an exact zero pivot was met)"""
+        out = np.zeros(3, dtype=np.int64)
+        rc = self._check(self._L.calipso_hip_sparse_kkt_factorize(self._h, float(ep), float(ed), _pi(out)), "sparse_kkt_factorize")
+        self.inertia = tuple(int(v) for v in out)
+        return rc
+
+    def matrix(self):
+        """triu(jacobian_variables_symmetric) of the last assemble, scipy CSC"""
+        import scipy.sparse as sp
+        nz = np.zeros(max(self.info["nnz_upper"], 1))
+        self._check(self._L.calipso_hip_sparse_kkt_get_matrix(self._h, _pd(nz)), "sparse_kkt_get_matrix")
+        k = self.info["nnz_upper"]
+        return sp.csc_matrix((nz[:k], self._rowval[:k] - 1, self._colptr - 1), shape=(self.n, self.n))
+
+    def mul(self, v):
+        """H v for the unreduced matrix at the regularisation of the last assemble"""
+        v = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
+        if v.size != self.N:
+            raise CalipsoHipError("SparseKKT.mul: v has %d entries, N = %d" % (v.size, self.N))
+        out = np.zeros(self.N)
+        self._check(self._L.calipso_hip_sparse_kkt_mul(self._h, _pd(v), _pd(out)), "sparse_kkt_mul")
+        return out
+
+    def solve_symmetric(self, residual):
+        """search_direction_symmetric! with the current factorisation"""
+        r = np.ascontiguousarray(residual, dtype=np.float64).reshape(-1)
+        if r.size != self.N:
+            raise CalipsoHipError("SparseKKT.solve_symmetric: the residual has %d entries, N = %d" % (r.size, self.N))
+        out = np.zeros(self.N)
+        self._check(self._L.calipso_hip_sparse_kkt_solve_symmetric(self._h, _pd(r), _pd(out)), "sparse_kkt_solve_symmetric")
+        return out
+
+    def search_direction(self, residual, regularization=(0.0, 0.0, 0.0)):
+        """search_direction! from regularization = (ep, ep_last, ed): returns (step, regularization, info, status) with info = dict(factorizations, refinement_rounds,
+        residual_norm) and status 0 or 2 (refinement failed: the last refined step, no fallback).  A CUDA tensor / device pointer as residual: the device route,
+        the step comes back as a CUDA tensor."""
+        reg, info = np.ascontiguousarray(regularization, dtype=np.float64).copy(), np.zeros(4)
+        if reg.size != 3:
+            raise CalipsoHipError("SparseKKT.search_direction: regularization is (ep, ep_last, ed)")
+        if self._is_device(residual):
+            import torch
+            step = torch.empty(self.N, dtype=torch.float64, device=torch.device("cuda", self.device))
+            rp = self._device_pointer(residual, "residual", self.N)
+            rc = self._L.calipso_hip_sparse_kkt_search_direction_device(self._h, rp, C.c_void_p(step.data_ptr()), _pd(reg), _pd(info))
+        else:
+            r = np.ascontiguousarray(residual, dtype=np.float64).reshape(-1)
+            if r.size != self.N:
+                raise CalipsoHipError("SparseKKT.search_direction: the residual has %d entries, N = %d" % (r.size, self.N))
+            step = np.zeros(self.N)
+            rc = self._L.calipso_hip_sparse_kkt_search_direction(self._h, _pd(r), _pd(step), _pd(reg), _pd(info))
+        self.regularization = tuple(float(v) for v in reg)      # (also after an error: where the inertia correction stopped)
+        self._check(rc, "search_direction!")
+        return step, self.regularization, dict(factorizations=int(info[0]), refinement_rounds=int(info[1]), residual_norm=float(info[2])), rc
+
+    def timing(self):
+        """device milliseconds of the last search_direction: dict(assemble, factorize, solve, refinement_solves, refinement_mul, wall)"""
+        ms = np.zeros(8)
+        self._check(self._L.calipso_hip_sparse_kkt_timing(self._h, _pd(ms)), "sparse_kkt_timing")
+        return dict(zip(("assemble", "factorize", "solve", "refinement_solves", "refinement_mul", "wall"), (float(v) for v in ms[:6])))
 
 
 class SmallBatch(_Handle):

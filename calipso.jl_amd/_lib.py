@@ -102,6 +102,21 @@ SYMBOLS = {
     "calipso_hip_sparse_solve_device": (_i32, [_vp, _i64, _vp, _vp]),
     "calipso_hip_sparse_get_factor": (_i32, [_vp, _pi64, _pi64, _pi64, _pd, _pd]),
     "calipso_hip_sparse_timing": (_i32, [_vp, _pd]),
+    "calipso_hip_sparse_kkt_create": (_i32, [_i64, _i64, _i64, _i64, _i64, _pi64, _pi64, _pi64, _pi64, _pi64, _pi64, _pi64, _i32, _pi64, _i32, C.POINTER(_vp)]),
+    "calipso_hip_sparse_kkt_destroy": (_i32, [_vp]),
+    "calipso_hip_sparse_kkt_last_error": (C.c_char_p, [_vp]),
+    "calipso_hip_sparse_kkt_info": (_i32, [_vp, _pi64]),
+    "calipso_hip_sparse_kkt_pattern": (_i32, [_vp, _pi64, _pi64]),
+    "calipso_hip_sparse_kkt_set_option": (_i32, [_vp, C.c_char_p, _dbl]),
+    "calipso_hip_sparse_kkt_set_values": (_i32, [_vp, _pd, _pd, _pd, _pd, _pd]),
+    "calipso_hip_sparse_kkt_set_values_device": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "calipso_hip_sparse_kkt_factorize": (_i32, [_vp, _dbl, _dbl, _pi64]),
+    "calipso_hip_sparse_kkt_get_matrix": (_i32, [_vp, _pd]),
+    "calipso_hip_sparse_kkt_mul": (_i32, [_vp, _pd, _pd]),
+    "calipso_hip_sparse_kkt_solve_symmetric": (_i32, [_vp, _pd, _pd]),
+    "calipso_hip_sparse_kkt_search_direction": (_i32, [_vp, _pd, _pd, _pd, _pd]),
+    "calipso_hip_sparse_kkt_search_direction_device": (_i32, [_vp, _vp, _vp, _pd, _pd]),
+    "calipso_hip_sparse_kkt_timing": (_i32, [_vp, _pd]),
     "calipso_hip_small_create": (_i32, [_i64, _i64, _i64, _i32, C.POINTER(_vp)]),
     "calipso_hip_small_destroy": (_i32, [_vp]),
     "calipso_hip_small_last_error": (C.c_char_p, [_vp]),

@@ -501,6 +501,7 @@ inline BatchSc batch_of(const calipso_hip_solver* s) {
 bool sparse_is_multifrontal(const calipso_hip_sparse* sp);
 void sparse_borrow_stream(calipso_hip_sparse* sp, hipStream_t st);
 int sparse_batch(const calipso_hip_sparse* sp);
+hipStream_t sparse_stream(const calipso_hip_sparse* sp);      // the plan's stream (sparse_kkt.hip enqueues its kernels on it)
 int sparse_factor_from_dense(calipso_hip_sparse* sp, hipStream_t st, const Batch& bt, const double* S, const long long* src, int* icount, bool values_in_place = false);
 void sparse_values(calipso_hip_sparse* sp, double** values, long long* stride);      // the batch x nnz values the factorisation reads (instance-major)
 int sparse_solve_inplace(calipso_hip_sparse* sp, hipStream_t st, const Batch& bt, double* x);

@@ -964,6 +964,8 @@ void sparse_borrow_stream(calipso_hip_sparse* sp, hipStream_t st) {
     sp->stream = st; sp->owns_stream = false;
 }
 int sparse_batch(const calipso_hip_sparse* sp) { return sp ? sp->batch : 0; }
+// the stream every call of the plan enqueues on: a handle that owns a plan (sparse_kkt.hip) orders its own kernels with it
+hipStream_t sparse_stream(const calipso_hip_sparse* sp) { return sp ? sp->stream : nullptr; }
 // gather the pattern's entries from the dense S of every instance of `bt`, factor, add the pivot signs to the instances' counters
 void sparse_values(calipso_hip_sparse* sp, double** values, long long* stride) { *values = sp ? sp->d_Aval : nullptr; *stride = sp ? (long long)sp->plan.nnzA : 0; }
 // values_in_place: the caller has written the pattern's entries into sparse_values() itself (structured handles: blocks.hip) — no gather

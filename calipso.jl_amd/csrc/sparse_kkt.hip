@@ -1,0 +1,630 @@
+// sparse_kkt.hip — search_direction! (src/solver/search_direction.jl:1-23) on SPARSE problem data resident on the device: the handle behind
+// calipso_hip_sparse_kkt_* (include/calipso_hip.h).  Nothing here is dense: memory is O(nnz(Lxx) + nnz(gx) + nnz(hx) + nnz(L)).
+//
+//   analyse (host, once per pattern)   sparse_kkt.hpp: the pattern of triu(K) of jacobian_variables_symmetric, the slot of K.nzval of every input non-zero,
+//                                      diagonal and cone-block entry, row views of Lxx, gx, hx; then a calipso_hip_sparse of that pattern (sparse.hip).
+//   assemble (device, ONE launch)      residual_jacobian_variables! + residual_jacobian_variables_symmetric! (residual_jacobian_variables.jl:1-167) without ever
+//                                      forming H: one thread per written entry of K.nzval; the second-order blocks one thread per (cone, column) through the closed
+//                                      form of second_order_matrix_inverse (cones/second_order.jl:50-65, first-row quirk kept), O(dimension) per column.
+//   H v (device, two launches)         the unreduced N x N matrix applied from the same data: the rows that gather from Lxx, gx, hx (one thread per row, or one
+//                                      wavefront per row where the rows are long), and the r-, s-, t-rows (one thread each); fused with residual - H step and
+//                                      its infinity norm, so a refinement round reads back one double.
+//   residual_symmetric!, recovery      residual.jl:53-101, search_direction.jl:59-101: one thread per row, one per second-order cone.
+//   driver (host)                      inertia_correction! (inertia.jl:30-80) and iterative_refinement! (iterative_refinement.jl:1-52) through ic_begin / ic_after /
+//                                      refine_next of step_decisions.hpp; every retry is one assemble + one calipso_hip_sparse_factorize_device.
+// Every kernel runs on the sparse handle's stream.  Gathers only: no atomics on values, a fixed summation order, results reproducible bit for bit.
+#include <chrono>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "internal.hpp"
+#include "sparse_kkt.hpp"                  // the analysis: plain host C++
+
+using calipso::i64;
+using calipso::Options;
+using calipso::Scalars;
+using namespace calipso::sparse_kkt;
+static_assert(REFUSED_ARGUMENT == CALIPSO_ERR_ARGUMENT, "a refused pattern is an argument error");
+
+namespace {
+
+constexpr int KT = 256;                    // threads per workgroup of every kernel here
+constexpr int WAVE_ROW_MIN = 32;           // mean non-zeros per gathered row from which a wavefront takes a row instead of a thread
+
+struct View { const int *ptr, *idx, *src; };      // a row view (idx = column, src = position in the caller's nzval) or a column view (idx = row, src unused)
+
+// what every kernel reads: sizes, the point's offsets (point.jl:13-22), the resident data and the tables of the analysis
+struct KktDev {
+    int nx, ne, nc, n, N, q, nsoc, ncc;           // q = nonnegative rows, ncc = cone columns (sum of the dimensions)
+    int o_r, o_s, o_y, o_z, o_t;
+    int nnzL, nnzg, nnzh;
+    const double *Lxx, *gx, *hx, *w, *rho;
+    const int *slotL, *slotg, *sloth;             // slotL: -1 for the strict lower triangle AND for the diagonal (diag_x_src carries that one)
+    const int *diag_x, *diag_x_src, *diag_e, *diag_c;
+    const int *row_cone;                          // per cone row: its second-order cone, -1 nonnegative, -2 in no cone
+    const int *soc_start, *soc_dim, *col_cone, *col_index, *col_slot;
+    View Lr, gr, hr, gc, hc;
+};
+
+__device__ __forceinline__ double rabs(double x) { return x != x ? __builtin_huge_val() : fabs(x); }      // a NaN reports +inf (step_decisions.hpp: refine_next)
+
+// second_order_matrix_inverse's vector form (cones/second_order.jl:50-65) for u = first row of Cs + Cbar_t P, on the fly: U(k), X(k) give the entries, put(k, value)
+// takes entry k of the UNSCALED result times 1 / u[0] in the reference's order
+template <typename FU, typename FX, typename FP>
+__device__ __forceinline__ void arrow_inverse(int dm, FU U, FX X, FP put) {
+    const double u0 = U(0);
+    double uu = 0.0, d0 = 0.0;
+    for (int k = 1; k < dm; ++k) { const double uk = U(k); uu += uk * uk; d0 += (uk / u0) * X(k); }
+    const double alpha = -1.0 / (u0 * u0) * uu;
+    const double beta = 1.0 / (1.0 + alpha);
+    const double x0_1 = X(0) - d0;
+    double d1 = 0.0;
+    for (int k = 1; k < dm; ++k) { const double us = U(k) / u0; const double o = X(k) - beta * (us * x0_1); d1 += us * o; put(k, 1.0 / u0 * o); }
+    put(0, 1.0 / u0 * (X(0) - d1));
+}
+
+// ---- assemble: K.nzval from the three non-zero vectors, the point, rho, ep, ed ------------------------------------------------------------------------------
+__global__ __launch_bounds__(KT) void k_kkt_assemble(const KktDev d, double ep, double ed, double* __restrict__ K) {
+    long long e = (long long)blockIdx.x * KT + threadIdx.x;
+    if (e < d.nnzL) { const int s = d.slotL[e]; if (s >= 0) K[s] = d.Lxx[e]; return; }                      // Hessian, strict upper triangle
+    e -= d.nnzL;
+    if (e < d.nnzg) { K[d.slotg[e]] = d.gx[e]; return; }                                                    // Jacobians
+    e -= d.nnzg;
+    if (e < d.nnzh) { K[d.sloth[e]] = d.hx[e]; return; }
+    e -= d.nnzh;
+    if (e < d.nx) { const int p = d.diag_x_src[e]; K[d.diag_x[e]] = (p >= 0 ? d.Lxx[p] : 0.0) + ep; return; }   // Hessian diagonal + ep   :82-85
+    e -= d.nx;
+    if (e < d.ne) { K[d.diag_e[e]] = -1.0 / (d.rho[0] + ep) + (0.0 - ed); return; }                         // :127-131
+    e -= d.ne;
+    if (e < d.nc) {
+        const int kind = d.row_cone[e];
+        if (kind == -1) {                                                                                   // nonnegative: -Sb / (T + Sb P) + D   :139-143
+            const double Sb = d.w[d.o_s + e] - ed, T = d.w[d.o_t + e];
+            K[d.diag_c[e]] = -1.0 * Sb / (T + Sb * ep) + (0.0 - ed);
+        } else if (kind == -2) K[d.diag_c[e]] = 0.0;                                                        // a cone row in no cone: the structural diagonal only
+        return;
+    }
+    e -= d.nc;
+    if (e >= d.ncc) return;
+    // second-order blocks (:145-164): column i of -(Cs + Cbar_t P)^-1 Cbar_t + D, rows <= i
+    const int c = d.col_cone[e], i = d.col_index[e], st = d.soc_start[c], dm = d.soc_dim[c];
+    const double* sl = d.w + d.o_s + st; const double* t = d.w + d.o_t + st;
+    double* Kc = K + d.col_slot[e];
+    const double S0 = sl[0] - ed;
+    arrow_inverse(dm,
+                  [&](int k) { return t[k] + (k == 0 ? S0 : sl[k]) * ep; },
+                  [&](int a) { return i == 0 ? (a == 0 ? S0 : sl[a]) : (a == 0 ? sl[i] : (a == i ? S0 : 0.0)); },      // column i of Cbar_t = arrow(s) - ed I
+                  [&](int a, double v) { if (a <= i) Kc[a] = -v + (a == i ? (0.0 - ed) : 0.0); });
+}
+
+// ---- H v ----------------------------------------------------------------------------------------------------------------------------------------------------
+// what a row's result becomes: out[row] = value (calipso_hip_sparse_kkt_mul), or err[row] = res[row] - value with its magnitude folded into *norm
+struct Sink { double* out; const double* res; double* err; unsigned long long* norm; };
+
+__device__ __forceinline__ void sink_store(const Sink& k, int row, bool live, double value) {
+    double mag = 0.0;
+    if (live) {
+        if (k.out) k.out[row] = value;
+        if (k.err) { const double e = k.res[row] - value; k.err[row] = e; mag = rabs(e); }
+    }
+    if (!k.norm) return;                                                       // (uniform)
+    __shared__ double part[KT / 64];
+    for (int o = 32; o > 0; o >>= 1) mag = fmax(mag, __shfl_xor(mag, o));
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = mag;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double m = part[0];
+        for (int k2 = 1; k2 < KT / 64; ++k2) m = fmax(m, part[k2]);
+        if (m > 0.0) atomicMax(k.norm, (unsigned long long)__double_as_longlong(m));      // non-negative doubles order as their bit patterns
+    }
+}
+
+// row k of [x; y; z] (the rows that gather from Lxx, gx, hx): the terms of lane `l` of `nl` lanes
+__device__ __forceinline__ double gathered_terms(const KktDev& d, const double* __restrict__ v, int k, int l, int nl) {
+    double a = 0.0;
+    if (k < d.nx) {                                                            // Lxx v_x + gx' v_y + hx' v_z
+        for (int p = d.Lr.ptr[k] + l; p < d.Lr.ptr[k + 1]; p += nl) a += d.Lxx[d.Lr.src[p]] * v[d.Lr.idx[p]];
+        for (int p = d.gc.ptr[k] + l; p < d.gc.ptr[k + 1]; p += nl) a += d.gx[p] * v[d.o_y + d.gc.idx[p]];
+        for (int p = d.hc.ptr[k] + l; p < d.hc.ptr[k + 1]; p += nl) a += d.hx[p] * v[d.o_z + d.hc.idx[p]];
+    } else if (k < d.nx + d.ne) {
+        const int e = k - d.nx;
+        for (int p = d.gr.ptr[e] + l; p < d.gr.ptr[e + 1]; p += nl) a += d.gx[d.gr.src[p]] * v[d.gr.idx[p]];
+    } else {
+        const int c = k - d.nx - d.ne;
+        for (int p = d.hr.ptr[c] + l; p < d.hr.ptr[c + 1]; p += nl) a += d.hx[d.hr.src[p]] * v[d.hr.idx[p]];
+    }
+    return a;
+}
+// ... and what the row adds to them: ep on the diagonal, the -1 couplings, -ed
+__device__ __forceinline__ double gathered_tail(const KktDev& d, const double* __restrict__ v, int k, double ep, double ed) {
+    if (k < d.nx) return ep * v[k];
+    if (k < d.nx + d.ne) { const int e = k - d.nx; return -v[d.o_r + e] + (0.0 - ed) * v[d.o_y + e]; }
+    const int c = k - d.nx - d.ne;
+    return -v[d.o_s + c] + (0.0 - ed) * v[d.o_z + c];
+}
+__device__ __forceinline__ int gathered_row(const KktDev& d, int k) { return k < d.nx ? k : (k < d.nx + d.ne ? d.o_y + (k - d.nx) : d.o_z + (k - d.nx - d.ne)); }
+
+template <bool WAVE>
+__global__ __launch_bounds__(KT) void k_kkt_mul_gathered(const KktDev d, double ep, double ed, const double* __restrict__ v, const Sink sink) {
+    if (WAVE) {                                                                // one wavefront per row: KT / 64 rows per workgroup
+        const int k = blockIdx.x * (KT / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+        const bool live = k < d.n;
+        double a = live ? gathered_terms(d, v, k, lane, 64) : 0.0;
+        for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
+        const bool writer = live && lane == 0;
+        sink_store(sink, writer ? gathered_row(d, k) : 0, writer, writer ? a + gathered_tail(d, v, k, ep, ed) : 0.0);
+    } else {
+        const long long k = (long long)blockIdx.x * KT + threadIdx.x;
+        const bool live = k < d.n;
+        sink_store(sink, live ? gathered_row(d, (int)k) : 0, live, live ? gathered_terms(d, v, (int)k, 0, 1) + gathered_tail(d, v, (int)k, ep, ed) : 0.0);
+    }
+}
+
+// the r-, s- and t-rows: rho, the -1 couplings, the cone product Jacobians arrow(t), arrow(s) - ed I (residual_jacobian_variables.jl:59-105)
+__global__ __launch_bounds__(KT) void k_kkt_mul_local(const KktDev d, double ep, double ed, const double* __restrict__ v, const Sink sink) {
+    const long long k = (long long)blockIdx.x * KT + threadIdx.x;
+    const bool live = k < d.ne + 2ll * d.nc;
+    int row = 0; double a = 0.0;
+    if (live) {
+        if (k < d.ne) { row = d.o_r + (int)k; a = (d.rho[0] + ep) * v[row] - v[d.o_y + k]; }
+        else if (k < d.ne + d.nc) { const int c = (int)k - d.ne; row = d.o_s + c; a = ep * v[row] - v[d.o_z + c] - v[d.o_t + c]; }
+        else {
+            const int c = (int)k - d.ne - d.nc, kind = d.row_cone[c];
+            row = d.o_t + c;
+            if (kind == -1) a = d.w[d.o_t + c] * v[d.o_s + c] + (d.w[d.o_s + c] - ed) * v[d.o_t + c];
+            else if (kind >= 0) {
+                const int st = d.soc_start[kind], dm = d.soc_dim[kind], i = c - st;
+                const double* sl = d.w + d.o_s + st; const double* t = d.w + d.o_t + st;
+                const double* vs = v + d.o_s + st; const double* vt = v + d.o_t + st;
+                if (i == 0) for (int b = 0; b < dm; ++b) a += t[b] * vs[b] + (b == 0 ? sl[0] - ed : sl[b]) * vt[b];
+                else a = (t[i] * vs[0] + sl[i] * vt[0]) + (t[0] * vs[i] + (sl[0] - ed) * vt[i]);
+            }
+        }
+    }
+    sink_store(sink, row, live, a);
+}
+
+// ---- residual_symmetric! (residual.jl:53-101): rsym (n) from a residual in the point's layout -----------------------------------------------------------------
+__global__ __launch_bounds__(KT) void k_kkt_residual_symmetric(const KktDev d, double ep, double ed, const double* __restrict__ res, double* __restrict__ rsym) {
+    long long k = (long long)blockIdx.x * KT + threadIdx.x;
+    if (k < d.nx) { rsym[k] = res[k]; return; }
+    k -= d.nx;
+    if (k < d.ne) { rsym[d.nx + k] = res[d.o_y + k] + res[d.o_r + k] / (d.rho[0] + ep); return; }
+    k -= d.ne;
+    const int oc = d.nx + d.ne;
+    if (k < d.nc) {
+        const int kind = d.row_cone[k];
+        if (kind == -1) {
+            const double Sb = d.w[d.o_s + k] - ed, T = d.w[d.o_t + k];
+            rsym[oc + k] = res[d.o_z + k] + (res[d.o_t + k] + Sb * res[d.o_s + k]) / (T + Sb * ep);
+        } else if (kind == -2) rsym[oc + k] = res[d.o_z + k];
+        return;
+    }
+    k -= d.nc;
+    if (k >= d.nsoc) return;
+    // rz + (Cs + Cbar_t P)^-1 (Cbar_t rs + rt)
+    const int st = d.soc_start[k], dm = d.soc_dim[k];
+    const double* sl = d.w + d.o_s + st; const double* t = d.w + d.o_t + st;
+    const double* rs = res + d.o_s + st; const double* rt = res + d.o_t + st; const double* rz = res + d.o_z + st;
+    double* out = rsym + oc + st;
+    const double S0 = sl[0] - ed;
+    double v0 = 0.0;
+    for (int b = 0; b < dm; ++b) v0 += (b == 0 ? S0 : sl[b]) * rs[b];
+    v0 += rt[0];
+    arrow_inverse(dm,
+                  [&](int b) { return t[b] + (b == 0 ? S0 : sl[b]) * ep; },
+                  [&](int a) { return a == 0 ? v0 : (sl[a] * rs[0] + S0 * rs[a]) + rt[a]; },
+                  [&](int a, double v) { out[a] = rz[a] + v; });
+}
+
+// ---- the recovery of Dr, Ds, Dt (search_direction.jl:59-101): step (N) from the symmetric solution (n) and the residual --------------------------------------
+__global__ __launch_bounds__(KT) void k_kkt_recover(const KktDev d, double ep, double ed, const double* __restrict__ dsym, const double* __restrict__ res,
+                                                    double* __restrict__ step) {
+    long long k = (long long)blockIdx.x * KT + threadIdx.x;
+    if (k < d.nx) { step[k] = dsym[k]; return; }
+    k -= d.nx;
+    if (k < d.ne) { const double dy = dsym[d.nx + k]; step[d.o_y + k] = dy; step[d.o_r + k] = (res[d.o_r + k] + dy) / (d.rho[0] + ep); return; }
+    k -= d.ne;
+    const int oc = d.nx + d.ne;
+    if (k < d.nc) {
+        const int kind = d.row_cone[k];
+        const double dz = dsym[oc + k];
+        step[d.o_z + k] = dz;
+        if (kind == -1) {
+            const double Sb = d.w[d.o_s + k] - ed, T = d.w[d.o_t + k], rt = res[d.o_t + k];
+            const double ds = (rt + Sb * (res[d.o_s + k] + dz)) / (T + Sb * ep);
+            step[d.o_s + k] = ds;
+            step[d.o_t + k] = (rt - T * ds) / Sb;
+        } else if (kind == -2) { step[d.o_s + k] = 0.0; step[d.o_t + k] = 0.0; }
+        return;
+    }
+    k -= d.nc;
+    if (k >= d.nsoc) return;
+    const int st = d.soc_start[k], dm = d.soc_dim[k];
+    const double* sl = d.w + d.o_s + st; const double* t = d.w + d.o_t + st;
+    const double* rs = res + d.o_s + st; const double* rt = res + d.o_t + st; const double* dz = dsym + oc + st;
+    double* Ds = step + d.o_s + st; double* Dt = step + d.o_t + st;
+    const double S0 = sl[0] - ed;
+    // Ds = (Cs + Cbar_t P)^-1 (rt + Cbar_t (rs + dz))
+    double v0 = 0.0;
+    for (int b = 0; b < dm; ++b) v0 += (b == 0 ? S0 : sl[b]) * (rs[b] + dz[b]);
+    v0 = rt[0] + v0;
+    arrow_inverse(dm,
+                  [&](int b) { return t[b] + (b == 0 ? S0 : sl[b]) * ep; },
+                  [&](int a) { return a == 0 ? v0 : rt[a] + (sl[a] * (rs[0] + dz[0]) + S0 * (rs[a] + dz[a])); },
+                  [&](int a, double v) { Ds[a] = v; });
+    // Dt = Cbar_t^-1 (rt - Cs Ds): this thread reads back its own Ds
+    double c0 = 0.0;
+    for (int b = 0; b < dm; ++b) c0 += t[b] * Ds[b];
+    c0 = rt[0] - c0;
+    arrow_inverse(dm,
+                  [&](int b) { return b == 0 ? S0 : sl[b]; },
+                  [&](int a) { return a == 0 ? c0 : rt[a] - (t[a] * Ds[0] + t[0] * Ds[a]); },
+                  [&](int a, double v) { Dt[a] = v; });
+}
+
+__global__ __launch_bounds__(KT) void k_kkt_add(int N, double* __restrict__ step, const double* __restrict__ corr) {
+    const long long k = (long long)blockIdx.x * KT + threadIdx.x;
+    if (k < N) step[k] += corr[k];
+}
+
+unsigned blocks(long long items, int per_block = KT) { return (unsigned)std::max<long long>((items + per_block - 1) / per_block, 1); }
+
+}  // namespace
+
+struct calipso_hip_sparse_kkt {
+    Analysis an;
+    Options opt;
+    Scalars sc;                                // kappa (IC-2), ep / ed of the last assemble, ep_last
+    int device = 0;
+    calipso_hip_sparse* sp = nullptr;          // LDL^T of the pattern of triu(K); its stream orders everything here
+    hipStream_t st = nullptr;
+    KktDev d{};
+    bool wave_rows = false;
+    double *Lxx = nullptr, *gx = nullptr, *hx = nullptr, *w = nullptr, *rho = nullptr, *K = nullptr;
+    double *res = nullptr, *step = nullptr, *corr = nullptr, *err = nullptr, *rsym = nullptr, *dsym = nullptr, *norm = nullptr;
+    std::vector<void*> dev;
+    bool have[5] = {false, false, false, false, false};      // Lxx, gx, hx, w, penalty resident
+    bool assembled = false, factored = false;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    double ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    std::string err_text;
+};
+
+namespace {
+
+typedef calipso_hip_sparse_kkt KH;
+thread_local std::string g_kkt_err;
+
+int fail(KH* s, int rc, const std::string& text) { (s ? s->err_text : g_kkt_err) = text; return rc; }
+#define KK(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return fail(s, CALIPSO_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); } while (0)
+
+template <typename T>
+int upload(KH* s, const std::vector<T>& h, const T** out) {
+    T* p = nullptr;
+    KK(hipMalloc((void**)&p, sizeof(T) * std::max<size_t>(h.size(), 1)));
+    s->dev.push_back(p);
+    if (!h.empty()) KK(hipMemcpy(p, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice));
+    *out = p;
+    return CALIPSO_OK;
+}
+int reserve(KH* s, double** out, size_t count) {
+    KK(hipMalloc((void**)out, sizeof(double) * std::max<size_t>(count, 1)));
+    s->dev.push_back(*out);
+    KK(hipMemset(*out, 0, sizeof(double) * std::max<size_t>(count, 1)));
+    return CALIPSO_OK;
+}
+
+// every non-NULL pointer of a device entry must be device memory of the handle's device: checked before anything is enqueued
+int device_pointer(KH* s, const void* p, const char* entry, const char* arg) {
+    if (!p) return CALIPSO_OK;
+    hipPointerAttribute_t at;
+    std::memset(&at, 0, sizeof(at));
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": " + arg + " is not device memory (a host pointer?): the device entries take device pointers only");
+    }
+    if (at.type != hipMemoryTypeDevice) return fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": " + arg + " is not device memory: the device entries take device pointers only");
+    if (at.device != s->device) return fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": " + arg + " lives on device " + std::to_string(at.device) + ", the handle on device " + std::to_string(s->device));
+    return CALIPSO_OK;
+}
+#define DEVPTR(entry, p) do { const int rc__ = device_pointer(s, (const void*)(p), entry, #p); if (rc__ < 0) return rc__; } while (0)
+
+int sparse_failed(KH* s, int rc, const char* what) { return fail(s, rc, std::string(what) + ": " + calipso_hip_sparse_last_error(s->sp)); }
+
+int values_missing(KH* s, const char* entry) {
+    static const char* const names[5] = {"Lxx", "gx", "hx", "w", "penalty"};
+    const size_t need[5] = {(size_t)s->d.nnzL, (size_t)s->d.nnzg, (size_t)s->d.nnzh, (size_t)s->d.N, (size_t)(s->d.ne > 0)};
+    for (int i = 0; i < 5; ++i) if (need[i] && !s->have[i]) return fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": no " + names[i] + " resident (calipso_hip_sparse_kkt_set_values first)");
+    return CALIPSO_OK;
+}
+
+int set_values(KH* s, const double* Lxx, const double* gx, const double* hx, const double* w, const double* penalty, hipMemcpyKind kind) {
+    KK(hipSetDevice(s->device));
+    const double* src[5] = {Lxx, gx, hx, w, penalty};
+    double* dst[5] = {s->Lxx, s->gx, s->hx, s->w, s->rho};
+    const size_t count[5] = {(size_t)s->d.nnzL, (size_t)s->d.nnzg, (size_t)s->d.nnzh, (size_t)s->d.N, 1};
+    for (int i = 0; i < 5; ++i) if (src[i] && count[i]) { KK(hipMemcpyAsync(dst[i], src[i], sizeof(double) * count[i], kind, s->st)); s->have[i] = true; }
+    KK(hipStreamSynchronize(s->st));
+    s->assembled = false; s->factored = false;      // K and its factor belong to the values before
+    return CALIPSO_OK;
+}
+
+void enqueue_assemble(KH* s, double ep, double ed) {
+    const long long items = (long long)s->d.nnzL + s->d.nnzg + s->d.nnzh + s->d.nx + s->d.ne + s->d.nc + s->d.ncc;
+    hipLaunchKernelGGL(k_kkt_assemble, dim3(blocks(items)), dim3(KT), 0, s->st, s->d, ep, ed, s->K);
+}
+// one assemble + factorisation at (ep, ed); inertia as compute_inertia! (linear_solver.jl:33-44)
+int assemble_factorize(KH* s, double ep, double ed, int64_t inertia[3]) {
+    KK(hipEventRecord(s->ev[0], s->st));
+    enqueue_assemble(s, ep, ed);
+    KK(hipEventRecord(s->ev[1], s->st));
+    s->sc.ep = ep; s->sc.ed = ed; s->assembled = true; s->factored = false;
+    const int rc = calipso_hip_sparse_factorize_device(s->sp, s->K, inertia);      // (returns synchronised)
+    if (rc < 0) return sparse_failed(s, rc, "factorize");
+    s->factored = true;
+    float ms = 0.f; KK(hipEventElapsedTime(&ms, s->ev[0], s->ev[1])); s->ms[0] += ms;
+    double t[2] = {0.0, 0.0}; (void)calipso_hip_sparse_timing(s->sp, t); s->ms[1] += t[0];
+    return rc;
+}
+// search_direction_symmetric! (search_direction.jl:25-104) with the current factorisation: out (N) from res (N), both on the device
+int solve_symmetric(KH* s, const double* res, double* out, double* ms) {
+    KK(hipEventRecord(s->ev[0], s->st));
+    hipLaunchKernelGGL(k_kkt_residual_symmetric, dim3(blocks((long long)s->d.n + s->d.nsoc)), dim3(KT), 0, s->st, s->d, s->sc.ep, s->sc.ed, res, s->rsym);
+    const int rc = calipso_hip_sparse_solve_device(s->sp, 1, s->rsym, s->dsym);
+    if (rc < 0) return sparse_failed(s, rc, "solve");
+    hipLaunchKernelGGL(k_kkt_recover, dim3(blocks((long long)s->d.n + s->d.nsoc)), dim3(KT), 0, s->st, s->d, s->sc.ep, s->sc.ed, s->dsym, res, out);
+    KK(hipEventRecord(s->ev[1], s->st));
+    KK(hipStreamSynchronize(s->st));
+    float t = 0.f; KK(hipEventElapsedTime(&t, s->ev[0], s->ev[1])); *ms += t;
+    return CALIPSO_OK;
+}
+void enqueue_mul(KH* s, const double* v, const Sink& sink) {
+    if (s->wave_rows) hipLaunchKernelGGL(k_kkt_mul_gathered<true>, dim3(blocks(s->d.n, KT / 64)), dim3(KT), 0, s->st, s->d, s->sc.ep, s->sc.ed, v, sink);
+    else hipLaunchKernelGGL(k_kkt_mul_gathered<false>, dim3(blocks(s->d.n)), dim3(KT), 0, s->st, s->d, s->sc.ep, s->sc.ed, v, sink);
+    if (s->d.ne + s->d.nc > 0) hipLaunchKernelGGL(k_kkt_mul_local, dim3(blocks((long long)s->d.ne + 2ll * s->d.nc)), dim3(KT), 0, s->st, s->d, s->sc.ep, s->sc.ed, v, sink);
+}
+// err = res - H step and its infinity norm: one double comes back
+int residual_error(KH* s, const double* res, const double* step, double* norm) {
+    KK(hipEventRecord(s->ev[0], s->st));
+    KK(hipMemsetAsync(s->norm, 0, sizeof(double), s->st));
+    enqueue_mul(s, step, Sink{nullptr, res, s->err, reinterpret_cast<unsigned long long*>(s->norm)});
+    KK(hipEventRecord(s->ev[1], s->st));
+    KK(hipMemcpyAsync(norm, s->norm, sizeof(double), hipMemcpyDeviceToHost, s->st));
+    KK(hipStreamSynchronize(s->st));
+    float t = 0.f; KK(hipEventElapsedTime(&t, s->ev[0], s->ev[1])); s->ms[4] += t;
+    return CALIPSO_OK;
+}
+
+// search_direction! (search_direction.jl:1-23) on device vectors
+int search_direction(KH* s, const double* res, double* step, double regularization[3], double info[4]) {
+    const auto wall0 = std::chrono::steady_clock::now();
+    for (double& m : s->ms) m = 0.0;
+    const Options& o = s->opt;
+    Scalars& sc = s->sc;
+    sc.ep_last = regularization[1];
+    const auto leave = [&](int rc, double nfact, double rounds, double norm) {
+        regularization[0] = sc.ep; regularization[1] = sc.ep_last; regularization[2] = sc.ed;
+        if (info) { info[0] = nfact; info[1] = rounds; info[2] = norm; info[3] = 0.0; }
+        s->ms[5] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+        return rc;
+    };
+    // inertia_correction! (inertia.jl:30-80)
+    calipso::ic_begin(o, sc);
+    int nfact = 0;
+    for (bool first = true;; first = false) {
+        int64_t in[3] = {0, 0, 0};
+        const double ep = sc.ep, ed = sc.ed;
+        const int rc = assemble_factorize(s, ep, ed, in);
+        if (rc < 0) return leave(rc, nfact, 0, 0.0);
+        ++nfact;
+        const calipso::IcVerdict v = calipso::ic_after(o, sc, in, s->d.nx, (i64)s->d.ne + s->d.nc, first);
+        if (v == calipso::IC_DONE) break;
+        if (v == calipso::IC_FAILED) { fail(s, CALIPSO_ERR_INERTIA, "inertia correction failure (inertia.jl:72)"); return leave(CALIPSO_ERR_INERTIA, nfact, 0, 0.0); }
+    }
+    int rc = solve_symmetric(s, res, step, &s->ms[2]);
+    if (rc < 0) return leave(rc, nfact, 0, 0.0);
+    if (!o.iterative_refinement) return leave(CALIPSO_OK, nfact, 0, 0.0);
+    // iterative_refinement! (iterative_refinement.jl:1-52)
+    double norm = 0.0;
+    if ((rc = residual_error(s, res, step, &norm)) < 0) return leave(rc, nfact, 0, 0.0);
+    const double norm0 = norm;
+    int it = 0, status = CALIPSO_OK;
+    for (;;) {
+        const calipso::RefineVerdict v = calipso::refine_next(o, norm, norm0, &it);
+        if (v == calipso::REFINE_DONE) break;
+        if (v == calipso::REFINE_FAILED) { status = CALIPSO_WARN_REFINEMENT; break; }      // the reference goes on to `H \ residual` (search_direction.jl:22): not here
+        if ((rc = solve_symmetric(s, s->err, s->corr, &s->ms[3])) < 0) return leave(rc, nfact, it, norm);
+        hipLaunchKernelGGL(k_kkt_add,dim3(blocks(s->d.N)), dim3(KT), 0, s->st, s->d.N, step, s->corr);
+        if ((rc = residual_error(s, res, step, &norm)) < 0) return leave(rc, nfact, it, norm);
+        ++it;
+    }
+    KK(hipGetLastError());
+    return leave(status, nfact, it, norm);
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* calipso_hip_sparse_kkt_last_error(calipso_hip_sparse_kkt* s) { return s ? s->err_text.c_str() : g_kkt_err.c_str(); }
+
+int32_t calipso_hip_sparse_kkt_destroy(calipso_hip_sparse_kkt* s) {
+    if (!s) return CALIPSO_OK;
+    (void)hipSetDevice(s->device);
+    if (s->st) (void)hipStreamSynchronize(s->st);
+    for (void* p : s->dev) if (p) (void)hipFree(p);
+    for (hipEvent_t e : s->ev) if (e) (void)hipEventDestroy(e);
+    if (s->sp) (void)calipso_hip_sparse_destroy(s->sp);
+    delete s;
+    return CALIPSO_OK;
+}
+
+static int32_t kkt_create_impl(KH* s, int32_t method, const int64_t* perm) {
+    const Analysis& a = s->an;
+    KK(hipSetDevice(s->device));
+    const int rc0 = calipso_hip_sparse_create(a.n, a.colptr.data(), a.rowval.data(), method, perm, s->device, &s->sp);
+    if (rc0 != CALIPSO_OK) return fail(s, rc0, std::string("calipso_hip_sparse_create: ") + calipso_hip_sparse_last_error(s->sp));
+    s->st = calipso::sparse_stream(s->sp);
+    KK(hipEventCreate(&s->ev[0])); KK(hipEventCreate(&s->ev[1]));
+    KktDev& d = s->d;
+    d.nx = (int)a.nx; d.ne = (int)a.ne; d.nc = (int)a.nc; d.n = (int)a.n; d.N = (int)a.N; d.q = (int)a.n_nonnegative; d.nsoc = (int)a.n_soc; d.ncc = (int)a.n_cone_columns;
+    d.o_r = d.nx; d.o_s = d.nx + d.ne; d.o_y = d.o_s + d.nc; d.o_z = d.o_y + d.ne; d.o_t = d.o_z + d.nc;
+    d.nnzL = (int)a.slot_Lxx.size(); d.nnzg = (int)a.slot_gx.size(); d.nnzh = (int)a.slot_hx.size();
+    std::vector<int> slotL = a.slot_Lxx;                    // the diagonal's entries are written with ep, by the diagonal's own items
+    for (i64 j = 0; j < a.nx; ++j) if (a.diag_x_src[(size_t)j] >= 0) slotL[(size_t)a.diag_x_src[(size_t)j]] = -1;
+    std::vector<int> row_cone((size_t)a.nc, -2);
+    for (i64 c = 0; c < a.n_nonnegative; ++c) row_cone[(size_t)c] = -1;
+    for (i64 j = 0; j < a.n_soc; ++j) for (int i = 0; i < a.soc_dim[(size_t)j]; ++i) row_cone[(size_t)(a.soc_start[(size_t)j] + i)] = (int)j;
+    int rc;
+    if ((rc = upload(s, slotL, &d.slotL)) || (rc = upload(s, a.slot_gx, &d.slotg)) || (rc = upload(s, a.slot_hx, &d.sloth)) || (rc = upload(s, a.diag_x, &d.diag_x)) ||
+        (rc = upload(s, a.diag_x_src, &d.diag_x_src)) || (rc = upload(s, a.diag_e, &d.diag_e)) || (rc = upload(s, a.diag_c, &d.diag_c)) || (rc = upload(s, row_cone, &d.row_cone)) ||
+        (rc = upload(s, a.soc_start, &d.soc_start)) || (rc = upload(s, a.soc_dim, &d.soc_dim)) || (rc = upload(s, a.col_cone, &d.col_cone)) ||
+        (rc = upload(s, a.col_index, &d.col_index)) || (rc = upload(s, a.col_slot, &d.col_slot)) ||
+        (rc = upload(s, a.Lxx_rows.ptr, &d.Lr.ptr)) || (rc = upload(s, a.Lxx_rows.col, &d.Lr.idx)) || (rc = upload(s, a.Lxx_rows.src, &d.Lr.src)) ||
+        (rc = upload(s, a.gx_rows.ptr, &d.gr.ptr)) || (rc = upload(s, a.gx_rows.col, &d.gr.idx)) || (rc = upload(s, a.gx_rows.src, &d.gr.src)) ||
+        (rc = upload(s, a.hx_rows.ptr, &d.hr.ptr)) || (rc = upload(s, a.hx_rows.col, &d.hr.idx)) || (rc = upload(s, a.hx_rows.src, &d.hr.src)) ||
+        (rc = upload(s, a.gx_cols.ptr, &d.gc.ptr)) || (rc = upload(s, a.gx_cols.row, &d.gc.idx)) || (rc = upload(s, a.hx_cols.ptr, &d.hc.ptr)) || (rc = upload(s, a.hx_cols.row, &d.hc.idx)))
+        return rc;
+    d.gc.src = nullptr; d.hc.src = nullptr;
+    if ((rc = reserve(s, &s->Lxx, (size_t)d.nnzL)) || (rc = reserve(s, &s->gx, (size_t)d.nnzg)) || (rc = reserve(s, &s->hx, (size_t)d.nnzh)) || (rc = reserve(s, &s->w, (size_t)d.N)) ||
+        (rc = reserve(s, &s->rho, 1)) || (rc = reserve(s, &s->K, (size_t)a.nnzK())) || (rc = reserve(s, &s->res, (size_t)d.N)) || (rc = reserve(s, &s->step, (size_t)d.N)) ||
+        (rc = reserve(s, &s->corr, (size_t)d.N)) || (rc = reserve(s, &s->err, (size_t)d.N)) || (rc = reserve(s, &s->rsym, (size_t)d.n)) || (rc = reserve(s, &s->dsym, (size_t)d.n)) ||
+        (rc = reserve(s, &s->norm, 1))) return rc;
+    d.Lxx = s->Lxx; d.gx = s->gx; d.hx = s->hx; d.w = s->w; d.rho = s->rho;
+    // a wavefront per gathered row where the rows are long (a dense-pattern problem), a thread per row where they are short (stage-structured ones)
+    s->wave_rows = ((long long)d.nnzL + 2ll * d.nnzg + 2ll * d.nnzh) / std::max(d.n, 1) >= WAVE_ROW_MIN;
+    return CALIPSO_OK;
+}
+
+int32_t calipso_hip_sparse_kkt_create(int64_t nx, int64_t ne, int64_t nc, int64_t n_nonnegative, int64_t n_soc, const int64_t* dims, const int64_t* Lxx_colptr,
+                                      const int64_t* Lxx_rowval, const int64_t* gx_colptr, const int64_t* gx_rowval, const int64_t* hx_colptr, const int64_t* hx_rowval,
+                                      int32_t method, const int64_t* perm, int32_t device, calipso_hip_sparse_kkt** out) {
+    if (!out) return CALIPSO_ERR_ARGUMENT;
+    *out = nullptr;
+    if (method < 0 || method > 5 || (method == 3 && !perm)) return fail(nullptr, CALIPSO_ERR_ARGUMENT, "calipso_hip_sparse_kkt_create: method is 0 .. 5, and 3 comes with a perm");
+    Analysis a = analyse(nx, ne, nc, n_nonnegative, n_soc, dims, Lxx_colptr, Lxx_rowval, gx_colptr, gx_rowval, hx_colptr, hx_rowval);
+    if (a.status) return fail(nullptr, a.status, "calipso_hip_sparse_kkt_create: " + a.message);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return fail(nullptr, CALIPSO_ERR_HIP, "no HIP device available (libcalipso_hip has no CPU path)"); }
+    if (device < 0 || device >= ndev) return fail(nullptr, CALIPSO_ERR_ARGUMENT, "device ordinal out of range");
+    KH* s = new KH();
+    s->an = std::move(a); s->device = device;
+    const int32_t rc = kkt_create_impl(s, method, perm);
+    if (rc != CALIPSO_OK) { g_kkt_err = s->err_text; (void)calipso_hip_sparse_kkt_destroy(s); return rc; }      // no half-built handle leaves here
+    *out = s;
+    return CALIPSO_OK;
+}
+
+int32_t calipso_hip_sparse_kkt_info(calipso_hip_sparse_kkt* s, int64_t info[8]) {
+    if (!s || !info) return CALIPSO_ERR_ARGUMENT;
+    int64_t sp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    (void)calipso_hip_sparse_info(s->sp, sp);
+    info[0] = s->an.n; info[1] = s->an.nnzK(); info[2] = sp[2]; info[3] = sp[3]; info[4] = sp[7]; info[5] = 1; info[6] = s->an.max_dim; info[7] = s->an.N;
+    return CALIPSO_OK;
+}
+
+int32_t calipso_hip_sparse_kkt_pattern(calipso_hip_sparse_kkt* s, int64_t* colptr, int64_t* rowval) {
+    if (!s) return CALIPSO_ERR_ARGUMENT;
+    if (colptr) std::copy(s->an.colptr.begin(), s->an.colptr.end(), colptr);
+    if (rowval) std::copy(s->an.rowval.begin(), s->an.rowval.end(), rowval);
+    return CALIPSO_OK;
+}
+
+int32_t calipso_hip_sparse_kkt_set_option(calipso_hip_sparse_kkt* s, const char* name, double value) {
+    if (!s || !name) return CALIPSO_ERR_ARGUMENT;
+    if (calipso::set_search_direction_option(s->opt, name, value)) return CALIPSO_OK;
+    if (std::string(name) == "central_path") { s->sc.kappa = value; return CALIPSO_OK; }      // (the solver's scalar, not an option: IC-2 reads it, inertia.jl:44)
+    return fail(s, CALIPSO_ERR_ARGUMENT, std::string("calipso_hip_sparse_kkt_set_option: unknown option ") + name);
+}
+
+int32_t calipso_hip_sparse_kkt_set_values(calipso_hip_sparse_kkt* s, const double* Lxx, const double* gx, const double* hx, const double* w, const double* penalty) {
+    if (!s) return CALIPSO_ERR_ARGUMENT;
+    return set_values(s, Lxx, gx, hx, w, penalty, hipMemcpyHostToDevice);
+}
+int32_t calipso_hip_sparse_kkt_set_values_device(calipso_hip_sparse_kkt* s, const double* Lxx, const double* gx, const double* hx, const double* w, const double* penalty) {
+    if (!s) return CALIPSO_ERR_ARGUMENT;
+    KK(hipSetDevice(s->device));
+    static const char* const entry = "calipso_hip_sparse_kkt_set_values_device";
+    DEVPTR(entry, Lxx); DEVPTR(entry, gx); DEVPTR(entry, hx); DEVPTR(entry, w); DEVPTR(entry, penalty);
+    return set_values(s, Lxx, gx, hx, w, penalty, hipMemcpyDeviceToDevice);
+}
+
+int32_t calipso_hip_sparse_kkt_factorize(calipso_hip_sparse_kkt* s, double ep, double ed, int64_t inertia[3]) {
+    if (!s) return CALIPSO_ERR_ARGUMENT;
+    KK(hipSetDevice(s->device));
+    { const int rc = values_missing(s, "calipso_hip_sparse_kkt_factorize"); if (rc < 0) return rc; }
+    int64_t in[3] = {0, 0, 0};
+    const int rc = assemble_factorize(s, ep, ed, in);
+    if (inertia) std::copy(in, in + 3, inertia);
+    return rc;
+}
+
+int32_t calipso_hip_sparse_kkt_get_matrix(calipso_hip_sparse_kkt* s, double* nzval) {
+    if (!s || !nzval) return CALIPSO_ERR_ARGUMENT;
+    if (!s->assembled) return fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_sparse_kkt_get_matrix: factorize first");
+    KK(hipSetDevice(s->device));
+    KK(hipMemcpyAsync(nzval, s->K, sizeof(double) * (size_t)s->an.nnzK(), hipMemcpyDeviceToHost, s->st));
+    KK(hipStreamSynchronize(s->st));
+    return CALIPSO_OK;
+}
+
+int32_t calipso_hip_sparse_kkt_mul(calipso_hip_sparse_kkt* s, const double* v, double* out) {
+    if (!s || !v || !out) return CALIPSO_ERR_ARGUMENT;
+    if (!s->assembled) return fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_sparse_kkt_mul: factorize first (H is taken at the regularisation of the last assemble)");
+    KK(hipSetDevice(s->device));
+    const size_t bytes = sizeof(double) * (size_t)s->d.N;
+    KK(hipMemcpyAsync(s->corr, v, bytes, hipMemcpyHostToDevice, s->st));
+    KK(hipMemsetAsync(s->err, 0, bytes, s->st));
+    enqueue_mul(s, s->corr, Sink{s->err, nullptr, nullptr, nullptr});
+    KK(hipMemcpyAsync(out, s->err, bytes, hipMemcpyDeviceToHost, s->st));
+    KK(hipStreamSynchronize(s->st));
+    KK(hipGetLastError());
+    return CALIPSO_OK;
+}
+
+int32_t calipso_hip_sparse_kkt_solve_symmetric(calipso_hip_sparse_kkt* s, const double* residual, double* step) {
+    if (!s || !residual || !step) return CALIPSO_ERR_ARGUMENT;
+    if (!s->factored) return fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_sparse_kkt_solve_symmetric: factorize first");
+    KK(hipSetDevice(s->device));
+    const size_t bytes = sizeof(double) * (size_t)s->d.N;
+    KK(hipMemcpyAsync(s->res, residual, bytes, hipMemcpyHostToDevice, s->st));
+    double ms = 0.0;
+    const int rc = solve_symmetric(s, s->res, s->step, &ms);
+    if (rc < 0) return rc;
+    KK(hipMemcpyAsync(step, s->step, bytes, hipMemcpyDeviceToHost, s->st));
+    KK(hipStreamSynchronize(s->st));
+    KK(hipGetLastError());
+    return CALIPSO_OK;
+}
+
+int32_t calipso_hip_sparse_kkt_search_direction(calipso_hip_sparse_kkt* s, const double* residual, double* step, double regularization[3], double info[4]) {
+    if (!s || !residual || !step || !regularization) return fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_sparse_kkt_search_direction: residual, step and regularization are required");
+    KK(hipSetDevice(s->device));
+    { const int rc = values_missing(s, "calipso_hip_sparse_kkt_search_direction"); if (rc < 0) return rc; }
+    const size_t bytes = sizeof(double) * (size_t)s->d.N;
+    KK(hipMemcpyAsync(s->res, residual, bytes, hipMemcpyHostToDevice, s->st));
+    const int rc = search_direction(s, s->res, s->step, regularization, info);
+    if (rc < 0) return rc;
+    KK(hipMemcpyAsync(step, s->step, bytes, hipMemcpyDeviceToHost, s->st));
+    KK(hipStreamSynchronize(s->st));
+    return rc;
+}
+int32_t calipso_hip_sparse_kkt_search_direction_device(calipso_hip_sparse_kkt* s, const double* residual, double* step, double regularization[3], double info[4]) {
+    if (!s || !residual || !step || !regularization) return fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_sparse_kkt_search_direction_device: residual, step and regularization are required");
+    KK(hipSetDevice(s->device));
+    static const char* const entry = "calipso_hip_sparse_kkt_search_direction_device";
+    DEVPTR(entry, residual); DEVPTR(entry, step);
+    { const int rc = values_missing(s, entry); if (rc < 0) return rc; }
+    return search_direction(s, residual, step, regularization, info);
+}
+
+int32_t calipso_hip_sparse_kkt_timing(calipso_hip_sparse_kkt* s, double ms[8]) {
+    if (!s || !ms) return CALIPSO_ERR_ARGUMENT;
+    std::copy(s->ms, s->ms + 8, ms);
+    return CALIPSO_OK;
+}
+
+}  // extern "C"

@@ -424,6 +424,74 @@ function CALIPSO.linear_solve!(s::HIPSparseLDLSolver, x::VecOrMat{Float64}, A::S
     return
 end
 
+# ---- search_direction! on sparse problem data resident on the device (csrc/sparse_kkt.hip): ccall wrappers, no logic ---------------------------------
+"""
+    SparseKKT(Lxx, gx, hx; n_nonnegative, second_order_dims, method=:nested_dissection, perm=nothing)
+
+search_direction! (search_direction.jl:1-23) for a problem whose Lagrangian Hessian `Lxx` (both triangles) and Jacobians `gx`, `hx` are sparse and stay on the
+device: `set_values!`, then `sparse_search_direction!(kkt, residual, step, regularization)` with `regularization = [εp, εp_last, εd]`, in and out.  Returns
+`(status, info)`: status 2 = the refinement failed and `step` is the last refined step (there is no `H \\ residual` fallback).
+"""
+mutable struct SparseKKT
+    handle::Ptr{Cvoid}
+    N::Int
+    nnz_upper::Int
+end
+kkt_last_error(h) = unsafe_string(ccall((:calipso_hip_sparse_kkt_last_error, lib), Cstring, (Ptr{Cvoid},), h))
+kkt_check(rc, k, what) = rc < 0 ? throw(HIPError(rc, "$what: $(kkt_last_error(k.handle))")) : rc
+
+function SparseKKT(Lxx::SparseMatrixCSC{Float64,Int}, gx::SparseMatrixCSC{Float64,Int}, hx::SparseMatrixCSC{Float64,Int}; n_nonnegative::Integer,
+                   second_order_dims::Vector{Int}=Int[], method::Symbol=:nested_dissection, perm::Union{Nothing,Vector{Int}}=nothing, device::Integer=0)
+    href = Ref{Ptr{Cvoid}}(C_NULL)
+    rc = ccall((:calipso_hip_sparse_kkt_create, lib), Int32,
+               (Int64, Int64, Int64, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Int32, Ptr{Int64}, Int32, Ptr{Ptr{Cvoid}}),
+               size(Lxx, 1), size(gx, 1), size(hx, 1), n_nonnegative, length(second_order_dims), second_order_dims, Lxx.colptr, Lxx.rowval, gx.colptr, gx.rowval,
+               hx.colptr, hx.rowval, perm === nothing ? SPARSE_METHODS[method] : 3, perm === nothing ? C_NULL : perm, device, href)
+    rc != 0 && throw(HIPError(rc, "calipso_hip_sparse_kkt_create: $(kkt_last_error(C_NULL))"))
+    info = zeros(Int64, 8)
+    ccall((:calipso_hip_sparse_kkt_info, lib), Int32, (Ptr{Cvoid}, Ptr{Int64}), href[], info)
+    k = SparseKKT(href[], info[8], info[2])
+    finalizer(x -> ccall((:calipso_hip_sparse_kkt_destroy, lib), Int32, (Ptr{Cvoid},), x.handle), k)
+    return k
+end
+kkt_info(k::SparseKKT) = (info = zeros(Int64, 8); kkt_check(ccall((:calipso_hip_sparse_kkt_info, lib), Int32, (Ptr{Cvoid}, Ptr{Int64}), k.handle, info), k, "info"); info)
+kkt_pattern(k::SparseKKT, colptr::Vector{Int64}, rowval::Vector{Int64}) =
+    kkt_check(ccall((:calipso_hip_sparse_kkt_pattern, lib), Int32, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}), k.handle, colptr, rowval), k, "pattern")
+set_option!(k::SparseKKT, name::AbstractString, value::Real) =
+    kkt_check(ccall((:calipso_hip_sparse_kkt_set_option, lib), Int32, (Ptr{Cvoid}, Cstring, Float64), k.handle, name, value), k, "set_option!($name)")
+kkt_ptr(a) = a === nothing ? Ptr{Float64}(C_NULL) : pointer(a)
+# host arrays (nothing keeps what is resident); penalty: a one-element vector
+set_values!(k::SparseKKT; Lxx=nothing, gx=nothing, hx=nothing, w=nothing, penalty=nothing) = GC.@preserve Lxx gx hx w penalty kkt_check(
+    ccall((:calipso_hip_sparse_kkt_set_values, lib), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+          k.handle, kkt_ptr(Lxx), kkt_ptr(gx), kkt_ptr(hx), kkt_ptr(w), kkt_ptr(penalty)), k, "set_values!")
+# device pointers on the handle's device (C_NULL keeps what is resident)
+set_values_device!(k::SparseKKT; Lxx=C_NULL, gx=C_NULL, hx=C_NULL, w=C_NULL, penalty=C_NULL) = kkt_check(
+    ccall((:calipso_hip_sparse_kkt_set_values_device, lib), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), k.handle, Lxx, gx, hx, w, penalty),
+    k, "set_values_device!")
+function kkt_factorize!(k::SparseKKT, ep::Real, ed::Real)
+    out = zeros(Int64, 3)
+    rc = kkt_check(ccall((:calipso_hip_sparse_kkt_factorize, lib), Int32, (Ptr{Cvoid}, Float64, Float64, Ptr{Int64}), k.handle, ep, ed, out), k, "factorize")
+    return rc, out
+end
+kkt_matrix!(k::SparseKKT, nzval::Vector{Float64}) = kkt_check(ccall((:calipso_hip_sparse_kkt_get_matrix, lib), Int32, (Ptr{Cvoid}, Ptr{Float64}), k.handle, nzval), k, "get_matrix")
+kkt_mul!(k::SparseKKT, out::Vector{Float64}, v::Vector{Float64}) =
+    kkt_check(ccall((:calipso_hip_sparse_kkt_mul, lib), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), k.handle, v, out), k, "mul")
+solve_symmetric!(k::SparseKKT, step::Vector{Float64}, residual::Vector{Float64}) =
+    kkt_check(ccall((:calipso_hip_sparse_kkt_solve_symmetric, lib), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), k.handle, residual, step), k, "solve_symmetric")
+function sparse_search_direction!(k::SparseKKT, residual::Vector{Float64}, step::Vector{Float64}, regularization::Vector{Float64})
+    info = zeros(4)
+    rc = kkt_check(ccall((:calipso_hip_sparse_kkt_search_direction, lib), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                         k.handle, residual, step, regularization, info), k, "search_direction!")
+    return rc, info
+end
+function sparse_search_direction_device!(k::SparseKKT, residual::Ptr{Cvoid}, step::Ptr{Cvoid}, regularization::Vector{Float64})
+    info = zeros(4)
+    rc = kkt_check(ccall((:calipso_hip_sparse_kkt_search_direction_device, lib), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}),
+                         k.handle, residual, step, regularization, info), k, "search_direction_device!")
+    return rc, info
+end
+kkt_timing(k::SparseKKT) = (ms = zeros(8); kkt_check(ccall((:calipso_hip_sparse_kkt_timing, lib), Int32, (Ptr{Cvoid}, Ptr{Float64}), k.handle, ms), k, "timing"); ms)
+
 # The handle-resident variant: the KKT blocks are already on the device (uploaded by the evaluation callback or by set_field!), the
 # condensed matrix is never formed on the host.  factorize! = calipso_hip_factorize on those blocks with the handle's kappa / rho /
 # regularisation scalars (which the caller syncs with sync_scalars!); `A` is accepted for signature parity only.
@@ -826,6 +894,7 @@ function allreduce_sum!(c::HIPComm, v::Vector{Float64})
     return v
 end
 
+export SparseKKT, set_values!, set_values_device!, kkt_info, kkt_pattern, kkt_factorize!, kkt_matrix!, kkt_mul!, solve_symmetric!, sparse_search_direction!, sparse_search_direction_device!, kkt_timing
 export HIPSolver, streams_concurrent, rebind_stream!, spread_streams!, HIPLDLSolver, HIPSparseLDLSolver, hip_sparse_ldl_solver, HIPKKTSolver, hip_ldl_solver, HIPGroup, HIPSmallNewton, set_option!, set_cones!, set_qp!, set_evaluator!, set_parameters!, differentiate_adjoint!, solution, set_stream!, set_qp_device!, initialize_device!, set_state_device!, set_parameters_device!, solve_device!, solution_device!, differentiate_adjoint_device!, HIPComm, comm_unique_id, comm_size, gather_status, allreduce_sum!, newton_step!,
        search_direction_nonsymmetric!, analyze_structure!, clear_structure!, set_stage_parallel!, set_stage_blocks!, declared_structure, kernel_times, sync_scalars!, copy_back!
 

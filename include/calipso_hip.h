@@ -517,6 +517,56 @@ int32_t calipso_hip_sparse_solve_device(calipso_hip_sparse*, int64_t nrhs, const
 int32_t calipso_hip_sparse_get_factor(calipso_hip_sparse*, int64_t* perm, int64_t* Lp, int64_t* Li, double* Lx, double* D);
 int32_t calipso_hip_sparse_timing(calipso_hip_sparse*, double ms[2]);
 
+/* ---- search_direction! on sparse problem data resident on the device (csrc/sparse_kkt.hip; analysis: csrc/sparse_kkt.hpp) ---------------------------
+ * The linear-algebra half of a sparse solve!: search_direction! (src/solver/search_direction.jl:1-23) for a problem whose Lagrangian Hessian and Jacobians
+ * are SPARSE and stay on the device — no nx x nx or (ne + nc) x nx array exists anywhere.  Sparse non-zeros, a point w (layout of point.jl:13-22,
+ * N = nx + 2 ne + 3 nc) and a residual go in; the step, the regularisation it ended with and the work it took come out.  One system per handle.
+ * Patterns are Julia SparseMatrixCSC patterns (1-based Int64, rows ascending and duplicate-free within a column; else CALIPSO_ERR_ARGUMENT and a text):
+ * Lxx (nx x nx: the full Lagrangian Hessian, BOTH triangles, as the reference holds it), gx (ne x nx), hx (nc x nx).  Cone layout as
+ * calipso_hip_smallnewton_set_cones: n_nonnegative rows, then n_soc contiguous second-order cones of dims[j] >= 2 — of ANY dimension: the blocks are formed
+ * column by column through the closed form of second_order_matrix_inverse (cones/second_order.jl:50-65), O(dimension) per column.
+ *   create          the pattern of triu(K) of jacobian_variables_symmetric (solver.jl:88-122 obtains it from a warm-up assembly) + qdldl(K; perm) analyse
+ *                   (qdldl.jl:134-188) through calipso_hip_sparse_create: method / perm as there.  Without a HIP device: CALIPSO_ERR_HIP, "no HIP device".
+ *   info            info[8] = n, nnz(triu K), nnz(L), tree levels, numeric phase (as calipso_hip_sparse_info), launches of one assemble, largest cone dimension, N
+ *   pattern         colptr[n + 1], rowval[nnz(triu K)] of triu(K), 1-based, in the order idx.variables, idx.symmetric_equality, idx.symmetric_cone (indices.jl:20-63)
+ *   set_option      the regularisation and refinement options of options.jl:6-59 by name (include/calipso_options.hpp: set_search_direction_option), and
+ *                   "central_path": the solver's scalar that IC-2 reads (inertia.jl:44)
+ *   set_values      nzval of Lxx, gx, hx in the patterns' order, the point w (N), the penalty rho (1): host arrays, or (_device) device pointers on the handle's
+ *                   device — a host or foreign pointer there is CALIPSO_ERR_ARGUMENT naming the argument.  NULL keeps what is resident.
+ *   factorize       residual_jacobian_variables! + residual_jacobian_variables_symmetric! (residual_jacobian_variables.jl:1-167) at the given (ep, ed), on the
+ *                   device and without forming H, then factorize! + compute_inertia! (linear_solver.jl:19-44); CALIPSO_WARN_ZERO_PIVOT as calipso_hip_sparse_factorize
+ *   get_matrix      K.nzval of the last assemble (jacobian_variables_symmetric, upper triangle)
+ *   mul             out = H v for the unreduced N x N matrix at the regularisation of the last assemble (mul!(e, H, v), iterative_refinement.jl:9,39)
+ *   solve_symmetric search_direction_symmetric! (search_direction.jl:25-104): residual_symmetric! (residual.jl:53-101), linear_solve! with the current
+ *                   factorisation, the recovery of the r-, s- and t-parts (search_direction.jl:59-101)
+ *   search_direction  search_direction! whole: inertia_correction! (inertia.jl:30-80; every retry one assemble + one factorisation), search_direction_symmetric!,
+ *                   iterative_refinement! (iterative_refinement.jl:1-52; a round reads back one double).  regularization = [ep, ep_last, ed], in and out:
+ *                   ep_last is what the caller carries from call to call (primal_regularization_last).  info = [factorisations, refinement rounds,
+ *                   |residual - H step|_inf at exit, 0].  (_device: residual and step are device pointers.)  Returns CALIPSO_OK, CALIPSO_ERR_INERTIA,
+ *                   CALIPSO_ERR_ARGUMENT, CALIPSO_ERR_HIP, or CALIPSO_WARN_REFINEMENT: where the reference's refinement fails it goes on to `H \ residual`
+ *                   (search_direction.jl:22) — there is NO such fallback here; the call returns the warning with the last refined step in place, and the handle
+ *                   stays usable.
+ *   timing          ms[8] of the last search_direction, HIP events on the handle's stream: [assembles, factorisations, first solve, refinement solves,
+ *                   H v + norm of all rounds, wall-clock of the call, 0, 0] */
+typedef struct calipso_hip_sparse_kkt calipso_hip_sparse_kkt;
+int32_t calipso_hip_sparse_kkt_create(int64_t nx, int64_t ne, int64_t nc, int64_t n_nonnegative, int64_t n_soc, const int64_t* dims, const int64_t* Lxx_colptr,
+                                      const int64_t* Lxx_rowval, const int64_t* gx_colptr, const int64_t* gx_rowval, const int64_t* hx_colptr, const int64_t* hx_rowval,
+                                      int32_t method, const int64_t* perm, int32_t device, calipso_hip_sparse_kkt** out);
+int32_t calipso_hip_sparse_kkt_destroy(calipso_hip_sparse_kkt*);
+const char* calipso_hip_sparse_kkt_last_error(calipso_hip_sparse_kkt*);
+int32_t calipso_hip_sparse_kkt_info(calipso_hip_sparse_kkt*, int64_t info[8]);
+int32_t calipso_hip_sparse_kkt_pattern(calipso_hip_sparse_kkt*, int64_t* colptr, int64_t* rowval);
+int32_t calipso_hip_sparse_kkt_set_option(calipso_hip_sparse_kkt*, const char* name, double value);
+int32_t calipso_hip_sparse_kkt_set_values(calipso_hip_sparse_kkt*, const double* Lxx, const double* gx, const double* hx, const double* w, const double* penalty);
+int32_t calipso_hip_sparse_kkt_set_values_device(calipso_hip_sparse_kkt*, const double* Lxx, const double* gx, const double* hx, const double* w, const double* penalty);
+int32_t calipso_hip_sparse_kkt_factorize(calipso_hip_sparse_kkt*, double ep, double ed, int64_t inertia[3]);
+int32_t calipso_hip_sparse_kkt_get_matrix(calipso_hip_sparse_kkt*, double* nzval);
+int32_t calipso_hip_sparse_kkt_mul(calipso_hip_sparse_kkt*, const double* v, double* out);
+int32_t calipso_hip_sparse_kkt_solve_symmetric(calipso_hip_sparse_kkt*, const double* residual, double* step);
+int32_t calipso_hip_sparse_kkt_search_direction(calipso_hip_sparse_kkt*, const double* residual, double* step, double regularization[3], double info[4]);
+int32_t calipso_hip_sparse_kkt_search_direction_device(calipso_hip_sparse_kkt*, const double* residual, double* step, double regularization[3], double info[4]);
+int32_t calipso_hip_sparse_kkt_timing(calipso_hip_sparse_kkt*, double ms[8]);
+
 /* ---- batched small systems (BASELINE config C5): LDS-resident LDL^T + multi-right-hand-side solve, one workgroup per
  * instance, one launch for the whole batch.  The sensitivity solves of the reference's MPC auto-tuning loop
  * (examples/autotuning/cartpole.jl:179-227 -> differentiate.jl:29-58: n = 89, 102 parameter columns per step) for thousands of

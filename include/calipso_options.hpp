@@ -29,4 +29,22 @@ struct Options {
     double max_filter = 1000, differentiate = 1.0, warmstart = 0.0;
 };
 
+// the regularisation and refinement options (inertia.jl:30-80, iterative_refinement.jl:1-52) by name: one table for the set_option entry of a handle that runs
+// search_direction! alone.  false: `name` is none of them
+inline bool set_search_direction_option(Options& o, const char* name, double value) {
+    struct Real { const char* name; double Options::*field; };
+    struct Int { const char* name; i64 Options::*field; };
+    static const Real reals[] = {{"iterative_refinement_tolerance", &Options::iterative_refinement_tolerance}, {"min_regularization", &Options::min_regularization},
+                                 {"primal_regularization_initial", &Options::primal_regularization_initial}, {"dual_regularization_initial", &Options::dual_regularization_initial},
+                                 {"max_regularization", &Options::max_regularization}, {"dual_regularization", &Options::dual_regularization},
+                                 {"dual_regularization_exponent", &Options::dual_regularization_exponent}, {"scaling_regularization_initial", &Options::scaling_regularization_initial},
+                                 {"scaling_regularization", &Options::scaling_regularization}, {"scaling_regularization_last", &Options::scaling_regularization_last}};
+    static const Int ints[] = {{"iterative_refinement", &Options::iterative_refinement}, {"max_iterative_refinement", &Options::max_iterative_refinement},
+                               {"min_iterative_refinement", &Options::min_iterative_refinement}};
+    const auto same = [](const char* a, const char* b) { while (*a && *a == *b) { ++a; ++b; } return *a == *b; };
+    for (const Real& r : reals) if (same(r.name, name)) { o.*(r.field) = value; return true; }
+    for (const Int& r : ints) if (same(r.name, name)) { o.*(r.field) = (i64)value; return true; }
+    return false;
+}
+
 }  // namespace calipso

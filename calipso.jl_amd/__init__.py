@@ -13,7 +13,7 @@ import numpy as np
 from ._lib import CALLBACK_FN, EVAL_FN, CalipsoHipError, lib
 from ._marshal import QP_NAMES, pack_cotangent, qp_names, qp_shapes, unpack_columns
 
-__all__ = ["Solver", "Group", "LDLSolver", "SmallBatch", "SparseKKT", "Comm", "ordering", "symbolic", "Options", "initialize_b", "solve_b", "CalipsoHipError", "FLAGS", "splitmix_uniform",
+__all__ = ["Solver", "Group", "LDLSolver", "SmallBatch", "SparseKKT", "SparseConicQP", "Comm", "ordering", "symbolic", "Options", "initialize_b", "solve_b", "CalipsoHipError", "FLAGS", "splitmix_uniform",
            "mfma_f64_peak"]
 
 # evaluate! flags (include/calipso_hip.h)
@@ -863,7 +863,9 @@ class SparseKKT(_Handle):
     without a dense block anywhere.  Lxx (nx x nx, the full Lagrangian Hessian with both triangles), gx (ne x nx), hx (nc x nx): scipy sparse matrices whose
     PATTERN is used as it is (stored zeros included; a CSC matrix is taken in its own non-zero order, which later raw value arrays follow).  Cones: the first
     n_nonnegative rows of hx nonnegative (default: all that the second-order cones leave), then contiguous second-order cones of second_order_dims.
-    method / perm as SparseLDL.  There is no `H \\ residual` fallback: search_direction returns status 2 (CALIPSO_WARN_REFINEMENT) with the last refined step."""
+    method / perm as SparseLDL.  There is no `H \\ residual` fallback: search_direction returns status 2 (CALIPSO_WARN_REFINEMENT) with the last refined step.
+    With attach_qp the same handle runs the vector half of solve! and a whole solve! of the sparse conic QP (csrc/sparse_solve.hip): initialize, solve, and the steps of an
+    iteration one by one."""
     _last_error, _destroy = "calipso_hip_sparse_kkt_last_error", "calipso_hip_sparse_kkt_destroy"
     _message = _Handle._STATUS_MESSAGE
 
@@ -1009,6 +1011,127 @@ class SparseKKT(_Handle):
         ms = np.zeros(8)
         self._check(self._L.calipso_hip_sparse_kkt_timing(self._h, _pd(ms)), "sparse_kkt_timing")
         return dict(zip(("assemble", "factorize", "solve", "refinement_solves", "refinement_mul", "wall"), (float(v) for v in ms[:6])))
+
+    # ---- solve! on the same handle (include/calipso_hip.h, "solve! on sparse problem data"; csrc/sparse_solve.hip) ----------------------------------------
+    SOLVE_INFO = ("total_iterations", "outer_iterations", "accepted_iterates", "factorizations", "max_refinement_rounds", "refinement_failures", "worst_warning",
+                  "host_waits", "line_search_trials", "central_path", "penalty", "primal_regularization_last", "vector_ms", "search_direction_ms", "wall_ms", "status")
+    VECTORS = dict(solution="N", candidate="N", dual="ne", residual="N", merit_gradient="n", step="N", cone_product="nc", cone_target="nc", barrier_gradient="nc",
+                   equality_constraint="ne", cone_constraint="nc", objective_gradient_variables="nx")
+
+    def _host_vector(self, a, name, count):
+        v = np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+        if v.size != count:
+            raise CalipsoHipError("SparseKKT: %s has %d entries, not %d" % (name, v.size, count))
+        return v
+
+    def attach_qp(self, q=None, b=None, h=None, objective_constant=0.0):
+        """the vectors of the conic QP besides Lxx = c (P + P'), gx = A, hx = -G: q (nx), b (ne), h (nc); None keeps what is resident.  Host arrays or — all that
+        are given — float64 CUDA tensors / raw device pointers"""
+        given = [a for a in (q, b, h) if a is not None]
+        counts = (self.nx, self.ne, self.nc)
+        if given and all(self._is_device(a) for a in given):
+            ptrs = [self._device_pointer(a, nm, ct) for a, nm, ct in zip((q, b, h), ("q", "b", "h"), counts)]
+            self._check(self._L.calipso_hip_sparse_kkt_qp_attach_device(self._h, *ptrs, float(objective_constant)), "sparse_kkt_qp_attach_device")
+            return
+        arrs = [None if a is None else self._host_vector(a, nm, ct) for a, nm, ct in zip((q, b, h), ("q", "b", "h"), counts)]
+        self._check(self._L.calipso_hip_sparse_kkt_qp_attach(self._h, *[_opt(a) for a in arrs], float(objective_constant)), "sparse_kkt_qp_attach")
+
+    def initialize(self, x0):
+        """initialize!(solver, x0): x <- x0, slacks and duals as initialize.jl:9-48 (x0: a host array, or a CUDA tensor / device pointer)"""
+        if self._is_device(x0):
+            self._check(self._L.calipso_hip_sparse_kkt_initialize_device(self._h, self._device_pointer(x0, "x0", self.nx)), "sparse_kkt_initialize_device")
+        else:
+            self._check(self._L.calipso_hip_sparse_kkt_initialize(self._h, _pd(self._host_vector(x0, "x0", self.nx))), "sparse_kkt_initialize")
+
+    def solve(self):
+        """solve!: (status, info) with status 1 solved, 0 iteration caps, -102 a refinement failure without the option continue_after_refinement_failure (the point is
+        the last accepted iterate); the reference's error()s and refused arguments raise"""
+        info = np.zeros(16)
+        rc = self._L.calipso_hip_sparse_kkt_solve(self._h, _pd(info))
+        out = dict(zip(self.SOLVE_INFO, (float(v) for v in info)))
+        for k in self.SOLVE_INFO[:9] + ("status",):
+            out[k] = int(out[k])
+        self.solve_info = out
+        if rc != -102:
+            self._check(rc, "solve!")
+        return rc, out
+
+    def step_prologue(self):
+        """the prologue of a Newton step at the resident point: dict(objective, barrier, merit, constraint_violation, residual_violation, optimality_error,
+        slack_violation, norms = the eight norms behind them)"""
+        sc = np.zeros(16)
+        self._check(self._L.calipso_hip_sparse_kkt_step_prologue(self._h, 0, _pd(sc)), "sparse_kkt_step_prologue")
+        out = dict(zip(("objective", "barrier", "merit", "constraint_violation", "residual_violation", "optimality_error", "slack_violation"), (float(v) for v in sc[:7])))
+        out["norms"] = sc[8:].copy()
+        return out
+
+    def cone_search(self):
+        """the cone search on the resident step: the step sizes (cone slacks, their duals)"""
+        a = np.zeros(2)
+        self._check(self._L.calipso_hip_sparse_kkt_cone_search(self._h, _pd(a)), "sparse_kkt_cone_search")
+        return float(a[0]), float(a[1])
+
+    def candidate(self, a_s, a_t):
+        """the candidate at the two step sizes: (merit, constraint violation, merit_gradient . step.primals)"""
+        out = np.zeros(3)
+        self._check(self._L.calipso_hip_sparse_kkt_candidate(self._h, float(a_s), float(a_t), _pd(out)), "sparse_kkt_candidate")
+        return tuple(float(v) for v in out)
+
+    def accept(self, step_size):
+        """the candidate becomes the solution: (|g|_inf, |s o t|_inf)"""
+        out = np.zeros(2)
+        self._check(self._L.calipso_hip_sparse_kkt_accept(self._h, float(step_size), _pd(out)), "sparse_kkt_accept")
+        return float(out[0]), float(out[1])
+
+    def outer_update(self):
+        self._check(self._L.calipso_hip_sparse_kkt_outer_update(self._h), "sparse_kkt_outer_update")
+
+    def _vector_length(self, name):
+        return getattr(self, self.VECTORS[name]) if name in self.VECTORS else 0
+
+    def get(self, name):
+        out = np.zeros(self._vector_length(name))
+        self._check(self._L.calipso_hip_sparse_kkt_get(self._h, name.encode(), _pd(out), out.size), "sparse_kkt_get(%s)" % name)
+        return out
+
+    def set(self, name, v):
+        v = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
+        self._check(self._L.calipso_hip_sparse_kkt_set(self._h, name.encode(), _pd(v), v.size), "sparse_kkt_set(%s)" % name)
+
+    def solution_device(self):
+        """the resident point as a CUDA tensor of its own (a device-side copy of the N doubles on the handle's device)"""
+        import torch
+        p = C.c_void_p()
+        self._check(self._L.calipso_hip_sparse_kkt_solution_device(self._h, C.byref(p)), "sparse_kkt_solution_device")
+
+        class View:      # (the CUDA array interface: torch wraps the device memory without a copy)
+            __cuda_array_interface__ = dict(shape=(self.N,), typestr="<f8", data=(p.value, False), version=2)
+        return torch.as_tensor(View(), device=torch.device("cuda", self.device)).clone()
+
+    def keep_trace(self, rows):
+        self._check(self._L.calipso_hip_sparse_kkt_keep_trace(self._h, int(rows)), "sparse_kkt_keep_trace")
+        self._trace_rows = int(rows)
+
+    def trace(self):
+        """solution.all after each accepted iterate of the last solve (the first keep_trace rows of them)"""
+        cap = getattr(self, "_trace_rows", 0)
+        out, accepted = np.zeros((max(cap, 1), self.N)), C.c_int64()
+        rows = self._check(self._L.calipso_hip_sparse_kkt_trace(self._h, _pd(out), cap, C.byref(accepted)), "sparse_kkt_trace")
+        return out[:rows]
+
+
+def SparseConicQP(P, q, A, b, G, h, n_nonnegative=None, second_order_dims=(), objective_scale=0.5, **kw):
+    """min c x'Px + q'x  s.t.  Ax - b = 0,  h - Gx in K  (c = objective_scale) as a SparseKKT ready for initialize / solve: Lxx = c (P + P'), gx = A, hx = -G as CSC,
+    values and q, b, h resident.  P, A, G: scipy sparse matrices (or dense arrays); the cones as SparseKKT takes them; **kw goes to SparseKKT"""
+    import scipy.sparse as sp
+    P, A, G = (sp.csc_matrix(M) for M in (P, A, G))
+    Lxx, gx, hx = sp.csc_matrix(objective_scale * (P + P.T)), A, sp.csc_matrix(-G)
+    for M in (Lxx, gx, hx):
+        M.sort_indices()
+    s = SparseKKT(Lxx, gx, hx, n_nonnegative=n_nonnegative, second_order_dims=second_order_dims, **kw)
+    s.set_values(Lxx, gx, hx)
+    s.attach_qp(q, b, h)
+    return s
 
 
 class SmallBatch(_Handle):

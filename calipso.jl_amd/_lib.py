@@ -117,6 +117,21 @@ SYMBOLS = {
     "calipso_hip_sparse_kkt_search_direction": (_i32, [_vp, _pd, _pd, _pd, _pd]),
     "calipso_hip_sparse_kkt_search_direction_device": (_i32, [_vp, _vp, _vp, _pd, _pd]),
     "calipso_hip_sparse_kkt_timing": (_i32, [_vp, _pd]),
+    "calipso_hip_sparse_kkt_qp_attach": (_i32, [_vp, _pd, _pd, _pd, _dbl]),
+    "calipso_hip_sparse_kkt_qp_attach_device": (_i32, [_vp, _vp, _vp, _vp, _dbl]),
+    "calipso_hip_sparse_kkt_initialize": (_i32, [_vp, _pd]),
+    "calipso_hip_sparse_kkt_initialize_device": (_i32, [_vp, _vp]),
+    "calipso_hip_sparse_kkt_solve": (_i32, [_vp, _pd]),
+    "calipso_hip_sparse_kkt_step_prologue": (_i32, [_vp, _i32, _pd]),
+    "calipso_hip_sparse_kkt_cone_search": (_i32, [_vp, _pd]),
+    "calipso_hip_sparse_kkt_candidate": (_i32, [_vp, _dbl, _dbl, _pd]),
+    "calipso_hip_sparse_kkt_accept": (_i32, [_vp, _dbl, _pd]),
+    "calipso_hip_sparse_kkt_outer_update": (_i32, [_vp]),
+    "calipso_hip_sparse_kkt_get": (_i32, [_vp, C.c_char_p, _pd, _i64]),
+    "calipso_hip_sparse_kkt_set": (_i32, [_vp, C.c_char_p, _pd, _i64]),
+    "calipso_hip_sparse_kkt_solution_device": (_i32, [_vp, C.POINTER(_vp)]),
+    "calipso_hip_sparse_kkt_keep_trace": (_i32, [_vp, _i64]),
+    "calipso_hip_sparse_kkt_trace": (_i32, [_vp, _pd, _i64, _pi64]),
     "calipso_hip_small_create": (_i32, [_i64, _i64, _i64, _i32, C.POINTER(_vp)]),
     "calipso_hip_small_destroy": (_i32, [_vp]),
     "calipso_hip_small_last_error": (C.c_char_p, [_vp]),

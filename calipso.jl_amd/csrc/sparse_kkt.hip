@@ -19,8 +19,7 @@
 #include <string>
 #include <vector>
 
-#include "internal.hpp"
-#include "sparse_kkt.hpp"                  // the analysis: plain host C++
+#include "sparse_kkt_handle.hpp"           // the handle, KktDev, and (through sparse_kkt.hpp) the analysis: plain host C++
 
 using calipso::i64;
 using calipso::Options;
@@ -30,23 +29,7 @@ static_assert(REFUSED_ARGUMENT == CALIPSO_ERR_ARGUMENT, "a refused pattern is an
 
 namespace {
 
-constexpr int KT = 256;                    // threads per workgroup of every kernel here
 constexpr int WAVE_ROW_MIN = 32;           // mean non-zeros per gathered row from which a wavefront takes a row instead of a thread
-
-struct View { const int *ptr, *idx, *src; };      // a row view (idx = column, src = position in the caller's nzval) or a column view (idx = row, src unused)
-
-// what every kernel reads: sizes, the point's offsets (point.jl:13-22), the resident data and the tables of the analysis
-struct KktDev {
-    int nx, ne, nc, n, N, q, nsoc, ncc;           // q = nonnegative rows, ncc = cone columns (sum of the dimensions)
-    int o_r, o_s, o_y, o_z, o_t;
-    int nnzL, nnzg, nnzh;
-    const double *Lxx, *gx, *hx, *w, *rho;
-    const int *slotL, *slotg, *sloth;             // slotL: -1 for the strict lower triangle AND for the diagonal (diag_x_src carries that one)
-    const int *diag_x, *diag_x_src, *diag_e, *diag_c;
-    const int *row_cone;                          // per cone row: its second-order cone, -1 nonnegative, -2 in no cone
-    const int *soc_start, *soc_dim, *col_cone, *col_index, *col_slot;
-    View Lr, gr, hr, gc, hc;
-};
 
 __device__ __forceinline__ double rabs(double x) { return x != x ? __builtin_huge_val() : fabs(x); }      // a NaN reports +inf (step_decisions.hpp: refine_next)
 
@@ -274,25 +257,6 @@ unsigned blocks(long long items, int per_block = KT) { return (unsigned)std::max
 
 }  // namespace
 
-struct calipso_hip_sparse_kkt {
-    Analysis an;
-    Options opt;
-    Scalars sc;                                // kappa (IC-2), ep / ed of the last assemble, ep_last
-    int device = 0;
-    calipso_hip_sparse* sp = nullptr;          // LDL^T of the pattern of triu(K); its stream orders everything here
-    hipStream_t st = nullptr;
-    KktDev d{};
-    bool wave_rows = false;
-    double *Lxx = nullptr, *gx = nullptr, *hx = nullptr, *w = nullptr, *rho = nullptr, *K = nullptr;
-    double *res = nullptr, *step = nullptr, *corr = nullptr, *err = nullptr, *rsym = nullptr, *dsym = nullptr, *norm = nullptr;
-    std::vector<void*> dev;
-    bool have[5] = {false, false, false, false, false};      // Lxx, gx, hx, w, penalty resident
-    bool assembled = false, factored = false;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    double ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    std::string err_text;
-};
-
 namespace {
 
 typedef calipso_hip_sparse_kkt KH;
@@ -447,6 +411,16 @@ int search_direction(KH* s, const double* res, double* step, double regularizati
 
 }  // namespace
 
+// what sparse_solve.hip calls (sparse_kkt_handle.hpp)
+namespace calipso {
+namespace sparse_kkt {
+int kkt_fail(KH* s, int rc, const std::string& text) { return fail(s, rc, text); }
+int kkt_reserve(KH* s, double** out, size_t count) { return reserve(s, out, count); }
+int kkt_device_pointer(KH* s, const void* p, const char* entry, const char* arg) { return device_pointer(s, p, entry, arg); }
+int kkt_search_direction(KH* s, const double* res, double* step, double regularization[3], double info[4]) { return search_direction(s, res, step, regularization, info); }
+}  // namespace sparse_kkt
+}  // namespace calipso
+
 extern "C" {
 
 const char* calipso_hip_sparse_kkt_last_error(calipso_hip_sparse_kkt* s) { return s ? s->err_text.c_str() : g_kkt_err.c_str(); }
@@ -455,6 +429,7 @@ int32_t calipso_hip_sparse_kkt_destroy(calipso_hip_sparse_kkt* s) {
     if (!s) return CALIPSO_OK;
     (void)hipSetDevice(s->device);
     if (s->st) (void)hipStreamSynchronize(s->st);
+    solve_state_release(s);
     for (void* p : s->dev) if (p) (void)hipFree(p);
     for (hipEvent_t e : s->ev) if (e) (void)hipEventDestroy(e);
     if (s->sp) (void)calipso_hip_sparse_destroy(s->sp);
@@ -537,6 +512,7 @@ int32_t calipso_hip_sparse_kkt_set_option(calipso_hip_sparse_kkt* s, const char*
     if (!s || !name) return CALIPSO_ERR_ARGUMENT;
     if (calipso::set_search_direction_option(s->opt, name, value)) return CALIPSO_OK;
     if (std::string(name) == "central_path") { s->sc.kappa = value; return CALIPSO_OK; }      // (the solver's scalar, not an option: IC-2 reads it, inertia.jl:44)
+    { const int rc = solve_set_option(s, name, value); if (rc != 0) return rc < 0 ? rc : CALIPSO_OK; }      // what solve! reads besides (sparse_solve.hip)
     return fail(s, CALIPSO_ERR_ARGUMENT, std::string("calipso_hip_sparse_kkt_set_option: unknown option ") + name);
 }
 

@@ -1,0 +1,70 @@
+// sparse_kkt_handle.hpp — the handle behind calipso_hip_sparse_kkt_* as the two translation units that work on it see it: sparse_kkt.hip (search_direction!) and
+// sparse_solve.hip (the vector half of solve! and its driver).  What every kernel reads (KktDev), the handle itself, and the few functions of sparse_kkt.hip the
+// solve driver calls.
+#pragma once
+#include <string>
+#include <vector>
+
+#include "internal.hpp"
+#include "sparse_kkt.hpp"                  // the analysis: plain host C++
+
+namespace calipso {
+namespace sparse_kkt {
+
+constexpr int KT = 256;                    // threads per workgroup of every kernel on this handle
+
+struct View { const int *ptr, *idx, *src; };      // a row view (idx = column, src = position in the caller's nzval) or a column view (idx = row, src unused)
+
+// what every kernel reads: sizes, the point's offsets (point.jl:13-22), the resident data and the tables of the analysis
+struct KktDev {
+    int nx, ne, nc, n, N, q, nsoc, ncc;           // q = nonnegative rows, ncc = cone columns (sum of the dimensions)
+    int o_r, o_s, o_y, o_z, o_t;
+    int nnzL, nnzg, nnzh;
+    const double *Lxx, *gx, *hx, *w, *rho;
+    const int *slotL, *slotg, *sloth;             // slotL: -1 for the strict lower triangle AND for the diagonal (diag_x_src carries that one)
+    const int *diag_x, *diag_x_src, *diag_e, *diag_c;
+    const int *row_cone;                          // per cone row: its second-order cone, -1 nonnegative, -2 in no cone
+    const int *soc_start, *soc_dim, *col_cone, *col_index, *col_slot;
+    View Lr, gr, hr, gc, hc;
+};
+
+struct SolveState;                                // sparse_solve.hip: the resident vectors, workspace and counters of solve!
+
+}  // namespace sparse_kkt
+}  // namespace calipso
+
+struct calipso_hip_sparse_kkt {
+    calipso::sparse_kkt::Analysis an;
+    calipso::Options opt;
+    calipso::Scalars sc;                       // kappa (IC-2), ep / ed of the last assemble, ep_last; tau and rho of a solve
+    int device = 0;
+    calipso_hip_sparse* sp = nullptr;          // LDL^T of the pattern of triu(K); its stream orders everything here
+    hipStream_t st = nullptr;
+    calipso::sparse_kkt::KktDev d{};
+    bool wave_rows = false;
+    double *Lxx = nullptr, *gx = nullptr, *hx = nullptr, *w = nullptr, *rho = nullptr, *K = nullptr;
+    double *res = nullptr, *step = nullptr, *corr = nullptr, *err = nullptr, *rsym = nullptr, *dsym = nullptr, *norm = nullptr;
+    std::vector<void*> dev;
+    bool have[5] = {false, false, false, false, false};      // Lxx, gx, hx, w, penalty resident
+    bool assembled = false, factored = false;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    double ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    std::string err_text;
+    calipso::sparse_kkt::SolveState* solve = nullptr;        // made by the first solve entry that needs it (sparse_solve.hip), released with the handle
+    bool continue_after_refinement_failure = false;
+};
+
+namespace calipso {
+namespace sparse_kkt {
+
+// sparse_kkt.hip, for sparse_solve.hip
+int kkt_fail(calipso_hip_sparse_kkt* s, int rc, const std::string& text);                                   // sets last_error, returns rc
+int kkt_reserve(calipso_hip_sparse_kkt* s, double** out, size_t count);                                     // zeroed device doubles owned by the handle
+int kkt_device_pointer(calipso_hip_sparse_kkt* s, const void* p, const char* entry, const char* arg);       // the check of every _device entry
+int kkt_search_direction(calipso_hip_sparse_kkt* s, const double* res, double* step, double regularization[3], double info[4]);
+// sparse_solve.hip, for sparse_kkt.hip
+void solve_state_release(calipso_hip_sparse_kkt* s);                                                        // (before the handle's device memory is freed)
+int solve_set_option(calipso_hip_sparse_kkt* s, const char* name, double value);                            // 1 taken, 0 unknown, < 0 refused
+
+}  // namespace sparse_kkt
+}  // namespace calipso

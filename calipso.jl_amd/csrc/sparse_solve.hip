@@ -1,0 +1,864 @@
+// sparse_solve.hip — the vector half of solve! (src/solver/solve.jl:8-377) on the sparse handle of sparse_kkt.hip, and its host driver: a whole solve! of the sparse
+// conic QP   min 1/2 x'Lxx x + q'x   s.t.  gx x - b = 0,  hx x + hvec in K   with every vector resident on the device from initialize! to the converged point.
+//
+//   item space (sparse_solve.hpp: Layout)  every grid kernel runs over the same items: one thread per row of [x; equality; cone], then one thread per SMALL second-order
+//                                      cone (dimension <= SMALL_CONE_MAX), then one WAVEFRONT per wider cone — O(dimension) work per cone either way; a cone's
+//                                      barrier, gradient, product, target and violation come from its cone item, the nonnegative rows' from their row item.  Sections
+//                                      begin at multiples of 64; at most GRID_CAP workgroups of 256 threads, striding beyond that.
+//   QP evaluation                      evaluate! (evaluate.jl:37-121) for this problem class is a gather over the row views of Lxx, gx, hx and the column views of gx, hx
+//                                      that the handle holds: qp_hessian_row / qp_equality_row / qp_cone_row / qp_dual_rows, at the solution or, on the fly, at a
+//                                      candidate.  The driver reaches evaluation through these alone.
+//   reductions                         every sum is two-stage in a fixed order: a thread adds its items in stride order, a workgroup its threads by a butterfly, and
+//                                      stores one partial per (quantity, workgroup) into the workspace; ONE small finishing kernel adds the partials in workgroup order,
+//                                      forms the scalars and writes them into the published block.  Maxima and the cone-search masks take the same route (masks are
+//                                      gathered in LDS by atomicOr on integers, which is order-independent).  No floating-point atomics: reproducible bit for bit.
+//   driver (host)                      solve! through step_decisions.hpp (initial_scalars, step_norms, exit_kind, cone_step_sizes, line_search_accepts,
+//                                      filter_needs_augment, central_path_update, penalty_update), the filter of sparse_solve.hpp, search_direction() of sparse_kkt.hip.
+//                                      Host waits outside search_direction: accept and the next step's prologue are read back together, the masks with the first
+//                                      candidate, and every further line-search trial once: 2 accepted + outer + trials in all.
+// Every kernel runs on the sparse handle's stream.
+#include <chrono>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "sparse_kkt_handle.hpp"
+#include "sparse_solve.hpp"                // filter, published block, item space, workspace layout, argument checks: plain host C++
+
+using calipso::i64;
+using calipso::Options;
+using calipso::Scalars;
+using namespace calipso::sparse_kkt;
+using namespace calipso::sparse_solve;
+typedef calipso_hip_sparse_kkt KH;
+static_assert(KT == THREADS, "the workspace layout counts workgroups of KT threads");
+
+namespace {
+
+// what the solve kernels read and write besides KktDev
+struct SolveDev {
+    long long rows, small0, wide0, items;
+    int n_small, n_wide, grid;
+    const int *small_cones, *wide_cones;
+    const double *q, *b, *hvec;
+    double objective_constant;
+    double *w, *cand, *dual, *res, *step, *mgrad, *bgrad, *cprod, *ctarget, *g, *h, *gcand, *hcand, *fx;
+    double* ws; unsigned* wsm;                    // reduction workspace: doubles and mask words
+    long long off_prologue, off_candidate, off_accept;
+    double* pub; unsigned* pub_masks;             // the published block
+};
+
+}  // namespace
+
+struct calipso::sparse_kkt::SolveState {
+    Layout lay;
+    SolveDev v{};
+    double *q = nullptr, *b = nullptr, *hvec = nullptr, *trace = nullptr;
+    bool have_qp[3] = {false, false, false};
+    i64 trace_cap = 0, trace_rows = 0, trace_total = 0;
+    Filter filter;
+    double* hpub = nullptr;                       // pinned: the published block on the host
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool group_open = false;
+    double vector_ms = 0.0;
+    i64 waits = 0;
+    std::vector<void*> own;                       // device memory outside the handle's list (the trace)
+};
+
+namespace {
+
+typedef calipso::sparse_kkt::SolveState SS;
+
+__device__ __forceinline__ double rabs(double x) { return x != x ? __builtin_huge_val() : fabs(x); }      // a NaN reports +inf, as in sparse_kkt.hip
+
+// ---- the QP's evaluate! (evaluate.jl:37-121) row by row; X(j) gives entry j of the variables ---------------------------------------------------------------------
+template <typename FX> __device__ __forceinline__ double qp_hessian_row(const KktDev& d, int k, FX X) {          // (Lxx x)_k
+    double a = 0.0;
+    for (int p = d.Lr.ptr[k]; p < d.Lr.ptr[k + 1]; ++p) a += d.Lxx[d.Lr.src[p]] * X(d.Lr.idx[p]);
+    return a;
+}
+template <typename FX> __device__ __forceinline__ double qp_equality_row(const KktDev& d, const SolveDev& v, int i, FX X) {      // g_i = (gx x)_i - b_i
+    double a = 0.0;
+    for (int p = d.gr.ptr[i]; p < d.gr.ptr[i + 1]; ++p) a += d.gx[d.gr.src[p]] * X(d.gr.idx[p]);
+    return a - v.b[i];
+}
+template <typename FX> __device__ __forceinline__ double qp_cone_row(const KktDev& d, const SolveDev& v, int c, FX X) {          // h_c = (hx x)_c + hvec_c
+    double a = 0.0;
+    for (int p = d.hr.ptr[c]; p < d.hr.ptr[c + 1]; ++p) a += d.hx[d.hr.src[p]] * X(d.hr.idx[p]);
+    return a + v.hvec[c];
+}
+__device__ __forceinline__ void qp_dual_rows(const KktDev& d, int k, const double* __restrict__ y, const double* __restrict__ z, double* gy, double* hz) {      // (gx'y)_k, (hx'z)_k
+    double a = 0.0, b = 0.0;
+    for (int p = d.gc.ptr[k]; p < d.gc.ptr[k + 1]; ++p) a += d.gx[p] * y[d.gc.idx[p]];
+    for (int p = d.hc.ptr[k]; p < d.hc.ptr[k + 1]; ++p) b += d.hx[p] * z[d.hc.idx[p]];
+    *gy = a; *hz = b;
+}
+
+// ---- items ------------------------------------------------------------------------------------------------------------------------------------------------------
+// what item `it` is: 0 a row (*index = the row of [x; equality; cone]), 1 a second-order cone (*index = the cone, its entries q = *lane, *lane + *nl, ...), -1 padding.
+// Wave-uniform except inside the row section.
+__device__ __forceinline__ int item_kind(const SolveDev& v, long long it, int* index, int* lane, int* nl) {
+    if (it < v.rows) { *index = (int)it; return 0; }
+    if (it >= v.small0 && it < v.small0 + v.n_small) { *index = v.small_cones[it - v.small0]; *lane = 0; *nl = 1; return 1; }
+    if (it >= v.wide0) { *index = v.wide_cones[(it - v.wide0) >> 6]; *lane = (int)((it - v.wide0) & 63); *nl = 64; return 1; }
+    return -1;
+}
+__device__ __forceinline__ double cone_sum(double a, int nl) {       // over the lanes that share a cone (a whole wavefront, or the thread alone)
+    if (nl > 1) for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
+    return a;
+}
+
+// the workgroup's partials: quantities [0, FIRST_MAX) are sums, the rest maxima; one double per (quantity, workgroup) at ws[off + q * grid + workgroup]
+template <int NQ, int FIRST_MAX>
+__device__ __forceinline__ void store_partials(double (&val)[NQ], double* __restrict__ ws, long long off, int grid) {
+    __shared__ double part[NQ][KT / 64];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        double a = val[q];
+        for (int o = 32; o > 0; o >>= 1) { const double other = __shfl_xor(a, o); a = q < FIRST_MAX ? a + other : fmax(a, other); }
+        if ((threadIdx.x & 63) == 0) part[q][threadIdx.x >> 6] = a;
+    }
+    __syncthreads();
+    if (threadIdx.x < NQ) {
+        const int q = threadIdx.x;
+        double a = part[q][0];
+        for (int k = 1; k < KT / 64; ++k) a = q < FIRST_MAX ? a + part[q][k] : fmax(a, part[q][k]);
+        ws[off + (long long)q * grid + blockIdx.x] = a;
+    }
+}
+// the finishing kernels' first half: thread q < NQ combines the partials of quantity q in workgroup order into tot[q]
+template <int NQ, int FIRST_MAX>
+__device__ __forceinline__ void combine_partials(const double* __restrict__ ws, long long off, int grid, double* tot) {
+    if (threadIdx.x < NQ) {
+        const int q = threadIdx.x;
+        double a = ws[off + (long long)q * grid];
+        for (int b = 1; b < grid; ++b) { const double p = ws[off + (long long)q * grid + b]; a = q < FIRST_MAX ? a + p : fmax(a, p); }
+        tot[q] = a;
+    }
+    __syncthreads();
+}
+
+// ---- initialize! (initialize.jl:9-48): initialize_slacks! r <- g(x), s <- cone interior; initialize_duals! y, z <- 0, t <- cone interior ------------------------------
+__global__ __launch_bounds__(KT) void k_solve_init(const KktDev d, const SolveDev v) {
+    for (long long it = (long long)blockIdx.x * KT + threadIdx.x; it < v.rows; it += (long long)v.grid * KT) {
+        const int k = (int)it;
+        if (k < d.nx) continue;
+        if (k < d.nx + d.ne) {
+            const int i = k - d.nx;
+            v.w[d.o_r + i] = qp_equality_row(d, v, i, [&](int j) { return v.w[j]; });
+            v.w[d.o_y + i] = 0.0;
+            continue;
+        }
+        const int c = k - d.nx - d.ne, kind = d.row_cone[c];
+        const double e = kind == -1 ? 1.0 : (kind >= 0 ? (c == d.soc_start[kind] ? 1.0 : 0.1) : 0.0);      // nonnegative.jl:2-8, second_order.jl:2-10
+        v.w[d.o_s + c] = e; v.w[d.o_t + c] = e; v.w[d.o_z + c] = 0.0;
+    }
+}
+__global__ __launch_bounds__(KT) void k_solve_fill(int count, double* __restrict__ out, double value) {
+    const long long k = (long long)blockIdx.x * KT + threadIdx.x;
+    if (k < count) out[k] = value;
+}
+
+// ---- prologue of a step (solve.jl:100-135, 170-172): evaluate! at the solution, cone!(barrier, barrier_gradient, product, target), merit (merit.jl:2-15) and its
+// gradient (:17-31), residual! (residual.jl:1-51), constraint_violation! (constraint_violation.jl:1-13), the norms of optimality_error (optimality_error.jl:1-27) -----
+__global__ __launch_bounds__(KT) void k_solve_prologue(const KktDev d, const SolveDev v, double kappa) {
+    double val[PP_COUNT];
+#pragma unroll
+    for (int q = 0; q < PP_COUNT; ++q) val[q] = 0.0;
+    const double rho = d.rho[0];
+    const double* __restrict__ w = v.w;
+    for (long long it = (long long)blockIdx.x * KT + threadIdx.x; it < v.items; it += (long long)v.grid * KT) {
+        int k = 0, lane = 0, nl = 1;
+        const int kind = item_kind(v, it, &k, &lane, &nl);
+        if (kind == 0) {
+            if (k < d.nx) {
+                const double Lx = qp_hessian_row(d, k, [&](int j) { return w[j]; });
+                double gy, hz;
+                qp_dual_rows(d, k, w + d.o_y, w + d.o_z, &gy, &hz);
+                const double fx = Lx + v.q[k];
+                const double r = (fx + gy) + hz;                                                            // residual.jl:10-14
+                v.fx[k] = fx; v.mgrad[k] = fx; v.res[k] = r;
+                val[PP_OBJECTIVE] += 0.5 * w[k] * Lx + v.q[k] * w[k];
+                val[PP_RES_1] += rabs(r); val[PP_RES_N_INF] = fmax(val[PP_RES_N_INF], rabs(r));
+            } else if (k < d.nx + d.ne) {
+                const int i = k - d.nx;
+                const double g = qp_equality_row(d, v, i, [&](int j) { return w[j]; });
+                const double r = w[d.o_r + i], y = w[d.o_y + i], lam = v.dual[i];
+                const double rr = lam + rho * r - y, ry = g - r;                                            // :17-19, :29-33
+                v.g[i] = g; v.res[d.o_r + i] = rr; v.res[d.o_y + i] = ry; v.mgrad[d.nx + i] = lam + rho * r;
+                val[PP_DUAL_DOT_R] += lam * r; val[PP_R_DOT_R] += r * r; val[PP_THETA] += rabs(g - r); val[PP_Y_1] += rabs(y);
+                val[PP_RES_1] += rabs(rr) + rabs(ry);
+                val[PP_RES_N_INF] = fmax(val[PP_RES_N_INF], rabs(rr)); val[PP_RES_Y_INF] = fmax(val[PP_RES_Y_INF], rabs(ry));
+            } else {
+                const int c = k - d.nx - d.ne, ck = d.row_cone[c];
+                const double h = qp_cone_row(d, v, c, [&](int j) { return w[j]; });
+                const double sl = w[d.o_s + c], z = w[d.o_z + c], t = w[d.o_t + c];
+                const double rs = -z - t, rz = h - sl;                                                      // :22-26, :36-40
+                v.h[c] = h; v.res[d.o_s + c] = rs; v.res[d.o_z + c] = rz;
+                val[PP_THETA] += rabs(h - sl); val[PP_Z_1] += rabs(z); val[PP_T_1] += rabs(t);
+                val[PP_RES_1] += rabs(rs) + rabs(rz);
+                val[PP_RES_N_INF] = fmax(val[PP_RES_N_INF], rabs(rs)); val[PP_RES_Z_INF] = fmax(val[PP_RES_Z_INF], rabs(rz));
+                if (ck < 0) {                                                                               // nonnegative.jl:11-26; a row in no cone holds zeros
+                    const bool nn = ck == -1;
+                    const double prod = nn ? sl * t : 0.0, target = nn ? 1.0 : 0.0, bg = nn ? 1.0 / sl : 0.0;
+                    const double rt = prod - kappa * target;                                                // :43-48
+                    v.cprod[c] = prod; v.ctarget[c] = target; v.bgrad[c] = bg; v.res[d.o_t + c] = rt; v.mgrad[d.nx + d.ne + c] = -1.0 * kappa * bg;
+                    if (nn) val[PP_BARRIER] += log(sl);
+                    val[PP_RES_1] += rabs(rt); val[PP_RES_T_INF] = fmax(val[PP_RES_T_INF], rabs(rt));
+                }
+            }
+        } else if (kind == 1) {                                                                             // second_order.jl:13-42
+            const int st = d.soc_start[k], dm = d.soc_dim[k];
+            const double* sl = w + d.o_s + st; const double* t = w + d.o_t + st;
+            double tail = 0.0, dot = 0.0;
+            for (int q = lane; q < dm; q += nl) { if (q > 0) tail += sl[q] * sl[q]; dot += sl[q] * t[q]; }
+            tail = cone_sum(tail, nl); dot = cone_sum(dot, nl);
+            const double det = sl[0] * sl[0] - tail, sc = 1.0 / det;
+            if (lane == 0) val[PP_BARRIER] += 0.5 * log(det);
+            for (int q = lane; q < dm; q += nl) {
+                const double prod = q == 0 ? dot : sl[0] * t[q] + t[0] * sl[q], target = q == 0 ? 1.0 : 0.0, bg = q == 0 ? sc * sl[0] : sc * (-sl[q]);
+                const double rt = prod - kappa * target;
+                v.cprod[st + q] = prod; v.ctarget[st + q] = target; v.bgrad[st + q] = bg; v.res[d.o_t + st + q] = rt; v.mgrad[d.nx + d.ne + st + q] = -1.0 * kappa * bg;
+                val[PP_RES_1] += rabs(rt); val[PP_RES_T_INF] = fmax(val[PP_RES_T_INF], rabs(rt));
+            }
+        }
+    }
+    store_partials<PP_COUNT, PP_FIRST_MAX>(val, v.ws, v.off_prologue, v.grid);
+}
+__global__ __launch_bounds__(64) void k_solve_prologue_finish(const KktDev d, const SolveDev v, double kappa) {
+    __shared__ double tot[PP_COUNT];
+    combine_partials<PP_COUNT, PP_FIRST_MAX>(v.ws, v.off_prologue, v.grid, tot);
+    if (threadIdx.x != 0) return;
+    double* pub = v.pub;
+    const double f = tot[PP_OBJECTIVE] + v.objective_constant;
+    double M = 0.0;                                                                                         // merit.jl:2-15
+    M += f;
+    M += tot[PP_DUAL_DOT_R] + 0.5 * d.rho[0] * tot[PP_R_DOT_R];
+    M -= kappa * tot[PP_BARRIER];
+    pub[PUB_OBJECTIVE] = f; pub[PUB_BARRIER] = tot[PP_BARRIER]; pub[PUB_DUAL_DOT_R] = tot[PP_DUAL_DOT_R]; pub[PUB_R_DOT_R] = tot[PP_R_DOT_R];
+    pub[PUB_MERIT] = M; pub[PUB_THETA] = tot[PP_THETA] / (double)(d.ne + d.nc);                             // constraint_violation.jl:12
+    pub[PUB_RES_1] = tot[PP_RES_1]; pub[PUB_RES_N_INF] = tot[PP_RES_N_INF]; pub[PUB_RES_Y_INF] = tot[PP_RES_Y_INF]; pub[PUB_RES_Z_INF] = tot[PP_RES_Z_INF];
+    pub[PUB_RES_T_INF] = tot[PP_RES_T_INF]; pub[PUB_Y_1] = tot[PP_Y_1]; pub[PUB_Z_1] = tot[PP_Z_1]; pub[PUB_T_1] = tot[PP_T_1];
+}
+
+// ---- cone search (solve.jl:190-221): for every trial step size scaling_line_search^k, k < nk, whether s - a Ds (and t - a Dt) violates a cone
+// (nonnegative.jl:29-34, second_order.jl:45-47); a is formed as the reference forms it, a <- scaling_line_search * a (cones.hip: violation_masks) ----------------------
+__device__ __forceinline__ void mask_set(unsigned* lm, int which, int k) { atomicOr(&lm[which * calipso::CONE_MASK_WORDS + (k >> 5)], 1u << (k & 31)); }
+
+__global__ __launch_bounds__(KT) void k_solve_cone_masks(const KktDev d, const SolveDev v, double tau, double sls, int nk) {
+    __shared__ unsigned lm[PUB_MASK_INTS];
+    if (threadIdx.x < PUB_MASK_INTS) lm[threadIdx.x] = 0u;
+    __syncthreads();
+    const double* __restrict__ w = v.w;
+    const double keep = 1.0 - tau;
+    for (long long it = (long long)blockIdx.x * KT + threadIdx.x; it < v.items; it += (long long)v.grid * KT) {
+        int k = 0, lane = 0, nl = 1;
+        const int kind = item_kind(v, it, &k, &lane, &nl);
+        if (kind == 0) {
+            const int c = k - d.nx - d.ne;
+            if (c < 0 || d.row_cone[c] != -1) continue;
+            for (int which = 0; which < 2; ++which) {
+                const int o = which == 0 ? d.o_s : d.o_t;
+                const double x = w[o + c], D = v.step[o + c];
+                double a = 1.0;
+                for (int tr = 0; tr < nk; ++tr) { if (x - a * D <= keep * x) mask_set(lm, which, tr); a = sls * a; }
+            }
+        } else if (kind == 1) {
+            const int st = d.soc_start[k], dm = d.soc_dim[k];
+            for (int which = 0; which < 2; ++which) {
+                const int o = (which == 0 ? d.o_s : d.o_t) + st;
+                const double* x = w + o; const double* D = v.step + o;
+                double a = 1.0;
+                for (int tr = 0; tr < nk; ++tr) {
+                    double nrm = 0.0;
+                    for (int q = (lane == 0 ? nl : lane); q < dm; q += nl) { const double e = (x[q] - a * D[q]) - keep * x[q]; nrm += e * e; }
+                    nrm = cone_sum(nrm, nl);
+                    if (lane == 0 && (x[0] - a * D[0]) - keep * x[0] <= sqrt(nrm)) mask_set(lm, which, tr);
+                    a = sls * a;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < PUB_MASK_INTS) v.wsm[(long long)threadIdx.x * v.grid + blockIdx.x] = lm[threadIdx.x];
+}
+// the masks of all workgroups, and the two step sizes the first candidate takes (as cone_step_sizes of step_decisions.hpp forms them; the host decides on the masks)
+__global__ __launch_bounds__(64) void k_solve_masks_finish(const SolveDev v, double sls, int nk) {
+    __shared__ unsigned m[PUB_MASK_INTS];
+    if (threadIdx.x < PUB_MASK_INTS) {
+        unsigned a = 0u;
+        for (int b = 0; b < v.grid; ++b) a |= v.wsm[(long long)threadIdx.x * v.grid + b];
+        m[threadIdx.x] = a; v.pub_masks[threadIdx.x] = a;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    bool failed = false;
+    for (int which = 0; which < 2; ++which) {
+        int first = -1;
+        for (int k = 0; k < nk && first < 0; ++k) if (!(m[which * calipso::CONE_MASK_WORDS + (k >> 5)] & (1u << (k & 31)))) first = k;
+        double a = 1.0;
+        for (int k = 0; k < first; ++k) a = sls * a;
+        if (first < 0) failed = true;
+        v.pub[which == 0 ? PUB_STEP_S : PUB_STEP_T] = a;
+    }
+    v.pub[PUB_CONE_SEARCH_FAILED] = failed ? 1.0 : 0.0;
+}
+
+// ---- candidate (solve.jl:206-229, 268-276) and what is evaluated at it (:231-250, 278-297): x^, r^, s^ with a_s (t^ with a_t, first candidate only), f, g, h, the
+// barrier, merit and constraint violation there; first: also dd = merit_gradient . step.primals (line_search.jl:2-18).  alpha: the step sizes on the device (the
+// published block, behind the masks' finishing kernel) or NULL for the values given ---------------------------------------------------------------------------------
+__global__ __launch_bounds__(KT) void k_solve_candidate(const KktDev d, const SolveDev v, const double* __restrict__ alpha, double a_s, double a_t, int first) {
+    if (alpha) { a_s = alpha[PUB_STEP_S]; a_t = alpha[PUB_STEP_T]; }
+    double val[CP_COUNT];
+#pragma unroll
+    for (int q = 0; q < CP_COUNT; ++q) val[q] = 0.0;
+    const double* __restrict__ w = v.w;
+    const double* __restrict__ D = v.step;
+    const auto X = [&](int j) { return w[j] - a_s * D[j]; };
+    for (long long it = (long long)blockIdx.x * KT + threadIdx.x; it < v.items; it += (long long)v.grid * KT) {
+        int k = 0, lane = 0, nl = 1;
+        const int kind = item_kind(v, it, &k, &lane, &nl);
+        if (kind == 0) {
+            if (first) val[CP_DD] += v.mgrad[k] * D[k];                                                     // (the primals are the first n entries of the step: point.jl:20)
+            if (k < d.nx) {
+                const double xh = X(k), Lx = qp_hessian_row(d, k, X);
+                v.cand[k] = xh;
+                val[CP_OBJECTIVE] += 0.5 * xh * Lx + v.q[k] * xh;
+            } else if (k < d.nx + d.ne) {
+                const int i = k - d.nx;
+                const double rh = w[d.o_r + i] - a_s * D[d.o_r + i], g = qp_equality_row(d, v, i, X), lam = v.dual[i];
+                v.cand[d.o_r + i] = rh; v.gcand[i] = g;
+                val[CP_DUAL_DOT_R] += lam * rh; val[CP_R_DOT_R] += rh * rh; val[CP_THETA] += rabs(g - rh);
+            } else {
+                const int c = k - d.nx - d.ne;
+                const double sh = w[d.o_s + c] - a_s * D[d.o_s + c], h = qp_cone_row(d, v, c, X);
+                v.cand[d.o_s + c] = sh; v.hcand[c] = h;
+                if (first) v.cand[d.o_t + c] = w[d.o_t + c] - a_t * D[d.o_t + c];
+                val[CP_THETA] += rabs(h - sh);
+                if (d.row_cone[c] == -1) val[CP_BARRIER] += log(sh);
+            }
+        } else if (kind == 1) {
+            const int st = d.soc_start[k], dm = d.soc_dim[k];
+            const double* sl = w + d.o_s + st; const double* Ds = D + d.o_s + st;
+            double tail = 0.0;
+            for (int q = (lane == 0 ? nl : lane); q < dm; q += nl) { const double e = sl[q] - a_s * Ds[q]; tail += e * e; }
+            tail = cone_sum(tail, nl);
+            const double s0 = sl[0] - a_s * Ds[0];
+            if (lane == 0) val[CP_BARRIER] += 0.5 * log(s0 * s0 - tail);
+        }
+    }
+    store_partials<CP_COUNT, CP_COUNT>(val, v.ws, v.off_candidate, v.grid);
+}
+__global__ __launch_bounds__(64) void k_solve_candidate_finish(const KktDev d, const SolveDev v, double kappa, int first) {
+    __shared__ double tot[CP_COUNT];
+    combine_partials<CP_COUNT, CP_COUNT>(v.ws, v.off_candidate, v.grid, tot);
+    if (threadIdx.x != 0) return;
+    const double f = tot[CP_OBJECTIVE] + v.objective_constant;
+    double M = 0.0;
+    M += f;
+    M += tot[CP_DUAL_DOT_R] + 0.5 * d.rho[0] * tot[CP_R_DOT_R];
+    M -= kappa * tot[CP_BARRIER];
+    v.pub[PUB_CAND_OBJECTIVE] = f; v.pub[PUB_CAND_BARRIER] = tot[CP_BARRIER]; v.pub[PUB_CAND_MERIT] = M; v.pub[PUB_CAND_THETA] = tot[CP_THETA] / (double)(d.ne + d.nc);
+    if (first) v.pub[PUB_DD] = tot[CP_DD];
+}
+
+// ---- accept (solve.jl:309-333): x, r, s, t <- candidate, y <- y - a Dy, z <- z - a Dz, the constraints evaluated at the candidate become the solution's,
+// cone!(product), |g|_inf and |s o t|_inf.  start: nothing moves — g is evaluated at the solution and the cone product is taken as it LIES in its buffer
+// (solve.jl:85-86 read it before :88 forms it: stale on first use, kept) ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(KT) void k_solve_accept(const KktDev d, const SolveDev v, double a, int start) {
+    double val[AP_COUNT] = {0.0, 0.0};
+    for (long long it = (long long)blockIdx.x * KT + threadIdx.x; it < v.items; it += (long long)v.grid * KT) {
+        int k = 0, lane = 0, nl = 1;
+        const int kind = item_kind(v, it, &k, &lane, &nl);
+        if (kind == 0) {
+            if (k < d.nx) { if (!start) v.w[k] = v.cand[k]; }
+            else if (k < d.nx + d.ne) {
+                const int i = k - d.nx;
+                double g;
+                if (start) g = qp_equality_row(d, v, i, [&](int j) { return v.w[j]; });
+                else { g = v.gcand[i]; v.w[d.o_r + i] = v.cand[d.o_r + i]; v.w[d.o_y + i] = v.w[d.o_y + i] - a * v.step[d.o_y + i]; }
+                v.g[i] = g;
+                val[AP_G_INF] = fmax(val[AP_G_INF], rabs(g));
+            } else {
+                const int c = k - d.nx - d.ne;
+                if (start) { val[AP_PRODUCT_INF] = fmax(val[AP_PRODUCT_INF], rabs(v.cprod[c])); continue; }
+                const double sh = v.cand[d.o_s + c], th = v.cand[d.o_t + c];
+                v.w[d.o_s + c] = sh; v.w[d.o_t + c] = th; v.w[d.o_z + c] = v.w[d.o_z + c] - a * v.step[d.o_z + c];
+                v.h[c] = v.hcand[c];
+                if (d.row_cone[c] < 0) {
+                    const double prod = d.row_cone[c] == -1 ? sh * th : 0.0;
+                    v.cprod[c] = prod;
+                    val[AP_PRODUCT_INF] = fmax(val[AP_PRODUCT_INF], rabs(prod));
+                }
+            }
+        } else if (kind == 1 && !start) {                                                                   // (the cone reads the candidate, which nobody writes here)
+            const int st = d.soc_start[k], dm = d.soc_dim[k];
+            const double* sh = v.cand + d.o_s + st; const double* th = v.cand + d.o_t + st;
+            double dot = 0.0;
+            for (int q = lane; q < dm; q += nl) dot += sh[q] * th[q];
+            dot = cone_sum(dot, nl);
+            for (int q = lane; q < dm; q += nl) {
+                const double prod = q == 0 ? dot : sh[0] * th[q] + th[0] * sh[q];
+                v.cprod[st + q] = prod;
+                val[AP_PRODUCT_INF] = fmax(val[AP_PRODUCT_INF], rabs(prod));
+            }
+        }
+    }
+    store_partials<AP_COUNT, 0>(val, v.ws, v.off_accept, v.grid);
+}
+__global__ __launch_bounds__(64) void k_solve_accept_finish(const SolveDev v) {
+    __shared__ double tot[AP_COUNT];
+    combine_partials<AP_COUNT, 0>(v.ws, v.off_accept, v.grid, tot);
+    if (threadIdx.x == 0) { v.pub[PUB_G_INF] = tot[AP_G_INF]; v.pub[PUB_PRODUCT_INF] = tot[AP_PRODUCT_INF]; }
+}
+
+// ---- outer update (solve.jl:362-364): lambda <- lambda + rho r, with the penalty BEFORE its own update (:365) -----------------------------------------------------------
+__global__ __launch_bounds__(KT) void k_solve_outer_update(const KktDev d, const SolveDev v, double rho) {
+    const long long i = (long long)blockIdx.x * KT + threadIdx.x;
+    if (i < d.ne) v.dual[i] = v.dual[i] + rho * v.w[d.o_r + i];
+}
+
+// ---- host -------------------------------------------------------------------------------------------------------------------------------------------------------
+#define KK(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return kkt_fail(s, CALIPSO_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); } while (0)
+#define REFUSE(text) do { const std::string t__ = (text); if (!t__.empty()) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, t__); } while (0)
+
+unsigned blocks_of(long long items) { return (unsigned)std::max<long long>((items + KT - 1) / KT, 1); }
+
+int reserve_ints(KH* s, const std::vector<int>& h, const int** out) {
+    int* p = nullptr;
+    KK(hipMalloc((void**)&p, sizeof(int) * std::max<size_t>(h.size(), 1)));
+    s->dev.push_back(p);
+    if (!h.empty()) KK(hipMemcpy(p, h.data(), sizeof(int) * h.size(), hipMemcpyHostToDevice));
+    *out = p;
+    return CALIPSO_OK;
+}
+
+// the resident vectors, the workspace and the published block: made once per handle, by the first entry that needs them
+int ensure_state(KH* s) {
+    if (s->solve) return CALIPSO_OK;
+    KK(hipSetDevice(s->device));
+    SS* t = new SS();
+    s->solve = t;                                            // (released with the handle, whatever happens below)
+    const KktDev& d = s->d;
+    std::vector<int> small, wide;
+    for (int j = 0; j < d.nsoc; ++j) (s->an.soc_dim[(size_t)j] <= SMALL_CONE_MAX ? small : wide).push_back(j);
+    t->lay = layout(d.nx, d.ne, d.nc, (i64)small.size(), (i64)wide.size());
+    t->filter = Filter((i64)s->opt.max_filter);
+    SolveDev& v = t->v;
+    v.rows = t->lay.rows; v.small0 = t->lay.small0; v.wide0 = t->lay.wide0; v.items = t->lay.items;
+    v.n_small = (int)small.size(); v.n_wide = (int)wide.size(); v.grid = t->lay.grid;
+    v.off_prologue = t->lay.off_prologue; v.off_candidate = t->lay.off_candidate; v.off_accept = t->lay.off_accept;
+    int rc;
+    if ((rc = reserve_ints(s, small, &v.small_cones)) || (rc = reserve_ints(s, wide, &v.wide_cones))) return rc;
+    double *wsm = nullptr, *pub = nullptr;
+    if ((rc = kkt_reserve(s, &t->q, (size_t)d.nx)) || (rc = kkt_reserve(s, &t->b, (size_t)d.ne)) || (rc = kkt_reserve(s, &t->hvec, (size_t)d.nc)) ||
+        (rc = kkt_reserve(s, &v.cand, (size_t)d.N)) || (rc = kkt_reserve(s, &v.dual, (size_t)d.ne)) || (rc = kkt_reserve(s, &v.mgrad, (size_t)d.n)) ||
+        (rc = kkt_reserve(s, &v.bgrad, (size_t)d.nc)) || (rc = kkt_reserve(s, &v.cprod, (size_t)d.nc)) || (rc = kkt_reserve(s, &v.ctarget, (size_t)d.nc)) ||
+        (rc = kkt_reserve(s, &v.g, (size_t)d.ne)) || (rc = kkt_reserve(s, &v.h, (size_t)d.nc)) || (rc = kkt_reserve(s, &v.gcand, (size_t)d.ne)) ||
+        (rc = kkt_reserve(s, &v.hcand, (size_t)d.nc)) || (rc = kkt_reserve(s, &v.fx, (size_t)d.nx)) || (rc = kkt_reserve(s, &v.ws, (size_t)t->lay.doubles)) ||
+        (rc = kkt_reserve(s, &wsm, (size_t)(t->lay.mask_ints + 1) / 2)) || (rc = kkt_reserve(s, &pub, PUB_ALLOC_DOUBLES))) return rc;
+    v.q = t->q; v.b = t->b; v.hvec = t->hvec; v.w = s->w; v.res = s->res; v.step = s->step;
+    v.wsm = reinterpret_cast<unsigned*>(wsm); v.pub = pub; v.pub_masks = reinterpret_cast<unsigned*>(pub + PUB_DOUBLES);
+    v.objective_constant = 0.0;
+    KK(hipHostMalloc((void**)&t->hpub, sizeof(double) * PUB_ALLOC_DOUBLES));
+    std::memset(t->hpub, 0, sizeof(double) * PUB_ALLOC_DOUBLES);
+    KK(hipEventCreate(&t->ev[0])); KK(hipEventCreate(&t->ev[1]));
+    return CALIPSO_OK;
+}
+
+// ---- enqueues: each records the beginning of a timed group, the read-back closes it -----------------------------------------------------------------------------
+void open_group(KH* s) { SS* t = s->solve; if (!t->group_open) { (void)hipEventRecord(t->ev[0], s->st); t->group_open = true; } }
+
+void enqueue_init(KH* s) { SS* t = s->solve; open_group(s); hipLaunchKernelGGL(k_solve_init, dim3((unsigned)t->v.grid), dim3(KT), 0, s->st, s->d, t->v); }
+void enqueue_prologue(KH* s) {
+    SS* t = s->solve; open_group(s);
+    hipLaunchKernelGGL(k_solve_prologue, dim3((unsigned)t->v.grid), dim3(KT), 0, s->st, s->d, t->v, s->sc.kappa);
+    hipLaunchKernelGGL(k_solve_prologue_finish, dim3(1), dim3(64), 0, s->st, s->d, t->v, s->sc.kappa);
+}
+int mask_trials(const Options& o) { return (int)std::min<i64>(o.max_cone_line_search + 1, calipso::CONE_MASK_TRIALS); }
+void enqueue_cone_masks(KH* s) {
+    SS* t = s->solve; open_group(s);
+    hipLaunchKernelGGL(k_solve_cone_masks, dim3((unsigned)t->v.grid), dim3(KT), 0, s->st, s->d, t->v, s->sc.tau, s->opt.scaling_line_search, mask_trials(s->opt));
+    hipLaunchKernelGGL(k_solve_masks_finish, dim3(1), dim3(64), 0, s->st, t->v, s->opt.scaling_line_search, mask_trials(s->opt));
+}
+void enqueue_candidate(KH* s, bool from_masks, double a_s, double a_t, bool first) {
+    SS* t = s->solve; open_group(s);
+    hipLaunchKernelGGL(k_solve_candidate, dim3((unsigned)t->v.grid), dim3(KT), 0, s->st, s->d, t->v, from_masks ? (const double*)t->v.pub : (const double*)nullptr, a_s, a_t,
+                       first ? 1 : 0);
+    hipLaunchKernelGGL(k_solve_candidate_finish, dim3(1), dim3(64), 0, s->st, s->d, t->v, s->sc.kappa, first ? 1 : 0);
+}
+void enqueue_accept(KH* s, double a, bool start) {
+    SS* t = s->solve; open_group(s);
+    hipLaunchKernelGGL(k_solve_accept, dim3((unsigned)t->v.grid), dim3(KT), 0, s->st, s->d, t->v, a, start ? 1 : 0);
+    hipLaunchKernelGGL(k_solve_accept_finish, dim3(1), dim3(64), 0, s->st, t->v);
+}
+void enqueue_outer_update(KH* s, double rho) {
+    SS* t = s->solve; open_group(s);
+    if (s->d.ne) hipLaunchKernelGGL(k_solve_outer_update, dim3(blocks_of(s->d.ne)), dim3(KT), 0, s->st, s->d, t->v, rho);
+}
+// the penalty lives on the device (KktDev::rho): the kernels of both halves read it there.  Written by a kernel: stream-ordered, no host wait
+void enqueue_penalty(KH* s) {
+    open_group(s);
+    hipLaunchKernelGGL(k_solve_fill, dim3(1), dim3(KT), 0, s->st, 1, s->rho, s->sc.rho);
+    s->have[4] = true;
+}
+// the ONE read-back of a group: the published block, whole
+int read_published(KH* s) {
+    SS* t = s->solve;
+    open_group(s);
+    KK(hipEventRecord(t->ev[1], s->st));
+    KK(hipMemcpyAsync(t->hpub, t->v.pub, PUB_BYTES, hipMemcpyDeviceToHost, s->st));
+    KK(hipStreamSynchronize(s->st));
+    KK(hipGetLastError());
+    float ms = 0.f; KK(hipEventElapsedTime(&ms, t->ev[0], t->ev[1]));
+    t->vector_ms += ms; t->group_open = false; t->waits += 1;
+    return CALIPSO_OK;
+}
+const int* host_masks(const SS* t) { return reinterpret_cast<const int*>(t->hpub + PUB_DOUBLES); }
+
+// what an entry needs resident before it enqueues anything
+int ready(KH* s, const char* entry, bool point) {
+    static const char* const names[3] = {"Lxx", "gx", "hx"};
+    const size_t need[3] = {(size_t)s->d.nnzL, (size_t)s->d.nnzg, (size_t)s->d.nnzh};
+    for (int i = 0; i < 3; ++i) if (need[i] && !s->have[i]) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": no " + names[i] + " resident (calipso_hip_sparse_kkt_set_values first)");
+    SS* t = s->solve;
+    static const char* const qp[3] = {"q", "b", "hvec"};
+    const size_t len[3] = {(size_t)s->d.nx, (size_t)s->d.ne, (size_t)s->d.nc};
+    for (int i = 0; i < 3; ++i) if (len[i] && !t->have_qp[i]) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": no " + qp[i] + " resident (calipso_hip_sparse_kkt_qp_attach first)");
+    if (point && !s->have[3]) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": no point resident (calipso_hip_sparse_kkt_initialize, or set_values with w, first)");
+    if (point && s->d.ne && !s->have[4]) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": no penalty resident");
+    return CALIPSO_OK;
+}
+#define ENTRY(name, point)                                                                                             \
+    static const char* const entry = name;                                                                             \
+    if (!s) return CALIPSO_ERR_ARGUMENT;                                                                               \
+    KK(hipSetDevice(s->device));                                                                                       \
+    { const int rc__ = ensure_state(s); if (rc__ < 0) return rc__; }                                                   \
+    { const int rc__ = ready(s, entry, point); if (rc__ < 0) return rc__; }                                           \
+    SS* t = s->solve; (void)t; (void)entry
+
+int qp_attach(KH* s, const double* q, const double* b, const double* hvec, double objective_constant, hipMemcpyKind kind) {
+    SS* t = s->solve;
+    const double* src[3] = {q, b, hvec};
+    double* dst[3] = {t->q, t->b, t->hvec};
+    const size_t count[3] = {(size_t)s->d.nx, (size_t)s->d.ne, (size_t)s->d.nc};
+    for (int i = 0; i < 3; ++i) if (src[i] && count[i]) { KK(hipMemcpyAsync(dst[i], src[i], sizeof(double) * count[i], kind, s->st)); t->have_qp[i] = true; }
+    KK(hipStreamSynchronize(s->st));
+    t->v.objective_constant = objective_constant;
+    return CALIPSO_OK;
+}
+int initialize(KH* s, const double* x0, hipMemcpyKind kind) {
+    SS* t = s->solve;
+    if (s->d.nx) KK(hipMemcpyAsync(s->w, x0, sizeof(double) * (size_t)s->d.nx, kind, s->st));
+    enqueue_init(s);
+    KK(hipStreamSynchronize(s->st));
+    KK(hipGetLastError());
+    t->group_open = false;
+    s->have[3] = true;
+    s->assembled = false; s->factored = false;               // K and its factor belong to the point before
+    return CALIPSO_OK;
+}
+double* resident(KH* s, int vec) {
+    SolveDev& v = s->solve->v;
+    double* const p[V_COUNT] = {s->w, v.cand, v.dual, s->res, v.mgrad, s->step, v.cprod, v.ctarget, v.bgrad, v.g, v.h, v.fx};
+    return p[vec];
+}
+
+// solve!(solver)  solve.jl:8-377, laid out as calipso_hip_solve / inner_iteration of api.hip
+int solve(KH* s, double info[16]) {
+    const auto wall0 = std::chrono::steady_clock::now();
+    SS* t = s->solve;
+    const Options& o = s->opt; Scalars& sc = s->sc; const KktDev& d = s->d;
+    const double* pub = t->hpub;
+    t->vector_ms = 0.0; t->waits = 0; t->trace_rows = 0; t->trace_total = 0; t->group_open = false;
+    i64 total_iterations = 1, outer = 0, accepted = 0, nfact = 0, max_rounds = 0, refine_fail = 0, trials = 0;
+    int worst = 0;
+    double sd_ms = 0.0;
+    const auto leave = [&](int rc) {
+        if (info) {
+            const double out[16] = {(double)total_iterations, (double)outer, (double)accepted, (double)nfact, (double)max_rounds, (double)refine_fail, (double)worst, (double)t->waits,
+                                    (double)trials, sc.kappa, sc.rho, sc.ep_last, t->vector_ms, sd_ms, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count(),
+                                    (double)rc};
+            std::copy(out, out + 16, info);
+        }
+        return rc;
+    };
+    int rc;
+    if (o.warmstart == 0.0) enqueue_init(s);                                                  // initialize.jl:15-36
+    calipso::initial_scalars(o, sc);                                                          // initialize.jl:38-48
+    sc.ep_last = 0.0;                                                                         // (every solve starts as a fresh solver does)
+    enqueue_penalty(s);
+    if (d.ne) hipLaunchKernelGGL(k_solve_fill, dim3(blocks_of(d.ne)), dim3(KT), 0, s->st, d.ne, t->v.dual, o.dual_initial);
+    enqueue_accept(s, 0.0, true);                                                             // :85-86: |g|_inf, and the cone product as it lies (stale on first use)
+    enqueue_prologue(s);                                                                      // (forms the cone product and target of :88-91 too)
+    if ((rc = read_published(s)) < 0) return leave(rc);
+    double equality_violation = pub[PUB_G_INF], cone_product_violation = pub[PUB_PRODUCT_INF];
+    t->filter.reset();                                                                        // :95
+    for (i64 j = 1; j <= o.max_outer_iterations; ++j) {
+        outer = j;
+        for (i64 i = 1; i <= o.max_residual_iterations; ++i) {
+            // the published block holds the prologue of this step (:100-135, 170-172)
+            const double M = pub[PUB_MERIT], theta = pub[PUB_THETA];
+            const calipso::StepNorms norms = calipso::step_norms(pub, d.N, d.ne, d.nc);
+            const int kind = calipso::exit_kind(o, sc.kappa, norms, equality_violation, cone_product_violation, true);      // :138-143, :165
+            if (kind == 1) return leave(1);
+            if (kind == 2) break;
+            // :175-185: Hessian and Jacobians are constant, the dual Hessians zero, the cone Jacobians formed inside the kernels of sparse_kkt.hip
+            double reg[3] = {sc.ep, sc.ep_last, sc.ed}, sdinfo[4] = {0, 0, 0, 0};
+            rc = kkt_search_direction(s, s->res, s->step, reg, sdinfo);                       // :187
+            nfact += (i64)sdinfo[0]; max_rounds = std::max(max_rounds, (i64)sdinfo[1]);
+            for (int k = 0; k < 5; ++k) sd_ms += s->ms[k];
+            if (rc < 0) return leave(rc);
+            if (rc == CALIPSO_WARN_REFINEMENT) {
+                refine_fail += 1; worst = std::max(worst, rc);
+                // the reference goes on to `H \ residual` (search_direction.jl:22): no such fallback on this handle
+                if (!s->continue_after_refinement_failure) {
+                    kkt_fail(s, -100 - CALIPSO_WARN_REFINEMENT, "calipso_hip_sparse_kkt_solve: iterative refinement failed (iterative_refinement.jl:50) and this handle has no `H \\ residual` fallback; the point is the last accepted iterate");
+                    return leave(-100 - CALIPSO_WARN_REFINEMENT);
+                }
+            }
+            // cone search (:190-221) and the first candidate (:206-250) behind it, its step sizes taken from the masks on the device: one read-back
+            enqueue_cone_masks(s);
+            enqueue_candidate(s, true, 0.0, 0.0, true);
+            if ((rc = read_published(s)) < 0) return leave(rc);
+            double step_size = 1.0, step_size_t = 1.0;
+            if (!calipso::cone_step_sizes(host_masks(t), host_masks(t) + calipso::CONE_MASK_WORDS, o, &step_size, &step_size_t)) {
+                kkt_fail(s, CALIPSO_ERR_CONE_SEARCH, "cone search failure (solve.jl:210,220)");
+                return leave(CALIPSO_ERR_CONE_SEARCH);
+            }
+            if (step_size != pub[PUB_STEP_S] || step_size_t != pub[PUB_STEP_T])
+                return leave(kkt_fail(s, CALIPSO_ERR_HIP, "calipso_hip_sparse_kkt_solve: the step sizes formed on the device are not those of cone_step_sizes()"));
+            double Mh = pub[PUB_CAND_MERIT], thetah = pub[PUB_CAND_THETA];
+            const double dd = pub[PUB_DD];
+            i64 residual_iteration = 0;
+            while (residual_iteration < o.max_residual_line_search) {                         // :254-302
+                if (calipso::line_search_accepts(o, t->filter.accepts(thetah, Mh), theta, M, thetah, Mh, dd, step_size)) break;
+                step_size = o.scaling_line_search * step_size;
+                enqueue_candidate(s, false, step_size, step_size_t, false);                   // :268-297
+                if ((rc = read_published(s)) < 0) return leave(rc);
+                Mh = pub[PUB_CAND_MERIT]; thetah = pub[PUB_CAND_THETA];
+                residual_iteration += 1; trials += 1;
+            }
+            if (residual_iteration >= o.max_residual_line_search) worst = std::max(worst, (int)CALIPSO_WARN_LINE_SEARCH);
+            if (calipso::filter_needs_augment(o, theta, M, Mh, dd, step_size))                // filter.jl:81-89
+                t->filter.augment((1.0 - o.violation_tolerance) * theta, M - o.merit_tolerance * theta);
+            enqueue_accept(s, step_size, false);                                              // :309-333
+            if (t->trace_rows < t->trace_cap) {
+                KK(hipMemcpyAsync(t->trace + (size_t)t->trace_rows * (size_t)d.N, s->w, sizeof(double) * (size_t)d.N, hipMemcpyDeviceToDevice, s->st));
+                t->trace_rows += 1;
+            }
+            t->trace_total += 1;
+            enqueue_prologue(s);                                                              // the next step's, at the same scalars: read back with the two violations
+            if ((rc = read_published(s)) < 0) return leave(rc);
+            equality_violation = pub[PUB_G_INF]; cone_product_violation = pub[PUB_PRODUCT_INF];
+            total_iterations += 1; accepted += 1;
+        }
+        calipso::central_path_update(o, sc);                                                  // :356-359
+        enqueue_outer_update(s, sc.rho);                                                      // :362-364
+        calipso::penalty_update(o, sc);                                                       // :365
+        enqueue_penalty(s);
+        t->filter.reset();                                                                    // :368
+        if (j < o.max_outer_iterations) {
+            enqueue_prologue(s);
+            if ((rc = read_published(s)) < 0) return leave(rc);
+        }
+    }
+    KK(hipStreamSynchronize(s->st));
+    t->group_open = false;
+    return leave(0);
+}
+
+}  // namespace
+
+namespace calipso {
+namespace sparse_kkt {
+
+void solve_state_release(KH* s) {
+    SS* t = s->solve;
+    if (!t) return;
+    for (void* p : t->own) if (p) (void)hipFree(p);
+    if (t->hpub) (void)hipHostFree(t->hpub);
+    for (hipEvent_t e : t->ev) if (e) (void)hipEventDestroy(e);
+    delete t;
+    s->solve = nullptr;
+}
+
+int solve_set_option(KH* s, const char* name, double value) {
+    if (calipso::set_solve_option(s->opt, name, value)) {
+        if (s->solve && !std::strcmp(name, "max_filter")) s->solve->filter = Filter((i64)s->opt.max_filter);
+        return 1;
+    }
+    const std::string n(name);
+    if (n == "continue_after_refinement_failure") { s->continue_after_refinement_failure = value != 0.0; return 1; }
+    if (n == "fraction_to_boundary") { s->sc.tau = value; return 1; }
+    if (n == "penalty") {
+        if (hipSetDevice(s->device) != hipSuccess) return kkt_fail(s, CALIPSO_ERR_HIP, "hipSetDevice");
+        { const int rc = ensure_state(s); if (rc < 0) return rc; }
+        s->sc.rho = value;
+        enqueue_penalty(s);
+        if (hipStreamSynchronize(s->st) != hipSuccess) return kkt_fail(s, CALIPSO_ERR_HIP, "hipStreamSynchronize");
+        s->solve->group_open = false;
+        return 1;
+    }
+    return 0;
+}
+
+}  // namespace sparse_kkt
+}  // namespace calipso
+
+extern "C" {
+
+int32_t calipso_hip_sparse_kkt_qp_attach(calipso_hip_sparse_kkt* s, const double* q, const double* b, const double* hvec, double objective_constant) {
+    if (!s) return CALIPSO_ERR_ARGUMENT;
+    KK(hipSetDevice(s->device));
+    { const int rc = ensure_state(s); if (rc < 0) return rc; }
+    return qp_attach(s, q, b, hvec, objective_constant, hipMemcpyHostToDevice);
+}
+int32_t calipso_hip_sparse_kkt_qp_attach_device(calipso_hip_sparse_kkt* s, const double* q, const double* b, const double* hvec, double objective_constant) {
+    if (!s) return CALIPSO_ERR_ARGUMENT;
+    KK(hipSetDevice(s->device));
+    { const int rc = ensure_state(s); if (rc < 0) return rc; }
+    static const char* const entry = "calipso_hip_sparse_kkt_qp_attach_device";
+    const void* ptrs[3] = {q, b, hvec}; const char* const names[3] = {"q", "b", "hvec"};
+    for (int i = 0; i < 3; ++i) { const int rc = kkt_device_pointer(s, ptrs[i], entry, names[i]); if (rc < 0) return rc; }
+    return qp_attach(s, q, b, hvec, objective_constant, hipMemcpyDeviceToDevice);
+}
+
+int32_t calipso_hip_sparse_kkt_initialize(calipso_hip_sparse_kkt* s, const double* x0) {
+    ENTRY("calipso_hip_sparse_kkt_initialize", false);
+    if (!x0 && s->d.nx) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_sparse_kkt_initialize: x0 is NULL");
+    return initialize(s, x0, hipMemcpyHostToDevice);
+}
+int32_t calipso_hip_sparse_kkt_initialize_device(calipso_hip_sparse_kkt* s, const double* x0) {
+    ENTRY("calipso_hip_sparse_kkt_initialize_device", false);
+    if (!x0 && s->d.nx) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_sparse_kkt_initialize_device: x0 is NULL");
+    { const int rc = kkt_device_pointer(s, x0, entry, "x0"); if (rc < 0) return rc; }
+    return initialize(s, x0, hipMemcpyDeviceToDevice);
+}
+
+int32_t calipso_hip_sparse_kkt_solve(calipso_hip_sparse_kkt* s, double info[16]) {
+    if (!s) return CALIPSO_ERR_ARGUMENT;
+    KK(hipSetDevice(s->device));
+    { const int rc = ensure_state(s); if (rc < 0) return rc; }
+    if (s->d.ne && !s->have[4]) s->have[4] = true;           // (solve! sets the penalty itself: initialize.jl:44-48)
+    { const int rc = ready(s, "calipso_hip_sparse_kkt_solve", true); if (rc < 0) return rc; }
+    (void)hipGetLastError();
+    return solve(s, info);
+}
+
+int32_t calipso_hip_sparse_kkt_step_prologue(calipso_hip_sparse_kkt* s, int32_t which, double scalars[16]) {
+    ENTRY("calipso_hip_sparse_kkt_step_prologue", true);
+    if (which != 0) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_sparse_kkt_step_prologue: which: the prologue is taken at the solution (0); calipso_hip_sparse_kkt_candidate evaluates a candidate");
+    enqueue_prologue(s);
+    { const int rc = read_published(s); if (rc < 0) return rc; }
+    if (scalars) {
+        const double* p = t->hpub;
+        const calipso::StepNorms n = calipso::step_norms(p, s->d.N, s->d.ne, s->d.nc);
+        const double out[16] = {p[PUB_OBJECTIVE], p[PUB_BARRIER], p[PUB_MERIT], p[PUB_THETA], n.residual_violation, n.optimality, n.slack_violation, 0.0,
+                                p[8], p[9], p[10], p[11], p[12], p[13], p[14], p[15]};
+        std::copy(out, out + 16, scalars);
+    }
+    return CALIPSO_OK;
+}
+
+int32_t calipso_hip_sparse_kkt_cone_search(calipso_hip_sparse_kkt* s, double a[2]) {
+    ENTRY("calipso_hip_sparse_kkt_cone_search", true);
+    if (!a) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_sparse_kkt_cone_search: a is NULL");
+    enqueue_cone_masks(s);
+    { const int rc = read_published(s); if (rc < 0) return rc; }
+    if (!calipso::cone_step_sizes(host_masks(t), host_masks(t) + calipso::CONE_MASK_WORDS, s->opt, &a[0], &a[1])) return kkt_fail(s, CALIPSO_ERR_CONE_SEARCH, "cone search failure (solve.jl:210,220)");
+    return CALIPSO_OK;
+}
+
+int32_t calipso_hip_sparse_kkt_candidate(calipso_hip_sparse_kkt* s, double a_s, double a_t, double out[3]) {
+    ENTRY("calipso_hip_sparse_kkt_candidate", true);
+    REFUSE(check_step_sizes(entry, a_s, a_t));
+    enqueue_candidate(s, false, a_s, a_t, true);
+    { const int rc = read_published(s); if (rc < 0) return rc; }
+    if (out) { out[0] = t->hpub[PUB_CAND_MERIT]; out[1] = t->hpub[PUB_CAND_THETA]; out[2] = t->hpub[PUB_DD]; }
+    return CALIPSO_OK;
+}
+
+int32_t calipso_hip_sparse_kkt_accept(calipso_hip_sparse_kkt* s, double a, double violations[2]) {
+    ENTRY("calipso_hip_sparse_kkt_accept", true);
+    REFUSE(check_step_sizes(entry, a, 1.0));
+    enqueue_accept(s, a, false);
+    { const int rc = read_published(s); if (rc < 0) return rc; }
+    if (violations) { violations[0] = t->hpub[PUB_G_INF]; violations[1] = t->hpub[PUB_PRODUCT_INF]; }
+    s->assembled = false; s->factored = false;
+    return CALIPSO_OK;
+}
+
+int32_t calipso_hip_sparse_kkt_outer_update(calipso_hip_sparse_kkt* s) {
+    ENTRY("calipso_hip_sparse_kkt_outer_update", true);
+    double rho = 0.0;
+    KK(hipMemcpyAsync(&rho, s->rho, sizeof(double), hipMemcpyDeviceToHost, s->st));
+    KK(hipStreamSynchronize(s->st));
+    enqueue_outer_update(s, rho);
+    KK(hipStreamSynchronize(s->st));
+    t->group_open = false;
+    return CALIPSO_OK;
+}
+
+int32_t calipso_hip_sparse_kkt_get(calipso_hip_sparse_kkt* s, const char* name, double* out, int64_t len) {
+    if (!s) return CALIPSO_ERR_ARGUMENT;
+    KK(hipSetDevice(s->device));
+    { const int rc = ensure_state(s); if (rc < 0) return rc; }
+    REFUSE(check_named_vector("calipso_hip_sparse_kkt_get", name, out, len, s->d.nx, s->d.ne, s->d.nc, false));
+    if (len) KK(hipMemcpyAsync(out, resident(s, vector_by_name(name)), sizeof(double) * (size_t)len, hipMemcpyDeviceToHost, s->st));
+    KK(hipStreamSynchronize(s->st));
+    return CALIPSO_OK;
+}
+int32_t calipso_hip_sparse_kkt_set(calipso_hip_sparse_kkt* s, const char* name, const double* in, int64_t len) {
+    if (!s) return CALIPSO_ERR_ARGUMENT;
+    KK(hipSetDevice(s->device));
+    { const int rc = ensure_state(s); if (rc < 0) return rc; }
+    REFUSE(check_named_vector("calipso_hip_sparse_kkt_set", name, in, len, s->d.nx, s->d.ne, s->d.nc, true));
+    const int vec = vector_by_name(name);
+    if (len) KK(hipMemcpyAsync(resident(s, vec), in, sizeof(double) * (size_t)len, hipMemcpyHostToDevice, s->st));
+    KK(hipStreamSynchronize(s->st));
+    if (vec == V_SOLUTION) { s->have[3] = true; s->assembled = false; s->factored = false; }
+    return CALIPSO_OK;
+}
+int32_t calipso_hip_sparse_kkt_solution_device(calipso_hip_sparse_kkt* s, double** p) {
+    if (!s || !p) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_sparse_kkt_solution_device: p is NULL");
+    KK(hipSetDevice(s->device));
+    KK(hipStreamSynchronize(s->st));
+    *p = s->w;
+    return CALIPSO_OK;
+}
+
+int32_t calipso_hip_sparse_kkt_keep_trace(calipso_hip_sparse_kkt* s, int64_t rows) {
+    if (!s) return CALIPSO_ERR_ARGUMENT;
+    KK(hipSetDevice(s->device));
+    { const int rc = ensure_state(s); if (rc < 0) return rc; }
+    REFUSE(check_keep_trace(rows));
+    SS* t = s->solve;
+    if (rows > t->trace_cap) {
+        KK(hipStreamSynchronize(s->st));
+        double* p = nullptr;
+        KK(hipMalloc((void**)&p, sizeof(double) * (size_t)rows * (size_t)std::max(s->d.N, 1)));
+        for (void*& old : t->own) if (old == t->trace) { (void)hipFree(old); old = nullptr; }
+        t->own.push_back(p);
+        t->trace = p;
+        t->trace_rows = 0; t->trace_total = 0;
+    }
+    t->trace_cap = rows;
+    t->trace_rows = std::min(t->trace_rows, rows);
+    return CALIPSO_OK;
+}
+int32_t calipso_hip_sparse_kkt_trace(calipso_hip_sparse_kkt* s, double* out, int64_t cap_rows, int64_t* accepted) {
+    if (!s) return CALIPSO_ERR_ARGUMENT;
+    KK(hipSetDevice(s->device));
+    { const int rc = ensure_state(s); if (rc < 0) return rc; }
+    REFUSE(check_trace(out, cap_rows));
+    SS* t = s->solve;
+    const i64 rows = std::min<i64>(t->trace_rows, cap_rows);
+    if (rows > 0 && s->d.N) KK(hipMemcpyAsync(out, t->trace, sizeof(double) * (size_t)rows * (size_t)s->d.N, hipMemcpyDeviceToHost, s->st));
+    KK(hipStreamSynchronize(s->st));
+    if (accepted) *accepted = t->trace_total;
+    return (int32_t)rows;
+}
+
+}  // extern "C"

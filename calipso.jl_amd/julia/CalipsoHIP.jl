@@ -492,6 +492,33 @@ function sparse_search_direction_device!(k::SparseKKT, residual::Ptr{Cvoid}, ste
 end
 kkt_timing(k::SparseKKT) = (ms = zeros(8); kkt_check(ccall((:calipso_hip_sparse_kkt_timing, lib), Int32, (Ptr{Cvoid}, Ptr{Float64}), k.handle, ms), k, "timing"); ms)
 
+# ---- solve! on the same handle (csrc/sparse_solve.hip): the sparse conic QP  min c x'Px + q'x  s.t.  Ax - b = 0,  h - Gx in K  with Lxx = c (P + P'), gx = A, hx = -G ----
+# host vectors (nothing keeps what is resident)
+qp_attach!(k::SparseKKT; q=nothing, b=nothing, h=nothing, objective_constant::Real=0.0) = GC.@preserve q b h kkt_check(
+    ccall((:calipso_hip_sparse_kkt_qp_attach, lib), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Float64), k.handle, kkt_ptr(q), kkt_ptr(b), kkt_ptr(h),
+          objective_constant), k, "qp_attach!")
+# initialize!(solver, x0)  initialize.jl:9-48
+sparse_initialize!(k::SparseKKT, x0::Vector{Float64}) = kkt_check(ccall((:calipso_hip_sparse_kkt_initialize, lib), Int32, (Ptr{Cvoid}, Ptr{Float64}), k.handle, x0), k, "initialize!")
+"""
+    sparse_solve!(kkt) -> (status, info)
+
+solve! (solve.jl:8-377) with every vector resident on the device.  status 1 solved, 0 iteration caps, -102 a refinement failure without the option
+`continue_after_refinement_failure` (the point is the last accepted iterate); the reference's error()s throw.  `info` as calipso_hip_sparse_kkt_solve documents it.
+"""
+function sparse_solve!(k::SparseKKT)
+    info = zeros(16)
+    rc = ccall((:calipso_hip_sparse_kkt_solve, lib), Int32, (Ptr{Cvoid}, Ptr{Float64}), k.handle, info)
+    rc == -102 || kkt_check(rc, k, "solve!")
+    return rc, info
+end
+function sparse_get(k::SparseKKT, name::AbstractString, len::Integer)
+    out = zeros(len)
+    kkt_check(ccall((:calipso_hip_sparse_kkt_get, lib), Int32, (Ptr{Cvoid}, Cstring, Ptr{Float64}, Int64), k.handle, name, out, len), k, "get($name)")
+    return out
+end
+sparse_set!(k::SparseKKT, name::AbstractString, v::Vector{Float64}) =
+    kkt_check(ccall((:calipso_hip_sparse_kkt_set, lib), Int32, (Ptr{Cvoid}, Cstring, Ptr{Float64}, Int64), k.handle, name, v, length(v)), k, "set($name)")
+
 # The handle-resident variant: the KKT blocks are already on the device (uploaded by the evaluation callback or by set_field!), the
 # condensed matrix is never formed on the host.  factorize! = calipso_hip_factorize on those blocks with the handle's kappa / rho /
 # regularisation scalars (which the caller syncs with sync_scalars!); `A` is accepted for signature parity only.
@@ -894,7 +921,7 @@ function allreduce_sum!(c::HIPComm, v::Vector{Float64})
     return v
 end
 
-export SparseKKT, set_values!, set_values_device!, kkt_info, kkt_pattern, kkt_factorize!, kkt_matrix!, kkt_mul!, solve_symmetric!, sparse_search_direction!, sparse_search_direction_device!, kkt_timing
+export SparseKKT, set_values!, set_values_device!, kkt_info, kkt_pattern, kkt_factorize!, kkt_matrix!, kkt_mul!, solve_symmetric!, sparse_search_direction!, sparse_search_direction_device!, kkt_timing, qp_attach!, sparse_initialize!, sparse_solve!, sparse_get, sparse_set!
 export HIPSolver, streams_concurrent, rebind_stream!, spread_streams!, HIPLDLSolver, HIPSparseLDLSolver, hip_sparse_ldl_solver, HIPKKTSolver, hip_ldl_solver, HIPGroup, HIPSmallNewton, set_option!, set_cones!, set_qp!, set_evaluator!, set_parameters!, differentiate_adjoint!, solution, set_stream!, set_qp_device!, initialize_device!, set_state_device!, set_parameters_device!, solve_device!, solution_device!, differentiate_adjoint_device!, HIPComm, comm_unique_id, comm_size, gather_status, allreduce_sum!, newton_step!,
        search_direction_nonsymmetric!, analyze_structure!, clear_structure!, set_stage_parallel!, set_stage_blocks!, declared_structure, kernel_times, sync_scalars!, copy_back!
 

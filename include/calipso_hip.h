@@ -567,6 +567,57 @@ int32_t calipso_hip_sparse_kkt_search_direction(calipso_hip_sparse_kkt*, const d
 int32_t calipso_hip_sparse_kkt_search_direction_device(calipso_hip_sparse_kkt*, const double* residual, double* step, double regularization[3], double info[4]);
 int32_t calipso_hip_sparse_kkt_timing(calipso_hip_sparse_kkt*, double ms[8]);
 
+/* ---- solve! on sparse problem data resident on the device (csrc/sparse_solve.hip; host pieces: csrc/sparse_solve.hpp) --------------------------------------
+ * The vector half of a sparse solve! on the same handle, and the whole solve! (src/solver/solve.jl:8-377) for the problem class that needs no user code, the
+ * sparse conic QP   min c x'Px + q'x  s.t.  Ax - b = 0,  h - Gx in K   in the handle's terms: Lxx = c (P + P'), gx = A, hx = -G (set_values), and three more
+ * resident vectors q (nx), b (ne), hvec (nc).  evaluate! (evaluate.jl:37-121) is then a gather over the views the handle holds: f = 1/2 x'Lxx x + q'x + constant,
+ * fx = Lxx x + q, g = gx x - b, h = hx x + hvec, gx'y, hx'z; Hessian and Jacobians are constant and the dual Hessians zero.  Every vector stays on the device
+ * from initialize! to the converged point; sums are reduced in a fixed order, so a solve repeats bit for bit.
+ *   qp_attach       q, b, hvec and the objective's constant: host arrays, or (_device) device pointers, checked as in set_values_device.  NULL keeps what is resident.
+ *   initialize      initialize!(solver, x0) (initialize.jl:9-48): x <- x0, r <- g(x0), s, t <- the cones' interior points, y, z <- 0.  (_device: x0 on the device.)
+ *   solve           solve! whole.  Without the option warmstart it repeats initialize_slacks! / initialize_duals! from the resident x, as calipso_hip_solve does.  The
+ *                   decisions are those of csrc/step_decisions.hpp; the linear algebra is search_direction above, on resident vectors; primal_regularization_last
+ *                   starts at 0 in every solve.  Returns 1 solved, 0 iteration caps, CALIPSO_ERR_INERTIA, CALIPSO_ERR_CONE_SEARCH, CALIPSO_ERR_ARGUMENT (nothing
+ *                   attached, no point), CALIPSO_ERR_HIP — and -100 - CALIPSO_WARN_REFINEMENT where the refinement fails and the reference goes on to `H \ residual`
+ *                   (search_direction.jl:22): the handle has no such fallback, the point is the last accepted iterate and the handle stays usable.  With the option
+ *                   continue_after_refinement_failure = 1 the step search_direction left (the last refined one) is taken, the event counted, and the solve goes on.
+ *                   info[16] = total_iterations, outer iterations, accepted iterates, factorisations, most refinement rounds of a step, refinement failures, worst
+ *                   warning (CALIPSO_WARN_LINE_SEARCH as calipso_hip_solve reports it), host waits outside search_direction, line-search trials beyond the first
+ *                   candidates, central_path and penalty at exit, primal_regularization_last, device ms of the vector half, device ms inside search_direction,
+ *                   wall ms, the status.  Host waits: accept is read back together with the next step's prologue, the cone-search masks with the first candidate,
+ *                   every further trial once, the prologue behind an outer update once: 2 accepted + outer + trials.
+ *   step_prologue   solve.jl:100-135, 170-172 at the solution (which = 0): evaluate!, cone!(barrier, barrier_gradient, product, target), merit and merit_gradient
+ *                   (merit.jl:2-31), residual! (residual.jl:1-51), constraint_violation!, the norms of optimality_error.jl:1-27 — central_path as set_option gave it,
+ *                   the penalty and the dual as resident.  scalars[16] = f, barrier, merit, constraint violation, residual violation, optimality error, slack
+ *                   violation, 0, then |residual|_1, |residual[1:n]|_inf, |residual_y|_inf, |residual_z|_inf, |residual_t|_inf, |y|_1, |z|_1, |t|_1
+ *   cone_search     solve.jl:190-221 on the resident step with fraction_to_boundary and max_cone_line_search: a[2] = the step sizes of the cone slacks and of
+ *                   their duals, or CALIPSO_ERR_CONE_SEARCH
+ *   candidate       solve.jl:206-250: x^, r^, s^ with a_s, t^ with a_t; out[3] = merit and constraint violation at the candidate, merit_gradient . step.primals
+ *   accept          solve.jl:309-333 with step size a: violations[2] = |g|_inf, |s o t|_inf
+ *   outer_update    solve.jl:362-364: dual <- dual + penalty r
+ *   get / set       the resident vectors by their reference names: solution, candidate, dual, residual, merit_gradient, step, cone_product, cone_target,
+ *                   barrier_gradient, equality_constraint, cone_constraint, objective_gradient_variables; set takes solution, dual and step (tests, warm starts)
+ *   solution_device the resident point (N doubles on the handle's device), synchronised
+ *   keep_trace / trace   solution.all after each accepted iterate of a solve, at most `rows` of them kept on the device; trace returns the rows copied (at most
+ *                   cap_rows) and, in *accepted, the accepted iterates of the last solve
+ *   set_option      additionally every option solve! reads (include/calipso_options.hpp: set_solve_option), fraction_to_boundary, penalty (the resident scalar),
+ *                   warmstart, continue_after_refinement_failure */
+int32_t calipso_hip_sparse_kkt_qp_attach(calipso_hip_sparse_kkt*, const double* q, const double* b, const double* hvec, double objective_constant);
+int32_t calipso_hip_sparse_kkt_qp_attach_device(calipso_hip_sparse_kkt*, const double* q, const double* b, const double* hvec, double objective_constant);
+int32_t calipso_hip_sparse_kkt_initialize(calipso_hip_sparse_kkt*, const double* x0);
+int32_t calipso_hip_sparse_kkt_initialize_device(calipso_hip_sparse_kkt*, const double* x0);
+int32_t calipso_hip_sparse_kkt_solve(calipso_hip_sparse_kkt*, double info[16]);
+int32_t calipso_hip_sparse_kkt_step_prologue(calipso_hip_sparse_kkt*, int32_t which, double scalars[16]);
+int32_t calipso_hip_sparse_kkt_cone_search(calipso_hip_sparse_kkt*, double a[2]);
+int32_t calipso_hip_sparse_kkt_candidate(calipso_hip_sparse_kkt*, double a_s, double a_t, double out[3]);
+int32_t calipso_hip_sparse_kkt_accept(calipso_hip_sparse_kkt*, double a, double violations[2]);
+int32_t calipso_hip_sparse_kkt_outer_update(calipso_hip_sparse_kkt*);
+int32_t calipso_hip_sparse_kkt_get(calipso_hip_sparse_kkt*, const char* name, double* out, int64_t len);
+int32_t calipso_hip_sparse_kkt_set(calipso_hip_sparse_kkt*, const char* name, const double* in, int64_t len);
+int32_t calipso_hip_sparse_kkt_solution_device(calipso_hip_sparse_kkt*, double** p);
+int32_t calipso_hip_sparse_kkt_keep_trace(calipso_hip_sparse_kkt*, int64_t rows);
+int32_t calipso_hip_sparse_kkt_trace(calipso_hip_sparse_kkt*, double* out, int64_t cap_rows, int64_t* accepted);
+
 /* ---- batched small systems (BASELINE config C5): LDS-resident LDL^T + multi-right-hand-side solve, one workgroup per
  * instance, one launch for the whole batch.  The sensitivity solves of the reference's MPC auto-tuning loop
  * (examples/autotuning/cartpole.jl:179-227 -> differentiate.jl:29-58: n = 89, 102 parameter columns per step) for thousands of

@@ -47,4 +47,26 @@ inline bool set_search_direction_option(Options& o, const char* name, double val
     return false;
 }
 
+// every other option solve! reads (solve.jl:8-377, merit.jl, filter.jl, line_search.jl, initialize.jl:38-48) by name, for the set_option entry of a handle that runs a
+// whole solve!.  residual_norm and constraint_norm are not in it: the kernels take the 1-norms, the options' defaults.  false: `name` is none of them
+inline bool set_solve_option(Options& o, const char* name, double value) {
+    struct Real { const char* name; double Options::*field; };
+    struct Int { const char* name; i64 Options::*field; };
+    static const Real reals[] = {{"scaling_line_search", &Options::scaling_line_search}, {"central_path_initial", &Options::central_path_initial},
+                                 {"central_path_update_tolerance", &Options::central_path_update_tolerance}, {"central_path_scaling", &Options::central_path_scaling},
+                                 {"central_path_exponent", &Options::central_path_exponent}, {"penalty_initial", &Options::penalty_initial},
+                                 {"penalty_scaling", &Options::penalty_scaling}, {"dual_initial", &Options::dual_initial}, {"residual_tolerance", &Options::residual_tolerance},
+                                 {"optimality_tolerance", &Options::optimality_tolerance}, {"slack_tolerance", &Options::slack_tolerance},
+                                 {"equality_tolerance", &Options::equality_tolerance}, {"complementarity_tolerance", &Options::complementarity_tolerance},
+                                 {"max_penalty", &Options::max_penalty}, {"violation_tolerance", &Options::violation_tolerance}, {"violation_exponent", &Options::violation_exponent},
+                                 {"merit_tolerance", &Options::merit_tolerance}, {"merit_exponent", &Options::merit_exponent}, {"armijo_tolerance", &Options::armijo_tolerance},
+                                 {"machine_tolerance", &Options::machine_tolerance}, {"max_filter", &Options::max_filter}, {"warmstart", &Options::warmstart}};
+    static const Int ints[] = {{"max_outer_iterations", &Options::max_outer_iterations}, {"max_residual_iterations", &Options::max_residual_iterations},
+                               {"max_residual_line_search", &Options::max_residual_line_search}, {"max_cone_line_search", &Options::max_cone_line_search}};
+    const auto same = [](const char* a, const char* b) { while (*a && *a == *b) { ++a; ++b; } return *a == *b; };
+    for (const Real& r : reals) if (same(r.name, name)) { o.*(r.field) = value; return true; }
+    for (const Int& r : ints) if (same(r.name, name)) { o.*(r.field) = (i64)value; return true; }
+    return false;
+}
+
 }  // namespace calipso

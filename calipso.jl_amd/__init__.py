@@ -865,7 +865,8 @@ class SparseKKT(_Handle):
     n_nonnegative rows of hx nonnegative (default: all that the second-order cones leave), then contiguous second-order cones of second_order_dims.
     method / perm as SparseLDL.  There is no `H \\ residual` fallback: search_direction returns status 2 (CALIPSO_WARN_REFINEMENT) with the last refined step.
     With attach_qp the same handle runs the vector half of solve! and a whole solve! of the sparse conic QP (csrc/sparse_solve.hip): initialize, solve, and the steps of an
-    iteration one by one."""
+    iteration one by one — and differentiate! in both directions (csrc/sparse_differentiate.hip): solve_columns, differentiate, vjp with the data gradients on the
+    stored patterns."""
     _last_error, _destroy = "calipso_hip_sparse_kkt_last_error", "calipso_hip_sparse_kkt_destroy"
     _message = _Handle._STATUS_MESSAGE
 
@@ -1007,10 +1008,12 @@ class SparseKKT(_Handle):
         return step, self.regularization, dict(factorizations=int(info[0]), refinement_rounds=int(info[1]), residual_norm=float(info[2])), rc
 
     def timing(self):
-        """device milliseconds of the last search_direction: dict(assemble, factorize, solve, refinement_solves, refinement_mul, wall)"""
+        """device milliseconds of the last search_direction: dict(assemble, factorize, solve, refinement_solves, refinement_mul, wall); and of the last solve_columns /
+        differentiate / vjp: columns_map (its first pre + multi-column solve + post), columns_rounds (its correction rounds, read-backs included) — their assemble and
+        factorisation are added to the first two"""
         ms = np.zeros(8)
         self._check(self._L.calipso_hip_sparse_kkt_timing(self._h, _pd(ms)), "sparse_kkt_timing")
-        return dict(zip(("assemble", "factorize", "solve", "refinement_solves", "refinement_mul", "wall"), (float(v) for v in ms[:6])))
+        return dict(zip(("assemble", "factorize", "solve", "refinement_solves", "refinement_mul", "wall", "columns_map", "columns_rounds"), (float(v) for v in ms)))
 
     # ---- solve! on the same handle (include/calipso_hip.h, "solve! on sparse problem data"; csrc/sparse_solve.hip) ----------------------------------------
     SOLVE_INFO = ("total_iterations", "outer_iterations", "accepted_iterates", "factorizations", "max_refinement_rounds", "refinement_failures", "worst_warning",
@@ -1086,7 +1089,128 @@ class SparseKKT(_Handle):
     def outer_update(self):
         self._check(self._L.calipso_hip_sparse_kkt_outer_update(self._h), "sparse_kkt_outer_update")
 
+    # ---- differentiate! on the same handle (include/calipso_hip.h, "differentiate! on sparse problem data"; csrc/sparse_differentiate.hip) -------------------
+    GRADIENTS = "LqgbHh"      # the data gradients of vjp by letter: Lxx, q, gx, b, hx, hvec — the matrices as the values on their stored patterns
+    _QP_LETTERS = dict(P="L", A="g", G="H")      # a handle from SparseConicQP also answers for P, A, G
+
+    def _columns_call(self, entry, a, message, call):
+        """a (N,) or (N, k), host array or CUDA tensor -> call(k, pointer of the N x k column-major block, pointer of an N x k output) -> the output in a's shape"""
+        if self._is_device(a) and hasattr(a, "is_cuda"):
+            import torch
+            if a.dim() not in (1, 2) or a.shape[0] != self.N:
+                raise ValueError(message)
+            k = 1 if a.dim() == 1 else int(a.shape[1])
+            src = a.detach().reshape(self.N, k).t().contiguous()
+            out = torch.empty((k, self.N), dtype=torch.float64, device=torch.device("cuda", self.device))
+            self._check(call(True, k, self._device_pointer(src, entry, k * self.N), C.c_void_p(out.data_ptr())), entry)
+            return out[0] if a.dim() == 1 else out.t()
+        flat, k, squeeze = pack_cotangent(a, (), self.N, message)
+        out = np.zeros(k * self.N)
+        self._check(call(False, k, _pd(flat), _pd(out)), entry)
+        return unpack_columns(out, (), k, (self.N,), squeeze)
+
+    def solve_columns(self, B, transposed=False):
+        """X = M B for the condensed solve's map M of solve_symmetric (transposed: M' B) with the CURRENT factorisation, all columns of B (N,) or (N, k) through the
+        launches of one; no refinement.  A CUDA tensor takes the device route and comes back as one"""
+        L = self._L
+        return self._columns_call("sparse_kkt_solve_columns", B, "SparseKKT.solve_columns: B must be (N,) or (N, k)", lambda dev, k, b, x:
+                                  (L.calipso_hip_sparse_kkt_solve_columns_device if dev else L.calipso_hip_sparse_kkt_solve_columns)(self._h, k, 1 if transposed else 0, b, x))
+
+    def differentiate(self, J):
+        """forward differentiate! for the caller's dR/dtheta J (N,) or (N, k): one factorisation at the (ep, ed) the handle holds, then S = -M J (with the correction rounds
+        under set_option("differentiate_refinement", 1): differentiate_info)"""
+        L = self._L
+        return self._columns_call("sparse_kkt_differentiate", J, "SparseKKT.differentiate: J must be (N,) or (N, k)", lambda dev, k, j, s:
+                                  (L.calipso_hip_sparse_kkt_differentiate_device if dev else L.calipso_hip_sparse_kkt_differentiate)(self._h, k, j, s))
+
+    def vjp(self, V, adjoint=True, qp=""):
+        """reverse differentiate! for cotangents V = dLoss/dw (N,) or (N, k): the same factorisation, lambda = M' V, and the gradients of the loss with respect to the data
+        named in qp, letters out of "LqgbHh" = Lxx, q, gx, b, hx, hvec: vectors as they are, matrices as the values ON THEIR STORED PATTERNS in the handle's non-zero
+        order.  A handle from SparseConicQP also takes "P", "A", "G": gradients on the stored patterns of the P, A, G it was given (grad_P = c (gLxx(i, j) + gLxx(j, i)),
+        grad_A = g_gx, grad_G = -g_hx).  Returns a dict: "adjoint" (unless adjoint=False) and one entry per letter, each with a trailing k axis only when V had one.
+        A CUDA tensor takes the device route and everything comes back as CUDA tensors"""
+        qp = qp or ""
+        if any(c not in self.GRADIENTS + "PAG" for c in qp):
+            raise ValueError("SparseKKT.vjp: qp is a string of letters out of 'LqgbHh' (and 'PAG' on a handle from SparseConicQP)")
+        if any(c in "PAG" for c in qp) and not hasattr(self, "_conic_qp"):
+            raise ValueError("SparseKKT.vjp: P, A, G are the data of a handle from SparseConicQP; this handle answers for 'LqgbHh'")
+        asked = [self._QP_LETTERS.get(c, c) for c in qp]
+        sizes = dict(zip(self.GRADIENTS, (self.nnz[0], self.nx, self.nnz[1], self.ne, self.nnz[2], self.nc)))
+        message = "SparseKKT.vjp: V must be (N,) or (N, k)"
+        device = self._is_device(V) and hasattr(V, "is_cuda")
+        if device:
+            import torch
+            if V.dim() not in (1, 2) or V.shape[0] != self.N:
+                raise ValueError(message)
+            squeeze, k = V.dim() == 1, (1 if V.dim() == 1 else int(V.shape[1]))
+            where = torch.device("cuda", self.device)
+            src = V.detach().reshape(self.N, k).t().contiguous()
+            adj = torch.empty((k, self.N), dtype=torch.float64, device=where) if adjoint else None
+            grads = {c: torch.empty((k, sizes[c]), dtype=torch.float64, device=where) for c in set(asked)}
+            ptrs = (C.c_void_p * 6)(*[C.c_void_p(grads[c].data_ptr()) if c in grads else None for c in self.GRADIENTS]) if grads else None
+            self._check(self._L.calipso_hip_sparse_kkt_differentiate_adjoint_device(self._h, k, self._device_pointer(src, "V", k * self.N),
+                                                                                    C.c_void_p(adj.data_ptr()) if adjoint else None, ptrs), "sparse_kkt_differentiate_adjoint_device")
+            shape = lambda t: t[0] if squeeze else t.t()
+        else:
+            flat, k, squeeze = pack_cotangent(V, (), self.N, message)
+            adj = np.zeros((k, self.N)) if adjoint else None
+            grads = {c: np.zeros((k, sizes[c])) for c in set(asked)}
+            ptrs = (C.POINTER(C.c_double) * 6)(*[_pd(grads[c]) if c in grads and grads[c].size else None for c in self.GRADIENTS]) if grads else None
+            self._check(self._L.calipso_hip_sparse_kkt_differentiate_adjoint(self._h, k, _pd(flat), _opt(adj), ptrs), "sparse_kkt_differentiate_adjoint")
+            shape = lambda a: a[0].copy() if squeeze else a.T.copy()
+        out = {}
+        if adjoint:
+            out["adjoint"] = shape(adj)
+        for c in qp:
+            g = grads[self._QP_LETTERS.get(c, c)]
+            if c == "P":
+                ij, ji, scale = self._conic_qp_positions(device)
+                g = scale * (g[:, ij] + g[:, ji])
+            elif c == "G":
+                g = -g
+            out[c] = shape(g)
+        return out
+
+    def _conic_qp_positions(self, device):
+        """for each stored entry (i, j) of the P given to SparseConicQP: where (i, j) and (j, i) lie in Lxx's non-zero order, and the objective scale"""
+        ij, ji, scale = self._conic_qp
+        if (ij < 0).any() or (ji < 0).any():
+            raise CalipsoHipError("SparseKKT.vjp: an entry of P's pattern is not in the pattern of c (P + P') (the sum cancelled it): its gradient is not on Lxx's pattern")
+        if device:
+            import torch
+            if not hasattr(self, "_conic_qp_device"):
+                self._conic_qp_device = tuple(torch.as_tensor(a, device=torch.device("cuda", self.device)) for a in (ij, ji))
+            return self._conic_qp_device + (scale,)
+        return ij, ji, scale
+
+    def _column_report(self, what):
+        out = np.zeros(4)
+        self._check(getattr(self._L, "calipso_hip_sparse_kkt_" + what)(self._h, _pd(out)), what)
+        return dict(columns=int(out[0]), rounds=int(out[1]), failed_columns=int(out[2]), final_norm=float(out[3]))
+
+    def differentiate_info(self):
+        """report of the last differentiate(): dict(columns, rounds (largest over the columns), failed_columns, final_norm); zeros when no round ran"""
+        return self._column_report("differentiate_info")
+
+    def vjp_info(self):
+        """report of the last vjp(), as differentiate_info()"""
+        return self._column_report("differentiate_adjoint_info")
+
+    def vjp_times(self):
+        """HIP-event times of the last vjp() in ms: dict(device = entry to last kernel, copy = the results to the caller, gradients = of device, the gradient kernel alone)"""
+        out = np.zeros(3)
+        self._check(self._L.calipso_hip_sparse_kkt_differentiate_adjoint_times(self._h, _pd(out)), "sparse_kkt_differentiate_adjoint_times")
+        return dict(device=float(out[0]), copy=float(out[1]), gradients=float(out[2]))
+
+    def differentiate_bytes(self):
+        """the device bytes solve_columns / differentiate / vjp hold for their columns: grown on demand, kept (a call that repeats its shapes allocates nothing)"""
+        out = np.zeros(1, dtype=np.int64)
+        self._check(self._L.calipso_hip_sparse_kkt_differentiate_bytes(self._h, _pi(out)), "sparse_kkt_differentiate_bytes")
+        return int(out[0])
+
     def _vector_length(self, name):
+        if name == "differentiate_slacks":      # (not a vector of the reference's solver: the s, then the t that differentiate! forms the cone blocks at)
+            return 2 * self.nc
         return getattr(self, self.VECTORS[name]) if name in self.VECTORS else 0
 
     def get(self, name):
@@ -1122,7 +1246,8 @@ class SparseKKT(_Handle):
 
 def SparseConicQP(P, q, A, b, G, h, n_nonnegative=None, second_order_dims=(), objective_scale=0.5, **kw):
     """min c x'Px + q'x  s.t.  Ax - b = 0,  h - Gx in K  (c = objective_scale) as a SparseKKT ready for initialize / solve: Lxx = c (P + P'), gx = A, hx = -G as CSC,
-    values and q, b, h resident.  P, A, G: scipy sparse matrices (or dense arrays); the cones as SparseKKT takes them; **kw goes to SparseKKT"""
+    values and q, b, h resident.  P, A, G: scipy sparse matrices (or dense arrays); the cones as SparseKKT takes them; **kw goes to SparseKKT.  The handle's vjp then
+    also answers for "P", "A", "G": gradients on the stored patterns of P, A, G as given here (CSC order)"""
     import scipy.sparse as sp
     P, A, G = (sp.csc_matrix(M) for M in (P, A, G))
     Lxx, gx, hx = sp.csc_matrix(objective_scale * (P + P.T)), A, sp.csc_matrix(-G)
@@ -1131,6 +1256,16 @@ def SparseConicQP(P, q, A, b, G, h, n_nonnegative=None, second_order_dims=(), ob
     s = SparseKKT(Lxx, gx, hx, n_nonnegative=n_nonnegative, second_order_dims=second_order_dims, **kw)
     s.set_values(Lxx, gx, hx)
     s.attach_qp(q, b, h)
+    # for SparseKKT.vjp(qp="P..."): where the stored entries (i, j) of P and their mirrors (j, i) lie in Lxx's non-zero order (-1: not in its pattern)
+    nx = s.nx
+    keys = np.repeat(np.arange(nx, dtype=np.int64), np.diff(Lxx.indptr)) * nx + Lxx.indices      # column-major keys of a sorted CSC pattern: ascending
+    def position(rows, cols):
+        want = cols.astype(np.int64) * nx + rows
+        at = np.minimum(np.searchsorted(keys, want), max(keys.size - 1, 0))
+        return np.where(keys[at] == want, at, -1) if keys.size else np.full(want.shape, -1, dtype=np.int64)
+    P_csc = sp.csc_matrix(P)
+    rows, cols = P_csc.indices, np.repeat(np.arange(nx), np.diff(P_csc.indptr))
+    s._conic_qp = (position(rows, cols), position(cols, rows), float(objective_scale))
     return s
 
 

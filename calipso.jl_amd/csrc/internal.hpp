@@ -439,6 +439,9 @@ void launch_refine_rows_multi(calipso_hip_solver* s, const double* X, const doub
 void launch_refine_x_multi(calipso_hip_solver* s, const double* X, const double* R, const double* hx, long long ldh, int p, double* E, const double* part, double* norms);
 void launch_accumulate_masked(calipso_hip_solver* s, const int* active, const double* C, int p, double* X, double* Xsave);      // X(:, c) += C(:, c) where active[c] (2: Xsave(:, c) = X(:, c) first)
 void launch_restore_masked(calipso_hip_solver* s, const int* restore, const double* Xsave, int p, double* X);                   // X(:, c) = Xsave(:, c) where restore[c]
+// the same two on a stream for columns of N rows: what the solver forms call, and the sparse handle's correction rounds (sparse_differentiate.hip)
+void launch_accumulate_masked(hipStream_t stream, int N, const int* active, const double* C, int p, double* X, double* Xsave);
+void launch_restore_masked(hipStream_t stream, int N, const int* restore, const double* Xsave, int p, double* X);
 void launch_scale_into(calipso_hip_solver* s, const double* x, double* y, size_t n, double a);                 // y = a x
 // columns.hip: p columns through the current factors (the caller has evaluated the parameter Jacobians it needs, factored, and formed jacobian_parameters): solution_sensitivity =
 // -H^-1 jacobian_parameters (+ the correction rounds where the option asks); p cotangent columns from the host -> *lam (N x p), *grad_theta (np x p): device, the reverse workspace

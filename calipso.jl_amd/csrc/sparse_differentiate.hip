@@ -1,0 +1,528 @@
+// sparse_differentiate.hip — differentiate! (src/solver/differentiate.jl:1-61) in both directions on the sparse handle of sparse_kkt.hip: the entries behind
+// calipso_hip_sparse_kkt_solve_columns / _differentiate / _differentiate_adjoint (include/calipso_hip.h).  Nothing here is dense: besides the N x k columns themselves
+// the memory is that of the handle, and the data gradients live on the stored patterns.
+//
+//   the map, k columns at once     step = M residual of search_direction_symmetric! (search_direction.jl:25-104) and its transpose (sparse_differentiate.hpp): a "pre"
+//                                  launch, ONE calipso_hip_sparse_solve_device for all k columns, a "post" launch.  blockIdx.y carries the column: no loop over columns
+//                                  anywhere.  One thread per (row, column); a second-order cone of any dimension one thread per (cone, column), as in sparse_kkt.hip.
+//   H X, H' X, k columns           the unreduced matrix applied from the same data, one thread per (row, column), fused with E = R - H X and the per-column infinity
+//                                  norms (k doubles, read back once per round).  Transposed: Lxx through its column view, the s and t couplings of the local rows swapped.
+//   correction rounds              iterative_refinement.jl:14-44 on all columns with the decisions of sensitivity_columns.hpp and the masked accumulate / restore of
+//                                  vectors.hip (the ones columns.hip launches).
+//   data gradients                 one launch, one thread per (stored non-zero or vector entry, column), the entry index fastest.
+// Gathers only: no floating-point atomics (the norm: atomicMax on the bit patterns of non-negative doubles, which is order-independent); a call repeats bit for bit.
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "sparse_kkt_handle.hpp"
+#include "sparse_differentiate.hpp"
+
+using calipso::i64;
+using namespace calipso::sparse_kkt;
+using namespace calipso::sparse_differentiate;
+typedef calipso_hip_sparse_kkt KH;
+
+struct calipso::sparse_kkt::DiffState {
+    double* ws = nullptr; size_t doubles = 0;     // the workspace of a k-column pass (sparse_differentiate.hpp: Layout): grown on demand, kept
+    int* masks = nullptr; size_t ints = 0;
+    double* wd = nullptr;                         // N: the resident point with the kept slacks in its s and t rows (what the kernels read the cone blocks from)
+    double* gbuf = nullptr; size_t gdoubles = 0;  // the gradients of a host call before they are copied out
+    calipso::SensitivityColumns cols;
+    std::vector<double> norms;
+    double info_forward[4] = {0, 0, 0, 0}, info_reverse[4] = {0, 0, 0, 0}, times[3] = {0, 0, 0};
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};      // a reverse call: entry, last kernel, around the gradient kernel, after the copies
+    hipEvent_t ev_pass[4] = {nullptr, nullptr, nullptr, nullptr};          // around the first pre + solve + post of a call, around its correction rounds
+    bool rounds_ran = false;
+};
+
+namespace {
+
+typedef calipso::sparse_kkt::DiffState DS;
+
+__device__ __forceinline__ double rabs(double x) { return x != x ? __builtin_huge_val() : fabs(x); }      // a NaN reports +inf, as in sparse_kkt.hip
+
+// ---- the condensed solve's outer halves: G (n x k) from V (N x k) before the LDL^T solve, OUT (N x k) from its solution Hs (n x k) and V after it -----------------
+// items: [0, nx) variables, [nx, nx + ne) equality rows, [.., n) cone rows, [n, n + nsoc) second-order cones; blockIdx.y: the column
+template <bool TRANSPOSED>
+__global__ __launch_bounds__(KT) void k_diff_pre(const KktDev d, double ep, double ed, const double* __restrict__ V, double* __restrict__ G, double* __restrict__ OUT) {
+    long long k = (long long)blockIdx.x * KT + threadIdx.x;
+    const size_t col = blockIdx.y;
+    const double* v = V + col * (size_t)d.N;
+    double* g = G + col * (size_t)d.n;
+    if (k < d.nx) { g[k] = v[k]; return; }
+    k -= d.nx;
+    const MapScalars c{ep, ed, d.ne ? d.rho[0] : 0.0};
+    if (k < d.ne) { g[d.nx + k] = TRANSPOSED ? equality_transposed_pre(c, v[d.o_r + k], v[d.o_y + k]) : equality_forward_pre(c, v[d.o_r + k], v[d.o_y + k]); return; }
+    k -= d.ne;
+    const int oc = d.nx + d.ne;
+    if (k < d.nc) {
+        const int kind = d.row_cone[k];
+        if (kind == -1) {
+            const double sl = d.w[d.o_s + k], t = d.w[d.o_t + k];
+            g[oc + k] = TRANSPOSED ? nonnegative_transposed_pre(c, sl, t, v[d.o_s + k], v[d.o_z + k], v[d.o_t + k]) : nonnegative_forward_pre(c, sl, t, v[d.o_s + k], v[d.o_z + k], v[d.o_t + k]);
+        } else if (kind == -2) g[oc + k] = v[d.o_z + k];
+        return;
+    }
+    k -= d.nc;
+    if (k >= d.nsoc) return;
+    const int st = d.soc_start[k], dm = d.soc_dim[k];
+    const double* sl = d.w + d.o_s + st; const double* t = d.w + d.o_t + st;
+    if (TRANSPOSED) {       // the temporaries in the cone's entries of the output column, which the post launch writes
+        double* out = OUT + col * (size_t)d.N;
+        soc_transposed_pre(c, dm, sl, t, v + d.o_s + st, v + d.o_z + st, v + d.o_t + st, g + oc + st, out + d.o_t + st, out + d.o_s + st);
+    } else soc_forward_pre(c, dm, sl, t, v + d.o_s + st, v + d.o_z + st, v + d.o_t + st, g + oc + st);
+}
+
+template <bool TRANSPOSED>
+__global__ __launch_bounds__(KT) void k_diff_post(const KktDev d, double ep, double ed, const double* __restrict__ Hs, const double* __restrict__ V, double* __restrict__ OUT) {
+    long long k = (long long)blockIdx.x * KT + threadIdx.x;
+    const size_t col = blockIdx.y;
+    const double* v = V + col * (size_t)d.N;
+    const double* h = Hs + col * (size_t)d.n;
+    double* out = OUT + col * (size_t)d.N;
+    if (k < d.nx) { out[k] = h[k]; return; }
+    k -= d.nx;
+    const MapScalars c{ep, ed, d.ne ? d.rho[0] : 0.0};
+    if (k < d.ne) {
+        const double he = h[d.nx + k];
+        out[d.o_y + k] = he;
+        out[d.o_r + k] = TRANSPOSED ? equality_transposed_post(c, he, v[d.o_r + k]) : equality_forward_post(c, he, v[d.o_r + k]);
+        return;
+    }
+    k -= d.ne;
+    const int oc = d.nx + d.ne;
+    if (k < d.nc) {
+        const int kind = d.row_cone[k];
+        const double hc = h[oc + k];
+        out[d.o_z + k] = hc;
+        if (kind == -1) {
+            const double sl = d.w[d.o_s + k], t = d.w[d.o_t + k];
+            if (TRANSPOSED) nonnegative_transposed_post(c, sl, t, hc, v[d.o_s + k], v[d.o_t + k], &out[d.o_s + k], &out[d.o_t + k]);
+            else nonnegative_forward_post(c, sl, t, hc, v[d.o_s + k], v[d.o_t + k], &out[d.o_s + k], &out[d.o_t + k]);
+        } else if (kind == -2) { out[d.o_s + k] = 0.0; out[d.o_t + k] = 0.0; }
+        return;
+    }
+    k -= d.nc;
+    if (k >= d.nsoc) return;
+    const int st = d.soc_start[k], dm = d.soc_dim[k];
+    const double* sl = d.w + d.o_s + st; const double* t = d.w + d.o_t + st;
+    if (TRANSPOSED) soc_transposed_post(c, dm, sl, t, h + oc + st, v + d.o_s + st, v + d.o_t + st, out + d.o_s + st, out + d.o_t + st);
+    else soc_forward_post(c, dm, sl, t, h + oc + st, v + d.o_s + st, v + d.o_t + st, out + d.o_s + st, out + d.o_t + st);
+}
+
+// ---- H X (TRANSPOSED: H' X) for k columns, one thread per (row of the point's layout, column): E = R - H X and the columns' infinity norms, or (R NULL) E = H X -----
+// row i of arrow(a) v over the cone's dm entries
+__device__ __forceinline__ double arrow_row(const double* __restrict__ a, double a0, const double* __restrict__ v, int dm, int i) {
+    if (i == 0) { double r = 0.0; for (int b = 0; b < dm; ++b) r += (b == 0 ? a0 : a[b]) * v[b]; return r; }
+    return a[i] * v[0] + a0 * v[i];
+}
+// (C v)_c for the cone block C = arrow(a) - shift I of cone row c (a: the s or the t rows of the point)
+__device__ __forceinline__ double cone_block_row(const KktDev& d, const double* __restrict__ a, double shift, const double* __restrict__ v, int c) {
+    const int kind = d.row_cone[c];
+    if (kind == -1) return (a[c] - shift) * v[c];
+    if (kind < 0) return 0.0;
+    const int st = d.soc_start[kind];
+    return arrow_row(a + st, a[st] - shift, v + st, d.soc_dim[kind], c - st);
+}
+
+template <bool TRANSPOSED>
+__global__ __launch_bounds__(KT) void k_diff_mul(const KktDev d, double ep, double ed, const double* __restrict__ X, const double* __restrict__ R, double* __restrict__ E,
+                                                 unsigned long long* __restrict__ norms) {
+    const long long j = (long long)blockIdx.x * KT + threadIdx.x;
+    const size_t col = blockIdx.y;
+    const double* v = X + col * (size_t)d.N;
+    double mag = 0.0;
+    if (j < d.N) {
+        double a = 0.0;
+        const int i = (int)j;
+        if (i < d.o_r) {                                                        // Lxx v_x (Lxx' v_x) + gx' v_y + hx' v_z + ep v_x
+            if (TRANSPOSED) for (int p = d.Lc.ptr[i]; p < d.Lc.ptr[i + 1]; ++p) a += d.Lxx[p] * v[d.Lc.idx[p]];
+            else for (int p = d.Lr.ptr[i]; p < d.Lr.ptr[i + 1]; ++p) a += d.Lxx[d.Lr.src[p]] * v[d.Lr.idx[p]];
+            for (int p = d.gc.ptr[i]; p < d.gc.ptr[i + 1]; ++p) a += d.gx[p] * v[d.o_y + d.gc.idx[p]];
+            for (int p = d.hc.ptr[i]; p < d.hc.ptr[i + 1]; ++p) a += d.hx[p] * v[d.o_z + d.hc.idx[p]];
+            a += ep * v[i];
+        } else if (i < d.o_s) { const int e = i - d.o_r; a = (d.rho[0] + ep) * v[i] - v[d.o_y + e]; }
+        else if (i < d.o_y) {                                                   // the s rows: ep v_s - v_z - v_t; transposed: the column of H, arrow(t) v_t in place of -v_t
+            const int c = i - d.o_s;
+            a = ep * v[i] - v[d.o_z + c];
+            a = TRANSPOSED ? a + cone_block_row(d, d.w + d.o_t, 0.0, v + d.o_t, c) : a - v[d.o_t + c];
+        } else if (i < d.o_z) {
+            const int e = i - d.o_y;
+            for (int p = d.gr.ptr[e]; p < d.gr.ptr[e + 1]; ++p) a += d.gx[d.gr.src[p]] * v[d.gr.idx[p]];
+            a += -v[d.o_r + e] + (0.0 - ed) * v[i];
+        } else if (i < d.o_t) {
+            const int c = i - d.o_z;
+            for (int p = d.hr.ptr[c]; p < d.hr.ptr[c + 1]; ++p) a += d.hx[d.hr.src[p]] * v[d.hr.idx[p]];
+            a += -v[d.o_s + c] + (0.0 - ed) * v[i];
+        } else {                                                                // the t rows: arrow(t) v_s + (arrow(s) - ed I) v_t; transposed: -v_s in place of arrow(t) v_s
+            const int c = i - d.o_t;
+            a = cone_block_row(d, d.w + d.o_s, ed, v + d.o_t, c);
+            a = TRANSPOSED ? a - v[d.o_s + c] : a + cone_block_row(d, d.w + d.o_t, 0.0, v + d.o_s, c);
+        }
+        const size_t at = col * (size_t)d.N + (size_t)i;
+        if (R) { const double e = R[at] - a; E[at] = e; mag = rabs(e); }
+        else E[at] = a;
+    }
+    if (!norms) return;                                                         // (uniform)
+    __shared__ double part[KT / 64];
+    for (int o = 32; o > 0; o >>= 1) mag = fmax(mag, __shfl_xor(mag, o));
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = mag;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double m = part[0];
+        for (int q = 1; q < KT / 64; ++q) m = fmax(m, part[q]);
+        if (m > 0.0) atomicMax(&norms[col], (unsigned long long)__double_as_longlong(m));      // non-negative doubles order as their bit patterns
+    }
+}
+
+// ---- the data gradients on the stored patterns: one thread per (entry, column), the entry fastest --------------------------------------------------------------
+struct GradOut { double* p[6]; };                                               // Lxx, q, gx, b, hx, hvec; NULL: not asked for
+// the column of non-zero p of a CSC pattern: the last c with ptr[c] <= p
+__device__ __forceinline__ int column_of(const int* __restrict__ ptr, int ncols, int p) {
+    int lo = 0, hi = ncols;                                                     // ptr[lo] <= p < ptr[hi]
+    while (hi - lo > 1) { const int mid = lo + ((hi - lo) >> 1); if (ptr[mid] <= p) lo = mid; else hi = mid; }
+    return lo;
+}
+__global__ __launch_bounds__(KT) void k_diff_gradients(const KktDev d, const double* __restrict__ w, const double* __restrict__ LAM, const GradOut out) {
+    long long e = (long long)blockIdx.x * KT + threadIdx.x;
+    const size_t col = blockIdx.y;
+    const double* lam = LAM + col * (size_t)d.N;
+    const double *x = w, *y = w + d.o_y, *z = w + d.o_z, *lx = lam, *ly = lam + d.o_y, *lz = lam + d.o_z;
+    if (e < d.nnzL) { if (out.p[0]) { const int p = (int)e; out.p[0][col * (size_t)d.nnzL + p] = -lx[d.Lc.idx[p]] * x[column_of(d.Lc.ptr, d.nx, p)]; } return; }
+    e -= d.nnzL;
+    if (e < d.nx) { if (out.p[1]) out.p[1][col * (size_t)d.nx + e] = -lx[e]; return; }
+    e -= d.nx;
+    if (e < d.nnzg) {
+        if (out.p[2]) { const int p = (int)e, r = d.gc.idx[p], c = column_of(d.gc.ptr, d.nx, p); out.p[2][col * (size_t)d.nnzg + p] = -(ly[r] * x[c] + y[r] * lx[c]); }
+        return;
+    }
+    e -= d.nnzg;
+    if (e < d.ne) { if (out.p[3]) out.p[3][col * (size_t)d.ne + e] = ly[e]; return; }
+    e -= d.ne;
+    if (e < d.nnzh) {
+        if (out.p[4]) { const int p = (int)e, r = d.hc.idx[p], c = column_of(d.hc.ptr, d.nx, p); out.p[4][col * (size_t)d.nnzh + p] = -(lz[r] * x[c] + z[r] * lx[c]); }
+        return;
+    }
+    e -= d.nnzh;
+    if (e < d.nc && out.p[5]) out.p[5][col * (size_t)d.nc + e] = -lz[e];
+}
+
+__global__ __launch_bounds__(KT) void k_diff_scale(size_t count, const double* __restrict__ x, double* __restrict__ y, double a) {
+    const size_t i = (size_t)blockIdx.x * KT + threadIdx.x;
+    if (i < count) y[i] = a * x[i];
+}
+// the resident point's s, t rows of `wd` from the kept slacks (s, then t)
+__global__ __launch_bounds__(KT) void k_diff_place_slacks(const KktDev d, const double* __restrict__ kept, double* __restrict__ wd) {
+    const long long k = (long long)blockIdx.x * KT + threadIdx.x;
+    if (k < d.nc) wd[d.o_s + k] = kept[k];
+    else if (k < 2ll * d.nc) wd[d.o_t + (k - d.nc)] = kept[k];
+}
+
+// ---- host -------------------------------------------------------------------------------------------------------------------------------------------------------
+#define KK(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return kkt_fail(s, CALIPSO_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); } while (0)
+#define REFUSE(text) do { const std::string t__ = (text); if (!t__.empty()) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, t__); } while (0)
+#define DEVPTR(p) do { if (device) { const int rc__ = kkt_device_pointer(s, (const void*)(p), entry, #p); if (rc__ < 0) return rc__; } } while (0)
+
+unsigned blocks_of(long long items) { return (unsigned)std::max<long long>((items + KT - 1) / KT, 1); }
+
+int ensure_state(KH* s) {
+    if (s->diff) return CALIPSO_OK;
+    DS* t = new DS();
+    s->diff = t;                                             // (released with the handle, whatever happens below)
+    for (hipEvent_t& e : t->ev) KK(hipEventCreate(&e));
+    for (hipEvent_t& e : t->ev_pass) KK(hipEventCreate(&e));
+    return kkt_reserve(s, &t->wd, (size_t)s->d.N);
+}
+// grown on demand, never shrunk, kept: a call that repeats its shapes allocates nothing
+template <typename T>
+int grow(KH* s, T** buf, size_t* have, size_t want) {
+    if (want <= *have) return CALIPSO_OK;
+    KK(hipStreamSynchronize(s->st));
+    if (*buf) { (void)hipFree(*buf); *buf = nullptr; *have = 0; }
+    KK(hipMalloc((void**)buf, sizeof(T) * want));
+    KK(hipMemsetAsync(*buf, 0, sizeof(T) * want, s->st));
+    *have = want;
+    return CALIPSO_OK;
+}
+int reserve_pass(KH* s, const Layout& L, size_t k) {
+    DS* t = s->diff;
+    int rc = grow(s, &t->ws, &t->doubles, std::max<size_t>(L.doubles, 1));
+    if (rc >= 0 && L.ints) rc = grow(s, &t->masks, &t->ints, L.ints);
+    if (t->norms.size() < k) t->norms.assign(k, 0.0);
+    return rc;
+}
+
+// what the kernels read: the handle's data with the point whose s, t rows are the differentiate slacks
+KktDev slacks_view(KH* s) {
+    KktDev d = s->d;
+    if (s->slacks_kept && d.nc) {
+        hipLaunchKernelGGL(k_diff_place_slacks, dim3(blocks_of(2ll * d.nc)), dim3(KT), 0, s->st, s->d, s->dslack, s->diff->wd);
+        d.w = s->diff->wd;
+    }
+    return d;
+}
+
+// OUT = M V (transposed: M' V) for k columns on the device: pre, ONE k-column LDL^T solve, post
+int map_columns(KH* s, const KktDev& d, bool transposed, int k, const double* V, double* rsym, double* dsym, double* OUT, bool timed = false) {
+    const dim3 grid(blocks_of((long long)d.n + d.nsoc), (unsigned)k), block(KT);
+    if (timed) { KK(hipEventRecord(s->diff->ev_pass[0], s->st)); s->diff->rounds_ran = false; }
+    if (transposed) hipLaunchKernelGGL(k_diff_pre<true>, grid, block, 0, s->st, d, s->sc.ep, s->sc.ed, V, rsym, OUT);
+    else hipLaunchKernelGGL(k_diff_pre<false>, grid, block, 0, s->st, d, s->sc.ep, s->sc.ed, V, rsym, OUT);
+    const int rc = calipso_hip_sparse_solve_device(s->sp, k, rsym, dsym);
+    if (rc < 0) return kkt_sparse_failed(s, rc, "solve");
+    if (transposed) hipLaunchKernelGGL(k_diff_post<true>, grid, block, 0, s->st, d, s->sc.ep, s->sc.ed, dsym, V, OUT);
+    else hipLaunchKernelGGL(k_diff_post<false>, grid, block, 0, s->st, d, s->sc.ep, s->sc.ed, dsym, V, OUT);
+    if (timed) KK(hipEventRecord(s->diff->ev_pass[1], s->st));
+    return CALIPSO_OK;
+}
+// after the entry's last synchronise: the pass and its rounds into the handle's timing, slots 6 and 7 (calipso_hip_sparse_kkt_timing)
+int pass_times(KH* s) {
+    DS* t = s->diff;
+    float ms = 0.f;
+    KK(hipEventElapsedTime(&ms, t->ev_pass[0], t->ev_pass[1])); s->ms[6] = ms;
+    s->ms[7] = 0.0;
+    if (t->rounds_ran) { KK(hipEventElapsedTime(&ms, t->ev_pass[2], t->ev_pass[3])); s->ms[7] = ms; }
+    return CALIPSO_OK;
+}
+void enqueue_mul(KH* s, const KktDev& d, bool transposed, int k, const double* X, const double* R, double* E, double* norms) {
+    const dim3 grid(blocks_of(d.N), (unsigned)k), block(KT);
+    unsigned long long* nm = reinterpret_cast<unsigned long long*>(norms);
+    if (transposed) hipLaunchKernelGGL(k_diff_mul<true>, grid, block, 0, s->st, d, s->sc.ep, s->sc.ed, X, R, E, nm);
+    else hipLaunchKernelGGL(k_diff_mul<false>, grid, block, 0, s->st, d, s->sc.ep, s->sc.ed, X, R, E, nm);
+}
+
+// iterative_refinement.jl:14-44 over the k columns of X at once (columns.hip: refine_columns, on this handle's kernels): E = R - H X (H' X), the columns' norms read
+// back once per round, the correction through the same factors, X(:, j) += correction(:, j) for the columns sensitivity_columns.hpp keeps active
+int refine_columns(KH* s, const KktDev& d, const Layout& L, const double* R, bool transposed, int k, double info[4]) {
+    DS* t = s->diff;
+    double *w = t->ws, *X = w + L.X.off, *E = w + L.E.off, *C = w + L.C.off, *Xsave = w + L.Xsave.off, *norms = w + L.norms.off;
+    int *active = t->masks, *restore = t->masks + k;
+    calipso::SensitivityColumns& cols = t->cols;
+    cols.begin(k);
+    KK(hipEventRecord(t->ev_pass[2], s->st));
+    for (;;) {
+        KK(hipMemsetAsync(norms, 0, sizeof(double) * (size_t)k, s->st));
+        enqueue_mul(s, d, transposed, k, X, R, E, norms);
+        KK(hipMemcpyAsync(t->norms.data(), norms, sizeof(double) * (size_t)k, hipMemcpyDeviceToHost, s->st));
+        KK(hipStreamSynchronize(s->st));
+        KK(hipGetLastError());
+        cols.judge(s->opt, t->norms.data());
+        if (cols.n_restore) {
+            KK(hipMemcpyAsync(restore, cols.restore.data(), sizeof(int) * (size_t)k, hipMemcpyHostToDevice, s->st));
+            calipso::launch_restore_masked(s->st, d.N, restore, Xsave, k, X);
+            KK(hipStreamSynchronize(s->st));              // (cols.restore is rewritten by the next judge)
+        }
+        if (cols.finished()) break;
+        KK(hipMemcpyAsync(active, cols.active.data(), sizeof(int) * (size_t)k, hipMemcpyHostToDevice, s->st));
+        const int rc = map_columns(s, d, transposed, k, E, w + L.rsym.off, w + L.dsym.off, C);
+        if (rc < 0) return rc;
+        calipso::launch_accumulate_masked(s->st, d.N, active, C, k, X, Xsave);
+    }
+    cols.report(info);
+    KK(hipEventRecord(t->ev_pass[3], s->st));
+    t->rounds_ran = true;
+    return CALIPSO_OK;
+}
+// not with second-order cones, where the reference's answer IS the unrefined solve (quirk B-3, columns.hip: rounds_wanted), and not with iterative_refinement = 0
+bool rounds_wanted(const KH* s) { return s->differentiate_refinement && s->opt.iterative_refinement && s->d.nsoc == 0; }
+
+// the columns of a call into the workspace: the caller's (host or device) -> L.V
+int take_columns(KH* s, const Layout& L, const double* B, bool device) {
+    KK(hipMemcpyAsync(s->diff->ws + L.V.off, B, sizeof(double) * L.V.len, device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->st));
+    return CALIPSO_OK;
+}
+int give_columns(KH* s, const double* from, size_t count, double* to, bool device) {
+    if (to && count) KK(hipMemcpyAsync(to, from, sizeof(double) * count, device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s->st));
+    return CALIPSO_OK;
+}
+
+int factorize_held(KH* s, const KktDev& d) {
+    int64_t in[3] = {0, 0, 0};
+    const int rc = kkt_assemble_factorize(s, d, s->sc.ep, s->sc.ed, in);
+    return rc < 0 ? rc : CALIPSO_OK;
+}
+// K and its factor were formed at the differentiate slacks: where those are not the resident point's, the single-column entries must assemble again
+void leave_factorization(KH* s) { if (s->slacks_kept) { s->assembled = false; s->factored = false; } }
+
+int solve_columns(KH* s, const char* entry, int64_t k, int32_t transposed, const double* B, double* X, bool device) {
+    if (!s) return CALIPSO_ERR_ARGUMENT;
+    REFUSE(check_columns(entry, k));
+    REFUSE(check_array(entry, "B", B)); REFUSE(check_array(entry, "X", X));
+    KK(hipSetDevice(s->device));
+    DEVPTR(B); DEVPTR(X);
+    if (!s->factored) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": factorize first (the columns go through the current factorisation)");
+    int rc = ensure_state(s);
+    if (rc < 0) return rc;
+    const Layout L = layout((size_t)s->d.N, (size_t)s->d.n, (size_t)k, false);
+    if ((rc = reserve_pass(s, L, (size_t)k)) < 0 || (rc = take_columns(s, L, B, device)) < 0) return rc;
+    double* w = s->diff->ws;
+    if ((rc = map_columns(s, s->d, transposed != 0, (int)k, w + L.V.off, w + L.rsym.off, w + L.dsym.off, w + L.X.off, true)) < 0) return rc;
+    if ((rc = give_columns(s, w + L.X.off, L.X.len, X, device)) < 0) return rc;
+    KK(hipStreamSynchronize(s->st));
+    KK(hipGetLastError());
+    return pass_times(s);
+}
+
+int differentiate(KH* s, const char* entry, int64_t k, const double* jacobian_parameters, double* sensitivity, bool device) {
+    if (!s) return CALIPSO_ERR_ARGUMENT;
+    REFUSE(check_columns(entry, k));
+    REFUSE(check_array(entry, "jacobian_parameters", jacobian_parameters)); REFUSE(check_array(entry, "sensitivity", sensitivity));
+    KK(hipSetDevice(s->device));
+    DEVPTR(jacobian_parameters); DEVPTR(sensitivity);
+    int rc = kkt_values_missing(s, entry);
+    if (rc < 0 || (rc = ensure_state(s)) < 0) return rc;
+    DS* t = s->diff;
+    const bool rounds = rounds_wanted(s);
+    const Layout L = layout((size_t)s->d.N, (size_t)s->d.n, (size_t)k, rounds);
+    if ((rc = reserve_pass(s, L, (size_t)k)) < 0 || (rc = take_columns(s, L, jacobian_parameters, device)) < 0) return rc;
+    const double info0[4] = {(double)k, 0, 0, 0};
+    std::copy(info0, info0 + 4, t->info_forward);
+    const KktDev d = slacks_view(s);
+    if ((rc = factorize_held(s, d)) < 0) return rc;                                           // differentiate.jl:21-27
+    double *w = t->ws, *X = w + L.X.off;
+    rc = map_columns(s, d, false, (int)k, w + L.V.off, w + L.rsym.off, w + L.dsym.off, X, true);     // :29-53 for all columns
+    if (rc >= 0 && rounds) rc = refine_columns(s, d, L, w + L.V.off, false, (int)k, t->info_forward);
+    leave_factorization(s);
+    if (rc < 0) return rc;
+    hipLaunchKernelGGL(k_diff_scale, dim3(blocks_of((long long)L.X.len)), dim3(KT), 0, s->st, L.X.len, X, X, -1.0);      // :54-56 sensitivity = -step
+    if ((rc = give_columns(s, X, L.X.len, sensitivity, device)) < 0) return rc;
+    KK(hipStreamSynchronize(s->st));
+    KK(hipGetLastError());
+    return pass_times(s);
+}
+
+int differentiate_adjoint(KH* s, const char* entry, int64_t k, const double* cotangent, double* adjoint, double* const* grad, bool device) {
+    if (!s) return CALIPSO_ERR_ARGUMENT;
+    REFUSE(check_columns(entry, k));
+    REFUSE(check_array(entry, "cotangent", cotangent));
+    KK(hipSetDevice(s->device));
+    DEVPTR(cotangent); DEVPTR(adjoint);
+    static const char* const names[6] = {"grad[0] (Lxx)", "grad[1] (q)", "grad[2] (gx)", "grad[3] (b)", "grad[4] (hx)", "grad[5] (hvec)"};
+    bool wanted = false;
+    for (int i = 0; grad && i < 6; ++i) if (grad[i]) { wanted = true; if (device) { const int rc = kkt_device_pointer(s, grad[i], entry, names[i]); if (rc < 0) return rc; } }
+    int rc = kkt_values_missing(s, entry);
+    if (rc < 0 || (rc = ensure_state(s)) < 0) return rc;
+    DS* t = s->diff;
+    REFUSE(check_gradients(entry, wanted, s->qp_attached, s->have[3]));
+    const KktDev& h = s->d;
+    const bool rounds = rounds_wanted(s);
+    const Layout L = layout((size_t)h.N, (size_t)h.n, (size_t)k, rounds);
+    if ((rc = reserve_pass(s, L, (size_t)k)) < 0) return rc;
+    const size_t sizes[6] = {(size_t)h.nnzL, (size_t)h.nx, (size_t)h.nnzg, (size_t)h.ne, (size_t)h.nnzh, (size_t)h.nc};
+    GradOut out{};
+    if (wanted && !device) {                                                                  // a host call's gradients are staged on the device
+        size_t total = 0;
+        for (int i = 0; i < 6; ++i) if (grad[i]) total += sizes[i] * (size_t)k;
+        if ((rc = grow(s, &t->gbuf, &t->gdoubles, std::max<size_t>(total, 1))) < 0) return rc;
+        size_t at = 0;
+        for (int i = 0; i < 6; ++i) if (grad[i]) { out.p[i] = t->gbuf + at; at += sizes[i] * (size_t)k; }
+    } else if (wanted) for (int i = 0; i < 6; ++i) out.p[i] = grad[i];
+    const double info0[4] = {(double)k, 0, 0, 0};
+    std::copy(info0, info0 + 4, t->info_reverse);
+    t->times[0] = t->times[1] = t->times[2] = 0.0;
+    KK(hipEventRecord(t->ev[0], s->st));
+    if ((rc = take_columns(s, L, cotangent, device)) < 0) return rc;
+    const KktDev d = slacks_view(s);
+    if ((rc = factorize_held(s, d)) < 0) return rc;
+    double *w = t->ws, *V = w + L.V.off, *X = w + L.X.off;
+    rc = map_columns(s, d, true, (int)k, V, w + L.rsym.off, w + L.dsym.off, X, true);          // differentiate.jl:29-58 transposed, all columns at once
+    if (rc >= 0 && rounds) rc = refine_columns(s, d, L, V, true, (int)k, t->info_reverse);
+    leave_factorization(s);
+    if (rc < 0) return rc;
+    if (wanted) {
+        const long long items = (long long)h.nnzL + h.nx + h.nnzg + h.ne + h.nnzh + h.nc;
+        KK(hipEventRecord(t->ev[2], s->st));
+        hipLaunchKernelGGL(k_diff_gradients, dim3(blocks_of(items), (unsigned)k), dim3(KT), 0, s->st, h, s->w, X, out);      // x, y, z: the resident point's
+        KK(hipEventRecord(t->ev[3], s->st));
+    }
+    KK(hipEventRecord(t->ev[1], s->st));
+    if ((rc = give_columns(s, X, L.X.len, adjoint, device)) < 0) return rc;
+    if (wanted && !device) for (int i = 0; i < 6; ++i) if (grad[i] && (rc = give_columns(s, out.p[i], sizes[i] * (size_t)k, grad[i], false)) < 0) return rc;
+    KK(hipEventRecord(t->ev[4], s->st));
+    KK(hipStreamSynchronize(s->st));
+    KK(hipGetLastError());
+    float ms = 0.f;
+    KK(hipEventElapsedTime(&ms, t->ev[0], t->ev[1])); t->times[0] = ms;
+    KK(hipEventElapsedTime(&ms, t->ev[1], t->ev[4])); t->times[1] = ms;
+    if (wanted) { KK(hipEventElapsedTime(&ms, t->ev[2], t->ev[3])); t->times[2] = ms; }
+    return pass_times(s);
+}
+
+}  // namespace
+
+namespace calipso {
+namespace sparse_kkt {
+
+void diff_state_release(KH* s) {
+    DS* t = s->diff;
+    if (!t) return;
+    if (t->ws) (void)hipFree(t->ws);
+    if (t->masks) (void)hipFree(t->masks);
+    if (t->gbuf) (void)hipFree(t->gbuf);
+    for (hipEvent_t e : t->ev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : t->ev_pass) if (e) (void)hipEventDestroy(e);
+    delete t;
+    s->diff = nullptr;
+}
+
+int diff_set_option(KH* s, const char* name, double value) {
+    if (std::strcmp(name, "differentiate_refinement")) return 0;
+    if (!refinement_option(value)) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_sparse_kkt_set_option: differentiate_refinement is 0 or 1");
+    s->differentiate_refinement = value == 1.0;
+    return 1;
+}
+
+}  // namespace sparse_kkt
+}  // namespace calipso
+
+extern "C" {
+
+int32_t calipso_hip_sparse_kkt_solve_columns(calipso_hip_sparse_kkt* s, int64_t k, int32_t transposed, const double* B, double* X) {
+    return solve_columns(s, "calipso_hip_sparse_kkt_solve_columns", k, transposed, B, X, false);
+}
+int32_t calipso_hip_sparse_kkt_solve_columns_device(calipso_hip_sparse_kkt* s, int64_t k, int32_t transposed, const double* B, double* X) {
+    return solve_columns(s, "calipso_hip_sparse_kkt_solve_columns_device", k, transposed, B, X, true);
+}
+int32_t calipso_hip_sparse_kkt_differentiate(calipso_hip_sparse_kkt* s, int64_t k, const double* jacobian_parameters, double* sensitivity) {
+    return differentiate(s, "calipso_hip_sparse_kkt_differentiate", k, jacobian_parameters, sensitivity, false);
+}
+int32_t calipso_hip_sparse_kkt_differentiate_device(calipso_hip_sparse_kkt* s, int64_t k, const double* jacobian_parameters, double* sensitivity) {
+    return differentiate(s, "calipso_hip_sparse_kkt_differentiate_device", k, jacobian_parameters, sensitivity, true);
+}
+int32_t calipso_hip_sparse_kkt_differentiate_adjoint(calipso_hip_sparse_kkt* s, int64_t k, const double* cotangent, double* adjoint, double* const* grad) {
+    return differentiate_adjoint(s, "calipso_hip_sparse_kkt_differentiate_adjoint", k, cotangent, adjoint, grad, false);
+}
+int32_t calipso_hip_sparse_kkt_differentiate_adjoint_device(calipso_hip_sparse_kkt* s, int64_t k, const double* cotangent, double* adjoint, double* const* grad) {
+    return differentiate_adjoint(s, "calipso_hip_sparse_kkt_differentiate_adjoint_device", k, cotangent, adjoint, grad, true);
+}
+int32_t calipso_hip_sparse_kkt_differentiate_info(calipso_hip_sparse_kkt* s, double out[4]) {
+    if (!s || !out) return CALIPSO_ERR_ARGUMENT;
+    const double zero[4] = {0, 0, 0, 0};
+    const double* from = s->diff ? s->diff->info_forward : zero;
+    std::copy(from, from + 4, out);
+    return CALIPSO_OK;
+}
+int32_t calipso_hip_sparse_kkt_differentiate_adjoint_info(calipso_hip_sparse_kkt* s, double out[4]) {
+    if (!s || !out) return CALIPSO_ERR_ARGUMENT;
+    const double zero[4] = {0, 0, 0, 0};
+    const double* from = s->diff ? s->diff->info_reverse : zero;
+    std::copy(from, from + 4, out);
+    return CALIPSO_OK;
+}
+int32_t calipso_hip_sparse_kkt_differentiate_bytes(calipso_hip_sparse_kkt* s, int64_t* out) {
+    if (!s || !out) return CALIPSO_ERR_ARGUMENT;
+    const DS* t = s->diff;
+    *out = t ? (int64_t)(sizeof(double) * (t->doubles + t->gdoubles + (size_t)s->d.N) + sizeof(int) * t->ints) : 0;
+    return CALIPSO_OK;
+}
+int32_t calipso_hip_sparse_kkt_differentiate_adjoint_times(calipso_hip_sparse_kkt* s, double out[3]) {
+    if (!s || !out) return CALIPSO_ERR_ARGUMENT;
+    const double zero[3] = {0, 0, 0};
+    const double* from = s->diff ? s->diff->times : zero;
+    std::copy(from, from + 3, out);
+    return CALIPSO_OK;
+}
+
+}  // extern "C"

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "sparse_kkt_handle.hpp"           // the handle, KktDev, and (through sparse_kkt.hpp) the analysis: plain host C++
+#include "sparse_differentiate.hpp"        // arrow_inverse: the closed-form arrow inverse, shared with the multi-column maps
 
 using calipso::i64;
 using calipso::Options;
@@ -32,21 +33,6 @@ namespace {
 constexpr int WAVE_ROW_MIN = 32;           // mean non-zeros per gathered row from which a wavefront takes a row instead of a thread
 
 __device__ __forceinline__ double rabs(double x) { return x != x ? __builtin_huge_val() : fabs(x); }      // a NaN reports +inf (step_decisions.hpp: refine_next)
-
-// second_order_matrix_inverse's vector form (cones/second_order.jl:50-65) for u = first row of Cs + Cbar_t P, on the fly: U(k), X(k) give the entries, put(k, value)
-// takes entry k of the UNSCALED result times 1 / u[0] in the reference's order
-template <typename FU, typename FX, typename FP>
-__device__ __forceinline__ void arrow_inverse(int dm, FU U, FX X, FP put) {
-    const double u0 = U(0);
-    double uu = 0.0, d0 = 0.0;
-    for (int k = 1; k < dm; ++k) { const double uk = U(k); uu += uk * uk; d0 += (uk / u0) * X(k); }
-    const double alpha = -1.0 / (u0 * u0) * uu;
-    const double beta = 1.0 / (1.0 + alpha);
-    const double x0_1 = X(0) - d0;
-    double d1 = 0.0;
-    for (int k = 1; k < dm; ++k) { const double us = U(k) / u0; const double o = X(k) - beta * (us * x0_1); d1 += us * o; put(k, 1.0 / u0 * o); }
-    put(0, 1.0 / u0 * (X(0) - d1));
-}
 
 // ---- assemble: K.nzval from the three non-zero vectors, the point, rho, ep, ed ------------------------------------------------------------------------------
 __global__ __launch_bounds__(KT) void k_kkt_assemble(const KktDev d, double ep, double ed, double* __restrict__ K) {
@@ -313,17 +299,18 @@ int set_values(KH* s, const double* Lxx, const double* gx, const double* hx, con
     for (int i = 0; i < 5; ++i) if (src[i] && count[i]) { KK(hipMemcpyAsync(dst[i], src[i], sizeof(double) * count[i], kind, s->st)); s->have[i] = true; }
     KK(hipStreamSynchronize(s->st));
     s->assembled = false; s->factored = false;      // K and its factor belong to the values before
+    if (w) s->slacks_kept = false;                  // the differentiate slacks are the new point's own
     return CALIPSO_OK;
 }
 
-void enqueue_assemble(KH* s, double ep, double ed) {
-    const long long items = (long long)s->d.nnzL + s->d.nnzg + s->d.nnzh + s->d.nx + s->d.ne + s->d.nc + s->d.ncc;
-    hipLaunchKernelGGL(k_kkt_assemble, dim3(blocks(items)), dim3(KT), 0, s->st, s->d, ep, ed, s->K);
+void enqueue_assemble(KH* s, const KktDev& d, double ep, double ed) {
+    const long long items = (long long)d.nnzL + d.nnzg + d.nnzh + d.nx + d.ne + d.nc + d.ncc;
+    hipLaunchKernelGGL(k_kkt_assemble, dim3(blocks(items)), dim3(KT), 0, s->st, d, ep, ed, s->K);
 }
 // one assemble + factorisation at (ep, ed); inertia as compute_inertia! (linear_solver.jl:33-44)
-int assemble_factorize(KH* s, double ep, double ed, int64_t inertia[3]) {
+int assemble_factorize(KH* s, const KktDev& d, double ep, double ed, int64_t inertia[3]) {
     KK(hipEventRecord(s->ev[0], s->st));
-    enqueue_assemble(s, ep, ed);
+    enqueue_assemble(s, d, ep, ed);
     KK(hipEventRecord(s->ev[1], s->st));
     s->sc.ep = ep; s->sc.ed = ed; s->assembled = true; s->factored = false;
     const int rc = calipso_hip_sparse_factorize_device(s->sp, s->K, inertia);      // (returns synchronised)
@@ -381,7 +368,7 @@ int search_direction(KH* s, const double* res, double* step, double regularizati
     for (bool first = true;; first = false) {
         int64_t in[3] = {0, 0, 0};
         const double ep = sc.ep, ed = sc.ed;
-        const int rc = assemble_factorize(s, ep, ed, in);
+        const int rc = assemble_factorize(s, s->d, ep, ed, in);
         if (rc < 0) return leave(rc, nfact, 0, 0.0);
         ++nfact;
         const calipso::IcVerdict v = calipso::ic_after(o, sc, in, s->d.nx, (i64)s->d.ne + s->d.nc, first);
@@ -418,6 +405,9 @@ int kkt_fail(KH* s, int rc, const std::string& text) { return fail(s, rc, text);
 int kkt_reserve(KH* s, double** out, size_t count) { return reserve(s, out, count); }
 int kkt_device_pointer(KH* s, const void* p, const char* entry, const char* arg) { return device_pointer(s, p, entry, arg); }
 int kkt_search_direction(KH* s, const double* res, double* step, double regularization[3], double info[4]) { return search_direction(s, res, step, regularization, info); }
+int kkt_values_missing(KH* s, const char* entry) { return values_missing(s, entry); }
+int kkt_assemble_factorize(KH* s, const KktDev& d, double ep, double ed, int64_t inertia[3]) { return assemble_factorize(s, d, ep, ed, inertia); }
+int kkt_sparse_failed(KH* s, int rc, const char* what) { return sparse_failed(s, rc, what); }
 }  // namespace sparse_kkt
 }  // namespace calipso
 
@@ -430,6 +420,7 @@ int32_t calipso_hip_sparse_kkt_destroy(calipso_hip_sparse_kkt* s) {
     (void)hipSetDevice(s->device);
     if (s->st) (void)hipStreamSynchronize(s->st);
     solve_state_release(s);
+    diff_state_release(s);
     for (void* p : s->dev) if (p) (void)hipFree(p);
     for (hipEvent_t e : s->ev) if (e) (void)hipEventDestroy(e);
     if (s->sp) (void)calipso_hip_sparse_destroy(s->sp);
@@ -461,13 +452,14 @@ static int32_t kkt_create_impl(KH* s, int32_t method, const int64_t* perm) {
         (rc = upload(s, a.Lxx_rows.ptr, &d.Lr.ptr)) || (rc = upload(s, a.Lxx_rows.col, &d.Lr.idx)) || (rc = upload(s, a.Lxx_rows.src, &d.Lr.src)) ||
         (rc = upload(s, a.gx_rows.ptr, &d.gr.ptr)) || (rc = upload(s, a.gx_rows.col, &d.gr.idx)) || (rc = upload(s, a.gx_rows.src, &d.gr.src)) ||
         (rc = upload(s, a.hx_rows.ptr, &d.hr.ptr)) || (rc = upload(s, a.hx_rows.col, &d.hr.idx)) || (rc = upload(s, a.hx_rows.src, &d.hr.src)) ||
-        (rc = upload(s, a.gx_cols.ptr, &d.gc.ptr)) || (rc = upload(s, a.gx_cols.row, &d.gc.idx)) || (rc = upload(s, a.hx_cols.ptr, &d.hc.ptr)) || (rc = upload(s, a.hx_cols.row, &d.hc.idx)))
+        (rc = upload(s, a.gx_cols.ptr, &d.gc.ptr)) || (rc = upload(s, a.gx_cols.row, &d.gc.idx)) || (rc = upload(s, a.hx_cols.ptr, &d.hc.ptr)) || (rc = upload(s, a.hx_cols.row, &d.hc.idx)) ||
+        (rc = upload(s, a.Lxx_cols.ptr, &d.Lc.ptr)) || (rc = upload(s, a.Lxx_cols.row, &d.Lc.idx)))
         return rc;
-    d.gc.src = nullptr; d.hc.src = nullptr;
+    d.gc.src = nullptr; d.hc.src = nullptr; d.Lc.src = nullptr;
     if ((rc = reserve(s, &s->Lxx, (size_t)d.nnzL)) || (rc = reserve(s, &s->gx, (size_t)d.nnzg)) || (rc = reserve(s, &s->hx, (size_t)d.nnzh)) || (rc = reserve(s, &s->w, (size_t)d.N)) ||
         (rc = reserve(s, &s->rho, 1)) || (rc = reserve(s, &s->K, (size_t)a.nnzK())) || (rc = reserve(s, &s->res, (size_t)d.N)) || (rc = reserve(s, &s->step, (size_t)d.N)) ||
         (rc = reserve(s, &s->corr, (size_t)d.N)) || (rc = reserve(s, &s->err, (size_t)d.N)) || (rc = reserve(s, &s->rsym, (size_t)d.n)) || (rc = reserve(s, &s->dsym, (size_t)d.n)) ||
-        (rc = reserve(s, &s->norm, 1))) return rc;
+        (rc = reserve(s, &s->norm, 1)) || (rc = reserve(s, &s->dslack, 2 * (size_t)d.nc))) return rc;
     d.Lxx = s->Lxx; d.gx = s->gx; d.hx = s->hx; d.w = s->w; d.rho = s->rho;
     // a wavefront per gathered row where the rows are long (a dense-pattern problem), a thread per row where they are short (stage-structured ones)
     s->wave_rows = ((long long)d.nnzL + 2ll * d.nnzg + 2ll * d.nnzh) / std::max(d.n, 1) >= WAVE_ROW_MIN;
@@ -513,6 +505,7 @@ int32_t calipso_hip_sparse_kkt_set_option(calipso_hip_sparse_kkt* s, const char*
     if (calipso::set_search_direction_option(s->opt, name, value)) return CALIPSO_OK;
     if (std::string(name) == "central_path") { s->sc.kappa = value; return CALIPSO_OK; }      // (the solver's scalar, not an option: IC-2 reads it, inertia.jl:44)
     { const int rc = solve_set_option(s, name, value); if (rc != 0) return rc < 0 ? rc : CALIPSO_OK; }      // what solve! reads besides (sparse_solve.hip)
+    { const int rc = diff_set_option(s, name, value); if (rc != 0) return rc < 0 ? rc : CALIPSO_OK; }       // differentiate_refinement (sparse_differentiate.hip)
     return fail(s, CALIPSO_ERR_ARGUMENT, std::string("calipso_hip_sparse_kkt_set_option: unknown option ") + name);
 }
 
@@ -533,7 +526,7 @@ int32_t calipso_hip_sparse_kkt_factorize(calipso_hip_sparse_kkt* s, double ep, d
     KK(hipSetDevice(s->device));
     { const int rc = values_missing(s, "calipso_hip_sparse_kkt_factorize"); if (rc < 0) return rc; }
     int64_t in[3] = {0, 0, 0};
-    const int rc = assemble_factorize(s, ep, ed, in);
+    const int rc = assemble_factorize(s, s->d, ep, ed, in);
     if (inertia) std::copy(in, in + 3, inertia);
     return rc;
 }

@@ -26,9 +26,11 @@ struct KktDev {
     const int *row_cone;                          // per cone row: its second-order cone, -1 nonnegative, -2 in no cone
     const int *soc_start, *soc_dim, *col_cone, *col_index, *col_slot;
     View Lr, gr, hr, gc, hc;
+    View Lc;                                      // the column view of Lxx: Lxx' v, and the (row, column) of a stored non-zero (sparse_differentiate.hip)
 };
 
 struct SolveState;                                // sparse_solve.hip: the resident vectors, workspace and counters of solve!
+struct DiffState;                                 // sparse_differentiate.hip: the column workspace and reports of differentiate!
 
 }  // namespace sparse_kkt
 }  // namespace calipso
@@ -52,6 +54,11 @@ struct calipso_hip_sparse_kkt {
     std::string err_text;
     calipso::sparse_kkt::SolveState* solve = nullptr;        // made by the first solve entry that needs it (sparse_solve.hip), released with the handle
     bool continue_after_refinement_failure = false;
+    calipso::sparse_kkt::DiffState* diff = nullptr;          // made by the first differentiate entry (sparse_differentiate.hip), released with the handle
+    double* dslack = nullptr;                                // s, then t (2 nc) as the last search_direction of a solve! was assembled at (quirk B-12)
+    bool slacks_kept = false;                                // false: the differentiate slacks are the resident point's own
+    bool differentiate_refinement = false;
+    bool qp_attached = false;                                // q, b, hvec resident (qp_attach): what the data gradients ask for
 };
 
 namespace calipso {
@@ -62,9 +69,17 @@ int kkt_fail(calipso_hip_sparse_kkt* s, int rc, const std::string& text);       
 int kkt_reserve(calipso_hip_sparse_kkt* s, double** out, size_t count);                                     // zeroed device doubles owned by the handle
 int kkt_device_pointer(calipso_hip_sparse_kkt* s, const void* p, const char* entry, const char* arg);       // the check of every _device entry
 int kkt_search_direction(calipso_hip_sparse_kkt* s, const double* res, double* step, double regularization[3], double info[4]);
+// ... and for sparse_differentiate.hip
+int kkt_values_missing(calipso_hip_sparse_kkt* s, const char* entry);                                       // Lxx, gx, hx, w, penalty resident, or the refusal
+int kkt_assemble_factorize(calipso_hip_sparse_kkt* s, const KktDev& d, double ep, double ed, int64_t inertia[3]);   // one assemble from `d` (the handle's, or with other slacks) + factorisation
+int kkt_sparse_failed(calipso_hip_sparse_kkt* s, int rc, const char* what);
 // sparse_solve.hip, for sparse_kkt.hip
 void solve_state_release(calipso_hip_sparse_kkt* s);                                                        // (before the handle's device memory is freed)
 int solve_set_option(calipso_hip_sparse_kkt* s, const char* name, double value);                            // 1 taken, 0 unknown, < 0 refused
+void diff_keep_slacks(calipso_hip_sparse_kkt* s);                                                           // enqueue: dslack <- the resident s, t (no host wait)
+// sparse_differentiate.hip, for sparse_kkt.hip
+void diff_state_release(calipso_hip_sparse_kkt* s);
+int diff_set_option(calipso_hip_sparse_kkt* s, const char* name, double value);                             // 1 taken, 0 unknown, < 0 refused
 
 }  // namespace sparse_kkt
 }  // namespace calipso

@@ -155,6 +155,12 @@ __global__ __launch_bounds__(KT) void k_solve_init(const KktDev d, const SolveDe
         v.w[d.o_s + c] = e; v.w[d.o_t + c] = e; v.w[d.o_z + c] = 0.0;
     }
 }
+// the s, t a search_direction is about to be assembled at, kept for differentiate! (quirk B-12): s, then t
+__global__ __launch_bounds__(KT) void k_solve_keep_slacks(const KktDev d, double* __restrict__ kept) {
+    const long long k = (long long)blockIdx.x * KT + threadIdx.x;
+    if (k < d.nc) kept[k] = d.w[d.o_s + k];
+    else if (k < 2ll * d.nc) kept[k] = d.w[d.o_t + (k - d.nc)];
+}
 __global__ __launch_bounds__(KT) void k_solve_fill(int count, double* __restrict__ out, double value) {
     const long long k = (long long)blockIdx.x * KT + threadIdx.x;
     if (k < count) out[k] = value;
@@ -546,6 +552,8 @@ int qp_attach(KH* s, const double* q, const double* b, const double* hvec, doubl
     for (int i = 0; i < 3; ++i) if (src[i] && count[i]) { KK(hipMemcpyAsync(dst[i], src[i], sizeof(double) * count[i], kind, s->st)); t->have_qp[i] = true; }
     KK(hipStreamSynchronize(s->st));
     t->v.objective_constant = objective_constant;
+    s->qp_attached = true;
+    for (int i = 0; i < 3; ++i) if (count[i] && !t->have_qp[i]) s->qp_attached = false;
     return CALIPSO_OK;
 }
 int initialize(KH* s, const double* x0, hipMemcpyKind kind) {
@@ -557,6 +565,7 @@ int initialize(KH* s, const double* x0, hipMemcpyKind kind) {
     t->group_open = false;
     s->have[3] = true;
     s->assembled = false; s->factored = false;               // K and its factor belong to the point before
+    s->slacks_kept = false;                                  // the differentiate slacks are the new point's own
     return CALIPSO_OK;
 }
 double* resident(KH* s, int vec) {
@@ -606,6 +615,7 @@ int solve(KH* s, double info[16]) {
             if (kind == 2) break;
             // :175-185: Hessian and Jacobians are constant, the dual Hessians zero, the cone Jacobians formed inside the kernels of sparse_kkt.hip
             double reg[3] = {sc.ep, sc.ep_last, sc.ed}, sdinfo[4] = {0, 0, 0, 0};
+            diff_keep_slacks(s);                                                              // what differentiate! forms the cone blocks at: no host wait
             rc = kkt_search_direction(s, s->res, s->step, reg, sdinfo);                       // :187
             nfact += (i64)sdinfo[0]; max_rounds = std::max(max_rounds, (i64)sdinfo[1]);
             for (int k = 0; k < 5; ++k) sd_ms += s->ms[k];
@@ -673,6 +683,11 @@ int solve(KH* s, double info[16]) {
 
 namespace calipso {
 namespace sparse_kkt {
+
+void diff_keep_slacks(KH* s) {
+    if (s->d.nc) hipLaunchKernelGGL(k_solve_keep_slacks, dim3(blocks_of(2ll * s->d.nc)), dim3(KT), 0, s->st, s->d, s->dslack);
+    s->slacks_kept = true;
+}
 
 void solve_state_release(KH* s) {
     SS* t = s->solve;
@@ -806,7 +821,11 @@ int32_t calipso_hip_sparse_kkt_get(calipso_hip_sparse_kkt* s, const char* name, 
     KK(hipSetDevice(s->device));
     { const int rc = ensure_state(s); if (rc < 0) return rc; }
     REFUSE(check_named_vector("calipso_hip_sparse_kkt_get", name, out, len, s->d.nx, s->d.ne, s->d.nc, false));
-    if (len) KK(hipMemcpyAsync(out, resident(s, vector_by_name(name)), sizeof(double) * (size_t)len, hipMemcpyDeviceToHost, s->st));
+    if (vector_by_name(name) == V_DIFFERENTIATE_SLACKS) {
+        const size_t nc = (size_t)s->d.nc;
+        const double* from[2] = {s->slacks_kept ? s->dslack : s->w + s->d.o_s, s->slacks_kept ? s->dslack + nc : s->w + s->d.o_t};
+        for (int i = 0; i < 2 && nc; ++i) KK(hipMemcpyAsync(out + (size_t)i * nc, from[i], sizeof(double) * nc, hipMemcpyDeviceToHost, s->st));
+    } else if (len) KK(hipMemcpyAsync(out, resident(s, vector_by_name(name)), sizeof(double) * (size_t)len, hipMemcpyDeviceToHost, s->st));
     KK(hipStreamSynchronize(s->st));
     return CALIPSO_OK;
 }
@@ -818,7 +837,7 @@ int32_t calipso_hip_sparse_kkt_set(calipso_hip_sparse_kkt* s, const char* name, 
     const int vec = vector_by_name(name);
     if (len) KK(hipMemcpyAsync(resident(s, vec), in, sizeof(double) * (size_t)len, hipMemcpyHostToDevice, s->st));
     KK(hipStreamSynchronize(s->st));
-    if (vec == V_SOLUTION) { s->have[3] = true; s->assembled = false; s->factored = false; }
+    if (vec == V_SOLUTION) { s->have[3] = true; s->assembled = false; s->factored = false; s->slacks_kept = false; }
     return CALIPSO_OK;
 }
 int32_t calipso_hip_sparse_kkt_solution_device(calipso_hip_sparse_kkt* s, double** p) {

@@ -99,14 +99,16 @@ inline Layout layout(i64 nx, i64 ne, i64 nc, i64 n_small, i64 n_wide) {
 
 // ---- the resident vectors by their reference names (solver.jl, problem data) -----------------------------------------------------------------------------------
 enum Vector { V_SOLUTION, V_CANDIDATE, V_DUAL, V_RESIDUAL, V_MERIT_GRADIENT, V_STEP, V_CONE_PRODUCT, V_CONE_TARGET, V_BARRIER_GRADIENT, V_EQUALITY_CONSTRAINT,
-              V_CONE_CONSTRAINT, V_OBJECTIVE_GRADIENT_VARIABLES, V_COUNT };
+              V_CONE_CONSTRAINT, V_OBJECTIVE_GRADIENT_VARIABLES, V_COUNT,
+              // not a vector of the reference's solver: the s, t that differentiate! forms the cone blocks at (sparse_differentiate.hip), s then t; read only
+              V_DIFFERENTIATE_SLACKS = V_COUNT, V_NAMED };
 inline const char* vector_name(int v) {
-    static const char* const names[V_COUNT] = {"solution", "candidate", "dual", "residual", "merit_gradient", "step", "cone_product", "cone_target", "barrier_gradient",
-                                               "equality_constraint", "cone_constraint", "objective_gradient_variables"};
-    return v >= 0 && v < V_COUNT ? names[v] : "";
+    static const char* const names[V_NAMED] = {"solution", "candidate", "dual", "residual", "merit_gradient", "step", "cone_product", "cone_target", "barrier_gradient",
+                                               "equality_constraint", "cone_constraint", "objective_gradient_variables", "differentiate_slacks"};
+    return v >= 0 && v < V_NAMED ? names[v] : "";
 }
 inline int vector_by_name(const char* name) {
-    if (name) for (int v = 0; v < V_COUNT; ++v) if (!std::strcmp(name, vector_name(v))) return v;
+    if (name) for (int v = 0; v < V_NAMED; ++v) if (!std::strcmp(name, vector_name(v))) return v;
     return -1;
 }
 inline i64 vector_length(int v, i64 nx, i64 ne, i64 nc) {
@@ -116,6 +118,7 @@ inline i64 vector_length(int v, i64 nx, i64 ne, i64 nc) {
         case V_MERIT_GRADIENT: return nx + ne + nc;
         case V_CONE_PRODUCT: case V_CONE_TARGET: case V_BARRIER_GRADIENT: case V_CONE_CONSTRAINT: return nc;
         case V_OBJECTIVE_GRADIENT_VARIABLES: return nx;
+        case V_DIFFERENTIATE_SLACKS: return 2 * nc;
         default: return -1;
     }
 }

@@ -476,12 +476,14 @@ void launch_refine_rows_multi(calipso_hip_solver* s, const double* X, const doub
 void launch_refine_x_multi(calipso_hip_solver* s, const double* X, const double* R, const double* hx, long long ldh, int p, double* E, const double* part, double* norms) {
     hipLaunchKernelGGL(k_refine_x_multi, dim3(1, p, 1), dim3(RT), 0, s->stream, s->sc, s->d, X, R, hx, ldh, E, part, refine_multi_parts(s), norms);
 }
-void launch_accumulate_masked(calipso_hip_solver* s, const int* active, const double* C, int p, double* X, double* Xsave) {
-    hipLaunchKernelGGL(k_accumulate_masked, dim3((s->d.N + 255) / 256, p, 1), dim3(256), 0, s->stream, s->d.N, active, C, X, Xsave);
+void launch_accumulate_masked(hipStream_t stream, int N, const int* active, const double* C, int p, double* X, double* Xsave) {
+    hipLaunchKernelGGL(k_accumulate_masked, dim3((N + 255) / 256, p, 1), dim3(256), 0, stream, N, active, C, X, Xsave);
 }
-void launch_restore_masked(calipso_hip_solver* s, const int* restore, const double* Xsave, int p, double* X) {
-    hipLaunchKernelGGL(k_restore_masked, dim3((s->d.N + 255) / 256, p, 1), dim3(256), 0, s->stream, s->d.N, restore, Xsave, X);
+void launch_restore_masked(hipStream_t stream, int N, const int* restore, const double* Xsave, int p, double* X) {
+    hipLaunchKernelGGL(k_restore_masked, dim3((N + 255) / 256, p, 1), dim3(256), 0, stream, N, restore, Xsave, X);
 }
+void launch_accumulate_masked(calipso_hip_solver* s, const int* active, const double* C, int p, double* X, double* Xsave) { launch_accumulate_masked(s->stream, s->d.N, active, C, p, X, Xsave); }
+void launch_restore_masked(calipso_hip_solver* s, const int* restore, const double* Xsave, int p, double* X) { launch_restore_masked(s->stream, s->d.N, restore, Xsave, p, X); }
 void launch_scale_into(calipso_hip_solver* s, const double* x, double* y, size_t n, double a) {
     hipLaunchKernelGGL(k_scale_into, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, n, x, y, a);
 }

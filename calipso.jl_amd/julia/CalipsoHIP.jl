@@ -519,6 +519,33 @@ end
 sparse_set!(k::SparseKKT, name::AbstractString, v::Vector{Float64}) =
     kkt_check(ccall((:calipso_hip_sparse_kkt_set, lib), Int32, (Ptr{Cvoid}, Cstring, Ptr{Float64}, Int64), k.handle, name, v, length(v)), k, "set($name)")
 
+# ---- differentiate! on the same handle (csrc/sparse_differentiate.hip): ccall wrappers, no logic; not executed here either (see the note at the top) -----------
+# X = M B (transposed: M' B) through the current factorisation; B, X: N x k
+sparse_solve_columns!(k::SparseKKT, X::Matrix{Float64}, B::Matrix{Float64}; transposed::Bool=false) = kkt_check(
+    ccall((:calipso_hip_sparse_kkt_solve_columns, lib), Int32, (Ptr{Cvoid}, Int64, Int32, Ptr{Float64}, Ptr{Float64}), k.handle, size(B, 2), transposed ? 1 : 0, B, X), k, "solve_columns!")
+# differentiate! (differentiate.jl:13-58) for the caller's dR/dtheta (N x k): sensitivity = -M jacobian_parameters
+sparse_differentiate!(k::SparseKKT, sensitivity::Matrix{Float64}, jacobian_parameters::Matrix{Float64}) = kkt_check(
+    ccall((:calipso_hip_sparse_kkt_differentiate, lib), Int32, (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}), k.handle, size(jacobian_parameters, 2), jacobian_parameters, sensitivity), k, "differentiate!")
+# reverse mode: adjoint = M' cotangent (N x k, or nothing); grad: six arrays Lxx, q, gx, b, hx, hvec (size x k each, or nothing), the matrices on their stored patterns
+function sparse_differentiate_adjoint!(k::SparseKKT, cotangent::Matrix{Float64}; adjoint=nothing, grad=nothing)
+    ptrs = grad === nothing ? C_NULL : Ptr{Float64}[kkt_ptr(g) for g in grad]
+    GC.@preserve adjoint grad ptrs kkt_check(
+        ccall((:calipso_hip_sparse_kkt_differentiate_adjoint, lib), Int32, (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Ptr{Float64}}), k.handle, size(cotangent, 2), cotangent,
+              kkt_ptr(adjoint), ptrs), k, "differentiate_adjoint!")
+end
+sparse_differentiate_info(k::SparseKKT) = (out = zeros(4); kkt_check(ccall((:calipso_hip_sparse_kkt_differentiate_info, lib), Int32, (Ptr{Cvoid}, Ptr{Float64}), k.handle, out), k, "differentiate_info"); out)
+sparse_differentiate_adjoint_info(k::SparseKKT) = (out = zeros(4); kkt_check(ccall((:calipso_hip_sparse_kkt_differentiate_adjoint_info, lib), Int32, (Ptr{Cvoid}, Ptr{Float64}), k.handle, out), k, "differentiate_adjoint_info"); out)
+sparse_differentiate_adjoint_times(k::SparseKKT) = (out = zeros(3); kkt_check(ccall((:calipso_hip_sparse_kkt_differentiate_adjoint_times, lib), Int32, (Ptr{Cvoid}, Ptr{Float64}), k.handle, out), k, "differentiate_adjoint_times"); out)
+sparse_differentiate_bytes(k::SparseKKT) = (out = zeros(Int64, 1); kkt_check(ccall((:calipso_hip_sparse_kkt_differentiate_bytes, lib), Int32, (Ptr{Cvoid}, Ptr{Int64}), k.handle, out), k, "differentiate_bytes"); out[1])
+# the device forms: device pointers of the handle's device
+sparse_solve_columns_device!(k::SparseKKT, X::Ptr{Cvoid}, B::Ptr{Cvoid}, ncols::Integer; transposed::Bool=false) = kkt_check(
+    ccall((:calipso_hip_sparse_kkt_solve_columns_device, lib), Int32, (Ptr{Cvoid}, Int64, Int32, Ptr{Cvoid}, Ptr{Cvoid}), k.handle, ncols, transposed ? 1 : 0, B, X), k, "solve_columns_device!")
+sparse_differentiate_device!(k::SparseKKT, sensitivity::Ptr{Cvoid}, jacobian_parameters::Ptr{Cvoid}, ncols::Integer) = kkt_check(
+    ccall((:calipso_hip_sparse_kkt_differentiate_device, lib), Int32, (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}), k.handle, ncols, jacobian_parameters, sensitivity), k, "differentiate_device!")
+sparse_differentiate_adjoint_device!(k::SparseKKT, cotangent::Ptr{Cvoid}, ncols::Integer; adjoint::Ptr{Cvoid}=C_NULL, grad::Union{Nothing,Vector{Ptr{Cvoid}}}=nothing) = GC.@preserve grad kkt_check(
+    ccall((:calipso_hip_sparse_kkt_differentiate_adjoint_device, lib), Int32, (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Ptr{Cvoid}}), k.handle, ncols, cotangent, adjoint,
+          grad === nothing ? C_NULL : grad), k, "differentiate_adjoint_device!")
+
 # The handle-resident variant: the KKT blocks are already on the device (uploaded by the evaluation callback or by set_field!), the
 # condensed matrix is never formed on the host.  factorize! = calipso_hip_factorize on those blocks with the handle's kappa / rho /
 # regularisation scalars (which the caller syncs with sync_scalars!); `A` is accepted for signature parity only.
@@ -922,6 +949,7 @@ function allreduce_sum!(c::HIPComm, v::Vector{Float64})
 end
 
 export SparseKKT, set_values!, set_values_device!, kkt_info, kkt_pattern, kkt_factorize!, kkt_matrix!, kkt_mul!, solve_symmetric!, sparse_search_direction!, sparse_search_direction_device!, kkt_timing, qp_attach!, sparse_initialize!, sparse_solve!, sparse_get, sparse_set!
+export sparse_solve_columns!, sparse_differentiate!, sparse_differentiate_adjoint!, sparse_differentiate_info, sparse_differentiate_adjoint_info, sparse_differentiate_adjoint_times, sparse_differentiate_bytes, sparse_solve_columns_device!, sparse_differentiate_device!, sparse_differentiate_adjoint_device!
 export HIPSolver, streams_concurrent, rebind_stream!, spread_streams!, HIPLDLSolver, HIPSparseLDLSolver, hip_sparse_ldl_solver, HIPKKTSolver, hip_ldl_solver, HIPGroup, HIPSmallNewton, set_option!, set_cones!, set_qp!, set_evaluator!, set_parameters!, differentiate_adjoint!, solution, set_stream!, set_qp_device!, initialize_device!, set_state_device!, set_parameters_device!, solve_device!, solution_device!, differentiate_adjoint_device!, HIPComm, comm_unique_id, comm_size, gather_status, allreduce_sum!, newton_step!,
        search_direction_nonsymmetric!, analyze_structure!, clear_structure!, set_stage_parallel!, set_stage_blocks!, declared_structure, kernel_times, sync_scalars!, copy_back!
 

@@ -33,14 +33,21 @@ converge gives NaN gradients and a warning, as on the host path of QPLayer.
 GroupQPLayer is the batched layer over the general path: every input (count, ...) or unbatched and shared by the members; forward = qp_attach per member + initialize!
 with zeros + Group.solve (all members in lockstep through the same launches), backward = ONE Group.vjp(qp=...) for the inputs that need gradients — one factorisation
 launch chain and one transposed condensed solve for the whole group instead of one per member.  Gradients of shared inputs are summed over the members on the host, in
-member order.  Host tensors only: the handles take host arrays.  Members that did not converge get NaN gradients and one warning counts them."""
+member order.  Host tensors only: the handles take host arrays.  Members that did not converge get NaN gradients and one warning counts them.
+
+    x = SparseQPLayer.apply(kkt, P_values, q, A_values, b, G_values, h)   # ONE large sparse QP on a handle from SparseConicQP: no dense block anywhere
+
+SparseQPLayer is the layer over the sparse route: the matrices are given as the VALUES on the stored patterns of the P, A, G the handle was made from (CSC order,
+row indices ascending), and their gradients come back on those patterns — no nx x nx array exists in forward or backward.  forward = set_values + attach_qp +
+initialize with zeros + solve, backward = ONE SparseKKT.vjp for the cotangent.  Host tensors, or CUDA tensors on the handle's device: then the data, the solution and
+the gradients stay on the device and nothing but the solve's own read-backs crosses to the host.  A solve that does not end with status 1 warns and gives NaN gradients."""
 import warnings
 
 import numpy as np
 
 from ._marshal import QP_NAMES, cotangent_from_parts, dual_rows, qp_shapes
 
-__all__ = ["QPLayer", "ParametricLayer", "SolverQPLayer", "GroupQPLayer"]
+__all__ = ["QPLayer", "ParametricLayer", "SolverQPLayer", "GroupQPLayer", "SparseQPLayer"]
 
 _cls = {}
 
@@ -50,11 +57,11 @@ def _np(t):
 
 
 # ---- what the layers share; `h` is the handle or, for a group, its first member: whatever carries nx, ne, nc --------------------------------------------------------
-def _classify(torch, layer, h, data, count=None, host_only=False):
+def _classify(torch, layer, h, data, count=None, host_only=False, shapes=None):
     """the inputs' dtypes and shapes: per input True for the unbatched shape (shared by the items), False for a leading axis of `count`; count None: one item, no
-    leading axis admitted"""
+    leading axis admitted.  shapes: the six unbatched shapes where they are not those of the dense QP arrays"""
     shared = []
-    for name, t, dm in zip(QP_NAMES, data, qp_shapes(h.nx, h.ne, h.nc).values()):
+    for name, t, dm in zip(QP_NAMES, data, shapes or qp_shapes(h.nx, h.ne, h.nc).values()):
         if t.dtype != torch.float64:
             raise TypeError("%s: %s must be float64" % (layer, name))
         if host_only and t.is_cuda:
@@ -241,7 +248,54 @@ def _build():
             warning = "GroupQPLayer: %d of %d members did not converge: their gradients are NaN" % (int(bad.sum()), count)
             return (None, *_gradients(torch, out, want, ctx.shared, bad, warning, _sum_in_member_order, "cpu"), None, None)
 
-    return {"QPLayer": QPLayer, "ParametricLayer": ParametricLayer, "SolverQPLayer": SolverQPLayer, "GroupQPLayer": GroupQPLayer}
+    class SparseQPLayer(torch.autograd.Function):
+        """apply(kkt, P_values, q, A_values, b, G_values, h, return_duals=False): the solution x (nx,) of one sparse QP on a handle from SparseConicQP, or (x, y, z) with
+        return_duals.  P_values, A_values, G_values: the values on the stored patterns of the P, A, G the handle was made from"""
+
+        @staticmethod
+        def forward(ctx, kkt, P_values, q, A_values, b, G_values, h, return_duals=False):
+            data = (P_values, q, A_values, b, G_values, h)
+            if not hasattr(kkt, "_conic_qp"):
+                raise ValueError("SparseQPLayer: the handle must come from SparseConicQP")
+            shapes = [(int(kkt._conic_qp[0].size),), (kkt.nx,), (kkt.nnz[1],), (kkt.ne,), (kkt.nnz[2],), (kkt.nc,)]
+            _classify(torch, "SparseQPLayer", kkt, data, shapes=shapes)
+            on_device = all(t.is_cuda and t.device.index == kkt.device for t in data)
+            if not on_device and any(t.is_cuda for t in data):
+                raise ValueError("SparseQPLayer: the inputs are all host tensors or all CUDA tensors on the handle's device")
+            tensors = [t.detach().contiguous() if on_device else _np(t) for t in data]
+            key = object()
+            _solve_sparse(torch, kkt, tensors, on_device, key)
+            ctx.kkt, ctx.key, ctx.tensors, ctx.on_device, ctx.converged, ctx.device = kkt, key, tensors, on_device, kkt._qp_layer_converged, q.device
+            ctx.inputs, ctx.versions = data, [t._version for t in data]
+            oy, oz = dual_rows(kkt.nx, kkt.ne, kkt.nc)
+            if on_device:
+                w = kkt.solution_device()
+                out = (w[:kkt.nx].clone(), w[oy:oy + kkt.ne].clone(), w[oz:oz + kkt.nc].clone())
+                return out if return_duals else out[0]
+            w = kkt.get("solution")
+            return _outputs(torch, w[:kkt.nx], w[oy:oy + kkt.ne], w[oz:oz + kkt.nc], return_duals, q.device)
+
+        @staticmethod
+        def backward(ctx, gx, gy=None, gz=None):
+            kkt, want = ctx.kkt, _want(ctx)
+            _solved_again(kkt, ctx, lambda: _solve_sparse(torch, kkt, ctx.tensors, ctx.on_device, ctx.key), "SparseQPLayer: an input was modified in place after forward and the "
+                          "handle has solved other data since: backward cannot solve the same data again" if ctx.on_device else None)
+            warning = "SparseQPLayer: the solve did not converge (status != 1): the gradients are NaN"
+            if not ctx.on_device:
+                out = kkt.vjp(_cotangent(kkt, (), gx, gy, gz), adjoint=False, qp=want) if want else {}
+                return (None, *_gradients(torch, out, want, (False,) * 6, not ctx.converged, warning, None, ctx.device), None)
+            oy, oz = dual_rows(kkt.nx, kkt.ne, kkt.nc)
+            v = torch.zeros(kkt.N, dtype=torch.float64, device=ctx.device)
+            for g, at, n in ((gx, 0, kkt.nx), (gy, oy, kkt.ne), (gz, oz, kkt.nc)):
+                if g is not None and n:
+                    v[at:at + n] = g
+            out = kkt.vjp(v, adjoint=False, qp=want) if want else {}
+            if not ctx.converged:
+                warnings.warn(warning)
+                out = {name: torch.full_like(g, float("nan")) for name, g in out.items()}
+            return (None, *[out[name].contiguous() if name in out else None for name in QP_NAMES], None)
+
+    return {"QPLayer": QPLayer, "ParametricLayer": ParametricLayer, "SolverQPLayer": SolverQPLayer, "GroupQPLayer": GroupQPLayer, "SparseQPLayer": SparseQPLayer}
 
 
 def _solve_device(torch, sn, tensors, objective_scale, key):
@@ -275,6 +329,30 @@ def _solve_group(group, arrays, shared, objective_scale, key):
         initialize_b(solver, np.zeros(solver.nx))
     res = group.solve()
     group._qp_layer_key, group._qp_layer_converged = key, np.array([r == 1 for r in res])
+
+
+def _solve_sparse(torch, kkt, data, on_device, key):
+    """data: the six inputs as numpy arrays, or as CUDA tensors on the handle's device: Lxx = c (P + P') on its own pattern from P's values, gx = A, hx = -G"""
+    Pv, q, Av, b, Gv, h = data
+    ij, ji, c = kkt._conic_qp_positions(on_device)
+    if on_device:
+        Lxx = torch.zeros(kkt.nnz[0], dtype=torch.float64, device=Pv.device)
+        Lxx.index_add_(0, ij, c * Pv)      # (the positions of a pattern are distinct: each add touches an entry once, in a fixed order)
+        Lxx.index_add_(0, ji, c * Pv)
+        x0 = torch.zeros(kkt.nx, dtype=torch.float64, device=Pv.device)
+        pick = lambda t, n: t if n else None      # (an empty tensor has no device pointer to check)
+        kkt.set_values(pick(Lxx, kkt.nnz[0]), pick(Av, kkt.nnz[1]), pick(-Gv, kkt.nnz[2]))
+        kkt.attach_qp(q, pick(b, kkt.ne), pick(h, kkt.nc))
+    else:
+        Lxx = np.zeros(kkt.nnz[0])
+        Lxx[ij] += c * Pv
+        Lxx[ji] += c * Pv
+        x0 = np.zeros(kkt.nx)
+        kkt.set_values(Lxx, Av, -Gv)
+        kkt.attach_qp(q, b, h)
+    kkt.initialize(x0)
+    status, _ = kkt.solve()
+    kkt._qp_layer_key, kkt._qp_layer_converged = key, status == 1
 
 
 def _solve(sn, arrays, shared, objective_scale, key):

@@ -547,7 +547,9 @@ int32_t calipso_hip_sparse_timing(calipso_hip_sparse*, double ms[2]);
  *                   (search_direction.jl:22) — there is NO such fallback here; the call returns the warning with the last refined step in place, and the handle
  *                   stays usable.
  *   timing          ms[8] of the last search_direction, HIP events on the handle's stream: [assembles, factorisations, first solve, refinement solves,
- *                   H v + norm of all rounds, wall-clock of the call, 0, 0] */
+ *                   H v + norm of all rounds, wall-clock of the call, 0, 0]; the last two slots belong to the differentiate entries below: of the last
+ *                   solve_columns / differentiate / differentiate_adjoint, [6] its first pre + multi-column solve + post, [7] its correction rounds with their
+ *                   read-backs (their assemble and factorisation are added to [0] and [1]) */
 typedef struct calipso_hip_sparse_kkt calipso_hip_sparse_kkt;
 int32_t calipso_hip_sparse_kkt_create(int64_t nx, int64_t ne, int64_t nc, int64_t n_nonnegative, int64_t n_soc, const int64_t* dims, const int64_t* Lxx_colptr,
                                       const int64_t* Lxx_rowval, const int64_t* gx_colptr, const int64_t* gx_rowval, const int64_t* hx_colptr, const int64_t* hx_rowval,
@@ -617,6 +619,49 @@ int32_t calipso_hip_sparse_kkt_set(calipso_hip_sparse_kkt*, const char* name, co
 int32_t calipso_hip_sparse_kkt_solution_device(calipso_hip_sparse_kkt*, double** p);
 int32_t calipso_hip_sparse_kkt_keep_trace(calipso_hip_sparse_kkt*, int64_t rows);
 int32_t calipso_hip_sparse_kkt_trace(calipso_hip_sparse_kkt*, double* out, int64_t cap_rows, int64_t* accepted);
+
+/* ---- differentiate! on sparse problem data resident on the device (csrc/sparse_differentiate.hip; host and shared pieces: csrc/sparse_differentiate.hpp) -------
+ * differentiate! (src/solver/differentiate.jl:1-61) in both directions on the same handle, for k columns in the launches of one: the condensed solve of
+ * search_direction_symmetric! (search_direction.jl:25-104) is the linear map  step = M residual  (residual_symmetric!, K^-1 with K read from one triangle, the
+ * recovery of Dr, Ds, Dt), and a "pre" launch, ONE multi-column sparse LDL^T solve and a "post" launch apply M or M' to all columns.  H is the unreduced N x N matrix
+ * calipso_hip_sparse_kkt_mul applies; both are taken at the regularisation of the last assemble.  Every sum is a gather in a fixed order: a call repeats bit for bit.
+ * Arrays are column-major, N x k; the _device forms take device pointers of the handle's device, checked as in set_values_device.
+ *   solve_columns        X = M B (transposed = 0) or M' B with the CURRENT factorisation, as solve_symmetric (search_direction.jl:25-104); no refinement
+ *   differentiate        differentiate.jl:13-58 for the caller's dR/dtheta (N x k; the handle has no theta of its own): one assemble + factorisation at the (ep, ed)
+ *                        the handle holds, then sensitivity = -M jacobian_parameters (:54-56)
+ *   differentiate_adjoint  the same factorisation, then adjoint = lambda = M' cotangent (differentiate.jl:29-58 transposed), and the gradients of a loss with
+ *                        dLoss/dw = cotangent with respect to the QP's data: grad = NULL, or six pointers Lxx, q, gx, b, hx, hvec (NULLs skipped), each k x size with
+ *                        the matrices ON THEIR STORED PATTERNS in the caller's non-zero order (sizes nnz(Lxx), nx, nnz(gx), ne, nnz(hx), nc).  With x, y, z of the
+ *                        resident point and l_x, l_y, l_z the parts of lambda:  Lxx(i, c): -l_x[i] x[c];  q: -l_x;  gx(e, c): -(l_y[e] x[c] + y[e] l_x[c]);  b: +l_y;
+ *                        hx(m, c): -(l_z[m] x[c] + z[m] l_x[c]);  hvec: -l_z — one launch, one thread per (stored non-zero, column); no nx x nx array exists anywhere.
+ *                        adjoint may be NULL.
+ *   Option differentiate_refinement = 1 (set_option; default 0, other values CALIPSO_ERR_ARGUMENT): the correction rounds of iterative_refinement.jl:14-44 on all
+ *                        columns, forward against H, reverse against H', with the per-column decisions of csrc/sensitivity_columns.hpp; one read-back of k norms per
+ *                        round.  On a handle with any second-order cone the option is inert (quirk B-3, as calipso_hip_differentiate): the columns are the unrefined
+ *                        map bit for bit and 0 rounds are reported.
+ *   The slacks of the cone blocks (quirk B-12): the reference's differentiate! calls no cone!, it works on the cone product Jacobians where the last search direction
+ *                        left them, one iterate before the point solve! returns.  calipso_hip_sparse_kkt_solve keeps the s, t its last search_direction was assembled
+ *                        at (2 nc doubles, a device-to-device copy on the handle's stream) and the two differentiate entries assemble with those; after set_values
+ *                        with w, set("solution") or initialize they are the resident point's own.  get("differentiate_slacks") returns them (2 nc: s, then t).  x, y, z
+ *                        of the gradient formulas are always the resident point's.
+ *   differentiate_info / differentiate_adjoint_info   [columns, correction rounds (largest over the columns), columns that did not meet the stopping test, largest final
+ *                        column norm], as calipso_hip_differentiate_info; differentiate_adjoint_times: HIP-event ms of the last reverse call, [0] entry to last kernel,
+ *                        [1] the copies of the results, [2] of [0] the gradient kernel alone, as calipso_hip_differentiate_adjoint_times
+ * CALIPSO_ERR_ARGUMENT with calipso_hip_sparse_kkt_last_error naming the argument, the handle usable afterwards: a NULL handle, k < 1, k > 65535 (the multi-column
+ * solve's grid limit), a missing array, grad without an attached QP or without a resident point, no values resident (solve_columns: no factorisation). */
+int32_t calipso_hip_sparse_kkt_solve_columns(calipso_hip_sparse_kkt*, int64_t k, int32_t transposed, const double* B, double* X);
+int32_t calipso_hip_sparse_kkt_solve_columns_device(calipso_hip_sparse_kkt*, int64_t k, int32_t transposed, const double* B, double* X);
+int32_t calipso_hip_sparse_kkt_differentiate(calipso_hip_sparse_kkt*, int64_t k, const double* jacobian_parameters, double* sensitivity);
+int32_t calipso_hip_sparse_kkt_differentiate_device(calipso_hip_sparse_kkt*, int64_t k, const double* jacobian_parameters, double* sensitivity);
+int32_t calipso_hip_sparse_kkt_differentiate_adjoint(calipso_hip_sparse_kkt*, int64_t k, const double* cotangent, double* adjoint, double* const* grad);
+int32_t calipso_hip_sparse_kkt_differentiate_adjoint_device(calipso_hip_sparse_kkt*, int64_t k, const double* cotangent, double* adjoint, double* const* grad);
+int32_t calipso_hip_sparse_kkt_differentiate_info(calipso_hip_sparse_kkt*, double out[4]);
+int32_t calipso_hip_sparse_kkt_differentiate_adjoint_info(calipso_hip_sparse_kkt*, double out[4]);
+int32_t calipso_hip_sparse_kkt_differentiate_adjoint_times(calipso_hip_sparse_kkt*, double out[3]);
+/* the device bytes the three entries above hold for their columns (the N x k and n x k blocks, the rounds' blocks and masks, the staging of a host call's gradients, the
+ * N doubles of the point with the kept slacks): grown on demand, never shrunk, kept — a call that repeats its shapes allocates nothing.  The multi-column LDL^T solve's
+ * own right-hand-side buffers (2 n k doubles and its update vectors) belong to the calipso_hip_sparse handle and are not counted */
+int32_t calipso_hip_sparse_kkt_differentiate_bytes(calipso_hip_sparse_kkt*, int64_t* out);
 
 /* ---- batched small systems (BASELINE config C5): LDS-resident LDL^T + multi-right-hand-side solve, one workgroup per
  * instance, one launch for the whole batch.  The sensitivity solves of the reference's MPC auto-tuning loop

@@ -863,7 +863,8 @@ class SparseKKT(_Handle):
     without a dense block anywhere.  Lxx (nx x nx, the full Lagrangian Hessian with both triangles), gx (ne x nx), hx (nc x nx): scipy sparse matrices whose
     PATTERN is used as it is (stored zeros included; a CSC matrix is taken in its own non-zero order, which later raw value arrays follow).  Cones: the first
     n_nonnegative rows of hx nonnegative (default: all that the second-order cones leave), then contiguous second-order cones of second_order_dims.
-    method / perm as SparseLDL.  There is no `H \\ residual` fallback: search_direction returns status 2 (CALIPSO_WARN_REFINEMENT) with the last refined step.
+    method / perm as SparseLDL.  By default there is no `H \\ residual` fallback: search_direction returns status 2 (CALIPSO_WARN_REFINEMENT) with the last refined step;
+    with the option krylov_fallback = 1 it goes on to solve_nonsymmetric (preconditioned GMRES, csrc/sparse_krylov.hip) and still returns 2 (fallback_info()).
     With attach_qp the same handle runs the vector half of solve! and a whole solve! of the sparse conic QP (csrc/sparse_solve.hip): initialize, solve, and the steps of an
     iteration one by one — and differentiate! in both directions (csrc/sparse_differentiate.hip): solve_columns, differentiate, vjp with the data gradients on the
     stored patterns."""
@@ -987,7 +988,7 @@ class SparseKKT(_Handle):
 
     def search_direction(self, residual, regularization=(0.0, 0.0, 0.0)):
         """search_direction! from regularization = (ep, ep_last, ed): returns (step, regularization, info, status) with info = dict(factorizations, refinement_rounds,
-        residual_norm) and status 0 or 2 (refinement failed: the last refined step, no fallback).  A CUDA tensor / device pointer as residual: the device route,
+        residual_norm, fallback_iterations) and status 0 or 2 (refinement failed: the last refined step, or with krylov_fallback the GMRES step).  A CUDA tensor / device pointer as residual: the device route,
         the step comes back as a CUDA tensor."""
         reg, info = np.ascontiguousarray(regularization, dtype=np.float64).copy(), np.zeros(4)
         if reg.size != 3:
@@ -1005,7 +1006,40 @@ class SparseKKT(_Handle):
             rc = self._L.calipso_hip_sparse_kkt_search_direction(self._h, _pd(r), _pd(step), _pd(reg), _pd(info))
         self.regularization = tuple(float(v) for v in reg)      # (also after an error: where the inertia correction stopped)
         self._check(rc, "search_direction!")
-        return step, self.regularization, dict(factorizations=int(info[0]), refinement_rounds=int(info[1]), residual_norm=float(info[2])), rc
+        return step, self.regularization, dict(factorizations=int(info[0]), refinement_rounds=int(info[1]), residual_norm=float(info[2]),
+                                               fallback_iterations=int(info[3])), rc
+
+    def solve_nonsymmetric(self, residual):
+        """search_direction_nonsymmetric! for this handle: `H \\ residual` by restarted right-preconditioned GMRES with the current factorisation
+        (csrc/sparse_krylov.hip), whatever the option krylov_fallback says.  Returns the step; fallback_info() says whether it converged.  A CUDA tensor / device
+        pointer as residual: the device route, the step comes back as a CUDA tensor."""
+        if self._is_device(residual):
+            import torch
+            step = torch.empty(self.N, dtype=torch.float64, device=torch.device("cuda", self.device))
+            rp = self._device_pointer(residual, "residual", self.N)
+            self._check(self._L.calipso_hip_sparse_kkt_solve_nonsymmetric_device(self._h, rp, C.c_void_p(step.data_ptr())), "sparse_kkt_solve_nonsymmetric_device")
+            return step
+        r = np.ascontiguousarray(residual, dtype=np.float64).reshape(-1)
+        if r.size != self.N:
+            raise CalipsoHipError("SparseKKT.solve_nonsymmetric: the residual has %d entries, N = %d" % (r.size, self.N))
+        step = np.zeros(self.N)
+        self._check(self._L.calipso_hip_sparse_kkt_solve_nonsymmetric(self._h, _pd(r), _pd(step)), "sparse_kkt_solve_nonsymmetric")
+        return step
+
+    FALLBACK_INFO = ("taken", "iterations", "cycles", "residual_norm", "converged", "device_ms", "launches", "solve_fallbacks", "solve_iterations",
+                     "solve_most_iterations", "solve_unconverged", "workspace_bytes")
+
+    def fallback_info(self):
+        """the `H \\ residual` fallback (options krylov_fallback, krylov_restart, krylov_max_cycles): of the last search_direction / solve_nonsymmetric taken,
+        iterations, cycles, residual_norm (the true |residual - H step|_inf), converged, device_ms, launches (its own kernels); over the last solve
+        solve_fallbacks, solve_iterations, solve_most_iterations, solve_unconverged; workspace_bytes"""
+        out = np.zeros(12)
+        self._check(self._L.calipso_hip_sparse_kkt_fallback_info(self._h, _pd(out)), "sparse_kkt_fallback_info")
+        info = dict(zip(self.FALLBACK_INFO, (float(v) for v in out)))
+        for k in self.FALLBACK_INFO:
+            if k not in ("residual_norm", "device_ms"):
+                info[k] = int(info[k])
+        return info
 
     def timing(self):
         """device milliseconds of the last search_direction: dict(assemble, factorize, solve, refinement_solves, refinement_mul, wall); and of the last solve_columns /
@@ -1047,8 +1081,9 @@ class SparseKKT(_Handle):
             self._check(self._L.calipso_hip_sparse_kkt_initialize(self._h, _pd(self._host_vector(x0, "x0", self.nx))), "sparse_kkt_initialize")
 
     def solve(self):
-        """solve!: (status, info) with status 1 solved, 0 iteration caps, -102 a refinement failure without the option continue_after_refinement_failure (the point is
-        the last accepted iterate); the reference's error()s and refused arguments raise"""
+        """solve!: (status, info) with status 1 solved, 0 iteration caps, -102 a refinement failure without the options krylov_fallback (the `H \\ residual` fallback by
+        GMRES: fallback_info() counts them) or continue_after_refinement_failure (the point is the last accepted iterate); the reference's error()s and refused
+        arguments raise"""
         info = np.zeros(16)
         rc = self._L.calipso_hip_sparse_kkt_solve(self._h, _pd(info))
         out = dict(zip(self.SOLVE_INFO, (float(v) for v in info)))

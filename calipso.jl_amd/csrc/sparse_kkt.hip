@@ -12,6 +12,9 @@
 //   residual_symmetric!, recovery      residual.jl:53-101, search_direction.jl:59-101: one thread per row, one per second-order cone.
 //   driver (host)                      inertia_correction! (inertia.jl:30-80) and iterative_refinement! (iterative_refinement.jl:1-52) through ic_begin / ic_after /
 //                                      refine_next of step_decisions.hpp; every retry is one assemble + one calipso_hip_sparse_factorize_device.
+//   H \ residual (option krylov_fallback)  where the refinement fails (search_direction.jl:22): restarted right-preconditioned GMRES on H with solve_symmetric as
+//                                      preconditioner, gmres() below over the kernels of sparse_krylov.hip and the host logic of sparse_krylov.hpp; also the entry
+//                                      calipso_hip_sparse_kkt_solve_nonsymmetric.
 // Every kernel runs on the sparse handle's stream.  Gathers only: no atomics on values, a fixed summation order, results reproducible bit for bit.
 #include <chrono>
 #include <cmath>
@@ -338,14 +341,97 @@ void enqueue_mul(KH* s, const double* v, const Sink& sink) {
     if (s->d.ne + s->d.nc > 0) hipLaunchKernelGGL(k_kkt_mul_local, dim3(blocks((long long)s->d.ne + 2ll * s->d.nc)), dim3(KT), 0, s->st, s->d, s->sc.ep, s->sc.ed, v, sink);
 }
 // err = res - H step and its infinity norm: one double comes back
-int residual_error(KH* s, const double* res, const double* step, double* norm) {
+int residual_error(KH* s, const double* res, const double* step, double* norm, double* ms) {
     KK(hipEventRecord(s->ev[0], s->st));
     KK(hipMemsetAsync(s->norm, 0, sizeof(double), s->st));
     enqueue_mul(s, step, Sink{nullptr, res, s->err, reinterpret_cast<unsigned long long*>(s->norm)});
     KK(hipEventRecord(s->ev[1], s->st));
     KK(hipMemcpyAsync(norm, s->norm, sizeof(double), hipMemcpyDeviceToHost, s->st));
     KK(hipStreamSynchronize(s->st));
-    float t = 0.f; KK(hipEventElapsedTime(&t, s->ev[0], s->ev[1])); s->ms[4] += t;
+    float t = 0.f; KK(hipEventElapsedTime(&t, s->ev[0], s->ev[1])); *ms += t;
+    return CALIPSO_OK;
+}
+
+// ---- `H \ residual` (search_direction.jl:22, search_direction_nonsymmetric!) by restarted right-preconditioned GMRES: H the unreduced matrix at the regularisation
+// of the last assemble, M = solve_symmetric with the current factorisation, started from zero.  V and Z = M V are kept, so a cycle ends with x += Z y and no further
+// solve; one read-back per iteration (the Hessenberg column, |w|, the cycle's |r0|), one per cycle (the true |res - H x|_inf of residual_error).  x is built in
+// s->corr and copied into `step` only where everything stayed finite: otherwise `step` is left as it was.  Kernels: sparse_krylov.hip; decisions: sparse_krylov.hpp
+namespace kry = calipso::sparse_krylov;
+
+int krylov_reserve(KH* s, const kry::Layout& lay) {
+    if (!s->kry_ev[0]) { KK(hipEventCreate(&s->kry_ev[0])); KK(hipEventCreate(&s->kry_ev[1])); }
+    if ((size_t)lay.doubles <= s->kry_cap) return CALIPSO_OK;
+    KK(hipStreamSynchronize(s->st));
+    if (s->kry_ws) { (void)hipFree(s->kry_ws); s->kry_ws = nullptr; s->kry_cap = 0; }
+    KK(hipMalloc((void**)&s->kry_ws, sizeof(double) * (size_t)lay.doubles));
+    KK(hipMemsetAsync(s->kry_ws, 0, sizeof(double) * (size_t)lay.doubles, s->st));      // (on the handle's stream: ordered before the kernels that write here)
+    s->kry_cap = (size_t)lay.doubles;
+    return CALIPSO_OK;
+}
+
+int gmres(KH* s, const double* res, double* step) {
+    kry::FallbackReport& fr = s->fallback;
+    const kry::Layout lay = kry::layout(s->d.N, s->kry.restart);
+    { const int rc = krylov_reserve(s, lay); if (rc < 0) return rc; }
+    double* const ws = s->kry_ws;
+    double* const V = ws + lay.off_V; double* const Z = ws + lay.off_Z; double* const x = s->corr;
+    const size_t N = (size_t)s->d.N, bytes = sizeof(double) * N;
+    const double tolerance = s->opt.iterative_refinement_tolerance;
+    int iterations = 0, cycles = 0, launches = 0;
+    double true_norm = 0.0, unused_ms = 0.0;
+    bool converged = false, finite = true;
+    fr.v[kry::FI_TAKEN] = 1.0;
+    KK(hipEventRecord(s->kry_ev[0], s->st));
+    KK(hipMemsetAsync(x, 0, bytes, s->st));
+    const double* r0 = res;
+    for (;;) {
+        krylov_enqueue_update(s->st, lay, ws, 0, r0, V, false, true);                       // v0 = r0 / |r0|_2
+        krylov_enqueue_norm_scale(s->st, lay, ws, kry::COEF_BETA, V);
+        launches += 3;
+        kry::Cycle cycle;
+        kry::ColumnVerdict verdict = kry::COLUMN_CONTINUE;
+        double coef[kry::COEF_DOUBLES];
+        for (int j = 0; verdict == kry::COLUMN_CONTINUE; ++j) {
+            double* const w = V + (size_t)(j + 1) * N;
+            int rc = solve_symmetric(s, V + (size_t)j * N, Z + (size_t)j * N, &unused_ms);   // z_j = M v_j
+            if (rc < 0) return rc;
+            enqueue_mul(s, Z + (size_t)j * N, Sink{w, nullptr, nullptr, nullptr});            // w = H z_j (every row of w is written)
+            for (int pass = 0; pass < 2; ++pass) {                                           // classical Gram-Schmidt, twice
+                krylov_enqueue_dots(s->st, lay, ws, j + 1, w);
+                krylov_enqueue_update(s->st, lay, ws, j + 1, w, w, pass == 1, pass == 1);
+            }
+            krylov_enqueue_norm_scale(s->st, lay, ws, kry::COEF_NORM, w);                     // v_{j+1} = w / |w|_2
+            launches += 6;
+            KK(hipMemcpyAsync(coef, ws + lay.off_coef, sizeof(coef), hipMemcpyDeviceToHost, s->st));
+            KK(hipStreamSynchronize(s->st));
+            if (j == 0) {
+                const double beta = coef[kry::COEF_BETA];
+                if (!std::isfinite(beta)) { verdict = kry::COLUMN_NONFINITE; break; }
+                cycle.begin(s->kry.restart, beta);
+                if (beta == 0.0) { verdict = kry::COLUMN_BREAKDOWN; break; }                  // x is exact already
+            }
+            verdict = cycle.push(coef, coef[kry::COEF_NORM], tolerance);
+            iterations += 1;
+        }
+        double y[kry::RESTART_MAX];
+        if (verdict == kry::COLUMN_NONFINITE || !cycle.solve(y)) { finite = false; break; }
+        if (cycle.j > 0) { krylov_enqueue_combine(s->st, lay, ws, cycle.j, y, x); launches += 1; }
+        cycles += 1;
+        { const int rc = residual_error(s, res, x, &true_norm, &unused_ms); if (rc < 0) return rc; }      // s->err = res - H x
+        const kry::CycleVerdict next = kry::after_cycle(true_norm, tolerance, cycles, s->kry.max_cycles);
+        if (next == kry::CYCLE_NONFINITE) { finite = false; break; }
+        if (next == kry::CYCLE_CONVERGED) { converged = true; break; }
+        if (next == kry::CYCLE_UNCONVERGED) break;
+        r0 = s->err;
+    }
+    if (finite) KK(hipMemcpyAsync(step, x, bytes, hipMemcpyDeviceToDevice, s->st));
+    KK(hipEventRecord(s->kry_ev[1], s->st));
+    KK(hipStreamSynchronize(s->st));
+    KK(hipGetLastError());
+    float ms = 0.f; KK(hipEventElapsedTime(&ms, s->kry_ev[0], s->kry_ev[1]));
+    fr.step_taken = finite;
+    fr.v[kry::FI_ITERATIONS] = iterations; fr.v[kry::FI_CYCLES] = cycles; fr.v[kry::FI_NORM] = true_norm; fr.v[kry::FI_CONVERGED] = converged ? 1.0 : 0.0;
+    fr.v[kry::FI_DEVICE_MS] = ms; fr.v[kry::FI_LAUNCHES] = launches; fr.v[kry::FI_WORKSPACE_BYTES] = (double)(sizeof(double) * s->kry_cap);
     return CALIPSO_OK;
 }
 
@@ -356,9 +442,10 @@ int search_direction(KH* s, const double* res, double* step, double regularizati
     const Options& o = s->opt;
     Scalars& sc = s->sc;
     sc.ep_last = regularization[1];
+    s->fallback.begin_call();
     const auto leave = [&](int rc, double nfact, double rounds, double norm) {
         regularization[0] = sc.ep; regularization[1] = sc.ep_last; regularization[2] = sc.ed;
-        if (info) { info[0] = nfact; info[1] = rounds; info[2] = norm; info[3] = 0.0; }
+        if (info) { info[0] = nfact; info[1] = rounds; info[2] = norm; info[3] = s->fallback.v[kry::FI_ITERATIONS]; }
         s->ms[5] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
         return rc;
     };
@@ -380,16 +467,23 @@ int search_direction(KH* s, const double* res, double* step, double regularizati
     if (!o.iterative_refinement) return leave(CALIPSO_OK, nfact, 0, 0.0);
     // iterative_refinement! (iterative_refinement.jl:1-52)
     double norm = 0.0;
-    if ((rc = residual_error(s, res, step, &norm)) < 0) return leave(rc, nfact, 0, 0.0);
+    if ((rc = residual_error(s, res, step, &norm, &s->ms[4])) < 0) return leave(rc, nfact, 0, 0.0);
     const double norm0 = norm;
     int it = 0, status = CALIPSO_OK;
     for (;;) {
         const calipso::RefineVerdict v = calipso::refine_next(o, norm, norm0, &it);
         if (v == calipso::REFINE_DONE) break;
-        if (v == calipso::REFINE_FAILED) { status = CALIPSO_WARN_REFINEMENT; break; }      // the reference goes on to `H \ residual` (search_direction.jl:22): not here
+        if (v == calipso::REFINE_FAILED) {                                                   // the reference goes on to `H \ residual` (search_direction.jl:22)
+            status = CALIPSO_WARN_REFINEMENT;
+            if (s->kry.fallback) {                                                           // ... here: by GMRES, where the option asks for it
+                if ((rc = gmres(s, res, step)) < 0) return leave(rc, nfact, it, norm);
+                if (s->fallback.step_taken) norm = s->fallback.v[kry::FI_NORM];
+            }
+            break;
+        }
         if ((rc = solve_symmetric(s, s->err, s->corr, &s->ms[3])) < 0) return leave(rc, nfact, it, norm);
         hipLaunchKernelGGL(k_kkt_add,dim3(blocks(s->d.N)), dim3(KT), 0, s->st, s->d.N, step, s->corr);
-        if ((rc = residual_error(s, res, step, &norm)) < 0) return leave(rc, nfact, it, norm);
+        if ((rc = residual_error(s, res, step, &norm, &s->ms[4])) < 0) return leave(rc, nfact, it, norm);
         ++it;
     }
     KK(hipGetLastError());
@@ -422,7 +516,9 @@ int32_t calipso_hip_sparse_kkt_destroy(calipso_hip_sparse_kkt* s) {
     solve_state_release(s);
     diff_state_release(s);
     for (void* p : s->dev) if (p) (void)hipFree(p);
+    if (s->kry_ws) (void)hipFree(s->kry_ws);
     for (hipEvent_t e : s->ev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : s->kry_ev) if (e) (void)hipEventDestroy(e);
     if (s->sp) (void)calipso_hip_sparse_destroy(s->sp);
     delete s;
     return CALIPSO_OK;
@@ -504,6 +600,12 @@ int32_t calipso_hip_sparse_kkt_set_option(calipso_hip_sparse_kkt* s, const char*
     if (!s || !name) return CALIPSO_ERR_ARGUMENT;
     if (calipso::set_search_direction_option(s->opt, name, value)) return CALIPSO_OK;
     if (std::string(name) == "central_path") { s->sc.kappa = value; return CALIPSO_OK; }      // (the solver's scalar, not an option: IC-2 reads it, inertia.jl:44)
+    {                                                                                          // krylov_fallback, krylov_restart, krylov_max_cycles (sparse_krylov.hpp)
+        std::string why;
+        const int rc = calipso::sparse_krylov::set_option(s->kry, name, value, &why);
+        if (rc < 0) return fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_sparse_kkt_set_option: " + why);
+        if (rc > 0) return CALIPSO_OK;
+    }
     { const int rc = solve_set_option(s, name, value); if (rc != 0) return rc < 0 ? rc : CALIPSO_OK; }      // what solve! reads besides (sparse_solve.hip)
     { const int rc = diff_set_option(s, name, value); if (rc != 0) return rc < 0 ? rc : CALIPSO_OK; }       // differentiate_refinement (sparse_differentiate.hip)
     return fail(s, CALIPSO_ERR_ARGUMENT, std::string("calipso_hip_sparse_kkt_set_option: unknown option ") + name);
@@ -566,6 +668,42 @@ int32_t calipso_hip_sparse_kkt_solve_symmetric(calipso_hip_sparse_kkt* s, const 
     KK(hipMemcpyAsync(step, s->step, bytes, hipMemcpyDeviceToHost, s->st));
     KK(hipStreamSynchronize(s->st));
     KK(hipGetLastError());
+    return CALIPSO_OK;
+}
+
+// search_direction_nonsymmetric! for this handle: `H \ residual` by GMRES with the current factorisation, whatever the option krylov_fallback says
+static int32_t solve_nonsymmetric(KH* s, const double* res, double* step) {
+    s->fallback.begin_call();
+    KK(hipMemsetAsync(step, 0, sizeof(double) * (size_t)s->d.N, s->st));      // (a step that is not finite is not taken: zeros then)
+    const int rc = gmres(s, res, step);
+    if (rc < 0) return rc;
+    return s->fallback.v[calipso::sparse_krylov::FI_CONVERGED] != 0.0 ? CALIPSO_OK : CALIPSO_WARN_REFINEMENT;
+}
+int32_t calipso_hip_sparse_kkt_solve_nonsymmetric(calipso_hip_sparse_kkt* s, const double* residual, double* step) {
+    if (!s || !residual || !step) return CALIPSO_ERR_ARGUMENT;
+    if (!s->factored) return fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_sparse_kkt_solve_nonsymmetric: factorize first");
+    KK(hipSetDevice(s->device));
+    const size_t bytes = sizeof(double) * (size_t)s->d.N;
+    KK(hipMemcpyAsync(s->res, residual, bytes, hipMemcpyHostToDevice, s->st));
+    const int rc = solve_nonsymmetric(s, s->res, s->step);
+    if (rc < 0) return rc;
+    KK(hipMemcpyAsync(step, s->step, bytes, hipMemcpyDeviceToHost, s->st));
+    KK(hipStreamSynchronize(s->st));
+    KK(hipGetLastError());
+    return rc;
+}
+int32_t calipso_hip_sparse_kkt_solve_nonsymmetric_device(calipso_hip_sparse_kkt* s, const double* residual, double* step) {
+    if (!s || !residual || !step) return CALIPSO_ERR_ARGUMENT;
+    if (!s->factored) return fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_sparse_kkt_solve_nonsymmetric_device: factorize first");
+    KK(hipSetDevice(s->device));
+    static const char* const entry = "calipso_hip_sparse_kkt_solve_nonsymmetric_device";
+    DEVPTR(entry, residual); DEVPTR(entry, step);
+    return solve_nonsymmetric(s, residual, step);
+}
+int32_t calipso_hip_sparse_kkt_fallback_info(calipso_hip_sparse_kkt* s, double out[12]) {
+    if (!s || !out) return CALIPSO_ERR_ARGUMENT;
+    static_assert(calipso::sparse_krylov::FI_COUNT == 12, "out[12]");
+    std::copy(s->fallback.v, s->fallback.v + 12, out);
     return CALIPSO_OK;
 }
 

@@ -7,6 +7,7 @@
 
 #include "internal.hpp"
 #include "sparse_kkt.hpp"                  // the analysis: plain host C++
+#include "sparse_krylov.hpp"               // the `H \ residual` fallback's options, workspace layout and Hessenberg cycle: plain host C++
 
 namespace calipso {
 namespace sparse_kkt {
@@ -59,6 +60,11 @@ struct calipso_hip_sparse_kkt {
     bool slacks_kept = false;                                // false: the differentiate slacks are the resident point's own
     bool differentiate_refinement = false;
     bool qp_attached = false;                                // q, b, hvec resident (qp_attach): what the data gradients ask for
+    calipso::sparse_krylov::KrylovOptions kry;               // krylov_fallback, krylov_restart, krylov_max_cycles
+    calipso::sparse_krylov::FallbackReport fallback;         // what calipso_hip_sparse_kkt_fallback_info reports
+    double* kry_ws = nullptr;                                // the fallback's workspace (sparse_krylov.hpp: Layout), reserved on the first fallback and kept
+    size_t kry_cap = 0;                                      // ... its doubles
+    hipEvent_t kry_ev[2] = {nullptr, nullptr};
 };
 
 namespace calipso {
@@ -77,6 +83,11 @@ int kkt_sparse_failed(calipso_hip_sparse_kkt* s, int rc, const char* what);
 void solve_state_release(calipso_hip_sparse_kkt* s);                                                        // (before the handle's device memory is freed)
 int solve_set_option(calipso_hip_sparse_kkt* s, const char* name, double value);                            // 1 taken, 0 unknown, < 0 refused
 void diff_keep_slacks(calipso_hip_sparse_kkt* s);                                                           // enqueue: dslack <- the resident s, t (no host wait)
+// sparse_krylov.hip, for sparse_kkt.hip: the fallback's vector kernels on the workspace `ws` laid out by `l` (enqueues, no host wait)
+void krylov_enqueue_dots(hipStream_t st, const sparse_krylov::Layout& l, double* ws, int nv, const double* w);                  // partials of V[:, 0..nv)' w
+void krylov_enqueue_update(hipStream_t st, const sparse_krylov::Layout& l, double* ws, int nv, const double* src, double* dst, bool accumulate, bool norm);
+void krylov_enqueue_norm_scale(hipStream_t st, const sparse_krylov::Layout& l, double* ws, int slot, double* v);                // coef[slot] = |v|_2, v <- v / |v|_2
+void krylov_enqueue_combine(hipStream_t st, const sparse_krylov::Layout& l, double* ws, int nv, const double* y, double* x);     // x <- x + Z[:, 0..nv) y
 // sparse_differentiate.hip, for sparse_kkt.hip
 void diff_state_release(calipso_hip_sparse_kkt* s);
 int diff_set_option(calipso_hip_sparse_kkt* s, const char* name, double value);                             // 1 taken, 0 unknown, < 0 refused

@@ -581,6 +581,7 @@ int solve(KH* s, double info[16]) {
     const Options& o = s->opt; Scalars& sc = s->sc; const KktDev& d = s->d;
     const double* pub = t->hpub;
     t->vector_ms = 0.0; t->waits = 0; t->trace_rows = 0; t->trace_total = 0; t->group_open = false;
+    s->fallback.begin_solve();
     i64 total_iterations = 1, outer = 0, accepted = 0, nfact = 0, max_rounds = 0, refine_fail = 0, trials = 0;
     int worst = 0;
     double sd_ms = 0.0;
@@ -619,11 +620,14 @@ int solve(KH* s, double info[16]) {
             rc = kkt_search_direction(s, s->res, s->step, reg, sdinfo);                       // :187
             nfact += (i64)sdinfo[0]; max_rounds = std::max(max_rounds, (i64)sdinfo[1]);
             for (int k = 0; k < 5; ++k) sd_ms += s->ms[k];
+            sd_ms += s->fallback.v[calipso::sparse_krylov::FI_DEVICE_MS];                     // (0 where no fallback ran: its events are its own, not the eight slots')
             if (rc < 0) return leave(rc);
             if (rc == CALIPSO_WARN_REFINEMENT) {
                 refine_fail += 1; worst = std::max(worst, rc);
-                // the reference goes on to `H \ residual` (search_direction.jl:22): no such fallback on this handle
-                if (!s->continue_after_refinement_failure) {
+                // the reference goes on to `H \ residual` (search_direction.jl:22): with the option krylov_fallback search_direction did, by GMRES, and its step
+                // (converged or not, but finite) is taken; else there is no such fallback on this handle
+                if (s->fallback.step_taken) s->fallback.count_in_solve();
+                else if (!s->continue_after_refinement_failure) {
                     kkt_fail(s, -100 - CALIPSO_WARN_REFINEMENT, "calipso_hip_sparse_kkt_solve: iterative refinement failed (iterative_refinement.jl:50) and this handle has no `H \\ residual` fallback; the point is the last accepted iterate");
                     return leave(-100 - CALIPSO_WARN_REFINEMENT);
                 }

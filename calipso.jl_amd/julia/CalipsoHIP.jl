@@ -490,6 +490,12 @@ function sparse_search_direction_device!(k::SparseKKT, residual::Ptr{Cvoid}, ste
                          k.handle, residual, step, regularization, info), k, "search_direction_device!")
     return rc, info
 end
+# search_direction_nonsymmetric! for this handle: `H \ residual` by preconditioned GMRES with the current factorisation (csrc/sparse_krylov.hip)
+solve_nonsymmetric!(k::SparseKKT, step::Vector{Float64}, residual::Vector{Float64}) =
+    kkt_check(ccall((:calipso_hip_sparse_kkt_solve_nonsymmetric, lib), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), k.handle, residual, step), k, "solve_nonsymmetric")
+solve_nonsymmetric_device!(k::SparseKKT, step::Ptr{Cvoid}, residual::Ptr{Cvoid}) =
+    kkt_check(ccall((:calipso_hip_sparse_kkt_solve_nonsymmetric_device, lib), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), k.handle, residual, step), k, "solve_nonsymmetric_device")
+kkt_fallback_info(k::SparseKKT) = (out = zeros(12); kkt_check(ccall((:calipso_hip_sparse_kkt_fallback_info, lib), Int32, (Ptr{Cvoid}, Ptr{Float64}), k.handle, out), k, "fallback_info"); out)
 kkt_timing(k::SparseKKT) = (ms = zeros(8); kkt_check(ccall((:calipso_hip_sparse_kkt_timing, lib), Int32, (Ptr{Cvoid}, Ptr{Float64}), k.handle, ms), k, "timing"); ms)
 
 # ---- solve! on the same handle (csrc/sparse_solve.hip): the sparse conic QP  min c x'Px + q'x  s.t.  Ax - b = 0,  h - Gx in K  with Lxx = c (P + P'), gx = A, hx = -G ----

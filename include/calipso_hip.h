@@ -542,10 +542,25 @@ int32_t calipso_hip_sparse_timing(calipso_hip_sparse*, double ms[2]);
  *   search_direction  search_direction! whole: inertia_correction! (inertia.jl:30-80; every retry one assemble + one factorisation), search_direction_symmetric!,
  *                   iterative_refinement! (iterative_refinement.jl:1-52; a round reads back one double).  regularization = [ep, ep_last, ed], in and out:
  *                   ep_last is what the caller carries from call to call (primal_regularization_last).  info = [factorisations, refinement rounds,
- *                   |residual - H step|_inf at exit, 0].  (_device: residual and step are device pointers.)  Returns CALIPSO_OK, CALIPSO_ERR_INERTIA,
- *                   CALIPSO_ERR_ARGUMENT, CALIPSO_ERR_HIP, or CALIPSO_WARN_REFINEMENT: where the reference's refinement fails it goes on to `H \ residual`
- *                   (search_direction.jl:22) — there is NO such fallback here; the call returns the warning with the last refined step in place, and the handle
- *                   stays usable.
+ *                   |residual - H step|_inf at exit, GMRES iterations of the fallback].  (_device: residual and step are device pointers.)  Returns CALIPSO_OK,
+ *                   CALIPSO_ERR_INERTIA, CALIPSO_ERR_ARGUMENT, CALIPSO_ERR_HIP, or CALIPSO_WARN_REFINEMENT: where the reference's refinement fails it goes on to
+ *                   `H \ residual` (search_direction.jl:22).  By default there is NO such fallback here: the call returns the warning with the last refined step in
+ *                   place, and the handle stays usable.  With the option krylov_fallback = 1 the call goes on to solve_nonsymmetric below and still returns the
+ *                   warning, as the dense handle does; a fallback that met a non-finite number leaves the last refined step in place, exactly as without the option.
+ *   solve_nonsymmetric  search_direction_nonsymmetric! for this handle, `H \ residual` without a pivoted LU (csrc/sparse_krylov.hip, host logic csrc/sparse_krylov.hpp):
+ *                   restarted right-preconditioned GMRES on the unreduced H at the regularisation of the last assemble, preconditioned by solve_symmetric with the
+ *                   CURRENT factorisation, started from zero, whatever krylov_fallback says.  V and Z = M V are kept, so a cycle ends with x += Z y; classical
+ *                   Gram-Schmidt applied twice, two launches per pass whatever the iteration; one read-back per iteration.  A cycle ends when the estimate |g_j+1|
+ *                   (a 2-norm, which bounds the infinity norm) is at or below iterative_refinement_tolerance, at krylov_restart columns, or on an exact breakdown;
+ *                   then the TRUE |residual - H step|_inf decides: stop, restart from that residual, or — after krylov_max_cycles — leave the step in place
+ *                   unconverged (the reference does not inspect its LU's answer either).  Sums are reduced in a fixed order: a call repeats bit for bit.  Returns
+ *                   CALIPSO_OK converged, CALIPSO_WARN_REFINEMENT unconverged (not finite: a zero step); refusals as solve_symmetric.  (_device: device pointers.)
+ *   fallback_info   out[12]: of the last search_direction / solve_nonsymmetric [0] fallback taken, [1] GMRES iterations, [2] cycles, [3] the final true
+ *                   |residual - H step|_inf, [4] converged, [5] device ms (HIP events), [6] launches of the fallback's own kernels; accumulated over the last solve
+ *                   [7] fallbacks, [8] their iterations, [9] most iterations of one, [10] unconverged ones; [11] bytes of the workspace ((2 restart + 1) N doubles
+ *                   and partials, reserved on the first fallback and kept)
+ *   set_option      additionally krylov_fallback (0 / 1, default 0), krylov_restart (1 .. 32, default 16), krylov_max_cycles (1 .. 16, default 4); any other value is
+ *                   CALIPSO_ERR_ARGUMENT
  *   timing          ms[8] of the last search_direction, HIP events on the handle's stream: [assembles, factorisations, first solve, refinement solves,
  *                   H v + norm of all rounds, wall-clock of the call, 0, 0]; the last two slots belong to the differentiate entries below: of the last
  *                   solve_columns / differentiate / differentiate_adjoint, [6] its first pre + multi-column solve + post, [7] its correction rounds with their
@@ -568,6 +583,9 @@ int32_t calipso_hip_sparse_kkt_solve_symmetric(calipso_hip_sparse_kkt*, const do
 int32_t calipso_hip_sparse_kkt_search_direction(calipso_hip_sparse_kkt*, const double* residual, double* step, double regularization[3], double info[4]);
 int32_t calipso_hip_sparse_kkt_search_direction_device(calipso_hip_sparse_kkt*, const double* residual, double* step, double regularization[3], double info[4]);
 int32_t calipso_hip_sparse_kkt_timing(calipso_hip_sparse_kkt*, double ms[8]);
+int32_t calipso_hip_sparse_kkt_solve_nonsymmetric(calipso_hip_sparse_kkt*, const double* residual, double* step);
+int32_t calipso_hip_sparse_kkt_solve_nonsymmetric_device(calipso_hip_sparse_kkt*, const double* residual, double* step);
+int32_t calipso_hip_sparse_kkt_fallback_info(calipso_hip_sparse_kkt*, double out[12]);
 
 /* ---- solve! on sparse problem data resident on the device (csrc/sparse_solve.hip; host pieces: csrc/sparse_solve.hpp) --------------------------------------
  * The vector half of a sparse solve! on the same handle, and the whole solve! (src/solver/solve.jl:8-377) for the problem class that needs no user code, the
@@ -581,8 +599,10 @@ int32_t calipso_hip_sparse_kkt_timing(calipso_hip_sparse_kkt*, double ms[8]);
  *                   decisions are those of csrc/step_decisions.hpp; the linear algebra is search_direction above, on resident vectors; primal_regularization_last
  *                   starts at 0 in every solve.  Returns 1 solved, 0 iteration caps, CALIPSO_ERR_INERTIA, CALIPSO_ERR_CONE_SEARCH, CALIPSO_ERR_ARGUMENT (nothing
  *                   attached, no point), CALIPSO_ERR_HIP — and -100 - CALIPSO_WARN_REFINEMENT where the refinement fails and the reference goes on to `H \ residual`
- *                   (search_direction.jl:22): the handle has no such fallback, the point is the last accepted iterate and the handle stays usable.  With the option
- *                   continue_after_refinement_failure = 1 the step search_direction left (the last refined one) is taken, the event counted, and the solve goes on.
+ *                   (search_direction.jl:22): by default the handle has no such fallback, the point is the last accepted iterate and the handle stays usable.  With
+ *                   the option continue_after_refinement_failure = 1 the step search_direction left (the last refined one) is taken, the event counted, and the solve
+ *                   goes on.  With the option krylov_fallback = 1 search_direction takes the GMRES fallback above; its step, converged or unconverged but finite, is
+ *                   taken, the event counted in the refinement failures and the worst warning as before, and the solve goes on (fallback_info counts them).
  *                   info[16] = total_iterations, outer iterations, accepted iterates, factorisations, most refinement rounds of a step, refinement failures, worst
  *                   warning (CALIPSO_WARN_LINE_SEARCH as calipso_hip_solve reports it), host waits outside search_direction, line-search trials beyond the first
  *                   candidates, central_path and penalty at exit, primal_regularization_last, device ms of the vector half, device ms inside search_direction,

@@ -867,7 +867,9 @@ class SparseKKT(_Handle):
     with the option krylov_fallback = 1 it goes on to solve_nonsymmetric (preconditioned GMRES, csrc/sparse_krylov.hip) and still returns 2 (fallback_info()).
     With attach_qp the same handle runs the vector half of solve! and a whole solve! of the sparse conic QP (csrc/sparse_solve.hip): initialize, solve, and the steps of an
     iteration one by one — and differentiate! in both directions (csrc/sparse_differentiate.hip): solve_columns, differentiate, vjp with the data gradients on the
-    stored patterns."""
+    stored patterns.  With set_evaluator instead of attach_qp the same entries solve NONLINEAR problems: a device evaluator (calipso_device_sparse_eval_fn) writes fx, g,
+    h, the objective and the non-zeros of Lxx, gx, hx into the handle's resident arrays (set_parameters, evaluate; codegen.TrajectoryProblem.sparse_solver makes such a
+    handle from stage functions)."""
     _last_error, _destroy = "calipso_hip_sparse_kkt_last_error", "calipso_hip_sparse_kkt_destroy"
     _message = _Handle._STATUS_MESSAGE
 
@@ -1124,6 +1126,26 @@ class SparseKKT(_Handle):
     def outer_update(self):
         self._check(self._L.calipso_hip_sparse_kkt_outer_update(self._h), "sparse_kkt_outer_update")
 
+    # ---- nonlinear problems: a device evaluator instead of the QP (include/calipso_hip.h, "solve! on sparse data with an evaluator") ------------------------------
+    def set_evaluator(self, fn_ptr, user=None, num_parameters=0):
+        """a calipso_device_sparse_eval_fn (a ctypes function pointer or c_void_p from a loaded library) and its user object; replaces attach_qp, and attach_qp
+        replaces it; None removes it.  The caller keeps the library and the user object alive while the handle may call them"""
+        fn = None if fn_ptr is None else C.cast(fn_ptr, C.c_void_p)
+        self._check(self._L.calipso_hip_sparse_kkt_set_evaluator(self._h, fn, user, int(num_parameters)), "sparse_kkt_set_evaluator")
+        self.num_parameters = int(num_parameters) if fn_ptr is not None else 0
+
+    def set_parameters(self, theta):
+        """theta of the evaluator (num_parameters entries), resident on the handle: a host array, or a CUDA tensor / device pointer"""
+        count = getattr(self, "num_parameters", 0)
+        if self._is_device(theta):
+            self._check(self._L.calipso_hip_sparse_kkt_set_parameters_device(self._h, self._device_pointer(theta, "theta", count)), "sparse_kkt_set_parameters_device")
+        else:
+            self._check(self._L.calipso_hip_sparse_kkt_set_parameters(self._h, _opt(self._host_vector(theta, "theta", count))), "sparse_kkt_set_parameters")
+
+    def evaluate(self, flags, which=0):
+        """the evaluator at the solution (which = 0) or at the candidate (1), synchronised: CALIPSO_EVAL_* bits without the dual gradients and the parameter Jacobians"""
+        self._check(self._L.calipso_hip_sparse_kkt_evaluate(self._h, int(which), int(flags)), "sparse_kkt_evaluate")
+
     # ---- differentiate! on the same handle (include/calipso_hip.h, "differentiate! on sparse problem data"; csrc/sparse_differentiate.hip) -------------------
     GRADIENTS = "LqgbHh"      # the data gradients of vjp by letter: Lxx, q, gx, b, hx, hvec — the matrices as the values on their stored patterns
     _QP_LETTERS = dict(P="L", A="g", G="H")      # a handle from SparseConicQP also answers for P, A, G
@@ -1246,6 +1268,9 @@ class SparseKKT(_Handle):
     def _vector_length(self, name):
         if name == "differentiate_slacks":      # (not a vector of the reference's solver: the s, then the t that differentiate! forms the cone blocks at)
             return 2 * self.nc
+        extra = dict(objective=1, lagrangian_hessian=self.nnz[0], equality_jacobian_variables=self.nnz[1], cone_jacobian_variables=self.nnz[2])
+        if name in extra:                       # the evaluator's objective at the solution; the three resident non-zero arrays on their stored patterns
+            return extra[name]
         return getattr(self, self.VECTORS[name]) if name in self.VECTORS else 0
 
     def get(self, name):

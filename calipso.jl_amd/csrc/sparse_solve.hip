@@ -8,6 +8,11 @@
 //   QP evaluation                      evaluate! (evaluate.jl:37-121) for this problem class is a gather over the row views of Lxx, gx, hx and the column views of gx, hx
 //                                      that the handle holds: qp_hessian_row / qp_equality_row / qp_cone_row / qp_dual_rows, at the solution or, on the fly, at a
 //                                      candidate.  The driver reaches evaluation through these alone.
+//   evaluated problems                 with a calipso_device_sparse_eval_fn (set_evaluator) the kernels that evaluate are instantiated a second time (EVAL = true): they
+//                                      READ fx, g, h and the objective the evaluator wrote instead of gathering; gx'y and hx'z are still gathered, from the resident
+//                                      non-zero arrays the evaluator wrote into.  The candidate splits in two kernels around the evaluator's call.  Every call is an
+//                                      enqueue on the handle's stream in front of the kernel that reads it (enqueue_evaluator): no host wait is added.  The QP
+//                                      instantiation (EVAL = false) is the code as it was, bit for bit.
 //   reductions                         every sum is two-stage in a fixed order: a thread adds its items in stride order, a workgroup its threads by a butterfly, and
 //                                      stores one partial per (quantity, workgroup) into the workspace; ONE small finishing kernel adds the partials in workgroup order,
 //                                      forms the scalars and writes them into the published block.  Maxima and the cone-search masks take the same route (masks are
@@ -47,6 +52,7 @@ struct SolveDev {
     double* ws; unsigned* wsm;                    // reduction workspace: doubles and mask words
     long long off_prologue, off_candidate, off_accept;
     double* pub; unsigned* pub_masks;             // the published block
+    const double* fobj;                           // the evaluator's objective: [0] at the solution, [1] at the candidate (evaluated mode only)
 };
 
 }  // namespace
@@ -64,6 +70,12 @@ struct calipso::sparse_kkt::SolveState {
     double vector_ms = 0.0;
     i64 waits = 0;
     std::vector<void*> own;                       // device memory outside the handle's list (the trace)
+    // the evaluated problem class: a user's evaluator instead of the QP's gathers
+    calipso_device_sparse_eval_fn eval_fn = nullptr;
+    void* eval_user = nullptr;
+    i64 eval_np = 0;
+    double *theta = nullptr, *fobj = nullptr;     // np parameters; the objective at the solution and at the candidate
+    std::vector<int64_t> pattern[6];              // host copies of the patterns, 1-based as given to create: Lxx, gx, hx (colptr, rowval)
 };
 
 namespace {
@@ -140,13 +152,15 @@ __device__ __forceinline__ void combine_partials(const double* __restrict__ ws, 
 }
 
 // ---- initialize! (initialize.jl:9-48): initialize_slacks! r <- g(x), s <- cone interior; initialize_duals! y, z <- 0, t <- cone interior ------------------------------
-__global__ __launch_bounds__(KT) void k_solve_init(const KktDev d, const SolveDev v) {
+// EVAL (here and below): false the QP, whose evaluate! is the gathers above; true a user's evaluator, which wrote fx, g, h and the objective before the kernel runs
+template <bool EVAL> __global__ __launch_bounds__(KT) void k_solve_init(const KktDev d, const SolveDev v) {
     for (long long it = (long long)blockIdx.x * KT + threadIdx.x; it < v.rows; it += (long long)v.grid * KT) {
         const int k = (int)it;
         if (k < d.nx) continue;
         if (k < d.nx + d.ne) {
             const int i = k - d.nx;
-            v.w[d.o_r + i] = qp_equality_row(d, v, i, [&](int j) { return v.w[j]; });
+            if constexpr (EVAL) v.w[d.o_r + i] = v.g[i];
+            else v.w[d.o_r + i] = qp_equality_row(d, v, i, [&](int j) { return v.w[j]; });
             v.w[d.o_y + i] = 0.0;
             continue;
         }
@@ -168,7 +182,7 @@ __global__ __launch_bounds__(KT) void k_solve_fill(int count, double* __restrict
 
 // ---- prologue of a step (solve.jl:100-135, 170-172): evaluate! at the solution, cone!(barrier, barrier_gradient, product, target), merit (merit.jl:2-15) and its
 // gradient (:17-31), residual! (residual.jl:1-51), constraint_violation! (constraint_violation.jl:1-13), the norms of optimality_error (optimality_error.jl:1-27) -----
-__global__ __launch_bounds__(KT) void k_solve_prologue(const KktDev d, const SolveDev v, double kappa) {
+template <bool EVAL> __global__ __launch_bounds__(KT) void k_solve_prologue(const KktDev d, const SolveDev v, double kappa) {
     double val[PP_COUNT];
 #pragma unroll
     for (int q = 0; q < PP_COUNT; ++q) val[q] = 0.0;
@@ -179,29 +193,35 @@ __global__ __launch_bounds__(KT) void k_solve_prologue(const KktDev d, const Sol
         const int kind = item_kind(v, it, &k, &lane, &nl);
         if (kind == 0) {
             if (k < d.nx) {
-                const double Lx = qp_hessian_row(d, k, [&](int j) { return w[j]; });
-                double gy, hz;
+                double Lx = 0.0, gy, hz;
+                if constexpr (!EVAL) Lx = qp_hessian_row(d, k, [&](int j) { return w[j]; });
                 qp_dual_rows(d, k, w + d.o_y, w + d.o_z, &gy, &hz);
-                const double fx = Lx + v.q[k];
+                double fx;
+                if constexpr (EVAL) fx = v.fx[k]; else fx = Lx + v.q[k];
                 const double r = (fx + gy) + hz;                                                            // residual.jl:10-14
-                v.fx[k] = fx; v.mgrad[k] = fx; v.res[k] = r;
-                val[PP_OBJECTIVE] += 0.5 * w[k] * Lx + v.q[k] * w[k];
+                if constexpr (!EVAL) v.fx[k] = fx;
+                v.mgrad[k] = fx; v.res[k] = r;
+                if constexpr (!EVAL) val[PP_OBJECTIVE] += 0.5 * w[k] * Lx + v.q[k] * w[k];
                 val[PP_RES_1] += rabs(r); val[PP_RES_N_INF] = fmax(val[PP_RES_N_INF], rabs(r));
             } else if (k < d.nx + d.ne) {
                 const int i = k - d.nx;
-                const double g = qp_equality_row(d, v, i, [&](int j) { return w[j]; });
+                double g;
+                if constexpr (EVAL) g = v.g[i]; else g = qp_equality_row(d, v, i, [&](int j) { return w[j]; });
                 const double r = w[d.o_r + i], y = w[d.o_y + i], lam = v.dual[i];
                 const double rr = lam + rho * r - y, ry = g - r;                                            // :17-19, :29-33
-                v.g[i] = g; v.res[d.o_r + i] = rr; v.res[d.o_y + i] = ry; v.mgrad[d.nx + i] = lam + rho * r;
+                if constexpr (!EVAL) v.g[i] = g;
+                v.res[d.o_r + i] = rr; v.res[d.o_y + i] = ry; v.mgrad[d.nx + i] = lam + rho * r;
                 val[PP_DUAL_DOT_R] += lam * r; val[PP_R_DOT_R] += r * r; val[PP_THETA] += rabs(g - r); val[PP_Y_1] += rabs(y);
                 val[PP_RES_1] += rabs(rr) + rabs(ry);
                 val[PP_RES_N_INF] = fmax(val[PP_RES_N_INF], rabs(rr)); val[PP_RES_Y_INF] = fmax(val[PP_RES_Y_INF], rabs(ry));
             } else {
                 const int c = k - d.nx - d.ne, ck = d.row_cone[c];
-                const double h = qp_cone_row(d, v, c, [&](int j) { return w[j]; });
+                double h;
+                if constexpr (EVAL) h = v.h[c]; else h = qp_cone_row(d, v, c, [&](int j) { return w[j]; });
                 const double sl = w[d.o_s + c], z = w[d.o_z + c], t = w[d.o_t + c];
                 const double rs = -z - t, rz = h - sl;                                                      // :22-26, :36-40
-                v.h[c] = h; v.res[d.o_s + c] = rs; v.res[d.o_z + c] = rz;
+                if constexpr (!EVAL) v.h[c] = h;
+                v.res[d.o_s + c] = rs; v.res[d.o_z + c] = rz;
                 val[PP_THETA] += rabs(h - sl); val[PP_Z_1] += rabs(z); val[PP_T_1] += rabs(t);
                 val[PP_RES_1] += rabs(rs) + rabs(rz);
                 val[PP_RES_N_INF] = fmax(val[PP_RES_N_INF], rabs(rs)); val[PP_RES_Z_INF] = fmax(val[PP_RES_Z_INF], rabs(rz));
@@ -232,12 +252,13 @@ __global__ __launch_bounds__(KT) void k_solve_prologue(const KktDev d, const Sol
     }
     store_partials<PP_COUNT, PP_FIRST_MAX>(val, v.ws, v.off_prologue, v.grid);
 }
-__global__ __launch_bounds__(64) void k_solve_prologue_finish(const KktDev d, const SolveDev v, double kappa) {
+template <bool EVAL> __global__ __launch_bounds__(64) void k_solve_prologue_finish(const KktDev d, const SolveDev v, double kappa) {
     __shared__ double tot[PP_COUNT];
     combine_partials<PP_COUNT, PP_FIRST_MAX>(v.ws, v.off_prologue, v.grid, tot);
     if (threadIdx.x != 0) return;
     double* pub = v.pub;
-    const double f = tot[PP_OBJECTIVE] + v.objective_constant;
+    double f;
+    if constexpr (EVAL) f = v.fobj[0]; else f = tot[PP_OBJECTIVE] + v.objective_constant;
     double M = 0.0;                                                                                         // merit.jl:2-15
     M += f;
     M += tot[PP_DUAL_DOT_R] + 0.5 * d.rho[0] * tot[PP_R_DOT_R];
@@ -356,11 +377,64 @@ __global__ __launch_bounds__(KT) void k_solve_candidate(const KktDev d, const So
     }
     store_partials<CP_COUNT, CP_COUNT>(val, v.ws, v.off_candidate, v.grid);
 }
-__global__ __launch_bounds__(64) void k_solve_candidate_finish(const KktDev d, const SolveDev v, double kappa, int first) {
+// ---- the candidate in evaluated mode: the point must exist before it can be evaluated, so the kernel above splits.  k_solve_candidate_point forms x^, r^, s^ (t^
+// when first) and the partials of dd; the evaluator then runs at v.cand into the candidate's objective, gcand and hcand; k_solve_candidate_merit reduces
+// dual . r^, r^ . r^, the constraint violation and the barrier from what both left, reading the candidate where k_solve_candidate recomputes it (the same bits) -------
+__global__ __launch_bounds__(KT) void k_solve_candidate_point(const KktDev d, const SolveDev v, const double* __restrict__ alpha, double a_s, double a_t, int first) {
+    if (alpha) { a_s = alpha[PUB_STEP_S]; a_t = alpha[PUB_STEP_T]; }
+    double val[1] = {0.0};
+    const double* __restrict__ w = v.w;
+    const double* __restrict__ D = v.step;
+    for (long long it = (long long)blockIdx.x * KT + threadIdx.x; it < v.rows; it += (long long)v.grid * KT) {
+        const int k = (int)it;
+        if (first) val[0] += v.mgrad[k] * D[k];
+        if (k < d.nx + d.ne) v.cand[k] = w[k] - a_s * D[k];                                                 // x^, r^ (o_r = nx)
+        else {
+            const int c = k - d.nx - d.ne;
+            v.cand[d.o_s + c] = w[d.o_s + c] - a_s * D[d.o_s + c];
+            if (first) v.cand[d.o_t + c] = w[d.o_t + c] - a_t * D[d.o_t + c];
+        }
+    }
+    if (first) store_partials<1, 1>(val, v.ws, v.off_candidate + (long long)CP_DD * v.grid, v.grid);        // (uniform: every workgroup stores, or none)
+}
+__global__ __launch_bounds__(KT) void k_solve_candidate_merit(const KktDev d, const SolveDev v) {
+    static_assert(CP_DD == CP_COUNT - 1, "the partials of dd are the point kernel's: they lie behind the ones stored here");
+    double val[CP_DD];
+#pragma unroll
+    for (int q = 0; q < CP_DD; ++q) val[q] = 0.0;
+    const double* __restrict__ ch = v.cand;
+    for (long long it = (long long)blockIdx.x * KT + threadIdx.x; it < v.items; it += (long long)v.grid * KT) {
+        int k = 0, lane = 0, nl = 1;
+        const int kind = item_kind(v, it, &k, &lane, &nl);
+        if (kind == 0) {
+            if (k < d.nx) continue;
+            if (k < d.nx + d.ne) {
+                const int i = k - d.nx;
+                const double rh = ch[d.o_r + i], g = v.gcand[i], lam = v.dual[i];
+                val[CP_DUAL_DOT_R] += lam * rh; val[CP_R_DOT_R] += rh * rh; val[CP_THETA] += rabs(g - rh);
+            } else {
+                const int c = k - d.nx - d.ne;
+                const double sh = ch[d.o_s + c], h = v.hcand[c];
+                val[CP_THETA] += rabs(h - sh);
+                if (d.row_cone[c] == -1) val[CP_BARRIER] += log(sh);
+            }
+        } else if (kind == 1) {
+            const int st = d.soc_start[k], dm = d.soc_dim[k];
+            const double* sh = ch + d.o_s + st;
+            double tail = 0.0;
+            for (int q = (lane == 0 ? nl : lane); q < dm; q += nl) tail += sh[q] * sh[q];
+            tail = cone_sum(tail, nl);
+            if (lane == 0) val[CP_BARRIER] += 0.5 * log(sh[0] * sh[0] - tail);
+        }
+    }
+    store_partials<CP_DD, CP_DD>(val, v.ws, v.off_candidate, v.grid);
+}
+template <bool EVAL> __global__ __launch_bounds__(64) void k_solve_candidate_finish(const KktDev d, const SolveDev v, double kappa, int first) {
     __shared__ double tot[CP_COUNT];
     combine_partials<CP_COUNT, CP_COUNT>(v.ws, v.off_candidate, v.grid, tot);
     if (threadIdx.x != 0) return;
-    const double f = tot[CP_OBJECTIVE] + v.objective_constant;
+    double f;
+    if constexpr (EVAL) f = v.fobj[1]; else f = tot[CP_OBJECTIVE] + v.objective_constant;
     double M = 0.0;
     M += f;
     M += tot[CP_DUAL_DOT_R] + 0.5 * d.rho[0] * tot[CP_R_DOT_R];
@@ -372,7 +446,7 @@ __global__ __launch_bounds__(64) void k_solve_candidate_finish(const KktDev d, c
 // ---- accept (solve.jl:309-333): x, r, s, t <- candidate, y <- y - a Dy, z <- z - a Dz, the constraints evaluated at the candidate become the solution's,
 // cone!(product), |g|_inf and |s o t|_inf.  start: nothing moves — g is evaluated at the solution and the cone product is taken as it LIES in its buffer
 // (solve.jl:85-86 read it before :88 forms it: stale on first use, kept) ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(KT) void k_solve_accept(const KktDev d, const SolveDev v, double a, int start) {
+template <bool EVAL> __global__ __launch_bounds__(KT) void k_solve_accept(const KktDev d, const SolveDev v, double a, int start) {
     double val[AP_COUNT] = {0.0, 0.0};
     for (long long it = (long long)blockIdx.x * KT + threadIdx.x; it < v.items; it += (long long)v.grid * KT) {
         int k = 0, lane = 0, nl = 1;
@@ -382,7 +456,7 @@ __global__ __launch_bounds__(KT) void k_solve_accept(const KktDev d, const Solve
             else if (k < d.nx + d.ne) {
                 const int i = k - d.nx;
                 double g;
-                if (start) g = qp_equality_row(d, v, i, [&](int j) { return v.w[j]; });
+                if (start) { if constexpr (EVAL) g = v.g[i]; else g = qp_equality_row(d, v, i, [&](int j) { return v.w[j]; }); }
                 else { g = v.gcand[i]; v.w[d.o_r + i] = v.cand[d.o_r + i]; v.w[d.o_y + i] = v.w[d.o_y + i] - a * v.step[d.o_y + i]; }
                 v.g[i] = g;
                 val[AP_G_INF] = fmax(val[AP_G_INF], rabs(g));
@@ -463,7 +537,8 @@ int ensure_state(KH* s) {
         (rc = kkt_reserve(s, &v.bgrad, (size_t)d.nc)) || (rc = kkt_reserve(s, &v.cprod, (size_t)d.nc)) || (rc = kkt_reserve(s, &v.ctarget, (size_t)d.nc)) ||
         (rc = kkt_reserve(s, &v.g, (size_t)d.ne)) || (rc = kkt_reserve(s, &v.h, (size_t)d.nc)) || (rc = kkt_reserve(s, &v.gcand, (size_t)d.ne)) ||
         (rc = kkt_reserve(s, &v.hcand, (size_t)d.nc)) || (rc = kkt_reserve(s, &v.fx, (size_t)d.nx)) || (rc = kkt_reserve(s, &v.ws, (size_t)t->lay.doubles)) ||
-        (rc = kkt_reserve(s, &wsm, (size_t)(t->lay.mask_ints + 1) / 2)) || (rc = kkt_reserve(s, &pub, PUB_ALLOC_DOUBLES))) return rc;
+        (rc = kkt_reserve(s, &wsm, (size_t)(t->lay.mask_ints + 1) / 2)) || (rc = kkt_reserve(s, &pub, PUB_ALLOC_DOUBLES)) || (rc = kkt_reserve(s, &t->fobj, 2))) return rc;
+    v.fobj = t->fobj;
     v.q = t->q; v.b = t->b; v.hvec = t->hvec; v.w = s->w; v.res = s->res; v.step = s->step;
     v.wsm = reinterpret_cast<unsigned*>(wsm); v.pub = pub; v.pub_masks = reinterpret_cast<unsigned*>(pub + PUB_DOUBLES);
     v.objective_constant = 0.0;
@@ -476,11 +551,47 @@ int ensure_state(KH* s) {
 // ---- enqueues: each records the beginning of a timed group, the read-back closes it -----------------------------------------------------------------------------
 void open_group(KH* s) { SS* t = s->solve; if (!t->group_open) { (void)hipEventRecord(t->ev[0], s->st); t->group_open = true; } }
 
-void enqueue_init(KH* s) { SS* t = s->solve; open_group(s); hipLaunchKernelGGL(k_solve_init, dim3((unsigned)t->v.grid), dim3(KT), 0, s->st, s->d, t->v); }
-void enqueue_prologue(KH* s) {
+// the evaluator at the solution (which = 0) or at the candidate (1): a stream-ordered enqueue, no host wait.  The three matrices are the handle's resident arrays: an
+// evaluation that writes one leaves K and its factor behind
+int enqueue_evaluator(KH* s, int which, uint32_t flags) {
+    SS* t = s->solve; SolveDev& v = t->v; const KktDev& d = s->d;
+    open_group(s);
+    calipso_device_sparse_data out;
+    out.objective = t->fobj + which; out.objective_gradient_variables = v.fx;
+    out.equality_constraint = which ? v.gcand : v.g; out.cone_constraint = which ? v.hcand : v.h;
+    out.lagrangian_hessian = s->Lxx; out.equality_jacobian_variables = s->gx; out.cone_jacobian_variables = s->hx;
+    out.Lxx_colptr = t->pattern[0].data(); out.Lxx_rowval = t->pattern[1].data(); out.gx_colptr = t->pattern[2].data(); out.gx_rowval = t->pattern[3].data();
+    out.hx_colptr = t->pattern[4].data(); out.hx_rowval = t->pattern[5].data();
+    out.nx = d.nx; out.np = t->eval_np; out.ne = d.ne; out.nc = d.nc; out.nnz_Lxx = d.nnzL; out.nnz_gx = d.nnzg; out.nnz_hx = d.nnzh;
+    const int32_t r = t->eval_fn(t->eval_user, flags, which ? v.cand : s->w, s->w + d.o_y, s->w + d.o_z, t->theta, &out, (void*)s->st);
+    for (int i = 0; i < 3; ++i) if (flags & EVAL_MATRIX_BITS[i]) { s->have[i] = r == 0; s->assembled = false; s->factored = false; }
+    if (r != 0) {
+        (void)hipStreamSynchronize(s->st); (void)hipGetLastError();
+        t->group_open = false;
+        return kkt_fail(s, r == 1 ? CALIPSO_ERR_ARGUMENT : CALIPSO_ERR_HIP, "the device evaluator returned " + std::to_string(r) + " (flags " + std::to_string(flags) + ", " +
+                                                                                (which ? "candidate" : "solution") + ")");
+    }
+    return CALIPSO_OK;
+}
+// every variable-side bit: what solve.jl:100-135 and :175-185 evaluate at a point, the dual Hessians iff constraint_tensor (residual_jacobian_variables.jl:10-16)
+uint32_t prologue_flags(const Options& o) {
+    return o.constraint_tensor != 0.0 ? EVAL_EVERYTHING : EVAL_EVERYTHING & ~(uint32_t)(CALIPSO_EVAL_EQUALITY_DUAL_HESSIAN | CALIPSO_EVAL_CONE_DUAL_HESSIAN);
+}
+#define LAUNCH_CLASS(kernel, grid, block, ...)                                                                         \
+    do { if (t->eval_fn) hipLaunchKernelGGL(kernel<true>, grid, block, 0, s->st, __VA_ARGS__); else hipLaunchKernelGGL(kernel<false>, grid, block, 0, s->st, __VA_ARGS__); } while (0)
+
+int enqueue_init(KH* s) {
     SS* t = s->solve; open_group(s);
-    hipLaunchKernelGGL(k_solve_prologue, dim3((unsigned)t->v.grid), dim3(KT), 0, s->st, s->d, t->v, s->sc.kappa);
-    hipLaunchKernelGGL(k_solve_prologue_finish, dim3(1), dim3(64), 0, s->st, s->d, t->v, s->sc.kappa);
+    if (t->eval_fn) { const int rc = enqueue_evaluator(s, 0, CALIPSO_EVAL_EQUALITY); if (rc < 0) return rc; }      // r <- g(x): the point must be evaluated first
+    LAUNCH_CLASS(k_solve_init, dim3((unsigned)t->v.grid), dim3(KT), s->d, t->v);
+    return CALIPSO_OK;
+}
+int enqueue_prologue(KH* s) {
+    SS* t = s->solve; open_group(s);
+    if (t->eval_fn) { const int rc = enqueue_evaluator(s, 0, prologue_flags(s->opt)); if (rc < 0) return rc; }
+    LAUNCH_CLASS(k_solve_prologue, dim3((unsigned)t->v.grid), dim3(KT), s->d, t->v, s->sc.kappa);
+    LAUNCH_CLASS(k_solve_prologue_finish, dim3(1), dim3(64), s->d, t->v, s->sc.kappa);
+    return CALIPSO_OK;
 }
 int mask_trials(const Options& o) { return (int)std::min<i64>(o.max_cone_line_search + 1, calipso::CONE_MASK_TRIALS); }
 void enqueue_cone_masks(KH* s) {
@@ -488,16 +599,23 @@ void enqueue_cone_masks(KH* s) {
     hipLaunchKernelGGL(k_solve_cone_masks, dim3((unsigned)t->v.grid), dim3(KT), 0, s->st, s->d, t->v, s->sc.tau, s->opt.scaling_line_search, mask_trials(s->opt));
     hipLaunchKernelGGL(k_solve_masks_finish, dim3(1), dim3(64), 0, s->st, t->v, s->opt.scaling_line_search, mask_trials(s->opt));
 }
-void enqueue_candidate(KH* s, bool from_masks, double a_s, double a_t, bool first) {
+int enqueue_candidate(KH* s, bool from_masks, double a_s, double a_t, bool first) {
     SS* t = s->solve; open_group(s);
-    hipLaunchKernelGGL(k_solve_candidate, dim3((unsigned)t->v.grid), dim3(KT), 0, s->st, s->d, t->v, from_masks ? (const double*)t->v.pub : (const double*)nullptr, a_s, a_t,
-                       first ? 1 : 0);
-    hipLaunchKernelGGL(k_solve_candidate_finish, dim3(1), dim3(64), 0, s->st, s->d, t->v, s->sc.kappa, first ? 1 : 0);
+    const double* alpha = from_masks ? (const double*)t->v.pub : (const double*)nullptr;
+    if (t->eval_fn) {
+        hipLaunchKernelGGL(k_solve_candidate_point, dim3((unsigned)t->v.grid), dim3(KT), 0, s->st, s->d, t->v, alpha, a_s, a_t, first ? 1 : 0);
+        { const int rc = enqueue_evaluator(s, 1, EVAL_POINT); if (rc < 0) return rc; }
+        hipLaunchKernelGGL(k_solve_candidate_merit, dim3((unsigned)t->v.grid), dim3(KT), 0, s->st, s->d, t->v);
+    } else hipLaunchKernelGGL(k_solve_candidate, dim3((unsigned)t->v.grid), dim3(KT), 0, s->st, s->d, t->v, alpha, a_s, a_t, first ? 1 : 0);
+    LAUNCH_CLASS(k_solve_candidate_finish, dim3(1), dim3(64), s->d, t->v, s->sc.kappa, first ? 1 : 0);
+    return CALIPSO_OK;
 }
-void enqueue_accept(KH* s, double a, bool start) {
+int enqueue_accept(KH* s, double a, bool start) {
     SS* t = s->solve; open_group(s);
-    hipLaunchKernelGGL(k_solve_accept, dim3((unsigned)t->v.grid), dim3(KT), 0, s->st, s->d, t->v, a, start ? 1 : 0);
+    if (start && t->eval_fn) { const int rc = enqueue_evaluator(s, 0, CALIPSO_EVAL_EQUALITY); if (rc < 0) return rc; }
+    LAUNCH_CLASS(k_solve_accept, dim3((unsigned)t->v.grid), dim3(KT), s->d, t->v, a, start ? 1 : 0);
     hipLaunchKernelGGL(k_solve_accept_finish, dim3(1), dim3(64), 0, s->st, t->v);
+    return CALIPSO_OK;
 }
 void enqueue_outer_update(KH* s, double rho) {
     SS* t = s->solve; open_group(s);
@@ -527,11 +645,12 @@ const int* host_masks(const SS* t) { return reinterpret_cast<const int*>(t->hpub
 int ready(KH* s, const char* entry, bool point) {
     static const char* const names[3] = {"Lxx", "gx", "hx"};
     const size_t need[3] = {(size_t)s->d.nnzL, (size_t)s->d.nnzg, (size_t)s->d.nnzh};
-    for (int i = 0; i < 3; ++i) if (need[i] && !s->have[i]) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": no " + names[i] + " resident (calipso_hip_sparse_kkt_set_values first)");
     SS* t = s->solve;
+    const bool evaluated = t->eval_fn != nullptr;              // (an evaluator writes the three matrices itself, and stands where q, b, hvec stand for the QP)
+    for (int i = 0; i < 3 && !evaluated; ++i) if (need[i] && !s->have[i]) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": no " + names[i] + " resident (calipso_hip_sparse_kkt_set_values first)");
     static const char* const qp[3] = {"q", "b", "hvec"};
     const size_t len[3] = {(size_t)s->d.nx, (size_t)s->d.ne, (size_t)s->d.nc};
-    for (int i = 0; i < 3; ++i) if (len[i] && !t->have_qp[i]) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": no " + qp[i] + " resident (calipso_hip_sparse_kkt_qp_attach first)");
+    for (int i = 0; i < 3 && !evaluated; ++i) if (len[i] && !t->have_qp[i]) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": no " + qp[i] + " resident (calipso_hip_sparse_kkt_qp_attach first)");
     if (point && !s->have[3]) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": no point resident (calipso_hip_sparse_kkt_initialize, or set_values with w, first)");
     if (point && s->d.ne && !s->have[4]) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": no penalty resident");
     return CALIPSO_OK;
@@ -552,6 +671,7 @@ int qp_attach(KH* s, const double* q, const double* b, const double* hvec, doubl
     for (int i = 0; i < 3; ++i) if (src[i] && count[i]) { KK(hipMemcpyAsync(dst[i], src[i], sizeof(double) * count[i], kind, s->st)); t->have_qp[i] = true; }
     KK(hipStreamSynchronize(s->st));
     t->v.objective_constant = objective_constant;
+    t->eval_fn = nullptr; t->eval_user = nullptr;           // a handle holds one problem class: the QP replaces an evaluator
     s->qp_attached = true;
     for (int i = 0; i < 3; ++i) if (count[i] && !t->have_qp[i]) s->qp_attached = false;
     return CALIPSO_OK;
@@ -559,7 +679,7 @@ int qp_attach(KH* s, const double* q, const double* b, const double* hvec, doubl
 int initialize(KH* s, const double* x0, hipMemcpyKind kind) {
     SS* t = s->solve;
     if (s->d.nx) KK(hipMemcpyAsync(s->w, x0, sizeof(double) * (size_t)s->d.nx, kind, s->st));
-    enqueue_init(s);
+    { const int rc = enqueue_init(s); if (rc < 0) return rc; }
     KK(hipStreamSynchronize(s->st));
     KK(hipGetLastError());
     t->group_open = false;
@@ -570,7 +690,8 @@ int initialize(KH* s, const double* x0, hipMemcpyKind kind) {
 }
 double* resident(KH* s, int vec) {
     SolveDev& v = s->solve->v;
-    double* const p[V_COUNT] = {s->w, v.cand, v.dual, s->res, v.mgrad, s->step, v.cprod, v.ctarget, v.bgrad, v.g, v.h, v.fx};
+    double* const p[V_NAMED] = {s->w, v.cand, v.dual, s->res, v.mgrad, s->step, v.cprod, v.ctarget, v.bgrad, v.g, v.h, v.fx, nullptr,
+                                s->solve->fobj, s->Lxx, s->gx, s->hx};
     return p[vec];
 }
 
@@ -595,13 +716,13 @@ int solve(KH* s, double info[16]) {
         return rc;
     };
     int rc;
-    if (o.warmstart == 0.0) enqueue_init(s);                                                  // initialize.jl:15-36
+    if (o.warmstart == 0.0 && (rc = enqueue_init(s)) < 0) return leave(rc);                   // initialize.jl:15-36
     calipso::initial_scalars(o, sc);                                                          // initialize.jl:38-48
     sc.ep_last = 0.0;                                                                         // (every solve starts as a fresh solver does)
     enqueue_penalty(s);
     if (d.ne) hipLaunchKernelGGL(k_solve_fill, dim3(blocks_of(d.ne)), dim3(KT), 0, s->st, d.ne, t->v.dual, o.dual_initial);
-    enqueue_accept(s, 0.0, true);                                                             // :85-86: |g|_inf, and the cone product as it lies (stale on first use)
-    enqueue_prologue(s);                                                                      // (forms the cone product and target of :88-91 too)
+    if ((rc = enqueue_accept(s, 0.0, true)) < 0) return leave(rc);                            // :85-86: |g|_inf, and the cone product as it lies (stale on first use)
+    if ((rc = enqueue_prologue(s)) < 0) return leave(rc);                                     // (forms the cone product and target of :88-91 too)
     if ((rc = read_published(s)) < 0) return leave(rc);
     double equality_violation = pub[PUB_G_INF], cone_product_violation = pub[PUB_PRODUCT_INF];
     t->filter.reset();                                                                        // :95
@@ -614,7 +735,8 @@ int solve(KH* s, double info[16]) {
             const int kind = calipso::exit_kind(o, sc.kappa, norms, equality_violation, cone_product_violation, true);      // :138-143, :165
             if (kind == 1) return leave(1);
             if (kind == 2) break;
-            // :175-185: Hessian and Jacobians are constant, the dual Hessians zero, the cone Jacobians formed inside the kernels of sparse_kkt.hip
+            // :175-185: on a QP the Hessian and Jacobians are constant and the dual Hessians zero; with an evaluator they are the resident arrays the call in front of
+            // this step's prologue wrote, at this point and its y, z.  The cone Jacobians are formed inside the kernels of sparse_kkt.hip
             double reg[3] = {sc.ep, sc.ep_last, sc.ed}, sdinfo[4] = {0, 0, 0, 0};
             diff_keep_slacks(s);                                                              // what differentiate! forms the cone blocks at: no host wait
             rc = kkt_search_direction(s, s->res, s->step, reg, sdinfo);                       // :187
@@ -634,7 +756,7 @@ int solve(KH* s, double info[16]) {
             }
             // cone search (:190-221) and the first candidate (:206-250) behind it, its step sizes taken from the masks on the device: one read-back
             enqueue_cone_masks(s);
-            enqueue_candidate(s, true, 0.0, 0.0, true);
+            if ((rc = enqueue_candidate(s, true, 0.0, 0.0, true)) < 0) return leave(rc);
             if ((rc = read_published(s)) < 0) return leave(rc);
             double step_size = 1.0, step_size_t = 1.0;
             if (!calipso::cone_step_sizes(host_masks(t), host_masks(t) + calipso::CONE_MASK_WORDS, o, &step_size, &step_size_t)) {
@@ -649,7 +771,7 @@ int solve(KH* s, double info[16]) {
             while (residual_iteration < o.max_residual_line_search) {                         // :254-302
                 if (calipso::line_search_accepts(o, t->filter.accepts(thetah, Mh), theta, M, thetah, Mh, dd, step_size)) break;
                 step_size = o.scaling_line_search * step_size;
-                enqueue_candidate(s, false, step_size, step_size_t, false);                   // :268-297
+                if ((rc = enqueue_candidate(s, false, step_size, step_size_t, false)) < 0) return leave(rc);   // :268-297
                 if ((rc = read_published(s)) < 0) return leave(rc);
                 Mh = pub[PUB_CAND_MERIT]; thetah = pub[PUB_CAND_THETA];
                 residual_iteration += 1; trials += 1;
@@ -657,13 +779,13 @@ int solve(KH* s, double info[16]) {
             if (residual_iteration >= o.max_residual_line_search) worst = std::max(worst, (int)CALIPSO_WARN_LINE_SEARCH);
             if (calipso::filter_needs_augment(o, theta, M, Mh, dd, step_size))                // filter.jl:81-89
                 t->filter.augment((1.0 - o.violation_tolerance) * theta, M - o.merit_tolerance * theta);
-            enqueue_accept(s, step_size, false);                                              // :309-333
+            if ((rc = enqueue_accept(s, step_size, false)) < 0) return leave(rc);             // :309-333
             if (t->trace_rows < t->trace_cap) {
                 KK(hipMemcpyAsync(t->trace + (size_t)t->trace_rows * (size_t)d.N, s->w, sizeof(double) * (size_t)d.N, hipMemcpyDeviceToDevice, s->st));
                 t->trace_rows += 1;
             }
             t->trace_total += 1;
-            enqueue_prologue(s);                                                              // the next step's, at the same scalars: read back with the two violations
+            if ((rc = enqueue_prologue(s)) < 0) return leave(rc);                             // the next step's, at the same scalars: read back with the two violations
             if ((rc = read_published(s)) < 0) return leave(rc);
             equality_violation = pub[PUB_G_INF]; cone_product_violation = pub[PUB_PRODUCT_INF];
             total_iterations += 1; accepted += 1;
@@ -674,7 +796,7 @@ int solve(KH* s, double info[16]) {
         enqueue_penalty(s);
         t->filter.reset();                                                                    // :368
         if (j < o.max_outer_iterations) {
-            enqueue_prologue(s);
+            if ((rc = enqueue_prologue(s)) < 0) return leave(rc);
             if ((rc = read_published(s)) < 0) return leave(rc);
         }
     }
@@ -769,7 +891,7 @@ int32_t calipso_hip_sparse_kkt_solve(calipso_hip_sparse_kkt* s, double info[16])
 int32_t calipso_hip_sparse_kkt_step_prologue(calipso_hip_sparse_kkt* s, int32_t which, double scalars[16]) {
     ENTRY("calipso_hip_sparse_kkt_step_prologue", true);
     if (which != 0) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_sparse_kkt_step_prologue: which: the prologue is taken at the solution (0); calipso_hip_sparse_kkt_candidate evaluates a candidate");
-    enqueue_prologue(s);
+    { const int rc = enqueue_prologue(s); if (rc < 0) return rc; }
     { const int rc = read_published(s); if (rc < 0) return rc; }
     if (scalars) {
         const double* p = t->hpub;
@@ -793,7 +915,7 @@ int32_t calipso_hip_sparse_kkt_cone_search(calipso_hip_sparse_kkt* s, double a[2
 int32_t calipso_hip_sparse_kkt_candidate(calipso_hip_sparse_kkt* s, double a_s, double a_t, double out[3]) {
     ENTRY("calipso_hip_sparse_kkt_candidate", true);
     REFUSE(check_step_sizes(entry, a_s, a_t));
-    enqueue_candidate(s, false, a_s, a_t, true);
+    { const int rc = enqueue_candidate(s, false, a_s, a_t, true); if (rc < 0) return rc; }
     { const int rc = read_published(s); if (rc < 0) return rc; }
     if (out) { out[0] = t->hpub[PUB_CAND_MERIT]; out[1] = t->hpub[PUB_CAND_THETA]; out[2] = t->hpub[PUB_DD]; }
     return CALIPSO_OK;
@@ -802,7 +924,7 @@ int32_t calipso_hip_sparse_kkt_candidate(calipso_hip_sparse_kkt* s, double a_s, 
 int32_t calipso_hip_sparse_kkt_accept(calipso_hip_sparse_kkt* s, double a, double violations[2]) {
     ENTRY("calipso_hip_sparse_kkt_accept", true);
     REFUSE(check_step_sizes(entry, a, 1.0));
-    enqueue_accept(s, a, false);
+    { const int rc = enqueue_accept(s, a, false); if (rc < 0) return rc; }
     { const int rc = read_published(s); if (rc < 0) return rc; }
     if (violations) { violations[0] = t->hpub[PUB_G_INF]; violations[1] = t->hpub[PUB_PRODUCT_INF]; }
     s->assembled = false; s->factored = false;
@@ -824,7 +946,8 @@ int32_t calipso_hip_sparse_kkt_get(calipso_hip_sparse_kkt* s, const char* name, 
     if (!s) return CALIPSO_ERR_ARGUMENT;
     KK(hipSetDevice(s->device));
     { const int rc = ensure_state(s); if (rc < 0) return rc; }
-    REFUSE(check_named_vector("calipso_hip_sparse_kkt_get", name, out, len, s->d.nx, s->d.ne, s->d.nc, false));
+    const i64 nnz[3] = {s->d.nnzL, s->d.nnzg, s->d.nnzh};
+    REFUSE(check_named_vector("calipso_hip_sparse_kkt_get", name, out, len, s->d.nx, s->d.ne, s->d.nc, false, nnz));
     if (vector_by_name(name) == V_DIFFERENTIATE_SLACKS) {
         const size_t nc = (size_t)s->d.nc;
         const double* from[2] = {s->slacks_kept ? s->dslack : s->w + s->d.o_s, s->slacks_kept ? s->dslack + nc : s->w + s->d.o_t};
@@ -849,6 +972,71 @@ int32_t calipso_hip_sparse_kkt_solution_device(calipso_hip_sparse_kkt* s, double
     KK(hipSetDevice(s->device));
     KK(hipStreamSynchronize(s->st));
     *p = s->w;
+    return CALIPSO_OK;
+}
+
+// ---- the evaluated problem class ------------------------------------------------------------------------------------------------------------------------------------
+int32_t calipso_hip_sparse_kkt_set_evaluator(calipso_hip_sparse_kkt* s, calipso_device_sparse_eval_fn fn, void* user, int64_t np) {
+    if (!s) return CALIPSO_ERR_ARGUMENT;
+    KK(hipSetDevice(s->device));
+    { const int rc = ensure_state(s); if (rc < 0) return rc; }
+    REFUSE(check_set_evaluator(np));
+    SS* t = s->solve;
+    KK(hipStreamSynchronize(s->st));                         // (nothing of the evaluator before is in flight when its user object changes hands)
+    if (!fn) { t->eval_fn = nullptr; t->eval_user = nullptr; return CALIPSO_OK; }
+    if (np != t->eval_np || !t->theta) {
+        double* theta = nullptr;
+        { const int rc = kkt_reserve(s, &theta, (size_t)std::max<i64>(np, 1)); if (rc < 0) return rc; }      // zeros
+        t->theta = theta; t->eval_np = np;
+    }
+    if (t->pattern[0].empty()) {                              // the host copies an evaluator builds its address table from: 1-based, as create took them
+        const ColView* cols[3] = {&s->an.Lxx_cols, &s->an.gx_cols, &s->an.hx_cols};
+        for (int m = 0; m < 3; ++m) {
+            for (int p : cols[m]->ptr) t->pattern[2 * m].push_back((int64_t)p + 1);
+            for (int r : cols[m]->row) t->pattern[2 * m + 1].push_back((int64_t)r + 1);
+        }
+    }
+    t->eval_fn = fn; t->eval_user = user;
+    for (int i = 0; i < 3; ++i) t->have_qp[i] = false;       // a handle holds one problem class: the evaluator replaces the QP
+    s->qp_attached = false;
+    return CALIPSO_OK;
+}
+static int set_parameters(calipso_hip_sparse_kkt* s, const double* theta, hipMemcpyKind kind) {
+    SS* t = s->solve;
+    if (t->eval_np) KK(hipMemcpyAsync(t->theta, theta, sizeof(double) * (size_t)t->eval_np, kind, s->st));
+    KK(hipStreamSynchronize(s->st));
+    return CALIPSO_OK;
+}
+int32_t calipso_hip_sparse_kkt_set_parameters(calipso_hip_sparse_kkt* s, const double* theta) {
+    if (!s) return CALIPSO_ERR_ARGUMENT;
+    KK(hipSetDevice(s->device));
+    { const int rc = ensure_state(s); if (rc < 0) return rc; }
+    REFUSE(check_set_parameters("calipso_hip_sparse_kkt_set_parameters", s->solve->eval_fn != nullptr, s->solve->eval_np, theta));
+    return set_parameters(s, theta, hipMemcpyHostToDevice);
+}
+int32_t calipso_hip_sparse_kkt_set_parameters_device(calipso_hip_sparse_kkt* s, const double* theta) {
+    if (!s) return CALIPSO_ERR_ARGUMENT;
+    KK(hipSetDevice(s->device));
+    { const int rc = ensure_state(s); if (rc < 0) return rc; }
+    static const char* const entry = "calipso_hip_sparse_kkt_set_parameters_device";
+    REFUSE(check_set_parameters(entry, s->solve->eval_fn != nullptr, s->solve->eval_np, theta));
+    if (s->solve->eval_np) { const int rc = kkt_device_pointer(s, theta, entry, "theta"); if (rc < 0) return rc; }
+    return set_parameters(s, theta, hipMemcpyDeviceToDevice);
+}
+int32_t calipso_hip_sparse_kkt_evaluate(calipso_hip_sparse_kkt* s, int32_t which, uint32_t flags) {
+    if (!s) return CALIPSO_ERR_ARGUMENT;
+    KK(hipSetDevice(s->device));
+    { const int rc = ensure_state(s); if (rc < 0) return rc; }
+    static const char* const entry = "calipso_hip_sparse_kkt_evaluate";
+    SS* t = s->solve;
+    if (!t->eval_fn) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": no evaluator attached (calipso_hip_sparse_kkt_set_evaluator first)");
+    REFUSE(check_evaluate(which, flags));
+    if (!s->have[3]) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": no point resident (calipso_hip_sparse_kkt_initialize, or set_values with w, first)");
+    (void)hipGetLastError();
+    { const int rc = enqueue_evaluator(s, which, flags); if (rc < 0) return rc; }
+    KK(hipStreamSynchronize(s->st));
+    KK(hipGetLastError());
+    t->group_open = false;
     return CALIPSO_OK;
 }
 

@@ -101,18 +101,23 @@ inline Layout layout(i64 nx, i64 ne, i64 nc, i64 n_small, i64 n_wide) {
 enum Vector { V_SOLUTION, V_CANDIDATE, V_DUAL, V_RESIDUAL, V_MERIT_GRADIENT, V_STEP, V_CONE_PRODUCT, V_CONE_TARGET, V_BARRIER_GRADIENT, V_EQUALITY_CONSTRAINT,
               V_CONE_CONSTRAINT, V_OBJECTIVE_GRADIENT_VARIABLES, V_COUNT,
               // not a vector of the reference's solver: the s, t that differentiate! forms the cone blocks at (sparse_differentiate.hip), s then t; read only
-              V_DIFFERENTIATE_SLACKS = V_COUNT, V_NAMED };
+              V_DIFFERENTIATE_SLACKS = V_COUNT,
+              // ... nor these: the evaluator's objective at the solution (1) and the three resident non-zero arrays on their stored patterns; read only
+              V_OBJECTIVE, V_LAGRANGIAN_HESSIAN, V_EQUALITY_JACOBIAN_VARIABLES, V_CONE_JACOBIAN_VARIABLES, V_NAMED };
 inline const char* vector_name(int v) {
     static const char* const names[V_NAMED] = {"solution", "candidate", "dual", "residual", "merit_gradient", "step", "cone_product", "cone_target", "barrier_gradient",
-                                               "equality_constraint", "cone_constraint", "objective_gradient_variables", "differentiate_slacks"};
+                                               "equality_constraint", "cone_constraint", "objective_gradient_variables", "differentiate_slacks",
+                                               "objective", "lagrangian_hessian", "equality_jacobian_variables", "cone_jacobian_variables"};
     return v >= 0 && v < V_NAMED ? names[v] : "";
 }
 inline int vector_by_name(const char* name) {
     if (name) for (int v = 0; v < V_NAMED; ++v) if (!std::strcmp(name, vector_name(v))) return v;
     return -1;
 }
-inline i64 vector_length(int v, i64 nx, i64 ne, i64 nc) {
+inline i64 vector_length(int v, i64 nx, i64 ne, i64 nc, const i64* nnz = nullptr) {      // nnz: the non-zeros of Lxx, gx, hx (the three matrices have no length without)
     switch (v) {
+        case V_OBJECTIVE: return 1;
+        case V_LAGRANGIAN_HESSIAN: case V_EQUALITY_JACOBIAN_VARIABLES: case V_CONE_JACOBIAN_VARIABLES: return nnz ? nnz[v - V_LAGRANGIAN_HESSIAN] : -1;
         case V_SOLUTION: case V_CANDIDATE: case V_RESIDUAL: case V_STEP: return nx + 2 * ne + 3 * nc;
         case V_DUAL: case V_EQUALITY_CONSTRAINT: return ne;
         case V_MERIT_GRADIENT: return nx + ne + nc;
@@ -125,11 +130,11 @@ inline i64 vector_length(int v, i64 nx, i64 ne, i64 nc) {
 
 // ---- argument checks: an empty string, or the refusal's text (the entry returns CALIPSO_ERR_ARGUMENT with it) ---------------------------------------------------
 constexpr i64 TRACE_ROWS_MAX = 1 << 20;
-inline std::string check_named_vector(const char* entry, const char* name, const void* data, i64 len, i64 nx, i64 ne, i64 nc, bool writable_only) {
+inline std::string check_named_vector(const char* entry, const char* name, const void* data, i64 len, i64 nx, i64 ne, i64 nc, bool writable_only, const i64* nnz = nullptr) {
     const int v = vector_by_name(name);
     if (v < 0) return std::string(entry) + ": name: no resident vector called " + (name ? name : "(null)");
     if (writable_only && v != V_SOLUTION && v != V_DUAL && v != V_STEP) return std::string(entry) + ": name: only solution, dual and step can be set, not " + name;
-    const i64 want = vector_length(v, nx, ne, nc);
+    const i64 want = vector_length(v, nx, ne, nc, nnz);
     if (len != want) return std::string(entry) + ": len: " + name + " has " + std::to_string(want) + " entries, not " + std::to_string(len);
     if (!data && want > 0) return std::string(entry) + ": the array is NULL";
     return "";
@@ -141,6 +146,32 @@ inline std::string check_keep_trace(i64 rows) {
 inline std::string check_trace(const void* out, i64 cap_rows) {
     if (cap_rows < 0) return "calipso_hip_sparse_kkt_trace: cap_rows is negative";
     if (!out && cap_rows > 0) return "calipso_hip_sparse_kkt_trace: out is NULL with cap_rows > 0";
+    return "";
+}
+// ---- the evaluator's entries ------------------------------------------------------------------------------------------------------------------------------------
+// the bits an evaluation on the sparse handle may carry: no dual gradient (the handle gathers them), no parameter Jacobian (differentiate takes the caller's)
+constexpr uint32_t EVAL_DUAL_GRADIENTS = (1u << 5) | (1u << 9);
+constexpr uint32_t EVAL_PARAMETER_BITS = 0x1fu << 11;
+constexpr uint32_t EVAL_MATRIX_BITS[3] = {(1u << 2) | (1u << 6) | (1u << 10), 1u << 4, 1u << 8};      // what writes Lxx, gx, hx
+constexpr uint32_t EVAL_POINT = (1u << 0) | (1u << 3) | (1u << 7);                                    // objective, equality, cone: what a candidate asks for
+constexpr uint32_t EVAL_EVERYTHING = EVAL_POINT | (1u << 1) | EVAL_MATRIX_BITS[0] | EVAL_MATRIX_BITS[1] | EVAL_MATRIX_BITS[2];
+inline std::string check_evaluate(int which, uint32_t flags) {
+    static const char* const entry = "calipso_hip_sparse_kkt_evaluate";
+    if (which != 0 && which != 1) return std::string(entry) + ": which: 0 the solution, 1 the candidate, not " + std::to_string(which);
+    if (flags & EVAL_PARAMETER_BITS) return std::string(entry) + ": flags: parameter-Jacobian bits " + std::to_string(flags & EVAL_PARAMETER_BITS) +
+                                            ": the sparse handle asks its evaluator for no parameter Jacobian; differentiate takes the caller's dR/dtheta";
+    if (flags & EVAL_DUAL_GRADIENTS) return std::string(entry) + ": flags: a dual-gradient bit: (g'y)x and (h'z)x are formed by the handle from its column views, the evaluator has no destination for them";
+    if (flags >> 16) return std::string(entry) + ": flags: bits beyond CALIPSO_EVAL_CONE_DUAL_JACOBIAN_PARAMETERS";
+    if (!flags) return std::string(entry) + ": flags: nothing asked for";
+    return "";
+}
+inline std::string check_set_evaluator(i64 np) {
+    if (np < 0 || np > 0x7ffffff0) return "calipso_hip_sparse_kkt_set_evaluator: np: " + std::to_string(np) + " parameters";
+    return "";
+}
+inline std::string check_set_parameters(const char* entry, bool evaluator, i64 np, const void* theta) {
+    if (!evaluator) return std::string(entry) + ": no evaluator attached (calipso_hip_sparse_kkt_set_evaluator first): a QP has no parameters";
+    if (!theta && np > 0) return std::string(entry) + ": theta is NULL, the evaluator takes " + std::to_string(np) + " parameters";
     return "";
 }
 inline std::string check_step_sizes(const char* entry, double a_s, double a_t) {

@@ -525,6 +525,18 @@ end
 sparse_set!(k::SparseKKT, name::AbstractString, v::Vector{Float64}) =
     kkt_check(ccall((:calipso_hip_sparse_kkt_set, lib), Int32, (Ptr{Cvoid}, Cstring, Ptr{Float64}, Int64), k.handle, name, v, length(v)), k, "set($name)")
 
+# ---- solve! on sparse data with an evaluator: nonlinear problems on the same handle (ccall wrappers, no logic; not executed here either) ---------------------------
+# fn: a calipso_device_sparse_eval_fn from a shared library (dlsym), user: its object; replaces qp_attach!, and qp_attach! replaces it; fn = C_NULL removes it
+sparse_set_evaluator!(k::SparseKKT, fn::Ptr{Cvoid}, user::Ptr{Cvoid}=C_NULL; num_parameters::Integer=0) =
+    kkt_check(ccall((:calipso_hip_sparse_kkt_set_evaluator, lib), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64), k.handle, fn, user, num_parameters), k, "set_evaluator!")
+sparse_set_parameters!(k::SparseKKT, theta::Vector{Float64}) =
+    kkt_check(ccall((:calipso_hip_sparse_kkt_set_parameters, lib), Int32, (Ptr{Cvoid}, Ptr{Float64}), k.handle, theta), k, "set_parameters!")
+sparse_set_parameters_device!(k::SparseKKT, theta::Ptr{Cvoid}) =
+    kkt_check(ccall((:calipso_hip_sparse_kkt_set_parameters_device, lib), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), k.handle, theta), k, "set_parameters_device!")
+# the evaluator at the solution (which = 0) or at the candidate (1); flags: CALIPSO_EVAL_* without dual gradients and parameter Jacobians
+sparse_evaluate!(k::SparseKKT, flags::Integer; which::Integer=0) =
+    kkt_check(ccall((:calipso_hip_sparse_kkt_evaluate, lib), Int32, (Ptr{Cvoid}, Int32, UInt32), k.handle, which, flags), k, "evaluate!")
+
 # ---- differentiate! on the same handle (csrc/sparse_differentiate.hip): ccall wrappers, no logic; not executed here either (see the note at the top) -----------
 # X = M B (transposed: M' B) through the current factorisation; B, X: N x k
 sparse_solve_columns!(k::SparseKKT, X::Matrix{Float64}, B::Matrix{Float64}; transposed::Bool=false) = kkt_check(

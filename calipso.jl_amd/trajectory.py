@@ -16,7 +16,8 @@ checks and every address are plain C++ in include/calipso_trajectory_tables.hpp)
   * one evaluation kernel: a lane per stage instance of a template, 64-thread workgroups, different templates in different workgroup ranges of the same launch (every
     branch on the template is workgroup-uniform).  Index and address tables are stage-minor ([entry][stage]): the lanes of a wavefront read consecutive words;
   * an output with ONE writer (the values, the objective gradient, the Jacobians' non-zeros) is stored where the ADDRESS TABLE says: entry -> offset in the destination,
-    built once per handle from the dense layout or from the host copy of the block descriptors, uploaded on the first call from pinned memory;
+    built once per handle from the dense layout, from the host copy of the block descriptors or — a sparse handle — from the stored patterns of its three non-zero
+    arrays, uploaded on the first call from pinned memory;
   * an output that sums contributions of several stages (the objective, (g'y)x where stages t and t + 1 meet, (h'z)x, the Lagrangian Hessian, the Lagrangian's
     theta-gradient) gets per-stage PARTIALS and one finishing pass that adds them in a fixed order: no atomics, the same bits every run.  Quirk B-11 of the reference
     (tests/problems.py: TrajectoryProblem — where two consecutive dynamics stages both emit a (x_t+1, x_t+1) entry of (g'y)xx the later stage's value alone survives) is
@@ -29,7 +30,7 @@ import inspect
 
 import numpy as np
 
-from . import Solver
+from . import Solver, SparseKKT
 from . import codegen as _cg
 
 KINDS = ("cost", "dynamics", "equality", "nonnegative", "second_order")
@@ -69,7 +70,8 @@ class TrajectoryProblem:
     equalities 1..T], cone rows: the nonnegative rows of all stages, then the second-order cones stage by stage (methods.jl:46-50); theta = vcat(theta_t).
 
     .nx .np .ne .nc .T .indices .nonnegative_indices .second_order_indices (1-based, as Solver takes them); structure(); evaluate() (the host twin, the `methods`
-    contract of Solver and of the oracle); template_source(), source(), stats(), compile(), solver(); initialize_states, initialize_actions, get_trajectory,
+    contract of Solver and of the oracle); template_source(), source(), stats(), compile(), solver(); sparse_patterns(), sparse_solver() (a SparseKKT whose
+    evaluations run in the generated library: the route for implicit dynamics and long horizons); initialize_states, initialize_actions, get_trajectory,
     linear_interpolation."""
 
     def __init__(self, objective, dynamics, num_states, num_actions, equality=None, nonnegative=None, second_order=None, num_parameters=None, hessian="reference",
@@ -341,6 +343,28 @@ class TrajectoryProblem:
                 Hp[tp.p_i[q], tp.p_j[q]] = True
         return Zp, Hp | Hp.T
 
+    def sparse_patterns(self):
+        """the stored patterns a sparse handle takes, CSC as (colptr, rowval) pairs, 0-based, rows ascending: Lxx (both triangles), gx, hx — the non-zeros of
+        _patterns(), from the index tables by np.unique on (column, row) pairs: nothing of size nx x nx or (ne + nc) x nx is allocated, whatever the horizon"""
+        rows = {D_LXX: self.nx, D_GX: self.ne, D_HX: self.nc}
+        keys = {D_LXX: [], D_GX: [], D_HX: []}          # column * rows + row: sorting the keys sorts by column, then row
+        for tp in self.templates:
+            if len(tp.jac):
+                f = D_GX if tp.cls == 1 else D_HX
+                keys[f].append((tp.d_j[:len(tp.jac)] * rows[f] + tp.d_i[:len(tp.jac)]).reshape(-1))
+            q0 = tp.n_value_partials + tp.n_grad_partials
+            if len(tp.hess):
+                i, j = tp.p_i[q0:q0 + len(tp.hess)].reshape(-1), tp.p_j[q0:q0 + len(tp.hess)].reshape(-1)
+                keys[D_LXX] += [j * self.nx + i, i * self.nx + j]
+        out = []
+        for f in (D_LXX, D_GX, D_HX):
+            key = np.unique(np.concatenate(keys[f])) if keys[f] else np.zeros(0, dtype=np.int64)
+            col, row = (key // rows[f], key % rows[f]) if rows[f] else (key, key)
+            colptr = np.zeros(self.nx + 1, dtype=np.int64)
+            np.cumsum(np.bincount(col, minlength=self.nx), out=colptr[1:])
+            out.append((colptr, np.ascontiguousarray(row, dtype=np.int64)))
+        return tuple(out)
+
     def structure(self):
         """dict(row_first, row_last, hessian_block_start) (1-based) for Solver(structure=...) when the Lagrangian Hessian falls into at least two diagonal blocks (it does
         when no stage function couples x_t with x_t+1 in its second derivatives: explicit dynamics), else None (implicit dynamics, the pendulum: a dense handle).
@@ -481,7 +505,8 @@ class TrajectoryProblem:
         return guess
 
     def get_trajectory(self, solver_or_variables):
-        w = solver_or_variables.solution.variables if hasattr(solver_or_variables, "solution") else np.asarray(solver_or_variables)
+        s = solver_or_variables
+        w = s.solution.variables if hasattr(s, "solution") else s.get("solution")[:self.nx] if isinstance(s, SparseKKT) else np.asarray(s)
         return [w[idx].copy() for idx in self.indices.states], [w[idx].copy() for idx in self.indices.actions]
 
     # ---- printing ----------------------------------------------------------------------------------------------------------------------------------
@@ -637,6 +662,34 @@ class TrajectoryProblem:
         (s.set_device_block_evaluator if st is not None else s.set_device_evaluator)(entry, user)
         return s
 
+    def sparse_solver(self, parameters=None, options=None, device=0, method="nested_dissection", perm=None, **compile_args):
+        """a SparseKKT on sparse_patterns() whose evaluations run in the generated library's <name>_sparse_eval: the route for problems whose Hessian couples
+        consecutive stages (implicit dynamics: structure() is None) and for horizons a dense handle cannot hold.  The cone layout and theta (default: zeros) are set;
+        every SparseKKT method works on it — initialize(x0), solve(), get("solution"), and get_trajectory(handle) here.  The handle keeps the library and the
+        evaluator's user object alive; close() frees them."""
+        import scipy.sparse as sp
+        built = self.compile(**compile_args)
+        L = built.cdll
+        create, destroy = getattr(L, self.name + "_user_create"), getattr(L, self.name + "_user_destroy")
+        create.restype, create.argtypes, destroy.argtypes = ctypes.c_void_p, [ctypes.POINTER(ctypes.c_int32), ctypes.c_int64], [ctypes.c_void_p]
+        blob = self.tables()
+        user = create(blob.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), blob.size)
+        if not user:
+            raise RuntimeError("%s_user_create refused the tables" % self.name)
+        try:
+            mats = [sp.csc_matrix((np.ones(len(rowval)), rowval, colptr), shape=(rows, self.nx))
+                    for (colptr, rowval), rows in zip(self.sparse_patterns(), (self.nx, self.ne, self.nc))]
+            dims = [len(c) for st in self.indices.second_order for c in st]
+            s = TrajectorySparseKKT(*mats, n_nonnegative=self.n_nonnegative, second_order_dims=dims, method=method, perm=perm, device=device, options=options)
+        except Exception:
+            destroy(user)
+            raise
+        s._trajectory, s._library, s._user, s._user_destroy = self, L, user, destroy
+        s.set_evaluator(ctypes.cast(getattr(L, self.name + "_sparse_eval"), ctypes.c_void_p), user, self.np)
+        if parameters is not None:
+            s.set_parameters(parameters)
+        return s
+
     def enqueued(self, solver):
         """how many operations (copies, fills, kernels) the last evaluation call of `solver`'s evaluator enqueued"""
         fn = getattr(solver._library, self.name + "_debug_last_enqueued")
@@ -657,5 +710,21 @@ class TrajectorySolver(Solver):
                 pass
         Solver.close(self)
         user, self._user = getattr(self, "_user", None), None
+        if user:
+            self._user_destroy(user)
+
+
+class TrajectorySparseKKT(SparseKKT):
+    """a SparseKKT that owns the generated library's user object"""
+
+    def close(self):
+        h = getattr(self, "_h", None)
+        user, self._user = getattr(self, "_user", None), None
+        if h is not None and h.value and user:
+            try:
+                self.set_evaluator(None)    # synchronises the handle's stream: the user object's buffers outlive the kernels that read them
+            except Exception:
+                pass
+        SparseKKT.close(self)
         if user:
             self._user_destroy(user)

@@ -131,6 +131,26 @@ typedef struct calipso_device_block_data {
 typedef int32_t (*calipso_device_block_eval_fn)(void* user, uint32_t flags, const double* x, const double* y, const double* z, const double* theta,
                                                 const calipso_device_block_data* out, void* hip_stream);
 
+/* The same for a SPARSE handle (calipso_hip_sparse_kkt_set_evaluator): the three matrices are the handle's own resident non-zero arrays on the patterns given to
+ * calipso_hip_sparse_kkt_create, in the caller's non-zero order — the next assemble reads what the evaluator wrote, nothing is copied.  An evaluator asked for a
+ * Jacobian / the Hessian writes EVERY stored non-zero of it (zeros included).  lagrangian_hessian holds both triangles and receives the sum of the terms whose bits are
+ * set: fxx (OBJECTIVE_HESSIAN) + (y'g)xx (EQUALITY_DUAL_HESSIAN) + (z'h)xx (CONE_DUAL_HESSIAN).  (g'y)x and (h'z)x are never asked for: the handle forms them from its
+ * column views on the fresh Jacobian values; no parameter-Jacobian bit is ever set either.  The six pattern arrays are HOST copies (1-based, as given to create), for an
+ * evaluator that builds its own address table on the first call.  The evaluator enqueues on hip_stream and returns without waiting; 0, or a code the handle reports. */
+typedef struct calipso_device_sparse_data {
+    double* objective;                       /* [1]  */
+    double* objective_gradient_variables;    /* [nx] */
+    double* equality_constraint;             /* [ne] */
+    double* cone_constraint;                 /* [nc] */
+    double* lagrangian_hessian;              /* nzval on the handle's Lxx pattern (both triangles): fxx + (y'g)xx + (z'h)xx, the terms whose bits are set */
+    double* equality_jacobian_variables;     /* nzval on the gx pattern */
+    double* cone_jacobian_variables;         /* nzval on the hx pattern */
+    const int64_t *Lxx_colptr, *Lxx_rowval, *gx_colptr, *gx_rowval, *hx_colptr, *hx_rowval;   /* HOST copies, 1-based, as given to create */
+    int64_t nx, np, ne, nc, nnz_Lxx, nnz_gx, nnz_hx;
+} calipso_device_sparse_data;
+typedef int32_t (*calipso_device_sparse_eval_fn)(void* user, uint32_t flags, const double* x, const double* y, const double* z, const double* theta,
+                                                 const calipso_device_sparse_data* out, void* hip_stream);
+
 /* callback_inner(custom, solver) / callback_outer(custom, solver)  (solver.jl:183,193; called at solve.jl:350,371) */
 typedef void (*calipso_callback_fn)(void* user, calipso_hip_solver* solver);
 
@@ -639,6 +659,34 @@ int32_t calipso_hip_sparse_kkt_set(calipso_hip_sparse_kkt*, const char* name, co
 int32_t calipso_hip_sparse_kkt_solution_device(calipso_hip_sparse_kkt*, double** p);
 int32_t calipso_hip_sparse_kkt_keep_trace(calipso_hip_sparse_kkt*, int64_t rows);
 int32_t calipso_hip_sparse_kkt_trace(calipso_hip_sparse_kkt*, double* out, int64_t cap_rows, int64_t* accepted);
+
+/* ---- solve! on sparse data with an evaluator: the same entries for NONLINEAR problems (csrc/sparse_solve.hip) ----------------------------------------------------
+ * With a calipso_device_sparse_eval_fn the kernels above read what the evaluator wrote instead of gathering the QP: fx, g, h and the objective (a device scalar) at the
+ * solution, the objective, g, h at a candidate.  gx'y and hx'z are still gathered from the handle's column views; residual, merit, norms and the cones are unchanged.
+ * Every evaluator call is an enqueue on the handle's stream: the host waits of solve stay 2 accepted + outer + trials.  With a deterministic evaluator a solve
+ * repeats bit for bit.
+ *   set_evaluator   fn with its user pointer and the number of parameters np.  Replaces qp_attach, and qp_attach replaces it: a handle holds one problem class.
+ *                   fn = NULL removes it.  Lxx, gx, hx need no set_values then: the evaluator writes them.  theta starts as zeros.
+ *   set_parameters  theta (np doubles; _device: a device pointer, checked as in set_values_device), resident on the handle
+ *   evaluate        the evaluator at the solution (which = 0: into objective, objective_gradient_variables, equality_constraint, cone_constraint) or at the candidate
+ *                   (which = 1: x from the candidate, y and z the solution's; the objective and the constraints go to the candidate's own buffers, the gradient and
+ *                   the matrices to the only ones there are).  Synchronised.  flags: CALIPSO_EVAL_* without the dual gradients and without any parameter-Jacobian
+ *                   bit — those return CALIPSO_ERR_ARGUMENT naming the bit.  An evaluation that writes a matrix invalidates the assembled K and its factor.
+ *   get             additionally objective (1 double: the evaluator's at the solution), lagrangian_hessian, equality_jacobian_variables and
+ *                   cone_jacobian_variables (the three resident non-zero arrays, on either problem class)
+ *   An evaluator's non-zero return r becomes CALIPSO_ERR_ARGUMENT (r = 1) or CALIPSO_ERR_HIP (others) with r in last_error; the handle stays usable.
+ *   Where the calls are made: one with every variable-side bit (objective, gradient, constraints, both Jacobians, the Hessian terms — the dual ones iff the option
+ *                   constraint_tensor — at the resident y, z) in front of every prologue, standing in for solve.jl:100-135 and :175-185; OBJECTIVE | EQUALITY | CONE at
+ *                   every candidate, between the kernel that forms the point and the one that reduces merit and violation; EQUALITY in front of initialize and of
+ *                   the accept that starts a solve.
+ *   Which point the matrices belong to: after solve returns, the resident Hessian and Jacobians are those of the RETURNED point (the last prologue's evaluation), with
+ *                   its y, z — not, as in the reference, those of the last search direction one iterate earlier.  differentiate / differentiate_adjoint therefore
+ *                   assemble with the matrices of the returned point and the slacks of quirk B-12 (above); on a QP the matrices are constant and nothing differs.
+ *                   They keep taking the caller's dR/dtheta: the handle does not ask the evaluator for parameter Jacobians. */
+int32_t calipso_hip_sparse_kkt_set_evaluator(calipso_hip_sparse_kkt*, calipso_device_sparse_eval_fn fn, void* user, int64_t np);
+int32_t calipso_hip_sparse_kkt_set_parameters(calipso_hip_sparse_kkt*, const double* theta);
+int32_t calipso_hip_sparse_kkt_set_parameters_device(calipso_hip_sparse_kkt*, const double* theta);
+int32_t calipso_hip_sparse_kkt_evaluate(calipso_hip_sparse_kkt*, int32_t which, uint32_t flags);
 
 /* ---- differentiate! on sparse problem data resident on the device (csrc/sparse_differentiate.hip; host and shared pieces: csrc/sparse_differentiate.hpp) -------
  * differentiate! (src/solver/differentiate.jl:1-61) in both directions on the same handle, for k columns in the launches of one: the condensed solve of

@@ -3,13 +3,14 @@
 //
 //     CALIPSO_TRAJECTORY_EVALUATOR(my_problem_type, my_problem)
 //
-// which emits the five entries
+// which emits the six entries
 //     my_problem_device_eval          calipso_device_eval_fn        (dense layout)
 //     my_problem_block_eval           calipso_device_block_eval_fn  (the packed blocks of a structured handle)
+//     my_problem_sparse_eval          calipso_device_sparse_eval_fn (the non-zero arrays of a sparse handle, on their stored patterns)
 //     my_problem_user_create          (the int32 blob of TrajectoryProblem.tables(), words) -> the user object, NULL when the blob is refused
 //     my_problem_user_destroy         (user object)
 //     my_problem_debug_last_enqueued  (user object) -> operations the last evaluation call enqueued
-// The two evaluators run the same kernels; they differ in the address table (entry -> offset in the destination), built once per handle on the first call by
+// The three evaluators run the same kernels; they differ in the address table (entry -> offset in the destination), built once per handle on the first call by
 // calipso_trajectory_tables.hpp — the plain C++ half: the blob's checks and every address computed on the host — and uploaded from pinned memory in one copy.  One call
 // enqueues at most four operations: that upload, the fill, the evaluation kernel, the finishing pass.
 //
@@ -120,13 +121,14 @@ struct Route {                                 // one layout of the destinations
     RouteTable t;
     int* pinned = nullptr; int* device = nullptr;
     const void* key0 = nullptr; int64_t key1 = 0;      // the layout it was built for: (descriptor array, first block's values) or (nullptr, jacobian_ld)
+    const void* key2 = nullptr; const void* key3 = nullptr;      // ... or, with key0, the three nzval arrays of a sparse handle
     double* block_base = nullptr;
 };
 
 struct User {
     Tables t;
     double* part = nullptr;
-    Route dense, block;
+    Route dense, block, sparse;
     int last_enqueued = 0;
 };
 
@@ -194,7 +196,7 @@ template <class S> void* user_create(const int32_t* blob, int64_t words) {
 inline void user_destroy(void* p) {
     User* u = (User*)p;
     if (!u) return;
-    free_route(u->dense); free_route(u->block);
+    free_route(u->dense); free_route(u->block); free_route(u->sparse);
     if (u->part) (void)hipFree(u->part);
     delete u;
 }
@@ -246,6 +248,29 @@ int32_t block_eval(void* user, uint32_t flags, const double* x, const double* y,
     return run<S>(u, r, flags, x, y, z, theta, base, stream);
 }
 
+// the sparse handle's route: the Jacobians' and the Hessian's non-zeros go to their positions in the handle's nzval arrays.  It has no destination for the dual
+// gradients (the handle gathers them) nor for anything with respect to theta: such flags are code 1
+template <class S>
+int32_t sparse_eval(void* user, uint32_t flags, const double* x, const double* y, const double* z, const double* theta, const calipso_device_sparse_data* out,
+                    void* hip_stream) {
+    User* u = (User*)user;
+    if (!u || !out || out->nx != u->t.nx || out->ne != u->t.ne || out->nc != u->t.nc || out->np != u->t.np) return 1;
+    if (flags & (CALIPSO_EVAL_EQUALITY_DUAL_GRADIENT | CALIPSO_EVAL_CONE_DUAL_GRADIENT | CALIPSO_EVAL_EQUALITY_JACOBIAN_PARAMETERS | CALIPSO_EVAL_CONE_JACOBIAN_PARAMETERS | LPAR)) return 1;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    u->last_enqueued = 0;
+    Route& r = u->sparse;
+    if (r.ready && (r.key0 != out->lagrangian_hessian || r.key2 != out->equality_jacobian_variables || r.key3 != out->cone_jacobian_variables)) return 3;
+    if (!r.ready) {
+        r.key0 = out->lagrangian_hessian; r.key2 = out->equality_jacobian_variables; r.key3 = out->cone_jacobian_variables;
+        int rc = sparse_route(shape_of<S>(), u->t, out, r.t);
+        if (!rc) rc = upload(u, r, stream);
+        if (rc) { free_route(r); return rc; }
+    }
+    double* base[N_DEST] = {out->objective_gradient_variables, out->equality_constraint, out->cone_constraint, out->equality_jacobian_variables,
+                            out->cone_jacobian_variables, nullptr, nullptr, out->objective, nullptr, nullptr, out->lagrangian_hessian, nullptr};
+    return run<S>(u, r, flags, x, y, z, theta, base, stream);
+}
+
 }  // namespace trajectory
 }  // namespace calipso
 
@@ -261,5 +286,9 @@ int32_t block_eval(void* user, uint32_t flags, const double* x, const double* y,
     __attribute__((visibility("default"))) int32_t name##_block_eval(void* user, uint32_t flags, const double* x, const double* y, const double* z, const double* theta, \
                                                                      const calipso_device_block_data* out, void* hip_stream) { \
         return calipso::trajectory::block_eval<S>(user, flags, x, y, z, theta, out, hip_stream); \
+    } \
+    __attribute__((visibility("default"))) int32_t name##_sparse_eval(void* user, uint32_t flags, const double* x, const double* y, const double* z, const double* theta, \
+                                                                      const calipso_device_sparse_data* out, void* hip_stream) { \
+        return calipso::trajectory::sparse_eval<S>(user, flags, x, y, z, theta, out, hip_stream); \
     } \
     }

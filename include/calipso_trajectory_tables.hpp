@@ -4,6 +4,7 @@
 //   parse_tables   the blob -> Tables, or false when it does not fit the library's Shape or an index lies outside its range
 //   dense_route    the int32 table of a route for the dense layout (calipso_device_problem_data, leading dimension jacobian_ld)
 //   block_route    the same for the packed blocks of a structured handle (calipso_device_block_data)
+//   sparse_route   the same for the three non-zero arrays of a sparse handle on their stored patterns (calipso_device_sparse_data)
 // A route's table: per template its index tables as they are and its ADDRESS TABLE (entry -> offset in the destination), the finishing pass's addresses, field and
 // slot lists, and the fill's chunks (offset, length <= CHUNK) by category.  Return codes: 0, 1 an argument that does not fit, 4 a non-zero outside the declared
 // structure or a destination beyond 2^31 entries, 5 segments out of order (2 and 3 belong to calipso_trajectory.hpp: a HIP call failed, the layout changed).
@@ -129,6 +130,30 @@ struct BlockLayout {
     }
 };
 
+// the stored patterns of a sparse handle (calipso_device_sparse_data: CSC, 1-based, rows ascending within a column): a non-zero's address is its position in the
+// nzval array, found by binary search in its column; -1 where the pattern has no such entry.  D_GP, D_HP and D_LGP have no destination on this route — the flags that
+// would store through them are refused and their base is NULL — so they get address 0, which nothing stores through
+struct SparseLayout {
+    const calipso_device_sparse_data* o;
+    static int64_t find(const int64_t* colptr, const int64_t* rowval, int64_t i, int64_t j) {
+        int64_t lo = colptr[j] - 1, hi = colptr[j + 1] - 1;
+        while (lo < hi) {
+            const int64_t mid = lo + (hi - lo) / 2;
+            if (rowval[mid] < i + 1) lo = mid + 1; else hi = mid;
+        }
+        return lo < colptr[j + 1] - 1 && rowval[lo] == i + 1 ? lo : -1;
+    }
+    int64_t operator()(int dest, int64_t i, int64_t j) const {
+        switch (dest) {
+        case D_GX: return find(o->gx_colptr, o->gx_rowval, i, j);
+        case D_HX: return find(o->hx_colptr, o->hx_rowval, i, j);
+        case D_LXX: return find(o->Lxx_colptr, o->Lxx_rowval, i, j);
+        case D_GP: case D_HP: case D_LGP: return 0;
+        default: return -1;
+        }
+    }
+};
+
 struct RouteTable {                            // one layout of the destinations: the words to upload and where each table starts in them
     std::vector<int32_t> words;
     std::vector<int> vi, ri, pi, ad;           // per template
@@ -211,6 +236,28 @@ inline int block_route(const Shape& sh, const Tables& u, const calipso_device_bl
     add_parameter_segments(segs, u);
     *base = where.base;
     return build_table(sh, u, where, segs, r);
+}
+
+// a stored pattern as a route can address it: 1-based, column pointers from 1 to nnz + 1 without a decrease, rows in range, ascending and duplicate-free within a
+// column (what the binary search of SparseLayout relies on), fewer than 2^31 non-zeros
+inline bool sparse_pattern_ok(const int64_t* colptr, const int64_t* rowval, int64_t rows, int64_t cols, int64_t nnz) {
+    if (nnz < 0 || nnz >= (int64_t)1 << 31 || rows < 0 || cols < 0 || !colptr || (nnz > 0 && !rowval) || colptr[0] != 1 || colptr[cols] != nnz + 1) return false;
+    for (int64_t j = 0; j < cols; ++j) {
+        if (colptr[j + 1] < colptr[j] || colptr[j + 1] > nnz + 1) return false;
+        for (int64_t p = colptr[j] - 1; p < colptr[j + 1] - 1; ++p)
+            if (rowval[p] < 1 || rowval[p] > rows || (p > colptr[j] - 1 && rowval[p - 1] >= rowval[p])) return false;
+    }
+    return true;
+}
+
+// the route of a sparse handle: one fill segment per nzval array; 1 for sizes that are not the tables' or a pattern sparse_pattern_ok refuses
+inline int sparse_route(const Shape& sh, const Tables& u, const calipso_device_sparse_data* out, RouteTable& r) {
+    if (!out || out->nx != u.nx || out->ne != u.ne || out->nc != u.nc || out->np != u.np) return 1;
+    if (!sparse_pattern_ok(out->Lxx_colptr, out->Lxx_rowval, u.nx, u.nx, out->nnz_Lxx) || !sparse_pattern_ok(out->gx_colptr, out->gx_rowval, u.ne, u.nx, out->nnz_gx) ||
+        !sparse_pattern_ok(out->hx_colptr, out->hx_rowval, u.nc, u.nx, out->nnz_hx)) return 1;
+    std::vector<Segment> segs;
+    add_segment(segs, 0, 0, out->nnz_gx); add_segment(segs, 1, 0, out->nnz_hx); add_segment(segs, 2, 0, out->nnz_Lxx);
+    return build_table(sh, u, SparseLayout{out}, segs, r);
 }
 
 }  // namespace trajectory

@@ -1071,9 +1071,10 @@ class SparseKKT(_Handle):
         if given and all(self._is_device(a) for a in given):
             ptrs = [self._device_pointer(a, nm, ct) for a, nm, ct in zip((q, b, h), ("q", "b", "h"), counts)]
             self._check(self._L.calipso_hip_sparse_kkt_qp_attach_device(self._h, *ptrs, float(objective_constant)), "sparse_kkt_qp_attach_device")
-            return
-        arrs = [None if a is None else self._host_vector(a, nm, ct) for a, nm, ct in zip((q, b, h), ("q", "b", "h"), counts)]
-        self._check(self._L.calipso_hip_sparse_kkt_qp_attach(self._h, *[_opt(a) for a in arrs], float(objective_constant)), "sparse_kkt_qp_attach")
+        else:
+            arrs = [None if a is None else self._host_vector(a, nm, ct) for a, nm, ct in zip((q, b, h), ("q", "b", "h"), counts)]
+            self._check(self._L.calipso_hip_sparse_kkt_qp_attach(self._h, *[_opt(a) for a in arrs], float(objective_constant)), "sparse_kkt_qp_attach")
+        self._parameter_nnz = None              # (the attached QP replaced an evaluator and its parameter patterns)
 
     def initialize(self, x0):
         """initialize!(solver, x0): x <- x0, slacks and duals as initialize.jl:9-48 (x0: a host array, or a CUDA tensor / device pointer)"""
@@ -1133,6 +1134,7 @@ class SparseKKT(_Handle):
         fn = None if fn_ptr is None else C.cast(fn_ptr, C.c_void_p)
         self._check(self._L.calipso_hip_sparse_kkt_set_evaluator(self._h, fn, user, int(num_parameters)), "sparse_kkt_set_evaluator")
         self.num_parameters = int(num_parameters) if fn_ptr is not None else 0
+        self._parameter_nnz = None
 
     def set_parameters(self, theta):
         """theta of the evaluator (num_parameters entries), resident on the handle: a host array, or a CUDA tensor / device pointer"""
@@ -1145,6 +1147,36 @@ class SparseKKT(_Handle):
     def evaluate(self, flags, which=0):
         """the evaluator at the solution (which = 0) or at the candidate (1), synchronised: CALIPSO_EVAL_* bits without the dual gradients and the parameter Jacobians"""
         self._check(self._L.calipso_hip_sparse_kkt_evaluate(self._h, int(which), int(flags)), "sparse_kkt_evaluate")
+
+    PARAMETER_ARRAYS = ("lagrangian_gradient_parameters", "equality_jacobian_parameters", "cone_jacobian_parameters")
+
+    def set_parameter_patterns(self, Lp, gp, hp):
+        """the stored patterns of dR/dtheta's three non-zero blocks, each with num_parameters columns: Lp (nx rows, the Lagrangian's theta-gradient), gp (ne rows), hp (nc
+        rows) — scipy sparse matrices (their patterns, CSC) or 0-based (colptr, rowval) pairs with rows ascending within a column.  The evaluator then writes the values
+        (evaluate_parameters, get(name)) and differentiate() / vjp(theta=True) take dR/dtheta from it; nothing of size N x num_parameters exists.  set_evaluator and
+        attach_qp drop the patterns"""
+        arrs = []
+        for M in (Lp, gp, hp):
+            if hasattr(M, "tocsc"):
+                M = M.tocsc()
+                M.sort_indices()
+                colptr, rowval = M.indptr, M.indices
+            else:
+                colptr, rowval = M
+            arrs += [np.ascontiguousarray(colptr, dtype=np.int64).reshape(-1) + 1, np.ascontiguousarray(rowval, dtype=np.int64).reshape(-1) + 1]
+        count = getattr(self, "num_parameters", 0)
+        for name, colptr, rowval in zip(("Lp", "gp", "hp"), arrs[0::2], arrs[1::2]):      # (the library reads colptr[num_parameters] and that many rows)
+            if colptr.size != count + 1 or colptr[-1] - 1 != rowval.size:
+                raise CalipsoHipError("SparseKKT.set_parameter_patterns: %s has %d column pointers and %d rows; the evaluator takes %d parameters" % (name, colptr.size, rowval.size, count))
+        self._check(self._L.calipso_hip_sparse_kkt_set_parameter_patterns(self._h, *[_pi(a) if a.size else None for a in arrs]), "sparse_kkt_set_parameter_patterns")
+        self._parameter_nnz = tuple(int(a.size) for a in arrs[1::2])
+
+    def evaluate_parameters(self):
+        """the evaluator's five parameter bits at the resident x, y, z, theta into the three resident arrays of set_parameter_patterns, synchronised"""
+        self._check(self._L.calipso_hip_sparse_kkt_evaluate_parameters(self._h), "sparse_kkt_evaluate_parameters")
+
+    def _has_parameter_patterns(self):
+        return getattr(self, "_parameter_nnz", None) is not None and getattr(self, "num_parameters", 0) > 0
 
     # ---- differentiate! on the same handle (include/calipso_hip.h, "differentiate! on sparse problem data"; csrc/sparse_differentiate.hip) -------------------
     GRADIENTS = "LqgbHh"      # the data gradients of vjp by letter: Lxx, q, gx, b, hx, hvec — the matrices as the values on their stored patterns
@@ -1173,20 +1205,46 @@ class SparseKKT(_Handle):
         return self._columns_call("sparse_kkt_solve_columns", B, "SparseKKT.solve_columns: B must be (N,) or (N, k)", lambda dev, k, b, x:
                                   (L.calipso_hip_sparse_kkt_solve_columns_device if dev else L.calipso_hip_sparse_kkt_solve_columns)(self._h, k, 1 if transposed else 0, b, x))
 
-    def differentiate(self, J):
+    def differentiate(self, J=None, columns=None, device=False):
         """forward differentiate! for the caller's dR/dtheta J (N,) or (N, k): one factorisation at the (ep, ed) the handle holds, then S = -M J (with the correction rounds
-        under set_option("differentiate_refinement", 1): differentiate_info)"""
+        under set_option("differentiate_refinement", 1): differentiate_info).  J=None: the evaluator's own dR/dtheta on the stored patterns of set_parameter_patterns,
+        evaluated at the resident point and theta — all num_parameters columns, or those of `columns` (0-based parameter indices, repeats allowed); the result is
+        (N, k), bit for bit what differentiate(J) gives for the same block; device=True returns it as a CUDA tensor"""
         L = self._L
+        if J is None:
+            if columns is None:
+                k, cp = getattr(self, "num_parameters", 0), None
+            else:
+                cols = np.ascontiguousarray(columns, dtype=np.int64).reshape(-1) + 1
+                k, cp = int(cols.size), _pi(cols)
+            if device:
+                import torch
+                out = torch.empty((max(k, 1), self.N), dtype=torch.float64, device=torch.device("cuda", self.device))
+                self._check(L.calipso_hip_sparse_kkt_differentiate_parameters_device(self._h, k, cp, C.c_void_p(out.data_ptr())), "sparse_kkt_differentiate_parameters_device")
+                return out[:k].t()
+            out = np.zeros((max(k, 1), self.N))
+            self._check(L.calipso_hip_sparse_kkt_differentiate_parameters(self._h, k, cp, _pd(out)), "sparse_kkt_differentiate_parameters")
+            return out[:k].T.copy()
+        if columns is not None:
+            raise ValueError("SparseKKT.differentiate: columns selects parameters of the evaluator's dR/dtheta (J=None); a J of the caller's is taken whole")
         return self._columns_call("sparse_kkt_differentiate", J, "SparseKKT.differentiate: J must be (N,) or (N, k)", lambda dev, k, j, s:
                                   (L.calipso_hip_sparse_kkt_differentiate_device if dev else L.calipso_hip_sparse_kkt_differentiate)(self._h, k, j, s))
 
-    def vjp(self, V, adjoint=True, qp=""):
+    def vjp(self, V, adjoint=True, qp="", theta=None):
         """reverse differentiate! for cotangents V = dLoss/dw (N,) or (N, k): the same factorisation, lambda = M' V, and the gradients of the loss with respect to the data
         named in qp, letters out of "LqgbHh" = Lxx, q, gx, b, hx, hvec: vectors as they are, matrices as the values ON THEIR STORED PATTERNS in the handle's non-zero
         order.  A handle from SparseConicQP also takes "P", "A", "G": gradients on the stored patterns of the P, A, G it was given (grad_P = c (gLxx(i, j) + gLxx(j, i)),
         grad_A = g_gx, grad_G = -g_hx).  Returns a dict: "adjoint" (unless adjoint=False) and one entry per letter, each with a trailing k axis only when V had one.
-        A CUDA tensor takes the device route and everything comes back as CUDA tensors"""
+        A CUDA tensor takes the device route and everything comes back as CUDA tensors.
+        theta (default: True on a handle with set_parameter_patterns, else False): additionally "theta" = dLoss/dtheta = -R_theta' lambda (num_parameters,) or
+        (num_parameters, k), from the evaluator's dR/dtheta on its stored patterns at the resident point and theta — no host evaluation, no dense array"""
         qp = qp or ""
+        if theta is None:
+            theta = self._has_parameter_patterns()
+        if theta:
+            if qp:
+                raise ValueError("SparseKKT.vjp: theta belongs to a handle with an evaluator, qp to one with an attached QP")
+            return self._vjp_theta(V, adjoint)
         if any(c not in self.GRADIENTS + "PAG" for c in qp):
             raise ValueError("SparseKKT.vjp: qp is a string of letters out of 'LqgbHh' (and 'PAG' on a handle from SparseConicQP)")
         if any(c in "PAG" for c in qp) and not hasattr(self, "_conic_qp"):
@@ -1226,6 +1284,33 @@ class SparseKKT(_Handle):
             elif c == "G":
                 g = -g
             out[c] = shape(g)
+        return out
+
+    def _vjp_theta(self, V, adjoint):
+        message, npar = "SparseKKT.vjp: V must be (N,) or (N, k)", getattr(self, "num_parameters", 0)
+        if self._is_device(V) and hasattr(V, "is_cuda"):
+            import torch
+            if V.dim() not in (1, 2) or V.shape[0] != self.N:
+                raise ValueError(message)
+            squeeze, k = V.dim() == 1, (1 if V.dim() == 1 else int(V.shape[1]))
+            where = torch.device("cuda", self.device)
+            src = V.detach().reshape(self.N, k).t().contiguous()
+            adj = torch.empty((k, self.N), dtype=torch.float64, device=where) if adjoint else None
+            grad = torch.empty((k, max(npar, 1)), dtype=torch.float64, device=where)
+            self._check(self._L.calipso_hip_sparse_kkt_differentiate_adjoint_parameters_device(self._h, k, self._device_pointer(src, "V", k * self.N),
+                                                                                               C.c_void_p(adj.data_ptr()) if adjoint else None, C.c_void_p(grad.data_ptr())),
+                        "sparse_kkt_differentiate_adjoint_parameters_device")
+            shape = lambda t: t[0] if squeeze else t.t()
+            grad = grad[:, :npar]
+        else:
+            flat, k, squeeze = pack_cotangent(V, (), self.N, message)
+            adj = np.zeros((k, self.N)) if adjoint else None
+            grad = np.zeros((k, max(npar, 1)))
+            self._check(self._L.calipso_hip_sparse_kkt_differentiate_adjoint_parameters(self._h, k, _pd(flat), _opt(adj), _pd(grad)), "sparse_kkt_differentiate_adjoint_parameters")
+            shape = lambda a: a[0].copy() if squeeze else a.T.copy()
+            grad = grad[:, :npar]
+        out = {"adjoint": shape(adj)} if adjoint else {}
+        out["theta"] = shape(grad)
         return out
 
     def _conic_qp_positions(self, device):
@@ -1269,6 +1354,8 @@ class SparseKKT(_Handle):
         if name == "differentiate_slacks":      # (not a vector of the reference's solver: the s, then the t that differentiate! forms the cone blocks at)
             return 2 * self.nc
         extra = dict(objective=1, lagrangian_hessian=self.nnz[0], equality_jacobian_variables=self.nnz[1], cone_jacobian_variables=self.nnz[2])
+        if name in self.PARAMETER_ARRAYS:       # the resident values of dR/dtheta's three blocks on their stored patterns (set_parameter_patterns)
+            return (getattr(self, "_parameter_nnz", None) or (0, 0, 0))[self.PARAMETER_ARRAYS.index(name)]
         if name in extra:                       # the evaluator's objective at the solution; the three resident non-zero arrays on their stored patterns
             return extra[name]
         return getattr(self, self.VECTORS[name]) if name in self.VECTORS else 0

@@ -10,6 +10,10 @@
 //   correction rounds              iterative_refinement.jl:14-44 on all columns with the decisions of sensitivity_columns.hpp and the masked accumulate / restore of
 //                                  vectors.hip (the ones columns.hip launches).
 //   data gradients                 one launch, one thread per (stored non-zero or vector entry, column), the entry index fastest.
+//   parameter Jacobians            with set_parameter_patterns the evaluator writes Lx,theta, g,theta, h,theta as values on three stored CSC patterns (np columns).  Forward:
+//                                  a clear of V and one launch scatter the selected columns of dR/dtheta into it, one writer per address.  Reverse: grad_theta = -R_theta' lambda
+//                                  is a gather over the three columns in stored order — a thread per (short parameter, column), a wavefront with a fixed-order cross-lane
+//                                  sum per (long parameter, column); the split length is sparse_parameters.hpp's SPLIT_LENGTH.
 // Gathers only: no floating-point atomics (the norm: atomicMax on the bit patterns of non-negative doubles, which is order-independent); a call repeats bit for bit.
 #include <algorithm>
 #include <cstring>
@@ -18,17 +22,23 @@
 
 #include "sparse_kkt_handle.hpp"
 #include "sparse_differentiate.hpp"
+#include "sparse_parameters.hpp"           // the stored patterns of dR/dtheta: the column selection's check, the short / long split, the launch geometry
+#include "../../include/calipso_wave.hpp"  // wave_sum_l63
 
 using calipso::i64;
 using namespace calipso::sparse_kkt;
 using namespace calipso::sparse_differentiate;
 typedef calipso_hip_sparse_kkt KH;
+static_assert(KT == calipso::sparse_parameters::THREADS && KT % calipso::sparse_parameters::WAVE == 0,
+              "sparse_parameters.hpp counts workgroups of KT threads, and a wavefront of the gradient kernel lies within one of them");
 
 struct calipso::sparse_kkt::DiffState {
     double* ws = nullptr; size_t doubles = 0;     // the workspace of a k-column pass (sparse_differentiate.hpp: Layout): grown on demand, kept
     int* masks = nullptr; size_t ints = 0;
     double* wd = nullptr;                         // N: the resident point with the kept slacks in its s and t rows (what the kernels read the cone blocks from)
     double* gbuf = nullptr; size_t gdoubles = 0;  // the gradients of a host call before they are copied out
+    int* sel = nullptr; size_t sel_ints = 0;      // the selected parameters of a differentiate_parameters call, 0-based
+    std::vector<int> sel_host;
     calipso::SensitivityColumns cols;
     std::vector<double> norms;
     double info_forward[4] = {0, 0, 0, 0}, info_reverse[4] = {0, 0, 0, 0}, times[3] = {0, 0, 0};
@@ -209,6 +219,51 @@ __global__ __launch_bounds__(KT) void k_diff_gradients(const KktDev d, const dou
     if (e < d.nc && out.p[5]) out.p[5][col * (size_t)d.nc + e] = -lz[e];
 }
 
+// ---- dR/dtheta on its stored patterns ------------------------------------------------------------------------------------------------------------------------------
+// the selected columns into V (N x k, cleared before): thread e of column `col` writes entry e of parameter sel[col] (NULL: col itself) — the entries of Lx,theta into the
+// x rows, then those of g,theta into the y rows, then those of h,theta into the z rows.  Rows are duplicate-free within a column: one writer per address
+__global__ __launch_bounds__(KT) void k_diff_parameter_columns(const KktDev d, const ParamDev p, const int* __restrict__ sel, double* __restrict__ V) {
+    long long e = (long long)blockIdx.x * KT + threadIdx.x;
+    const size_t col = blockIdx.y;
+    const int j = sel ? sel[col] : (int)col;
+    double* v = V + col * (size_t)d.N;
+    const int off[3] = {0, d.o_y, d.o_z};
+    for (int m = 0; m < 3; ++m) {
+        const int lo = p.ptr[m][j], len = p.ptr[m][j + 1] - lo;
+        if (e < len) { v[off[m] + p.idx[m][lo + e]] = p.val[m][lo + e]; return; }
+        e -= len;
+    }
+}
+// grad_theta(j, col) = -(sum Lx,theta(i, j) lam_x[i] + sum g,theta(e, j) lam_y[e] + sum h,theta(m, j) lam_z[m]), the three columns in stored order.  Items
+// [0, np): one thread per parameter, whole sum in stored order (a long parameter's thread returns); [long0, ..): one wavefront per long parameter, lane l the entries
+// l, l + 64, ... of each array in turn, then the fixed tree of wave_sum_l63.  No atomics: one writer per (parameter, column)
+__global__ __launch_bounds__(KT) void k_diff_parameter_gradient(const KktDev d, const ParamDev p, const double* __restrict__ LAM, double* __restrict__ out) {
+    const long long item = (long long)blockIdx.x * KT + threadIdx.x;
+    const size_t col = blockIdx.y;
+    const double* lam = LAM + col * (size_t)d.N;
+    const int off[3] = {0, d.o_y, d.o_z};
+    if (item < p.long0) {
+        if (item >= p.np) return;
+        const int j = (int)item;
+        int len = 0;
+        for (int m = 0; m < 3; ++m) len += p.ptr[m][j + 1] - p.ptr[m][j];
+        if (len >= calipso::sparse_parameters::SPLIT_LENGTH) return;
+        double acc = 0.0;
+        for (int m = 0; m < 3; ++m)
+            for (int q = p.ptr[m][j]; q < p.ptr[m][j + 1]; ++q) acc += p.val[m][q] * lam[off[m] + p.idx[m][q]];
+        out[col * (size_t)p.np + j] = -acc;
+        return;
+    }
+    const long long w = (item - p.long0) >> 6;                                  // (wavefront-uniform: long0 and KT are multiples of 64)
+    if (w >= p.n_long) return;
+    const int lane = threadIdx.x & 63, j = p.long_columns[w];
+    double acc = 0.0;
+    for (int m = 0; m < 3; ++m)
+        for (int q = p.ptr[m][j] + lane; q < p.ptr[m][j + 1]; q += 64) acc += p.val[m][q] * lam[off[m] + p.idx[m][q]];
+    acc = calipso::wave_sum_l63(acc);
+    if (lane == 63) out[col * (size_t)p.np + j] = -acc;
+}
+
 __global__ __launch_bounds__(KT) void k_diff_scale(size_t count, const double* __restrict__ x, double* __restrict__ y, double a) {
     const size_t i = (size_t)blockIdx.x * KT + threadIdx.x;
     if (i < count) y[i] = a * x[i];
@@ -365,18 +420,46 @@ int solve_columns(KH* s, const char* entry, int64_t k, int32_t transposed, const
     return pass_times(s);
 }
 
-int differentiate(KH* s, const char* entry, int64_t k, const double* jacobian_parameters, double* sensitivity, bool device) {
+// the selected columns of the evaluator's dR/dtheta -> L.V: the evaluator's call, a clear, one launch (columns: k 1-based host indices, NULL = all)
+int take_parameter_columns(KH* s, const char* entry, const Layout& L, int64_t k, const int64_t* columns) {
+    DS* t = s->diff;
+    int rc = parameters_enqueue(s, entry);
+    if (rc < 0) return rc;
+    const int* sel = nullptr;
+    if (columns) {
+        if ((rc = grow(s, &t->sel, &t->sel_ints, (size_t)k)) < 0) return rc;
+        t->sel_host.resize((size_t)k);
+        for (int64_t c = 0; c < k; ++c) t->sel_host[(size_t)c] = (int)(columns[c] - 1);
+        KK(hipMemcpyAsync(t->sel, t->sel_host.data(), sizeof(int) * (size_t)k, hipMemcpyHostToDevice, s->st));
+        sel = t->sel;
+    }
+    double* V = t->ws + L.V.off;
+    KK(hipMemsetAsync(V, 0, sizeof(double) * L.V.len, s->st));
+    hipLaunchKernelGGL(k_diff_parameter_columns, dim3(calipso::sparse_parameters::scatter_blocks(s->par.longest), (unsigned)k), dim3(KT), 0, s->st, s->d, s->par.d, sel, V);
+    return CALIPSO_OK;
+}
+
+// jacobian_parameters: the caller's N x k block; NULL (parameters = true): the selected columns of the evaluator's dR/dtheta
+int differentiate(KH* s, const char* entry, int64_t k, const double* jacobian_parameters, double* sensitivity, bool device, bool parameters = false, const int64_t* columns = nullptr) {
     if (!s) return CALIPSO_ERR_ARGUMENT;
-    REFUSE(check_columns(entry, k));
-    REFUSE(check_array(entry, "jacobian_parameters", jacobian_parameters)); REFUSE(check_array(entry, "sensitivity", sensitivity));
+    if (parameters) {
+        if (!s->par.set) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": no parameter patterns set (calipso_hip_sparse_kkt_set_parameter_patterns first)");
+        REFUSE(calipso::sparse_parameters::check_selection(entry, s->par.d.np, k, columns));
+    } else {
+        REFUSE(check_columns(entry, k));
+        REFUSE(check_array(entry, "jacobian_parameters", jacobian_parameters));
+    }
+    REFUSE(check_array(entry, "sensitivity", sensitivity));
     KK(hipSetDevice(s->device));
-    DEVPTR(jacobian_parameters); DEVPTR(sensitivity);
+    if (!parameters) DEVPTR(jacobian_parameters);
+    DEVPTR(sensitivity);
     int rc = kkt_values_missing(s, entry);
     if (rc < 0 || (rc = ensure_state(s)) < 0) return rc;
     DS* t = s->diff;
     const bool rounds = rounds_wanted(s);
     const Layout L = layout((size_t)s->d.N, (size_t)s->d.n, (size_t)k, rounds);
-    if ((rc = reserve_pass(s, L, (size_t)k)) < 0 || (rc = take_columns(s, L, jacobian_parameters, device)) < 0) return rc;
+    if ((rc = reserve_pass(s, L, (size_t)k)) < 0) return rc;
+    if ((rc = parameters ? take_parameter_columns(s, entry, L, k, columns) : take_columns(s, L, jacobian_parameters, device)) < 0) return rc;
     const double info0[4] = {(double)k, 0, 0, 0};
     std::copy(info0, info0 + 4, t->info_forward);
     const KktDev d = slacks_view(s);
@@ -393,12 +476,19 @@ int differentiate(KH* s, const char* entry, int64_t k, const double* jacobian_pa
     return pass_times(s);
 }
 
-int differentiate_adjoint(KH* s, const char* entry, int64_t k, const double* cotangent, double* adjoint, double* const* grad, bool device) {
+// parameters: grad_theta (np x k) = -R_theta' lambda from the evaluator's dR/dtheta on its stored patterns, instead of the QP's data gradients
+int differentiate_adjoint(KH* s, const char* entry, int64_t k, const double* cotangent, double* adjoint, double* const* grad, bool device, bool parameters = false,
+                          double* grad_theta = nullptr) {
     if (!s) return CALIPSO_ERR_ARGUMENT;
     REFUSE(check_columns(entry, k));
     REFUSE(check_array(entry, "cotangent", cotangent));
+    if (parameters) {
+        if (!s->par.set) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": no parameter patterns set (calipso_hip_sparse_kkt_set_parameter_patterns first)");
+        REFUSE(check_array(entry, "grad_theta", grad_theta));
+    }
     KK(hipSetDevice(s->device));
     DEVPTR(cotangent); DEVPTR(adjoint);
+    if (parameters) DEVPTR(grad_theta);
     static const char* const names[6] = {"grad[0] (Lxx)", "grad[1] (q)", "grad[2] (gx)", "grad[3] (b)", "grad[4] (hx)", "grad[5] (hvec)"};
     bool wanted = false;
     for (int i = 0; grad && i < 6; ++i) if (grad[i]) { wanted = true; if (device) { const int rc = kkt_device_pointer(s, grad[i], entry, names[i]); if (rc < 0) return rc; } }
@@ -419,11 +509,18 @@ int differentiate_adjoint(KH* s, const char* entry, int64_t k, const double* cot
         size_t at = 0;
         for (int i = 0; i < 6; ++i) if (grad[i]) { out.p[i] = t->gbuf + at; at += sizes[i] * (size_t)k; }
     } else if (wanted) for (int i = 0; i < 6; ++i) out.p[i] = grad[i];
+    const size_t theta_count = parameters ? (size_t)s->par.d.np * (size_t)k : 0;
+    double* theta_out = grad_theta;
+    if (parameters && !device) {                                                              // ... and so is a host call's grad_theta
+        if ((rc = grow(s, &t->gbuf, &t->gdoubles, theta_count)) < 0) return rc;
+        theta_out = t->gbuf;
+    }
     const double info0[4] = {(double)k, 0, 0, 0};
     std::copy(info0, info0 + 4, t->info_reverse);
     t->times[0] = t->times[1] = t->times[2] = 0.0;
     KK(hipEventRecord(t->ev[0], s->st));
     if ((rc = take_columns(s, L, cotangent, device)) < 0) return rc;
+    if (parameters && (rc = parameters_enqueue(s, entry)) < 0) return rc;                     // dR/dtheta at the resident point and theta, on the handle's stream
     const KktDev d = slacks_view(s);
     if ((rc = factorize_held(s, d)) < 0) return rc;
     double *w = t->ws, *V = w + L.V.off, *X = w + L.X.off;
@@ -437,8 +534,15 @@ int differentiate_adjoint(KH* s, const char* entry, int64_t k, const double* cot
         hipLaunchKernelGGL(k_diff_gradients, dim3(blocks_of(items), (unsigned)k), dim3(KT), 0, s->st, h, s->w, X, out);      // x, y, z: the resident point's
         KK(hipEventRecord(t->ev[3], s->st));
     }
+    if (parameters) {
+        const calipso::sparse_parameters::Geometry geo = calipso::sparse_parameters::geometry(s->par.d.np, s->par.d.n_long);
+        KK(hipEventRecord(t->ev[2], s->st));
+        hipLaunchKernelGGL(k_diff_parameter_gradient, dim3(geo.blocks, (unsigned)k), dim3(KT), 0, s->st, h, s->par.d, X, theta_out);
+        KK(hipEventRecord(t->ev[3], s->st));
+    }
     KK(hipEventRecord(t->ev[1], s->st));
     if ((rc = give_columns(s, X, L.X.len, adjoint, device)) < 0) return rc;
+    if (parameters && !device && (rc = give_columns(s, theta_out, theta_count, grad_theta, false)) < 0) return rc;
     if (wanted && !device) for (int i = 0; i < 6; ++i) if (grad[i] && (rc = give_columns(s, out.p[i], sizes[i] * (size_t)k, grad[i], false)) < 0) return rc;
     KK(hipEventRecord(t->ev[4], s->st));
     KK(hipStreamSynchronize(s->st));
@@ -446,7 +550,7 @@ int differentiate_adjoint(KH* s, const char* entry, int64_t k, const double* cot
     float ms = 0.f;
     KK(hipEventElapsedTime(&ms, t->ev[0], t->ev[1])); t->times[0] = ms;
     KK(hipEventElapsedTime(&ms, t->ev[1], t->ev[4])); t->times[1] = ms;
-    if (wanted) { KK(hipEventElapsedTime(&ms, t->ev[2], t->ev[3])); t->times[2] = ms; }
+    if (wanted || parameters) { KK(hipEventElapsedTime(&ms, t->ev[2], t->ev[3])); t->times[2] = ms; }
     return pass_times(s);
 }
 
@@ -461,6 +565,7 @@ void diff_state_release(KH* s) {
     if (t->ws) (void)hipFree(t->ws);
     if (t->masks) (void)hipFree(t->masks);
     if (t->gbuf) (void)hipFree(t->gbuf);
+    if (t->sel) (void)hipFree(t->sel);
     for (hipEvent_t e : t->ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : t->ev_pass) if (e) (void)hipEventDestroy(e);
     delete t;
@@ -497,6 +602,18 @@ int32_t calipso_hip_sparse_kkt_differentiate_adjoint(calipso_hip_sparse_kkt* s, 
 int32_t calipso_hip_sparse_kkt_differentiate_adjoint_device(calipso_hip_sparse_kkt* s, int64_t k, const double* cotangent, double* adjoint, double* const* grad) {
     return differentiate_adjoint(s, "calipso_hip_sparse_kkt_differentiate_adjoint_device", k, cotangent, adjoint, grad, true);
 }
+int32_t calipso_hip_sparse_kkt_differentiate_parameters(calipso_hip_sparse_kkt* s, int64_t k, const int64_t* columns, double* sensitivity) {
+    return differentiate(s, "calipso_hip_sparse_kkt_differentiate_parameters", k, nullptr, sensitivity, false, true, columns);
+}
+int32_t calipso_hip_sparse_kkt_differentiate_parameters_device(calipso_hip_sparse_kkt* s, int64_t k, const int64_t* columns, double* sensitivity) {
+    return differentiate(s, "calipso_hip_sparse_kkt_differentiate_parameters_device", k, nullptr, sensitivity, true, true, columns);
+}
+int32_t calipso_hip_sparse_kkt_differentiate_adjoint_parameters(calipso_hip_sparse_kkt* s, int64_t k, const double* cotangent, double* adjoint, double* grad_theta) {
+    return differentiate_adjoint(s, "calipso_hip_sparse_kkt_differentiate_adjoint_parameters", k, cotangent, adjoint, nullptr, false, true, grad_theta);
+}
+int32_t calipso_hip_sparse_kkt_differentiate_adjoint_parameters_device(calipso_hip_sparse_kkt* s, int64_t k, const double* cotangent, double* adjoint, double* grad_theta) {
+    return differentiate_adjoint(s, "calipso_hip_sparse_kkt_differentiate_adjoint_parameters_device", k, cotangent, adjoint, nullptr, true, true, grad_theta);
+}
 int32_t calipso_hip_sparse_kkt_differentiate_info(calipso_hip_sparse_kkt* s, double out[4]) {
     if (!s || !out) return CALIPSO_ERR_ARGUMENT;
     const double zero[4] = {0, 0, 0, 0};
@@ -514,7 +631,7 @@ int32_t calipso_hip_sparse_kkt_differentiate_adjoint_info(calipso_hip_sparse_kkt
 int32_t calipso_hip_sparse_kkt_differentiate_bytes(calipso_hip_sparse_kkt* s, int64_t* out) {
     if (!s || !out) return CALIPSO_ERR_ARGUMENT;
     const DS* t = s->diff;
-    *out = t ? (int64_t)(sizeof(double) * (t->doubles + t->gdoubles + (size_t)s->d.N) + sizeof(int) * t->ints) : 0;
+    *out = t ? (int64_t)(sizeof(double) * (t->doubles + t->gdoubles + (size_t)s->d.N) + sizeof(int) * (t->ints + t->sel_ints)) : 0;
     return CALIPSO_OK;
 }
 int32_t calipso_hip_sparse_kkt_differentiate_adjoint_times(calipso_hip_sparse_kkt* s, double out[3]) {

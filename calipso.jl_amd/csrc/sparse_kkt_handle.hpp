@@ -30,6 +30,26 @@ struct KktDev {
     View Lc;                                      // the column view of Lxx: Lxx' v, and the (row, column) of a stored non-zero (sparse_differentiate.hip)
 };
 
+// the parameter Jacobians on their stored patterns (sparse_parameters.hpp) as the kernels of sparse_differentiate.hip read them: 0-based device copies of the three
+// CSC patterns (Lx,theta: nx rows; g,theta: ne rows; h,theta: nc rows; np columns each), the resident values, the parameters a wavefront sums
+struct ParamDev {
+    int np, n_long;
+    long long long0;                              // first item of the wavefront section of the gradient kernel (sparse_parameters.hpp: Geometry)
+    const int *ptr[3], *idx[3];
+    const double* val[3];
+    const int* long_columns;
+};
+// set_parameter_patterns (sparse_solve.hip) fills it; set_evaluator and qp_attach drop it
+struct ParameterPatterns {
+    bool set = false;
+    ParamDev d{};
+    double* val[3] = {nullptr, nullptr, nullptr};
+    long long nnz[3] = {0, 0, 0}, longest = 0;
+    int* ints[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // (ptr, idx) x 3 and the long columns on the device, with their capacities:
+    size_t int_cap[7] = {0, 0, 0, 0, 0, 0, 0}, val_cap[3] = {0, 0, 0};                   // kept when the patterns are dropped and taken again by the next call
+    std::vector<int64_t> host[6];                 // the HOST copies the evaluator is given: 1-based, (colptr, rowval) of Lp, gp, hp
+};
+
 struct SolveState;                                // sparse_solve.hip: the resident vectors, workspace and counters of solve!
 struct DiffState;                                 // sparse_differentiate.hip: the column workspace and reports of differentiate!
 
@@ -65,6 +85,7 @@ struct calipso_hip_sparse_kkt {
     double* kry_ws = nullptr;                                // the fallback's workspace (sparse_krylov.hpp: Layout), reserved on the first fallback and kept
     size_t kry_cap = 0;                                      // ... its doubles
     hipEvent_t kry_ev[2] = {nullptr, nullptr};
+    calipso::sparse_kkt::ParameterPatterns par;              // the stored patterns and resident values of dR/dtheta (set_parameter_patterns)
 };
 
 namespace calipso {
@@ -82,6 +103,7 @@ int kkt_sparse_failed(calipso_hip_sparse_kkt* s, int rc, const char* what);
 // sparse_solve.hip, for sparse_kkt.hip
 void solve_state_release(calipso_hip_sparse_kkt* s);                                                        // (before the handle's device memory is freed)
 int solve_set_option(calipso_hip_sparse_kkt* s, const char* name, double value);                            // 1 taken, 0 unknown, < 0 refused
+int parameters_enqueue(calipso_hip_sparse_kkt* s, const char* entry);                                       // enqueue: the evaluator's five parameter bits at the resident point into s->par (no host wait), or the refusal
 void diff_keep_slacks(calipso_hip_sparse_kkt* s);                                                           // enqueue: dslack <- the resident s, t (no host wait)
 // sparse_krylov.hip, for sparse_kkt.hip: the fallback's vector kernels on the workspace `ws` laid out by `l` (enqueues, no host wait)
 void krylov_enqueue_dots(hipStream_t st, const sparse_krylov::Layout& l, double* ws, int nv, const double* w);                  // partials of V[:, 0..nv)' w

@@ -30,6 +30,7 @@
 
 #include "sparse_kkt_handle.hpp"
 #include "sparse_solve.hpp"                // filter, published block, item space, workspace layout, argument checks: plain host C++
+#include "sparse_parameters.hpp"           // the stored patterns of dR/dtheta: their checks and the split into short and long columns: plain host C++
 
 using calipso::i64;
 using calipso::Options;
@@ -563,6 +564,13 @@ int enqueue_evaluator(KH* s, int which, uint32_t flags) {
     out.Lxx_colptr = t->pattern[0].data(); out.Lxx_rowval = t->pattern[1].data(); out.gx_colptr = t->pattern[2].data(); out.gx_rowval = t->pattern[3].data();
     out.hx_colptr = t->pattern[4].data(); out.hx_rowval = t->pattern[5].data();
     out.nx = d.nx; out.np = t->eval_np; out.ne = d.ne; out.nc = d.nc; out.nnz_Lxx = d.nnzL; out.nnz_gx = d.nnzg; out.nnz_hx = d.nnzh;
+    const ParameterPatterns& pp = s->par;                    // NULL / 0 without set_parameter_patterns
+    out.lagrangian_gradient_parameters = pp.set ? pp.val[0] : nullptr; out.equality_jacobian_parameters = pp.set ? pp.val[1] : nullptr;
+    out.cone_jacobian_parameters = pp.set ? pp.val[2] : nullptr;
+    out.Lp_colptr = pp.set ? pp.host[0].data() : nullptr; out.Lp_rowval = pp.set ? pp.host[1].data() : nullptr;
+    out.gp_colptr = pp.set ? pp.host[2].data() : nullptr; out.gp_rowval = pp.set ? pp.host[3].data() : nullptr;
+    out.hp_colptr = pp.set ? pp.host[4].data() : nullptr; out.hp_rowval = pp.set ? pp.host[5].data() : nullptr;
+    out.nnz_Lp = pp.set ? pp.nnz[0] : 0; out.nnz_gp = pp.set ? pp.nnz[1] : 0; out.nnz_hp = pp.set ? pp.nnz[2] : 0;
     const int32_t r = t->eval_fn(t->eval_user, flags, which ? v.cand : s->w, s->w + d.o_y, s->w + d.o_z, t->theta, &out, (void*)s->st);
     for (int i = 0; i < 3; ++i) if (flags & EVAL_MATRIX_BITS[i]) { s->have[i] = r == 0; s->assembled = false; s->factored = false; }
     if (r != 0) {
@@ -672,6 +680,7 @@ int qp_attach(KH* s, const double* q, const double* b, const double* hvec, doubl
     KK(hipStreamSynchronize(s->st));
     t->v.objective_constant = objective_constant;
     t->eval_fn = nullptr; t->eval_user = nullptr;           // a handle holds one problem class: the QP replaces an evaluator
+    s->par.set = false;                                      // ... and its parameter patterns go with it
     s->qp_attached = true;
     for (int i = 0; i < 3; ++i) if (count[i] && !t->have_qp[i]) s->qp_attached = false;
     return CALIPSO_OK;
@@ -815,6 +824,17 @@ void diff_keep_slacks(KH* s) {
     s->slacks_kept = true;
 }
 
+int parameters_enqueue(KH* s, const char* entry) {
+    if (!s->par.set || !s->solve || !s->solve->eval_fn)
+        return kkt_fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": no parameter patterns set (calipso_hip_sparse_kkt_set_parameter_patterns first)");
+    if (!s->have[3]) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": no point resident (calipso_hip_sparse_kkt_initialize, or set_values with w, first)");
+    SS* t = s->solve;
+    const bool open = t->group_open;                         // (the call belongs to no timed group of solve!)
+    const int rc = enqueue_evaluator(s, 0, EVAL_PARAMETER_BITS);
+    if (rc >= 0) t->group_open = open;
+    return rc;
+}
+
 void solve_state_release(KH* s) {
     SS* t = s->solve;
     if (!t) return;
@@ -947,6 +967,15 @@ int32_t calipso_hip_sparse_kkt_get(calipso_hip_sparse_kkt* s, const char* name, 
     KK(hipSetDevice(s->device));
     { const int rc = ensure_state(s); if (rc < 0) return rc; }
     const i64 nnz[3] = {s->d.nnzL, s->d.nnzg, s->d.nnzh};
+    if (const int m = calipso::sparse_parameters::array_by_name(name); m >= 0) {      // the three resident arrays of dR/dtheta on their stored patterns
+        const std::string what = std::string("calipso_hip_sparse_kkt_get: ") + name;
+        if (!s->par.set) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, what + ": no parameter patterns set (calipso_hip_sparse_kkt_set_parameter_patterns first)");
+        if (len != s->par.nnz[m]) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, what + ": len: the stored pattern has " + std::to_string(s->par.nnz[m]) + " non-zeros, not " + std::to_string(len));
+        if (!out && len > 0) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, what + ": the array is NULL");
+        if (len) KK(hipMemcpyAsync(out, s->par.val[m], sizeof(double) * (size_t)len, hipMemcpyDeviceToHost, s->st));
+        KK(hipStreamSynchronize(s->st));
+        return CALIPSO_OK;
+    }
     REFUSE(check_named_vector("calipso_hip_sparse_kkt_get", name, out, len, s->d.nx, s->d.ne, s->d.nc, false, nnz));
     if (vector_by_name(name) == V_DIFFERENTIATE_SLACKS) {
         const size_t nc = (size_t)s->d.nc;
@@ -983,6 +1012,7 @@ int32_t calipso_hip_sparse_kkt_set_evaluator(calipso_hip_sparse_kkt* s, calipso_
     REFUSE(check_set_evaluator(np));
     SS* t = s->solve;
     KK(hipStreamSynchronize(s->st));                         // (nothing of the evaluator before is in flight when its user object changes hands)
+    s->par.set = false;                                      // the parameter patterns belong to the evaluator they were set for
     if (!fn) { t->eval_fn = nullptr; t->eval_user = nullptr; return CALIPSO_OK; }
     if (np != t->eval_np || !t->theta) {
         double* theta = nullptr;
@@ -1037,6 +1067,73 @@ int32_t calipso_hip_sparse_kkt_evaluate(calipso_hip_sparse_kkt* s, int32_t which
     KK(hipStreamSynchronize(s->st));
     KK(hipGetLastError());
     t->group_open = false;
+    return CALIPSO_OK;
+}
+
+// ---- the parameter Jacobians on their stored patterns (sparse_parameters.hpp) ----------------------------------------------------------------------------------------
+int32_t calipso_hip_sparse_kkt_set_parameter_patterns(calipso_hip_sparse_kkt* s, const int64_t* Lp_colptr, const int64_t* Lp_rowval, const int64_t* gp_colptr,
+                                                      const int64_t* gp_rowval, const int64_t* hp_colptr, const int64_t* hp_rowval) {
+    if (!s) return CALIPSO_ERR_ARGUMENT;
+    KK(hipSetDevice(s->device));
+    { const int rc = ensure_state(s); if (rc < 0) return rc; }
+    static const char* const entry = "calipso_hip_sparse_kkt_set_parameter_patterns";
+    SS* t = s->solve;
+    if (!t->eval_fn) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": no evaluator attached (calipso_hip_sparse_kkt_set_evaluator first)");
+    namespace sp = calipso::sparse_parameters;
+    const sp::Patterns in{{Lp_colptr, gp_colptr, hp_colptr}, {Lp_rowval, gp_rowval, hp_rowval}};
+    const int64_t rows[3] = {s->d.nx, s->d.ne, s->d.nc};
+    const i64 np = t->eval_np;
+    REFUSE(sp::check_patterns(entry, np, rows, in));
+    KK(hipStreamSynchronize(s->st));                         // (no evaluation that reads the patterns before is in flight)
+    ParameterPatterns& pp = s->par;
+    pp.set = false;
+    const sp::Split split = sp::split_columns(np, in);
+    const sp::Geometry geo = sp::geometry(np, (int64_t)split.long_columns.size());
+    std::vector<int> host[7];                                // 0-based device copies: (ptr, idx) x 3, the long columns
+    ParamDev d{};
+    d.np = (int)np; d.n_long = (int)split.long_columns.size(); d.long0 = geo.long0;
+    for (int m = 0; m < 3; ++m) {
+        const i64 nnz = in.colptr[m][np] - 1;
+        pp.nnz[m] = nnz;
+        pp.host[2 * m].assign(in.colptr[m], in.colptr[m] + np + 1);
+        pp.host[2 * m + 1].assign(in.rowval[m], in.rowval[m] + nnz);
+        for (i64 j = 0; j <= np; ++j) host[2 * m].push_back((int)(in.colptr[m][j] - 1));
+        for (i64 p = 0; p < nnz; ++p) host[2 * m + 1].push_back((int)(in.rowval[m][p] - 1));
+    }
+    host[6].assign(split.long_columns.begin(), split.long_columns.end());
+    // the arrays of an earlier call are taken again where they are large enough: setting patterns repeatedly does not grow the handle
+    for (int i = 0; i < 7; ++i) {
+        const size_t want = std::max<size_t>(host[i].size(), 1);
+        if (want <= pp.int_cap[i]) continue;
+        double* p = nullptr;
+        { const int rc = kkt_reserve(s, &p, (want + 1) / 2); if (rc < 0) return rc; }
+        pp.ints[i] = reinterpret_cast<int*>(p); pp.int_cap[i] = want;
+    }
+    for (int m = 0; m < 3; ++m) {
+        const size_t want = (size_t)std::max<i64>(pp.nnz[m], 1);
+        if (want <= pp.val_cap[m]) continue;
+        { const int rc = kkt_reserve(s, &pp.val[m], want); if (rc < 0) return rc; }
+        pp.val_cap[m] = want;
+    }
+    KK(hipDeviceSynchronize());                              // kkt_reserve zeroes on the null stream, which the handle's non-blocking stream does not wait for
+    for (int i = 0; i < 7; ++i) if (!host[i].empty()) KK(hipMemcpyAsync(pp.ints[i], host[i].data(), sizeof(int) * host[i].size(), hipMemcpyHostToDevice, s->st));
+    for (int m = 0; m < 3; ++m) {
+        KK(hipMemsetAsync(pp.val[m], 0, sizeof(double) * (size_t)std::max<i64>(pp.nnz[m], 1), s->st));      // the values start as zeros
+        d.ptr[m] = pp.ints[2 * m]; d.idx[m] = pp.ints[2 * m + 1]; d.val[m] = pp.val[m];
+    }
+    d.long_columns = pp.ints[6];
+    KK(hipStreamSynchronize(s->st));                         // (the host copies above leave scope)
+    pp.d = d; pp.longest = split.longest;
+    pp.set = true;
+    return CALIPSO_OK;
+}
+int32_t calipso_hip_sparse_kkt_evaluate_parameters(calipso_hip_sparse_kkt* s) {
+    if (!s) return CALIPSO_ERR_ARGUMENT;
+    KK(hipSetDevice(s->device));
+    (void)hipGetLastError();
+    { const int rc = parameters_enqueue(s, "calipso_hip_sparse_kkt_evaluate_parameters"); if (rc < 0) return rc; }
+    KK(hipStreamSynchronize(s->st));
+    KK(hipGetLastError());
     return CALIPSO_OK;
 }
 

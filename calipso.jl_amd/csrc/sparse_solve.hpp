@@ -149,7 +149,8 @@ inline std::string check_trace(const void* out, i64 cap_rows) {
     return "";
 }
 // ---- the evaluator's entries ------------------------------------------------------------------------------------------------------------------------------------
-// the bits an evaluation on the sparse handle may carry: no dual gradient (the handle gathers them), no parameter Jacobian (differentiate takes the caller's)
+// the bits calipso_hip_sparse_kkt_evaluate may carry: no dual gradient (the handle gathers them), no parameter Jacobian (those are evaluate_parameters' and the
+// _parameters entries' of differentiate!, on the stored patterns of sparse_parameters.hpp)
 constexpr uint32_t EVAL_DUAL_GRADIENTS = (1u << 5) | (1u << 9);
 constexpr uint32_t EVAL_PARAMETER_BITS = 0x1fu << 11;
 constexpr uint32_t EVAL_MATRIX_BITS[3] = {(1u << 2) | (1u << 6) | (1u << 10), 1u << 4, 1u << 8};      // what writes Lxx, gx, hx

@@ -536,6 +536,12 @@ sparse_set_parameters_device!(k::SparseKKT, theta::Ptr{Cvoid}) =
 # the evaluator at the solution (which = 0) or at the candidate (1); flags: CALIPSO_EVAL_* without dual gradients and parameter Jacobians
 sparse_evaluate!(k::SparseKKT, flags::Integer; which::Integer=0) =
     kkt_check(ccall((:calipso_hip_sparse_kkt_evaluate, lib), Int32, (Ptr{Cvoid}, Int32, UInt32), k.handle, which, flags), k, "evaluate!")
+# the stored patterns of dR/dtheta's three blocks (1-based CSC, num_parameters columns): the Lagrangian's theta-gradient (nx rows), g,theta (ne rows), h,theta (nc rows)
+sparse_set_parameter_patterns!(k::SparseKKT, Lp_colptr::Vector{Int64}, Lp_rowval::Vector{Int64}, gp_colptr::Vector{Int64}, gp_rowval::Vector{Int64}, hp_colptr::Vector{Int64}, hp_rowval::Vector{Int64}) =
+    kkt_check(ccall((:calipso_hip_sparse_kkt_set_parameter_patterns, lib), Int32, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}), k.handle,
+                    Lp_colptr, Lp_rowval, gp_colptr, gp_rowval, hp_colptr, hp_rowval), k, "set_parameter_patterns!")
+# the evaluator's five parameter bits at the resident point and theta into the three resident arrays (sparse_get: lagrangian_gradient_parameters, ...)
+sparse_evaluate_parameters!(k::SparseKKT) = kkt_check(ccall((:calipso_hip_sparse_kkt_evaluate_parameters, lib), Int32, (Ptr{Cvoid},), k.handle), k, "evaluate_parameters!")
 
 # ---- differentiate! on the same handle (csrc/sparse_differentiate.hip): ccall wrappers, no logic; not executed here either (see the note at the top) -----------
 # X = M B (transposed: M' B) through the current factorisation; B, X: N x k
@@ -551,6 +557,20 @@ function sparse_differentiate_adjoint!(k::SparseKKT, cotangent::Matrix{Float64};
         ccall((:calipso_hip_sparse_kkt_differentiate_adjoint, lib), Int32, (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Ptr{Float64}}), k.handle, size(cotangent, 2), cotangent,
               kkt_ptr(adjoint), ptrs), k, "differentiate_adjoint!")
 end
+# the same two with the EVALUATOR's dR/dtheta on its stored patterns (sparse_set_parameter_patterns!): columns = 1-based parameter indices, nothing = all of them;
+# grad_theta: num_parameters x k
+sparse_differentiate_parameters!(k::SparseKKT, sensitivity::Matrix{Float64}; columns::Union{Nothing,Vector{Int64}}=nothing) = GC.@preserve columns kkt_check(
+    ccall((:calipso_hip_sparse_kkt_differentiate_parameters, lib), Int32, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Float64}), k.handle, size(sensitivity, 2),
+          columns === nothing ? C_NULL : pointer(columns), sensitivity), k, "differentiate_parameters!")
+sparse_differentiate_adjoint_parameters!(k::SparseKKT, grad_theta::Matrix{Float64}, cotangent::Matrix{Float64}; adjoint=nothing) = GC.@preserve adjoint kkt_check(
+    ccall((:calipso_hip_sparse_kkt_differentiate_adjoint_parameters, lib), Int32, (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), k.handle, size(cotangent, 2), cotangent,
+          kkt_ptr(adjoint), grad_theta), k, "differentiate_adjoint_parameters!")
+sparse_differentiate_parameters_device!(k::SparseKKT, sensitivity::Ptr{Cvoid}, ncols::Integer; columns::Union{Nothing,Vector{Int64}}=nothing) = GC.@preserve columns kkt_check(
+    ccall((:calipso_hip_sparse_kkt_differentiate_parameters_device, lib), Int32, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Cvoid}), k.handle, ncols,
+          columns === nothing ? C_NULL : pointer(columns), sensitivity), k, "differentiate_parameters_device!")
+sparse_differentiate_adjoint_parameters_device!(k::SparseKKT, grad_theta::Ptr{Cvoid}, cotangent::Ptr{Cvoid}, ncols::Integer; adjoint::Ptr{Cvoid}=C_NULL) = kkt_check(
+    ccall((:calipso_hip_sparse_kkt_differentiate_adjoint_parameters_device, lib), Int32, (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), k.handle, ncols, cotangent, adjoint,
+          grad_theta), k, "differentiate_adjoint_parameters_device!")
 sparse_differentiate_info(k::SparseKKT) = (out = zeros(4); kkt_check(ccall((:calipso_hip_sparse_kkt_differentiate_info, lib), Int32, (Ptr{Cvoid}, Ptr{Float64}), k.handle, out), k, "differentiate_info"); out)
 sparse_differentiate_adjoint_info(k::SparseKKT) = (out = zeros(4); kkt_check(ccall((:calipso_hip_sparse_kkt_differentiate_adjoint_info, lib), Int32, (Ptr{Cvoid}, Ptr{Float64}), k.handle, out), k, "differentiate_adjoint_info"); out)
 sparse_differentiate_adjoint_times(k::SparseKKT) = (out = zeros(3); kkt_check(ccall((:calipso_hip_sparse_kkt_differentiate_adjoint_times, lib), Int32, (Ptr{Cvoid}, Ptr{Float64}), k.handle, out), k, "differentiate_adjoint_times"); out)

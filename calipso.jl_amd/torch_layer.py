@@ -40,14 +40,21 @@ member order.  Host tensors only: the handles take host arrays.  Members that di
 SparseQPLayer is the layer over the sparse route: the matrices are given as the VALUES on the stored patterns of the P, A, G the handle was made from (CSC order,
 row indices ascending), and their gradients come back on those patterns — no nx x nx array exists in forward or backward.  forward = set_values + attach_qp +
 initialize with zeros + solve, backward = ONE SparseKKT.vjp for the cotangent.  Host tensors, or CUDA tensors on the handle's device: then the data, the solution and
-the gradients stay on the device and nothing but the solve's own read-backs crosses to the host.  A solve that does not end with status 1 warns and gives NaN gradients."""
+the gradients stay on the device and nothing but the solve's own read-backs crosses to the host.  A solve that does not end with status 1 warns and gives NaN gradients.
+
+    w = SparseTrajectoryLayer.apply(handle, theta, x0)   # the point (N,) of a nonlinear problem on a sparse handle whose evaluator provides dR/dtheta
+
+SparseTrajectoryLayer is the auto-tuning loop on the sparse route (TrajectoryProblem.sparse_solver(), or any SparseKKT with set_evaluator + set_parameter_patterns):
+forward = set_parameters + initialize + solve, backward = ONE SparseKKT.vjp(theta=True) — dLoss/dtheta from the evaluator's parameter Jacobians on their stored
+patterns, with no host evaluation and no dense array of any x num_parameters size.  theta and x0: float64 host tensors, or CUDA tensors on the handle's device (then
+theta, the point and the gradient stay on the device).  x0 gets no gradient."""
 import warnings
 
 import numpy as np
 
 from ._marshal import QP_NAMES, cotangent_from_parts, dual_rows, qp_shapes
 
-__all__ = ["QPLayer", "ParametricLayer", "SolverQPLayer", "GroupQPLayer", "SparseQPLayer"]
+__all__ = ["QPLayer", "ParametricLayer", "SolverQPLayer", "GroupQPLayer", "SparseQPLayer", "SparseTrajectoryLayer"]
 
 _cls = {}
 
@@ -295,7 +302,46 @@ def _build():
                 out = {name: torch.full_like(g, float("nan")) for name, g in out.items()}
             return (None, *[out[name].contiguous() if name in out else None for name in QP_NAMES], None)
 
-    return {"QPLayer": QPLayer, "ParametricLayer": ParametricLayer, "SolverQPLayer": SolverQPLayer, "GroupQPLayer": GroupQPLayer, "SparseQPLayer": SparseQPLayer}
+    class SparseTrajectoryLayer(torch.autograd.Function):
+        """apply(handle, theta, x0): the point w (N,) solve! returns for the parameters theta (num_parameters,) from the initial variables x0 (nx,), on a SparseKKT whose
+        evaluator provides dR/dtheta (set_parameter_patterns; TrajectoryProblem.sparse_solver() sets them)"""
+
+        @staticmethod
+        def forward(ctx, handle, theta, x0):
+            if not handle._has_parameter_patterns():
+                raise ValueError("SparseTrajectoryLayer: the handle needs an evaluator with parameters and set_parameter_patterns (TrajectoryProblem.sparse_solver() sets them)")
+            for name, t, n in (("theta", theta, handle.num_parameters), ("x0", x0, handle.nx)):
+                if t.dtype != torch.float64:
+                    raise TypeError("SparseTrajectoryLayer: %s must be float64" % name)
+                if tuple(t.shape) != (n,):
+                    raise ValueError("SparseTrajectoryLayer: %s must be (%d,)" % (name, n))
+            on_device = all(t.is_cuda and t.device.index == handle.device for t in (theta, x0))
+            if not on_device and (theta.is_cuda or x0.is_cuda):
+                raise ValueError("SparseTrajectoryLayer: theta and x0 are both host tensors or both CUDA tensors on the handle's device")
+            tensors = [t.detach().contiguous() if on_device else _np(t).copy() for t in (theta, x0)]
+            key = object()
+            _solve_sparse_parameters(handle, tensors, key)
+            ctx.handle, ctx.key, ctx.tensors, ctx.on_device, ctx.converged, ctx.device = handle, key, tensors, on_device, handle._qp_layer_converged, theta.device
+            ctx.inputs, ctx.versions = (theta, x0), [t._version for t in (theta, x0)]
+            return handle.solution_device() if on_device else torch.from_numpy(handle.get("solution").copy()).to(theta.device)
+
+        @staticmethod
+        def backward(ctx, gw):
+            handle = ctx.handle
+            _solved_again(handle, ctx, lambda: _solve_sparse_parameters(handle, ctx.tensors, ctx.key), "SparseTrajectoryLayer: an input was modified in place after forward "
+                          "and the handle has solved other data since: backward cannot solve the same data again" if ctx.on_device else None)
+            if not ctx.needs_input_grad[1]:
+                return None, None, None
+            g = handle.vjp(gw.detach().contiguous() if ctx.on_device else _np(gw), adjoint=False, theta=True)["theta"]
+            if not ctx.on_device:
+                g = torch.from_numpy(np.ascontiguousarray(g)).to(ctx.device)
+            if not ctx.converged:
+                warnings.warn("SparseTrajectoryLayer: the solve did not converge (status != 1): the gradient is NaN")
+                g = torch.full_like(g, float("nan"))
+            return None, g.contiguous(), None
+
+    return {"QPLayer": QPLayer, "ParametricLayer": ParametricLayer, "SolverQPLayer": SolverQPLayer, "GroupQPLayer": GroupQPLayer, "SparseQPLayer": SparseQPLayer,
+            "SparseTrajectoryLayer": SparseTrajectoryLayer}
 
 
 def _solve_device(torch, sn, tensors, objective_scale, key):
@@ -350,6 +396,15 @@ def _solve_sparse(torch, kkt, data, on_device, key):
         x0 = np.zeros(kkt.nx)
         kkt.set_values(Lxx, Av, -Gv)
         kkt.attach_qp(q, b, h)
+    kkt.initialize(x0)
+    status, _ = kkt.solve()
+    kkt._qp_layer_key, kkt._qp_layer_converged = key, status == 1
+
+
+def _solve_sparse_parameters(kkt, data, key):
+    """data: theta and x0 as numpy arrays, or as CUDA tensors on the handle's device"""
+    theta, x0 = data
+    kkt.set_parameters(theta)
     kkt.initialize(x0)
     status, _ = kkt.solve()
     kkt._qp_layer_key, kkt._qp_layer_converged = key, status == 1

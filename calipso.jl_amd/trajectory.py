@@ -365,6 +365,29 @@ class TrajectoryProblem:
             out.append((colptr, np.ascontiguousarray(row, dtype=np.int64)))
         return tuple(out)
 
+    def sparse_parameter_patterns(self):
+        """the stored patterns of dR/dtheta's three blocks a sparse handle takes (SparseKKT.set_parameter_patterns), CSC as (colptr, rowval) pairs with np columns, 0-based,
+        rows ascending: lagrangian_gradient_parameters (nx rows: the D_LGP partials of every template), equality_jacobian_parameters (ne rows), cone_jacobian_parameters
+        (nc rows) — from the index tables by np.unique on (column, row) keys, like sparse_patterns(): nothing of size nx x np, ne x np or nc x np is allocated"""
+        rows = {D_LGP: self.nx, D_GP: self.ne, D_HP: self.nc}
+        keys = {D_LGP: [], D_GP: [], D_HP: []}
+        for tp in self.templates:
+            nj = len(tp.jac)
+            if len(tp.cth):
+                f = D_GP if tp.cls == 1 else D_HP
+                keys[f].append((tp.d_j[nj:nj + len(tp.cth)] * rows[f] + tp.d_i[nj:nj + len(tp.cth)]).reshape(-1))
+            q0 = tp.nq - len(tp.gth)
+            if len(tp.gth):
+                keys[D_LGP].append((tp.p_j[q0:] * self.nx + tp.p_i[q0:]).reshape(-1))
+        out = []
+        for f in (D_LGP, D_GP, D_HP):
+            key = np.unique(np.concatenate(keys[f])) if keys[f] else np.zeros(0, dtype=np.int64)
+            col, row = (key // rows[f], key % rows[f]) if rows[f] else (key, key)
+            colptr = np.zeros(self.np + 1, dtype=np.int64)
+            np.cumsum(np.bincount(col, minlength=self.np), out=colptr[1:])
+            out.append((colptr, np.ascontiguousarray(row, dtype=np.int64)))
+        return tuple(out)
+
     def structure(self):
         """dict(row_first, row_last, hessian_block_start) (1-based) for Solver(structure=...) when the Lagrangian Hessian falls into at least two diagonal blocks (it does
         when no stage function couples x_t with x_t+1 in its second derivatives: explicit dynamics), else None (implicit dynamics, the pendulum: a dense handle).
@@ -665,7 +688,8 @@ class TrajectoryProblem:
     def sparse_solver(self, parameters=None, options=None, device=0, method="nested_dissection", perm=None, **compile_args):
         """a SparseKKT on sparse_patterns() whose evaluations run in the generated library's <name>_sparse_eval: the route for problems whose Hessian couples
         consecutive stages (implicit dynamics: structure() is None) and for horizons a dense handle cannot hold.  The cone layout and theta (default: zeros) are set;
-        every SparseKKT method works on it — initialize(x0), solve(), get("solution"), and get_trajectory(handle) here.  The handle keeps the library and the
+        every SparseKKT method works on it — initialize(x0), solve(), get("solution"), and get_trajectory(handle) here.  With parameters the patterns of
+        sparse_parameter_patterns() are set too, so differentiate() and vjp(v, theta=True) take dR/dtheta from the evaluator.  The handle keeps the library and the
         evaluator's user object alive; close() frees them."""
         import scipy.sparse as sp
         built = self.compile(**compile_args)
@@ -686,6 +710,8 @@ class TrajectoryProblem:
             raise
         s._trajectory, s._library, s._user, s._user_destroy = self, L, user, destroy
         s.set_evaluator(ctypes.cast(getattr(L, self.name + "_sparse_eval"), ctypes.c_void_p), user, self.np)
+        if self.np > 0:                         # differentiate() / vjp(theta=True) take dR/dtheta from the evaluator, on these stored patterns
+            s.set_parameter_patterns(*self.sparse_parameter_patterns())
         if parameters is not None:
             s.set_parameters(parameters)
         return s

@@ -135,8 +135,13 @@ typedef int32_t (*calipso_device_block_eval_fn)(void* user, uint32_t flags, cons
  * calipso_hip_sparse_kkt_create, in the caller's non-zero order — the next assemble reads what the evaluator wrote, nothing is copied.  An evaluator asked for a
  * Jacobian / the Hessian writes EVERY stored non-zero of it (zeros included).  lagrangian_hessian holds both triangles and receives the sum of the terms whose bits are
  * set: fxx (OBJECTIVE_HESSIAN) + (y'g)xx (EQUALITY_DUAL_HESSIAN) + (z'h)xx (CONE_DUAL_HESSIAN).  (g'y)x and (h'z)x are never asked for: the handle forms them from its
- * column views on the fresh Jacobian values; no parameter-Jacobian bit is ever set either.  The six pattern arrays are HOST copies (1-based, as given to create), for an
- * evaluator that builds its own address table on the first call.  The evaluator enqueues on hip_stream and returns without waiting; 0, or a code the handle reports. */
+ * column views on the fresh Jacobian values.  The six pattern arrays are HOST copies (1-based, as given to create), for an evaluator that builds its own address table
+ * on the first call.  The evaluator enqueues on hip_stream and returns without waiting; 0, or a code the handle reports.
+ * The parameter Jacobians: without calipso_hip_sparse_kkt_set_parameter_patterns the last fields are NULL / 0 and no parameter-Jacobian bit is ever set.  With it the
+ * three parameter arrays are the handle's resident values on the three stored CSC patterns with np columns (HOST copies of the patterns, 1-based, as given), and the
+ * evaluator may be called with the five parameter bits: it writes EVERY stored non-zero of an array it is asked for; lagrangian_gradient_parameters receives the sum
+ * of the terms whose bits are set: f_x,theta (OBJECTIVE_JACOBIAN_PARAMETERS) + (y'g)_x,theta (EQUALITY_DUAL_...) + (z'h)_x,theta (CONE_DUAL_...)
+ * (residual_jacobian_parameters.jl:8-14). */
 typedef struct calipso_device_sparse_data {
     double* objective;                       /* [1]  */
     double* objective_gradient_variables;    /* [nx] */
@@ -147,6 +152,11 @@ typedef struct calipso_device_sparse_data {
     double* cone_jacobian_variables;         /* nzval on the hx pattern */
     const int64_t *Lxx_colptr, *Lxx_rowval, *gx_colptr, *gx_rowval, *hx_colptr, *hx_rowval;   /* HOST copies, 1-based, as given to create */
     int64_t nx, np, ne, nc, nnz_Lxx, nnz_gx, nnz_hx;
+    double* lagrangian_gradient_parameters;  /* nzval on the Lp pattern (nx rows, np columns); NULL without parameter patterns, as everything below */
+    double* equality_jacobian_parameters;    /* nzval on the gp pattern (ne rows) */
+    double* cone_jacobian_parameters;        /* nzval on the hp pattern (nc rows) */
+    const int64_t *Lp_colptr, *Lp_rowval, *gp_colptr, *gp_rowval, *hp_colptr, *hp_rowval;     /* HOST copies, 1-based, as given to set_parameter_patterns */
+    int64_t nnz_Lp, nnz_gp, nnz_hp;
 } calipso_device_sparse_data;
 typedef int32_t (*calipso_device_sparse_eval_fn)(void* user, uint32_t flags, const double* x, const double* y, const double* z, const double* theta,
                                                  const calipso_device_sparse_data* out, void* hip_stream);
@@ -682,11 +692,22 @@ int32_t calipso_hip_sparse_kkt_trace(calipso_hip_sparse_kkt*, double* out, int64
  *   Which point the matrices belong to: after solve returns, the resident Hessian and Jacobians are those of the RETURNED point (the last prologue's evaluation), with
  *                   its y, z — not, as in the reference, those of the last search direction one iterate earlier.  differentiate / differentiate_adjoint therefore
  *                   assemble with the matrices of the returned point and the slacks of quirk B-12 (above); on a QP the matrices are constant and nothing differs.
- *                   They keep taking the caller's dR/dtheta: the handle does not ask the evaluator for parameter Jacobians. */
+ *                   The parameter Jacobians of differentiate_parameters / differentiate_adjoint_parameters are evaluated at the same resident point and theta.
+ *   set_parameter_patterns  the stored patterns of dR/dtheta's three non-zero blocks (residual_jacobian_parameters.jl:1-40), CSC with np columns, 1-based, rows ascending
+ *                   and duplicate-free within a column: Lp = lagrangian_gradient_parameters (nx rows), gp = equality_jacobian_parameters (ne rows), hp =
+ *                   cone_jacobian_parameters (nc rows).  Needs an evaluator with np > 0; a pattern that breaks the rule is CALIPSO_ERR_ARGUMENT naming the array.  The
+ *                   handle keeps three resident value arrays and device copies of the patterns — no array of size N x np, nx x np, ne x np or nc x np is ever
+ *                   allocated.  set_evaluator and qp_attach drop the patterns; a handle without them behaves as it did before they existed.  A later call takes the
+ *                   device arrays of an earlier one again where they are large enough; a refused call leaves the patterns there were.
+ *   evaluate_parameters  the evaluator with the five parameter bits at the resident x, y, z, theta into the three arrays.  Synchronised.  (evaluate keeps refusing those bits.)
+ *   get             additionally lagrangian_gradient_parameters, equality_jacobian_parameters, cone_jacobian_parameters (the resident values on their patterns) */
 int32_t calipso_hip_sparse_kkt_set_evaluator(calipso_hip_sparse_kkt*, calipso_device_sparse_eval_fn fn, void* user, int64_t np);
 int32_t calipso_hip_sparse_kkt_set_parameters(calipso_hip_sparse_kkt*, const double* theta);
 int32_t calipso_hip_sparse_kkt_set_parameters_device(calipso_hip_sparse_kkt*, const double* theta);
 int32_t calipso_hip_sparse_kkt_evaluate(calipso_hip_sparse_kkt*, int32_t which, uint32_t flags);
+int32_t calipso_hip_sparse_kkt_set_parameter_patterns(calipso_hip_sparse_kkt*, const int64_t* Lp_colptr, const int64_t* Lp_rowval, const int64_t* gp_colptr,
+                                                      const int64_t* gp_rowval, const int64_t* hp_colptr, const int64_t* hp_rowval);
+int32_t calipso_hip_sparse_kkt_evaluate_parameters(calipso_hip_sparse_kkt*);
 
 /* ---- differentiate! on sparse problem data resident on the device (csrc/sparse_differentiate.hip; host and shared pieces: csrc/sparse_differentiate.hpp) -------
  * differentiate! (src/solver/differentiate.jl:1-61) in both directions on the same handle, for k columns in the launches of one: the condensed solve of
@@ -703,6 +724,18 @@ int32_t calipso_hip_sparse_kkt_evaluate(calipso_hip_sparse_kkt*, int32_t which, 
  *                        resident point and l_x, l_y, l_z the parts of lambda:  Lxx(i, c): -l_x[i] x[c];  q: -l_x;  gx(e, c): -(l_y[e] x[c] + y[e] l_x[c]);  b: +l_y;
  *                        hx(m, c): -(l_z[m] x[c] + z[m] l_x[c]);  hvec: -l_z — one launch, one thread per (stored non-zero, column); no nx x nx array exists anywhere.
  *                        adjoint may be NULL.
+ *   differentiate_parameters  differentiate with the EVALUATOR's dR/dtheta (set_parameter_patterns): columns = k 1-based parameter indices (a HOST array in both forms;
+ *                        repeats allowed), or NULL for all parameters, and then k = np.  The evaluator is asked for the five parameter bits on the handle's stream; a clear
+ *                        and one launch write the N x k block of the selected columns straight into the pass's workspace (x rows from Lx,theta, y rows from g,theta, z rows
+ *                        from h,theta, one writer per address); from there on it IS differentiate, so the result is bit for bit what differentiate returns for the same
+ *                        block handed in by the caller.  No N x np array exists.
+ *   differentiate_adjoint_parameters  differentiate_adjoint with grad = NULL, then grad_theta (np x k, column-major) = -R_theta' lambda:  grad_theta(j, c) =
+ *                        -(sum_i Lx,theta(i, j) l_x[i, c] + sum_e g,theta(e, j) l_y[e, c] + sum_m h,theta(m, j) l_z[m, c]), a gather over the three stored columns in stored
+ *                        order: one thread per (parameter, cotangent column) for a column of fewer than 64 non-zeros, one wavefront with a fixed-order cross-lane sum
+ *                        for a longer one (the split length, csrc/sparse_parameters.hpp: SPLIT_LENGTH, is UNMEASURED).  No floating-point atomics: a call repeats bit for
+ *                        bit.  adjoint may be NULL; differentiate_adjoint_times[2] is this kernel's time.
+ *                        Both evaluate the parameter Jacobians at the resident point and theta — the point of the resident Hessian and Jacobians (the deviation from
+ *                        quirk B-12 described with set_evaluator above); info, times and bytes count these calls as they count the two above.
  *   Option differentiate_refinement = 1 (set_option; default 0, other values CALIPSO_ERR_ARGUMENT): the correction rounds of iterative_refinement.jl:14-44 on all
  *                        columns, forward against H, reverse against H', with the per-column decisions of csrc/sensitivity_columns.hpp; one read-back of k norms per
  *                        round.  On a handle with any second-order cone the option is inert (quirk B-3, as calipso_hip_differentiate): the columns are the unrefined
@@ -716,13 +749,18 @@ int32_t calipso_hip_sparse_kkt_evaluate(calipso_hip_sparse_kkt*, int32_t which, 
  *                        column norm], as calipso_hip_differentiate_info; differentiate_adjoint_times: HIP-event ms of the last reverse call, [0] entry to last kernel,
  *                        [1] the copies of the results, [2] of [0] the gradient kernel alone, as calipso_hip_differentiate_adjoint_times
  * CALIPSO_ERR_ARGUMENT with calipso_hip_sparse_kkt_last_error naming the argument, the handle usable afterwards: a NULL handle, k < 1, k > 65535 (the multi-column
- * solve's grid limit), a missing array, grad without an attached QP or without a resident point, no values resident (solve_columns: no factorisation). */
+ * solve's grid limit), a missing array, grad without an attached QP or without a resident point, no values resident (solve_columns: no factorisation); the _parameters
+ * entries: no parameter patterns set, a column index outside 1 .. np, columns = NULL with k != np, a NULL sensitivity / grad_theta. */
 int32_t calipso_hip_sparse_kkt_solve_columns(calipso_hip_sparse_kkt*, int64_t k, int32_t transposed, const double* B, double* X);
 int32_t calipso_hip_sparse_kkt_solve_columns_device(calipso_hip_sparse_kkt*, int64_t k, int32_t transposed, const double* B, double* X);
 int32_t calipso_hip_sparse_kkt_differentiate(calipso_hip_sparse_kkt*, int64_t k, const double* jacobian_parameters, double* sensitivity);
 int32_t calipso_hip_sparse_kkt_differentiate_device(calipso_hip_sparse_kkt*, int64_t k, const double* jacobian_parameters, double* sensitivity);
 int32_t calipso_hip_sparse_kkt_differentiate_adjoint(calipso_hip_sparse_kkt*, int64_t k, const double* cotangent, double* adjoint, double* const* grad);
 int32_t calipso_hip_sparse_kkt_differentiate_adjoint_device(calipso_hip_sparse_kkt*, int64_t k, const double* cotangent, double* adjoint, double* const* grad);
+int32_t calipso_hip_sparse_kkt_differentiate_parameters(calipso_hip_sparse_kkt*, int64_t k, const int64_t* columns, double* sensitivity);
+int32_t calipso_hip_sparse_kkt_differentiate_parameters_device(calipso_hip_sparse_kkt*, int64_t k, const int64_t* columns, double* sensitivity);
+int32_t calipso_hip_sparse_kkt_differentiate_adjoint_parameters(calipso_hip_sparse_kkt*, int64_t k, const double* cotangent, double* adjoint, double* grad_theta);
+int32_t calipso_hip_sparse_kkt_differentiate_adjoint_parameters_device(calipso_hip_sparse_kkt*, int64_t k, const double* cotangent, double* adjoint, double* grad_theta);
 int32_t calipso_hip_sparse_kkt_differentiate_info(calipso_hip_sparse_kkt*, double out[4]);
 int32_t calipso_hip_sparse_kkt_differentiate_adjoint_info(calipso_hip_sparse_kkt*, double out[4]);
 int32_t calipso_hip_sparse_kkt_differentiate_adjoint_times(calipso_hip_sparse_kkt*, double out[3]);

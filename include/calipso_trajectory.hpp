@@ -249,25 +249,34 @@ int32_t block_eval(void* user, uint32_t flags, const double* x, const double* y,
 }
 
 // the sparse handle's route: the Jacobians' and the Hessian's non-zeros go to their positions in the handle's nzval arrays.  It has no destination for the dual
-// gradients (the handle gathers them) nor for anything with respect to theta: such flags are code 1
+// gradients (the handle gathers them): such flags are code 1.  The derivatives with respect to theta go to the handle's stored parameter patterns when it has them
+// (the three parameter pattern pointers of calipso_device_sparse_data are non-NULL); without them those flags are code 1 as well
 template <class S>
 int32_t sparse_eval(void* user, uint32_t flags, const double* x, const double* y, const double* z, const double* theta, const calipso_device_sparse_data* out,
                     void* hip_stream) {
     User* u = (User*)user;
     if (!u || !out || out->nx != u->t.nx || out->ne != u->t.ne || out->nc != u->t.nc || out->np != u->t.np) return 1;
-    if (flags & (CALIPSO_EVAL_EQUALITY_DUAL_GRADIENT | CALIPSO_EVAL_CONE_DUAL_GRADIENT | CALIPSO_EVAL_EQUALITY_JACOBIAN_PARAMETERS | CALIPSO_EVAL_CONE_JACOBIAN_PARAMETERS | LPAR)) return 1;
+    const bool parameters = SparseLayout{out}.parameters();
+    if (flags & (CALIPSO_EVAL_EQUALITY_DUAL_GRADIENT | CALIPSO_EVAL_CONE_DUAL_GRADIENT)) return 1;
+    if (!parameters && (flags & (CALIPSO_EVAL_EQUALITY_JACOBIAN_PARAMETERS | CALIPSO_EVAL_CONE_JACOBIAN_PARAMETERS | LPAR))) return 1;
     hipStream_t stream = (hipStream_t)hip_stream;
     u->last_enqueued = 0;
     Route& r = u->sparse;
     if (r.ready && (r.key0 != out->lagrangian_hessian || r.key2 != out->equality_jacobian_variables || r.key3 != out->cone_jacobian_variables)) return 3;
+    if (r.ready && r.key1 != (int64_t)(intptr_t)out->lagrangian_gradient_parameters) {      // the handle's parameter patterns were set or replaced: the addresses are others
+        if (hipStreamSynchronize(stream) != hipSuccess) return 2;
+        free_route(r);
+    }
     if (!r.ready) {
         r.key0 = out->lagrangian_hessian; r.key2 = out->equality_jacobian_variables; r.key3 = out->cone_jacobian_variables;
+        r.key1 = (int64_t)(intptr_t)out->lagrangian_gradient_parameters;
         int rc = sparse_route(shape_of<S>(), u->t, out, r.t);
         if (!rc) rc = upload(u, r, stream);
         if (rc) { free_route(r); return rc; }
     }
     double* base[N_DEST] = {out->objective_gradient_variables, out->equality_constraint, out->cone_constraint, out->equality_jacobian_variables,
-                            out->cone_jacobian_variables, nullptr, nullptr, out->objective, nullptr, nullptr, out->lagrangian_hessian, nullptr};
+                            out->cone_jacobian_variables, parameters ? out->equality_jacobian_parameters : nullptr, parameters ? out->cone_jacobian_parameters : nullptr,
+                            out->objective, nullptr, nullptr, out->lagrangian_hessian, parameters ? out->lagrangian_gradient_parameters : nullptr};
     return run<S>(u, r, flags, x, y, z, theta, base, stream);
 }
 

@@ -131,10 +131,12 @@ struct BlockLayout {
 };
 
 // the stored patterns of a sparse handle (calipso_device_sparse_data: CSC, 1-based, rows ascending within a column): a non-zero's address is its position in the
-// nzval array, found by binary search in its column; -1 where the pattern has no such entry.  D_GP, D_HP and D_LGP have no destination on this route — the flags that
-// would store through them are refused and their base is NULL — so they get address 0, which nothing stores through
+// nzval array, found by binary search in its column; -1 where the pattern has no such entry.  D_GP, D_HP and D_LGP are addressed the same way in the stored parameter
+// patterns (calipso_hip_sparse_kkt_set_parameter_patterns) when the handle has them; without them they have no destination on this route — the flags that would store
+// through them are refused and their base is NULL — so they get address 0, which nothing stores through
 struct SparseLayout {
     const calipso_device_sparse_data* o;
+    bool parameters() const { return o->Lp_colptr && o->gp_colptr && o->hp_colptr; }
     static int64_t find(const int64_t* colptr, const int64_t* rowval, int64_t i, int64_t j) {
         int64_t lo = colptr[j] - 1, hi = colptr[j + 1] - 1;
         while (lo < hi) {
@@ -148,7 +150,9 @@ struct SparseLayout {
         case D_GX: return find(o->gx_colptr, o->gx_rowval, i, j);
         case D_HX: return find(o->hx_colptr, o->hx_rowval, i, j);
         case D_LXX: return find(o->Lxx_colptr, o->Lxx_rowval, i, j);
-        case D_GP: case D_HP: case D_LGP: return 0;
+        case D_GP: return parameters() ? find(o->gp_colptr, o->gp_rowval, i, j) : 0;
+        case D_HP: return parameters() ? find(o->hp_colptr, o->hp_rowval, i, j) : 0;
+        case D_LGP: return parameters() ? find(o->Lp_colptr, o->Lp_rowval, i, j) : 0;
         default: return -1;
         }
     }
@@ -257,7 +261,13 @@ inline int sparse_route(const Shape& sh, const Tables& u, const calipso_device_s
         !sparse_pattern_ok(out->hx_colptr, out->hx_rowval, u.nc, u.nx, out->nnz_hx)) return 1;
     std::vector<Segment> segs;
     add_segment(segs, 0, 0, out->nnz_gx); add_segment(segs, 1, 0, out->nnz_hx); add_segment(segs, 2, 0, out->nnz_Lxx);
-    return build_table(sh, u, SparseLayout{out}, segs, r);
+    const SparseLayout where{out};
+    if (where.parameters()) {                             // ... and one per stored parameter array
+        if (!sparse_pattern_ok(out->gp_colptr, out->gp_rowval, u.ne, u.np, out->nnz_gp) || !sparse_pattern_ok(out->hp_colptr, out->hp_rowval, u.nc, u.np, out->nnz_hp) ||
+            !sparse_pattern_ok(out->Lp_colptr, out->Lp_rowval, u.nx, u.np, out->nnz_Lp)) return 1;
+        add_segment(segs, 3, 0, out->nnz_gp); add_segment(segs, 4, 0, out->nnz_hp); add_segment(segs, 5, 0, out->nnz_Lp);
+    }
+    return build_table(sh, u, where, segs, r);
 }
 
 }  // namespace trajectory

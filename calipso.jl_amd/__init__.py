@@ -857,6 +857,49 @@ class SparseLDL(_Handle):
         return float(ms[0]), float(ms[1])
 
 
+class _Columns:
+    """A block (N,) or (N, k) — a host array, or a CUDA tensor for the device route — on its way through an entry of SparseKKT that takes and gives k x rows buffers:
+    k, whether the caller's shape has no k axis, the input's pointer, outputs on the same side and the way back into the caller's shape.  Without a block: outputs
+    for k columns alone.  (A CPU tensor's pointer goes through to the library, which refuses it naming the argument.)"""
+
+    def __init__(self, handle, message=None, block=None, name=None, k=0, device=False):
+        self.device, self.k, self.squeeze, self.pointer = device or hasattr(block, "is_cuda"), k, False, None
+        if self.device:
+            import torch
+            self._empty, self._where = torch.empty, dict(dtype=torch.float64, device=torch.device("cuda", handle.device))
+        if block is None:
+            return
+        if self.device:
+            if block.dim() not in (1, 2) or block.shape[0] != handle.N:
+                raise ValueError(message)
+            self.squeeze, self.k = block.dim() == 1, (1 if block.dim() == 1 else int(block.shape[1]))
+            self._block = block.detach().reshape(handle.N, self.k).t().contiguous()
+            self.pointer = handle._device_pointer(self._block, name, self.k * handle.N)
+        else:
+            self._block, self.k, self.squeeze = pack_cotangent(block, (), handle.N, message)
+            self.pointer = _pd(self._block)
+
+    def entry(self, L, name):
+        return getattr(L, "calipso_hip_" + name + ("_device" if self.device else ""))
+
+    def empty(self, rows):
+        """a k x rows output"""
+        return self._empty((self.k, rows), **self._where) if self.device else np.zeros((self.k, rows))
+
+    def ptr(self, out):
+        if out is None:
+            return None
+        if self.device:
+            return C.c_void_p(out.data_ptr())
+        return _pd(out) if out.size else None
+
+    def back(self, out):
+        """a k x rows output in the caller's shape: (rows,), or (rows, k)"""
+        if self.device:
+            return out[0] if self.squeeze else out.t()
+        return unpack_columns(out, (), self.k, (out.shape[1],), self.squeeze)
+
+
 class SparseKKT(_Handle):
     """search_direction! (src/solver/search_direction.jl:1-23) on sparse problem data resident on the device (include/calipso_hip.h, "search_direction! on
     sparse problem data"; csrc/sparse_kkt.hip): assembly of jacobian_variables_symmetric, inertia correction, the symmetric solve and iterative refinement
@@ -1182,53 +1225,35 @@ class SparseKKT(_Handle):
     GRADIENTS = "LqgbHh"      # the data gradients of vjp by letter: Lxx, q, gx, b, hx, hvec — the matrices as the values on their stored patterns
     _QP_LETTERS = dict(P="L", A="g", G="H")      # a handle from SparseConicQP also answers for P, A, G
 
-    def _columns_call(self, entry, a, message, call):
-        """a (N,) or (N, k), host array or CUDA tensor -> call(k, pointer of the N x k column-major block, pointer of an N x k output) -> the output in a's shape"""
-        if self._is_device(a) and hasattr(a, "is_cuda"):
-            import torch
-            if a.dim() not in (1, 2) or a.shape[0] != self.N:
-                raise ValueError(message)
-            k = 1 if a.dim() == 1 else int(a.shape[1])
-            src = a.detach().reshape(self.N, k).t().contiguous()
-            out = torch.empty((k, self.N), dtype=torch.float64, device=torch.device("cuda", self.device))
-            self._check(call(True, k, self._device_pointer(src, entry, k * self.N), C.c_void_p(out.data_ptr())), entry)
-            return out[0] if a.dim() == 1 else out.t()
-        flat, k, squeeze = pack_cotangent(a, (), self.N, message)
-        out = np.zeros(k * self.N)
-        self._check(call(False, k, _pd(flat), _pd(out)), entry)
-        return unpack_columns(out, (), k, (self.N,), squeeze)
-
     def solve_columns(self, B, transposed=False):
         """X = M B for the condensed solve's map M of solve_symmetric (transposed: M' B) with the CURRENT factorisation, all columns of B (N,) or (N, k) through the
         launches of one; no refinement.  A CUDA tensor takes the device route and comes back as one"""
-        L = self._L
-        return self._columns_call("sparse_kkt_solve_columns", B, "SparseKKT.solve_columns: B must be (N,) or (N, k)", lambda dev, k, b, x:
-                                  (L.calipso_hip_sparse_kkt_solve_columns_device if dev else L.calipso_hip_sparse_kkt_solve_columns)(self._h, k, 1 if transposed else 0, b, x))
+        cols = _Columns(self, "SparseKKT.solve_columns: B must be (N,) or (N, k)", B, "sparse_kkt_solve_columns")
+        out = cols.empty(self.N)
+        self._check(cols.entry(self._L, "sparse_kkt_solve_columns")(self._h, cols.k, 1 if transposed else 0, cols.pointer, cols.ptr(out)), "sparse_kkt_solve_columns")
+        return cols.back(out)
 
     def differentiate(self, J=None, columns=None, device=False):
         """forward differentiate! for the caller's dR/dtheta J (N,) or (N, k): one factorisation at the (ep, ed) the handle holds, then S = -M J (with the correction rounds
         under set_option("differentiate_refinement", 1): differentiate_info).  J=None: the evaluator's own dR/dtheta on the stored patterns of set_parameter_patterns,
         evaluated at the resident point and theta — all num_parameters columns, or those of `columns` (0-based parameter indices, repeats allowed); the result is
         (N, k), bit for bit what differentiate(J) gives for the same block; device=True returns it as a CUDA tensor"""
-        L = self._L
         if J is None:
             if columns is None:
                 k, cp = getattr(self, "num_parameters", 0), None
             else:
-                cols = np.ascontiguousarray(columns, dtype=np.int64).reshape(-1) + 1
-                k, cp = int(cols.size), _pi(cols)
-            if device:
-                import torch
-                out = torch.empty((max(k, 1), self.N), dtype=torch.float64, device=torch.device("cuda", self.device))
-                self._check(L.calipso_hip_sparse_kkt_differentiate_parameters_device(self._h, k, cp, C.c_void_p(out.data_ptr())), "sparse_kkt_differentiate_parameters_device")
-                return out[:k].t()
-            out = np.zeros((max(k, 1), self.N))
-            self._check(L.calipso_hip_sparse_kkt_differentiate_parameters(self._h, k, cp, _pd(out)), "sparse_kkt_differentiate_parameters")
-            return out[:k].T.copy()
+                selected = np.ascontiguousarray(columns, dtype=np.int64).reshape(-1) + 1
+                k, cp = int(selected.size), _pi(selected)
+            cols, name = _Columns(self, k=max(k, 1), device=device), "sparse_kkt_differentiate_parameters"      # (one column at least: the library refuses k = 0 by name)
+            out = cols.empty(self.N)
+            self._check(cols.entry(self._L, name)(self._h, k, cp, cols.ptr(out)), name + ("_device" if device else ""))
+            return cols.back(out)[:, :k]
         if columns is not None:
             raise ValueError("SparseKKT.differentiate: columns selects parameters of the evaluator's dR/dtheta (J=None); a J of the caller's is taken whole")
-        return self._columns_call("sparse_kkt_differentiate", J, "SparseKKT.differentiate: J must be (N,) or (N, k)", lambda dev, k, j, s:
-                                  (L.calipso_hip_sparse_kkt_differentiate_device if dev else L.calipso_hip_sparse_kkt_differentiate)(self._h, k, j, s))
+        cols = _Columns(self, "SparseKKT.differentiate: J must be (N,) or (N, k)", J, "sparse_kkt_differentiate")
+        out = cols.empty(self.N)
+        self._check(cols.entry(self._L, "sparse_kkt_differentiate")(self._h, cols.k, cols.pointer, cols.ptr(out)), "sparse_kkt_differentiate")
+        return cols.back(out)
 
     def vjp(self, V, adjoint=True, qp="", theta=None):
         """reverse differentiate! for cotangents V = dLoss/dw (N,) or (N, k): the same factorisation, lambda = M' V, and the gradients of the loss with respect to the data
@@ -1241,76 +1266,36 @@ class SparseKKT(_Handle):
         qp = qp or ""
         if theta is None:
             theta = self._has_parameter_patterns()
-        if theta:
-            if qp:
-                raise ValueError("SparseKKT.vjp: theta belongs to a handle with an evaluator, qp to one with an attached QP")
-            return self._vjp_theta(V, adjoint)
+        if theta and qp:
+            raise ValueError("SparseKKT.vjp: theta belongs to a handle with an evaluator, qp to one with an attached QP")
         if any(c not in self.GRADIENTS + "PAG" for c in qp):
             raise ValueError("SparseKKT.vjp: qp is a string of letters out of 'LqgbHh' (and 'PAG' on a handle from SparseConicQP)")
         if any(c in "PAG" for c in qp) and not hasattr(self, "_conic_qp"):
             raise ValueError("SparseKKT.vjp: P, A, G are the data of a handle from SparseConicQP; this handle answers for 'LqgbHh'")
-        asked = [self._QP_LETTERS.get(c, c) for c in qp]
-        sizes = dict(zip(self.GRADIENTS, (self.nnz[0], self.nx, self.nnz[1], self.ne, self.nnz[2], self.nc)))
-        message = "SparseKKT.vjp: V must be (N,) or (N, k)"
-        device = self._is_device(V) and hasattr(V, "is_cuda")
-        if device:
-            import torch
-            if V.dim() not in (1, 2) or V.shape[0] != self.N:
-                raise ValueError(message)
-            squeeze, k = V.dim() == 1, (1 if V.dim() == 1 else int(V.shape[1]))
-            where = torch.device("cuda", self.device)
-            src = V.detach().reshape(self.N, k).t().contiguous()
-            adj = torch.empty((k, self.N), dtype=torch.float64, device=where) if adjoint else None
-            grads = {c: torch.empty((k, sizes[c]), dtype=torch.float64, device=where) for c in set(asked)}
-            ptrs = (C.c_void_p * 6)(*[C.c_void_p(grads[c].data_ptr()) if c in grads else None for c in self.GRADIENTS]) if grads else None
-            self._check(self._L.calipso_hip_sparse_kkt_differentiate_adjoint_device(self._h, k, self._device_pointer(src, "V", k * self.N),
-                                                                                    C.c_void_p(adj.data_ptr()) if adjoint else None, ptrs), "sparse_kkt_differentiate_adjoint_device")
-            shape = lambda t: t[0] if squeeze else t.t()
-        else:
-            flat, k, squeeze = pack_cotangent(V, (), self.N, message)
-            adj = np.zeros((k, self.N)) if adjoint else None
-            grads = {c: np.zeros((k, sizes[c])) for c in set(asked)}
-            ptrs = (C.POINTER(C.c_double) * 6)(*[_pd(grads[c]) if c in grads and grads[c].size else None for c in self.GRADIENTS]) if grads else None
-            self._check(self._L.calipso_hip_sparse_kkt_differentiate_adjoint(self._h, k, _pd(flat), _opt(adj), ptrs), "sparse_kkt_differentiate_adjoint")
-            shape = lambda a: a[0].copy() if squeeze else a.T.copy()
+        cols = _Columns(self, "SparseKKT.vjp: V must be (N,) or (N, k)", V, "V")
+        adj = cols.empty(self.N) if adjoint else None
         out = {}
-        if adjoint:
-            out["adjoint"] = shape(adj)
-        for c in qp:
-            g = grads[self._QP_LETTERS.get(c, c)]
-            if c == "P":
-                ij, ji, scale = self._conic_qp_positions(device)
-                g = scale * (g[:, ij] + g[:, ji])
-            elif c == "G":
-                g = -g
-            out[c] = shape(g)
-        return out
-
-    def _vjp_theta(self, V, adjoint):
-        message, npar = "SparseKKT.vjp: V must be (N,) or (N, k)", getattr(self, "num_parameters", 0)
-        if self._is_device(V) and hasattr(V, "is_cuda"):
-            import torch
-            if V.dim() not in (1, 2) or V.shape[0] != self.N:
-                raise ValueError(message)
-            squeeze, k = V.dim() == 1, (1 if V.dim() == 1 else int(V.shape[1]))
-            where = torch.device("cuda", self.device)
-            src = V.detach().reshape(self.N, k).t().contiguous()
-            adj = torch.empty((k, self.N), dtype=torch.float64, device=where) if adjoint else None
-            grad = torch.empty((k, max(npar, 1)), dtype=torch.float64, device=where)
-            self._check(self._L.calipso_hip_sparse_kkt_differentiate_adjoint_parameters_device(self._h, k, self._device_pointer(src, "V", k * self.N),
-                                                                                               C.c_void_p(adj.data_ptr()) if adjoint else None, C.c_void_p(grad.data_ptr())),
-                        "sparse_kkt_differentiate_adjoint_parameters_device")
-            shape = lambda t: t[0] if squeeze else t.t()
-            grad = grad[:, :npar]
+        if theta:                                # the two entries differ only in which gradient arrays follow the adjoint
+            npar, name = getattr(self, "num_parameters", 0), "sparse_kkt_differentiate_adjoint_parameters"
+            grad = cols.empty(max(npar, 1))
+            self._check(cols.entry(self._L, name)(self._h, cols.k, cols.pointer, cols.ptr(adj), cols.ptr(grad)), name + ("_device" if cols.device else ""))
+            out["theta"] = cols.back(grad[:, :npar])
         else:
-            flat, k, squeeze = pack_cotangent(V, (), self.N, message)
-            adj = np.zeros((k, self.N)) if adjoint else None
-            grad = np.zeros((k, max(npar, 1)))
-            self._check(self._L.calipso_hip_sparse_kkt_differentiate_adjoint_parameters(self._h, k, _pd(flat), _opt(adj), _pd(grad)), "sparse_kkt_differentiate_adjoint_parameters")
-            shape = lambda a: a[0].copy() if squeeze else a.T.copy()
-            grad = grad[:, :npar]
-        out = {"adjoint": shape(adj)} if adjoint else {}
-        out["theta"] = shape(grad)
+            sizes = dict(zip(self.GRADIENTS, (self.nnz[0], self.nx, self.nnz[1], self.ne, self.nnz[2], self.nc)))
+            grads = {c: cols.empty(sizes[c]) for c in set(self._QP_LETTERS.get(c, c) for c in qp)}
+            ptrs = ((C.c_void_p if cols.device else C.POINTER(C.c_double)) * 6)(*[cols.ptr(grads.get(c)) for c in self.GRADIENTS]) if grads else None
+            name = "sparse_kkt_differentiate_adjoint"
+            self._check(cols.entry(self._L, name)(self._h, cols.k, cols.pointer, cols.ptr(adj), ptrs), name + ("_device" if cols.device else ""))
+            for c in qp:
+                g = grads[self._QP_LETTERS.get(c, c)]
+                if c == "P":
+                    ij, ji, scale = self._conic_qp_positions(cols.device)
+                    g = scale * (g[:, ij] + g[:, ji])
+                elif c == "G":
+                    g = -g
+                out[c] = cols.back(g)
+        if adjoint:
+            out = dict(adjoint=cols.back(adj), **out)
         return out
 
     def _conic_qp_positions(self, device):

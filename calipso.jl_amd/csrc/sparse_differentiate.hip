@@ -2,9 +2,8 @@
 // calipso_hip_sparse_kkt_solve_columns / _differentiate / _differentiate_adjoint (include/calipso_hip.h).  Nothing here is dense: besides the N x k columns themselves
 // the memory is that of the handle, and the data gradients live on the stored patterns.
 //
-//   the map, k columns at once     step = M residual of search_direction_symmetric! (search_direction.jl:25-104) and its transpose (sparse_differentiate.hpp): a "pre"
-//                                  launch, ONE calipso_hip_sparse_solve_device for all k columns, a "post" launch.  blockIdx.y carries the column: no loop over columns
-//                                  anywhere.  One thread per (row, column); a second-order cone of any dimension one thread per (cone, column), as in sparse_kkt.hip.
+//   the map, k columns at once     step = M residual of search_direction_symmetric! (search_direction.jl:25-104) and its transpose: map_columns of sparse_kkt.hip,
+//                                  which a Newton step's solve_symmetric goes through with one column.  No loop over columns anywhere.
 //   H X, H' X, k columns           the unreduced matrix applied from the same data, one thread per (row, column), fused with E = R - H X and the per-column infinity
 //                                  norms (k doubles, read back once per round).  Transposed: Lxx through its column view, the s and t couplings of the local rows swapped.
 //   correction rounds              iterative_refinement.jl:14-44 on all columns with the decisions of sensitivity_columns.hpp and the masked accumulate / restore of
@@ -28,16 +27,15 @@
 using calipso::i64;
 using namespace calipso::sparse_kkt;
 using namespace calipso::sparse_differentiate;
-typedef calipso_hip_sparse_kkt KH;
 static_assert(KT == calipso::sparse_parameters::THREADS && KT % calipso::sparse_parameters::WAVE == 0,
               "sparse_parameters.hpp counts workgroups of KT threads, and a wavefront of the gradient kernel lies within one of them");
 
 struct calipso::sparse_kkt::DiffState {
-    double* ws = nullptr; size_t doubles = 0;     // the workspace of a k-column pass (sparse_differentiate.hpp: Layout): grown on demand, kept
-    int* masks = nullptr; size_t ints = 0;
+    Grown<double> ws;                             // the workspace of a k-column pass (sparse_differentiate.hpp: Layout)
+    Grown<int> masks;
     double* wd = nullptr;                         // N: the resident point with the kept slacks in its s and t rows (what the kernels read the cone blocks from)
-    double* gbuf = nullptr; size_t gdoubles = 0;  // the gradients of a host call before they are copied out
-    int* sel = nullptr; size_t sel_ints = 0;      // the selected parameters of a differentiate_parameters call, 0-based
+    Grown<double> gbuf;                           // the gradients of a host call before they are copied out
+    Grown<int> sel;                               // the selected parameters of a differentiate_parameters call, 0-based
     std::vector<int> sel_host;
     calipso::SensitivityColumns cols;
     std::vector<double> norms;
@@ -52,75 +50,6 @@ namespace {
 typedef calipso::sparse_kkt::DiffState DS;
 
 __device__ __forceinline__ double rabs(double x) { return x != x ? __builtin_huge_val() : fabs(x); }      // a NaN reports +inf, as in sparse_kkt.hip
-
-// ---- the condensed solve's outer halves: G (n x k) from V (N x k) before the LDL^T solve, OUT (N x k) from its solution Hs (n x k) and V after it -----------------
-// items: [0, nx) variables, [nx, nx + ne) equality rows, [.., n) cone rows, [n, n + nsoc) second-order cones; blockIdx.y: the column
-template <bool TRANSPOSED>
-__global__ __launch_bounds__(KT) void k_diff_pre(const KktDev d, double ep, double ed, const double* __restrict__ V, double* __restrict__ G, double* __restrict__ OUT) {
-    long long k = (long long)blockIdx.x * KT + threadIdx.x;
-    const size_t col = blockIdx.y;
-    const double* v = V + col * (size_t)d.N;
-    double* g = G + col * (size_t)d.n;
-    if (k < d.nx) { g[k] = v[k]; return; }
-    k -= d.nx;
-    const MapScalars c{ep, ed, d.ne ? d.rho[0] : 0.0};
-    if (k < d.ne) { g[d.nx + k] = TRANSPOSED ? equality_transposed_pre(c, v[d.o_r + k], v[d.o_y + k]) : equality_forward_pre(c, v[d.o_r + k], v[d.o_y + k]); return; }
-    k -= d.ne;
-    const int oc = d.nx + d.ne;
-    if (k < d.nc) {
-        const int kind = d.row_cone[k];
-        if (kind == -1) {
-            const double sl = d.w[d.o_s + k], t = d.w[d.o_t + k];
-            g[oc + k] = TRANSPOSED ? nonnegative_transposed_pre(c, sl, t, v[d.o_s + k], v[d.o_z + k], v[d.o_t + k]) : nonnegative_forward_pre(c, sl, t, v[d.o_s + k], v[d.o_z + k], v[d.o_t + k]);
-        } else if (kind == -2) g[oc + k] = v[d.o_z + k];
-        return;
-    }
-    k -= d.nc;
-    if (k >= d.nsoc) return;
-    const int st = d.soc_start[k], dm = d.soc_dim[k];
-    const double* sl = d.w + d.o_s + st; const double* t = d.w + d.o_t + st;
-    if (TRANSPOSED) {       // the temporaries in the cone's entries of the output column, which the post launch writes
-        double* out = OUT + col * (size_t)d.N;
-        soc_transposed_pre(c, dm, sl, t, v + d.o_s + st, v + d.o_z + st, v + d.o_t + st, g + oc + st, out + d.o_t + st, out + d.o_s + st);
-    } else soc_forward_pre(c, dm, sl, t, v + d.o_s + st, v + d.o_z + st, v + d.o_t + st, g + oc + st);
-}
-
-template <bool TRANSPOSED>
-__global__ __launch_bounds__(KT) void k_diff_post(const KktDev d, double ep, double ed, const double* __restrict__ Hs, const double* __restrict__ V, double* __restrict__ OUT) {
-    long long k = (long long)blockIdx.x * KT + threadIdx.x;
-    const size_t col = blockIdx.y;
-    const double* v = V + col * (size_t)d.N;
-    const double* h = Hs + col * (size_t)d.n;
-    double* out = OUT + col * (size_t)d.N;
-    if (k < d.nx) { out[k] = h[k]; return; }
-    k -= d.nx;
-    const MapScalars c{ep, ed, d.ne ? d.rho[0] : 0.0};
-    if (k < d.ne) {
-        const double he = h[d.nx + k];
-        out[d.o_y + k] = he;
-        out[d.o_r + k] = TRANSPOSED ? equality_transposed_post(c, he, v[d.o_r + k]) : equality_forward_post(c, he, v[d.o_r + k]);
-        return;
-    }
-    k -= d.ne;
-    const int oc = d.nx + d.ne;
-    if (k < d.nc) {
-        const int kind = d.row_cone[k];
-        const double hc = h[oc + k];
-        out[d.o_z + k] = hc;
-        if (kind == -1) {
-            const double sl = d.w[d.o_s + k], t = d.w[d.o_t + k];
-            if (TRANSPOSED) nonnegative_transposed_post(c, sl, t, hc, v[d.o_s + k], v[d.o_t + k], &out[d.o_s + k], &out[d.o_t + k]);
-            else nonnegative_forward_post(c, sl, t, hc, v[d.o_s + k], v[d.o_t + k], &out[d.o_s + k], &out[d.o_t + k]);
-        } else if (kind == -2) { out[d.o_s + k] = 0.0; out[d.o_t + k] = 0.0; }
-        return;
-    }
-    k -= d.nc;
-    if (k >= d.nsoc) return;
-    const int st = d.soc_start[k], dm = d.soc_dim[k];
-    const double* sl = d.w + d.o_s + st; const double* t = d.w + d.o_t + st;
-    if (TRANSPOSED) soc_transposed_post(c, dm, sl, t, h + oc + st, v + d.o_s + st, v + d.o_t + st, out + d.o_s + st, out + d.o_t + st);
-    else soc_forward_post(c, dm, sl, t, h + oc + st, v + d.o_s + st, v + d.o_t + st, out + d.o_s + st, out + d.o_t + st);
-}
 
 // ---- H X (TRANSPOSED: H' X) for k columns, one thread per (row of the point's layout, column): E = R - H X and the columns' infinity norms, or (R NULL) E = H X -----
 // row i of arrow(a) v over the cone's dm entries
@@ -276,9 +205,6 @@ __global__ __launch_bounds__(KT) void k_diff_place_slacks(const KktDev d, const 
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------------------------------------------
-#define KK(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return kkt_fail(s, CALIPSO_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); } while (0)
-#define REFUSE(text) do { const std::string t__ = (text); if (!t__.empty()) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, t__); } while (0)
-#define DEVPTR(p) do { if (device) { const int rc__ = kkt_device_pointer(s, (const void*)(p), entry, #p); if (rc__ < 0) return rc__; } } while (0)
 
 unsigned blocks_of(long long items) { return (unsigned)std::max<long long>((items + KT - 1) / KT, 1); }
 
@@ -288,23 +214,13 @@ int ensure_state(KH* s) {
     s->diff = t;                                             // (released with the handle, whatever happens below)
     for (hipEvent_t& e : t->ev) KK(hipEventCreate(&e));
     for (hipEvent_t& e : t->ev_pass) KK(hipEventCreate(&e));
-    return kkt_reserve(s, &t->wd, (size_t)s->d.N);
-}
-// grown on demand, never shrunk, kept: a call that repeats its shapes allocates nothing
-template <typename T>
-int grow(KH* s, T** buf, size_t* have, size_t want) {
-    if (want <= *have) return CALIPSO_OK;
-    KK(hipStreamSynchronize(s->st));
-    if (*buf) { (void)hipFree(*buf); *buf = nullptr; *have = 0; }
-    KK(hipMalloc((void**)buf, sizeof(T) * want));
-    KK(hipMemsetAsync(*buf, 0, sizeof(T) * want, s->st));
-    *have = want;
-    return CALIPSO_OK;
+    return device_fixed(s, &t->wd, (size_t)s->d.N);
 }
 int reserve_pass(KH* s, const Layout& L, size_t k) {
     DS* t = s->diff;
-    int rc = grow(s, &t->ws, &t->doubles, std::max<size_t>(L.doubles, 1));
-    if (rc >= 0 && L.ints) rc = grow(s, &t->masks, &t->ints, L.ints);
+    int rc = device_grown(s, t->ws, std::max<size_t>(L.doubles, 1));
+    if (rc >= 0 && L.ints) rc = device_grown(s, t->masks, L.ints);
+    t->rounds_ran = false;                                   // (a new pass: pass_times reads the rounds' events only where they ran)
     if (t->norms.size() < k) t->norms.assign(k, 0.0);
     return rc;
 }
@@ -319,19 +235,6 @@ KktDev slacks_view(KH* s) {
     return d;
 }
 
-// OUT = M V (transposed: M' V) for k columns on the device: pre, ONE k-column LDL^T solve, post
-int map_columns(KH* s, const KktDev& d, bool transposed, int k, const double* V, double* rsym, double* dsym, double* OUT, bool timed = false) {
-    const dim3 grid(blocks_of((long long)d.n + d.nsoc), (unsigned)k), block(KT);
-    if (timed) { KK(hipEventRecord(s->diff->ev_pass[0], s->st)); s->diff->rounds_ran = false; }
-    if (transposed) hipLaunchKernelGGL(k_diff_pre<true>, grid, block, 0, s->st, d, s->sc.ep, s->sc.ed, V, rsym, OUT);
-    else hipLaunchKernelGGL(k_diff_pre<false>, grid, block, 0, s->st, d, s->sc.ep, s->sc.ed, V, rsym, OUT);
-    const int rc = calipso_hip_sparse_solve_device(s->sp, k, rsym, dsym);
-    if (rc < 0) return kkt_sparse_failed(s, rc, "solve");
-    if (transposed) hipLaunchKernelGGL(k_diff_post<true>, grid, block, 0, s->st, d, s->sc.ep, s->sc.ed, dsym, V, OUT);
-    else hipLaunchKernelGGL(k_diff_post<false>, grid, block, 0, s->st, d, s->sc.ep, s->sc.ed, dsym, V, OUT);
-    if (timed) KK(hipEventRecord(s->diff->ev_pass[1], s->st));
-    return CALIPSO_OK;
-}
 // after the entry's last synchronise: the pass and its rounds into the handle's timing, slots 6 and 7 (calipso_hip_sparse_kkt_timing)
 int pass_times(KH* s) {
     DS* t = s->diff;
@@ -352,8 +255,8 @@ void enqueue_mul(KH* s, const KktDev& d, bool transposed, int k, const double* X
 // back once per round, the correction through the same factors, X(:, j) += correction(:, j) for the columns sensitivity_columns.hpp keeps active
 int refine_columns(KH* s, const KktDev& d, const Layout& L, const double* R, bool transposed, int k, double info[4]) {
     DS* t = s->diff;
-    double *w = t->ws, *X = w + L.X.off, *E = w + L.E.off, *C = w + L.C.off, *Xsave = w + L.Xsave.off, *norms = w + L.norms.off;
-    int *active = t->masks, *restore = t->masks + k;
+    double *w = t->ws.p, *X = w + L.X.off, *E = w + L.E.off, *C = w + L.C.off, *Xsave = w + L.Xsave.off, *norms = w + L.norms.off;
+    int *active = t->masks.p, *restore = active + k;
     calipso::SensitivityColumns& cols = t->cols;
     cols.begin(k);
     KK(hipEventRecord(t->ev_pass[2], s->st));
@@ -385,7 +288,7 @@ bool rounds_wanted(const KH* s) { return s->differentiate_refinement && s->opt.i
 
 // the columns of a call into the workspace: the caller's (host or device) -> L.V
 int take_columns(KH* s, const Layout& L, const double* B, bool device) {
-    KK(hipMemcpyAsync(s->diff->ws + L.V.off, B, sizeof(double) * L.V.len, device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->st));
+    KK(hipMemcpyAsync(s->diff->ws.p + L.V.off, B, sizeof(double) * L.V.len, device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->st));
     return CALIPSO_OK;
 }
 int give_columns(KH* s, const double* from, size_t count, double* to, bool device) {
@@ -395,7 +298,7 @@ int give_columns(KH* s, const double* from, size_t count, double* to, bool devic
 
 int factorize_held(KH* s, const KktDev& d) {
     int64_t in[3] = {0, 0, 0};
-    const int rc = kkt_assemble_factorize(s, d, s->sc.ep, s->sc.ed, in);
+    const int rc = assemble_factorize(s, d, s->sc.ep, s->sc.ed, in);
     return rc < 0 ? rc : CALIPSO_OK;
 }
 // K and its factor were formed at the differentiate slacks: where those are not the resident point's, the single-column entries must assemble again
@@ -407,13 +310,13 @@ int solve_columns(KH* s, const char* entry, int64_t k, int32_t transposed, const
     REFUSE(check_array(entry, "B", B)); REFUSE(check_array(entry, "X", X));
     KK(hipSetDevice(s->device));
     DEVPTR(B); DEVPTR(X);
-    if (!s->factored) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": factorize first (the columns go through the current factorisation)");
+    if (!s->factored) return fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": factorize first (the columns go through the current factorisation)");
     int rc = ensure_state(s);
     if (rc < 0) return rc;
     const Layout L = layout((size_t)s->d.N, (size_t)s->d.n, (size_t)k, false);
     if ((rc = reserve_pass(s, L, (size_t)k)) < 0 || (rc = take_columns(s, L, B, device)) < 0) return rc;
-    double* w = s->diff->ws;
-    if ((rc = map_columns(s, s->d, transposed != 0, (int)k, w + L.V.off, w + L.rsym.off, w + L.dsym.off, w + L.X.off, true)) < 0) return rc;
+    double* w = s->diff->ws.p;
+    if ((rc = map_columns(s, s->d, transposed != 0, (int)k, w + L.V.off, w + L.rsym.off, w + L.dsym.off, w + L.X.off, s->diff->ev_pass)) < 0) return rc;
     if ((rc = give_columns(s, w + L.X.off, L.X.len, X, device)) < 0) return rc;
     KK(hipStreamSynchronize(s->st));
     KK(hipGetLastError());
@@ -427,13 +330,13 @@ int take_parameter_columns(KH* s, const char* entry, const Layout& L, int64_t k,
     if (rc < 0) return rc;
     const int* sel = nullptr;
     if (columns) {
-        if ((rc = grow(s, &t->sel, &t->sel_ints, (size_t)k)) < 0) return rc;
+        if ((rc = device_grown(s, t->sel, (size_t)k)) < 0) return rc;
         t->sel_host.resize((size_t)k);
         for (int64_t c = 0; c < k; ++c) t->sel_host[(size_t)c] = (int)(columns[c] - 1);
-        KK(hipMemcpyAsync(t->sel, t->sel_host.data(), sizeof(int) * (size_t)k, hipMemcpyHostToDevice, s->st));
-        sel = t->sel;
+        KK(hipMemcpyAsync(t->sel.p, t->sel_host.data(), sizeof(int) * (size_t)k, hipMemcpyHostToDevice, s->st));
+        sel = t->sel.p;
     }
-    double* V = t->ws + L.V.off;
+    double* V = t->ws.p + L.V.off;
     KK(hipMemsetAsync(V, 0, sizeof(double) * L.V.len, s->st));
     hipLaunchKernelGGL(k_diff_parameter_columns, dim3(calipso::sparse_parameters::scatter_blocks(s->par.longest), (unsigned)k), dim3(KT), 0, s->st, s->d, s->par.d, sel, V);
     return CALIPSO_OK;
@@ -443,7 +346,7 @@ int take_parameter_columns(KH* s, const char* entry, const Layout& L, int64_t k,
 int differentiate(KH* s, const char* entry, int64_t k, const double* jacobian_parameters, double* sensitivity, bool device, bool parameters = false, const int64_t* columns = nullptr) {
     if (!s) return CALIPSO_ERR_ARGUMENT;
     if (parameters) {
-        if (!s->par.set) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": no parameter patterns set (calipso_hip_sparse_kkt_set_parameter_patterns first)");
+        if (!s->par.set) return fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": no parameter patterns set (calipso_hip_sparse_kkt_set_parameter_patterns first)");
         REFUSE(calipso::sparse_parameters::check_selection(entry, s->par.d.np, k, columns));
     } else {
         REFUSE(check_columns(entry, k));
@@ -453,7 +356,7 @@ int differentiate(KH* s, const char* entry, int64_t k, const double* jacobian_pa
     KK(hipSetDevice(s->device));
     if (!parameters) DEVPTR(jacobian_parameters);
     DEVPTR(sensitivity);
-    int rc = kkt_values_missing(s, entry);
+    int rc = values_missing(s, entry);
     if (rc < 0 || (rc = ensure_state(s)) < 0) return rc;
     DS* t = s->diff;
     const bool rounds = rounds_wanted(s);
@@ -464,8 +367,8 @@ int differentiate(KH* s, const char* entry, int64_t k, const double* jacobian_pa
     std::copy(info0, info0 + 4, t->info_forward);
     const KktDev d = slacks_view(s);
     if ((rc = factorize_held(s, d)) < 0) return rc;                                           // differentiate.jl:21-27
-    double *w = t->ws, *X = w + L.X.off;
-    rc = map_columns(s, d, false, (int)k, w + L.V.off, w + L.rsym.off, w + L.dsym.off, X, true);     // :29-53 for all columns
+    double *w = t->ws.p, *X = w + L.X.off;
+    rc = map_columns(s, d, false, (int)k, w + L.V.off, w + L.rsym.off, w + L.dsym.off, X, t->ev_pass);     // :29-53 for all columns
     if (rc >= 0 && rounds) rc = refine_columns(s, d, L, w + L.V.off, false, (int)k, t->info_forward);
     leave_factorization(s);
     if (rc < 0) return rc;
@@ -483,7 +386,7 @@ int differentiate_adjoint(KH* s, const char* entry, int64_t k, const double* cot
     REFUSE(check_columns(entry, k));
     REFUSE(check_array(entry, "cotangent", cotangent));
     if (parameters) {
-        if (!s->par.set) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": no parameter patterns set (calipso_hip_sparse_kkt_set_parameter_patterns first)");
+        if (!s->par.set) return fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": no parameter patterns set (calipso_hip_sparse_kkt_set_parameter_patterns first)");
         REFUSE(check_array(entry, "grad_theta", grad_theta));
     }
     KK(hipSetDevice(s->device));
@@ -491,8 +394,8 @@ int differentiate_adjoint(KH* s, const char* entry, int64_t k, const double* cot
     if (parameters) DEVPTR(grad_theta);
     static const char* const names[6] = {"grad[0] (Lxx)", "grad[1] (q)", "grad[2] (gx)", "grad[3] (b)", "grad[4] (hx)", "grad[5] (hvec)"};
     bool wanted = false;
-    for (int i = 0; grad && i < 6; ++i) if (grad[i]) { wanted = true; if (device) { const int rc = kkt_device_pointer(s, grad[i], entry, names[i]); if (rc < 0) return rc; } }
-    int rc = kkt_values_missing(s, entry);
+    for (int i = 0; grad && i < 6; ++i) if (grad[i]) { wanted = true; if (device) { const int rc = device_pointer(s, grad[i], entry, names[i]); if (rc < 0) return rc; } }
+    int rc = values_missing(s, entry);
     if (rc < 0 || (rc = ensure_state(s)) < 0) return rc;
     DS* t = s->diff;
     REFUSE(check_gradients(entry, wanted, s->qp_attached, s->have[3]));
@@ -505,15 +408,15 @@ int differentiate_adjoint(KH* s, const char* entry, int64_t k, const double* cot
     if (wanted && !device) {                                                                  // a host call's gradients are staged on the device
         size_t total = 0;
         for (int i = 0; i < 6; ++i) if (grad[i]) total += sizes[i] * (size_t)k;
-        if ((rc = grow(s, &t->gbuf, &t->gdoubles, std::max<size_t>(total, 1))) < 0) return rc;
+        if ((rc = device_grown(s, t->gbuf, std::max<size_t>(total, 1))) < 0) return rc;
         size_t at = 0;
-        for (int i = 0; i < 6; ++i) if (grad[i]) { out.p[i] = t->gbuf + at; at += sizes[i] * (size_t)k; }
+        for (int i = 0; i < 6; ++i) if (grad[i]) { out.p[i] = t->gbuf.p + at; at += sizes[i] * (size_t)k; }
     } else if (wanted) for (int i = 0; i < 6; ++i) out.p[i] = grad[i];
     const size_t theta_count = parameters ? (size_t)s->par.d.np * (size_t)k : 0;
     double* theta_out = grad_theta;
     if (parameters && !device) {                                                              // ... and so is a host call's grad_theta
-        if ((rc = grow(s, &t->gbuf, &t->gdoubles, theta_count)) < 0) return rc;
-        theta_out = t->gbuf;
+        if ((rc = device_grown(s, t->gbuf, theta_count)) < 0) return rc;
+        theta_out = t->gbuf.p;
     }
     const double info0[4] = {(double)k, 0, 0, 0};
     std::copy(info0, info0 + 4, t->info_reverse);
@@ -523,8 +426,8 @@ int differentiate_adjoint(KH* s, const char* entry, int64_t k, const double* cot
     if (parameters && (rc = parameters_enqueue(s, entry)) < 0) return rc;                     // dR/dtheta at the resident point and theta, on the handle's stream
     const KktDev d = slacks_view(s);
     if ((rc = factorize_held(s, d)) < 0) return rc;
-    double *w = t->ws, *V = w + L.V.off, *X = w + L.X.off;
-    rc = map_columns(s, d, true, (int)k, V, w + L.rsym.off, w + L.dsym.off, X, true);          // differentiate.jl:29-58 transposed, all columns at once
+    double *w = t->ws.p, *V = w + L.V.off, *X = w + L.X.off;
+    rc = map_columns(s, d, true, (int)k, V, w + L.rsym.off, w + L.dsym.off, X, t->ev_pass);          // differentiate.jl:29-58 transposed, all columns at once
     if (rc >= 0 && rounds) rc = refine_columns(s, d, L, V, true, (int)k, t->info_reverse);
     leave_factorization(s);
     if (rc < 0) return rc;
@@ -562,10 +465,6 @@ namespace sparse_kkt {
 void diff_state_release(KH* s) {
     DS* t = s->diff;
     if (!t) return;
-    if (t->ws) (void)hipFree(t->ws);
-    if (t->masks) (void)hipFree(t->masks);
-    if (t->gbuf) (void)hipFree(t->gbuf);
-    if (t->sel) (void)hipFree(t->sel);
     for (hipEvent_t e : t->ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : t->ev_pass) if (e) (void)hipEventDestroy(e);
     delete t;
@@ -574,7 +473,7 @@ void diff_state_release(KH* s) {
 
 int diff_set_option(KH* s, const char* name, double value) {
     if (std::strcmp(name, "differentiate_refinement")) return 0;
-    if (!refinement_option(value)) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_sparse_kkt_set_option: differentiate_refinement is 0 or 1");
+    if (!refinement_option(value)) return fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_sparse_kkt_set_option: differentiate_refinement is 0 or 1");
     s->differentiate_refinement = value == 1.0;
     return 1;
 }
@@ -631,7 +530,7 @@ int32_t calipso_hip_sparse_kkt_differentiate_adjoint_info(calipso_hip_sparse_kkt
 int32_t calipso_hip_sparse_kkt_differentiate_bytes(calipso_hip_sparse_kkt* s, int64_t* out) {
     if (!s || !out) return CALIPSO_ERR_ARGUMENT;
     const DS* t = s->diff;
-    *out = t ? (int64_t)(sizeof(double) * (t->doubles + t->gdoubles + (size_t)s->d.N) + sizeof(int) * (t->ints + t->sel_ints)) : 0;
+    *out = t ? (int64_t)(sizeof(double) * (t->ws.cap + t->gbuf.cap + (size_t)s->d.N) + sizeof(int) * (t->masks.cap + t->sel.cap)) : 0;
     return CALIPSO_OK;
 }
 int32_t calipso_hip_sparse_kkt_differentiate_adjoint_times(calipso_hip_sparse_kkt* s, double out[3]) {

@@ -1,5 +1,6 @@
-// sparse_differentiate.hpp — what differentiate! on the sparse handle (sparse_differentiate.hip) shares between device and host: the per-row and per-cone arithmetic
-// of the condensed solve's four maps, the workspace layout of a k-column pass and the argument checks of the entries.  No HIP include: the hipcc-only qualifiers sit
+// sparse_differentiate.hpp — what the sparse handle shares between device and host: the per-row and per-cone arithmetic of the condensed solve's four maps — the ONLY
+// copy: the map kernels of sparse_kkt.hip, which every Newton step's solve and every column of differentiate! go through, call these functions — and, for
+// differentiate! (sparse_differentiate.hip), the workspace layout of a k-column pass and the argument checks of the entries.  No HIP include: the hipcc-only qualifiers sit
 // behind CALIPSO_HD, so tests/sparse_differentiate_host/main.cpp builds the maps' dense matrices on the CPU under the sanitizers.
 //
 // The condensed solve of search_direction_symmetric! (search_direction.jl:25-104) is  step = M residual,  M = E K^-1 F + D:
@@ -80,7 +81,7 @@ CALIPSO_HD void nonnegative_transposed_post(const MapScalars& c, double s, doubl
 }
 
 // ---- second-order cones: s, t and every vector are the cone's dm entries ---------------------------------------------------------------------------------------
-// rsym = r_z + W (Cbar r_s + r_t)      (the operation order of k_kkt_residual_symmetric)
+// rsym = r_z + W (Cbar r_s + r_t)
 CALIPSO_HD void soc_forward_pre(const MapScalars& c, int dm, const double* s, const double* t, const double* r_s, const double* r_z, const double* r_t, double* out) {
     const double S0 = s[0] - c.ed, ep = c.ep;
     double v0 = 0.0;
@@ -91,7 +92,7 @@ CALIPSO_HD void soc_forward_pre(const MapScalars& c, int dm, const double* s, co
                   [&](int a) { return a == 0 ? v0 : (s[a] * r_s[0] + S0 * r_s[a]) + r_t[a]; },
                   [&](int a, double v) { out[a] = r_z[a] + v; });
 }
-// Ds = W (r_t + Cbar (r_s + dz)),  Dt = Cbar^-1 (r_t - Ct Ds)      (the operation order of k_kkt_recover; Ds is read back)
+// Ds = W (r_t + Cbar (r_s + dz)),  Dt = Cbar^-1 (r_t - Ct Ds)      (Ds is read back)
 CALIPSO_HD void soc_forward_post(const MapScalars& c, int dm, const double* s, const double* t, const double* dz, const double* r_s, const double* r_t, double* Ds, double* Dt) {
     const double S0 = s[0] - c.ed, ep = c.ep;
     double v0 = 0.0;

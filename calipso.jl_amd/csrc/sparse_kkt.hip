@@ -9,7 +9,10 @@
 //   H v (device, two launches)         the unreduced N x N matrix applied from the same data: the rows that gather from Lxx, gx, hx (one thread per row, or one
 //                                      wavefront per row where the rows are long), and the r-, s-, t-rows (one thread each); fused with residual - H step and
 //                                      its infinity norm, so a refinement round reads back one double.
-//   residual_symmetric!, recovery      residual.jl:53-101, search_direction.jl:59-101: one thread per row, one per second-order cone.
+//   the condensed map, k columns       step = M residual of search_direction_symmetric! (search_direction.jl:25-104) and its transpose: map_columns — a "pre" launch
+//                                      (residual_symmetric!, residual.jl:53-101), ONE calipso_hip_sparse_solve_device for all k columns, a "post" launch (the recovery,
+//                                      search_direction.jl:59-101).  One thread per (row, column), one per (second-order cone, column); blockIdx.y carries the column.  The
+//                                      row arithmetic is sparse_differentiate.hpp's, the only copy: solve_symmetric is the forward map with one column.
 //   driver (host)                      inertia_correction! (inertia.jl:30-80) and iterative_refinement! (iterative_refinement.jl:1-52) through ic_begin / ic_after /
 //                                      refine_next of step_decisions.hpp; every retry is one assemble + one calipso_hip_sparse_factorize_device.
 //   H \ residual (option krylov_fallback)  where the refinement fails (search_direction.jl:22): restarted right-preconditioned GMRES on H with solve_symmetric as
@@ -23,12 +26,13 @@
 #include <vector>
 
 #include "sparse_kkt_handle.hpp"           // the handle, KktDev, and (through sparse_kkt.hpp) the analysis: plain host C++
-#include "sparse_differentiate.hpp"        // arrow_inverse: the closed-form arrow inverse, shared with the multi-column maps
+#include "sparse_differentiate.hpp"        // the row arithmetic of the condensed maps and arrow_inverse, the closed-form arrow inverse: device and host
 
 using calipso::i64;
 using calipso::Options;
 using calipso::Scalars;
 using namespace calipso::sparse_kkt;
+using namespace calipso::sparse_differentiate;
 static_assert(REFUSED_ARGUMENT == CALIPSO_ERR_ARGUMENT, "a refused pattern is an argument error");
 
 namespace {
@@ -158,83 +162,73 @@ __global__ __launch_bounds__(KT) void k_kkt_mul_local(const KktDev d, double ep,
     sink_store(sink, row, live, a);
 }
 
-// ---- residual_symmetric! (residual.jl:53-101): rsym (n) from a residual in the point's layout -----------------------------------------------------------------
-__global__ __launch_bounds__(KT) void k_kkt_residual_symmetric(const KktDev d, double ep, double ed, const double* __restrict__ res, double* __restrict__ rsym) {
+// ---- the condensed solve's outer halves: G (n x k) from V (N x k) before the LDL^T solve, OUT (N x k) from its solution Hs (n x k) and V after it -----------------
+// items: [0, nx) variables, [nx, nx + ne) equality rows, [.., n) cone rows, [n, n + nsoc) second-order cones; blockIdx.y: the column
+template <bool TRANSPOSED>
+__global__ __launch_bounds__(KT) void k_kkt_map_pre(const KktDev d, double ep, double ed, const double* __restrict__ V, double* __restrict__ G, double* __restrict__ OUT) {
     long long k = (long long)blockIdx.x * KT + threadIdx.x;
-    if (k < d.nx) { rsym[k] = res[k]; return; }
+    const size_t col = blockIdx.y;
+    const double* v = V + col * (size_t)d.N;
+    double* g = G + col * (size_t)d.n;
+    if (k < d.nx) { g[k] = v[k]; return; }
     k -= d.nx;
-    if (k < d.ne) { rsym[d.nx + k] = res[d.o_y + k] + res[d.o_r + k] / (d.rho[0] + ep); return; }
+    const MapScalars c{ep, ed, d.ne ? d.rho[0] : 0.0};
+    if (k < d.ne) { g[d.nx + k] = TRANSPOSED ? equality_transposed_pre(c, v[d.o_r + k], v[d.o_y + k]) : equality_forward_pre(c, v[d.o_r + k], v[d.o_y + k]); return; }
     k -= d.ne;
     const int oc = d.nx + d.ne;
     if (k < d.nc) {
         const int kind = d.row_cone[k];
         if (kind == -1) {
-            const double Sb = d.w[d.o_s + k] - ed, T = d.w[d.o_t + k];
-            rsym[oc + k] = res[d.o_z + k] + (res[d.o_t + k] + Sb * res[d.o_s + k]) / (T + Sb * ep);
-        } else if (kind == -2) rsym[oc + k] = res[d.o_z + k];
+            const double sl = d.w[d.o_s + k], t = d.w[d.o_t + k];
+            g[oc + k] = TRANSPOSED ? nonnegative_transposed_pre(c, sl, t, v[d.o_s + k], v[d.o_z + k], v[d.o_t + k]) : nonnegative_forward_pre(c, sl, t, v[d.o_s + k], v[d.o_z + k], v[d.o_t + k]);
+        } else if (kind == -2) g[oc + k] = v[d.o_z + k];
         return;
     }
     k -= d.nc;
     if (k >= d.nsoc) return;
-    // rz + (Cs + Cbar_t P)^-1 (Cbar_t rs + rt)
     const int st = d.soc_start[k], dm = d.soc_dim[k];
     const double* sl = d.w + d.o_s + st; const double* t = d.w + d.o_t + st;
-    const double* rs = res + d.o_s + st; const double* rt = res + d.o_t + st; const double* rz = res + d.o_z + st;
-    double* out = rsym + oc + st;
-    const double S0 = sl[0] - ed;
-    double v0 = 0.0;
-    for (int b = 0; b < dm; ++b) v0 += (b == 0 ? S0 : sl[b]) * rs[b];
-    v0 += rt[0];
-    arrow_inverse(dm,
-                  [&](int b) { return t[b] + (b == 0 ? S0 : sl[b]) * ep; },
-                  [&](int a) { return a == 0 ? v0 : (sl[a] * rs[0] + S0 * rs[a]) + rt[a]; },
-                  [&](int a, double v) { out[a] = rz[a] + v; });
+    if (TRANSPOSED) {       // the temporaries in the cone's entries of the output column, which the post launch writes
+        double* out = OUT + col * (size_t)d.N;
+        soc_transposed_pre(c, dm, sl, t, v + d.o_s + st, v + d.o_z + st, v + d.o_t + st, g + oc + st, out + d.o_t + st, out + d.o_s + st);
+    } else soc_forward_pre(c, dm, sl, t, v + d.o_s + st, v + d.o_z + st, v + d.o_t + st, g + oc + st);
 }
 
-// ---- the recovery of Dr, Ds, Dt (search_direction.jl:59-101): step (N) from the symmetric solution (n) and the residual --------------------------------------
-__global__ __launch_bounds__(KT) void k_kkt_recover(const KktDev d, double ep, double ed, const double* __restrict__ dsym, const double* __restrict__ res,
-                                                    double* __restrict__ step) {
+template <bool TRANSPOSED>
+__global__ __launch_bounds__(KT) void k_kkt_map_post(const KktDev d, double ep, double ed, const double* __restrict__ Hs, const double* __restrict__ V, double* __restrict__ OUT) {
     long long k = (long long)blockIdx.x * KT + threadIdx.x;
-    if (k < d.nx) { step[k] = dsym[k]; return; }
+    const size_t col = blockIdx.y;
+    const double* v = V + col * (size_t)d.N;
+    const double* h = Hs + col * (size_t)d.n;
+    double* out = OUT + col * (size_t)d.N;
+    if (k < d.nx) { out[k] = h[k]; return; }
     k -= d.nx;
-    if (k < d.ne) { const double dy = dsym[d.nx + k]; step[d.o_y + k] = dy; step[d.o_r + k] = (res[d.o_r + k] + dy) / (d.rho[0] + ep); return; }
+    const MapScalars c{ep, ed, d.ne ? d.rho[0] : 0.0};
+    if (k < d.ne) {
+        const double he = h[d.nx + k];
+        out[d.o_y + k] = he;
+        out[d.o_r + k] = TRANSPOSED ? equality_transposed_post(c, he, v[d.o_r + k]) : equality_forward_post(c, he, v[d.o_r + k]);
+        return;
+    }
     k -= d.ne;
     const int oc = d.nx + d.ne;
     if (k < d.nc) {
         const int kind = d.row_cone[k];
-        const double dz = dsym[oc + k];
-        step[d.o_z + k] = dz;
+        const double hc = h[oc + k];
+        out[d.o_z + k] = hc;
         if (kind == -1) {
-            const double Sb = d.w[d.o_s + k] - ed, T = d.w[d.o_t + k], rt = res[d.o_t + k];
-            const double ds = (rt + Sb * (res[d.o_s + k] + dz)) / (T + Sb * ep);
-            step[d.o_s + k] = ds;
-            step[d.o_t + k] = (rt - T * ds) / Sb;
-        } else if (kind == -2) { step[d.o_s + k] = 0.0; step[d.o_t + k] = 0.0; }
+            const double sl = d.w[d.o_s + k], t = d.w[d.o_t + k];
+            if (TRANSPOSED) nonnegative_transposed_post(c, sl, t, hc, v[d.o_s + k], v[d.o_t + k], &out[d.o_s + k], &out[d.o_t + k]);
+            else nonnegative_forward_post(c, sl, t, hc, v[d.o_s + k], v[d.o_t + k], &out[d.o_s + k], &out[d.o_t + k]);
+        } else if (kind == -2) { out[d.o_s + k] = 0.0; out[d.o_t + k] = 0.0; }
         return;
     }
     k -= d.nc;
     if (k >= d.nsoc) return;
     const int st = d.soc_start[k], dm = d.soc_dim[k];
     const double* sl = d.w + d.o_s + st; const double* t = d.w + d.o_t + st;
-    const double* rs = res + d.o_s + st; const double* rt = res + d.o_t + st; const double* dz = dsym + oc + st;
-    double* Ds = step + d.o_s + st; double* Dt = step + d.o_t + st;
-    const double S0 = sl[0] - ed;
-    // Ds = (Cs + Cbar_t P)^-1 (rt + Cbar_t (rs + dz))
-    double v0 = 0.0;
-    for (int b = 0; b < dm; ++b) v0 += (b == 0 ? S0 : sl[b]) * (rs[b] + dz[b]);
-    v0 = rt[0] + v0;
-    arrow_inverse(dm,
-                  [&](int b) { return t[b] + (b == 0 ? S0 : sl[b]) * ep; },
-                  [&](int a) { return a == 0 ? v0 : rt[a] + (sl[a] * (rs[0] + dz[0]) + S0 * (rs[a] + dz[a])); },
-                  [&](int a, double v) { Ds[a] = v; });
-    // Dt = Cbar_t^-1 (rt - Cs Ds): this thread reads back its own Ds
-    double c0 = 0.0;
-    for (int b = 0; b < dm; ++b) c0 += t[b] * Ds[b];
-    c0 = rt[0] - c0;
-    arrow_inverse(dm,
-                  [&](int b) { return b == 0 ? S0 : sl[b]; },
-                  [&](int a) { return a == 0 ? c0 : rt[a] - (t[a] * Ds[0] + t[0] * Ds[a]); },
-                  [&](int a, double v) { Dt[a] = v; });
+    if (TRANSPOSED) soc_transposed_post(c, dm, sl, t, h + oc + st, v + d.o_s + st, v + d.o_t + st, out + d.o_s + st, out + d.o_t + st);
+    else soc_forward_post(c, dm, sl, t, h + oc + st, v + d.o_s + st, v + d.o_t + st, out + d.o_s + st, out + d.o_t + st);
 }
 
 __global__ __launch_bounds__(KT) void k_kkt_add(int N, double* __restrict__ step, const double* __restrict__ corr) {
@@ -244,31 +238,14 @@ __global__ __launch_bounds__(KT) void k_kkt_add(int N, double* __restrict__ step
 
 unsigned blocks(long long items, int per_block = KT) { return (unsigned)std::max<long long>((items + per_block - 1) / per_block, 1); }
 
-}  // namespace
-
-namespace {
-
-typedef calipso_hip_sparse_kkt KH;
 thread_local std::string g_kkt_err;
 
-int fail(KH* s, int rc, const std::string& text) { (s ? s->err_text : g_kkt_err) = text; return rc; }
-#define KK(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return fail(s, CALIPSO_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); } while (0)
+}  // namespace
 
-template <typename T>
-int upload(KH* s, const std::vector<T>& h, const T** out) {
-    T* p = nullptr;
-    KK(hipMalloc((void**)&p, sizeof(T) * std::max<size_t>(h.size(), 1)));
-    s->dev.push_back(p);
-    if (!h.empty()) KK(hipMemcpy(p, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice));
-    *out = p;
-    return CALIPSO_OK;
-}
-int reserve(KH* s, double** out, size_t count) {
-    KK(hipMalloc((void**)out, sizeof(double) * std::max<size_t>(count, 1)));
-    s->dev.push_back(*out);
-    KK(hipMemset(*out, 0, sizeof(double) * std::max<size_t>(count, 1)));
-    return CALIPSO_OK;
-}
+// ---- what the other units of the handle call too (sparse_kkt_handle.hpp) -----------------------------------------------------------------------------------------
+namespace calipso::sparse_kkt {
+
+int fail(KH* s, int rc, const std::string& text) { (s ? s->err_text : g_kkt_err) = text; return rc; }
 
 // every non-NULL pointer of a device entry must be device memory of the handle's device: checked before anything is enqueued
 int device_pointer(KH* s, const void* p, const char* entry, const char* arg) {
@@ -283,9 +260,6 @@ int device_pointer(KH* s, const void* p, const char* entry, const char* arg) {
     if (at.device != s->device) return fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": " + arg + " lives on device " + std::to_string(at.device) + ", the handle on device " + std::to_string(s->device));
     return CALIPSO_OK;
 }
-#define DEVPTR(entry, p) do { const int rc__ = device_pointer(s, (const void*)(p), entry, #p); if (rc__ < 0) return rc__; } while (0)
-
-int sparse_failed(KH* s, int rc, const char* what) { return fail(s, rc, std::string(what) + ": " + calipso_hip_sparse_last_error(s->sp)); }
 
 int values_missing(KH* s, const char* entry) {
     static const char* const names[5] = {"Lxx", "gx", "hx", "w", "penalty"};
@@ -294,8 +268,24 @@ int values_missing(KH* s, const char* entry) {
     return CALIPSO_OK;
 }
 
-int set_values(KH* s, const double* Lxx, const double* gx, const double* hx, const double* w, const double* penalty, hipMemcpyKind kind) {
+int enter(KH* s, const char* entry, Need need) {
+    if (!s) return CALIPSO_ERR_ARGUMENT;
     KK(hipSetDevice(s->device));
+    if (need == VALUES) return values_missing(s, entry);
+    if (need >= STATE) { const int rc = solve_state(s); if (rc < 0) return rc; }
+    return need > STATE ? solve_ready(s, entry, need == STATE_POINT) : CALIPSO_OK;
+}
+
+}  // namespace calipso::sparse_kkt
+
+namespace {
+
+int sparse_failed(KH* s, int rc, const char* what) { return fail(s, rc, std::string(what) + ": " + calipso_hip_sparse_last_error(s->sp)); }
+
+int set_values(KH* s, const char* entry, const double* Lxx, const double* gx, const double* hx, const double* w, const double* penalty, bool device) {
+    ENTER(HANDLE);
+    DEVPTR(Lxx); DEVPTR(gx); DEVPTR(hx); DEVPTR(w); DEVPTR(penalty);
+    const hipMemcpyKind kind = device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     const double* src[5] = {Lxx, gx, hx, w, penalty};
     double* dst[5] = {s->Lxx, s->gx, s->hx, s->w, s->rho};
     const size_t count[5] = {(size_t)s->d.nnzL, (size_t)s->d.nnzg, (size_t)s->d.nnzh, (size_t)s->d.N, 1};
@@ -310,6 +300,10 @@ void enqueue_assemble(KH* s, const KktDev& d, double ep, double ed) {
     const long long items = (long long)d.nnzL + d.nnzg + d.nnzh + d.nx + d.ne + d.nc + d.ncc;
     hipLaunchKernelGGL(k_kkt_assemble, dim3(blocks(items)), dim3(KT), 0, s->st, d, ep, ed, s->K);
 }
+}  // namespace
+
+namespace calipso::sparse_kkt {
+
 // one assemble + factorisation at (ep, ed); inertia as compute_inertia! (linear_solver.jl:33-44)
 int assemble_factorize(KH* s, const KktDev& d, double ep, double ed, int64_t inertia[3]) {
     KK(hipEventRecord(s->ev[0], s->st));
@@ -323,14 +317,28 @@ int assemble_factorize(KH* s, const KktDev& d, double ep, double ed, int64_t ine
     double t[2] = {0.0, 0.0}; (void)calipso_hip_sparse_timing(s->sp, t); s->ms[1] += t[0];
     return rc;
 }
-// search_direction_symmetric! (search_direction.jl:25-104) with the current factorisation: out (N) from res (N), both on the device
-int solve_symmetric(KH* s, const double* res, double* out, double* ms) {
-    KK(hipEventRecord(s->ev[0], s->st));
-    hipLaunchKernelGGL(k_kkt_residual_symmetric, dim3(blocks((long long)s->d.n + s->d.nsoc)), dim3(KT), 0, s->st, s->d, s->sc.ep, s->sc.ed, res, s->rsym);
-    const int rc = calipso_hip_sparse_solve_device(s->sp, 1, s->rsym, s->dsym);
+
+int map_columns(KH* s, const KktDev& d, bool transposed, int k, const double* V, double* rsym, double* dsym, double* OUT, const hipEvent_t* around) {
+    const dim3 grid(blocks((long long)d.n + d.nsoc), (unsigned)k), block(KT);
+    if (around) KK(hipEventRecord(around[0], s->st));
+    if (transposed) hipLaunchKernelGGL(k_kkt_map_pre<true>, grid, block, 0, s->st, d, s->sc.ep, s->sc.ed, V, rsym, OUT);
+    else hipLaunchKernelGGL(k_kkt_map_pre<false>, grid, block, 0, s->st, d, s->sc.ep, s->sc.ed, V, rsym, OUT);
+    const int rc = calipso_hip_sparse_solve_device(s->sp, k, rsym, dsym);
     if (rc < 0) return sparse_failed(s, rc, "solve");
-    hipLaunchKernelGGL(k_kkt_recover, dim3(blocks((long long)s->d.n + s->d.nsoc)), dim3(KT), 0, s->st, s->d, s->sc.ep, s->sc.ed, s->dsym, res, out);
-    KK(hipEventRecord(s->ev[1], s->st));
+    if (transposed) hipLaunchKernelGGL(k_kkt_map_post<true>, grid, block, 0, s->st, d, s->sc.ep, s->sc.ed, dsym, V, OUT);
+    else hipLaunchKernelGGL(k_kkt_map_post<false>, grid, block, 0, s->st, d, s->sc.ep, s->sc.ed, dsym, V, OUT);
+    if (around) KK(hipEventRecord(around[1], s->st));
+    return CALIPSO_OK;
+}
+
+}  // namespace calipso::sparse_kkt
+
+namespace {
+
+// search_direction_symmetric! (search_direction.jl:25-104) with the current factorisation: out (N) from res (N), both on the device — the forward map, one column
+int solve_symmetric(KH* s, const double* res, double* out, double* ms) {
+    const int rc = map_columns(s, s->d, false, 1, res, s->rsym, s->dsym, out, s->ev);
+    if (rc < 0) return rc;
     KK(hipStreamSynchronize(s->st));
     float t = 0.f; KK(hipEventElapsedTime(&t, s->ev[0], s->ev[1])); *ms += t;
     return CALIPSO_OK;
@@ -358,22 +366,12 @@ int residual_error(KH* s, const double* res, const double* step, double* norm, d
 // s->corr and copied into `step` only where everything stayed finite: otherwise `step` is left as it was.  Kernels: sparse_krylov.hip; decisions: sparse_krylov.hpp
 namespace kry = calipso::sparse_krylov;
 
-int krylov_reserve(KH* s, const kry::Layout& lay) {
-    if (!s->kry_ev[0]) { KK(hipEventCreate(&s->kry_ev[0])); KK(hipEventCreate(&s->kry_ev[1])); }
-    if ((size_t)lay.doubles <= s->kry_cap) return CALIPSO_OK;
-    KK(hipStreamSynchronize(s->st));
-    if (s->kry_ws) { (void)hipFree(s->kry_ws); s->kry_ws = nullptr; s->kry_cap = 0; }
-    KK(hipMalloc((void**)&s->kry_ws, sizeof(double) * (size_t)lay.doubles));
-    KK(hipMemsetAsync(s->kry_ws, 0, sizeof(double) * (size_t)lay.doubles, s->st));      // (on the handle's stream: ordered before the kernels that write here)
-    s->kry_cap = (size_t)lay.doubles;
-    return CALIPSO_OK;
-}
-
 int gmres(KH* s, const double* res, double* step) {
     kry::FallbackReport& fr = s->fallback;
     const kry::Layout lay = kry::layout(s->d.N, s->kry.restart);
-    { const int rc = krylov_reserve(s, lay); if (rc < 0) return rc; }
-    double* const ws = s->kry_ws;
+    if (!s->kry_ev[0]) { KK(hipEventCreate(&s->kry_ev[0])); KK(hipEventCreate(&s->kry_ev[1])); }
+    if (const int rc = device_grown(s, s->kry_ws, (size_t)lay.doubles); rc < 0) return rc;
+    double* const ws = s->kry_ws.p;
     double* const V = ws + lay.off_V; double* const Z = ws + lay.off_Z; double* const x = s->corr;
     const size_t N = (size_t)s->d.N, bytes = sizeof(double) * N;
     const double tolerance = s->opt.iterative_refinement_tolerance;
@@ -431,12 +429,14 @@ int gmres(KH* s, const double* res, double* step) {
     float ms = 0.f; KK(hipEventElapsedTime(&ms, s->kry_ev[0], s->kry_ev[1]));
     fr.step_taken = finite;
     fr.v[kry::FI_ITERATIONS] = iterations; fr.v[kry::FI_CYCLES] = cycles; fr.v[kry::FI_NORM] = true_norm; fr.v[kry::FI_CONVERGED] = converged ? 1.0 : 0.0;
-    fr.v[kry::FI_DEVICE_MS] = ms; fr.v[kry::FI_LAUNCHES] = launches; fr.v[kry::FI_WORKSPACE_BYTES] = (double)(sizeof(double) * s->kry_cap);
+    fr.v[kry::FI_DEVICE_MS] = ms; fr.v[kry::FI_LAUNCHES] = launches; fr.v[kry::FI_WORKSPACE_BYTES] = (double)(sizeof(double) * s->kry_ws.cap);
     return CALIPSO_OK;
 }
 
+}  // namespace
+
 // search_direction! (search_direction.jl:1-23) on device vectors
-int search_direction(KH* s, const double* res, double* step, double regularization[3], double info[4]) {
+int calipso::sparse_kkt::search_direction(KH* s, const double* res, double* step, double regularization[3], double info[4]) {
     const auto wall0 = std::chrono::steady_clock::now();
     for (double& m : s->ms) m = 0.0;
     const Options& o = s->opt;
@@ -490,21 +490,6 @@ int search_direction(KH* s, const double* res, double* step, double regularizati
     return leave(status, nfact, it, norm);
 }
 
-}  // namespace
-
-// what sparse_solve.hip calls (sparse_kkt_handle.hpp)
-namespace calipso {
-namespace sparse_kkt {
-int kkt_fail(KH* s, int rc, const std::string& text) { return fail(s, rc, text); }
-int kkt_reserve(KH* s, double** out, size_t count) { return reserve(s, out, count); }
-int kkt_device_pointer(KH* s, const void* p, const char* entry, const char* arg) { return device_pointer(s, p, entry, arg); }
-int kkt_search_direction(KH* s, const double* res, double* step, double regularization[3], double info[4]) { return search_direction(s, res, step, regularization, info); }
-int kkt_values_missing(KH* s, const char* entry) { return values_missing(s, entry); }
-int kkt_assemble_factorize(KH* s, const KktDev& d, double ep, double ed, int64_t inertia[3]) { return assemble_factorize(s, d, ep, ed, inertia); }
-int kkt_sparse_failed(KH* s, int rc, const char* what) { return sparse_failed(s, rc, what); }
-}  // namespace sparse_kkt
-}  // namespace calipso
-
 extern "C" {
 
 const char* calipso_hip_sparse_kkt_last_error(calipso_hip_sparse_kkt* s) { return s ? s->err_text.c_str() : g_kkt_err.c_str(); }
@@ -516,7 +501,6 @@ int32_t calipso_hip_sparse_kkt_destroy(calipso_hip_sparse_kkt* s) {
     solve_state_release(s);
     diff_state_release(s);
     for (void* p : s->dev) if (p) (void)hipFree(p);
-    if (s->kry_ws) (void)hipFree(s->kry_ws);
     for (hipEvent_t e : s->ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : s->kry_ev) if (e) (void)hipEventDestroy(e);
     if (s->sp) (void)calipso_hip_sparse_destroy(s->sp);
@@ -541,21 +525,21 @@ static int32_t kkt_create_impl(KH* s, int32_t method, const int64_t* perm) {
     for (i64 c = 0; c < a.n_nonnegative; ++c) row_cone[(size_t)c] = -1;
     for (i64 j = 0; j < a.n_soc; ++j) for (int i = 0; i < a.soc_dim[(size_t)j]; ++i) row_cone[(size_t)(a.soc_start[(size_t)j] + i)] = (int)j;
     int rc;
-    if ((rc = upload(s, slotL, &d.slotL)) || (rc = upload(s, a.slot_gx, &d.slotg)) || (rc = upload(s, a.slot_hx, &d.sloth)) || (rc = upload(s, a.diag_x, &d.diag_x)) ||
-        (rc = upload(s, a.diag_x_src, &d.diag_x_src)) || (rc = upload(s, a.diag_e, &d.diag_e)) || (rc = upload(s, a.diag_c, &d.diag_c)) || (rc = upload(s, row_cone, &d.row_cone)) ||
-        (rc = upload(s, a.soc_start, &d.soc_start)) || (rc = upload(s, a.soc_dim, &d.soc_dim)) || (rc = upload(s, a.col_cone, &d.col_cone)) ||
-        (rc = upload(s, a.col_index, &d.col_index)) || (rc = upload(s, a.col_slot, &d.col_slot)) ||
-        (rc = upload(s, a.Lxx_rows.ptr, &d.Lr.ptr)) || (rc = upload(s, a.Lxx_rows.col, &d.Lr.idx)) || (rc = upload(s, a.Lxx_rows.src, &d.Lr.src)) ||
-        (rc = upload(s, a.gx_rows.ptr, &d.gr.ptr)) || (rc = upload(s, a.gx_rows.col, &d.gr.idx)) || (rc = upload(s, a.gx_rows.src, &d.gr.src)) ||
-        (rc = upload(s, a.hx_rows.ptr, &d.hr.ptr)) || (rc = upload(s, a.hx_rows.col, &d.hr.idx)) || (rc = upload(s, a.hx_rows.src, &d.hr.src)) ||
-        (rc = upload(s, a.gx_cols.ptr, &d.gc.ptr)) || (rc = upload(s, a.gx_cols.row, &d.gc.idx)) || (rc = upload(s, a.hx_cols.ptr, &d.hc.ptr)) || (rc = upload(s, a.hx_cols.row, &d.hc.idx)) ||
-        (rc = upload(s, a.Lxx_cols.ptr, &d.Lc.ptr)) || (rc = upload(s, a.Lxx_cols.row, &d.Lc.idx)))
+    if ((rc = device_upload(s, slotL, &d.slotL)) || (rc = device_upload(s, a.slot_gx, &d.slotg)) || (rc = device_upload(s, a.slot_hx, &d.sloth)) || (rc = device_upload(s, a.diag_x, &d.diag_x)) ||
+        (rc = device_upload(s, a.diag_x_src, &d.diag_x_src)) || (rc = device_upload(s, a.diag_e, &d.diag_e)) || (rc = device_upload(s, a.diag_c, &d.diag_c)) || (rc = device_upload(s, row_cone, &d.row_cone)) ||
+        (rc = device_upload(s, a.soc_start, &d.soc_start)) || (rc = device_upload(s, a.soc_dim, &d.soc_dim)) || (rc = device_upload(s, a.col_cone, &d.col_cone)) ||
+        (rc = device_upload(s, a.col_index, &d.col_index)) || (rc = device_upload(s, a.col_slot, &d.col_slot)) ||
+        (rc = device_upload(s, a.Lxx_rows.ptr, &d.Lr.ptr)) || (rc = device_upload(s, a.Lxx_rows.col, &d.Lr.idx)) || (rc = device_upload(s, a.Lxx_rows.src, &d.Lr.src)) ||
+        (rc = device_upload(s, a.gx_rows.ptr, &d.gr.ptr)) || (rc = device_upload(s, a.gx_rows.col, &d.gr.idx)) || (rc = device_upload(s, a.gx_rows.src, &d.gr.src)) ||
+        (rc = device_upload(s, a.hx_rows.ptr, &d.hr.ptr)) || (rc = device_upload(s, a.hx_rows.col, &d.hr.idx)) || (rc = device_upload(s, a.hx_rows.src, &d.hr.src)) ||
+        (rc = device_upload(s, a.gx_cols.ptr, &d.gc.ptr)) || (rc = device_upload(s, a.gx_cols.row, &d.gc.idx)) || (rc = device_upload(s, a.hx_cols.ptr, &d.hc.ptr)) || (rc = device_upload(s, a.hx_cols.row, &d.hc.idx)) ||
+        (rc = device_upload(s, a.Lxx_cols.ptr, &d.Lc.ptr)) || (rc = device_upload(s, a.Lxx_cols.row, &d.Lc.idx)))
         return rc;
     d.gc.src = nullptr; d.hc.src = nullptr; d.Lc.src = nullptr;
-    if ((rc = reserve(s, &s->Lxx, (size_t)d.nnzL)) || (rc = reserve(s, &s->gx, (size_t)d.nnzg)) || (rc = reserve(s, &s->hx, (size_t)d.nnzh)) || (rc = reserve(s, &s->w, (size_t)d.N)) ||
-        (rc = reserve(s, &s->rho, 1)) || (rc = reserve(s, &s->K, (size_t)a.nnzK())) || (rc = reserve(s, &s->res, (size_t)d.N)) || (rc = reserve(s, &s->step, (size_t)d.N)) ||
-        (rc = reserve(s, &s->corr, (size_t)d.N)) || (rc = reserve(s, &s->err, (size_t)d.N)) || (rc = reserve(s, &s->rsym, (size_t)d.n)) || (rc = reserve(s, &s->dsym, (size_t)d.n)) ||
-        (rc = reserve(s, &s->norm, 1)) || (rc = reserve(s, &s->dslack, 2 * (size_t)d.nc))) return rc;
+    if ((rc = device_fixed(s, &s->Lxx, (size_t)d.nnzL)) || (rc = device_fixed(s, &s->gx, (size_t)d.nnzg)) || (rc = device_fixed(s, &s->hx, (size_t)d.nnzh)) || (rc = device_fixed(s, &s->w, (size_t)d.N)) ||
+        (rc = device_fixed(s, &s->rho, 1)) || (rc = device_fixed(s, &s->K, (size_t)a.nnzK())) || (rc = device_fixed(s, &s->res, (size_t)d.N)) || (rc = device_fixed(s, &s->step, (size_t)d.N)) ||
+        (rc = device_fixed(s, &s->corr, (size_t)d.N)) || (rc = device_fixed(s, &s->err, (size_t)d.N)) || (rc = device_fixed(s, &s->rsym, (size_t)d.n)) || (rc = device_fixed(s, &s->dsym, (size_t)d.n)) ||
+        (rc = device_fixed(s, &s->norm, 1)) || (rc = device_fixed(s, &s->dslack, 2 * (size_t)d.nc))) return rc;
     d.Lxx = s->Lxx; d.gx = s->gx; d.hx = s->hx; d.w = s->w; d.rho = s->rho;
     // a wavefront per gathered row where the rows are long (a dense-pattern problem), a thread per row where they are short (stage-structured ones)
     s->wave_rows = ((long long)d.nnzL + 2ll * d.nnzg + 2ll * d.nnzh) / std::max(d.n, 1) >= WAVE_ROW_MIN;
@@ -612,21 +596,15 @@ int32_t calipso_hip_sparse_kkt_set_option(calipso_hip_sparse_kkt* s, const char*
 }
 
 int32_t calipso_hip_sparse_kkt_set_values(calipso_hip_sparse_kkt* s, const double* Lxx, const double* gx, const double* hx, const double* w, const double* penalty) {
-    if (!s) return CALIPSO_ERR_ARGUMENT;
-    return set_values(s, Lxx, gx, hx, w, penalty, hipMemcpyHostToDevice);
+    return set_values(s, "calipso_hip_sparse_kkt_set_values", Lxx, gx, hx, w, penalty, false);
 }
 int32_t calipso_hip_sparse_kkt_set_values_device(calipso_hip_sparse_kkt* s, const double* Lxx, const double* gx, const double* hx, const double* w, const double* penalty) {
-    if (!s) return CALIPSO_ERR_ARGUMENT;
-    KK(hipSetDevice(s->device));
-    static const char* const entry = "calipso_hip_sparse_kkt_set_values_device";
-    DEVPTR(entry, Lxx); DEVPTR(entry, gx); DEVPTR(entry, hx); DEVPTR(entry, w); DEVPTR(entry, penalty);
-    return set_values(s, Lxx, gx, hx, w, penalty, hipMemcpyDeviceToDevice);
+    return set_values(s, "calipso_hip_sparse_kkt_set_values_device", Lxx, gx, hx, w, penalty, true);
 }
 
 int32_t calipso_hip_sparse_kkt_factorize(calipso_hip_sparse_kkt* s, double ep, double ed, int64_t inertia[3]) {
-    if (!s) return CALIPSO_ERR_ARGUMENT;
-    KK(hipSetDevice(s->device));
-    { const int rc = values_missing(s, "calipso_hip_sparse_kkt_factorize"); if (rc < 0) return rc; }
+    static const char* const entry = "calipso_hip_sparse_kkt_factorize";
+    ENTER(VALUES);
     int64_t in[3] = {0, 0, 0};
     const int rc = assemble_factorize(s, s->d, ep, ed, in);
     if (inertia) std::copy(in, in + 3, inertia);
@@ -671,34 +649,33 @@ int32_t calipso_hip_sparse_kkt_solve_symmetric(calipso_hip_sparse_kkt* s, const 
     return CALIPSO_OK;
 }
 
-// search_direction_nonsymmetric! for this handle: `H \ residual` by GMRES with the current factorisation, whatever the option krylov_fallback says
-static int32_t solve_nonsymmetric(KH* s, const double* res, double* step) {
+// search_direction_nonsymmetric! for this handle: `H \ residual` by GMRES with the current factorisation, whatever the option krylov_fallback says.  A host call
+// goes through the handle's own res and step; a device call works on the caller's vectors
+static int32_t solve_nonsymmetric(KH* s, const char* entry, const double* residual, double* step, bool device) {
+    if (!s || !residual || !step) return CALIPSO_ERR_ARGUMENT;
+    if (!s->factored) return fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": factorize first");
+    KK(hipSetDevice(s->device));
+    DEVPTR(residual); DEVPTR(step);
+    const size_t bytes = sizeof(double) * (size_t)s->d.N;
+    const double* res = device ? residual : s->res;
+    double* out = device ? step : s->step;
+    if (!device) KK(hipMemcpyAsync(s->res, residual, bytes, hipMemcpyHostToDevice, s->st));
     s->fallback.begin_call();
-    KK(hipMemsetAsync(step, 0, sizeof(double) * (size_t)s->d.N, s->st));      // (a step that is not finite is not taken: zeros then)
-    const int rc = gmres(s, res, step);
+    KK(hipMemsetAsync(out, 0, bytes, s->st));                                  // (a step that is not finite is not taken: zeros then)
+    const int rc = gmres(s, res, out);
     if (rc < 0) return rc;
+    if (!device) {
+        KK(hipMemcpyAsync(step, s->step, bytes, hipMemcpyDeviceToHost, s->st));
+        KK(hipStreamSynchronize(s->st));
+        KK(hipGetLastError());
+    }
     return s->fallback.v[calipso::sparse_krylov::FI_CONVERGED] != 0.0 ? CALIPSO_OK : CALIPSO_WARN_REFINEMENT;
 }
 int32_t calipso_hip_sparse_kkt_solve_nonsymmetric(calipso_hip_sparse_kkt* s, const double* residual, double* step) {
-    if (!s || !residual || !step) return CALIPSO_ERR_ARGUMENT;
-    if (!s->factored) return fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_sparse_kkt_solve_nonsymmetric: factorize first");
-    KK(hipSetDevice(s->device));
-    const size_t bytes = sizeof(double) * (size_t)s->d.N;
-    KK(hipMemcpyAsync(s->res, residual, bytes, hipMemcpyHostToDevice, s->st));
-    const int rc = solve_nonsymmetric(s, s->res, s->step);
-    if (rc < 0) return rc;
-    KK(hipMemcpyAsync(step, s->step, bytes, hipMemcpyDeviceToHost, s->st));
-    KK(hipStreamSynchronize(s->st));
-    KK(hipGetLastError());
-    return rc;
+    return solve_nonsymmetric(s, "calipso_hip_sparse_kkt_solve_nonsymmetric", residual, step, false);
 }
 int32_t calipso_hip_sparse_kkt_solve_nonsymmetric_device(calipso_hip_sparse_kkt* s, const double* residual, double* step) {
-    if (!s || !residual || !step) return CALIPSO_ERR_ARGUMENT;
-    if (!s->factored) return fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_sparse_kkt_solve_nonsymmetric_device: factorize first");
-    KK(hipSetDevice(s->device));
-    static const char* const entry = "calipso_hip_sparse_kkt_solve_nonsymmetric_device";
-    DEVPTR(entry, residual); DEVPTR(entry, step);
-    return solve_nonsymmetric(s, residual, step);
+    return solve_nonsymmetric(s, "calipso_hip_sparse_kkt_solve_nonsymmetric_device", residual, step, true);
 }
 int32_t calipso_hip_sparse_kkt_fallback_info(calipso_hip_sparse_kkt* s, double out[12]) {
     if (!s || !out) return CALIPSO_ERR_ARGUMENT;
@@ -707,10 +684,12 @@ int32_t calipso_hip_sparse_kkt_fallback_info(calipso_hip_sparse_kkt* s, double o
     return CALIPSO_OK;
 }
 
-int32_t calipso_hip_sparse_kkt_search_direction(calipso_hip_sparse_kkt* s, const double* residual, double* step, double regularization[3], double info[4]) {
-    if (!s || !residual || !step || !regularization) return fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_sparse_kkt_search_direction: residual, step and regularization are required");
-    KK(hipSetDevice(s->device));
-    { const int rc = values_missing(s, "calipso_hip_sparse_kkt_search_direction"); if (rc < 0) return rc; }
+static int32_t search_direction_entry(KH* s, const char* entry, const double* residual, double* step, double regularization[3], double info[4], bool device) {
+    if (!s || !residual || !step || !regularization) return fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": residual, step and regularization are required");
+    ENTER(HANDLE);
+    DEVPTR(residual); DEVPTR(step);
+    if (const int rc = values_missing(s, entry); rc < 0) return rc;
+    if (device) return search_direction(s, residual, step, regularization, info);
     const size_t bytes = sizeof(double) * (size_t)s->d.N;
     KK(hipMemcpyAsync(s->res, residual, bytes, hipMemcpyHostToDevice, s->st));
     const int rc = search_direction(s, s->res, s->step, regularization, info);
@@ -719,13 +698,11 @@ int32_t calipso_hip_sparse_kkt_search_direction(calipso_hip_sparse_kkt* s, const
     KK(hipStreamSynchronize(s->st));
     return rc;
 }
+int32_t calipso_hip_sparse_kkt_search_direction(calipso_hip_sparse_kkt* s, const double* residual, double* step, double regularization[3], double info[4]) {
+    return search_direction_entry(s, "calipso_hip_sparse_kkt_search_direction", residual, step, regularization, info, false);
+}
 int32_t calipso_hip_sparse_kkt_search_direction_device(calipso_hip_sparse_kkt* s, const double* residual, double* step, double regularization[3], double info[4]) {
-    if (!s || !residual || !step || !regularization) return fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_sparse_kkt_search_direction_device: residual, step and regularization are required");
-    KK(hipSetDevice(s->device));
-    static const char* const entry = "calipso_hip_sparse_kkt_search_direction_device";
-    DEVPTR(entry, residual); DEVPTR(entry, step);
-    { const int rc = values_missing(s, entry); if (rc < 0) return rc; }
-    return search_direction(s, residual, step, regularization, info);
+    return search_direction_entry(s, "calipso_hip_sparse_kkt_search_direction_device", residual, step, regularization, info, true);
 }
 
 int32_t calipso_hip_sparse_kkt_timing(calipso_hip_sparse_kkt* s, double ms[8]) {

@@ -1,7 +1,8 @@
-// sparse_kkt_handle.hpp — the handle behind calipso_hip_sparse_kkt_* as the two translation units that work on it see it: sparse_kkt.hip (search_direction!) and
-// sparse_solve.hip (the vector half of solve! and its driver).  What every kernel reads (KktDev), the handle itself, and the few functions of sparse_kkt.hip the
-// solve driver calls.
+// sparse_kkt_handle.hpp — the handle behind calipso_hip_sparse_kkt_* as the translation units that work on it see it: sparse_kkt.hip (search_direction!),
+// sparse_solve.hip (the vector half of solve! and its driver), sparse_differentiate.hip (differentiate!) and sparse_krylov.hip.  What every kernel reads (KktDev), the
+// handle itself, the one owner of its device memory (device_fixed, device_grown), the first lines of every entry (enter) and what the units call of each other.
 #pragma once
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -39,14 +40,16 @@ struct ParamDev {
     const double* val[3];
     const int* long_columns;
 };
+// a buffer of the handle that grows on demand, is never shrunk and is kept (device_grown below): a call that repeats its shapes allocates nothing
+template <typename T> struct Grown { T* p = nullptr; size_t cap = 0; };      // cap: entries
+
 // set_parameter_patterns (sparse_solve.hip) fills it; set_evaluator and qp_attach drop it
 struct ParameterPatterns {
     bool set = false;
     ParamDev d{};
-    double* val[3] = {nullptr, nullptr, nullptr};
+    Grown<double> val[3];                         // the resident values; kept when the patterns are dropped and taken again by the next call, as are
+    Grown<int> ints[7];                           // (ptr, idx) x 3 and the long columns on the device
     long long nnz[3] = {0, 0, 0}, longest = 0;
-    int* ints[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // (ptr, idx) x 3 and the long columns on the device, with their capacities:
-    size_t int_cap[7] = {0, 0, 0, 0, 0, 0, 0}, val_cap[3] = {0, 0, 0};                   // kept when the patterns are dropped and taken again by the next call
     std::vector<int64_t> host[6];                 // the HOST copies the evaluator is given: 1-based, (colptr, rowval) of Lp, gp, hp
 };
 
@@ -67,7 +70,7 @@ struct calipso_hip_sparse_kkt {
     bool wave_rows = false;
     double *Lxx = nullptr, *gx = nullptr, *hx = nullptr, *w = nullptr, *rho = nullptr, *K = nullptr;
     double *res = nullptr, *step = nullptr, *corr = nullptr, *err = nullptr, *rsym = nullptr, *dsym = nullptr, *norm = nullptr;
-    std::vector<void*> dev;
+    std::vector<void*> dev;                    // every device allocation of the handle (device_fixed, device_grown): freed with it
     bool have[5] = {false, false, false, false, false};      // Lxx, gx, hx, w, penalty resident
     bool assembled = false, factored = false;
     hipEvent_t ev[2] = {nullptr, nullptr};
@@ -82,8 +85,7 @@ struct calipso_hip_sparse_kkt {
     bool qp_attached = false;                                // q, b, hvec resident (qp_attach): what the data gradients ask for
     calipso::sparse_krylov::KrylovOptions kry;               // krylov_fallback, krylov_restart, krylov_max_cycles
     calipso::sparse_krylov::FallbackReport fallback;         // what calipso_hip_sparse_kkt_fallback_info reports
-    double* kry_ws = nullptr;                                // the fallback's workspace (sparse_krylov.hpp: Layout), reserved on the first fallback and kept
-    size_t kry_cap = 0;                                      // ... its doubles
+    calipso::sparse_kkt::Grown<double> kry_ws;               // the fallback's workspace (sparse_krylov.hpp: Layout), reserved on the first fallback and kept
     hipEvent_t kry_ev[2] = {nullptr, nullptr};
     calipso::sparse_kkt::ParameterPatterns par;              // the stored patterns and resident values of dR/dtheta (set_parameter_patterns)
 };
@@ -91,17 +93,60 @@ struct calipso_hip_sparse_kkt {
 namespace calipso {
 namespace sparse_kkt {
 
-// sparse_kkt.hip, for sparse_solve.hip
-int kkt_fail(calipso_hip_sparse_kkt* s, int rc, const std::string& text);                                   // sets last_error, returns rc
-int kkt_reserve(calipso_hip_sparse_kkt* s, double** out, size_t count);                                     // zeroed device doubles owned by the handle
-int kkt_device_pointer(calipso_hip_sparse_kkt* s, const void* p, const char* entry, const char* arg);       // the check of every _device entry
-int kkt_search_direction(calipso_hip_sparse_kkt* s, const double* res, double* step, double regularization[3], double info[4]);
-// ... and for sparse_differentiate.hip
-int kkt_values_missing(calipso_hip_sparse_kkt* s, const char* entry);                                       // Lxx, gx, hx, w, penalty resident, or the refusal
-int kkt_assemble_factorize(calipso_hip_sparse_kkt* s, const KktDev& d, double ep, double ed, int64_t inertia[3]);   // one assemble from `d` (the handle's, or with other slacks) + factorisation
-int kkt_sparse_failed(calipso_hip_sparse_kkt* s, int rc, const char* what);
+typedef calipso_hip_sparse_kkt KH;
+
+// sparse_kkt.hip, for the other units
+int fail(KH* s, int rc, const std::string& text);                                                           // sets last_error, returns rc
+int device_pointer(KH* s, const void* p, const char* entry, const char* arg);                               // the check of every _device entry
+int search_direction(KH* s, const double* res, double* step, double regularization[3], double info[4]);
+int values_missing(KH* s, const char* entry);                                                               // Lxx, gx, hx, w, penalty resident, or the refusal
+int assemble_factorize(KH* s, const KktDev& d, double ep, double ed, int64_t inertia[3]);                    // one assemble from `d` (the handle's, or with other slacks) + factorisation
+// OUT = M V (transposed: M' V) for k columns on the device: the "pre" launch, ONE k-column LDL^T solve, the "post" launch; `around`: two events recorded around them
+int map_columns(KH* s, const KktDev& d, bool transposed, int k, const double* V, double* rsym, double* dsym, double* OUT, const hipEvent_t* around = nullptr);
+// the first lines of an entry: the handle, its device and, by `need`, the solve state and what must be resident — or the refusal, under the entry's name
+enum Need { HANDLE, VALUES, STATE, STATE_READY, STATE_POINT };      // VALUES: values_missing; STATE: the solve state; _READY: + the problem's data; _POINT: + a point and the penalty
+int enter(KH* s, const char* entry, Need need);
+
+#define KK(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return fail(s, CALIPSO_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); } while (0)
+#define REFUSE(text) do { const std::string t__ = (text); if (!t__.empty()) return fail(s, CALIPSO_ERR_ARGUMENT, t__); } while (0)
+#define ENTER(need) do { const int rc__ = enter(s, entry, need); if (rc__ < 0) return rc__; } while (0)      // (`entry`: the entry's name)
+// in the one body of a host / _device pair of entries (`device`: which of the two)
+#define DEVPTR(p) do { if (device) { const int rc__ = device_pointer(s, (const void*)(p), entry, #p); if (rc__ < 0) return rc__; } } while (0)
+
+// ---- the handle's device memory.  Two ways to own it, both on the handle's list and freed with it, both zero-filled on the HANDLE'S stream: a fill on the null
+// stream would not be ordered with what follows, the stream being non-blocking ------------------------------------------------------------------------------------
+// a fixed allocation: made once
+template <typename T> int device_fixed(KH* s, T** out, size_t count) {
+    count = std::max<size_t>(count, 1);
+    KK(hipMalloc((void**)out, sizeof(T) * count));
+    s->dev.push_back(*out);
+    KK(hipMemsetAsync(*out, 0, sizeof(T) * count, s->st));
+    return CALIPSO_OK;
+}
+// ... and one that holds a host vector's entries
+template <typename T> int device_upload(KH* s, const std::vector<T>& h, const T** out) {
+    T* p = nullptr;
+    const int rc = device_fixed(s, &p, h.size());
+    if (rc < 0) return rc;
+    if (!h.empty()) KK(hipMemcpyAsync(p, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice, s->st));
+    KK(hipStreamSynchronize(s->st));                         // (the vector may be the caller's local)
+    *out = p;
+    return CALIPSO_OK;
+}
+// a grown buffer: larger only when asked for more than it has; nothing in flight reads the one that is freed
+template <typename T> int device_grown(KH* s, Grown<T>& b, size_t want) {
+    if (want <= b.cap) return CALIPSO_OK;
+    KK(hipStreamSynchronize(s->st));
+    if (b.p) { (void)hipFree(b.p); s->dev.erase(std::find(s->dev.begin(), s->dev.end(), (void*)b.p)); b = Grown<T>(); }
+    const int rc = device_fixed(s, &b.p, want);
+    if (rc >= 0) b.cap = want;
+    return rc;
+}
+
 // sparse_solve.hip, for sparse_kkt.hip
-void solve_state_release(calipso_hip_sparse_kkt* s);                                                        // (before the handle's device memory is freed)
+int solve_state(KH* s);                                                                                     // the resident vectors of solve!: made by the first entry that needs them
+int solve_ready(KH* s, const char* entry, bool point);                                                      // what a solve entry needs resident before it enqueues anything, or the refusal
+void solve_state_release(calipso_hip_sparse_kkt* s);
 int solve_set_option(calipso_hip_sparse_kkt* s, const char* name, double value);                            // 1 taken, 0 unknown, < 0 refused
 int parameters_enqueue(calipso_hip_sparse_kkt* s, const char* entry);                                       // enqueue: the evaluator's five parameter bits at the resident point into s->par (no host wait), or the refusal
 void diff_keep_slacks(calipso_hip_sparse_kkt* s);                                                           // enqueue: dslack <- the resident s, t (no host wait)

@@ -37,7 +37,6 @@ using calipso::Options;
 using calipso::Scalars;
 using namespace calipso::sparse_kkt;
 using namespace calipso::sparse_solve;
-typedef calipso_hip_sparse_kkt KH;
 static_assert(KT == THREADS, "the workspace layout counts workgroups of KT threads");
 
 namespace {
@@ -61,7 +60,8 @@ struct SolveDev {
 struct calipso::sparse_kkt::SolveState {
     Layout lay;
     SolveDev v{};
-    double *q = nullptr, *b = nullptr, *hvec = nullptr, *trace = nullptr;
+    double *q = nullptr, *b = nullptr, *hvec = nullptr;
+    Grown<double> trace;                          // trace_cap rows of N
     bool have_qp[3] = {false, false, false};
     i64 trace_cap = 0, trace_rows = 0, trace_total = 0;
     Filter filter;
@@ -70,12 +70,12 @@ struct calipso::sparse_kkt::SolveState {
     bool group_open = false;
     double vector_ms = 0.0;
     i64 waits = 0;
-    std::vector<void*> own;                       // device memory outside the handle's list (the trace)
     // the evaluated problem class: a user's evaluator instead of the QP's gathers
     calipso_device_sparse_eval_fn eval_fn = nullptr;
     void* eval_user = nullptr;
     i64 eval_np = 0;
-    double *theta = nullptr, *fobj = nullptr;     // np parameters; the objective at the solution and at the candidate
+    Grown<double> theta;                          // np parameters
+    double* fobj = nullptr;                       // the objective at the solution and at the candidate
     std::vector<int64_t> pattern[6];              // host copies of the patterns, 1-based as given to create: Lxx, gx, hx (colptr, rowval)
 };
 
@@ -501,24 +501,13 @@ __global__ __launch_bounds__(KT) void k_solve_outer_update(const KktDev d, const
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------------------------------------------
-#define KK(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return kkt_fail(s, CALIPSO_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); } while (0)
-#define REFUSE(text) do { const std::string t__ = (text); if (!t__.empty()) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, t__); } while (0)
-
 unsigned blocks_of(long long items) { return (unsigned)std::max<long long>((items + KT - 1) / KT, 1); }
 
-int reserve_ints(KH* s, const std::vector<int>& h, const int** out) {
-    int* p = nullptr;
-    KK(hipMalloc((void**)&p, sizeof(int) * std::max<size_t>(h.size(), 1)));
-    s->dev.push_back(p);
-    if (!h.empty()) KK(hipMemcpy(p, h.data(), sizeof(int) * h.size(), hipMemcpyHostToDevice));
-    *out = p;
-    return CALIPSO_OK;
-}
+}  // namespace
 
-// the resident vectors, the workspace and the published block: made once per handle, by the first entry that needs them
-int ensure_state(KH* s) {
+// the resident vectors, the workspace and the published block: made once per handle, by the first entry that needs them (on the handle's device: enter)
+int calipso::sparse_kkt::solve_state(KH* s) {
     if (s->solve) return CALIPSO_OK;
-    KK(hipSetDevice(s->device));
     SS* t = new SS();
     s->solve = t;                                            // (released with the handle, whatever happens below)
     const KktDev& d = s->d;
@@ -531,23 +520,24 @@ int ensure_state(KH* s) {
     v.n_small = (int)small.size(); v.n_wide = (int)wide.size(); v.grid = t->lay.grid;
     v.off_prologue = t->lay.off_prologue; v.off_candidate = t->lay.off_candidate; v.off_accept = t->lay.off_accept;
     int rc;
-    if ((rc = reserve_ints(s, small, &v.small_cones)) || (rc = reserve_ints(s, wide, &v.wide_cones))) return rc;
-    double *wsm = nullptr, *pub = nullptr;
-    if ((rc = kkt_reserve(s, &t->q, (size_t)d.nx)) || (rc = kkt_reserve(s, &t->b, (size_t)d.ne)) || (rc = kkt_reserve(s, &t->hvec, (size_t)d.nc)) ||
-        (rc = kkt_reserve(s, &v.cand, (size_t)d.N)) || (rc = kkt_reserve(s, &v.dual, (size_t)d.ne)) || (rc = kkt_reserve(s, &v.mgrad, (size_t)d.n)) ||
-        (rc = kkt_reserve(s, &v.bgrad, (size_t)d.nc)) || (rc = kkt_reserve(s, &v.cprod, (size_t)d.nc)) || (rc = kkt_reserve(s, &v.ctarget, (size_t)d.nc)) ||
-        (rc = kkt_reserve(s, &v.g, (size_t)d.ne)) || (rc = kkt_reserve(s, &v.h, (size_t)d.nc)) || (rc = kkt_reserve(s, &v.gcand, (size_t)d.ne)) ||
-        (rc = kkt_reserve(s, &v.hcand, (size_t)d.nc)) || (rc = kkt_reserve(s, &v.fx, (size_t)d.nx)) || (rc = kkt_reserve(s, &v.ws, (size_t)t->lay.doubles)) ||
-        (rc = kkt_reserve(s, &wsm, (size_t)(t->lay.mask_ints + 1) / 2)) || (rc = kkt_reserve(s, &pub, PUB_ALLOC_DOUBLES)) || (rc = kkt_reserve(s, &t->fobj, 2))) return rc;
+    if ((rc = device_upload(s, small, &v.small_cones)) || (rc = device_upload(s, wide, &v.wide_cones))) return rc;
+    if ((rc = device_fixed(s, &t->q, (size_t)d.nx)) || (rc = device_fixed(s, &t->b, (size_t)d.ne)) || (rc = device_fixed(s, &t->hvec, (size_t)d.nc)) ||
+        (rc = device_fixed(s, &v.cand, (size_t)d.N)) || (rc = device_fixed(s, &v.dual, (size_t)d.ne)) || (rc = device_fixed(s, &v.mgrad, (size_t)d.n)) ||
+        (rc = device_fixed(s, &v.bgrad, (size_t)d.nc)) || (rc = device_fixed(s, &v.cprod, (size_t)d.nc)) || (rc = device_fixed(s, &v.ctarget, (size_t)d.nc)) ||
+        (rc = device_fixed(s, &v.g, (size_t)d.ne)) || (rc = device_fixed(s, &v.h, (size_t)d.nc)) || (rc = device_fixed(s, &v.gcand, (size_t)d.ne)) ||
+        (rc = device_fixed(s, &v.hcand, (size_t)d.nc)) || (rc = device_fixed(s, &v.fx, (size_t)d.nx)) || (rc = device_fixed(s, &v.ws, (size_t)t->lay.doubles)) ||
+        (rc = device_fixed(s, &v.wsm, (size_t)t->lay.mask_ints)) || (rc = device_fixed(s, &v.pub, PUB_ALLOC_DOUBLES)) || (rc = device_fixed(s, &t->fobj, 2))) return rc;
     v.fobj = t->fobj;
     v.q = t->q; v.b = t->b; v.hvec = t->hvec; v.w = s->w; v.res = s->res; v.step = s->step;
-    v.wsm = reinterpret_cast<unsigned*>(wsm); v.pub = pub; v.pub_masks = reinterpret_cast<unsigned*>(pub + PUB_DOUBLES);
+    v.pub_masks = reinterpret_cast<unsigned*>(v.pub + PUB_DOUBLES);      // (the mask words lie inside the published block: it is read back in one copy)
     v.objective_constant = 0.0;
     KK(hipHostMalloc((void**)&t->hpub, sizeof(double) * PUB_ALLOC_DOUBLES));
     std::memset(t->hpub, 0, sizeof(double) * PUB_ALLOC_DOUBLES);
     KK(hipEventCreate(&t->ev[0])); KK(hipEventCreate(&t->ev[1]));
     return CALIPSO_OK;
 }
+
+namespace {
 
 // ---- enqueues: each records the beginning of a timed group, the read-back closes it -----------------------------------------------------------------------------
 void open_group(KH* s) { SS* t = s->solve; if (!t->group_open) { (void)hipEventRecord(t->ev[0], s->st); t->group_open = true; } }
@@ -565,18 +555,18 @@ int enqueue_evaluator(KH* s, int which, uint32_t flags) {
     out.hx_colptr = t->pattern[4].data(); out.hx_rowval = t->pattern[5].data();
     out.nx = d.nx; out.np = t->eval_np; out.ne = d.ne; out.nc = d.nc; out.nnz_Lxx = d.nnzL; out.nnz_gx = d.nnzg; out.nnz_hx = d.nnzh;
     const ParameterPatterns& pp = s->par;                    // NULL / 0 without set_parameter_patterns
-    out.lagrangian_gradient_parameters = pp.set ? pp.val[0] : nullptr; out.equality_jacobian_parameters = pp.set ? pp.val[1] : nullptr;
-    out.cone_jacobian_parameters = pp.set ? pp.val[2] : nullptr;
+    out.lagrangian_gradient_parameters = pp.set ? pp.val[0].p : nullptr; out.equality_jacobian_parameters = pp.set ? pp.val[1].p : nullptr;
+    out.cone_jacobian_parameters = pp.set ? pp.val[2].p : nullptr;
     out.Lp_colptr = pp.set ? pp.host[0].data() : nullptr; out.Lp_rowval = pp.set ? pp.host[1].data() : nullptr;
     out.gp_colptr = pp.set ? pp.host[2].data() : nullptr; out.gp_rowval = pp.set ? pp.host[3].data() : nullptr;
     out.hp_colptr = pp.set ? pp.host[4].data() : nullptr; out.hp_rowval = pp.set ? pp.host[5].data() : nullptr;
     out.nnz_Lp = pp.set ? pp.nnz[0] : 0; out.nnz_gp = pp.set ? pp.nnz[1] : 0; out.nnz_hp = pp.set ? pp.nnz[2] : 0;
-    const int32_t r = t->eval_fn(t->eval_user, flags, which ? v.cand : s->w, s->w + d.o_y, s->w + d.o_z, t->theta, &out, (void*)s->st);
+    const int32_t r = t->eval_fn(t->eval_user, flags, which ? v.cand : s->w, s->w + d.o_y, s->w + d.o_z, t->theta.p, &out, (void*)s->st);
     for (int i = 0; i < 3; ++i) if (flags & EVAL_MATRIX_BITS[i]) { s->have[i] = r == 0; s->assembled = false; s->factored = false; }
     if (r != 0) {
         (void)hipStreamSynchronize(s->st); (void)hipGetLastError();
         t->group_open = false;
-        return kkt_fail(s, r == 1 ? CALIPSO_ERR_ARGUMENT : CALIPSO_ERR_HIP, "the device evaluator returned " + std::to_string(r) + " (flags " + std::to_string(flags) + ", " +
+        return fail(s, r == 1 ? CALIPSO_ERR_ARGUMENT : CALIPSO_ERR_HIP, "the device evaluator returned " + std::to_string(r) + " (flags " + std::to_string(flags) + ", " +
                                                                                 (which ? "candidate" : "solution") + ")");
     }
     return CALIPSO_OK;
@@ -649,30 +639,30 @@ int read_published(KH* s) {
 }
 const int* host_masks(const SS* t) { return reinterpret_cast<const int*>(t->hpub + PUB_DOUBLES); }
 
+}  // namespace
+
 // what an entry needs resident before it enqueues anything
-int ready(KH* s, const char* entry, bool point) {
+int calipso::sparse_kkt::solve_ready(KH* s, const char* entry, bool point) {
     static const char* const names[3] = {"Lxx", "gx", "hx"};
     const size_t need[3] = {(size_t)s->d.nnzL, (size_t)s->d.nnzg, (size_t)s->d.nnzh};
     SS* t = s->solve;
     const bool evaluated = t->eval_fn != nullptr;              // (an evaluator writes the three matrices itself, and stands where q, b, hvec stand for the QP)
-    for (int i = 0; i < 3 && !evaluated; ++i) if (need[i] && !s->have[i]) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": no " + names[i] + " resident (calipso_hip_sparse_kkt_set_values first)");
+    for (int i = 0; i < 3 && !evaluated; ++i) if (need[i] && !s->have[i]) return fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": no " + names[i] + " resident (calipso_hip_sparse_kkt_set_values first)");
     static const char* const qp[3] = {"q", "b", "hvec"};
     const size_t len[3] = {(size_t)s->d.nx, (size_t)s->d.ne, (size_t)s->d.nc};
-    for (int i = 0; i < 3 && !evaluated; ++i) if (len[i] && !t->have_qp[i]) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": no " + qp[i] + " resident (calipso_hip_sparse_kkt_qp_attach first)");
-    if (point && !s->have[3]) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": no point resident (calipso_hip_sparse_kkt_initialize, or set_values with w, first)");
-    if (point && s->d.ne && !s->have[4]) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": no penalty resident");
+    for (int i = 0; i < 3 && !evaluated; ++i) if (len[i] && !t->have_qp[i]) return fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": no " + qp[i] + " resident (calipso_hip_sparse_kkt_qp_attach first)");
+    if (point && !s->have[3]) return fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": no point resident (calipso_hip_sparse_kkt_initialize, or set_values with w, first)");
+    if (point && s->d.ne && !s->have[4]) return fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": no penalty resident");
     return CALIPSO_OK;
 }
-#define ENTRY(name, point)                                                                                             \
-    static const char* const entry = name;                                                                             \
-    if (!s) return CALIPSO_ERR_ARGUMENT;                                                                               \
-    KK(hipSetDevice(s->device));                                                                                       \
-    { const int rc__ = ensure_state(s); if (rc__ < 0) return rc__; }                                                   \
-    { const int rc__ = ready(s, entry, point); if (rc__ < 0) return rc__; }                                           \
-    SS* t = s->solve; (void)t; (void)entry
 
-int qp_attach(KH* s, const double* q, const double* b, const double* hvec, double objective_constant, hipMemcpyKind kind) {
+namespace {
+
+int qp_attach(KH* s, const char* entry, const double* q, const double* b, const double* hvec, double objective_constant, bool device) {
+    ENTER(STATE);
+    DEVPTR(q); DEVPTR(b); DEVPTR(hvec);
     SS* t = s->solve;
+    const hipMemcpyKind kind = device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     const double* src[3] = {q, b, hvec};
     double* dst[3] = {t->q, t->b, t->hvec};
     const size_t count[3] = {(size_t)s->d.nx, (size_t)s->d.ne, (size_t)s->d.nc};
@@ -685,9 +675,12 @@ int qp_attach(KH* s, const double* q, const double* b, const double* hvec, doubl
     for (int i = 0; i < 3; ++i) if (count[i] && !t->have_qp[i]) s->qp_attached = false;
     return CALIPSO_OK;
 }
-int initialize(KH* s, const double* x0, hipMemcpyKind kind) {
+int initialize(KH* s, const char* entry, const double* x0, bool device) {
+    ENTER(STATE_READY);
+    if (!x0 && s->d.nx) return fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": x0 is NULL");
+    DEVPTR(x0);
     SS* t = s->solve;
-    if (s->d.nx) KK(hipMemcpyAsync(s->w, x0, sizeof(double) * (size_t)s->d.nx, kind, s->st));
+    if (s->d.nx) KK(hipMemcpyAsync(s->w, x0, sizeof(double) * (size_t)s->d.nx, device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->st));
     { const int rc = enqueue_init(s); if (rc < 0) return rc; }
     KK(hipStreamSynchronize(s->st));
     KK(hipGetLastError());
@@ -695,6 +688,15 @@ int initialize(KH* s, const double* x0, hipMemcpyKind kind) {
     s->have[3] = true;
     s->assembled = false; s->factored = false;               // K and its factor belong to the point before
     s->slacks_kept = false;                                  // the differentiate slacks are the new point's own
+    return CALIPSO_OK;
+}
+int set_parameters(KH* s, const char* entry, const double* theta, bool device) {
+    ENTER(STATE);
+    SS* t = s->solve;
+    REFUSE(check_set_parameters(entry, t->eval_fn != nullptr, t->eval_np, theta));
+    if (t->eval_np) DEVPTR(theta);
+    if (t->eval_np) KK(hipMemcpyAsync(t->theta.p, theta, sizeof(double) * (size_t)t->eval_np, device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->st));
+    KK(hipStreamSynchronize(s->st));
     return CALIPSO_OK;
 }
 double* resident(KH* s, int vec) {
@@ -748,7 +750,7 @@ int solve(KH* s, double info[16]) {
             // this step's prologue wrote, at this point and its y, z.  The cone Jacobians are formed inside the kernels of sparse_kkt.hip
             double reg[3] = {sc.ep, sc.ep_last, sc.ed}, sdinfo[4] = {0, 0, 0, 0};
             diff_keep_slacks(s);                                                              // what differentiate! forms the cone blocks at: no host wait
-            rc = kkt_search_direction(s, s->res, s->step, reg, sdinfo);                       // :187
+            rc = search_direction(s, s->res, s->step, reg, sdinfo);                       // :187
             nfact += (i64)sdinfo[0]; max_rounds = std::max(max_rounds, (i64)sdinfo[1]);
             for (int k = 0; k < 5; ++k) sd_ms += s->ms[k];
             sd_ms += s->fallback.v[calipso::sparse_krylov::FI_DEVICE_MS];                     // (0 where no fallback ran: its events are its own, not the eight slots')
@@ -759,7 +761,7 @@ int solve(KH* s, double info[16]) {
                 // (converged or not, but finite) is taken; else there is no such fallback on this handle
                 if (s->fallback.step_taken) s->fallback.count_in_solve();
                 else if (!s->continue_after_refinement_failure) {
-                    kkt_fail(s, -100 - CALIPSO_WARN_REFINEMENT, "calipso_hip_sparse_kkt_solve: iterative refinement failed (iterative_refinement.jl:50) and this handle has no `H \\ residual` fallback; the point is the last accepted iterate");
+                    fail(s, -100 - CALIPSO_WARN_REFINEMENT, "calipso_hip_sparse_kkt_solve: iterative refinement failed (iterative_refinement.jl:50) and this handle has no `H \\ residual` fallback; the point is the last accepted iterate");
                     return leave(-100 - CALIPSO_WARN_REFINEMENT);
                 }
             }
@@ -769,11 +771,11 @@ int solve(KH* s, double info[16]) {
             if ((rc = read_published(s)) < 0) return leave(rc);
             double step_size = 1.0, step_size_t = 1.0;
             if (!calipso::cone_step_sizes(host_masks(t), host_masks(t) + calipso::CONE_MASK_WORDS, o, &step_size, &step_size_t)) {
-                kkt_fail(s, CALIPSO_ERR_CONE_SEARCH, "cone search failure (solve.jl:210,220)");
+                fail(s, CALIPSO_ERR_CONE_SEARCH, "cone search failure (solve.jl:210,220)");
                 return leave(CALIPSO_ERR_CONE_SEARCH);
             }
             if (step_size != pub[PUB_STEP_S] || step_size_t != pub[PUB_STEP_T])
-                return leave(kkt_fail(s, CALIPSO_ERR_HIP, "calipso_hip_sparse_kkt_solve: the step sizes formed on the device are not those of cone_step_sizes()"));
+                return leave(fail(s, CALIPSO_ERR_HIP, "calipso_hip_sparse_kkt_solve: the step sizes formed on the device are not those of cone_step_sizes()"));
             double Mh = pub[PUB_CAND_MERIT], thetah = pub[PUB_CAND_THETA];
             const double dd = pub[PUB_DD];
             i64 residual_iteration = 0;
@@ -790,7 +792,7 @@ int solve(KH* s, double info[16]) {
                 t->filter.augment((1.0 - o.violation_tolerance) * theta, M - o.merit_tolerance * theta);
             if ((rc = enqueue_accept(s, step_size, false)) < 0) return leave(rc);             // :309-333
             if (t->trace_rows < t->trace_cap) {
-                KK(hipMemcpyAsync(t->trace + (size_t)t->trace_rows * (size_t)d.N, s->w, sizeof(double) * (size_t)d.N, hipMemcpyDeviceToDevice, s->st));
+                KK(hipMemcpyAsync(t->trace.p + (size_t)t->trace_rows * (size_t)d.N, s->w, sizeof(double) * (size_t)d.N, hipMemcpyDeviceToDevice, s->st));
                 t->trace_rows += 1;
             }
             t->trace_total += 1;
@@ -826,8 +828,8 @@ void diff_keep_slacks(KH* s) {
 
 int parameters_enqueue(KH* s, const char* entry) {
     if (!s->par.set || !s->solve || !s->solve->eval_fn)
-        return kkt_fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": no parameter patterns set (calipso_hip_sparse_kkt_set_parameter_patterns first)");
-    if (!s->have[3]) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": no point resident (calipso_hip_sparse_kkt_initialize, or set_values with w, first)");
+        return fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": no parameter patterns set (calipso_hip_sparse_kkt_set_parameter_patterns first)");
+    if (!s->have[3]) return fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": no point resident (calipso_hip_sparse_kkt_initialize, or set_values with w, first)");
     SS* t = s->solve;
     const bool open = t->group_open;                         // (the call belongs to no timed group of solve!)
     const int rc = enqueue_evaluator(s, 0, EVAL_PARAMETER_BITS);
@@ -838,7 +840,6 @@ int parameters_enqueue(KH* s, const char* entry) {
 void solve_state_release(KH* s) {
     SS* t = s->solve;
     if (!t) return;
-    for (void* p : t->own) if (p) (void)hipFree(p);
     if (t->hpub) (void)hipHostFree(t->hpub);
     for (hipEvent_t e : t->ev) if (e) (void)hipEventDestroy(e);
     delete t;
@@ -854,11 +855,11 @@ int solve_set_option(KH* s, const char* name, double value) {
     if (n == "continue_after_refinement_failure") { s->continue_after_refinement_failure = value != 0.0; return 1; }
     if (n == "fraction_to_boundary") { s->sc.tau = value; return 1; }
     if (n == "penalty") {
-        if (hipSetDevice(s->device) != hipSuccess) return kkt_fail(s, CALIPSO_ERR_HIP, "hipSetDevice");
-        { const int rc = ensure_state(s); if (rc < 0) return rc; }
+        if (hipSetDevice(s->device) != hipSuccess) return fail(s, CALIPSO_ERR_HIP, "hipSetDevice");
+        { const int rc = solve_state(s); if (rc < 0) return rc; }
         s->sc.rho = value;
         enqueue_penalty(s);
-        if (hipStreamSynchronize(s->st) != hipSuccess) return kkt_fail(s, CALIPSO_ERR_HIP, "hipStreamSynchronize");
+        if (hipStreamSynchronize(s->st) != hipSuccess) return fail(s, CALIPSO_ERR_HIP, "hipStreamSynchronize");
         s->solve->group_open = false;
         return 1;
     }
@@ -871,46 +872,29 @@ int solve_set_option(KH* s, const char* name, double value) {
 extern "C" {
 
 int32_t calipso_hip_sparse_kkt_qp_attach(calipso_hip_sparse_kkt* s, const double* q, const double* b, const double* hvec, double objective_constant) {
-    if (!s) return CALIPSO_ERR_ARGUMENT;
-    KK(hipSetDevice(s->device));
-    { const int rc = ensure_state(s); if (rc < 0) return rc; }
-    return qp_attach(s, q, b, hvec, objective_constant, hipMemcpyHostToDevice);
+    return qp_attach(s, "calipso_hip_sparse_kkt_qp_attach", q, b, hvec, objective_constant, false);
 }
 int32_t calipso_hip_sparse_kkt_qp_attach_device(calipso_hip_sparse_kkt* s, const double* q, const double* b, const double* hvec, double objective_constant) {
-    if (!s) return CALIPSO_ERR_ARGUMENT;
-    KK(hipSetDevice(s->device));
-    { const int rc = ensure_state(s); if (rc < 0) return rc; }
-    static const char* const entry = "calipso_hip_sparse_kkt_qp_attach_device";
-    const void* ptrs[3] = {q, b, hvec}; const char* const names[3] = {"q", "b", "hvec"};
-    for (int i = 0; i < 3; ++i) { const int rc = kkt_device_pointer(s, ptrs[i], entry, names[i]); if (rc < 0) return rc; }
-    return qp_attach(s, q, b, hvec, objective_constant, hipMemcpyDeviceToDevice);
+    return qp_attach(s, "calipso_hip_sparse_kkt_qp_attach_device", q, b, hvec, objective_constant, true);
 }
 
-int32_t calipso_hip_sparse_kkt_initialize(calipso_hip_sparse_kkt* s, const double* x0) {
-    ENTRY("calipso_hip_sparse_kkt_initialize", false);
-    if (!x0 && s->d.nx) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_sparse_kkt_initialize: x0 is NULL");
-    return initialize(s, x0, hipMemcpyHostToDevice);
-}
-int32_t calipso_hip_sparse_kkt_initialize_device(calipso_hip_sparse_kkt* s, const double* x0) {
-    ENTRY("calipso_hip_sparse_kkt_initialize_device", false);
-    if (!x0 && s->d.nx) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_sparse_kkt_initialize_device: x0 is NULL");
-    { const int rc = kkt_device_pointer(s, x0, entry, "x0"); if (rc < 0) return rc; }
-    return initialize(s, x0, hipMemcpyDeviceToDevice);
-}
+int32_t calipso_hip_sparse_kkt_initialize(calipso_hip_sparse_kkt* s, const double* x0) { return initialize(s, "calipso_hip_sparse_kkt_initialize", x0, false); }
+int32_t calipso_hip_sparse_kkt_initialize_device(calipso_hip_sparse_kkt* s, const double* x0) { return initialize(s, "calipso_hip_sparse_kkt_initialize_device", x0, true); }
 
 int32_t calipso_hip_sparse_kkt_solve(calipso_hip_sparse_kkt* s, double info[16]) {
-    if (!s) return CALIPSO_ERR_ARGUMENT;
-    KK(hipSetDevice(s->device));
-    { const int rc = ensure_state(s); if (rc < 0) return rc; }
+    static const char* const entry = "calipso_hip_sparse_kkt_solve";
+    ENTER(STATE);
     if (s->d.ne && !s->have[4]) s->have[4] = true;           // (solve! sets the penalty itself: initialize.jl:44-48)
-    { const int rc = ready(s, "calipso_hip_sparse_kkt_solve", true); if (rc < 0) return rc; }
+    { const int rc = solve_ready(s, entry, true); if (rc < 0) return rc; }
     (void)hipGetLastError();
     return solve(s, info);
 }
 
 int32_t calipso_hip_sparse_kkt_step_prologue(calipso_hip_sparse_kkt* s, int32_t which, double scalars[16]) {
-    ENTRY("calipso_hip_sparse_kkt_step_prologue", true);
-    if (which != 0) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_sparse_kkt_step_prologue: which: the prologue is taken at the solution (0); calipso_hip_sparse_kkt_candidate evaluates a candidate");
+    static const char* const entry = "calipso_hip_sparse_kkt_step_prologue";
+    ENTER(STATE_POINT);
+    SS* t = s->solve;
+    if (which != 0) return fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_sparse_kkt_step_prologue: which: the prologue is taken at the solution (0); calipso_hip_sparse_kkt_candidate evaluates a candidate");
     { const int rc = enqueue_prologue(s); if (rc < 0) return rc; }
     { const int rc = read_published(s); if (rc < 0) return rc; }
     if (scalars) {
@@ -924,16 +908,20 @@ int32_t calipso_hip_sparse_kkt_step_prologue(calipso_hip_sparse_kkt* s, int32_t 
 }
 
 int32_t calipso_hip_sparse_kkt_cone_search(calipso_hip_sparse_kkt* s, double a[2]) {
-    ENTRY("calipso_hip_sparse_kkt_cone_search", true);
-    if (!a) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_sparse_kkt_cone_search: a is NULL");
+    static const char* const entry = "calipso_hip_sparse_kkt_cone_search";
+    ENTER(STATE_POINT);
+    SS* t = s->solve;
+    if (!a) return fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_sparse_kkt_cone_search: a is NULL");
     enqueue_cone_masks(s);
     { const int rc = read_published(s); if (rc < 0) return rc; }
-    if (!calipso::cone_step_sizes(host_masks(t), host_masks(t) + calipso::CONE_MASK_WORDS, s->opt, &a[0], &a[1])) return kkt_fail(s, CALIPSO_ERR_CONE_SEARCH, "cone search failure (solve.jl:210,220)");
+    if (!calipso::cone_step_sizes(host_masks(t), host_masks(t) + calipso::CONE_MASK_WORDS, s->opt, &a[0], &a[1])) return fail(s, CALIPSO_ERR_CONE_SEARCH, "cone search failure (solve.jl:210,220)");
     return CALIPSO_OK;
 }
 
 int32_t calipso_hip_sparse_kkt_candidate(calipso_hip_sparse_kkt* s, double a_s, double a_t, double out[3]) {
-    ENTRY("calipso_hip_sparse_kkt_candidate", true);
+    static const char* const entry = "calipso_hip_sparse_kkt_candidate";
+    ENTER(STATE_POINT);
+    SS* t = s->solve;
     REFUSE(check_step_sizes(entry, a_s, a_t));
     { const int rc = enqueue_candidate(s, false, a_s, a_t, true); if (rc < 0) return rc; }
     { const int rc = read_published(s); if (rc < 0) return rc; }
@@ -942,7 +930,9 @@ int32_t calipso_hip_sparse_kkt_candidate(calipso_hip_sparse_kkt* s, double a_s, 
 }
 
 int32_t calipso_hip_sparse_kkt_accept(calipso_hip_sparse_kkt* s, double a, double violations[2]) {
-    ENTRY("calipso_hip_sparse_kkt_accept", true);
+    static const char* const entry = "calipso_hip_sparse_kkt_accept";
+    ENTER(STATE_POINT);
+    SS* t = s->solve;
     REFUSE(check_step_sizes(entry, a, 1.0));
     { const int rc = enqueue_accept(s, a, false); if (rc < 0) return rc; }
     { const int rc = read_published(s); if (rc < 0) return rc; }
@@ -952,7 +942,9 @@ int32_t calipso_hip_sparse_kkt_accept(calipso_hip_sparse_kkt* s, double a, doubl
 }
 
 int32_t calipso_hip_sparse_kkt_outer_update(calipso_hip_sparse_kkt* s) {
-    ENTRY("calipso_hip_sparse_kkt_outer_update", true);
+    static const char* const entry = "calipso_hip_sparse_kkt_outer_update";
+    ENTER(STATE_POINT);
+    SS* t = s->solve;
     double rho = 0.0;
     KK(hipMemcpyAsync(&rho, s->rho, sizeof(double), hipMemcpyDeviceToHost, s->st));
     KK(hipStreamSynchronize(s->st));
@@ -963,20 +955,19 @@ int32_t calipso_hip_sparse_kkt_outer_update(calipso_hip_sparse_kkt* s) {
 }
 
 int32_t calipso_hip_sparse_kkt_get(calipso_hip_sparse_kkt* s, const char* name, double* out, int64_t len) {
-    if (!s) return CALIPSO_ERR_ARGUMENT;
-    KK(hipSetDevice(s->device));
-    { const int rc = ensure_state(s); if (rc < 0) return rc; }
+    static const char* const entry = "calipso_hip_sparse_kkt_get";
+    ENTER(STATE);
     const i64 nnz[3] = {s->d.nnzL, s->d.nnzg, s->d.nnzh};
     if (const int m = calipso::sparse_parameters::array_by_name(name); m >= 0) {      // the three resident arrays of dR/dtheta on their stored patterns
-        const std::string what = std::string("calipso_hip_sparse_kkt_get: ") + name;
-        if (!s->par.set) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, what + ": no parameter patterns set (calipso_hip_sparse_kkt_set_parameter_patterns first)");
-        if (len != s->par.nnz[m]) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, what + ": len: the stored pattern has " + std::to_string(s->par.nnz[m]) + " non-zeros, not " + std::to_string(len));
-        if (!out && len > 0) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, what + ": the array is NULL");
-        if (len) KK(hipMemcpyAsync(out, s->par.val[m], sizeof(double) * (size_t)len, hipMemcpyDeviceToHost, s->st));
+        const std::string what = std::string(entry) + ": " + name;
+        if (!s->par.set) return fail(s, CALIPSO_ERR_ARGUMENT, what + ": no parameter patterns set (calipso_hip_sparse_kkt_set_parameter_patterns first)");
+        if (len != s->par.nnz[m]) return fail(s, CALIPSO_ERR_ARGUMENT, what + ": len: the stored pattern has " + std::to_string(s->par.nnz[m]) + " non-zeros, not " + std::to_string(len));
+        if (!out && len > 0) return fail(s, CALIPSO_ERR_ARGUMENT, what + ": the array is NULL");
+        if (len) KK(hipMemcpyAsync(out, s->par.val[m].p, sizeof(double) * (size_t)len, hipMemcpyDeviceToHost, s->st));
         KK(hipStreamSynchronize(s->st));
         return CALIPSO_OK;
     }
-    REFUSE(check_named_vector("calipso_hip_sparse_kkt_get", name, out, len, s->d.nx, s->d.ne, s->d.nc, false, nnz));
+    REFUSE(check_named_vector(entry, name, out, len, s->d.nx, s->d.ne, s->d.nc, false, nnz));
     if (vector_by_name(name) == V_DIFFERENTIATE_SLACKS) {
         const size_t nc = (size_t)s->d.nc;
         const double* from[2] = {s->slacks_kept ? s->dslack : s->w + s->d.o_s, s->slacks_kept ? s->dslack + nc : s->w + s->d.o_t};
@@ -986,10 +977,9 @@ int32_t calipso_hip_sparse_kkt_get(calipso_hip_sparse_kkt* s, const char* name, 
     return CALIPSO_OK;
 }
 int32_t calipso_hip_sparse_kkt_set(calipso_hip_sparse_kkt* s, const char* name, const double* in, int64_t len) {
-    if (!s) return CALIPSO_ERR_ARGUMENT;
-    KK(hipSetDevice(s->device));
-    { const int rc = ensure_state(s); if (rc < 0) return rc; }
-    REFUSE(check_named_vector("calipso_hip_sparse_kkt_set", name, in, len, s->d.nx, s->d.ne, s->d.nc, true));
+    static const char* const entry = "calipso_hip_sparse_kkt_set";
+    ENTER(STATE);
+    REFUSE(check_named_vector(entry, name, in, len, s->d.nx, s->d.ne, s->d.nc, true));
     const int vec = vector_by_name(name);
     if (len) KK(hipMemcpyAsync(resident(s, vec), in, sizeof(double) * (size_t)len, hipMemcpyHostToDevice, s->st));
     KK(hipStreamSynchronize(s->st));
@@ -997,7 +987,7 @@ int32_t calipso_hip_sparse_kkt_set(calipso_hip_sparse_kkt* s, const char* name, 
     return CALIPSO_OK;
 }
 int32_t calipso_hip_sparse_kkt_solution_device(calipso_hip_sparse_kkt* s, double** p) {
-    if (!s || !p) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_sparse_kkt_solution_device: p is NULL");
+    if (!s || !p) return fail(s, CALIPSO_ERR_ARGUMENT, "calipso_hip_sparse_kkt_solution_device: p is NULL");
     KK(hipSetDevice(s->device));
     KK(hipStreamSynchronize(s->st));
     *p = s->w;
@@ -1006,18 +996,18 @@ int32_t calipso_hip_sparse_kkt_solution_device(calipso_hip_sparse_kkt* s, double
 
 // ---- the evaluated problem class ------------------------------------------------------------------------------------------------------------------------------------
 int32_t calipso_hip_sparse_kkt_set_evaluator(calipso_hip_sparse_kkt* s, calipso_device_sparse_eval_fn fn, void* user, int64_t np) {
-    if (!s) return CALIPSO_ERR_ARGUMENT;
-    KK(hipSetDevice(s->device));
-    { const int rc = ensure_state(s); if (rc < 0) return rc; }
+    static const char* const entry = "calipso_hip_sparse_kkt_set_evaluator";
+    ENTER(STATE);
     REFUSE(check_set_evaluator(np));
     SS* t = s->solve;
     KK(hipStreamSynchronize(s->st));                         // (nothing of the evaluator before is in flight when its user object changes hands)
     s->par.set = false;                                      // the parameter patterns belong to the evaluator they were set for
     if (!fn) { t->eval_fn = nullptr; t->eval_user = nullptr; return CALIPSO_OK; }
-    if (np != t->eval_np || !t->theta) {
-        double* theta = nullptr;
-        { const int rc = kkt_reserve(s, &theta, (size_t)std::max<i64>(np, 1)); if (rc < 0) return rc; }      // zeros
-        t->theta = theta; t->eval_np = np;
+    if (np != t->eval_np || !t->theta.p) {                     // another count of parameters: they start as zeros
+        const size_t count = (size_t)std::max<i64>(np, 1);
+        if (const int rc = device_grown(s, t->theta, count); rc < 0) return rc;
+        KK(hipMemsetAsync(t->theta.p, 0, sizeof(double) * count, s->st));
+        t->eval_np = np;
     }
     if (t->pattern[0].empty()) {                              // the host copies an evaluator builds its address table from: 1-based, as create took them
         const ColView* cols[3] = {&s->an.Lxx_cols, &s->an.gx_cols, &s->an.hx_cols};
@@ -1031,37 +1021,15 @@ int32_t calipso_hip_sparse_kkt_set_evaluator(calipso_hip_sparse_kkt* s, calipso_
     s->qp_attached = false;
     return CALIPSO_OK;
 }
-static int set_parameters(calipso_hip_sparse_kkt* s, const double* theta, hipMemcpyKind kind) {
-    SS* t = s->solve;
-    if (t->eval_np) KK(hipMemcpyAsync(t->theta, theta, sizeof(double) * (size_t)t->eval_np, kind, s->st));
-    KK(hipStreamSynchronize(s->st));
-    return CALIPSO_OK;
-}
-int32_t calipso_hip_sparse_kkt_set_parameters(calipso_hip_sparse_kkt* s, const double* theta) {
-    if (!s) return CALIPSO_ERR_ARGUMENT;
-    KK(hipSetDevice(s->device));
-    { const int rc = ensure_state(s); if (rc < 0) return rc; }
-    REFUSE(check_set_parameters("calipso_hip_sparse_kkt_set_parameters", s->solve->eval_fn != nullptr, s->solve->eval_np, theta));
-    return set_parameters(s, theta, hipMemcpyHostToDevice);
-}
-int32_t calipso_hip_sparse_kkt_set_parameters_device(calipso_hip_sparse_kkt* s, const double* theta) {
-    if (!s) return CALIPSO_ERR_ARGUMENT;
-    KK(hipSetDevice(s->device));
-    { const int rc = ensure_state(s); if (rc < 0) return rc; }
-    static const char* const entry = "calipso_hip_sparse_kkt_set_parameters_device";
-    REFUSE(check_set_parameters(entry, s->solve->eval_fn != nullptr, s->solve->eval_np, theta));
-    if (s->solve->eval_np) { const int rc = kkt_device_pointer(s, theta, entry, "theta"); if (rc < 0) return rc; }
-    return set_parameters(s, theta, hipMemcpyDeviceToDevice);
-}
+int32_t calipso_hip_sparse_kkt_set_parameters(calipso_hip_sparse_kkt* s, const double* theta) { return set_parameters(s, "calipso_hip_sparse_kkt_set_parameters", theta, false); }
+int32_t calipso_hip_sparse_kkt_set_parameters_device(calipso_hip_sparse_kkt* s, const double* theta) { return set_parameters(s, "calipso_hip_sparse_kkt_set_parameters_device", theta, true); }
 int32_t calipso_hip_sparse_kkt_evaluate(calipso_hip_sparse_kkt* s, int32_t which, uint32_t flags) {
-    if (!s) return CALIPSO_ERR_ARGUMENT;
-    KK(hipSetDevice(s->device));
-    { const int rc = ensure_state(s); if (rc < 0) return rc; }
     static const char* const entry = "calipso_hip_sparse_kkt_evaluate";
+    ENTER(STATE);
     SS* t = s->solve;
-    if (!t->eval_fn) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": no evaluator attached (calipso_hip_sparse_kkt_set_evaluator first)");
+    if (!t->eval_fn) return fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": no evaluator attached (calipso_hip_sparse_kkt_set_evaluator first)");
     REFUSE(check_evaluate(which, flags));
-    if (!s->have[3]) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": no point resident (calipso_hip_sparse_kkt_initialize, or set_values with w, first)");
+    if (!s->have[3]) return fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": no point resident (calipso_hip_sparse_kkt_initialize, or set_values with w, first)");
     (void)hipGetLastError();
     { const int rc = enqueue_evaluator(s, which, flags); if (rc < 0) return rc; }
     KK(hipStreamSynchronize(s->st));
@@ -1073,12 +1041,10 @@ int32_t calipso_hip_sparse_kkt_evaluate(calipso_hip_sparse_kkt* s, int32_t which
 // ---- the parameter Jacobians on their stored patterns (sparse_parameters.hpp) ----------------------------------------------------------------------------------------
 int32_t calipso_hip_sparse_kkt_set_parameter_patterns(calipso_hip_sparse_kkt* s, const int64_t* Lp_colptr, const int64_t* Lp_rowval, const int64_t* gp_colptr,
                                                       const int64_t* gp_rowval, const int64_t* hp_colptr, const int64_t* hp_rowval) {
-    if (!s) return CALIPSO_ERR_ARGUMENT;
-    KK(hipSetDevice(s->device));
-    { const int rc = ensure_state(s); if (rc < 0) return rc; }
     static const char* const entry = "calipso_hip_sparse_kkt_set_parameter_patterns";
+    ENTER(STATE);
     SS* t = s->solve;
-    if (!t->eval_fn) return kkt_fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": no evaluator attached (calipso_hip_sparse_kkt_set_evaluator first)");
+    if (!t->eval_fn) return fail(s, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": no evaluator attached (calipso_hip_sparse_kkt_set_evaluator first)");
     namespace sp = calipso::sparse_parameters;
     const sp::Patterns in{{Lp_colptr, gp_colptr, hp_colptr}, {Lp_rowval, gp_rowval, hp_rowval}};
     const int64_t rows[3] = {s->d.nx, s->d.ne, s->d.nc};
@@ -1102,54 +1068,36 @@ int32_t calipso_hip_sparse_kkt_set_parameter_patterns(calipso_hip_sparse_kkt* s,
     }
     host[6].assign(split.long_columns.begin(), split.long_columns.end());
     // the arrays of an earlier call are taken again where they are large enough: setting patterns repeatedly does not grow the handle
-    for (int i = 0; i < 7; ++i) {
-        const size_t want = std::max<size_t>(host[i].size(), 1);
-        if (want <= pp.int_cap[i]) continue;
-        double* p = nullptr;
-        { const int rc = kkt_reserve(s, &p, (want + 1) / 2); if (rc < 0) return rc; }
-        pp.ints[i] = reinterpret_cast<int*>(p); pp.int_cap[i] = want;
-    }
+    for (int i = 0; i < 7; ++i) if (const int rc = device_grown(s, pp.ints[i], std::max<size_t>(host[i].size(), 1)); rc < 0) return rc;
+    for (int m = 0; m < 3; ++m) if (const int rc = device_grown(s, pp.val[m], (size_t)std::max<i64>(pp.nnz[m], 1)); rc < 0) return rc;
+    for (int i = 0; i < 7; ++i) if (!host[i].empty()) KK(hipMemcpyAsync(pp.ints[i].p, host[i].data(), sizeof(int) * host[i].size(), hipMemcpyHostToDevice, s->st));
     for (int m = 0; m < 3; ++m) {
-        const size_t want = (size_t)std::max<i64>(pp.nnz[m], 1);
-        if (want <= pp.val_cap[m]) continue;
-        { const int rc = kkt_reserve(s, &pp.val[m], want); if (rc < 0) return rc; }
-        pp.val_cap[m] = want;
+        KK(hipMemsetAsync(pp.val[m].p, 0, sizeof(double) * (size_t)std::max<i64>(pp.nnz[m], 1), s->st));      // the values start as zeros
+        d.ptr[m] = pp.ints[2 * m].p; d.idx[m] = pp.ints[2 * m + 1].p; d.val[m] = pp.val[m].p;
     }
-    KK(hipDeviceSynchronize());                              // kkt_reserve zeroes on the null stream, which the handle's non-blocking stream does not wait for
-    for (int i = 0; i < 7; ++i) if (!host[i].empty()) KK(hipMemcpyAsync(pp.ints[i], host[i].data(), sizeof(int) * host[i].size(), hipMemcpyHostToDevice, s->st));
-    for (int m = 0; m < 3; ++m) {
-        KK(hipMemsetAsync(pp.val[m], 0, sizeof(double) * (size_t)std::max<i64>(pp.nnz[m], 1), s->st));      // the values start as zeros
-        d.ptr[m] = pp.ints[2 * m]; d.idx[m] = pp.ints[2 * m + 1]; d.val[m] = pp.val[m];
-    }
-    d.long_columns = pp.ints[6];
+    d.long_columns = pp.ints[6].p;
     KK(hipStreamSynchronize(s->st));                         // (the host copies above leave scope)
     pp.d = d; pp.longest = split.longest;
     pp.set = true;
     return CALIPSO_OK;
 }
 int32_t calipso_hip_sparse_kkt_evaluate_parameters(calipso_hip_sparse_kkt* s) {
-    if (!s) return CALIPSO_ERR_ARGUMENT;
-    KK(hipSetDevice(s->device));
+    static const char* const entry = "calipso_hip_sparse_kkt_evaluate_parameters";
+    ENTER(HANDLE);
     (void)hipGetLastError();
-    { const int rc = parameters_enqueue(s, "calipso_hip_sparse_kkt_evaluate_parameters"); if (rc < 0) return rc; }
+    { const int rc = parameters_enqueue(s, entry); if (rc < 0) return rc; }
     KK(hipStreamSynchronize(s->st));
     KK(hipGetLastError());
     return CALIPSO_OK;
 }
 
 int32_t calipso_hip_sparse_kkt_keep_trace(calipso_hip_sparse_kkt* s, int64_t rows) {
-    if (!s) return CALIPSO_ERR_ARGUMENT;
-    KK(hipSetDevice(s->device));
-    { const int rc = ensure_state(s); if (rc < 0) return rc; }
+    static const char* const entry = "calipso_hip_sparse_kkt_keep_trace";
+    ENTER(STATE);
     REFUSE(check_keep_trace(rows));
     SS* t = s->solve;
-    if (rows > t->trace_cap) {
-        KK(hipStreamSynchronize(s->st));
-        double* p = nullptr;
-        KK(hipMalloc((void**)&p, sizeof(double) * (size_t)rows * (size_t)std::max(s->d.N, 1)));
-        for (void*& old : t->own) if (old == t->trace) { (void)hipFree(old); old = nullptr; }
-        t->own.push_back(p);
-        t->trace = p;
+    if (rows > t->trace_cap) {                                // more rows than were kept: the trace starts again
+        if (const int rc = device_grown(s, t->trace, (size_t)rows * (size_t)std::max(s->d.N, 1)); rc < 0) return rc;
         t->trace_rows = 0; t->trace_total = 0;
     }
     t->trace_cap = rows;
@@ -1157,13 +1105,12 @@ int32_t calipso_hip_sparse_kkt_keep_trace(calipso_hip_sparse_kkt* s, int64_t row
     return CALIPSO_OK;
 }
 int32_t calipso_hip_sparse_kkt_trace(calipso_hip_sparse_kkt* s, double* out, int64_t cap_rows, int64_t* accepted) {
-    if (!s) return CALIPSO_ERR_ARGUMENT;
-    KK(hipSetDevice(s->device));
-    { const int rc = ensure_state(s); if (rc < 0) return rc; }
+    static const char* const entry = "calipso_hip_sparse_kkt_trace";
+    ENTER(STATE);
     REFUSE(check_trace(out, cap_rows));
     SS* t = s->solve;
     const i64 rows = std::min<i64>(t->trace_rows, cap_rows);
-    if (rows > 0 && s->d.N) KK(hipMemcpyAsync(out, t->trace, sizeof(double) * (size_t)rows * (size_t)s->d.N, hipMemcpyDeviceToHost, s->st));
+    if (rows > 0 && s->d.N) KK(hipMemcpyAsync(out, t->trace.p, sizeof(double) * (size_t)rows * (size_t)s->d.N, hipMemcpyDeviceToHost, s->st));
     KK(hipStreamSynchronize(s->st));
     if (accepted) *accepted = t->trace_total;
     return (int32_t)rows;

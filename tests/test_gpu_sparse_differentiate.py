@@ -319,6 +319,30 @@ def test_repetition_and_the_solve_is_left_alone(solved):
     assert np.array_equal(first_solution, solved["w"]) and info["host_waits"] == solved["info"]["host_waits"]
 
 
+def test_buffers_that_grow_give_a_fresh_handles_bits(block_references, solved):
+    """the column workspace and the trace are grown on demand and kept: what comes out of a buffer that grew is what a fresh handle gives"""
+    ref = block_references(dc.INERT)                                     # nx 12
+    B = np.random.default_rng(5).standard_normal((ref["M"].shape[0], 5))
+    g, held = block_handle(ref["prob"], ref["w"]), []
+    for k in (1, 5, 2):
+        got = g.solve_columns(B[:, :k])
+        held.append(g.differentiate_bytes())
+    assert np.array_equal(got, block_handle(ref["prob"], ref["w"]).solve_columns(B[:, :2]))
+    assert 0 < held[0] < held[1] == held[2]                              # grew once, did not shrink
+    base = solved["base"]
+
+    def traced(*rows):
+        h, _ = conic_handle(base)
+        for r in rows:
+            h.keep_trace(r)
+        h.initialize(np.zeros(base.nx))
+        status, info = h.solve()
+        assert status == 1 and info["accepted_iterates"] > 5
+        return h.trace()
+    grown, want = traced(2, 5), traced(5)
+    assert grown.shape == want.shape == (5, solved["w"].size) and np.array_equal(grown, want) and np.abs(want[4]).max() > 0.0
+
+
 def test_sparse_qp_layer_gradients_against_the_oracle(solved):
     from calipso_jl_amd.torch_layer import SparseQPLayer
     base, mats, S = solved["base"], solved["mats"], solved["S"]

@@ -86,6 +86,25 @@ def test_a_superset_pattern_with_stored_zeros_moves_nothing(block_references):
     check_blocks(g, inputs, ref)
 
 
+@pytest.mark.parametrize("name", ["staged_2_3_1_1_0_3", "staged_3_4_2_1_1_3", "qp_soc64_70_5_66"])
+def test_the_single_column_solve_is_the_one_column_map(block_references, name):
+    """solve_symmetric and search_direction go through the multi-column map with one column: the same bits as solve_columns, and a handle that used the column
+    entries steps as one that never did (the dense-pattern case takes the wavefront-per-row H v in its refinement)"""
+    ref = block_references(name)
+    g, (Lxx, gx, hx) = handle(ref["prob"])
+    g.set_values(Lxx, gx, hx, ref["w"], kc.RHO, central_path=kc.KAPPA)
+    assert g.factorize(kc.EP, kc.ED) == 0
+    R, R2 = ref["R"], np.random.default_rng(3).standard_normal(g.N)
+    one = g.solve_symmetric(R)
+    assert np.array_equal(g.solve_columns(R), one)
+    assert np.array_equal(g.solve_columns(np.stack([R, R2], axis=1))[:, 0], one)
+    fresh, _ = handle(ref["prob"])
+    fresh.set_values(Lxx, gx, hx, ref["w"], kc.RHO, central_path=kc.KAPPA)
+    step, reg, info, status = g.search_direction(R, (0.0, 0.0, 0.0))
+    want = fresh.search_direction(R, (0.0, 0.0, 0.0))
+    assert np.array_equal(step, want[0]) and (reg, info, status) == want[1:]
+
+
 @pytest.mark.parametrize("name", sorted(kc.WHOLE))
 def test_whole_search_direction(oracle_mod, name):
     shape, pid, kind, want = kc.WHOLE[name]

@@ -318,6 +318,77 @@ def test_the_hand_written_parametric_evaluator_against_the_oracle(parametric):
     assert ones[0] == 0.0 and np.all(ones[1:] != 0.0)                            # a parameter with no entry in any array: its gradient is written, as zero
 
 
+# ---- 4b. the handle's grown buffers: patterns and parameters set again give a fresh handle's bits ---------------------------------------------------------------------------
+def parametric_handle(parametric):
+    """a fresh handle on the fixture's problem, its sparse inputs, and attach(g, user, mats, count): the hand-written evaluator with that user object and `count`
+    parameters, the patterns of the blocks `mats` and the fixture's theta"""
+    prob = parametric["prob"]
+    q, dims = kc.cone_layout(prob)
+    inputs = kc.sparse_inputs(prob)
+    g = load_pkg().SparseKKT(*inputs, n_nonnegative=q, second_order_dims=dims)
+
+    def attach(g, user, mats, count=prob.np):
+        g.set_evaluator(C.cast(parametric_library().qp_sparse_parameters_eval, C.c_void_p), user, count)
+        if count == prob.np:
+            g.set_parameter_patterns(*mats)
+            g.set_parameters(prob.parameters)
+    return g, inputs, attach
+
+
+def test_parameter_patterns_set_again_give_a_fresh_handles_arrays(parametric):
+    prob, full = parametric["prob"], parametric["mats"]
+
+    def thinned(M):                                                            # a strict sub-pattern: every third stored entry dropped
+        M = sp.coo_matrix(M)
+        keep = np.arange(M.nnz) % 3 != 0
+        out = sp.csc_matrix((M.data[keep], (M.row[keep], M.col[keep])), shape=M.shape)
+        out.sort_indices()
+        return out
+    sub = [thinned(M) for M in full]
+    assert all(0 < a.nnz < b.nnz for a, b in zip(sub, full))
+    g, inputs, attach = parametric_handle(parametric)
+    w = np.random.default_rng(6).standard_normal(g.N)
+    g.set("solution", w)
+    users = []
+    for mats in (full, sub, full):
+        L, user = parametric_user(prob, list(inputs) + list(mats))
+        users.append(user)
+        fresh, _, _ = parametric_handle(parametric)
+        fresh.set("solution", w)
+        got = []
+        for h in (g, fresh):
+            attach(h, user, mats)
+            h.evaluate_parameters()
+            got.append([h.get(n) for n in h.PARAMETER_ARRAYS])
+        for a, b, M, sign in zip(got[0], got[1], mats, (1.0, -1.0, 1.0)):   # Lx,theta = Qt, g,theta = -Bt, h,theta = Ht on the patterns set last
+            assert a.shape == b.shape == (M.nnz,) and np.array_equal(a, b) and np.array_equal(a, sign * M.data)
+        fresh.close()
+    g.close()
+    for user in users:
+        L.qp_sparse_parameters_destroy(user)
+
+
+def test_the_evaluator_set_again_with_another_parameter_count_solves_to_the_same_trace(parametric):
+    prob = parametric["prob"]
+    g, inputs, attach = parametric_handle(parametric)
+    L, user = parametric_user(prob, list(inputs) + list(parametric["mats"]))
+
+    def run():
+        g.keep_trace(8)
+        g.initialize(np.zeros(prob.nx))
+        status, info = g.solve()
+        return status, info["total_iterations"], g.trace(), info["accepted_iterates"]
+    attach(g, user, parametric["mats"])
+    before = run()
+    attach(g, user, None, prob.np + 3)                                         # more parameters: theta grows
+    attach(g, user, parametric["mats"])                                        # ... and back: theta is set again
+    after = run()
+    assert before[0] == after[0] == 1 and before[1] == after[1] and before[3] > 0
+    assert before[2].shape == (min(8, before[3]), g.N) and np.array_equal(before[2], after[2])
+    g.close()
+    L.qp_sparse_parameters_destroy(user)
+
+
 # ---- 5. a nonlinear whole solve ----------------------------------------------------------------------------------------------------------------------------------------
 def test_cartpole_mpc_solved_then_differentiated_against_the_oracle_at_the_handles_own_state(oracle_mod):
     """the method of test_gpu_trajectory_codegen.py:220-243 with its 1e-8: the oracle differentiated at the handle's point, scalars, Hessian, Jacobian and slacks"""

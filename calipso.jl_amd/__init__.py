@@ -13,7 +13,7 @@ import numpy as np
 from ._lib import CALLBACK_FN, EVAL_FN, CalipsoHipError, lib
 from ._marshal import QP_NAMES, pack_cotangent, qp_names, qp_shapes, unpack_columns
 
-__all__ = ["Solver", "Group", "LDLSolver", "SmallBatch", "SparseKKT", "SparseConicQP", "Comm", "ordering", "symbolic", "Options", "initialize_b", "solve_b", "CalipsoHipError", "FLAGS", "splitmix_uniform",
+__all__ = ["Solver", "Group", "LDLSolver", "SmallBatch", "SparseKKT", "SparseKKTGroup", "SparseConicQP", "Comm", "ordering", "symbolic", "Options", "initialize_b", "solve_b", "CalipsoHipError", "FLAGS", "splitmix_uniform",
            "mfma_f64_peak"]
 
 # evaluate! flags (include/calipso_hip.h)
@@ -1374,6 +1374,168 @@ class SparseKKT(_Handle):
         out, accepted = np.zeros((max(cap, 1), self.N)), C.c_int64()
         rows = self._check(self._L.calipso_hip_sparse_kkt_trace(self._h, _pd(out), cap, C.byref(accepted)), "sparse_kkt_trace")
         return out[:rows]
+
+
+class SparseKKTGroup(_Handle):
+    """search_direction! for a GROUP of `members` (1 .. 128) same-pattern sparse problems in lockstep (include/calipso_hip.h, "search_direction! on sparse data, for
+    GROUPS"; csrc/sparse_kkt_group.hip): one analysis, one multifrontal plan, the members through the same launches.  Lxx, gx, hx, the cones, method, perm, device as
+    SparseKKT — only the PATTERNS are taken here; every value array is members x count, member-major: a (members, count) array, or a sequence of `members` sparse
+    matrices / vectors.  Member m's results are bit for bit those of a SparseKKT on the same data.  Options are shared; central_path (kappa) and the penalty are per
+    member.  There is no `H \\ residual` fallback in a group: a member whose refinement fails gets status 2 and its last refined step."""
+    _last_error, _destroy = "calipso_hip_sparse_kkt_group_last_error", "calipso_hip_sparse_kkt_group_destroy"
+    _message = _Handle._STATUS_MESSAGE
+    REPORT = ("factorization_rounds", "refinement_rounds", "host_waits", "launches", "device_ms", "wall_ms", "last_factorization_active", "last_refinement_active")
+
+    def __init__(self, Lxx, gx, hx, members, n_nonnegative=None, second_order_dims=(), method="nested_dissection", perm=None, device=0, options=None):
+        import scipy.sparse as sp
+        self._L = lib()
+        as_csc = lambda A: A if sp.isspmatrix_csc(A) else sp.csc_matrix(A)
+        Lxx, gx, hx = as_csc(Lxx), as_csc(gx), as_csc(hx)
+        self.nx, self.ne, self.nc = int(Lxx.shape[0]), int(gx.shape[0]), int(hx.shape[0])
+        if Lxx.shape != (self.nx, self.nx) or gx.shape[1] != self.nx or hx.shape[1] != self.nx:
+            raise ValueError("SparseKKTGroup: Lxx is nx x nx, gx ne x nx, hx nc x nx")
+        self.n, self.N = self.nx + self.ne + self.nc, self.nx + 2 * self.ne + 3 * self.nc
+        self.nnz = (int(Lxx.indptr[-1]), int(gx.indptr[-1]), int(hx.indptr[-1]))
+        self.members = int(members)
+        dims = np.ascontiguousarray(list(second_order_dims), dtype=np.int64)
+        if n_nonnegative is None:
+            n_nonnegative = self.nc - int(dims.sum())
+        one_based = lambda A: (np.ascontiguousarray(A.indptr, dtype=np.int64) + 1, np.ascontiguousarray(A.indices, dtype=np.int64) + 1)
+        pats = [one_based(A) for A in (Lxx, gx, hx)]
+        pp = None if perm is None else np.ascontiguousarray(perm, dtype=np.int64)
+        h = C.c_void_p()
+        rc = self._L.calipso_hip_sparse_kkt_group_create(self.nx, self.ne, self.nc, int(n_nonnegative), int(dims.size), _pi(dims) if dims.size else None,
+                                                         _pi(pats[0][0]), _pi(pats[0][1]), _pi(pats[1][0]), _pi(pats[1][1]), _pi(pats[2][0]), _pi(pats[2][1]),
+                                                         3 if pp is not None else SPARSE_METHODS[method], _pi(pp) if pp is not None else None, device, self.members, C.byref(h))
+        if rc != 0:
+            raise CalipsoHipError("calipso_hip_sparse_kkt_group_create failed (%d): %s" % (rc, self._L.calipso_hip_sparse_kkt_group_last_error(None).decode()))
+        self._h = h
+        self.device = int(device)
+        info = np.zeros(9, dtype=np.int64)
+        self._check(self._L.calipso_hip_sparse_kkt_group_info(self._h, _pi(info)), "sparse_kkt_group_info")
+        self.info = dict(n=int(info[0]), nnz_upper=int(info[1]), nnzL=int(info[2]), levels=int(info[3]),
+                         numeric={0: "columns_global_accumulator", 1: "columns_lds_accumulator", 2: "multifrontal"}[int(info[4])], assemble_launches=int(info[5]),
+                         max_cone_dimension=int(info[6]), N=int(info[7]), members=int(info[8]))
+        self._colptr, self._rowval = np.zeros(self.n + 1, dtype=np.int64), np.zeros(max(self.info["nnz_upper"], 1), dtype=np.int64)
+        self._check(self._L.calipso_hip_sparse_kkt_group_pattern(self._h, _pi(self._colptr), _pi(self._rowval)), "sparse_kkt_group_pattern")
+        self.inertia = [(0, 0, 0)] * self.members
+        self.status = 0
+        for k, v in (options or {}).items():
+            self.set_option(k, v)
+
+    def set_option(self, name, value):
+        """the regularisation and refinement options by name, shared by the group; "central_path": every member's kappa.  krylov_fallback = 1 is refused"""
+        self._check(self._L.calipso_hip_sparse_kkt_group_set_option(self._h, name.encode(), float(value)), "sparse_kkt_group_set_option(%s)" % name)
+
+    def _is_device(self, a):
+        return a is not None and hasattr(a, "is_cuda")
+
+    def _device_pointer(self, a, name, count):
+        if a is None:
+            return None
+        import torch
+        if a.dtype != torch.float64 or a.numel() != self.members * count or not a.is_contiguous():
+            raise ValueError("%s must be a contiguous float64 tensor of %d x %d entries" % (name, self.members, count))
+        if a.is_cuda and a.device.index != self.device:
+            raise ValueError("%s is on %s, the group on device %d" % (name, a.device, self.device))
+        if a.is_cuda:
+            torch.cuda.current_stream(a.device).synchronize()      # the group works on its own stream
+        return C.c_void_p(a.data_ptr())      # (a CPU tensor's pointer goes through: the library refuses it, naming the argument)
+
+    def _host(self, a, name, count, what):
+        """members x count doubles from a (members, count) array or a sequence of `members` sparse matrices / vectors"""
+        if a is None:
+            return None
+        if not isinstance(a, np.ndarray):
+            a = [np.asarray(m.data if hasattr(m, "indptr") else m, dtype=np.float64).reshape(-1) for m in a]
+            if any(m.size != count for m in a):
+                raise CalipsoHipError("SparseKKTGroup.%s: %s has %s values per member, not %d" % (what, name, sorted(set(m.size for m in a)), count))
+        v = np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+        if v.size != self.members * count:
+            raise CalipsoHipError("SparseKKTGroup.%s: %s has %d values, not %d x %d" % (what, name, v.size, self.members, count))
+        return v
+
+    def set_values(self, Lxx=None, gx=None, hx=None, w=None, penalty=None, central_path=None):
+        """non-zeros of Lxx, gx, hx (per member: sparse matrices of the analysed pattern, or the values in its order), the points w (members x N), the penalties rho
+        and central_path kappa (members each, or one number for all); None keeps what is resident.  Host data, or — all that are given of the first five — float64
+        CUDA tensors of members x count entries (the device route; central_path stays a host value)."""
+        kappa = None if central_path is None else np.ascontiguousarray(np.broadcast_to(np.asarray(central_path, dtype=np.float64).reshape(-1), (self.members,)))
+        given = [a for a in (Lxx, gx, hx, w, penalty) if a is not None]
+        names, counts = ("Lxx", "gx", "hx", "w", "penalty"), self.nnz + (self.N, 1)
+        if given and all(self._is_device(a) for a in given):
+            ptrs = [self._device_pointer(a, nm, ct) for a, nm, ct in zip((Lxx, gx, hx, w, penalty), names, counts)]
+            self._check(self._L.calipso_hip_sparse_kkt_group_set_values_device(self._h, *(ptrs + [_opt(kappa)])), "sparse_kkt_group_set_values_device")
+            return
+        if penalty is not None:
+            penalty = np.ascontiguousarray(np.broadcast_to(np.asarray(penalty, dtype=np.float64).reshape(-1), (self.members,)))
+        arrs = [self._host(a, nm, ct, "set_values") for a, nm, ct in zip((Lxx, gx, hx, w, penalty), names, counts)]
+        self._check(self._L.calipso_hip_sparse_kkt_group_set_values(self._h, *[_opt(a) for a in arrs + [kappa]]), "sparse_kkt_group_set_values")
+
+    def factorize(self, ep, ed):
+        """one assemble + one batched factorisation, member m at (ep[m], ed[m]) (numbers: the same for all); sets .inertia (a tuple per member); returns the warning
+        status (1 = a member met an exact zero pivot)"""
+        ep = np.ascontiguousarray(np.broadcast_to(np.asarray(ep, dtype=np.float64).reshape(-1), (self.members,)))
+        ed = np.ascontiguousarray(np.broadcast_to(np.asarray(ed, dtype=np.float64).reshape(-1), (self.members,)))
+        out = np.zeros(3 * self.members, dtype=np.int64)
+        rc = self._check(self._L.calipso_hip_sparse_kkt_group_factorize(self._h, _pd(ep), _pd(ed), _pi(out)), "sparse_kkt_group_factorize")
+        self.inertia = [tuple(int(v) for v in out[3 * m:3 * m + 3]) for m in range(self.members)]
+        return rc
+
+    def matrix(self, member):
+        """triu(jacobian_variables_symmetric) of the member's last assemble, scipy CSC"""
+        import scipy.sparse as sp
+        nz = np.zeros(max(self.info["nnz_upper"], 1))
+        self._check(self._L.calipso_hip_sparse_kkt_group_get_matrix(self._h, int(member), _pd(nz)), "sparse_kkt_group_get_matrix")
+        k = self.info["nnz_upper"]
+        return sp.csc_matrix((nz[:k], self._rowval[:k] - 1, self._colptr - 1), shape=(self.n, self.n))
+
+    def mul(self, v):
+        """H v per member (members x N) for the unreduced matrices at the regularisation of every member's last assemble"""
+        v = self._host(v, "v", self.N, "mul")
+        out = np.zeros(self.members * self.N)
+        self._check(self._L.calipso_hip_sparse_kkt_group_mul(self._h, _pd(v), _pd(out)), "sparse_kkt_group_mul")
+        return out.reshape(self.members, self.N)
+
+    def solve_symmetric(self, residual):
+        """search_direction_symmetric! per member (members x N) with the current factorisations"""
+        r = self._host(residual, "the residual", self.N, "solve_symmetric")
+        out = np.zeros(self.members * self.N)
+        self._check(self._L.calipso_hip_sparse_kkt_group_solve_symmetric(self._h, _pd(r), _pd(out)), "sparse_kkt_group_solve_symmetric")
+        return out.reshape(self.members, self.N)
+
+    def search_direction(self, residual, regularization=(0.0, 0.0, 0.0)):
+        """search_direction! of every member in lockstep from regularization = (ep, ep_last, ed) per member (members x 3, or one triple for all): returns
+        (steps (members x N), regularizations (a triple per member), infos (a dict per member: factorizations, refinement_rounds, residual_norm), statuses (per member:
+        0, 2 = refinement failed, -1 = inertia correction failed: that member's step is left as it was — zeros on the host route), report (dict of REPORT)).  .status
+        is the worst member status.  A CUDA tensor as residual: the device route, the steps come back as a CUDA tensor."""
+        reg = np.ascontiguousarray(np.broadcast_to(np.asarray(regularization, dtype=np.float64).reshape(-1, 3), (self.members, 3))).copy()
+        info, status, report = np.zeros(4 * self.members), np.zeros(self.members, dtype=np.int32), np.zeros(8)
+        if self._is_device(residual):
+            import torch
+            step = torch.zeros(self.members, self.N, dtype=torch.float64, device=torch.device("cuda", self.device))
+            rp = self._device_pointer(residual, "residual", self.N)
+            torch.cuda.current_stream(step.device).synchronize()
+            rc = self._L.calipso_hip_sparse_kkt_group_search_direction_device(self._h, rp, C.c_void_p(step.data_ptr()), _pd(reg), _pd(info), status.ctypes.data_as(C.POINTER(C.c_int32)), _pd(report))
+        else:
+            r = self._host(residual, "the residual", self.N, "search_direction")
+            step = np.zeros((self.members, self.N))
+            rc = self._L.calipso_hip_sparse_kkt_group_search_direction(self._h, _pd(r), _pd(step), _pd(reg), _pd(info), status.ctypes.data_as(C.POINTER(C.c_int32)), _pd(report))
+        if rc != -1:                                             # (CALIPSO_ERR_INERTIA is a member's status here: the others went on)
+            self._check(rc, "search_direction! (group)")
+        self.status = int(rc)
+        self.regularization = [tuple(float(v) for v in reg[m]) for m in range(self.members)]
+        infos = [dict(factorizations=int(info[4 * m]), refinement_rounds=int(info[4 * m + 1]), residual_norm=float(info[4 * m + 2])) for m in range(self.members)]
+        rep = dict(zip(self.REPORT, (float(v) for v in report)))
+        for k in self.REPORT:
+            if not k.endswith("_ms"):
+                rep[k] = int(rep[k])
+        return step, self.regularization, infos, [int(v) for v in status], rep
+
+    def timing(self):
+        """device milliseconds of the last search_direction: dict(inertia_correction, solve, refinement, wall, device)"""
+        ms = np.zeros(8)
+        self._check(self._L.calipso_hip_sparse_kkt_group_timing(self._h, _pd(ms)), "sparse_kkt_group_timing")
+        return dict(inertia_correction=float(ms[0]), solve=float(ms[1]), refinement=float(ms[2]), wall=float(ms[5]), device=float(ms[6]))
 
 
 def SparseConicQP(P, q, A, b, G, h, n_nonnegative=None, second_order_dims=(), objective_scale=0.5, **kw):

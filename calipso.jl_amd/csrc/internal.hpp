@@ -507,6 +507,7 @@ int sparse_batch(const calipso_hip_sparse* sp);
 hipStream_t sparse_stream(const calipso_hip_sparse* sp);      // the plan's stream (sparse_kkt.hip enqueues its kernels on it)
 int sparse_factor_from_dense(calipso_hip_sparse* sp, hipStream_t st, const Batch& bt, const double* S, const long long* src, int* icount, bool values_in_place = false);
 void sparse_values(calipso_hip_sparse* sp, double** values, long long* stride);      // the batch x nnz values the factorisation reads (instance-major)
+int sparse_inertia_enqueue(calipso_hip_sparse* sp, hipStream_t st, const Batch& bt, long long* out);      // compute_inertia! of those factors on the device: out[3 * slot ..]
 int sparse_solve_inplace(calipso_hip_sparse* sp, hipStream_t st, const Batch& bt, double* x);
 int sparse_reserve_solve(calipso_hip_sparse* sp, int batch);
 int sparse_solve_inplace_multi(calipso_hip_sparse* sp, hipStream_t st, int slot, double* X, long long ld, int p);

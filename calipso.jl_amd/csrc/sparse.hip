@@ -952,6 +952,30 @@ __global__ __launch_bounds__(256) void k_count_signs(calipso::Batch bt, const do
         icount[5] += sh[2][0] + sh[2][1] + sh[2][2] + sh[2][3];
     }
 }
+// compute_inertia! as calipso_hip_sparse_factorize reports it, on the device: the up-looking factorisation stops at the first exact zero pivot in elimination order,
+// the rest of D counts as zeros and inertia[0] = -1 (qdldl.jl:444,456,579).  One workgroup per matrix of `bt`; out[3 * slot ..]: integers, so no order of summation shows
+__global__ __launch_bounds__(256) void k_reference_inertia(calipso::Batch bt, const double* __restrict__ D, int n, long long* __restrict__ out) {
+    __shared__ int sh[3][4];
+    const int slot = bt.slot[blockIdx.z];
+    const double* Dz = D + (size_t)slot * n;
+    int first = n;
+    for (int i = threadIdx.x; i < n; i += 256) if (Dz[i] == 0.0) { first = i; break; }      // (a thread's indices ascend)
+    for (int o = 32; o > 0; o >>= 1) first = min(first, __shfl_xor(first, o));
+    if ((threadIdx.x & 63) == 0) sh[0][threadIdx.x >> 6] = first;
+    __syncthreads();
+    first = min(min(sh[0][0], sh[0][1]), min(sh[0][2], sh[0][3]));
+    __syncthreads();
+    int pos = 0, nonpos = 0;
+    for (int i = threadIdx.x; i < first; i += 256) { const double v = Dz[i]; pos += v > 0.0; nonpos += v <= 0.0; }
+    pos = calipso::wave_sum_i(pos); nonpos = calipso::wave_sum_i(nonpos);
+    if ((threadIdx.x & 63) == 0) { sh[1][threadIdx.x >> 6] = pos; sh[2][threadIdx.x >> 6] = nonpos; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        long long p = sh[1][0] + sh[1][1] + sh[1][2] + sh[1][3], q = sh[2][0] + sh[2][1] + sh[2][2] + sh[2][3], z = 0;
+        if (first < n) { z = n - first; q += n - first; p = -1; }
+        out[3 * (size_t)slot] = p; out[3 * (size_t)slot + 1] = q; out[3 * (size_t)slot + 2] = z;
+    }
+}
 }  // namespace
 
 namespace calipso {
@@ -978,8 +1002,15 @@ int sparse_factor_from_dense(calipso_hip_sparse* sp, hipStream_t st, const Batch
     sl.use = 1;
     for (int k = 0; k < bt.n; ++k) sl.slot[k] = bt.slot[k];
     mf_enqueue_factor(sp, st, sl, nz);
-    hipLaunchKernelGGL(k_count_signs, dim3(1, 1, nz), dim3(256), 0, st, bt, sp->d.D, sp->n, icount);
+    if (icount) hipLaunchKernelGGL(k_count_signs, dim3(1, 1, nz), dim3(256), 0, st, bt, sp->d.D, sp->n, icount);      // (NULL: the caller counts by sparse_inertia_enqueue)
     sp->factored = true;
+    return CALIPSO_OK;
+}
+// the reference's inertia of the factors of the matrices of `bt` into out[3 * slot ..] (device, batch x 3), in stream order: what calipso_hip_sparse_factorize returns
+int sparse_inertia_enqueue(calipso_hip_sparse* sp, hipStream_t st, const Batch& bt, long long* out) {
+    if (!sp || !sp->mf || !out || bt.n < 1 || bt.n > sp->batch) return CALIPSO_ERR_ARGUMENT;
+    for (int k = 0; k < bt.n; ++k) if (bt.slot[k] < 0 || bt.slot[k] >= sp->batch) return CALIPSO_ERR_ARGUMENT;
+    hipLaunchKernelGGL(k_reference_inertia, dim3(1, 1, (unsigned)bt.n), dim3(256), 0, st, bt, sp->d.D, sp->n, out);
     return CALIPSO_OK;
 }
 // x <- S^-1 x for the first n entries of every instance's x (a slab buffer)

@@ -99,6 +99,7 @@ typedef calipso_hip_sparse_kkt KH;
 int fail(KH* s, int rc, const std::string& text);                                                           // sets last_error, returns rc
 int device_pointer(KH* s, const void* p, const char* entry, const char* arg);                               // the check of every _device entry
 int search_direction(KH* s, const double* res, double* step, double regularization[3], double info[4]);
+int create_tables(KH* s, int32_t method, const int64_t* perm);                                              // the plan of triu(K), stream, events, the analysis tables on the device (also the group's)
 int values_missing(KH* s, const char* entry);                                                               // Lxx, gx, hx, w, penalty resident, or the refusal
 int assemble_factorize(KH* s, const KktDev& d, double ep, double ed, int64_t inertia[3]);                    // one assemble from `d` (the handle's, or with other slacks) + factorisation
 // OUT = M V (transposed: M' V) for k columns on the device: the "pre" launch, ONE k-column LDL^T solve, the "post" launch; `around`: two events recorded around them

@@ -1,5 +1,5 @@
 // step_decisions.hpp — every decision the host takes inside a Newton step and between the steps of a solve, as free functions on values: the ONE copy that the
-// single-handle driver (api.hip), the group driver (group.hip) and the sparse handle's drivers (sparse_kkt.hip, sparse_solve.hip) all call.  Plain C++ (no HIP, no handle, no device, no error string): tests/step_decisions runs it
+// single-handle driver (api.hip), the group driver (group.hip) and the sparse handle's drivers (sparse_kkt.hip, sparse_solve.hip; for groups sparse_kkt_group.hpp) all call.  Plain C++ (no HIP, no handle, no device, no error string): tests/step_decisions runs it
 // on the CPU.  Every floating-point expression is the reference's, operand order and parentheses included — the drivers' results are compared bit for bit.
 #pragma once
 #include <algorithm>

@@ -498,7 +498,78 @@ solve_nonsymmetric_device!(k::SparseKKT, step::Ptr{Cvoid}, residual::Ptr{Cvoid})
 kkt_fallback_info(k::SparseKKT) = (out = zeros(12); kkt_check(ccall((:calipso_hip_sparse_kkt_fallback_info, lib), Int32, (Ptr{Cvoid}, Ptr{Float64}), k.handle, out), k, "fallback_info"); out)
 kkt_timing(k::SparseKKT) = (ms = zeros(8); kkt_check(ccall((:calipso_hip_sparse_kkt_timing, lib), Int32, (Ptr{Cvoid}, Ptr{Float64}), k.handle, ms), k, "timing"); ms)
 
-# ---- solve! on the same handle (csrc/sparse_solve.hip): the sparse conic QP  min c x'Px + q'x  s.t.  Ax - b = 0,  h - Gx in K  with Lxx = c (P + P'), gx = A, hx = -G ----
+# ---- search_direction! on sparse data for groups of same-pattern problems in lockstep (csrc/sparse_kkt_group.hip): ccall wrappers, no logic ----------------------
+"""
+    SparseKKTGroup(Lxx, gx, hx, members; n_nonnegative, second_order_dims, method=:nested_dissection, perm=nothing)
+
+`members` (1 .. 128) problems of one pattern through the same launches: one analysis, one multifrontal plan.  Every array is member-major (`members` pieces of
+one length).  `group_search_direction!(g, residual, step, regularization)` returns `(worst, info, status, report)`; member m's results are bit for bit those of a
+`SparseKKT` on the same data.  No `H \\ residual` fallback: a member whose refinement fails gets status 2 and its last refined step.
+"""
+mutable struct SparseKKTGroup
+    handle::Ptr{Cvoid}
+    N::Int
+    nnz_upper::Int
+    members::Int
+end
+group_last_error(h) = unsafe_string(ccall((:calipso_hip_sparse_kkt_group_last_error, lib), Cstring, (Ptr{Cvoid},), h))
+group_check(rc, g, what) = rc < 0 ? throw(HIPError(rc, "$what: $(group_last_error(g.handle))")) : rc
+function SparseKKTGroup(Lxx::SparseMatrixCSC{Float64,Int}, gx::SparseMatrixCSC{Float64,Int}, hx::SparseMatrixCSC{Float64,Int}, members::Integer; n_nonnegative::Integer,
+                        second_order_dims::Vector{Int}=Int[], method::Symbol=:nested_dissection, perm::Union{Nothing,Vector{Int}}=nothing, device::Integer=0)
+    href = Ref{Ptr{Cvoid}}(C_NULL)
+    rc = ccall((:calipso_hip_sparse_kkt_group_create, lib), Int32,
+               (Int64, Int64, Int64, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Int32, Ptr{Int64}, Int32, Int64, Ptr{Ptr{Cvoid}}),
+               size(Lxx, 1), size(gx, 1), size(hx, 1), n_nonnegative, length(second_order_dims), second_order_dims, Lxx.colptr, Lxx.rowval, gx.colptr, gx.rowval,
+               hx.colptr, hx.rowval, perm === nothing ? SPARSE_METHODS[method] : 3, perm === nothing ? C_NULL : perm, device, members, href)
+    rc != 0 && throw(HIPError(rc, "calipso_hip_sparse_kkt_group_create: $(group_last_error(C_NULL))"))
+    info = zeros(Int64, 9)
+    ccall((:calipso_hip_sparse_kkt_group_info, lib), Int32, (Ptr{Cvoid}, Ptr{Int64}), href[], info)
+    g = SparseKKTGroup(href[], info[8], info[2], info[9])
+    finalizer(x -> ccall((:calipso_hip_sparse_kkt_group_destroy, lib), Int32, (Ptr{Cvoid},), x.handle), g)
+    return g
+end
+group_info(g::SparseKKTGroup) = (info = zeros(Int64, 9); group_check(ccall((:calipso_hip_sparse_kkt_group_info, lib), Int32, (Ptr{Cvoid}, Ptr{Int64}), g.handle, info), g, "info"); info)
+group_pattern(g::SparseKKTGroup, colptr::Vector{Int64}, rowval::Vector{Int64}) =
+    group_check(ccall((:calipso_hip_sparse_kkt_group_pattern, lib), Int32, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}), g.handle, colptr, rowval), g, "pattern")
+set_option!(g::SparseKKTGroup, name::AbstractString, value::Real) =
+    group_check(ccall((:calipso_hip_sparse_kkt_group_set_option, lib), Int32, (Ptr{Cvoid}, Cstring, Float64), g.handle, name, value), g, "set_option!($name)")
+# host arrays, members x count each (nothing keeps what is resident); penalty and central_path: `members` values
+set_values!(g::SparseKKTGroup; Lxx=nothing, gx=nothing, hx=nothing, w=nothing, penalty=nothing, central_path=nothing) = GC.@preserve Lxx gx hx w penalty central_path group_check(
+    ccall((:calipso_hip_sparse_kkt_group_set_values, lib), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+          g.handle, kkt_ptr(Lxx), kkt_ptr(gx), kkt_ptr(hx), kkt_ptr(w), kkt_ptr(penalty), kkt_ptr(central_path)), g, "set_values!")
+# device pointers on the group's device (C_NULL keeps what is resident); central_path stays a host vector
+set_values_device!(g::SparseKKTGroup; Lxx=C_NULL, gx=C_NULL, hx=C_NULL, w=C_NULL, penalty=C_NULL, central_path=nothing) = GC.@preserve central_path group_check(
+    ccall((:calipso_hip_sparse_kkt_group_set_values_device, lib), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}),
+          g.handle, Lxx, gx, hx, w, penalty, kkt_ptr(central_path)), g, "set_values_device!")
+function group_factorize!(g::SparseKKTGroup, ep::Vector{Float64}, ed::Vector{Float64})
+    out = zeros(Int64, 3 * g.members)
+    rc = group_check(ccall((:calipso_hip_sparse_kkt_group_factorize, lib), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}), g.handle, ep, ed, out), g, "factorize")
+    return rc, out
+end
+group_matrix!(g::SparseKKTGroup, member::Integer, nzval::Vector{Float64}) =      # member: 0-based, as the C entry takes it
+    group_check(ccall((:calipso_hip_sparse_kkt_group_get_matrix, lib), Int32, (Ptr{Cvoid}, Int64, Ptr{Float64}), g.handle, member, nzval), g, "get_matrix")
+group_mul!(g::SparseKKTGroup, out::Vector{Float64}, v::Vector{Float64}) =
+    group_check(ccall((:calipso_hip_sparse_kkt_group_mul, lib), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), g.handle, v, out), g, "mul")
+solve_symmetric!(g::SparseKKTGroup, step::Vector{Float64}, residual::Vector{Float64}) =
+    group_check(ccall((:calipso_hip_sparse_kkt_group_solve_symmetric, lib), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), g.handle, residual, step), g, "solve_symmetric")
+# returns the worst member status (0, 2 or -1 = a member's inertia correction failed: see status), info (4 per member), status (per member), report (8)
+function group_search_direction!(g::SparseKKTGroup, residual::Vector{Float64}, step::Vector{Float64}, regularization::Vector{Float64})
+    info, status, report = zeros(4 * g.members), zeros(Int32, g.members), zeros(8)
+    rc = ccall((:calipso_hip_sparse_kkt_group_search_direction, lib), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}),
+               g.handle, residual, step, regularization, info, status, report)
+    rc != -1 && group_check(rc, g, "search_direction!")
+    return rc, info, status, report
+end
+function group_search_direction_device!(g::SparseKKTGroup, residual::Ptr{Cvoid}, step::Ptr{Cvoid}, regularization::Vector{Float64})
+    info, status, report = zeros(4 * g.members), zeros(Int32, g.members), zeros(8)
+    rc = ccall((:calipso_hip_sparse_kkt_group_search_direction_device, lib), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}),
+               g.handle, residual, step, regularization, info, status, report)
+    rc != -1 && group_check(rc, g, "search_direction_device!")
+    return rc, info, status, report
+end
+group_timing(g::SparseKKTGroup) = (ms = zeros(8); group_check(ccall((:calipso_hip_sparse_kkt_group_timing, lib), Int32, (Ptr{Cvoid}, Ptr{Float64}), g.handle, ms), g, "timing"); ms)
+
+# ---- solve! on the same handle (csrc/sparse_solve.hip): the sparse conic QP min c x'Px + q'x  s.t.  Ax - b = 0,  h - Gx in K  with Lxx = c (P + P'), gx = A, hx = -G ----
 # host vectors (nothing keeps what is resident)
 qp_attach!(k::SparseKKT; q=nothing, b=nothing, h=nothing, objective_constant::Real=0.0) = GC.@preserve q b h kkt_check(
     ccall((:calipso_hip_sparse_kkt_qp_attach, lib), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Float64), k.handle, kkt_ptr(q), kkt_ptr(b), kkt_ptr(h),
@@ -987,7 +1058,8 @@ function allreduce_sum!(c::HIPComm, v::Vector{Float64})
 end
 
 export SparseKKT, set_values!, set_values_device!, kkt_info, kkt_pattern, kkt_factorize!, kkt_matrix!, kkt_mul!, solve_symmetric!, sparse_search_direction!, sparse_search_direction_device!, kkt_timing, qp_attach!, sparse_initialize!, sparse_solve!, sparse_get, sparse_set!
-export sparse_solve_columns!, sparse_differentiate!, sparse_differentiate_adjoint!, sparse_differentiate_info, sparse_differentiate_adjoint_info, sparse_differentiate_adjoint_times, sparse_differentiate_bytes, sparse_solve_columns_device!, sparse_differentiate_device!, sparse_differentiate_adjoint_device!
+export SparseKKTGroup, group_info, group_pattern, group_factorize!, group_matrix!, group_mul!, group_search_direction!, group_search_direction_device!, group_timing
+export sparse_solve_columns!, sparse_differentiate!,sparse_differentiate_adjoint!, sparse_differentiate_info, sparse_differentiate_adjoint_info, sparse_differentiate_adjoint_times, sparse_differentiate_bytes, sparse_solve_columns_device!, sparse_differentiate_device!, sparse_differentiate_adjoint_device!
 export HIPSolver, streams_concurrent, rebind_stream!, spread_streams!, HIPLDLSolver, HIPSparseLDLSolver, hip_sparse_ldl_solver, HIPKKTSolver, hip_ldl_solver, HIPGroup, HIPSmallNewton, set_option!, set_cones!, set_qp!, set_evaluator!, set_parameters!, differentiate_adjoint!, solution, set_stream!, set_qp_device!, initialize_device!, set_state_device!, set_parameters_device!, solve_device!, solution_device!, differentiate_adjoint_device!, HIPComm, comm_unique_id, comm_size, gather_status, allreduce_sum!, newton_step!,
        search_direction_nonsymmetric!, analyze_structure!, clear_structure!, set_stage_parallel!, set_stage_blocks!, declared_structure, kernel_times, sync_scalars!, copy_back!
 

@@ -617,6 +617,64 @@ int32_t calipso_hip_sparse_kkt_solve_nonsymmetric(calipso_hip_sparse_kkt*, const
 int32_t calipso_hip_sparse_kkt_solve_nonsymmetric_device(calipso_hip_sparse_kkt*, const double* residual, double* step);
 int32_t calipso_hip_sparse_kkt_fallback_info(calipso_hip_sparse_kkt*, double out[12]);
 
+/* ---- search_direction! on sparse data, for GROUPS of same-pattern problems in lockstep (csrc/sparse_kkt_group.hip; host bookkeeping: csrc/sparse_kkt_group.hpp) ----
+ * `members` problems (1 .. 128) that share the patterns of Lxx, gx, hx and the cone layout — sampling MPC, a parameter sweep, a minibatch — stepped through the
+ * SAME launches: one analysis, one device copy of its tables, one multifrontal plan with calipso_hip_sparse_set_batch(members); per member its own non-zeros,
+ * point, penalty, kappa and work vectors.  Every array below is members x count, member-major (member m's piece at m * count).  Member m's results are, bit for
+ * bit, those of a calipso_hip_sparse_kkt on the same data, whatever the group's size and the member's place in it: the kernels call the single handle's arithmetic
+ * (csrc/sparse_kkt_kernels.hpp) after shifting their pointers, the member on blockIdx.z through the list of active members.  The host waits of a call are those of
+ * its slowest member, not the sum, and its launches do not depend on the number of members.
+ *   create          the arguments of calipso_hip_sparse_kkt_create and `members`; anything but 1 .. 128 is CALIPSO_ERR_ARGUMENT naming the argument.  A group needs
+ *                   the multifrontal numeric phase (info[4] == 2: method 4); the column method factors a batch one matrix after the other, so on such a plan
+ *                   create refuses with a text that names the numeric phase.  Without a HIP device: CALIPSO_ERR_HIP, "no HIP device".
+ *   info            info[9] = the eight values of calipso_hip_sparse_kkt_info, then members
+ *   pattern         as calipso_hip_sparse_kkt_pattern: triu(K) is the same for every member
+ *   set_option      the regularisation and refinement options (options.jl:6-59) by name, shared by the group; "central_path" sets every member's kappa (IC-2,
+ *                   inertia.jl:44).  krylov_fallback = 1 is CALIPSO_ERR_ARGUMENT, "not built for groups": there is no `H \ residual` (search_direction.jl:22) in a
+ *                   group, a member whose refinement fails gets status 2 and its last refined step — what the single handle does by default.
+ *   set_values      as calipso_hip_sparse_kkt_set_values with members x count arrays; penalty and central_path take `members` values (rho and kappa are per
+ *                   member).  NULL keeps what is resident.  (_device: device pointers, except central_path, which the host reads.)
+ *   factorize       residual_jacobian_variables_symmetric! (residual_jacobian_variables.jl:1-167) + factorize! + compute_inertia! (linear_solver.jl:19-44) of every
+ *                   member at ITS (ep[m], ed[m]): one assemble launch into the plan's own value storage, one batched factorisation; inertia = members x 3
+ *   get_matrix      K.nzval of `member`'s last assemble
+ *   mul             out = H v per member (mul!(e, H, v), iterative_refinement.jl:9,39), each at the regularisation of its last assemble; v, out = members x N
+ *   solve_symmetric search_direction_symmetric! (search_direction.jl:25-104) per member with the current factors; residual, step = members x N
+ *   search_direction  search_direction! (search_direction.jl:1-23) of every member in lockstep: inertia_correction! (inertia.jl:30-80) round by round over the
+ *                   members still walking — one assemble, one batched factorisation, ONE read-back of all their inertias, the verdict per member on that member's
+ *                   own scalars; one pre launch, one batched solve, one post launch for all that passed; iterative_refinement! (iterative_refinement.jl:1-52) as
+ *                   one fused H v / norm pass over the active members, ONE read-back of the norms, the verdict per member, the correction solve and add for
+ *                   those that go on.  regularization (members x 3, in and out), info (members x 4; [3] is 0: no fallback) and status (members) mean per member
+ *                   what the single entry's outputs and return value mean.  A member whose inertia correction fails gets CALIPSO_ERR_INERTIA in status, its
+ *                   regularisation is where the walk stopped, its step is untouched, and the other members go on.  Returns the worst member status — 0, 2
+ *                   (CALIPSO_WARN_REFINEMENT) or CALIPSO_ERR_INERTIA — or CALIPSO_ERR_ARGUMENT / CALIPSO_ERR_HIP, which fail the call.  report[8] = lockstep
+ *                   factorisation rounds, lockstep refinement rounds, host waits, kernel launches (this file's, and per batched factorisation / solve one per
+ *                   level of the plan's schedule — fronts beyond the LDS take more — and the two permutations), device ms, wall ms, members active in the last
+ *                   factorisation round, members active in the last refinement round.  (_device: residual and step are device pointers.)
+ *   timing          ms[8] of the last search_direction, HIP events on the plan's stream: [inertia correction, first solve, refinement, 0, 0, wall-clock, the
+ *                   three together, 0] */
+typedef struct calipso_hip_sparse_kkt_group calipso_hip_sparse_kkt_group;
+int32_t calipso_hip_sparse_kkt_group_create(int64_t nx, int64_t ne, int64_t nc, int64_t n_nonnegative, int64_t n_soc, const int64_t* dims, const int64_t* Lxx_colptr,
+                                            const int64_t* Lxx_rowval, const int64_t* gx_colptr, const int64_t* gx_rowval, const int64_t* hx_colptr, const int64_t* hx_rowval,
+                                            int32_t method, const int64_t* perm, int32_t device, int64_t members, calipso_hip_sparse_kkt_group** out);
+int32_t calipso_hip_sparse_kkt_group_destroy(calipso_hip_sparse_kkt_group*);
+const char* calipso_hip_sparse_kkt_group_last_error(calipso_hip_sparse_kkt_group*);
+int32_t calipso_hip_sparse_kkt_group_info(calipso_hip_sparse_kkt_group*, int64_t info[9]);
+int32_t calipso_hip_sparse_kkt_group_pattern(calipso_hip_sparse_kkt_group*, int64_t* colptr, int64_t* rowval);
+int32_t calipso_hip_sparse_kkt_group_set_option(calipso_hip_sparse_kkt_group*, const char* name, double value);
+int32_t calipso_hip_sparse_kkt_group_set_values(calipso_hip_sparse_kkt_group*, const double* Lxx, const double* gx, const double* hx, const double* w, const double* penalty,
+                                                const double* central_path);
+int32_t calipso_hip_sparse_kkt_group_set_values_device(calipso_hip_sparse_kkt_group*, const double* Lxx, const double* gx, const double* hx, const double* w, const double* penalty,
+                                                       const double* central_path);
+int32_t calipso_hip_sparse_kkt_group_factorize(calipso_hip_sparse_kkt_group*, const double* ep, const double* ed, int64_t* inertia);
+int32_t calipso_hip_sparse_kkt_group_get_matrix(calipso_hip_sparse_kkt_group*, int64_t member, double* nzval);
+int32_t calipso_hip_sparse_kkt_group_mul(calipso_hip_sparse_kkt_group*, const double* v, double* out);
+int32_t calipso_hip_sparse_kkt_group_solve_symmetric(calipso_hip_sparse_kkt_group*, const double* residual, double* step);
+int32_t calipso_hip_sparse_kkt_group_search_direction(calipso_hip_sparse_kkt_group*, const double* residual, double* step, double* regularization, double* info,
+                                                      int32_t* status, double report[8]);
+int32_t calipso_hip_sparse_kkt_group_search_direction_device(calipso_hip_sparse_kkt_group*, const double* residual, double* step, double* regularization, double* info,
+                                                             int32_t* status, double report[8]);
+int32_t calipso_hip_sparse_kkt_group_timing(calipso_hip_sparse_kkt_group*, double ms[8]);
+
 /* ---- solve! on sparse problem data resident on the device (csrc/sparse_solve.hip; host pieces: csrc/sparse_solve.hpp) --------------------------------------
  * The vector half of a sparse solve! on the same handle, and the whole solve! (src/solver/solve.jl:8-377) for the problem class that needs no user code, the
  * sparse conic QP   min c x'Px + q'x  s.t.  Ax - b = 0,  h - Gx in K   in the handle's terms: Lxx = c (P + P'), gx = A, hx = -G (set_values), and three more

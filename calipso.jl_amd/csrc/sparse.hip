@@ -19,15 +19,22 @@
 #include <algorithm>
 #include <numeric>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "internal.hpp"
 #include "device_utils.hpp"
+#include "device_memory.hpp"               // the one owner of the plan's device memory
 #include "pivot16.hpp"
 #include "ldl_device.hpp"
 #include "sparse_plan.hpp"                 // the analyse phase and the records the kernels read: plain host C++
 
 using calipso::i64;
+using calipso::Grown;
+using calipso::device_fixed;
+using calipso::device_upload;
+using calipso::device_grown;
+using calipso::device_release;
 using namespace calipso::sparse_plan;
 static_assert(REFUSED_ARGUMENT == CALIPSO_ERR_ARGUMENT, "a refused pattern is an argument error");
 
@@ -140,15 +147,6 @@ __global__ __launch_bounds__(64) void k_sp_backward(SpDev d, int first, int ncol
         __syncthreads();
     }
 }
-__global__ void k_sp_permute_in(const double* __restrict__ b, const int* __restrict__ perm, int n, double* __restrict__ x) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) x[(size_t)blockIdx.y * n + i] = b[(size_t)blockIdx.y * n + perm[i]];          // permute!(x, perm)  qdldl.jl:333
-}
-__global__ void k_sp_permute_out(const double* __restrict__ x, const int* __restrict__ perm, int n, double* __restrict__ out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[(size_t)blockIdx.y * n + perm[i]] = x[(size_t)blockIdx.y * n + i];        // ipermute!(x, perm) qdldl.jl:349
-}
-
 
 // ---- multifrontal path (nested-dissection orders) ---------------------------------------------------------------------------------------------
 // The pieces of the dissection (leaf pieces of <= 48 vertices, separators) are the SUPERNODES: node s owns the contiguous columns
@@ -795,17 +793,19 @@ struct calipso_hip_sparse {
     int n = 0, device = 0;
     bool lds_acc = true;
     bool mf = false;                             // multifrontal numeric phase (plan.mf: nested-dissection orders whose fronts fit)
-    MfDev md{};
-    size_t cap_uvec = 0;
-    int batch = 1, selected = 0;                 // matrices of this pattern factored together / the one get_factor reads
-    double* wpart = nullptr;                     // partial products of the backward sweep: (column of the solve, node of the level, row block, 64)
-    size_t cap_wpart = 0;
-    std::vector<i64> inertia_all;                // batch x 3
-    std::vector<void*> dev;                      // every device allocation
+    MfDev md{};                                  // md and d hold COPIES of the pointers below: refresh_views() after anything grew
     SpDev d{};
-    int* d_perm = nullptr;
-    double *d_Aval = nullptr, *d_rhs = nullptr, *d_x = nullptr;
-    size_t cap_rhs = 0;
+    int batch = 1, selected = 0;                 // matrices of this pattern factored together / the one get_factor reads
+    std::vector<long long> inertia_all;          // batch x 3
+    std::vector<void*> dev;                      // every device allocation (device_memory.hpp): freed with the handle
+    std::vector<void*>& device_allocations() { return dev; }
+    hipStream_t device_stream() const { return stream; }
+    int device_error(const std::string& text) { err = text; return CALIPSO_ERR_HIP; }
+    Grown<double> Aval, Lx, D, panel, upd, fpool, wscr;      // what holds VALUES, for `batch` matrices, instance-major (alloc_values)
+    Grown<long long> inertia_dev;                // batch x 3: k_reference_inertia's
+    Grown<double> rhs, x, uvec;                  // a solve's right-hand sides, the permuted vectors and the update vectors of the sweeps (sparse_reserve_solve)
+    Grown<double> wpart;                         // partial products of the backward sweep: (column of the solve, node of the level, row block, 64)
+    const int* d_perm = nullptr;
     int work_slots = 0;
     hipStream_t stream = nullptr;
     bool owns_stream = true;      // false once a solver handle lent its own stream (sparse_borrow_stream): a stream per plan would only crowd the hardware queues
@@ -822,52 +822,30 @@ static thread_local std::string g_sparse_err;
 
 namespace {
 
-// (re)allocate everything that holds VALUES, for `batch` matrices of the analysed pattern: instance-major
+// the copies that the kernels' records hold of the handle's buffers: the one place that takes them, after anything was made or grew
+void refresh_views(calipso_hip_sparse* s) {
+    s->d.Aval = s->md.Aval = s->Aval.p; s->d.D = s->md.D = s->D.p; s->d.Lx = s->Lx.p;
+    s->md.panel = s->panel.p; s->md.upd = s->upd.p; s->md.fpool = s->fpool.p; s->md.wscr = s->wscr.p; s->md.uvec = s->uvec.p;
+}
+// everything that holds VALUES, made anew for `batch` matrices of the analysed pattern (the stream is idle): what a smaller batch no longer needs is given back, and
+// everything starts as zeros, filled on the plan's stream: of these only Aval is read before it is written (entries a structured handle never writes are structural zeros)
 int alloc_values(calipso_hip_sparse* s, int batch) {
     const size_t B = (size_t)batch;
-    const i64 nnzA = s->plan.nnzA;
-    for (double** pp : {&s->d_Aval, &s->d.Lx, &s->d.D, &s->md.panel, &s->md.upd, &s->md.fpool, &s->md.wscr}) if (*pp) { (void)hipFree(*pp); *pp = nullptr; }
-    PK(hipMalloc((void**)&s->d_Aval, sizeof(double) * B * std::max<size_t>((size_t)nnzA, 1)));
-    PK(hipMemset(s->d_Aval, 0, sizeof(double) * B * std::max<size_t>((size_t)nnzA, 1)));      // (entries a structured handle never writes are structural zeros)
-    PK(hipMalloc((void**)&s->d.D, sizeof(double) * B * (size_t)s->n));
-    if (s->mf) {
-        const MfPlan& M = *s->plan.mf;
-        PK(hipMalloc((void**)&s->md.panel, sizeof(double) * B * std::max<size_t>((size_t)M.panel_total, 1)));
-        PK(hipMalloc((void**)&s->md.upd, sizeof(double) * B * std::max<size_t>((size_t)M.upd_total, 1)));
-        if (M.pool_total) PK(hipMalloc((void**)&s->md.fpool, sizeof(double) * B * (size_t)M.pool_total));
-        if (M.wide_count) PK(hipMalloc((void**)&s->md.wscr, sizeof(double) * B * (size_t)M.wide_count * WF_SCR));
-        s->md.sPanel = M.panel_total; s->md.sUpd = M.upd_total; s->md.sPool = M.pool_total;
-    } else {
-        PK(hipMalloc((void**)&s->d.Lx, sizeof(double) * B * std::max<size_t>((size_t)s->plan.L.nnzL, 1)));
+    const MfPlan* M = s->mf ? &*s->plan.mf : nullptr;
+    const std::pair<Grown<double>*, size_t> each[7] = {{&s->Aval, std::max<size_t>((size_t)s->plan.nnzA, 1)}, {&s->D, (size_t)s->n}, {&s->Lx, M ? 0 : std::max<size_t>((size_t)s->plan.L.nnzL, 1)},
+        {&s->panel, M ? std::max<size_t>((size_t)M->panel_total, 1) : 0}, {&s->upd, M ? std::max<size_t>((size_t)M->upd_total, 1) : 0}, {&s->fpool, M ? (size_t)M->pool_total : 0},
+        {&s->wscr, M ? (size_t)M->wide_count * WF_SCR : 0}};
+    for (const auto& [b, per_matrix] : each) {
+        device_release(s, *b);
+        if (const int rc = device_grown(s, *b, B * per_matrix)) return rc;
     }
-    s->d.Aval = s->d_Aval;
-    s->md.Aval = s->d_Aval; s->md.D = s->d.D;
-    s->md.sA = nnzA; s->md.sD = s->n;
+    device_release(s, s->inertia_dev);
+    if (const int rc = device_grown(s, s->inertia_dev, 3 * B)) return rc;
+    if (M) { s->md.sPanel = M->panel_total; s->md.sUpd = M->upd_total; s->md.sPool = M->pool_total; }
+    s->md.sA = s->plan.nnzA; s->md.sD = s->n;
+    refresh_views(s);
     s->batch = batch; s->selected = 0; s->factored = false;
     s->inertia_all.assign(3 * B, 0);
-    return CALIPSO_OK;
-}
-
-template <typename T>
-int upload(calipso_hip_sparse* s, const std::vector<T>& h, const T** out) {
-    T* p = nullptr;
-    PK(hipMalloc((void**)&p, sizeof(T) * std::max<size_t>(h.size(), 1)));
-    s->dev.push_back(p);
-    if (!h.empty()) PK(hipMemcpy(p, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice));
-    *out = p;
-    return CALIPSO_OK;
-}
-
-// room for the partial products of the wide fronts' backward sweep, for `cols` columns per solve
-int mf_reserve_wide_solve(calipso_hip_sparse* s, size_t cols) {
-    if (!s->mf || !s->plan.mf->wide_count) return CALIPSO_OK;
-    const size_t need = cols * (size_t)s->plan.mf->wide_count * (size_t)s->plan.mf->wide_blocks * 64;
-    if (need > s->cap_wpart) {
-        if (s->wpart) (void)hipFree(s->wpart);
-        s->wpart = nullptr; s->cap_wpart = 0;
-        PK(hipMalloc((void**)&s->wpart, sizeof(double) * need));
-        s->cap_wpart = need;
-    }
     return CALIPSO_OK;
 }
 // the numeric factorisation of nz matrices (storage slots sl) on stream st: a launch per level of the tree (fronts beyond the LDS: three, sparse_wide.hpp)
@@ -880,13 +858,13 @@ void mf_enqueue_factor(calipso_hip_sparse* s, hipStream_t st, const MfSlots& sl,
 // both sweeps of a solve for ny = instances x nrhs columns of X (already permuted)
 void mf_enqueue_solve(calipso_hip_sparse* s, hipStream_t st, const MfSlots& sl, unsigned ny, int nrhs, double* X) {
     const MfPlan& M = *s->plan.mf;
-    const bool wide_ok = s->wpart && (size_t)ny * (size_t)M.wide_count * (size_t)M.wide_blocks * 64 <= s->cap_wpart;
+    const bool wide_ok = s->wpart.p && (size_t)ny * (size_t)M.wide_count * (size_t)M.wide_blocks * 64 <= s->wpart.cap;
     for (const MfSeg& g : M.levels) {
         if (g.wide.solve && wide_ok) mf_wide_forward(st, s->md, sl, g.wide, g.first, g.count, ny, s->n, nrhs, M.usum, X);
         else MF_LAUNCH_SOLVE(k_mf_forward, g, dim3((unsigned)g.count, ny), g.lds_solve, st, s->md, sl, g.first, s->n, nrhs, M.usum, X);
     }
     for (auto g = M.levels.rbegin(); g != M.levels.rend(); ++g) {
-        if (g->wide.solve && wide_ok) mf_wide_backward(st, s->md, sl, g->wide, g->first, g->count, ny, s->n, nrhs, X, s->wpart, M.wide_blocks);
+        if (g->wide.solve && wide_ok) mf_wide_backward(st, s->md, sl, g->wide, g->first, g->count, ny, s->n, nrhs, X, s->wpart.p, M.wide_blocks);
         else MF_LAUNCH_SOLVE(k_mf_backward, (*g), dim3((unsigned)g->count, ny), g->lds_solve, st, s->md, sl, g->first, s->n, nrhs, X);
     }
 }
@@ -953,33 +931,42 @@ __global__ __launch_bounds__(256) void k_count_signs(calipso::Batch bt, const do
     }
 }
 // compute_inertia! as calipso_hip_sparse_factorize reports it, on the device: the up-looking factorisation stops at the first exact zero pivot in elimination order,
-// the rest of D counts as zeros and inertia[0] = -1 (qdldl.jl:444,456,579).  One workgroup per matrix of `bt`; out[3 * slot ..]: integers, so no order of summation shows
-__global__ __launch_bounds__(256) void k_reference_inertia(calipso::Batch bt, const double* __restrict__ D, int n, long long* __restrict__ out) {
-    __shared__ int sh[3][4];
-    const int slot = bt.slot[blockIdx.z];
+// the rest of D counts as zeros and inertia[0] = -1 (qdldl.jl:444,456,579).  One workgroup per matrix of `sl` (a whole batch: slot = blockIdx.z); out[3 * slot ..]:
+// integers, so no order of summation shows.  It only reads D: both numeric phases.  Neither pass over D leaves early: a thread's loads do not wait for one another
+constexpr int IN_THREADS = 1024, IN_WAVES = IN_THREADS / 64;
+__global__ __launch_bounds__(IN_THREADS) void k_reference_inertia(const MfSlots sl, const double* __restrict__ D, int n, long long* __restrict__ out) {
+    __shared__ int sh[3][IN_WAVES];
+    const int slot = sl.use ? sl.slot[blockIdx.z] : (int)blockIdx.z, wave = threadIdx.x >> 6;
     const double* Dz = D + (size_t)slot * n;
     int first = n;
-    for (int i = threadIdx.x; i < n; i += 256) if (Dz[i] == 0.0) { first = i; break; }      // (a thread's indices ascend)
+    for (int i = threadIdx.x; i < n; i += IN_THREADS) first = min(first, Dz[i] == 0.0 ? i : n);
     for (int o = 32; o > 0; o >>= 1) first = min(first, __shfl_xor(first, o));
-    if ((threadIdx.x & 63) == 0) sh[0][threadIdx.x >> 6] = first;
+    if ((threadIdx.x & 63) == 0) sh[0][wave] = first;
     __syncthreads();
-    first = min(min(sh[0][0], sh[0][1]), min(sh[0][2], sh[0][3]));
-    __syncthreads();
+    for (int w = 0; w < IN_WAVES; ++w) first = min(first, sh[0][w]);
     int pos = 0, nonpos = 0;
-    for (int i = threadIdx.x; i < first; i += 256) { const double v = Dz[i]; pos += v > 0.0; nonpos += v <= 0.0; }
+    for (int i = threadIdx.x; i < first; i += IN_THREADS) { const double v = Dz[i]; pos += v > 0.0; nonpos += v <= 0.0; }
     pos = calipso::wave_sum_i(pos); nonpos = calipso::wave_sum_i(nonpos);
-    if ((threadIdx.x & 63) == 0) { sh[1][threadIdx.x >> 6] = pos; sh[2][threadIdx.x >> 6] = nonpos; }
+    if ((threadIdx.x & 63) == 0) { sh[1][wave] = pos; sh[2][wave] = nonpos; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        long long p = sh[1][0] + sh[1][1] + sh[1][2] + sh[1][3], q = sh[2][0] + sh[2][1] + sh[2][2] + sh[2][3], z = 0;
+        long long p = 0, q = 0, z = 0;
+        for (int w = 0; w < IN_WAVES; ++w) { p += sh[1][w]; q += sh[2][w]; }
         if (first < n) { z = n - first; q += n - first; p = -1; }
         out[3 * (size_t)slot] = p; out[3 * (size_t)slot + 1] = q; out[3 * (size_t)slot + 2] = z;
     }
 }
+// the storage slots of the matrices of `bt` as the kernels take them — or false: not 1 .. batch matrices, a slot outside 0 .. batch - 1
+bool slots_of(const calipso_hip_sparse* sp, const calipso::Batch& bt, MfSlots* sl) {
+    if (bt.n < 1 || bt.n > sp->batch || bt.n > calipso::MAX_BATCH) return false;
+    *sl = MfSlots{};
+    sl->use = 1;
+    for (int k = 0; k < bt.n; ++k) { if (bt.slot[k] < 0 || bt.slot[k] >= sp->batch) return false; sl->slot[k] = bt.slot[k]; }
+    return true;
+}
 }  // namespace
 
 namespace calipso {
-int sparse_reserve_solve(calipso_hip_sparse* s, int batch);
 bool sparse_is_multifrontal(const calipso_hip_sparse* sp) { return sp && sp->mf; }
 // a plan owned by a solver handle is only ever driven on that handle's stream: give the plan's own stream back
 void sparse_borrow_stream(calipso_hip_sparse* sp, hipStream_t st) {
@@ -990,39 +977,34 @@ void sparse_borrow_stream(calipso_hip_sparse* sp, hipStream_t st) {
 int sparse_batch(const calipso_hip_sparse* sp) { return sp ? sp->batch : 0; }
 // the stream every call of the plan enqueues on: a handle that owns a plan (sparse_kkt.hip) orders its own kernels with it
 hipStream_t sparse_stream(const calipso_hip_sparse* sp) { return sp ? sp->stream : nullptr; }
+void sparse_values(calipso_hip_sparse* sp, double** values, long long* stride) { *values = sp ? sp->Aval.p : nullptr; *stride = sp ? (long long)sp->plan.nnzA : 0; }
 // gather the pattern's entries from the dense S of every instance of `bt`, factor, add the pivot signs to the instances' counters
-void sparse_values(calipso_hip_sparse* sp, double** values, long long* stride) { *values = sp ? sp->d_Aval : nullptr; *stride = sp ? (long long)sp->plan.nnzA : 0; }
 // values_in_place: the caller has written the pattern's entries into sparse_values() itself (structured handles: blocks.hip) — no gather
 int sparse_factor_from_dense(calipso_hip_sparse* sp, hipStream_t st, const Batch& bt, const double* S, const long long* src, int* icount, bool values_in_place) {
-    if (!sp || !sp->mf || bt.n > sp->batch) return CALIPSO_ERR_ARGUMENT;
-    for (int k = 0; k < bt.n; ++k) if (bt.slot[k] >= sp->batch) return CALIPSO_ERR_ARGUMENT;
+    MfSlots sl;
+    if (!sp || !sp->mf || !slots_of(sp, bt, &sl)) return CALIPSO_ERR_ARGUMENT;
     const unsigned nz = (unsigned)bt.n;
-    if (!values_in_place) hipLaunchKernelGGL(k_gather_dense, dim3((unsigned)((sp->plan.nnzA + 255) / 256), 1, nz), dim3(256), 0, st, bt, S, src, (long long)sp->plan.nnzA, sp->d_Aval);
-    MfSlots sl{};
-    sl.use = 1;
-    for (int k = 0; k < bt.n; ++k) sl.slot[k] = bt.slot[k];
+    if (!values_in_place) hipLaunchKernelGGL(k_gather_dense, dim3((unsigned)((sp->plan.nnzA + 255) / 256), 1, nz), dim3(256), 0, st, bt, S, src, (long long)sp->plan.nnzA, sp->Aval.p);
     mf_enqueue_factor(sp, st, sl, nz);
-    if (icount) hipLaunchKernelGGL(k_count_signs, dim3(1, 1, nz), dim3(256), 0, st, bt, sp->d.D, sp->n, icount);      // (NULL: the caller counts by sparse_inertia_enqueue)
+    if (icount) hipLaunchKernelGGL(k_count_signs, dim3(1, 1, nz), dim3(256), 0, st, bt, sp->D.p, sp->n, icount);      // (NULL: the caller counts by sparse_inertia_enqueue)
     sp->factored = true;
     return CALIPSO_OK;
 }
 // the reference's inertia of the factors of the matrices of `bt` into out[3 * slot ..] (device, batch x 3), in stream order: what calipso_hip_sparse_factorize returns
 int sparse_inertia_enqueue(calipso_hip_sparse* sp, hipStream_t st, const Batch& bt, long long* out) {
-    if (!sp || !sp->mf || !out || bt.n < 1 || bt.n > sp->batch) return CALIPSO_ERR_ARGUMENT;
-    for (int k = 0; k < bt.n; ++k) if (bt.slot[k] < 0 || bt.slot[k] >= sp->batch) return CALIPSO_ERR_ARGUMENT;
-    hipLaunchKernelGGL(k_reference_inertia, dim3(1, 1, (unsigned)bt.n), dim3(256), 0, st, bt, sp->d.D, sp->n, out);
+    MfSlots sl;
+    if (!sp || !sp->mf || !out || !slots_of(sp, bt, &sl)) return CALIPSO_ERR_ARGUMENT;
+    hipLaunchKernelGGL(k_reference_inertia, dim3(1, 1, (unsigned)bt.n), dim3(IN_THREADS), 0, st, sl, sp->D.p, sp->n, out);
     return CALIPSO_OK;
 }
 // x <- S^-1 x for the first n entries of every instance's x (a slab buffer)
 int sparse_solve_inplace(calipso_hip_sparse* sp, hipStream_t st, const Batch& bt, double* x) {
-    if (!sp || !sp->mf || bt.n > sp->batch) return CALIPSO_ERR_ARGUMENT;
+    MfSlots sl;
+    if (!sp || !sp->mf || !slots_of(sp, bt, &sl)) return CALIPSO_ERR_ARGUMENT;
     const unsigned nz = (unsigned)bt.n, gx = (unsigned)((sp->n + 255) / 256);
-    MfSlots sl{};
-    sl.use = 1;
-    for (int k = 0; k < bt.n; ++k) { if (bt.slot[k] >= sp->batch) return CALIPSO_ERR_ARGUMENT; sl.slot[k] = bt.slot[k]; }
-    hipLaunchKernelGGL(k_permute_in_slab, dim3(gx, 1, nz), dim3(256), 0, st, bt, x, sp->d_perm, sp->n, sp->d_x);
-    mf_enqueue_solve(sp, st, sl, nz, 1, sp->d_x);
-    hipLaunchKernelGGL(k_permute_out_slab, dim3(gx, 1, nz), dim3(256), 0, st, bt, sp->d_x, sp->d_perm, sp->n, x);
+    hipLaunchKernelGGL(k_permute_in_slab, dim3(gx, 1, nz), dim3(256), 0, st, bt, x, sp->d_perm, sp->n, sp->x.p);
+    mf_enqueue_solve(sp, st, sl, nz, 1, sp->x.p);
+    hipLaunchKernelGGL(k_permute_out_slab, dim3(gx, 1, nz), dim3(256), 0, st, bt, sp->x.p, sp->d_perm, sp->n, x);
     return CALIPSO_OK;
 }
 // X (ld x p, column-major, in the slab of the single instance `slot`) <- S^-1 X: all p right-hand sides through the tree in the same launches
@@ -1035,36 +1017,27 @@ int sparse_solve_inplace_multi(calipso_hip_sparse* s, hipStream_t st, int slot, 
     // every column of the launch belongs to the same factor: with nrhs = p the kernels take slot[blockIdx.y / p] = slot[0]
     sl.slot[0] = slot;
     const unsigned gx = (unsigned)((s->n + 255) / 256), ny = (unsigned)p;
-    hipLaunchKernelGGL(k_permute_in_cols, dim3(gx, ny), dim3(256), 0, st, X, ld, s->d_perm, s->n, s->d_x);
-    mf_enqueue_solve(s, st, sl, ny, p, s->d_x);
-    hipLaunchKernelGGL(k_permute_out_cols, dim3(gx, ny), dim3(256), 0, st, s->d_x, s->d_perm, s->n, X, ld);
+    hipLaunchKernelGGL(k_permute_in_cols, dim3(gx, ny), dim3(256), 0, st, X, ld, s->d_perm, s->n, s->x.p);
+    mf_enqueue_solve(s, st, sl, ny, p, s->x.p);
+    hipLaunchKernelGGL(k_permute_out_cols, dim3(gx, ny), dim3(256), 0, st, s->x.p, s->d_perm, s->n, X, ld);
     return CALIPSO_OK;
 }
-// buffers for in-place solves of `batch` instances with one right-hand side each (sparse_solve_inplace allocates nothing)
-int sparse_reserve_solve(calipso_hip_sparse* s, int batch) {
+// buffers for solves of `cols` columns in all (instances x right-hand sides): afterwards a solve of that many allocates nothing
+int sparse_reserve_solve(calipso_hip_sparse* s, int cols) {
     PK(hipSetDevice(s->device));
-    const size_t need = (size_t)s->n * (size_t)batch;
-    if (need > s->cap_rhs) {
-        if (s->d_rhs) (void)hipFree(s->d_rhs);
-        if (s->d_x) (void)hipFree(s->d_x);
-        s->d_rhs = s->d_x = nullptr; s->cap_rhs = 0;
-        PK(hipMalloc((void**)&s->d_rhs, sizeof(double) * need)); PK(hipMalloc((void**)&s->d_x, sizeof(double) * need));
-        s->cap_rhs = need;
-    }
-    const size_t need_u = (size_t)std::max<long long>(s->mf ? s->plan.mf->usum : 0, 1) * (size_t)batch;
-    if (need_u > s->cap_uvec) {
-        if (s->md.uvec) (void)hipFree(s->md.uvec);
-        s->md.uvec = nullptr; s->cap_uvec = 0;
-        PK(hipMalloc((void**)&s->md.uvec, sizeof(double) * need_u));
-        s->cap_uvec = need_u;
-    }
-    return mf_reserve_wide_solve(s, (size_t)batch);
+    const size_t C = (size_t)cols;
+    const MfPlan* M = s->mf ? &*s->plan.mf : nullptr;
+    int rc;
+    if ((rc = device_grown(s, s->rhs, (size_t)s->n * C)) || (rc = device_grown(s, s->x, (size_t)s->n * C)) ||
+        (rc = device_grown(s, s->uvec, M ? (size_t)std::max<long long>(M->usum, 1) * C : 0)) ||
+        (rc = device_grown(s, s->wpart, M ? C * (size_t)M->wide_count * (size_t)M->wide_blocks * 64 : 0))) return rc;
+    refresh_views(s);
+    return CALIPSO_OK;
 }
 void sparse_work(const calipso_hip_sparse* sp, double out[3]) { out[0] = (double)sp->plan.R.flops; out[1] = (double)sp->plan.L.nnzL; out[2] = (double)sp->n; }
 void sparse_describe(const calipso_hip_sparse* sp, int64_t out[4]) { out[0] = sp->plan.levels(); out[1] = sp->mf ? sp->plan.mf->max_front : 0; out[2] = sp->plan.A.nnzU; out[3] = sp->mf ? 2 : (sp->lds_acc ? 1 : 0); }
 }  // namespace calipso
 
-// (tests / A-B timing) how plans made AFTERWARDS treat fronts beyond the LDS: 1 = many workgroups per front (default), 0 = one; returns the old value
 // (tests / A-B timing) how plans made AFTERWARDS treat fronts beyond the LDS: 1 = many workgroups per front (default), 0 = one; returns the old value
 // (tests / A-B timing) whether plans made AFTERWARDS carry the extend-add items of the LDS fronts (1, default) or assemble child by child, row by row (0); returns the old value
 extern "C" int32_t calipso_hip_debug_mf_items(int32_t on) { const int was = g_mf_items; if (on >= 0) g_mf_items = on != 0; return was; }
@@ -1096,11 +1069,6 @@ int32_t calipso_hip_sparse_destroy(calipso_hip_sparse* s) {
     if (s->stream && s->owns_stream) (void)hipStreamSynchronize(s->stream);
     if (s->graph_factor) (void)hipGraphExecDestroy(s->graph_factor);
     for (void* p : s->dev) if (p) (void)hipFree(p);
-    for (double* p : {s->d_Aval, s->d.Lx, s->d.D, s->md.panel, s->md.upd, s->md.fpool, s->md.wscr}) if (p) (void)hipFree(p);
-    if (s->d_rhs) (void)hipFree(s->d_rhs);
-    if (s->d_x) (void)hipFree(s->d_x);
-    if (s->md.uvec) (void)hipFree(s->md.uvec);
-    if (s->wpart) (void)hipFree(s->wpart);
     if (s->e0) (void)hipEventDestroy(s->e0);
     if (s->e1) (void)hipEventDestroy(s->e1);
     if (s->stream && s->owns_stream) (void)hipStreamDestroy(s->stream);
@@ -1167,24 +1135,22 @@ static int32_t sparse_create_impl(int64_t n, const int64_t* colptr, const int64_
     int rc;
     std::vector<int> hperm((size_t)n);
     for (i64 k = 0; k < n; ++k) hperm[(size_t)k] = (int)(P.perm[(size_t)k] - 1);
-    const int* cperm = nullptr;
-    if ((rc = upload(s, P.cols.order, &s->d.order)) || (rc = upload(s, P.A.Alp, &s->d.Alp)) || (rc = upload(s, P.A.Ali, &s->d.Ali)) || (rc = upload(s, P.A.Asrc, &s->d.Asrc)) ||
-        (rc = upload(s, P.L.Lp, &s->d.Lp)) || (rc = upload(s, P.L.Li, &s->d.Li)) || (rc = upload(s, P.R.Rp, &s->d.Rp)) || (rc = upload(s, P.R.Rk, &s->d.Rk)) ||
-        (rc = upload(s, P.R.Rpos, &s->d.Rpos)) || (rc = upload(s, P.R.Rend, &s->d.Rend)) || (rc = upload(s, hperm, &cperm))) return rc;
-    s->d_perm = const_cast<int*>(cperm);
+    if ((rc = device_upload(s, P.cols.order, &s->d.order)) || (rc = device_upload(s, P.A.Alp, &s->d.Alp)) || (rc = device_upload(s, P.A.Ali, &s->d.Ali)) || (rc = device_upload(s, P.A.Asrc, &s->d.Asrc)) ||
+        (rc = device_upload(s, P.L.Lp, &s->d.Lp)) || (rc = device_upload(s, P.L.Li, &s->d.Li)) || (rc = device_upload(s, P.R.Rp, &s->d.Rp)) || (rc = device_upload(s, P.R.Rk, &s->d.Rk)) ||
+        (rc = device_upload(s, P.R.Rpos, &s->d.Rpos)) || (rc = device_upload(s, P.R.Rend, &s->d.Rend)) || (rc = device_upload(s, hperm, &s->d_perm))) return rc;
     if ((rc = alloc_values(s, 1))) return rc;
     if (s->mf) {
         const MfPlan& M = *P.mf;
         MfDev& md = s->md;
         md.nnodes = M.nnodes;
-        if ((rc = upload(s, M.order, &md.order)) || (rc = upload(s, M.first, &md.nfirst)) || (rc = upload(s, M.cols, &md.ncols)) || (rc = upload(s, M.rows, &md.nrows)) ||
-            (rc = upload(s, M.rowptr, &md.rowptr)) || (rc = upload(s, M.rowsv, &md.rows)) || (rc = upload(s, M.rel, &md.rel)) || (rc = upload(s, M.childptr, &md.childptr)) ||
-            (rc = upload(s, M.children, &md.children)) || (rc = upload(s, M.panel_off, &md.panel_off)) || (rc = upload(s, M.upd_off, &md.upd_off)) ||
-            (rc = upload(s, M.u_off, &md.u_off)) || (rc = upload(s, M.Aloc, &md.Aloc)) || (rc = upload(s, M.foff, &md.foff))) return rc;
+        if ((rc = device_upload(s, M.order, &md.order)) || (rc = device_upload(s, M.first, &md.nfirst)) || (rc = device_upload(s, M.cols, &md.ncols)) || (rc = device_upload(s, M.rows, &md.nrows)) ||
+            (rc = device_upload(s, M.rowptr, &md.rowptr)) || (rc = device_upload(s, M.rowsv, &md.rows)) || (rc = device_upload(s, M.rel, &md.rel)) || (rc = device_upload(s, M.childptr, &md.childptr)) ||
+            (rc = device_upload(s, M.children, &md.children)) || (rc = device_upload(s, M.panel_off, &md.panel_off)) || (rc = device_upload(s, M.upd_off, &md.upd_off)) ||
+            (rc = device_upload(s, M.u_off, &md.u_off)) || (rc = device_upload(s, M.Aloc, &md.Aloc)) || (rc = device_upload(s, M.foff, &md.foff))) return rc;
         md.xit = nullptr;
-        if ((rc = upload(s, M.nrec, &md.nrec)) || (rc = upload(s, M.crec, &md.crec)) || (!M.xit.empty() && (rc = upload(s, M.xit, &md.xit)))) return rc;
-        if (M.wide_count && ((rc = upload(s, M.wptrE, &md.wptrE)) || (rc = upload(s, M.wptrC, &md.wptrC)) || (rc = upload(s, M.wEcol, &md.wEcol)) ||
-                             (rc = upload(s, M.wEsrc, &md.wEsrc)) || (rc = upload(s, M.wC, &md.wC)))) return rc;
+        if ((rc = device_upload(s, M.nrec, &md.nrec)) || (rc = device_upload(s, M.crec, &md.crec)) || (!M.xit.empty() && (rc = device_upload(s, M.xit, &md.xit)))) return rc;
+        if (M.wide_count && ((rc = device_upload(s, M.wptrE, &md.wptrE)) || (rc = device_upload(s, M.wptrC, &md.wptrC)) || (rc = device_upload(s, M.wEcol, &md.wEcol)) ||
+                             (rc = device_upload(s, M.wEsrc, &md.wEsrc)) || (rc = device_upload(s, M.wC, &md.wC)))) return rc;
         for (const MfSeg& g : M.levels) if (g.wide.on && !mf_wide_prepare(&s->err)) return CALIPSO_ERR_HIP;
         md.Alp = s->d.Alp; md.Asrc = s->d.Asrc;
         for (const void* fn : {(const void*)k_mf_factor<256, false>, (const void*)k_mf_factor<512, false>, (const void*)k_mf_forward<256, false>,
@@ -1196,7 +1162,7 @@ static int32_t sparse_create_impl(int64_t n, const int64_t* colptr, const int64_
         PK(hipFuncSetAttribute((const void*)k_sp_factor<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * SP_LDS_MAX_N)));
     } else {
         s->work_slots = std::min(s->work_slots, 512);
-        PK(hipMalloc((void**)&s->d.work, sizeof(double) * (size_t)s->work_slots * (size_t)n)); s->dev.push_back(s->d.work);
+        if ((rc = device_fixed(s, &s->d.work, (size_t)s->work_slots * (size_t)n))) return rc;
     }
     return CALIPSO_OK;
 }
@@ -1235,7 +1201,7 @@ static int32_t sparse_factorize(calipso_hip_sparse* s, const double* nzval, int6
     if (!s || (!nzval && s->plan.nnzA > 0)) return CALIPSO_ERR_ARGUMENT;
     PK(hipSetDevice(s->device));
     const size_t B = (size_t)s->batch;
-    if (s->plan.nnzA) PK(hipMemcpyAsync(s->d_Aval, nzval, sizeof(double) * B * (size_t)s->plan.nnzA, kind, s->stream));
+    if (s->plan.nnzA) PK(hipMemcpyAsync(s->Aval.p, nzval, sizeof(double) * B * (size_t)s->plan.nnzA, kind, s->stream));
     PK(hipEventRecord(s->e0, s->stream));
     if (!s->graph_tried) {          // the level schedule is a fixed launch sequence with fixed arguments: captured once, replayed afterwards
         s->graph_tried = true;
@@ -1252,21 +1218,13 @@ static int32_t sparse_factorize(calipso_hip_sparse* s, const double* nzval, int6
     if (s->graph_factor) PK(hipGraphLaunch(s->graph_factor, s->stream));
     else enqueue_factor(s);
     PK(hipEventRecord(s->e1, s->stream));
-    std::vector<double> D(B * (size_t)s->n);
-    PK(hipMemcpyAsync(D.data(), s->d.D, sizeof(double) * D.size(), hipMemcpyDeviceToHost, s->stream));
+    hipLaunchKernelGGL(k_reference_inertia, dim3(1, 1, (unsigned)B), dim3(IN_THREADS), 0, s->stream, MfSlots{}, s->D.p, s->n, s->inertia_dev.p);      // compute_inertia! as the reference sees it
+    PK(hipMemcpyAsync(s->inertia_all.data(), s->inertia_dev.p, sizeof(long long) * 3 * B, hipMemcpyDeviceToHost, s->stream));
     PK(hipStreamSynchronize(s->stream));
     PK(hipGetLastError());
     float ms = 0.f; PK(hipEventElapsedTime(&ms, s->e0, s->e1)); s->ms_factor = ms;
-    // compute_inertia! as the reference sees it: the up-looking factorisation stops at the first exact zero pivot in elimination order and the
-    // rest of D stays at the zeros it was reset to (qdldl.jl:444,456,579)
     int rc = CALIPSO_OK;
-    for (size_t z = 0; z < B; ++z) {
-        const double* Dz = D.data() + z * (size_t)s->n;
-        i64 pos = 0, nonpos = 0, zero = 0; int k = 0;
-        for (; k < s->n; ++k) { const double dk = Dz[k]; if (dk == 0.0) break; pos += dk > 0.0; nonpos += dk <= 0.0; }
-        if (k < s->n) { zero = s->n - k; nonpos += s->n - k; pos = -1; rc = CALIPSO_WARN_ZERO_PIVOT; }
-        s->inertia_all[3 * z] = pos; s->inertia_all[3 * z + 1] = nonpos; s->inertia_all[3 * z + 2] = zero;
-    }
+    for (size_t z = 0; z < B; ++z) if (s->inertia_all[3 * z + 2] > 0) rc = CALIPSO_WARN_ZERO_PIVOT;
     s->factored = true;
     if (inertia) std::copy(s->inertia_all.begin(), s->inertia_all.end(), inertia);
     return rc;
@@ -1283,41 +1241,27 @@ static int32_t sparse_solve(calipso_hip_sparse* s, int64_t nrhs, const double* b
     PK(hipSetDevice(s->device));
     const size_t cols = (size_t)nrhs * (size_t)s->batch;
     const size_t need = (size_t)s->n * cols;
-    if (need > s->cap_rhs) {
-        if (s->d_rhs) (void)hipFree(s->d_rhs);
-        if (s->d_x) (void)hipFree(s->d_x);
-        s->d_rhs = s->d_x = nullptr; s->cap_rhs = 0;
-        PK(hipMalloc((void**)&s->d_rhs, sizeof(double) * need)); PK(hipMalloc((void**)&s->d_x, sizeof(double) * need));
-        s->cap_rhs = need;
-    }
-    PK(hipMemcpyAsync(s->d_rhs, b, sizeof(double) * need, kin, s->stream));
+    if (const int rrc = calipso::sparse_reserve_solve(s, (int)cols)) return rrc;
+    PK(hipMemcpyAsync(s->rhs.p, b, sizeof(double) * need, kin, s->stream));
     PK(hipEventRecord(s->e0, s->stream));
     const unsigned gx = (unsigned)((s->n + 255) / 256), ny = (unsigned)cols;
-    hipLaunchKernelGGL(k_sp_permute_in, dim3(gx, ny), dim3(256), 0, s->stream, s->d_rhs, s->d_perm, s->n, s->d_x);
+    hipLaunchKernelGGL(k_permute_in_cols, dim3(gx, ny), dim3(256), 0, s->stream, s->rhs.p, (long long)s->n, s->d_perm, s->n, s->x.p);          // permute!(x, perm)  qdldl.jl:333
     if (s->mf) {
-        const size_t need_u = (size_t)std::max<long long>(s->plan.mf->usum, 1) * cols;
-        if (need_u > s->cap_uvec) {
-            if (s->md.uvec) (void)hipFree(s->md.uvec);
-            s->md.uvec = nullptr; s->cap_uvec = 0;
-            PK(hipMalloc((void**)&s->md.uvec, sizeof(double) * need_u));
-            s->cap_uvec = need_u;
-        }
-        { const int wrc = mf_reserve_wide_solve(s, cols); if (wrc) return wrc; }
-        mf_enqueue_solve(s, s->stream, MfSlots{}, ny, (int)nrhs, s->d_x);
+        mf_enqueue_solve(s, s->stream, MfSlots{}, ny, (int)nrhs, s->x.p);
     } else {
         for (int z = 0; z < s->batch; ++z) {
             SpDev d = s->d;
             d.Lx += (size_t)z * (size_t)s->plan.L.nnzL; d.D += (size_t)z * (size_t)s->n;
-            double* xz = s->d_x + (size_t)z * (size_t)nrhs * (size_t)s->n;
+            double* xz = s->x.p + (size_t)z * (size_t)nrhs * (size_t)s->n;
             for (const Segment& g : s->plan.cols.plan)
                 hipLaunchKernelGGL(k_sp_forward, dim3(g.chain ? 1 : (unsigned)std::min(g.count, 4096), (unsigned)nrhs), dim3(64), 0, s->stream, d, g.first, g.count, xz);
             for (auto g = s->plan.cols.plan.rbegin(); g != s->plan.cols.plan.rend(); ++g)
                 hipLaunchKernelGGL(k_sp_backward, dim3(g->chain ? 1 : (unsigned)std::min(g->count, 4096), (unsigned)nrhs), dim3(64), 0, s->stream, d, g->first, g->count, xz);
         }
     }
-    hipLaunchKernelGGL(k_sp_permute_out, dim3(gx, ny), dim3(256), 0, s->stream, s->d_x, s->d_perm, s->n, s->d_rhs);
+    hipLaunchKernelGGL(k_permute_out_cols, dim3(gx, ny), dim3(256), 0, s->stream, s->x.p, s->d_perm, s->n, s->rhs.p, (long long)s->n);         // ipermute!(x, perm) qdldl.jl:349
     PK(hipEventRecord(s->e1, s->stream));
-    PK(hipMemcpyAsync(x, s->d_rhs, sizeof(double) * need, kout, s->stream));
+    PK(hipMemcpyAsync(x, s->rhs.p, sizeof(double) * need, kout, s->stream));
     PK(hipStreamSynchronize(s->stream));
     PK(hipGetLastError());
     float ms = 0.f; PK(hipEventElapsedTime(&ms, s->e0, s->e1)); s->ms_solve = ms;
@@ -1342,7 +1286,7 @@ int32_t calipso_hip_sparse_get_factor(calipso_hip_sparse* s, int64_t* perm, int6
         // multifrontal storage: dense m x c panels per node; pick the entries of the exact pattern out of them
         const MfPlan& M = *s->plan.mf;
         std::vector<double> panel((size_t)M.panel_total);
-        PK(hipMemcpyAsync(panel.data(), s->md.panel + (size_t)s->selected * (size_t)M.panel_total, sizeof(double) * panel.size(), hipMemcpyDeviceToHost, s->stream));
+        PK(hipMemcpyAsync(panel.data(), s->panel.p + (size_t)s->selected * (size_t)M.panel_total, sizeof(double) * panel.size(), hipMemcpyDeviceToHost, s->stream));
         PK(hipStreamSynchronize(s->stream));
         for (int t = 0; t < M.nnodes; ++t) {
             const int f = M.first[(size_t)t], c = M.cols[(size_t)t], m = c + M.rows[(size_t)t];
@@ -1356,8 +1300,8 @@ int32_t calipso_hip_sparse_get_factor(calipso_hip_sparse* s, int64_t* perm, int6
                 }
         }
     } else
-    if (Lx && nnzL) PK(hipMemcpyAsync(Lx, s->d.Lx + (size_t)s->selected * nnzL, sizeof(double) * nnzL, hipMemcpyDeviceToHost, s->stream));
-    if (D) PK(hipMemcpyAsync(D, s->d.D + (size_t)s->selected * (size_t)s->n, sizeof(double) * (size_t)s->n, hipMemcpyDeviceToHost, s->stream));
+    if (Lx && nnzL) PK(hipMemcpyAsync(Lx, s->Lx.p + (size_t)s->selected * nnzL, sizeof(double) * nnzL, hipMemcpyDeviceToHost, s->stream));
+    if (D) PK(hipMemcpyAsync(D, s->D.p + (size_t)s->selected * (size_t)s->n, sizeof(double) * (size_t)s->n, hipMemcpyDeviceToHost, s->stream));
     PK(hipStreamSynchronize(s->stream));
     return CALIPSO_OK;
 }

@@ -1,12 +1,13 @@
 // sparse_kkt_handle.hpp — the handle behind calipso_hip_sparse_kkt_* as the translation units that work on it see it: sparse_kkt.hip (search_direction!),
 // sparse_solve.hip (the vector half of solve! and its driver), sparse_differentiate.hip (differentiate!) and sparse_krylov.hip.  What every kernel reads (KktDev), the
-// handle itself, the one owner of its device memory (device_fixed, device_grown), the first lines of every entry (enter) and what the units call of each other.
+// handle itself, the first lines of every entry (enter) and what the units call of each other.
 #pragma once
 #include <algorithm>
 #include <string>
 #include <vector>
 
 #include "internal.hpp"
+#include "device_memory.hpp"               // the one owner of the handle's device memory: device_fixed, device_upload, device_grown
 #include "sparse_kkt.hpp"                  // the analysis: plain host C++
 #include "sparse_krylov.hpp"               // the `H \ residual` fallback's options, workspace layout and Hessenberg cycle: plain host C++
 
@@ -40,8 +41,10 @@ struct ParamDev {
     const double* val[3];
     const int* long_columns;
 };
-// a buffer of the handle that grows on demand, is never shrunk and is kept (device_grown below): a call that repeats its shapes allocates nothing
-template <typename T> struct Grown { T* p = nullptr; size_t cap = 0; };      // cap: entries
+using calipso::Grown;                             // device_memory.hpp: a buffer that grows on demand, is never shrunk and is kept
+using calipso::device_fixed;
+using calipso::device_upload;
+using calipso::device_grown;
 
 // set_parameter_patterns (sparse_solve.hip) fills it; set_evaluator and qp_attach drop it
 struct ParameterPatterns {
@@ -71,6 +74,9 @@ struct calipso_hip_sparse_kkt {
     double *Lxx = nullptr, *gx = nullptr, *hx = nullptr, *w = nullptr, *rho = nullptr, *K = nullptr;
     double *res = nullptr, *step = nullptr, *corr = nullptr, *err = nullptr, *rsym = nullptr, *dsym = nullptr, *norm = nullptr;
     std::vector<void*> dev;                    // every device allocation of the handle (device_fixed, device_grown): freed with it
+    std::vector<void*>& device_allocations() { return dev; }                                  // what device_memory.hpp asks of a handle
+    hipStream_t device_stream() const { return st; }
+    int device_error(const std::string& text) { err_text = text; return CALIPSO_ERR_HIP; }
     bool have[5] = {false, false, false, false, false};      // Lxx, gx, hx, w, penalty resident
     bool assembled = false, factored = false;
     hipEvent_t ev[2] = {nullptr, nullptr};
@@ -113,36 +119,6 @@ int enter(KH* s, const char* entry, Need need);
 #define ENTER(need) do { const int rc__ = enter(s, entry, need); if (rc__ < 0) return rc__; } while (0)      // (`entry`: the entry's name)
 // in the one body of a host / _device pair of entries (`device`: which of the two)
 #define DEVPTR(p) do { if (device) { const int rc__ = device_pointer(s, (const void*)(p), entry, #p); if (rc__ < 0) return rc__; } } while (0)
-
-// ---- the handle's device memory.  Two ways to own it, both on the handle's list and freed with it, both zero-filled on the HANDLE'S stream: a fill on the null
-// stream would not be ordered with what follows, the stream being non-blocking ------------------------------------------------------------------------------------
-// a fixed allocation: made once
-template <typename T> int device_fixed(KH* s, T** out, size_t count) {
-    count = std::max<size_t>(count, 1);
-    KK(hipMalloc((void**)out, sizeof(T) * count));
-    s->dev.push_back(*out);
-    KK(hipMemsetAsync(*out, 0, sizeof(T) * count, s->st));
-    return CALIPSO_OK;
-}
-// ... and one that holds a host vector's entries
-template <typename T> int device_upload(KH* s, const std::vector<T>& h, const T** out) {
-    T* p = nullptr;
-    const int rc = device_fixed(s, &p, h.size());
-    if (rc < 0) return rc;
-    if (!h.empty()) KK(hipMemcpyAsync(p, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice, s->st));
-    KK(hipStreamSynchronize(s->st));                         // (the vector may be the caller's local)
-    *out = p;
-    return CALIPSO_OK;
-}
-// a grown buffer: larger only when asked for more than it has; nothing in flight reads the one that is freed
-template <typename T> int device_grown(KH* s, Grown<T>& b, size_t want) {
-    if (want <= b.cap) return CALIPSO_OK;
-    KK(hipStreamSynchronize(s->st));
-    if (b.p) { (void)hipFree(b.p); s->dev.erase(std::find(s->dev.begin(), s->dev.end(), (void*)b.p)); b = Grown<T>(); }
-    const int rc = device_fixed(s, &b.p, want);
-    if (rc >= 0) b.cap = want;
-    return rc;
-}
 
 // sparse_solve.hip, for sparse_kkt.hip
 int solve_state(KH* s);                                                                                     // the resident vectors of solve!: made by the first entry that needs them

@@ -650,3 +650,141 @@ def test_assembly_through_extend_add_items_has_the_bits_of_the_row_wise_assembly
     assert np.abs(out[1][2] - ref["D"]).max() <= 1e-11 * np.abs(ref["D"]).max()
     assert abs(out[1][1] - ref["L"]).max() <= 1e-11 * max(1.0, abs(ref["L"]).max())
     assert np.abs(K @ out[1][3] - b).max() <= 1e-8 * max(1.0, np.abs(out[1][3]).max())
+
+
+# ---- the plan handle's memory, inertia rule and permutes: small block-tridiagonal KKT patterns, the multifrontal phase and the column method -----------------------
+PLAN_METHODS = {"nested_dissection": "multifrontal", "rcm": "columns_lds_accumulator"}
+
+
+def _plan_pattern(seed=31):
+    """a 6-stage trajectory KKT matrix (n = 51, more than one front) and triu of it in CSC order"""
+    K = staged_kkt(6, 3, 2, np.random.default_rng(seed))
+    A = sp.triu(K).tocsc(); A.sort_indices()
+    return K, A
+
+
+def _reference_inertia(D):
+    """compute_inertia! as QDLDL leaves D: stop at the first exact zero pivot, the rest counts as zeros (qdldl.jl:444,456,579)"""
+    n, zero = len(D), np.flatnonzero(D == 0.0)
+    k = int(zero[0]) if len(zero) else n
+    head = D[:k]
+    return (-1 if k < n else int((head > 0.0).sum()), int((head <= 0.0).sum()) + n - k, n - k)
+
+
+@pytest.mark.parametrize("method", list(PLAN_METHODS))
+def test_inertia_of_a_mixed_batch_is_the_reference_rule_on_D(method):
+    """a quasi-definite matrix, one with an exact zero pivot at the first eliminated column, one with an exact zero pivot in the middle of the order (row and column
+    of that vertex hold explicit zeros: whatever is subtracted from its diagonal is 0) and a negative-definite one, on one pattern: every inertia triple and the
+    zero-pivot warning are the rule applied to the D that get_factor returns for the instance — at batch 4 and at batch 130, beyond the slot table of a group"""
+    pkg = load_pkg()
+    K, A = _plan_pattern()
+    n = K.shape[0]
+    S = pkg.SparseLDL(A, method=method)
+    assert S.info["numeric"] == PLAN_METHODS[method]
+    assert S.factorize(A) == 0 and S.inertia == (33, 18, 0)
+    perm = S.factor()[0]
+    rows, cols = A.indices, np.repeat(np.arange(n), np.diff(A.indptr))
+
+    def zero_pivot_at(k):
+        v, vals = int(perm[k]) - 1, A.data.copy()
+        vals[(rows == v) | (cols == v)] = 0.0
+        return vals
+    negative = np.where(rows == cols, -float(n), 0.1 * A.data / np.abs(A.data).max())
+    four = np.stack([A.data, zero_pivot_at(0), zero_pivot_at(n // 2), negative])
+    expect_first_zero = [n, 0, n // 2, n]
+    for batch in (4, 130):
+        S.set_batch(batch)
+        assert S.factorize(four[np.arange(batch) % 4]) == 1
+        assert S.inertia_all.shape == (batch, 3)
+        for z in range(batch):
+            S.select(z)
+            D = S.factor()[2]
+            zero = np.flatnonzero(D == 0.0)
+            assert (int(zero[0]) if len(zero) else n) == expect_first_zero[z % 4], (z, D)
+            assert tuple(int(v) for v in S.inertia_all[z]) == _reference_inertia(D), (z, S.inertia_all[z], D)
+        assert tuple(S.inertia_all[3]) == (0, n, 0)
+    S.set_batch(2)
+    assert S.factorize(four[[0, 3]]) == 0 and S.inertia_all.tolist() == [[33, 18, 0], [0, n, 0]]          # no zero pivot: no warning
+    S.close()
+
+
+def _plan_stage(S, vals, rhs, device):
+    """factorize (unless vals is None) and solve; rhs: (batch, nrhs, n).  Returns (inertia triples, solutions (batch, nrhs, n), every instance's L values and D)"""
+    batch, nrhs, n = rhs.shape
+    if device:
+        if vals is not None:
+            S.factorize_device(torch.from_numpy(vals).to("cuda:0"))
+        X = S.solve_device(torch.from_numpy(rhs).to("cuda:0"))
+        torch.cuda.synchronize()
+        X = X.cpu().numpy()
+    else:
+        if vals is not None:
+            S.factorize(vals)
+        X = S.solve(rhs[0].T if batch == 1 else np.transpose(rhs, (0, 2, 1)))
+        X = X.T[None] if batch == 1 else np.transpose(X, (0, 2, 1))
+    factors = []
+    for z in range(batch):
+        S.select(z)
+        _, Lm, D = S.factor()
+        factors += [Lm.toarray(), D]
+    return [np.array(S.inertia_all), np.ascontiguousarray(X)] + factors
+
+
+@pytest.mark.parametrize("device", [False, True], ids=["host", "device"])
+@pytest.mark.parametrize("method", list(PLAN_METHODS))
+def test_growth_and_shrink_of_the_plan_leave_no_trace(method, device):
+    """one handle through batch 1 / one right-hand side, batch 5 / seven, batch 2 / one, then three right-hand sides on the same factors: after every stage the inertia,
+    the factors and the solutions are the bits of a fresh handle that was given that stage alone — whatever grew, shrank or was kept between the stages"""
+    if device and torch is None:
+        pytest.skip("torch not installed")
+    pkg = load_pkg()
+    K, A = _plan_pattern()
+    n = K.shape[0]
+    rng = np.random.default_rng(37)
+    vals = A.data[None, :] * (1.0 + 0.1 * rng.random((5, A.nnz)))
+    rhs = rng.standard_normal((5, 7, n))
+    S = pkg.SparseLDL(A, method=method)
+    assert S.info["numeric"] == PLAN_METHODS[method]
+    for batch, nrhs, refactor in [(1, 1, True), (5, 7, True), (2, 1, True), (2, 3, False)]:
+        if refactor and batch != getattr(S, "batch", 1):
+            S.set_batch(batch)
+        b = np.ascontiguousarray(rhs[:batch, :nrhs])
+        got = _plan_stage(S, vals[:batch] if refactor else None, b, device)
+        F = pkg.SparseLDL(A, method=method)
+        if batch > 1:
+            F.set_batch(batch)
+        want = _plan_stage(F, vals[:batch], b, device)
+        F.close()
+        assert len(got) == len(want) == 2 + 2 * batch
+        for k, (g, w) in enumerate(zip(got, want)):
+            assert np.array_equal(g, w), (batch, nrhs, k)
+        for z in range(batch):                                                                                   # ... and they are solutions
+            Uz = sp.csc_matrix((vals[z], A.indices, A.indptr), shape=A.shape)
+            Kz = Uz + sp.triu(Uz, 1).T
+            assert np.abs(Kz @ got[1][z].T - b[z].T).max() <= 1e-9 * max(1.0, np.abs(got[1][z]).max())
+    S.close()
+
+
+@pytest.mark.parametrize("method", list(PLAN_METHODS))
+def test_right_hand_sides_of_a_batch_are_solved_as_single_columns(method):
+    """five right-hand sides for each of three matrices in one call (columns with a leading dimension through the permutes and the sweeps) have the bits of the
+    fifteen one-column solves of a handle that holds the matching matrix alone"""
+    pkg = load_pkg()
+    K, A = _plan_pattern()
+    n = K.shape[0]
+    rng = np.random.default_rng(41)
+    vals = A.data[None, :] * (1.0 + 0.1 * rng.random((3, A.nnz)))
+    rhs = rng.standard_normal((3, n, 5))
+    S = pkg.SparseLDL(A, method=method)
+    assert S.info["numeric"] == PLAN_METHODS[method]
+    S.set_batch(3)
+    assert S.factorize(vals) == 0
+    X = S.solve(rhs)
+    assert X.shape == (3, n, 5)
+    S.close()
+    one = pkg.SparseLDL(A, method=method)
+    for z in range(3):
+        assert one.factorize(vals[z]) == 0
+        for j in range(5):
+            assert np.array_equal(one.solve(rhs[z, :, j]), X[z, :, j]), (z, j)
+    one.close()

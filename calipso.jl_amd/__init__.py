@@ -13,7 +13,7 @@ import numpy as np
 from ._lib import CALLBACK_FN, EVAL_FN, CalipsoHipError, lib
 from ._marshal import QP_NAMES, pack_cotangent, qp_names, qp_shapes, unpack_columns
 
-__all__ = ["Solver", "Group", "LDLSolver", "SmallBatch", "SparseKKT", "SparseKKTGroup", "SparseConicQP", "Comm", "ordering", "symbolic", "Options", "initialize_b", "solve_b", "CalipsoHipError", "FLAGS", "splitmix_uniform",
+__all__ = ["Solver", "Group", "LDLSolver", "SmallBatch", "SparseKKT", "SparseKKTGroup", "SparseConicQP", "SparseConicQPGroup", "Comm", "ordering", "symbolic", "Options", "initialize_b", "solve_b", "CalipsoHipError", "FLAGS", "splitmix_uniform",
            "mfma_f64_peak"]
 
 # evaluate! flags (include/calipso_hip.h)
@@ -1536,6 +1536,101 @@ class SparseKKTGroup(_Handle):
         ms = np.zeros(8)
         self._check(self._L.calipso_hip_sparse_kkt_group_timing(self._h, _pd(ms)), "sparse_kkt_group_timing")
         return dict(inertia_correction=float(ms[0]), solve=float(ms[1]), refinement=float(ms[2]), wall=float(ms[5]), device=float(ms[6]))
+
+    # ---- solve! of every member in lockstep (include/calipso_hip.h, "solve! on sparse data, for GROUPS"; csrc/sparse_solve_group.hip) ----
+    SOLVE_REPORT = REPORT + ("ticks", "outer_update_rounds", "line_search_trial_rounds", "solve_host_waits", "solve_launches", "vector_ms", "search_direction_ms", "solve_wall_ms")
+
+    def attach_qp(self, q, b, h, objective_constants=None):
+        """the vectors of every member's conic QP besides Lxx, gx, hx (set_values): q (members x nx), b (members x ne), h (members x nc) — (members, count) arrays or
+        sequences of `members` vectors — and one objective constant per member (host values).  Host arrays or — all three — float64 CUDA tensors"""
+        counts = (self.nx, self.ne, self.nc)
+        const = None if objective_constants is None else np.ascontiguousarray(np.broadcast_to(np.asarray(objective_constants, dtype=np.float64).reshape(-1), (self.members,)))
+        if all(self._is_device(a) for a in (q, b, h)):
+            ptrs = [self._device_pointer(a, nm, ct) for a, nm, ct in zip((q, b, h), ("q", "b", "h"), counts)]
+            self._check(self._L.calipso_hip_sparse_kkt_group_qp_attach_device(self._h, *(ptrs + [_opt(const)])), "sparse_kkt_group_qp_attach_device")
+            return
+        arrs = [self._host(a, nm, ct, "attach_qp") for a, nm, ct in zip((q, b, h), ("q", "b", "h"), counts)]
+        self._check(self._L.calipso_hip_sparse_kkt_group_qp_attach(self._h, *[_opt(a) for a in arrs + [const]]), "sparse_kkt_group_qp_attach")
+
+    def initialize(self, x0):
+        """initialize!(solver, x0) of every member: x0 (members x nx) — a host array, or a CUDA tensor"""
+        if self._is_device(x0):
+            self._check(self._L.calipso_hip_sparse_kkt_group_initialize_device(self._h, self._device_pointer(x0, "x0", self.nx)), "sparse_kkt_group_initialize_device")
+        else:
+            self._check(self._L.calipso_hip_sparse_kkt_group_initialize(self._h, _opt(self._host(x0, "x0", self.nx, "initialize"))), "sparse_kkt_group_initialize")
+
+    def solve(self):
+        """solve! of every member in lockstep: (statuses (per member: 1 solved, 0 iteration caps, -102 a refinement failure without continue_after_refinement_failure
+        — the point is the last accepted iterate —, -1 / -2 the reference's inertia / cone search error()s), infos (a dict per member, SparseKKT.SOLVE_INFO),
+        report (dict of SOLVE_REPORT)).  .status is the worst member status; refused arguments raise.  Member m's results are bit for bit SparseKKT.solve's."""
+        status, info, report = np.zeros(self.members, dtype=np.int32), np.zeros(16 * self.members), np.zeros(16)
+        rc = self._L.calipso_hip_sparse_kkt_group_solve(self._h, status.ctypes.data_as(C.POINTER(C.c_int32)), _pd(info), _pd(report))
+        if rc < 0 and not any(int(v) == rc for v in status):         # (a member's error status is that member's: the others went on)
+            self._check(rc, "solve! (group)")
+        self.status = int(rc)
+        infos = []
+        for m in range(self.members):
+            out = dict(zip(SparseKKT.SOLVE_INFO, (float(v) for v in info[16 * m:16 * m + 16])))
+            for k in SparseKKT.SOLVE_INFO[:9] + ("status",):
+                out[k] = int(out[k])
+            infos.append(out)
+        rep = dict(zip(self.SOLVE_REPORT, (float(v) for v in report)))
+        for k in self.SOLVE_REPORT:
+            if not k.endswith("_ms"):
+                rep[k] = int(rep[k])
+        self.solve_info, self.solve_report = infos, rep
+        return [int(v) for v in status], infos, rep
+
+    def get(self, name, member):
+        """a resident vector of `member` by SparseKKT's names (SparseKKT.VECTORS)"""
+        out = np.zeros(getattr(self, SparseKKT.VECTORS[name]) if name in SparseKKT.VECTORS else 0)
+        self._check(self._L.calipso_hip_sparse_kkt_group_get(self._h, name.encode(), int(member), _pd(out), out.size), "sparse_kkt_group_get(%s)" % name)
+        return out
+
+    def solution_device(self):
+        """the members' resident points as a CUDA tensor of its own (members x N)"""
+        import torch
+        p = C.c_void_p()
+        self._check(self._L.calipso_hip_sparse_kkt_group_solution_device(self._h, C.byref(p)), "sparse_kkt_group_solution_device")
+
+        class View:      # (the CUDA array interface: torch wraps the device memory without a copy)
+            __cuda_array_interface__ = dict(shape=(self.members, self.N), typestr="<f8", data=(p.value, False), version=2)
+        return torch.as_tensor(View(), device=torch.device("cuda", self.device)).clone()
+
+    def keep_trace(self, rows):
+        self._check(self._L.calipso_hip_sparse_kkt_group_keep_trace(self._h, int(rows)), "sparse_kkt_group_keep_trace")
+        self._trace_rows = int(rows)
+
+    def trace(self, member):
+        """solution.all after each accepted iterate of `member` in the last solve (the first keep_trace rows of them)"""
+        cap = getattr(self, "_trace_rows", 0)
+        out, accepted = np.zeros((max(cap, 1), self.N)), C.c_int64()
+        rows = self._check(self._L.calipso_hip_sparse_kkt_group_trace(self._h, int(member), _pd(out), cap, C.byref(accepted)), "sparse_kkt_group_trace")
+        return out[:rows]
+
+
+def SparseConicQPGroup(problems, n_nonnegative=None, second_order_dims=(), objective_scale=0.5, **kw):
+    """a list of (P, q, A, b, G, h) — min c x'Px + q'x  s.t.  Ax - b = 0,  h - Gx in K per member, as SparseConicQP takes them — as a SparseKKTGroup ready for
+    initialize / solve: Lxx = c (P + P'), gx = A, hx = -G as CSC, every member's values and q, b, h resident.  Every member must have the first one's patterns:
+    another pattern is refused with a message naming the member.  **kw goes to SparseKKTGroup"""
+    import scipy.sparse as sp
+    mats, vecs = [], []
+    for m, (P, q, A, b, G, h) in enumerate(problems):
+        P, A, G = (sp.csc_matrix(M) for M in (P, A, G))
+        trio = [sp.csc_matrix(objective_scale * (P + P.T)), sp.csc_matrix(A), sp.csc_matrix(-G)]
+        for M in trio:
+            M.sort_indices()
+        if mats:
+            for name, M, first in zip(("P + P'", "A", "G"), trio, mats[0]):
+                if M.shape != first.shape or not np.array_equal(M.indptr, first.indptr) or not np.array_equal(M.indices, first.indices):
+                    raise CalipsoHipError("SparseConicQPGroup: member %d: the pattern of %s is not member 0's (a group shares one analysis; same-pattern problems only)" % (m, name))
+        mats.append(trio); vecs.append((q, b, h))
+    if not mats:
+        raise CalipsoHipError("SparseConicQPGroup: no members")
+    g = SparseKKTGroup(mats[0][0], mats[0][1], mats[0][2], len(mats), n_nonnegative=n_nonnegative, second_order_dims=second_order_dims, **kw)
+    g.set_values([t[0] for t in mats], [t[1] for t in mats], [t[2] for t in mats])
+    g.attach_qp([v[0] for v in vecs], [v[1] for v in vecs], [v[2] for v in vecs])
+    return g
 
 
 def SparseConicQP(P, q, A, b, G, h, n_nonnegative=None, second_order_dims=(), objective_scale=0.5, **kw):

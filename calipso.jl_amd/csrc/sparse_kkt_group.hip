@@ -16,46 +16,24 @@
 #include <string>
 #include <vector>
 
-#include "sparse_kkt_handle.hpp"
+#include "sparse_kkt_group_handle.hpp"     // the group handle, Strides, member_data: shared with sparse_solve_group.hip
 #include "sparse_kkt_kernels.hpp"
-#include "sparse_kkt_group.hpp"
 
 using calipso::Batch;
 using calipso::i64;
 using namespace calipso::sparse_kkt;
 namespace grp = calipso::sparse_kkt_group;
+using grp::GH;
+using grp::Strides;
+using grp::member_data;
 static_assert(grp::MAX_MEMBERS == calipso::MAX_BATCH, "a group is a batch of the multifrontal plan");
 static_assert(grp::STATUS_OK == CALIPSO_OK && grp::STATUS_REFINEMENT == CALIPSO_WARN_REFINEMENT && grp::STATUS_INERTIA == CALIPSO_ERR_INERTIA && grp::REFUSED == CALIPSO_ERR_ARGUMENT, "statuses");
-
-struct calipso_hip_sparse_kkt_group {
-    KH* base = nullptr;                        // the analysis, the plan, its stream, the tables on the device, the owner of every allocation here, the error text
-    int members = 0;
-    grp::Layout lay;
-    double* slab = nullptr;                    // lay.doubles
-    double* K = nullptr; long long strideK = 0;      // the plan's own values: member m's K at K + m * strideK
-    long long* inertia = nullptr;              // members x 3 on the device
-    grp::Lockstep ls;                          // the shared options and every member's scalars, phase and counts
-    bool have[5] = {false, false, false, false, false};
-    bool assembled = false, factored = false;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    double ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    int launches_factor = 0, launches_solve = 0;     // of one batched factorisation / solve of the plan (per level of its schedule; the two permutations)
-    std::vector<int64_t> inertia_host;
-    std::vector<double> norm_host;
-};
-typedef calipso_hip_sparse_kkt_group GH;
 
 namespace {
 
 // ---- the group kernels: blockIdx.z = place in the active list ---------------------------------------------------------------------------------------------------
 struct Active { int n; int member[calipso::MAX_BATCH]; double ep[calipso::MAX_BATCH], ed[calipso::MAX_BATCH]; };      // members walk different regularisations
-struct Strides { long long L, g, h, N, n, K; };
 
-__device__ __forceinline__ KktDev member_data(const KktDev& d, const Strides& s, int m) {
-    KktDev r = d;
-    r.Lxx += (size_t)m * s.L; r.gx += (size_t)m * s.g; r.hx += (size_t)m * s.h; r.w += (size_t)m * s.N; r.rho += m;
-    return r;
-}
 __device__ __forceinline__ Sink member_sink(const Sink& k, const Strides& s, int m) {
     const size_t o = (size_t)m * s.N;
     return Sink{k.out ? k.out + o : nullptr, k.res ? k.res + o : nullptr, k.err ? k.err + o : nullptr, k.norm ? k.norm + m : nullptr};
@@ -162,15 +140,15 @@ void enqueue_mul(GH* g, const std::vector<int>& members, const double* V, const 
 
 #define GK(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return gfail(g, CALIPSO_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); } while (0)
 
-// search_direction! for every member on device vectors (members x N each)
-int search_direction(GH* g, const double* res, double* step, double* regularization, double* info, int32_t* status, double* report) {
+// search_direction! for the members `who` on device vectors (members x N each); the others are left as they are
+int search_direction(GH* g, const std::vector<int>& who, const double* res, double* step, double* regularization, double* info, int32_t* status, double* report) {
     const auto wall0 = std::chrono::steady_clock::now();
     KH* s = g->base;
     const KktDev& d = s->d;
     grp::Lockstep& ls = g->ls;
     int waits = 0, launches = 0;
     for (double& m : g->ms) m = 0.0;
-    ls.begin(regularization);
+    ls.begin(regularization, who);
     GK(hipEventRecord(g->ev[0], s->st));
     // inertia_correction! (inertia.jl:30-80): a round per retry of the slowest member
     for (;;) {
@@ -208,12 +186,12 @@ int search_direction(GH* g, const double* res, double* step, double* regularizat
     for (int k = 0; k < 3; ++k) GK(hipEventElapsedTime(&t[k], g->ev[k], g->ev[k + 1]));
     g->ms[0] = t[0]; g->ms[1] = t[1]; g->ms[2] = t[2]; g->ms[6] = (double)t[0] + t[1] + t[2];
     g->ms[5] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
-    ls.outputs(regularization, info, status);
+    ls.outputs(regularization, info, status, who);
     if (report) {
         report[grp::R_FACTOR_ROUNDS] = ls.factor_rounds; report[grp::R_REFINE_ROUNDS] = ls.refine_rounds; report[grp::R_HOST_WAITS] = waits; report[grp::R_LAUNCHES] = launches;
         report[grp::R_DEVICE_MS] = g->ms[6]; report[grp::R_WALL_MS] = g->ms[5]; report[grp::R_LAST_FACTOR_ACTIVE] = ls.last_factor_active; report[grp::R_LAST_REFINE_ACTIVE] = ls.last_refine_active;
     }
-    const int worst = ls.worst();
+    const int worst = ls.worst(who);
     if (worst == CALIPSO_ERR_INERTIA) {
         std::string who;
         for (int k : ls.in_phase(grp::FAILED_INERTIA)) who += (who.empty() ? "" : ", ") + std::to_string(k);
@@ -247,12 +225,12 @@ int search_direction_entry(GH* g, const char* entry, const double* residual, dou
     GK(hipSetDevice(s->device));
     DEVPTR(residual); DEVPTR(step);
     if (const int rc = values_missing(g, entry); rc < 0) return rc;
-    if (device) return search_direction(g, residual, step, regularization, info, status, report);
+    if (device) return search_direction(g, everyone(g), residual, step, regularization, info, status, report);
     const size_t N = (size_t)s->d.N, bytes = sizeof(double) * N * (size_t)g->members;
     double* res = arr(g, grp::A_RES); double* stp = arr(g, grp::A_STEP);
     GK(hipMemcpyAsync(res, residual, bytes, hipMemcpyHostToDevice, s->st));
     GK(hipMemcpyAsync(stp, step, bytes, hipMemcpyHostToDevice, s->st));          // a member whose inertia correction fails keeps the caller's step
-    const int rc = search_direction(g, res, stp, regularization, info, status, report);
+    const int rc = search_direction(g, everyone(g), res, stp, regularization, info, status, report);
     if (rc < 0 && rc != CALIPSO_ERR_INERTIA) return rc;
     GK(hipMemcpyAsync(step, stp, bytes, hipMemcpyDeviceToHost, s->st));
     GK(hipStreamSynchronize(s->st));
@@ -260,6 +238,14 @@ int search_direction_entry(GH* g, const char* entry, const double* residual, dou
 }
 
 }  // namespace
+
+// what sparse_solve_group.hip calls here (sparse_kkt_group_handle.hpp)
+int grp::group_fail(GH* g, int rc, const std::string& text) { return gfail(g, rc, text); }
+double* grp::group_array(GH* g, grp::Array a) { return arr(g, a); }
+Strides grp::group_strides(const GH* g) { return strides(g); }
+int grp::group_search_direction(GH* g, const std::vector<int>& members, const double* res, double* step, double* regularization, double* info, int32_t* status, double* report) {
+    return search_direction(g, members, res, step, regularization, info, status, report);
+}
 
 extern "C" {
 
@@ -271,6 +257,7 @@ int32_t calipso_hip_sparse_kkt_group_destroy(calipso_hip_sparse_kkt_group* g) {
         (void)hipSetDevice(g->base->device);
         if (g->base->st) (void)hipStreamSynchronize(g->base->st);
         for (hipEvent_t e : g->ev) if (e) (void)hipEventDestroy(e);
+        grp::group_solve_release(g);
         (void)calipso_hip_sparse_kkt_destroy(g->base);      // the tables, the slab, the plan
     }
     delete g;
@@ -345,6 +332,7 @@ int32_t calipso_hip_sparse_kkt_group_set_option(calipso_hip_sparse_kkt_group* g,
     if (std::string(name) == "krylov_fallback") return CALIPSO_OK;                                          // (0: what a group does anyway)
     if (calipso::set_search_direction_option(g->ls.opt, name, value)) return CALIPSO_OK;
     if (std::string(name) == "central_path") { for (grp::Member& q : g->ls.m) q.sc.kappa = value; return CALIPSO_OK; }      // every member's; set_values takes one per member
+    { const int rc = grp::group_solve_set_option(g, name, value); if (rc != 0) return rc < 0 ? rc : CALIPSO_OK; }         // what solve! reads besides (sparse_solve_group.hip)
     return gfail(g, CALIPSO_ERR_ARGUMENT, std::string(entry) + ": unknown option " + name);
 }
 

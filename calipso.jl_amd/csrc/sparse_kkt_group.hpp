@@ -83,15 +83,20 @@ struct Lockstep {
     std::vector<int> in_phase(Phase p) const { std::vector<int> out; for (int k = 0; k < members(); ++k) if (m[(size_t)k].phase == p) out.push_back(k); return out; }
 
     // search_direction.jl:1 / inertia.jl:30-41: every member starts IC-1 from the ep_last the caller carries (regularization[3 k + 1])
-    void begin(const double* regularization) {
+    void begin(const double* regularization) { begin(regularization, everyone()); }
+    // ... for a subset `who` of the members (a whole solve! in lockstep steps only those still walking): members outside it stay FINISHED and are not touched,
+    // neither their scalars nor their counts nor their status; regularization is indexed by member all the same
+    void begin(const double* regularization, const std::vector<int>& who) {
         factor_rounds = refine_rounds = last_factor_active = last_refine_active = 0;
-        for (int k = 0; k < members(); ++k) {
+        for (Member& q : m) q.phase = FINISHED;
+        for (int k : who) {
             Member& q = m[(size_t)k];
             q.sc.ep_last = regularization[3 * k + 1];
             ic_begin(opt, q.sc);
             q.phase = WALKING; q.first = true; q.factorizations = q.rounds = 0; q.status = STATUS_OK; q.norm = q.norm0 = 0.0;
         }
     }
+    std::vector<int> everyone() const { std::vector<int> all((size_t)members()); for (int k = 0; k < members(); ++k) all[(size_t)k] = k; return all; }
     // the members a factorisation round assembles and factors
     std::vector<int> walking() const { return in_phase(WALKING); }
     // ... and what their inertias (inertia[3 k ..] of member k: entries of other members are not read) make of them: done and failed members leave the set
@@ -131,14 +136,16 @@ struct Lockstep {
         return round;
     }
     // the worst member status: an inertia failure before a refinement warning before success
-    int worst() const {
+    int worst() const { return worst(everyone()); }
+    int worst(const std::vector<int>& who) const {
         int w = STATUS_OK;
-        for (const Member& q : m) { if (q.status == STATUS_INERTIA) return STATUS_INERTIA; if (q.status == STATUS_REFINEMENT) w = STATUS_REFINEMENT; }
+        for (int k : who) { const Member& q = m[(size_t)k]; if (q.status == STATUS_INERTIA) return STATUS_INERTIA; if (q.status == STATUS_REFINEMENT) w = STATUS_REFINEMENT; }
         return w;
     }
-    // what the entry writes per member: regularization[3], info[4], status
-    void outputs(double* regularization, double* info, int32_t* status) const {
-        for (int k = 0; k < members(); ++k) {
+    // what the entry writes per member (of `who`: the entries of other members are left alone): regularization[3], info[4], status
+    void outputs(double* regularization, double* info, int32_t* status) const { outputs(regularization, info, status, everyone()); }
+    void outputs(double* regularization, double* info, int32_t* status, const std::vector<int>& who) const {
+        for (int k : who) {
             const Member& q = m[(size_t)k];
             regularization[3 * k] = q.sc.ep; regularization[3 * k + 1] = q.sc.ep_last; regularization[3 * k + 2] = q.sc.ed;
             if (info) { info[4 * k] = q.factorizations; info[4 * k + 1] = q.rounds; info[4 * k + 2] = q.norm; info[4 * k + 3] = 0.0; }

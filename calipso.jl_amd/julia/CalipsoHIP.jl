@@ -569,6 +569,38 @@ function group_search_direction_device!(g::SparseKKTGroup, residual::Ptr{Cvoid},
 end
 group_timing(g::SparseKKTGroup) = (ms = zeros(8); group_check(ccall((:calipso_hip_sparse_kkt_group_timing, lib), Int32, (Ptr{Cvoid}, Ptr{Float64}), g.handle, ms), g, "timing"); ms)
 
+# ---- solve! of every member of a group in lockstep (csrc/sparse_solve_group.hip): ccall wrappers, no logic.  Arrays are members x count, member-major; `member` is
+# 0-based, as the C entries take it.  Member m's results are bit for bit those of sparse_solve! on a SparseKKT with the same data and options
+qp_attach!(g::SparseKKTGroup, q::Vector{Float64}, b::Vector{Float64}, h::Vector{Float64}; objective_constants=nothing) = GC.@preserve objective_constants group_check(
+    ccall((:calipso_hip_sparse_kkt_group_qp_attach, lib), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), g.handle, q, b, h, kkt_ptr(objective_constants)),
+    g, "qp_attach!")
+qp_attach_device!(g::SparseKKTGroup, q::Ptr{Cvoid}, b::Ptr{Cvoid}, h::Ptr{Cvoid}; objective_constants=nothing) = GC.@preserve objective_constants group_check(
+    ccall((:calipso_hip_sparse_kkt_group_qp_attach_device, lib), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}), g.handle, q, b, h, kkt_ptr(objective_constants)),
+    g, "qp_attach_device!")
+group_initialize!(g::SparseKKTGroup, x0::Vector{Float64}) = group_check(ccall((:calipso_hip_sparse_kkt_group_initialize, lib), Int32, (Ptr{Cvoid}, Ptr{Float64}), g.handle, x0), g, "initialize!")
+group_initialize_device!(g::SparseKKTGroup, x0::Ptr{Cvoid}) =
+    group_check(ccall((:calipso_hip_sparse_kkt_group_initialize_device, lib), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), g.handle, x0), g, "initialize_device!")
+# returns the worst member status (a member's own error status does not throw: see status), status (per member), info (16 per member), report (16)
+function group_solve!(g::SparseKKTGroup)
+    status, info, report = zeros(Int32, g.members), zeros(16 * g.members), zeros(16)
+    rc = ccall((:calipso_hip_sparse_kkt_group_solve, lib), Int32, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}), g.handle, status, info, report)
+    rc < 0 && !(rc in status) && group_check(rc, g, "solve!")
+    return rc, status, info, report
+end
+group_get!(g::SparseKKTGroup, name::AbstractString, member::Integer, out::Vector{Float64}) =
+    group_check(ccall((:calipso_hip_sparse_kkt_group_get, lib), Int32, (Ptr{Cvoid}, Cstring, Int64, Ptr{Float64}, Int64), g.handle, name, member, out, length(out)), g, "get($name)")
+function group_solution_device(g::SparseKKTGroup)
+    p = Ref{Ptr{Float64}}(C_NULL)
+    group_check(ccall((:calipso_hip_sparse_kkt_group_solution_device, lib), Int32, (Ptr{Cvoid}, Ptr{Ptr{Float64}}), g.handle, p), g, "solution_device")
+    return p[]
+end
+group_keep_trace!(g::SparseKKTGroup, rows::Integer) = group_check(ccall((:calipso_hip_sparse_kkt_group_keep_trace, lib), Int32, (Ptr{Cvoid}, Int64), g.handle, rows), g, "keep_trace!")
+function group_trace!(g::SparseKKTGroup, member::Integer, out::Matrix{Float64})      # out: N x cap_rows (column r = accepted iterate r); returns (rows written, accepted in all)
+    accepted = Ref{Int64}(0)
+    rows = group_check(ccall((:calipso_hip_sparse_kkt_group_trace, lib), Int32, (Ptr{Cvoid}, Int64, Ptr{Float64}, Int64, Ptr{Int64}), g.handle, member, out, size(out, 2), accepted), g, "trace")
+    return rows, accepted[]
+end
+
 # ---- solve! on the same handle (csrc/sparse_solve.hip): the sparse conic QP min c x'Px + q'x  s.t.  Ax - b = 0,  h - Gx in K  with Lxx = c (P + P'), gx = A, hx = -G ----
 # host vectors (nothing keeps what is resident)
 qp_attach!(k::SparseKKT; q=nothing, b=nothing, h=nothing, objective_constant::Real=0.0) = GC.@preserve q b h kkt_check(

@@ -675,6 +675,42 @@ int32_t calipso_hip_sparse_kkt_group_search_direction_device(calipso_hip_sparse_
                                                              int32_t* status, double report[8]);
 int32_t calipso_hip_sparse_kkt_group_timing(calipso_hip_sparse_kkt_group*, double ms[8]);
 
+/* ---- solve! on sparse data, for GROUPS of same-pattern conic QPs in lockstep (csrc/sparse_solve_group.hip; host bookkeeping: csrc/sparse_solve_group.hpp) ----------
+ * A whole solve! (src/solver/solve.jl:8-377) of the sparse conic QP of calipso_hip_sparse_kkt_qp_attach for every member of a group, device-resident.  Member m's
+ * status, counts, scalars, trace and point are, bit for bit, those of calipso_hip_sparse_kkt_solve on the same data with the same options: the kernels call the
+ * single handle's arithmetic (csrc/sparse_solve_kernels.hpp) on the single handle's grid after shifting their pointers by the member's strides.  The members'
+ * kappa, tau, rho and step sizes live in a member-major device array that one stream-ordered copy fills at the head of every read-back group.
+ *   qp_attach       q (members x nx), b (members x ne), hvec (members x nc), member-major, and one objective constant per member (NULL: zeros; a HOST array on both
+ *                   routes).  A NULL array of a non-empty block is CALIPSO_ERR_ARGUMENT naming it.  (_device: q, b, hvec are device pointers.)
+ *   initialize      initialize! (initialize.jl:9-48) of every member: x0 = members x nx
+ *   solve           one tick: every live member is classified from its published prologue (solved members leave with status 1); the members that need an outer
+ *                   update get it in one batch with ONE read-back, and are classified again (a member at its outer cap ends with status 0); the others take one
+ *                   group search_direction restricted to them; a member whose inertia correction fails ends with CALIPSO_ERR_INERTIA, one whose refinement fails
+ *                   with -102 at its last accepted iterate — or, with continue_after_refinement_failure = 1, takes its last refined step; cone masks and the first
+ *                   candidate with ONE read-back (a cone search failure ends that member with CALIPSO_ERR_CONE_SEARCH); while any member's filter or line search
+ *                   rejects, a further candidate for the rejecting members at their own step sizes, ONE read-back per round; accept, trace row and the next
+ *                   prologue with ONE read-back.  A member that has ended is never launched again: its point is its last accepted iterate.  status (members),
+ *                   info (members x 16, per member the layout of calipso_hip_sparse_kkt_solve's info; the three times are the group's).  Returns the worst
+ *                   (smallest) member status.  report[16] = the eight of search_direction summed over the ticks, then ticks, outer-update rounds, line-search
+ *                   trial rounds, host waits (all), launches (all), vector-half device ms, search_direction device ms, wall ms.
+ *   get             a resident vector of `member` by the names of calipso_hip_sparse_kkt_get (the twelve vectors of the solver)
+ *   solution_device the members' points on the device: members x N
+ *   keep_trace      keep the first `rows` accepted iterates of every member;  trace: those of `member` (returns the rows written; *accepted: all it accepted)
+ *   set_option      additionally every option solve! reads (include/calipso_options.hpp: set_solve_option, warmstart among them), penalty (every member's resident
+ *                   scalar), fraction_to_boundary and continue_after_refinement_failure: shared by the group.  As on the single handle, solve starts every member's
+ *                   kappa, tau and rho from the OPTIONS (initialize.jl:38-48: central_path_initial, penalty_initial), so central_path, fraction_to_boundary and
+ *                   penalty act on search_direction and the building blocks only, not on solve.  After solve the members' K and factors are of mixed age (they
+ *                   left at different ticks): the group holds no current factorisation, factorize or search_direction make one. */
+int32_t calipso_hip_sparse_kkt_group_qp_attach(calipso_hip_sparse_kkt_group*, const double* q, const double* b, const double* hvec, const double* objective_constants);
+int32_t calipso_hip_sparse_kkt_group_qp_attach_device(calipso_hip_sparse_kkt_group*, const double* q, const double* b, const double* hvec, const double* objective_constants);
+int32_t calipso_hip_sparse_kkt_group_initialize(calipso_hip_sparse_kkt_group*, const double* x0);
+int32_t calipso_hip_sparse_kkt_group_initialize_device(calipso_hip_sparse_kkt_group*, const double* x0);
+int32_t calipso_hip_sparse_kkt_group_solve(calipso_hip_sparse_kkt_group*, int32_t* status, double* info, double report[16]);
+int32_t calipso_hip_sparse_kkt_group_get(calipso_hip_sparse_kkt_group*, const char* name, int64_t member, double* out, int64_t len);
+int32_t calipso_hip_sparse_kkt_group_solution_device(calipso_hip_sparse_kkt_group*, double** p);
+int32_t calipso_hip_sparse_kkt_group_keep_trace(calipso_hip_sparse_kkt_group*, int64_t rows);
+int32_t calipso_hip_sparse_kkt_group_trace(calipso_hip_sparse_kkt_group*, int64_t member, double* out, int64_t cap_rows, int64_t* accepted);
+
 /* ---- solve! on sparse problem data resident on the device (csrc/sparse_solve.hip; host pieces: csrc/sparse_solve.hpp) --------------------------------------
  * The vector half of a sparse solve! on the same handle, and the whole solve! (src/solver/solve.jl:8-377) for the problem class that needs no user code, the
  * sparse conic QP   min c x'Px + q'x  s.t.  Ax - b = 0,  h - Gx in K   in the handle's terms: Lxx = c (P + P'), gx = A, hx = -G (set_values), and three more
